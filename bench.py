@@ -28,6 +28,8 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0   # MI355X HBM3E spec peak (/opt/skills/guides/MI355X_MICROARCH.md)
 EVENT_EVERY = 4         # the timed steps whose sweep kernel is bracketed by HIP events: every 4th (bench.py: timed loop)
+DUMP_BYTES = 64 << 20   # --dump-outputs: size cap of all files together
+DUMP_SAMPLE = 65536     # --dump-outputs: larger per-pair / per-reference outputs are a fixed, seeded sample of this many entries
 
 WORKLOAD_OF_MODE = {
     1: "score-only sweep (lane-state checkpoints + one maximum per 32-step window) + traceback by window re-sweep "
@@ -65,12 +67,17 @@ def parse_args():
     ap.add_argument("--tfused", type=int, default=None, help="transposed fused kernel (include/swmi.h): -1 automatic, 0 never, 1 every pair that qualifies")
     ap.add_argument("--mode", type=int, default=None, help="kernel pipeline (include/swmi.h): 1 default, 2 event-tracked maxima, 0 HBM direction field")
     ap.add_argument("--opt", action="append", default=[], metavar="NAME=VALUE", help="any swmi_set_option knob, e.g. device_strings=0 (A/B runs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (rank 0) as DIR/<name>.npy, float32/float64, "
+                         "at most %d MB in all: two builds run with the same arguments can be compared output for output" % (DUMP_BYTES >> 20))
     args = ap.parse_args()
     strong = args.scaling == "strong"
     if args.steps is None:
         args.steps = 2 if strong else 50
     if args.warmup is None:
         args.warmup = 1 if strong else 5
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.n_refs is None:
         args.n_refs = 100000 if strong else 1000
     return args
@@ -303,6 +310,9 @@ def main():
     elapsed = float(tmax.item())
 
     # ---- outside the timed region -----------------------------------------------------------------------
+    if args.dump_outputs and rank == 0:
+        # the last timed step ran in slot (steps - 1) % depth; nothing has run that slot since
+        dump_outputs(args.dump_outputs, batch_outputs(batches[(args.steps - 1) % depth], last))
     # (a) the reduce on its own: blocking exchanges of this shard's totals
     reduce_ms = None
     if reducer is not None:
@@ -523,6 +533,13 @@ def strong_scaling(args, world, rank, local_rank, one_gpu, dev):
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     elapsed = float(tmax.item())
 
+    if args.dump_outputs and rank == 0:
+        sel = sample_ids(len(last["totals"]))
+        dump_outputs(args.dump_outputs, {
+            "ref_index": local_ids[sel], "ref_total": last["totals"][sel],
+            "reduce_best": [last["best"]], "reduce_winners": last["winners"],
+            "top_k": np.array(last["top"], dtype=np.int64).reshape(-1, 2), "winner_sites": [last["winner_sites"]]})
+
     # a labelled second figure, outside the timed region: the driver's shortcut.  The reference's driver keeps only the winning
     # references' alignments (Distribution.java:341-353), so a scores-only pass over the shard (option scores_only: the sweep
     # kernels alone) + the full path for the winners (the "winners" part of every step above) gives the same output.
@@ -597,6 +614,57 @@ def strong_scaling(args, world, rank, local_rank, one_gpu, dev):
                             "compared": "per-reference totals over all reads, GPU vs oracle, same run"}
         print(json.dumps(out), flush=True)
     ctx.close()
+
+
+def sample_ids(n):
+    """0 .. n-1, or a fixed, seeded, sorted sample of DUMP_SAMPLE of them (the same for every run with the same n)"""
+    import numpy as np
+    if n <= DUMP_SAMPLE:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(20261015).choice(n, DUMP_SAMPLE, replace=False))
+
+
+def batch_outputs(b, reduced):
+    """What a caller of the weak-scaling step receives from batch b: every pair's score and alignment count, every
+    reference's total, the alignments of every pair (OptAlignments: begin, end cell, both aligned strings) and, with a
+    reduce, its result.  aln_chars holds, per alignment, its aligned reference string and then its aligned read string
+    (aln_len codes each).  Pairs and references beyond DUMP_SAMPLE are sampled; the alignments of the sampled pairs are
+    taken in pair order for as long as they fit in DUMP_BYTES."""
+    import numpy as np
+    pairs, refs = sample_ids(b.n_refs * b.n_reads), sample_ids(b.n_refs)
+    scores, naln = b.pair_results()
+    out = {"pair_index": pairs, "pair_score": scores[pairs], "pair_n_alignments": naln[pairs],
+           "ref_index": refs, "ref_total": b.ref_totals()[refs]}
+    if reduced is not None:
+        out["reduce_best"], out["reduce_winners"] = [reduced[0]], reduced[1]
+    room = DUMP_BYTES - 8 * sum(np.size(v) for v in out.values())
+    cols = {k: [] for k in ("aln_pair", "aln_begin", "aln_end_i", "aln_end_j", "aln_len")}
+    chars = []
+    for p in pairs.tolist():
+        alns = b.alignments(p, with_cell=True)
+        cost = sum(5 * 8 + 2 * 4 * len(r) for _, (r, _q), _c in alns)
+        if cost > room:
+            break
+        room -= cost
+        for begin, (r, q), (ei, ej) in alns:
+            for k, v in zip(cols, (p, begin, ei, ej, len(r))):
+                cols[k].append(v)
+            chars.append(r + q)
+    out.update(cols)
+    out["aln_chars"] = np.frombuffer("".join(chars).encode("latin-1"), dtype=np.uint8).astype(np.float32)
+    return out
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array, float32 kept, everything else as float64 (exact for these integers)"""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float32 if getattr(v, "dtype", None) == np.float32 else np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_BYTES, total
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+    print("bench.py: %d arrays (%.1f MB) written to %s" % (len(arrays), total / 1e6, path), file=sys.stderr, flush=True)
 
 
 def cpu_baseline(refs, reads, gpu_scores, gpu_naln):

@@ -1,7 +1,7 @@
 """Times the sections of bench.py's multi-GPU step loop (run_async / reduce submit / collect / wait) on a one-rank RCCL
 group.  Measured on one MI355X: async 1, submit 34, collect 3, wait 160, totals 6 us = 204 us per step; blocking run 188 us."""
 import os, sys, time
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 os.environ.setdefault("MASTER_ADDR","127.0.0.1"); os.environ.setdefault("MASTER_PORT","29555")
 import numpy as np, torch, torch.distributed as dist
 import sparksmithwaterman_amd as sw

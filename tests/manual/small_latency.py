@@ -2,7 +2,7 @@
 """The per-call floor of a tiny batch (one pair of 80 x 400, EngineerData's smallest point): wall per run and the kernels'
 share of it, for the automatic pipeline, the fused traceback and the resident kernel (no oracle)."""
 import os, sys, time
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import sparksmithwaterman_amd as sw
 REF = "CCTGGGTCCTGCCTCGCATCTGACCAGGGCAGGTGGCCTCCTCATCACACTGCTGCCTCTGCTGTTGGCCCTGCTCATGA"
 READ_80 = "AATTTTAGTCTCTCCCTACCCTTTTGGACAGAGCTTCCTGTCCTCTCATTTCACAGGTTATGCAACAGAGGGTTCTGTGT"

@@ -2,7 +2,7 @@
 """The sweep of 1000 pairs x 2000 bp for a byte alphabet (generic cell stream) and for reads of 60 / 250 rows (R = 1 / 4): wall
 and sweep-kernel time per run, one step at a time (A/B of kernel builds through SWMI_LIB; no oracle)."""
 import os, sys, time, random
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import sparksmithwaterman_amd as sw
 rng = random.Random(3)
 for alpha, m in (("ACGTKMSW", 150), ("ACGTKMSW", 250), ("ACGT", 250), ("ACGT", 60)):

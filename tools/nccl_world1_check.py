@@ -1,7 +1,7 @@
 """Rehearsal of MaxReducer's RCCL path on a ONE-rank nccl group (run on the GPU box): the blocking call, and the
 pipelined submit/collect form bench.py uses, each timed.  Real multi-GPU numbers can only come from an 8-GPU node."""
 import os, sys, time
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 os.environ.setdefault("MASTER_ADDR", "127.0.0.1"); os.environ.setdefault("MASTER_PORT", "29533")
 import torch, torch.distributed as dist
 from sparksmithwaterman_amd import distributed as swd
