@@ -230,12 +230,27 @@ int      swmi_stream_push(swmi_stream *s, const uint8_t *ref_bytes, const uint64
  * threads (0: 6); the file stays mapped until the stream is closed and a reference's bytes are re-read from it when
  * one of its alignment strings is asked for.  One file per stream. */
 int      swmi_stream_push_file(swmi_stream *s, const char *path, const char *delimiter, uint32_t parse_threads);
+/* the same for one rank's share of the file: the records of shard `shard` of `n_shards` by the byte-range rule of
+ * swmi_io_read_refs_shard (swmi_io.h) -- what a driver that partitions ONE reference file over its ranks pushes, as
+ * DistributeReference partitions its reference list over the executors (Distribution.java:329-338).  A shard may hold no
+ * record (the stream then has none); the whole-file checks apply on every shard.  (0, 1) is swmi_stream_push_file. */
+int      swmi_stream_push_file_shard(swmi_stream *s, const char *path, const char *delimiter, uint32_t parse_threads,
+                                     uint32_t shard, uint32_t n_shards);
 int      swmi_stream_finish(swmi_stream *s);                  /* blocks until every chunk is done */
 uint64_t swmi_stream_n_refs(const swmi_stream *s);
 uint32_t swmi_stream_n_chunks(const swmi_stream *s);
 int      swmi_stream_chunk(swmi_stream *s, uint32_t k, swmi_batch **batch, uint64_t *first_ref);
 int      swmi_stream_totals(const swmi_stream *s, int32_t *totals, uint64_t n);   /* MapRef totals of all references */
 int      swmi_stream_metadata(const swmi_stream *s, uint64_t ref, char *buf, size_t cap);
+/* file sources: the byte offset in its file of reference `ref`'s metadata line.  With the file's place in the DirectoryCrawler
+ * walk this is the order in which the control driver meets the reference (Distribution.java:586-613), which OptSeqsComp's stable
+ * sort keeps among equal metadata (:621, :647-666).  SWMI_ERR_INVALID for references pushed from memory. */
+int      swmi_stream_ref_pos(const swmi_stream *s, uint64_t ref, uint64_t *pos);
+/* the sequence bytes of reference `ref` (GetRefSeqs' concatenated lines, InOutOps.java:127-150) into buf, for a driver that aligns
+ * its winning references again after the stream dropped their records (option stream_keep_records = 0): file sources re-read
+ * the one record from the mapped file, memory sources copy the bytes kept at push.  *len always receives the size; buf = NULL
+ * asks for it only; cap < size is SWMI_ERR_RANGE. */
+int      swmi_stream_ref_sequence(const swmi_stream *s, uint64_t ref, uint8_t *buf, uint64_t cap, uint64_t *len);
 int      swmi_stream_get_stats(const swmi_stream *s, swmi_stream_stats *st);
 void     swmi_stream_close(swmi_stream *s);
 

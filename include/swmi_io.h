@@ -31,10 +31,24 @@ int swmi_io_read_reads(const char *path, const char *delimiter, swmi_seqset **ou
  * start with a metadata line is SWMI_ERR_INVALID (the reference dies with a NullPointerException at :148/:153). */
 int swmi_io_read_refs(const char *path, const char *delimiter, swmi_seqset **out);
 
+/* One rank's share of a reference file, for a driver that partitions ONE file over n_shards ranks the way
+ * DistributeReference repartitions its reference list over the executors (src/sw/Distribution.java:329-338).
+ * Shard s owns the records whose metadata line starts in the byte range [floor(n*s/S), floor(n*(s+1)/S)) of the
+ * file (n = its size, S = n_shards), both bounds moved forward to the next metadata line: the shards of a file,
+ * taken in order, are exactly the records swmi_io_read_refs returns, each once, in file order, balanced by bytes
+ * (roughly cells) without any rank reading the whole file.  A shard may hold no record.  The whole-file checks of
+ * swmi_io_read_refs apply on every shard (an empty file, or one not starting with a metadata line, is
+ * SWMI_ERR_INVALID); shard >= n_shards is SWMI_ERR_INVALID.  swmi_stream_push_file_shard (swmi.h) takes the same range. */
+int swmi_io_read_refs_shard(const char *path, const char *delimiter, uint32_t shard, uint32_t n_shards, swmi_seqset **out);
+
 uint32_t        swmi_seqset_count(const swmi_seqset *s);
 const uint8_t  *swmi_seqset_bytes(const swmi_seqset *s);     /* all sequences back to back            */
 const uint64_t *swmi_seqset_offsets(const swmi_seqset *s);   /* count+1 entries, offsets[0] == 0      */
 const char     *swmi_seqset_metadata(const swmi_seqset *s, uint32_t k);   /* refs only; "" for reads  */
+/* refs: count entries, the byte offset in its file of each record's metadata line -- with the file's place in the
+ * DirectoryCrawler walk, the order in which NoDistribution meets the record (Distribution.java:586-613), which OptSeqsComp's
+ * stable sort by metadata keeps among equal metadata lines (:621, :647-666).  NULL for reads and for a set of no record. */
+const uint64_t *swmi_seqset_positions(const swmi_seqset *s);
 void            swmi_seqset_free(swmi_seqset *s);
 
 #ifdef __cplusplus

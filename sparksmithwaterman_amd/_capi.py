@@ -77,12 +77,15 @@ SYMBOLS = [
     ("swmi_stream_open", C.c_int, [_P, C.POINTER(Params), C.c_char_p, _u64p, C.c_uint32, C.c_uint32, C.c_uint64, C.POINTER(_P)]),
     ("swmi_stream_push", C.c_int, [_P, C.c_char_p, _u64p, C.c_uint32]),
     ("swmi_stream_push_file", C.c_int, [_P, C.c_char_p, C.c_char_p, C.c_uint32]),
+    ("swmi_stream_push_file_shard", C.c_int, [_P, C.c_char_p, C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32]),
     ("swmi_stream_finish", C.c_int, [_P]),
     ("swmi_stream_n_refs", C.c_uint64, [_P]),
     ("swmi_stream_n_chunks", C.c_uint32, [_P]),
     ("swmi_stream_chunk", C.c_int, [_P, C.c_uint32, C.POINTER(_P), _u64p]),
     ("swmi_stream_totals", C.c_int, [_P, C.POINTER(C.c_int32), C.c_uint64]),
     ("swmi_stream_metadata", C.c_int, [_P, C.c_uint64, C.c_char_p, C.c_size_t]),
+    ("swmi_stream_ref_pos", C.c_int, [_P, C.c_uint64, _u64p]),
+    ("swmi_stream_ref_sequence", C.c_int, [_P, C.c_uint64, C.c_void_p, C.c_uint64, _u64p]),
     ("swmi_stream_get_stats", C.c_int, [_P, C.POINTER(StreamStats)]),
     ("swmi_stream_close", None, [_P]),
     ("swmi_align_batch", C.c_int, [_P, C.POINTER(Params), C.c_char_p, _u64p, C.c_uint32, C.c_char_p, _u64p,

@@ -243,6 +243,14 @@ class Stream:
         check(self._lib.swmi_stream_push_file(self._h, os.fspath(path).encode(), delimiter.encode("latin-1"), int(parse_threads)))
         return self
 
+    def push_file_shard(self, path, shard, n_shards, delimiter=">gi", parse_threads=0):
+        """shard `shard` of `n_shards` of a FASTA file: the records whose metadata line starts in the shard's byte range
+        (swmi_stream_push_file_shard); (0, 1) is push_file"""
+        import os
+        check(self._lib.swmi_stream_push_file_shard(self._h, os.fspath(path).encode(), delimiter.encode("latin-1"),
+                                                    int(parse_threads), int(shard), int(n_shards)))
+        return self
+
     def finish(self):
         check(self._lib.swmi_stream_finish(self._h))
         return self
@@ -266,13 +274,32 @@ class Stream:
         import numpy as np
         n = self.n_refs()
         out = np.empty(n, dtype=np.int32)
-        check(self._lib.swmi_stream_totals(self._h, out.ctypes.data_as(C.POINTER(C.c_int32)), n))
+        if n:                                       # (a shard may hold no reference)
+            check(self._lib.swmi_stream_totals(self._h, out.ctypes.data_as(C.POINTER(C.c_int32)), n))
         return out
 
+    def ref_pos(self, ref):
+        """byte offset of reference `ref`'s metadata line in its file (file sources)"""
+        v = C.c_uint64()
+        check(self._lib.swmi_stream_ref_pos(self._h, ref, C.byref(v)))
+        return v.value
+
+    def ref_sequence(self, ref):
+        """reference `ref`'s sequence as bytes (re-read from the mapped file for file sources)"""
+        n = C.c_uint64()
+        check(self._lib.swmi_stream_ref_sequence(self._h, ref, None, 0, C.byref(n)))
+        buf = C.create_string_buffer(max(n.value, 1))
+        check(self._lib.swmi_stream_ref_sequence(self._h, ref, buf, n.value, C.byref(n)))
+        return buf.raw[:n.value]
+
     def metadata(self, ref):
-        buf = C.create_string_buffer(4096)
-        check(self._lib.swmi_stream_metadata(self._h, ref, buf, 4096))
-        return buf.value.decode("latin-1")
+        cap = 4096
+        while True:                                 # (the library truncates to the buffer: grow it until the line fits)
+            buf = C.create_string_buffer(cap)
+            check(self._lib.swmi_stream_metadata(self._h, ref, buf, cap))
+            if len(buf.value) < cap - 1:
+                return buf.value.decode("latin-1")
+            cap *= 4
 
     def stats(self):
         st = StreamStats()

@@ -2355,6 +2355,11 @@ extern "C" int swmi_stream_push(swmi_stream *s, const uint8_t *ref_bytes, const 
 }
 
 extern "C" int swmi_stream_push_file(swmi_stream *s, const char *path, const char *delimiter, uint32_t parse_threads) {
+    return swmi_stream_push_file_shard(s, path, delimiter, parse_threads, 0, 1);
+}
+
+extern "C" int swmi_stream_push_file_shard(swmi_stream *s, const char *path, const char *delimiter, uint32_t parse_threads,
+                                           uint32_t shard, uint32_t n_shards) {
     if (!s || !path || !delimiter) return fail(SWMI_ERR_INVALID, "null argument");
     if (s->finished) return fail(SWMI_ERR_INVALID, "the stream is finished");
     if (s->map_p) return fail(SWMI_ERR_UNSUPPORTED, "one file per stream");
@@ -2363,15 +2368,15 @@ extern "C" int swmi_stream_push_file(swmi_stream *s, const char *path, const cha
     if (rc) return rc;
     const uint8_t *p = s->map_p;
     const size_t n = s->map_n;
-    if (n == 0) return fail(SWMI_ERR_INVALID, "reference file has no record: %s", path);                // ref is null at InOutOps.java:153
-    if (swmi_io_next_record(p, n, 0, delimiter) != 0)
-        return fail(SWMI_ERR_INVALID, "reference file does not start with a metadata line: %s", path);  // seq is null at :148
+    // whole-file checks (InOutOps.java:148,153), then this shard's records [lo, hi) (swmi_io.h: swmi_io_read_refs_shard)
+    size_t lo = 0, hi = 0;
+    if ((rc = swmi_io_shard_range(p, n, delimiter, shard, n_shards, path, &lo, &hi))) return rc;
     // segment boundaries: record starts about chunk_bytes apart
-    std::vector<size_t> cut{0};
-    while (cut.back() < n) {
+    std::vector<size_t> cut{lo};
+    while (cut.back() < hi) {
         const size_t want = cut.back() + s->chunk_bytes;
-        size_t nxt = want >= n ? n : swmi_io_next_record(p, n, want, delimiter);
-        if (nxt <= cut.back()) nxt = n;
+        size_t nxt = want >= hi ? hi : swmi_io_next_record(p, n, want, delimiter);
+        if (nxt <= cut.back() || nxt > hi) nxt = hi;
         cut.push_back(nxt);
     }
     const uint32_t n_seg = (uint32_t)(cut.size() - 1);
@@ -2467,6 +2472,49 @@ extern "C" int swmi_stream_metadata(const swmi_stream *s, uint64_t ref, char *bu
         const size_t len = std::min<size_t>(cap - 1, r.meta_len);
         memcpy(buf, b->src_map + r.meta_pos, len);
         buf[len] = 0;
+    }
+    return SWMI_OK;
+}
+
+// the chunk holding streamed reference `ref` and its index within it (the stream must be finished)
+static int stream_locate(const swmi_stream *s, uint64_t ref, const swmi_batch **b, uint32_t *local) {
+    if (!s->finished) return fail(SWMI_ERR_INVALID, "call swmi_stream_finish first");
+    if (ref >= s->first_ref.back()) return fail(SWMI_ERR_RANGE, "reference %llu out of range", (unsigned long long)ref);
+    const size_t k = (size_t)(std::upper_bound(s->first_ref.begin(), s->first_ref.end(), ref) - s->first_ref.begin()) - 1;
+    *b = s->results[k];
+    *local = (uint32_t)(ref - s->first_ref[k]);
+    return SWMI_OK;
+}
+
+extern "C" int swmi_stream_ref_pos(const swmi_stream *s, uint64_t ref, uint64_t *pos) {
+    if (!s || !pos) return fail(SWMI_ERR_INVALID, "null argument");
+    const swmi_batch *b;
+    uint32_t r;
+    int rc = stream_locate(s, ref, &b, &r);
+    if (rc) return rc;
+    if (!b->src_map) return fail(SWMI_ERR_INVALID, "reference %llu was not read from a file", (unsigned long long)ref);
+    *pos = b->src_recs[r].meta_pos;
+    return SWMI_OK;
+}
+
+extern "C" int swmi_stream_ref_sequence(const swmi_stream *s, uint64_t ref, uint8_t *buf, uint64_t cap, uint64_t *len) {
+    if (!s || !len) return fail(SWMI_ERR_INVALID, "null argument");
+    const swmi_batch *b;
+    uint32_t r;
+    int rc = stream_locate(s, ref, &b, &r);
+    if (rc) return rc;
+    const uint64_t n = b->ref_off[r + 1] - b->ref_off[r];
+    *len = n;
+    if (!buf) return SWMI_OK;
+    if (cap < n) return fail(SWMI_ERR_RANGE, "reference %llu has %llu bytes, the buffer %llu", (unsigned long long)ref,
+                             (unsigned long long)n, (unsigned long long)cap);
+    if (b->src_map) {                             // its lines again from the mapped file (GetRefSeqs' rules, InOutOps.java:127-150)
+        std::vector<uint8_t> tmp;
+        swmi_io_read_record(b->src_map, b->src_recs[r], tmp);
+        if (tmp.size() != n) return fail(SWMI_ERR_INVALID, "reference %llu changed in its file", (unsigned long long)ref);
+        if (n) memcpy(buf, tmp.data(), n);
+    } else if (n) {
+        memcpy(buf, b->ref_bytes.data() + b->ref_off[r], n);
     }
     return SWMI_OK;
 }

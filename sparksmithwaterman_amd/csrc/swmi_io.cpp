@@ -16,6 +16,7 @@ struct swmi_seqset {
     std::vector<uint8_t> bytes;
     std::vector<uint64_t> off{0};
     std::vector<std::string> meta;
+    std::vector<uint64_t> pos;      // refs: byte offset of each record's metadata line in its file
 };
 
 extern "C" const char *swmi_last_error(void);
@@ -121,6 +122,7 @@ extern "C" int swmi_io_read_refs(const char *path, const char *delimiter, swmi_s
         if (is_metadata(m.p + b, e - b, delimiter, dlen)) {                                     // :131-145
             if (open_rec) s->off.push_back(s->bytes.size());
             s->meta.emplace_back((const char *)m.p + b, e - b);
+            s->pos.push_back(b);
             open_rec = true;
         } else {
             if (!open_rec)                                                                      // seq is null at :148
@@ -203,6 +205,22 @@ int swmi_io_parse_segment(const uint8_t *p, size_t from, size_t to, const char *
     return SWMI_OK;
 }
 
+// the byte range [*lo, *hi) of shard `shard` of `n_shards` of a mapped reference file: the records whose metadata line starts in
+// [floor(n*shard/n_shards), floor(n*(shard+1)/n_shards)), both bounds moved forward to the next record start.  The shards of a
+// file, in order, are its records each once.  The whole-file checks come first, so every shard of a bad file fails alike.
+int swmi_io_shard_range(const uint8_t *p, size_t n, const char *delim, uint32_t shard, uint32_t n_shards, const char *path,
+                        size_t *lo, size_t *hi) {
+    if (n_shards == 0 || shard >= n_shards) return swmi_io_fail(SWMI_ERR_INVALID, "shard out of range");
+    if (n == 0) return swmi_io_fail(SWMI_ERR_INVALID, std::string("reference file has no record: ") + path);              // InOutOps.java:153
+    if (swmi_io_next_record(p, n, 0, delim) != 0)
+        return swmi_io_fail(SWMI_ERR_INVALID, std::string("reference file does not start with a metadata line: ") + path);  // :148
+    const size_t a = (size_t)((unsigned __int128)n * shard / n_shards);
+    const size_t z = (size_t)((unsigned __int128)n * (shard + 1) / n_shards);
+    *lo = swmi_io_next_record(p, n, a, delim);
+    *hi = swmi_io_next_record(p, n, z, delim);
+    return SWMI_OK;
+}
+
 // the sequence of one record again (for the alignment strings of a streamed reference: the stream keeps no copy of the bytes)
 void swmi_io_read_record(const uint8_t *p, const swmi_io_recpos &r, std::vector<uint8_t> &out) {
     out.clear();
@@ -210,10 +228,35 @@ void swmi_io_read_record(const uint8_t *p, const swmi_io_recpos &r, std::vector<
     while (pos < r.seq_end && next_line(p, r.seq_end, pos, b, e)) out.insert(out.end(), p + b, p + e);
 }
 
+extern "C" int swmi_io_read_refs_shard(const char *path, const char *delimiter, uint32_t shard, uint32_t n_shards,
+                                       swmi_seqset **out) {
+    if (!path || !delimiter || !out) return swmi_io_fail(SWMI_ERR_INVALID, "null argument");
+    *out = nullptr;
+    Mapped m;
+    int rc = map_file(path, m);
+    if (rc) return rc;
+    size_t lo = 0, hi = 0;
+    if ((rc = swmi_io_shard_range(m.p, m.n, delimiter, shard, n_shards, path, &lo, &hi))) return rc;
+    std::unique_ptr<swmi_seqset> s(new swmi_seqset);
+    std::vector<swmi_io_recpos> recs;
+    s->bytes.resize(hi - lo);
+    if ((rc = swmi_io_parse_segment(m.p, lo, hi, delimiter, s->bytes.data(), s->off, recs))) return rc;   // the stream's parser
+    s->bytes.resize(s->off.back());
+    for (const auto &r : recs) {
+        s->meta.emplace_back((const char *)m.p + r.meta_pos, r.meta_len);
+        s->pos.push_back(r.meta_pos);
+    }
+    *out = s.release();
+    return SWMI_OK;
+}
+
 extern "C" uint32_t swmi_seqset_count(const swmi_seqset *s) { return s ? (uint32_t)(s->off.size() - 1) : 0; }
 extern "C" const uint8_t *swmi_seqset_bytes(const swmi_seqset *s) { return s ? s->bytes.data() : nullptr; }
 extern "C" const uint64_t *swmi_seqset_offsets(const swmi_seqset *s) { return s ? s->off.data() : nullptr; }
 extern "C" const char *swmi_seqset_metadata(const swmi_seqset *s, uint32_t k) {
     return (s && k < s->meta.size()) ? s->meta[k].c_str() : "";
+}
+extern "C" const uint64_t *swmi_seqset_positions(const swmi_seqset *s) {
+    return (s && !s->pos.empty()) ? s->pos.data() : nullptr;
 }
 extern "C" void swmi_seqset_free(swmi_seqset *s) { delete s; }

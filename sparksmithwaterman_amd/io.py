@@ -22,10 +22,12 @@ _P = C.c_void_p
 IO_SYMBOLS = [
     ("swmi_io_read_reads", C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(_P)]),
     ("swmi_io_read_refs", C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(_P)]),
+    ("swmi_io_read_refs_shard", C.c_int, [C.c_char_p, C.c_char_p, C.c_uint32, C.c_uint32, C.POINTER(_P)]),
     ("swmi_seqset_count", C.c_uint32, [_P]),
     ("swmi_seqset_bytes", C.POINTER(C.c_uint8), [_P]),
     ("swmi_seqset_offsets", C.POINTER(C.c_uint64), [_P]),
     ("swmi_seqset_metadata", C.c_char_p, [_P, C.c_uint32]),
+    ("swmi_seqset_positions", C.POINTER(C.c_uint64), [_P]),
     ("swmi_seqset_free", None, [_P]),
 ]
 _bound = False
@@ -56,6 +58,8 @@ class SeqSet:
             self.blob = C.string_at(lib.swmi_seqset_bytes(handle), total) if total else b""
             self.metadata = ([lib.swmi_seqset_metadata(handle, k).decode("latin-1") for k in range(n)]
                              if with_meta else [""] * n)
+            pos = lib.swmi_seqset_positions(handle) if with_meta else None
+            self.positions = [pos[k] for k in range(n)] if pos else []    # refs: byte offset of each metadata line
         finally:
             lib.swmi_seqset_free(handle)
 
@@ -79,6 +83,14 @@ def read_reads_packed(file, delimiter=DELIMITER):
 def read_refs_packed(file, delimiter=DELIMITER):
     h = _P()
     _capi.check(_lib().swmi_io_read_refs(_path(file), delimiter.encode("latin-1"), C.byref(h)))
+    return SeqSet(h, True)
+
+
+def read_refs_shard_packed(file, delimiter=DELIMITER, shard=0, n_shards=1):
+    """Shard `shard` of `n_shards` of a reference file (swmi_io_read_refs_shard: the records whose metadata line starts in the
+    shard's byte range); the shards in order are read_refs_packed's records, each once."""
+    h = _P()
+    _capi.check(_lib().swmi_io_read_refs_shard(_path(file), delimiter.encode("latin-1"), int(shard), int(n_shards), C.byref(h)))
     return SeqSet(h, True)
 
 

@@ -17,7 +17,8 @@ import time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
-def write_fasta(path, refs, width=80):
+def write_fasta(path, refs, width=80, first=0):
+    """refs (bytes) as ">gi|ref<first + k>" records of `width`-character lines"""
     import numpy as np
     t0 = time.perf_counter()
     with open(path, "wb") as f:
@@ -29,7 +30,7 @@ def write_fasta(path, refs, width=80):
             body = a[:full * width].reshape(full, width)
             lines = np.concatenate([body, np.full((full, 1), 10, dtype=np.uint8)], axis=1).tobytes()
             tail = a[full * width:].tobytes()
-            buf.append(b">gi|ref%d\n" % k)
+            buf.append(b">gi|ref%d\n" % (first + k))
             buf.append(lines)
             if tail:
                 buf.append(tail + b"\n")
