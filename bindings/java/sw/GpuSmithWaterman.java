@@ -32,6 +32,8 @@ public class GpuSmithWaterman
 	static native void nativeDestroy( long ctx ) ;
 	static native long nativeAlignBatch( long ctx , int match , int mismatch , int gap , int tieMode , byte[] types ,
 			ByteBuffer refBytes , long[] refOff , int nRefs , ByteBuffer readBytes , long[] readOff , int nReads ) ;
+	/** affine gaps on the context: alignScores { match , mismatch , gap , gapOpen } -- a gap of length k costs gapOpen + k * gap */
+	static native void nativeSetGapOpen( long ctx , int gapOpen ) ;
 	static native void nativeFreeBatch( long ctx , long batch ) ;
 	static native int nativeRefTotal( long batch , int ref ) ;
 	static native long nativeRefSiteCount( long batch , int ref ) ;
@@ -139,6 +141,9 @@ public class GpuSmithWaterman
 			byte[] types = { (byte)ty[0] , (byte)ty[1] , (byte)ty[2] , (byte)ty[3] } ;
 
 			long ctx = context() ;
+			// alignScores may carry a fourth entry, gapOpen (<= 0): affine gaps; three entries keep the linear scoring
+			if( sc.length != 3 && sc.length != 4 ) throw new IllegalArgumentException( "alignScores needs 3 or 4 entries: " + sc.length ) ;
+			nativeSetGapOpen( ctx , sc.length == 4 ? sc[3] : 0 ) ;
 			long batch = nativeAlignBatch( ctx , sc[0] , sc[1] , sc[2] , TIE_SERIAL , types , refBuf , refOff , n , readBuf , readOff , reads.size() ) ;
 			try
 			{

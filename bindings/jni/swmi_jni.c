@@ -42,6 +42,13 @@ JNIEXPORT void JNICALL Java_sw_GpuSmithWaterman_nativeDestroy(JNIEnv *env, jclas
     swmi_destroy((swmi_ctx *)(intptr_t)ctx);
 }
 
+/* affine gaps on this context from now on: a gap of length k costs gapOpen + k * gap (0: linear) */
+JNIEXPORT void JNICALL Java_sw_GpuSmithWaterman_nativeSetGapOpen(JNIEnv *env, jclass cls, jlong ctx, jint gapOpen) {
+    char err[640];
+    (void)cls;
+    if (swmi_shim_set_gap_open((swmi_ctx *)(intptr_t)ctx, gapOpen, err, sizeof err) != SWMI_OK) throw_msg(env, err);
+}
+
 /* refBytes/readBytes: direct ByteBuffers of ISO-8859-1 bytes; refOff/readOff: long[n+1] */
 JNIEXPORT jlong JNICALL Java_sw_GpuSmithWaterman_nativeAlignBatch(
         JNIEnv *env, jclass cls, jlong ctx, jint match, jint mismatch, jint gap, jint tieMode, jbyteArray types,

@@ -22,6 +22,15 @@ static int check_side(const char *what, const void *bytes, int64_t cap, const in
     return SWMI_OK;
 }
 
+int swmi_shim_set_gap_open(swmi_ctx *ctx, int32_t gap_open, char *err, size_t err_len) {
+    int rc;
+    if (!ctx) return shim_fail(SWMI_ERR_INVALID, err, err_len, "nativeSetGapOpen", "context handle is 0");
+    if (gap_open > 0) return shim_fail(SWMI_ERR_INVALID, err, err_len, "nativeSetGapOpen", "gapOpen must be <= 0");
+    if ((rc = swmi_set_option(ctx, "gap_open", gap_open)) != SWMI_OK)
+        return shim_fail(rc, err, err_len, "nativeSetGapOpen", swmi_last_error());
+    return SWMI_OK;
+}
+
 int swmi_shim_align_batch(swmi_ctx *ctx, int32_t match, int32_t mismatch, int32_t gap, int32_t tie_mode,
                           const signed char *types, size_t types_len,
                           const void *ref_bytes, int64_t ref_cap, const int64_t *ref_off, int32_t n_refs,

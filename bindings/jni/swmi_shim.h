@@ -26,6 +26,10 @@ int swmi_shim_align_batch(swmi_ctx *ctx, int32_t match, int32_t mismatch, int32_
                           const void *read_bytes, int64_t read_cap, const int64_t *read_off, int32_t n_reads,
                           swmi_batch **out, char *err, size_t err_len);
 
+/* nativeSetGapOpen: affine gaps on this context (swmi_set_option "gap_open"): a gap of length k then costs gap_open + k * gap.
+ * gap_open <= 0; 0 (the default) is the linear scoring.  Applies to the batches the context aligns from then on. */
+int swmi_shim_set_gap_open(swmi_ctx *ctx, int32_t gap_open, char *err, size_t err_len);
+
 /* nativeRefTotal / nativeRefSiteCount / nativeRefSite */
 int swmi_shim_ref_total(const swmi_batch *b, int32_t ref, int32_t *total, char *err, size_t err_len);
 int swmi_shim_ref_site_count(swmi_batch *b, int32_t ref, int64_t *n, char *err, size_t err_len);

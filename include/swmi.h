@@ -115,6 +115,13 @@ void        swmi_default_params(swmi_params *p);
  * stream_keep_records (default 1): 0 = a stream drops every chunk's alignment records once its scores, counts and totals are
  *                taken -- for a driver that reduces to the winning references and aligns those again (Distribution.java:341-353
  *                discards every other reference's alignments too); the alignment accessors of such chunks fail.
+ * gap_open (default 0, must be <= 0, else SWMI_ERR_INVALID): affine gaps -- a gap of length k costs gap_open + k * gap (gap is then the
+ *                per-base extension).  A run with gap_open != 0 takes the affine kernels (swmi_affine.hip; swmi_batch_mode = 3): the Gotoh
+ *                recurrence with the same tie chains, maximum cells and walk order as the linear path.  Bounds:
+ *                gap <= 0, |match|, |mismatch|, |gap|, |gap_open| <= 2^20, reads of at most 1024 bases; outside them the run returns
+ *                SWMI_ERR_UNSUPPORTED before anything is launched.  scores_only, device_strings, zero_copy, cell_cap, max_workspace_bytes,
+ *                arena_words_per_pair and profiling apply to affine runs; mode, tb_split, resident, tfused, col_chunks and debug_* do not.
+ * affine: -1 (default) the affine kernels only when gap_open != 0; 1 always, also at gap_open = 0 (where they give the linear results).
  * Further knobs: spin_us (how long a run polls its stream before it blocks, default 2000); col_chunks (0 automatic,
  * 1 never, N > 1 force up to N column chunks per pair: a launch of few pairs with long references is swept by several
  * wavefronts per pair -- a read of more than 256 rows by several strip pipelines); debug_strip_spins / debug_reverse_strips (tests of the strip pipeline's give-up path). */
@@ -151,7 +158,7 @@ typedef struct swmi_timing {
     uint32_t tfused_pairs;      /* pairs swept in the transposed layout and traced back by the same wavefront        */
 } swmi_timing;
 int  swmi_batch_timing(const swmi_batch *b, swmi_timing *t);
-/* The kernel pipeline (0, 1 or 2, see swmi_set_option "mode") the last run of the batch used. */
+/* The kernel pipeline (0, 1 or 2, see swmi_set_option "mode"; 3: the affine kernels, option "gap_open") the last run of the batch used. */
 int  swmi_batch_mode(const swmi_batch *b, int *mode);
 
 /* ---- results of the last run (host memory owned by the batch) ------------------- */

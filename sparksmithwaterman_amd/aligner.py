@@ -30,9 +30,11 @@ class Context:
         check(self._lib.swmi_create(int(device), C.byref(h)))
         self._h = h
         self.device = int(device)
+        self.options = {}                   # what set_option() last set, by name
 
     def set_option(self, name, value):
         check(self._lib.swmi_set_option(self._h, name.encode(), int(value)))
+        self.options[name] = int(value)
 
     def upload(self, refs, reads):
         """Sequences -> HBM.  refs/reads: lists of str or bytes."""

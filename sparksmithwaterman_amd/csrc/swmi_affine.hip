@@ -1,0 +1,340 @@
+// swmi_affine.hip -- gfx950 kernels of the affine-gap (Gotoh) path: a gap of length k costs gap_open + k * gap.
+//
+// Recurrence (DESIGN.md "Affine gaps"; i = read row, j = reference column; o = gap_open <= 0, e = gap <= 0):
+//   E(i,j) = max(H(i,j-1) + o + e, E(i,j-1) + e)     deletion state,  xE = 1 iff the extension is strictly better
+//   F(i,j) = max(H(i-1,j) + o + e, F(i-1,j) + e)     insertion state, xF likewise
+//   H(i,j) = max(0, E, F, H(i-1,j-1) + s(i,j)) with the linear path's tie chains (serial '>=' a > i > d, strict '>' d > i > a)
+// E and F are clamped at 0: only positive values ever reach H, the direction or a walked x bit, so no -inf sentinel is needed.
+//
+// sw_affine_sweep_kernel: ONE WAVEFRONT PER PAIR, the anti-diagonal systolic mapping of the linear sweep.
+//   Lane l owns R = ceil(m / 64) consecutive read rows (R = 1..16, m <= 1024) and at step t works on column j = t - l + 1.
+//   H and E of its rows stay in registers; H and F of its last row, and the reference base, pass to lane l+1 by DPP
+//   (wave_shr:1).  Every cell leaves a 4-bit code in the pair's direction field:
+//     bits 0-1  what H(i,j) came from: 0 = H is 0 (the walk stops), 1 = diagonal, 2 = F (insertion), 3 = E (deletion)
+//     bit 2     xE(i,j)        bit 3  xF(i,j)
+//   8 anti-diagonal steps per dword, laid out [block w][row slot k][lane]: dword (w * R + k) * 64 + lane holds steps
+//   t = 8w .. 8w+7 of row i = l * R + k + 1, step t at bits 4 * (t % 8).  Every store writes 256 contiguous bytes.
+//   The pair's maximum and its tied cells are tracked as in the linear sweep: a wave-uniform threshold, a cell list capped
+//   at cell_cap (more: SWMI_F_CELL_OVF, the host re-runs the pair with an exact-size list).
+//
+// sw_affine_traceback_kernel: one wavefront per (pair, slot); slot s walks the pair's maximum cells s, s + S, ...  The walk
+//   is the three-state machine of DESIGN.md "Affine gaps"; the field is staged in LDS a tile of consecutive 8-step blocks at a
+//   time (a path never moves to a later step), the ops are packed 16 per dword in LDS, and the record goes out through
+//   swmi_emit.h with rank SWMI_RANK_BY_CELL (the host orders a pair's records by cell).
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "swmi_device.h"
+#include "swmi_emit.h"
+
+#define WAVE 64
+#define AFF_WAVES 4                    // wavefronts (= pairs) per workgroup of the sweep
+#define BALLOT(pred) __builtin_amdgcn_ballot_w64(pred)
+#define WAVE_SYNC() do { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); } while (0)
+
+// direction codes of the field (bits 0-1)
+#define AFF_STOP 0u
+#define AFF_DIAG 1u
+#define AFF_INS  2u
+#define AFF_DEL  3u
+
+namespace {
+
+// v_mov_b32_dpp wave_shr:1 : lane l receives lane l-1's value, lane 0 keeps `old`
+__device__ __forceinline__ int aff_shr1(int old, int src) {
+    return __builtin_amdgcn_update_dpp(old, src, 0x138 /*wave_shr:1*/, 0xf, 0xf, false);
+}
+// same, lane 0 receives 0 (row 0 of the matrix: H = 0, F clamped to 0)
+__device__ __forceinline__ int aff_shr1_zero(int src) {
+    return __builtin_amdgcn_update_dpp(0, src, 0x138 /*wave_shr:1*/, 0xf, 0xf, true);
+}
+__device__ __forceinline__ uint32_t uni(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+__device__ __forceinline__ uint32_t lanes_below(uint64_t mask) {
+    return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+}
+
+template <int R>
+struct AffState {
+    int h[R], e[R];        // H and E of the lane's rows at its previous column
+    int q[R];              // the rows' base codes (SWMI_CODE_PAD past the read)
+    uint32_t acc[R];       // codes of the current 8-step block
+    int rb;                // reference base code of the lane's current column
+    int nh_prev;           // lane l-1's last-row H one step ago: the diagonal of row 0
+    int f_last;            // F of the lane's last row at its previous column (what lane l+1 reads as F(i-1, j))
+    int thr;               // wave-uniform running maximum (starts at 1: a maximum of 0 is the degenerate case)
+    uint32_t cnt;          // wave-uniform number of cells equal to thr
+};
+
+// 8 anti-diagonal steps t0 .. t0+7 (a lane outside its column range keeps its state).  The steps are a loop, not unrolled:
+// eight copies of R cells let the scheduler hoist the compares of many cells at once, and their masks spilled the SGPRs.
+template <int R, bool STRICT>
+__device__ __forceinline__ void aff_block8(AffState<R> &S, const uint2 rw, const uint32_t t0, const uint32_t lane,
+                                           const uint32_t n, const uint32_t row0, const uint32_t vrows,
+                                           const int o, const int e, const int vmat, const int vmis,
+                                           uint2 *__restrict__ cells, const uint32_t ccap) {
+    const int oe = o + e;
+#pragma unroll 1
+    for (uint32_t s = 0; s < 8; ++s) {
+        const uint32_t wsel = s < 4 ? rw.x : rw.y;
+        const int feed = (int)((wsel >> (8u * (s & 3u))) & 0xFFu);
+        S.rb = aff_shr1(feed, S.rb);
+        const int nh = aff_shr1_zero(S.h[R - 1]);
+        const int nf = aff_shr1_zero(S.f_last);
+        const uint32_t c0 = t0 + s - lane;                       // column index j - 1 of this lane
+        const bool inr = c0 < n;
+        int mrow = -1;
+        if (inr) {
+            int diag = S.nh_prev, up = nh, fup = nf;
+            uint32_t sh = 4u * s;
+#pragma unroll
+            for (int k = 0; k < R; ++k) {
+                const int left = S.h[k];
+                const int dg = diag + (S.rb == S.q[k] ? vmat : vmis);
+                const int t1 = left + oe, t2 = S.e[k] + e;
+                const int en = max(max(t1, t2), 0);
+                const int u1 = up + oe, u2 = fup + e;
+                const int fn = max(max(u1, u2), 0);
+                const int hv = max(max(en, fn), dg);             // en, fn >= 0: hv >= 0
+                uint32_t d;
+                if (STRICT) d = hv == 0 ? AFF_STOP : (en == hv ? AFF_DEL : (fn == hv ? AFF_INS : AFF_DIAG));
+                else        d = hv == 0 ? AFF_STOP : (dg == hv ? AFF_DIAG : (fn == hv ? AFF_INS : AFF_DEL));
+                // x bits from the sign of the difference (no compare mask): |values| < 2^30 + 2^21, the difference fits
+                const uint32_t code = d | (((uint32_t)(t1 - t2) >> 31) << 2) | (((uint32_t)(u1 - u2) >> 31) << 3);
+                S.acc[k] |= code << sh;
+                diag = left;
+                up = hv;
+                fup = fn;
+                S.h[k] = hv;
+                S.e[k] = en;
+                if ((uint32_t)k < vrows) mrow = max(mrow, hv);
+            }
+            S.f_last = fup;
+        }
+        S.nh_prev = nh;
+        // tied maxima (SmithWaterman.java:176-185): the wave leaves the step only when some lane reached the threshold
+        if (BALLOT(mrow >= S.thr) != 0ull) {
+            uint64_t gt = BALLOT(mrow > S.thr);
+            if (gt) {
+                while (gt) {
+                    S.thr = __builtin_amdgcn_readlane(mrow, (int)__builtin_ctzll(gt));
+                    gt = BALLOT(mrow > S.thr);
+                }
+                S.cnt = 0;
+            }
+#pragma unroll
+            for (int k = 0; k < R; ++k) {
+                const bool hit = inr && (uint32_t)k < vrows && S.h[k] == S.thr;
+                const uint64_t hm = BALLOT(hit);
+                if (hm) {
+                    const uint32_t pos = S.cnt + lanes_below(hm);
+                    if (hit && pos < ccap) cells[pos] = make_uint2(row0 + (uint32_t)k + 1u, c0 + 1u);
+                    S.cnt += (uint32_t)__popcll(hm);
+                }
+            }
+        }
+    }
+}
+
+template <int R, bool STRICT>
+__device__ __forceinline__ void aff_sweep_pair(const FillArgs &A, const int o, const PairDesc pd, const uint32_t lane) {
+    const SeqDesc rd = A.refs[pd.ref_id];
+    const SeqDesc qd = A.reads[pd.read_id];
+    const uint32_t n = rd.len, m = qd.len;
+    const uint32_t *__restrict__ refw = A.seqw + rd.boff;
+    const uint32_t *__restrict__ readw = A.seqw + qd.boff;
+    uint32_t *__restrict__ dir = A.dir + pd.dir_off;
+    const uint32_t W = swmi_aff_blocks(m, n);
+    const uint32_t row0 = lane * R;
+    const uint32_t vrows = row0 >= m ? 0u : (m - row0 < (uint32_t)R ? m - row0 : (uint32_t)R);
+    const uint64_t cbase = A.cells_off ? A.cells_off[pd.out_id] : (uint64_t)pd.out_id * A.cell_cap;
+    const uint32_t ccap = A.cells_cap ? A.cells_cap[pd.out_id] : A.cell_cap;
+    uint2 *__restrict__ cells = A.cells + cbase;
+
+    AffState<R> S;
+#pragma unroll
+    for (int k = 0; k < R; ++k) {
+        const uint32_t row = row0 + (uint32_t)k;
+        S.q[k] = row < m ? (int)((readw[row >> 2] >> (8u * (row & 3u))) & 0xFFu) : (int)SWMI_CODE_PAD;
+        S.h[k] = 0;
+        S.e[k] = 0;
+    }
+    S.rb = 0; S.nh_prev = 0; S.f_last = 0;
+    S.thr = 1; S.cnt = 0;
+    for (uint32_t w = 0; w < W; ++w) {
+        const uint32_t t0 = 8u * w;
+        // lane 0's 8 reference bases (images are padded: the last block may read past the end)
+        const uint2 rw = *reinterpret_cast<const uint2 *>(refw + (t0 >> 2));
+#pragma unroll
+        for (int k = 0; k < R; ++k) S.acc[k] = 0u;
+        aff_block8<R, STRICT>(S, rw, t0, lane, n, row0, vrows, o, A.gap, A.match, A.mismatch, cells, ccap);
+        uint32_t *__restrict__ dst = dir + (uint64_t)w * R * WAVE + lane;
+#pragma unroll
+        for (int k = 0; k < R; ++k) dst[k * WAVE] = S.acc[k];
+    }
+    if (lane == 0) {
+        PairOut po;
+        if (S.cnt == 0u) {                                       // maximum 0: every one of the m*n cells ties (SmithWaterman.java:154)
+            po.score = 0;
+            po.flags = SWMI_F_DEGENERATE;
+            po.n_cells = (uint64_t)m * n;
+        } else {
+            po.score = S.thr;
+            po.flags = S.cnt > ccap ? SWMI_F_CELL_OVF : 0u;
+            po.n_cells = S.cnt;
+        }
+        A.out[pd.out_id] = po;
+    }
+}
+
+// RLO..RHI: the rows per lane this instantiation of the kernel takes (the others' registers would cap its occupancy)
+template <int RLO, int RHI, bool STRICT>
+__device__ __forceinline__ void aff_sweep_dispatch(const FillArgs &A, const int o, const PairDesc pd, const uint32_t R, const uint32_t lane) {
+    if constexpr (RLO <= RHI) {
+        if (R == (uint32_t)RLO) aff_sweep_pair<RLO, STRICT>(A, o, pd, lane);
+        else aff_sweep_dispatch<RLO + 1, RHI, STRICT>(A, o, pd, R, lane);
+    }
+}
+
+template <int RLO, int RHI>
+__device__ __forceinline__ void aff_sweep_entry(const FillArgs &A, const int o) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) A.hdr->reserved = 0ull;      // the traceback's bump allocator
+    const uint32_t pair = blockIdx.x * AFF_WAVES + (threadIdx.x >> 6);
+    if (pair >= A.n_pairs) return;
+    const uint32_t lane = threadIdx.x & 63u;
+    const PairDesc pd = A.pairs[pair];
+    const uint32_t R = uni(swmi_aff_rows_per_lane(A.reads[pd.read_id].len));
+    if (R < (uint32_t)RLO || R > (uint32_t)RHI) return;
+    if (A.strict) aff_sweep_dispatch<RLO, RHI, true>(A, o, pd, R, lane);
+    else          aff_sweep_dispatch<RLO, RHI, false>(A, o, pd, R, lane);
+}
+
+}  // namespace
+
+extern "C" __global__ void __launch_bounds__(WAVE * AFF_WAVES) sw_affine_sweep_kernel(const FillArgs A, const int gap_open) {
+    aff_sweep_entry<1, 4>(A, gap_open);
+}
+extern "C" __global__ void __launch_bounds__(WAVE * AFF_WAVES) sw_affine_sweep_wide_kernel(const FillArgs A, const int gap_open) {
+    aff_sweep_entry<5, SWMI_AFF_RMAX>(A, gap_open);
+}
+
+// ------------------------------------------------------------------------------------------------
+// traceback
+// ------------------------------------------------------------------------------------------------
+// LDS of one wavefront: [tile_words] direction tile | [ops_words] ops, 16 per dword | [SWMI_EMIT_SCRATCH_WORDS] string scratch
+extern "C" __global__ void __launch_bounds__(WAVE) sw_affine_traceback_kernel(const TraceArgs A, const uint32_t tile_words,
+                                                                               const uint32_t ops_words) {
+    extern __shared__ uint32_t lds[];
+    const uint32_t lane = threadIdx.x;
+    const uint32_t slot = blockIdx.y, nslots = gridDim.y;
+    const PairDesc pd = A.pairs[blockIdx.x];
+    const PairOut po = A.out[pd.out_id];
+    if (A.out_host && slot == 0 && lane == 0) A.out_host[pd.out_id] = po;      // result straight into pinned host memory
+    if (po.flags & (SWMI_F_DEGENERATE | SWMI_F_CELL_OVF)) return;
+    if (po.n_cells <= slot) return;
+    uint32_t *tile = lds;
+    uint32_t *ops = lds + tile_words;
+    uint32_t *scratch = ops + ops_words;
+    const SeqDesc rd = A.refs[pd.ref_id];
+    const SeqDesc qd = A.reads[pd.read_id];
+    const uint32_t n = rd.len, m = qd.len;
+    const uint32_t R = uni(swmi_aff_rows_per_lane(m));
+    const uint32_t W = uni(swmi_aff_blocks(m, n));
+    const uint32_t blk_words = R * WAVE;                          // dwords of one 8-step block
+    const uint32_t NB = tile_words / blk_words;                   // blocks per tile (>= 1: the host sizes the tile)
+    const uint32_t max_ops = ops_words * 16u;
+    const uint32_t *__restrict__ dir = A.dir + pd.dir_off;
+    const uint8_t *__restrict__ raw_ref = A.raw ? A.raw + A.raw_off[pd.ref_id] : nullptr;
+    const uint8_t *__restrict__ raw_read = A.raw ? A.raw + A.raw_off[A.raw_reads_at + pd.read_id] : nullptr;
+    const uint64_t cbase = A.cells_off ? A.cells_off[pd.out_id] : (uint64_t)pd.out_id * A.cell_cap;
+    const uint2 *__restrict__ cells = A.cells + cbase;
+    const uint32_t ncell = (uint32_t)po.n_cells;
+    uint32_t wlo = 0xFFFFFFFFu, whi = 0u;                         // blocks [wlo, whi) are in the tile
+
+    for (uint32_t c = slot; c < ncell; c += nslots) {
+        const uint32_t ci = uni(cells[c].x), cj = uni(cells[c].y);
+        uint32_t i = ci, j = cj;
+        uint32_t l = (i - 1u) / R, k = (i - 1u) - l * R;          // lane and row slot of row i
+        uint32_t st = 0u;                                         // 0: H, else the state entered (AFF_DIAG / AFF_INS / AFF_DEL)
+        uint32_t n_ops = 0, cur = 0;
+        int begin = 0;
+        bool ok = true;
+        while (i != 0u && j != 0u) {
+            const uint32_t t = j - 1u + l, w = t >> 3;
+            if (w < wlo || w >= whi) {                            // stage the tile that ends at this block
+                if (w >= W) { ok = false; break; }                // (a corrupted list: never walks off the field)
+                WAVE_SYNC();
+                wlo = w + 1u >= NB ? w + 1u - NB : 0u;
+                whi = w + 1u;
+                const uint32_t *__restrict__ src = dir + (uint64_t)wlo * blk_words;
+                const uint32_t words = (whi - wlo) * blk_words;
+                for (uint32_t x = lane; x < words; x += WAVE) tile[x] = src[x];
+                WAVE_SYNC();
+            }
+            const uint32_t code = uni((tile[((w - wlo) * R + k) * WAVE + l] >> (4u * (t & 7u))) & 15u);
+            if (st == 0u) {
+                st = code & 3u;
+                if (st == AFF_STOP) break;                        // H(i, j) == 0: `while (score > 0)` (SmithWaterman.java:380)
+            }
+            if (n_ops >= max_ops) { ok = false; break; }
+            begin = (int)j;
+            uint32_t op;
+            if (st == AFF_DIAG) {
+                op = SWMI_DIR_A;
+                st = 0u;
+                --i; --j;
+            } else if (st == AFF_INS) {
+                op = SWMI_DIR_I;
+                st = (code & 8u) ? AFF_INS : 0u;
+                --i;
+            } else {
+                op = SWMI_DIR_D;
+                st = (code & 4u) ? AFF_DEL : 0u;
+                --j;
+            }
+            if (op != SWMI_DIR_D) { if (k == 0u) { k = R - 1u; --l; } else --k; }
+            cur |= op << (2u * (n_ops & 15u));
+            ++n_ops;
+            if ((n_ops & 15u) == 0u) { if (lane == 0) ops[(n_ops >> 4) - 1u] = cur; cur = 0u; }
+        }
+        if ((n_ops & 15u) != 0u && lane == 0) ops[n_ops >> 4] = cur;
+        WAVE_SYNC();
+        const bool strings = A.raw != nullptr;
+        const uint32_t words = swmi_payload_words(n_ops, strings);
+        unsigned long long off;
+        uint32_t rslot;
+        if (ok && swmi_reserve(A, lane, words, 1u, off, rslot)) {
+            uint32_t *dst = A.arena + off;
+            if (lane == 0) swmi_write_rec(A, rslot, pd.out_id, SWMI_RANK_BY_CELL, begin, ci, cj, n_ops, off);
+            if (strings) swmi_emit_strings(dst, SwmiOpsPacked{ops}, n_ops, ci, cj, raw_ref, raw_read, lane, scratch);
+            else for (uint32_t x = lane; x < words; x += WAVE) dst[x] = ops[x];
+        } else if (lane == 0) {
+            atomicOr(&A.out[pd.out_id].flags, SWMI_F_ARENA_OVF);
+            if (A.ovf_host) *A.ovf_host = 1u;
+        }
+        WAVE_SYNC();
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// host-callable launchers
+// ------------------------------------------------------------------------------------------------
+// r_min / r_max: the rows per lane of the launch's shortest and longest read (only the kernels that have pairs are launched)
+extern "C" hipError_t swmi_launch_affine_sweep(const FillArgs *a, int32_t gap_open, uint32_t r_min, uint32_t r_max, hipStream_t st) {
+    if (a->n_pairs == 0) return hipSuccess;
+    const dim3 grid((a->n_pairs + AFF_WAVES - 1) / AFF_WAVES), block(WAVE * AFF_WAVES);
+    if (r_min <= 4u) hipLaunchKernelGGL(sw_affine_sweep_kernel, grid, block, 0, st, *a, (int)gap_open);
+    if (r_max >= 5u) hipLaunchKernelGGL(sw_affine_sweep_wide_kernel, grid, block, 0, st, *a, (int)gap_open);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t swmi_launch_affine_traceback(const TraceArgs *a, uint32_t tile_words, uint32_t ops_words, hipStream_t st) {
+    if (a->n_pairs == 0) return hipSuccess;
+    static const bool attrs = [] {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(sw_affine_traceback_kernel),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        return true;
+    }();
+    (void)attrs;
+    const size_t lds = ((size_t)tile_words + ops_words + SWMI_EMIT_SCRATCH_WORDS) * sizeof(uint32_t);
+    hipLaunchKernelGGL(sw_affine_traceback_kernel, dim3(a->n_pairs, SWMI_AFF_TB_SLOTS), dim3(WAVE), lds, st, *a, tile_words, ops_words);
+    return hipGetLastError();
+}

@@ -35,6 +35,8 @@ extern "C" hipError_t swmi_launch_traceback(const TraceArgs *a, hipStream_t st, 
 extern "C" hipError_t swmi_launch_traceback_split(const TraceArgs *a, uint32_t n_windows, hipStream_t st);
 extern "C" hipError_t swmi_launch_resident(const TraceArgs *a, const ResidentArgs *x, hipStream_t st);
 extern "C" hipError_t swmi_launch_tfused(const TraceArgs *a, const TFusedArgs *x, hipStream_t st);
+extern "C" hipError_t swmi_launch_affine_sweep(const FillArgs *a, int32_t gap_open, uint32_t r_min, uint32_t r_max, hipStream_t st);
+extern "C" hipError_t swmi_launch_affine_traceback(const TraceArgs *a, uint32_t tile_words, uint32_t ops_words, hipStream_t st);
 extern "C" hipError_t swmi_launch_encode(const uint8_t *raw, const uint64_t *raw_off, SeqDesc *desc, uint32_t *seqw,
                                          const uint8_t *lut, uint32_t n_seq, hipStream_t st);
 
@@ -147,6 +149,8 @@ struct swmi_ctx {
                                             // that only needs totals and re-aligns its few winners, Distribution.java:341-353)
     int device_strings = 1;                 // the traceback kernels write both aligned strings behind every record (swmi_emit.h); 0: 2-bit ops only, strings built by the host
     bool cell_cap_set = false;              // cell_cap given by the caller (otherwise small launches get longer lists)
+    int32_t gap_open = 0;                   // affine gaps: a gap of length k costs gap_open + k * gap (0: linear)
+    int affine = -1;                        // -1: the affine kernels (mode 3) when gap_open != 0; 1: always
     // swmi_batch_run_async: one run in flight on the context's own host thread
     std::thread worker;
     std::mutex job_mu;
@@ -215,7 +219,8 @@ struct swmi_batch {
     std::vector<Work> work;                 // schedule (pairs sorted by work), valid for work_mode
     int work_mode = -1;
     bool work_tfused = false;               // the schedule's workspace sizes leave room for sw_tfused_kernel's column checkpoints
-    uint32_t eff_mode = 1;                  // pipeline of the current run
+    uint32_t eff_mode = 1;                  // pipeline of the current run (3: the affine kernels, swmi_affine.hip)
+    int32_t gap_open = 0;                   // the context's gap_open when the run started (mode 3)
     uint64_t work_cells = 0;
     std::vector<uint8_t> pairs_on_device;   // image of the PairDesc array currently in d_pairs
     const void *pairs_dev_ptr = nullptr;
@@ -235,6 +240,7 @@ struct swmi_batch {
         uint32_t res_lds_words = 0, res_ops_words = 0;
         int resident_opt = -1;
         int tfused_opt = -1;
+        uint32_t aff_r_min = 0, aff_r_max = 0;      // mode 3: rows per lane of the chunk's shortest and longest read
         size_t n_tf = 0;
         uint32_t tf_max_m = 0, tf_max_n = 0, tf_max_path = 0;
         bool exact = false, scores_only = false;
@@ -399,6 +405,13 @@ extern "C" int swmi_set_option(swmi_ctx *ctx, const char *name, int64_t value) {
     } else if (!strcmp(name, "profiling")) {
         if (value < 0 || value > 2) return fail(SWMI_ERR_INVALID, "profiling must be 0, 1 (every stage) or 2 (the sweep only)");
         ctx->profiling = (int)value;
+    } else if (!strcmp(name, "gap_open")) {
+        if (value > 0) return fail(SWMI_ERR_INVALID, "gap_open must be <= 0 (a penalty), got %lld", (long long)value);
+        if (value < INT32_MIN) return fail(SWMI_ERR_INVALID, "gap_open out of range");
+        ctx->gap_open = (int32_t)value;
+    } else if (!strcmp(name, "affine")) {
+        if (value != -1 && value != 1) return fail(SWMI_ERR_INVALID, "affine must be -1 (when gap_open != 0) or 1 (always)");
+        ctx->affine = (int)value;
     } else if (!strcmp(name, "arena_words_per_pair")) {
         if (value < 1) return fail(SWMI_ERR_INVALID, "arena_words_per_pair out of range");
         ctx->arena_words_per_pair = (uint64_t)value;
@@ -629,6 +642,7 @@ static int prepare_chunk(RunState &rs, const std::vector<Work> &work, size_t lo,
     std::vector<uint32_t> tf_items;          // pairs handled whole by sw_tfused_kernel (transposed sweep + traceback)
     size_t n_tf = 0;
     uint32_t tf_max_m = 0, tf_max_n = 0, tf_max_path = 0;
+    uint32_t aff_r_min = 0xFFFFFFFFu, aff_r_max = 0;
     const uint32_t res_cell_cap = SWMI_RES_CELL_CAP;
     swmi_batch::Prep &pr = b->prep;
     const auto p0 = std::chrono::steady_clock::now();
@@ -643,6 +657,7 @@ static int prepare_chunk(RunState &rs, const std::vector<Work> &work, size_t lo,
         seam_priv_words = pr.seam_priv_words; n_strip_chunks = pr.n_strip_chunks;
         n_res = pr.n_res; res_lds_words = pr.res_lds_words; res_ops_words = pr.res_ops_words;
         n_tf = pr.n_tf; tf_max_m = pr.tf_max_m; tf_max_n = pr.tf_max_n; tf_max_path = pr.tf_max_path;
+        aff_r_min = pr.aff_r_min; aff_r_max = pr.aff_r_max;
     } else {
     // Column chunks (swmi_device.h: ColItem): a launch of few pairs leaves most of the 1024 SIMDs idle while every pair is
     // one dependent chain of n + 63 steps.  A positive-score path spans at most m + match*m/|gap| columns (A <= m
@@ -802,6 +817,8 @@ static int prepare_chunk(RunState &rs, const std::vector<Work> &work, size_t lo,
         if (m_ != pb_m || n_ != pb_n) { pb_m = m_; pb_n = n_; pb_val = (uint32_t)path_bound(n_, m_, b->params); }   // (runs of equal lengths)
         max_path = std::max<uint32_t>(max_path, pb_val);
         max_read = std::max(max_read, m_);
+        aff_r_min = std::min(aff_r_min, swmi_aff_rows_per_lane(m_));
+        aff_r_max = std::max(aff_r_max, swmi_aff_rows_per_lane(m_));
     }
     n_strip_items = strip_items.size();
     n_col_items = col_items.size();
@@ -884,6 +901,7 @@ static int prepare_chunk(RunState &rs, const std::vector<Work> &work, size_t lo,
         pr.tfused_opt = ctx->tfused; pr.n_tf = n_tf; pr.tf_max_m = tf_max_m; pr.tf_max_n = tf_max_n; pr.tf_max_path = tf_max_path;
         pr.col_chunks_opt = ctx->col_chunks; pr.reverse_strips = ctx->dbg_reverse_strips != 0;
         pr.scores_only = ctx->scores_only != 0;
+        pr.aff_r_min = aff_r_min; pr.aff_r_max = aff_r_max;
     }
     rs.prep_us += std::chrono::duration<double, std::micro>(p1 - p0).count();
     rs.prep_upload_us += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - p1).count();
@@ -1055,7 +1073,9 @@ static int run_chunk(RunState &rs, const std::vector<Work> &work, size_t lo, siz
     {
         // the traceback stages one alignment's ops and the read per walker (4 per workgroup) next to its direction tiles:
         // 160 KB of LDS per workgroup bound the longest pair (m + n of about 16 k bases in mode 0, 24 k in modes 1/2)
-        const uint64_t need = traceback_lds_bytes(b->eff_mode, max_path, max_read);
+        // (mode 3: the affine traceback's direction tile, the ops packed 16 per dword and the string scratch)
+        const uint64_t need = b->eff_mode == 3 ? 4ull * (SWMI_AFF_TILE_WORDS + ((uint64_t)max_path + 15) / 16 + 1 + 128)   // (+ SWMI_EMIT_SCRATCH_WORDS, swmi_emit.h)
+                                               : traceback_lds_bytes(b->eff_mode, max_path, max_read);
         if (need > 160ull * 1024)
             return fail(SWMI_ERR_UNSUPPORTED, "a pair of %u bases in total needs %llu bytes of LDS for the traceback (limit 163840)",
                         max_path, (unsigned long long)need);
@@ -1207,7 +1227,8 @@ static int run_chunk(RunState &rs, const std::vector<Work> &work, size_t lo, siz
         if (ctx->profiling && !ext_timing) HIP_TRY(hipEventRecord(ctx->ev[0], ctx->stream));
         if (attempt == 0 && !whole_only) {       // the workspace survives an arena-overflow retry
             if (fa.n_strip_items) HIP_TRY(hipMemsetAsync(fa.progress, 0, (size_t)fa.n_strip_items * sizeof(uint32_t), ctx->stream));
-            HIP_TRY(swmi_launch_fill(&fa, ctx->stream, ext_timing ? ctx->ev[0] : nullptr, ext_timing ? ctx->ev[1] : nullptr));
+            if (b->eff_mode == 3) HIP_TRY(swmi_launch_affine_sweep(&fa, b->gap_open, pr.aff_r_min, pr.aff_r_max, ctx->stream));
+            else HIP_TRY(swmi_launch_fill(&fa, ctx->stream, ext_timing ? ctx->ev[0] : nullptr, ext_timing ? ctx->ev[1] : nullptr));
             rs.launches++;
         }
         if (n_tf) HIP_TRY(swmi_launch_tfused(&ta, &xt, ctx->stream));             // (sweep AND traceback of its pairs: timed with the sweep)
@@ -1232,6 +1253,8 @@ static int run_chunk(RunState &rs, const std::vector<Work> &work, size_t lo, siz
             ta.q_cap = (uint32_t)q_cap;
             if (attempt > 0 || whole_only) HIP_TRY(hipMemsetAsync(ta.q_count, 0, 4, ctx->stream));      // (no sweep kernel ran to zero it)
             HIP_TRY(swmi_launch_traceback_split(&ta, (uint32_t)n_windows, ctx->stream));
+        } else if (b->eff_mode == 3) {
+            HIP_TRY(swmi_launch_affine_traceback(&ta, SWMI_AFF_TILE_WORDS, (uint32_t)(((uint64_t)max_path + 15) / 16 + 1), ctx->stream));
         } else if (n_res + n_tf < np) {
             HIP_TRY(swmi_launch_traceback(&ta, ctx->stream, ext_timing ? ctx->ev[2] : nullptr, ext_timing ? ctx->ev[3] : nullptr));
         }
@@ -1500,6 +1523,20 @@ extern "C" int swmi_batch_run(swmi_ctx *ctx, swmi_batch *b, const swmi_params *p
     if (p->types[0] == p->types[1] || p->types[0] == p->types[2] || p->types[1] == p->types[2])
         return fail(SWMI_ERR_UNSUPPORTED, "alignTypes a/i/d must be pairwise distinct");
     std::lock_guard<std::mutex> g(ctx->mu);
+    const bool affine = ctx->affine == 1 || ctx->gap_open != 0;
+    if (affine) {
+        // the bounds within which every sum of the affine recurrence fits int32 (DESIGN.md "Affine gaps"); checked before
+        // anything is launched
+        const int64_t lim = 1 << 20;
+        if (p->gap > 0)
+            return fail(SWMI_ERR_UNSUPPORTED, "affine gaps need gap <= 0 (the per-base extension), got %d", p->gap);
+        if (std::llabs((int64_t)p->match) > lim || std::llabs((int64_t)p->mismatch) > lim || std::llabs((int64_t)p->gap) > lim ||
+            std::llabs((int64_t)ctx->gap_open) > lim)
+            return fail(SWMI_ERR_UNSUPPORTED, "affine gaps need |match|, |mismatch|, |gap|, |gap_open| <= 2^20");
+        for (uint32_t q = 0; q < b->n_reads; q++)
+            if (b->read_desc[q].len > SWMI_AFF_MAX_READ)
+                return fail(SWMI_ERR_UNSUPPORTED, "affine gaps: read %u has %u bases (at most %u)", q, b->read_desc[q].len, SWMI_AFF_MAX_READ);
+    }
     static const bool host_dbg = getenv("SWMI_DEBUG_HOST") != nullptr;
     auto now = [] { return std::chrono::steady_clock::now(); };
     auto us = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point c) {
@@ -1532,6 +1569,8 @@ extern "C" int swmi_batch_run(swmi_ctx *ctx, swmi_batch *b, const swmi_params *p
     // The schedule only depends on the sequence lengths and the pipeline mode: built once per batch.
     // mode 1 needs pad rows that cannot outgrow the real cells they derive from: mismatch <= 0 and gap <= 0
     b->eff_mode = (ctx->mode == 1 && (p->mismatch > 0 || p->gap > 0)) ? 2u : ctx->mode;
+    b->gap_open = ctx->gap_open;
+    if (affine) b->eff_mode = 3;                         // the affine kernels (swmi_affine.hip): no other pipeline option applies
     // (measured, profiles/r02/sweeps_*.md: with ~5 alignments per pair the split traceback wins up to ~200 pairs; from a
     // few hundred pairs on one workgroup per pair keeps every SIMD busy anyway and its teams share the window re-sweeps)
     if (ctx->tb_split < 0 && !ctx->scores_only && b->eff_mode == 1 && n_pairs >= 64 && n_pairs <= 256 &&
@@ -2280,6 +2319,7 @@ extern "C" int swmi_stream_open(swmi_ctx *ctx, const swmi_params *p, const uint8
         sl.ctx->tb_split = ctx->tb_split; sl.ctx->col_chunks = ctx->col_chunks; sl.ctx->resident = ctx->resident; sl.ctx->tfused = ctx->tfused;
         sl.ctx->auto_ties_x100 = ctx->auto_ties_x100; sl.ctx->arena_words_per_pair = ctx->arena_words_per_pair;
         sl.ctx->device_strings = ctx->device_strings; sl.ctx->scores_only = ctx->scores_only;
+        sl.ctx->gap_open = ctx->gap_open; sl.ctx->affine = ctx->affine;
         sl.ctx->spin_us = 50;                    // (a chunk takes milliseconds: the slot threads mostly block)
         sl.shell = new swmi_batch;
     }

@@ -247,10 +247,12 @@ SWMI_HD static inline uint32_t swmi_rows_per_lane(uint32_t m) {
     return r < 1u ? 1u : (r > SWMI_RMAX ? SWMI_RMAX : r);
 }
 // dwords of per-pair workspace.  mode 0: the direction field; mode 1: lane-state checkpoints + one maximum per
-// checkpoint window; mode 2: lane-state checkpoints.
+// checkpoint window; mode 2: lane-state checkpoints; mode 3: the affine direction field (swmi_aff_dir_words).
 // tfused: the context lets sw_tfused_kernel take pairs (option "tfused" = 1): such a pair keeps its column checkpoints in the
 // same region, which must then hold them.
+SWMI_HD static inline uint64_t swmi_aff_dir_words(uint32_t m, uint32_t n);
 SWMI_HD static inline uint64_t swmi_dir_words(uint32_t m, uint32_t n, uint32_t mode, bool tfused = false) {
+    if (mode == 3) return swmi_aff_dir_words(m, n);       // the affine pipeline: its 4-bit direction field
     uint32_t R = swmi_rows_per_lane(m);
     uint64_t strips = ((uint64_t)m + 64u * R - 1u) / (64u * R);
     uint64_t wblocks = ((uint64_t)n + 63u + 15u) / 16u;   // T = n + 63 steps at most
@@ -260,6 +262,25 @@ SWMI_HD static inline uint64_t swmi_dir_words(uint32_t m, uint32_t n, uint32_t m
     if (tfused && mode == 1 && m <= 256u && n <= 64u * 40u && ((uint64_t)m + 64u) * 64u > words) words = ((uint64_t)m + 64u) * 64u;
     return words;
 }
+// ---- affine gaps (swmi_affine.hip): one wavefront per pair, R = ceil(m / 64) rows per lane, 4-bit codes, 8 steps per dword ----
+#define SWMI_AFF_RMAX     16u         // rows per lane of the widest affine sweep: reads of at most 1024 bases
+#define SWMI_AFF_MAX_READ (64u * SWMI_AFF_RMAX)
+#define SWMI_AFF_TB_SLOTS 4u          // traceback wavefronts per pair: slot s walks the maximum cells s, s + 4, ...
+#define SWMI_AFF_TILE_WORDS 4096u     // LDS dwords of a traceback wavefront's direction tile (at least one 8-step block)
+SWMI_HD static inline uint32_t swmi_aff_rows_per_lane(uint32_t m) {
+    uint32_t r = (m + 63u) / 64u;
+    return r < 1u ? 1u : r;
+}
+// 8-step blocks of a pair's field: T = n + lact - 1 anti-diagonal steps, lact = the lanes that own read rows
+SWMI_HD static inline uint32_t swmi_aff_blocks(uint32_t m, uint32_t n) {
+    const uint32_t R = swmi_aff_rows_per_lane(m), lact = m ? (m + R - 1u) / R : 1u;
+    return (uint32_t)(((uint64_t)n + lact - 1u + 7u) / 8u);
+}
+// dwords of a pair's affine direction field: one dword per (block, row slot, lane)
+SWMI_HD static inline uint64_t swmi_aff_dir_words(uint32_t m, uint32_t n) {
+    return (uint64_t)swmi_aff_blocks(m, n) * swmi_aff_rows_per_lane(m) * 64u;
+}
+
 // int32 seam rows of a pair whose read spans several strips: one row of n+1 per strip
 SWMI_HD static inline uint64_t swmi_seam_words(uint32_t m, uint32_t n) {
     if (m <= 64u * SWMI_RMAX) return 0;

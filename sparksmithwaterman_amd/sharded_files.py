@@ -164,6 +164,9 @@ def _rank_main(args):
     scores = [int(x) for x in args.scores.split(",")]
     ctx = sw.Context(dev_id)
     try:
+        if len(scores) == 4:                                # match,mismatch,gap,gapOpen: affine gaps on this rank's context
+            ctx.set_option("gap_open", scores[3])
+            scores = scores[:3]
         t0 = time.perf_counter()
         st = run_rank(ctx, args.ref_dir, args.in_dir, args.out_dir, rank, world, args.delimiter, args.out_name, args.out_ext,
                       sw.make_params(scores, None, tie), args.stream_chunk_bytes, 0, 0,
@@ -194,7 +197,8 @@ def main(argv=None):
     ap.add_argument("--delimiter", default=_io.DELIMITER)
     ap.add_argument("--out-name", default="result")
     ap.add_argument("--out-ext", default=".txt")
-    ap.add_argument("--scores", default="5,-3,-4", help="match,mismatch,gap (Distribution.java:36)")
+    ap.add_argument("--scores", default="5,-3,-4",
+                    help="match,mismatch,gap (Distribution.java:36), or match,mismatch,gap,gapOpen for affine gaps (gapOpen <= 0)")
     ap.add_argument("--tie", choices=("serial", "strict"), default="serial",
                     help="serial: SmithWaterman's aligner (NoDistribution, DistributeReference); strict: DistributedSW's (DistributeAlgorithm)")
     ap.add_argument("--stream-chunk-bytes", type=int, default=512 << 10, help="sequence bytes per streamed chunk")

@@ -14,6 +14,8 @@ test written against the reference reads the same here:
 
 All alignment work happens in libswmi.so on the GPU; nothing here computes a score.
 """
+import contextlib as _contextlib
+
 from . import _capi
 from .aligner import Context, make_params, DEFAULT_SCORES, DEFAULT_TYPES
 
@@ -32,6 +34,24 @@ def _algo(align_scores, align_types):
             DEFAULT_TYPES if align_types is None else align_types)
 
 
+@_contextlib.contextmanager
+def _scores(ctx, align_scores):
+    """alignScores {match, mismatch, gap} or {match, mismatch, gap, gapOpen}: yields the three entries make_params takes
+    and, for four, sets the context's "gap_open" for the call (affine gaps: a gap of length k costs gapOpen + k * gap)."""
+    sc = tuple(int(x) for x in align_scores)
+    if len(sc) != 4:
+        yield sc
+        return
+    if sc[3] > 0:
+        raise ValueError("gapOpen (alignScores[3]) must be <= 0, got %d" % sc[3])
+    prev = ctx.options.get("gap_open", 0)
+    ctx.set_option("gap_open", sc[3])
+    try:
+        yield sc[:3]
+    finally:
+        ctx.set_option("gap_open", prev)
+
+
 class SmithWaterman:
     class OptAlignments:
         """Function3<String[], int[], char[], Tuple2<Integer, ArrayList<Tuple2<Integer,String[]>>>>."""
@@ -43,12 +63,13 @@ class SmithWaterman:
         def call(self, seqs, alignScores=None, alignTypes=None):
             ctx = self._ctx or default_context()
             sc, ty = _algo(alignScores, alignTypes)
-            b = ctx.upload([seqs[0]], [seqs[1]])
-            try:
-                b.run(make_params(sc, ty, self.tie_mode))
-                return b.score(0), b.alignments(0)
-            finally:
-                b.free()
+            with _scores(ctx, sc) as sc3:
+                b = ctx.upload([seqs[0]], [seqs[1]])
+                try:
+                    b.run(make_params(sc3, ty, self.tie_mode))
+                    return b.score(0), b.alignments(0)
+                finally:
+                    b.free()
 
 
 class DistributedSW:
@@ -87,13 +108,14 @@ class Distribution:
             for idxs in groups.values():
                 _, reads, algo = tuples[idxs[0]]
                 sc, ty = _algo(*(algo if algo is not None else (None, None)))
-                b = ctx.upload([tuples[i][0][1] for i in idxs], list(reads))
-                try:
-                    b.run(make_params(sc, ty, self._tie))
-                    for r, i in enumerate(idxs):
-                        out[i] = (b.ref_total(r), (tuples[i][0], b.ref_match_sites(r)))
-                finally:
-                    b.free()
+                with _scores(ctx, sc) as sc3:
+                    b = ctx.upload([tuples[i][0][1] for i in idxs], list(reads))
+                    try:
+                        b.run(make_params(sc3, ty, self._tie))
+                        for r, i in enumerate(idxs):
+                            out[i] = (b.ref_total(r), (tuples[i][0], b.ref_match_sites(r)))
+                    finally:
+                        b.free()
             return out
 
     class MapRef:
@@ -161,8 +183,10 @@ class _FileDriver:
             out_ext = ioArgs[5] if ioArgs[5] is not None else out_ext
         sc, ty = _algo(*(algoArgs if algoArgs is not None else (None, None)))
         ctx = self._ctx or default_context()
-        params = make_params(sc, ty, self._tie)
+        with _scores(ctx, sc) as sc3:
+            return self._run(ctx, make_params(sc3, ty, self._tie), ref_dir, in_dir, delim, out_dir, out_name, out_ext)
 
+    def _run(self, ctx, params, ref_dir, in_dir, delim, out_dir, out_name, out_ext):
         in_crawl = _io.DirectoryCrawler(in_dir)
         input_num = 0
         while in_crawl.hasNext():

@@ -1,0 +1,303 @@
+"""Affine gap penalties on the GPU (swmi_affine.hip, swmi_set_option "gap_open" / "affine").
+
+Checked against the oracle at gap_open = 0 (the affine kernels must reduce to the linear results bit for bit) and against the
+numpy restatement of the contract in tests/affine_reference.py otherwise."""
+import os
+import random
+import subprocess
+
+import numpy as np
+import pytest
+
+import sparksmithwaterman_amd as sw
+from sparksmithwaterman_amd import _capi
+from oracle import sw_oracle as orc
+
+import affine_reference as ar
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ERR_INVALID, ERR_UNSUPPORTED = -1, -5       # swmi_status (include/swmi.h)
+
+
+def _golden(name):
+    import json
+    with open(os.path.join(ROOT, "tests", "golden", name)) as f:
+        return json.load(f)
+
+
+@pytest.fixture
+def ctx():
+    c = sw.Context(0)
+    yield c
+    c.close()
+
+
+def _rand(rng, n, alphabet="ACGT"):
+    return "".join(rng.choice(alphabet) for _ in range(n))
+
+
+def _expect_linear(ref, read, scores, tie):
+    s, al = orc.opt_alignments((ref, read), scores[:3], b"aid-", tie)
+    return s, [(a[0], tuple(a[1])) for a in al]
+
+
+def _expect_affine(ref, read, scores, tie):
+    return ar.align_numpy(ref, read, scores, tie)
+
+
+def _check(b, refs, reads, expect, tie, map_ref=True, alignments=True):
+    """every pair's score, alignment list and strings; the MapRef view (totals, stably sorted match sites)"""
+    exp = {}
+    for r, ref in enumerate(refs):
+        for q, read in enumerate(reads):
+            pair = r * len(reads) + q
+            es, ea = exp[(r, q)] = expect(ref, read)
+            assert b.score(pair) == es, (r, q, len(ref), len(read))
+            if not alignments:
+                continue
+            n, flags = b.n_alignments(pair)
+            assert n == len(ea), (r, q, n, len(ea))
+            if flags & sw.PAIR_DEGENERATE:
+                assert es == 0 and (n == 0 or b.alignment(pair, n - 1) == (0, ("", "")))
+                continue
+            assert b.alignments(pair) == ea, (r, q, ref, read)
+    if map_ref and alignments:
+        packed = b.ref_sites_packed()
+        for r in range(len(refs)):
+            total = int(np.int32(sum(exp[(r, q)][0] for q in range(len(reads)))))
+            sites = sorted([a for q in range(len(reads)) for a in exp[(r, q)][1] if a != (0, ("", ""))], key=lambda t: t[0])
+            ndeg = sum(len(exp[(r, q)][1]) for q in range(len(reads)) if exp[(r, q)][0] == 0)
+            assert b.ref_total(r) == total
+            assert packed[r] == (total, ndeg, sites), r
+            if ndeg < 5000:
+                assert b.ref_match_sites(r) == [(0, ("", ""))] * ndeg + sites, r
+    return exp
+
+
+def _run(ctx, refs, reads, scores, tie):
+    ctx.set_option("gap_open", scores[3])
+    return ctx.upload(refs, reads).run(sw.make_params(scores[:3], None, tie))
+
+
+# 1 -- gap_open = 0 on the affine kernels reduces to today's results
+@pytest.mark.parametrize("tie", [0, 1])
+def test_affine_kernels_at_gap_open_zero_match_the_oracle(ctx, tie):
+    ctx.set_option("affine", 1)
+    kats = _golden("kat.json")["kats"] + _golden("engineerdata_small.json")["kats"]
+    n_checked = 0
+    for k in kats:
+        if k["scores"][2] > 0 or tuple(k.get("types", "aid-")) != tuple("aid-"):
+            continue                        # (a positive gap is outside the affine bounds; alignTypes are the linear path's)
+        if k["tie_mode"] != tie:
+            continue
+        b = _run(ctx, [k["ref"]], [k["read"]], tuple(k["scores"]) + (0,), tie)
+        assert b.pipeline_mode() == 3
+        assert b.score(0) == k["score"], k["name"]
+        assert [[x[0], x[1][0], x[1][1]] for x in b.alignments(0)] == k["alignments"], k["name"]
+        b.free()
+        n_checked += 1
+    assert n_checked >= 3
+    rng = random.Random(11 + tie)
+    refs = [_rand(rng, rng.randint(1, 600), rng.choice(["ACGT", "AC", "ACGTacgtN"])) for _ in range(20)]
+    refs[3] = "ACGTTGCA" * 60                           # periodic: a tied maximum per period
+    reads = [_rand(rng, rng.randint(1, 200)) for _ in range(50)]
+    reads[7] = "ACGTTGCAAC"
+    b = _run(ctx, refs, reads, (5, -3, -4, 0), tie)
+    assert b.pipeline_mode() == 3
+    _check(b, refs, reads, lambda rf, rd: _expect_linear(rf, rd, (5, -3, -4), tie), tie)
+    b.free()
+
+
+# 2 -- gap_open != 0 against the numpy restatement
+def test_affine_read_lengths_and_long_references(ctx):
+    rng = random.Random(5)
+    reads = [_rand(rng, m) for m in (1, 63, 64, 65, 128, 150, 256, 257, 512, 1024)]
+    refs = [_rand(rng, 700), _rand(rng, 1500)]
+    for o, tie in ((-1, 0), (-6, 1), (-12, 0)):
+        b = _run(ctx, refs, reads, (5, -3, -2, o), tie)
+        assert b.pipeline_mode() == 3
+        _check(b, refs, reads, lambda rf, rd: _expect_affine(rf, rd, (5, -3, -2, o), tie), tie)
+        b.free()
+    # a 20 kbp reference with a planted read and a read of 1024
+    big = _rand(rng, 20000)
+    reads2 = [big[13000:13150], big[5000:5400] + big[5460:6084], _rand(rng, 90)]
+    b = _run(ctx, [big], reads2, (2, -3, -1, -6), 0)
+    _check(b, [big], reads2, lambda rf, rd: _expect_affine(rf, rd, (2, -3, -1, -6), 0), 0)
+    b.free()
+
+
+@pytest.mark.parametrize("tie", [0, 1])
+def test_affine_ties_symbols_and_empty_sides(ctx, tie):
+    rng = random.Random(21 + tie)
+    # EngineerData-shaped periodic pairs: many tied maxima; non-ACGT bytes and mixed case; empty sequences
+    refs = ["CCTGGGTCCTGCCTCG" * 25, "acgtNNacgtRYacgt" * 12, "", _rand(rng, 300, "ACGTacgt\xe9\xc9x"), "AAAA"]
+    reads = ["CCTGGGTCCTGC", "ACGTNNACG", "", _rand(rng, 80, "ACGTacgt\xe9\xc9"), "TT", "CCTGGGACCTGCCTCGCC"]
+    for o in (-1, -6, -12):
+        b = _run(ctx, refs, reads, (5, -3, -4, o), tie)
+        _check(b, refs, reads, lambda rf, rd: _expect_affine(rf, rd, (5, -3, -4, o), tie), tie)
+        b.free()
+
+
+def test_affine_kats(ctx):
+    for k in _golden("affine_kat.json")["kats"]:
+        b = _run(ctx, [k["ref"]], [k["read"]], tuple(k["scores"]), k["tie_mode"])
+        assert b.score(0) == k["score"], k["name"]
+        assert [[x[0], x[1][0], x[1][1]] for x in b.alignments(0)] == k["alignments"], k["name"]
+        b.free()
+
+
+# 3 -- the options that apply to affine runs give the same results
+@pytest.mark.parametrize("opt", [("device_strings", 0), ("zero_copy", 0), ("scores_only", 1), ("cell_cap", 4),
+                                 ("max_workspace_bytes", 1 << 20)])
+def test_affine_options(ctx, opt):
+    rng = random.Random(31)
+    refs = ["ACGTTGCA" * 40, _rand(rng, 900), "GATTACA" * 30 + _rand(rng, 200), _rand(rng, 64), _rand(rng, 2500)]
+    reads = ["ACGTTGCAAC", _rand(rng, 150), "GATTACAGATTACA", _rand(rng, 300), _rand(rng, 400)]     # (> 1 MiB of field in all)
+    sc = (5, -3, -2, -6)
+    ctx.set_option(*opt)
+    b = _run(ctx, refs, reads, sc, 0)
+    assert b.pipeline_mode() == 3
+    _check(b, refs, reads, lambda rf, rd: _expect_affine(rf, rd, sc, 0), 0, alignments=opt[0] != "scores_only")
+    if opt[0] == "cell_cap":
+        assert b.timing().rerun_pairs >= 1
+    if opt[0] == "max_workspace_bytes":
+        assert b.timing().fill_launches >= 2
+    b.free()
+
+
+def test_affine_async_and_one_shot(ctx):
+    rng = random.Random(41)
+    refs = [_rand(rng, 500) for _ in range(3)]
+    reads = [_rand(rng, 120) for _ in range(4)]
+    sc = (5, -3, -2, -6)
+    ctx.set_option("gap_open", sc[3])
+    b = ctx.upload(refs, reads).run_async(sw.make_params(sc[:3])).wait()
+    assert b.pipeline_mode() == 3
+    _check(b, refs, reads, lambda rf, rd: _expect_affine(rf, rd, sc, 0), 0)
+    b.free()
+    score, alns = sw.SmithWaterman.OptAlignments(ctx).call([refs[0], reads[0]], list(sc))
+    assert (score, alns) == _expect_affine(refs[0], reads[0], sc, 0)
+
+
+# 4 -- a stream from a FASTA file
+def test_affine_stream_from_fasta(ctx, tmp_path):
+    rng = random.Random(51)
+    refs = [_rand(rng, rng.randint(200, 800)) for _ in range(40)]
+    reads = [_rand(rng, 150), refs[17][100:250], _rand(rng, 64)]
+    path = tmp_path / "refs.fa"
+    with open(path, "w") as f:
+        for k, r in enumerate(refs):
+            f.write(">gi|ref%d\n" % k)
+            for x in range(0, len(r), 70):
+                f.write(r[x:x + 70] + "\n")
+    sc = (5, -3, -2, -6)
+    ctx.set_option("gap_open", sc[3])
+    st = ctx.stream(reads, sw.make_params(sc[:3]), slots=2, chunk_bytes=1 << 16)
+    st.push_file(path).finish()
+    exp = [[_expect_affine(r, q, sc, 0) for q in reads] for r in refs]
+    totals = st.totals()
+    assert [int(t) for t in totals] == [sum(e[0] for e in row) for row in exp]
+    for first, c in st.chunks():
+        assert c.pipeline_mode() == 3
+        for r in range(c.n_refs):
+            if (first + r) % 7 == 3 or first + r == 17:
+                sites = sorted([a for e in exp[first + r] for a in e[1]], key=lambda t: t[0])
+                assert c.ref_match_sites(r) == sites, first + r
+    st.close()
+
+
+# 5 -- out of bounds
+def test_affine_bounds(ctx):
+    with pytest.raises(_capi.SwmiError) as e:
+        ctx.set_option("gap_open", 1)
+    assert e.value.code == ERR_INVALID
+    with pytest.raises(_capi.SwmiError) as e:
+        ctx.set_option("affine", 0)
+    assert e.value.code == ERR_INVALID
+    ctx.set_option("gap_open", -6)
+    b = ctx.upload(["ACGT" * 10], ["A" * 1025])
+    with pytest.raises(_capi.SwmiError) as e:
+        b.run(sw.make_params((5, -3, -4)))
+    assert e.value.code == ERR_UNSUPPORTED
+    b.free()
+    b = ctx.upload(["ACGT" * 10], ["ACG"])
+    for bad in ((5, -3, 1), ((1 << 20) + 1, -3, -4)):
+        with pytest.raises(_capi.SwmiError) as e:
+            b.run(sw.make_params(bad))
+        assert e.value.code == ERR_UNSUPPORTED
+    ctx.set_option("gap_open", -((1 << 20) + 1))
+    with pytest.raises(_capi.SwmiError) as e:
+        b.run(sw.make_params((5, -3, -4)))
+    assert e.value.code == ERR_UNSUPPORTED
+    b.free()
+
+
+# 6 -- back to the linear kernels on the same context
+def test_gap_open_back_to_zero_runs_mode_1(ctx):
+    rng = random.Random(61)
+    refs = [_rand(rng, 400) for _ in range(3)]
+    reads = [_rand(rng, 100) for _ in range(3)]
+    b = ctx.upload(refs, reads)
+    ctx.set_option("gap_open", -6)
+    assert b.run(sw.make_params()).pipeline_mode() == 3
+    ctx.set_option("gap_open", 0)
+    b.run(sw.make_params())
+    assert b.pipeline_mode() == 1
+    _check(b, refs, reads, lambda rf, rd: _expect_linear(rf, rd, (5, -3, -4), 0), 0)
+    b.free()
+
+
+# 7 -- the JNI shim's entry point from plain C99
+_SHIM_C = r"""
+#include <stdio.h>
+#include "swmi.h"
+#include "swmi_shim.h"
+int main(void) {
+    char err[640];
+    swmi_ctx *ctx = NULL;
+    swmi_batch *b = NULL;
+    const signed char types[4] = {'a', 'i', 'd', '-'};
+    const char *ref = "%(ref)s", *read = "%(read)s";
+    int64_t ro[2], qo[2], n = 0, k;
+    int32_t total = 0;
+    ro[0] = 0; ro[1] = %(n)d; qo[0] = 0; qo[1] = %(m)d;
+    if (swmi_create(0, &ctx) != SWMI_OK) { printf("ERROR %%s\n", swmi_last_error()); return 3; }
+    if (swmi_shim_set_gap_open(ctx, 1, err, sizeof err) != SWMI_ERR_INVALID) { printf("ERROR positive gapOpen accepted\n"); return 4; }
+    if (swmi_shim_set_gap_open(NULL, -1, err, sizeof err) != SWMI_ERR_INVALID) { printf("ERROR null context accepted\n"); return 4; }
+    if (swmi_shim_set_gap_open(ctx, %(o)d, err, sizeof err) != SWMI_OK) { printf("ERROR %%s\n", err); return 5; }
+    if (swmi_shim_align_batch(ctx, %(match)d, %(mismatch)d, %(gap)d, %(tie)d, types, 4, ref, %(n)d, ro, 1, read, %(m)d, qo, 1, &b, err, sizeof err) != SWMI_OK) {
+        printf("ERROR %%s\n", err); return 6;
+    }
+    if (swmi_shim_ref_total(b, 0, &total, err, sizeof err) != SWMI_OK) { printf("ERROR %%s\n", err); return 7; }
+    if (swmi_shim_ref_site_count(b, 0, &n, err, sizeof err) != SWMI_OK) { printf("ERROR %%s\n", err); return 7; }
+    printf("%%d %%ld", (int)total, (long)n);
+    for (k = 0; k < n; k++) {
+        int32_t begin = 0; const char *ra = NULL, *qa = NULL; uint32_t len = 0;
+        if (swmi_shim_ref_site(b, 0, k, &begin, &ra, &qa, &len, err, sizeof err) != SWMI_OK) { printf("ERROR %%s\n", err); return 8; }
+        printf(" %%d:%%s/%%s", (int)begin, ra, qa);
+    }
+    printf("\n");
+    swmi_batch_free(ctx, b);
+    swmi_destroy(ctx);
+    return 0;
+}
+"""
+
+
+def test_c99_shim_sets_gap_open(tmp_path):
+    k = _golden("affine_kat.json")["kats"][0]
+    src = tmp_path / "shim_affine.c"
+    src.write_text(_SHIM_C % dict(ref=k["ref"], read=k["read"], n=len(k["ref"]), m=len(k["read"]), match=k["scores"][0],
+                                  mismatch=k["scores"][1], gap=k["scores"][2], o=k["scores"][3], tie=k["tie_mode"]))
+    exe = tmp_path / "shim_affine"
+    lib = os.path.join(ROOT, "sparksmithwaterman_amd", "lib")
+    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Wextra", "-Werror", "-pedantic",
+                           "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "bindings", "jni"),
+                           str(src), os.path.join(ROOT, "bindings", "jni", "swmi_shim.c"),
+                           "-L", lib, "-lswmi", "-Wl,-rpath," + lib, "-o", str(exe)])
+    out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0, out.stdout + out.stderr
+    sites = sorted(k["alignments"], key=lambda a: a[0])
+    assert out.stdout.split() == [str(k["score"]), str(len(sites))] + ["%d:%s/%s" % tuple(a) for a in sites]
