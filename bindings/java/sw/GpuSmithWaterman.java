@@ -34,6 +34,8 @@ public class GpuSmithWaterman
 			ByteBuffer refBytes , long[] refOff , int nRefs , ByteBuffer readBytes , long[] readOff , int nReads ) ;
 	/** affine gaps on the context: alignScores { match , mismatch , gap , gapOpen } -- a gap of length k costs gapOpen + k * gap */
 	static native void nativeSetGapOpen( long ctx , int gapOpen ) ;
+	/** substitution scores on the context: alphabet = n ISO-8859-1 symbols, scores = n * n, row = read base; null clears */
+	static native void nativeSetScoreMatrix( long ctx , byte[] alphabet , int[] scores ) ;
 	static native void nativeFreeBatch( long ctx , long batch ) ;
 	static native int nativeRefTotal( long batch , int ref ) ;
 	static native long nativeRefSiteCount( long batch , int ref ) ;
@@ -44,32 +46,79 @@ public class GpuSmithWaterman
 	static native void nativeRefSitesPacked( long batch , int refLo , int refHi , int[] totals , long[] degenerate , long[] siteFirst ,
 			int[] begins , int[] lens , long[] strOff , byte[] blob ) ;
 
+	/** a native context and the version of the score matrix it holds (0: none set on it yet) */
+	private static final class NativeContext
+	{
+		final long handle ;
+		long matrixVersion = 0 ;		// (touched only by the owning thread)
+		NativeContext( long handle ) { this.handle = handle ; }
+	}
+
 	/** one context per executor thread: MapRef.call runs concurrently on every task thread */
-	private static final java.util.concurrent.ConcurrentHashMap<Long,Long> CONTEXTS = new java.util.concurrent.ConcurrentHashMap<Long,Long>() ;
+	private static final java.util.concurrent.ConcurrentHashMap<Long,NativeContext> CONTEXTS = new java.util.concurrent.ConcurrentHashMap<Long,NativeContext>() ;
 	static
 	{
 		// executor threads outlive tasks; whatever is still open when the JVM goes down is destroyed here
 		Runtime.getRuntime().addShutdownHook( new Thread() { @Override public void run() { releaseAllContexts() ; } } ) ;
 	}
 
-	private static long context()
+	/** the score matrix every context applies before its next batch: { alphabet , scores } (null: none), and its version */
+	private static volatile Object[] MATRIX = null ;
+	private static final java.util.concurrent.atomic.AtomicLong MATRIX_VERSION = new java.util.concurrent.atomic.AtomicLong() ;
+
+	/**
+	 * Substitution scores for every batch aligned from now on, on every executor thread (include/swmi.h: swmi_set_score_matrix):
+	 * alphabet = the n symbols (ISO-8859-1, distinct ignoring case), scores[i][j] = score of read base alphabet[i] against
+	 * reference base alphabet[j].  Bases outside the alphabet keep alignScores' match / mismatch.  null clears the matrix.
+	 * Symbols must be ISO-8859-1 characters (U+0000..U+00FF): sequences are passed to the library as ISO-8859-1 bytes.
+	 */
+	public static void setScoreMatrix( String alphabet , int[][] scores )
+	{
+		if( alphabet == null ) { MATRIX = new Object[] { null , null , Long.valueOf( MATRIX_VERSION.incrementAndGet() ) } ; return ; }
+		int n = alphabet.length() ;
+		for( int i = 0 ; i < n ; i++ )
+			if( alphabet.charAt(i) > 0xFF )
+				throw new IllegalArgumentException( "score matrix symbol " + i + " (U+" + Integer.toHexString( alphabet.charAt(i) ).toUpperCase() + ") is not an ISO-8859-1 character" ) ;
+		if( scores == null || scores.length != n ) throw new IllegalArgumentException( "scores needs " + n + " rows" ) ;
+		int[] flat = new int[n*n] ;
+		for( int i = 0 ; i < n ; i++ )
+		{
+			if( scores[i] == null || scores[i].length != n ) throw new IllegalArgumentException( "row " + i + " needs " + n + " entries" ) ;
+			System.arraycopy( scores[i] , 0 , flat , i * n , n ) ;
+		}
+		MATRIX = new Object[] { alphabet.getBytes( StandardCharsets.ISO_8859_1 ) , flat , Long.valueOf( MATRIX_VERSION.incrementAndGet() ) } ;
+	}
+
+	/** the current matrix on this thread's context, if it does not hold it yet (the version lives with the context, so a context
+	 *  created after another was destroyed never inherits its state) */
+	private static void applyScoreMatrix( NativeContext ctx )
+	{
+		Object[] m = MATRIX ;
+		if( m == null ) return ;
+		long ver = ((Long)m[2]).longValue() ;
+		if( ctx.matrixVersion == ver ) return ;
+		nativeSetScoreMatrix( ctx.handle , (byte[])m[0] , (int[])m[1] ) ;
+		ctx.matrixVersion = ver ;
+	}
+
+	private static NativeContext context()
 	{
 		Long tid = Long.valueOf( Thread.currentThread().getId() ) ;
-		Long ctx = CONTEXTS.get( tid ) ;
+		NativeContext ctx = CONTEXTS.get( tid ) ;
 		if( ctx == null )
 		{
 			int nGpus = Integer.getInteger( "swmi.gpus" , 8 ) ;
-			ctx = Long.valueOf( nativeCreate( (int)( tid.longValue() % nGpus ) ) ) ;
+			ctx = new NativeContext( nativeCreate( (int)( tid.longValue() % nGpus ) ) ) ;
 			CONTEXTS.put( tid , ctx ) ;
 		}
-		return ctx.longValue() ;
+		return ctx ;
 	}
 
 	/** destroys the calling thread's context (device buffers, HIP stream): call it when a task thread retires */
 	public static void releaseThreadContext()
 	{
-		Long ctx = CONTEXTS.remove( Long.valueOf( Thread.currentThread().getId() ) ) ;
-		if( ctx != null ) nativeDestroy( ctx.longValue() ) ;
+		NativeContext ctx = CONTEXTS.remove( Long.valueOf( Thread.currentThread().getId() ) ) ;
+		if( ctx != null ) nativeDestroy( ctx.handle ) ;
 	}
 
 	/** destroys every context (no native call may be in flight) */
@@ -77,8 +126,8 @@ public class GpuSmithWaterman
 	{
 		for( Long tid : new ArrayList<Long>( CONTEXTS.keySet() ) )
 		{
-			Long ctx = CONTEXTS.remove( tid ) ;
-			if( ctx != null ) nativeDestroy( ctx.longValue() ) ;
+			NativeContext ctx = CONTEXTS.remove( tid ) ;
+			if( ctx != null ) nativeDestroy( ctx.handle ) ;
 		}
 	}
 
@@ -140,10 +189,12 @@ public class GpuSmithWaterman
 			ByteBuffer refBuf = pack( refs , refOff ) , readBuf = pack( reads , readOff ) ;
 			byte[] types = { (byte)ty[0] , (byte)ty[1] , (byte)ty[2] , (byte)ty[3] } ;
 
-			long ctx = context() ;
+			NativeContext nc = context() ;
+			long ctx = nc.handle ;
 			// alignScores may carry a fourth entry, gapOpen (<= 0): affine gaps; three entries keep the linear scoring
 			if( sc.length != 3 && sc.length != 4 ) throw new IllegalArgumentException( "alignScores needs 3 or 4 entries: " + sc.length ) ;
 			nativeSetGapOpen( ctx , sc.length == 4 ? sc[3] : 0 ) ;
+			applyScoreMatrix( nc ) ;
 			long batch = nativeAlignBatch( ctx , sc[0] , sc[1] , sc[2] , TIE_SERIAL , types , refBuf , refOff , n , readBuf , readOff , reads.size() ) ;
 			try
 			{

@@ -49,6 +49,35 @@ JNIEXPORT void JNICALL Java_sw_GpuSmithWaterman_nativeSetGapOpen(JNIEnv *env, jc
     if (swmi_shim_set_gap_open((swmi_ctx *)(intptr_t)ctx, gapOpen, err, sizeof err) != SWMI_OK) throw_msg(env, err);
 }
 
+/* a substitution score matrix on this context from now on: alphabet = n ISO-8859-1 symbols, scores = int[n * n], row = read base;
+ * alphabet == null clears it */
+JNIEXPORT void JNICALL Java_sw_GpuSmithWaterman_nativeSetScoreMatrix(JNIEnv *env, jclass cls, jlong ctx, jbyteArray alphabet,
+                                                                     jintArray scores) {
+    char err[640];
+    jbyte *a = NULL;
+    jint *sc = NULL;
+    jsize n = 0, ns = 0;
+    int rc;
+    (void)cls;
+    if (alphabet) {
+        if (!scores) { throw_msg(env, "nativeSetScoreMatrix: scores is null"); return; }
+        n = (*env)->GetArrayLength(env, alphabet);
+        ns = (*env)->GetArrayLength(env, scores);
+        a = (*env)->GetByteArrayElements(env, alphabet, NULL);
+        sc = (*env)->GetIntArrayElements(env, scores, NULL);
+        if (!a || !sc) {
+            if (a) (*env)->ReleaseByteArrayElements(env, alphabet, a, JNI_ABORT);
+            if (sc) (*env)->ReleaseIntArrayElements(env, scores, sc, JNI_ABORT);
+            return;                                                   /* (OutOfMemoryError pending) */
+        }
+    }
+    rc = swmi_shim_set_score_matrix((swmi_ctx *)(intptr_t)ctx, (const signed char *)a, (size_t)n, (const int32_t *)sc, (size_t)ns,
+                                    err, sizeof err);
+    if (a) (*env)->ReleaseByteArrayElements(env, alphabet, a, JNI_ABORT);
+    if (sc) (*env)->ReleaseIntArrayElements(env, scores, sc, JNI_ABORT);
+    if (rc != SWMI_OK) throw_msg(env, err);
+}
+
 /* refBytes/readBytes: direct ByteBuffers of ISO-8859-1 bytes; refOff/readOff: long[n+1] */
 JNIEXPORT jlong JNICALL Java_sw_GpuSmithWaterman_nativeAlignBatch(
         JNIEnv *env, jclass cls, jlong ctx, jint match, jint mismatch, jint gap, jint tieMode, jbyteArray types,

@@ -31,6 +31,19 @@ int swmi_shim_set_gap_open(swmi_ctx *ctx, int32_t gap_open, char *err, size_t er
     return SWMI_OK;
 }
 
+int swmi_shim_set_score_matrix(swmi_ctx *ctx, const signed char *alphabet, size_t n, const int32_t *scores, size_t n_scores,
+                               char *err, size_t err_len) {
+    int rc;
+    if (!ctx) return shim_fail(SWMI_ERR_INVALID, err, err_len, "nativeSetScoreMatrix", "context handle is 0");
+    if (n > 64) return shim_fail(SWMI_ERR_INVALID, err, err_len, "nativeSetScoreMatrix", "at most 64 symbols");
+    if (n > 0 && (!alphabet || !scores))
+        return shim_fail(SWMI_ERR_INVALID, err, err_len, "nativeSetScoreMatrix", "alphabet or scores is null");
+    if (n_scores != n * n) return shim_fail(SWMI_ERR_INVALID, err, err_len, "nativeSetScoreMatrix", "scores must hold n * n entries");
+    if ((rc = swmi_set_score_matrix(ctx, n ? (const uint8_t *)alphabet : NULL, (uint32_t)n, n ? scores : NULL)) != SWMI_OK)
+        return shim_fail(rc, err, err_len, "nativeSetScoreMatrix", swmi_last_error());
+    return SWMI_OK;
+}
+
 int swmi_shim_align_batch(swmi_ctx *ctx, int32_t match, int32_t mismatch, int32_t gap, int32_t tie_mode,
                           const signed char *types, size_t types_len,
                           const void *ref_bytes, int64_t ref_cap, const int64_t *ref_off, int32_t n_refs,

@@ -30,6 +30,12 @@ int swmi_shim_align_batch(swmi_ctx *ctx, int32_t match, int32_t mismatch, int32_
  * gap_open <= 0; 0 (the default) is the linear scoring.  Applies to the batches the context aligns from then on. */
 int swmi_shim_set_gap_open(swmi_ctx *ctx, int32_t gap_open, char *err, size_t err_len);
 
+/* nativeSetScoreMatrix: a substitution score matrix on this context (swmi_set_score_matrix): `alphabet` = n symbols narrowed to
+ * bytes (ISO-8859-1), `scores` = n * n entries, row = read base, column = reference base (n_scores must be n * n).  n = 0 clears
+ * it.  Applies to the batches the context aligns from then on (on the affine kernels). */
+int swmi_shim_set_score_matrix(swmi_ctx *ctx, const signed char *alphabet, size_t n, const int32_t *scores, size_t n_scores,
+                               char *err, size_t err_len);
+
 /* nativeRefTotal / nativeRefSiteCount / nativeRefSite */
 int swmi_shim_ref_total(const swmi_batch *b, int32_t ref, int32_t *total, char *err, size_t err_len);
 int swmi_shim_ref_site_count(swmi_batch *b, int32_t ref, int64_t *n, char *err, size_t err_len);

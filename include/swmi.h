@@ -124,8 +124,22 @@ void        swmi_default_params(swmi_params *p);
  * affine: -1 (default) the affine kernels only when gap_open != 0; 1 always, also at gap_open = 0 (where they give the linear results).
  * Further knobs: spin_us (how long a run polls its stream before it blocks, default 2000); col_chunks (0 automatic,
  * 1 never, N > 1 force up to N column chunks per pair: a launch of few pairs with long references is swept by several
- * wavefronts per pair -- a read of more than 256 rows by several strip pipelines); debug_strip_spins / debug_reverse_strips (tests of the strip pipeline's give-up path). */
+ * wavefronts per pair -- a read of more than 256 rows by several strip pipelines); debug_strip_spins / debug_reverse_strips (tests of the strip pipeline's give-up path);
+ * debug_async_delay_us (0 .. 10^7, default 0: the async worker waits this long before it starts a run -- a test of what a run takes
+ * when it is asked for, not when it starts). */
 int         swmi_set_option(swmi_ctx *ctx, const char *name, int64_t value);
+
+/* Substitution score matrix.  alphabet: n bytes, 1 <= n <= 64, pairwise distinct after canonicalisation
+ * (Character.toUpperCase on ISO-8859-1: 'a' and 'A' are one symbol, and a matrix on 'A' also scores 'a'); scores[i * n + j] is the
+ * score of READ base alphabet[i] against REFERENCE base alphabet[j] (row = read, column = reference; asymmetric matrices are
+ * allowed).  A cell whose two bases are both in the alphabet takes the matrix entry; any other cell scores as before: match when
+ * the bases are equal, else mismatch.  n = 0 (the pointers may be NULL) clears the matrix.  Duplicate symbols, n > 64 or an
+ * entry with |entry| > 2^20 return SWMI_ERR_INVALID and leave the context as it was.
+ * A run with a matrix takes the affine kernels whatever gap_open / affine say (swmi_batch_mode = 3), with the affine bounds: reads
+ * of at most 1024 bases, gap <= 0, |match|, |mismatch|, |gap|, |gap_open| <= 2^20 -- outside them SWMI_ERR_UNSUPPORTED before
+ * anything is launched.  A run uses the matrix set when it was asked for (swmi_batch_run, swmi_batch_run_async, swmi_stream_open
+ * for all of a stream's chunks); setting another one later does not change it.  Without a matrix nothing changes. */
+int         swmi_set_score_matrix(swmi_ctx *ctx, const uint8_t *alphabet, uint32_t n, const int32_t *scores);
 
 /* ---- staged path: upload once, run many times (what bench.py times) ------------- */
 /* ref_off/read_off have n+1 entries, off[0] == 0, non-decreasing; lengths < 2^30.  */
@@ -158,7 +172,8 @@ typedef struct swmi_timing {
     uint32_t tfused_pairs;      /* pairs swept in the transposed layout and traced back by the same wavefront        */
 } swmi_timing;
 int  swmi_batch_timing(const swmi_batch *b, swmi_timing *t);
-/* The kernel pipeline (0, 1 or 2, see swmi_set_option "mode"; 3: the affine kernels, option "gap_open") the last run of the batch used. */
+/* The kernel pipeline (0, 1 or 2, see swmi_set_option "mode"; 3: the affine kernels, option "gap_open" or a score matrix) the last run
+ * of the batch used. */
 int  swmi_batch_mode(const swmi_batch *b, int *mode);
 
 /* ---- results of the last run (host memory owned by the batch) ------------------- */

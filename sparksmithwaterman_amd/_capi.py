@@ -52,6 +52,7 @@ SYMBOLS = [
     ("swmi_destroy", None, [_P]),
     ("swmi_default_params", None, [C.POINTER(Params)]),
     ("swmi_set_option", C.c_int, [_P, C.c_char_p, C.c_int64]),
+    ("swmi_set_score_matrix", C.c_int, [_P, C.c_char_p, C.c_uint32, C.POINTER(C.c_int32)]),
     ("swmi_batch_upload", C.c_int, [_P, C.c_char_p, _u64p, C.c_uint32, C.c_char_p, _u64p, C.c_uint32, C.POINTER(_P)]),
     ("swmi_batch_run", C.c_int, [_P, _P, C.POINTER(Params)]),
     ("swmi_batch_run_async", C.c_int, [_P, _P, C.POINTER(Params)]),

@@ -31,10 +31,29 @@ class Context:
         self._h = h
         self.device = int(device)
         self.options = {}                   # what set_option() last set, by name
+        self.score_matrix = None            # what set_score_matrix() last set: (alphabet bytes, row-major scores), or None
 
     def set_option(self, name, value):
         check(self._lib.swmi_set_option(self._h, name.encode(), int(value)))
         self.options[name] = int(value)
+
+    def set_score_matrix(self, alphabet, scores=None):
+        """Substitution scores (swmi_set_score_matrix): alphabet = n symbols (str or bytes, 1..64, distinct ignoring case),
+        scores = n x n (rows: read base, columns: reference base), or a sparksmithwaterman_amd.matrix.ScoreMatrix as the only
+        argument.  Cells with both bases in the alphabet take the matrix entry, every other cell match / mismatch as before.
+        The runs asked for from now on use it (on the affine kernels, swmi_batch_mode 3)."""
+        from . import matrix as _matrix
+        if isinstance(alphabet, _matrix.ScoreMatrix) and scores is None:
+            alphabet, scores = alphabet.alphabet, alphabet.scores
+        sym, flat = _matrix.validate(alphabet, scores)
+        arr = (C.c_int32 * len(flat))(*flat)
+        check(self._lib.swmi_set_score_matrix(self._h, sym, len(sym), arr))
+        self.score_matrix = (sym, tuple(flat))
+
+    def clear_score_matrix(self):
+        """Back to match / mismatch scoring (the linear or affine pipeline the options select)."""
+        check(self._lib.swmi_set_score_matrix(self._h, None, 0, None))
+        self.score_matrix = None
 
     def upload(self, refs, reads):
         """Sequences -> HBM.  refs/reads: lists of str or bytes."""

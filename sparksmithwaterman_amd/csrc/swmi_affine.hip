@@ -17,6 +17,15 @@
 //   The pair's maximum and its tied cells are tracked as in the linear sweep: a wave-uniform threshold, a cell list capped
 //   at cell_cap (more: SWMI_F_CELL_OVF, the host re-runs the pair with an exact-size list).
 //
+// sw_affine_sweep_matrix_kernel / _wide_kernel: the same sweep with s(i,j) from a substitution score matrix
+//   (swmi_set_score_matrix, DESIGN.md "Score matrices").  The workgroup stages two tables in LDS (layout: swmi_aff_mat_words):
+//     key[code]   = class(code) * 4 | hi << 16, hi = code when the code is outside the alphabet (class n), else 0x1FF
+//     tab[cq * (n+1) + cr]  the matrix, row = read class, column = reference class; row and column n (outside the
+//                           alphabet) hold mismatch
+//   A lane keeps key-derived words for its rows (q = class * (n+1) * 4 | hi << 16, hi = 0x3FF inside the alphabet) and passes the reference base's key along
+//   the wave instead of its code: the cell reads tab at byte offset q.lo + key.lo, and scores match instead when both high
+//   halves are equal (the same code outside the alphabet -- today's equality rule).
+//
 // sw_affine_traceback_kernel: one wavefront per (pair, slot); slot s walks the pair's maximum cells s, s + S, ...  The walk
 //   is the three-state machine of DESIGN.md "Affine gaps"; the field is staged in LDS a tile of consecutive 8-step blocks at a
 //   time (a path never moves to a later step), the ops are packed 16 per dword in LDS, and the record goes out through
@@ -52,12 +61,16 @@ __device__ __forceinline__ uint32_t lanes_below(uint64_t mask) {
     return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
 }
 
+// the score matrix of the matrix sweeps (only their instantiations reference it: the other kernels allocate no LDS)
+__shared__ uint32_t aff_mkey[256];
+__shared__ int aff_mtab[SWMI_MAT_NN_MAX * SWMI_MAT_NN_MAX];
+
 template <int R>
 struct AffState {
     int h[R], e[R];        // H and E of the lane's rows at its previous column
-    int q[R];              // the rows' base codes (SWMI_CODE_PAD past the read)
+    int q[R];              // the rows' base codes (SWMI_CODE_PAD past the read); MATRIX: their score-table row words
     uint32_t acc[R];       // codes of the current 8-step block
-    int rb;                // reference base code of the lane's current column
+    int rb;                // reference base code of the lane's current column; MATRIX: its key word
     int nh_prev;           // lane l-1's last-row H one step ago: the diagonal of row 0
     int f_last;            // F of the lane's last row at its previous column (what lane l+1 reads as F(i-1, j))
     int thr;               // wave-uniform running maximum (starts at 1: a maximum of 0 is the degenerate case)
@@ -66,7 +79,7 @@ struct AffState {
 
 // 8 anti-diagonal steps t0 .. t0+7 (a lane outside its column range keeps its state).  The steps are a loop, not unrolled:
 // eight copies of R cells let the scheduler hoist the compares of many cells at once, and their masks spilled the SGPRs.
-template <int R, bool STRICT>
+template <int R, bool STRICT, bool MATRIX>
 __device__ __forceinline__ void aff_block8(AffState<R> &S, const uint2 rw, const uint32_t t0, const uint32_t lane,
                                            const uint32_t n, const uint32_t row0, const uint32_t vrows,
                                            const int o, const int e, const int vmat, const int vmis,
@@ -75,7 +88,8 @@ __device__ __forceinline__ void aff_block8(AffState<R> &S, const uint2 rw, const
 #pragma unroll 1
     for (uint32_t s = 0; s < 8; ++s) {
         const uint32_t wsel = s < 4 ? rw.x : rw.y;
-        const int feed = (int)((wsel >> (8u * (s & 3u))) & 0xFFu);
+        const uint32_t fb = (wsel >> (8u * (s & 3u))) & 0xFFu;
+        const int feed = MATRIX ? (int)aff_mkey[fb] : (int)fb;  // (wave-uniform: lane 0's column)
         S.rb = aff_shr1(feed, S.rb);
         const int nh = aff_shr1_zero(S.h[R - 1]);
         const int nf = aff_shr1_zero(S.f_last);
@@ -85,10 +99,19 @@ __device__ __forceinline__ void aff_block8(AffState<R> &S, const uint2 rw, const
         if (inr) {
             int diag = S.nh_prev, up = nh, fup = nf;
             uint32_t sh = 4u * s;
+            const uint32_t rkey = (uint32_t)S.rb, rlo = rkey & 0xFFFFu;
 #pragma unroll
             for (int k = 0; k < R; ++k) {
                 const int left = S.h[k];
-                const int dg = diag + (S.rb == S.q[k] ? vmat : vmis);
+                int sv;
+                if (MATRIX) {
+                    const uint32_t qk = (uint32_t)S.q[k];
+                    const int tv = *reinterpret_cast<const int *>(reinterpret_cast<const char *>(aff_mtab) + ((qk & 0xFFFFu) + rlo));
+                    sv = (qk ^ rkey) < 0x10000u ? vmat : tv;
+                } else {
+                    sv = S.rb == S.q[k] ? vmat : vmis;
+                }
+                const int dg = diag + sv;
                 const int t1 = left + oe, t2 = S.e[k] + e;
                 const int en = max(max(t1, t2), 0);
                 const int u1 = up + oe, u2 = fup + e;
@@ -134,8 +157,8 @@ __device__ __forceinline__ void aff_block8(AffState<R> &S, const uint2 rw, const
     }
 }
 
-template <int R, bool STRICT>
-__device__ __forceinline__ void aff_sweep_pair(const FillArgs &A, const int o, const PairDesc pd, const uint32_t lane) {
+template <int R, bool STRICT, bool MATRIX>
+__device__ __forceinline__ void aff_sweep_pair(const FillArgs &A, const int o, const PairDesc pd, const uint32_t lane, const uint32_t nn) {
     const SeqDesc rd = A.refs[pd.ref_id];
     const SeqDesc qd = A.reads[pd.read_id];
     const uint32_t n = rd.len, m = qd.len;
@@ -154,6 +177,12 @@ __device__ __forceinline__ void aff_sweep_pair(const FillArgs &A, const int o, c
     for (int k = 0; k < R; ++k) {
         const uint32_t row = row0 + (uint32_t)k;
         S.q[k] = row < m ? (int)((readw[row >> 2] >> (8u * (row & 3u))) & 0xFFu) : (int)SWMI_CODE_PAD;
+        if (MATRIX) {                                            // row word: class * (n+1) * 4 | hi << 16
+            // (a read base inside the alphabet takes hi = 0x3FF, never a reference key's; pad rows: class n, hi 0xFFFF)
+            const uint32_t key = row < m ? aff_mkey[S.q[k]] : ((nn - 1u) * 4u) | (0xFFFFu << 16);
+            const uint32_t hi = (key >> 16) == 0x1FFu ? 0x3FFu : key >> 16;
+            S.q[k] = (int)(((key & 0xFFFFu) * nn) | (hi << 16));
+        }
         S.h[k] = 0;
         S.e[k] = 0;
     }
@@ -165,7 +194,7 @@ __device__ __forceinline__ void aff_sweep_pair(const FillArgs &A, const int o, c
         const uint2 rw = *reinterpret_cast<const uint2 *>(refw + (t0 >> 2));
 #pragma unroll
         for (int k = 0; k < R; ++k) S.acc[k] = 0u;
-        aff_block8<R, STRICT>(S, rw, t0, lane, n, row0, vrows, o, A.gap, A.match, A.mismatch, cells, ccap);
+        aff_block8<R, STRICT, MATRIX>(S, rw, t0, lane, n, row0, vrows, o, A.gap, A.match, A.mismatch, cells, ccap);
         uint32_t *__restrict__ dst = dir + (uint64_t)w * R * WAVE + lane;
 #pragma unroll
         for (int k = 0; k < R; ++k) dst[k * WAVE] = S.acc[k];
@@ -186,34 +215,53 @@ __device__ __forceinline__ void aff_sweep_pair(const FillArgs &A, const int o, c
 }
 
 // RLO..RHI: the rows per lane this instantiation of the kernel takes (the others' registers would cap its occupancy)
-template <int RLO, int RHI, bool STRICT>
-__device__ __forceinline__ void aff_sweep_dispatch(const FillArgs &A, const int o, const PairDesc pd, const uint32_t R, const uint32_t lane) {
+template <int RLO, int RHI, bool STRICT, bool MATRIX>
+__device__ __forceinline__ void aff_sweep_dispatch(const FillArgs &A, const int o, const PairDesc pd, const uint32_t R, const uint32_t lane,
+                                                   const uint32_t nn) {
     if constexpr (RLO <= RHI) {
-        if (R == (uint32_t)RLO) aff_sweep_pair<RLO, STRICT>(A, o, pd, lane);
-        else aff_sweep_dispatch<RLO + 1, RHI, STRICT>(A, o, pd, R, lane);
+        if (R == (uint32_t)RLO) aff_sweep_pair<RLO, STRICT, MATRIX>(A, o, pd, lane, nn);
+        else aff_sweep_dispatch<RLO + 1, RHI, STRICT, MATRIX>(A, o, pd, R, lane, nn);
     }
 }
 
-template <int RLO, int RHI>
-__device__ __forceinline__ void aff_sweep_entry(const FillArgs &A, const int o) {
+// mat / nn (MATRIX only): the score matrix image (swmi_aff_mat_words) and its side n + 1
+template <int RLO, int RHI, bool MATRIX>
+__device__ __forceinline__ void aff_sweep_entry(const FillArgs &A, const int o, const uint32_t *__restrict__ mat, const uint32_t nn) {
     if (blockIdx.x == 0 && threadIdx.x == 0) A.hdr->reserved = 0ull;      // the traceback's bump allocator
+    if (MATRIX) {                                                          // (before any wavefront leaves)
+        for (uint32_t x = threadIdx.x; x < 256u; x += WAVE * AFF_WAVES) aff_mkey[x] = mat[x];
+        const uint32_t n = nn - 1u;
+        for (uint32_t x = threadIdx.x; x < nn * nn; x += WAVE * AFF_WAVES) {
+            const uint32_t cq = x / nn, cr = x - cq * nn;
+            aff_mtab[x] = (cq == n || cr == n) ? A.mismatch : (int)mat[256u + x];
+        }
+        __syncthreads();
+    }
     const uint32_t pair = blockIdx.x * AFF_WAVES + (threadIdx.x >> 6);
     if (pair >= A.n_pairs) return;
     const uint32_t lane = threadIdx.x & 63u;
     const PairDesc pd = A.pairs[pair];
     const uint32_t R = uni(swmi_aff_rows_per_lane(A.reads[pd.read_id].len));
     if (R < (uint32_t)RLO || R > (uint32_t)RHI) return;
-    if (A.strict) aff_sweep_dispatch<RLO, RHI, true>(A, o, pd, R, lane);
-    else          aff_sweep_dispatch<RLO, RHI, false>(A, o, pd, R, lane);
+    if (A.strict) aff_sweep_dispatch<RLO, RHI, true, MATRIX>(A, o, pd, R, lane, nn);
+    else          aff_sweep_dispatch<RLO, RHI, false, MATRIX>(A, o, pd, R, lane, nn);
 }
 
 }  // namespace
 
 extern "C" __global__ void __launch_bounds__(WAVE * AFF_WAVES) sw_affine_sweep_kernel(const FillArgs A, const int gap_open) {
-    aff_sweep_entry<1, 4>(A, gap_open);
+    aff_sweep_entry<1, 4, false>(A, gap_open, nullptr, 0u);
 }
 extern "C" __global__ void __launch_bounds__(WAVE * AFF_WAVES) sw_affine_sweep_wide_kernel(const FillArgs A, const int gap_open) {
-    aff_sweep_entry<5, SWMI_AFF_RMAX>(A, gap_open);
+    aff_sweep_entry<5, SWMI_AFF_RMAX, false>(A, gap_open, nullptr, 0u);
+}
+extern "C" __global__ void __launch_bounds__(WAVE * AFF_WAVES) sw_affine_sweep_matrix_kernel(const FillArgs A, const int gap_open,
+                                                                                            const uint32_t *mat, const uint32_t nn) {
+    aff_sweep_entry<1, 4, true>(A, gap_open, mat, nn);
+}
+extern "C" __global__ void __launch_bounds__(WAVE * AFF_WAVES) sw_affine_sweep_matrix_wide_kernel(const FillArgs A, const int gap_open,
+                                                                                                 const uint32_t *mat, const uint32_t nn) {
+    aff_sweep_entry<5, SWMI_AFF_RMAX, true>(A, gap_open, mat, nn);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -323,6 +371,17 @@ extern "C" hipError_t swmi_launch_affine_sweep(const FillArgs *a, int32_t gap_op
     const dim3 grid((a->n_pairs + AFF_WAVES - 1) / AFF_WAVES), block(WAVE * AFF_WAVES);
     if (r_min <= 4u) hipLaunchKernelGGL(sw_affine_sweep_kernel, grid, block, 0, st, *a, (int)gap_open);
     if (r_max >= 5u) hipLaunchKernelGGL(sw_affine_sweep_wide_kernel, grid, block, 0, st, *a, (int)gap_open);
+    return hipGetLastError();
+}
+
+// the matrix sweeps: mat = the device image of the score matrix (swmi_aff_mat_words dwords), nn = its side n + 1 (2 .. 65)
+extern "C" hipError_t swmi_launch_affine_sweep_matrix(const FillArgs *a, int32_t gap_open, const uint32_t *mat, uint32_t nn, uint32_t r_min,
+                                                      uint32_t r_max, hipStream_t st) {
+    if (a->n_pairs == 0) return hipSuccess;
+    if (nn < 2u || nn > SWMI_MAT_NN_MAX) return hipErrorInvalidValue;
+    const dim3 grid((a->n_pairs + AFF_WAVES - 1) / AFF_WAVES), block(WAVE * AFF_WAVES);
+    if (r_min <= 4u) hipLaunchKernelGGL(sw_affine_sweep_matrix_kernel, grid, block, 0, st, *a, (int)gap_open, mat, nn);
+    if (r_max >= 5u) hipLaunchKernelGGL(sw_affine_sweep_matrix_wide_kernel, grid, block, 0, st, *a, (int)gap_open, mat, nn);
     return hipGetLastError();
 }
 

@@ -36,6 +36,8 @@ extern "C" hipError_t swmi_launch_traceback_split(const TraceArgs *a, uint32_t n
 extern "C" hipError_t swmi_launch_resident(const TraceArgs *a, const ResidentArgs *x, hipStream_t st);
 extern "C" hipError_t swmi_launch_tfused(const TraceArgs *a, const TFusedArgs *x, hipStream_t st);
 extern "C" hipError_t swmi_launch_affine_sweep(const FillArgs *a, int32_t gap_open, uint32_t r_min, uint32_t r_max, hipStream_t st);
+extern "C" hipError_t swmi_launch_affine_sweep_matrix(const FillArgs *a, int32_t gap_open, const uint32_t *mat, uint32_t nn, uint32_t r_min,
+                                                      uint32_t r_max, hipStream_t st);
 extern "C" hipError_t swmi_launch_affine_traceback(const TraceArgs *a, uint32_t tile_words, uint32_t ops_words, hipStream_t st);
 extern "C" hipError_t swmi_launch_encode(const uint8_t *raw, const uint64_t *raw_off, SeqDesc *desc, uint32_t *seqw,
                                          const uint8_t *lut, uint32_t n_seq, hipStream_t st);
@@ -113,6 +115,15 @@ struct PinnedBuf {
     ~PinnedBuf() { release(); }
 };
 
+// A substitution score matrix (swmi_set_score_matrix), immutable once built: contexts, stream slots and the batches of the
+// runs that use it share it, so a new matrix set while a run is in flight never touches that run's copy.
+struct ScoreMatrix {
+    uint64_t gen = 0;                       // unique per matrix set (the prep cache and the batch's device copy key on it)
+    uint32_t n = 0;                         // symbols
+    int32_t max_entry = 0;                  // the largest score (path_bound)
+    std::vector<uint32_t> image;            // the device image: swmi_aff_mat_words(n + 1) dwords (swmi_device.h)
+};
+
 // ------------------------------------------------------------------------------------------
 // context
 // ------------------------------------------------------------------------------------------
@@ -137,6 +148,7 @@ struct swmi_ctx {
     int64_t spin_us = 2000;                 // how long a run polls its stream for completion before it blocks (a batch is sub-millisecond)
     uint32_t dbg_strip_spins = 0;           // test knob: spin budget of the strip pipeline (0 = default)
     uint32_t dbg_reverse_strips = 0;        // test knob: strip items dispatched consumer-first
+    uint32_t dbg_async_delay_us = 0;        // test knob: the async worker waits this long before it starts a job
     uint32_t auto_ties_x100 = 300;          // automatic traceback grain: split when a sampled pair has this many tied maxima (x 1/100) on average
     uint32_t col_chunks = 0;                // test knob: force this many column chunks per pair (0 = automatic)
     int tb_split = -1;                      // mode-1 traceback grain: -1 automatic, 0 one workgroup per pair, 1 one wavefront per window / alignment
@@ -151,6 +163,8 @@ struct swmi_ctx {
     bool cell_cap_set = false;              // cell_cap given by the caller (otherwise small launches get longer lists)
     int32_t gap_open = 0;                   // affine gaps: a gap of length k costs gap_open + k * gap (0: linear)
     int affine = -1;                        // -1: the affine kernels (mode 3) when gap_open != 0; 1: always
+    std::mutex mat_mu;                      // guards `matrix` (not ctx->mu: setting a matrix does not wait for a run)
+    std::shared_ptr<const ScoreMatrix> matrix;   // swmi_set_score_matrix; a run with one takes the affine kernels
     // swmi_batch_run_async: one run in flight on the context's own host thread
     std::thread worker;
     std::mutex job_mu;
@@ -158,6 +172,8 @@ struct swmi_ctx {
     std::atomic<int> job_state{0};          // 0 idle, 1 submitted, 2 finished, 3 quit
     swmi_batch *job_batch = nullptr;
     swmi_params job_params{};
+    std::shared_ptr<const ScoreMatrix> job_matrix;   // the matrix when swmi_batch_run_async was called
+    uint32_t job_delay_us = 0;                       // debug_async_delay_us when swmi_batch_run_async was called
     int job_rc = 0;
     std::string job_err;
 };
@@ -221,6 +237,9 @@ struct swmi_batch {
     bool work_tfused = false;               // the schedule's workspace sizes leave room for sw_tfused_kernel's column checkpoints
     uint32_t eff_mode = 1;                  // pipeline of the current run (3: the affine kernels, swmi_affine.hip)
     int32_t gap_open = 0;                   // the context's gap_open when the run started (mode 3)
+    std::shared_ptr<const ScoreMatrix> mat; // the score matrix of the current run (null: none); keeps its host image alive
+    DevBuf d_mat;                           // ... its device image, copied on the run's stream
+    uint64_t d_mat_gen = 0;                 // generation of the matrix in d_mat (0: none)
     uint64_t work_cells = 0;
     std::vector<uint8_t> pairs_on_device;   // image of the PairDesc array currently in d_pairs
     const void *pairs_dev_ptr = nullptr;
@@ -241,6 +260,7 @@ struct swmi_batch {
         int resident_opt = -1;
         int tfused_opt = -1;
         uint32_t aff_r_min = 0, aff_r_max = 0;      // mode 3: rows per lane of the chunk's shortest and longest read
+        uint64_t mat_gen = 0;                       // the score matrix's generation (0: none): it bounds the paths
         size_t n_tf = 0;
         uint32_t tf_max_m = 0, tf_max_n = 0, tf_max_path = 0;
         bool exact = false, scores_only = false;
@@ -382,6 +402,9 @@ extern "C" int swmi_set_option(swmi_ctx *ctx, const char *name, int64_t value) {
         ctx->dbg_strip_spins = (uint32_t)value;
     } else if (!strcmp(name, "debug_reverse_strips")) {
         ctx->dbg_reverse_strips = value != 0;
+    } else if (!strcmp(name, "debug_async_delay_us")) {
+        if (value < 0 || value > 10000000) return fail(SWMI_ERR_INVALID, "debug_async_delay_us out of range");
+        ctx->dbg_async_delay_us = (uint32_t)value;
     } else if (!strcmp(name, "tfused")) {
         if (value < -1 || value > 1) return fail(SWMI_ERR_INVALID, "tfused must be -1 (automatic), 0 or 1");
         ctx->tfused = (int)value;
@@ -418,6 +441,45 @@ extern "C" int swmi_set_option(swmi_ctx *ctx, const char *name, int64_t value) {
     } else {
         return fail(SWMI_ERR_INVALID, "unknown option '%s'", name);
     }
+    return SWMI_OK;
+}
+
+extern "C" int swmi_set_score_matrix(swmi_ctx *ctx, const uint8_t *alphabet, uint32_t n, const int32_t *scores) {
+    if (!ctx) return fail(SWMI_ERR_INVALID, "null context");
+    if (n == 0) {                                          // clears the matrix
+        std::lock_guard<std::mutex> g(ctx->mat_mu);
+        ctx->matrix.reset();
+        return SWMI_OK;
+    }
+    if (n > SWMI_MAT_MAX_SYMBOLS) return fail(SWMI_ERR_INVALID, "a score matrix has at most %u symbols, got %u", SWMI_MAT_MAX_SYMBOLS, n);
+    if (!alphabet || !scores) return fail(SWMI_ERR_INVALID, "alphabet or scores is null");
+    const uint8_t *T = code_table();
+    uint32_t cls[256];
+    for (uint32_t c = 0; c < 256; c++) cls[c] = n;         // class n: outside the alphabet
+    for (uint32_t i = 0; i < n; i++) {
+        const uint8_t c = T[alphabet[i]];
+        if (cls[c] != n)
+            return fail(SWMI_ERR_INVALID, "score matrix symbols %u and %u are the same symbol (0x%02x, 0x%02x)", cls[c], i,
+                        alphabet[cls[c]], alphabet[i]);
+        cls[c] = i;
+    }
+    auto M = std::make_shared<ScoreMatrix>();
+    M->n = n;
+    M->max_entry = INT32_MIN;
+    const uint32_t nn = n + 1;
+    M->image.assign(swmi_aff_mat_words(nn), 0u);
+    for (uint64_t x = 0; x < (uint64_t)n * n; x++) {
+        if (std::llabs((int64_t)scores[x]) > (1 << 20))
+            return fail(SWMI_ERR_INVALID, "score matrix entry [%u][%u] = %d: |entries| must be <= 2^20", (uint32_t)(x / n),
+                        (uint32_t)(x % n), scores[x]);
+        M->max_entry = std::max(M->max_entry, scores[x]);
+        M->image[256 + (x / n) * nn + x % n] = (uint32_t)scores[x];
+    }
+    for (uint32_t c = 0; c < 256; c++) M->image[c] = cls[c] * 4u | ((cls[c] == n ? c : 0x1FFu) << 16);
+    static std::atomic<uint64_t> gens{0};
+    M->gen = ++gens;
+    std::lock_guard<std::mutex> g(ctx->mat_mu);
+    ctx->matrix = std::move(M);
     return SWMI_OK;
 }
 
@@ -487,7 +549,7 @@ extern "C" void swmi_batch_free(swmi_ctx *ctx, swmi_batch *b) {
     b->d_dir.release(); b->d_seam.release(); b->d_result.release(); b->d_cells.release();
     b->d_cells_off.release(); b->d_cells_cap.release(); b->d_dbg.release(); b->d_dbg2.release();
     b->d_strip_items.release(); b->d_progress.release(); b->d_col_items.release(); b->d_win_off.release(); b->d_queue.release(); b->d_res_items.release();
-    b->d_tf_items.release();
+    b->d_tf_items.release(); b->d_mat.release();
     b->h_result.release();
     delete b;
 }
@@ -594,11 +656,12 @@ inline uint64_t rec_words(uint32_t n_ops, bool strings) {
 #define SWMI_RES_CELL_CAP 128u            // maximum cells a resident pair lists in LDS (sw_resident_pairs_kernel)
 
 // longest possible traceback of an n x m pair: A + I <= m rows, A + D <= n columns, and -- with match > 0 > gap -- the
-// score match*A + gap*(I + D) must stay positive (`while (score > 0)`), which caps the gap moves
-static uint64_t path_bound(uint64_t n_, uint64_t m_, const swmi_params &p) {
+// score match*A + gap*(I + D) must stay positive (`while (score > 0)`), which caps the gap moves.  smax: the largest score of
+// one alignment move (match; with a score matrix the larger of match and its largest entry)
+static uint64_t path_bound(uint64_t n_, uint64_t m_, const swmi_params &p, int32_t smax) {
     uint64_t path = n_ + m_;
-    if (p.match > 0 && p.gap < 0 && p.mismatch <= p.match) {
-        const uint64_t g = (uint64_t)(-(int64_t)p.gap), mt = (uint64_t)p.match;
+    if (smax > 0 && p.gap < 0 && p.mismatch <= smax) {
+        const uint64_t g = (uint64_t)(-(int64_t)p.gap), mt = (uint64_t)smax;
         path = std::min(path, std::min(m_ + std::min(n_, mt * m_ / g), n_ + std::min(m_, mt * n_ / g)));
     }
     return path;
@@ -650,7 +713,8 @@ static int prepare_chunk(RunState &rs, const std::vector<Work> &work, size_t lo,
                           memcmp(&pr.params, &b->params, sizeof(swmi_params)) == 0 && b->pairs_dev_ptr == b->d_pairs.p &&
                           b->pairs_on_device.size() == np * sizeof(PairDesc) && pr.col_chunks_opt == ctx->col_chunks &&
                           pr.reverse_strips == (ctx->dbg_reverse_strips != 0) && pr.resident_opt == ctx->resident &&
-                          pr.tfused_opt == ctx->tfused && pr.exact == (cells_exact != nullptr) && pr.scores_only == (ctx->scores_only != 0);
+                          pr.tfused_opt == ctx->tfused && pr.exact == (cells_exact != nullptr) && pr.scores_only == (ctx->scores_only != 0) &&
+                          pr.mat_gen == (b->mat ? b->mat->gen : 0u);
     if (prepared) {
         dir_words = pr.dir_words; seam_words = pr.seam_words; max_path = pr.max_path; max_read = pr.max_read;
         n_strip_items = pr.n_strip_items; n_col_items = pr.n_col_items; n_windows = pr.n_windows;
@@ -677,7 +741,7 @@ static int prepare_chunk(RunState &rs, const std::vector<Work> &work, size_t lo,
     auto res_need_words = [&](uint32_t m_, uint32_t n_, uint32_t &opw) -> uint64_t {
         const uint32_t R_ = swmi_rows_per_lane(m_), lact = (m_ + R_ - 1) / R_;
         const uint64_t nblk = ((uint64_t)n_ + lact - 1 + 15) / 16, n_ck = (nblk + SWMI_CK_BLOCKS - 1) / SWMI_CK_BLOCKS;
-        opw = (uint32_t)((path_bound(n_, m_, P) + 15) / 16 + 1);
+        opw = (uint32_t)((path_bound(n_, m_, P, P.match) + 15) / 16 + 1);
         return nblk * R_ * 64 + ((n_ck + 1) & ~1ull) + 2ull * res_cell_cap + 64ull * opw + (n_ + 3) / 4 + 1 + (m_ + 3) / 4 + 1 + 8 +
                128;                                           // (SWMI_EMIT_SCRATCH_WORDS: the string scratch of swmi_emit.h)
     };
@@ -706,6 +770,8 @@ static int prepare_chunk(RunState &rs, const std::vector<Work> &work, size_t lo,
     pd.resize(np);
     if (b->eff_mode == 1) win_off.resize(np + 1);
     uint32_t pb_m = 0xFFFFFFFFu, pb_n = 0xFFFFFFFFu, pb_val = 0;
+    // (a score matrix entry above match lets a positive path run longer: the bound takes the largest score of one move)
+    const int32_t smax = b->mat ? std::max(b->params.match, b->mat->max_entry) : b->params.match;
     for (size_t k = 0; k < np; k++) {
         const Work &w = work[lo + k];
         PairDesc d{};
@@ -729,7 +795,7 @@ static int prepare_chunk(RunState &rs, const std::vector<Work> &work, size_t lo,
             d.pad = SWMI_PAD_RESIDENT;                  // (every other kernel skips the pair)
             tf_items.push_back((uint32_t)k);
             tf_max_m = std::max(tf_max_m, m_); tf_max_n = std::max(tf_max_n, n_);
-            tf_max_path = std::max<uint32_t>(tf_max_path, (uint32_t)path_bound(n_, m_, P));
+            tf_max_path = std::max<uint32_t>(tf_max_path, (uint32_t)path_bound(n_, m_, P, P.match));
         } else if (res_fit) {
             d.pad = SWMI_PAD_RESIDENT;
             res_items.push_back((uint32_t)k);
@@ -814,7 +880,7 @@ static int prepare_chunk(RunState &rs, const std::vector<Work> &work, size_t lo,
             }
         }
         pd[k] = d;
-        if (m_ != pb_m || n_ != pb_n) { pb_m = m_; pb_n = n_; pb_val = (uint32_t)path_bound(n_, m_, b->params); }   // (runs of equal lengths)
+        if (m_ != pb_m || n_ != pb_n) { pb_m = m_; pb_n = n_; pb_val = (uint32_t)path_bound(n_, m_, b->params, smax); }   // (runs of equal lengths)
         max_path = std::max<uint32_t>(max_path, pb_val);
         max_read = std::max(max_read, m_);
         aff_r_min = std::min(aff_r_min, swmi_aff_rows_per_lane(m_));
@@ -902,6 +968,7 @@ static int prepare_chunk(RunState &rs, const std::vector<Work> &work, size_t lo,
         pr.col_chunks_opt = ctx->col_chunks; pr.reverse_strips = ctx->dbg_reverse_strips != 0;
         pr.scores_only = ctx->scores_only != 0;
         pr.aff_r_min = aff_r_min; pr.aff_r_max = aff_r_max;
+        pr.mat_gen = b->mat ? b->mat->gen : 0u;
     }
     rs.prep_us += std::chrono::duration<double, std::micro>(p1 - p0).count();
     rs.prep_upload_us += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - p1).count();
@@ -1227,7 +1294,10 @@ static int run_chunk(RunState &rs, const std::vector<Work> &work, size_t lo, siz
         if (ctx->profiling && !ext_timing) HIP_TRY(hipEventRecord(ctx->ev[0], ctx->stream));
         if (attempt == 0 && !whole_only) {       // the workspace survives an arena-overflow retry
             if (fa.n_strip_items) HIP_TRY(hipMemsetAsync(fa.progress, 0, (size_t)fa.n_strip_items * sizeof(uint32_t), ctx->stream));
-            if (b->eff_mode == 3) HIP_TRY(swmi_launch_affine_sweep(&fa, b->gap_open, pr.aff_r_min, pr.aff_r_max, ctx->stream));
+            if (b->eff_mode == 3 && b->mat)
+                HIP_TRY(swmi_launch_affine_sweep_matrix(&fa, b->gap_open, b->d_mat.as<uint32_t>(), b->mat->n + 1u, pr.aff_r_min, pr.aff_r_max,
+                                                        ctx->stream));
+            else if (b->eff_mode == 3) HIP_TRY(swmi_launch_affine_sweep(&fa, b->gap_open, pr.aff_r_min, pr.aff_r_max, ctx->stream));
             else HIP_TRY(swmi_launch_fill(&fa, ctx->stream, ext_timing ? ctx->ev[0] : nullptr, ext_timing ? ctx->ev[1] : nullptr));
             rs.launches++;
         }
@@ -1513,7 +1583,13 @@ static int ensure_indexed(swmi_batch *b) {
     return SWMI_OK;
 }
 
-extern "C" int swmi_batch_run(swmi_ctx *ctx, swmi_batch *b, const swmi_params *p) {
+static std::shared_ptr<const ScoreMatrix> ctx_matrix(swmi_ctx *ctx) {
+    std::lock_guard<std::mutex> g(ctx->mat_mu);
+    return ctx->matrix;
+}
+
+// mat: the score matrix the run uses (the context's when the run was asked for), or null
+static int batch_run(swmi_ctx *ctx, swmi_batch *b, const swmi_params *p, std::shared_ptr<const ScoreMatrix> mat) {
     if (!ctx || !b || !p) return fail(SWMI_ERR_INVALID, "null argument");
     if (p->tie_mode != SWMI_TIE_SERIAL && p->tie_mode != SWMI_TIE_STRICT)
         return fail(SWMI_ERR_INVALID, "unknown tie_mode %d", p->tie_mode);
@@ -1523,7 +1599,7 @@ extern "C" int swmi_batch_run(swmi_ctx *ctx, swmi_batch *b, const swmi_params *p
     if (p->types[0] == p->types[1] || p->types[0] == p->types[2] || p->types[1] == p->types[2])
         return fail(SWMI_ERR_UNSUPPORTED, "alignTypes a/i/d must be pairwise distinct");
     std::lock_guard<std::mutex> g(ctx->mu);
-    const bool affine = ctx->affine == 1 || ctx->gap_open != 0;
+    const bool affine = ctx->affine == 1 || ctx->gap_open != 0 || mat != nullptr;   // (a score matrix runs on the affine kernels only)
     if (affine) {
         // the bounds within which every sum of the affine recurrence fits int32 (DESIGN.md "Affine gaps"); checked before
         // anything is launched
@@ -1571,6 +1647,18 @@ extern "C" int swmi_batch_run(swmi_ctx *ctx, swmi_batch *b, const swmi_params *p
     b->eff_mode = (ctx->mode == 1 && (p->mismatch > 0 || p->gap > 0)) ? 2u : ctx->mode;
     b->gap_open = ctx->gap_open;
     if (affine) b->eff_mode = 3;                         // the affine kernels (swmi_affine.hip): no other pipeline option applies
+    b->mat = std::move(mat);
+    if (b->mat && b->d_mat_gen != b->mat->gen) {
+        // the run's own device copy, on its stream, complete before the run goes on: whatever an earlier (failed) run left on
+        // the stream is done with d_mat, and the pageable host image is read before anything can release it.  Only when the
+        // matrix changes: a batch re-run under the same matrix copies nothing.
+        int rc0;
+        if ((rc0 = b->d_mat.reserve((size_t)swmi_aff_mat_words(SWMI_MAT_NN_MAX) * 4))) return rc0;
+        b->d_mat_gen = 0;
+        HIP_TRY(hipMemcpyAsync(b->d_mat.p, b->mat->image.data(), b->mat->image.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        b->d_mat_gen = b->mat->gen;
+    }
     // (measured, profiles/r02/sweeps_*.md: with ~5 alignments per pair the split traceback wins up to ~200 pairs; from a
     // few hundred pairs on one workgroup per pair keeps every SIMD busy anyway and its teams share the window re-sweeps)
     if (ctx->tb_split < 0 && !ctx->scores_only && b->eff_mode == 1 && n_pairs >= 64 && n_pairs <= 256 &&
@@ -1615,7 +1703,7 @@ extern "C" int swmi_batch_run(swmi_ctx *ctx, swmi_batch *b, const swmi_params *p
         uint32_t max_n = 0, max_m = 0;
         for (const auto &d : b->ref_desc) max_n = std::max(max_n, d.len);
         for (const auto &d : b->read_desc) max_m = std::max(max_m, d.len);
-        if (traceback_lds_bytes(0, path_bound(max_n, max_m, *p), max_m) > 160ull * 1024)
+        if (traceback_lds_bytes(0, path_bound(max_n, max_m, *p, p->match), max_m) > 160ull * 1024)
             b->eff_mode = (p->mismatch > 0 || p->gap > 0) ? 2u : 1u;
     }
     if (b->work_mode != (int)b->eff_mode || b->work_tfused != (ctx->tfused == 1)) {
@@ -1748,6 +1836,11 @@ extern "C" int swmi_batch_run(swmi_ctx *ctx, swmi_batch *b, const swmi_params *p
     return SWMI_OK;
 }
 
+extern "C" int swmi_batch_run(swmi_ctx *ctx, swmi_batch *b, const swmi_params *p) {
+    if (!ctx || !b || !p) return fail(SWMI_ERR_INVALID, "null argument");
+    return batch_run(ctx, b, p, ctx_matrix(ctx));
+}
+
 // ---- asynchronous run: the same swmi_batch_run on the context's own host thread -------------------------------
 // The caller gets its thread back while the GPU works (a Spark task can prepare its next partition, bench.py's rank
 // can do the previous step's reduce).  The helper thread spins briefly between jobs, so back-to-back runs start
@@ -1763,7 +1856,8 @@ static void swmi_worker_loop(swmi_ctx *ctx) {
             st = ctx->job_state.load();
         }
         if (st == 3) return;
-        const int rc = swmi_batch_run(ctx, ctx->job_batch, &ctx->job_params);
+        if (ctx->job_delay_us) std::this_thread::sleep_for(std::chrono::microseconds(ctx->job_delay_us));
+        const int rc = batch_run(ctx, ctx->job_batch, &ctx->job_params, std::move(ctx->job_matrix));
         ctx->job_rc = rc;
         ctx->job_err = rc ? swmi_last_error() : "";
         { std::lock_guard<std::mutex> lk(ctx->job_mu); ctx->job_state.store(2, std::memory_order_release); }
@@ -1778,6 +1872,8 @@ extern "C" int swmi_batch_run_async(swmi_ctx *ctx, swmi_batch *b, const swmi_par
     if (!ctx->worker.joinable()) ctx->worker = std::thread(swmi_worker_loop, ctx);
     ctx->job_batch = b;
     ctx->job_params = *p;
+    ctx->job_matrix = ctx_matrix(ctx);                 // (the matrix set now, whatever is set while the run is in flight)
+    ctx->job_delay_us = ctx->dbg_async_delay_us;
     { std::lock_guard<std::mutex> lk(ctx->job_mu); ctx->job_state.store(1, std::memory_order_release); }
     ctx->job_cv.notify_all();
     return SWMI_OK;
@@ -2320,6 +2416,7 @@ extern "C" int swmi_stream_open(swmi_ctx *ctx, const swmi_params *p, const uint8
         sl.ctx->auto_ties_x100 = ctx->auto_ties_x100; sl.ctx->arena_words_per_pair = ctx->arena_words_per_pair;
         sl.ctx->device_strings = ctx->device_strings; sl.ctx->scores_only = ctx->scores_only;
         sl.ctx->gap_open = ctx->gap_open; sl.ctx->affine = ctx->affine;
+        sl.ctx->matrix = ctx_matrix(ctx);
         sl.ctx->spin_us = 50;                    // (a chunk takes milliseconds: the slot threads mostly block)
         sl.shell = new swmi_batch;
     }

@@ -280,6 +280,12 @@ SWMI_HD static inline uint32_t swmi_aff_blocks(uint32_t m, uint32_t n) {
 SWMI_HD static inline uint64_t swmi_aff_dir_words(uint32_t m, uint32_t n) {
     return (uint64_t)swmi_aff_blocks(m, n) * swmi_aff_rows_per_lane(m) * 64u;
 }
+// score matrices (swmi_set_score_matrix) on the affine sweeps: at most 64 symbols, plus class n = outside the alphabet.
+// Device image: 256 key dwords by base code (class * 4 | hi << 16, hi = the code outside the alphabet, else 0x1FF), then the
+// (n+1) x (n+1) int32 scores, row = read class, column = reference class (row and column n are not read: the kernel fills them).
+#define SWMI_MAT_MAX_SYMBOLS 64u
+#define SWMI_MAT_NN_MAX (SWMI_MAT_MAX_SYMBOLS + 1u)
+SWMI_HD static inline uint32_t swmi_aff_mat_words(uint32_t nn) { return 256u + nn * nn; }
 
 // int32 seam rows of a pair whose read spans several strips: one row of n+1 per strip
 SWMI_HD static inline uint64_t swmi_seam_words(uint32_t m, uint32_t n) {

@@ -167,6 +167,9 @@ def _rank_main(args):
         if len(scores) == 4:                                # match,mismatch,gap,gapOpen: affine gaps on this rank's context
             ctx.set_option("gap_open", scores[3])
             scores = scores[:3]
+        if args.matrix:                                     # substitution scores on this rank's context (NCBI text format)
+            from . import matrix as _matrix
+            ctx.set_score_matrix(_matrix.load(args.matrix))
         t0 = time.perf_counter()
         st = run_rank(ctx, args.ref_dir, args.in_dir, args.out_dir, rank, world, args.delimiter, args.out_name, args.out_ext,
                       sw.make_params(scores, None, tie), args.stream_chunk_bytes, 0, 0,
@@ -199,6 +202,9 @@ def main(argv=None):
     ap.add_argument("--out-ext", default=".txt")
     ap.add_argument("--scores", default="5,-3,-4",
                     help="match,mismatch,gap (Distribution.java:36), or match,mismatch,gap,gapOpen for affine gaps (gapOpen <= 0)")
+    ap.add_argument("--matrix", default=None,
+                    help="a substitution score matrix file in the NCBI text format (row = read base, column = reference base); "
+                         "bases outside its alphabet score match / mismatch from --scores")
     ap.add_argument("--tie", choices=("serial", "strict"), default="serial",
                     help="serial: SmithWaterman's aligner (NoDistribution, DistributeReference); strict: DistributedSW's (DistributeAlgorithm)")
     ap.add_argument("--stream-chunk-bytes", type=int, default=512 << 10, help="sequence bytes per streamed chunk")
