@@ -34,6 +34,8 @@ public class GpuSmithWaterman
 			ByteBuffer refBytes , long[] refOff , int nRefs , ByteBuffer readBytes , long[] readOff , int nReads ) ;
 	/** affine gaps on the context: alignScores { match , mismatch , gap , gapOpen } -- a gap of length k costs gapOpen + k * gap */
 	static native void nativeSetGapOpen( long ctx , int gapOpen ) ;
+	/** end-to-end alignment on the context: ALIGN_LOCAL, ALIGN_FIT or ALIGN_GLOBAL (include/swmi.h: option "align_mode") */
+	static native void nativeSetAlignMode( long ctx , int alignMode ) ;
 	/** substitution scores on the context: alphabet = n ISO-8859-1 symbols, scores = n * n, row = read base; null clears */
 	static native void nativeSetScoreMatrix( long ctx , byte[] alphabet , int[] scores ) ;
 	static native void nativeFreeBatch( long ctx , long batch ) ;
@@ -60,6 +62,22 @@ public class GpuSmithWaterman
 	{
 		// executor threads outlive tasks; whatever is still open when the JVM goes down is destroyed here
 		Runtime.getRuntime().addShutdownHook( new Thread() { @Override public void run() { releaseAllContexts() ; } } ) ;
+	}
+
+	public static final int ALIGN_LOCAL = 0 , ALIGN_FIT = 1 , ALIGN_GLOBAL = 2 ;
+	/** what every context aligns end to end from its next batch on (applied next to gapOpen, before every batch) */
+	private static volatile int ALIGN_MODE = ALIGN_LOCAL ;
+
+	/**
+	 * ALIGN_LOCAL (the default): Smith-Waterman.  ALIGN_FIT: the whole read against any stretch of the reference.  ALIGN_GLOBAL: the
+	 * whole read against the whole reference.  Totals may then be zero or negative, and every match site spells the whole read.
+	 * For every batch aligned from now on, on every executor thread.
+	 */
+	public static void setAlignMode( int alignMode )
+	{
+		if( alignMode != ALIGN_LOCAL && alignMode != ALIGN_FIT && alignMode != ALIGN_GLOBAL )
+			throw new IllegalArgumentException( "alignMode must be ALIGN_LOCAL, ALIGN_FIT or ALIGN_GLOBAL: " + alignMode ) ;
+		ALIGN_MODE = alignMode ;
 	}
 
 	/** the score matrix every context applies before its next batch: { alphabet , scores } (null: none), and its version */
@@ -194,6 +212,7 @@ public class GpuSmithWaterman
 			// alignScores may carry a fourth entry, gapOpen (<= 0): affine gaps; three entries keep the linear scoring
 			if( sc.length != 3 && sc.length != 4 ) throw new IllegalArgumentException( "alignScores needs 3 or 4 entries: " + sc.length ) ;
 			nativeSetGapOpen( ctx , sc.length == 4 ? sc[3] : 0 ) ;
+			nativeSetAlignMode( ctx , ALIGN_MODE ) ;
 			applyScoreMatrix( nc ) ;
 			long batch = nativeAlignBatch( ctx , sc[0] , sc[1] , sc[2] , TIE_SERIAL , types , refBuf , refOff , n , readBuf , readOff , reads.size() ) ;
 			try

@@ -49,6 +49,13 @@ JNIEXPORT void JNICALL Java_sw_GpuSmithWaterman_nativeSetGapOpen(JNIEnv *env, jc
     if (swmi_shim_set_gap_open((swmi_ctx *)(intptr_t)ctx, gapOpen, err, sizeof err) != SWMI_OK) throw_msg(env, err);
 }
 
+/* end-to-end alignment on this context from now on: 0 local, 1 fit (the whole read), 2 global (the whole read and reference) */
+JNIEXPORT void JNICALL Java_sw_GpuSmithWaterman_nativeSetAlignMode(JNIEnv *env, jclass cls, jlong ctx, jint alignMode) {
+    char err[640];
+    (void)cls;
+    if (swmi_shim_set_align_mode((swmi_ctx *)(intptr_t)ctx, alignMode, err, sizeof err) != SWMI_OK) throw_msg(env, err);
+}
+
 /* a substitution score matrix on this context from now on: alphabet = n ISO-8859-1 symbols, scores = int[n * n], row = read base;
  * alphabet == null clears it */
 JNIEXPORT void JNICALL Java_sw_GpuSmithWaterman_nativeSetScoreMatrix(JNIEnv *env, jclass cls, jlong ctx, jbyteArray alphabet,

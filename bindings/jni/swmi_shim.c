@@ -31,6 +31,14 @@ int swmi_shim_set_gap_open(swmi_ctx *ctx, int32_t gap_open, char *err, size_t er
     return SWMI_OK;
 }
 
+int swmi_shim_set_align_mode(swmi_ctx *ctx, int32_t align_mode, char *err, size_t err_len) {
+    int rc;
+    if (!ctx) return shim_fail(SWMI_ERR_INVALID, err, err_len, "nativeSetAlignMode", "context handle is 0");
+    if ((rc = swmi_set_option(ctx, "align_mode", align_mode)) != SWMI_OK)
+        return shim_fail(rc, err, err_len, "nativeSetAlignMode", swmi_last_error());
+    return SWMI_OK;
+}
+
 int swmi_shim_set_score_matrix(swmi_ctx *ctx, const signed char *alphabet, size_t n, const int32_t *scores, size_t n_scores,
                                char *err, size_t err_len) {
     int rc;

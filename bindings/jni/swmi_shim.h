@@ -29,6 +29,10 @@ int swmi_shim_align_batch(swmi_ctx *ctx, int32_t match, int32_t mismatch, int32_
 /* nativeSetGapOpen: affine gaps on this context (swmi_set_option "gap_open"): a gap of length k then costs gap_open + k * gap.
  * gap_open <= 0; 0 (the default) is the linear scoring.  Applies to the batches the context aligns from then on. */
 int swmi_shim_set_gap_open(swmi_ctx *ctx, int32_t gap_open, char *err, size_t err_len);
+/* nativeSetAlignMode: what the context aligns end to end from then on (swmi_set_option "align_mode"): SWMI_ALIGN_LOCAL (0, the
+ * default), SWMI_ALIGN_FIT (1: the whole read against any stretch of the reference) or SWMI_ALIGN_GLOBAL (2: the whole read against
+ * the whole reference).  Any other value is SWMI_ERR_INVALID and leaves the context as it was. */
+int swmi_shim_set_align_mode(swmi_ctx *ctx, int32_t align_mode, char *err, size_t err_len);
 
 /* nativeSetScoreMatrix: a substitution score matrix on this context (swmi_set_score_matrix): `alphabet` = n symbols narrowed to
  * bytes (ISO-8859-1), `scores` = n * n entries, row = read base, column = reference base (n_scores must be n * n).  n = 0 clears

@@ -47,6 +47,11 @@ typedef enum swmi_status {
     SWMI_ERR_RANGE        = -6   /* index out of range in an accessor                         */
 } swmi_status;
 
+/* What is aligned end to end (swmi_set_option "align_mode"). */
+#define SWMI_ALIGN_LOCAL  0  /* Smith-Waterman: any stretch of the read against any stretch of the reference (the default) */
+#define SWMI_ALIGN_FIT    1  /* the whole read against any stretch of the reference ("glocal", semi-global)              */
+#define SWMI_ALIGN_GLOBAL 2  /* Needleman-Wunsch: the whole read against the whole reference                              */
+
 /* Which reference aligner's tie-breaking is reproduced. */
 #define SWMI_TIE_SERIAL 0  /* SmithWaterman.GetCellScore, '>=' chain: a > i > d (SmithWaterman.java:223-249);
                               max cells in row-major order (SmithWaterman.java:157-185)                        */
@@ -122,6 +127,17 @@ void        swmi_default_params(swmi_params *p);
  *                SWMI_ERR_UNSUPPORTED before anything is launched.  scores_only, device_strings, zero_copy, cell_cap, max_workspace_bytes,
  *                arena_words_per_pair and profiling apply to affine runs; mode, tb_split, resident, tfused, col_chunks and debug_* do not.
  * affine: -1 (default) the affine kernels only when gap_open != 0; 1 always, also at gap_open = 0 (where they give the linear results).
+ * align_mode (default SWMI_ALIGN_LOCAL; any value but the three is SWMI_ERR_INVALID and leaves the context as it was): SWMI_ALIGN_FIT aligns
+ *                the WHOLE read against any stretch of the reference, SWMI_ALIGN_GLOBAL the whole read against the whole reference -- the
+ *                Gotoh recurrence of gap_open without the floor at 0, with H(i,0) = gap_open + i * gap and H(0,j) = 0 (fit) or
+ *                gap_open + j * gap (global); the pair's score is the maximum of the last read row (fit: every tied column is a maximum
+ *                cell, ascending) or H(m,n) (global), and may be zero or negative: SWMI_PAIR_DEGENERATE is never set.  Every alignment spells
+ *                the whole read (and, global, the whole reference); `begin` is the 1-based column of the first reference base it consumes
+ *                (the end column if it consumes none).  Such a run takes the affine kernels whatever gap_open / affine say (swmi_batch_mode
+ *                = 3), with or without a matrix, within the affine bounds; global mode also needs
+ *                3 * |gap_open| + (64 * ceil(m / 64) + n) * |gap| <= 2^31 for the longest read m and reference n of the batch, else
+ *                SWMI_ERR_UNSUPPORTED before anything is launched.  A pair with an empty side scores 0 with no alignments in every mode.
+ *                A run (async runs and stream slots included) takes the value set when it was asked for.
  * Further knobs: spin_us (how long a run polls its stream before it blocks, default 2000); col_chunks (0 automatic,
  * 1 never, N > 1 force up to N column chunks per pair: a launch of few pairs with long references is swept by several
  * wavefronts per pair -- a read of more than 256 rows by several strip pipelines); debug_strip_spins / debug_reverse_strips (tests of the strip pipeline's give-up path);
@@ -172,7 +188,7 @@ typedef struct swmi_timing {
     uint32_t tfused_pairs;      /* pairs swept in the transposed layout and traced back by the same wavefront        */
 } swmi_timing;
 int  swmi_batch_timing(const swmi_batch *b, swmi_timing *t);
-/* The kernel pipeline (0, 1 or 2, see swmi_set_option "mode"; 3: the affine kernels, option "gap_open" or a score matrix) the last run
+/* The kernel pipeline (0, 1 or 2, see swmi_set_option "mode"; 3: the affine kernels, option "gap_open", "align_mode" or a score matrix) the last run
  * of the batch used. */
 int  swmi_batch_mode(const swmi_batch *b, int *mode);
 

@@ -12,6 +12,9 @@ LIB_PATH = os.environ.get("SWMI_LIB") or os.path.join(_HERE, "lib", "libswmi.so"
 
 TIE_SERIAL = 0
 TIE_STRICT = 1
+ALIGN_LOCAL = 0      # option "align_mode": Smith-Waterman (the default)
+ALIGN_FIT = 1        # the whole read against any stretch of the reference
+ALIGN_GLOBAL = 2     # the whole read against the whole reference
 PAIR_DEGENERATE = 0x1
 
 

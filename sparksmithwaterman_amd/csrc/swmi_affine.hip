@@ -26,10 +26,21 @@
 //   the wave instead of its code: the cell reads tab at byte offset q.lo + key.lo, and scores match instead when both high
 //   halves are equal (the same code outside the alphabet -- today's equality rule).
 //
+// sw_affine_sweep_{fit,global}[_matrix][_wide]_kernel: the end-to-end modes (option "align_mode", DESIGN.md "End-to-end
+//   modes"): the same sweep with MODE = 1 (fit: the whole read against any stretch of the reference) or 2 (global).  No floor
+//   at 0 on E, F and H, so the direction is always 1..3; H of a lane's rows starts at the column-0 value o + i*e and E at
+//   H(i,0) + o (which gives E(i,1) = H(i,0) + o + e with xE = 0: no -inf needed); lane 0's feed from above is row 0 of the
+//   mode (H = 0 in fit mode, o + j*e in global mode; F(0,j) := H(0,j) + o, the same trick).  The maximum is taken over row m
+//   only -- one lane, one row slot -- from INT32_MIN up: every column j of row m that ties (fit) or the one cell (m,n) (global).
+//   The x bits come from compares: the operands may be negative and their difference need not fit int32.
+//
 // sw_affine_traceback_kernel: one wavefront per (pair, slot); slot s walks the pair's maximum cells s, s + S, ...  The walk
 //   is the three-state machine of DESIGN.md "Affine gaps"; the field is staged in LDS a tile of consecutive 8-step blocks at a
 //   time (a path never moves to a later step), the ops are packed 16 per dword in LDS, and the record goes out through
 //   swmi_emit.h with rank SWMI_RANK_BY_CELL (the host orders a pair's records by cell).
+// sw_affine_traceback_{fit,global}_kernel: the walk of the end-to-end modes.  It ends at row 0, not at a code 0; at column 0
+//   the rest of the read is inserted without touching the field; global mode then deletes the rest of the reference;
+//   `begin` follows the moves that consume a reference base.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "swmi_device.h"
@@ -45,6 +56,10 @@
 #define AFF_DIAG 1u
 #define AFF_INS  2u
 #define AFF_DEL  3u
+// MODE of the sweeps and the traceback (= option "align_mode")
+#define AFF_LOCAL  0
+#define AFF_FIT    1
+#define AFF_GLOBAL 2
 
 namespace {
 
@@ -79,7 +94,8 @@ struct AffState {
 
 // 8 anti-diagonal steps t0 .. t0+7 (a lane outside its column range keeps its state).  The steps are a loop, not unrolled:
 // eight copies of R cells let the scheduler hoist the compares of many cells at once, and their masks spilled the SGPRs.
-template <int R, bool STRICT, bool MATRIX>
+// MODE != AFF_LOCAL: vrows is the row slot of read row m in the lane that owns it, 0xFFFFFFFF in every other lane
+template <int R, bool STRICT, bool MATRIX, int MODE>
 __device__ __forceinline__ void aff_block8(AffState<R> &S, const uint2 rw, const uint32_t t0, const uint32_t lane,
                                            const uint32_t n, const uint32_t row0, const uint32_t vrows,
                                            const int o, const int e, const int vmat, const int vmis,
@@ -91,11 +107,21 @@ __device__ __forceinline__ void aff_block8(AffState<R> &S, const uint2 rw, const
         const uint32_t fb = (wsel >> (8u * (s & 3u))) & 0xFFu;
         const int feed = MATRIX ? (int)aff_mkey[fb] : (int)fb;  // (wave-uniform: lane 0's column)
         S.rb = aff_shr1(feed, S.rb);
-        const int nh = aff_shr1_zero(S.h[R - 1]);
-        const int nf = aff_shr1_zero(S.f_last);
+        int nh, nf;
+        if constexpr (MODE == AFF_LOCAL) {
+            nh = aff_shr1_zero(S.h[R - 1]);
+            nf = aff_shr1_zero(S.f_last);
+        }
         const uint32_t c0 = t0 + s - lane;                       // column index j - 1 of this lane
+        if constexpr (MODE != AFF_LOCAL) {
+            // lane 0 reads row 0 of the mode: H(0,j) = 0 (fit) or o + j*e (global), F(0,j) := H(0,j) + o
+            // (unsigned arithmetic: lane 0 runs up to 70 columns past n, where the value is not used)
+            const int h0 = MODE == AFF_GLOBAL ? (int)((uint32_t)o + (c0 + 1u) * (uint32_t)e) : 0;
+            nh = aff_shr1(h0, S.h[R - 1]);
+            nf = aff_shr1((int)((uint32_t)h0 + (uint32_t)o), S.f_last);
+        }
         const bool inr = c0 < n;
-        int mrow = -1;
+        int mrow = MODE == AFF_LOCAL ? -1 : 0;
         if (inr) {
             int diag = S.nh_prev, up = nh, fup = nf;
             uint32_t sh = 4u * s;
@@ -113,26 +139,52 @@ __device__ __forceinline__ void aff_block8(AffState<R> &S, const uint2 rw, const
                 }
                 const int dg = diag + sv;
                 const int t1 = left + oe, t2 = S.e[k] + e;
-                const int en = max(max(t1, t2), 0);
                 const int u1 = up + oe, u2 = fup + e;
-                const int fn = max(max(u1, u2), 0);
-                const int hv = max(max(en, fn), dg);             // en, fn >= 0: hv >= 0
-                uint32_t d;
-                if (STRICT) d = hv == 0 ? AFF_STOP : (en == hv ? AFF_DEL : (fn == hv ? AFF_INS : AFF_DIAG));
-                else        d = hv == 0 ? AFF_STOP : (dg == hv ? AFF_DIAG : (fn == hv ? AFF_INS : AFF_DEL));
-                // x bits from the sign of the difference (no compare mask): |values| < 2^30 + 2^21, the difference fits
-                const uint32_t code = d | (((uint32_t)(t1 - t2) >> 31) << 2) | (((uint32_t)(u1 - u2) >> 31) << 3);
+                int en, fn, hv;
+                uint32_t code;
+                if constexpr (MODE == AFF_LOCAL) {
+                    en = max(max(t1, t2), 0);
+                    fn = max(max(u1, u2), 0);
+                    hv = max(max(en, fn), dg);                   // en, fn >= 0: hv >= 0
+                    uint32_t d;
+                    if (STRICT) d = hv == 0 ? AFF_STOP : (en == hv ? AFF_DEL : (fn == hv ? AFF_INS : AFF_DIAG));
+                    else        d = hv == 0 ? AFF_STOP : (dg == hv ? AFF_DIAG : (fn == hv ? AFF_INS : AFF_DEL));
+                    // x bits from the sign of the difference (no compare mask): |values| < 2^30 + 2^21, the difference fits
+                    code = d | (((uint32_t)(t1 - t2) >> 31) << 2) | (((uint32_t)(u1 - u2) >> 31) << 3);
+                } else {
+                    en = max(t1, t2);
+                    fn = max(u1, u2);
+                    hv = max(max(en, fn), dg);
+                    uint32_t d;
+                    if (STRICT) d = en == hv ? AFF_DEL : (fn == hv ? AFF_INS : AFF_DIAG);
+                    else        d = dg == hv ? AFF_DIAG : (fn == hv ? AFF_INS : AFF_DEL);
+                    // x bits from compares: the operands are of either sign here and their difference need not fit int32
+                    code = d | (t2 > t1 ? 4u : 0u) | (u2 > u1 ? 8u : 0u);
+                }
                 S.acc[k] |= code << sh;
                 diag = left;
                 up = hv;
                 fup = fn;
                 S.h[k] = hv;
                 S.e[k] = en;
-                if ((uint32_t)k < vrows) mrow = max(mrow, hv);
+                if constexpr (MODE == AFF_LOCAL) { if ((uint32_t)k < vrows) mrow = max(mrow, hv); }
+                else                             { if ((uint32_t)k == vrows) mrow = hv; }
             }
             S.f_last = fup;
         }
         S.nh_prev = nh;
+        if constexpr (MODE != AFF_LOCAL) {
+            // row m only: the one lane that owns it, at every column (fit) or at column n (global)
+            const bool cand = inr && vrows != 0xFFFFFFFFu && (MODE == AFF_FIT || c0 + 1u == n);
+            const uint64_t cm = BALLOT(cand && mrow >= S.thr);
+            if (cm != 0ull) {
+                const int v = __builtin_amdgcn_readlane(mrow, (int)__builtin_ctzll(cm));
+                if (v > S.thr) { S.thr = v; S.cnt = 0u; }
+                if (cand && S.cnt < ccap) cells[S.cnt] = make_uint2(row0 + vrows + 1u, c0 + 1u);
+                S.cnt += 1u;
+            }
+            continue;
+        }
         // tied maxima (SmithWaterman.java:176-185): the wave leaves the step only when some lane reached the threshold
         if (BALLOT(mrow >= S.thr) != 0ull) {
             uint64_t gt = BALLOT(mrow > S.thr);
@@ -157,7 +209,7 @@ __device__ __forceinline__ void aff_block8(AffState<R> &S, const uint2 rw, const
     }
 }
 
-template <int R, bool STRICT, bool MATRIX>
+template <int R, bool STRICT, bool MATRIX, int MODE>
 __device__ __forceinline__ void aff_sweep_pair(const FillArgs &A, const int o, const PairDesc pd, const uint32_t lane, const uint32_t nn) {
     const SeqDesc rd = A.refs[pd.ref_id];
     const SeqDesc qd = A.reads[pd.read_id];
@@ -167,7 +219,9 @@ __device__ __forceinline__ void aff_sweep_pair(const FillArgs &A, const int o, c
     uint32_t *__restrict__ dir = A.dir + pd.dir_off;
     const uint32_t W = swmi_aff_blocks(m, n);
     const uint32_t row0 = lane * R;
-    const uint32_t vrows = row0 >= m ? 0u : (m - row0 < (uint32_t)R ? m - row0 : (uint32_t)R);
+    // (the end-to-end modes track row m alone: its row slot in the lane that owns it, no slot elsewhere)
+    const uint32_t vrows = MODE != AFF_LOCAL ? (m - 1u - row0 < (uint32_t)R ? m - 1u - row0 : 0xFFFFFFFFu)
+                         : row0 >= m ? 0u : (m - row0 < (uint32_t)R ? m - row0 : (uint32_t)R);
     const uint64_t cbase = A.cells_off ? A.cells_off[pd.out_id] : (uint64_t)pd.out_id * A.cell_cap;
     const uint32_t ccap = A.cells_cap ? A.cells_cap[pd.out_id] : A.cell_cap;
     uint2 *__restrict__ cells = A.cells + cbase;
@@ -183,25 +237,30 @@ __device__ __forceinline__ void aff_sweep_pair(const FillArgs &A, const int o, c
             const uint32_t hi = (key >> 16) == 0x1FFu ? 0x3FFu : key >> 16;
             S.q[k] = (int)(((key & 0xFFFFu) * nn) | (hi << 16));
         }
-        S.h[k] = 0;
-        S.e[k] = 0;
+        if constexpr (MODE == AFF_LOCAL) {
+            S.h[k] = 0;
+            S.e[k] = 0;
+        } else {                                                 // column 0: H(i,0) = o + i*e, E(i,0) := H(i,0) + o
+            S.h[k] = o + (int)(row + 1u) * A.gap;
+            S.e[k] = S.h[k] + o;
+        }
     }
-    S.rb = 0; S.nh_prev = 0; S.f_last = 0;
-    S.thr = 1; S.cnt = 0;
+    S.rb = 0; S.nh_prev = 0; S.f_last = 0;                       // (nh_prev of lane 0: H(0,0) = 0 in every mode)
+    S.thr = MODE == AFF_LOCAL ? 1 : INT32_MIN; S.cnt = 0;
     for (uint32_t w = 0; w < W; ++w) {
         const uint32_t t0 = 8u * w;
         // lane 0's 8 reference bases (images are padded: the last block may read past the end)
         const uint2 rw = *reinterpret_cast<const uint2 *>(refw + (t0 >> 2));
 #pragma unroll
         for (int k = 0; k < R; ++k) S.acc[k] = 0u;
-        aff_block8<R, STRICT, MATRIX>(S, rw, t0, lane, n, row0, vrows, o, A.gap, A.match, A.mismatch, cells, ccap);
+        aff_block8<R, STRICT, MATRIX, MODE>(S, rw, t0, lane, n, row0, vrows, o, A.gap, A.match, A.mismatch, cells, ccap);
         uint32_t *__restrict__ dst = dir + (uint64_t)w * R * WAVE + lane;
 #pragma unroll
         for (int k = 0; k < R; ++k) dst[k * WAVE] = S.acc[k];
     }
     if (lane == 0) {
         PairOut po;
-        if (S.cnt == 0u) {                                       // maximum 0: every one of the m*n cells ties (SmithWaterman.java:154)
+        if (MODE == AFF_LOCAL && S.cnt == 0u) {                                       // maximum 0: every one of the m*n cells ties (SmithWaterman.java:154)
             po.score = 0;
             po.flags = SWMI_F_DEGENERATE;
             po.n_cells = (uint64_t)m * n;
@@ -215,17 +274,17 @@ __device__ __forceinline__ void aff_sweep_pair(const FillArgs &A, const int o, c
 }
 
 // RLO..RHI: the rows per lane this instantiation of the kernel takes (the others' registers would cap its occupancy)
-template <int RLO, int RHI, bool STRICT, bool MATRIX>
+template <int RLO, int RHI, bool STRICT, bool MATRIX, int MODE>
 __device__ __forceinline__ void aff_sweep_dispatch(const FillArgs &A, const int o, const PairDesc pd, const uint32_t R, const uint32_t lane,
                                                    const uint32_t nn) {
     if constexpr (RLO <= RHI) {
-        if (R == (uint32_t)RLO) aff_sweep_pair<RLO, STRICT, MATRIX>(A, o, pd, lane, nn);
-        else aff_sweep_dispatch<RLO + 1, RHI, STRICT, MATRIX>(A, o, pd, R, lane, nn);
+        if (R == (uint32_t)RLO) aff_sweep_pair<RLO, STRICT, MATRIX, MODE>(A, o, pd, lane, nn);
+        else aff_sweep_dispatch<RLO + 1, RHI, STRICT, MATRIX, MODE>(A, o, pd, R, lane, nn);
     }
 }
 
 // mat / nn (MATRIX only): the score matrix image (swmi_aff_mat_words) and its side n + 1
-template <int RLO, int RHI, bool MATRIX>
+template <int RLO, int RHI, bool MATRIX, int MODE = AFF_LOCAL>
 __device__ __forceinline__ void aff_sweep_entry(const FillArgs &A, const int o, const uint32_t *__restrict__ mat, const uint32_t nn) {
     if (blockIdx.x == 0 && threadIdx.x == 0) A.hdr->reserved = 0ull;      // the traceback's bump allocator
     if (MATRIX) {                                                          // (before any wavefront leaves)
@@ -243,8 +302,8 @@ __device__ __forceinline__ void aff_sweep_entry(const FillArgs &A, const int o, 
     const PairDesc pd = A.pairs[pair];
     const uint32_t R = uni(swmi_aff_rows_per_lane(A.reads[pd.read_id].len));
     if (R < (uint32_t)RLO || R > (uint32_t)RHI) return;
-    if (A.strict) aff_sweep_dispatch<RLO, RHI, true, MATRIX>(A, o, pd, R, lane, nn);
-    else          aff_sweep_dispatch<RLO, RHI, false, MATRIX>(A, o, pd, R, lane, nn);
+    if (A.strict) aff_sweep_dispatch<RLO, RHI, true, MATRIX, MODE>(A, o, pd, R, lane, nn);
+    else          aff_sweep_dispatch<RLO, RHI, false, MATRIX, MODE>(A, o, pd, R, lane, nn);
 }
 
 }  // namespace
@@ -263,13 +322,33 @@ extern "C" __global__ void __launch_bounds__(WAVE * AFF_WAVES) sw_affine_sweep_m
                                                                                                  const uint32_t *mat, const uint32_t nn) {
     aff_sweep_entry<5, SWMI_AFF_RMAX, true>(A, gap_open, mat, nn);
 }
+// the end-to-end modes (option "align_mode"): fit and global, plain and matrix, narrow and wide
+#define AFF_ENDS_KERNELS(name, MODE)                                                                                                  \
+    extern "C" __global__ void __launch_bounds__(WAVE * AFF_WAVES) sw_affine_sweep_##name##_kernel(const FillArgs A, const int gap_open) { \
+        aff_sweep_entry<1, 4, false, MODE>(A, gap_open, nullptr, 0u);                                                                \
+    }                                                                                                                                 \
+    extern "C" __global__ void __launch_bounds__(WAVE * AFF_WAVES) sw_affine_sweep_##name##_wide_kernel(const FillArgs A, const int gap_open) { \
+        aff_sweep_entry<5, SWMI_AFF_RMAX, false, MODE>(A, gap_open, nullptr, 0u);                                                    \
+    }                                                                                                                                 \
+    extern "C" __global__ void __launch_bounds__(WAVE * AFF_WAVES) sw_affine_sweep_##name##_matrix_kernel(                            \
+        const FillArgs A, const int gap_open, const uint32_t *mat, const uint32_t nn) {                                               \
+        aff_sweep_entry<1, 4, true, MODE>(A, gap_open, mat, nn);                                                                      \
+    }                                                                                                                                 \
+    extern "C" __global__ void __launch_bounds__(WAVE * AFF_WAVES) sw_affine_sweep_##name##_matrix_wide_kernel(                       \
+        const FillArgs A, const int gap_open, const uint32_t *mat, const uint32_t nn) {                                               \
+        aff_sweep_entry<5, SWMI_AFF_RMAX, true, MODE>(A, gap_open, mat, nn);                                                          \
+    }
+AFF_ENDS_KERNELS(fit, AFF_FIT)
+AFF_ENDS_KERNELS(global, AFF_GLOBAL)
+#undef AFF_ENDS_KERNELS
 
 // ------------------------------------------------------------------------------------------------
 // traceback
 // ------------------------------------------------------------------------------------------------
 // LDS of one wavefront: [tile_words] direction tile | [ops_words] ops, 16 per dword | [SWMI_EMIT_SCRATCH_WORDS] string scratch
-extern "C" __global__ void __launch_bounds__(WAVE) sw_affine_traceback_kernel(const TraceArgs A, const uint32_t tile_words,
-                                                                               const uint32_t ops_words) {
+namespace {
+template <int MODE>
+__device__ __forceinline__ void aff_traceback(const TraceArgs A, const uint32_t tile_words, const uint32_t ops_words) {
     extern __shared__ uint32_t lds[];
     const uint32_t lane = threadIdx.x;
     const uint32_t slot = blockIdx.y, nslots = gridDim.y;
@@ -303,9 +382,17 @@ extern "C" __global__ void __launch_bounds__(WAVE) sw_affine_traceback_kernel(co
         uint32_t l = (i - 1u) / R, k = (i - 1u) - l * R;          // lane and row slot of row i
         uint32_t st = 0u;                                         // 0: H, else the state entered (AFF_DIAG / AFF_INS / AFF_DEL)
         uint32_t n_ops = 0, cur = 0;
-        int begin = 0;
+        int begin = MODE == AFF_LOCAL ? 0 : (int)cj;
         bool ok = true;
-        while (i != 0u && j != 0u) {
+        while (MODE == AFF_LOCAL ? (i != 0u && j != 0u) : (i != 0u)) {
+            if (MODE != AFF_LOCAL && j == 0u) {                   // the read's head hangs over the reference start: inserted,
+                if (n_ops >= max_ops) { ok = false; break; }      // and the field is not touched
+                --i;
+                cur |= SWMI_DIR_I << (2u * (n_ops & 15u));
+                ++n_ops;
+                if ((n_ops & 15u) == 0u) { if (lane == 0) ops[(n_ops >> 4) - 1u] = cur; cur = 0u; }
+                continue;
+            }
             const uint32_t t = j - 1u + l, w = t >> 3;
             if (w < wlo || w >= whi) {                            // stage the tile that ends at this block
                 if (w >= W) { ok = false; break; }                // (a corrupted list: never walks off the field)
@@ -320,10 +407,11 @@ extern "C" __global__ void __launch_bounds__(WAVE) sw_affine_traceback_kernel(co
             const uint32_t code = uni((tile[((w - wlo) * R + k) * WAVE + l] >> (4u * (t & 7u))) & 15u);
             if (st == 0u) {
                 st = code & 3u;
-                if (st == AFF_STOP) break;                        // H(i, j) == 0: `while (score > 0)` (SmithWaterman.java:380)
+                if (MODE == AFF_LOCAL) { if (st == AFF_STOP) break; }   // H(i, j) == 0: `while (score > 0)` (SmithWaterman.java:380)
+                else if (st == AFF_STOP) { ok = false; break; }         // (these sweeps write no code 0: a corrupted field)
             }
             if (n_ops >= max_ops) { ok = false; break; }
-            begin = (int)j;
+            if (MODE == AFF_LOCAL || st != AFF_INS) begin = (int)j;     // (end-to-end: the moves that consume a reference base)
             uint32_t op;
             if (st == AFF_DIAG) {
                 op = SWMI_DIR_A;
@@ -343,6 +431,16 @@ extern "C" __global__ void __launch_bounds__(WAVE) sw_affine_traceback_kernel(co
             ++n_ops;
             if ((n_ops & 15u) == 0u) { if (lane == 0) ops[(n_ops >> 4) - 1u] = cur; cur = 0u; }
         }
+        if (MODE == AFF_GLOBAL) {                                 // row 0: the rest of the reference is deleted
+            while (ok && j != 0u) {
+                if (n_ops >= max_ops) { ok = false; break; }
+                begin = (int)j;
+                --j;
+                cur |= SWMI_DIR_D << (2u * (n_ops & 15u));
+                ++n_ops;
+                if ((n_ops & 15u) == 0u) { if (lane == 0) ops[(n_ops >> 4) - 1u] = cur; cur = 0u; }
+            }
+        }
         if ((n_ops & 15u) != 0u && lane == 0) ops[n_ops >> 4] = cur;
         WAVE_SYNC();
         const bool strings = A.raw != nullptr;
@@ -361,39 +459,67 @@ extern "C" __global__ void __launch_bounds__(WAVE) sw_affine_traceback_kernel(co
         WAVE_SYNC();
     }
 }
+}  // namespace
+
+extern "C" __global__ void __launch_bounds__(WAVE) sw_affine_traceback_kernel(const TraceArgs A, const uint32_t tile_words,
+                                                                               const uint32_t ops_words) {
+    aff_traceback<AFF_LOCAL>(A, tile_words, ops_words);
+}
+extern "C" __global__ void __launch_bounds__(WAVE) sw_affine_traceback_fit_kernel(const TraceArgs A, const uint32_t tile_words,
+                                                                                   const uint32_t ops_words) {
+    aff_traceback<AFF_FIT>(A, tile_words, ops_words);
+}
+extern "C" __global__ void __launch_bounds__(WAVE) sw_affine_traceback_global_kernel(const TraceArgs A, const uint32_t tile_words,
+                                                                                      const uint32_t ops_words) {
+    aff_traceback<AFF_GLOBAL>(A, tile_words, ops_words);
+}
 
 // ------------------------------------------------------------------------------------------------
 // host-callable launchers
 // ------------------------------------------------------------------------------------------------
 // r_min / r_max: the rows per lane of the launch's shortest and longest read (only the kernels that have pairs are launched)
-extern "C" hipError_t swmi_launch_affine_sweep(const FillArgs *a, int32_t gap_open, uint32_t r_min, uint32_t r_max, hipStream_t st) {
+// align_mode: 0 local, 1 fit, 2 global (option "align_mode")
+extern "C" hipError_t swmi_launch_affine_sweep(const FillArgs *a, int32_t gap_open, uint32_t align_mode, uint32_t r_min, uint32_t r_max,
+                                               hipStream_t st) {
     if (a->n_pairs == 0) return hipSuccess;
+    if (align_mode > 2u) return hipErrorInvalidValue;
     const dim3 grid((a->n_pairs + AFF_WAVES - 1) / AFF_WAVES), block(WAVE * AFF_WAVES);
-    if (r_min <= 4u) hipLaunchKernelGGL(sw_affine_sweep_kernel, grid, block, 0, st, *a, (int)gap_open);
-    if (r_max >= 5u) hipLaunchKernelGGL(sw_affine_sweep_wide_kernel, grid, block, 0, st, *a, (int)gap_open);
+    auto *const narrow = align_mode == 0u ? sw_affine_sweep_kernel : align_mode == 1u ? sw_affine_sweep_fit_kernel : sw_affine_sweep_global_kernel;
+    auto *const wide = align_mode == 0u ? sw_affine_sweep_wide_kernel
+                                        : align_mode == 1u ? sw_affine_sweep_fit_wide_kernel : sw_affine_sweep_global_wide_kernel;
+    if (r_min <= 4u) hipLaunchKernelGGL(narrow, grid, block, 0, st, *a, (int)gap_open);
+    if (r_max >= 5u) hipLaunchKernelGGL(wide, grid, block, 0, st, *a, (int)gap_open);
     return hipGetLastError();
 }
 
 // the matrix sweeps: mat = the device image of the score matrix (swmi_aff_mat_words dwords), nn = its side n + 1 (2 .. 65)
-extern "C" hipError_t swmi_launch_affine_sweep_matrix(const FillArgs *a, int32_t gap_open, const uint32_t *mat, uint32_t nn, uint32_t r_min,
-                                                      uint32_t r_max, hipStream_t st) {
+extern "C" hipError_t swmi_launch_affine_sweep_matrix(const FillArgs *a, int32_t gap_open, uint32_t align_mode, const uint32_t *mat, uint32_t nn,
+                                                      uint32_t r_min, uint32_t r_max, hipStream_t st) {
     if (a->n_pairs == 0) return hipSuccess;
-    if (nn < 2u || nn > SWMI_MAT_NN_MAX) return hipErrorInvalidValue;
+    if (nn < 2u || nn > SWMI_MAT_NN_MAX || align_mode > 2u) return hipErrorInvalidValue;
     const dim3 grid((a->n_pairs + AFF_WAVES - 1) / AFF_WAVES), block(WAVE * AFF_WAVES);
-    if (r_min <= 4u) hipLaunchKernelGGL(sw_affine_sweep_matrix_kernel, grid, block, 0, st, *a, (int)gap_open, mat, nn);
-    if (r_max >= 5u) hipLaunchKernelGGL(sw_affine_sweep_matrix_wide_kernel, grid, block, 0, st, *a, (int)gap_open, mat, nn);
+    auto *const narrow = align_mode == 0u ? sw_affine_sweep_matrix_kernel
+                                          : align_mode == 1u ? sw_affine_sweep_fit_matrix_kernel : sw_affine_sweep_global_matrix_kernel;
+    auto *const wide = align_mode == 0u ? sw_affine_sweep_matrix_wide_kernel
+                                        : align_mode == 1u ? sw_affine_sweep_fit_matrix_wide_kernel : sw_affine_sweep_global_matrix_wide_kernel;
+    if (r_min <= 4u) hipLaunchKernelGGL(narrow, grid, block, 0, st, *a, (int)gap_open, mat, nn);
+    if (r_max >= 5u) hipLaunchKernelGGL(wide, grid, block, 0, st, *a, (int)gap_open, mat, nn);
     return hipGetLastError();
 }
 
-extern "C" hipError_t swmi_launch_affine_traceback(const TraceArgs *a, uint32_t tile_words, uint32_t ops_words, hipStream_t st) {
+extern "C" hipError_t swmi_launch_affine_traceback(const TraceArgs *a, uint32_t align_mode, uint32_t tile_words, uint32_t ops_words,
+                                                   hipStream_t st) {
     if (a->n_pairs == 0) return hipSuccess;
+    if (align_mode > 2u) return hipErrorInvalidValue;
     static const bool attrs = [] {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(sw_affine_traceback_kernel),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        for (auto *k : {sw_affine_traceback_kernel, sw_affine_traceback_fit_kernel, sw_affine_traceback_global_kernel})
+            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         return true;
     }();
     (void)attrs;
     const size_t lds = ((size_t)tile_words + ops_words + SWMI_EMIT_SCRATCH_WORDS) * sizeof(uint32_t);
-    hipLaunchKernelGGL(sw_affine_traceback_kernel, dim3(a->n_pairs, SWMI_AFF_TB_SLOTS), dim3(WAVE), lds, st, *a, tile_words, ops_words);
+    auto *const kern = align_mode == 0u ? sw_affine_traceback_kernel
+                                        : align_mode == 1u ? sw_affine_traceback_fit_kernel : sw_affine_traceback_global_kernel;
+    hipLaunchKernelGGL(kern, dim3(a->n_pairs, SWMI_AFF_TB_SLOTS), dim3(WAVE), lds, st, *a, tile_words, ops_words);
     return hipGetLastError();
 }

@@ -35,10 +35,12 @@ extern "C" hipError_t swmi_launch_traceback(const TraceArgs *a, hipStream_t st, 
 extern "C" hipError_t swmi_launch_traceback_split(const TraceArgs *a, uint32_t n_windows, hipStream_t st);
 extern "C" hipError_t swmi_launch_resident(const TraceArgs *a, const ResidentArgs *x, hipStream_t st);
 extern "C" hipError_t swmi_launch_tfused(const TraceArgs *a, const TFusedArgs *x, hipStream_t st);
-extern "C" hipError_t swmi_launch_affine_sweep(const FillArgs *a, int32_t gap_open, uint32_t r_min, uint32_t r_max, hipStream_t st);
-extern "C" hipError_t swmi_launch_affine_sweep_matrix(const FillArgs *a, int32_t gap_open, const uint32_t *mat, uint32_t nn, uint32_t r_min,
+extern "C" hipError_t swmi_launch_affine_sweep(const FillArgs *a, int32_t gap_open, uint32_t align_mode, uint32_t r_min, uint32_t r_max,
+                                               hipStream_t st);
+extern "C" hipError_t swmi_launch_affine_sweep_matrix(const FillArgs *a, int32_t gap_open, uint32_t align_mode, const uint32_t *mat, uint32_t nn, uint32_t r_min,
                                                       uint32_t r_max, hipStream_t st);
-extern "C" hipError_t swmi_launch_affine_traceback(const TraceArgs *a, uint32_t tile_words, uint32_t ops_words, hipStream_t st);
+extern "C" hipError_t swmi_launch_affine_traceback(const TraceArgs *a, uint32_t align_mode, uint32_t tile_words, uint32_t ops_words,
+                                                   hipStream_t st);
 extern "C" hipError_t swmi_launch_encode(const uint8_t *raw, const uint64_t *raw_off, SeqDesc *desc, uint32_t *seqw,
                                          const uint8_t *lut, uint32_t n_seq, hipStream_t st);
 
@@ -163,6 +165,7 @@ struct swmi_ctx {
     bool cell_cap_set = false;              // cell_cap given by the caller (otherwise small launches get longer lists)
     int32_t gap_open = 0;                   // affine gaps: a gap of length k costs gap_open + k * gap (0: linear)
     int affine = -1;                        // -1: the affine kernels (mode 3) when gap_open != 0; 1: always
+    int align_mode = SWMI_ALIGN_LOCAL;      // SWMI_ALIGN_FIT / _GLOBAL: end-to-end alignment, on the affine kernels
     std::mutex mat_mu;                      // guards `matrix` (not ctx->mu: setting a matrix does not wait for a run)
     std::shared_ptr<const ScoreMatrix> matrix;   // swmi_set_score_matrix; a run with one takes the affine kernels
     // swmi_batch_run_async: one run in flight on the context's own host thread
@@ -173,6 +176,7 @@ struct swmi_ctx {
     swmi_batch *job_batch = nullptr;
     swmi_params job_params{};
     std::shared_ptr<const ScoreMatrix> job_matrix;   // the matrix when swmi_batch_run_async was called
+    int job_align_mode = 0;                          // align_mode when swmi_batch_run_async was called
     uint32_t job_delay_us = 0;                       // debug_async_delay_us when swmi_batch_run_async was called
     int job_rc = 0;
     std::string job_err;
@@ -237,6 +241,7 @@ struct swmi_batch {
     bool work_tfused = false;               // the schedule's workspace sizes leave room for sw_tfused_kernel's column checkpoints
     uint32_t eff_mode = 1;                  // pipeline of the current run (3: the affine kernels, swmi_affine.hip)
     int32_t gap_open = 0;                   // the context's gap_open when the run started (mode 3)
+    int align_mode = 0;                     // the context's align_mode when the run was asked for (mode 3)
     std::shared_ptr<const ScoreMatrix> mat; // the score matrix of the current run (null: none); keeps its host image alive
     DevBuf d_mat;                           // ... its device image, copied on the run's stream
     uint64_t d_mat_gen = 0;                 // generation of the matrix in d_mat (0: none)
@@ -261,6 +266,7 @@ struct swmi_batch {
         int tfused_opt = -1;
         uint32_t aff_r_min = 0, aff_r_max = 0;      // mode 3: rows per lane of the chunk's shortest and longest read
         uint64_t mat_gen = 0;                       // the score matrix's generation (0: none): it bounds the paths
+        int align_mode = 0;                         // ... as does the alignment mode
         size_t n_tf = 0;
         uint32_t tf_max_m = 0, tf_max_n = 0, tf_max_path = 0;
         bool exact = false, scores_only = false;
@@ -435,6 +441,10 @@ extern "C" int swmi_set_option(swmi_ctx *ctx, const char *name, int64_t value) {
     } else if (!strcmp(name, "affine")) {
         if (value != -1 && value != 1) return fail(SWMI_ERR_INVALID, "affine must be -1 (when gap_open != 0) or 1 (always)");
         ctx->affine = (int)value;
+    } else if (!strcmp(name, "align_mode")) {
+        if (value != SWMI_ALIGN_LOCAL && value != SWMI_ALIGN_FIT && value != SWMI_ALIGN_GLOBAL)
+            return fail(SWMI_ERR_INVALID, "align_mode must be 0 (local), 1 (fit) or 2 (global), got %lld", (long long)value);
+        ctx->align_mode = (int)value;
     } else if (!strcmp(name, "arena_words_per_pair")) {
         if (value < 1) return fail(SWMI_ERR_INVALID, "arena_words_per_pair out of range");
         ctx->arena_words_per_pair = (uint64_t)value;
@@ -658,8 +668,10 @@ inline uint64_t rec_words(uint32_t n_ops, bool strings) {
 // longest possible traceback of an n x m pair: A + I <= m rows, A + D <= n columns, and -- with match > 0 > gap -- the
 // score match*A + gap*(I + D) must stay positive (`while (score > 0)`), which caps the gap moves.  smax: the largest score of
 // one alignment move (match; with a score matrix the larger of match and its largest entry)
-static uint64_t path_bound(uint64_t n_, uint64_t m_, const swmi_params &p, int32_t smax) {
+// align_mode != 0: the score may be anything, so only A + I <= m and A + D <= n hold: m + n moves
+static uint64_t path_bound(uint64_t n_, uint64_t m_, const swmi_params &p, int32_t smax, int align_mode = 0) {
     uint64_t path = n_ + m_;
+    if (align_mode != 0) return path;
     if (smax > 0 && p.gap < 0 && p.mismatch <= smax) {
         const uint64_t g = (uint64_t)(-(int64_t)p.gap), mt = (uint64_t)smax;
         path = std::min(path, std::min(m_ + std::min(n_, mt * m_ / g), n_ + std::min(m_, mt * n_ / g)));
@@ -714,7 +726,7 @@ static int prepare_chunk(RunState &rs, const std::vector<Work> &work, size_t lo,
                           b->pairs_on_device.size() == np * sizeof(PairDesc) && pr.col_chunks_opt == ctx->col_chunks &&
                           pr.reverse_strips == (ctx->dbg_reverse_strips != 0) && pr.resident_opt == ctx->resident &&
                           pr.tfused_opt == ctx->tfused && pr.exact == (cells_exact != nullptr) && pr.scores_only == (ctx->scores_only != 0) &&
-                          pr.mat_gen == (b->mat ? b->mat->gen : 0u);
+                          pr.mat_gen == (b->mat ? b->mat->gen : 0u) && pr.align_mode == b->align_mode;
     if (prepared) {
         dir_words = pr.dir_words; seam_words = pr.seam_words; max_path = pr.max_path; max_read = pr.max_read;
         n_strip_items = pr.n_strip_items; n_col_items = pr.n_col_items; n_windows = pr.n_windows;
@@ -880,7 +892,7 @@ static int prepare_chunk(RunState &rs, const std::vector<Work> &work, size_t lo,
             }
         }
         pd[k] = d;
-        if (m_ != pb_m || n_ != pb_n) { pb_m = m_; pb_n = n_; pb_val = (uint32_t)path_bound(n_, m_, b->params, smax); }   // (runs of equal lengths)
+        if (m_ != pb_m || n_ != pb_n) { pb_m = m_; pb_n = n_; pb_val = (uint32_t)path_bound(n_, m_, b->params, smax, b->align_mode); }   // (runs of equal lengths)
         max_path = std::max<uint32_t>(max_path, pb_val);
         max_read = std::max(max_read, m_);
         aff_r_min = std::min(aff_r_min, swmi_aff_rows_per_lane(m_));
@@ -969,6 +981,7 @@ static int prepare_chunk(RunState &rs, const std::vector<Work> &work, size_t lo,
         pr.scores_only = ctx->scores_only != 0;
         pr.aff_r_min = aff_r_min; pr.aff_r_max = aff_r_max;
         pr.mat_gen = b->mat ? b->mat->gen : 0u;
+        pr.align_mode = b->align_mode;
     }
     rs.prep_us += std::chrono::duration<double, std::micro>(p1 - p0).count();
     rs.prep_upload_us += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - p1).count();
@@ -1295,9 +1308,10 @@ static int run_chunk(RunState &rs, const std::vector<Work> &work, size_t lo, siz
         if (attempt == 0 && !whole_only) {       // the workspace survives an arena-overflow retry
             if (fa.n_strip_items) HIP_TRY(hipMemsetAsync(fa.progress, 0, (size_t)fa.n_strip_items * sizeof(uint32_t), ctx->stream));
             if (b->eff_mode == 3 && b->mat)
-                HIP_TRY(swmi_launch_affine_sweep_matrix(&fa, b->gap_open, b->d_mat.as<uint32_t>(), b->mat->n + 1u, pr.aff_r_min, pr.aff_r_max,
-                                                        ctx->stream));
-            else if (b->eff_mode == 3) HIP_TRY(swmi_launch_affine_sweep(&fa, b->gap_open, pr.aff_r_min, pr.aff_r_max, ctx->stream));
+                HIP_TRY(swmi_launch_affine_sweep_matrix(&fa, b->gap_open, (uint32_t)b->align_mode, b->d_mat.as<uint32_t>(), b->mat->n + 1u,
+                                                        pr.aff_r_min, pr.aff_r_max, ctx->stream));
+            else if (b->eff_mode == 3)
+                HIP_TRY(swmi_launch_affine_sweep(&fa, b->gap_open, (uint32_t)b->align_mode, pr.aff_r_min, pr.aff_r_max, ctx->stream));
             else HIP_TRY(swmi_launch_fill(&fa, ctx->stream, ext_timing ? ctx->ev[0] : nullptr, ext_timing ? ctx->ev[1] : nullptr));
             rs.launches++;
         }
@@ -1324,7 +1338,8 @@ static int run_chunk(RunState &rs, const std::vector<Work> &work, size_t lo, siz
             if (attempt > 0 || whole_only) HIP_TRY(hipMemsetAsync(ta.q_count, 0, 4, ctx->stream));      // (no sweep kernel ran to zero it)
             HIP_TRY(swmi_launch_traceback_split(&ta, (uint32_t)n_windows, ctx->stream));
         } else if (b->eff_mode == 3) {
-            HIP_TRY(swmi_launch_affine_traceback(&ta, SWMI_AFF_TILE_WORDS, (uint32_t)(((uint64_t)max_path + 15) / 16 + 1), ctx->stream));
+            HIP_TRY(swmi_launch_affine_traceback(&ta, (uint32_t)b->align_mode, SWMI_AFF_TILE_WORDS, (uint32_t)(((uint64_t)max_path + 15) / 16 + 1),
+                                                 ctx->stream));
         } else if (n_res + n_tf < np) {
             HIP_TRY(swmi_launch_traceback(&ta, ctx->stream, ext_timing ? ctx->ev[2] : nullptr, ext_timing ? ctx->ev[3] : nullptr));
         }
@@ -1400,7 +1415,8 @@ static int run_chunk(RunState &rs, const std::vector<Work> &work, size_t lo, siz
             outs.assign((const PairOut *)(h + result_out_off()), (const PairOut *)(h + result_out_off()) + np);
             for (size_t k = 0; k < np; k++) {
                 PairOut &o = outs[k];
-                if (o.score <= 0 && !(o.flags & SWMI_F_DEGENERATE)) {
+                // (the end-to-end modes have no degenerate case: a score of 0 or below is an ordinary score)
+                if (o.score <= 0 && !(o.flags & SWMI_F_DEGENERATE) && b->align_mode == 0) {
                     const uint32_t pair = work[lo + k].pair;
                     o.score = 0; o.flags = SWMI_F_DEGENERATE;
                     o.n_cells = (uint64_t)b->read_desc[pair % b->n_reads].len * b->ref_desc[pair / b->n_reads].len;
@@ -1589,7 +1605,8 @@ static std::shared_ptr<const ScoreMatrix> ctx_matrix(swmi_ctx *ctx) {
 }
 
 // mat: the score matrix the run uses (the context's when the run was asked for), or null
-static int batch_run(swmi_ctx *ctx, swmi_batch *b, const swmi_params *p, std::shared_ptr<const ScoreMatrix> mat) {
+// align_mode: the context's when the run was asked for
+static int batch_run(swmi_ctx *ctx, swmi_batch *b, const swmi_params *p, std::shared_ptr<const ScoreMatrix> mat, const int align_mode) {
     if (!ctx || !b || !p) return fail(SWMI_ERR_INVALID, "null argument");
     if (p->tie_mode != SWMI_TIE_SERIAL && p->tie_mode != SWMI_TIE_STRICT)
         return fail(SWMI_ERR_INVALID, "unknown tie_mode %d", p->tie_mode);
@@ -1599,7 +1616,8 @@ static int batch_run(swmi_ctx *ctx, swmi_batch *b, const swmi_params *p, std::sh
     if (p->types[0] == p->types[1] || p->types[0] == p->types[2] || p->types[1] == p->types[2])
         return fail(SWMI_ERR_UNSUPPORTED, "alignTypes a/i/d must be pairwise distinct");
     std::lock_guard<std::mutex> g(ctx->mu);
-    const bool affine = ctx->affine == 1 || ctx->gap_open != 0 || mat != nullptr;   // (a score matrix runs on the affine kernels only)
+    // (a score matrix and the end-to-end modes run on the affine kernels only)
+    const bool affine = ctx->affine == 1 || ctx->gap_open != 0 || mat != nullptr || align_mode != SWMI_ALIGN_LOCAL;
     if (affine) {
         // the bounds within which every sum of the affine recurrence fits int32 (DESIGN.md "Affine gaps"); checked before
         // anything is launched
@@ -1612,6 +1630,18 @@ static int batch_run(swmi_ctx *ctx, swmi_batch *b, const swmi_params *p, std::sh
         for (uint32_t q = 0; q < b->n_reads; q++)
             if (b->read_desc[q].len > SWMI_AFF_MAX_READ)
                 return fail(SWMI_ERR_UNSUPPORTED, "affine gaps: read %u has %u bases (at most %u)", q, b->read_desc[q].len, SWMI_AFF_MAX_READ);
+        if (align_mode == SWMI_ALIGN_GLOBAL) {
+            // global mode: the smallest sum a sweep forms is 3 * gap_open + (64 * ceil(m / 64) + n) * gap (swmi.h, DESIGN.md
+            // "End-to-end modes"); it must not leave int32.  Checked per pair in 64-bit arithmetic: it falls with m and n, so
+            // the longest read against the longest reference decides.
+            uint64_t max_m = 0, max_n = 0;
+            for (uint32_t q = 0; q < b->n_reads; q++) max_m = std::max<uint64_t>(max_m, b->read_desc[q].len);
+            for (uint32_t r = 0; r < b->n_refs; r++) max_n = std::max<uint64_t>(max_n, b->ref_desc[r].len);
+            const int64_t low = 3 * (int64_t)ctx->gap_open + (int64_t)(64 * ((max_m + 63) / 64) + max_n) * (int64_t)p->gap;
+            if (max_m && max_n && low < (int64_t)INT32_MIN)
+                return fail(SWMI_ERR_UNSUPPORTED, "align_mode global: 3 * gap_open + (64 * ceil(m / 64) + n) * gap = %lld for the longest read "
+                            "(%llu) and reference (%llu) is below -2^31", (long long)low, (unsigned long long)max_m, (unsigned long long)max_n);
+        }
     }
     static const bool host_dbg = getenv("SWMI_DEBUG_HOST") != nullptr;
     auto now = [] { return std::chrono::steady_clock::now(); };
@@ -1646,6 +1676,7 @@ static int batch_run(swmi_ctx *ctx, swmi_batch *b, const swmi_params *p, std::sh
     // mode 1 needs pad rows that cannot outgrow the real cells they derive from: mismatch <= 0 and gap <= 0
     b->eff_mode = (ctx->mode == 1 && (p->mismatch > 0 || p->gap > 0)) ? 2u : ctx->mode;
     b->gap_open = ctx->gap_open;
+    b->align_mode = align_mode;
     if (affine) b->eff_mode = 3;                         // the affine kernels (swmi_affine.hip): no other pipeline option applies
     b->mat = std::move(mat);
     if (b->mat && b->d_mat_gen != b->mat->gen) {
@@ -1838,7 +1869,7 @@ static int batch_run(swmi_ctx *ctx, swmi_batch *b, const swmi_params *p, std::sh
 
 extern "C" int swmi_batch_run(swmi_ctx *ctx, swmi_batch *b, const swmi_params *p) {
     if (!ctx || !b || !p) return fail(SWMI_ERR_INVALID, "null argument");
-    return batch_run(ctx, b, p, ctx_matrix(ctx));
+    return batch_run(ctx, b, p, ctx_matrix(ctx), ctx->align_mode);
 }
 
 // ---- asynchronous run: the same swmi_batch_run on the context's own host thread -------------------------------
@@ -1857,7 +1888,7 @@ static void swmi_worker_loop(swmi_ctx *ctx) {
         }
         if (st == 3) return;
         if (ctx->job_delay_us) std::this_thread::sleep_for(std::chrono::microseconds(ctx->job_delay_us));
-        const int rc = batch_run(ctx, ctx->job_batch, &ctx->job_params, std::move(ctx->job_matrix));
+        const int rc = batch_run(ctx, ctx->job_batch, &ctx->job_params, std::move(ctx->job_matrix), ctx->job_align_mode);
         ctx->job_rc = rc;
         ctx->job_err = rc ? swmi_last_error() : "";
         { std::lock_guard<std::mutex> lk(ctx->job_mu); ctx->job_state.store(2, std::memory_order_release); }
@@ -1873,6 +1904,7 @@ extern "C" int swmi_batch_run_async(swmi_ctx *ctx, swmi_batch *b, const swmi_par
     ctx->job_batch = b;
     ctx->job_params = *p;
     ctx->job_matrix = ctx_matrix(ctx);                 // (the matrix set now, whatever is set while the run is in flight)
+    ctx->job_align_mode = ctx->align_mode;             // (likewise)
     ctx->job_delay_us = ctx->dbg_async_delay_us;
     { std::lock_guard<std::mutex> lk(ctx->job_mu); ctx->job_state.store(1, std::memory_order_release); }
     ctx->job_cv.notify_all();
@@ -2415,7 +2447,7 @@ extern "C" int swmi_stream_open(swmi_ctx *ctx, const swmi_params *p, const uint8
         sl.ctx->tb_split = ctx->tb_split; sl.ctx->col_chunks = ctx->col_chunks; sl.ctx->resident = ctx->resident; sl.ctx->tfused = ctx->tfused;
         sl.ctx->auto_ties_x100 = ctx->auto_ties_x100; sl.ctx->arena_words_per_pair = ctx->arena_words_per_pair;
         sl.ctx->device_strings = ctx->device_strings; sl.ctx->scores_only = ctx->scores_only;
-        sl.ctx->gap_open = ctx->gap_open; sl.ctx->affine = ctx->affine;
+        sl.ctx->gap_open = ctx->gap_open; sl.ctx->affine = ctx->affine; sl.ctx->align_mode = ctx->align_mode;
         sl.ctx->matrix = ctx_matrix(ctx);
         sl.ctx->spin_us = 50;                    // (a chunk takes milliseconds: the slot threads mostly block)
         sl.shell = new swmi_batch;

@@ -143,6 +143,9 @@ def run_rank(ctx, ref_dir, in_dir, out_dir, rank=0, world=1, delimiter=_io.DELIM
     return st
 
 
+_ALIGN_MODES = {"local": _capi.ALIGN_LOCAL, "fit": _capi.ALIGN_FIT, "global": _capi.ALIGN_GLOBAL}
+
+
 def _rank_main(args):
     """one rank of the CLI (a fresh child of the launcher)"""
     import torch
@@ -167,6 +170,8 @@ def _rank_main(args):
         if len(scores) == 4:                                # match,mismatch,gap,gapOpen: affine gaps on this rank's context
             ctx.set_option("gap_open", scores[3])
             scores = scores[:3]
+        if args.align_mode != "local":                      # end-to-end alignment: the streamed scores-only pass and the
+            ctx.set_option("align_mode", _ALIGN_MODES[args.align_mode])    # realignment of the winners both run on this context
         if args.matrix:                                     # substitution scores on this rank's context (NCBI text format)
             from . import matrix as _matrix
             ctx.set_score_matrix(_matrix.load(args.matrix))
@@ -205,6 +210,11 @@ def main(argv=None):
     ap.add_argument("--matrix", default=None,
                     help="a substitution score matrix file in the NCBI text format (row = read base, column = reference base); "
                          "bases outside its alphabet score match / mismatch from --scores")
+    ap.add_argument("--align-mode", choices=tuple(_ALIGN_MODES), default="local",
+                    help="local: Smith-Waterman; fit: the whole read against any stretch of the reference; global: the whole read "
+                         "against the whole reference.  Totals may then be zero or negative; the reduce keeps the control driver's "
+                         "rule (`int max = 0`, ties kept): a reference whose total is negative never wins, and when no total is "
+                         "positive the references whose total is exactly 0 tie, as they do today")
     ap.add_argument("--tie", choices=("serial", "strict"), default="serial",
                     help="serial: SmithWaterman's aligner (NoDistribution, DistributeReference); strict: DistributedSW's (DistributeAlgorithm)")
     ap.add_argument("--stream-chunk-bytes", type=int, default=512 << 10, help="sequence bytes per streamed chunk")
