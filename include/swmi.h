@@ -60,7 +60,12 @@ typedef enum swmi_status {
                               stable sort of the alignments by beginning (DistributedSW.java:480)              */
 
 /* alignScores {match, mismatch, gap} and alignTypes {a, i, d, none}: the two arrays
- * OptAlignments.call takes (SmithWaterman.java:47-57); defaults Distribution.java:36-37. */
+ * OptAlignments.call takes (SmithWaterman.java:47-57); defaults Distribution.java:36-37.
+ * Every score sum is a Java int (uint32 wrap-around), for any int32 scores, with one documented deviation: a POSITIVE gap under
+ * which some H + gap could pass 2^31 - 1 is SWMI_ERR_UNSUPPORTED before anything is launched.  With s1 the largest and s2 the
+ * next smaller positive value among {match, mismatch, gap}, B = 2^31 - 1 and L = the batch's longest read + longest reference,
+ * a run needs  min(B, min(L, B / s1) * s1 + min(L, B / s2) * s2) + gap <= B  (integer divisions; the s2 term is 0 without an
+ * s2).  gap <= 0 is never refused. */
 typedef struct swmi_params {
     int32_t match;       /* default  5 */
     int32_t mismatch;    /* default -3 */

@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <functional>
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
@@ -1642,6 +1643,26 @@ static int batch_run(swmi_ctx *ctx, swmi_batch *b, const swmi_params *p, std::sh
                 return fail(SWMI_ERR_UNSUPPORTED, "align_mode global: 3 * gap_open + (64 * ceil(m / 64) + n) * gap = %lld for the longest read "
                             "(%llu) and reference (%llu) is below -2^31", (long long)low, (unsigned long long)max_m, (unsigned long long)max_n);
         }
+    }
+    if (!affine && p->gap > 0) {
+        // The cell streams form the gap candidate as max(up, left) + gap where the reference wraps W + gap and N + gap each on
+        // its own (SmithWaterman.java:227,235).  The two agree while no H + gap passes 2^31 - 1, always so for gap <= 0.  An H
+        // is the exact sum of the scores along its path (a wrapped sum is negative and loses to 0), a path of at most m + n
+        // moves: the largest positive score s1 at most (2^31 - 1) / s1 times, every other move at most the next positive
+        // score s2.  A positive gap under which that bound plus gap leaves int32 is refused (swmi.h).
+        uint64_t max_m = 0, max_n = 0;
+        for (uint32_t q = 0; q < b->n_reads; q++) max_m = std::max<uint64_t>(max_m, b->read_desc[q].len);
+        for (uint32_t r = 0; r < b->n_refs; r++) max_n = std::max<uint64_t>(max_n, b->ref_desc[r].len);
+        const uint64_t B = 0x7FFFFFFFull, moves = max_m + max_n;
+        uint64_t pos[3] = {(uint64_t)std::max(p->match, 0), (uint64_t)std::max(p->mismatch, 0), (uint64_t)p->gap};
+        std::sort(pos, pos + 3, std::greater<uint64_t>());
+        const uint64_t s1 = pos[0], s2 = pos[1] != s1 ? pos[1] : (pos[2] != s1 ? pos[2] : 0);
+        uint64_t h_max = std::min(moves, B / s1) * s1 + (s2 ? std::min(moves, B / s2) * s2 : 0);
+        h_max = std::min(h_max, B);
+        if (max_m && max_n && h_max + (uint64_t)p->gap > B)
+            return fail(SWMI_ERR_UNSUPPORTED, "a positive gap score of %d could make H + gap pass 2^31 - 1 on a pair of %llu + %llu bases "
+                        "(H may reach %llu); such sums are not reproduced", p->gap, (unsigned long long)max_m, (unsigned long long)max_n,
+                        (unsigned long long)h_max);
     }
     static const bool host_dbg = getenv("SWMI_DEBUG_HOST") != nullptr;
     auto now = [] { return std::chrono::steady_clock::now(); };

@@ -1254,9 +1254,14 @@ __device__ __forceinline__ void traceback_pair(const TraceArgs &A, const PairDes
     const uint32_t *__restrict__ dirp = A.dir + pd.dir_off;
     const uint32_t umat = (uint32_t)A.match, umis = (uint32_t)A.mismatch, ugap = (uint32_t)A.gap;
     const int dec0 = A.match > A.mismatch ? A.match : A.mismatch;
-    const uint32_t udec = dec0 > 0 ? (uint32_t)dec0 : 0u;    // the most one alignment move can lower the tracked score
-    const uint32_t ugdec = A.gap > 0 ? (uint32_t)A.gap : 0u;  // ... and one gap move
-    (void)udec; (void)ugdec;                                  // (only the SWMI_WALK_DIAGONALS build of the walk uses them)
+    // The walk's shortcuts compare the score with up to 2 gap and 21 alignment moves' worth of these two.  With scores so large
+    // that such a product could pass 2^31 both become 2^32 - 1: k moves' worth is then 2^32 - k (mod 2^32, 1 <= k <= 23), above
+    // every score in the unsigned compares below, so the shortcuts are off and every move is checked
+    // (tests/test_gpu_parity.py::test_scores_that_wrap).
+    const bool dec_fits = dec0 <= 0x7FFFFFFF / 23 && A.gap <= 0x7FFFFFFF / 23;
+    const uint32_t udec = !dec_fits ? 0xFFFFFFFFu : dec0 > 0 ? (uint32_t)dec0 : 0u;    // the most one alignment move can lower the tracked score
+    const uint32_t ugdec = !dec_fits ? 0xFFFFFFFFu : A.gap > 0 ? (uint32_t)A.gap : 0u;  // ... and one gap move
+    (void)udec; (void)ugdec;                                  // (the -DSWMI_WALK_CHASE build of the walk does not use them)
     const bool acgt = rd.acgt && qd.acgt && SWMI_SCORES_FIT(A);
     // the caller's own bytes of the two sequences (for the aligned strings; loaded here, long before they are needed)
     const uint8_t *__restrict__ raw_ref = A.raw ? A.raw + A.raw_off[pd.ref_id] : nullptr;
@@ -1519,7 +1524,7 @@ __device__ __forceinline__ void traceback_pair(const TraceArgs &A, const PairDes
                         const uint32_t vb = (uint32_t)(vmask >> fb) & 0x1FFFFFu;
                         const uint32_t frun = (uint32_t)__builtin_ctz(~((uint32_t)(amask >> fb) & 0x1FFFFFu));   // 0..21
                         const uint32_t has3 = (vb >> frun) & 1u;                   // bit 21 is never set
-                        if ((!g1 || (vb & 1u)) && (int)score > (int)((g1 + has3) * ugdec + frun * udec)) {
+                        if ((!g1 || (vb & 1u)) && score > (g1 + has3) * ugdec + frun * udec) {    // (score > 0 here: an unsigned compare)
                             const uint32_t isI3 = (uint32_t)(imask >> (fb + frun)) & 1u & has3;
                             const uint32_t nm = (uint32_t)__builtin_popcountll(mm & ((((1ull << frun) - 1ull)) << fb));
                             const uint32_t i1 = g1 & isI1, total = g1 + frun + has3;
@@ -1554,7 +1559,7 @@ __device__ __forceinline__ void traceback_pair(const TraceArgs &A, const PairDes
                     uint32_t run = (uint32_t)__builtin_ctzll(~((amask >> base) & 0x1FFFFFull));     // 0..21
                     if (run > 0) {
                         const uint64_t range = ((1ull << run) - 1ull) << base;
-                        if ((int)score > (int)(run * udec)) {
+                        if (score > run * udec) {
                             // no move lowers the score by more than udec: it stays positive through the whole run
                             const uint32_t nm = (uint32_t)__builtin_popcountll(mm & range);
                             score -= nm * umat + (run - nm) * umis;

@@ -10,6 +10,7 @@ import pytest
 from oracle import sw_oracle as orc
 
 import affine_reference as ar
+import limit_cases as lc
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -85,6 +86,20 @@ def test_affine_kats():
     assert by["AKAT-3s"]["alignments"] != by["AKAT-3t"]["alignments"]
     assert by["AKAT-4"]["score"] == 0 and len(by["AKAT-4"]["alignments"]) == len(by["AKAT-4"]["ref"]) * len(by["AKAT-4"]["read"])
     assert by["AKAT-5"]["alignments"] == []
+
+
+@pytest.mark.parametrize("tie", [0, 1])
+def test_restatements_agree_at_the_score_bounds(tie):
+    """every score at +-2^20 (the GPU tests' inputs at reduced length): align_numpy's int64 against align_scalar's Python
+    ints, which keeps the numpy restatement trustworthy where tests/test_affine_gpu.py leans on it"""
+    for sc in lc.AFFINE_BOUND_SCORES:
+        ref, read = lc.affine_bound_pair(160, 40, 20)
+        got = ar.align_scalar(ref, read, sc, tie)
+        assert got == ar.align_numpy(ref, read, sc, tie), sc
+        assert got[0] >= 40 * lc.L
+    read = lc.rand_seq(random.Random(1410), 96, "AC")
+    sc = lc.AFFINE_BOUND_SCORES[0]
+    assert ar.align_scalar(read, read, sc, tie) == ar.align_numpy(read, read, sc, tie) == (96 * lc.L, [(1, (read, read))])
 
 
 class _FakeBatch:

@@ -14,6 +14,7 @@ from sparksmithwaterman_amd import _capi
 from oracle import sw_oracle as orc
 
 import affine_reference as ar
+import limit_cases as lc
 
 pytestmark = pytest.mark.gpu
 
@@ -231,6 +232,69 @@ def test_affine_bounds(ctx):
     with pytest.raises(_capi.SwmiError) as e:
         b.run(sw.make_params((5, -3, -4)))
     assert e.value.code == ERR_UNSUPPORTED
+    b.free()
+
+
+# 5b -- local mode AT its bounds, against the restatement in unbounded Python ints (fit and global: tests/test_ends_gpu.py)
+@pytest.mark.parametrize("sc", lc.AFFINE_BOUND_SCORES, ids=lc.score_id)
+def test_affine_local_bounds_scores_and_read_length(ctx, sc):
+    """every score at +-2^20 and the longest read: the local cell takes its x bits from the sign of t1 - t2
+    (swmi_affine.hip: "|values| < 2^30 + 2^21, the difference fits"), H reaches 200 * 2^20 on the cut"""
+    ref, read = lc.affine_bound_pair(1024, 200, 50)
+    assert len(read) == 1024 and len(ref) == 300
+    ctx.set_option("affine", 1)                                   # (gap_open = 0 alone would select the linear pipeline)
+    for tie in (0, 1):
+        b = _run(ctx, [ref], [read], sc, tie)
+        assert b.pipeline_mode() == 3
+        assert (b.score(0), b.alignments(0)) == ar.align_scalar(ref, read, sc, tie), (sc, tie)
+        b.free()
+
+
+def test_affine_local_perfect_match_reaches_2_30_and_the_total_wraps(ctx):
+    """1024 matches of 2^20: the largest H the bounds allow; three such pairs make MapRef's Java int total wrap on mode 3"""
+    L = lc.L
+    sc = (L, -L, -L, -L)
+    read = lc.rand_seq(random.Random(1410), 1024, "AC")
+    b = _run(ctx, [read], [read] * 3, sc, 0)
+    assert b.pipeline_mode() == 3
+    want = ar.align_scalar(read, read, sc, 0)
+    assert want == (1 << 30, [(1, (read, read))])
+    for q in range(3):
+        assert b.score(q) == 1 << 30
+        assert (b.score(q), b.alignments(q)) == want
+    total = int(np.array([1 << 30] * 3, dtype=np.int32).sum(dtype=np.int32))
+    assert total == -(1 << 30)
+    assert b.ref_total(0) == total and [int(x) for x in b.ref_totals()] == [total]
+    assert b.ref_sites_packed() == [(total, 0, want[1] * 3)]
+    b.free()
+    b = _run(ctx, [read], [read], sc, 1)
+    assert (b.score(0), b.alignments(0)) == ar.align_numpy(read, read, sc, 1) == want
+    b.free()
+
+
+def test_affine_local_bound_path_lds(ctx):
+    """gap = 0 lifts the cap "the score stays positive" off a local path: path_bound is m + n as in fit and global mode, and
+    the traceback's LDS bounds it the same way (tests/test_ends_gpu.py::test_ends_bound_path_lds): 587760 runs, 587761 does not"""
+    limit = (160 * 1024 // 4 - 4096 - 128 - 1) * 16
+    assert limit == 587760
+    rng = random.Random(1420)
+    ref = list(_rand(rng, limit, "ACT"))
+    for at in (0, 1, 300000, limit - 2):                          # (the read's only matches: four tied maxima)
+        ref[at] = "G"
+    ref = "".join(ref)
+    sc = (2, -3, 0, -2)
+    b = _run(ctx, [ref[:limit - 1]], ["G"], sc, 0)                # m + n = limit
+    assert b.pipeline_mode() == 3
+    assert (b.score(0), b.alignments(0)) == ar.align_scalar(ref[:limit - 1], "G", sc, 0)
+    assert b.n_alignments(0)[0] == 4
+    b.free()
+    b = ctx.upload([ref], ["G"])                                  # m + n = limit + 1
+    with pytest.raises(_capi.SwmiError) as err:
+        b.run(sw.make_params(sc[:3]))
+    assert err.value.code == ERR_UNSUPPORTED
+    ctx.set_option("gap_open", -2)
+    b.run(sw.make_params((2, -3, -1)))                            # gap < 0 caps the path again: the same pair runs
+    assert b.score(0) == 2
     b.free()
 
 

@@ -12,6 +12,8 @@ import sparksmithwaterman_amd as sw
 from sparksmithwaterman_amd import synth
 from oracle import sw_oracle as orc
 
+import limit_cases as lc
+
 pytestmark = pytest.mark.gpu
 
 REF = "CCTGGGTCCTGCCTCGCATCTGACCAGGGCAGGTGGCCTCCTCATCACACTGCTGCCTCTGCTGTTGGCCCTGCTCATGA"   # EngineerData.java:23
@@ -489,3 +491,145 @@ def test_many_tied_maxima_in_every_pair_of_a_large_launch(ctx):
             assert b.score(k) == es and b.n_alignments(k)[0] == len(ea)
             assert b.alignments(k) == ea
         b.free()
+
+
+# ---- Java int wrap-around on every pipeline ----
+# An alphabet of 36 symbols keeps chance matches rare: under these scores nearly every isolated match is a tied maximum,
+# and each one costs an alignment record on both sides of the comparison.  Match and mismatch are outside int4, so every
+# pair takes the compare-and-select cell whatever its symbols are.
+_WIDE = "ABCDEFGHIJKLMNOPQRSTUVWXYZ0123456789"
+
+
+def _wrap_batch():
+    """References of 1, 17, 90 and 333 bases x reads of 1, 3, 64, 65, 130, 257 and 300 (rows per lane 1-4, two strips):
+    exact cuts (runs of matches as long as the read: the sum wraps again and again), a cut with substitutions and both kinds
+    of gap, a read random over AC against AC stretches (dense matches: gaps and wraps interleave), K outside the fast symbols"""
+    rng = random.Random(20261017)
+    ac65 = lc.rand_seq(rng, 65, "AC")
+    r333 = lc.rand_seq(rng, 140, _WIDE) + ac65[10:50] + lc.rand_seq(rng, 153, _WIDE)
+    r90 = lc.rand_seq(rng, 30, _WIDE) + ac65[20:50] + lc.rand_seq(rng, 29, _WIDE) + "K"
+    refs = ["C", lc.rand_seq(rng, 17, "AC"), r90, r333]
+    noisy = list(r333[150:285])
+    for x in (9, 40, 41, 77, 120):
+        noisy[x] = rng.choice(_WIDE)
+    del noisy[100:104]                                            # the read lacks 4 reference bases ...
+    noisy[60:60] = "Q"                                            # ... and has one of its own
+    r300 = r333[20:200] + "K" + lc.rand_seq(rng, 19, _WIDE) + r90[:60] + lc.rand_seq(rng, 40, "AC")
+    reads = ["C", refs[1][6:9], r333[100:164], ac65, "".join(noisy)[:130], r333[30:287], r300]
+    assert [len(x) for x in refs] == [1, 17, 90, 333] and [len(x) for x in reads] == [1, 3, 64, 65, 130, 257, 300]
+    return refs, reads
+
+
+@pytest.mark.parametrize("scores", lc.WRAP_SCORES, ids=lc.score_id)
+def test_scores_that_wrap(ctx, scores):
+    """One batch per score set under which Java int sums wrap (tests/test_oracle.py proves that the wrap changes answers on
+    such inputs): score, every tied cell, every alignment, ref_total and the match sites, in both tie orders"""
+    refs, reads = _wrap_batch()
+    for tie in (0, 1):
+        check_batch(ctx, refs, reads, scores, tie=tie)
+
+
+@pytest.mark.parametrize("m", [64, 257])
+def test_diagonal_that_just_fits_and_just_wraps(ctx, m):
+    """a read cut exactly from the reference: with match a = (2^31 - 1) // m the whole diagonal fits and the score is a * m;
+    with a + 1 the last cell of the diagonal wraps"""
+    rng = random.Random(640 + m)
+    ref = lc.rand_seq(rng, 333, _WIDE)
+    read = ref[40:40 + m]
+    a = (2 ** 31 - 1) // m
+    assert a * m <= 2 ** 31 - 1 < (a + 1) * m
+    for match in (a, a + 1):
+        for tie in (0, 1):
+            check_batch(ctx, [ref], [read], (match, -3, -4), tie=tie)
+    b = ctx.upload([ref], [read])
+    try:
+        assert b.run(sw.make_params((a, -3, -4))).score(0) == a * m
+        wrapped = b.run(sw.make_params((a + 1, -3, -4))).score(0)
+        assert wrapped != (a + 1) * m
+        assert wrapped == orc.opt_alignments((ref, read), (a + 1, -3, -4))[0] and 0 < wrapped < 2 ** 31
+    finally:
+        b.free()
+
+
+@pytest.mark.parametrize("match", [0x7FFFFFFF // 23, 0x7FFFFFFF // 23 + 1])
+def test_walk_shortcuts_at_their_threshold(ctx, match):
+    """The traceback walk takes a run of up to 21 alignment moves and 2 gap moves in one go when the score exceeds that many
+    moves' worth of max(match, mismatch): a 32-bit product that fits up to match = (2^31 - 1) / 23 = 93,368,854 and is switched
+    off above (swmi_kernels.hip: dec_fits).  One match, a deletion, then a run of 21 matches; 22 matches still fit an int."""
+    assert 23 * (0x7FFFFFFF // 23) <= 0x7FFFFFFF < 23 * (0x7FFFFFFF // 23 + 1) and 22 * match - 4 < 2 ** 31
+    rng = random.Random(933)
+    ref = lc.rand_seq(rng, 90, _WIDE)
+    read = ref[30] + ref[32:53]
+    for tie in (0, 1):
+        check_batch(ctx, [ref, ref[20:60]], [read, ref[30:52]], (match, -3, -4), tie=tie)
+    s, al = orc.opt_alignments((ref, read), (match, -3, -4))
+    assert s == 22 * match - 4 and [len(a[1][0]) for a in al] == [23]
+
+
+def test_positive_gap_that_could_wrap(ctx):
+    """The documented deviation (include/swmi.h): the kernels form max(up, left) + gap, so a positive
+    gap under which some H + gap could pass 2^31 - 1 is refused before a launch.  Both sides of the rule: on 17 + 3 bases
+    (10^9, 5, g) is inside for 2 * 10^9 + 20 * g + g <= 2^31 - 1, i.e. up to g = 7,023,030, and matches the oracle there."""
+    ref, read = "CACCACACAACCACACA", "CAC"
+    assert lc.positive_gap_accepted((10 ** 9, 5, 7023030), 20) and not lc.positive_gap_accepted((10 ** 9, 5, 7023031), 20)
+    for tie in (0, 1):
+        check_batch(ctx, [ref], [read], (10 ** 9, 5, 7023030), tie=tie)
+    b = ctx.upload([ref], [read])
+    try:
+        with pytest.raises(sw.SwmiError) as e:
+            b.run(sw.make_params((10 ** 9, 5, 7023031)))
+        assert e.value.code == -5
+        b.run(sw.make_params((10 ** 9, 5, -7023031)))             # (a gap <= 0 is never refused)
+    finally:
+        b.free()
+    b = ctx.upload(["AC"], ["A"])
+    try:
+        for sc in lc.POSITIVE_GAP_WRAP_SCORES:
+            assert not lc.positive_gap_accepted(sc, 3)
+            with pytest.raises(sw.SwmiError) as e:
+                b.run(sw.make_params(sc))
+            assert e.value.code == -5
+    finally:
+        b.free()
+    refs, reads = _wrap_batch()
+    assert lc.positive_gap_accepted((10 ** 9, 5, 7), 633)        # (test_scores_that_wrap's positive gap is inside)
+
+
+def test_ref_total_wraps(ctx):
+    """MapRef's total is a Java int sum (swmi_ref_total, Distribution.java:403-436): three pairs of 2^30 each give -2^30"""
+    rng = random.Random(1730)
+    ref = lc.rand_seq(rng, 120, _WIDE)
+    cuts = [ref[5:21], ref[50:66], ref[100:116], ref[30:46]]
+    sc = (1 << 26, -3, -4)
+    for n_reads, want in ((3, -(1 << 30)), (4, 0)):
+        reads = cuts[:n_reads]
+        b = ctx.upload([ref], reads).run(sw.make_params(sc))
+        try:
+            assert [b.score(q) for q in range(n_reads)] == [1 << 30] * n_reads          # (no pair's own score wraps)
+            t, (_, sites) = orc.map_ref((">gi|r", ref), reads, sc)
+            assert t == want
+            assert b.ref_total(0) == t and (n_reads != 3 or b.ref_total(0) < 0)
+            assert [int(x) for x in b.ref_totals()] == [t]
+            assert b.ref_sites_packed() == [(t, 0, sites)]
+        finally:
+            b.free()
+        check_batch(ctx, [ref], reads, sc)
+
+
+@pytest.mark.parametrize("scores", lc.LARGE_SCORES, ids=lc.score_id)
+def test_large_scores_without_wrap(ctx, scores):
+    """large operands on both sides of every compare and no wrap at all: reads of up to 300 bases, every H below 2^31"""
+    refs, reads = _wrap_batch()
+    assert max(scores) * max(len(x) for x in reads) < 2 ** 31
+    for tie in (0, 1):
+        check_batch(ctx, refs, reads, scores, tie=tie)
+
+
+def test_wrap_kats(ctx):
+    for k in lc.wrap_kats():
+        b = ctx.upload([k["ref"]], [k["read"]]).run(sw.make_params(k["scores"], tuple("aid-"), k["tie_mode"]))
+        try:
+            assert b.score(0) == k["score"], k["name"]
+            assert [[x[0], x[1][0], x[1][1]] for x in b.alignments(0)] == k["alignments"], k["name"]
+        finally:
+            b.free()

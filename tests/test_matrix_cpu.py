@@ -12,6 +12,7 @@ from sparksmithwaterman_amd import matrix as M
 
 import affine_reference as ar
 import matrix_reference as mr
+import limit_cases as lc
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -46,6 +47,23 @@ def test_restatements_agree(tie):
         sc = (rng.randint(-2, 5), rng.randint(-5, 2), -rng.randint(0, 4), -rng.randint(0, 5))
         ref, read = _rand(rng, rng.randint(0, 14), "ACGTNacgtX"), _rand(rng, rng.randint(0, 10), "ACGTNacgtX")
         assert mr.align_scalar(ref, read, sc, mat, tie) == mr.align_numpy(ref, read, sc, mat, tie), (ref, read, sc, mat)
+
+
+@pytest.mark.parametrize("tie", [0, 1])
+def test_restatements_agree_at_the_entry_bound(tie):
+    """the 64-symbol matrix with entries in +-2^20 of tests/test_matrix_gpu.py at reduced length: align_numpy (int64, a
+    256 x 256 table built through the case rule) against align_scalar (Python ints, a dict)"""
+    mat, draw = lc.big_matrix()
+    assert max(max(r) for r in mat[1]) == lc.L and min(min(r) for r in mat[1]) == -lc.L
+    assert any(mat[1][i][j] != mat[1][j][i] for i in range(64) for j in range(64))
+    rng = random.Random(1520 + tie)
+    reads = [lc.rand_seq(rng, m, draw) for m in (1, 33, 65, 128)]
+    refs = [lc.rand_seq(rng, 40, draw), reads[3][20:90] + lc.rand_seq(rng, 30, draw)]
+    for o in (0, -lc.L):
+        sc = (lc.L, -lc.L, -lc.L, o)
+        for ref in refs:
+            for read in reads:
+                assert mr.align_scalar(ref, read, sc, mat, tie) == mr.align_numpy(ref, read, sc, mat, tie), (ref, read, o)
 
 
 @pytest.mark.parametrize("tie", [0, 1])

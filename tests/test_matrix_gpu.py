@@ -18,6 +18,7 @@ from oracle import io_oracle_py as ioo
 from oracle import sw_oracle as orc
 
 import matrix_reference as mr
+import limit_cases as lc
 
 pytestmark = pytest.mark.gpu
 
@@ -301,6 +302,39 @@ def test_bounds(ctx):
         with pytest.raises(_capi.SwmiError) as e:
             ctx.set_option("debug_async_delay_us", bad)
         assert e.value.code == ERR_INVALID
+
+
+# 5b -- the largest matrix the ABI takes, at the entry bound, in local mode
+@pytest.mark.parametrize("tie", [0, 1])
+def test_64_symbols_at_the_entry_bound(ctx, tie):
+    """64 symbols (a 65 x 65 table, 16.9 KB of LDS), bytes at and above 0x80, lower-case letters in the sequences, entries
+    random in +-2^20 with both extremes present, two bytes outside the alphabet; every rows-per-lane class boundary of the
+    narrow sweep and the longest read; gap_open 0 and at its bound.  The scalar restatement (Python ints) checks the short
+    reads, the numpy one (int64; tests/test_matrix_cpu.py holds it to the scalar one on these inputs) the longest."""
+    mat, draw = lc.big_matrix()
+    rng = random.Random(1510 + tie)
+    reads = [lc.rand_seq(rng, m, draw) for m in (1, 64, 65, 1024)]
+    refs = [lc.rand_seq(rng, 40, draw), reads[3][500:700] + lc.rand_seq(rng, 100, draw)]
+    assert any(ord(c) >= 0x80 for c in refs[1]) and any(c.islower() for c in refs[1])
+    L = lc.L
+    for o in (0, -L):
+        sc = (L, -L, -L, o)
+        b = _run(ctx, refs, reads, sc, mat, tie)
+        assert b.pipeline_mode() == 3
+        _check(b, refs, reads, lambda rf, rd: (mr.align_scalar if len(rd) <= 65 else mr.align_numpy)(rf, rd, sc, mat, tie))
+        b.free()
+
+
+def test_all_entries_at_the_bound(ctx):
+    """the matrix test_bounds installs -- 64 symbols, every entry 2^20 -- run on a small pair"""
+    alpha = bytes(range(0x21, 0x21 + 64)).decode("latin-1")
+    mat = (alpha, [[1 << 20] * 64 for _ in range(64)])
+    refs, reads = ["ACGTAC#!~xA", "Z9"], ["CGT!a~", "z"]          # (~ is outside: match / mismatch; x is the symbol X)
+    for sc, tie in (((5, -3, -4, -6), 0), ((1 << 20, -(1 << 20), -(1 << 20), 0), 1)):
+        b = _run(ctx, refs, reads, sc, mat, tie)
+        exp = _check(b, refs, reads, lambda rf, rd: mr.align_scalar(rf, rd, sc, mat, tie))
+        assert exp[(1, 1)][0] == 1 << 20                          # read z / reference Z: one symbol
+        b.free()
 
 
 # 6 -- the JNI shim's entry point from plain C99 (tests/c/shim_matrix.c)

@@ -10,6 +10,8 @@ import pytest
 from oracle import sw_oracle as orc
 from oracle import sw_oracle_py as opy
 
+import limit_cases as lc
+
 REF = "CCTGGGTCCTGCCTCGCATCTGACCAGGGCAGGTGGCCTCCTCATCACACTGCTGCCTCTGCTGTTGGCCCTGCTCATGA"   # EngineerData.java:23
 READ_80 = "AATTTTAGTCTCTCCCTACCCTTTTGGACAGAGCTTCCTGTCCTCTCATTTCACAGGTTATGCAACAGAGGGTTCTGTGT"  # EngineerData.java:26
 READ_20 = "ACTGACTGACTGACTGACTG"   # EngineerData.java:29
@@ -131,3 +133,70 @@ def test_map_ref_goldens_both_oracles(map_ref_goldens):
         assert (t, _norm(sites)) == (g["total"], g["match_sites"]), g["name"]
         t2, (_, s2) = opy.map_ref((">gi|ref0", g["ref"]), g["reads"], tuple(g["scores"]), ("a", "i", "d", "-"), strict=bool(g["tie_mode"]))
         assert (t2, _norm(s2)) == (g["total"], g["match_sites"]), g["name"]
+
+
+# ---- Java int wrap-around: both oracles, and the proof that the inputs make sums wrap ----
+# (the last two: a positive gap under which a GAP sum wraps -- the library refuses those, the reference defines them)
+_ALL_WRAP_SCORES = lc.WRAP_SCORES + lc.POSITIVE_GAP_WRAP_SCORES
+
+
+def _twin_batch(refs, reads, scores, tie):
+    """the Python twin's answers of a batch: every pair's (score, alignments), every reference's MapRef total"""
+    pairs = [[opy.opt_alignments((ref, read), scores, ("a", "i", "d", "-"), strict=bool(tie)) for read in reads] for ref in refs]
+    totals = [opy.map_ref((">gi|r", ref), reads, scores, ("a", "i", "d", "-"), strict=bool(tie))[0] for ref in refs]
+    return [[(s, _norm(a)) for s, a in row] for row in pairs], totals
+
+
+def wrap_changed_pairs(k, tie):
+    """(pairs of small_wrap_batch(k) whose answer the wrap changes, pairs in all): the twin as it is against the twin with
+    _i32 replaced by the identity, i.e. computing in unbounded ints"""
+    refs, reads = lc.small_wrap_batch(k)
+    sc = _ALL_WRAP_SCORES[k]
+    wrapped, _ = _twin_batch(refs, reads, sc, tie)
+    keep = opy._i32
+    opy._i32 = lambda x: x
+    try:
+        plain, _ = _twin_batch(refs, reads, sc, tie)
+    finally:
+        opy._i32 = keep
+    return sum(w != p for rw, rp in zip(wrapped, plain) for w, p in zip(rw, rp)), len(refs) * len(reads)
+
+
+@pytest.mark.parametrize("tie_mode", [0, 1])
+@pytest.mark.parametrize("k", range(len(_ALL_WRAP_SCORES)), ids=[lc.score_id(sc) for sc in _ALL_WRAP_SCORES])
+def test_oracles_agree_where_sums_wrap(k, tie_mode):
+    """sw_oracle.c wraps in uint32 and the twin through _i32: the same scores, alignments and MapRef totals under every
+    wrapping score set -- and the inputs do their job: computed without the wrap, at least one pair's answer differs"""
+    sc = _ALL_WRAP_SCORES[k]
+    refs, reads = lc.small_wrap_batch(k)
+    assert max(map(len, refs)) <= 80 and max(map(len, reads)) <= 40
+    pairs, totals = _twin_batch(refs, reads, sc, tie_mode)
+    for r, ref in enumerate(refs):
+        for q, read in enumerate(reads):
+            s, al = orc.opt_alignments((ref, read), sc, b"aid-", tie_mode)
+            assert (s, _norm(al)) == pairs[r][q], (ref, read, sc)
+            assert 0 <= s < 2 ** 31
+        t, (_, sites) = orc.map_ref((">gi|r", ref), reads, sc, b"aid-", tie_mode)
+        assert t == totals[r]
+        assert _norm(sites) == sorted([a for q in range(len(reads)) for a in pairs[r][q][1]], key=lambda a: a[0])
+    changed, n = wrap_changed_pairs(k, tie_mode)
+    assert changed >= 1, (sc, changed, n)
+    assert opy._i32(1 << 31) == -(1 << 31)                       # (the twin wraps again)
+
+
+def test_wrap_kats_both_oracles():
+    kats = lc.wrap_kats()
+    assert len(kats) >= 3
+    for k in kats:
+        score, alns, H, T = orc.opt_alignments((k["ref"], k["read"]), k["scores"], b"aid-", k["tie_mode"], matrices=True)
+        assert H == k["H"], k["name"]
+        for i, row in enumerate(k.get("T", [])):
+            for j, ch in enumerate(row):
+                if H[i][j] > 0:
+                    assert T[i][j] == ch, (k["name"], i, j)
+        assert (score, _norm(alns)) == (k["score"], k["alignments"]), k["name"]
+        score, alns = opy.opt_alignments((k["ref"], k["read"]), tuple(k["scores"]), ("a", "i", "d", "-"), strict=bool(k["tie_mode"]))
+        assert (score, _norm(alns)) == (k["score"], k["alignments"]), k["name"]
+    by = {k["name"]: k for k in kats}
+    assert by["WKAT-1"]["score"] == 2 ** 31 - 4 != 3 * 2 ** 30   # (3 * 2^30 is what unbounded ints give)
+    assert by["WKAT-3"]["score"] == 2 ** 31 - 1
