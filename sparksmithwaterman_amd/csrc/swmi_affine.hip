@@ -45,6 +45,7 @@
 #include <stdint.h>
 #include "swmi_device.h"
 #include "swmi_emit.h"
+#include "swmi_launch.h"
 
 #define WAVE 64
 #define AFF_WAVES 4                    // wavefronts (= pairs) per workgroup of the sweep

@@ -1,0 +1,357 @@
+// swmi_ctx.cpp -- library and context: ABI version, the thread's last error, options, score matrices, sequence upload.
+#include <cstdarg>
+#include <cstdio>
+#include <cstdlib>
+
+#include "swmi_host.h"
+#include "swmi_launch.h"
+
+// ------------------------------------------------------------------------------------------
+// errors
+// ------------------------------------------------------------------------------------------
+static thread_local std::string g_err;
+
+int swmi_host::fail(int code, const char *fmt, ...) {
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    g_err = buf;
+    return code;
+}
+
+int swmi_io_fail(int code, const std::string &msg) { return fail(code, "%s", msg.c_str()); }
+
+static const uint8_t *code_table();
+
+// ------------------------------------------------------------------------------------------
+// library / context
+// ------------------------------------------------------------------------------------------
+extern "C" int swmi_abi_version(void) { return SWMI_ABI_VERSION; }
+
+extern "C" const char *swmi_last_error(void) { return g_err.c_str(); }
+
+extern "C" int swmi_device_count(int *count) {
+    if (!count) return fail(SWMI_ERR_INVALID, "count is null");
+    int n = 0;
+    hipError_t e = hipGetDeviceCount(&n);
+    if (e != hipSuccess) { *count = 0; return fail(SWMI_ERR_NO_DEVICE, "hipGetDeviceCount: %s", hipGetErrorString(e)); }
+    *count = n;
+    return SWMI_OK;
+}
+
+extern "C" void swmi_default_params(swmi_params *p) {
+    if (!p) return;
+    p->match = 5; p->mismatch = -3; p->gap = -4;            // Distribution.java:36
+    p->tie_mode = SWMI_TIE_SERIAL;
+    p->types[0] = 'a'; p->types[1] = 'i'; p->types[2] = 'd'; p->types[3] = '-';   // Distribution.java:37
+}
+
+static void ctx_release(swmi_ctx *c) {
+    for (auto &ev : c->ev) if (ev) (void)hipEventDestroy(ev);
+    if (c->stream) (void)hipStreamDestroy(c->stream);
+    c->h_err.release();
+    c->d_lut.release();
+    c->d_hdr_ring.release();
+    delete c;
+}
+
+extern "C" int swmi_create(int device, swmi_ctx **out) {
+    if (!out) return fail(SWMI_ERR_INVALID, "out is null");
+    *out = nullptr;
+    int n = 0;
+    hipError_t e = hipGetDeviceCount(&n);
+    if (e != hipSuccess || n <= 0)
+        return fail(SWMI_ERR_NO_DEVICE, "no HIP device available (%s); this library has no CPU fallback",
+                    e != hipSuccess ? hipGetErrorString(e) : "device count 0");
+    if (device < 0 || device >= n) return fail(SWMI_ERR_INVALID, "device %d out of range [0,%d)", device, n);
+    hipDeviceProp_t prop;
+    e = hipGetDeviceProperties(&prop, device);
+    if (e != hipSuccess) return fail(SWMI_ERR_NO_DEVICE, "hipGetDeviceProperties: %s", hipGetErrorString(e));
+    if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
+        return fail(SWMI_ERR_NO_DEVICE, "device %d is %s; the kernels are built for gfx950 (MI355X) only",
+                    device, prop.gcnArchName);
+    e = hipSetDevice(device);
+    if (e != hipSuccess) return fail(SWMI_ERR_NO_DEVICE, "hipSetDevice: %s", hipGetErrorString(e));
+    // (no process-wide hipSetDeviceFlags: a run polls its own stream for `spin_us` before it blocks, see wait_for_stream)
+    swmi_ctx *c = new swmi_ctx;
+    c->device = device;
+    e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
+    if (e != hipSuccess) { c->stream = nullptr; ctx_release(c); return fail(SWMI_ERR_HIP, "hipStreamCreate: %s", hipGetErrorString(e)); }
+    for (auto &ev : c->ev) {
+        e = hipEventCreate(&ev);
+        if (e != hipSuccess) { ev = nullptr; ctx_release(c); return fail(SWMI_ERR_HIP, "hipEventCreate: %s", hipGetErrorString(e)); }
+    }
+    { int r = c->h_err.reserve(64); if (r) { ctx_release(c); return r; } }
+    { static const char *ee = getenv("SWMI_EXT_EVENTS"); if (ee) c->ext_events = atoi(ee) != 0; }
+    *(volatile uint32_t *)c->h_err.p = 0u;
+    { int r = c->d_lut.reserve(256); if (r) { ctx_release(c); return r; } }
+    e = hipMemcpy(c->d_lut.p, code_table(), 256, hipMemcpyHostToDevice);
+    if (e != hipSuccess) { ctx_release(c); return fail(SWMI_ERR_HIP, "code table upload: %s", hipGetErrorString(e)); }
+    *out = c;
+    return SWMI_OK;
+}
+
+extern "C" void swmi_destroy(swmi_ctx *ctx) {
+    if (!ctx) return;
+    (void)hipSetDevice(ctx->device);
+    if (ctx->worker.joinable()) {
+        {
+            std::unique_lock<std::mutex> lk(ctx->job_mu);
+            ctx->job_cv.wait(lk, [&] { return ctx->job_state.load() != 1; });      // a run still in flight
+            ctx->job_state.store(3);
+        }
+        ctx->job_cv.notify_all();
+        ctx->worker.join();
+    }
+    ctx_release(ctx);
+}
+
+extern "C" int swmi_set_option(swmi_ctx *ctx, const char *name, int64_t value) {
+    if (!ctx || !name) return fail(SWMI_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> g(ctx->mu);
+    if (!strcmp(name, "cell_cap")) {
+        if (value < 1 || value > (1 << 20)) return fail(SWMI_ERR_INVALID, "cell_cap out of range");
+        ctx->cell_cap = (uint32_t)value;
+        ctx->cell_cap_set = true;
+    } else if (!strcmp(name, "max_workspace_bytes")) {
+        if (value < (1 << 20)) return fail(SWMI_ERR_INVALID, "max_workspace_bytes too small");
+        ctx->max_workspace_bytes = (uint64_t)value;
+    } else if (!strcmp(name, "mode")) {
+        // -1 is the same as 1 (kept for callers that passed "automatic": mode 0 was measured and is never faster)
+        if (value < -1 || value > 2) return fail(SWMI_ERR_INVALID, "mode must be -1 (automatic), 0, 1 or 2");
+        ctx->mode = value < 0 ? 1u : (uint32_t)value;
+    } else if (!strcmp(name, "auto_ties_x100")) {
+        if (value < 100) return fail(SWMI_ERR_INVALID, "auto_ties_x100 out of range");
+        ctx->auto_ties_x100 = (uint32_t)value;
+    } else if (!strcmp(name, "spin_us")) {
+        if (value < 0) return fail(SWMI_ERR_INVALID, "spin_us out of range");
+        ctx->spin_us = value;
+    } else if (!strcmp(name, "debug_strip_spins")) {
+        ctx->dbg_strip_spins = (uint32_t)value;
+    } else if (!strcmp(name, "debug_reverse_strips")) {
+        ctx->dbg_reverse_strips = value != 0;
+    } else if (!strcmp(name, "debug_async_delay_us")) {
+        if (value < 0 || value > 10000000) return fail(SWMI_ERR_INVALID, "debug_async_delay_us out of range");
+        ctx->dbg_async_delay_us = (uint32_t)value;
+    } else if (!strcmp(name, "tfused")) {
+        if (value < -1 || value > 1) return fail(SWMI_ERR_INVALID, "tfused must be -1 (automatic), 0 or 1");
+        ctx->tfused = (int)value;
+    } else if (!strcmp(name, "resident")) {
+        if (value < -1 || value > 1) return fail(SWMI_ERR_INVALID, "resident must be -1 (automatic), 0 or 1");
+        ctx->resident = (int)value;
+    } else if (!strcmp(name, "scores_only")) {
+        ctx->scores_only = value != 0;
+    } else if (!strcmp(name, "stream_keep_records")) {
+        ctx->stream_keep_records = value != 0;
+    } else if (!strcmp(name, "device_strings")) {
+        ctx->device_strings = value != 0;
+    } else if (!strcmp(name, "tb_split")) {
+        if (value < -1 || value > 1) return fail(SWMI_ERR_INVALID, "tb_split must be -1 (automatic), 0 or 1");
+        ctx->tb_split = (int)value;
+    } else if (!strcmp(name, "col_chunks")) {
+        if (value < 0 || value > 4096) return fail(SWMI_ERR_INVALID, "col_chunks out of range");
+        ctx->col_chunks = (uint32_t)value;
+    } else if (!strcmp(name, "zero_copy")) {
+        ctx->zero_copy = value != 0;
+    } else if (!strcmp(name, "profiling")) {
+        if (value < 0 || value > 2) return fail(SWMI_ERR_INVALID, "profiling must be 0, 1 (every stage) or 2 (the sweep only)");
+        ctx->profiling = (int)value;
+    } else if (!strcmp(name, "gap_open")) {
+        if (value > 0) return fail(SWMI_ERR_INVALID, "gap_open must be <= 0 (a penalty), got %lld", (long long)value);
+        if (value < INT32_MIN) return fail(SWMI_ERR_INVALID, "gap_open out of range");
+        ctx->gap_open = (int32_t)value;
+    } else if (!strcmp(name, "affine")) {
+        if (value != -1 && value != 1) return fail(SWMI_ERR_INVALID, "affine must be -1 (when gap_open != 0) or 1 (always)");
+        ctx->affine = (int)value;
+    } else if (!strcmp(name, "align_mode")) {
+        if (value != SWMI_ALIGN_LOCAL && value != SWMI_ALIGN_FIT && value != SWMI_ALIGN_GLOBAL)
+            return fail(SWMI_ERR_INVALID, "align_mode must be 0 (local), 1 (fit) or 2 (global), got %lld", (long long)value);
+        ctx->align_mode = (int)value;
+    } else if (!strcmp(name, "arena_words_per_pair")) {
+        if (value < 1) return fail(SWMI_ERR_INVALID, "arena_words_per_pair out of range");
+        ctx->arena_words_per_pair = (uint64_t)value;
+    } else {
+        return fail(SWMI_ERR_INVALID, "unknown option '%s'", name);
+    }
+    return SWMI_OK;
+}
+
+extern "C" int swmi_set_score_matrix(swmi_ctx *ctx, const uint8_t *alphabet, uint32_t n, const int32_t *scores) {
+    if (!ctx) return fail(SWMI_ERR_INVALID, "null context");
+    if (n == 0) {                                          // clears the matrix
+        std::lock_guard<std::mutex> g(ctx->mat_mu);
+        ctx->matrix.reset();
+        return SWMI_OK;
+    }
+    if (n > SWMI_MAT_MAX_SYMBOLS) return fail(SWMI_ERR_INVALID, "a score matrix has at most %u symbols, got %u", SWMI_MAT_MAX_SYMBOLS, n);
+    if (!alphabet || !scores) return fail(SWMI_ERR_INVALID, "alphabet or scores is null");
+    const uint8_t *T = code_table();
+    uint32_t cls[256];
+    for (uint32_t c = 0; c < 256; c++) cls[c] = n;         // class n: outside the alphabet
+    for (uint32_t i = 0; i < n; i++) {
+        const uint8_t c = T[alphabet[i]];
+        if (cls[c] != n)
+            return fail(SWMI_ERR_INVALID, "score matrix symbols %u and %u are the same symbol (0x%02x, 0x%02x)", cls[c], i,
+                        alphabet[cls[c]], alphabet[i]);
+        cls[c] = i;
+    }
+    auto M = std::make_shared<ScoreMatrix>();
+    M->n = n;
+    M->max_entry = INT32_MIN;
+    const uint32_t nn = n + 1;
+    M->image.assign(swmi_aff_mat_words(nn), 0u);
+    for (uint64_t x = 0; x < (uint64_t)n * n; x++) {
+        if (std::llabs((int64_t)scores[x]) > (1 << 20))
+            return fail(SWMI_ERR_INVALID, "score matrix entry [%u][%u] = %d: |entries| must be <= 2^20", (uint32_t)(x / n),
+                        (uint32_t)(x % n), scores[x]);
+        M->max_entry = std::max(M->max_entry, scores[x]);
+        M->image[256 + (x / n) * nn + x % n] = (uint32_t)scores[x];
+    }
+    for (uint32_t c = 0; c < 256; c++) M->image[c] = cls[c] * 4u | ((cls[c] == n ? c : 0x1FFu) << 16);
+    static std::atomic<uint64_t> gens{0};
+    M->gen = ++gens;
+    std::lock_guard<std::mutex> g(ctx->mat_mu);
+    ctx->matrix = std::move(M);
+    return SWMI_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// sequence encoding
+// ------------------------------------------------------------------------------------------
+// Canonical base codes: Character.toUpperCase restricted to ISO-8859-1 input (SmithWaterman.java:311-312:
+// a-z and 0xE0-0xFE except 0xF7 drop 0x20; 0xB5 and 0xFF map outside Latin-1 and only equal themselves) followed by a permutation of the byte values that puts the eight
+// "fast" symbols A,C,G,T,N,U,R,Y on the codes 0,4,...,28 (their bit offsets in an 8 x int4 score profile), so that
+// code(x) == code(y)  <=>  toUpperCase(x) == toUpperCase(y).  Sequences made of those symbols only (and scores within
+// int4) run the v_dot8_i32_i4 cell stream -- a reference with N stretches stays on the fast path; any other byte alphabet
+// runs the compare-and-select variant.
+static const uint8_t *code_table() {
+    static uint8_t T[256];
+    static std::once_flag once;              // MapRef.call runs on every executor thread (Distribution.java:32,403)
+    std::call_once(once, [] {
+        uint8_t perm[256];
+        for (int i = 0; i < 256; i++) perm[i] = (uint8_t)i;
+        const uint8_t fast[8] = {'A', 'C', 'G', 'T', 'N', 'U', 'R', 'Y'};
+        for (int k = 0; k < 8; k++) std::swap(perm[fast[k]], perm[4 * k]);   // -> 0,4,...,28
+        for (int i = 0; i < 256; i++) {
+            int u = i;
+            if ((i >= 'a' && i <= 'z') || (i >= 0xE0 && i <= 0xFE && i != 0xF7)) u = i - 32;
+            T[i] = perm[u];
+        }
+    });
+    return T;
+}
+
+// Geometry of the byte images (swmi_device.h): every image 16-byte aligned and followed by SWMI_SEQ_PAD_WORDS zero
+// dwords.  The bytes themselves are canonicalised on the GPU (sw_encode_kernel, swmi_prep.hip).
+static uint64_t layout_sequences(const uint64_t *off, uint32_t n, uint64_t word0, std::vector<SeqDesc> &desc) {
+    desc.resize(n);
+    uint64_t at = word0;
+    for (uint32_t s = 0; s < n; s++) {
+        const uint64_t len = off[s + 1] - off[s];
+        at = (at + 3) & ~(uint64_t)3;
+        SeqDesc d{};
+        d.len = (uint32_t)len;
+        d.boff = (uint32_t)at;                 // (checked against 2^32 by the caller)
+        d.acgt = 0;                            // set by the encode kernel
+        desc[s] = d;
+        at += (len + 3) / 4 + SWMI_SEQ_PAD_WORDS;
+    }
+    return at;
+}
+
+int swmi_host::check_offsets(const uint64_t *off, uint32_t n, const char *what) {
+    if (!off) return fail(SWMI_ERR_INVALID, "%s offsets are null", what);
+    if (off[0] != 0) return fail(SWMI_ERR_INVALID, "%s offsets must start at 0", what);
+    for (uint32_t k = 0; k < n; k++) {
+        if (off[k + 1] < off[k]) return fail(SWMI_ERR_INVALID, "%s offsets decrease at %u", what, k);
+        if (off[k + 1] - off[k] >= (1ull << 30))
+            return fail(SWMI_ERR_UNSUPPORTED, "%s %u is longer than 2^30-1 bases", what, k);
+    }
+    return SWMI_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// upload
+// ------------------------------------------------------------------------------------------
+extern "C" void swmi_batch_free(swmi_ctx *ctx, swmi_batch *b) {
+    if (!b) return;
+    if (ctx) (void)hipSetDevice(ctx->device);
+    b->d_raw.release(); b->d_raw_off.release();
+    b->d_seqw.release(); b->d_refs.release(); b->d_reads.release(); b->d_pairs.release();
+    b->d_dir.release(); b->d_seam.release(); b->d_result.release(); b->d_cells.release();
+    b->d_cells_off.release(); b->d_cells_cap.release(); b->d_dbg.release(); b->d_dbg2.release();
+    b->d_strip_items.release(); b->d_progress.release(); b->d_col_items.release(); b->d_win_off.release(); b->d_queue.release(); b->d_res_items.release();
+    b->d_tf_items.release(); b->d_mat.release();
+    b->h_result.release();
+    delete b;
+}
+
+// Device side of an upload: geometry from the offsets already stored in the batch, the raw bytes H2D, and the
+// canonical images written by sw_encode_kernel.  `ref_src` / `read_src` may be pinned (the streaming path) or pageable.
+// Enqueued on `st` and synchronised before returning.
+int swmi_host::upload_device(swmi_ctx *ctx, swmi_batch *b, hipStream_t st, const uint8_t *ref_src, const uint8_t *read_src) {
+    const uint32_t n_refs = b->n_refs, n_reads = b->n_reads;
+    const uint64_t ref_total = b->ref_off[n_refs], read_total = b->read_off[n_reads];
+    uint64_t words = layout_sequences(b->ref_off.data(), n_refs, 0, b->ref_desc);
+    words = layout_sequences(b->read_off.data(), n_reads, words, b->read_desc);
+    words = ((words + 3) & ~(uint64_t)3) + SWMI_SEQ_PAD_WORDS;
+    if (words >= (1ull << 32)) return fail(SWMI_ERR_UNSUPPORTED, "sequence image exceeds 16 GiB");
+    int rc;
+    const uint64_t read_base = (ref_total + 15) & ~(uint64_t)15;
+    if ((rc = b->d_seqw.reserve(words * 4))) return rc;
+    if ((rc = b->d_raw.reserve(read_base + read_total + 16))) return rc;
+    if ((rc = b->d_raw_off.reserve(((uint64_t)n_refs + n_reads + 2) * 8))) return rc;
+    if ((rc = b->d_refs.reserve(std::max<size_t>(n_refs, 1) * sizeof(SeqDesc)))) return rc;
+    if ((rc = b->d_reads.reserve(std::max<size_t>(n_reads, 1) * sizeof(SeqDesc)))) return rc;
+    HIP_TRY(hipMemsetAsync(b->d_seqw.p, 0, words * 4, st));
+    uint8_t *raw = b->d_raw.as<uint8_t>();
+    uint64_t *roff = b->d_raw_off.as<uint64_t>();
+    if (ref_total) HIP_TRY(hipMemcpyAsync(raw, ref_src, ref_total, hipMemcpyHostToDevice, st));
+    if (read_total) HIP_TRY(hipMemcpyAsync(raw + read_base, read_src, read_total, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(roff, b->ref_off.data(), ((size_t)n_refs + 1) * 8, hipMemcpyHostToDevice, st));
+    // (the reads' offsets are stored absolute -- from the start of `raw` -- so that one base pointer serves both sides)
+    std::vector<uint64_t> read_abs(b->read_off);
+    for (auto &o : read_abs) o += read_base;
+    HIP_TRY(hipMemcpyAsync(roff + n_refs + 1, read_abs.data(), ((size_t)n_reads + 1) * 8, hipMemcpyHostToDevice, st));
+    if (n_refs) HIP_TRY(hipMemcpyAsync(b->d_refs.p, b->ref_desc.data(), n_refs * sizeof(SeqDesc), hipMemcpyHostToDevice, st));
+    if (n_reads) HIP_TRY(hipMemcpyAsync(b->d_reads.p, b->read_desc.data(), n_reads * sizeof(SeqDesc), hipMemcpyHostToDevice, st));
+    HIP_TRY(swmi_launch_encode(raw, roff, b->d_refs.as<SeqDesc>(), b->d_seqw.as<uint32_t>(), ctx->d_lut.as<uint8_t>(), n_refs, st));
+    HIP_TRY(swmi_launch_encode(raw, roff + n_refs + 1, b->d_reads.as<SeqDesc>(), b->d_seqw.as<uint32_t>(),
+                               ctx->d_lut.as<uint8_t>(), n_reads, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    // a new set of sequences invalidates everything derived from the old one
+    b->work_mode = -1; b->plan_key = PlanKey{}; b->pairs_dev_ptr = nullptr; b->pairs_on_device.clear();
+    b->has_run = false; b->acgt_known = false; b->auto_choice = -1;
+    return SWMI_OK;
+}
+
+extern "C" int swmi_batch_upload(swmi_ctx *ctx,
+                                 const uint8_t *ref_bytes, const uint64_t *ref_off, uint32_t n_refs,
+                                 const uint8_t *read_bytes, const uint64_t *read_off, uint32_t n_reads,
+                                 swmi_batch **out) {
+    if (!ctx || !out) return fail(SWMI_ERR_INVALID, "null argument");
+    *out = nullptr;
+    int rc;
+    if ((rc = check_offsets(ref_off, n_refs, "reference"))) return rc;
+    if ((rc = check_offsets(read_off, n_reads, "read"))) return rc;
+    if ((n_refs && ref_off[n_refs] && !ref_bytes) || (n_reads && read_off[n_reads] && !read_bytes))
+        return fail(SWMI_ERR_INVALID, "sequence bytes are null");
+    if ((uint64_t)n_refs * n_reads >= (1ull << 32))
+        return fail(SWMI_ERR_UNSUPPORTED, "more than 2^32-1 pairs in one batch");
+    std::lock_guard<std::mutex> g(ctx->mu);
+    HIP_TRY(hipSetDevice(ctx->device));
+
+    std::unique_ptr<swmi_batch> b(new swmi_batch);
+    b->n_refs = n_refs; b->n_reads = n_reads;
+    b->ref_off.assign(ref_off, ref_off + n_refs + 1);
+    b->read_off.assign(read_off, read_off + n_reads + 1);
+    // the caller's buffers are only valid during this call: the original bytes are kept for the alignment strings
+    // (characters keep their case, SmithWaterman.java:388-406)
+    b->ref_bytes.assign(ref_bytes, ref_bytes + ref_off[n_refs]);
+    b->read_bytes.assign(read_bytes, read_bytes + read_off[n_reads]);
+    if ((rc = upload_device(ctx, b.get(), ctx->stream, ref_bytes, read_bytes))) { swmi_batch_free(ctx, b.release()); return rc; }
+    *out = b.release();
+    return SWMI_OK;
+}

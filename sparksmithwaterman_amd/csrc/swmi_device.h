@@ -1,4 +1,4 @@
-// swmi_device.h -- structures shared by the host runtime (swmi_api.cpp) and the gfx950 kernels
+// swmi_device.h -- structures shared by the host runtime (swmi_host.h and its units) and the gfx950 kernels
 // (swmi_kernels.hip).  HBM data layout of one batch:
 //
 //   seqw   uint32[]   every sequence as a BYTE image: 1 canonical code per base, 4 per dword, image start
@@ -35,6 +35,13 @@
 #define SWMI_CK_BLOCKS     2u         // mode 1: a lane-state checkpoint every 2 blocks = 32 anti-diagonal steps
 #endif                                 // (-DSWMI_CK_BLOCKS=4u builds the 64-step variant measured in profiles/r02/ck_blocks.md)
 #define SWMI_CODE_PAD      0x1FFu     // never equals a base code (codes are 0..255)
+
+// LDS layout constants the host dimensions launches by
+#define SWMI_LDS_BYTES (160u * 1024u)     // LDS of a CU = the most one workgroup may ask for
+#define SWMI_EMIT_SCRATCH_WORDS 128u      // LDS dwords emit_strings needs: 256 characters of each string
+#define SWMI_TB_BLOCKS 16u
+#define SWMI_TB_REFWIN_WORDS 96u      // (16*16 + 63) / 4 + slack
+#define SWMI_RES_CELL_CAP 128u            // maximum cells a resident pair lists in LDS (sw_resident_pairs_kernel)
 
 // op codes of an alignment record (2 bits per traceback step)
 #define SWMI_DIR_D 0u

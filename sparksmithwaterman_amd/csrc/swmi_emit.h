@@ -17,8 +17,6 @@
 #include <stdint.h>
 #include "swmi_device.h"
 
-#define SWMI_EMIT_SCRATCH_WORDS 128u      // LDS dwords emit_strings needs: 256 characters of each string
-
 struct SwmiOpsPerByte {                   // ops staged one per byte (traceback_pair, tf_walk)
     const uint8_t *b;
     __device__ __forceinline__ uint32_t operator()(uint32_t t) const { return b[t]; }

@@ -1,0 +1,331 @@
+// swmi_host.h -- what the units of the host runtime share (internal; the C ABI is include/swmi.h).
+//
+//   swmi_ctx.cpp      library / context / options / score matrix / upload; owns the thread's last error
+//   swmi_run.cpp      run_chunk, batch_run, the async worker, and (swmi_plan.h) the chunk plan -- the whole per-step path, in ONE unit
+//   swmi_results.cpp  the record stream and its lazy index, pair accessors, MapRef views
+//   swmi_stream.cpp   swmi_stream_*
+//   swmi_diag.cpp     SWMI_DEBUG_FILL / SWMI_DEBUG_WATCHDOG printers
+//
+// Owns device memory, the HIP stream, batching/chunking, the overflow re-runs and the host-side assembly of results (the
+// part of the reference that builds Java Strings from the traceback stack, src/sw/SmithWaterman.java:418-431, and MapRef's
+// aggregation, src/sw/Distribution.java:403-436).  All DP arithmetic and every traceback step run in the gfx950 kernels:
+// there is no CPU implementation of the algorithm in this library, and every entry point fails if no GPU is usable.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <atomic>
+#include <condition_variable>
+#include <cstdint>
+#include <cstring>
+#include <memory>
+#include <mutex>
+#include <string>
+#include <thread>
+#include <unordered_map>
+#include <vector>
+
+#include "../../include/swmi.h"
+#include "swmi_device.h"
+#include "swmi_io_internal.h"
+
+// Functions shared between the units: hidden, so that the library exports what include/swmi.h declares and nothing more.
+// None of them is called on the per-step path of a repeated run (fail: errors; settle_raw: the exact-size re-run and
+// streams; the diagnostics: behind their environment switches).
+namespace swmi_host __attribute__((visibility("hidden"))) {
+int fail(int code, const char *fmt, ...);      // sets swmi_last_error(); returns code
+int check_offsets(const uint64_t *off, uint32_t n, const char *what);
+int upload_device(swmi_ctx *ctx, swmi_batch *b, hipStream_t st, const uint8_t *ref_src, const uint8_t *read_src);
+int settle_raw(swmi_batch *b);
+int dump_traceback_diagnostics(swmi_batch *b, const TraceArgs &ta, size_t np, size_t n_tf);
+int dump_fill_diagnostics(swmi_batch *b, const FillArgs &fa, size_t np);
+void watchdog_wait(hipStream_t st, const swmi_batch *b, const char *limit_s);
+}  // namespace swmi_host
+using namespace swmi_host;
+
+#define HIP_TRY(expr)                                                                         \
+    do {                                                                                      \
+        hipError_t e_ = (expr);                                                               \
+        if (e_ != hipSuccess)                                                                 \
+            return fail(e_ == hipErrorOutOfMemory ? SWMI_ERR_NOMEM : SWMI_ERR_HIP,            \
+                        "%s failed: %s", #expr, hipGetErrorString(e_));                       \
+    } while (0)
+
+// ------------------------------------------------------------------------------------------
+// device buffer with capacity (grow-only)
+// ------------------------------------------------------------------------------------------
+struct DevBuf {
+    void *p = nullptr;
+    size_t cap = 0;
+    // Allocations leave headroom (x 1.5 for workspaces of 256 MiB and more, x 1.25 when growing): a stream's chunks differ by a
+    // few per cent, and freeing and re-allocating a 20 GB workspace for every new largest chunk stalled every slot of a stream
+    // for 1.5-3 s each time (hipFree / hipMalloc hold a device-wide lock; profiles/r03/config3_host_breakdown.txt).
+    int reserve(size_t bytes) {
+        if (bytes <= cap) return SWMI_OK;
+        size_t want = bytes >= (256u << 20) ? bytes + bytes / 2 : bytes;      // (big workspaces: the first allocation already leaves room)
+        if (p) { want = std::max(want, cap + cap / 4); (void)hipFree(p); p = nullptr; cap = 0; }
+        hipError_t e = hipMalloc(&p, want);
+        if (e != hipSuccess && want > bytes) { want = bytes; e = hipMalloc(&p, want); }
+        if (e != hipSuccess) { p = nullptr; return fail(SWMI_ERR_NOMEM, "hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e)); }
+        cap = want;
+        return SWMI_OK;
+    }
+    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+    template <class T> T *as() const { return (T *)p; }
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { release(); }                 // (a buffer added to a struct later cannot be forgotten by its free function)
+};
+
+struct PinnedBuf {
+    void *p = nullptr;      // host address
+    void *dp = nullptr;     // the same memory as the GPU addresses it (zero-copy results)
+    size_t cap = 0;
+    int reserve(size_t bytes) {
+        if (bytes <= cap) return SWMI_OK;
+        if (p) { bytes = std::max(bytes, cap + cap / 4); (void)hipHostFree(p); p = nullptr; dp = nullptr; cap = 0; }      // (headroom: see DevBuf)
+        hipError_t e = hipHostMalloc(&p, bytes, hipHostMallocMapped);
+        if (e != hipSuccess) { p = nullptr; return fail(SWMI_ERR_NOMEM, "hipHostMalloc(%zu) failed: %s", bytes, hipGetErrorString(e)); }
+        e = hipHostGetDevicePointer(&dp, p, 0);
+        if (e != hipSuccess) { (void)hipHostFree(p); p = nullptr; return fail(SWMI_ERR_HIP, "hipHostGetDevicePointer: %s", hipGetErrorString(e)); }
+        cap = bytes;
+        return SWMI_OK;
+    }
+    void release() { if (p) (void)hipHostFree(p); p = nullptr; dp = nullptr; cap = 0; }
+    PinnedBuf() = default;
+    PinnedBuf(const PinnedBuf &) = delete;
+    PinnedBuf &operator=(const PinnedBuf &) = delete;
+    ~PinnedBuf() { release(); }
+};
+
+// A substitution score matrix (swmi_set_score_matrix), immutable once built: contexts, stream slots and the batches of the
+// runs that use it share it, so a new matrix set while a run is in flight never touches that run's copy.
+struct ScoreMatrix {
+    uint64_t gen = 0;                       // unique per matrix set (the plan cache and the batch's device copy key on it)
+    uint32_t n = 0;                         // symbols
+    int32_t max_entry = 0;                  // the largest score (path_bound)
+    std::vector<uint32_t> image;            // the device image: swmi_aff_mat_words(n + 1) dwords (swmi_device.h)
+};
+
+// ------------------------------------------------------------------------------------------
+// context
+// ------------------------------------------------------------------------------------------
+struct swmi_ctx {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    std::mutex mu;
+    // options
+    uint32_t cell_cap = 64;
+    uint64_t max_workspace_bytes = 32ull << 30;
+    int profiling = 0;
+    uint32_t mode = 1;                      // requested pipeline (see swmi.h); mode 1 falls back to 2 for scores it cannot handle
+    int zero_copy = 1;                      // kernels write results straight into pinned host memory (no D2H copy)
+    uint64_t arena_words_per_pair = 160;    // first guess of the record arena (header + ops + two strings of a ~180-step alignment), grows on demand
+    uint64_t arena_copy_wpp = 160;          // arena words per pair fetched with the first D2H (tracks the last run)
+    uint64_t recs_per_pair_x16 = 32;        // first guess of the record table: entries per pair x 16, grows on demand
+    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    PinnedBuf h_err;                        // one host-mapped word the kernels raise on an internal failure (strip pipeline timeout)
+    DevBuf d_hdr_ring;                      // arena headers of launches that run sw_tfused_kernel / sw_resident_pairs_kernel ONLY: a fresh zeroed
+    uint32_t hdr_next = 0;                  // slot per launch, so that no kernel has to run first just to reset the bump pointer
+    DevBuf d_lut;                           // 256-byte canonical-code table of the encode kernel
+    int64_t spin_us = 2000;                 // how long a run polls its stream for completion before it blocks (a batch is sub-millisecond)
+    uint32_t dbg_strip_spins = 0;           // test knob: spin budget of the strip pipeline (0 = default)
+    uint32_t dbg_reverse_strips = 0;        // test knob: strip items dispatched consumer-first
+    uint32_t dbg_async_delay_us = 0;        // test knob: the async worker waits this long before it starts a job
+    uint32_t auto_ties_x100 = 300;          // automatic traceback grain: split when a sampled pair has this many tied maxima (x 1/100) on average
+    uint32_t col_chunks = 0;                // test knob: force this many column chunks per pair (0 = automatic)
+    int tb_split = -1;                      // mode-1 traceback grain: -1 automatic, 0 one workgroup per pair, 1 one wavefront per window / alignment
+    bool ext_events = false;                // SWMI_EXT_EVENTS=1: the plain two-kernel run is timed by the dispatches' own start/stop times (pure kernel
+                                            // durations, as rocprofv3 shows them) -- measured 8-12 us per run DEARER than three hipEventRecord, so off
+    int tfused = -1;                        // transposed sweep + traceback by one wavefront per pair (swmi_tfused.hip): -1 automatic, 0 never, 1 whenever a pair qualifies
+    int resident = -1;                      // small pairs handled by one wavefront with the direction field in LDS: -1 automatic, 0 never, 1 whenever it fits
+    int scores_only = 0;                    // 1: the sweep only -- every pair's score (and MapRef's totals), no tied-maximum lists, no alignments
+    int stream_keep_records = 1;            // streams: 0 = a chunk's alignment records are dropped once its scores and counts are taken (a driver
+                                            // that only needs totals and re-aligns its few winners, Distribution.java:341-353)
+    int device_strings = 1;                 // the traceback kernels write both aligned strings behind every record (swmi_emit.h); 0: 2-bit ops only, strings built by the host
+    bool cell_cap_set = false;              // cell_cap given by the caller (otherwise small launches get longer lists)
+    int32_t gap_open = 0;                   // affine gaps: a gap of length k costs gap_open + k * gap (0: linear)
+    int affine = -1;                        // -1: the affine kernels (mode 3) when gap_open != 0; 1: always
+    int align_mode = SWMI_ALIGN_LOCAL;      // SWMI_ALIGN_FIT / _GLOBAL: end-to-end alignment, on the affine kernels
+    std::mutex mat_mu;                      // guards `matrix` (not ctx->mu: setting a matrix does not wait for a run)
+    std::shared_ptr<const ScoreMatrix> matrix;   // swmi_set_score_matrix; a run with one takes the affine kernels
+    // swmi_batch_run_async: one run in flight on the context's own host thread
+    std::thread worker;
+    std::mutex job_mu;
+    std::condition_variable job_cv;
+    std::atomic<int> job_state{0};          // 0 idle, 1 submitted, 2 finished, 3 quit
+    swmi_batch *job_batch = nullptr;
+    swmi_params job_params{};
+    std::shared_ptr<const ScoreMatrix> job_matrix;   // the matrix when swmi_batch_run_async was called
+    int job_align_mode = 0;                          // align_mode when swmi_batch_run_async was called
+    uint32_t job_delay_us = 0;                       // debug_async_delay_us when swmi_batch_run_async was called
+    int job_rc = 0;
+    std::string job_err;
+};
+
+// (in the header: every swmi_batch_run takes the context's matrix, and no per-step call may cross a unit boundary)
+static inline std::shared_ptr<const ScoreMatrix> ctx_matrix(swmi_ctx *ctx) {
+    std::lock_guard<std::mutex> g(ctx->mat_mu);
+    return ctx->matrix;
+}
+
+// one alignment as parsed from the arena
+struct HostAln {
+    uint32_t rank;
+    int32_t begin, end_i, end_j;
+    uint32_t n_ops;
+    const uint32_t *rec = nullptr;   // the alignment's payload in the arena: the two strings written by the kernels, or the packed ops
+    int64_t str_id = -1;    // records without strings: >= 0 once the strings are built, offset of the reference-side string in swmi_batch::str_buf
+};
+
+struct PairRes {
+    int32_t score = 0;
+    uint32_t flags = 0;
+    uint64_t n_cells = 0;
+    uint64_t first = 0;     // index of the pair's first HostAln (ordered)
+    uint64_t count = 0;     // alignment records present (0 when degenerate)
+};
+
+struct SiteRef { uint64_t pair; uint64_t k; int32_t begin; };
+
+struct Work {            // one pair scheduled for a launch
+    uint32_t pair;       // ref * n_reads + read
+    uint64_t cells;      // m * n
+    uint64_t dir_words;  // workspace dwords (direction field or checkpoints)
+    uint64_t seam_words;
+};
+
+// Everything the plan of a chunk (swmi_plan.h: plan_chunk) depends on.  A run whose key equals the key of the plan the
+// batch holds -- a repeated run of the same chunk with the same parameters: bench.py's steps, a Spark job re-running a
+// partition -- skips the per-pair preparation and its uploads.  An input of the planner that is missing here gives a stale
+// plan on such a re-run: add it to BOTH the struct and operator==.
+struct __attribute__((visibility("hidden"))) PlanKey {
+    bool valid = false;                     // false: no plan (a new upload, the sampled pre-pass: they reset the key)
+    size_t lo = 0, hi = 0;                  // the chunk: work[lo, hi) ...
+    const void *work = nullptr;             // ... of this schedule
+    swmi_params params{};
+    uint32_t eff_mode = 0;
+    uint32_t col_chunks = 0;                // the context's options the planner reads
+    bool reverse_strips = false;
+    int resident = -1, tfused = -1;
+    bool exact = false;                     // the exact-size re-run: no resident, no tfused pairs
+    bool scores_only = false;
+    uint64_t mat_gen = 0;                   // the score matrix's generation (0: none): it bounds the paths
+    int align_mode = 0;                     // ... as does the alignment mode
+    const void *d_pairs = nullptr;          // where the chunk's PairDesc image sits on the device, and its size
+    size_t pairs_bytes = 0;
+    bool operator==(const PlanKey &o) const {
+        return valid == o.valid && lo == o.lo && hi == o.hi && work == o.work && memcmp(&params, &o.params, sizeof(swmi_params)) == 0 &&
+               eff_mode == o.eff_mode && col_chunks == o.col_chunks && reverse_strips == o.reverse_strips && resident == o.resident &&
+               tfused == o.tfused && exact == o.exact && scores_only == o.scores_only && mat_gen == o.mat_gen &&
+               align_mode == o.align_mode && d_pairs == o.d_pairs && pairs_bytes == o.pairs_bytes;
+    }
+};
+
+// What the planner derives for a chunk besides the arrays it uploads: the sizes everything downstream is dimensioned by.
+struct __attribute__((visibility("hidden"))) ChunkPlan {
+    uint64_t dir_words = 0, seam_words = 0; // workspace of the launch
+    uint64_t seam_priv_words = 0;           // private seam rows of the strip pipeline's column chunks (behind the shared rows in d_seam)
+    uint32_t max_path = 0, max_read = 0;    // longest possible traceback / longest read
+    size_t n_strip_items = 0;               // mode 1: (pair, column chunk, strip) of every read longer than one strip, one wavefront each
+    size_t n_strip_chunks = 0;              // ... and how many chunk sweeps (0: every multi-strip pair in one)
+    size_t n_col_items = 0;                 // mode 1: column chunks of single-strip pairs when the launch has few pairs
+    uint64_t n_windows = 0;                 // split traceback: checkpoint windows of all pairs
+    size_t n_res = 0;                       // pairs handled whole by sw_resident_pairs_kernel
+    uint32_t res_lds_words = 0, res_ops_words = 0;
+    size_t n_tf = 0;                        // pairs handled whole by sw_tfused_kernel (transposed sweep + traceback)
+    uint32_t tf_max_m = 0, tf_max_n = 0, tf_max_path = 0;
+    uint32_t aff_r_min = 0xFFFFFFFFu, aff_r_max = 0;   // mode 3: rows per lane of the chunk's shortest and longest read
+};
+
+struct swmi_batch {
+    uint32_t n_refs = 0, n_reads = 0;
+    // original bytes (for string building: characters keep their case) and offsets
+    std::vector<uint8_t> ref_bytes, read_bytes;
+    // a streamed chunk keeps no copy of its references: their bytes are read again from the mapped file when an
+    // alignment string is asked for (swmi_stream_push_file)
+    const uint8_t *src_map = nullptr;
+    std::vector<swmi_io_recpos> src_recs;
+    std::unordered_map<uint32_t, std::vector<uint8_t>> src_cache;
+    std::vector<uint64_t> ref_off, read_off;
+    std::vector<SeqDesc> ref_desc, read_desc;
+    // device
+    DevBuf d_raw, d_raw_off;                // the caller's bytes as uploaded (input of the encode kernel) and their offsets
+    DevBuf d_seqw, d_refs, d_reads, d_pairs, d_dir, d_seam, d_result, d_cells, d_cells_off, d_cells_cap, d_dbg, d_dbg2;
+    DevBuf d_strip_items, d_progress;       // mode 1: strip-per-wavefront sweep of long reads
+    DevBuf d_col_items;                     // mode 1: column chunks of single-strip pairs
+    DevBuf d_win_off, d_queue;              // split traceback: per-pair window offsets, walk-item queue
+    DevBuf d_tf_items;                      // pairs of the launch taken by sw_tfused_kernel
+    DevBuf d_res_items;                     // resident pairs of the launch
+    bool views_built = false;               // some MapRef view of the last run was built (they are reset by the next run)
+    bool tb_split_used = false;             // the last run used the split traceback
+    bool acgt_known = false;                // ref_desc/read_desc[].acgt fetched back from the device (set there by the encode kernel)
+    PinnedBuf h_result;
+    // per run
+    swmi_params params{};
+    bool has_run = false;
+    int auto_choice = -1;                   // sampled pre-pass of the automatic traceback grain: 0 tie-heavy, 1 not, -1 not decided yet
+    swmi_params auto_params{};
+    std::vector<Work> work;                 // schedule (pairs sorted by work), valid for work_mode
+    int work_mode = -1;
+    bool work_tfused = false;               // the schedule's workspace sizes leave room for sw_tfused_kernel's column checkpoints
+    uint32_t eff_mode = 1;                  // pipeline of the current run (3: the affine kernels, swmi_affine.hip)
+    int32_t gap_open = 0;                   // the context's gap_open when the run started (mode 3)
+    int align_mode = 0;                     // the context's align_mode when the run was asked for (mode 3)
+    std::shared_ptr<const ScoreMatrix> mat; // the score matrix of the current run (null: none); keeps its host image alive
+    DevBuf d_mat;                           // ... its device image, copied on the run's stream
+    uint64_t d_mat_gen = 0;                 // generation of the matrix in d_mat (0: none)
+    uint64_t work_cells = 0;
+    std::vector<uint8_t> pairs_on_device;   // image of the PairDesc array currently in d_pairs
+    const void *pairs_dev_ptr = nullptr;
+    PlanKey plan_key;                       // the chunk the device-side item lists and `plan` were prepared for last
+    ChunkPlan plan;
+    std::vector<PairRes> pairs;             // by pair index
+    // raw record streams of the last run (one per launch chunk), indexed lazily on the first alignment access
+    // the record table entries (AlnRec, swmi_device.h) and the payload arenas of the launches, one RawChunk per launch
+    struct RawChunk { size_t at, words; size_t tab_at, n_rec; size_t lo; std::vector<uint32_t> wpos; };   // wpos: re-run chunks only
+    std::vector<uint32_t> raw;
+    std::vector<AlnRec> rtab;
+    // a run of ONE launch with results in pinned memory leaves its record stream where the kernels wrote it (the pinned block
+    // is the batch's own and lives until the next run): copied into `raw` only when something needs it there
+    const uint32_t *raw_ext = nullptr;
+    const AlnRec *rtab_ext = nullptr;
+    uint64_t raw_ext_records = 0, raw_ext_cap = 0;
+    std::vector<RawChunk> raw_chunks;
+    bool indexed = false;
+    bool rec_strings = false;               // the records of the last run carry both aligned strings (option device_strings)
+    bool scores_only = false;               // the last run computed scores only (option scores_only): no counts, no alignments
+    bool records_dropped = false;           // a streamed chunk whose records were not kept (option stream_keep_records = 0)
+    std::vector<HostAln> alns;              // grouped by pair, ordered as OptAlignments returns them
+    std::vector<char> str_buf;              // every alignment's two NUL-terminated strings, at fixed offsets (str_at)
+    std::vector<uint64_t> str_at;           // per alignment: offset of its reference-side string; the read side follows it
+    // MapRef view cache
+    std::vector<int8_t> ref_view_ready;
+    std::vector<std::vector<SiteRef>> ref_sites;
+    std::vector<uint64_t> ref_degenerate;   // leading (0,"","") sites per ref
+    swmi_timing timing{};
+};
+
+struct RunState {
+    swmi_ctx *ctx;
+    swmi_batch *b;
+    FillArgs fa{};
+    TraceArgs ta{};
+    float fill_ms = 0, tb_ms = 0, d2h_ms = 0;
+    uint32_t launches = 0;
+    double enqueue_us = 0, wait_us = 0, copyout_us = 0, prep_us = 0, prep_upload_us = 0;
+    bool one_wave_sweep = false;            // the strip pipeline gave up once in this run: long reads are swept by one wavefront
+    bool tb_split = false;                  // mode 1: detect per window + walk per alignment instead of one workgroup per pair
+    bool defer_copy = false;                // this launch is the whole run: its records may stay in the pinned block
+    bool keep = true;                       // the launch's records belong to the batch's results (false: the sampled pre-pass)
+};
+
+// layout of the result block: [ArenaHdr | PairOut x np | record table, tab_cap entries | arena words ...]
+static inline size_t result_out_off() { return 64; }
+static inline size_t result_tab_off(size_t np) { return (64 + np * sizeof(PairOut) + 255) & ~(size_t)255; }
+static inline size_t result_arena_off(size_t np, uint64_t tab_cap) { return (result_tab_off(np) + tab_cap * sizeof(AlnRec) + 255) & ~(size_t)255; }
+// dwords of one alignment's payload: the two strings, n_ops / 4 + 1 dwords each, or the ops packed 16 per dword (swmi_emit.h)
+static inline uint64_t rec_words(uint32_t n_ops, bool strings) {
+    return strings ? 2 * ((uint64_t)n_ops / 4 + 1) : ((uint64_t)n_ops + 15) / 16;
+}

@@ -20,7 +20,7 @@ struct swmi_seqset {
 };
 
 extern "C" const char *swmi_last_error(void);
-int swmi_io_fail(int code, const std::string &msg);   // defined in swmi_api.cpp (thread-local error string)
+int swmi_io_fail(int code, const std::string &msg);   // defined in swmi_ctx.cpp (thread-local error string)
 
 namespace {
 
@@ -137,7 +137,7 @@ extern "C" int swmi_io_read_refs(const char *path, const char *delimiter, swmi_s
 }
 
 // ------------------------------------------------------------------------------------------------
-// segment-wise GetRefSeqs for the streaming path (swmi_stream_push_file, swmi_api.cpp): the same line rules, applied to
+// segment-wise GetRefSeqs for the streaming path (swmi_stream_push_file, swmi_stream.cpp): the same line rules, applied to
 // one slice of the mapped file at a time so that several host threads parse while the GPU aligns earlier slices.
 // ------------------------------------------------------------------------------------------------
 #include "swmi_io_internal.h"

@@ -1,4 +1,4 @@
-// swmi_io_internal.h -- pieces of the native FASTA reader (swmi_io.cpp) the streaming path of swmi_api.cpp uses.
+// swmi_io_internal.h -- pieces of the native FASTA reader (swmi_io.cpp) the streaming path of swmi_stream.cpp uses.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>

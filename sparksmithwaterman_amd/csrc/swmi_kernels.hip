@@ -31,6 +31,7 @@
 #include <stdlib.h>
 #include "swmi_device.h"
 #include "swmi_emit.h"
+#include "swmi_launch.h"
 
 #define WAVE 64
 #ifndef SWMI_HELPER_SLEEP
@@ -1013,8 +1014,6 @@ sw_sweep_winmax_cols_kernel(const FillArgs A) {
 //    tracked score H(pred) = H - s(ref,read) would reach 0 (`while (score > 0)`, SmithWaterman.java:380), and
 //    the whole run is emitted at once.  Gap moves (insertion / deletion) are taken one at a time.
 // ------------------------------------------------------------------------------------------------
-#define SWMI_TB_BLOCKS 16u
-#define SWMI_TB_REFWIN_WORDS 96u      // (16*16 + 63) / 4 + slack
 #define SWMI_TB_SLOTS 4u
 #if SWMI_CK_BLOCKS > 2
 #define SWMI_TB_WAVES 4u            // (64-step windows: a team's span of 4 windows is what the reference-window staging holds)

@@ -1,0 +1,21 @@
+// swmi_launch.h -- the host-callable launchers of the gfx950 kernels (internal).  Included by every .hip file that defines
+// one and by the host units that call one, so that the compiler checks each definition against the prototype its callers
+// see (an `extern "C"` mismatch would otherwise link and break at run time).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "swmi_device.h"
+
+extern "C" hipError_t swmi_launch_fill(const FillArgs *a, hipStream_t st, hipEvent_t ev_start, hipEvent_t ev_stop);
+extern "C" hipError_t swmi_launch_traceback(const TraceArgs *a, hipStream_t st, hipEvent_t ev_start, hipEvent_t ev_stop);
+extern "C" hipError_t swmi_launch_traceback_split(const TraceArgs *a, uint32_t n_windows, hipStream_t st);
+extern "C" hipError_t swmi_launch_resident(const TraceArgs *a, const ResidentArgs *x, hipStream_t st);
+extern "C" hipError_t swmi_launch_tfused(const TraceArgs *a, const TFusedArgs *x, hipStream_t st);
+extern "C" hipError_t swmi_launch_affine_sweep(const FillArgs *a, int32_t gap_open, uint32_t align_mode, uint32_t r_min, uint32_t r_max,
+                                               hipStream_t st);
+extern "C" hipError_t swmi_launch_affine_sweep_matrix(const FillArgs *a, int32_t gap_open, uint32_t align_mode, const uint32_t *mat, uint32_t nn, uint32_t r_min,
+                                                      uint32_t r_max, hipStream_t st);
+extern "C" hipError_t swmi_launch_affine_traceback(const TraceArgs *a, uint32_t align_mode, uint32_t tile_words, uint32_t ops_words,
+                                                   hipStream_t st);
+extern "C" hipError_t swmi_launch_encode(const uint8_t *raw, const uint64_t *raw_off, SeqDesc *desc, uint32_t *seqw,
+                                         const uint8_t *lut, uint32_t n_seq, hipStream_t st);

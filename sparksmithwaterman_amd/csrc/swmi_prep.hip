@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "swmi_device.h"
+#include "swmi_launch.h"
 
 #define WAVE 64
 #define ENC_WAVES 4

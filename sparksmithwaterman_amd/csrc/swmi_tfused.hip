@@ -36,6 +36,7 @@
 #include <stdlib.h>
 #include "swmi_device.h"
 #include "swmi_emit.h"
+#include "swmi_launch.h"
 
 #define WAVE 64
 #define TF_WAVES 4                       // wavefronts of a workgroup that sweep a pair each

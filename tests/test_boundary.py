@@ -159,7 +159,7 @@ def test_two_batches_in_flight_alternating():
 
 @pytest.mark.gpu
 def test_repeated_runs_header_ring_and_deferred_record_stream():
-    """Host-side bookkeeping of repeated runs (swmi_api.cpp): a launch of whole-pair kernels only takes its arena header from a
+    """Host-side bookkeeping of repeated runs (swmi_run.cpp): a launch of whole-pair kernels only takes its arena header from a
     ring of 1024 zeroed slots (1100 runs wrap it); the record stream of a single-launch run stays in the pinned block until an
     alignment is asked for, so a second run must not disturb what the first one handed out, and results read after any number
     of runs are the last run's."""
@@ -190,6 +190,67 @@ def test_repeated_runs_header_ring_and_deferred_record_stream():
         assert b.alignments(5) == first == want[(refs[2], reads[1])][1]
         b.free()
         ctx.close()
+
+
+@pytest.mark.gpu
+def test_plan_cache_follows_every_input():
+    """The chunk plan a batch keeps between runs (swmi_host.h: PlanKey / ChunkPlan) must be made again whenever one of its
+    inputs changes.  ONE batch, never uploaded again, is run under the defaults, then with one input changed at a time and
+    changed back; after every run every pair's score -- and, for three pairs, every alignment -- must equal what a FRESH
+    batch gives under the same settings.  A key that misses an input shows as a difference between the two (a stale plan),
+    or as an SWMI_ERR_*.  The default-settings runs are checked against the oracle as well."""
+    from oracle import sw_oracle as orc
+    rng = random.Random(29)
+    refs = ["".join(rng.choice("ACGT") for _ in range(n)) for n in (30, 400, 2100)]
+    reads = [refs[0][5:25], refs[1][100:250], refs[2][500:800]]          # 20, 150 and 300 bases: the last one takes the strip path
+    refs.append("acgtnACGTNxx" * 10 + reads[1].lower() + "RYKMacgu" * 6)   # lower case and bytes outside ACGT
+    n_pairs = len(refs) * len(reads)
+    watched = (1 * 3 + 1, 2 * 3 + 2, 3 * 3 + 0)                         # (400, 150), (2100, 300), (mixed, 20)
+    want = [orc.opt_alignments((ref, read)) for ref in refs for read in reads]
+    ctx = sw.Context(0)
+    kept = ctx.upload(refs, reads)
+
+    def check(what, params=None, alignments=True, oracle=False):
+        kept.run(params)
+        fresh = ctx.upload(refs, reads).run(params)
+        assert list(kept.scores()) == list(fresh.scores()), what
+        if alignments:
+            for pair in watched:
+                assert kept.alignments(pair) == fresh.alignments(pair), (what, pair)
+        if oracle:
+            assert [int(x) for x in kept.scores()] == [w[0] for w in want], what
+            for pair in watched:
+                assert kept.alignments(pair) == want[pair][1], (what, pair)
+        fresh.free()
+
+    def option(name, value, default):
+        return (lambda: ctx.set_option(name, value)), (lambda: ctx.set_option(name, default))
+
+    m_a = ("ACGT", [[4, -2, -1, -2], [-2, 4, -2, -1], [-1, -2, 4, -2], [-2, -1, -2, 4]])
+    m_b = ("ACGTN", [[9, -3, -3, -3, 0], [-3, 9, -3, -3, 0], [-3, -3, 9, -3, 0], [-3, -3, -3, 9, 0], [0, 0, 0, 0, 1]])
+    nothing = (lambda: None), (lambda: None)
+    steps = [("resident 1", option("resident", 1, -1), None, True),
+             ("tfused 1", option("tfused", 1, -1), None, True),
+             ("col_chunks 3", option("col_chunks", 3, 0), None, True),
+             ("debug_reverse_strips 1", option("debug_reverse_strips", 1, 0), None, True),
+             ("scores_only 1", option("scores_only", 1, 0), None, False),
+             ("params (1,-1,-1)", nothing, sw.make_params((1, -1, -1)), True),
+             ("tie_mode strict", nothing, sw.make_params(tie_mode=sw.TIE_STRICT), True),
+             ("gap_open -5", option("gap_open", -5, 0), None, True),
+             ("score matrix A", ((lambda: ctx.set_score_matrix(*m_a)), ctx.clear_score_matrix), None, True),
+             ("score matrix B", ((lambda: ctx.set_score_matrix(*m_b)), ctx.clear_score_matrix), None, True),
+             ("align_mode fit", option("align_mode", sw.ALIGN_FIT, sw.ALIGN_LOCAL), None, True),       # (every read <= 1,024 bases)
+             ("align_mode global", option("align_mode", sw.ALIGN_GLOBAL, sw.ALIGN_LOCAL), None, True)]
+    check("defaults", oracle=True)
+    check("defaults again", oracle=True)
+    for name, (change, change_back), params, alignments in steps:
+        change()
+        check(name, params, alignments)
+        change_back()
+        check("defaults after " + name, oracle=True)
+    assert n_pairs == 12
+    kept.free()
+    ctx.close()
 
 
 @pytest.mark.gpu
