@@ -36,6 +36,8 @@ public class GpuSmithWaterman
 	static native void nativeSetGapOpen( long ctx , int gapOpen ) ;
 	/** end-to-end alignment on the context: ALIGN_LOCAL, ALIGN_FIT or ALIGN_GLOBAL (include/swmi.h: option "align_mode") */
 	static native void nativeSetAlignMode( long ctx , int alignMode ) ;
+	/** reads longer than 1024 bases on the affine kernels: 1 allowed, 0 refused (include/swmi.h: option "long_reads") */
+	static native void nativeSetLongReads( long ctx , int longReads ) ;
 	/** substitution scores on the context: alphabet = n ISO-8859-1 symbols, scores = n * n, row = read base; null clears */
 	static native void nativeSetScoreMatrix( long ctx , byte[] alphabet , int[] scores ) ;
 	static native void nativeFreeBatch( long ctx , long batch ) ;
@@ -79,6 +81,15 @@ public class GpuSmithWaterman
 			throw new IllegalArgumentException( "alignMode must be ALIGN_LOCAL, ALIGN_FIT or ALIGN_GLOBAL: " + alignMode ) ;
 		ALIGN_MODE = alignMode ;
 	}
+
+	/** whether every context lets the affine kernels take reads longer than 1024 bases (applied next to alignMode, before every batch) */
+	private static volatile boolean LONG_READS = false ;
+
+	/**
+	 * true: runs on the affine kernels (gapOpen, a score matrix, ALIGN_FIT / ALIGN_GLOBAL) take reads longer than 1024 bases, swept in
+	 * strips of 1024 rows; false (the default): such a read is refused.  For every batch aligned from now on, on every executor thread.
+	 */
+	public static void setLongReads( boolean longReads ) { LONG_READS = longReads ; }
 
 	/** the score matrix every context applies before its next batch: { alphabet , scores } (null: none), and its version */
 	private static volatile Object[] MATRIX = null ;
@@ -213,6 +224,7 @@ public class GpuSmithWaterman
 			if( sc.length != 3 && sc.length != 4 ) throw new IllegalArgumentException( "alignScores needs 3 or 4 entries: " + sc.length ) ;
 			nativeSetGapOpen( ctx , sc.length == 4 ? sc[3] : 0 ) ;
 			nativeSetAlignMode( ctx , ALIGN_MODE ) ;
+			nativeSetLongReads( ctx , LONG_READS ? 1 : 0 ) ;
 			applyScoreMatrix( nc ) ;
 			long batch = nativeAlignBatch( ctx , sc[0] , sc[1] , sc[2] , TIE_SERIAL , types , refBuf , refOff , n , readBuf , readOff , reads.size() ) ;
 			try

@@ -56,6 +56,13 @@ JNIEXPORT void JNICALL Java_sw_GpuSmithWaterman_nativeSetAlignMode(JNIEnv *env, 
     if (swmi_shim_set_align_mode((swmi_ctx *)(intptr_t)ctx, alignMode, err, sizeof err) != SWMI_OK) throw_msg(env, err);
 }
 
+/* reads longer than 1024 bases on the affine kernels from now on: 1 allowed, 0 refused */
+JNIEXPORT void JNICALL Java_sw_GpuSmithWaterman_nativeSetLongReads(JNIEnv *env, jclass cls, jlong ctx, jint longReads) {
+    char err[640];
+    (void)cls;
+    if (swmi_shim_set_long_reads((swmi_ctx *)(intptr_t)ctx, longReads, err, sizeof err) != SWMI_OK) throw_msg(env, err);
+}
+
 /* a substitution score matrix on this context from now on: alphabet = n ISO-8859-1 symbols, scores = int[n * n], row = read base;
  * alphabet == null clears it */
 JNIEXPORT void JNICALL Java_sw_GpuSmithWaterman_nativeSetScoreMatrix(JNIEnv *env, jclass cls, jlong ctx, jbyteArray alphabet,

@@ -143,6 +143,18 @@ void        swmi_default_params(swmi_params *p);
  *                3 * |gap_open| + (64 * ceil(m / 64) + n) * |gap| <= 2^31 for the longest read m and reference n of the batch, else
  *                SWMI_ERR_UNSUPPORTED before anything is launched.  A pair with an empty side scores 0 with no alignments in every mode.
  *                A run (async runs and stream slots included) takes the value set when it was asked for.
+ * long_reads (default 0; any value but 0 and 1 is SWMI_ERR_INVALID and leaves the context as it was): 1 lets a run on the affine kernels
+ *                (gap_open, affine, a score matrix, align_mode) take reads of MORE than 1024 bases: such a read is swept in strips of
+ *                1024 rows by the same wavefront and walked across the strips; reads of at most 1024 bases in the
+ *                same batch take the kernels they take today.  The rule "reads of at most 1024 bases" is then a rule on sums.  With m
+ *                the batch's longest read, M = 1024 * ceil(m / 1024) for m > 1024 and 64 * ceil(m / 64) otherwise (the rows a sweep
+ *                computes), and S = the largest of |match|, |mismatch|, |gap|, |gap_open| and the |entries| of the score matrix, a run
+ *                needs  M * S <= 2^30;  global mode needs 3 * |gap_open| + (M + n) * |gap| <= 2^31 with this M; a pair's direction field
+ *                (4 * ceil(m / 1024) * ceil((n + 63) / 8) KiB for m > 1024) must fit max_workspace_bytes; the traceback's bound on a
+ *                pair's longest path (587,760 moves) stays.  Outside them SWMI_ERR_UNSUPPORTED before anything is launched.  The other
+ *                affine bounds (gap <= 0, |scores| <= 2^20) stay; at S = 2^20 the rule is today's M <= 1024.  With 0 nothing changes:
+ *                a read of more than 1024 bases is SWMI_ERR_UNSUPPORTED.  A run (async runs and stream slots included) takes the value
+ *                set when it was asked for.
  * Further knobs: spin_us (how long a run polls its stream before it blocks, default 2000); col_chunks (0 automatic,
  * 1 never, N > 1 force up to N column chunks per pair: a launch of few pairs with long references is swept by several
  * wavefronts per pair -- a read of more than 256 rows by several strip pipelines); debug_strip_spins / debug_reverse_strips (tests of the strip pipeline's give-up path);

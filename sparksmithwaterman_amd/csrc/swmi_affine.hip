@@ -34,6 +34,14 @@
 //   only -- one lane, one row slot -- from INT32_MIN up: every column j of row m that ties (fit) or the one cell (m,n) (global).
 //   The x bits come from compares: the operands may be negative and their difference need not fit int32.
 //
+// sw_affine_sweep_long[_fit|_global][_matrix]_kernel: reads longer than 1024 bases (option "long_reads", DESIGN.md "Long
+//   reads").  Still one wavefront per pair: the read is swept in ceil(m / 1024) strips of 1024 rows, every strip with R = 16
+//   (the last one padded with SWMI_CODE_PAD rows), each strip leaving the field of a (1024, n) pair; the strips' fields are
+//   consecutive.  What lane 0 reads from above in strips 1.. is the SEAM: (H, F) of the strip's last row, written by lane 63
+//   of the strip above into one row of n pairs per pair in HBM, rewritten in place strip after strip.  The threshold and the
+//   cell list live on across the strips; cells carry global row indices.  These kernels return for m <= 1024, the others for
+//   m > 1024: the host launches each over the pairs it takes.
+//
 // sw_affine_traceback_kernel: one wavefront per (pair, slot); slot s walks the pair's maximum cells s, s + S, ...  The walk
 //   is the three-state machine of DESIGN.md "Affine gaps"; the field is staged in LDS a tile of consecutive 8-step blocks at a
 //   time (a path never moves to a later step), the ops are packed 16 per dword in LDS, and the record goes out through
@@ -41,6 +49,8 @@
 // sw_affine_traceback_{fit,global}_kernel: the walk of the end-to-end modes.  It ends at row 0, not at a code 0; at column 0
 //   the rest of the read is inserted without touching the field; global mode then deletes the rest of the reference;
 //   `begin` follows the moves that consume a reference base.
+// sw_affine_traceback_long[_fit|_global]_kernel: the same walks over the strips' fields: row i is in strip (i - 1) / 1024; a
+//   step up from a strip's first row goes to lane 63, row slot 15 of the strip above; the LDS tile is keyed by the strip too.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "swmi_device.h"
@@ -81,6 +91,13 @@ __device__ __forceinline__ uint32_t lanes_below(uint64_t mask) {
 __shared__ uint32_t aff_mkey[256];
 __shared__ int aff_mtab[SWMI_MAT_NN_MAX * SWMI_MAT_NN_MAX];
 
+// the strip sweeps (LONG): lane 0's feed from above and lane 63's hand-over to the next strip
+struct AffSeam {
+    int h, f;              // lanes 0..7: (H, F) of the row above the strip at the 8 columns lane 0 takes in this block
+    int2 *row;             // the pair's seam row: (H, F) per column
+    uint32_t wlane;        // the lane that writes it (63), none in the read's last strip
+};
+
 template <int R>
 struct AffState {
     int h[R], e[R];        // H and E of the lane's rows at its previous column
@@ -96,11 +113,13 @@ struct AffState {
 // 8 anti-diagonal steps t0 .. t0+7 (a lane outside its column range keeps its state).  The steps are a loop, not unrolled:
 // eight copies of R cells let the scheduler hoist the compares of many cells at once, and their masks spilled the SGPRs.
 // MODE != AFF_LOCAL: vrows is the row slot of read row m in the lane that owns it, 0xFFFFFFFF in every other lane
-template <int R, bool STRICT, bool MATRIX, int MODE>
+// LONG: one strip of a long read -- lane 0 is fed from Z (every strip, the first one too: its Z holds row 0 of the mode) and lane
+// Z.wlane leaves (H, F) of its last row in the seam row
+template <int R, bool STRICT, bool MATRIX, int MODE, bool LONG = false>
 __device__ __forceinline__ void aff_block8(AffState<R> &S, const uint2 rw, const uint32_t t0, const uint32_t lane,
                                            const uint32_t n, const uint32_t row0, const uint32_t vrows,
                                            const int o, const int e, const int vmat, const int vmis,
-                                           uint2 *__restrict__ cells, const uint32_t ccap) {
+                                           uint2 *__restrict__ cells, const uint32_t ccap, const AffSeam &Z = AffSeam{}) {
     const int oe = o + e;
 #pragma unroll 1
     for (uint32_t s = 0; s < 8; ++s) {
@@ -109,12 +128,15 @@ __device__ __forceinline__ void aff_block8(AffState<R> &S, const uint2 rw, const
         const int feed = MATRIX ? (int)aff_mkey[fb] : (int)fb;  // (wave-uniform: lane 0's column)
         S.rb = aff_shr1(feed, S.rb);
         int nh, nf;
-        if constexpr (MODE == AFF_LOCAL) {
+        if constexpr (LONG) {
+            nh = aff_shr1(__builtin_amdgcn_readlane(Z.h, (int)s), S.h[R - 1]);
+            nf = aff_shr1(__builtin_amdgcn_readlane(Z.f, (int)s), S.f_last);
+        } else if constexpr (MODE == AFF_LOCAL) {
             nh = aff_shr1_zero(S.h[R - 1]);
             nf = aff_shr1_zero(S.f_last);
         }
         const uint32_t c0 = t0 + s - lane;                       // column index j - 1 of this lane
-        if constexpr (MODE != AFF_LOCAL) {
+        if constexpr (MODE != AFF_LOCAL && !LONG) {
             // lane 0 reads row 0 of the mode: H(0,j) = 0 (fit) or o + j*e (global), F(0,j) := H(0,j) + o
             // (unsigned arithmetic: lane 0 runs up to 70 columns past n, where the value is not used)
             const int h0 = MODE == AFF_GLOBAL ? (int)((uint32_t)o + (c0 + 1u) * (uint32_t)e) : 0;
@@ -172,6 +194,7 @@ __device__ __forceinline__ void aff_block8(AffState<R> &S, const uint2 rw, const
                 else                             { if ((uint32_t)k == vrows) mrow = hv; }
             }
             S.f_last = fup;
+            if constexpr (LONG) { if (lane == Z.wlane) Z.row[c0] = make_int2(S.h[R - 1], fup); }
         }
         S.nh_prev = nh;
         if constexpr (MODE != AFF_LOCAL) {
@@ -274,6 +297,94 @@ __device__ __forceinline__ void aff_sweep_pair(const FillArgs &A, const int o, c
     }
 }
 
+// A read of more than 1024 bases, strip after strip (R = 16 in every strip).
+// The seam row is rewritten IN PLACE.  In a strip, lane 0 is at column t + 1 at step t and its block of 8 columns is loaded at
+// the block's first step, so a load at step t touches columns >= t + 1; lane 63 is at column t - 62 at step t.  A column is
+// therefore read (by this strip) at least 63 steps before this strip overwrites it, and what it reads was written by the strip
+// above, whose stores all precede the fence between the strips.  Vector loads and stores only: the row is rewritten by
+// vector stores of this kernel, which the scalar cache does not see.
+template <bool STRICT, bool MATRIX, int MODE>
+__device__ __forceinline__ void aff_sweep_long_pair(const FillArgs &A, const int o, const PairDesc pd, const uint32_t lane, const uint32_t nn) {
+    constexpr int R = SWMI_AFF_RMAX;
+    const SeqDesc rd = A.refs[pd.ref_id];
+    const SeqDesc qd = A.reads[pd.read_id];
+    const uint32_t n = rd.len, m = qd.len;
+    const uint32_t *__restrict__ refw = A.seqw + rd.boff;
+    const uint32_t *__restrict__ readw = A.seqw + qd.boff;
+    const uint32_t NS = swmi_aff_strips(m), W = swmi_aff_strip_blocks(n);
+    const uint64_t cbase = A.cells_off ? A.cells_off[pd.out_id] : (uint64_t)pd.out_id * A.cell_cap;
+    const uint32_t ccap = A.cells_cap ? A.cells_cap[pd.out_id] : A.cell_cap;
+    uint2 *__restrict__ cells = A.cells + cbase;
+    AffSeam Z;
+    Z.row = reinterpret_cast<int2 *>(A.seam + pd.seam_off);
+
+    AffState<R> S;
+    S.thr = MODE == AFF_LOCAL ? 1 : INT32_MIN; S.cnt = 0;       // (wave-uniform: they live on across the strips)
+    for (uint32_t sx = 0; sx < NS; ++sx) {
+        const uint32_t row0 = sx * SWMI_AFF_MAX_READ + lane * R;             // global index of the lane's first row, less 1
+        // (the end-to-end modes track row m alone, which is in the last strip)
+        const uint32_t vrows = MODE != AFF_LOCAL ? (m - 1u - row0 < (uint32_t)R ? m - 1u - row0 : 0xFFFFFFFFu)
+                             : row0 >= m ? 0u : (m - row0 < (uint32_t)R ? m - row0 : (uint32_t)R);
+#pragma unroll
+        for (int k = 0; k < R; ++k) {
+            const uint32_t row = row0 + (uint32_t)k;
+            S.q[k] = row < m ? (int)((readw[row >> 2] >> (8u * (row & 3u))) & 0xFFu) : (int)SWMI_CODE_PAD;
+            if (MATRIX) {                                        // (as in aff_sweep_pair)
+                const uint32_t key = row < m ? aff_mkey[S.q[k]] : ((nn - 1u) * 4u) | (0xFFFFu << 16);
+                const uint32_t hi = (key >> 16) == 0x1FFu ? 0x3FFu : key >> 16;
+                S.q[k] = (int)(((key & 0xFFFFu) * nn) | (hi << 16));
+            }
+            if constexpr (MODE == AFF_LOCAL) {
+                S.h[k] = 0;
+                S.e[k] = 0;
+            } else {                                             // column 0, global row index
+                S.h[k] = o + (int)(row + 1u) * A.gap;
+                S.e[k] = S.h[k] + o;
+            }
+        }
+        S.rb = 0; S.f_last = 0;
+        // nh_prev of lane 0: H(1024 * sx, 0)
+        S.nh_prev = MODE != AFF_LOCAL && sx ? o + (int)(sx * SWMI_AFF_MAX_READ) * A.gap : 0;
+        Z.wlane = sx + 1u < NS ? 63u : 0xFFFFFFFFu;
+        uint32_t *__restrict__ dir = A.dir + pd.dir_off + (uint64_t)sx * swmi_aff_strip_words(n);
+        // the strip above has written the whole seam row: its stores are in memory before this strip loads any of it
+        if (sx) __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent");
+        for (uint32_t w = 0; w < W; ++w) {
+            const uint32_t t0 = 8u * w;
+            const uint2 rw = *reinterpret_cast<const uint2 *>(refw + (t0 >> 2));
+            // lane 0's feed from above at columns t0 + 1 .. t0 + 8, one column per lane 0..7: row 0 of the mode (as in
+            // aff_block8), below it the seam -- the true F, not the H + o stand-in of row 0
+            const uint32_t c = t0 + lane;
+            Z.h = MODE == AFF_GLOBAL ? (int)((uint32_t)o + (c + 1u) * (uint32_t)A.gap) : 0;
+            Z.f = MODE == AFF_LOCAL ? 0 : (int)((uint32_t)Z.h + (uint32_t)o);
+            if (sx) {
+                int2 v = make_int2(0, 0);
+                if (lane < 8u && c < n) v = Z.row[c];
+                Z.h = v.x; Z.f = v.y;
+            }
+#pragma unroll
+            for (int k = 0; k < R; ++k) S.acc[k] = 0u;
+            aff_block8<R, STRICT, MATRIX, MODE, true>(S, rw, t0, lane, n, row0, vrows, o, A.gap, A.match, A.mismatch, cells, ccap, Z);
+            uint32_t *__restrict__ dst = dir + (uint64_t)w * R * WAVE + lane;
+#pragma unroll
+            for (int k = 0; k < R; ++k) dst[k * WAVE] = S.acc[k];
+        }
+    }
+    if (lane == 0) {
+        PairOut po;
+        if (MODE == AFF_LOCAL && S.cnt == 0u) {
+            po.score = 0;
+            po.flags = SWMI_F_DEGENERATE;
+            po.n_cells = (uint64_t)m * n;
+        } else {
+            po.score = S.thr;
+            po.flags = S.cnt > ccap ? SWMI_F_CELL_OVF : 0u;
+            po.n_cells = S.cnt;
+        }
+        A.out[pd.out_id] = po;
+    }
+}
+
 // RLO..RHI: the rows per lane this instantiation of the kernel takes (the others' registers would cap its occupancy)
 template <int RLO, int RHI, bool STRICT, bool MATRIX, int MODE>
 __device__ __forceinline__ void aff_sweep_dispatch(const FillArgs &A, const int o, const PairDesc pd, const uint32_t R, const uint32_t lane,
@@ -285,7 +396,8 @@ __device__ __forceinline__ void aff_sweep_dispatch(const FillArgs &A, const int 
 }
 
 // mat / nn (MATRIX only): the score matrix image (swmi_aff_mat_words) and its side n + 1
-template <int RLO, int RHI, bool MATRIX, int MODE = AFF_LOCAL>
+// LONG: the strip sweep of reads longer than 1024 bases (RLO, RHI unused)
+template <int RLO, int RHI, bool MATRIX, int MODE = AFF_LOCAL, bool LONG = false>
 __device__ __forceinline__ void aff_sweep_entry(const FillArgs &A, const int o, const uint32_t *__restrict__ mat, const uint32_t nn) {
     if (blockIdx.x == 0 && threadIdx.x == 0) A.hdr->reserved = 0ull;      // the traceback's bump allocator
     if (MATRIX) {                                                          // (before any wavefront leaves)
@@ -301,6 +413,12 @@ __device__ __forceinline__ void aff_sweep_entry(const FillArgs &A, const int o, 
     if (pair >= A.n_pairs) return;
     const uint32_t lane = threadIdx.x & 63u;
     const PairDesc pd = A.pairs[pair];
+    if constexpr (LONG) {
+        if (uni(A.reads[pd.read_id].len) <= SWMI_AFF_MAX_READ) return;
+        if (A.strict) aff_sweep_long_pair<true, MATRIX, MODE>(A, o, pd, lane, nn);
+        else          aff_sweep_long_pair<false, MATRIX, MODE>(A, o, pd, lane, nn);
+        return;
+    }
     const uint32_t R = uni(swmi_aff_rows_per_lane(A.reads[pd.read_id].len));
     if (R < (uint32_t)RLO || R > (uint32_t)RHI) return;
     if (A.strict) aff_sweep_dispatch<RLO, RHI, true, MATRIX, MODE>(A, o, pd, R, lane, nn);
@@ -342,6 +460,19 @@ extern "C" __global__ void __launch_bounds__(WAVE * AFF_WAVES) sw_affine_sweep_m
 AFF_ENDS_KERNELS(fit, AFF_FIT)
 AFF_ENDS_KERNELS(global, AFF_GLOBAL)
 #undef AFF_ENDS_KERNELS
+// reads longer than 1024 bases (option "long_reads"): one kernel per mode, plain and matrix
+#define AFF_LONG_KERNELS(name, MODE)                                                                                                  \
+    extern "C" __global__ void __launch_bounds__(WAVE * AFF_WAVES) sw_affine_sweep_##name##_kernel(const FillArgs A, const int gap_open) { \
+        aff_sweep_entry<SWMI_AFF_RMAX, SWMI_AFF_RMAX, false, MODE, true>(A, gap_open, nullptr, 0u);                                  \
+    }                                                                                                                                 \
+    extern "C" __global__ void __launch_bounds__(WAVE * AFF_WAVES) sw_affine_sweep_##name##_matrix_kernel(                            \
+        const FillArgs A, const int gap_open, const uint32_t *mat, const uint32_t nn) {                                               \
+        aff_sweep_entry<SWMI_AFF_RMAX, SWMI_AFF_RMAX, true, MODE, true>(A, gap_open, mat, nn);                                       \
+    }
+AFF_LONG_KERNELS(long, AFF_LOCAL)
+AFF_LONG_KERNELS(long_fit, AFF_FIT)
+AFF_LONG_KERNELS(long_global, AFF_GLOBAL)
+#undef AFF_LONG_KERNELS
 
 // ------------------------------------------------------------------------------------------------
 // traceback
@@ -460,6 +591,130 @@ __device__ __forceinline__ void aff_traceback(const TraceArgs A, const uint32_t 
         WAVE_SYNC();
     }
 }
+
+// aff_traceback for the pairs of the strip sweeps (reads longer than 1024 bases): R = 16, the field of strip sx at
+// sx * swmi_aff_strip_words(n).  A sibling, not a parameter: the walk above keeps its code.
+template <int MODE>
+__device__ __forceinline__ void aff_traceback_long(const TraceArgs A, const uint32_t tile_words, const uint32_t ops_words) {
+    extern __shared__ uint32_t lds[];
+    const uint32_t lane = threadIdx.x;
+    const uint32_t slot = blockIdx.y, nslots = gridDim.y;
+    const PairDesc pd = A.pairs[blockIdx.x];
+    const PairOut po = A.out[pd.out_id];
+    if (A.out_host && slot == 0 && lane == 0) A.out_host[pd.out_id] = po;      // result straight into pinned host memory
+    if (po.flags & (SWMI_F_DEGENERATE | SWMI_F_CELL_OVF)) return;
+    if (po.n_cells <= slot) return;
+    uint32_t *tile = lds;
+    uint32_t *ops = lds + tile_words;
+    uint32_t *scratch = ops + ops_words;
+    const SeqDesc rd = A.refs[pd.ref_id];
+    const SeqDesc qd = A.reads[pd.read_id];
+    const uint32_t n = rd.len, m = qd.len;
+    const uint32_t R = SWMI_AFF_RMAX;
+    const uint32_t W = uni(swmi_aff_strip_blocks(n));
+    const uint32_t blk_words = R * WAVE;                          // dwords of one 8-step block
+    const uint32_t NB = tile_words / blk_words;                   // blocks per tile (>= 1: the host sizes the tile)
+    const uint32_t max_ops = ops_words * 16u;
+    const uint32_t *__restrict__ dir = A.dir + pd.dir_off;
+    const uint8_t *__restrict__ raw_ref = A.raw ? A.raw + A.raw_off[pd.ref_id] : nullptr;
+    const uint8_t *__restrict__ raw_read = A.raw ? A.raw + A.raw_off[A.raw_reads_at + pd.read_id] : nullptr;
+    const uint64_t cbase = A.cells_off ? A.cells_off[pd.out_id] : (uint64_t)pd.out_id * A.cell_cap;
+    const uint2 *__restrict__ cells = A.cells + cbase;
+    const uint32_t ncell = (uint32_t)po.n_cells;
+    uint32_t wlo = 0xFFFFFFFFu, whi = 0u;                         // blocks [wlo, whi) are in the tile
+    uint32_t tsx = 0xFFFFFFFFu;                                   // ... of this strip
+    const uint32_t NS = uni(swmi_aff_strips(m));
+
+    for (uint32_t c = slot; c < ncell; c += nslots) {
+        const uint32_t ci = uni(cells[c].x), cj = uni(cells[c].y);
+        uint32_t i = ci, j = cj;
+        uint32_t l = (i - 1u) / R, k = (i - 1u) - l * R;          // (global) lane and row slot of row i
+        uint32_t sx = l / WAVE;                                   // its strip, and the lane within it
+        l -= sx * WAVE;
+        uint32_t st = 0u;                                         // 0: H, else the state entered (AFF_DIAG / AFF_INS / AFF_DEL)
+        uint32_t n_ops = 0, cur = 0;
+        int begin = MODE == AFF_LOCAL ? 0 : (int)cj;
+        bool ok = true;
+        while (MODE == AFF_LOCAL ? (i != 0u && j != 0u) : (i != 0u)) {
+            if (MODE != AFF_LOCAL && j == 0u) {                   // the read's head hangs over the reference start: inserted,
+                if (n_ops >= max_ops) { ok = false; break; }      // and the field is not touched
+                --i;
+                cur |= SWMI_DIR_I << (2u * (n_ops & 15u));
+                ++n_ops;
+                if ((n_ops & 15u) == 0u) { if (lane == 0) ops[(n_ops >> 4) - 1u] = cur; cur = 0u; }
+                continue;
+            }
+            const uint32_t t = j - 1u + l, w = t >> 3;
+            if (w < wlo || w >= whi || sx != tsx) {             // stage the tile that ends at this block
+                if (w >= W || sx >= NS) { ok = false; break; }    // (a corrupted list: never walks off the field)
+                WAVE_SYNC();
+                wlo = w + 1u >= NB ? w + 1u - NB : 0u;
+                whi = w + 1u;
+                tsx = sx;
+                const uint32_t *__restrict__ src = dir + (uint64_t)sx * swmi_aff_strip_words(n) + (uint64_t)wlo * blk_words;
+                const uint32_t words = (whi - wlo) * blk_words;
+                for (uint32_t x = lane; x < words; x += WAVE) tile[x] = src[x];
+                WAVE_SYNC();
+            }
+            const uint32_t code = uni((tile[((w - wlo) * R + k) * WAVE + l] >> (4u * (t & 7u))) & 15u);
+            if (st == 0u) {
+                st = code & 3u;
+                if (MODE == AFF_LOCAL) { if (st == AFF_STOP) break; }   // H(i, j) == 0: `while (score > 0)` (SmithWaterman.java:380)
+                else if (st == AFF_STOP) { ok = false; break; }         // (these sweeps write no code 0: a corrupted field)
+            }
+            if (n_ops >= max_ops) { ok = false; break; }
+            if (MODE == AFF_LOCAL || st != AFF_INS) begin = (int)j;     // (end-to-end: the moves that consume a reference base)
+            uint32_t op;
+            if (st == AFF_DIAG) {
+                op = SWMI_DIR_A;
+                st = 0u;
+                --i; --j;
+            } else if (st == AFF_INS) {
+                op = SWMI_DIR_I;
+                st = (code & 8u) ? AFF_INS : 0u;
+                --i;
+            } else {
+                op = SWMI_DIR_D;
+                st = (code & 4u) ? AFF_DEL : 0u;
+                --j;
+            }
+            if (op != SWMI_DIR_D) {
+                if (k != 0u) --k;
+                else if (l != 0u) { k = R - 1u; --l; }
+                else { k = R - 1u; l = WAVE - 1u; --sx; }         // up from a strip's first row: the last row of the strip above
+            }
+            cur |= op << (2u * (n_ops & 15u));
+            ++n_ops;
+            if ((n_ops & 15u) == 0u) { if (lane == 0) ops[(n_ops >> 4) - 1u] = cur; cur = 0u; }
+        }
+        if (MODE == AFF_GLOBAL) {                                 // row 0: the rest of the reference is deleted
+            while (ok && j != 0u) {
+                if (n_ops >= max_ops) { ok = false; break; }
+                begin = (int)j;
+                --j;
+                cur |= SWMI_DIR_D << (2u * (n_ops & 15u));
+                ++n_ops;
+                if ((n_ops & 15u) == 0u) { if (lane == 0) ops[(n_ops >> 4) - 1u] = cur; cur = 0u; }
+            }
+        }
+        if ((n_ops & 15u) != 0u && lane == 0) ops[n_ops >> 4] = cur;
+        WAVE_SYNC();
+        const bool strings = A.raw != nullptr;
+        const uint32_t words = swmi_payload_words(n_ops, strings);
+        unsigned long long off;
+        uint32_t rslot;
+        if (ok && swmi_reserve(A, lane, words, 1u, off, rslot)) {
+            uint32_t *dst = A.arena + off;
+            if (lane == 0) swmi_write_rec(A, rslot, pd.out_id, SWMI_RANK_BY_CELL, begin, ci, cj, n_ops, off);
+            if (strings) swmi_emit_strings(dst, SwmiOpsPacked{ops}, n_ops, ci, cj, raw_ref, raw_read, lane, scratch);
+            else for (uint32_t x = lane; x < words; x += WAVE) dst[x] = ops[x];
+        } else if (lane == 0) {
+            atomicOr(&A.out[pd.out_id].flags, SWMI_F_ARENA_OVF);
+            if (A.ovf_host) *A.ovf_host = 1u;
+        }
+        WAVE_SYNC();
+    }
+}
 }  // namespace
 
 extern "C" __global__ void __launch_bounds__(WAVE) sw_affine_traceback_kernel(const TraceArgs A, const uint32_t tile_words,
@@ -473,6 +728,18 @@ extern "C" __global__ void __launch_bounds__(WAVE) sw_affine_traceback_fit_kerne
 extern "C" __global__ void __launch_bounds__(WAVE) sw_affine_traceback_global_kernel(const TraceArgs A, const uint32_t tile_words,
                                                                                       const uint32_t ops_words) {
     aff_traceback<AFF_GLOBAL>(A, tile_words, ops_words);
+}
+extern "C" __global__ void __launch_bounds__(WAVE) sw_affine_traceback_long_kernel(const TraceArgs A, const uint32_t tile_words,
+                                                                                    const uint32_t ops_words) {
+    aff_traceback_long<AFF_LOCAL>(A, tile_words, ops_words);
+}
+extern "C" __global__ void __launch_bounds__(WAVE) sw_affine_traceback_long_fit_kernel(const TraceArgs A, const uint32_t tile_words,
+                                                                                        const uint32_t ops_words) {
+    aff_traceback_long<AFF_FIT>(A, tile_words, ops_words);
+}
+extern "C" __global__ void __launch_bounds__(WAVE) sw_affine_traceback_long_global_kernel(const TraceArgs A, const uint32_t tile_words,
+                                                                                           const uint32_t ops_words) {
+    aff_traceback_long<AFF_GLOBAL>(A, tile_words, ops_words);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -508,19 +775,41 @@ extern "C" hipError_t swmi_launch_affine_sweep_matrix(const FillArgs *a, int32_t
     return hipGetLastError();
 }
 
-extern "C" hipError_t swmi_launch_affine_traceback(const TraceArgs *a, uint32_t align_mode, uint32_t tile_words, uint32_t ops_words,
-                                                   hipStream_t st) {
+// the strip sweeps of reads longer than 1024 bases (option "long_reads"); mat: the score matrix image and nn its side, or null
+extern "C" hipError_t swmi_launch_affine_sweep_long(const FillArgs *a, int32_t gap_open, uint32_t align_mode, const uint32_t *mat, uint32_t nn,
+                                                    hipStream_t st) {
+    if (a->n_pairs == 0) return hipSuccess;
+    if (align_mode > 2u || (mat && (nn < 2u || nn > SWMI_MAT_NN_MAX))) return hipErrorInvalidValue;
+    const dim3 grid((a->n_pairs + AFF_WAVES - 1) / AFF_WAVES), block(WAVE * AFF_WAVES);
+    if (mat) {
+        auto *const kern = align_mode == 0u ? sw_affine_sweep_long_matrix_kernel
+                                            : align_mode == 1u ? sw_affine_sweep_long_fit_matrix_kernel : sw_affine_sweep_long_global_matrix_kernel;
+        hipLaunchKernelGGL(kern, grid, block, 0, st, *a, (int)gap_open, mat, nn);
+    } else {
+        auto *const kern = align_mode == 0u ? sw_affine_sweep_long_kernel
+                                            : align_mode == 1u ? sw_affine_sweep_long_fit_kernel : sw_affine_sweep_long_global_kernel;
+        hipLaunchKernelGGL(kern, grid, block, 0, st, *a, (int)gap_open);
+    }
+    return hipGetLastError();
+}
+
+// long_reads: the walk over the strips' fields (every pair of the launch has a read longer than 1024 bases)
+extern "C" hipError_t swmi_launch_affine_traceback(const TraceArgs *a, uint32_t align_mode, uint32_t long_reads, uint32_t tile_words,
+                                                   uint32_t ops_words, hipStream_t st) {
     if (a->n_pairs == 0) return hipSuccess;
     if (align_mode > 2u) return hipErrorInvalidValue;
     static const bool attrs = [] {
-        for (auto *k : {sw_affine_traceback_kernel, sw_affine_traceback_fit_kernel, sw_affine_traceback_global_kernel})
+        for (auto *k : {sw_affine_traceback_kernel, sw_affine_traceback_fit_kernel, sw_affine_traceback_global_kernel,
+                        sw_affine_traceback_long_kernel, sw_affine_traceback_long_fit_kernel, sw_affine_traceback_long_global_kernel})
             (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         return true;
     }();
     (void)attrs;
     const size_t lds = ((size_t)tile_words + ops_words + SWMI_EMIT_SCRATCH_WORDS) * sizeof(uint32_t);
-    auto *const kern = align_mode == 0u ? sw_affine_traceback_kernel
-                                        : align_mode == 1u ? sw_affine_traceback_fit_kernel : sw_affine_traceback_global_kernel;
+    auto *const kern = long_reads ? (align_mode == 0u ? sw_affine_traceback_long_kernel
+                                                      : align_mode == 1u ? sw_affine_traceback_long_fit_kernel : sw_affine_traceback_long_global_kernel)
+                                  : (align_mode == 0u ? sw_affine_traceback_kernel
+                                                      : align_mode == 1u ? sw_affine_traceback_fit_kernel : sw_affine_traceback_global_kernel);
     hipLaunchKernelGGL(kern, dim3(a->n_pairs, SWMI_AFF_TB_SLOTS), dim3(WAVE), lds, st, *a, tile_words, ops_words);
     return hipGetLastError();
 }

@@ -283,10 +283,21 @@ SWMI_HD static inline uint32_t swmi_aff_blocks(uint32_t m, uint32_t n) {
     const uint32_t R = swmi_aff_rows_per_lane(m), lact = m ? (m + R - 1u) / R : 1u;
     return (uint32_t)(((uint64_t)n + lact - 1u + 7u) / 8u);
 }
-// dwords of a pair's affine direction field: one dword per (block, row slot, lane)
+// ---- reads longer than SWMI_AFF_MAX_READ (option "long_reads"): swept in strips of 1024 rows, every strip with 16 rows per lane ----
+// strips of a read of m bases (the last one padded with SWMI_CODE_PAD rows)
+SWMI_HD static inline uint32_t swmi_aff_strips(uint32_t m) { return m ? (m + SWMI_AFF_MAX_READ - 1u) / SWMI_AFF_MAX_READ : 1u; }
+// 8-step blocks of ONE strip's field: the field of a (1024, n) pair, all 64 lanes own rows
+SWMI_HD static inline uint32_t swmi_aff_strip_blocks(uint32_t n) { return (uint32_t)(((uint64_t)n + 63u + 7u) / 8u); }
+// dwords of one strip's field: [block][row slot][lane]
+SWMI_HD static inline uint64_t swmi_aff_strip_words(uint32_t n) { return (uint64_t)swmi_aff_strip_blocks(n) * SWMI_AFF_RMAX * 64u; }
+// dwords of a pair's affine direction field: one dword per (block, row slot, lane); m > 1024: the strips' fields, consecutive
 SWMI_HD static inline uint64_t swmi_aff_dir_words(uint32_t m, uint32_t n) {
+    if (m > SWMI_AFF_MAX_READ) return (uint64_t)swmi_aff_strips(m) * swmi_aff_strip_words(n);
     return (uint64_t)swmi_aff_blocks(m, n) * swmi_aff_rows_per_lane(m) * 64u;
 }
+// dwords of a mode-3 pair's seam row: (H, F) of the strip's last row at every column, one row rewritten in place by every
+// strip but the last (reads of one strip have none)
+SWMI_HD static inline uint64_t swmi_aff_seam_words(uint32_t m, uint32_t n) { return m > SWMI_AFF_MAX_READ ? 2ull * n : 0ull; }
 // score matrices (swmi_set_score_matrix) on the affine sweeps: at most 64 symbols, plus class n = outside the alphabet.
 // Device image: 256 key dwords by base code (class * 4 | hi << 16, hi = the code outside the alphabet, else 0x1FF), then the
 // (n+1) x (n+1) int32 scores, row = read class, column = reference class (row and column n are not read: the kernel fills them).

@@ -148,6 +148,7 @@ struct swmi_ctx {
     int32_t gap_open = 0;                   // affine gaps: a gap of length k costs gap_open + k * gap (0: linear)
     int affine = -1;                        // -1: the affine kernels (mode 3) when gap_open != 0; 1: always
     int align_mode = SWMI_ALIGN_LOCAL;      // SWMI_ALIGN_FIT / _GLOBAL: end-to-end alignment, on the affine kernels
+    int long_reads = 0;                     // 1: the affine kernels take reads longer than 1024 bases, swept in strips (swmi.h)
     std::mutex mat_mu;                      // guards `matrix` (not ctx->mu: setting a matrix does not wait for a run)
     std::shared_ptr<const ScoreMatrix> matrix;   // swmi_set_score_matrix; a run with one takes the affine kernels
     // swmi_batch_run_async: one run in flight on the context's own host thread
@@ -159,6 +160,7 @@ struct swmi_ctx {
     swmi_params job_params{};
     std::shared_ptr<const ScoreMatrix> job_matrix;   // the matrix when swmi_batch_run_async was called
     int job_align_mode = 0;                          // align_mode when swmi_batch_run_async was called
+    int job_long_reads = 0;                          // long_reads when swmi_batch_run_async was called
     uint32_t job_delay_us = 0;                       // debug_async_delay_us when swmi_batch_run_async was called
     int job_rc = 0;
     std::string job_err;
@@ -213,13 +215,14 @@ struct __attribute__((visibility("hidden"))) PlanKey {
     bool scores_only = false;
     uint64_t mat_gen = 0;                   // the score matrix's generation (0: none): it bounds the paths
     int align_mode = 0;                     // ... as does the alignment mode
+    int long_reads = 0;                     // option "long_reads" of the run
     const void *d_pairs = nullptr;          // where the chunk's PairDesc image sits on the device, and its size
     size_t pairs_bytes = 0;
     bool operator==(const PlanKey &o) const {
         return valid == o.valid && lo == o.lo && hi == o.hi && work == o.work && memcmp(&params, &o.params, sizeof(swmi_params)) == 0 &&
                eff_mode == o.eff_mode && col_chunks == o.col_chunks && reverse_strips == o.reverse_strips && resident == o.resident &&
                tfused == o.tfused && exact == o.exact && scores_only == o.scores_only && mat_gen == o.mat_gen &&
-               align_mode == o.align_mode && d_pairs == o.d_pairs && pairs_bytes == o.pairs_bytes;
+               align_mode == o.align_mode && long_reads == o.long_reads && d_pairs == o.d_pairs && pairs_bytes == o.pairs_bytes;
     }
 };
 
@@ -236,7 +239,8 @@ struct __attribute__((visibility("hidden"))) ChunkPlan {
     uint32_t res_lds_words = 0, res_ops_words = 0;
     size_t n_tf = 0;                        // pairs handled whole by sw_tfused_kernel (transposed sweep + traceback)
     uint32_t tf_max_m = 0, tf_max_n = 0, tf_max_path = 0;
-    uint32_t aff_r_min = 0xFFFFFFFFu, aff_r_max = 0;   // mode 3: rows per lane of the chunk's shortest and longest read
+    uint32_t aff_r_min = 0xFFFFFFFFu, aff_r_max = 0;   // mode 3: rows per lane of the chunk's shortest and longest read of at most 1024 bases
+    size_t aff_n_long = 0;                  // mode 3: pairs whose read is longer (the strip kernels); they are the LAST of the PairDesc array
 };
 
 struct swmi_batch {
@@ -273,6 +277,7 @@ struct swmi_batch {
     uint32_t eff_mode = 1;                  // pipeline of the current run (3: the affine kernels, swmi_affine.hip)
     int32_t gap_open = 0;                   // the context's gap_open when the run started (mode 3)
     int align_mode = 0;                     // the context's align_mode when the run was asked for (mode 3)
+    int long_reads = 0;                     // ... and its long_reads
     std::shared_ptr<const ScoreMatrix> mat; // the score matrix of the current run (null: none); keeps its host image alive
     DevBuf d_mat;                           // ... its device image, copied on the run's stream
     uint64_t d_mat_gen = 0;                 // generation of the matrix in d_mat (0: none)

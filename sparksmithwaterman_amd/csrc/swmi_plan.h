@@ -299,10 +299,16 @@ static int plan_chunk(swmi_ctx *ctx, swmi_batch *b, const std::vector<Work> &wor
         if (m_ != pb_m || n_ != pb_n) { pb_m = m_; pb_n = n_; pb_val = (uint32_t)path_bound(n_, m_, b->params, smax, b->align_mode); }   // (runs of equal lengths)
         plan.max_path = std::max<uint32_t>(plan.max_path, pb_val);
         plan.max_read = std::max(plan.max_read, m_);
+        if (m_ > SWMI_AFF_MAX_READ) { plan.aff_n_long++; continue; }      // (mode 3 with long_reads: the strip kernels' pair)
         plan.aff_r_min = std::min(plan.aff_r_min, swmi_aff_rows_per_lane(m_));
         plan.aff_r_max = std::max(plan.aff_r_max, swmi_aff_rows_per_lane(m_));
     }
     pl.finish(work, lo);
+    if (b->eff_mode == 3 && plan.aff_n_long) {
+        // the strip kernels' pairs go last (each keeps its out_id and its offsets): the sweeps and the tracebacks of the two
+        // kinds are launched over their own part of the array
+        std::stable_partition(it.pd.begin(), it.pd.end(), [&](const PairDesc &d) { return b->read_desc[d.read_id].len <= SWMI_AFF_MAX_READ; });
+    }
     return SWMI_OK;
 }
 
@@ -354,6 +360,7 @@ static int prepare_chunk(RunState &rs, const std::vector<Work> &work, size_t lo,
     key.resident = ctx->resident; key.tfused = ctx->tfused;
     key.exact = cells_exact != nullptr; key.scores_only = ctx->scores_only != 0;
     key.mat_gen = b->mat ? b->mat->gen : 0u; key.align_mode = b->align_mode;
+    key.long_reads = b->long_reads;
     key.d_pairs = b->d_pairs.p; key.pairs_bytes = np * sizeof(PairDesc);
     auto p1 = p0;
     if (key == b->plan_key) {

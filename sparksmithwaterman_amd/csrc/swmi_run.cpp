@@ -258,11 +258,17 @@ static int enqueue_launches(RunState &rs, Launch &L, const ResidentArgs &xa, con
     if (ctx->profiling && !ext) HIP_TRY(hipEventRecord(ctx->ev[0], ctx->stream));
     if (first && !L.whole_only) {       // the workspace survives an arena-overflow retry
         if (fa.n_strip_items) HIP_TRY(hipMemsetAsync(fa.progress, 0, (size_t)fa.n_strip_items * sizeof(uint32_t), ctx->stream));
-        if (b->eff_mode == 3 && b->mat)
-            HIP_TRY(swmi_launch_affine_sweep_matrix(&fa, b->gap_open, (uint32_t)b->align_mode, b->d_mat.as<uint32_t>(), b->mat->n + 1u,
-                                                    plan.aff_r_min, plan.aff_r_max, ctx->stream));
-        else if (b->eff_mode == 3)
-            HIP_TRY(swmi_launch_affine_sweep(&fa, b->gap_open, (uint32_t)b->align_mode, plan.aff_r_min, plan.aff_r_max, ctx->stream));
+        if (b->eff_mode == 3) {
+            // the pairs of the strip kernels (reads longer than 1024 bases, option "long_reads") are the last aff_n_long
+            FillArgs fs = fa, fl = fa;
+            fs.n_pairs = (uint32_t)(np - plan.aff_n_long);
+            fl.n_pairs = (uint32_t)plan.aff_n_long; fl.pairs = fa.pairs + fs.n_pairs;
+            const uint32_t *mat = b->mat ? b->d_mat.as<uint32_t>() : nullptr;
+            const uint32_t nn = b->mat ? b->mat->n + 1u : 0u;
+            if (mat) HIP_TRY(swmi_launch_affine_sweep_matrix(&fs, b->gap_open, (uint32_t)b->align_mode, mat, nn, plan.aff_r_min, plan.aff_r_max, ctx->stream));
+            else     HIP_TRY(swmi_launch_affine_sweep(&fs, b->gap_open, (uint32_t)b->align_mode, plan.aff_r_min, plan.aff_r_max, ctx->stream));
+            HIP_TRY(swmi_launch_affine_sweep_long(&fl, b->gap_open, (uint32_t)b->align_mode, mat, nn, ctx->stream));
+        }
         else HIP_TRY(swmi_launch_fill(&fa, ctx->stream, ext ? ctx->ev[0] : nullptr, ext ? ctx->ev[1] : nullptr));
         rs.launches++;
     }
@@ -286,8 +292,12 @@ static int enqueue_launches(RunState &rs, Launch &L, const ResidentArgs &xa, con
         if (!first || L.whole_only) HIP_TRY(hipMemsetAsync(ta.q_count, 0, 4, ctx->stream));      // (no sweep kernel ran to zero it)
         HIP_TRY(swmi_launch_traceback_split(&ta, (uint32_t)plan.n_windows, ctx->stream));
     } else if (b->eff_mode == 3) {
-        HIP_TRY(swmi_launch_affine_traceback(&ta, (uint32_t)b->align_mode, SWMI_AFF_TILE_WORDS, (uint32_t)(((uint64_t)plan.max_path + 15) / 16 + 1),
-                                             ctx->stream));
+        TraceArgs ts = ta, tl = ta;
+        ts.n_pairs = (uint32_t)(np - plan.aff_n_long);
+        tl.n_pairs = (uint32_t)plan.aff_n_long; tl.pairs = ta.pairs + ts.n_pairs;
+        const uint32_t ops_words = (uint32_t)(((uint64_t)plan.max_path + 15) / 16 + 1);
+        HIP_TRY(swmi_launch_affine_traceback(&ts, (uint32_t)b->align_mode, 0u, SWMI_AFF_TILE_WORDS, ops_words, ctx->stream));
+        HIP_TRY(swmi_launch_affine_traceback(&tl, (uint32_t)b->align_mode, 1u, SWMI_AFF_TILE_WORDS, ops_words, ctx->stream));
     } else if (n_res + n_tf < np) {
         HIP_TRY(swmi_launch_traceback(&ta, ctx->stream, ext ? ctx->ev[2] : nullptr, ext ? ctx->ev[3] : nullptr));
     }
@@ -503,7 +513,9 @@ static int run_chunk(RunState &rs, const std::vector<Work> &work, size_t lo, siz
 // a run of the whole batch
 // ------------------------------------------------------------------------------------------
 // what a run cannot compute, refused before anything is launched (under ctx->mu: the context's options are read)
-static int check_run_params(const swmi_ctx *ctx, const swmi_batch *b, const swmi_params *p, bool affine, int align_mode) {
+// mat: the run's score matrix or null; long_reads: option "long_reads" of the run
+static int check_run_params(const swmi_ctx *ctx, const swmi_batch *b, const swmi_params *p, bool affine, int align_mode,
+                            const ScoreMatrix *mat, int long_reads) {
     if (p->tie_mode != SWMI_TIE_SERIAL && p->tie_mode != SWMI_TIE_STRICT)
         return fail(SWMI_ERR_INVALID, "unknown tie_mode %d", p->tie_mode);
     // GetAlignment tests `align == alignTypes[0]`, then `== alignTypes[1]`, else deletion
@@ -520,15 +532,33 @@ static int check_run_params(const swmi_ctx *ctx, const swmi_batch *b, const swmi
         if (std::llabs((int64_t)p->match) > lim || std::llabs((int64_t)p->mismatch) > lim || std::llabs((int64_t)p->gap) > lim ||
             std::llabs((int64_t)ctx->gap_open) > lim)
             return fail(SWMI_ERR_UNSUPPORTED, "affine gaps need |match|, |mismatch|, |gap|, |gap_open| <= 2^20");
-        for (uint32_t q = 0; q < b->n_reads; q++)
+        for (uint32_t q = 0; q < b->n_reads && !long_reads; q++)
             if (b->read_desc[q].len > SWMI_AFF_MAX_READ)
-                return fail(SWMI_ERR_UNSUPPORTED, "affine gaps: read %u has %u bases (at most %u)", q, b->read_desc[q].len, SWMI_AFF_MAX_READ);
+                return fail(SWMI_ERR_UNSUPPORTED, "affine gaps: read %u has %u bases (at most %u; option long_reads lifts the limit)", q,
+                            b->read_desc[q].len, SWMI_AFF_MAX_READ);
+        longest_sequences(b, max_m, max_n);
+        // the rows a sweep computes for the longest read: whole strips of 1024 above 1024 bases, else whole lanes' rows
+        const uint64_t rows = max_m > SWMI_AFF_MAX_READ ? (uint64_t)SWMI_AFF_MAX_READ * swmi_aff_strips((uint32_t)max_m) : 64 * ((max_m + 63) / 64);
+        if (long_reads) {
+            // M * S <= 2^30 (swmi.h, DESIGN.md "Long reads"): H <= M * S, and no sum of the recurrence leaves int32
+            int64_t S = std::max(std::max(std::llabs((int64_t)p->match), std::llabs((int64_t)p->mismatch)),
+                                 std::max(std::llabs((int64_t)p->gap), std::llabs((int64_t)ctx->gap_open)));
+            if (mat)
+                for (size_t x = 256; x < mat->image.size(); x++) S = std::max<int64_t>(S, std::llabs((int64_t)(int32_t)mat->image[x]));
+            if ((int64_t)rows * S > ((int64_t)1 << 30))
+                return fail(SWMI_ERR_UNSUPPORTED, "long_reads: the longest read (%llu bases) is swept as %llu rows, and %llu * %lld (the largest "
+                            "|score|) is above 2^30", (unsigned long long)max_m, (unsigned long long)rows, (unsigned long long)rows, (long long)S);
+            // a pair of several strips is one launch's work at the least: refused when its field alone is over the cap
+            if (max_m > SWMI_AFF_MAX_READ && max_n && swmi_aff_dir_words((uint32_t)max_m, (uint32_t)max_n) * 4 > ctx->max_workspace_bytes)
+                return fail(SWMI_ERR_UNSUPPORTED, "long_reads: the direction field of the longest read (%llu) against the longest reference (%llu) "
+                            "takes %llu bytes, more than max_workspace_bytes (%llu)", (unsigned long long)max_m, (unsigned long long)max_n,
+                            (unsigned long long)(swmi_aff_dir_words((uint32_t)max_m, (uint32_t)max_n) * 4), (unsigned long long)ctx->max_workspace_bytes);
+        }
         if (align_mode == SWMI_ALIGN_GLOBAL) {
             // global mode: the smallest sum a sweep forms is 3 * gap_open + (64 * ceil(m / 64) + n) * gap (swmi.h, DESIGN.md
             // "End-to-end modes"); it must not leave int32.  Checked per pair in 64-bit arithmetic: it falls with m and n, so
             // the longest read against the longest reference decides.
-            longest_sequences(b, max_m, max_n);
-            const int64_t low = 3 * (int64_t)ctx->gap_open + (int64_t)(64 * ((max_m + 63) / 64) + max_n) * (int64_t)p->gap;
+            const int64_t low = 3 * (int64_t)ctx->gap_open + (int64_t)(rows + max_n) * (int64_t)p->gap;
             if (max_m && max_n && low < (int64_t)INT32_MIN)
                 return fail(SWMI_ERR_UNSUPPORTED, "align_mode global: 3 * gap_open + (64 * ceil(m / 64) + n) * gap = %lld for the longest read "
                             "(%llu) and reference (%llu) is below -2^31", (long long)low, (unsigned long long)max_m, (unsigned long long)max_n);
@@ -618,6 +648,9 @@ static void build_schedule(const swmi_ctx *ctx, swmi_batch *b) {
     std::stable_sort(ro.begin(), ro.end(), [&](uint32_t a, uint32_t c) { return b->ref_desc[a].len > b->ref_desc[c].len; });
     std::stable_sort(qo.begin(), qo.end(), [&](uint32_t a, uint32_t c) { return b->read_desc[a].len > b->read_desc[c].len; });
     const bool refs_uniform = n_refs && b->ref_desc[ro.front()].len == b->ref_desc[ro.back()].len;
+    // (mode 3: the seam row of a read of several strips, none otherwise)
+    const bool aff = b->eff_mode == 3;
+    auto seam_words = [aff](uint32_t m, uint32_t n) { return aff ? swmi_aff_seam_words(m, n) : swmi_seam_words(m, n); };
     auto add = [&](uint32_t r, uint32_t q, uint32_t n, uint32_t m, uint64_t dw, uint64_t sw) {
         Work w;
         w.pair = r * n_reads + q;
@@ -633,7 +666,7 @@ static void build_schedule(const swmi_ctx *ctx, swmi_batch *b) {
             if (m == 0) continue;
             const uint32_t n = n_refs ? b->ref_desc[ro[0]].len : 0;
             if (n == 0) break;
-            const uint64_t dw = swmi_dir_words(m, n, b->eff_mode, tf), sw = swmi_seam_words(m, n);
+            const uint64_t dw = swmi_dir_words(m, n, b->eff_mode, tf), sw = seam_words(m, n);
             for (uint32_t r : ro) add(r, q, n, m, dw, sw);
         }
     } else {
@@ -646,7 +679,7 @@ static void build_schedule(const swmi_ctx *ctx, swmi_batch *b) {
             for (uint32_t q : qo) {
                 const uint32_t m = b->read_desc[q].len;
                 if (m == 0) continue;
-                if (m != last_m) { dw = swmi_dir_words(m, n, b->eff_mode, tf); sw = swmi_seam_words(m, n); last_m = m; }
+                if (m != last_m) { dw = swmi_dir_words(m, n, b->eff_mode, tf); sw = seam_words(m, n); last_m = m; }
                 add(r, q, n, m, dw, sw);
             }
         }
@@ -691,13 +724,15 @@ static int rerun_overflowed(RunState &rs, const std::vector<Work> &work, const s
 
 // mat: the score matrix the run uses (the context's when the run was asked for), or null
 // align_mode: the context's when the run was asked for
-static int batch_run(swmi_ctx *ctx, swmi_batch *b, const swmi_params *p, std::shared_ptr<const ScoreMatrix> mat, const int align_mode) {
+// long_reads: likewise
+static int batch_run(swmi_ctx *ctx, swmi_batch *b, const swmi_params *p, std::shared_ptr<const ScoreMatrix> mat, const int align_mode,
+                     const int long_reads) {
     if (!ctx || !b || !p) return fail(SWMI_ERR_INVALID, "null argument");
     std::lock_guard<std::mutex> g(ctx->mu);
     // (a score matrix and the end-to-end modes run on the affine kernels only)
     const bool affine = ctx->affine == 1 || ctx->gap_open != 0 || mat != nullptr || align_mode != SWMI_ALIGN_LOCAL;
     int rc;
-    if ((rc = check_run_params(ctx, b, p, affine, align_mode))) return rc;
+    if ((rc = check_run_params(ctx, b, p, affine, align_mode, mat.get(), long_reads))) return rc;
     static const bool host_dbg = getenv("SWMI_DEBUG_HOST") != nullptr;
     const auto h0 = Clock::now();
     {   // (hipSetDevice costs microseconds even when nothing changes; a sub-millisecond batch notices)
@@ -725,6 +760,7 @@ static int batch_run(swmi_ctx *ctx, swmi_batch *b, const swmi_params *p, std::sh
     b->eff_mode = (ctx->mode == 1 && (p->mismatch > 0 || p->gap > 0)) ? 2u : ctx->mode;
     b->gap_open = ctx->gap_open;
     b->align_mode = align_mode;
+    b->long_reads = long_reads;
     if (affine) b->eff_mode = 3;                         // the affine kernels (swmi_affine.hip): no other pipeline option applies
     b->mat = std::move(mat);
     if (b->mat && b->d_mat_gen != b->mat->gen) {
@@ -792,7 +828,7 @@ static int batch_run(swmi_ctx *ctx, swmi_batch *b, const swmi_params *p, std::sh
 
 extern "C" int swmi_batch_run(swmi_ctx *ctx, swmi_batch *b, const swmi_params *p) {
     if (!ctx || !b || !p) return fail(SWMI_ERR_INVALID, "null argument");
-    return batch_run(ctx, b, p, ctx_matrix(ctx), ctx->align_mode);
+    return batch_run(ctx, b, p, ctx_matrix(ctx), ctx->align_mode, ctx->long_reads);
 }
 
 // ---- asynchronous run: the same swmi_batch_run on the context's own host thread -------------------------------
@@ -811,7 +847,7 @@ static void swmi_worker_loop(swmi_ctx *ctx) {
         }
         if (st == 3) return;
         if (ctx->job_delay_us) std::this_thread::sleep_for(std::chrono::microseconds(ctx->job_delay_us));
-        const int rc = batch_run(ctx, ctx->job_batch, &ctx->job_params, std::move(ctx->job_matrix), ctx->job_align_mode);
+        const int rc = batch_run(ctx, ctx->job_batch, &ctx->job_params, std::move(ctx->job_matrix), ctx->job_align_mode, ctx->job_long_reads);
         ctx->job_rc = rc;
         ctx->job_err = rc ? swmi_last_error() : "";
         { std::lock_guard<std::mutex> lk(ctx->job_mu); ctx->job_state.store(2, std::memory_order_release); }
@@ -828,6 +864,7 @@ extern "C" int swmi_batch_run_async(swmi_ctx *ctx, swmi_batch *b, const swmi_par
     ctx->job_params = *p;
     ctx->job_matrix = ctx_matrix(ctx);                 // (the matrix set now, whatever is set while the run is in flight)
     ctx->job_align_mode = ctx->align_mode;             // (likewise)
+    ctx->job_long_reads = ctx->long_reads;
     ctx->job_delay_us = ctx->dbg_async_delay_us;
     { std::lock_guard<std::mutex> lk(ctx->job_mu); ctx->job_state.store(1, std::memory_order_release); }
     ctx->job_cv.notify_all();

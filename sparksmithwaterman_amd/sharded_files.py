@@ -172,6 +172,8 @@ def _rank_main(args):
             scores = scores[:3]
         if args.align_mode != "local":                      # end-to-end alignment: the streamed scores-only pass and the
             ctx.set_option("align_mode", _ALIGN_MODES[args.align_mode])    # realignment of the winners both run on this context
+        if args.long_reads:                                 # reads longer than 1024 bases on the affine kernels
+            ctx.set_option("long_reads", 1)
         if args.matrix:                                     # substitution scores on this rank's context (NCBI text format)
             from . import matrix as _matrix
             ctx.set_score_matrix(_matrix.load(args.matrix))
@@ -192,11 +194,8 @@ def _rank_main(args):
         dist.destroy_process_group()
 
 
-def main(argv=None):
+def _parser():
     import argparse
-    import socket
-    import subprocess
-    import sys
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--ref-dir", required=True)
     ap.add_argument("--in-dir", required=True)
@@ -215,11 +214,21 @@ def main(argv=None):
                          "against the whole reference.  Totals may then be zero or negative; the reduce keeps the control driver's "
                          "rule (`int max = 0`, ties kept): a reference whose total is negative never wins, and when no total is "
                          "positive the references whose total is exactly 0 tie, as they do today")
+    ap.add_argument("--long-reads", action="store_true",
+                    help="let the affine kernels (gapOpen, --matrix, --align-mode) take reads longer than 1024 bases, swept in strips "
+                         "of 1024 rows (option long_reads); without it such a read is refused")
     ap.add_argument("--tie", choices=("serial", "strict"), default="serial",
                     help="serial: SmithWaterman's aligner (NoDistribution, DistributeReference); strict: DistributedSW's (DistributeAlgorithm)")
     ap.add_argument("--stream-chunk-bytes", type=int, default=512 << 10, help="sequence bytes per streamed chunk")
     ap.add_argument("--stats", default=None, help="per-rank JSON of phase times, cells and records, e.g. O/rank<r>.json ('<r>': the rank)")
-    args = ap.parse_args(argv)
+    return ap
+
+
+def main(argv=None):
+    import socket
+    import subprocess
+    import sys
+    args = _parser().parse_args(argv)
     if "RANK" in os.environ:
         _rank_main(args)
         return 0
