@@ -51,6 +51,12 @@
 //   `begin` follows the moves that consume a reference base.
 // sw_affine_traceback_long[_fit|_global]_kernel: the same walks over the strips' fields: row i is in strip (i - 1) / 1024; a
 //   step up from a strip's first row goes to lane 63, row slot 15 of the strip above; the LDS tile is keyed by the strip too.
+//
+// How the 24 kernels are made: the 18 sweeps are aff_sweep_entry<RLO, RHI, MATRIX, MODE, LONG> over one block function
+//   (aff_block8); the 6 tracebacks are aff_traceback<MODE, LONG>, where !LONG is the walk with one strip.  One macro defines
+//   the sweeps, one the tracebacks; the launchers pick a kernel from a table.  The per-pair sweep is two thin bodies,
+//   aff_sweep_pair and aff_sweep_long_pair, over shared pieces: vrows, the cell list and the epilogue as functions of values,
+//   the row load and the block store as text (DESIGN.md 8e says why).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "swmi_device.h"
@@ -233,6 +239,70 @@ __device__ __forceinline__ void aff_block8(AffState<R> &S, const uint2 rw, const
     }
 }
 
+// The pieces the sweep of a short read and the strip sweep of a long one share.  They take and return values: a helper that
+// is handed a reference to the lane's state changes the register allocation of the sweeps it is inlined into.
+// vrows of a lane whose first row is row0 + 1: LOCAL the number of its rows inside the read; the end-to-end modes track row m
+// alone: its row slot in the lane that owns it, no slot (0xFFFFFFFF) elsewhere
+template <int R, int MODE>
+__device__ __forceinline__ uint32_t aff_vrows(const uint32_t m, const uint32_t row0) {
+    return MODE != AFF_LOCAL ? (m - 1u - row0 < (uint32_t)R ? m - 1u - row0 : 0xFFFFFFFFu)
+                             : row0 >= m ? 0u : (m - row0 < (uint32_t)R ? m - row0 : (uint32_t)R);
+}
+
+// the pair's cell list and its cap (the exact-size lists of a re-run, else cell_cap cells per pair)
+struct AffCells { uint2 *p; uint32_t cap; };
+__device__ __forceinline__ AffCells aff_cell_list(const FillArgs &A, const PairDesc pd) {
+    const uint64_t cbase = A.cells_off ? A.cells_off[pd.out_id] : (uint64_t)pd.out_id * A.cell_cap;
+    const uint32_t ccap = A.cells_cap ? A.cells_cap[pd.out_id] : A.cell_cap;
+    return AffCells{A.cells + cbase, ccap};
+}
+
+template <int MODE>
+__device__ __forceinline__ void aff_pair_out(const FillArgs &A, const PairDesc pd, const uint32_t lane, const int thr, const uint32_t cnt,
+                                             const uint32_t ccap, const uint32_t m, const uint32_t n) {
+    if (lane == 0) {
+        PairOut po;
+        if (MODE == AFF_LOCAL && cnt == 0u) {                    // maximum 0: every one of the m*n cells ties (SmithWaterman.java:154)
+            po.score = 0;
+            po.flags = SWMI_F_DEGENERATE;
+            po.n_cells = (uint64_t)m * n;
+        } else {
+            po.score = thr;
+            po.flags = cnt > ccap ? SWMI_F_CELL_OVF : 0u;
+            po.n_cells = cnt;
+        }
+        A.out[pd.out_id] = po;
+    }
+}
+
+// The two pieces that read or write the lane's state S are shared as TEXT, not as functions.  As an inlined function -- handed
+// S, its arrays, a pointer to them, or one row at a time by value -- either one changes the register allocation of the sweeps
+// (DESIGN.md 8e); the same statements expanded in place cannot.  Both expect R, MATRIX, MODE, S, A, o and the names below.
+// AFF_LOAD_ROWS (readw, m, row0, nn): the lane's rows row0 + 1 .. row0 + R (global row indices) -- their base codes, with MATRIX
+//   their row words class * (n+1) * 4 | hi << 16 (a read base inside the alphabet takes hi = 0x3FF, never a reference key's;
+//   pad rows: class n, hi 0xFFFF) -- and H and E at column 0: 0 (local), else H(i,0) = o + i*e, E(i,0) := H(i,0) + o
+#define AFF_LOAD_ROWS                                                                                         \
+    _Pragma("unroll") for (int k = 0; k < R; ++k) {                                                           \
+        const uint32_t row = row0 + (uint32_t)k;                                                              \
+        S.q[k] = row < m ? (int)((readw[row >> 2] >> (8u * (row & 3u))) & 0xFFu) : (int)SWMI_CODE_PAD;        \
+        if (MATRIX) {                                                                                         \
+            const uint32_t key = row < m ? aff_mkey[S.q[k]] : ((nn - 1u) * 4u) | (0xFFFFu << 16);             \
+            const uint32_t hi = (key >> 16) == 0x1FFu ? 0x3FFu : key >> 16;                                   \
+            S.q[k] = (int)(((key & 0xFFFFu) * nn) | (hi << 16));                                              \
+        }                                                                                                     \
+        if constexpr (MODE == AFF_LOCAL) {                                                                    \
+            S.h[k] = 0;                                                                                       \
+            S.e[k] = 0;                                                                                       \
+        } else {                                                                                              \
+            S.h[k] = o + (int)(row + 1u) * A.gap;                                                             \
+            S.e[k] = S.h[k] + o;                                                                              \
+        }                                                                                                     \
+    }
+// AFF_STORE_BLOCK (dir, w, lane): block w of a field, the codes of the lane's R rows, 256 contiguous bytes per row slot
+#define AFF_STORE_BLOCK                                                                                       \
+    uint32_t *__restrict__ dst = dir + (uint64_t)w * R * WAVE + lane;                                         \
+    _Pragma("unroll") for (int k = 0; k < R; ++k) dst[k * WAVE] = S.acc[k];
+
 template <int R, bool STRICT, bool MATRIX, int MODE>
 __device__ __forceinline__ void aff_sweep_pair(const FillArgs &A, const int o, const PairDesc pd, const uint32_t lane, const uint32_t nn) {
     const SeqDesc rd = A.refs[pd.ref_id];
@@ -243,32 +313,13 @@ __device__ __forceinline__ void aff_sweep_pair(const FillArgs &A, const int o, c
     uint32_t *__restrict__ dir = A.dir + pd.dir_off;
     const uint32_t W = swmi_aff_blocks(m, n);
     const uint32_t row0 = lane * R;
-    // (the end-to-end modes track row m alone: its row slot in the lane that owns it, no slot elsewhere)
-    const uint32_t vrows = MODE != AFF_LOCAL ? (m - 1u - row0 < (uint32_t)R ? m - 1u - row0 : 0xFFFFFFFFu)
-                         : row0 >= m ? 0u : (m - row0 < (uint32_t)R ? m - row0 : (uint32_t)R);
-    const uint64_t cbase = A.cells_off ? A.cells_off[pd.out_id] : (uint64_t)pd.out_id * A.cell_cap;
-    const uint32_t ccap = A.cells_cap ? A.cells_cap[pd.out_id] : A.cell_cap;
-    uint2 *__restrict__ cells = A.cells + cbase;
+    const uint32_t vrows = aff_vrows<R, MODE>(m, row0);
+    const AffCells cl = aff_cell_list(A, pd);
+    const uint32_t ccap = cl.cap;
+    uint2 *__restrict__ cells = cl.p;
 
     AffState<R> S;
-#pragma unroll
-    for (int k = 0; k < R; ++k) {
-        const uint32_t row = row0 + (uint32_t)k;
-        S.q[k] = row < m ? (int)((readw[row >> 2] >> (8u * (row & 3u))) & 0xFFu) : (int)SWMI_CODE_PAD;
-        if (MATRIX) {                                            // row word: class * (n+1) * 4 | hi << 16
-            // (a read base inside the alphabet takes hi = 0x3FF, never a reference key's; pad rows: class n, hi 0xFFFF)
-            const uint32_t key = row < m ? aff_mkey[S.q[k]] : ((nn - 1u) * 4u) | (0xFFFFu << 16);
-            const uint32_t hi = (key >> 16) == 0x1FFu ? 0x3FFu : key >> 16;
-            S.q[k] = (int)(((key & 0xFFFFu) * nn) | (hi << 16));
-        }
-        if constexpr (MODE == AFF_LOCAL) {
-            S.h[k] = 0;
-            S.e[k] = 0;
-        } else {                                                 // column 0: H(i,0) = o + i*e, E(i,0) := H(i,0) + o
-            S.h[k] = o + (int)(row + 1u) * A.gap;
-            S.e[k] = S.h[k] + o;
-        }
-    }
+    AFF_LOAD_ROWS
     S.rb = 0; S.nh_prev = 0; S.f_last = 0;                       // (nh_prev of lane 0: H(0,0) = 0 in every mode)
     S.thr = MODE == AFF_LOCAL ? 1 : INT32_MIN; S.cnt = 0;
     for (uint32_t w = 0; w < W; ++w) {
@@ -278,26 +329,12 @@ __device__ __forceinline__ void aff_sweep_pair(const FillArgs &A, const int o, c
 #pragma unroll
         for (int k = 0; k < R; ++k) S.acc[k] = 0u;
         aff_block8<R, STRICT, MATRIX, MODE>(S, rw, t0, lane, n, row0, vrows, o, A.gap, A.match, A.mismatch, cells, ccap);
-        uint32_t *__restrict__ dst = dir + (uint64_t)w * R * WAVE + lane;
-#pragma unroll
-        for (int k = 0; k < R; ++k) dst[k * WAVE] = S.acc[k];
+        AFF_STORE_BLOCK
     }
-    if (lane == 0) {
-        PairOut po;
-        if (MODE == AFF_LOCAL && S.cnt == 0u) {                                       // maximum 0: every one of the m*n cells ties (SmithWaterman.java:154)
-            po.score = 0;
-            po.flags = SWMI_F_DEGENERATE;
-            po.n_cells = (uint64_t)m * n;
-        } else {
-            po.score = S.thr;
-            po.flags = S.cnt > ccap ? SWMI_F_CELL_OVF : 0u;
-            po.n_cells = S.cnt;
-        }
-        A.out[pd.out_id] = po;
-    }
+    aff_pair_out<MODE>(A, pd, lane, S.thr, S.cnt, ccap, m, n);
 }
 
-// A read of more than 1024 bases, strip after strip (R = 16 in every strip).
+// A read of more than 1024 bases, strip after strip (R = 16 in every strip), over the same pieces as aff_sweep_pair.
 // The seam row is rewritten IN PLACE.  In a strip, lane 0 is at column t + 1 at step t and its block of 8 columns is loaded at
 // the block's first step, so a load at step t touches columns >= t + 1; lane 63 is at column t - 62 at step t.  A column is
 // therefore read (by this strip) at least 63 steps before this strip overwrites it, and what it reads was written by the strip
@@ -312,9 +349,9 @@ __device__ __forceinline__ void aff_sweep_long_pair(const FillArgs &A, const int
     const uint32_t *__restrict__ refw = A.seqw + rd.boff;
     const uint32_t *__restrict__ readw = A.seqw + qd.boff;
     const uint32_t NS = swmi_aff_strips(m), W = swmi_aff_strip_blocks(n);
-    const uint64_t cbase = A.cells_off ? A.cells_off[pd.out_id] : (uint64_t)pd.out_id * A.cell_cap;
-    const uint32_t ccap = A.cells_cap ? A.cells_cap[pd.out_id] : A.cell_cap;
-    uint2 *__restrict__ cells = A.cells + cbase;
+    const AffCells cl = aff_cell_list(A, pd);
+    const uint32_t ccap = cl.cap;
+    uint2 *__restrict__ cells = cl.p;
     AffSeam Z;
     Z.row = reinterpret_cast<int2 *>(A.seam + pd.seam_off);
 
@@ -322,26 +359,8 @@ __device__ __forceinline__ void aff_sweep_long_pair(const FillArgs &A, const int
     S.thr = MODE == AFF_LOCAL ? 1 : INT32_MIN; S.cnt = 0;       // (wave-uniform: they live on across the strips)
     for (uint32_t sx = 0; sx < NS; ++sx) {
         const uint32_t row0 = sx * SWMI_AFF_MAX_READ + lane * R;             // global index of the lane's first row, less 1
-        // (the end-to-end modes track row m alone, which is in the last strip)
-        const uint32_t vrows = MODE != AFF_LOCAL ? (m - 1u - row0 < (uint32_t)R ? m - 1u - row0 : 0xFFFFFFFFu)
-                             : row0 >= m ? 0u : (m - row0 < (uint32_t)R ? m - row0 : (uint32_t)R);
-#pragma unroll
-        for (int k = 0; k < R; ++k) {
-            const uint32_t row = row0 + (uint32_t)k;
-            S.q[k] = row < m ? (int)((readw[row >> 2] >> (8u * (row & 3u))) & 0xFFu) : (int)SWMI_CODE_PAD;
-            if (MATRIX) {                                        // (as in aff_sweep_pair)
-                const uint32_t key = row < m ? aff_mkey[S.q[k]] : ((nn - 1u) * 4u) | (0xFFFFu << 16);
-                const uint32_t hi = (key >> 16) == 0x1FFu ? 0x3FFu : key >> 16;
-                S.q[k] = (int)(((key & 0xFFFFu) * nn) | (hi << 16));
-            }
-            if constexpr (MODE == AFF_LOCAL) {
-                S.h[k] = 0;
-                S.e[k] = 0;
-            } else {                                             // column 0, global row index
-                S.h[k] = o + (int)(row + 1u) * A.gap;
-                S.e[k] = S.h[k] + o;
-            }
-        }
+        const uint32_t vrows = aff_vrows<R, MODE>(m, row0);               // (row m is in the last strip)
+        AFF_LOAD_ROWS
         S.rb = 0; S.f_last = 0;
         // nh_prev of lane 0: H(1024 * sx, 0)
         S.nh_prev = MODE != AFF_LOCAL && sx ? o + (int)(sx * SWMI_AFF_MAX_READ) * A.gap : 0;
@@ -365,25 +384,14 @@ __device__ __forceinline__ void aff_sweep_long_pair(const FillArgs &A, const int
 #pragma unroll
             for (int k = 0; k < R; ++k) S.acc[k] = 0u;
             aff_block8<R, STRICT, MATRIX, MODE, true>(S, rw, t0, lane, n, row0, vrows, o, A.gap, A.match, A.mismatch, cells, ccap, Z);
-            uint32_t *__restrict__ dst = dir + (uint64_t)w * R * WAVE + lane;
-#pragma unroll
-            for (int k = 0; k < R; ++k) dst[k * WAVE] = S.acc[k];
+            AFF_STORE_BLOCK
         }
     }
-    if (lane == 0) {
-        PairOut po;
-        if (MODE == AFF_LOCAL && S.cnt == 0u) {
-            po.score = 0;
-            po.flags = SWMI_F_DEGENERATE;
-            po.n_cells = (uint64_t)m * n;
-        } else {
-            po.score = S.thr;
-            po.flags = S.cnt > ccap ? SWMI_F_CELL_OVF : 0u;
-            po.n_cells = S.cnt;
-        }
-        A.out[pd.out_id] = po;
-    }
+    aff_pair_out<MODE>(A, pd, lane, S.thr, S.cnt, ccap, m, n);
 }
+
+#undef AFF_LOAD_ROWS
+#undef AFF_STORE_BLOCK
 
 // RLO..RHI: the rows per lane this instantiation of the kernel takes (the others' registers would cap its occupancy)
 template <int RLO, int RHI, bool STRICT, bool MATRIX, int MODE>
@@ -427,59 +435,48 @@ __device__ __forceinline__ void aff_sweep_entry(const FillArgs &A, const int o, 
 
 }  // namespace
 
-extern "C" __global__ void __launch_bounds__(WAVE * AFF_WAVES) sw_affine_sweep_kernel(const FillArgs A, const int gap_open) {
-    aff_sweep_entry<1, 4, false>(A, gap_open, nullptr, 0u);
-}
-extern "C" __global__ void __launch_bounds__(WAVE * AFF_WAVES) sw_affine_sweep_wide_kernel(const FillArgs A, const int gap_open) {
-    aff_sweep_entry<5, SWMI_AFF_RMAX, false>(A, gap_open, nullptr, 0u);
-}
-extern "C" __global__ void __launch_bounds__(WAVE * AFF_WAVES) sw_affine_sweep_matrix_kernel(const FillArgs A, const int gap_open,
-                                                                                            const uint32_t *mat, const uint32_t nn) {
-    aff_sweep_entry<1, 4, true>(A, gap_open, mat, nn);
-}
-extern "C" __global__ void __launch_bounds__(WAVE * AFF_WAVES) sw_affine_sweep_matrix_wide_kernel(const FillArgs A, const int gap_open,
-                                                                                                 const uint32_t *mat, const uint32_t nn) {
-    aff_sweep_entry<5, SWMI_AFF_RMAX, true>(A, gap_open, mat, nn);
-}
-// the end-to-end modes (option "align_mode"): fit and global, plain and matrix, narrow and wide
-#define AFF_ENDS_KERNELS(name, MODE)                                                                                                  \
-    extern "C" __global__ void __launch_bounds__(WAVE * AFF_WAVES) sw_affine_sweep_##name##_kernel(const FillArgs A, const int gap_open) { \
-        aff_sweep_entry<1, 4, false, MODE>(A, gap_open, nullptr, 0u);                                                                \
-    }                                                                                                                                 \
-    extern "C" __global__ void __launch_bounds__(WAVE * AFF_WAVES) sw_affine_sweep_##name##_wide_kernel(const FillArgs A, const int gap_open) { \
-        aff_sweep_entry<5, SWMI_AFF_RMAX, false, MODE>(A, gap_open, nullptr, 0u);                                                    \
-    }                                                                                                                                 \
-    extern "C" __global__ void __launch_bounds__(WAVE * AFF_WAVES) sw_affine_sweep_##name##_matrix_kernel(                            \
-        const FillArgs A, const int gap_open, const uint32_t *mat, const uint32_t nn) {                                               \
-        aff_sweep_entry<1, 4, true, MODE>(A, gap_open, mat, nn);                                                                      \
-    }                                                                                                                                 \
-    extern "C" __global__ void __launch_bounds__(WAVE * AFF_WAVES) sw_affine_sweep_##name##_matrix_wide_kernel(                       \
-        const FillArgs A, const int gap_open, const uint32_t *mat, const uint32_t nn) {                                               \
-        aff_sweep_entry<5, SWMI_AFF_RMAX, true, MODE>(A, gap_open, mat, nn);                                                          \
+// The 18 sweep kernels: local, fit and global (option "align_mode"), each plain and with a score matrix (MATRIX = 0 / 1: the
+// two signatures), each narrow (R = 1..4), wide (R = 5..16) and long (option "long_reads": RLO, RHI unused).
+#define AFF_SWEEP_PARAMS_0 const FillArgs A, const int gap_open
+#define AFF_SWEEP_PARAMS_1 const FillArgs A, const int gap_open, const uint32_t *mat, const uint32_t nn
+#define AFF_SWEEP_ARGS_0 A, gap_open, nullptr, 0u
+#define AFF_SWEEP_ARGS_1 A, gap_open, mat, nn
+#define AFF_SWEEP_KERNEL(name, RLO, RHI, MATRIX, MODE, LONG)                                               \
+    extern "C" __global__ void __launch_bounds__(WAVE * AFF_WAVES) name(AFF_SWEEP_PARAMS_##MATRIX) {      \
+        aff_sweep_entry<RLO, RHI, MATRIX != 0, MODE, LONG>(AFF_SWEEP_ARGS_##MATRIX);                       \
     }
-AFF_ENDS_KERNELS(fit, AFF_FIT)
-AFF_ENDS_KERNELS(global, AFF_GLOBAL)
-#undef AFF_ENDS_KERNELS
-// reads longer than 1024 bases (option "long_reads"): one kernel per mode, plain and matrix
-#define AFF_LONG_KERNELS(name, MODE)                                                                                                  \
-    extern "C" __global__ void __launch_bounds__(WAVE * AFF_WAVES) sw_affine_sweep_##name##_kernel(const FillArgs A, const int gap_open) { \
-        aff_sweep_entry<SWMI_AFF_RMAX, SWMI_AFF_RMAX, false, MODE, true>(A, gap_open, nullptr, 0u);                                  \
-    }                                                                                                                                 \
-    extern "C" __global__ void __launch_bounds__(WAVE * AFF_WAVES) sw_affine_sweep_##name##_matrix_kernel(                            \
-        const FillArgs A, const int gap_open, const uint32_t *mat, const uint32_t nn) {                                               \
-        aff_sweep_entry<SWMI_AFF_RMAX, SWMI_AFF_RMAX, true, MODE, true>(A, gap_open, mat, nn);                                       \
-    }
-AFF_LONG_KERNELS(long, AFF_LOCAL)
-AFF_LONG_KERNELS(long_fit, AFF_FIT)
-AFF_LONG_KERNELS(long_global, AFF_GLOBAL)
-#undef AFF_LONG_KERNELS
+AFF_SWEEP_KERNEL(sw_affine_sweep_kernel, 1, 4, 0, AFF_LOCAL, false)
+AFF_SWEEP_KERNEL(sw_affine_sweep_wide_kernel, 5, SWMI_AFF_RMAX, 0, AFF_LOCAL, false)
+AFF_SWEEP_KERNEL(sw_affine_sweep_long_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, AFF_LOCAL, true)
+AFF_SWEEP_KERNEL(sw_affine_sweep_matrix_kernel, 1, 4, 1, AFF_LOCAL, false)
+AFF_SWEEP_KERNEL(sw_affine_sweep_matrix_wide_kernel, 5, SWMI_AFF_RMAX, 1, AFF_LOCAL, false)
+AFF_SWEEP_KERNEL(sw_affine_sweep_long_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, AFF_LOCAL, true)
+AFF_SWEEP_KERNEL(sw_affine_sweep_fit_kernel, 1, 4, 0, AFF_FIT, false)
+AFF_SWEEP_KERNEL(sw_affine_sweep_fit_wide_kernel, 5, SWMI_AFF_RMAX, 0, AFF_FIT, false)
+AFF_SWEEP_KERNEL(sw_affine_sweep_long_fit_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, AFF_FIT, true)
+AFF_SWEEP_KERNEL(sw_affine_sweep_fit_matrix_kernel, 1, 4, 1, AFF_FIT, false)
+AFF_SWEEP_KERNEL(sw_affine_sweep_fit_matrix_wide_kernel, 5, SWMI_AFF_RMAX, 1, AFF_FIT, false)
+AFF_SWEEP_KERNEL(sw_affine_sweep_long_fit_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, AFF_FIT, true)
+AFF_SWEEP_KERNEL(sw_affine_sweep_global_kernel, 1, 4, 0, AFF_GLOBAL, false)
+AFF_SWEEP_KERNEL(sw_affine_sweep_global_wide_kernel, 5, SWMI_AFF_RMAX, 0, AFF_GLOBAL, false)
+AFF_SWEEP_KERNEL(sw_affine_sweep_long_global_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, AFF_GLOBAL, true)
+AFF_SWEEP_KERNEL(sw_affine_sweep_global_matrix_kernel, 1, 4, 1, AFF_GLOBAL, false)
+AFF_SWEEP_KERNEL(sw_affine_sweep_global_matrix_wide_kernel, 5, SWMI_AFF_RMAX, 1, AFF_GLOBAL, false)
+AFF_SWEEP_KERNEL(sw_affine_sweep_long_global_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, AFF_GLOBAL, true)
+#undef AFF_SWEEP_KERNEL
+#undef AFF_SWEEP_PARAMS_0
+#undef AFF_SWEEP_PARAMS_1
+#undef AFF_SWEEP_ARGS_0
+#undef AFF_SWEEP_ARGS_1
 
 // ------------------------------------------------------------------------------------------------
 // traceback
 // ------------------------------------------------------------------------------------------------
 // LDS of one wavefront: [tile_words] direction tile | [ops_words] ops, 16 per dword | [SWMI_EMIT_SCRATCH_WORDS] string scratch
+// LONG: the pairs of the strip sweeps (reads longer than 1024 bases): R = 16, the field of strip sx at sx * swmi_aff_strip_words(n).
+// !LONG: one strip -- sx and tsx stay 0 and fold away.
 namespace {
-template <int MODE>
+template <int MODE, bool LONG>
 __device__ __forceinline__ void aff_traceback(const TraceArgs A, const uint32_t tile_words, const uint32_t ops_words) {
     extern __shared__ uint32_t lds[];
     const uint32_t lane = threadIdx.x;
@@ -495,8 +492,8 @@ __device__ __forceinline__ void aff_traceback(const TraceArgs A, const uint32_t 
     const SeqDesc rd = A.refs[pd.ref_id];
     const SeqDesc qd = A.reads[pd.read_id];
     const uint32_t n = rd.len, m = qd.len;
-    const uint32_t R = uni(swmi_aff_rows_per_lane(m));
-    const uint32_t W = uni(swmi_aff_blocks(m, n));
+    const uint32_t R = LONG ? SWMI_AFF_RMAX : uni(swmi_aff_rows_per_lane(m));
+    const uint32_t W = uni(LONG ? swmi_aff_strip_blocks(n) : swmi_aff_blocks(m, n));
     const uint32_t blk_words = R * WAVE;                          // dwords of one 8-step block
     const uint32_t NB = tile_words / blk_words;                   // blocks per tile (>= 1: the host sizes the tile)
     const uint32_t max_ops = ops_words * 16u;
@@ -507,130 +504,15 @@ __device__ __forceinline__ void aff_traceback(const TraceArgs A, const uint32_t 
     const uint2 *__restrict__ cells = A.cells + cbase;
     const uint32_t ncell = (uint32_t)po.n_cells;
     uint32_t wlo = 0xFFFFFFFFu, whi = 0u;                         // blocks [wlo, whi) are in the tile
-
-    for (uint32_t c = slot; c < ncell; c += nslots) {
-        const uint32_t ci = uni(cells[c].x), cj = uni(cells[c].y);
-        uint32_t i = ci, j = cj;
-        uint32_t l = (i - 1u) / R, k = (i - 1u) - l * R;          // lane and row slot of row i
-        uint32_t st = 0u;                                         // 0: H, else the state entered (AFF_DIAG / AFF_INS / AFF_DEL)
-        uint32_t n_ops = 0, cur = 0;
-        int begin = MODE == AFF_LOCAL ? 0 : (int)cj;
-        bool ok = true;
-        while (MODE == AFF_LOCAL ? (i != 0u && j != 0u) : (i != 0u)) {
-            if (MODE != AFF_LOCAL && j == 0u) {                   // the read's head hangs over the reference start: inserted,
-                if (n_ops >= max_ops) { ok = false; break; }      // and the field is not touched
-                --i;
-                cur |= SWMI_DIR_I << (2u * (n_ops & 15u));
-                ++n_ops;
-                if ((n_ops & 15u) == 0u) { if (lane == 0) ops[(n_ops >> 4) - 1u] = cur; cur = 0u; }
-                continue;
-            }
-            const uint32_t t = j - 1u + l, w = t >> 3;
-            if (w < wlo || w >= whi) {                            // stage the tile that ends at this block
-                if (w >= W) { ok = false; break; }                // (a corrupted list: never walks off the field)
-                WAVE_SYNC();
-                wlo = w + 1u >= NB ? w + 1u - NB : 0u;
-                whi = w + 1u;
-                const uint32_t *__restrict__ src = dir + (uint64_t)wlo * blk_words;
-                const uint32_t words = (whi - wlo) * blk_words;
-                for (uint32_t x = lane; x < words; x += WAVE) tile[x] = src[x];
-                WAVE_SYNC();
-            }
-            const uint32_t code = uni((tile[((w - wlo) * R + k) * WAVE + l] >> (4u * (t & 7u))) & 15u);
-            if (st == 0u) {
-                st = code & 3u;
-                if (MODE == AFF_LOCAL) { if (st == AFF_STOP) break; }   // H(i, j) == 0: `while (score > 0)` (SmithWaterman.java:380)
-                else if (st == AFF_STOP) { ok = false; break; }         // (these sweeps write no code 0: a corrupted field)
-            }
-            if (n_ops >= max_ops) { ok = false; break; }
-            if (MODE == AFF_LOCAL || st != AFF_INS) begin = (int)j;     // (end-to-end: the moves that consume a reference base)
-            uint32_t op;
-            if (st == AFF_DIAG) {
-                op = SWMI_DIR_A;
-                st = 0u;
-                --i; --j;
-            } else if (st == AFF_INS) {
-                op = SWMI_DIR_I;
-                st = (code & 8u) ? AFF_INS : 0u;
-                --i;
-            } else {
-                op = SWMI_DIR_D;
-                st = (code & 4u) ? AFF_DEL : 0u;
-                --j;
-            }
-            if (op != SWMI_DIR_D) { if (k == 0u) { k = R - 1u; --l; } else --k; }
-            cur |= op << (2u * (n_ops & 15u));
-            ++n_ops;
-            if ((n_ops & 15u) == 0u) { if (lane == 0) ops[(n_ops >> 4) - 1u] = cur; cur = 0u; }
-        }
-        if (MODE == AFF_GLOBAL) {                                 // row 0: the rest of the reference is deleted
-            while (ok && j != 0u) {
-                if (n_ops >= max_ops) { ok = false; break; }
-                begin = (int)j;
-                --j;
-                cur |= SWMI_DIR_D << (2u * (n_ops & 15u));
-                ++n_ops;
-                if ((n_ops & 15u) == 0u) { if (lane == 0) ops[(n_ops >> 4) - 1u] = cur; cur = 0u; }
-            }
-        }
-        if ((n_ops & 15u) != 0u && lane == 0) ops[n_ops >> 4] = cur;
-        WAVE_SYNC();
-        const bool strings = A.raw != nullptr;
-        const uint32_t words = swmi_payload_words(n_ops, strings);
-        unsigned long long off;
-        uint32_t rslot;
-        if (ok && swmi_reserve(A, lane, words, 1u, off, rslot)) {
-            uint32_t *dst = A.arena + off;
-            if (lane == 0) swmi_write_rec(A, rslot, pd.out_id, SWMI_RANK_BY_CELL, begin, ci, cj, n_ops, off);
-            if (strings) swmi_emit_strings(dst, SwmiOpsPacked{ops}, n_ops, ci, cj, raw_ref, raw_read, lane, scratch);
-            else for (uint32_t x = lane; x < words; x += WAVE) dst[x] = ops[x];
-        } else if (lane == 0) {
-            atomicOr(&A.out[pd.out_id].flags, SWMI_F_ARENA_OVF);
-            if (A.ovf_host) *A.ovf_host = 1u;
-        }
-        WAVE_SYNC();
-    }
-}
-
-// aff_traceback for the pairs of the strip sweeps (reads longer than 1024 bases): R = 16, the field of strip sx at
-// sx * swmi_aff_strip_words(n).  A sibling, not a parameter: the walk above keeps its code.
-template <int MODE>
-__device__ __forceinline__ void aff_traceback_long(const TraceArgs A, const uint32_t tile_words, const uint32_t ops_words) {
-    extern __shared__ uint32_t lds[];
-    const uint32_t lane = threadIdx.x;
-    const uint32_t slot = blockIdx.y, nslots = gridDim.y;
-    const PairDesc pd = A.pairs[blockIdx.x];
-    const PairOut po = A.out[pd.out_id];
-    if (A.out_host && slot == 0 && lane == 0) A.out_host[pd.out_id] = po;      // result straight into pinned host memory
-    if (po.flags & (SWMI_F_DEGENERATE | SWMI_F_CELL_OVF)) return;
-    if (po.n_cells <= slot) return;
-    uint32_t *tile = lds;
-    uint32_t *ops = lds + tile_words;
-    uint32_t *scratch = ops + ops_words;
-    const SeqDesc rd = A.refs[pd.ref_id];
-    const SeqDesc qd = A.reads[pd.read_id];
-    const uint32_t n = rd.len, m = qd.len;
-    const uint32_t R = SWMI_AFF_RMAX;
-    const uint32_t W = uni(swmi_aff_strip_blocks(n));
-    const uint32_t blk_words = R * WAVE;                          // dwords of one 8-step block
-    const uint32_t NB = tile_words / blk_words;                   // blocks per tile (>= 1: the host sizes the tile)
-    const uint32_t max_ops = ops_words * 16u;
-    const uint32_t *__restrict__ dir = A.dir + pd.dir_off;
-    const uint8_t *__restrict__ raw_ref = A.raw ? A.raw + A.raw_off[pd.ref_id] : nullptr;
-    const uint8_t *__restrict__ raw_read = A.raw ? A.raw + A.raw_off[A.raw_reads_at + pd.read_id] : nullptr;
-    const uint64_t cbase = A.cells_off ? A.cells_off[pd.out_id] : (uint64_t)pd.out_id * A.cell_cap;
-    const uint2 *__restrict__ cells = A.cells + cbase;
-    const uint32_t ncell = (uint32_t)po.n_cells;
-    uint32_t wlo = 0xFFFFFFFFu, whi = 0u;                         // blocks [wlo, whi) are in the tile
-    uint32_t tsx = 0xFFFFFFFFu;                                   // ... of this strip
-    const uint32_t NS = uni(swmi_aff_strips(m));
+    uint32_t tsx = LONG ? 0xFFFFFFFFu : 0u;                       // ... of this strip
+    const uint32_t NS = LONG ? uni(swmi_aff_strips(m)) : 1u;
 
     for (uint32_t c = slot; c < ncell; c += nslots) {
         const uint32_t ci = uni(cells[c].x), cj = uni(cells[c].y);
         uint32_t i = ci, j = cj;
         uint32_t l = (i - 1u) / R, k = (i - 1u) - l * R;          // (global) lane and row slot of row i
-        uint32_t sx = l / WAVE;                                   // its strip, and the lane within it
-        l -= sx * WAVE;
+        uint32_t sx = 0u;                                         // its strip, and the lane within it
+        if constexpr (LONG) { sx = l / WAVE; l -= sx * WAVE; }
         uint32_t st = 0u;                                         // 0: H, else the state entered (AFF_DIAG / AFF_INS / AFF_DEL)
         uint32_t n_ops = 0, cur = 0;
         int begin = MODE == AFF_LOCAL ? 0 : (int)cj;
@@ -645,13 +527,13 @@ __device__ __forceinline__ void aff_traceback_long(const TraceArgs A, const uint
                 continue;
             }
             const uint32_t t = j - 1u + l, w = t >> 3;
-            if (w < wlo || w >= whi || sx != tsx) {             // stage the tile that ends at this block
-                if (w >= W || sx >= NS) { ok = false; break; }    // (a corrupted list: never walks off the field)
+            if (w < wlo || w >= whi || (LONG && sx != tsx)) {     // stage the tile that ends at this block
+                if (w >= W || (LONG && sx >= NS)) { ok = false; break; }    // (a corrupted list: never walks off the field)
                 WAVE_SYNC();
                 wlo = w + 1u >= NB ? w + 1u - NB : 0u;
                 whi = w + 1u;
-                tsx = sx;
-                const uint32_t *__restrict__ src = dir + (uint64_t)sx * swmi_aff_strip_words(n) + (uint64_t)wlo * blk_words;
+                if constexpr (LONG) tsx = sx;
+                const uint32_t *__restrict__ src = dir + (LONG ? (uint64_t)sx * swmi_aff_strip_words(n) : 0ull) + (uint64_t)wlo * blk_words;
                 const uint32_t words = (whi - wlo) * blk_words;
                 for (uint32_t x = lane; x < words; x += WAVE) tile[x] = src[x];
                 WAVE_SYNC();
@@ -680,7 +562,7 @@ __device__ __forceinline__ void aff_traceback_long(const TraceArgs A, const uint
             }
             if (op != SWMI_DIR_D) {
                 if (k != 0u) --k;
-                else if (l != 0u) { k = R - 1u; --l; }
+                else if (!LONG || l != 0u) { k = R - 1u; --l; }
                 else { k = R - 1u; l = WAVE - 1u; --sx; }         // up from a strip's first row: the last row of the strip above
             }
             cur |= op << (2u * (n_ops & 15u));
@@ -717,78 +599,48 @@ __device__ __forceinline__ void aff_traceback_long(const TraceArgs A, const uint
 }
 }  // namespace
 
-extern "C" __global__ void __launch_bounds__(WAVE) sw_affine_traceback_kernel(const TraceArgs A, const uint32_t tile_words,
-                                                                               const uint32_t ops_words) {
-    aff_traceback<AFF_LOCAL>(A, tile_words, ops_words);
-}
-extern "C" __global__ void __launch_bounds__(WAVE) sw_affine_traceback_fit_kernel(const TraceArgs A, const uint32_t tile_words,
-                                                                                   const uint32_t ops_words) {
-    aff_traceback<AFF_FIT>(A, tile_words, ops_words);
-}
-extern "C" __global__ void __launch_bounds__(WAVE) sw_affine_traceback_global_kernel(const TraceArgs A, const uint32_t tile_words,
-                                                                                      const uint32_t ops_words) {
-    aff_traceback<AFF_GLOBAL>(A, tile_words, ops_words);
-}
-extern "C" __global__ void __launch_bounds__(WAVE) sw_affine_traceback_long_kernel(const TraceArgs A, const uint32_t tile_words,
-                                                                                    const uint32_t ops_words) {
-    aff_traceback_long<AFF_LOCAL>(A, tile_words, ops_words);
-}
-extern "C" __global__ void __launch_bounds__(WAVE) sw_affine_traceback_long_fit_kernel(const TraceArgs A, const uint32_t tile_words,
-                                                                                        const uint32_t ops_words) {
-    aff_traceback_long<AFF_FIT>(A, tile_words, ops_words);
-}
-extern "C" __global__ void __launch_bounds__(WAVE) sw_affine_traceback_long_global_kernel(const TraceArgs A, const uint32_t tile_words,
-                                                                                           const uint32_t ops_words) {
-    aff_traceback_long<AFF_GLOBAL>(A, tile_words, ops_words);
-}
+#define AFF_TRACEBACK_KERNEL(name, MODE, LONG)                                                                                    \
+    extern "C" __global__ void __launch_bounds__(WAVE) name(const TraceArgs A, const uint32_t tile_words, const uint32_t ops_words) { \
+        aff_traceback<MODE, LONG>(A, tile_words, ops_words);                                                                       \
+    }
+AFF_TRACEBACK_KERNEL(sw_affine_traceback_kernel, AFF_LOCAL, false)
+AFF_TRACEBACK_KERNEL(sw_affine_traceback_fit_kernel, AFF_FIT, false)
+AFF_TRACEBACK_KERNEL(sw_affine_traceback_global_kernel, AFF_GLOBAL, false)
+AFF_TRACEBACK_KERNEL(sw_affine_traceback_long_kernel, AFF_LOCAL, true)
+AFF_TRACEBACK_KERNEL(sw_affine_traceback_long_fit_kernel, AFF_FIT, true)
+AFF_TRACEBACK_KERNEL(sw_affine_traceback_long_global_kernel, AFF_GLOBAL, true)
+#undef AFF_TRACEBACK_KERNEL
 
 // ------------------------------------------------------------------------------------------------
 // host-callable launchers
 // ------------------------------------------------------------------------------------------------
-// r_min / r_max: the rows per lane of the launch's shortest and longest read (only the kernels that have pairs are launched)
 // align_mode: 0 local, 1 fit, 2 global (option "align_mode")
-extern "C" hipError_t swmi_launch_affine_sweep(const FillArgs *a, int32_t gap_open, uint32_t align_mode, uint32_t r_min, uint32_t r_max,
-                                               hipStream_t st) {
-    if (a->n_pairs == 0) return hipSuccess;
-    if (align_mode > 2u) return hipErrorInvalidValue;
-    const dim3 grid((a->n_pairs + AFF_WAVES - 1) / AFF_WAVES), block(WAVE * AFF_WAVES);
-    auto *const narrow = align_mode == 0u ? sw_affine_sweep_kernel : align_mode == 1u ? sw_affine_sweep_fit_kernel : sw_affine_sweep_global_kernel;
-    auto *const wide = align_mode == 0u ? sw_affine_sweep_wide_kernel
-                                        : align_mode == 1u ? sw_affine_sweep_fit_wide_kernel : sw_affine_sweep_global_wide_kernel;
-    if (r_min <= 4u) hipLaunchKernelGGL(narrow, grid, block, 0, st, *a, (int)gap_open);
-    if (r_max >= 5u) hipLaunchKernelGGL(wide, grid, block, 0, st, *a, (int)gap_open);
-    return hipGetLastError();
-}
-
-// the matrix sweeps: mat = the device image of the score matrix (swmi_aff_mat_words dwords), nn = its side n + 1 (2 .. 65)
-extern "C" hipError_t swmi_launch_affine_sweep_matrix(const FillArgs *a, int32_t gap_open, uint32_t align_mode, const uint32_t *mat, uint32_t nn,
-                                                      uint32_t r_min, uint32_t r_max, hipStream_t st) {
-    if (a->n_pairs == 0) return hipSuccess;
-    if (nn < 2u || nn > SWMI_MAT_NN_MAX || align_mode > 2u) return hipErrorInvalidValue;
-    const dim3 grid((a->n_pairs + AFF_WAVES - 1) / AFF_WAVES), block(WAVE * AFF_WAVES);
-    auto *const narrow = align_mode == 0u ? sw_affine_sweep_matrix_kernel
-                                          : align_mode == 1u ? sw_affine_sweep_fit_matrix_kernel : sw_affine_sweep_global_matrix_kernel;
-    auto *const wide = align_mode == 0u ? sw_affine_sweep_matrix_wide_kernel
-                                        : align_mode == 1u ? sw_affine_sweep_fit_matrix_wide_kernel : sw_affine_sweep_global_matrix_wide_kernel;
-    if (r_min <= 4u) hipLaunchKernelGGL(narrow, grid, block, 0, st, *a, (int)gap_open, mat, nn);
-    if (r_max >= 5u) hipLaunchKernelGGL(wide, grid, block, 0, st, *a, (int)gap_open, mat, nn);
-    return hipGetLastError();
-}
-
-// the strip sweeps of reads longer than 1024 bases (option "long_reads"); mat: the score matrix image and nn its side, or null
-extern "C" hipError_t swmi_launch_affine_sweep_long(const FillArgs *a, int32_t gap_open, uint32_t align_mode, const uint32_t *mat, uint32_t nn,
-                                                    hipStream_t st) {
+// mat / nn: the device image of the score matrix (swmi_aff_mat_words dwords) and its side n + 1 (2 .. 65), or null: the plain sweeps
+// long_reads 0: the narrow and the wide sweep; r_min / r_max: the rows per lane of the launch's shortest and longest read (only
+//   the kernels that have pairs are launched).  long_reads 1: the strip sweep (every pair has a read longer than 1024 bases)
+extern "C" hipError_t swmi_launch_affine_sweep(const FillArgs *a, int32_t gap_open, uint32_t align_mode, const uint32_t *mat, uint32_t nn,
+                                               uint32_t r_min, uint32_t r_max, uint32_t long_reads, hipStream_t st) {
     if (a->n_pairs == 0) return hipSuccess;
     if (align_mode > 2u || (mat && (nn < 2u || nn > SWMI_MAT_NN_MAX))) return hipErrorInvalidValue;
+    // [narrow / wide / long][plain / matrix][align_mode]: one typed table per signature, so that a launch is checked against it
+    static void (*const plain[3][3])(FillArgs, int) = {
+        {sw_affine_sweep_kernel, sw_affine_sweep_fit_kernel, sw_affine_sweep_global_kernel},
+        {sw_affine_sweep_wide_kernel, sw_affine_sweep_fit_wide_kernel, sw_affine_sweep_global_wide_kernel},
+        {sw_affine_sweep_long_kernel, sw_affine_sweep_long_fit_kernel, sw_affine_sweep_long_global_kernel}};
+    static void (*const matrix[3][3])(FillArgs, int, const uint32_t *, uint32_t) = {
+        {sw_affine_sweep_matrix_kernel, sw_affine_sweep_fit_matrix_kernel, sw_affine_sweep_global_matrix_kernel},
+        {sw_affine_sweep_matrix_wide_kernel, sw_affine_sweep_fit_matrix_wide_kernel, sw_affine_sweep_global_matrix_wide_kernel},
+        {sw_affine_sweep_long_matrix_kernel, sw_affine_sweep_long_fit_matrix_kernel, sw_affine_sweep_long_global_matrix_kernel}};
     const dim3 grid((a->n_pairs + AFF_WAVES - 1) / AFF_WAVES), block(WAVE * AFF_WAVES);
-    if (mat) {
-        auto *const kern = align_mode == 0u ? sw_affine_sweep_long_matrix_kernel
-                                            : align_mode == 1u ? sw_affine_sweep_long_fit_matrix_kernel : sw_affine_sweep_long_global_matrix_kernel;
-        hipLaunchKernelGGL(kern, grid, block, 0, st, *a, (int)gap_open, mat, nn);
-    } else {
-        auto *const kern = align_mode == 0u ? sw_affine_sweep_long_kernel
-                                            : align_mode == 1u ? sw_affine_sweep_long_fit_kernel : sw_affine_sweep_long_global_kernel;
-        hipLaunchKernelGGL(kern, grid, block, 0, st, *a, (int)gap_open);
+    // (a launch's own error is what hipGetLastError returns below)
+    const auto launch = [&](int shape) {
+        if (mat) hipLaunchKernelGGL(matrix[shape][align_mode], grid, block, 0, st, *a, (int)gap_open, mat, nn);
+        else     hipLaunchKernelGGL(plain[shape][align_mode], grid, block, 0, st, *a, (int)gap_open);
+    };
+    if (long_reads) launch(2);
+    else {
+        if (r_min <= 4u) launch(0);
+        if (r_max >= 5u) launch(1);
     }
     return hipGetLastError();
 }
@@ -798,18 +650,17 @@ extern "C" hipError_t swmi_launch_affine_traceback(const TraceArgs *a, uint32_t 
                                                    uint32_t ops_words, hipStream_t st) {
     if (a->n_pairs == 0) return hipSuccess;
     if (align_mode > 2u) return hipErrorInvalidValue;
+    static void (*const kern[2][3])(TraceArgs, uint32_t, uint32_t) = {      // [long_reads][align_mode]
+        {sw_affine_traceback_kernel, sw_affine_traceback_fit_kernel, sw_affine_traceback_global_kernel},
+        {sw_affine_traceback_long_kernel, sw_affine_traceback_long_fit_kernel, sw_affine_traceback_long_global_kernel}};
     static const bool attrs = [] {
-        for (auto *k : {sw_affine_traceback_kernel, sw_affine_traceback_fit_kernel, sw_affine_traceback_global_kernel,
-                        sw_affine_traceback_long_kernel, sw_affine_traceback_long_fit_kernel, sw_affine_traceback_long_global_kernel})
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        for (auto &row : kern)
+            for (auto *k : row)
+                (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         return true;
     }();
     (void)attrs;
     const size_t lds = ((size_t)tile_words + ops_words + SWMI_EMIT_SCRATCH_WORDS) * sizeof(uint32_t);
-    auto *const kern = long_reads ? (align_mode == 0u ? sw_affine_traceback_long_kernel
-                                                      : align_mode == 1u ? sw_affine_traceback_long_fit_kernel : sw_affine_traceback_long_global_kernel)
-                                  : (align_mode == 0u ? sw_affine_traceback_kernel
-                                                      : align_mode == 1u ? sw_affine_traceback_fit_kernel : sw_affine_traceback_global_kernel);
-    hipLaunchKernelGGL(kern, dim3(a->n_pairs, SWMI_AFF_TB_SLOTS), dim3(WAVE), lds, st, *a, tile_words, ops_words);
+    hipLaunchKernelGGL(kern[long_reads ? 1 : 0][align_mode], dim3(a->n_pairs, SWMI_AFF_TB_SLOTS), dim3(WAVE), lds, st, *a, tile_words, ops_words);
     return hipGetLastError();
 }

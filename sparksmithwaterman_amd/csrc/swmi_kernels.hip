@@ -592,7 +592,7 @@ __device__ __forceinline__ void fill_pair(const FillArgs &A, const PairDesc pd, 
                 const uint32_t need = 4u * g + 8u < nblk_prod ? 4u * g + 8u : nblk_prod;
                 // the give-up is progress-based: the budget (~60 ms of s_sleep by default) restarts whenever the producer
                 // advances, so a slow producer is waited for and only one that does not move at all is abandoned -- the host
-                // then re-runs the chunk with the one-wavefront sweep, which needs no other workgroup (swmi_api.cpp)
+                // then re-runs the chunk with the one-wavefront sweep, which needs no other workgroup (swmi_run.cpp)
                 const uint32_t budget = A.strip_spins ? A.strip_spins : (1u << 18);
                 uint32_t spins = 0;
                 SWMI_SD(const unsigned long long dg0 = __builtin_amdgcn_s_memtime(); if (prod_seen < need) dg_polls++;)
@@ -2305,7 +2305,7 @@ extern "C" hipError_t swmi_launch_resident(const TraceArgs *a, const ResidentArg
 }
 
 // ------------------------------------------------------------------------------------------------
-// host-callable launchers (the runtime in swmi_api.cpp is plain C++)
+// host-callable launchers (the runtime in swmi_run.cpp is plain C++)
 // ------------------------------------------------------------------------------------------------
 // Small launches: the dispatcher may stack several workgroups on one CU while other CUs stay empty (measured: 250
 // workgroups of the 67-VGPR column-chunk kernel ran two to a CU, each wave sharing its SIMD, 1.5x slower per step).  A

@@ -265,9 +265,8 @@ static int enqueue_launches(RunState &rs, Launch &L, const ResidentArgs &xa, con
             fl.n_pairs = (uint32_t)plan.aff_n_long; fl.pairs = fa.pairs + fs.n_pairs;
             const uint32_t *mat = b->mat ? b->d_mat.as<uint32_t>() : nullptr;
             const uint32_t nn = b->mat ? b->mat->n + 1u : 0u;
-            if (mat) HIP_TRY(swmi_launch_affine_sweep_matrix(&fs, b->gap_open, (uint32_t)b->align_mode, mat, nn, plan.aff_r_min, plan.aff_r_max, ctx->stream));
-            else     HIP_TRY(swmi_launch_affine_sweep(&fs, b->gap_open, (uint32_t)b->align_mode, plan.aff_r_min, plan.aff_r_max, ctx->stream));
-            HIP_TRY(swmi_launch_affine_sweep_long(&fl, b->gap_open, (uint32_t)b->align_mode, mat, nn, ctx->stream));
+            HIP_TRY(swmi_launch_affine_sweep(&fs, b->gap_open, (uint32_t)b->align_mode, mat, nn, plan.aff_r_min, plan.aff_r_max, 0u, ctx->stream));
+            HIP_TRY(swmi_launch_affine_sweep(&fl, b->gap_open, (uint32_t)b->align_mode, mat, nn, 0u, 0u, 1u, ctx->stream));
         }
         else HIP_TRY(swmi_launch_fill(&fa, ctx->stream, ext ? ctx->ev[0] : nullptr, ext ? ctx->ev[1] : nullptr));
         rs.launches++;
