@@ -38,6 +38,8 @@ public class GpuSmithWaterman
 	static native void nativeSetAlignMode( long ctx , int alignMode ) ;
 	/** reads longer than 1024 bases on the affine kernels: 1 allowed, 0 refused (include/swmi.h: option "long_reads") */
 	static native void nativeSetLongReads( long ctx , int longReads ) ;
+	/** reads longer than 1024 bases inside a band of this half-width around the diagonal, 0: no band (include/swmi.h: option "band") */
+	static native void nativeSetBand( long ctx , int band ) ;
 	/** substitution scores on the context: alphabet = n ISO-8859-1 symbols, scores = n * n, row = read base; null clears */
 	static native void nativeSetScoreMatrix( long ctx , byte[] alphabet , int[] scores ) ;
 	static native void nativeFreeBatch( long ctx , long batch ) ;
@@ -90,6 +92,15 @@ public class GpuSmithWaterman
 	 * strips of 1024 rows; false (the default): such a read is refused.  For every batch aligned from now on, on every executor thread.
 	 */
 	public static void setLongReads( boolean longReads ) { LONG_READS = longReads ; }
+
+	/** the half-width of the band every context aligns reads longer than 1024 bases in, 0: none (applied next to longReads, before every batch) */
+	private static volatile int BAND = 0 ;
+
+	/**
+	 * band &gt; 0: a read longer than 1024 bases (setLongReads) is aligned inside the band |j - i| &lt;= band only, rounded outwards to strips
+	 * of 1024 rows, on the affine kernels; 0 (the default): no band.  For every batch aligned from now on, on every executor thread.
+	 */
+	public static void setBand( int band ) { BAND = band ; }
 
 	/** the score matrix every context applies before its next batch: { alphabet , scores } (null: none), and its version */
 	private static volatile Object[] MATRIX = null ;
@@ -225,6 +236,7 @@ public class GpuSmithWaterman
 			nativeSetGapOpen( ctx , sc.length == 4 ? sc[3] : 0 ) ;
 			nativeSetAlignMode( ctx , ALIGN_MODE ) ;
 			nativeSetLongReads( ctx , LONG_READS ? 1 : 0 ) ;
+			nativeSetBand( ctx , BAND ) ;
 			applyScoreMatrix( nc ) ;
 			long batch = nativeAlignBatch( ctx , sc[0] , sc[1] , sc[2] , TIE_SERIAL , types , refBuf , refOff , n , readBuf , readOff , reads.size() ) ;
 			try

@@ -63,6 +63,13 @@ JNIEXPORT void JNICALL Java_sw_GpuSmithWaterman_nativeSetLongReads(JNIEnv *env, 
     if (swmi_shim_set_long_reads((swmi_ctx *)(intptr_t)ctx, longReads, err, sizeof err) != SWMI_OK) throw_msg(env, err);
 }
 
+/* a band of this half-width around the diagonal for reads longer than 1024 bases from now on, 0: none */
+JNIEXPORT void JNICALL Java_sw_GpuSmithWaterman_nativeSetBand(JNIEnv *env, jclass cls, jlong ctx, jint band) {
+    char err[640];
+    (void)cls;
+    if (swmi_shim_set_band((swmi_ctx *)(intptr_t)ctx, band, err, sizeof err) != SWMI_OK) throw_msg(env, err);
+}
+
 /* a substitution score matrix on this context from now on: alphabet = n ISO-8859-1 symbols, scores = int[n * n], row = read base;
  * alphabet == null clears it */
 JNIEXPORT void JNICALL Java_sw_GpuSmithWaterman_nativeSetScoreMatrix(JNIEnv *env, jclass cls, jlong ctx, jbyteArray alphabet,

@@ -36,6 +36,9 @@ int swmi_shim_set_align_mode(swmi_ctx *ctx, int32_t align_mode, char *err, size_
 /* nativeSetLongReads: 1 lets the affine kernels take reads longer than 1024 bases from then on (swmi_set_option "long_reads"), 0 (the
  * default) refuses them.  Any other value is SWMI_ERR_INVALID and leaves the context as it was. */
 int swmi_shim_set_long_reads(swmi_ctx *ctx, int32_t long_reads, char *err, size_t err_len);
+/* nativeSetBand: reads longer than 1024 bases are aligned inside a band of this half-width around the diagonal from then on
+ * (swmi_set_option "band"), 0 (the default): no band.  A value outside 0 .. 2^20 is SWMI_ERR_INVALID and leaves the context as it was. */
+int swmi_shim_set_band(swmi_ctx *ctx, int32_t band, char *err, size_t err_len);
 
 /* nativeSetScoreMatrix: a substitution score matrix on this context (swmi_set_score_matrix): `alphabet` = n symbols narrowed to
  * bytes (ISO-8859-1), `scores` = n * n entries, row = read base, column = reference base (n_scores must be n * n).  n = 0 clears

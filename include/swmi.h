@@ -155,6 +155,24 @@ void        swmi_default_params(swmi_params *p);
  *                affine bounds (gap <= 0, |scores| <= 2^20) stay; at S = 2^20 the rule is today's M <= 1024.  With 0 nothing changes:
  *                a read of more than 1024 bases is SWMI_ERR_UNSUPPORTED.  A run (async runs and stream slots included) takes the value
  *                set when it was asked for.
+ * band (default 0 = no band and no change; 1 .. 2^20 = the half-width w in columns; any other value is SWMI_ERR_INVALID and leaves the
+ *                context as it was): a read of MORE than 1024 bases (so long_reads = 1 is needed for there to be any) is aligned inside
+ *                a band around the diagonal j = i only.  The band is a staircase with the sweep's strip height: row i (1-based) is in
+ *                strip s = (i - 1) / 1024, and cell (i, j) exists iff  max(1, 1024 s + 1 - w) <= j <= min(n, 1024 (s + 1) + w)  -- every
+ *                cell with |j - i| <= w, rounded outwards to strips.  A cell outside does not exist: in local mode its H, E and F read as
+ *                0 and it is never a maximum cell; in fit and global mode they read as -infinity.  Inside, everything is as without a
+ *                band, in global coordinates; fit mode takes its maximum over the in-band columns of row m; local mode with maximum 0
+ *                counts the IN-BAND cells in n_cells.  A pair whose read has at most 1024 bases is computed in full by the kernels it
+ *                takes today: cut its reference for the same effect.  A run with band > 0 takes the affine kernels whatever gap_open /
+ *                affine say (swmi_batch_mode = 3).  Refused with SWMI_ERR_UNSUPPORTED before anything is launched, for the batch's
+ *                longest read m (NS = ceil(m / 1024), M = 1024 NS) and the extreme references: a strip with an empty window
+ *                (n < 1024 (NS - 1) + 1 - w); global mode with (m, n) outside the band (n > 1024 NS + w, NS of the shortest long read);
+ *                fit and global mode unless  M * S <= 2^29  (S as under long_reads; local mode keeps M * S <= 2^30); global mode unless
+ *                3 * |gap_open| + (M + n) * |gap| <= 2^30; a pair whose banded direction field (4 KiB per 8-step block, strip s has
+ *                ceil((window + 63) / 8) blocks) is over max_workspace_bytes -- the chunking sees the smaller field, so a pair that did
+ *                not fit without a band may fit with one.  scores_only, device_strings, zero_copy, cell_cap and profiling apply as to
+ *                any affine run.  A run (async runs and stream slots included) takes the value set when it was asked for (DESIGN.md
+ *                section 8f).
  * Further knobs: spin_us (how long a run polls its stream before it blocks, default 2000); col_chunks (0 automatic,
  * 1 never, N > 1 force up to N column chunks per pair: a launch of few pairs with long references is swept by several
  * wavefronts per pair -- a read of more than 256 rows by several strip pipelines); debug_strip_spins / debug_reverse_strips (tests of the strip pipeline's give-up path);

@@ -15,6 +15,7 @@ TIE_STRICT = 1
 ALIGN_LOCAL = 0      # option "align_mode": Smith-Waterman (the default)
 ALIGN_FIT = 1        # the whole read against any stretch of the reference
 ALIGN_GLOBAL = 2     # the whole read against the whole reference
+BAND_MAX = 1 << 20   # option "band": the largest half-width (0: no band)
 PAIR_DEGENERATE = 0x1
 
 

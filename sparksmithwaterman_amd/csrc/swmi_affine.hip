@@ -102,6 +102,7 @@ struct AffSeam {
     int h, f;              // lanes 0..7: (H, F) of the row above the strip at the 8 columns lane 0 takes in this block
     int2 *row;             // the pair's seam row: (H, F) per column
     uint32_t wlane;        // the lane that writes it (63), none in the read's last strip
+    uint32_t coff;         // BAND: the columns left of the strip's window (`row` starts at the window, cells are listed with global columns)
 };
 
 template <int R>
@@ -121,7 +122,8 @@ struct AffState {
 // MODE != AFF_LOCAL: vrows is the row slot of read row m in the lane that owns it, 0xFFFFFFFF in every other lane
 // LONG: one strip of a long read -- lane 0 is fed from Z (every strip, the first one too: its Z holds row 0 of the mode) and lane
 // Z.wlane leaves (H, F) of its last row in the seam row
-template <int R, bool STRICT, bool MATRIX, int MODE, bool LONG = false>
+// BAND (with LONG): the strip sweeps a window of the reference -- n is the window's length, columns count from its first one
+template <int R, bool STRICT, bool MATRIX, int MODE, bool LONG = false, bool BAND = false>
 __device__ __forceinline__ void aff_block8(AffState<R> &S, const uint2 rw, const uint32_t t0, const uint32_t lane,
                                            const uint32_t n, const uint32_t row0, const uint32_t vrows,
                                            const int o, const int e, const int vmat, const int vmis,
@@ -210,7 +212,7 @@ __device__ __forceinline__ void aff_block8(AffState<R> &S, const uint2 rw, const
             if (cm != 0ull) {
                 const int v = __builtin_amdgcn_readlane(mrow, (int)__builtin_ctzll(cm));
                 if (v > S.thr) { S.thr = v; S.cnt = 0u; }
-                if (cand && S.cnt < ccap) cells[S.cnt] = make_uint2(row0 + vrows + 1u, c0 + 1u);
+                if (cand && S.cnt < ccap) cells[S.cnt] = make_uint2(row0 + vrows + 1u, c0 + 1u + (BAND ? Z.coff : 0u));
                 S.cnt += 1u;
             }
             continue;
@@ -231,7 +233,7 @@ __device__ __forceinline__ void aff_block8(AffState<R> &S, const uint2 rw, const
                 const uint64_t hm = BALLOT(hit);
                 if (hm) {
                     const uint32_t pos = S.cnt + lanes_below(hm);
-                    if (hit && pos < ccap) cells[pos] = make_uint2(row0 + (uint32_t)k + 1u, c0 + 1u);
+                    if (hit && pos < ccap) cells[pos] = make_uint2(row0 + (uint32_t)k + 1u, c0 + 1u + (BAND ? Z.coff : 0u));
                     S.cnt += (uint32_t)__popcll(hm);
                 }
             }
@@ -390,6 +392,99 @@ __device__ __forceinline__ void aff_sweep_long_pair(const FillArgs &A, const int
     aff_pair_out<MODE>(A, pd, lane, S.thr, S.cnt, ccap, m, n);
 }
 
+// The strip sweep under option "band" (half-width wb >= 1): strip sx sweeps the window of columns clo .. chi =
+// swmi_aff_band_lo / _hi (sx) and leaves the field of a (1024, chi - clo + 1) pair behind the fields of the strips above.
+// aff_block8 counts columns from the window's first one; only what surrounds it differs from aff_sweep_long_pair:
+//   - a cell outside the band reads as OUT: 0 in local mode (what the clamps make of -inf), SWMI_AFF_BAND_NEG otherwise
+//   - column clo - 1 of the strip's rows is the mode's column 0 when clo = 1, else OUT (H and E)
+//   - nh_prev of lane 0, the diagonal of the strip's first row at column clo, is H(1024 sx, clo - 1): the mode's value when
+//     clo = 1, else the seam's -- the strip above wrote it, clo(sx) - 1 >= clo(sx - 1)
+//   - lane 0's feed from above is the seam up to column chi(sx - 1), the last one the strip above wrote, and OUT beyond: the
+//     seam words there are stale
+//   - the reference words are read from byte clo - 1 of the image, which is not 8-aligned: three dwords, two byte-aligns
+// The seam row is still rewritten in place, and the argument of aff_sweep_long_pair holds relative to the window's origin: in
+// strip sx lane 0 is at column clo + t at step t and loads the seam of columns clo + t0 .. clo + t0 + 7 at step t0 <= t, lane 63
+// is at column clo + t - 63: a column is read at least 63 steps before this strip overwrites it.  Column clo - 1 (nh_prev) is
+// left of the window and not written by this strip at all.  What strip sx reads, columns clo(sx) - 1 .. chi(sx - 1), lies inside
+// clo(sx - 1) .. chi(sx - 1), all written by the strip above before the fence.
+template <bool STRICT, bool MATRIX, int MODE>
+__device__ __forceinline__ void aff_sweep_band_pair(const FillArgs &A, const int o, const PairDesc pd, const uint32_t lane, const uint32_t nn,
+                                                    const uint32_t wb) {
+    constexpr int R = SWMI_AFF_RMAX;
+    constexpr int OUT = MODE == AFF_LOCAL ? 0 : SWMI_AFF_BAND_NEG;
+    const SeqDesc rd = A.refs[pd.ref_id];
+    const SeqDesc qd = A.reads[pd.read_id];
+    const uint32_t n = rd.len, m = qd.len;
+    const uint32_t *__restrict__ refw = A.seqw + rd.boff;
+    const uint32_t *__restrict__ readw = A.seqw + qd.boff;
+    const uint32_t NS = swmi_aff_strips(m);
+    const AffCells cl = aff_cell_list(A, pd);
+    const uint32_t ccap = cl.cap;
+    uint2 *__restrict__ cells = cl.p;
+    int2 *const seam = reinterpret_cast<int2 *>(A.seam + pd.seam_off);
+    AffSeam Z;
+    uint32_t *__restrict__ dir = A.dir + pd.dir_off;
+    uint64_t inband = 0ull;                                      // in-band cells with i <= m (the degenerate count)
+
+    AffState<R> S;
+    S.thr = MODE == AFF_LOCAL ? 1 : INT32_MIN; S.cnt = 0;
+    for (uint32_t sx = 0; sx < NS; ++sx) {
+        const uint32_t row0 = sx * SWMI_AFF_MAX_READ + lane * R;
+        const uint32_t vrows = aff_vrows<R, MODE>(m, row0);
+        const uint32_t clo = swmi_aff_band_lo(sx, wb), chi = swmi_aff_band_hi(sx, n, wb);
+        const uint32_t nw = chi - clo + 1u, W = swmi_aff_strip_blocks(nw);
+        const uint32_t seam_end = sx ? swmi_aff_band_hi(sx - 1u, n, wb) - (clo - 1u) : 0u;   // window columns the strip above wrote
+        const uint32_t srows = m - sx * SWMI_AFF_MAX_READ < SWMI_AFF_MAX_READ ? m - sx * SWMI_AFF_MAX_READ : SWMI_AFF_MAX_READ;
+        inband += (uint64_t)srows * nw;
+        AFF_LOAD_ROWS
+        if (clo > 1u) {
+#pragma unroll
+            for (int k = 0; k < R; ++k) { S.h[k] = OUT; S.e[k] = OUT; }
+        }
+        S.rb = 0; S.f_last = 0;
+        Z.row = seam + (clo - 1u);
+        Z.coff = clo - 1u;
+        Z.wlane = sx + 1u < NS ? 63u : 0xFFFFFFFFu;
+        if (sx) __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent");
+        if (clo > 1u) S.nh_prev = seam[clo - 2u].x;                                // (a vector load, behind the fence)
+        else S.nh_prev = MODE != AFF_LOCAL && sx ? o + (int)(sx * SWMI_AFF_MAX_READ) * A.gap : 0;
+        const uint32_t boff = clo - 1u, bsh = boff & 3u;
+        const uint32_t *__restrict__ refb = refw + (boff >> 2);
+        for (uint32_t w = 0; w < W; ++w) {
+            const uint32_t t0 = 8u * w;
+            // lane 0's 8 reference bases from byte boff + t0 on (the image's padding covers the last block and the third dword)
+            const uint32_t r0 = refb[t0 >> 2], r1 = refb[(t0 >> 2) + 1u], r2 = refb[(t0 >> 2) + 2u];
+            const uint2 rw = make_uint2(__builtin_amdgcn_alignbyte(r1, r0, bsh), __builtin_amdgcn_alignbyte(r2, r1, bsh));
+            const uint32_t c = t0 + lane;                        // window column - 1 of lanes 0..7
+            Z.h = MODE == AFF_GLOBAL ? (int)((uint32_t)o + (c + 1u) * (uint32_t)A.gap) : 0;      // (strip 0: clo = 1, row 0 of the mode)
+            Z.f = MODE == AFF_LOCAL ? 0 : (int)((uint32_t)Z.h + (uint32_t)o);
+            if (sx) {
+                int2 v = make_int2(OUT, OUT);
+                if (lane < 8u && c < seam_end) v = Z.row[c];
+                Z.h = v.x; Z.f = v.y;
+            }
+#pragma unroll
+            for (int k = 0; k < R; ++k) S.acc[k] = 0u;
+            aff_block8<R, STRICT, MATRIX, MODE, true, true>(S, rw, t0, lane, nw, row0, vrows, o, A.gap, A.match, A.mismatch, cells, ccap, Z);
+            AFF_STORE_BLOCK
+        }
+        dir += (uint64_t)W * R * WAVE;
+    }
+    if (lane == 0) {
+        PairOut po;
+        if (MODE == AFF_LOCAL && S.cnt == 0u) {                  // maximum 0: every in-band cell ties
+            po.score = 0;
+            po.flags = SWMI_F_DEGENERATE;
+            po.n_cells = inband;
+        } else {
+            po.score = S.thr;
+            po.flags = S.cnt > ccap ? SWMI_F_CELL_OVF : 0u;
+            po.n_cells = S.cnt;
+        }
+        A.out[pd.out_id] = po;
+    }
+}
+
 #undef AFF_LOAD_ROWS
 #undef AFF_STORE_BLOCK
 
@@ -404,9 +499,10 @@ __device__ __forceinline__ void aff_sweep_dispatch(const FillArgs &A, const int 
 }
 
 // mat / nn (MATRIX only): the score matrix image (swmi_aff_mat_words) and its side n + 1
-// LONG: the strip sweep of reads longer than 1024 bases (RLO, RHI unused)
-template <int RLO, int RHI, bool MATRIX, int MODE = AFF_LOCAL, bool LONG = false>
-__device__ __forceinline__ void aff_sweep_entry(const FillArgs &A, const int o, const uint32_t *__restrict__ mat, const uint32_t nn) {
+// LONG: the strip sweep of reads longer than 1024 bases (RLO, RHI unused); BAND (with LONG): inside a band of half-width wb
+template <int RLO, int RHI, bool MATRIX, int MODE = AFF_LOCAL, bool LONG = false, bool BAND = false>
+__device__ __forceinline__ void aff_sweep_entry(const FillArgs &A, const int o, const uint32_t *__restrict__ mat, const uint32_t nn,
+                                                const uint32_t wb = 0u) {
     if (blockIdx.x == 0 && threadIdx.x == 0) A.hdr->reserved = 0ull;      // the traceback's bump allocator
     if (MATRIX) {                                                          // (before any wavefront leaves)
         for (uint32_t x = threadIdx.x; x < 256u; x += WAVE * AFF_WAVES) aff_mkey[x] = mat[x];
@@ -423,6 +519,11 @@ __device__ __forceinline__ void aff_sweep_entry(const FillArgs &A, const int o, 
     const PairDesc pd = A.pairs[pair];
     if constexpr (LONG) {
         if (uni(A.reads[pd.read_id].len) <= SWMI_AFF_MAX_READ) return;
+        if constexpr (BAND) {
+            if (A.strict) aff_sweep_band_pair<true, MATRIX, MODE>(A, o, pd, lane, nn, wb);
+            else          aff_sweep_band_pair<false, MATRIX, MODE>(A, o, pd, lane, nn, wb);
+            return;
+        }
         if (A.strict) aff_sweep_long_pair<true, MATRIX, MODE>(A, o, pd, lane, nn);
         else          aff_sweep_long_pair<false, MATRIX, MODE>(A, o, pd, lane, nn);
         return;
@@ -437,14 +538,20 @@ __device__ __forceinline__ void aff_sweep_entry(const FillArgs &A, const int o, 
 
 // The 18 sweep kernels: local, fit and global (option "align_mode"), each plain and with a score matrix (MATRIX = 0 / 1: the
 // two signatures), each narrow (R = 1..4), wide (R = 5..16) and long (option "long_reads": RLO, RHI unused).
-#define AFF_SWEEP_PARAMS_0 const FillArgs A, const int gap_open
-#define AFF_SWEEP_PARAMS_1 const FillArgs A, const int gap_open, const uint32_t *mat, const uint32_t nn
-#define AFF_SWEEP_ARGS_0 A, gap_open, nullptr, 0u
-#define AFF_SWEEP_ARGS_1 A, gap_open, mat, nn
-#define AFF_SWEEP_KERNEL(name, RLO, RHI, MATRIX, MODE, LONG)                                               \
-    extern "C" __global__ void __launch_bounds__(WAVE * AFF_WAVES) name(AFF_SWEEP_PARAMS_##MATRIX) {      \
-        aff_sweep_entry<RLO, RHI, MATRIX != 0, MODE, LONG>(AFF_SWEEP_ARGS_##MATRIX);                       \
+// BAND = 0 / 1: the six banded strip sweeps (option "band") take the half-width as one more scalar argument
+#define AFF_SWEEP_PARAMS_00 const FillArgs A, const int gap_open
+#define AFF_SWEEP_PARAMS_10 const FillArgs A, const int gap_open, const uint32_t *mat, const uint32_t nn
+#define AFF_SWEEP_PARAMS_01 const FillArgs A, const int gap_open, const uint32_t band
+#define AFF_SWEEP_PARAMS_11 const FillArgs A, const int gap_open, const uint32_t *mat, const uint32_t nn, const uint32_t band
+#define AFF_SWEEP_ARGS_00 A, gap_open, nullptr, 0u
+#define AFF_SWEEP_ARGS_10 A, gap_open, mat, nn
+#define AFF_SWEEP_ARGS_01 A, gap_open, nullptr, 0u, band
+#define AFF_SWEEP_ARGS_11 A, gap_open, mat, nn, band
+#define AFF_SWEEP_KERNEL_B(name, RLO, RHI, MATRIX, MODE, LONG, BAND)                                           \
+    extern "C" __global__ void __launch_bounds__(WAVE * AFF_WAVES) name(AFF_SWEEP_PARAMS_##MATRIX##BAND) {    \
+        aff_sweep_entry<RLO, RHI, MATRIX != 0, MODE, LONG, BAND != 0>(AFF_SWEEP_ARGS_##MATRIX##BAND);         \
     }
+#define AFF_SWEEP_KERNEL(name, RLO, RHI, MATRIX, MODE, LONG) AFF_SWEEP_KERNEL_B(name, RLO, RHI, MATRIX, MODE, LONG, 0)
 AFF_SWEEP_KERNEL(sw_affine_sweep_kernel, 1, 4, 0, AFF_LOCAL, false)
 AFF_SWEEP_KERNEL(sw_affine_sweep_wide_kernel, 5, SWMI_AFF_RMAX, 0, AFF_LOCAL, false)
 AFF_SWEEP_KERNEL(sw_affine_sweep_long_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, AFF_LOCAL, true)
@@ -463,11 +570,22 @@ AFF_SWEEP_KERNEL(sw_affine_sweep_long_global_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMA
 AFF_SWEEP_KERNEL(sw_affine_sweep_global_matrix_kernel, 1, 4, 1, AFF_GLOBAL, false)
 AFF_SWEEP_KERNEL(sw_affine_sweep_global_matrix_wide_kernel, 5, SWMI_AFF_RMAX, 1, AFF_GLOBAL, false)
 AFF_SWEEP_KERNEL(sw_affine_sweep_long_global_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, AFF_GLOBAL, true)
+AFF_SWEEP_KERNEL_B(sw_affine_sweep_band_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, AFF_LOCAL, true, 1)
+AFF_SWEEP_KERNEL_B(sw_affine_sweep_band_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, AFF_LOCAL, true, 1)
+AFF_SWEEP_KERNEL_B(sw_affine_sweep_band_fit_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, AFF_FIT, true, 1)
+AFF_SWEEP_KERNEL_B(sw_affine_sweep_band_fit_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, AFF_FIT, true, 1)
+AFF_SWEEP_KERNEL_B(sw_affine_sweep_band_global_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, AFF_GLOBAL, true, 1)
+AFF_SWEEP_KERNEL_B(sw_affine_sweep_band_global_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, AFF_GLOBAL, true, 1)
 #undef AFF_SWEEP_KERNEL
-#undef AFF_SWEEP_PARAMS_0
-#undef AFF_SWEEP_PARAMS_1
-#undef AFF_SWEEP_ARGS_0
-#undef AFF_SWEEP_ARGS_1
+#undef AFF_SWEEP_KERNEL_B
+#undef AFF_SWEEP_PARAMS_00
+#undef AFF_SWEEP_PARAMS_10
+#undef AFF_SWEEP_PARAMS_01
+#undef AFF_SWEEP_PARAMS_11
+#undef AFF_SWEEP_ARGS_00
+#undef AFF_SWEEP_ARGS_10
+#undef AFF_SWEEP_ARGS_01
+#undef AFF_SWEEP_ARGS_11
 
 // ------------------------------------------------------------------------------------------------
 // traceback
@@ -475,9 +593,16 @@ AFF_SWEEP_KERNEL(sw_affine_sweep_long_global_matrix_kernel, SWMI_AFF_RMAX, SWMI_
 // LDS of one wavefront: [tile_words] direction tile | [ops_words] ops, 16 per dword | [SWMI_EMIT_SCRATCH_WORDS] string scratch
 // LONG: the pairs of the strip sweeps (reads longer than 1024 bases): R = 16, the field of strip sx at sx * swmi_aff_strip_words(n).
 // !LONG: one strip -- sx and tsx stay 0 and fold away.
+// BAND (with LONG): the fields of the banded strip sweeps (half-width wb): strip sx holds the window of columns from clo =
+//   swmi_aff_band_lo(sx) on -- W blocks at swmi_aff_band_strip_off(sx) -- so step t of cell (i, j) is (j - clo) + lane; a step up
+//   across the seam changes clo, chi and W along with the strip.  In local mode a cell outside the window reads as H = 0, so an
+//   in-band cell may take its diagonal from one (0 + match): the walk that steps onto a column left of clo or right of chi has
+//   reached a cell with H = 0 and ends there, as at column 0, without touching the field -- that cell has no code.  (Left of the
+//   window the step index would wrap in lane 0 and name an inactive step of the row elsewhere; right of it it may lie past the
+//   strip's blocks.)  Fit and global never get there: an outside value loses every max strictly.
 namespace {
-template <int MODE, bool LONG>
-__device__ __forceinline__ void aff_traceback(const TraceArgs A, const uint32_t tile_words, const uint32_t ops_words) {
+template <int MODE, bool LONG, bool BAND = false>
+__device__ __forceinline__ void aff_traceback(const TraceArgs A, const uint32_t tile_words, const uint32_t ops_words, const uint32_t wb = 0u) {
     extern __shared__ uint32_t lds[];
     const uint32_t lane = threadIdx.x;
     const uint32_t slot = blockIdx.y, nslots = gridDim.y;
@@ -493,7 +618,8 @@ __device__ __forceinline__ void aff_traceback(const TraceArgs A, const uint32_t 
     const SeqDesc qd = A.reads[pd.read_id];
     const uint32_t n = rd.len, m = qd.len;
     const uint32_t R = LONG ? SWMI_AFF_RMAX : uni(swmi_aff_rows_per_lane(m));
-    const uint32_t W = uni(LONG ? swmi_aff_strip_blocks(n) : swmi_aff_blocks(m, n));
+    uint32_t W = uni(LONG ? swmi_aff_strip_blocks(n) : swmi_aff_blocks(m, n));      // (BAND: of strip sx, set with it)
+    uint32_t clo = 1u, chi = n;                                   // first and last column of strip sx's window
     const uint32_t blk_words = R * WAVE;                          // dwords of one 8-step block
     const uint32_t NB = tile_words / blk_words;                   // blocks per tile (>= 1: the host sizes the tile)
     const uint32_t max_ops = ops_words * 16u;
@@ -513,6 +639,10 @@ __device__ __forceinline__ void aff_traceback(const TraceArgs A, const uint32_t 
         uint32_t l = (i - 1u) / R, k = (i - 1u) - l * R;          // (global) lane and row slot of row i
         uint32_t sx = 0u;                                         // its strip, and the lane within it
         if constexpr (LONG) { sx = l / WAVE; l -= sx * WAVE; }
+        if constexpr (BAND) {
+            if (sx >= NS) sx = NS;                                // (a corrupted list: refused below, and no window is computed for it)
+            else { clo = swmi_aff_band_lo(sx, wb); chi = swmi_aff_band_hi(sx, n, wb); W = swmi_aff_band_blocks(sx, n, wb); }
+        }
         uint32_t st = 0u;                                         // 0: H, else the state entered (AFF_DIAG / AFF_INS / AFF_DEL)
         uint32_t n_ops = 0, cur = 0;
         int begin = MODE == AFF_LOCAL ? 0 : (int)cj;
@@ -526,14 +656,19 @@ __device__ __forceinline__ void aff_traceback(const TraceArgs A, const uint32_t 
                 if ((n_ops & 15u) == 0u) { if (lane == 0) ops[(n_ops >> 4) - 1u] = cur; cur = 0u; }
                 continue;
             }
-            const uint32_t t = j - 1u + l, w = t >> 3;
+            if constexpr (BAND && MODE == AFF_LOCAL) {
+                // outside the strip's window: H = 0, the walk ends (only ever reached in state H, by a diagonal step)
+                if (sx < NS && (j < clo || j > chi)) { ok = st == 0u; break; }
+            }
+            const uint32_t t = j - (BAND ? clo : 1u) + l, w = t >> 3;      // (BAND: clo <= j here, or the list is corrupted and w >= W refuses it)
             if (w < wlo || w >= whi || (LONG && sx != tsx)) {     // stage the tile that ends at this block
                 if (w >= W || (LONG && sx >= NS)) { ok = false; break; }    // (a corrupted list: never walks off the field)
                 WAVE_SYNC();
                 wlo = w + 1u >= NB ? w + 1u - NB : 0u;
                 whi = w + 1u;
                 if constexpr (LONG) tsx = sx;
-                const uint32_t *__restrict__ src = dir + (LONG ? (uint64_t)sx * swmi_aff_strip_words(n) : 0ull) + (uint64_t)wlo * blk_words;
+                const uint32_t *__restrict__ src = dir + (BAND ? swmi_aff_band_strip_off(sx, n, wb) : LONG ? (uint64_t)sx * swmi_aff_strip_words(n) : 0ull) +
+                                                   (uint64_t)wlo * blk_words;
                 const uint32_t words = (whi - wlo) * blk_words;
                 for (uint32_t x = lane; x < words; x += WAVE) tile[x] = src[x];
                 WAVE_SYNC();
@@ -563,7 +698,10 @@ __device__ __forceinline__ void aff_traceback(const TraceArgs A, const uint32_t 
             if (op != SWMI_DIR_D) {
                 if (k != 0u) --k;
                 else if (!LONG || l != 0u) { k = R - 1u; --l; }
-                else { k = R - 1u; l = WAVE - 1u; --sx; }         // up from a strip's first row: the last row of the strip above
+                else {                                            // up from a strip's first row: the last row of the strip above
+                    k = R - 1u; l = WAVE - 1u; --sx;
+                    if constexpr (BAND) { clo = swmi_aff_band_lo(sx, wb); chi = swmi_aff_band_hi(sx, n, wb); W = swmi_aff_band_blocks(sx, n, wb); }
+                }
             }
             cur |= op << (2u * (n_ops & 15u));
             ++n_ops;
@@ -599,17 +737,30 @@ __device__ __forceinline__ void aff_traceback(const TraceArgs A, const uint32_t 
 }
 }  // namespace
 
-#define AFF_TRACEBACK_KERNEL(name, MODE, LONG)                                                                                    \
-    extern "C" __global__ void __launch_bounds__(WAVE) name(const TraceArgs A, const uint32_t tile_words, const uint32_t ops_words) { \
-        aff_traceback<MODE, LONG>(A, tile_words, ops_words);                                                                       \
+#define AFF_TB_PARAMS_0 const TraceArgs A, const uint32_t tile_words, const uint32_t ops_words
+#define AFF_TB_PARAMS_1 const TraceArgs A, const uint32_t tile_words, const uint32_t ops_words, const uint32_t band
+#define AFF_TB_ARGS_0 A, tile_words, ops_words
+#define AFF_TB_ARGS_1 A, tile_words, ops_words, band
+#define AFF_TRACEBACK_KERNEL_B(name, MODE, LONG, BAND)                                                      \
+    extern "C" __global__ void __launch_bounds__(WAVE) name(AFF_TB_PARAMS_##BAND) {                        \
+        aff_traceback<MODE, LONG, BAND != 0>(AFF_TB_ARGS_##BAND);                                          \
     }
+#define AFF_TRACEBACK_KERNEL(name, MODE, LONG) AFF_TRACEBACK_KERNEL_B(name, MODE, LONG, 0)
 AFF_TRACEBACK_KERNEL(sw_affine_traceback_kernel, AFF_LOCAL, false)
 AFF_TRACEBACK_KERNEL(sw_affine_traceback_fit_kernel, AFF_FIT, false)
 AFF_TRACEBACK_KERNEL(sw_affine_traceback_global_kernel, AFF_GLOBAL, false)
 AFF_TRACEBACK_KERNEL(sw_affine_traceback_long_kernel, AFF_LOCAL, true)
 AFF_TRACEBACK_KERNEL(sw_affine_traceback_long_fit_kernel, AFF_FIT, true)
 AFF_TRACEBACK_KERNEL(sw_affine_traceback_long_global_kernel, AFF_GLOBAL, true)
+AFF_TRACEBACK_KERNEL_B(sw_affine_traceback_band_kernel, AFF_LOCAL, true, 1)
+AFF_TRACEBACK_KERNEL_B(sw_affine_traceback_band_fit_kernel, AFF_FIT, true, 1)
+AFF_TRACEBACK_KERNEL_B(sw_affine_traceback_band_global_kernel, AFF_GLOBAL, true, 1)
 #undef AFF_TRACEBACK_KERNEL
+#undef AFF_TRACEBACK_KERNEL_B
+#undef AFF_TB_PARAMS_0
+#undef AFF_TB_PARAMS_1
+#undef AFF_TB_ARGS_0
+#undef AFF_TB_ARGS_1
 
 // ------------------------------------------------------------------------------------------------
 // host-callable launchers
@@ -618,10 +769,21 @@ AFF_TRACEBACK_KERNEL(sw_affine_traceback_long_global_kernel, AFF_GLOBAL, true)
 // mat / nn: the device image of the score matrix (swmi_aff_mat_words dwords) and its side n + 1 (2 .. 65), or null: the plain sweeps
 // long_reads 0: the narrow and the wide sweep; r_min / r_max: the rows per lane of the launch's shortest and longest read (only
 //   the kernels that have pairs are launched).  long_reads 1: the strip sweep (every pair has a read longer than 1024 bases)
+// band: with long_reads, the half-width of option "band" (0: none): the banded strip sweep
 extern "C" hipError_t swmi_launch_affine_sweep(const FillArgs *a, int32_t gap_open, uint32_t align_mode, const uint32_t *mat, uint32_t nn,
-                                               uint32_t r_min, uint32_t r_max, uint32_t long_reads, hipStream_t st) {
+                                               uint32_t r_min, uint32_t r_max, uint32_t long_reads, uint32_t band, hipStream_t st) {
     if (a->n_pairs == 0) return hipSuccess;
-    if (align_mode > 2u || (mat && (nn < 2u || nn > SWMI_MAT_NN_MAX))) return hipErrorInvalidValue;
+    if (align_mode > 2u || (mat && (nn < 2u || nn > SWMI_MAT_NN_MAX)) || band > SWMI_AFF_BAND_MAX) return hipErrorInvalidValue;
+    if (long_reads && band) {
+        static void (*const bplain[3])(FillArgs, int, uint32_t) = {
+            sw_affine_sweep_band_kernel, sw_affine_sweep_band_fit_kernel, sw_affine_sweep_band_global_kernel};
+        static void (*const bmatrix[3])(FillArgs, int, const uint32_t *, uint32_t, uint32_t) = {
+            sw_affine_sweep_band_matrix_kernel, sw_affine_sweep_band_fit_matrix_kernel, sw_affine_sweep_band_global_matrix_kernel};
+        const dim3 bgrid((a->n_pairs + AFF_WAVES - 1) / AFF_WAVES), bblock(WAVE * AFF_WAVES);
+        if (mat) hipLaunchKernelGGL(bmatrix[align_mode], bgrid, bblock, 0, st, *a, (int)gap_open, mat, nn, band);
+        else     hipLaunchKernelGGL(bplain[align_mode], bgrid, bblock, 0, st, *a, (int)gap_open, band);
+        return hipGetLastError();
+    }
     // [narrow / wide / long][plain / matrix][align_mode]: one typed table per signature, so that a launch is checked against it
     static void (*const plain[3][3])(FillArgs, int) = {
         {sw_affine_sweep_kernel, sw_affine_sweep_fit_kernel, sw_affine_sweep_global_kernel},
@@ -646,10 +808,13 @@ extern "C" hipError_t swmi_launch_affine_sweep(const FillArgs *a, int32_t gap_op
 }
 
 // long_reads: the walk over the strips' fields (every pair of the launch has a read longer than 1024 bases)
-extern "C" hipError_t swmi_launch_affine_traceback(const TraceArgs *a, uint32_t align_mode, uint32_t long_reads, uint32_t tile_words,
+// band: as for the sweep
+extern "C" hipError_t swmi_launch_affine_traceback(const TraceArgs *a, uint32_t align_mode, uint32_t long_reads, uint32_t band, uint32_t tile_words,
                                                    uint32_t ops_words, hipStream_t st) {
     if (a->n_pairs == 0) return hipSuccess;
-    if (align_mode > 2u) return hipErrorInvalidValue;
+    if (align_mode > 2u || band > SWMI_AFF_BAND_MAX) return hipErrorInvalidValue;
+    static void (*const bkern[3])(TraceArgs, uint32_t, uint32_t, uint32_t) = {      // [align_mode]: the banded long walks
+        sw_affine_traceback_band_kernel, sw_affine_traceback_band_fit_kernel, sw_affine_traceback_band_global_kernel};
     static void (*const kern[2][3])(TraceArgs, uint32_t, uint32_t) = {      // [long_reads][align_mode]
         {sw_affine_traceback_kernel, sw_affine_traceback_fit_kernel, sw_affine_traceback_global_kernel},
         {sw_affine_traceback_long_kernel, sw_affine_traceback_long_fit_kernel, sw_affine_traceback_long_global_kernel}};
@@ -657,10 +822,15 @@ extern "C" hipError_t swmi_launch_affine_traceback(const TraceArgs *a, uint32_t 
         for (auto &row : kern)
             for (auto *k : row)
                 (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        for (auto *k : bkern)
+            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         return true;
     }();
     (void)attrs;
     const size_t lds = ((size_t)tile_words + ops_words + SWMI_EMIT_SCRATCH_WORDS) * sizeof(uint32_t);
-    hipLaunchKernelGGL(kern[long_reads ? 1 : 0][align_mode], dim3(a->n_pairs, SWMI_AFF_TB_SLOTS), dim3(WAVE), lds, st, *a, tile_words, ops_words);
+    if (long_reads && band)
+        hipLaunchKernelGGL(bkern[align_mode], dim3(a->n_pairs, SWMI_AFF_TB_SLOTS), dim3(WAVE), lds, st, *a, tile_words, ops_words, band);
+    else
+        hipLaunchKernelGGL(kern[long_reads ? 1 : 0][align_mode], dim3(a->n_pairs, SWMI_AFF_TB_SLOTS), dim3(WAVE), lds, st, *a, tile_words, ops_words);
     return hipGetLastError();
 }

@@ -298,6 +298,51 @@ SWMI_HD static inline uint64_t swmi_aff_dir_words(uint32_t m, uint32_t n) {
 // dwords of a mode-3 pair's seam row: (H, F) of the strip's last row at every column, one row rewritten in place by every
 // strip but the last (reads of one strip have none)
 SWMI_HD static inline uint64_t swmi_aff_seam_words(uint32_t m, uint32_t n) { return m > SWMI_AFF_MAX_READ ? 2ull * n : 0ull; }
+// ---- option "band" (half-width w >= 1, reads longer than SWMI_AFF_MAX_READ only): strip s sweeps the WINDOW of columns
+// swmi_aff_band_lo(s, w) .. swmi_aff_band_hi(s, n, w) -- the band |j - i| <= w rounded outwards to the strip -- and leaves the
+// field of a (1024, window length) pair; the strips' fields are consecutive, now of unequal size.  The host refuses a pair with
+// an empty window, so lo <= hi holds for every strip a kernel sees. ----
+#define SWMI_AFF_BAND_MAX (1u << 20)
+// the value of a cell outside the band in fit and global mode: below every real value less three scores, and two more scores
+// added to it do not leave int32 (DESIGN.md 8f derives it from the bounds of a banded run): -2^31 + 2^27
+#define SWMI_AFF_BAND_NEG (-2013265920)
+SWMI_HD static inline uint32_t swmi_aff_band_lo(uint32_t s, uint32_t w) {
+    const uint64_t a = (uint64_t)SWMI_AFF_MAX_READ * s;                  // 1024 s + 1 - w, at least 1
+    return a > w ? (uint32_t)(a + 1u - w) : 1u;
+}
+SWMI_HD static inline uint32_t swmi_aff_band_hi(uint32_t s, uint32_t n, uint32_t w) {
+    const uint64_t a = (uint64_t)SWMI_AFF_MAX_READ * ((uint64_t)s + 1u) + w;
+    return a < n ? (uint32_t)a : n;
+}
+// 8-step blocks of strip s's field: swmi_aff_strip_blocks of its window
+SWMI_HD static inline uint32_t swmi_aff_band_blocks(uint32_t s, uint32_t n, uint32_t w) {
+    return swmi_aff_strip_blocks(swmi_aff_band_hi(s, n, w) - swmi_aff_band_lo(s, w) + 1u);
+}
+// blocks of the strips before strip s, in closed form.  With B(x) = (x + 70) / 8 the blocks of a window of x columns, strips
+// below sa = w / 1024 + 1 start at column 1 and strips from sb = the first s with 1024 (s + 1) + w >= n on end at column n:
+//   s < sa, s < sb    window 1024 (s + 1) + w    128 (s + 1) + B(w)
+//   between the two   window n (sb < sa) or 1024 + 2 w (sa < sb): the same for every such strip
+//   s >= sa, s >= sb  window n + w - 1024 s        B(n + w) - 128 s
+// (1024 s is a multiple of 8, so it leaves the rounding alone) -- three arithmetic series.
+SWMI_HD static inline uint64_t swmi_aff_band_blocks_before(uint32_t s, uint32_t n, uint32_t w) {
+    const uint64_t sa = (uint64_t)w / SWMI_AFF_MAX_READ + 1u;
+    const uint64_t sb = (uint64_t)n > (uint64_t)SWMI_AFF_MAX_READ + w ? ((uint64_t)n - w + SWMI_AFF_MAX_READ - 1u) / SWMI_AFF_MAX_READ - 1u : 0u;
+    const uint64_t p = sa < sb ? sa : sb, q = sa < sb ? sb : sa;
+    const uint64_t k1 = s < p ? s : p;
+    const uint64_t e2 = s < q ? s : q, k2 = e2 > p ? e2 - p : 0u;
+    const uint64_t k3 = s > q ? s - q : 0u;
+    const uint64_t mid = sb < sa ? ((uint64_t)n + 70u) / 8u : ((uint64_t)SWMI_AFF_MAX_READ + 2ull * w + 70u) / 8u;
+    return 64ull * k1 * (k1 + 1u) + k1 * (((uint64_t)w + 70u) / 8u)
+         + k2 * mid
+         + k3 * (((uint64_t)n + w + 70u) / 8u) - 64ull * k3 * (2u * q + k3 - 1u);
+}
+// dword offset of strip s's field in the pair's, and the whole field of a banded pair (m > 1024)
+SWMI_HD static inline uint64_t swmi_aff_band_strip_off(uint32_t s, uint32_t n, uint32_t w) {
+    return swmi_aff_band_blocks_before(s, n, w) * SWMI_AFF_RMAX * 64u;
+}
+SWMI_HD static inline uint64_t swmi_aff_band_dir_words(uint32_t m, uint32_t n, uint32_t w) {
+    return swmi_aff_band_strip_off(swmi_aff_strips(m), n, w);
+}
 // score matrices (swmi_set_score_matrix) on the affine sweeps: at most 64 symbols, plus class n = outside the alphabet.
 // Device image: 256 key dwords by base code (class * 4 | hi << 16, hi = the code outside the alphabet, else 0x1FF), then the
 // (n+1) x (n+1) int32 scores, row = read class, column = reference class (row and column n are not read: the kernel fills them).

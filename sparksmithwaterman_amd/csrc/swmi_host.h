@@ -149,6 +149,7 @@ struct swmi_ctx {
     int affine = -1;                        // -1: the affine kernels (mode 3) when gap_open != 0; 1: always
     int align_mode = SWMI_ALIGN_LOCAL;      // SWMI_ALIGN_FIT / _GLOBAL: end-to-end alignment, on the affine kernels
     int long_reads = 0;                     // 1: the affine kernels take reads longer than 1024 bases, swept in strips (swmi.h)
+    int band = 0;                           // > 0: the half-width of the band the strip sweeps of such reads keep to (swmi.h); the affine kernels
     std::mutex mat_mu;                      // guards `matrix` (not ctx->mu: setting a matrix does not wait for a run)
     std::shared_ptr<const ScoreMatrix> matrix;   // swmi_set_score_matrix; a run with one takes the affine kernels
     // swmi_batch_run_async: one run in flight on the context's own host thread
@@ -161,6 +162,7 @@ struct swmi_ctx {
     std::shared_ptr<const ScoreMatrix> job_matrix;   // the matrix when swmi_batch_run_async was called
     int job_align_mode = 0;                          // align_mode when swmi_batch_run_async was called
     int job_long_reads = 0;                          // long_reads when swmi_batch_run_async was called
+    int job_band = 0;                                // band when swmi_batch_run_async was called
     uint32_t job_delay_us = 0;                       // debug_async_delay_us when swmi_batch_run_async was called
     int job_rc = 0;
     std::string job_err;
@@ -216,13 +218,14 @@ struct __attribute__((visibility("hidden"))) PlanKey {
     uint64_t mat_gen = 0;                   // the score matrix's generation (0: none): it bounds the paths
     int align_mode = 0;                     // ... as does the alignment mode
     int long_reads = 0;                     // option "long_reads" of the run
+    int band = 0;                           // option "band" of the run
     const void *d_pairs = nullptr;          // where the chunk's PairDesc image sits on the device, and its size
     size_t pairs_bytes = 0;
     bool operator==(const PlanKey &o) const {
         return valid == o.valid && lo == o.lo && hi == o.hi && work == o.work && memcmp(&params, &o.params, sizeof(swmi_params)) == 0 &&
                eff_mode == o.eff_mode && col_chunks == o.col_chunks && reverse_strips == o.reverse_strips && resident == o.resident &&
                tfused == o.tfused && exact == o.exact && scores_only == o.scores_only && mat_gen == o.mat_gen &&
-               align_mode == o.align_mode && long_reads == o.long_reads && d_pairs == o.d_pairs && pairs_bytes == o.pairs_bytes;
+               align_mode == o.align_mode && long_reads == o.long_reads && band == o.band && d_pairs == o.d_pairs && pairs_bytes == o.pairs_bytes;
     }
 };
 
@@ -273,11 +276,13 @@ struct swmi_batch {
     swmi_params auto_params{};
     std::vector<Work> work;                 // schedule (pairs sorted by work), valid for work_mode
     int work_mode = -1;
+    int work_band = 0;                      // the band the schedule's workspace sizes were made for (mode 3)
     bool work_tfused = false;               // the schedule's workspace sizes leave room for sw_tfused_kernel's column checkpoints
     uint32_t eff_mode = 1;                  // pipeline of the current run (3: the affine kernels, swmi_affine.hip)
     int32_t gap_open = 0;                   // the context's gap_open when the run started (mode 3)
     int align_mode = 0;                     // the context's align_mode when the run was asked for (mode 3)
     int long_reads = 0;                     // ... and its long_reads
+    int band = 0;                           // ... and its band
     std::shared_ptr<const ScoreMatrix> mat; // the score matrix of the current run (null: none); keeps its host image alive
     DevBuf d_mat;                           // ... its device image, copied on the run's stream
     uint64_t d_mat_gen = 0;                 // generation of the matrix in d_mat (0: none)

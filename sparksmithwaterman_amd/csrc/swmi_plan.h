@@ -360,7 +360,7 @@ static int prepare_chunk(RunState &rs, const std::vector<Work> &work, size_t lo,
     key.resident = ctx->resident; key.tfused = ctx->tfused;
     key.exact = cells_exact != nullptr; key.scores_only = ctx->scores_only != 0;
     key.mat_gen = b->mat ? b->mat->gen : 0u; key.align_mode = b->align_mode;
-    key.long_reads = b->long_reads;
+    key.long_reads = b->long_reads; key.band = b->band;
     key.d_pairs = b->d_pairs.p; key.pairs_bytes = np * sizeof(PairDesc);
     auto p1 = p0;
     if (key == b->plan_key) {

@@ -265,8 +265,9 @@ static int enqueue_launches(RunState &rs, Launch &L, const ResidentArgs &xa, con
             fl.n_pairs = (uint32_t)plan.aff_n_long; fl.pairs = fa.pairs + fs.n_pairs;
             const uint32_t *mat = b->mat ? b->d_mat.as<uint32_t>() : nullptr;
             const uint32_t nn = b->mat ? b->mat->n + 1u : 0u;
-            HIP_TRY(swmi_launch_affine_sweep(&fs, b->gap_open, (uint32_t)b->align_mode, mat, nn, plan.aff_r_min, plan.aff_r_max, 0u, ctx->stream));
-            HIP_TRY(swmi_launch_affine_sweep(&fl, b->gap_open, (uint32_t)b->align_mode, mat, nn, 0u, 0u, 1u, ctx->stream));
+            HIP_TRY(swmi_launch_affine_sweep(&fs, b->gap_open, (uint32_t)b->align_mode, mat, nn, plan.aff_r_min, plan.aff_r_max, 0u, 0u, ctx->stream));
+            // (option "band": the banded strip sweep; the other pairs are swept in full)
+            HIP_TRY(swmi_launch_affine_sweep(&fl, b->gap_open, (uint32_t)b->align_mode, mat, nn, 0u, 0u, 1u, (uint32_t)b->band, ctx->stream));
         }
         else HIP_TRY(swmi_launch_fill(&fa, ctx->stream, ext ? ctx->ev[0] : nullptr, ext ? ctx->ev[1] : nullptr));
         rs.launches++;
@@ -295,8 +296,8 @@ static int enqueue_launches(RunState &rs, Launch &L, const ResidentArgs &xa, con
         ts.n_pairs = (uint32_t)(np - plan.aff_n_long);
         tl.n_pairs = (uint32_t)plan.aff_n_long; tl.pairs = ta.pairs + ts.n_pairs;
         const uint32_t ops_words = (uint32_t)(((uint64_t)plan.max_path + 15) / 16 + 1);
-        HIP_TRY(swmi_launch_affine_traceback(&ts, (uint32_t)b->align_mode, 0u, SWMI_AFF_TILE_WORDS, ops_words, ctx->stream));
-        HIP_TRY(swmi_launch_affine_traceback(&tl, (uint32_t)b->align_mode, 1u, SWMI_AFF_TILE_WORDS, ops_words, ctx->stream));
+        HIP_TRY(swmi_launch_affine_traceback(&ts, (uint32_t)b->align_mode, 0u, 0u, SWMI_AFF_TILE_WORDS, ops_words, ctx->stream));
+        HIP_TRY(swmi_launch_affine_traceback(&tl, (uint32_t)b->align_mode, 1u, (uint32_t)b->band, SWMI_AFF_TILE_WORDS, ops_words, ctx->stream));
     } else if (n_res + n_tf < np) {
         HIP_TRY(swmi_launch_traceback(&ta, ctx->stream, ext ? ctx->ev[2] : nullptr, ext ? ctx->ev[3] : nullptr));
     }
@@ -511,10 +512,53 @@ static int run_chunk(RunState &rs, const std::vector<Work> &work, size_t lo, siz
 // ------------------------------------------------------------------------------------------
 // a run of the whole batch
 // ------------------------------------------------------------------------------------------
+// Option "band" (half-width w) with at least one read longer than 1024 bases: what a banded run refuses (swmi.h),
+// in 64-bit arithmetic.  rows = 1024 * strips of the longest read, S = the largest |score|, max_n = the longest reference.
+// Every condition is monotone in m and n, so the extreme lengths decide for every long pair of the batch.
+static int check_band(const swmi_ctx *ctx, const swmi_batch *b, const swmi_params *p, int align_mode, int band, uint64_t rows, int64_t S,
+                      uint64_t max_n) {
+    const int64_t w = band;
+    uint64_t min_n = UINT64_MAX, min_long = UINT64_MAX, max_m = 0;
+    for (uint32_t r = 0; r < b->n_refs; r++)
+        if (b->ref_desc[r].len) min_n = std::min<uint64_t>(min_n, b->ref_desc[r].len);       // (a pair with an empty side is not swept)
+    for (uint32_t q = 0; q < b->n_reads; q++) {
+        const uint64_t m = b->read_desc[q].len;
+        if (m > SWMI_AFF_MAX_READ) min_long = std::min(min_long, m);
+        max_m = std::max(max_m, m);
+    }
+    // a strip whose window is empty: the last strip's window starts at column 1024 (NS - 1) + 1 - w
+    const int64_t last_lo = (int64_t)rows - SWMI_AFF_MAX_READ + 1 - w;
+    if ((int64_t)min_n < last_lo)
+        return fail(SWMI_ERR_UNSUPPORTED, "band %d: the last strip of the longest read (%llu bases) starts at column %lld, past the end of the "
+                    "shortest reference (%llu)", band, (unsigned long long)max_m, (long long)last_lo, (unsigned long long)min_n);
+    // global mode: the one cell (m, n) must lie in the band, n <= 1024 NS + w
+    const uint64_t min_rows = (uint64_t)SWMI_AFF_MAX_READ * swmi_aff_strips((uint32_t)min_long);
+    if (align_mode == SWMI_ALIGN_GLOBAL && max_n > min_rows + (uint64_t)w)
+        return fail(SWMI_ERR_UNSUPPORTED, "band %d, align_mode global: the end of the longest reference (%llu) lies outside the band of a read of "
+                    "%llu bases (at most %llu)", band, (unsigned long long)max_n, (unsigned long long)min_long, (unsigned long long)(min_rows + w));
+    // the arithmetic bounds of a banded run: half of an unbanded run's, which leaves room for the value of a cell outside the band
+    if (align_mode != SWMI_ALIGN_LOCAL && (int64_t)rows * S > ((int64_t)1 << 29))
+        return fail(SWMI_ERR_UNSUPPORTED, "band %d, align_mode fit / global: the longest read (%llu bases) is swept as %llu rows, and %llu * %lld (the "
+                    "largest |score|) is above 2^29", band, (unsigned long long)max_m, (unsigned long long)rows, (unsigned long long)rows, (long long)S);
+    if (align_mode == SWMI_ALIGN_GLOBAL) {
+        const int64_t low = 3 * (int64_t)ctx->gap_open + (int64_t)(rows + max_n) * (int64_t)p->gap;
+        if (low < -((int64_t)1 << 30))
+            return fail(SWMI_ERR_UNSUPPORTED, "band %d, align_mode global: 3 * gap_open + (1024 * ceil(m / 1024) + n) * gap = %lld for the longest "
+                        "read (%llu) and reference (%llu) is below -2^30", band, (long long)low, (unsigned long long)max_m, (unsigned long long)max_n);
+    }
+    // the field of the largest pair alone against the workspace cap (it grows with m and with n)
+    const uint64_t bytes = swmi_aff_band_dir_words((uint32_t)max_m, (uint32_t)max_n, (uint32_t)band) * 4;
+    if (bytes > ctx->max_workspace_bytes)
+        return fail(SWMI_ERR_UNSUPPORTED, "band %d: the direction field of the longest read (%llu) against the longest reference (%llu) takes %llu "
+                    "bytes, more than max_workspace_bytes (%llu)", band, (unsigned long long)max_m, (unsigned long long)max_n,
+                    (unsigned long long)bytes, (unsigned long long)ctx->max_workspace_bytes);
+    return SWMI_OK;
+}
+
 // what a run cannot compute, refused before anything is launched (under ctx->mu: the context's options are read)
-// mat: the run's score matrix or null; long_reads: option "long_reads" of the run
+// mat: the run's score matrix or null; long_reads, band: options "long_reads" and "band" of the run
 static int check_run_params(const swmi_ctx *ctx, const swmi_batch *b, const swmi_params *p, bool affine, int align_mode,
-                            const ScoreMatrix *mat, int long_reads) {
+                            const ScoreMatrix *mat, int long_reads, int band) {
     if (p->tie_mode != SWMI_TIE_SERIAL && p->tie_mode != SWMI_TIE_STRICT)
         return fail(SWMI_ERR_INVALID, "unknown tie_mode %d", p->tie_mode);
     // GetAlignment tests `align == alignTypes[0]`, then `== alignTypes[1]`, else deletion
@@ -547,8 +591,13 @@ static int check_run_params(const swmi_ctx *ctx, const swmi_batch *b, const swmi
             if ((int64_t)rows * S > ((int64_t)1 << 30))
                 return fail(SWMI_ERR_UNSUPPORTED, "long_reads: the longest read (%llu bases) is swept as %llu rows, and %llu * %lld (the largest "
                             "|score|) is above 2^30", (unsigned long long)max_m, (unsigned long long)rows, (unsigned long long)rows, (long long)S);
+            if (band > 0 && max_m > SWMI_AFF_MAX_READ && max_n) {
+                int rc = check_band(ctx, b, p, align_mode, band, rows, S, max_n);
+                if (rc) return rc;
+            }
             // a pair of several strips is one launch's work at the least: refused when its field alone is over the cap
-            if (max_m > SWMI_AFF_MAX_READ && max_n && swmi_aff_dir_words((uint32_t)max_m, (uint32_t)max_n) * 4 > ctx->max_workspace_bytes)
+            // (a banded run is checked with its own, smaller field in check_band)
+            if (band <= 0 && max_m > SWMI_AFF_MAX_READ && max_n && swmi_aff_dir_words((uint32_t)max_m, (uint32_t)max_n) * 4 > ctx->max_workspace_bytes)
                 return fail(SWMI_ERR_UNSUPPORTED, "long_reads: the direction field of the longest read (%llu) against the longest reference (%llu) "
                             "takes %llu bytes, more than max_workspace_bytes (%llu)", (unsigned long long)max_m, (unsigned long long)max_n,
                             (unsigned long long)(swmi_aff_dir_words((uint32_t)max_m, (uint32_t)max_n) * 4), (unsigned long long)ctx->max_workspace_bytes);
@@ -631,9 +680,11 @@ static int choose_traceback_grain(swmi_ctx *ctx, swmi_batch *b, const swmi_param
 // The schedule: every pair with two non-empty sides (pairs with an empty side never enter ScoreMatrix's loops,
 // SmithWaterman.java:157-159: (0, [])).  It only depends on the sequence lengths and the pipeline mode: built once per batch.
 static void build_schedule(const swmi_ctx *ctx, swmi_batch *b) {
-    if (b->work_mode == (int)b->eff_mode && b->work_tfused == (ctx->tfused == 1)) return;
+    const int band = b->eff_mode == 3 ? b->band : 0;
+    if (b->work_mode == (int)b->eff_mode && b->work_tfused == (ctx->tfused == 1) && b->work_band == band) return;
     const uint32_t n_refs = b->n_refs, n_reads = b->n_reads;
     b->work_tfused = ctx->tfused == 1;
+    b->work_band = band;
     b->work.clear();
     b->work.reserve((uint64_t)n_refs * n_reads);
     b->work_cells = 0;
@@ -659,13 +710,17 @@ static void build_schedule(const swmi_ctx *ctx, swmi_batch *b) {
         b->work.push_back(w);
     };
     const bool tf = ctx->tfused == 1;
+    // (option "band": a read of several strips leaves the field of its windows only)
+    auto dir_words = [&](uint32_t m, uint32_t n) {
+        return band > 0 && m > SWMI_AFF_MAX_READ ? swmi_aff_band_dir_words(m, n, (uint32_t)band) : swmi_dir_words(m, n, b->eff_mode, tf);
+    };
     if (refs_uniform) {                              // (reads outermost: descending m x the one n)
         for (uint32_t q : qo) {
             const uint32_t m = b->read_desc[q].len;
             if (m == 0) continue;
             const uint32_t n = n_refs ? b->ref_desc[ro[0]].len : 0;
             if (n == 0) break;
-            const uint64_t dw = swmi_dir_words(m, n, b->eff_mode, tf), sw = seam_words(m, n);
+            const uint64_t dw = dir_words(m, n), sw = seam_words(m, n);
             for (uint32_t r : ro) add(r, q, n, m, dw, sw);
         }
     } else {
@@ -678,7 +733,7 @@ static void build_schedule(const swmi_ctx *ctx, swmi_batch *b) {
             for (uint32_t q : qo) {
                 const uint32_t m = b->read_desc[q].len;
                 if (m == 0) continue;
-                if (m != last_m) { dw = swmi_dir_words(m, n, b->eff_mode, tf); sw = seam_words(m, n); last_m = m; }
+                if (m != last_m) { dw = dir_words(m, n); sw = seam_words(m, n); last_m = m; }
                 add(r, q, n, m, dw, sw);
             }
         }
@@ -723,15 +778,16 @@ static int rerun_overflowed(RunState &rs, const std::vector<Work> &work, const s
 
 // mat: the score matrix the run uses (the context's when the run was asked for), or null
 // align_mode: the context's when the run was asked for
-// long_reads: likewise
+// long_reads, band: likewise
 static int batch_run(swmi_ctx *ctx, swmi_batch *b, const swmi_params *p, std::shared_ptr<const ScoreMatrix> mat, const int align_mode,
-                     const int long_reads) {
+                     const int long_reads, const int band) {
     if (!ctx || !b || !p) return fail(SWMI_ERR_INVALID, "null argument");
     std::lock_guard<std::mutex> g(ctx->mu);
     // (a score matrix and the end-to-end modes run on the affine kernels only)
-    const bool affine = ctx->affine == 1 || ctx->gap_open != 0 || mat != nullptr || align_mode != SWMI_ALIGN_LOCAL;
+    // (... and so does a band)
+    const bool affine = ctx->affine == 1 || ctx->gap_open != 0 || mat != nullptr || align_mode != SWMI_ALIGN_LOCAL || band > 0;
     int rc;
-    if ((rc = check_run_params(ctx, b, p, affine, align_mode, mat.get(), long_reads))) return rc;
+    if ((rc = check_run_params(ctx, b, p, affine, align_mode, mat.get(), long_reads, band))) return rc;
     static const bool host_dbg = getenv("SWMI_DEBUG_HOST") != nullptr;
     const auto h0 = Clock::now();
     {   // (hipSetDevice costs microseconds even when nothing changes; a sub-millisecond batch notices)
@@ -760,6 +816,7 @@ static int batch_run(swmi_ctx *ctx, swmi_batch *b, const swmi_params *p, std::sh
     b->gap_open = ctx->gap_open;
     b->align_mode = align_mode;
     b->long_reads = long_reads;
+    b->band = band;
     if (affine) b->eff_mode = 3;                         // the affine kernels (swmi_affine.hip): no other pipeline option applies
     b->mat = std::move(mat);
     if (b->mat && b->d_mat_gen != b->mat->gen) {
@@ -827,7 +884,7 @@ static int batch_run(swmi_ctx *ctx, swmi_batch *b, const swmi_params *p, std::sh
 
 extern "C" int swmi_batch_run(swmi_ctx *ctx, swmi_batch *b, const swmi_params *p) {
     if (!ctx || !b || !p) return fail(SWMI_ERR_INVALID, "null argument");
-    return batch_run(ctx, b, p, ctx_matrix(ctx), ctx->align_mode, ctx->long_reads);
+    return batch_run(ctx, b, p, ctx_matrix(ctx), ctx->align_mode, ctx->long_reads, ctx->band);
 }
 
 // ---- asynchronous run: the same swmi_batch_run on the context's own host thread -------------------------------
@@ -846,7 +903,7 @@ static void swmi_worker_loop(swmi_ctx *ctx) {
         }
         if (st == 3) return;
         if (ctx->job_delay_us) std::this_thread::sleep_for(std::chrono::microseconds(ctx->job_delay_us));
-        const int rc = batch_run(ctx, ctx->job_batch, &ctx->job_params, std::move(ctx->job_matrix), ctx->job_align_mode, ctx->job_long_reads);
+        const int rc = batch_run(ctx, ctx->job_batch, &ctx->job_params, std::move(ctx->job_matrix), ctx->job_align_mode, ctx->job_long_reads, ctx->job_band);
         ctx->job_rc = rc;
         ctx->job_err = rc ? swmi_last_error() : "";
         { std::lock_guard<std::mutex> lk(ctx->job_mu); ctx->job_state.store(2, std::memory_order_release); }
@@ -864,6 +921,7 @@ extern "C" int swmi_batch_run_async(swmi_ctx *ctx, swmi_batch *b, const swmi_par
     ctx->job_matrix = ctx_matrix(ctx);                 // (the matrix set now, whatever is set while the run is in flight)
     ctx->job_align_mode = ctx->align_mode;             // (likewise)
     ctx->job_long_reads = ctx->long_reads;
+    ctx->job_band = ctx->band;
     ctx->job_delay_us = ctx->dbg_async_delay_us;
     { std::lock_guard<std::mutex> lk(ctx->job_mu); ctx->job_state.store(1, std::memory_order_release); }
     ctx->job_cv.notify_all();

@@ -174,6 +174,8 @@ def _rank_main(args):
             ctx.set_option("align_mode", _ALIGN_MODES[args.align_mode])    # realignment of the winners both run on this context
         if args.long_reads:                                 # reads longer than 1024 bases on the affine kernels
             ctx.set_option("long_reads", 1)
+        if args.band:                                       # ... inside a band around the diagonal
+            ctx.set_option("band", args.band)
         if args.matrix:                                     # substitution scores on this rank's context (NCBI text format)
             from . import matrix as _matrix
             ctx.set_score_matrix(_matrix.load(args.matrix))
@@ -217,6 +219,9 @@ def _parser():
     ap.add_argument("--long-reads", action="store_true",
                     help="let the affine kernels (gapOpen, --matrix, --align-mode) take reads longer than 1024 bases, swept in strips "
                          "of 1024 rows (option long_reads); without it such a read is refused")
+    ap.add_argument("--band", type=int, default=0, metavar="W",
+                    help="with --long-reads: align a read longer than 1024 bases inside the band |j - i| <= W only, rounded outwards to "
+                         "strips of 1024 rows (option band); runs on the affine kernels.  0 (the default): no band")
     ap.add_argument("--tie", choices=("serial", "strict"), default="serial",
                     help="serial: SmithWaterman's aligner (NoDistribution, DistributeReference); strict: DistributedSW's (DistributeAlgorithm)")
     ap.add_argument("--stream-chunk-bytes", type=int, default=512 << 10, help="sequence bytes per streamed chunk")

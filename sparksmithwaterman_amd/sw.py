@@ -35,12 +35,13 @@ def _algo(align_scores, align_types):
 
 
 @_contextlib.contextmanager
-def _scores(ctx, align_scores, align_mode=None, long_reads=None):
+def _scores(ctx, align_scores, align_mode=None, long_reads=None, band=None):
     """alignScores {match, mismatch, gap} or {match, mismatch, gap, gapOpen}: yields the three entries make_params takes
     and, for four, sets the context's "gap_open" for the call (affine gaps: a gap of length k costs gapOpen + k * gap).
     align_mode (ALIGN_LOCAL / ALIGN_FIT / ALIGN_GLOBAL, or None: the context's own) is set for the call in the same way;
     long_reads (True / False, or None: the context's own) likewise sets option "long_reads": reads longer than 1024 bases on the
-    affine kernels.  The options are put back afterwards."""
+    affine kernels; band (a half-width, 0: none, or None: the context's own) sets option "band".  The options are put back
+    afterwards."""
     sc = tuple(int(x) for x in align_scores)
     if len(sc) == 4 and sc[3] > 0:
         raise ValueError("gapOpen (alignScores[3]) must be <= 0, got %d" % sc[3])
@@ -57,6 +58,9 @@ def _scores(ctx, align_scores, align_mode=None, long_reads=None):
         if long_reads is not None:
             restore.append(("long_reads", ctx.options.get("long_reads", 0)))
             ctx.set_option("long_reads", 1 if long_reads else 0)
+        if band is not None:
+            restore.append(("band", ctx.options.get("band", 0)))
+            ctx.set_option("band", int(band))
         yield sc[:3]
     finally:
         for name, prev in reversed(restore):
@@ -68,15 +72,16 @@ class SmithWaterman:
         """Function3<String[], int[], char[], Tuple2<Integer, ArrayList<Tuple2<Integer,String[]>>>>."""
         tie_mode = _capi.TIE_SERIAL
 
-        def __init__(self, context=None, align_mode=None, long_reads=None):
+        def __init__(self, context=None, align_mode=None, long_reads=None, band=None):
             self._ctx = context
             self._align_mode = align_mode       # ALIGN_FIT / ALIGN_GLOBAL: end-to-end alignment (option "align_mode")
             self._long_reads = long_reads       # True: reads longer than 1024 bases on the affine kernels (option "long_reads")
+            self._band = band                   # a half-width: such reads inside the band |j - i| <= band only (option "band")
 
         def call(self, seqs, alignScores=None, alignTypes=None):
             ctx = self._ctx or default_context()
             sc, ty = _algo(alignScores, alignTypes)
-            with _scores(ctx, sc, self._align_mode, self._long_reads) as sc3:
+            with _scores(ctx, sc, self._align_mode, self._long_reads, self._band) as sc3:
                 b = ctx.upload([seqs[0]], [seqs[1]])
                 try:
                     b.run(make_params(sc3, ty, self.tie_mode))
@@ -106,8 +111,9 @@ class Distribution:
         together; results come back in input order, each exactly what MapRef.call returns.
         """
 
-        def __init__(self, context=None, tie_mode=_capi.TIE_SERIAL, align_mode=None, long_reads=None):
+        def __init__(self, context=None, tie_mode=_capi.TIE_SERIAL, align_mode=None, long_reads=None, band=None):
             self._ctx = context
+            self._band = band
             self._tie = tie_mode
             self._align_mode = align_mode
             self._long_reads = long_reads
@@ -123,7 +129,7 @@ class Distribution:
             for idxs in groups.values():
                 _, reads, algo = tuples[idxs[0]]
                 sc, ty = _algo(*(algo if algo is not None else (None, None)))
-                with _scores(ctx, sc, self._align_mode, self._long_reads) as sc3:
+                with _scores(ctx, sc, self._align_mode, self._long_reads, self._band) as sc3:
                     b = ctx.upload([tuples[i][0][1] for i in idxs], list(reads))
                     try:
                         b.run(make_params(sc3, ty, self._tie))
@@ -136,8 +142,8 @@ class Distribution:
     class MapRef:
         """PairFunction<Tuple3<String[], ArrayList<String>, Tuple2<int[],char[]>>, Integer, Tuple2<...>>."""
 
-        def __init__(self, context=None, tie_mode=_capi.TIE_SERIAL, align_mode=None, long_reads=None):
-            self._mp = Distribution.MapPartition(context, tie_mode, align_mode, long_reads)
+        def __init__(self, context=None, tie_mode=_capi.TIE_SERIAL, align_mode=None, long_reads=None, band=None):
+            self._mp = Distribution.MapPartition(context, tie_mode, align_mode, long_reads, band)
 
         def call(self, tuple3):
             return self._mp.call([tuple3])[0]
@@ -182,8 +188,9 @@ class _FileDriver:
     REF_DIR, IN_DIR = "/home/ubuntu/project/reference", "/home/ubuntu/project/input"   # :43-44
     OUT_DIR = "/home/ubuntu/project/output/reference"                 # :50
 
-    def __init__(self, context=None, tie_mode=_capi.TIE_SERIAL, align_mode=None, long_reads=None):
+    def __init__(self, context=None, tie_mode=_capi.TIE_SERIAL, align_mode=None, long_reads=None, band=None):
         self._ctx = context
+        self._band = band
         self._tie = tie_mode
         self._align_mode = align_mode
         self._long_reads = long_reads
@@ -200,7 +207,7 @@ class _FileDriver:
             out_ext = ioArgs[5] if ioArgs[5] is not None else out_ext
         sc, ty = _algo(*(algoArgs if algoArgs is not None else (None, None)))
         ctx = self._ctx or default_context()
-        with _scores(ctx, sc, self._align_mode, self._long_reads) as sc3:
+        with _scores(ctx, sc, self._align_mode, self._long_reads, self._band) as sc3:
             return self._run(ctx, make_params(sc3, ty, self._tie), ref_dir, in_dir, delim, out_dir, out_name, out_ext)
 
     def _run(self, ctx, params, ref_dir, in_dir, delim, out_dir, out_name, out_ext):
