@@ -52,11 +52,18 @@
 // sw_affine_traceback_long[_fit|_global]_kernel: the same walks over the strips' fields: row i is in strip (i - 1) / 1024; a
 //   step up from a strip's first row goes to lane 63, row slot 15 of the strip above; the LDS tile is keyed by the strip too.
 //
-// How the 24 kernels are made: the 18 sweeps are aff_sweep_entry<RLO, RHI, MATRIX, MODE, LONG> over one block function
-//   (aff_block8); the 6 tracebacks are aff_traceback<MODE, LONG>, where !LONG is the walk with one strip.  One macro defines
-//   the sweeps, one the tracebacks; the launchers pick a kernel from a table.  The per-pair sweep is two thin bodies,
-//   aff_sweep_pair and aff_sweep_long_pair, over shared pieces: vrows, the cell list and the epilogue as functions of values,
-//   the row load and the block store as text (DESIGN.md 8e says why).
+// sw_affine_sweep_band[_fit|_global][_matrix]_kernel, sw_affine_traceback_band[_fit|_global]_kernel: the strip kernels under
+//   option "band" (half-width w, DESIGN.md "Banded alignment"): strip s sweeps the window of columns swmi_aff_band_lo(s, w) ..
+//   swmi_aff_band_hi(s, n, w) only and leaves that window's field; a cell outside the band reads as 0 (local) or
+//   SWMI_AFF_BAND_NEG; the walk takes a strip's window origin and block count from (s, n, w).  The half-width is one more
+//   scalar kernel argument.
+//
+// How the 33 kernels are made: the 24 sweeps are aff_sweep_entry<RLO, RHI, MATRIX, MODE, LONG, BAND> over one block function
+//   (aff_block8); the 9 tracebacks are aff_traceback<MODE, LONG, BAND>, where !LONG is the walk with one strip and !BAND the
+//   walk whose windows are the whole reference.  One macro defines the sweeps, one the tracebacks; the launchers pick a kernel
+//   from typed tables.  The per-pair sweep is two thin bodies, aff_sweep_pair and aff_sweep_long_pair<.., BAND> (the one strip
+//   loop, banded or not), over shared pieces: vrows and the cell list as functions of values, the row load, the block store
+//   and the epilogue as text (DESIGN.md 8e and 8f say why).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "swmi_device.h"
@@ -259,24 +266,6 @@ __device__ __forceinline__ AffCells aff_cell_list(const FillArgs &A, const PairD
     return AffCells{A.cells + cbase, ccap};
 }
 
-template <int MODE>
-__device__ __forceinline__ void aff_pair_out(const FillArgs &A, const PairDesc pd, const uint32_t lane, const int thr, const uint32_t cnt,
-                                             const uint32_t ccap, const uint32_t m, const uint32_t n) {
-    if (lane == 0) {
-        PairOut po;
-        if (MODE == AFF_LOCAL && cnt == 0u) {                    // maximum 0: every one of the m*n cells ties (SmithWaterman.java:154)
-            po.score = 0;
-            po.flags = SWMI_F_DEGENERATE;
-            po.n_cells = (uint64_t)m * n;
-        } else {
-            po.score = thr;
-            po.flags = cnt > ccap ? SWMI_F_CELL_OVF : 0u;
-            po.n_cells = cnt;
-        }
-        A.out[pd.out_id] = po;
-    }
-}
-
 // The two pieces that read or write the lane's state S are shared as TEXT, not as functions.  As an inlined function -- handed
 // S, its arrays, a pointer to them, or one row at a time by value -- either one changes the register allocation of the sweeps
 // (DESIGN.md 8e); the same statements expanded in place cannot.  Both expect R, MATRIX, MODE, S, A, o and the names below.
@@ -304,6 +293,23 @@ __device__ __forceinline__ void aff_pair_out(const FillArgs &A, const PairDesc p
 #define AFF_STORE_BLOCK                                                                                       \
     uint32_t *__restrict__ dst = dir + (uint64_t)w * R * WAVE + lane;                                         \
     _Pragma("unroll") for (int k = 0; k < R; ++k) dst[k * WAVE] = S.acc[k];
+// AFF_PAIR_OUT(NCELLS) (lane, pd, ccap): the pair's PairOut.  NCELLS is what the degenerate case counts -- the pair's m * n cells
+//   or, under option "band", those inside the band -- and is evaluated in that branch only.  Text as well: as a function that
+//   takes the count as a value it changes the short local sweeps, as one that picks it inside the banded local ones
+#define AFF_PAIR_OUT(NCELLS)                                                                                  \
+    if (lane == 0) {                                                                                          \
+        PairOut po;                                                                                           \
+        if (MODE == AFF_LOCAL && S.cnt == 0u) {     /* maximum 0: every cell ties (SmithWaterman.java:154) */ \
+            po.score = 0;                                                                                     \
+            po.flags = SWMI_F_DEGENERATE;                                                                     \
+            po.n_cells = NCELLS;                                                                              \
+        } else {                                                                                              \
+            po.score = S.thr;                                                                                 \
+            po.flags = S.cnt > ccap ? SWMI_F_CELL_OVF : 0u;                                                   \
+            po.n_cells = S.cnt;                                                                               \
+        }                                                                                                     \
+        A.out[pd.out_id] = po;                                                                                \
+    }
 
 template <int R, bool STRICT, bool MATRIX, int MODE>
 __device__ __forceinline__ void aff_sweep_pair(const FillArgs &A, const int o, const PairDesc pd, const uint32_t lane, const uint32_t nn) {
@@ -333,130 +339,102 @@ __device__ __forceinline__ void aff_sweep_pair(const FillArgs &A, const int o, c
         aff_block8<R, STRICT, MATRIX, MODE>(S, rw, t0, lane, n, row0, vrows, o, A.gap, A.match, A.mismatch, cells, ccap);
         AFF_STORE_BLOCK
     }
-    aff_pair_out<MODE>(A, pd, lane, S.thr, S.cnt, ccap, m, n);
+    AFF_PAIR_OUT((uint64_t)m * n)
 }
 
-// A read of more than 1024 bases, strip after strip (R = 16 in every strip), over the same pieces as aff_sweep_pair.
-// The seam row is rewritten IN PLACE.  In a strip, lane 0 is at column t + 1 at step t and its block of 8 columns is loaded at
-// the block's first step, so a load at step t touches columns >= t + 1; lane 63 is at column t - 62 at step t.  A column is
-// therefore read (by this strip) at least 63 steps before this strip overwrites it, and what it reads was written by the strip
-// above, whose stores all precede the fence between the strips.  Vector loads and stores only: the row is rewritten by
-// vector stores of this kernel, which the scalar cache does not see.
-template <bool STRICT, bool MATRIX, int MODE>
-__device__ __forceinline__ void aff_sweep_long_pair(const FillArgs &A, const int o, const PairDesc pd, const uint32_t lane, const uint32_t nn) {
-    constexpr int R = SWMI_AFF_RMAX;
-    const SeqDesc rd = A.refs[pd.ref_id];
-    const SeqDesc qd = A.reads[pd.read_id];
-    const uint32_t n = rd.len, m = qd.len;
-    const uint32_t *__restrict__ refw = A.seqw + rd.boff;
-    const uint32_t *__restrict__ readw = A.seqw + qd.boff;
-    const uint32_t NS = swmi_aff_strips(m), W = swmi_aff_strip_blocks(n);
-    const AffCells cl = aff_cell_list(A, pd);
-    const uint32_t ccap = cl.cap;
-    uint2 *__restrict__ cells = cl.p;
-    AffSeam Z;
-    Z.row = reinterpret_cast<int2 *>(A.seam + pd.seam_off);
-
-    AffState<R> S;
-    S.thr = MODE == AFF_LOCAL ? 1 : INT32_MIN; S.cnt = 0;       // (wave-uniform: they live on across the strips)
-    for (uint32_t sx = 0; sx < NS; ++sx) {
-        const uint32_t row0 = sx * SWMI_AFF_MAX_READ + lane * R;             // global index of the lane's first row, less 1
-        const uint32_t vrows = aff_vrows<R, MODE>(m, row0);               // (row m is in the last strip)
-        AFF_LOAD_ROWS
-        S.rb = 0; S.f_last = 0;
-        // nh_prev of lane 0: H(1024 * sx, 0)
-        S.nh_prev = MODE != AFF_LOCAL && sx ? o + (int)(sx * SWMI_AFF_MAX_READ) * A.gap : 0;
-        Z.wlane = sx + 1u < NS ? 63u : 0xFFFFFFFFu;
-        uint32_t *__restrict__ dir = A.dir + pd.dir_off + (uint64_t)sx * swmi_aff_strip_words(n);
-        // the strip above has written the whole seam row: its stores are in memory before this strip loads any of it
-        if (sx) __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent");
-        for (uint32_t w = 0; w < W; ++w) {
-            const uint32_t t0 = 8u * w;
-            const uint2 rw = *reinterpret_cast<const uint2 *>(refw + (t0 >> 2));
-            // lane 0's feed from above at columns t0 + 1 .. t0 + 8, one column per lane 0..7: row 0 of the mode (as in
-            // aff_block8), below it the seam -- the true F, not the H + o stand-in of row 0
-            const uint32_t c = t0 + lane;
-            Z.h = MODE == AFF_GLOBAL ? (int)((uint32_t)o + (c + 1u) * (uint32_t)A.gap) : 0;
-            Z.f = MODE == AFF_LOCAL ? 0 : (int)((uint32_t)Z.h + (uint32_t)o);
-            if (sx) {
-                int2 v = make_int2(0, 0);
-                if (lane < 8u && c < n) v = Z.row[c];
-                Z.h = v.x; Z.f = v.y;
-            }
-#pragma unroll
-            for (int k = 0; k < R; ++k) S.acc[k] = 0u;
-            aff_block8<R, STRICT, MATRIX, MODE, true>(S, rw, t0, lane, n, row0, vrows, o, A.gap, A.match, A.mismatch, cells, ccap, Z);
-            AFF_STORE_BLOCK
-        }
-    }
-    aff_pair_out<MODE>(A, pd, lane, S.thr, S.cnt, ccap, m, n);
-}
-
-// The strip sweep under option "band" (half-width wb >= 1): strip sx sweeps the window of columns clo .. chi =
-// swmi_aff_band_lo / _hi (sx) and leaves the field of a (1024, chi - clo + 1) pair behind the fields of the strips above.
-// aff_block8 counts columns from the window's first one; only what surrounds it differs from aff_sweep_long_pair:
+// A read of more than 1024 bases, strip after strip (R = 16 in every strip), over the same pieces as aff_sweep_pair.  Strip sx
+// sweeps a WINDOW of columns clo .. chi and leaves the field of a (1024, chi - clo + 1) pair behind the fields of the strips
+// above; aff_block8 counts columns from the window's first one.  !BAND: the window is the whole reference -- clo = 1, chi = n,
+// the same W blocks in every strip -- and everything that depends on it is a constant that folds away.
+// BAND (option "band", half-width wb >= 1): clo, chi = swmi_aff_band_lo / _hi (sx), and
 //   - a cell outside the band reads as OUT: 0 in local mode (what the clamps make of -inf), SWMI_AFF_BAND_NEG otherwise
 //   - column clo - 1 of the strip's rows is the mode's column 0 when clo = 1, else OUT (H and E)
 //   - nh_prev of lane 0, the diagonal of the strip's first row at column clo, is H(1024 sx, clo - 1): the mode's value when
 //     clo = 1, else the seam's -- the strip above wrote it, clo(sx) - 1 >= clo(sx - 1)
 //   - lane 0's feed from above is the seam up to column chi(sx - 1), the last one the strip above wrote, and OUT beyond: the
-//     seam words there are stale
+//     seam words there are stale (!BAND: every column of the seam is the strip above's)
 //   - the reference words are read from byte clo - 1 of the image, which is not 8-aligned: three dwords, two byte-aligns
-// The seam row is still rewritten in place, and the argument of aff_sweep_long_pair holds relative to the window's origin: in
-// strip sx lane 0 is at column clo + t at step t and loads the seam of columns clo + t0 .. clo + t0 + 7 at step t0 <= t, lane 63
-// is at column clo + t - 63: a column is read at least 63 steps before this strip overwrites it.  Column clo - 1 (nh_prev) is
-// left of the window and not written by this strip at all.  What strip sx reads, columns clo(sx) - 1 .. chi(sx - 1), lies inside
-// clo(sx - 1) .. chi(sx - 1), all written by the strip above before the fence.
-template <bool STRICT, bool MATRIX, int MODE>
-__device__ __forceinline__ void aff_sweep_band_pair(const FillArgs &A, const int o, const PairDesc pd, const uint32_t lane, const uint32_t nn,
+//   - the strips' fields are of unequal size: the field pointer runs
+// The seam row is rewritten IN PLACE.  In strip sx lane 0 is at column clo + t at step t and loads the seam of its block's 8
+// columns clo + t0 .. clo + t0 + 7 at the block's first step t0 <= t, so a load at step t touches columns >= clo + t; lane 63 is
+// at column clo + t - 63 at step t.  A column is therefore read (by this strip) at least 63 steps before this strip overwrites
+// it.  Column clo - 1 (nh_prev) is left of the window and not written by this strip at all.  What strip sx reads, columns
+// clo(sx) - 1 .. chi(sx - 1), lies inside clo(sx - 1) .. chi(sx - 1), all written by the strip above, whose stores all precede
+// the fence between the strips (clo = 1: columns 1 .. n, and column 0 is the mode's).  Vector loads and stores only: the row is
+// rewritten by vector stores of this kernel, which the scalar cache does not see.
+template <bool STRICT, bool MATRIX, int MODE, bool BAND>
+__device__ __forceinline__ void aff_sweep_long_pair(const FillArgs &A, const int o, const PairDesc pd, const uint32_t lane, const uint32_t nn,
                                                     const uint32_t wb) {
     constexpr int R = SWMI_AFF_RMAX;
-    constexpr int OUT = MODE == AFF_LOCAL ? 0 : SWMI_AFF_BAND_NEG;
+    constexpr int OUT = BAND && MODE != AFF_LOCAL ? SWMI_AFF_BAND_NEG : 0;
     const SeqDesc rd = A.refs[pd.ref_id];
     const SeqDesc qd = A.reads[pd.read_id];
     const uint32_t n = rd.len, m = qd.len;
     const uint32_t *__restrict__ refw = A.seqw + rd.boff;
     const uint32_t *__restrict__ readw = A.seqw + qd.boff;
     const uint32_t NS = swmi_aff_strips(m);
+    uint32_t W = BAND ? 0u : swmi_aff_strip_blocks(n);           // (BAND: of strip sx, set with its window)
     const AffCells cl = aff_cell_list(A, pd);
     const uint32_t ccap = cl.cap;
     uint2 *__restrict__ cells = cl.p;
     int2 *const seam = reinterpret_cast<int2 *>(A.seam + pd.seam_off);
     AffSeam Z;
+    Z.row = seam;
     uint32_t *__restrict__ dir = A.dir + pd.dir_off;
-    uint64_t inband = 0ull;                                      // in-band cells with i <= m (the degenerate count)
+    uint64_t inband = 0ull;                                      // BAND: in-band cells with i <= m (the degenerate count)
 
     AffState<R> S;
-    S.thr = MODE == AFF_LOCAL ? 1 : INT32_MIN; S.cnt = 0;
+    S.thr = MODE == AFF_LOCAL ? 1 : INT32_MIN; S.cnt = 0;       // (wave-uniform: they live on across the strips)
     for (uint32_t sx = 0; sx < NS; ++sx) {
-        const uint32_t row0 = sx * SWMI_AFF_MAX_READ + lane * R;
-        const uint32_t vrows = aff_vrows<R, MODE>(m, row0);
-        const uint32_t clo = swmi_aff_band_lo(sx, wb), chi = swmi_aff_band_hi(sx, n, wb);
-        const uint32_t nw = chi - clo + 1u, W = swmi_aff_strip_blocks(nw);
-        const uint32_t seam_end = sx ? swmi_aff_band_hi(sx - 1u, n, wb) - (clo - 1u) : 0u;   // window columns the strip above wrote
-        const uint32_t srows = m - sx * SWMI_AFF_MAX_READ < SWMI_AFF_MAX_READ ? m - sx * SWMI_AFF_MAX_READ : SWMI_AFF_MAX_READ;
-        inband += (uint64_t)srows * nw;
+        const uint32_t row0 = sx * SWMI_AFF_MAX_READ + lane * R;             // global index of the lane's first row, less 1
+        const uint32_t vrows = aff_vrows<R, MODE>(m, row0);               // (row m is in the last strip)
+        uint32_t clo = 1u, nw = n, seam_end = n;                 // the window's first column and length; the window columns the strip above wrote
+        if constexpr (BAND) {
+            clo = swmi_aff_band_lo(sx, wb);
+            nw = swmi_aff_band_hi(sx, n, wb) - clo + 1u;
+            W = swmi_aff_strip_blocks(nw);
+            seam_end = sx ? swmi_aff_band_hi(sx - 1u, n, wb) - (clo - 1u) : 0u;
+            const uint32_t srows = m - sx * SWMI_AFF_MAX_READ < SWMI_AFF_MAX_READ ? m - sx * SWMI_AFF_MAX_READ : SWMI_AFF_MAX_READ;
+            inband += (uint64_t)srows * nw;
+        }
         AFF_LOAD_ROWS
-        if (clo > 1u) {
+        if constexpr (BAND) {
+            if (clo > 1u) {
 #pragma unroll
-            for (int k = 0; k < R; ++k) { S.h[k] = OUT; S.e[k] = OUT; }
+                for (int k = 0; k < R; ++k) { S.h[k] = OUT; S.e[k] = OUT; }
+            }
         }
         S.rb = 0; S.f_last = 0;
-        Z.row = seam + (clo - 1u);
-        Z.coff = clo - 1u;
+        // nh_prev of lane 0: H(1024 * sx, clo - 1)
+        if constexpr (!BAND) S.nh_prev = MODE != AFF_LOCAL && sx ? o + (int)(sx * SWMI_AFF_MAX_READ) * A.gap : 0;
+        if constexpr (BAND) {
+            Z.row = seam + (clo - 1u);
+            Z.coff = clo - 1u;
+        }
         Z.wlane = sx + 1u < NS ? 63u : 0xFFFFFFFFu;
+        if constexpr (!BAND) dir = A.dir + pd.dir_off + (uint64_t)sx * swmi_aff_strip_words(n);
+        // the strip above has written its window of the seam row: its stores are in memory before this strip loads any of it
         if (sx) __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent");
-        if (clo > 1u) S.nh_prev = seam[clo - 2u].x;                                // (a vector load, behind the fence)
-        else S.nh_prev = MODE != AFF_LOCAL && sx ? o + (int)(sx * SWMI_AFF_MAX_READ) * A.gap : 0;
-        const uint32_t boff = clo - 1u, bsh = boff & 3u;
+        if constexpr (BAND) {
+            if (clo > 1u) S.nh_prev = seam[clo - 2u].x;                            // (a vector load, behind the fence)
+            else S.nh_prev = MODE != AFF_LOCAL && sx ? o + (int)(sx * SWMI_AFF_MAX_READ) * A.gap : 0;
+        }
+        const uint32_t boff = clo - 1u, bsh = boff & 3u;         // (BAND) the window's first byte of the image
         const uint32_t *__restrict__ refb = refw + (boff >> 2);
         for (uint32_t w = 0; w < W; ++w) {
             const uint32_t t0 = 8u * w;
-            // lane 0's 8 reference bases from byte boff + t0 on (the image's padding covers the last block and the third dword)
-            const uint32_t r0 = refb[t0 >> 2], r1 = refb[(t0 >> 2) + 1u], r2 = refb[(t0 >> 2) + 2u];
-            const uint2 rw = make_uint2(__builtin_amdgcn_alignbyte(r1, r0, bsh), __builtin_amdgcn_alignbyte(r2, r1, bsh));
-            const uint32_t c = t0 + lane;                        // window column - 1 of lanes 0..7
-            Z.h = MODE == AFF_GLOBAL ? (int)((uint32_t)o + (c + 1u) * (uint32_t)A.gap) : 0;      // (strip 0: clo = 1, row 0 of the mode)
+            // lane 0's 8 reference bases, from byte boff + t0 on (the image's padding covers the last block and the third dword)
+            uint2 rw;
+            if constexpr (BAND) {
+                const uint32_t r0 = refb[t0 >> 2], r1 = refb[(t0 >> 2) + 1u], r2 = refb[(t0 >> 2) + 2u];
+                rw = make_uint2(__builtin_amdgcn_alignbyte(r1, r0, bsh), __builtin_amdgcn_alignbyte(r2, r1, bsh));
+            } else {
+                rw = *reinterpret_cast<const uint2 *>(refb + (t0 >> 2));
+            }
+            // lane 0's feed from above at window columns t0 + 1 .. t0 + 8, one column per lane 0..7: row 0 of the mode (as in
+            // aff_block8; strip 0 has clo = 1), below it the seam -- the true F, not the H + o stand-in of row 0
+            const uint32_t c = t0 + lane;
+            Z.h = MODE == AFF_GLOBAL ? (int)((uint32_t)o + (c + 1u) * (uint32_t)A.gap) : 0;
             Z.f = MODE == AFF_LOCAL ? 0 : (int)((uint32_t)Z.h + (uint32_t)o);
             if (sx) {
                 int2 v = make_int2(OUT, OUT);
@@ -465,28 +443,17 @@ __device__ __forceinline__ void aff_sweep_band_pair(const FillArgs &A, const int
             }
 #pragma unroll
             for (int k = 0; k < R; ++k) S.acc[k] = 0u;
-            aff_block8<R, STRICT, MATRIX, MODE, true, true>(S, rw, t0, lane, nw, row0, vrows, o, A.gap, A.match, A.mismatch, cells, ccap, Z);
+            aff_block8<R, STRICT, MATRIX, MODE, true, BAND>(S, rw, t0, lane, nw, row0, vrows, o, A.gap, A.match, A.mismatch, cells, ccap, Z);
             AFF_STORE_BLOCK
         }
-        dir += (uint64_t)W * R * WAVE;
+        if constexpr (BAND) dir += (uint64_t)W * R * WAVE;
     }
-    if (lane == 0) {
-        PairOut po;
-        if (MODE == AFF_LOCAL && S.cnt == 0u) {                  // maximum 0: every in-band cell ties
-            po.score = 0;
-            po.flags = SWMI_F_DEGENERATE;
-            po.n_cells = inband;
-        } else {
-            po.score = S.thr;
-            po.flags = S.cnt > ccap ? SWMI_F_CELL_OVF : 0u;
-            po.n_cells = S.cnt;
-        }
-        A.out[pd.out_id] = po;
-    }
+    AFF_PAIR_OUT(BAND ? inband : (uint64_t)m * n)
 }
 
 #undef AFF_LOAD_ROWS
 #undef AFF_STORE_BLOCK
+#undef AFF_PAIR_OUT
 
 // RLO..RHI: the rows per lane this instantiation of the kernel takes (the others' registers would cap its occupancy)
 template <int RLO, int RHI, bool STRICT, bool MATRIX, int MODE>
@@ -519,13 +486,8 @@ __device__ __forceinline__ void aff_sweep_entry(const FillArgs &A, const int o, 
     const PairDesc pd = A.pairs[pair];
     if constexpr (LONG) {
         if (uni(A.reads[pd.read_id].len) <= SWMI_AFF_MAX_READ) return;
-        if constexpr (BAND) {
-            if (A.strict) aff_sweep_band_pair<true, MATRIX, MODE>(A, o, pd, lane, nn, wb);
-            else          aff_sweep_band_pair<false, MATRIX, MODE>(A, o, pd, lane, nn, wb);
-            return;
-        }
-        if (A.strict) aff_sweep_long_pair<true, MATRIX, MODE>(A, o, pd, lane, nn);
-        else          aff_sweep_long_pair<false, MATRIX, MODE>(A, o, pd, lane, nn);
+        if (A.strict) aff_sweep_long_pair<true, MATRIX, MODE, BAND>(A, o, pd, lane, nn, wb);
+        else          aff_sweep_long_pair<false, MATRIX, MODE, BAND>(A, o, pd, lane, nn, wb);
         return;
     }
     const uint32_t R = uni(swmi_aff_rows_per_lane(A.reads[pd.read_id].len));
@@ -536,9 +498,9 @@ __device__ __forceinline__ void aff_sweep_entry(const FillArgs &A, const int o, 
 
 }  // namespace
 
-// The 18 sweep kernels: local, fit and global (option "align_mode"), each plain and with a score matrix (MATRIX = 0 / 1: the
-// two signatures), each narrow (R = 1..4), wide (R = 5..16) and long (option "long_reads": RLO, RHI unused).
-// BAND = 0 / 1: the six banded strip sweeps (option "band") take the half-width as one more scalar argument
+// The 24 sweep kernels: local, fit and global (option "align_mode"), each plain and with a score matrix (MATRIX = 0 / 1), each
+// narrow (R = 1..4), wide (R = 5..16), long (option "long_reads": RLO, RHI unused) and banded long (option "band", BAND = 1:
+// the half-width is one more scalar argument).  MATRIX and BAND make the four signatures.
 #define AFF_SWEEP_PARAMS_00 const FillArgs A, const int gap_open
 #define AFF_SWEEP_PARAMS_10 const FillArgs A, const int gap_open, const uint32_t *mat, const uint32_t nn
 #define AFF_SWEEP_PARAMS_01 const FillArgs A, const int gap_open, const uint32_t band
@@ -547,37 +509,35 @@ __device__ __forceinline__ void aff_sweep_entry(const FillArgs &A, const int o, 
 #define AFF_SWEEP_ARGS_10 A, gap_open, mat, nn
 #define AFF_SWEEP_ARGS_01 A, gap_open, nullptr, 0u, band
 #define AFF_SWEEP_ARGS_11 A, gap_open, mat, nn, band
-#define AFF_SWEEP_KERNEL_B(name, RLO, RHI, MATRIX, MODE, LONG, BAND)                                           \
+#define AFF_SWEEP_KERNEL(name, RLO, RHI, MATRIX, MODE, LONG, BAND)                                             \
     extern "C" __global__ void __launch_bounds__(WAVE * AFF_WAVES) name(AFF_SWEEP_PARAMS_##MATRIX##BAND) {    \
         aff_sweep_entry<RLO, RHI, MATRIX != 0, MODE, LONG, BAND != 0>(AFF_SWEEP_ARGS_##MATRIX##BAND);         \
     }
-#define AFF_SWEEP_KERNEL(name, RLO, RHI, MATRIX, MODE, LONG) AFF_SWEEP_KERNEL_B(name, RLO, RHI, MATRIX, MODE, LONG, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_kernel, 1, 4, 0, AFF_LOCAL, false)
-AFF_SWEEP_KERNEL(sw_affine_sweep_wide_kernel, 5, SWMI_AFF_RMAX, 0, AFF_LOCAL, false)
-AFF_SWEEP_KERNEL(sw_affine_sweep_long_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, AFF_LOCAL, true)
-AFF_SWEEP_KERNEL(sw_affine_sweep_matrix_kernel, 1, 4, 1, AFF_LOCAL, false)
-AFF_SWEEP_KERNEL(sw_affine_sweep_matrix_wide_kernel, 5, SWMI_AFF_RMAX, 1, AFF_LOCAL, false)
-AFF_SWEEP_KERNEL(sw_affine_sweep_long_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, AFF_LOCAL, true)
-AFF_SWEEP_KERNEL(sw_affine_sweep_fit_kernel, 1, 4, 0, AFF_FIT, false)
-AFF_SWEEP_KERNEL(sw_affine_sweep_fit_wide_kernel, 5, SWMI_AFF_RMAX, 0, AFF_FIT, false)
-AFF_SWEEP_KERNEL(sw_affine_sweep_long_fit_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, AFF_FIT, true)
-AFF_SWEEP_KERNEL(sw_affine_sweep_fit_matrix_kernel, 1, 4, 1, AFF_FIT, false)
-AFF_SWEEP_KERNEL(sw_affine_sweep_fit_matrix_wide_kernel, 5, SWMI_AFF_RMAX, 1, AFF_FIT, false)
-AFF_SWEEP_KERNEL(sw_affine_sweep_long_fit_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, AFF_FIT, true)
-AFF_SWEEP_KERNEL(sw_affine_sweep_global_kernel, 1, 4, 0, AFF_GLOBAL, false)
-AFF_SWEEP_KERNEL(sw_affine_sweep_global_wide_kernel, 5, SWMI_AFF_RMAX, 0, AFF_GLOBAL, false)
-AFF_SWEEP_KERNEL(sw_affine_sweep_long_global_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, AFF_GLOBAL, true)
-AFF_SWEEP_KERNEL(sw_affine_sweep_global_matrix_kernel, 1, 4, 1, AFF_GLOBAL, false)
-AFF_SWEEP_KERNEL(sw_affine_sweep_global_matrix_wide_kernel, 5, SWMI_AFF_RMAX, 1, AFF_GLOBAL, false)
-AFF_SWEEP_KERNEL(sw_affine_sweep_long_global_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, AFF_GLOBAL, true)
-AFF_SWEEP_KERNEL_B(sw_affine_sweep_band_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, AFF_LOCAL, true, 1)
-AFF_SWEEP_KERNEL_B(sw_affine_sweep_band_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, AFF_LOCAL, true, 1)
-AFF_SWEEP_KERNEL_B(sw_affine_sweep_band_fit_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, AFF_FIT, true, 1)
-AFF_SWEEP_KERNEL_B(sw_affine_sweep_band_fit_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, AFF_FIT, true, 1)
-AFF_SWEEP_KERNEL_B(sw_affine_sweep_band_global_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, AFF_GLOBAL, true, 1)
-AFF_SWEEP_KERNEL_B(sw_affine_sweep_band_global_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, AFF_GLOBAL, true, 1)
+AFF_SWEEP_KERNEL(sw_affine_sweep_kernel, 1, 4, 0, AFF_LOCAL, false, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_wide_kernel, 5, SWMI_AFF_RMAX, 0, AFF_LOCAL, false, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_long_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, AFF_LOCAL, true, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_matrix_kernel, 1, 4, 1, AFF_LOCAL, false, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_matrix_wide_kernel, 5, SWMI_AFF_RMAX, 1, AFF_LOCAL, false, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_long_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, AFF_LOCAL, true, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_fit_kernel, 1, 4, 0, AFF_FIT, false, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_fit_wide_kernel, 5, SWMI_AFF_RMAX, 0, AFF_FIT, false, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_long_fit_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, AFF_FIT, true, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_fit_matrix_kernel, 1, 4, 1, AFF_FIT, false, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_fit_matrix_wide_kernel, 5, SWMI_AFF_RMAX, 1, AFF_FIT, false, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_long_fit_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, AFF_FIT, true, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_global_kernel, 1, 4, 0, AFF_GLOBAL, false, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_global_wide_kernel, 5, SWMI_AFF_RMAX, 0, AFF_GLOBAL, false, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_long_global_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, AFF_GLOBAL, true, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_global_matrix_kernel, 1, 4, 1, AFF_GLOBAL, false, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_global_matrix_wide_kernel, 5, SWMI_AFF_RMAX, 1, AFF_GLOBAL, false, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_long_global_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, AFF_GLOBAL, true, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_band_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, AFF_LOCAL, true, 1)
+AFF_SWEEP_KERNEL(sw_affine_sweep_band_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, AFF_LOCAL, true, 1)
+AFF_SWEEP_KERNEL(sw_affine_sweep_band_fit_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, AFF_FIT, true, 1)
+AFF_SWEEP_KERNEL(sw_affine_sweep_band_fit_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, AFF_FIT, true, 1)
+AFF_SWEEP_KERNEL(sw_affine_sweep_band_global_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, AFF_GLOBAL, true, 1)
+AFF_SWEEP_KERNEL(sw_affine_sweep_band_global_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, AFF_GLOBAL, true, 1)
 #undef AFF_SWEEP_KERNEL
-#undef AFF_SWEEP_KERNEL_B
 #undef AFF_SWEEP_PARAMS_00
 #undef AFF_SWEEP_PARAMS_10
 #undef AFF_SWEEP_PARAMS_01
@@ -741,22 +701,20 @@ __device__ __forceinline__ void aff_traceback(const TraceArgs A, const uint32_t 
 #define AFF_TB_PARAMS_1 const TraceArgs A, const uint32_t tile_words, const uint32_t ops_words, const uint32_t band
 #define AFF_TB_ARGS_0 A, tile_words, ops_words
 #define AFF_TB_ARGS_1 A, tile_words, ops_words, band
-#define AFF_TRACEBACK_KERNEL_B(name, MODE, LONG, BAND)                                                      \
+#define AFF_TRACEBACK_KERNEL(name, MODE, LONG, BAND)                                                        \
     extern "C" __global__ void __launch_bounds__(WAVE) name(AFF_TB_PARAMS_##BAND) {                        \
         aff_traceback<MODE, LONG, BAND != 0>(AFF_TB_ARGS_##BAND);                                          \
     }
-#define AFF_TRACEBACK_KERNEL(name, MODE, LONG) AFF_TRACEBACK_KERNEL_B(name, MODE, LONG, 0)
-AFF_TRACEBACK_KERNEL(sw_affine_traceback_kernel, AFF_LOCAL, false)
-AFF_TRACEBACK_KERNEL(sw_affine_traceback_fit_kernel, AFF_FIT, false)
-AFF_TRACEBACK_KERNEL(sw_affine_traceback_global_kernel, AFF_GLOBAL, false)
-AFF_TRACEBACK_KERNEL(sw_affine_traceback_long_kernel, AFF_LOCAL, true)
-AFF_TRACEBACK_KERNEL(sw_affine_traceback_long_fit_kernel, AFF_FIT, true)
-AFF_TRACEBACK_KERNEL(sw_affine_traceback_long_global_kernel, AFF_GLOBAL, true)
-AFF_TRACEBACK_KERNEL_B(sw_affine_traceback_band_kernel, AFF_LOCAL, true, 1)
-AFF_TRACEBACK_KERNEL_B(sw_affine_traceback_band_fit_kernel, AFF_FIT, true, 1)
-AFF_TRACEBACK_KERNEL_B(sw_affine_traceback_band_global_kernel, AFF_GLOBAL, true, 1)
+AFF_TRACEBACK_KERNEL(sw_affine_traceback_kernel, AFF_LOCAL, false, 0)
+AFF_TRACEBACK_KERNEL(sw_affine_traceback_fit_kernel, AFF_FIT, false, 0)
+AFF_TRACEBACK_KERNEL(sw_affine_traceback_global_kernel, AFF_GLOBAL, false, 0)
+AFF_TRACEBACK_KERNEL(sw_affine_traceback_long_kernel, AFF_LOCAL, true, 0)
+AFF_TRACEBACK_KERNEL(sw_affine_traceback_long_fit_kernel, AFF_FIT, true, 0)
+AFF_TRACEBACK_KERNEL(sw_affine_traceback_long_global_kernel, AFF_GLOBAL, true, 0)
+AFF_TRACEBACK_KERNEL(sw_affine_traceback_band_kernel, AFF_LOCAL, true, 1)
+AFF_TRACEBACK_KERNEL(sw_affine_traceback_band_fit_kernel, AFF_FIT, true, 1)
+AFF_TRACEBACK_KERNEL(sw_affine_traceback_band_global_kernel, AFF_GLOBAL, true, 1)
 #undef AFF_TRACEBACK_KERNEL
-#undef AFF_TRACEBACK_KERNEL_B
 #undef AFF_TB_PARAMS_0
 #undef AFF_TB_PARAMS_1
 #undef AFF_TB_ARGS_0
@@ -774,17 +732,8 @@ extern "C" hipError_t swmi_launch_affine_sweep(const FillArgs *a, int32_t gap_op
                                                uint32_t r_min, uint32_t r_max, uint32_t long_reads, uint32_t band, hipStream_t st) {
     if (a->n_pairs == 0) return hipSuccess;
     if (align_mode > 2u || (mat && (nn < 2u || nn > SWMI_MAT_NN_MAX)) || band > SWMI_AFF_BAND_MAX) return hipErrorInvalidValue;
-    if (long_reads && band) {
-        static void (*const bplain[3])(FillArgs, int, uint32_t) = {
-            sw_affine_sweep_band_kernel, sw_affine_sweep_band_fit_kernel, sw_affine_sweep_band_global_kernel};
-        static void (*const bmatrix[3])(FillArgs, int, const uint32_t *, uint32_t, uint32_t) = {
-            sw_affine_sweep_band_matrix_kernel, sw_affine_sweep_band_fit_matrix_kernel, sw_affine_sweep_band_global_matrix_kernel};
-        const dim3 bgrid((a->n_pairs + AFF_WAVES - 1) / AFF_WAVES), bblock(WAVE * AFF_WAVES);
-        if (mat) hipLaunchKernelGGL(bmatrix[align_mode], bgrid, bblock, 0, st, *a, (int)gap_open, mat, nn, band);
-        else     hipLaunchKernelGGL(bplain[align_mode], bgrid, bblock, 0, st, *a, (int)gap_open, band);
-        return hipGetLastError();
-    }
-    // [narrow / wide / long][plain / matrix][align_mode]: one typed table per signature, so that a launch is checked against it
+    // [narrow / wide / long][align_mode], and [align_mode] of the banded long sweeps: one typed table per signature (plain /
+    // matrix, without / with the half-width), so that a launch is checked against its kernel's parameter list
     static void (*const plain[3][3])(FillArgs, int) = {
         {sw_affine_sweep_kernel, sw_affine_sweep_fit_kernel, sw_affine_sweep_global_kernel},
         {sw_affine_sweep_wide_kernel, sw_affine_sweep_fit_wide_kernel, sw_affine_sweep_global_wide_kernel},
@@ -793,11 +742,18 @@ extern "C" hipError_t swmi_launch_affine_sweep(const FillArgs *a, int32_t gap_op
         {sw_affine_sweep_matrix_kernel, sw_affine_sweep_fit_matrix_kernel, sw_affine_sweep_global_matrix_kernel},
         {sw_affine_sweep_matrix_wide_kernel, sw_affine_sweep_fit_matrix_wide_kernel, sw_affine_sweep_global_matrix_wide_kernel},
         {sw_affine_sweep_long_matrix_kernel, sw_affine_sweep_long_fit_matrix_kernel, sw_affine_sweep_long_global_matrix_kernel}};
+    static void (*const bplain[3])(FillArgs, int, uint32_t) = {
+        sw_affine_sweep_band_kernel, sw_affine_sweep_band_fit_kernel, sw_affine_sweep_band_global_kernel};
+    static void (*const bmatrix[3])(FillArgs, int, const uint32_t *, uint32_t, uint32_t) = {
+        sw_affine_sweep_band_matrix_kernel, sw_affine_sweep_band_fit_matrix_kernel, sw_affine_sweep_band_global_matrix_kernel};
     const dim3 grid((a->n_pairs + AFF_WAVES - 1) / AFF_WAVES), block(WAVE * AFF_WAVES);
+    const bool banded = long_reads && band;                       // (the long shape only)
     // (a launch's own error is what hipGetLastError returns below)
     const auto launch = [&](int shape) {
-        if (mat) hipLaunchKernelGGL(matrix[shape][align_mode], grid, block, 0, st, *a, (int)gap_open, mat, nn);
-        else     hipLaunchKernelGGL(plain[shape][align_mode], grid, block, 0, st, *a, (int)gap_open);
+        if (banded && mat) hipLaunchKernelGGL(bmatrix[align_mode], grid, block, 0, st, *a, (int)gap_open, mat, nn, band);
+        else if (banded)   hipLaunchKernelGGL(bplain[align_mode], grid, block, 0, st, *a, (int)gap_open, band);
+        else if (mat)      hipLaunchKernelGGL(matrix[shape][align_mode], grid, block, 0, st, *a, (int)gap_open, mat, nn);
+        else               hipLaunchKernelGGL(plain[shape][align_mode], grid, block, 0, st, *a, (int)gap_open);
     };
     if (long_reads) launch(2);
     else {
@@ -813,24 +769,25 @@ extern "C" hipError_t swmi_launch_affine_traceback(const TraceArgs *a, uint32_t 
                                                    uint32_t ops_words, hipStream_t st) {
     if (a->n_pairs == 0) return hipSuccess;
     if (align_mode > 2u || band > SWMI_AFF_BAND_MAX) return hipErrorInvalidValue;
-    static void (*const bkern[3])(TraceArgs, uint32_t, uint32_t, uint32_t) = {      // [align_mode]: the banded long walks
-        sw_affine_traceback_band_kernel, sw_affine_traceback_band_fit_kernel, sw_affine_traceback_band_global_kernel};
     static void (*const kern[2][3])(TraceArgs, uint32_t, uint32_t) = {      // [long_reads][align_mode]
         {sw_affine_traceback_kernel, sw_affine_traceback_fit_kernel, sw_affine_traceback_global_kernel},
         {sw_affine_traceback_long_kernel, sw_affine_traceback_long_fit_kernel, sw_affine_traceback_long_global_kernel}};
+    static void (*const bkern[3])(TraceArgs, uint32_t, uint32_t, uint32_t) = {      // [align_mode]: the banded long walks
+        sw_affine_traceback_band_kernel, sw_affine_traceback_band_fit_kernel, sw_affine_traceback_band_global_kernel};
     static const bool attrs = [] {
-        for (auto &row : kern)
-            for (auto *k : row)
-                (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        for (auto *k : bkern)
+        const auto big_lds = [](auto *k) {
             (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        };
+        for (int mode = 0; mode < 3; ++mode) { big_lds(kern[0][mode]); big_lds(kern[1][mode]); big_lds(bkern[mode]); }
         return true;
     }();
     (void)attrs;
     const size_t lds = ((size_t)tile_words + ops_words + SWMI_EMIT_SCRATCH_WORDS) * sizeof(uint32_t);
-    if (long_reads && band)
-        hipLaunchKernelGGL(bkern[align_mode], dim3(a->n_pairs, SWMI_AFF_TB_SLOTS), dim3(WAVE), lds, st, *a, tile_words, ops_words, band);
-    else
-        hipLaunchKernelGGL(kern[long_reads ? 1 : 0][align_mode], dim3(a->n_pairs, SWMI_AFF_TB_SLOTS), dim3(WAVE), lds, st, *a, tile_words, ops_words);
+    // (band...: the half-width, for the kernels that take it)
+    const auto launch = [&](auto *k, auto... band) {
+        hipLaunchKernelGGL(k, dim3(a->n_pairs, SWMI_AFF_TB_SLOTS), dim3(WAVE), lds, st, *a, tile_words, ops_words, band...);
+    };
+    if (long_reads && band) launch(bkern[align_mode], band);
+    else                    launch(kern[long_reads ? 1 : 0][align_mode]);
     return hipGetLastError();
 }

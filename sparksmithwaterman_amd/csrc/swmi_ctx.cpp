@@ -168,14 +168,14 @@ extern "C" int swmi_set_option(swmi_ctx *ctx, const char *name, int64_t value) {
     } else if (!strcmp(name, "align_mode")) {
         if (value != SWMI_ALIGN_LOCAL && value != SWMI_ALIGN_FIT && value != SWMI_ALIGN_GLOBAL)
             return fail(SWMI_ERR_INVALID, "align_mode must be 0 (local), 1 (fit) or 2 (global), got %lld", (long long)value);
-        ctx->align_mode = (int)value;
+        ctx->modes.align_mode = (int)value;
     } else if (!strcmp(name, "long_reads")) {
         if (value != 0 && value != 1) return fail(SWMI_ERR_INVALID, "long_reads must be 0 or 1, got %lld", (long long)value);
-        ctx->long_reads = (int)value;
+        ctx->modes.long_reads = (int)value;
     } else if (!strcmp(name, "band")) {
         if (value < 0 || value > (int64_t)SWMI_AFF_BAND_MAX)
             return fail(SWMI_ERR_INVALID, "band must be 0 (none) or a half-width of 1 .. %u columns, got %lld", SWMI_AFF_BAND_MAX, (long long)value);
-        ctx->band = (int)value;
+        ctx->modes.band = (int)value;
     } else if (!strcmp(name, "arena_words_per_pair")) {
         if (value < 1) return fail(SWMI_ERR_INVALID, "arena_words_per_pair out of range");
         ctx->arena_words_per_pair = (uint64_t)value;

@@ -22,6 +22,7 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <unordered_map>
 #include <vector>
 
@@ -108,6 +109,22 @@ struct ScoreMatrix {
     std::vector<uint32_t> image;            // the device image: swmi_aff_mat_words(n + 1) dwords (swmi_device.h)
 };
 
+// What a run takes as the context has it WHEN THE RUN IS ASKED FOR: swmi_batch_run_async records it at the call, a stream's
+// slots copy it at swmi_stream_open.  The context holds the plain part, RunModes, the plan key embeds it and every hand-over
+// copies it whole: a new option of this kind is a new member, its setter, its checks and its consumer.  (gap_open and affine
+// are not of this kind: a run reads them from the context when it STARTS, under ctx->mu -- an asynchronous run too.)
+struct __attribute__((visibility("hidden"))) RunModes {
+    int align_mode = SWMI_ALIGN_LOCAL;      // SWMI_ALIGN_FIT / _GLOBAL: end-to-end alignment, on the affine kernels
+    int long_reads = 0;                     // 1: the affine kernels take reads longer than 1024 bases, swept in strips (swmi.h)
+    int band = 0;                           // > 0: the half-width of the band the strip sweeps of such reads keep to (swmi.h); the affine kernels
+    bool operator==(const RunModes &o) const { return memcmp(this, &o, sizeof(RunModes)) == 0; }
+};
+static_assert(std::has_unique_object_representations_v<RunModes>, "RunModes is compared bytewise: no padding, no floating point");
+struct __attribute__((visibility("hidden"))) RunOptions {
+    RunModes modes;
+    std::shared_ptr<const ScoreMatrix> mat; // swmi_set_score_matrix (null: none); keeps the matrix's host image alive
+};
+
 // ------------------------------------------------------------------------------------------
 // context
 // ------------------------------------------------------------------------------------------
@@ -147,9 +164,7 @@ struct swmi_ctx {
     bool cell_cap_set = false;              // cell_cap given by the caller (otherwise small launches get longer lists)
     int32_t gap_open = 0;                   // affine gaps: a gap of length k costs gap_open + k * gap (0: linear)
     int affine = -1;                        // -1: the affine kernels (mode 3) when gap_open != 0; 1: always
-    int align_mode = SWMI_ALIGN_LOCAL;      // SWMI_ALIGN_FIT / _GLOBAL: end-to-end alignment, on the affine kernels
-    int long_reads = 0;                     // 1: the affine kernels take reads longer than 1024 bases, swept in strips (swmi.h)
-    int band = 0;                           // > 0: the half-width of the band the strip sweeps of such reads keep to (swmi.h); the affine kernels
+    RunModes modes;                         // options "align_mode", "long_reads" and "band"
     std::mutex mat_mu;                      // guards `matrix` (not ctx->mu: setting a matrix does not wait for a run)
     std::shared_ptr<const ScoreMatrix> matrix;   // swmi_set_score_matrix; a run with one takes the affine kernels
     // swmi_batch_run_async: one run in flight on the context's own host thread
@@ -159,19 +174,16 @@ struct swmi_ctx {
     std::atomic<int> job_state{0};          // 0 idle, 1 submitted, 2 finished, 3 quit
     swmi_batch *job_batch = nullptr;
     swmi_params job_params{};
-    std::shared_ptr<const ScoreMatrix> job_matrix;   // the matrix when swmi_batch_run_async was called
-    int job_align_mode = 0;                          // align_mode when swmi_batch_run_async was called
-    int job_long_reads = 0;                          // long_reads when swmi_batch_run_async was called
-    int job_band = 0;                                // band when swmi_batch_run_async was called
+    RunOptions job_opt;                              // run_options(ctx) when swmi_batch_run_async was called
     uint32_t job_delay_us = 0;                       // debug_async_delay_us when swmi_batch_run_async was called
     int job_rc = 0;
     std::string job_err;
 };
 
-// (in the header: every swmi_batch_run takes the context's matrix, and no per-step call may cross a unit boundary)
-static inline std::shared_ptr<const ScoreMatrix> ctx_matrix(swmi_ctx *ctx) {
+// the context's run options as set now (in the header: every swmi_batch_run takes them, and no per-step call may cross a unit boundary)
+static inline RunOptions run_options(swmi_ctx *ctx) {
     std::lock_guard<std::mutex> g(ctx->mat_mu);
-    return ctx->matrix;
+    return RunOptions{ctx->modes, ctx->matrix};
 }
 
 // one alignment as parsed from the arena
@@ -203,7 +215,8 @@ struct Work {            // one pair scheduled for a launch
 // Everything the plan of a chunk (swmi_plan.h: plan_chunk) depends on.  A run whose key equals the key of the plan the
 // batch holds -- a repeated run of the same chunk with the same parameters: bench.py's steps, a Spark job re-running a
 // partition -- skips the per-pair preparation and its uploads.  An input of the planner that is missing here gives a stale
-// plan on such a re-run: add it to BOTH the struct and operator==.
+// plan on such a re-run: add it to BOTH the struct and operator== -- unless it is one of the run's modes: a member added to
+// RunModes is part of the key as it is.
 struct __attribute__((visibility("hidden"))) PlanKey {
     bool valid = false;                     // false: no plan (a new upload, the sampled pre-pass: they reset the key)
     size_t lo = 0, hi = 0;                  // the chunk: work[lo, hi) ...
@@ -215,17 +228,15 @@ struct __attribute__((visibility("hidden"))) PlanKey {
     int resident = -1, tfused = -1;
     bool exact = false;                     // the exact-size re-run: no resident, no tfused pairs
     bool scores_only = false;
-    uint64_t mat_gen = 0;                   // the score matrix's generation (0: none): it bounds the paths
-    int align_mode = 0;                     // ... as does the alignment mode
-    int long_reads = 0;                     // option "long_reads" of the run
-    int band = 0;                           // option "band" of the run
+    uint64_t mat_gen = 0;                   // the score matrix's generation (0: none): it bounds the paths (not the matrix: a key keeps none alive)
+    RunModes modes;                         // the run's modes: the alignment mode bounds the paths too
     const void *d_pairs = nullptr;          // where the chunk's PairDesc image sits on the device, and its size
     size_t pairs_bytes = 0;
     bool operator==(const PlanKey &o) const {
         return valid == o.valid && lo == o.lo && hi == o.hi && work == o.work && memcmp(&params, &o.params, sizeof(swmi_params)) == 0 &&
                eff_mode == o.eff_mode && col_chunks == o.col_chunks && reverse_strips == o.reverse_strips && resident == o.resident &&
                tfused == o.tfused && exact == o.exact && scores_only == o.scores_only && mat_gen == o.mat_gen &&
-               align_mode == o.align_mode && long_reads == o.long_reads && band == o.band && d_pairs == o.d_pairs && pairs_bytes == o.pairs_bytes;
+               modes == o.modes && d_pairs == o.d_pairs && pairs_bytes == o.pairs_bytes;
     }
 };
 
@@ -280,11 +291,8 @@ struct swmi_batch {
     bool work_tfused = false;               // the schedule's workspace sizes leave room for sw_tfused_kernel's column checkpoints
     uint32_t eff_mode = 1;                  // pipeline of the current run (3: the affine kernels, swmi_affine.hip)
     int32_t gap_open = 0;                   // the context's gap_open when the run started (mode 3)
-    int align_mode = 0;                     // the context's align_mode when the run was asked for (mode 3)
-    int long_reads = 0;                     // ... and its long_reads
-    int band = 0;                           // ... and its band
-    std::shared_ptr<const ScoreMatrix> mat; // the score matrix of the current run (null: none); keeps its host image alive
-    DevBuf d_mat;                           // ... its device image, copied on the run's stream
+    RunOptions opt;                         // the context's run options when the run was asked for (mode 3)
+    DevBuf d_mat;                           // the device image of opt.mat, copied on the run's stream
     uint64_t d_mat_gen = 0;                 // generation of the matrix in d_mat (0: none)
     uint64_t work_cells = 0;
     std::vector<uint8_t> pairs_on_device;   // image of the PairDesc array currently in d_pairs

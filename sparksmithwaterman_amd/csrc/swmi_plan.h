@@ -277,7 +277,7 @@ static int plan_chunk(swmi_ctx *ctx, swmi_batch *b, const std::vector<Work> &wor
     if (b->eff_mode == 1) it.win_off.resize(np + 1);
     uint32_t pb_m = 0xFFFFFFFFu, pb_n = 0xFFFFFFFFu, pb_val = 0;
     // (a score matrix entry above match lets a positive path run longer: the bound takes the largest score of one move)
-    const int32_t smax = b->mat ? std::max(b->params.match, b->mat->max_entry) : b->params.match;
+    const int32_t smax = b->opt.mat ? std::max(b->params.match, b->opt.mat->max_entry) : b->params.match;
     for (size_t k = 0; k < np; k++) {
         const Work &w = work[lo + k];
         PairDesc d{};
@@ -296,7 +296,7 @@ static int plan_chunk(swmi_ctx *ctx, swmi_batch *b, const std::vector<Work> &wor
         else if (b->eff_mode == 1 && m_ > 64u * SWMI_RMAX && it.strip_items.size() < (1u << 30)) pl.take_strips(k, d, m_, n_);
         else if (pl.cols_fit(d, m_)) pl.take_cols(k, d, m_, n_);
         it.pd[k] = d;
-        if (m_ != pb_m || n_ != pb_n) { pb_m = m_; pb_n = n_; pb_val = (uint32_t)path_bound(n_, m_, b->params, smax, b->align_mode); }   // (runs of equal lengths)
+        if (m_ != pb_m || n_ != pb_n) { pb_m = m_; pb_n = n_; pb_val = (uint32_t)path_bound(n_, m_, b->params, smax, b->opt.modes.align_mode); }   // (runs of equal lengths)
         plan.max_path = std::max<uint32_t>(plan.max_path, pb_val);
         plan.max_read = std::max(plan.max_read, m_);
         if (m_ > SWMI_AFF_MAX_READ) { plan.aff_n_long++; continue; }      // (mode 3 with long_reads: the strip kernels' pair)
@@ -359,8 +359,7 @@ static int prepare_chunk(RunState &rs, const std::vector<Work> &work, size_t lo,
     key.col_chunks = ctx->col_chunks; key.reverse_strips = ctx->dbg_reverse_strips != 0;
     key.resident = ctx->resident; key.tfused = ctx->tfused;
     key.exact = cells_exact != nullptr; key.scores_only = ctx->scores_only != 0;
-    key.mat_gen = b->mat ? b->mat->gen : 0u; key.align_mode = b->align_mode;
-    key.long_reads = b->long_reads; key.band = b->band;
+    key.mat_gen = b->opt.mat ? b->opt.mat->gen : 0u; key.modes = b->opt.modes;
     key.d_pairs = b->d_pairs.p; key.pairs_bytes = np * sizeof(PairDesc);
     auto p1 = p0;
     if (key == b->plan_key) {

@@ -263,11 +263,11 @@ static int enqueue_launches(RunState &rs, Launch &L, const ResidentArgs &xa, con
             FillArgs fs = fa, fl = fa;
             fs.n_pairs = (uint32_t)(np - plan.aff_n_long);
             fl.n_pairs = (uint32_t)plan.aff_n_long; fl.pairs = fa.pairs + fs.n_pairs;
-            const uint32_t *mat = b->mat ? b->d_mat.as<uint32_t>() : nullptr;
-            const uint32_t nn = b->mat ? b->mat->n + 1u : 0u;
-            HIP_TRY(swmi_launch_affine_sweep(&fs, b->gap_open, (uint32_t)b->align_mode, mat, nn, plan.aff_r_min, plan.aff_r_max, 0u, 0u, ctx->stream));
+            const uint32_t *mat = b->opt.mat ? b->d_mat.as<uint32_t>() : nullptr;
+            const uint32_t nn = b->opt.mat ? b->opt.mat->n + 1u : 0u;
+            HIP_TRY(swmi_launch_affine_sweep(&fs, b->gap_open, (uint32_t)b->opt.modes.align_mode, mat, nn, plan.aff_r_min, plan.aff_r_max, 0u, 0u, ctx->stream));
             // (option "band": the banded strip sweep; the other pairs are swept in full)
-            HIP_TRY(swmi_launch_affine_sweep(&fl, b->gap_open, (uint32_t)b->align_mode, mat, nn, 0u, 0u, 1u, (uint32_t)b->band, ctx->stream));
+            HIP_TRY(swmi_launch_affine_sweep(&fl, b->gap_open, (uint32_t)b->opt.modes.align_mode, mat, nn, 0u, 0u, 1u, (uint32_t)b->opt.modes.band, ctx->stream));
         }
         else HIP_TRY(swmi_launch_fill(&fa, ctx->stream, ext ? ctx->ev[0] : nullptr, ext ? ctx->ev[1] : nullptr));
         rs.launches++;
@@ -296,8 +296,8 @@ static int enqueue_launches(RunState &rs, Launch &L, const ResidentArgs &xa, con
         ts.n_pairs = (uint32_t)(np - plan.aff_n_long);
         tl.n_pairs = (uint32_t)plan.aff_n_long; tl.pairs = ta.pairs + ts.n_pairs;
         const uint32_t ops_words = (uint32_t)(((uint64_t)plan.max_path + 15) / 16 + 1);
-        HIP_TRY(swmi_launch_affine_traceback(&ts, (uint32_t)b->align_mode, 0u, 0u, SWMI_AFF_TILE_WORDS, ops_words, ctx->stream));
-        HIP_TRY(swmi_launch_affine_traceback(&tl, (uint32_t)b->align_mode, 1u, (uint32_t)b->band, SWMI_AFF_TILE_WORDS, ops_words, ctx->stream));
+        HIP_TRY(swmi_launch_affine_traceback(&ts, (uint32_t)b->opt.modes.align_mode, 0u, 0u, SWMI_AFF_TILE_WORDS, ops_words, ctx->stream));
+        HIP_TRY(swmi_launch_affine_traceback(&tl, (uint32_t)b->opt.modes.align_mode, 1u, (uint32_t)b->opt.modes.band, SWMI_AFF_TILE_WORDS, ops_words, ctx->stream));
     } else if (n_res + n_tf < np) {
         HIP_TRY(swmi_launch_traceback(&ta, ctx->stream, ext ? ctx->ev[2] : nullptr, ext ? ctx->ev[3] : nullptr));
     }
@@ -335,7 +335,7 @@ static void collect_scores(const swmi_batch *b, const std::vector<Work> &work, c
     for (size_t k = 0; k < L.np; k++) {
         PairOut &o = outs[k];
         // (the end-to-end modes have no degenerate case: a score of 0 or below is an ordinary score)
-        if (o.score <= 0 && !(o.flags & SWMI_F_DEGENERATE) && b->align_mode == 0) {
+        if (o.score <= 0 && !(o.flags & SWMI_F_DEGENERATE) && b->opt.modes.align_mode == 0) {
             const uint32_t pair = work[L.lo + k].pair;
             o.score = 0; o.flags = SWMI_F_DEGENERATE;
             o.n_cells = (uint64_t)b->read_desc[pair % b->n_reads].len * b->ref_desc[pair / b->n_reads].len;
@@ -515,8 +515,9 @@ static int run_chunk(RunState &rs, const std::vector<Work> &work, size_t lo, siz
 // Option "band" (half-width w) with at least one read longer than 1024 bases: what a banded run refuses (swmi.h),
 // in 64-bit arithmetic.  rows = 1024 * strips of the longest read, S = the largest |score|, max_n = the longest reference.
 // Every condition is monotone in m and n, so the extreme lengths decide for every long pair of the batch.
-static int check_band(const swmi_ctx *ctx, const swmi_batch *b, const swmi_params *p, int align_mode, int band, uint64_t rows, int64_t S,
+static int check_band(const swmi_ctx *ctx, const swmi_batch *b, const swmi_params *p, const RunModes &md, uint64_t rows, int64_t S,
                       uint64_t max_n) {
+    const int align_mode = md.align_mode, band = md.band;
     const int64_t w = band;
     uint64_t min_n = UINT64_MAX, min_long = UINT64_MAX, max_m = 0;
     for (uint32_t r = 0; r < b->n_refs; r++)
@@ -556,9 +557,10 @@ static int check_band(const swmi_ctx *ctx, const swmi_batch *b, const swmi_param
 }
 
 // what a run cannot compute, refused before anything is launched (under ctx->mu: the context's options are read)
-// mat: the run's score matrix or null; long_reads, band: options "long_reads" and "band" of the run
-static int check_run_params(const swmi_ctx *ctx, const swmi_batch *b, const swmi_params *p, bool affine, int align_mode,
-                            const ScoreMatrix *mat, int long_reads, int band) {
+// opt: the run's options (the context's when the run was asked for)
+static int check_run_params(const swmi_ctx *ctx, const swmi_batch *b, const swmi_params *p, bool affine, const RunOptions &opt) {
+    const RunModes &md = opt.modes;
+    const ScoreMatrix *mat = opt.mat.get();
     if (p->tie_mode != SWMI_TIE_SERIAL && p->tie_mode != SWMI_TIE_STRICT)
         return fail(SWMI_ERR_INVALID, "unknown tie_mode %d", p->tie_mode);
     // GetAlignment tests `align == alignTypes[0]`, then `== alignTypes[1]`, else deletion
@@ -575,14 +577,14 @@ static int check_run_params(const swmi_ctx *ctx, const swmi_batch *b, const swmi
         if (std::llabs((int64_t)p->match) > lim || std::llabs((int64_t)p->mismatch) > lim || std::llabs((int64_t)p->gap) > lim ||
             std::llabs((int64_t)ctx->gap_open) > lim)
             return fail(SWMI_ERR_UNSUPPORTED, "affine gaps need |match|, |mismatch|, |gap|, |gap_open| <= 2^20");
-        for (uint32_t q = 0; q < b->n_reads && !long_reads; q++)
+        for (uint32_t q = 0; q < b->n_reads && !md.long_reads; q++)
             if (b->read_desc[q].len > SWMI_AFF_MAX_READ)
                 return fail(SWMI_ERR_UNSUPPORTED, "affine gaps: read %u has %u bases (at most %u; option long_reads lifts the limit)", q,
                             b->read_desc[q].len, SWMI_AFF_MAX_READ);
         longest_sequences(b, max_m, max_n);
         // the rows a sweep computes for the longest read: whole strips of 1024 above 1024 bases, else whole lanes' rows
         const uint64_t rows = max_m > SWMI_AFF_MAX_READ ? (uint64_t)SWMI_AFF_MAX_READ * swmi_aff_strips((uint32_t)max_m) : 64 * ((max_m + 63) / 64);
-        if (long_reads) {
+        if (md.long_reads) {
             // M * S <= 2^30 (swmi.h, DESIGN.md "Long reads"): H <= M * S, and no sum of the recurrence leaves int32
             int64_t S = std::max(std::max(std::llabs((int64_t)p->match), std::llabs((int64_t)p->mismatch)),
                                  std::max(std::llabs((int64_t)p->gap), std::llabs((int64_t)ctx->gap_open)));
@@ -591,18 +593,18 @@ static int check_run_params(const swmi_ctx *ctx, const swmi_batch *b, const swmi
             if ((int64_t)rows * S > ((int64_t)1 << 30))
                 return fail(SWMI_ERR_UNSUPPORTED, "long_reads: the longest read (%llu bases) is swept as %llu rows, and %llu * %lld (the largest "
                             "|score|) is above 2^30", (unsigned long long)max_m, (unsigned long long)rows, (unsigned long long)rows, (long long)S);
-            if (band > 0 && max_m > SWMI_AFF_MAX_READ && max_n) {
-                int rc = check_band(ctx, b, p, align_mode, band, rows, S, max_n);
+            if (md.band > 0 && max_m > SWMI_AFF_MAX_READ && max_n) {
+                int rc = check_band(ctx, b, p, md, rows, S, max_n);
                 if (rc) return rc;
             }
             // a pair of several strips is one launch's work at the least: refused when its field alone is over the cap
             // (a banded run is checked with its own, smaller field in check_band)
-            if (band <= 0 && max_m > SWMI_AFF_MAX_READ && max_n && swmi_aff_dir_words((uint32_t)max_m, (uint32_t)max_n) * 4 > ctx->max_workspace_bytes)
+            if (md.band <= 0 && max_m > SWMI_AFF_MAX_READ && max_n && swmi_aff_dir_words((uint32_t)max_m, (uint32_t)max_n) * 4 > ctx->max_workspace_bytes)
                 return fail(SWMI_ERR_UNSUPPORTED, "long_reads: the direction field of the longest read (%llu) against the longest reference (%llu) "
                             "takes %llu bytes, more than max_workspace_bytes (%llu)", (unsigned long long)max_m, (unsigned long long)max_n,
                             (unsigned long long)(swmi_aff_dir_words((uint32_t)max_m, (uint32_t)max_n) * 4), (unsigned long long)ctx->max_workspace_bytes);
         }
-        if (align_mode == SWMI_ALIGN_GLOBAL) {
+        if (md.align_mode == SWMI_ALIGN_GLOBAL) {
             // global mode: the smallest sum a sweep forms is 3 * gap_open + (64 * ceil(m / 64) + n) * gap (swmi.h, DESIGN.md
             // "End-to-end modes"); it must not leave int32.  Checked per pair in 64-bit arithmetic: it falls with m and n, so
             // the longest read against the longest reference decides.
@@ -680,7 +682,7 @@ static int choose_traceback_grain(swmi_ctx *ctx, swmi_batch *b, const swmi_param
 // The schedule: every pair with two non-empty sides (pairs with an empty side never enter ScoreMatrix's loops,
 // SmithWaterman.java:157-159: (0, [])).  It only depends on the sequence lengths and the pipeline mode: built once per batch.
 static void build_schedule(const swmi_ctx *ctx, swmi_batch *b) {
-    const int band = b->eff_mode == 3 ? b->band : 0;
+    const int band = b->eff_mode == 3 ? b->opt.modes.band : 0;
     if (b->work_mode == (int)b->eff_mode && b->work_tfused == (ctx->tfused == 1) && b->work_band == band) return;
     const uint32_t n_refs = b->n_refs, n_reads = b->n_reads;
     b->work_tfused = ctx->tfused == 1;
@@ -776,18 +778,15 @@ static int rerun_overflowed(RunState &rs, const std::vector<Work> &work, const s
     return SWMI_OK;
 }
 
-// mat: the score matrix the run uses (the context's when the run was asked for), or null
-// align_mode: the context's when the run was asked for
-// long_reads, band: likewise
-static int batch_run(swmi_ctx *ctx, swmi_batch *b, const swmi_params *p, std::shared_ptr<const ScoreMatrix> mat, const int align_mode,
-                     const int long_reads, const int band) {
+// opt: the context's run options when the run was asked for (run_options)
+static int batch_run(swmi_ctx *ctx, swmi_batch *b, const swmi_params *p, RunOptions opt) {
     if (!ctx || !b || !p) return fail(SWMI_ERR_INVALID, "null argument");
     std::lock_guard<std::mutex> g(ctx->mu);
     // (a score matrix and the end-to-end modes run on the affine kernels only)
     // (... and so does a band)
-    const bool affine = ctx->affine == 1 || ctx->gap_open != 0 || mat != nullptr || align_mode != SWMI_ALIGN_LOCAL || band > 0;
+    const bool affine = ctx->affine == 1 || ctx->gap_open != 0 || opt.mat != nullptr || opt.modes.align_mode != SWMI_ALIGN_LOCAL || opt.modes.band > 0;
     int rc;
-    if ((rc = check_run_params(ctx, b, p, affine, align_mode, mat.get(), long_reads, band))) return rc;
+    if ((rc = check_run_params(ctx, b, p, affine, opt))) return rc;
     static const bool host_dbg = getenv("SWMI_DEBUG_HOST") != nullptr;
     const auto h0 = Clock::now();
     {   // (hipSetDevice costs microseconds even when nothing changes; a sub-millisecond batch notices)
@@ -814,20 +813,17 @@ static int batch_run(swmi_ctx *ctx, swmi_batch *b, const swmi_params *p, std::sh
     // mode 1 needs pad rows that cannot outgrow the real cells they derive from: mismatch <= 0 and gap <= 0
     b->eff_mode = (ctx->mode == 1 && (p->mismatch > 0 || p->gap > 0)) ? 2u : ctx->mode;
     b->gap_open = ctx->gap_open;
-    b->align_mode = align_mode;
-    b->long_reads = long_reads;
-    b->band = band;
     if (affine) b->eff_mode = 3;                         // the affine kernels (swmi_affine.hip): no other pipeline option applies
-    b->mat = std::move(mat);
-    if (b->mat && b->d_mat_gen != b->mat->gen) {
+    b->opt = std::move(opt);
+    if (b->opt.mat && b->d_mat_gen != b->opt.mat->gen) {
         // the run's own device copy, on its stream, complete before the run goes on: whatever an earlier (failed) run left on
         // the stream is done with d_mat, and the pageable host image is read before anything can release it.  Only when the
         // matrix changes: a batch re-run under the same matrix copies nothing.
         if ((rc = b->d_mat.reserve((size_t)swmi_aff_mat_words(SWMI_MAT_NN_MAX) * 4))) return rc;
         b->d_mat_gen = 0;
-        HIP_TRY(hipMemcpyAsync(b->d_mat.p, b->mat->image.data(), b->mat->image.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(b->d_mat.p, b->opt.mat->image.data(), b->opt.mat->image.size() * 4, hipMemcpyHostToDevice, ctx->stream));
         HIP_TRY(hipStreamSynchronize(ctx->stream));
-        b->d_mat_gen = b->mat->gen;
+        b->d_mat_gen = b->opt.mat->gen;
     }
     if ((rc = choose_traceback_grain(ctx, b, p))) return rc;
     if (b->eff_mode == 0) {
@@ -884,7 +880,7 @@ static int batch_run(swmi_ctx *ctx, swmi_batch *b, const swmi_params *p, std::sh
 
 extern "C" int swmi_batch_run(swmi_ctx *ctx, swmi_batch *b, const swmi_params *p) {
     if (!ctx || !b || !p) return fail(SWMI_ERR_INVALID, "null argument");
-    return batch_run(ctx, b, p, ctx_matrix(ctx), ctx->align_mode, ctx->long_reads, ctx->band);
+    return batch_run(ctx, b, p, run_options(ctx));
 }
 
 // ---- asynchronous run: the same swmi_batch_run on the context's own host thread -------------------------------
@@ -903,7 +899,7 @@ static void swmi_worker_loop(swmi_ctx *ctx) {
         }
         if (st == 3) return;
         if (ctx->job_delay_us) std::this_thread::sleep_for(std::chrono::microseconds(ctx->job_delay_us));
-        const int rc = batch_run(ctx, ctx->job_batch, &ctx->job_params, std::move(ctx->job_matrix), ctx->job_align_mode, ctx->job_long_reads, ctx->job_band);
+        const int rc = batch_run(ctx, ctx->job_batch, &ctx->job_params, std::move(ctx->job_opt));
         ctx->job_rc = rc;
         ctx->job_err = rc ? swmi_last_error() : "";
         { std::lock_guard<std::mutex> lk(ctx->job_mu); ctx->job_state.store(2, std::memory_order_release); }
@@ -918,10 +914,7 @@ extern "C" int swmi_batch_run_async(swmi_ctx *ctx, swmi_batch *b, const swmi_par
     if (!ctx->worker.joinable()) ctx->worker = std::thread(swmi_worker_loop, ctx);
     ctx->job_batch = b;
     ctx->job_params = *p;
-    ctx->job_matrix = ctx_matrix(ctx);                 // (the matrix set now, whatever is set while the run is in flight)
-    ctx->job_align_mode = ctx->align_mode;             // (likewise)
-    ctx->job_long_reads = ctx->long_reads;
-    ctx->job_band = ctx->band;
+    ctx->job_opt = run_options(ctx);                   // (what is set now, whatever is set while the run is in flight)
     ctx->job_delay_us = ctx->dbg_async_delay_us;
     { std::lock_guard<std::mutex> lk(ctx->job_mu); ctx->job_state.store(1, std::memory_order_release); }
     ctx->job_cv.notify_all();

@@ -175,9 +175,8 @@ extern "C" int swmi_stream_open(swmi_ctx *ctx, const swmi_params *p, const uint8
         sl.ctx->tb_split = ctx->tb_split; sl.ctx->col_chunks = ctx->col_chunks; sl.ctx->resident = ctx->resident; sl.ctx->tfused = ctx->tfused;
         sl.ctx->auto_ties_x100 = ctx->auto_ties_x100; sl.ctx->arena_words_per_pair = ctx->arena_words_per_pair;
         sl.ctx->device_strings = ctx->device_strings; sl.ctx->scores_only = ctx->scores_only;
-        sl.ctx->gap_open = ctx->gap_open; sl.ctx->affine = ctx->affine; sl.ctx->align_mode = ctx->align_mode;
-        sl.ctx->long_reads = ctx->long_reads; sl.ctx->band = ctx->band;
-        sl.ctx->matrix = ctx_matrix(ctx);
+        sl.ctx->gap_open = ctx->gap_open; sl.ctx->affine = ctx->affine;
+        sl.ctx->modes = ctx->modes; sl.ctx->matrix = run_options(ctx).mat;
         sl.ctx->spin_us = 50;                    // (a chunk takes milliseconds: the slot threads mostly block)
         sl.shell = new swmi_batch;
     }

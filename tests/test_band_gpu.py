@@ -10,6 +10,7 @@ import sparksmithwaterman_amd as sw
 from sparksmithwaterman_amd import _capi
 from sparksmithwaterman_amd import matrix as M
 
+import affine_grid_cases as gc
 import affine_reference as ar
 import band_reference as br
 import ends_reference as er
@@ -424,5 +425,58 @@ def test_band_stream_equals_the_batch(ctx):
             assert c.ref_match_sites(r) == b.ref_match_sites(first + r), first + r
     for r in range(3):
         assert b.score(r) == exp[(r, 0)][0]
+    st.close()
+    b.free()
+
+
+def test_run_options_travel_together(ctx):
+    """The score matrix, align_mode, long_reads and band a run takes are those set when it was asked for, all four together: an
+    asynchronous run and a stream's slots hand them over as one value, and a field lost on the way would show here alone.
+    Each of the four is changed before the run starts, and each changes the result (long_reads 0 refuses the long read)."""
+    refs, reads, w, _, _ = _plumbing()
+    reads = reads[:2]                                             # one read of two strips, one short read
+    assert 1024 < len(reads[0]) <= 1300 and len(reads[1]) <= 1024
+    mat, mode = gc.score_matrix(), 1
+    assert not any(br.refused(len(q), len(r), w, mode) for r in refs for q in reads)
+    exp = _expect(refs, reads, SC, mode, w, 0, mat)
+    assert exp[(1, 1)] != br.align_numpy(refs[1], reads[1], SC, mode, w, 0)              # no matrix
+    assert exp[(1, 0)] != br.align_numpy(refs[1], reads[0], SC, 0, w, 0, mat)            # local
+    assert exp[(1, 0)] != br.align_numpy(refs[1], reads[0], SC, mode, 0, 0, mat)         # no band
+    p = sw.make_params(SC[:3])
+
+    def set_all():
+        ctx.set_score_matrix(*mat)
+        ctx.set_option("align_mode", mode)
+        ctx.set_option("long_reads", 1)
+        ctx.set_option("band", w)
+
+    def change_all():
+        ctx.clear_score_matrix()
+        ctx.set_option("align_mode", 0)
+        ctx.set_option("long_reads", 0)
+        ctx.set_option("band", 0)
+
+    ctx.set_option("gap_open", SC[3])
+    set_all()
+    ctx.set_option("debug_async_delay_us", 50000)
+    b = ctx.upload(refs, reads).run_async(p)
+    change_all()                                                  # none of it reaches the run in flight
+    b.wait()
+    assert b.pipeline_mode() == 3
+    _check(b, refs, reads, exp)
+    b.free()
+
+    set_all()
+    st = ctx.stream(reads, p, slots=2, chunk_bytes=1 << 12)
+    change_all()                                                  # (the slots copied all four at the open)
+    st.push(refs[:2]).push(refs[2:]).finish()
+    set_all()
+    b = ctx.upload(refs, reads).run(p)
+    _check(b, refs, reads, exp)
+    assert [int(t) for t in st.totals()] == [b.ref_total(r) for r in range(len(refs))]
+    for first, c in st.chunks():
+        assert c.pipeline_mode() == 3
+        for r in range(c.n_refs):
+            assert c.ref_match_sites(r) == b.ref_match_sites(first + r), first + r
     st.close()
     b.free()
