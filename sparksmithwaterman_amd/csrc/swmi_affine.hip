@@ -69,11 +69,9 @@
 #include "swmi_device.h"
 #include "swmi_emit.h"
 #include "swmi_launch.h"
+#include "swmi_wave.h"
 
-#define WAVE 64
 #define AFF_WAVES 4                    // wavefronts (= pairs) per workgroup of the sweep
-#define BALLOT(pred) __builtin_amdgcn_ballot_w64(pred)
-#define WAVE_SYNC() do { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); } while (0)
 
 // direction codes of the field (bits 0-1)
 #define AFF_STOP 0u
@@ -86,19 +84,6 @@
 #define AFF_GLOBAL 2
 
 namespace {
-
-// v_mov_b32_dpp wave_shr:1 : lane l receives lane l-1's value, lane 0 keeps `old`
-__device__ __forceinline__ int aff_shr1(int old, int src) {
-    return __builtin_amdgcn_update_dpp(old, src, 0x138 /*wave_shr:1*/, 0xf, 0xf, false);
-}
-// same, lane 0 receives 0 (row 0 of the matrix: H = 0, F clamped to 0)
-__device__ __forceinline__ int aff_shr1_zero(int src) {
-    return __builtin_amdgcn_update_dpp(0, src, 0x138 /*wave_shr:1*/, 0xf, 0xf, true);
-}
-__device__ __forceinline__ uint32_t uni(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
-__device__ __forceinline__ uint32_t lanes_below(uint64_t mask) {
-    return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-}
 
 // the score matrix of the matrix sweeps (only their instantiations reference it: the other kernels allocate no LDS)
 __shared__ uint32_t aff_mkey[256];
@@ -141,22 +126,22 @@ __device__ __forceinline__ void aff_block8(AffState<R> &S, const uint2 rw, const
         const uint32_t wsel = s < 4 ? rw.x : rw.y;
         const uint32_t fb = (wsel >> (8u * (s & 3u))) & 0xFFu;
         const int feed = MATRIX ? (int)aff_mkey[fb] : (int)fb;  // (wave-uniform: lane 0's column)
-        S.rb = aff_shr1(feed, S.rb);
+        S.rb = wave_shr1(feed, S.rb);
         int nh, nf;
         if constexpr (LONG) {
-            nh = aff_shr1(__builtin_amdgcn_readlane(Z.h, (int)s), S.h[R - 1]);
-            nf = aff_shr1(__builtin_amdgcn_readlane(Z.f, (int)s), S.f_last);
+            nh = wave_shr1(__builtin_amdgcn_readlane(Z.h, (int)s), S.h[R - 1]);
+            nf = wave_shr1(__builtin_amdgcn_readlane(Z.f, (int)s), S.f_last);
         } else if constexpr (MODE == AFF_LOCAL) {
-            nh = aff_shr1_zero(S.h[R - 1]);
-            nf = aff_shr1_zero(S.f_last);
+            nh = wave_shr1_zero(S.h[R - 1]);
+            nf = wave_shr1_zero(S.f_last);
         }
         const uint32_t c0 = t0 + s - lane;                       // column index j - 1 of this lane
         if constexpr (MODE != AFF_LOCAL && !LONG) {
             // lane 0 reads row 0 of the mode: H(0,j) = 0 (fit) or o + j*e (global), F(0,j) := H(0,j) + o
             // (unsigned arithmetic: lane 0 runs up to 70 columns past n, where the value is not used)
             const int h0 = MODE == AFF_GLOBAL ? (int)((uint32_t)o + (c0 + 1u) * (uint32_t)e) : 0;
-            nh = aff_shr1(h0, S.h[R - 1]);
-            nf = aff_shr1((int)((uint32_t)h0 + (uint32_t)o), S.f_last);
+            nh = wave_shr1(h0, S.h[R - 1]);
+            nf = wave_shr1((int)((uint32_t)h0 + (uint32_t)o), S.f_last);
         }
         const bool inr = c0 < n;
         int mrow = MODE == AFF_LOCAL ? -1 : 0;
@@ -239,7 +224,7 @@ __device__ __forceinline__ void aff_block8(AffState<R> &S, const uint2 rw, const
                 const bool hit = inr && (uint32_t)k < vrows && S.h[k] == S.thr;
                 const uint64_t hm = BALLOT(hit);
                 if (hm) {
-                    const uint32_t pos = S.cnt + lanes_below(hm);
+                    const uint32_t pos = S.cnt + lanemask_lt_count(hm);
                     if (hit && pos < ccap) cells[pos] = make_uint2(row0 + (uint32_t)k + 1u, c0 + 1u + (BAND ? Z.coff : 0u));
                     S.cnt += (uint32_t)__popcll(hm);
                 }
@@ -775,10 +760,9 @@ extern "C" hipError_t swmi_launch_affine_traceback(const TraceArgs *a, uint32_t 
     static void (*const bkern[3])(TraceArgs, uint32_t, uint32_t, uint32_t) = {      // [align_mode]: the banded long walks
         sw_affine_traceback_band_kernel, sw_affine_traceback_band_fit_kernel, sw_affine_traceback_band_global_kernel};
     static const bool attrs = [] {
-        const auto big_lds = [](auto *k) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        };
-        for (int mode = 0; mode < 3; ++mode) { big_lds(kern[0][mode]); big_lds(kern[1][mode]); big_lds(bkern[mode]); }
+        for (int mode = 0; mode < 3; ++mode) {
+            swmi_allow_big_lds(kern[0][mode]); swmi_allow_big_lds(kern[1][mode]); swmi_allow_big_lds(bkern[mode]);
+        }
         return true;
     }();
     (void)attrs;

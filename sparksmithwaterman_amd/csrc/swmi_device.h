@@ -1,5 +1,5 @@
 // swmi_device.h -- structures shared by the host runtime (swmi_host.h and its units) and the gfx950 kernels
-// (swmi_kernels.hip).  HBM data layout of one batch:
+// (the swmi_*.hip units).  HBM data layout of one batch:
 //
 //   seqw   uint32[]   every sequence as a BYTE image: 1 canonical code per base, 4 per dword, image start
 //                     16-byte aligned.  Codes: the eight fast symbols A,C,G,T,N,U,R,Y (any case) -> 0,4,...,28 --

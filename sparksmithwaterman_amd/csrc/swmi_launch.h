@@ -6,6 +6,13 @@
 #include <stdint.h>
 #include "swmi_device.h"
 
+// Allow `kernel` the whole 160 KB of a CU's LDS as dynamic shared memory (the default limit is 64 KB).  A launcher calls it
+// once per process, behind a static guard of its own.
+template <class K>
+static inline void swmi_allow_big_lds(K kernel) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+}
+
 extern "C" hipError_t swmi_launch_fill(const FillArgs *a, hipStream_t st, hipEvent_t ev_start, hipEvent_t ev_stop);
 extern "C" hipError_t swmi_launch_traceback(const TraceArgs *a, hipStream_t st, hipEvent_t ev_start, hipEvent_t ev_stop);
 extern "C" hipError_t swmi_launch_traceback_split(const TraceArgs *a, uint32_t n_windows, hipStream_t st);

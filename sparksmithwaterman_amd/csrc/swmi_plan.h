@@ -25,7 +25,7 @@ static uint64_t path_bound(uint64_t n_, uint64_t m_, const swmi_params &p, int32
     return path;
 }
 
-// bytes of LDS a traceback workgroup needs for pairs whose longest path / read are given (swmi_kernels.hip: SWMI_TB_WAVES = 8)
+// bytes of LDS a traceback workgroup needs for pairs whose longest path / read are given (swmi_walk.h: SWMI_TB_WAVES = 8)
 static uint64_t traceback_lds_bytes(uint32_t mode, uint64_t max_path, uint64_t max_read) {
     const uint64_t lds_words = (max_path + 3) / 4 + 1, lds_read_words = (max_read + 3) / 4 + 1;
     const uint64_t win = (uint64_t)SWMI_RMAX * 64;

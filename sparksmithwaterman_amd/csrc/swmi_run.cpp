@@ -639,7 +639,7 @@ static int check_run_params(const swmi_ctx *ctx, const swmi_batch *b, const swmi
 // tied maxima per pair are counted.  Periodic references (the reference's own EngineerData sets: every period ends
 // in a tied maximum, EngineerData.java:118) give every pair many alignments; one workgroup per pair then walks them
 // four at a time while most of the chip idles, so such batches take the split traceback (one wavefront per
-// window and per alignment, swmi_kernels.hip).
+// window and per alignment, swmi_traceback.hip).
 // (measured, profiles/r02/sweeps_*.md: with ~5 alignments per pair the split traceback wins up to ~200 pairs; from a
 // few hundred pairs on one workgroup per pair keeps every SIMD busy anyway and its teams share the window re-sweeps)
 static int choose_traceback_grain(swmi_ctx *ctx, swmi_batch *b, const swmi_params *p) {

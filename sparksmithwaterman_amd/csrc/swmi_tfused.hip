@@ -1,11 +1,11 @@
 // swmi_tfused.hip -- gfx950 kernel: sweep AND traceback of a pair in ONE launch, in the TRANSPOSED layout (option "tfused").
 //
-// Same results as the sweep + traceback kernels of swmi_kernels.hip (ScoreMatrix.call src/sw/SmithWaterman.java:129-190,
+// Same results as the sweep + traceback kernels of swmi_sweep.hip and swmi_traceback.hip (ScoreMatrix.call src/sw/SmithWaterman.java:129-190,
 // GetCellScore.call :217-252 / DistributedSW.java:305-330, GetAlignment.call :354-436) for the usual pair: both sequences of
 // fast symbols, int4 scores, gap < 0, a read of at most 256 bases, a reference of at most 64 * SWMI_TF_BMAX bases.
 // Measurements and the decision to leave it opt-in: DESIGN.md 4.4.
 //
-// Why transposed.  The sweep of swmi_kernels.hip puts the READ's rows on the lanes (R = 3 rows per lane at 150 bp) and
+// Why transposed.  The sweep of swmi_sweep.hip puts the READ's rows on the lanes (R = 3 rows per lane at 150 bp) and
 // streams the reference through: n + 63 steps of 3 R cell instructions + ~8 of per-step overhead (neighbour exchange, symbol
 // feed, window maximum, checkpoints).  At 150 x 2000 that is 2050 x 17 = 34.8 k instructions per pair, half of them overhead,
 // and one wavefront per SIMD issues one instruction per ~5 cycles whatever it is (tools/ubench_occ.hip): what counts is the
@@ -37,41 +37,27 @@
 #include "swmi_device.h"
 #include "swmi_emit.h"
 #include "swmi_launch.h"
+#include "swmi_wave.h"
 
-#define WAVE 64
 #define TF_WAVES 4                       // wavefronts of a workgroup that sweep a pair each
 #define TF_HELPERS SWMI_TF_HELPERS       // ... and wavefronts that only take tasks (at most)
 #define TF_BR SWMI_TF_BR                 // columns per lane of a re-swept block
 #define TF_BW (64u * TF_BR)              // ... and its width
 #define TF_ACC (TF_BR >= 5u ? 2u : 1u)   // candidate stripes a block takes cells from, counted from its right edge
-#define BALLOT(pred) __builtin_amdgcn_ballot_w64(pred)
-#define WAVE_SYNC() do { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); } while (0)
 
 namespace {
 
-__device__ __forceinline__ int tf_shr1(int old, int src) { return __builtin_amdgcn_update_dpp(old, src, 0x138 /*wave_shr:1*/, 0xf, 0xf, false); }
-__device__ __forceinline__ int tf_shr1_zero(int src) { return __builtin_amdgcn_update_dpp(0, src, 0x138, 0xf, 0xf, true); }
 __device__ __forceinline__ int tf_ror1(int src) { return __builtin_amdgcn_update_dpp(src, src, 0x13C /*wave_ror:1*/, 0xf, 0xf, false); }
 __device__ __forceinline__ int tf_max3(int a, int b, int c) { const int t = a > b ? a : b; return t > c ? t : c; }
 __device__ __forceinline__ int tf_subsat(int a, uint32_t b) { return (int)__builtin_elementwise_sub_sat((uint32_t)a, b); }
 
+// (stays private: wave_max_i32 of swmi_wave.h is the asm form, which changes this kernel's instruction stream)
 __device__ __forceinline__ int tf_wave_max(int v) {
 #define TF_DPP_MAX(ctrl, rmask) { int o_ = __builtin_amdgcn_update_dpp(v, v, ctrl, rmask, 0xf, false); v = v > o_ ? v : o_; }
     TF_DPP_MAX(0x111, 0xf) TF_DPP_MAX(0x112, 0xf) TF_DPP_MAX(0x114, 0xf) TF_DPP_MAX(0x118, 0xf) TF_DPP_MAX(0x142, 0xa) TF_DPP_MAX(0x143, 0xc)
 #undef TF_DPP_MAX
     return __builtin_amdgcn_readlane(v, 63);
 }
-__device__ __forceinline__ uint32_t tf_scan_add(uint32_t v) {          // inclusive prefix sum over the 64 lanes
-#define TF_DPP_ADD(ctrl, rmask) { const uint32_t o_ = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, ctrl, rmask, 0xf, true); v += o_; }
-    TF_DPP_ADD(0x111, 0xf) TF_DPP_ADD(0x112, 0xf) TF_DPP_ADD(0x114, 0xf) TF_DPP_ADD(0x118, 0xf) TF_DPP_ADD(0x142, 0xa) TF_DPP_ADD(0x143, 0xc)
-#undef TF_DPP_ADD
-    return v;
-}
-__device__ __forceinline__ uint32_t tf_lanes_below(uint64_t mask) {
-    return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-}
-__device__ __forceinline__ uint32_t tf_ld_l2(const uint32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ uint32_t tf_uni(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
 
 // 8 x int4 score profile of one reference column: nibble c/4 = score of the column's base against read symbol c
 __device__ __forceinline__ int tf_profile(uint32_t code, bool inside, int match, int mismatch) {
@@ -101,7 +87,7 @@ __device__ __forceinline__ int tf_sweep(const TfPair &P, const uint32_t lane, in
         H[k] = 0; hp[k] = 0;
     }
     int nwL = 0, M = 0, oh = 0;
-    const uint32_t T = tf_uni(P.m + P.L - 1u);
+    const uint32_t T = uni(P.m + P.L - 1u);
     uint32_t *__restrict__ ckrow = P.ck;                                  // (wave-uniform: the store takes it as its scalar base)
     for (uint32_t t0 = 0; t0 < T; t0 += 64u) {
         const uint32_t idx = t0 + 63u - lane;
@@ -109,9 +95,9 @@ __device__ __forceinline__ int tf_sweep(const TfPair &P, const uint32_t lane, in
         const uint32_t tend = T - t0 < 64u ? T - t0 : 64u;
         for (uint32_t r = 0; r < tend; ++r, ckrow += WAVE) {
             Q = tf_ror1(Q);
-            oh = tf_shr1(Q, oh);                                       // the symbol moves one lane down; lane 0 takes the next one
-            const int nw_next = tf_shr1_zero(H[B - 1]);                // lane l-1 finished this row one step ago: W's H now, NW next step
-            const int hpL = tf_shr1_zero(hp[B - 1]);
+            oh = wave_shr1(Q, oh);                                       // the symbol moves one lane down; lane 0 takes the next one
+            const int nw_next = wave_shr1_zero(H[B - 1]);                // lane l-1 finished this row one step ago: W's H now, NW next step
+            const int hpL = wave_shr1_zero(hp[B - 1]);
 #pragma unroll
             for (int k = B - 1; k >= 1; --k) H[k] = __builtin_amdgcn_sdot8(oh, q[k], H[k - 1], true);    // NW + s, in place
             H[0] = __builtin_amdgcn_sdot8(oh, q[0], nwL, true);
@@ -161,10 +147,10 @@ __device__ __forceinline__ uint32_t tf_replay_group(TfReplayState &S, const int 
 #pragma unroll
     for (uint32_t rr = 0; rr < 16u; ++rr) {
         S.Q = tf_ror1(S.Q);
-        S.oh = tf_shr1(S.Q, S.oh);
+        S.oh = wave_shr1(S.Q, S.oh);
         S.Bq = tf_ror1(S.Bq);
-        const int nw_next = tf_shr1(S.Bq, S.Hs[TF_BR - 1]);                  // lane 0: the boundary column
-        const int hpL = tf_shr1(tf_subsat(S.Bq, subW), S.wlast);
+        const int nw_next = wave_shr1(S.Bq, S.Hs[TF_BR - 1]);                  // lane 0: the boundary column
+        const int hpL = wave_shr1(tf_subsat(S.Bq, subW), S.wlast);
         int a[TF_BR];
 #pragma unroll
         for (int kk = TF_BR - 1; kk >= 1; --kk) a[kk] = __builtin_amdgcn_sdot8(S.oh, q[kk], S.Hs[kk - 1], true);
@@ -192,7 +178,7 @@ __device__ __forceinline__ uint32_t tf_replay_group(TfReplayState &S, const int 
                 const bool ok = S.Hs[kk] == target && row >= 0 && row < (int)P.m && c < P.n && c >= acc_lo && c < acc_hi;
                 const uint64_t mk = BALLOT(ok);
                 if (mk) {
-                    const uint32_t pos = cnt + tf_lanes_below(mk);
+                    const uint32_t pos = cnt + lanemask_lt_count(mk);
                     if (ok && pos >= base && pos - base < cell_cap) cells[pos - base] = make_uint2((uint32_t)row + 1u, c + 1u);
                     cnt += (uint32_t)__builtin_popcountll(mk);
                 }
@@ -226,7 +212,7 @@ __device__ __forceinline__ uint32_t tf_replay(const TfPair &P, const uint32_t la
         const uint32_t idx = t0 + 63u - lane;
         S.Q = idx < P.m ? (int)(4u << (P.read_b[idx] & 28u)) : 0;        // one-hot nibble 4: the dot product yields 4 s
         S.Bq = TAGH;                                                     // left boundary column, H(i, c_lo - 1) in stored form
-        if (k_stripe && idx < P.m) S.Bq = (int)(4u * tf_ld_l2(ckcol + (size_t)(idx + k_stripe - 1u) * WAVE)) + TAGH;
+        if (k_stripe && idx < P.m) S.Bq = (int)(4u * ld_l2(ckcol + (size_t)(idx + k_stripe - 1u) * WAVE)) + TAGH;
         const uint32_t tend = T - t0 < 64u ? T - t0 : 64u;               // (a multiple of 16)
         for (uint32_t r0 = 0; r0 < tend; r0 += 16u) {
             const TfReplayState S0 = S;
@@ -332,7 +318,7 @@ __device__ __forceinline__ uint32_t tf_queue_try_take(TfQueue *q, const uint32_t
             if (__hip_atomic_compare_exchange_strong(&q->taken, &t, t + 1u, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) { idx = t; break; }
         }
     }
-    return tf_uni(idx);
+    return uni(idx);
 }
 
 // before a wavefront overwrites its own tile: the walk items reading it must be through
@@ -386,7 +372,7 @@ __device__ __forceinline__ bool tf_walk(const TraceArgs &A, const TFusedArgs &X,
         const uint32_t op = STRICT ? 2u - tag : tag;                     // SWMI_DIR_D 0, SWMI_DIR_I 1, SWMI_DIR_A 2
         const bool isA = valid && op == SWMI_DIR_A;
         const uint32_t dlt = rc == qc ? umat : umis;                     // SmithWaterman.java:388-406, H(pred) = H - delta
-        const uint32_t cum = tf_scan_add(isA ? dlt : 0u);
+        const uint32_t cum = wave_scan_add_u32(isA ? dlt : 0u);
         const uint64_t runm = ~BALLOT(isA);
         const uint32_t r = runm ? (uint32_t)__builtin_ctzll(runm) : 64u;
         const uint64_t inrun = r >= 64u ? ~0ull : ((1ull << r) - 1ull);
@@ -489,11 +475,11 @@ __device__ __forceinline__ void tf_block_task(const TraceArgs &A, const TFusedAr
                 tf_lds_add(&sh->tile_users[me], pushed);
                 tf_queue_publish(&sh->qw, at);
             }
-            pushed = tf_uni(pushed);
+            pushed = uni(pushed);
         }
         for (uint32_t a = 0; a + pushed < here; ++a) {
             const uint2 c0 = R.cells[a];
-            const bool moved = tf_walk<STRICT>(A, X, sh, P, out_id, pmax, tf_uni(c0.x), tf_uni(c0.y), R.tile, P.B * kd, -1, me, lane, R);
+            const bool moved = tf_walk<STRICT>(A, X, sh, P, out_id, pmax, uni(c0.x), uni(c0.y), R.tile, P.B * kd, -1, me, lane, R);
             if (moved && a + 1u + pushed < here) {                         // the walk left the block and re-swept another one into this tile
                 WAVE_SYNC();                                               // (no walk item can be reading it: the walk waited for them)
                 (void)tf_replay<STRICT>(P, lane, kd, R.tile, false, pmax, 0u, 0u, R.cells, 0u, 0u);
@@ -601,8 +587,8 @@ __device__ __forceinline__ void tf_workgroup(const TraceArgs &A, const TFusedArg
                     tf_queue_publish(&sh->qb, at);
                 } else myslot->tasks_total = ntask;
             }
-            left_rest = ((uint64_t)tf_uni((uint32_t)(left_rest >> 32)) << 32) | tf_uni((uint32_t)left_rest);
-            left_top = tf_uni(left_top);
+            left_rest = ((uint64_t)uni((uint32_t)(left_rest >> 32)) << 32) | uni((uint32_t)left_rest);
+            left_top = uni(left_top);
             if (lane == 0) { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); tf_lds_add(&sh->owners_done, 1u); }
             counted = true;
             const unsigned long long tt0 = A.dbg ? __builtin_amdgcn_s_memtime() : 0ull;
@@ -628,17 +614,17 @@ __device__ __forceinline__ void tf_workgroup(const TraceArgs &A, const TFusedArg
     // ---- B + C: tasks, any pair of the workgroup ------------------------------------------------------------------------------
     auto pair_of = [&](const uint32_t sw, TfPair &P) {
         TfSlot *slot = &sh->slot[sw];
-        P.n = tf_uni(slot->n); P.m = tf_uni(slot->m);
+        P.n = uni(slot->n); P.m = uni(slot->m);
         P.B = swmi_tf_cols_per_lane(P.n);
         P.L = (P.n + P.B - 1u) / P.B;
         uint32_t *codes = regions + sw * X.lds_words + region_codes;
         P.ref_b = reinterpret_cast<const uint8_t *>(codes);
         P.read_b = reinterpret_cast<const uint8_t *>(codes + X.ref_words);
-        P.ck = reinterpret_cast<uint32_t *>((uintptr_t)(((unsigned long long)tf_uni(slot->ck_hi) << 32) | tf_uni(slot->ck_lo)));
+        P.ck = reinterpret_cast<uint32_t *>((uintptr_t)(((unsigned long long)uni(slot->ck_hi) << 32) | uni(slot->ck_lo)));
         P.match = A.match; P.mismatch = A.mismatch;
         P.g = g;
-        P.raw_ref = A.raw ? A.raw + A.raw_off[tf_uni(slot->ref_id)] : nullptr;
-        P.raw_read = A.raw ? A.raw + A.raw_off[A.raw_reads_at + tf_uni(slot->read_id)] : nullptr;
+        P.raw_ref = A.raw ? A.raw + A.raw_off[uni(slot->ref_id)] : nullptr;
+        P.raw_read = A.raw ? A.raw + A.raw_off[A.raw_reads_at + uni(slot->read_id)] : nullptr;
     };
     // everybody: block tasks first, then walk items, until every pair of the workgroup is through.  A helper lists cells
     // without handing any out (allow_push false): nobody ever reads a helper's tile, so a helper never waits.
@@ -649,10 +635,10 @@ __device__ __forceinline__ void tf_workgroup(const TraceArgs &A, const TFusedArg
             TF_MARK(0x500u | idx);
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
             const uint4 e = sh->qb.e[idx];
-            const uint32_t sw = tf_uni(e.x) & 0xFFu;
+            const uint32_t sw = uni(e.x) & 0xFFu;
             TfPair P;
             pair_of(sw, P);
-            tf_block_task<STRICT>(A, X, sh, sw, P, tf_uni(e.y), tf_uni(e.z), tf_uni(e.w), wave, lane, R, wave < TF_WAVES && X.n_helpers != 0u);
+            tf_block_task<STRICT>(A, X, sh, sw, P, uni(e.y), uni(e.z), uni(e.w), wave, lane, R, wave < TF_WAVES && X.n_helpers != 0u);
             ++n_taken;
             spins = 0;
             continue;
@@ -662,12 +648,12 @@ __device__ __forceinline__ void tf_workgroup(const TraceArgs &A, const TFusedArg
             TF_MARK(0x800u | idx);
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
             const uint4 e = sh->qw.e[idx];
-            const uint32_t e0 = tf_uni(e.x), sw = e0 & 0xFFu, owner = (e0 >> 8) & 0xFFu;
+            const uint32_t e0 = uni(e.x), sw = e0 & 0xFFu, owner = (e0 >> 8) & 0xFFu;
             TfSlot *slot = &sh->slot[sw];
             TfPair P;
             pair_of(sw, P);
             const uint32_t *otile = regions + owner * X.lds_words;
-            (void)tf_walk<STRICT>(A, X, sh, P, tf_uni(slot->out_id), (int)tf_uni(slot->pmax), tf_uni(e.z), tf_uni(e.w), otile, tf_uni(e.y),
+            (void)tf_walk<STRICT>(A, X, sh, P, uni(slot->out_id), (int)uni(slot->pmax), uni(e.z), uni(e.w), otile, uni(e.y),
                                   (int)owner, wave, lane, R);         // (its own tile too is given back before it may be overwritten)
             tf_task_done(A, slot, 0u, lane);
             spins = 0;
@@ -697,20 +683,19 @@ __device__ __forceinline__ void tf_workgroup(const TraceArgs &A, const TFusedArg
 extern "C" __global__ void __launch_bounds__(WAVE * (TF_WAVES + TF_HELPERS))
 sw_tfused_kernel(const TraceArgs A, const TFusedArgs X) {
     extern __shared__ uint32_t tf_lds[];
-    const uint32_t wave = tf_uni(threadIdx.x >> 6), lane = threadIdx.x & 63u;
+    const uint32_t wave = uni(threadIdx.x >> 6), lane = threadIdx.x & 63u;
     if (A.strict) tf_workgroup<true>(A, X, wave, lane, tf_lds);
     else          tf_workgroup<false>(A, X, wave, lane, tf_lds);
 }
 
 extern "C" hipError_t swmi_launch_tfused(const TraceArgs *a, const TFusedArgs *x, hipStream_t st) {
     if (x->n_items == 0) return hipSuccess;
-    static const bool attr = [] { (void)hipFuncSetAttribute(reinterpret_cast<const void *>(sw_tfused_kernel),
-                                                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); return true; }();
+    static const bool attr = [] { swmi_allow_big_lds(sw_tfused_kernel); return true; }();
     (void)attr;
     const uint32_t groups = (x->n_items + TF_WAVES - 1) / TF_WAVES;
     size_t lds = (size_t)(TF_WAVES + x->n_helpers) * x->lds_words * sizeof(uint32_t) + ((sizeof(TfShared) + 3u) / 4u) * 4u;
     // a launch that fits the chip once: an LDS request that keeps the dispatcher from stacking workgroups on some CUs while
-    // others stay empty (swmi_kernels.hip, spread_lds)
+    // others stay empty (swmi_sweep.hip, spread_lds)
     static const int spread = getenv("SWMI_LDS_SPREAD") ? atoi(getenv("SWMI_LDS_SPREAD")) : 1;
     if (spread && groups <= 4u * 256u) {
         const size_t even = ((size_t)(160u * 1024u) / ((groups + 255u) / 256u)) & ~(size_t)1023;

@@ -555,7 +555,7 @@ def test_diagonal_that_just_fits_and_just_wraps(ctx, m):
 def test_walk_shortcuts_at_their_threshold(ctx, match):
     """The traceback walk takes a run of up to 21 alignment moves and 2 gap moves in one go when the score exceeds that many
     moves' worth of max(match, mismatch): a 32-bit product that fits up to match = (2^31 - 1) / 23 = 93,368,854 and is switched
-    off above (swmi_kernels.hip: dec_fits).  One match, a deletion, then a run of 21 matches; 22 matches still fit an int."""
+    off above (swmi_walk.h: dec_fits).  One match, a deletion, then a run of 21 matches; 22 matches still fit an int."""
     assert 23 * (0x7FFFFFFF // 23) <= 0x7FFFFFFF < 23 * (0x7FFFFFFF // 23 + 1) and 22 * match - 4 < 2 ** 31
     rng = random.Random(933)
     ref = lc.rand_seq(rng, 90, _WIDE)

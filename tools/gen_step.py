@@ -4,7 +4,7 @@
 asm statement (hipcc pads every boundary between two asm statements with an s_nop of its own) -- per step the lane's
 R cells, both neighbour exchanges, the reference feed and the window maximum.
 
-State of a lane (swmi_kernels.hip, SweepFast): H of its R rows ping-pongs between two register sets (hin = the
+State of a lane (swmi_cells.h, SweepState): H of its R rows ping-pongs between two register sets (hin = the
 previous step's, hout = the one before, overwritten here); hp[k] = max(H[k] + gap, 0) is kept beside it, in place.
 With gap <= 0 the recurrence of SmithWaterman.java:223-249
     H = max(0, W + gap, N + gap, NW + s)        becomes        H = max3(NW + s, hp(N), hp(W))
