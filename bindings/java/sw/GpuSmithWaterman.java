@@ -40,6 +40,8 @@ public class GpuSmithWaterman
 	static native void nativeSetLongReads( long ctx , int longReads ) ;
 	/** reads longer than 1024 bases inside a band of this half-width around the diagonal, 0: no band (include/swmi.h: option "band") */
 	static native void nativeSetBand( long ctx , int band ) ;
+	/** seed extension with ALIGN_GLOBAL: 1 on, 0 off (include/swmi.h: option "extend") */
+	static native void nativeSetExtend( long ctx , int extend ) ;
 	/** substitution scores on the context: alphabet = n ISO-8859-1 symbols, scores = n * n, row = read base; null clears */
 	static native void nativeSetScoreMatrix( long ctx , byte[] alphabet , int[] scores ) ;
 	static native void nativeFreeBatch( long ctx , long batch ) ;
@@ -101,6 +103,17 @@ public class GpuSmithWaterman
 	 * of 1024 rows, on the affine kernels; 0 (the default): no band.  For every batch aligned from now on, on every executor thread.
 	 */
 	public static void setBand( int band ) { BAND = band ; }
+
+	/** whether every context runs ALIGN_GLOBAL as seed extension (applied next to band, before every batch) */
+	private static volatile boolean EXTEND = false ;
+
+	/**
+	 * true: with ALIGN_GLOBAL the alignment is anchored at the start of the read and of the reference and ends at the cell with the
+	 * best score, the tails left unaligned (seed extension; the total may be zero or negative; for left extension reverse both
+	 * sequences); with another align mode the batch is refused.  false (the default): off.  For every batch aligned from now on, on
+	 * every executor thread.
+	 */
+	public static void setExtend( boolean extend ) { EXTEND = extend ; }
 
 	/** the score matrix every context applies before its next batch: { alphabet , scores } (null: none), and its version */
 	private static volatile Object[] MATRIX = null ;
@@ -237,6 +250,7 @@ public class GpuSmithWaterman
 			nativeSetAlignMode( ctx , ALIGN_MODE ) ;
 			nativeSetLongReads( ctx , LONG_READS ? 1 : 0 ) ;
 			nativeSetBand( ctx , BAND ) ;
+			nativeSetExtend( ctx , EXTEND ? 1 : 0 ) ;
 			applyScoreMatrix( nc ) ;
 			long batch = nativeAlignBatch( ctx , sc[0] , sc[1] , sc[2] , TIE_SERIAL , types , refBuf , refOff , n , readBuf , readOff , reads.size() ) ;
 			try

@@ -39,6 +39,10 @@ int swmi_shim_set_long_reads(swmi_ctx *ctx, int32_t long_reads, char *err, size_
 /* nativeSetBand: reads longer than 1024 bases are aligned inside a band of this half-width around the diagonal from then on
  * (swmi_set_option "band"), 0 (the default): no band.  A value outside 0 .. 2^20 is SWMI_ERR_INVALID and leaves the context as it was. */
 int swmi_shim_set_band(swmi_ctx *ctx, int32_t band, char *err, size_t err_len);
+/* nativeSetExtend: 1 = seed extension from then on (swmi_set_option "extend"): a global run ends at the cell with the best score
+ * instead of at (m, n); a run in another align_mode is then refused (SWMI_ERR_UNSUPPORTED).  0 (the default): off.  Any other
+ * value is SWMI_ERR_INVALID and leaves the context as it was. */
+int swmi_shim_set_extend(swmi_ctx *ctx, int32_t extend, char *err, size_t err_len);
 
 /* nativeSetScoreMatrix: a substitution score matrix on this context (swmi_set_score_matrix): `alphabet` = n symbols narrowed to
  * bytes (ISO-8859-1), `scores` = n * n entries, row = read base, column = reference base (n_scores must be n * n).  n = 0 clears

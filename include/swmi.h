@@ -173,6 +173,24 @@ void        swmi_default_params(swmi_params *p);
  *                not fit without a band may fit with one.  scores_only, device_strings, zero_copy, cell_cap and profiling apply as to
  *                any affine run.  A run (async runs and stream slots included) takes the value set when it was asked for (DESIGN.md
  *                section 8f).
+ * extend (default 0; any value but 0 and 1 is SWMI_ERR_INVALID and leaves the context as it was): 1 turns a run with align_mode =
+ *                SWMI_ALIGN_GLOBAL into SEED EXTENSION (ksw2's extz, BWA-MEM's extension step): the alignment is anchored at the start
+ *                of the read and of the reference, runs along the diagonal, and ends at the cell with the best score, the tail of the
+ *                read or of the reference left unaligned.  E, F, H, the x bits, the tie chains and the boundaries are global mode's
+ *                (H(0,0) = 0, H(0,j) = gap_open + j * gap, H(i,0) = gap_open + i * gap, no floor at 0); the pair's score is the maximum
+ *                of H(i,j) over 1 <= i <= m, 1 <= j <= n -- under band, over the in-band cells of a long read -- and every tied cell is
+ *                a maximum cell, in local mode's order (serial tie mode row-major; strict per anti-diagonal with ascending j, then
+ *                the stable sort by begin), with cell_cap, the exact-size re-run and the other affine options as for local and fit
+ *                lists.  Row 0 and column 0 do not compete: the library reports the best NON-EMPTY extension, so the score may be zero
+ *                or negative (SWMI_PAIR_DEGENERATE is never set), and a score <= 0 tells the caller that not extending at all (score 0)
+ *                is no worse.  The walk is global mode's, started at the maximum cell (i, j): the alignment spells exactly read[:i] and
+ *                ref[:j], `begin` is 1, and end_i / end_j of swmi_pair_alignment are the maximum cell.  For LEFT extension reverse both
+ *                sequences.  The bounds are global mode's, unchanged (the affine bounds, 3 * |gap_open| + (M + n) * |gap| <= 2^31, under
+ *                long_reads M * S <= 2^30, under band M * S <= 2^29 and 3 * |gap_open| + (M + n) * |gap| <= 2^30, no strip with an empty
+ *                window), but for one: the end cell is free, so a banded extend run does NOT need (m, n) inside the band and takes a
+ *                reference longer than 1024 NS + w.  extend = 1 with any other align_mode is SWMI_ERR_UNSUPPORTED before anything is
+ *                launched.  With 0 nothing changes.  A run (async runs and stream slots included) takes the value set when it was asked
+ *                for.
  * Further knobs: spin_us (how long a run polls its stream before it blocks, default 2000); col_chunks (0 automatic,
  * 1 never, N > 1 force up to N column chunks per pair: a launch of few pairs with long references is swept by several
  * wavefronts per pair -- a read of more than 256 rows by several strip pipelines); debug_strip_spins / debug_reverse_strips (tests of the strip pipeline's give-up path);

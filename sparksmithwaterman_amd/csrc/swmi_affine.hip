@@ -58,7 +58,12 @@
 //   SWMI_AFF_BAND_NEG; the walk takes a strip's window origin and block count from (s, n, w).  The half-width is one more
 //   scalar kernel argument.
 //
-// How the 33 kernels are made: the 24 sweeps are aff_sweep_entry<RLO, RHI, MATRIX, MODE, LONG, BAND> over one block function
+// sw_affine_sweep_extend[_matrix][_wide]_kernel, sw_affine_sweep_{long,band}_extend[_matrix]_kernel: seed extension (option
+//   "extend" on a global run), MODE = 3: global mode's cells, boundaries and field, bit for bit, with the maximum
+//   taken over every cell of rows 1 .. m as in local mode, from INT32_MIN up (the score may be <= 0; there is no degenerate
+//   case).  The walk from a maximum cell is global mode's: these runs are traced back by the three global traceback kernels.
+//
+// How the 41 kernels are made: the 32 sweeps are aff_sweep_entry<RLO, RHI, MATRIX, MODE, LONG, BAND> over one block function
 //   (aff_block8); the 9 tracebacks are aff_traceback<MODE, LONG, BAND>, where !LONG is the walk with one strip and !BAND the
 //   walk whose windows are the whole reference.  One macro defines the sweeps, one the tracebacks; the launchers pick a kernel
 //   from typed tables.  The per-pair sweep is two thin bodies, aff_sweep_pair and aff_sweep_long_pair<.., BAND> (the one strip
@@ -82,6 +87,12 @@
 #define AFF_LOCAL  0
 #define AFF_FIT    1
 #define AFF_GLOBAL 2
+// option "extend" (with align_mode global): global mode's cells, local mode's maximum over every cell.  Internal to this file
+// and the launchers' tables: the host passes it in place of the align_mode
+#define AFF_EXTEND 3
+// the modes that sweep global mode's cells (row 0 is o + j*e), and the ones whose maximum is taken over row m alone
+#define AFF_ROW0_GAPS(MODE) ((MODE) == AFF_GLOBAL || (MODE) == AFF_EXTEND)
+#define AFF_ROW_M_ONLY(MODE) ((MODE) == AFF_FIT || (MODE) == AFF_GLOBAL)
 
 namespace {
 
@@ -111,7 +122,11 @@ struct AffState {
 
 // 8 anti-diagonal steps t0 .. t0+7 (a lane outside its column range keeps its state).  The steps are a loop, not unrolled:
 // eight copies of R cells let the scheduler hoist the compares of many cells at once, and their masks spilled the SGPRs.
-// MODE != AFF_LOCAL: vrows is the row slot of read row m in the lane that owns it, 0xFFFFFFFF in every other lane
+// AFF_FIT, AFF_GLOBAL: vrows is the row slot of read row m in the lane that owns it, 0xFFFFFFFF in every other lane
+// AFF_EXTEND: global mode's cell, then local mode's tied maxima from INT32_MIN up -- vrows is local mode's, so pad rows never
+//   compete.  A lane without a cell in this step idles at mrow = INT32_MIN: it passes `mrow >= thr` only while thr is still
+//   INT32_MIN, which is before step 0 alone (lane 0's cell (1, 1) -- of the first window under BAND -- raises it there), and it
+//   lists nothing even then: a listed cell is inr, inside the read and holds a real H
 // LONG: one strip of a long read -- lane 0 is fed from Z (every strip, the first one too: its Z holds row 0 of the mode) and lane
 // Z.wlane leaves (H, F) of its last row in the seam row
 // BAND (with LONG): the strip sweeps a window of the reference -- n is the window's length, columns count from its first one
@@ -139,12 +154,12 @@ __device__ __forceinline__ void aff_block8(AffState<R> &S, const uint2 rw, const
         if constexpr (MODE != AFF_LOCAL && !LONG) {
             // lane 0 reads row 0 of the mode: H(0,j) = 0 (fit) or o + j*e (global), F(0,j) := H(0,j) + o
             // (unsigned arithmetic: lane 0 runs up to 70 columns past n, where the value is not used)
-            const int h0 = MODE == AFF_GLOBAL ? (int)((uint32_t)o + (c0 + 1u) * (uint32_t)e) : 0;
+            const int h0 = AFF_ROW0_GAPS(MODE) ? (int)((uint32_t)o + (c0 + 1u) * (uint32_t)e) : 0;
             nh = wave_shr1(h0, S.h[R - 1]);
             nf = wave_shr1((int)((uint32_t)h0 + (uint32_t)o), S.f_last);
         }
         const bool inr = c0 < n;
-        int mrow = MODE == AFF_LOCAL ? -1 : 0;
+        int mrow = MODE == AFF_LOCAL ? -1 : (MODE == AFF_EXTEND ? INT32_MIN : 0);
         if (inr) {
             int diag = S.nh_prev, up = nh, fup = nf;
             uint32_t sh = 4u * s;
@@ -190,14 +205,14 @@ __device__ __forceinline__ void aff_block8(AffState<R> &S, const uint2 rw, const
                 fup = fn;
                 S.h[k] = hv;
                 S.e[k] = en;
-                if constexpr (MODE == AFF_LOCAL) { if ((uint32_t)k < vrows) mrow = max(mrow, hv); }
-                else                             { if ((uint32_t)k == vrows) mrow = hv; }
+                if constexpr (!AFF_ROW_M_ONLY(MODE)) { if ((uint32_t)k < vrows) mrow = max(mrow, hv); }
+                else                                 { if ((uint32_t)k == vrows) mrow = hv; }
             }
             S.f_last = fup;
             if constexpr (LONG) { if (lane == Z.wlane) Z.row[c0] = make_int2(S.h[R - 1], fup); }
         }
         S.nh_prev = nh;
-        if constexpr (MODE != AFF_LOCAL) {
+        if constexpr (AFF_ROW_M_ONLY(MODE)) {
             // row m only: the one lane that owns it, at every column (fit) or at column n (global)
             const bool cand = inr && vrows != 0xFFFFFFFFu && (MODE == AFF_FIT || c0 + 1u == n);
             const uint64_t cm = BALLOT(cand && mrow >= S.thr);
@@ -235,11 +250,11 @@ __device__ __forceinline__ void aff_block8(AffState<R> &S, const uint2 rw, const
 
 // The pieces the sweep of a short read and the strip sweep of a long one share.  They take and return values: a helper that
 // is handed a reference to the lane's state changes the register allocation of the sweeps it is inlined into.
-// vrows of a lane whose first row is row0 + 1: LOCAL the number of its rows inside the read; the end-to-end modes track row m
+// vrows of a lane whose first row is row0 + 1: LOCAL and EXTEND the number of its rows inside the read; fit and global track row m
 // alone: its row slot in the lane that owns it, no slot (0xFFFFFFFF) elsewhere
 template <int R, int MODE>
 __device__ __forceinline__ uint32_t aff_vrows(const uint32_t m, const uint32_t row0) {
-    return MODE != AFF_LOCAL ? (m - 1u - row0 < (uint32_t)R ? m - 1u - row0 : 0xFFFFFFFFu)
+    return AFF_ROW_M_ONLY(MODE) ? (m - 1u - row0 < (uint32_t)R ? m - 1u - row0 : 0xFFFFFFFFu)
                              : row0 >= m ? 0u : (m - row0 < (uint32_t)R ? m - row0 : (uint32_t)R);
 }
 
@@ -419,7 +434,7 @@ __device__ __forceinline__ void aff_sweep_long_pair(const FillArgs &A, const int
             // lane 0's feed from above at window columns t0 + 1 .. t0 + 8, one column per lane 0..7: row 0 of the mode (as in
             // aff_block8; strip 0 has clo = 1), below it the seam -- the true F, not the H + o stand-in of row 0
             const uint32_t c = t0 + lane;
-            Z.h = MODE == AFF_GLOBAL ? (int)((uint32_t)o + (c + 1u) * (uint32_t)A.gap) : 0;
+            Z.h = AFF_ROW0_GAPS(MODE) ? (int)((uint32_t)o + (c + 1u) * (uint32_t)A.gap) : 0;
             Z.f = MODE == AFF_LOCAL ? 0 : (int)((uint32_t)Z.h + (uint32_t)o);
             if (sx) {
                 int2 v = make_int2(OUT, OUT);
@@ -483,7 +498,7 @@ __device__ __forceinline__ void aff_sweep_entry(const FillArgs &A, const int o, 
 
 }  // namespace
 
-// The 24 sweep kernels: local, fit and global (option "align_mode"), each plain and with a score matrix (MATRIX = 0 / 1), each
+// The 32 sweep kernels: local, fit and global (option "align_mode") and extend (option "extend"), each plain and with a score matrix (MATRIX = 0 / 1), each
 // narrow (R = 1..4), wide (R = 5..16), long (option "long_reads": RLO, RHI unused) and banded long (option "band", BAND = 1:
 // the half-width is one more scalar argument).  MATRIX and BAND make the four signatures.
 #define AFF_SWEEP_PARAMS_00 const FillArgs A, const int gap_open
@@ -522,6 +537,14 @@ AFF_SWEEP_KERNEL(sw_affine_sweep_band_fit_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 
 AFF_SWEEP_KERNEL(sw_affine_sweep_band_fit_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, AFF_FIT, true, 1)
 AFF_SWEEP_KERNEL(sw_affine_sweep_band_global_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, AFF_GLOBAL, true, 1)
 AFF_SWEEP_KERNEL(sw_affine_sweep_band_global_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, AFF_GLOBAL, true, 1)
+AFF_SWEEP_KERNEL(sw_affine_sweep_extend_kernel, 1, 4, 0, AFF_EXTEND, false, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_extend_wide_kernel, 5, SWMI_AFF_RMAX, 0, AFF_EXTEND, false, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_long_extend_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, AFF_EXTEND, true, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_extend_matrix_kernel, 1, 4, 1, AFF_EXTEND, false, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_extend_matrix_wide_kernel, 5, SWMI_AFF_RMAX, 1, AFF_EXTEND, false, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_long_extend_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, AFF_EXTEND, true, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_band_extend_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, AFF_EXTEND, true, 1)
+AFF_SWEEP_KERNEL(sw_affine_sweep_band_extend_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, AFF_EXTEND, true, 1)
 #undef AFF_SWEEP_KERNEL
 #undef AFF_SWEEP_PARAMS_00
 #undef AFF_SWEEP_PARAMS_10
@@ -708,7 +731,7 @@ AFF_TRACEBACK_KERNEL(sw_affine_traceback_band_global_kernel, AFF_GLOBAL, true, 1
 // ------------------------------------------------------------------------------------------------
 // host-callable launchers
 // ------------------------------------------------------------------------------------------------
-// align_mode: 0 local, 1 fit, 2 global (option "align_mode")
+// align_mode: 0 local, 1 fit, 2 global (option "align_mode"), 3 extend (option "extend" on a global run: AFF_EXTEND)
 // mat / nn: the device image of the score matrix (swmi_aff_mat_words dwords) and its side n + 1 (2 .. 65), or null: the plain sweeps
 // long_reads 0: the narrow and the wide sweep; r_min / r_max: the rows per lane of the launch's shortest and longest read (only
 //   the kernels that have pairs are launched).  long_reads 1: the strip sweep (every pair has a read longer than 1024 bases)
@@ -716,21 +739,24 @@ AFF_TRACEBACK_KERNEL(sw_affine_traceback_band_global_kernel, AFF_GLOBAL, true, 1
 extern "C" hipError_t swmi_launch_affine_sweep(const FillArgs *a, int32_t gap_open, uint32_t align_mode, const uint32_t *mat, uint32_t nn,
                                                uint32_t r_min, uint32_t r_max, uint32_t long_reads, uint32_t band, hipStream_t st) {
     if (a->n_pairs == 0) return hipSuccess;
-    if (align_mode > 2u || (mat && (nn < 2u || nn > SWMI_MAT_NN_MAX)) || band > SWMI_AFF_BAND_MAX) return hipErrorInvalidValue;
+    if (align_mode > 3u || (mat && (nn < 2u || nn > SWMI_MAT_NN_MAX)) || band > SWMI_AFF_BAND_MAX) return hipErrorInvalidValue;
     // [narrow / wide / long][align_mode], and [align_mode] of the banded long sweeps: one typed table per signature (plain /
     // matrix, without / with the half-width), so that a launch is checked against its kernel's parameter list
-    static void (*const plain[3][3])(FillArgs, int) = {
-        {sw_affine_sweep_kernel, sw_affine_sweep_fit_kernel, sw_affine_sweep_global_kernel},
-        {sw_affine_sweep_wide_kernel, sw_affine_sweep_fit_wide_kernel, sw_affine_sweep_global_wide_kernel},
-        {sw_affine_sweep_long_kernel, sw_affine_sweep_long_fit_kernel, sw_affine_sweep_long_global_kernel}};
-    static void (*const matrix[3][3])(FillArgs, int, const uint32_t *, uint32_t) = {
-        {sw_affine_sweep_matrix_kernel, sw_affine_sweep_fit_matrix_kernel, sw_affine_sweep_global_matrix_kernel},
-        {sw_affine_sweep_matrix_wide_kernel, sw_affine_sweep_fit_matrix_wide_kernel, sw_affine_sweep_global_matrix_wide_kernel},
-        {sw_affine_sweep_long_matrix_kernel, sw_affine_sweep_long_fit_matrix_kernel, sw_affine_sweep_long_global_matrix_kernel}};
-    static void (*const bplain[3])(FillArgs, int, uint32_t) = {
-        sw_affine_sweep_band_kernel, sw_affine_sweep_band_fit_kernel, sw_affine_sweep_band_global_kernel};
-    static void (*const bmatrix[3])(FillArgs, int, const uint32_t *, uint32_t, uint32_t) = {
-        sw_affine_sweep_band_matrix_kernel, sw_affine_sweep_band_fit_matrix_kernel, sw_affine_sweep_band_global_matrix_kernel};
+    static void (*const plain[3][4])(FillArgs, int) = {
+        {sw_affine_sweep_kernel, sw_affine_sweep_fit_kernel, sw_affine_sweep_global_kernel, sw_affine_sweep_extend_kernel},
+        {sw_affine_sweep_wide_kernel, sw_affine_sweep_fit_wide_kernel, sw_affine_sweep_global_wide_kernel, sw_affine_sweep_extend_wide_kernel},
+        {sw_affine_sweep_long_kernel, sw_affine_sweep_long_fit_kernel, sw_affine_sweep_long_global_kernel, sw_affine_sweep_long_extend_kernel}};
+    static void (*const matrix[3][4])(FillArgs, int, const uint32_t *, uint32_t) = {
+        {sw_affine_sweep_matrix_kernel, sw_affine_sweep_fit_matrix_kernel, sw_affine_sweep_global_matrix_kernel, sw_affine_sweep_extend_matrix_kernel},
+        {sw_affine_sweep_matrix_wide_kernel, sw_affine_sweep_fit_matrix_wide_kernel, sw_affine_sweep_global_matrix_wide_kernel,
+         sw_affine_sweep_extend_matrix_wide_kernel},
+        {sw_affine_sweep_long_matrix_kernel, sw_affine_sweep_long_fit_matrix_kernel, sw_affine_sweep_long_global_matrix_kernel,
+         sw_affine_sweep_long_extend_matrix_kernel}};
+    static void (*const bplain[4])(FillArgs, int, uint32_t) = {
+        sw_affine_sweep_band_kernel, sw_affine_sweep_band_fit_kernel, sw_affine_sweep_band_global_kernel, sw_affine_sweep_band_extend_kernel};
+    static void (*const bmatrix[4])(FillArgs, int, const uint32_t *, uint32_t, uint32_t) = {
+        sw_affine_sweep_band_matrix_kernel, sw_affine_sweep_band_fit_matrix_kernel, sw_affine_sweep_band_global_matrix_kernel,
+        sw_affine_sweep_band_extend_matrix_kernel};
     const dim3 grid((a->n_pairs + AFF_WAVES - 1) / AFF_WAVES), block(WAVE * AFF_WAVES);
     const bool banded = long_reads && band;                       // (the long shape only)
     // (a launch's own error is what hipGetLastError returns below)
@@ -753,7 +779,10 @@ extern "C" hipError_t swmi_launch_affine_sweep(const FillArgs *a, int32_t gap_op
 extern "C" hipError_t swmi_launch_affine_traceback(const TraceArgs *a, uint32_t align_mode, uint32_t long_reads, uint32_t band, uint32_t tile_words,
                                                    uint32_t ops_words, hipStream_t st) {
     if (a->n_pairs == 0) return hipSuccess;
-    if (align_mode > 2u || band > SWMI_AFF_BAND_MAX) return hipErrorInvalidValue;
+    if (align_mode > 3u || band > SWMI_AFF_BAND_MAX) return hipErrorInvalidValue;
+    // an extend run is walked by global mode's kernels: aff_traceback<AFF_GLOBAL, ..> starts at whatever cell the list names and
+    // makes no use of its being (m, n)
+    if (align_mode == AFF_EXTEND) align_mode = AFF_GLOBAL;
     static void (*const kern[2][3])(TraceArgs, uint32_t, uint32_t) = {      // [long_reads][align_mode]
         {sw_affine_traceback_kernel, sw_affine_traceback_fit_kernel, sw_affine_traceback_global_kernel},
         {sw_affine_traceback_long_kernel, sw_affine_traceback_long_fit_kernel, sw_affine_traceback_long_global_kernel}};

@@ -176,6 +176,9 @@ extern "C" int swmi_set_option(swmi_ctx *ctx, const char *name, int64_t value) {
         if (value < 0 || value > (int64_t)SWMI_AFF_BAND_MAX)
             return fail(SWMI_ERR_INVALID, "band must be 0 (none) or a half-width of 1 .. %u columns, got %lld", SWMI_AFF_BAND_MAX, (long long)value);
         ctx->modes.band = (int)value;
+    } else if (!strcmp(name, "extend")) {
+        if (value != 0 && value != 1) return fail(SWMI_ERR_INVALID, "extend must be 0 or 1, got %lld", (long long)value);
+        ctx->modes.extend = (int)value;
     } else if (!strcmp(name, "arena_words_per_pair")) {
         if (value < 1) return fail(SWMI_ERR_INVALID, "arena_words_per_pair out of range");
         ctx->arena_words_per_pair = (uint64_t)value;

@@ -117,6 +117,9 @@ struct __attribute__((visibility("hidden"))) RunModes {
     int align_mode = SWMI_ALIGN_LOCAL;      // SWMI_ALIGN_FIT / _GLOBAL: end-to-end alignment, on the affine kernels
     int long_reads = 0;                     // 1: the affine kernels take reads longer than 1024 bases, swept in strips (swmi.h)
     int band = 0;                           // > 0: the half-width of the band the strip sweeps of such reads keep to (swmi.h); the affine kernels
+    int extend = 0;                         // 1: seed extension -- a global run whose maximum is taken over every cell (swmi.h); refused in the other modes
+    // the MODE of the affine kernels and their launchers: the align_mode, or 3 (extend) for a global run with option "extend"
+    uint32_t kernel_mode() const { return extend && align_mode == SWMI_ALIGN_GLOBAL ? 3u : (uint32_t)align_mode; }
     bool operator==(const RunModes &o) const { return memcmp(this, &o, sizeof(RunModes)) == 0; }
 };
 static_assert(std::has_unique_object_representations_v<RunModes>, "RunModes is compared bytewise: no padding, no floating point");
@@ -164,7 +167,7 @@ struct swmi_ctx {
     bool cell_cap_set = false;              // cell_cap given by the caller (otherwise small launches get longer lists)
     int32_t gap_open = 0;                   // affine gaps: a gap of length k costs gap_open + k * gap (0: linear)
     int affine = -1;                        // -1: the affine kernels (mode 3) when gap_open != 0; 1: always
-    RunModes modes;                         // options "align_mode", "long_reads" and "band"
+    RunModes modes;                         // options "align_mode", "long_reads", "band" and "extend"
     std::mutex mat_mu;                      // guards `matrix` (not ctx->mu: setting a matrix does not wait for a run)
     std::shared_ptr<const ScoreMatrix> matrix;   // swmi_set_score_matrix; a run with one takes the affine kernels
     // swmi_batch_run_async: one run in flight on the context's own host thread

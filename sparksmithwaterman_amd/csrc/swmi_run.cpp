@@ -265,9 +265,9 @@ static int enqueue_launches(RunState &rs, Launch &L, const ResidentArgs &xa, con
             fl.n_pairs = (uint32_t)plan.aff_n_long; fl.pairs = fa.pairs + fs.n_pairs;
             const uint32_t *mat = b->opt.mat ? b->d_mat.as<uint32_t>() : nullptr;
             const uint32_t nn = b->opt.mat ? b->opt.mat->n + 1u : 0u;
-            HIP_TRY(swmi_launch_affine_sweep(&fs, b->gap_open, (uint32_t)b->opt.modes.align_mode, mat, nn, plan.aff_r_min, plan.aff_r_max, 0u, 0u, ctx->stream));
+            HIP_TRY(swmi_launch_affine_sweep(&fs, b->gap_open, b->opt.modes.kernel_mode(), mat, nn, plan.aff_r_min, plan.aff_r_max, 0u, 0u, ctx->stream));
             // (option "band": the banded strip sweep; the other pairs are swept in full)
-            HIP_TRY(swmi_launch_affine_sweep(&fl, b->gap_open, (uint32_t)b->opt.modes.align_mode, mat, nn, 0u, 0u, 1u, (uint32_t)b->opt.modes.band, ctx->stream));
+            HIP_TRY(swmi_launch_affine_sweep(&fl, b->gap_open, b->opt.modes.kernel_mode(), mat, nn, 0u, 0u, 1u, (uint32_t)b->opt.modes.band, ctx->stream));
         }
         else HIP_TRY(swmi_launch_fill(&fa, ctx->stream, ext ? ctx->ev[0] : nullptr, ext ? ctx->ev[1] : nullptr));
         rs.launches++;
@@ -296,8 +296,8 @@ static int enqueue_launches(RunState &rs, Launch &L, const ResidentArgs &xa, con
         ts.n_pairs = (uint32_t)(np - plan.aff_n_long);
         tl.n_pairs = (uint32_t)plan.aff_n_long; tl.pairs = ta.pairs + ts.n_pairs;
         const uint32_t ops_words = (uint32_t)(((uint64_t)plan.max_path + 15) / 16 + 1);
-        HIP_TRY(swmi_launch_affine_traceback(&ts, (uint32_t)b->opt.modes.align_mode, 0u, 0u, SWMI_AFF_TILE_WORDS, ops_words, ctx->stream));
-        HIP_TRY(swmi_launch_affine_traceback(&tl, (uint32_t)b->opt.modes.align_mode, 1u, (uint32_t)b->opt.modes.band, SWMI_AFF_TILE_WORDS, ops_words, ctx->stream));
+        HIP_TRY(swmi_launch_affine_traceback(&ts, b->opt.modes.kernel_mode(), 0u, 0u, SWMI_AFF_TILE_WORDS, ops_words, ctx->stream));
+        HIP_TRY(swmi_launch_affine_traceback(&tl, b->opt.modes.kernel_mode(), 1u, (uint32_t)b->opt.modes.band, SWMI_AFF_TILE_WORDS, ops_words, ctx->stream));
     } else if (n_res + n_tf < np) {
         HIP_TRY(swmi_launch_traceback(&ta, ctx->stream, ext ? ctx->ev[2] : nullptr, ext ? ctx->ev[3] : nullptr));
     }
@@ -532,9 +532,10 @@ static int check_band(const swmi_ctx *ctx, const swmi_batch *b, const swmi_param
     if ((int64_t)min_n < last_lo)
         return fail(SWMI_ERR_UNSUPPORTED, "band %d: the last strip of the longest read (%llu bases) starts at column %lld, past the end of the "
                     "shortest reference (%llu)", band, (unsigned long long)max_m, (long long)last_lo, (unsigned long long)min_n);
-    // global mode: the one cell (m, n) must lie in the band, n <= 1024 NS + w
+    // global mode: the one cell (m, n) must lie in the band, n <= 1024 NS + w (option "extend": the end cell is free -- the
+    // maximum is taken over the in-band cells, and the reference may run on past the band)
     const uint64_t min_rows = (uint64_t)SWMI_AFF_MAX_READ * swmi_aff_strips((uint32_t)min_long);
-    if (align_mode == SWMI_ALIGN_GLOBAL && max_n > min_rows + (uint64_t)w)
+    if (align_mode == SWMI_ALIGN_GLOBAL && !md.extend && max_n > min_rows + (uint64_t)w)
         return fail(SWMI_ERR_UNSUPPORTED, "band %d, align_mode global: the end of the longest reference (%llu) lies outside the band of a read of "
                     "%llu bases (at most %llu)", band, (unsigned long long)max_n, (unsigned long long)min_long, (unsigned long long)(min_rows + w));
     // the arithmetic bounds of a banded run: half of an unbanded run's, which leaves room for the value of a cell outside the band
@@ -568,6 +569,9 @@ static int check_run_params(const swmi_ctx *ctx, const swmi_batch *b, const swmi
     // cells; that behaviour is not reproduced.
     if (p->types[0] == p->types[1] || p->types[0] == p->types[2] || p->types[1] == p->types[2])
         return fail(SWMI_ERR_UNSUPPORTED, "alignTypes a/i/d must be pairwise distinct");
+    // option "extend" is global mode's sweep with another choice of maximum cells: there is no such sweep for local and fit
+    if (md.extend && md.align_mode != SWMI_ALIGN_GLOBAL)
+        return fail(SWMI_ERR_UNSUPPORTED, "extend = 1 needs align_mode global (2), got align_mode %d", md.align_mode);
     uint64_t max_m, max_n;
     if (affine) {
         // the bounds within which every sum of the affine recurrence fits int32 (DESIGN.md "Affine gaps")

@@ -176,6 +176,8 @@ def _rank_main(args):
             ctx.set_option("long_reads", 1)
         if args.band:                                       # ... inside a band around the diagonal
             ctx.set_option("band", args.band)
+        if args.extend:                                     # seed extension: the global sweep, ended at the best cell
+            ctx.set_option("extend", 1)
         if args.matrix:                                     # substitution scores on this rank's context (NCBI text format)
             from . import matrix as _matrix
             ctx.set_score_matrix(_matrix.load(args.matrix))
@@ -198,7 +200,14 @@ def _rank_main(args):
 
 def _parser():
     import argparse
-    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+
+    class Parser(argparse.ArgumentParser):
+        def parse_args(self, args=None, namespace=None):
+            ns = super().parse_args(args, namespace)
+            if ns.extend and ns.align_mode != "global":
+                self.error("--extend requires --align-mode global")
+            return ns
+    ap = Parser(description=__doc__.split("\n")[0])
     ap.add_argument("--ref-dir", required=True)
     ap.add_argument("--in-dir", required=True)
     ap.add_argument("--out-dir", required=True)
@@ -222,6 +231,10 @@ def _parser():
     ap.add_argument("--band", type=int, default=0, metavar="W",
                     help="with --long-reads: align a read longer than 1024 bases inside the band |j - i| <= W only, rounded outwards to "
                          "strips of 1024 rows (option band); runs on the affine kernels.  0 (the default): no band")
+    ap.add_argument("--extend", action="store_true",
+                    help="with --align-mode global: seed extension (option extend) -- the alignment is anchored at the start of the read "
+                         "and of the reference and ends at the cell with the best score, the tails left unaligned; for left extension "
+                         "reverse both sequences")
     ap.add_argument("--tie", choices=("serial", "strict"), default="serial",
                     help="serial: SmithWaterman's aligner (NoDistribution, DistributeReference); strict: DistributedSW's (DistributeAlgorithm)")
     ap.add_argument("--stream-chunk-bytes", type=int, default=512 << 10, help="sequence bytes per streamed chunk")

@@ -35,18 +35,21 @@ def _algo(align_scores, align_types):
 
 
 @_contextlib.contextmanager
-def _scores(ctx, align_scores, align_mode=None, long_reads=None, band=None):
+def _scores(ctx, align_scores, align_mode=None, long_reads=None, band=None, extend=None):
     """alignScores {match, mismatch, gap} or {match, mismatch, gap, gapOpen}: yields the three entries make_params takes
     and, for four, sets the context's "gap_open" for the call (affine gaps: a gap of length k costs gapOpen + k * gap).
     align_mode (ALIGN_LOCAL / ALIGN_FIT / ALIGN_GLOBAL, or None: the context's own) is set for the call in the same way;
     long_reads (True / False, or None: the context's own) likewise sets option "long_reads": reads longer than 1024 bases on the
-    affine kernels; band (a half-width, 0: none, or None: the context's own) sets option "band".  The options are put back
+    affine kernels; band (a half-width, 0: none, or None: the context's own) sets option "band"; extend (True / False, or None:
+    the context's own) sets option "extend": seed extension, with align_mode ALIGN_GLOBAL only.  The options are put back
     afterwards."""
     sc = tuple(int(x) for x in align_scores)
     if len(sc) == 4 and sc[3] > 0:
         raise ValueError("gapOpen (alignScores[3]) must be <= 0, got %d" % sc[3])
     if align_mode is not None and align_mode not in (_capi.ALIGN_LOCAL, _capi.ALIGN_FIT, _capi.ALIGN_GLOBAL):
         raise ValueError("align_mode must be ALIGN_LOCAL, ALIGN_FIT or ALIGN_GLOBAL, got %r" % (align_mode,))
+    if extend is not None and extend is not True and extend is not False:
+        raise ValueError("extend must be None, True or False, got %r" % (extend,))
     restore = []
     try:
         if len(sc) == 4:
@@ -61,6 +64,9 @@ def _scores(ctx, align_scores, align_mode=None, long_reads=None, band=None):
         if band is not None:
             restore.append(("band", ctx.options.get("band", 0)))
             ctx.set_option("band", int(band))
+        if extend is not None:
+            restore.append(("extend", ctx.options.get("extend", 0)))
+            ctx.set_option("extend", 1 if extend else 0)
         yield sc[:3]
     finally:
         for name, prev in reversed(restore):
@@ -72,16 +78,17 @@ class SmithWaterman:
         """Function3<String[], int[], char[], Tuple2<Integer, ArrayList<Tuple2<Integer,String[]>>>>."""
         tie_mode = _capi.TIE_SERIAL
 
-        def __init__(self, context=None, align_mode=None, long_reads=None, band=None):
+        def __init__(self, context=None, align_mode=None, long_reads=None, band=None, extend=None):
             self._ctx = context
             self._align_mode = align_mode       # ALIGN_FIT / ALIGN_GLOBAL: end-to-end alignment (option "align_mode")
             self._long_reads = long_reads       # True: reads longer than 1024 bases on the affine kernels (option "long_reads")
             self._band = band                   # a half-width: such reads inside the band |j - i| <= band only (option "band")
+            self._extend = extend               # True: seed extension, with ALIGN_GLOBAL -- anchored at the start, ends at the best cell (option "extend")
 
         def call(self, seqs, alignScores=None, alignTypes=None):
             ctx = self._ctx or default_context()
             sc, ty = _algo(alignScores, alignTypes)
-            with _scores(ctx, sc, self._align_mode, self._long_reads, self._band) as sc3:
+            with _scores(ctx, sc, self._align_mode, self._long_reads, self._band, self._extend) as sc3:
                 b = ctx.upload([seqs[0]], [seqs[1]])
                 try:
                     b.run(make_params(sc3, ty, self.tie_mode))
@@ -111,9 +118,10 @@ class Distribution:
         together; results come back in input order, each exactly what MapRef.call returns.
         """
 
-        def __init__(self, context=None, tie_mode=_capi.TIE_SERIAL, align_mode=None, long_reads=None, band=None):
+        def __init__(self, context=None, tie_mode=_capi.TIE_SERIAL, align_mode=None, long_reads=None, band=None, extend=None):
             self._ctx = context
             self._band = band
+            self._extend = extend
             self._tie = tie_mode
             self._align_mode = align_mode
             self._long_reads = long_reads
@@ -129,7 +137,7 @@ class Distribution:
             for idxs in groups.values():
                 _, reads, algo = tuples[idxs[0]]
                 sc, ty = _algo(*(algo if algo is not None else (None, None)))
-                with _scores(ctx, sc, self._align_mode, self._long_reads, self._band) as sc3:
+                with _scores(ctx, sc, self._align_mode, self._long_reads, self._band, self._extend) as sc3:
                     b = ctx.upload([tuples[i][0][1] for i in idxs], list(reads))
                     try:
                         b.run(make_params(sc3, ty, self._tie))
@@ -142,8 +150,8 @@ class Distribution:
     class MapRef:
         """PairFunction<Tuple3<String[], ArrayList<String>, Tuple2<int[],char[]>>, Integer, Tuple2<...>>."""
 
-        def __init__(self, context=None, tie_mode=_capi.TIE_SERIAL, align_mode=None, long_reads=None, band=None):
-            self._mp = Distribution.MapPartition(context, tie_mode, align_mode, long_reads, band)
+        def __init__(self, context=None, tie_mode=_capi.TIE_SERIAL, align_mode=None, long_reads=None, band=None, extend=None):
+            self._mp = Distribution.MapPartition(context, tie_mode, align_mode, long_reads, band, extend)
 
         def call(self, tuple3):
             return self._mp.call([tuple3])[0]
@@ -188,9 +196,10 @@ class _FileDriver:
     REF_DIR, IN_DIR = "/home/ubuntu/project/reference", "/home/ubuntu/project/input"   # :43-44
     OUT_DIR = "/home/ubuntu/project/output/reference"                 # :50
 
-    def __init__(self, context=None, tie_mode=_capi.TIE_SERIAL, align_mode=None, long_reads=None, band=None):
+    def __init__(self, context=None, tie_mode=_capi.TIE_SERIAL, align_mode=None, long_reads=None, band=None, extend=None):
         self._ctx = context
         self._band = band
+        self._extend = extend
         self._tie = tie_mode
         self._align_mode = align_mode
         self._long_reads = long_reads
@@ -207,7 +216,7 @@ class _FileDriver:
             out_ext = ioArgs[5] if ioArgs[5] is not None else out_ext
         sc, ty = _algo(*(algoArgs if algoArgs is not None else (None, None)))
         ctx = self._ctx or default_context()
-        with _scores(ctx, sc, self._align_mode, self._long_reads, self._band) as sc3:
+        with _scores(ctx, sc, self._align_mode, self._long_reads, self._band, self._extend) as sc3:
             return self._run(ctx, make_params(sc3, ty, self._tie), ref_dir, in_dir, delim, out_dir, out_name, out_ext)
 
     def _run(self, ctx, params, ref_dir, in_dir, delim, out_dir, out_name, out_ext):
