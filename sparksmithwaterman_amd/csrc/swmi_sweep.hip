@@ -334,15 +334,43 @@ __device__ __forceinline__ void sweep_fast(const FillArgs &A, const PairDesc pd,
         pair_max = pair_max > wm ? pair_max : wm;
         S.lmax = -1;
     };
+    // The sweep in three parts.  HEAD: the blocks of a chunk's halo (windows before g_lo: no checkpoint, no maximum) and
+    // whatever else is not steady; STEADY: the windows from g_lo on whose 32 steps all keep lane 0 inside the reference, one
+    // pass of SweepWindowAsm's loop each -- checkpoint, reference loads, steps, window maximum and loop control in one
+    // generated statement (tools/gen_step.py); TAIL: the remaining blocks, block by block like the head.
+    int steady_max = -1;                                  // per lane: maximum over the steady windows (lanes with rows)
+    bool closed = false;                                  // the window before block tb is closed already (by the steady part)
     for (uint32_t tb = 0; tb < nblk; ++tb) {
-        const uint4 w = wnext;                            // base codes of (local) columns 16tb+1 .. 16tb+16
-        wnext = refq[tb + 1];                             // prefetch (images are padded)
         const uint32_t tbg = tb + (col0 >> 4);            // the block's number in the pair's own sweep
         if ((tbg % SWMI_CK_BLOCKS) == 0u) {
             const uint32_t g = tbg / SWMI_CK_BLOCKS;
-            if (tb > 0u) {
+            if (tb > 0u && !closed) {
                 if (g > g_lo) close_window(g - 1u); else S.lmax = -1;
             }
+            closed = false;
+#if !defined(SWMI_NO_ASM) && SWMI_CK_BLOCKS == 2u
+            const uint32_t nwin = n > 16u * tb ? (n - 16u * tb) / 32u : 0u;     // windows ahead with 16 * block + 15 < n for both blocks
+            if (g >= g_lo && nwin > 0u) {
+                // byte offsets from the pair's workspace: the checkpoint of window g (this lane's column of it), the maximum
+                // of window g - 1 (stored one pass late; the first pass stores nothing); from the reference image: block tb
+                uint32_t cko = (g * (uint32_t)(R + 2) * WAVE + lane) * 4u;
+                uint32_t wmo = ((uint32_t)G.wmax_off + g - 1u) * 4u;
+                uint32_t rfo = tb * 16u;
+                const uint32_t lact_s = uni(lact);
+                int wm_last;
+                uint32_t wx = wnext.x, wy = wnext.y, wz = wnext.z, ww = wnext.w;
+                SweepWindowAsm<R>::run(S.h, S.g, S.hp, S.q, S.rbx, S.rby, wx, wy, wz, ww, one, gm, S.lmax, wm_last, steady_max,
+                                       cko, wmo, rfo, uni64((uint64_t)(uintptr_t)(A.dir + pd.dir_off)), uni64((uint64_t)(uintptr_t)refq),
+                                       lact_s >= WAVE ? ~0ull : (1ull << lact_s) - 1ull, uni(nwin - 1u));
+                wnext = make_uint4(wx, wy, wz, ww);       // the block after the last steady window
+                // the last window's maximum is still one value per lane (already without the lanes that hold no rows)
+                const int wm = wave_max_i32(wm_last);
+                if (lane == 0) A.dir[pd.dir_off + G.wmax_off + g + nwin - 1u] = (uint32_t)wm;
+                tb += 2u * nwin - 1u;
+                closed = true;
+                continue;
+            }
+#endif
             if (g >= g_lo) {
                 // checkpoint in the layout the replay expects: H of the rows, the N received one step earlier, the
                 // reference operand of the last step ([ck][slot][lane], 256 B stores)
@@ -353,6 +381,8 @@ __device__ __forceinline__ void sweep_fast(const FillArgs &A, const PairDesc pd,
                 ck[(R + 1) * WAVE] = (uint32_t)S.rby;
             }
         }
+        const uint4 w = wnext;                            // base codes of (local) columns 16tb+1 .. 16tb+16
+        wnext = refq[tb + 1];                             // prefetch (images are padded)
         const uint32_t t0 = 16u * tb;
 #ifndef SWMI_NO_ASM
         if (t0 + 15u < n) {
@@ -368,9 +398,13 @@ __device__ __forceinline__ void sweep_fast(const FillArgs &A, const PairDesc pd,
             sweep_tail_block<R>(S, w, wnext.x, t0, lane_eff, n, one, gm);
         }
     }
-    {
+    if (!closed) {
         const uint32_t gl = (nblk - 1u + (col0 >> 4)) / SWMI_CK_BLOCKS;
         if (gl >= g_lo) close_window(gl);
+    }
+    {
+        const int sm = wave_max_i32(steady_max);
+        pair_max = pair_max > sm ? pair_max : sm;
     }
     if (lane != 0) return;
     if (A.dbg) {      // diagnostics: where the wave ran (HW_ID: wave, SIMD, CU, SE ...) and how long

@@ -25,6 +25,12 @@ Hazards the script enforces by construction (it simulates the previous step's ta
 pads with s_nop where an instruction order cannot avoid it):
   * v_dot* result read by another VALU opcode: 3 wait states;
   * a VGPR written by a VALU and read through DPP (or overwritten by a DPP mov): 2 wait states.
+
+SweepWindowAsm<R> (window_body, emit_window) wraps 32 of these steps -- one steady checkpoint window -- and everything the
+window needs into the body of a scalar loop inside ONE statement: the checkpoint stores, the reference loads (two register
+sets, one per half of the window, each reloaded while the other half runs), the window maximum (copied under the lane mask,
+reduced by DPP steps spread between the next window's cell instructions, stored by lane 63 under a one-lane exec) and the
+loop control.  The body's hazards are checked against itself as its own predecessor.
 """
 import os
 import sys
@@ -41,21 +47,22 @@ SGPR_WAIT = 2     # gfx940/gfx950: a VALU writes an SGPR, a VALU reads it
 
 
 class Ins:
-    def __init__(self, text, wr=(), rd=(), dot=(), dpp_rd=(), dpp_wr=(), sg_wr=(), sg_rd=()):
+    def __init__(self, text, wr=(), rd=(), dot=(), dpp_rd=(), dpp_wr=(), sg_wr=(), sg_rd=(), ex=False):
         self.text = text
         self.wr, self.rd, self.dot, self.dpp_rd, self.dpp_wr = tuple(wr), tuple(rd), tuple(dot), tuple(dpp_rd), tuple(dpp_wr)
         self.sg_wr, self.sg_rd = tuple(sg_wr), tuple(sg_rd)      # SGPR pairs written by a VALU (v_cmp) / read by a VALU (v_addc)
+        self.ex = ex                                             # writes exec
         self.states = 1
 
 
-def stream(R, odd, feed_byte, tail=False):
-    """instruction list of one step; register names are asm operand names.  Even steps read h / write g and consume
+def stream(R, odd, feed_byte, tail=False, wf=("%[wf0]", "%[wf1]")):
+    """instruction list of one step; register names are asm operand names (wf: the two reference words of the step's group).  Even steps read h / write g and consume
     rbx / prepare rby; odd steps the other way round.  tail: the step of a block in which some lanes have run past the last
     column -- they compute values nobody reads, but their window maximum must not see them: it is updated under a lane
     mask (v_cmp once per step, v_cndmask per update)."""
     H, G = ("g", "h") if odd else ("h", "g")
     RB, RBN = ("rby", "rbx") if odd else ("rbx", "rby")
-    WF = "wf1" if feed_byte == 0 else "wf0"          # the last step of a group of four is fed from the next dword
+    WF = wf[1] if feed_byte == 0 else wf[0]          # the last step of a group of four is fed from the next dword
     hin = lambda k: f"%[{H}{k}]"
     hout = lambda k: f"%[{G}{k}]"
     hp = lambda k: f"%[p{k}]"
@@ -70,7 +77,7 @@ def stream(R, odd, feed_byte, tail=False):
             ins.append(Ins(f"v_dot8c_i32_i4_e32 {hin(k-1)}, %[q{k}], %[{RB}]", wr=[an(k)], dot=[an(k)], rd=[f"q{k}", RB, f"{H}{k-1}"]))
         else:
             ins.append(Ins(f"v_dot8_i32_i4 %[a{k}], %[q{k}], %[{RB}], {hin(k-1)}", wr=[f"a{k}"], dot=[f"a{k}"], rd=[f"q{k}", RB, f"{H}{k-1}"]))
-    ins.append(Ins(f"v_lshlrev_b32_sdwa %[{RBN}], %[{WF}], %[one] dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_{feed_byte} src1_sel:DWORD",
+    ins.append(Ins(f"v_lshlrev_b32_sdwa %[{RBN}], {WF}, %[one] dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_{feed_byte} src1_sel:DWORD",
                    wr=[RBN], rd=[WF, "one"]))
     ins.append(Ins(f"v_max_i32_dpp %[x], {hp(R-1)}, {hp(0)} {dpp}", wr=["x"], rd=["p0"], dpp_rd=[f"p{R-1}"]))
     ins.append(Ins(f"v_add_u32_dpp %[a0], {hout(R-1)}, %[s0] {dpp}", wr=["a0"], rd=["s0"], dpp_rd=[f"{G}{R-1}"]))
@@ -285,6 +292,101 @@ def emit_tail(R, ph):
     L.append("};")
     return "\n".join(L)
 
+WORD_VGPR = 56    # v[56:63]: the two 16-byte reference words of a window (fixed: an asm operand cannot name a dword of a tuple)
+
+
+def window_body(R):
+    """the loop body of SweepWindowAsm: one steady checkpoint window = checkpoint, 32 steps, window maximum.
+    Returns (instructions with hazards padded, s_nop count)."""
+    A = [f"v{WORD_VGPR + i}" for i in range(4)]          # columns 1..16 of the window (and, reloaded, of the next one)
+    B = [f"v{WORD_VGPR + 4 + i}" for i in range(4)]      # columns 17..32
+    words = A + B + [A[0]]
+    dppz = "wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:0"
+    top = [Ins(f"v_mov_b32_dpp %[t], %[g{R-1}] {dppz}", wr=["t"], dpp_rd=[f"g{R-1}"])]       # the N received one step earlier
+    for k in range(R):
+        top.append(Ins(f"global_store_dword %[cko], %[h{k}], %[dirb] offset:{256 * k}", rd=[f"h{k}", "cko"]))
+    top.append(Ins(f"global_store_dword %[cko], %[t], %[dirb] offset:{256 * R}", rd=["t", "cko"]))
+    top.append(Ins(f"global_store_dword %[cko], %[rby], %[dirb] offset:{256 * (R + 1)}", rd=["rby", "cko"]))
+    top.append(Ins(f"global_load_dwordx4 v[{WORD_VGPR + 4}:{WORD_VGPR + 7}], %[rfo], %[refb] offset:16", wr=B, rd=["rfo"]))
+    top.append(Ins(f"v_add_u32_e32 %[cko], {256 * (R + 2)}, %[cko]", wr=["cko"], rd=["cko"]))
+    # the previous window's maximum: six reducing steps on the masked copy, each between cell instructions that cover its
+    # two wait states; lane 63 ends up holding it and stores it (exec = that lane, or no lane in the loop's first pass)
+    red = [Ins(f"v_max_i32_dpp %[scr], %[scr], %[scr] {c} bank_mask:0xf", wr=["scr"], dpp_rd=["scr"])
+           for c in ("row_shr:1 row_mask:0xf", "row_shr:2 row_mask:0xf", "row_shr:4 row_mask:0xf", "row_shr:8 row_mask:0xf",
+                     "row_bcast:15 row_mask:0xa", "row_bcast:31 row_mask:0xc")]
+    put = [Ins("s_mov_b64 exec, %[smask]", ex=True),
+           Ins("global_store_dword %[wmo], %[scr], %[dirb]", rd=["scr", "wmo"]),
+           Ins("s_mov_b64 exec, %[sexec]", ex=True)]
+    steps = []
+    for s in range(32):
+        one = stream(R, s & 1, (s + 1) & 3, wf=(words[s // 4], words[s // 4 + 1]))
+        if s in (15, 31):          # the step's feed is the first use of a word loaded 15 steps earlier (the stores before it are long done)
+            one.insert(0, Ins("s_waitcnt vmcnt(0)"))
+        if s == 16:                # the first word's last reader was step 14: the next window's takes its place
+            one.insert(0, Ins(f"global_load_dwordx4 v[{WORD_VGPR}:{WORD_VGPR + 3}], %[rfo], %[refb] offset:32", wr=A, rd=["rfo"]))
+        steps += one
+    body = top
+    for i, ins in enumerate(steps):
+        body.append(ins)
+        if i % 3 == 2 and red:
+            body.append(red.pop(0))
+            if not red:
+                body += put
+    body += [Ins("v_cndmask_b32_e64 %[scr], -1, %[lm], %[lmask]", wr=["scr"], rd=["lm"]),      # lanes without rows are left out
+             Ins("v_mov_b32_e32 %[lm], -1", wr=["lm"]),
+             Ins("v_max_i32_e32 %[pm], %[pm], %[scr]", wr=["pm"], rd=["pm", "scr"]),
+             Ins("v_add_u32_e32 %[rfo], 32, %[rfo]", wr=["rfo"], rd=["rfo"]),
+             Ins("v_add_u32_e32 %[wmo], 4, %[wmo]", wr=["wmo"], rd=["wmo"]),
+             Ins("s_mov_b64 %[smask], %[s63]"),
+             Ins("s_sub_u32 %[cnt], %[cnt], 1"),
+             Ins("s_cbranch_scc0 .Lswmi_window_%=")]
+    out = pad_hazards(body[-8:], body)                   # the body follows itself
+    # while exec is narrowed nothing but the store may issue, and the store follows the narrowing directly
+    for i, ins in enumerate(out):
+        if ins.ex and "smask" in ins.text:
+            assert out[i + 1].text.startswith("global_store_dword") and out[i + 2].ex, "exec is narrowed around the store alone"
+    return out, sum(1 for i in out if i.text.startswith("s_nop"))
+
+
+def emit_window(R, n_valu4):
+    """one steady checkpoint window per pass of a scalar loop, the loop inside ONE asm statement"""
+    body, n_nop = window_body(R)
+    n_all = len(body)
+    L = []
+    L.append(f"// R={R}: one window of 32 steps, {n_all} instructions = 8 x {n_valu4} + {n_all - 8 * n_valu4}, {n_nop} s_nop  ({n_all / 32:.2f} per step)")
+    L.append(f"template <> struct SweepWindowAsm<{R}> {{")
+    L.append(f"    static __device__ __forceinline__ void run(int (&h)[{R}], int (&g)[{R}], int (&hp)[{R}], const int (&q)[{R}], int &rbx, int &rby,")
+    L.append(f"                                               uint32_t &w0, uint32_t &w1, uint32_t &w2, uint32_t &w3, const int one, const uint32_t gm,")
+    L.append(f"                                               int &lm, int &scr, int &pm, uint32_t &cko, uint32_t &wmo, uint32_t &rfo,")
+    L.append(f"                                               const uint64_t dirb, const uint64_t refb, const uint64_t lmask, uint32_t cnt) {{")
+    L.append("        int s0, a0, x, t" + "".join(f", a{k}" for k in range(1, R)) + ";")
+    L.append("        unsigned long long smask, s63, sexec;")
+    L.append("        asm volatile(")
+    pro = ["s_nop 4",                                   # the scalar operands may come straight from v_readfirstlane
+           "s_mov_b64 %[sexec], exec", "s_lshl_b64 %[s63], 1, 63", "s_mov_b64 %[smask], 0",
+           f"v_mov_b32_e32 v{WORD_VGPR}, %[w0]", f"v_mov_b32_e32 v{WORD_VGPR + 1}, %[w1]",
+           f"v_mov_b32_e32 v{WORD_VGPR + 2}, %[w2]", f"v_mov_b32_e32 v{WORD_VGPR + 3}, %[w3]",
+           "v_mov_b32_e32 %[scr], -1", ".Lswmi_window_%=:"]
+    epi = [f"v_mov_b32_e32 %[w0], v{WORD_VGPR}", f"v_mov_b32_e32 %[w1], v{WORD_VGPR + 1}",
+           f"v_mov_b32_e32 %[w2], v{WORD_VGPR + 2}", f"v_mov_b32_e32 %[w3], v{WORD_VGPR + 3}"]
+    for t in pro + [i.text for i in body] + epi:
+        L.append(f'            "{t}\\n\\t"')
+    outs = [f'[h{k}] "+v"(h[{k}])' for k in range(R)] + [f'[g{k}] "+v"(g[{k}])' for k in range(R)]
+    outs += [f'[p{k}] "+v"(hp[{k}])' for k in range(R)]
+    outs += ['[rbx] "+v"(rbx)', '[rby] "+v"(rby)', '[lm] "+v"(lm)', '[pm] "+v"(pm)', '[cko] "+v"(cko)', '[wmo] "+v"(wmo)', '[rfo] "+v"(rfo)']
+    outs += ['[w0] "+v"(w0)', '[w1] "+v"(w1)', '[w2] "+v"(w2)', '[w3] "+v"(w3)', '[cnt] "+s"(cnt)']
+    outs += ['[scr] "=&v"(scr)', '[s0] "=&v"(s0)', '[a0] "=&v"(a0)', '[x] "=&v"(x)', '[t] "=&v"(t)']
+    outs += [f'[a{k}] "=&v"(a{k})' for k in range(1, R)]
+    outs += ['[smask] "=&s"(smask)', '[s63] "=&s"(s63)', '[sexec] "=&s"(sexec)']
+    ins_ = [f'[q{k}] "v"(q[{k}])' for k in range(R)]
+    ins_ += ['[one] "v"(one)', '[gm] "s"(gm)', '[dirb] "s"(dirb)', '[refb] "s"(refb)', '[lmask] "s"(lmask)']
+    L.append("            : " + ", ".join(outs))
+    L.append("            : " + ", ".join(ins_))
+    L.append('            : "memory", "scc", ' + ", ".join(f'"v{WORD_VGPR + i}"' for i in range(8)) + ");")
+    L.append("    }")
+    L.append("};")
+    return "\n".join(L), n_all, n_nop
+
 
 def main():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -292,11 +394,21 @@ def main():
     parts = ["// GENERATED by tools/gen_step.py -- do not edit; re-run the script instead.",
              "// Four anti-diagonal steps of the mode-1 score sweep per specialisation (see the script's docstring).",
              "template <int R> struct SweepStep4Asm;", ""]
+    per4 = {}
     for R in (1, 2, 3, 4):
         text, nv, nn = emit(R)
+        per4[R] = nv + nn
         parts.append(text)
         parts.append("")
         print(f"R={R}: {(nv + nn) / 4:.2f} instructions per step ({(nv + nn) / 4 / R:.2f} per cell), {nn} s_nop per 4 steps")
+    parts += ["// A whole steady checkpoint window per pass of a scalar loop, the loop and all of the window's bookkeeping inside one",
+              "// statement: checkpoint stores, reference loads, window maximum, loop control (see window_body in the script).",
+              "template <int R> struct SweepWindowAsm;", ""]
+    for R in (1, 2, 3, 4):
+        text, na, nn = emit_window(R, per4[R])
+        parts.append(text)
+        parts.append("")
+        print(f"R={R} window: {na} instructions per 32 steps, {na - 8 * per4[R]} outside the steps, {nn} s_nop")
     parts += ["// The same step for the blocks at the end of a sweep, where lanes run past the last column: one step per statement,",
               "// the window maximum updated under a lane mask (see the script's docstring).",
               "template <int R, int PH> struct SweepStepTailAsm;", ""]
