@@ -1,4 +1,4 @@
-"""The affine-gap contract without a GPU: the two restatements in tests/affine_reference.py against each other, against the
+"""The affine-gap contract without a GPU: the two restatements in tests/gotoh_reference.py against each other, against the
 oracle at gap_open = 0, and against the hand-checked known answers (tests/golden/affine_kat.json); the host mirror's
 four-entry alignScores."""
 import json
@@ -9,7 +9,7 @@ import pytest
 
 from oracle import sw_oracle as orc
 
-import affine_reference as ar
+import gotoh_reference as gr
 import limit_cases as lc
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -39,7 +39,7 @@ def test_restatements_agree(tie):
             ref = (_rand(rng, rng.randint(2, 5), "ACGT") * 8)[:rng.randint(8, 40)]      # periodic: tied maxima
         read = _rand(rng, rng.randint(0, 16), alphabet)
         sc = (rng.randint(1, 6), rng.randint(-5, 0), rng.randint(-4, 0), rng.choice([0, -1, -2, -6, -12]))
-        assert ar.align_scalar(ref, read, sc, tie) == ar.align_numpy(ref, read, sc, tie), (ref, read, sc)
+        assert gr.align_scalar(ref, read, sc, tie_mode=tie) == gr.align_numpy(ref, read, sc, tie_mode=tie), (ref, read, sc)
 
 
 @pytest.mark.parametrize("tie", [0, 1])
@@ -50,8 +50,8 @@ def test_gap_open_zero_is_the_linear_oracle(tie, kats):
             continue
         sc = tuple(k["scores"]) + (0,)
         exp = (k["score"], [(a[0], (a[1], a[2])) for a in k["alignments"]])
-        assert ar.align_scalar(k["ref"], k["read"], sc, tie) == exp, k["name"]
-        assert ar.align_numpy(k["ref"], k["read"], sc, tie) == exp, k["name"]
+        assert gr.align_scalar(k["ref"], k["read"], sc, tie_mode=tie) == exp, k["name"]
+        assert gr.align_numpy(k["ref"], k["read"], sc, tie_mode=tie) == exp, k["name"]
         n += 1
     assert n >= 3
     rng = random.Random(200 + tie)
@@ -59,8 +59,8 @@ def test_gap_open_zero_is_the_linear_oracle(tie, kats):
         ref, read = _rand(rng, rng.randint(0, 60), "ACGT"), _rand(rng, rng.randint(0, 25), "ACGT")
         sc = (rng.randint(1, 5), rng.randint(-4, 0), rng.randint(-5, 0))
         exp = _oracle(ref, read, sc, tie)
-        assert ar.align_numpy(ref, read, sc + (0,), tie) == exp
-        assert ar.align_scalar(ref, read, sc + (0,), tie) == exp
+        assert gr.align_numpy(ref, read, sc + (0,), tie_mode=tie) == exp
+        assert gr.align_scalar(ref, read, sc + (0,), tie_mode=tie) == exp
 
 
 def test_affine_kats():
@@ -69,20 +69,20 @@ def test_affine_kats():
     for k in kats:
         sc = tuple(k["scores"])
         exp = (k["score"], [(a[0], (a[1], a[2])) for a in k["alignments"]])
-        got = ar.align_scalar(k["ref"], k["read"], sc, k["tie_mode"], matrices=True)
+        got = gr.align_scalar(k["ref"], k["read"], sc, tie_mode=k["tie_mode"], matrices=True)
         assert got[:2] == exp, k["name"]
-        assert ar.align_numpy(k["ref"], k["read"], sc, k["tie_mode"]) == exp, k["name"]
+        assert gr.align_numpy(k["ref"], k["read"], sc, tie_mode=k["tie_mode"]) == exp, k["name"]
         H, E, F, D, XE, XF = got[2:]
         assert H == k["H"], k["name"]
-        assert [[None if v <= ar.NEG // 2 else v for v in row] for row in E] == k["E"], k["name"]
-        assert [[None if v <= ar.NEG // 2 else v for v in row] for row in F] == k["F"], k["name"]
+        assert [[None if v == gr.NINF else v for v in row] for row in E] == k["E"], k["name"]
+        assert [[None if v == gr.NINF else v for v in row] for row in F] == k["F"], k["name"]
         assert ["".join(r) for r in D] == k["T"], k["name"]
         assert ["".join(str(x) for x in r) for r in XE] == k["xE"], k["name"]
         assert ["".join(str(x) for x in r) for r in XF] == k["xF"], k["name"]
     by = {k["name"]: k for k in kats}
     # o changes the path: the same pair with o = 0 splits the gap
     k1 = by["AKAT-1"]
-    assert ar.align_scalar(k1["ref"], k1["read"], tuple(k1["scores"][:3]) + (0,))[1] != ar.align_scalar(k1["ref"], k1["read"], tuple(k1["scores"]))[1]
+    assert gr.align_scalar(k1["ref"], k1["read"], tuple(k1["scores"][:3]) + (0,))[1] != gr.align_scalar(k1["ref"], k1["read"], tuple(k1["scores"]))[1]
     assert by["AKAT-3s"]["alignments"] != by["AKAT-3t"]["alignments"]
     assert by["AKAT-4"]["score"] == 0 and len(by["AKAT-4"]["alignments"]) == len(by["AKAT-4"]["ref"]) * len(by["AKAT-4"]["read"])
     assert by["AKAT-5"]["alignments"] == []
@@ -94,12 +94,12 @@ def test_restatements_agree_at_the_score_bounds(tie):
     ints, which keeps the numpy restatement trustworthy where tests/test_affine_gpu.py leans on it"""
     for sc in lc.AFFINE_BOUND_SCORES:
         ref, read = lc.affine_bound_pair(160, 40, 20)
-        got = ar.align_scalar(ref, read, sc, tie)
-        assert got == ar.align_numpy(ref, read, sc, tie), sc
+        got = gr.align_scalar(ref, read, sc, tie_mode=tie)
+        assert got == gr.align_numpy(ref, read, sc, tie_mode=tie), sc
         assert got[0] >= 40 * lc.L
     read = lc.rand_seq(random.Random(1410), 96, "AC")
     sc = lc.AFFINE_BOUND_SCORES[0]
-    assert ar.align_scalar(read, read, sc, tie) == ar.align_numpy(read, read, sc, tie) == (96 * lc.L, [(1, (read, read))])
+    assert gr.align_scalar(read, read, sc, tie_mode=tie) == gr.align_numpy(read, read, sc, tie_mode=tie) == (96 * lc.L, [(1, (read, read))])
 
 
 class _FakeBatch:

@@ -5,13 +5,10 @@ import itertools
 
 import pytest
 
-import affine_reference as ar
-import band_reference as br
-import ends_reference as er
-import matrix_reference as mr
 import affine_grid_cases as gc
+import gotoh_reference as gr
 
-GAP = ar.GAP_CHAR
+GAP = gr.GAP_CHAR
 _NUMPY = {}
 
 
@@ -20,15 +17,13 @@ def _numpy(matrix, R, mode, tie):
     key = (matrix, R, mode, tie)
     if key not in _NUMPY:
         _, ref, read = gc.walk_grid(matrix)[R - 1]
-        _NUMPY[key] = er.align_numpy(ref, read, gc.WALK_SCORES, mode, tie, gc.score_matrix() if matrix else None)
+        _NUMPY[key] = gr.align_numpy(ref, read, gc.WALK_SCORES, mode, tie_mode=tie, matrix=gc.score_matrix() if matrix else None)
     return _NUMPY[key]
 
 
 def _scalar(ref, read, sc, mode, tie, matrix=None):
-    """the plain-loop restatement (ends_reference.align_scalar hands local mode to the numpy form: take the scalar one)"""
-    if mode != 0:
-        return er.align_scalar(ref, read, sc, mode, tie, matrix)
-    return ar.align_scalar(ref, read, sc, tie) if matrix is None else mr.align_scalar(ref, read, sc, matrix, tie)
+    """the plain-loop restatement"""
+    return gr.align_scalar(ref, read, sc, mode, tie_mode=tie, matrix=matrix)
 
 
 def _walk_ties(R, mode):
@@ -85,7 +80,7 @@ def test_shape_grid_sample_scalar_and_numpy_agree(matrix):
         for mode in (0, 1, 2):
             for tie in (((q // 3 + mode) % 2,) if matrix else (0, 1)):
                 want = _scalar(refs[1], reads[q], sc, mode, tie, mat)
-                assert er.align_numpy(refs[1], reads[q], sc, mode, tie, mat) == want, (len(reads[q]), mode, tie)
+                assert gr.align_numpy(refs[1], reads[q], sc, mode, tie_mode=tie, matrix=mat) == want, (len(reads[q]), mode, tie)
                 if mode == 2:
                     assert len(want[1]) == 1                      # global mode ends in the one cell (m, n)
 
@@ -137,7 +132,7 @@ def test_shape_grid_has_tied_alignments(matrix):
     sc = gc.SHAPE_SCORES[matrix]
     for mode in (0, 1):
         for tie in (0, 1):
-            assert any(len(er.align_numpy(refs[0], reads[q], sc, mode, tie, mat)[1]) > 1 for q in range(len(reads))), (mode, tie)
+            assert any(len(gr.align_numpy(refs[0], reads[q], sc, mode, tie_mode=tie, matrix=mat)[1]) > 1 for q in range(len(reads))), (mode, tie)
 
 
 # 4 -- the mixed launches
@@ -150,9 +145,9 @@ def test_mixed_launch_cases(matrix):
     assert sorted(map(sorted, gc.MIXED_SUBSETS)) == sorted([[0, 2], [1, 2], [0, 1, 2], [2], [0, 1]])
     for mode in (1, 2):
         for r in range(2):
-            assert not br.refused(1025, len(refs[r]), gc.MIXED_BAND, mode)
+            assert not gr.refused(1025, len(refs[r]), gc.MIXED_BAND, mode)
         # the band bites: the banded result of the long read differs from the unbanded one
-        assert br.align_numpy(refs[0], reads[2], sc, mode, gc.MIXED_BAND, 0, mat) != er.align_numpy(refs[0], reads[2], sc, mode, 0, mat)
+        assert gr.align_numpy(refs[0], reads[2], sc, mode, gc.MIXED_BAND, matrix=mat) != gr.align_numpy(refs[0], reads[2], sc, mode, matrix=mat)
 
 
 # 5 -- coverage: every (R, mode, matrix, tie) body is reached by the GPU module's parametrisation (nothing is launched)

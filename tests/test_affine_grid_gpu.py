@@ -42,22 +42,16 @@ The 24 sweep kernels and 9 traceback kernels, and the tests that run them (G: th
 Each narrow and wide sweep kernel holds one body per (R, tie order): 16 x 3 modes x 2 (plain / matrix) x 2 tie orders = 192
 bodies.  GRID_PARAMS below times the 16 classes of affine_grid_cases.RS is that grid; tests/test_affine_grid_cpu.py checks it.
 All comparisons are exact: score, flags, number and order of the alignments, every begin and both strings, and the MapRef view."""
-import os
-import subprocess
-
-import numpy as np
 import pytest
 
 import sparksmithwaterman_amd as sw
-from sparksmithwaterman_amd import _capi
 
+import affine_gpu_util as u
 import affine_grid_cases as gc
-import band_reference as br
-import ends_reference as er
+import gotoh_reference as gr
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ERR_UNSUPPORTED = -5                         # swmi_status (include/swmi.h)
 
 MODES = (0, 1, 2)                            # local, fit, global
@@ -79,20 +73,6 @@ def _matrix(matrix):
     return gc.score_matrix() if matrix else None
 
 
-def _run(ctx, refs, reads, sc, mode, matrix, tie, **options):
-    ctx.set_option("gap_open", sc[3])
-    ctx.set_option("align_mode", mode)
-    for name, value in options.items():
-        ctx.set_option(name, value)
-    if matrix:
-        ctx.set_score_matrix(*gc.score_matrix())
-    else:
-        ctx.clear_score_matrix()
-    b = ctx.upload(refs, reads).run(sw.make_params(sc[:3], None, tie))
-    assert b.pipeline_mode() == 3
-    return b
-
-
 def _results(b, n_pairs):
     """what the batch holds for every pair: (score, (count, flags), alignments or None where the pair is degenerate)"""
     out = []
@@ -100,34 +80,6 @@ def _results(b, n_pairs):
         n, flags = b.n_alignments(pair)
         out.append((b.score(pair), (n, flags), None if flags & sw.PAIR_DEGENERATE else b.alignments(pair)))
     return out
-
-
-def _check(b, refs, reads, exp, mode):
-    """every pair's score, flags, alignment list and strings; the MapRef view (totals, stably sorted match sites), as _check of
-    tests/test_long_reads_gpu.py does; exp[(r, q)] = (score, alignments)"""
-    for r in range(len(refs)):
-        for q in range(len(reads)):
-            pair = r * len(reads) + q
-            es, ea = exp[(r, q)]
-            assert b.score(pair) == es, (r, q, len(refs[r]), len(reads[q]), b.score(pair), es)
-            n, flags = b.n_alignments(pair)
-            assert n == len(ea), (r, q, n, len(ea))
-            if mode != 0:
-                assert flags == 0, (r, q, flags)
-            elif flags & sw.PAIR_DEGENERATE:
-                assert flags == sw.PAIR_DEGENERATE and es == 0, (r, q, flags)
-                continue
-            else:
-                assert flags == 0 and es > 0, (r, q, flags)
-            assert b.alignments(pair) == ea, (r, q, len(refs[r]), len(reads[q]))
-    packed = b.ref_sites_packed()
-    for r in range(len(refs)):
-        total = int(np.int32(sum(exp[(r, q)][0] for q in range(len(reads)))))
-        sites = sorted([a for q in range(len(reads)) for a in exp[(r, q)][1] if mode != 0 or a != (0, ("", ""))], key=lambda t: t[0])
-        ndeg = sum(len(exp[(r, q)][1]) for q in range(len(reads)) if mode == 0 and exp[(r, q)][0] == 0)
-        assert b.ref_total(r) == total
-        assert packed[r] == (total, ndeg, sites), r
-        assert b.ref_match_sites(r) == sites, r
 
 
 # 1 -- the shape grid: three read lengths of every class against a reference of about 150 bases and one of 37.  The issue pairs
@@ -138,9 +90,9 @@ def test_grid_shapes(ctx, mode, matrix, tie):
     refs, reads = gc.shape_grid(matrix)
     assert sorted({gc.rows_per_lane(len(q)) for q in reads}) == list(gc.RS)
     sc = gc.SHAPE_SCORES[matrix]
-    exp = {(r, q): er.align_numpy(refs[r], reads[q], sc, mode, tie, _matrix(matrix)) for r in range(len(refs)) for q in range(len(reads))}
-    b = _run(ctx, refs, reads, sc, mode, matrix, tie)
-    _check(b, refs, reads, exp, mode)
+    exp = u.expect(refs, reads, sc, mode, tie=tie, matrix=_matrix(matrix))
+    b = u.run(ctx, refs, reads, sc, tie, mode, matrix=_matrix(matrix))
+    u.check(b, refs, reads, exp, mode)
     b.free()
 
 
@@ -154,10 +106,10 @@ def test_grid_walks(ctx, mode, matrix, tie):
     assert [gc.rows_per_lane(len(read)) for _, _, read in grid] == list(gc.RS)
     refs = [ref for _, ref, _ in grid]
     reads = [read for _, _, read in grid]
-    exp = [er.align_numpy(ref, read, gc.WALK_SCORES, mode, tie, _matrix(matrix)) for _, ref, read in grid]
+    exp = [gr.align_numpy(ref, read, gc.WALK_SCORES, mode, tie_mode=tie, matrix=_matrix(matrix)) for _, ref, read in grid]
     first = None
     for device_strings in (1, 0):                                 # (the second run reuses the expected values)
-        b = _run(ctx, refs, reads, gc.WALK_SCORES, mode, matrix, tie, device_strings=device_strings)
+        b = u.run(ctx, refs, reads, gc.WALK_SCORES, tie, mode, matrix=_matrix(matrix), device_strings=device_strings)
         for x, (es, ea) in enumerate(exp):
             pair = x * len(reads) + x
             assert b.score(pair) == es, (x + 1, b.score(pair), es)
@@ -180,12 +132,12 @@ def test_mixed_launch_fit_global(ctx, mode, matrix):
     refs, reads = gc.mixed_launch(matrix)
     sc = gc.SHAPE_SCORES[matrix]
     mat = _matrix(matrix)
-    exp = {(r, q): er.align_numpy(refs[r], reads[q], sc, mode, 0, mat) for r in range(len(refs)) for q in range(len(reads))}
+    exp = u.expect(refs, reads, sc, mode, matrix=mat)
     seen = {}
     for subset in gc.MIXED_SUBSETS:
         sub = [reads[q] for q in subset]
-        b = _run(ctx, refs, sub, sc, mode, matrix, 0, long_reads=1, band=0)
-        _check(b, refs, sub, {(r, x): exp[(r, q)] for r in range(len(refs)) for x, q in enumerate(subset)}, mode)
+        b = u.run(ctx, refs, sub, sc, 0, mode, w=0, matrix=_matrix(matrix), long_reads=1)
+        u.check(b, refs, sub, {(r, x): exp[(r, q)] for r in range(len(refs)) for x, q in enumerate(subset)}, mode)
         got = _results(b, len(refs) * len(sub))
         for r in range(len(refs)):
             for x, q in enumerate(subset):                        # a pair's result is the same in every sub-batch it occurs in
@@ -195,10 +147,10 @@ def test_mixed_launch_fit_global(ctx, mode, matrix):
     # the three-read batch inside a band: the band applies to the read of more than 1024 bases only
     w = gc.MIXED_BAND
     for r in range(len(refs)):
-        assert not br.refused(len(reads[2]), len(refs[r]), w, mode)
-        exp[(r, 2)] = br.align_numpy(refs[r], reads[2], sc, mode, w, 0, mat)
-    b = _run(ctx, refs, reads, sc, mode, matrix, 0, long_reads=1, band=w)
-    _check(b, refs, reads, exp, mode)
+        assert not gr.refused(len(reads[2]), len(refs[r]), w, mode)
+        exp[(r, 2)] = gr.align_numpy(refs[r], reads[2], sc, mode, w, matrix=mat)
+    b = u.run(ctx, refs, reads, sc, 0, mode, w=w, matrix=_matrix(matrix), long_reads=1)
+    u.check(b, refs, reads, exp, mode)
     b.free()
 
 
@@ -212,14 +164,7 @@ def _lcg(n, x):
 
 
 def test_c99_shim_sets_long_reads_and_band(tmp_path):
-    exe = tmp_path / "shim_long"
-    lib = os.path.join(ROOT, "sparksmithwaterman_amd", "lib")
-    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Wextra", "-Werror", "-pedantic",
-                           "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "bindings", "jni"),
-                           os.path.join(ROOT, "tests", "c", "shim_long.c"), os.path.join(ROOT, "bindings", "jni", "swmi_shim.c"),
-                           "-L", lib, "-lswmi", "-Wl,-rpath," + lib, "-o", str(exe)])
-    out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0, out.stdout + out.stderr
+    out = u.run_shim(tmp_path, "shim_long")
     read = _lcg(1025, 20260)
     ref = _lcg(300, 4242) + read
     sc = (5, -3, -2, -6)
@@ -229,8 +174,8 @@ def test_c99_shim_sets_long_reads_and_band(tmp_path):
         sites = sorted(al, key=lambda t: t[0])
         return " ".join([str(s), str(len(sites))] + ["%d:%s/%s" % (a[0], a[1][0], a[1][1]) for a in sites] + ["mode", "3"])
 
-    full = er.align_numpy(ref, read, sc, 0, 0)
-    banded = br.align_numpy(ref, read, sc, 0, 16, 0)
+    full = gr.align_numpy(ref, read, sc)
+    banded = gr.align_numpy(ref, read, sc, 0, 16)
     assert full[0] == 5 * 1025 and 0 < banded[0] < full[0]        # the band cuts the read's diagonal
     refused = "refused %d" % ERR_UNSUPPORTED
-    assert out.stdout.splitlines() == [refused, line(full), line(banded), refused]
+    assert out.splitlines() == [refused, line(full), line(banded), refused]

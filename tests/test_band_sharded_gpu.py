@@ -1,6 +1,6 @@
 """sharded_files --band --long-reads --align-mode on one MI355X, two ranks: a 1300-base read against two small reference files.
 The result file must be what the mirror classes' own file driver writes with the same options, and the winner's alignment must
-be the one tests/band_reference.py builds."""
+be the one tests/gotoh_reference.py builds."""
 import os
 import random
 import subprocess
@@ -10,8 +10,7 @@ import pytest
 
 import sparksmithwaterman_amd as sw
 
-import band_reference as br
-import ends_reference as er
+import gotoh_reference as gr
 
 pytestmark = pytest.mark.gpu
 
@@ -49,8 +48,8 @@ def test_sharded_files_band(tmp_path):
     (ref_dir / "a.fa").write_text(_fasta(refs_a))
     (ref_dir / "b.fa").write_text(_fasta(refs_b))
     (in_dir / "input1.txt").write_text(">gi reads\n" + read + "\n")
-    banded = {name: br.align_numpy(seq, read, SCORES, 1, W, 0) for name, seq in refs_a + refs_b}
-    assert banded[">gi|shifted"] != er.align_numpy(shifted, read, SCORES, 1, 0)
+    banded = {name: gr.align_numpy(seq, read, SCORES, 1, W) for name, seq in refs_a + refs_b}
+    assert banded[">gi|shifted"] != gr.align_numpy(shifted, read, SCORES, 1)
     assert max(banded, key=lambda k: banded[k][0]) == ">gi|near"          # (unbanded, the shifted copy would win)
     env = dict(os.environ, SWMI_ONE_GPU="1", PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""))
     cmd = [sys.executable, "-m", "sparksmithwaterman_amd.sharded_files", "--ref-dir", str(ref_dir), "--in-dir", str(in_dir),
@@ -67,7 +66,7 @@ def test_sharded_files_band(tmp_path):
     got = open(out_dir / "result1.txt", newline="", encoding="latin-1").read()
     want = open(ctl_dir / "result1.txt", newline="", encoding="latin-1").read()
     assert _body(got) == _body(want)
-    # ... and the file the reference's own output routine builds from band_reference: the one winner, its sites sorted by begin
+    # ... and the file the reference's own output routine builds from gotoh_reference: the one winner, its sites sorted by begin
     from sparksmithwaterman_amd import io as swio
     score, alns = banded[">gi|near"]
     built = swio.InOutOps.GetOutputStr().call([read], ((4, 1), score, 0), [([">gi|near", near], sorted(alns, key=lambda t: t[0]))])

@@ -1,5 +1,5 @@
 """End-to-end alignment modes (option "align_mode": fit, global) without a GPU: the two restatements of the contract in
-tests/ends_reference.py against each other, against properties that hold by construction and against the known answers
+tests/gotoh_reference.py against each other, against properties that hold by construction and against the known answers
 (tests/golden/ends_kat.json); the host mirror's align_mode keyword on a fake context."""
 import json
 import os
@@ -7,7 +7,7 @@ import random
 
 import pytest
 
-import ends_reference as er
+import gotoh_reference as gr
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -36,20 +36,20 @@ def _pairs(seed, count, max_len=12):
         yield ref, read, sc
 
 
-@pytest.mark.parametrize("mode", [er.FIT, er.GLOBAL])
+@pytest.mark.parametrize("mode", [gr.FIT, gr.GLOBAL])
 @pytest.mark.parametrize("tie", [0, 1])
 def test_restatements_agree_and_alignments_rescore(mode, tie):
     for ref, read, sc in _pairs(100 + 2 * mode + tie, 400):
-        got = er.align_scalar(ref, read, sc, mode, tie)
-        assert er.align_numpy(ref, read, sc, mode, tie) == got, (ref, read, sc)
+        got = gr.align_scalar(ref, read, sc, mode, tie_mode=tie)
+        assert gr.align_numpy(ref, read, sc, mode, tie_mode=tie) == got, (ref, read, sc)
         score, alns = got
         assert len(alns) >= 1
         for begin, (ra, qa) in alns:
             assert len(ra) == len(qa)
-            assert er.rescore(ra, qa, sc) == score, (ref, read, sc, ra, qa)
+            assert gr.rescore(ra, qa, sc) == score, (ref, read, sc, ra, qa)
             assert qa.replace("_", "") == read                    # the whole read
             used = ra.replace("_", "")
-            if mode == er.GLOBAL:
+            if mode == gr.GLOBAL:
                 assert used == ref and begin == 1                 # the whole reference
             elif used:
                 assert ref[begin - 1:].startswith(used)
@@ -59,9 +59,9 @@ def test_restatements_agree_and_alignments_rescore(mode, tie):
 @pytest.mark.parametrize("tie", [0, 1])
 def test_local_ge_fit_ge_global(tie):
     for ref, read, sc in _pairs(7 + tie, 500):
-        loc = er.align_numpy(ref, read, sc, er.LOCAL, tie)[0]
-        fit = er.align_scalar(ref, read, sc, er.FIT, tie)[0]
-        glo = er.align_scalar(ref, read, sc, er.GLOBAL, tie)[0]
+        loc = gr.align_numpy(ref, read, sc, gr.LOCAL, tie_mode=tie)[0]
+        fit = gr.align_scalar(ref, read, sc, gr.FIT, tie_mode=tie)[0]
+        glo = gr.align_scalar(ref, read, sc, gr.GLOBAL, tie_mode=tie)[0]
         assert loc >= fit >= glo, (ref, read, sc, loc, fit, glo)
         # and fit is the best global score over the stretches of the reference, never below the all-insertion alignment
         assert fit >= sc[3] + len(read) * sc[2]
@@ -74,12 +74,12 @@ def test_restatements_agree_with_a_matrix():
         ref = "".join(rng.choice(m[0][:20] + "z") for _ in range(rng.randint(1, 14)))
         read = "".join(rng.choice(m[0][:20] + "z") for _ in range(rng.randint(1, 14)))
         sc = (1, -1, rng.randint(-2, 0), rng.randint(-11, 0))
-        for mode in (er.FIT, er.GLOBAL):
+        for mode in (gr.FIT, gr.GLOBAL):
             for tie in (0, 1):
-                got = er.align_scalar(ref, read, sc, mode, tie, m)
-                assert er.align_numpy(ref, read, sc, mode, tie, m) == got
+                got = gr.align_scalar(ref, read, sc, mode, tie_mode=tie, matrix=m)
+                assert gr.align_numpy(ref, read, sc, mode, tie_mode=tie, matrix=m) == got
                 for _, (ra, qa) in got[1]:
-                    assert er.rescore(ra, qa, sc, m) == got[0]
+                    assert gr.rescore(ra, qa, sc, m) == got[0]
 
 
 def test_ends_kats():
@@ -88,13 +88,13 @@ def test_ends_kats():
     for k in kats:
         sc, m = tuple(k["scores"]), _matrix(k["matrix"])
         exp = (k["score"], [(a[0], (a[1], a[2])) for a in k["alignments"]])
-        got = er.align_scalar(k["ref"], k["read"], sc, k["align_mode"], k["tie_mode"], m, matrices=True)
+        got = gr.align_scalar(k["ref"], k["read"], sc, k["align_mode"], tie_mode=k["tie_mode"], matrix=m, matrices=True)
         assert got[:2] == exp, k["name"]
-        assert er.align_numpy(k["ref"], k["read"], sc, k["align_mode"], k["tie_mode"], m) == exp, k["name"]
+        assert gr.align_numpy(k["ref"], k["read"], sc, k["align_mode"], tie_mode=k["tie_mode"], matrix=m) == exp, k["name"]
         H, E, F, D, XE, XF = got[2:]
         assert H == k["H"], k["name"]
-        assert [[None if v <= er.NEG // 2 else v for v in row] for row in E] == k["E"], k["name"]
-        assert [[None if v <= er.NEG // 2 else v for v in row] for row in F] == k["F"], k["name"]
+        assert [[None if v == gr.NINF else v for v in row] for row in E] == k["E"], k["name"]
+        assert [[None if v == gr.NINF else v for v in row] for row in F] == k["F"], k["name"]
         assert ["".join(r) for r in D] == k["T"], k["name"]
         assert ["".join(str(x) for x in r) for r in XE] == k["xE"], k["name"]
         assert ["".join(str(x) for x in r) for r in XF] == k["xF"], k["name"]

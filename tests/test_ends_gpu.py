@@ -1,21 +1,20 @@
 """End-to-end alignment modes on the GPU (swmi_affine.hip, swmi_set_option "align_mode": 1 fit, 2 global).
 
-Every pair of every launch is checked against the numpy restatement of the contract in tests/ends_reference.py: score, number
+Every pair of every launch is checked against the numpy restatement of the contract in tests/gotoh_reference.py: score, number
 of alignments, each `beginning` and both strings.  The bounds of swmi.h / DESIGN.md section 8d are pinned from both sides
 against the scalar restatement, which computes in unbounded Python ints."""
 import json
 import os
 import random
-import subprocess
 
-import numpy as np
 import pytest
 
 import sparksmithwaterman_amd as sw
 from sparksmithwaterman_amd import _capi
 from sparksmithwaterman_amd import matrix as swmatrix
 
-import ends_reference as er
+import affine_gpu_util as u
+import gotoh_reference as gr
 
 pytestmark = pytest.mark.gpu
 
@@ -42,44 +41,6 @@ def ctx():
     c.close()
 
 
-def _rand(rng, n, alphabet="ACGT"):
-    return "".join(rng.choice(alphabet) for _ in range(n))
-
-
-def _run(ctx, refs, reads, scores, mode, tie):
-    ctx.set_option("gap_open", scores[3])
-    ctx.set_option("align_mode", mode)
-    return ctx.upload(refs, reads).run(sw.make_params(scores[:3], None, tie))
-
-
-def _check(b, refs, reads, scores, mode, tie, matrix=None, alignments=True, map_ref=True):
-    """every pair: score, count, each beginning and both strings; then the MapRef view (totals, match sites by beginning)"""
-    exp = {}
-    for r, ref in enumerate(refs):
-        for q, read in enumerate(reads):
-            pair = r * len(reads) + q
-            es, ea = exp[(r, q)] = er.align_numpy(ref, read, scores, mode, tie, matrix)
-            assert b.score(pair) == es, (r, q, len(ref), len(read), b.score(pair), es)
-            if not alignments:
-                continue
-            n, flags = b.n_alignments(pair)
-            assert n == len(ea), (r, q, n, len(ea))
-            if mode != sw.ALIGN_LOCAL:
-                assert not flags & sw.PAIR_DEGENERATE
-            elif flags & sw.PAIR_DEGENERATE:
-                continue
-            assert b.alignments(pair) == ea, (r, q, ref, read)
-    if map_ref and alignments and mode != sw.ALIGN_LOCAL:
-        packed = b.ref_sites_packed()
-        for r in range(len(refs)):
-            total = int(np.int32(sum(exp[(r, q)][0] for q in range(len(reads)))))
-            sites = sorted([a for q in range(len(reads)) for a in exp[(r, q)][1]], key=lambda t: t[0])
-            assert b.ref_total(r) == total
-            assert packed[r] == (total, 0, sites), r
-            assert b.ref_match_sites(r) == sites, r
-    return exp
-
-
 # 1 -- the known answers
 def test_ends_kats(ctx):
     for k in _kats():
@@ -89,12 +50,12 @@ def test_ends_kats(ctx):
             ctx.set_score_matrix(m)
         else:
             ctx.clear_score_matrix()
-        b = _run(ctx, [k["ref"]], [k["read"]], tuple(k["scores"]), k["align_mode"], k["tie_mode"])
+        b = u.run(ctx, [k["ref"]], [k["read"]], tuple(k["scores"]), k["tie_mode"], k["align_mode"], mode3=False)
         assert b.pipeline_mode() == 3
         assert b.score(0) == k["score"], k["name"]
         assert b.n_alignments(0) == (len(k["alignments"]), 0), k["name"]
         assert [[x[0], x[1][0], x[1][1]] for x in b.alignments(0)] == k["alignments"], k["name"]
-        assert (b.score(0), b.alignments(0)) == er.align_numpy(k["ref"], k["read"], tuple(k["scores"]), k["align_mode"], k["tie_mode"], mat)
+        assert (b.score(0), b.alignments(0)) == gr.align_numpy(k["ref"], k["read"], tuple(k["scores"]), k["align_mode"], tie_mode=k["tie_mode"], matrix=mat)
         b.free()
 
 
@@ -103,14 +64,14 @@ def test_ends_kats(ctx):
 @pytest.mark.parametrize("tie", [0, 1])
 def test_ends_read_lengths(ctx, mode, tie):
     rng = random.Random(300 + 2 * mode + tie)
-    big = _rand(rng, 6000)
-    reads = [_rand(rng, m) for m in (1, 63, 64, 65, 255, 256, 257, 1023)] + [big[2000:2500] + big[2530:3054]]     # (the last: 1024)
+    big = u.rand(rng, 6000)
+    reads = [u.rand(rng, m) for m in (1, 63, 64, 65, 255, 256, 257, 1023)] + [big[2000:2500] + big[2530:3054]]     # (the last: 1024)
     assert [len(r) for r in reads][-1] == 1024
-    refs = [_rand(rng, 40), _rand(rng, 300), big[1500:3600], big]
+    refs = [u.rand(rng, 40), u.rand(rng, 300), big[1500:3600], big]
     sc = (5, -3, -2, -6) if mode == sw.ALIGN_FIT else (2, -3, -1, -4)
-    b = _run(ctx, refs, reads, sc, mode, tie)
+    b = u.run(ctx, refs, reads, sc, tie, mode, mode3=False)
     assert b.pipeline_mode() == 3
-    _check(b, refs, reads, sc, mode, tie)
+    u.check(b, refs, reads, u.expect(refs, reads, sc, mode, tie=tie), mode)
     b.free()
 
 
@@ -121,10 +82,10 @@ def test_ends_random_pairs(ctx, mode, tie):
     rng = random.Random(400 + 2 * mode + tie)
     for sc in ((1, -1, -1, 0), (2, -3, -1, -3), (3, 1, 0, -2), (0, -2, -2, 0), (5, -3, 0, 0)):
         alpha = rng.choice(["AC", "A", "ACGTacgtN\xe9"])
-        refs = [_rand(rng, rng.randint(1, 90), alpha) for _ in range(12)] + ["", "AC" * 150]
-        reads = [_rand(rng, rng.randint(1, 70), alpha) for _ in range(10)] + ["", "CA", "ACACAC"]
-        b = _run(ctx, refs, reads, sc, mode, tie)
-        _check(b, refs, reads, sc, mode, tie)
+        refs = [u.rand(rng, rng.randint(1, 90), alpha) for _ in range(12)] + ["", "AC" * 150]
+        reads = [u.rand(rng, rng.randint(1, 70), alpha) for _ in range(10)] + ["", "CA", "ACACAC"]
+        b = u.run(ctx, refs, reads, sc, tie, mode, mode3=False)
+        u.check(b, refs, reads, u.expect(refs, reads, sc, mode, tie=tie), mode)
         b.free()
 
 
@@ -135,8 +96,9 @@ def test_ends_cell_cap_rerun(ctx, tie):
     refs = ["ACGTTGCA" * 40, "AC" * 100, "GATTACA"]
     reads = ["ACGTTGCAAC", "CACA", "ACGTTGCAACGTTGCA"]
     sc = (2, -3, -1, -2)
-    b = _run(ctx, refs, reads, sc, sw.ALIGN_FIT, tie)
-    exp = _check(b, refs, reads, sc, sw.ALIGN_FIT, tie)
+    b = u.run(ctx, refs, reads, sc, tie, sw.ALIGN_FIT, mode3=False)
+    exp = u.expect(refs, reads, sc, sw.ALIGN_FIT, tie=tie)
+    u.check(b, refs, reads, exp, sw.ALIGN_FIT)
     assert max(len(v[1]) for v in exp.values()) > 4 and b.timing().rerun_pairs >= 1
     b.free()
 
@@ -147,27 +109,27 @@ def test_ends_matrix_and_options_that_select_kernels(ctx, mode):
     rng = random.Random(500 + mode)
     m, mat = _matrix("BLOSUM62")
     prot = mat[0][:20]
-    refs = [_rand(rng, 400, prot), _rand(rng, 90, prot + "z"), _rand(rng, 1200, prot)]
-    reads = [refs[0][100:160], _rand(rng, 300, prot), _rand(rng, 70, prot + "z"), refs[2][50:400] + refs[2][420:700]]
+    refs = [u.rand(rng, 400, prot), u.rand(rng, 90, prot + "z"), u.rand(rng, 1200, prot)]
+    reads = [refs[0][100:160], u.rand(rng, 300, prot), u.rand(rng, 70, prot + "z"), refs[2][50:400] + refs[2][420:700]]
     ctx.set_score_matrix(m)
     for tie in (0, 1):
         sc = (1, -1, -1, -10)
-        b = _run(ctx, refs, reads, sc, mode, tie)
+        b = u.run(ctx, refs, reads, sc, tie, mode, mode3=False)
         assert b.pipeline_mode() == 3
-        _check(b, refs, reads, sc, mode, tie, mat)
+        u.check(b, refs, reads, u.expect(refs, reads, sc, mode, tie=tie, matrix=mat), mode)
         b.free()
     ctx.clear_score_matrix()
-    refs = [_rand(rng, 500), _rand(rng, 100)]
-    reads = [_rand(rng, 150), refs[0][40:300]]
+    refs = [u.rand(rng, 500), u.rand(rng, 100)]
+    reads = [u.rand(rng, 150), refs[0][40:300]]
     sc = (5, -3, -4, 0)                                           # gap_open = 0: still the mode-3 kernels
-    b = _run(ctx, refs, reads, sc, mode, 0)
+    b = u.run(ctx, refs, reads, sc, 0, mode, mode3=False)
     assert b.pipeline_mode() == 3
-    _check(b, refs, reads, sc, mode, 0)
+    u.check(b, refs, reads, u.expect(refs, reads, sc, mode), mode)
     b.free()
     ctx.set_option("affine", 1)
-    b = _run(ctx, refs, reads, sc, mode, 1)
+    b = u.run(ctx, refs, reads, sc, 1, mode, mode3=False)
     assert b.pipeline_mode() == 3
-    _check(b, refs, reads, sc, mode, 1)
+    u.check(b, refs, reads, u.expect(refs, reads, sc, mode, tie=1), mode)
     b.free()
 
 
@@ -177,16 +139,16 @@ def test_ends_matrix_and_options_that_select_kernels(ctx, mode):
                                  ("arena_words_per_pair", 1), ("max_workspace_bytes", 1 << 20)])
 def test_ends_options(ctx, mode, opt):
     rng = random.Random(600)
-    refs = ["ACGTTGCA" * 40, _rand(rng, 900), "GATTACA" * 30 + _rand(rng, 200), _rand(rng, 64), _rand(rng, 2500)]
-    reads = ["ACGTTGCAAC", _rand(rng, 150), "GATTACAGATTACA", _rand(rng, 300), refs[4][1000:1400]]
+    refs = ["ACGTTGCA" * 40, u.rand(rng, 900), "GATTACA" * 30 + u.rand(rng, 200), u.rand(rng, 64), u.rand(rng, 2500)]
+    reads = ["ACGTTGCAAC", u.rand(rng, 150), "GATTACAGATTACA", u.rand(rng, 300), refs[4][1000:1400]]
     sc = (5, -3, -2, -6)
     ctx.set_option(*opt)
-    b = _run(ctx, refs, reads, sc, mode, 0)
+    b = u.run(ctx, refs, reads, sc, 0, mode, mode3=False)
     assert b.pipeline_mode() == 3
-    _check(b, refs, reads, sc, mode, 0, alignments=opt[0] != "scores_only")
+    u.check(b, refs, reads, u.expect(refs, reads, sc, mode), mode, alignments=opt[0] != "scores_only")
     if opt[0] == "scores_only":
         assert [b.ref_total(r) for r in range(len(refs))] == \
-            [sum(er.align_numpy(rf, rd, sc, mode, 0)[0] for rd in reads) for rf in refs]
+            [sum(gr.align_numpy(rf, rd, sc, mode)[0] for rd in reads) for rf in refs]
     if opt[0] == "cell_cap" and mode == sw.ALIGN_FIT:
         assert b.timing().rerun_pairs >= 1
     if opt[0] == "max_workspace_bytes":
@@ -197,8 +159,8 @@ def test_ends_options(ctx, mode, opt):
 # 7 -- run_async takes the mode set when it was asked for; the mirror's keyword
 def test_ends_async_and_mirror(ctx):
     rng = random.Random(700)
-    refs = [_rand(rng, 500) for _ in range(3)]
-    reads = [_rand(rng, 120) for _ in range(4)]
+    refs = [u.rand(rng, 500) for _ in range(3)]
+    reads = [u.rand(rng, 120) for _ in range(4)]
     sc = (5, -3, -2, -6)
     ctx.set_option("gap_open", sc[3])
     ctx.set_option("align_mode", sw.ALIGN_FIT)
@@ -208,16 +170,16 @@ def test_ends_async_and_mirror(ctx):
     b.wait()
     ctx.set_option("debug_async_delay_us", 0)
     assert b.pipeline_mode() == 3
-    _check(b, refs, reads, sc, sw.ALIGN_FIT, 0)
+    u.check(b, refs, reads, u.expect(refs, reads, sc, sw.ALIGN_FIT), sw.ALIGN_FIT)
     b.free()
     for mode in MODES:
         got = sw.SmithWaterman.OptAlignments(ctx, align_mode=mode).call([refs[0], reads[0]], list(sc))
-        assert got == er.align_numpy(refs[0], reads[0], sc, mode, 0)
+        assert got == gr.align_numpy(refs[0], reads[0], sc, mode)
         got = sw.DistributedSW.OptAlignments(ctx, align_mode=mode).call([refs[0], reads[0]], list(sc))
-        assert got == er.align_numpy(refs[0], reads[0], sc, mode, 1)
+        assert got == gr.align_numpy(refs[0], reads[0], sc, mode, tie_mode=1)
         assert ctx.options["align_mode"] == sw.ALIGN_LOCAL and ctx.options["gap_open"] == sc[3]
     total, (ref, sites) = sw.Distribution.MapRef(ctx, align_mode=sw.ALIGN_FIT).call(((">r", refs[1]), reads, (list(sc), ["a", "i", "d", "-"])))
-    exp = [er.align_numpy(refs[1], q, sc, sw.ALIGN_FIT, 0) for q in reads]
+    exp = [gr.align_numpy(refs[1], q, sc, sw.ALIGN_FIT) for q in reads]
     assert total == sum(e[0] for e in exp)
     assert sites == sorted([a for e in exp for a in e[1]], key=lambda t: t[0])
 
@@ -226,8 +188,8 @@ def test_ends_async_and_mirror(ctx):
 @pytest.mark.parametrize("mode", MODES)
 def test_ends_stream_from_fasta(ctx, tmp_path, mode):
     rng = random.Random(800 + mode)
-    refs = [_rand(rng, rng.randint(200, 800)) for _ in range(40)]
-    reads = [_rand(rng, 150), refs[17][100:250], "W" * 300]        # (the last: no base of it is in any reference)
+    refs = [u.rand(rng, rng.randint(200, 800)) for _ in range(40)]
+    reads = [u.rand(rng, 150), refs[17][100:250], "W" * 300]        # (the last: no base of it is in any reference)
     path = tmp_path / "refs.fa"
     with open(path, "w") as f:
         for k, r in enumerate(refs):
@@ -237,7 +199,7 @@ def test_ends_stream_from_fasta(ctx, tmp_path, mode):
     sc = (5, -3, -2, -6)
     ctx.set_option("gap_open", sc[3])
     ctx.set_option("align_mode", mode)
-    exp = [[er.align_numpy(r, q, sc, mode, 0) for q in reads] for r in refs]
+    exp = [[gr.align_numpy(r, q, sc, mode) for q in reads] for r in refs]
     want = [sum(e[0] for e in row) for row in exp]
     assert min(want) < 0                                          # negative totals come through untouched
     st = ctx.stream(reads, sw.make_params(sc[:3]), slots=2, chunk_bytes=1 << 16)
@@ -263,8 +225,8 @@ def test_ends_stream_from_fasta(ctx, tmp_path, mode):
 def test_ends_rerun_under_another_mode(ctx):
     from oracle import sw_oracle as orc
     rng = random.Random(900)
-    refs = [_rand(rng, 400) for _ in range(3)]
-    reads = [_rand(rng, 100) for _ in range(3)] + [refs[1][30:200]]
+    refs = [u.rand(rng, 400) for _ in range(3)]
+    reads = [u.rand(rng, 100) for _ in range(3)] + [refs[1][30:200]]
     sc = (5, -3, -4, -6)
     b = ctx.upload(refs, reads)
     p = sw.make_params(sc[:3])
@@ -273,7 +235,7 @@ def test_ends_rerun_under_another_mode(ctx):
         ctx.set_option("align_mode", mode)
         b.run(p)
         assert b.pipeline_mode() == 3
-        _check(b, refs, reads, sc, mode, 0)
+        u.check(b, refs, reads, u.expect(refs, reads, sc, mode), mode)
     ctx.set_option("align_mode", sw.ALIGN_LOCAL)
     ctx.set_option("gap_open", 0)
     b.run(p)
@@ -294,30 +256,25 @@ def test_ends_invalid_value(ctx):
         with pytest.raises(_capi.SwmiError) as e:
             ctx.set_option("align_mode", bad)
         assert e.value.code == ERR_INVALID
-    b = _run_keep(ctx, ["CGTCCAGACT"], ["AGGTCGAC"], (2, -3, -1, -3))
+    b = u.run(ctx, ["CGTCCAGACT"], ["AGGTCGAC"], (2, -3, -1, -3), mode3=False)       # (align_mode left as it is)
     assert (b.score(0), b.alignments(0)) == (2, [(2, ("__GTCCAGAC", "AGGTC__GAC"))])      # still fit
     b.free()
 
 
-def _run_keep(ctx, refs, reads, scores):
-    ctx.set_option("gap_open", scores[3])
-    return ctx.upload(refs, reads).run(sw.make_params(scores[:3]))
-
-
 # 11 -- both sides of every bound, against the restatement in unbounded ints
 def _scalar(ref, read, sc, mode):
-    return er.align_scalar(ref, read, sc, mode, 0)
+    return gr.align_scalar(ref, read, sc, mode)
 
 
 def test_ends_bounds_scores_and_read_length(ctx):
     rng = random.Random(1100)
     L = 1 << 20
     # inside: every score at its bound, the longest read; fit values reach gap_open + 1024 * gap - (gap_open + 2 * gap)
-    read = _rand(rng, 1024, "AC")
-    ref = read[:500] + _rand(rng, 40, "AC") + read[560:]
+    read = u.rand(rng, 1024, "AC")
+    ref = read[:500] + u.rand(rng, 40, "AC") + read[560:]
     for sc in ((L, -L, -L, -L), (L, L, -L, -L), (-L, -L, -L, 0)):
         for mode, rf in ((sw.ALIGN_FIT, ref), (sw.ALIGN_FIT, "CA"), (sw.ALIGN_GLOBAL, ref[:950])):
-            b = _run(ctx, [rf], [read], sc, mode, 0)
+            b = u.run(ctx, [rf], [read], sc, 0, mode, mode3=False)
             assert (b.score(0), b.alignments(0)) == _scalar(rf, read, sc, mode), (sc, mode, len(rf))
             b.free()
     # outside: one more in any score, one more read base, a positive gap
@@ -351,10 +308,10 @@ def test_ends_bound_global_int32(ctx, o, m):
     rows = 64 * ((m + 63) // 64)
     n_ok = ((1 << 31) - 3 * -o) // -e - rows
     assert 3 * -o + (rows + n_ok) * -e <= 1 << 31 < 3 * -o + (rows + n_ok + 1) * -e
-    read = _rand(rng, m, "AC")
-    ref = _rand(rng, n_ok + 1, "AC")
+    read = u.rand(rng, m, "AC")
+    ref = u.rand(rng, n_ok + 1, "AC")
     sc = (1 << 20, -3, e, o)
-    b = _run(ctx, [ref[:n_ok]], [read], sc, sw.ALIGN_GLOBAL, 0)
+    b = u.run(ctx, [ref[:n_ok]], [read], sc, 0, sw.ALIGN_GLOBAL, mode3=False)
     assert (b.score(0), b.alignments(0)) == _scalar(ref[:n_ok], read, sc, sw.ALIGN_GLOBAL)
     b.free()
     ctx.set_option("align_mode", sw.ALIGN_GLOBAL)
@@ -374,10 +331,10 @@ def test_ends_bound_path_lds(ctx):
     limit = (160 * 1024 // 4 - 4096 - 128 - 1) * 16
     assert limit == 587760
     rng = random.Random(1300)
-    ref = _rand(rng, limit, "ACGT")
+    ref = u.rand(rng, limit, "ACGT")
     sc = (2, -3, -1, -2)
     for mode in MODES:
-        b = _run(ctx, [ref[:limit - 1]], ["G"], sc, mode, 0)     # m + n = limit
+        b = u.run(ctx, [ref[:limit - 1]], ["G"], sc, 0, mode, mode3=False)     # m + n = limit
         assert (b.score(0), b.alignments(0)) == _scalar(ref[:limit - 1], "G", sc, mode)
         b.free()
         ctx.set_option("align_mode", mode)
@@ -394,13 +351,6 @@ def test_ends_bound_path_lds(ctx):
 
 # 12 -- the JNI shim's entry point from plain C99 (tests/c/shim_ends.c)
 def test_c99_shim_sets_align_mode(tmp_path):
-    exe = tmp_path / "shim_ends"
-    lib = os.path.join(ROOT, "sparksmithwaterman_amd", "lib")
-    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Wextra", "-Werror", "-pedantic",
-                           "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "bindings", "jni"),
-                           os.path.join(ROOT, "tests", "c", "shim_ends.c"), os.path.join(ROOT, "bindings", "jni", "swmi_shim.c"),
-                           "-L", lib, "-lswmi", "-Wl,-rpath," + lib, "-o", str(exe)])
-    out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0, out.stdout + out.stderr
-    assert out.stdout.splitlines() == ["2 1 2:__GTCCAGAC/AGGTC__GAC mode 3", "-4 1 1:_CGTCCAGACT/AGGTC__GAC_ mode 3",
+    out = u.run_shim(tmp_path, "shim_ends")
+    assert out.splitlines() == ["2 1 2:__GTCCAGAC/AGGTC__GAC mode 3", "-4 1 1:_CGTCCAGACT/AGGTC__GAC_ mode 3",
                                        "7 1 2:GTCCAGAC/GTC__GAC mode 3"]

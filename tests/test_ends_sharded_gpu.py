@@ -1,6 +1,6 @@
 """sharded_files --align-mode fit on one MI355X (every rank on GPU 0, gloo for the exchange) against a test-side driver loop:
 the control driver's loop (oracle/io_oracle_py's file pieces, `int max = 0`, ties kept, its writer) with the fit-mode
-restatement of tests/ends_reference.py as the aligner."""
+restatement of tests/gotoh_reference.py as the aligner."""
 import json
 import os
 import subprocess
@@ -10,7 +10,7 @@ import pytest
 
 from oracle import io_oracle_py as ioo
 
-import ends_reference as er
+import gotoh_reference as gr
 
 pytestmark = pytest.mark.gpu
 
@@ -51,7 +51,7 @@ def _driver(ref_dir, in_dir, out_dir, mode, tie=0):
             ref_seqs = ioo.get_ref_seqs(ref_file, ">gi")
             num_refs += len(ref_seqs)
             for ref in ref_seqs:
-                res = [er.align_numpy(ref[1], q, SCORES, mode, tie) for q in reads]
+                res = [gr.align_numpy(ref[1], q, SCORES, mode, tie_mode=tie) for q in reads]
                 total = sum(r[0] for r in res)
                 sites = sorted([a for r in res for a in r[1]], key=lambda t: t[0])
                 if total > mx:
@@ -80,8 +80,8 @@ def test_sharded_files_fit_mode(tmp_path, world):
            "--align-mode", "fit", "--stats", str(out_dir / "rank<r>.json")]
     rc = subprocess.run(cmd, cwd=ROOT, env=env, timeout=900)     # the launcher makes no GPU call; the ranks are its children
     assert rc.returncode == 0
-    expect = _driver(ref_dir, in_dir, out_dir, er.FIT)
-    local = _driver(ref_dir, in_dir, out_dir, er.LOCAL)
+    expect = _driver(ref_dir, in_dir, out_dir, gr.FIT)
+    local = _driver(ref_dir, in_dir, out_dir, gr.LOCAL)
     assert _body(expect[0]) != _body(local[0])                  # the mode shows in the result
     assert "Maximum alignment score = 0" in expect[1] and "Reference:" not in expect[1]     # negative totals never win
     for k, text in enumerate(expect, 1):

@@ -1,6 +1,6 @@
-"""Host-side checks of seed extension (option "extend") that need no GPU: the two restatements of tests/extend_reference.py
+"""Host-side checks of seed extension (option "extend") that need no GPU: the two restatements of tests/gotoh_reference.py
 agree, the hand-checkable vectors of tests/golden/extend_kat.json hold, an extend result is the global alignment of the prefixes
-that end in its maximum cells (against ends_reference / band_reference, which the project already trusts), the mirror takes the
+that end in its maximum cells (the same module's plain global mode, which the project already trusts), the mirror takes the
 extend= keyword and the sharded driver's parser knows --extend."""
 import json
 import os
@@ -8,10 +8,7 @@ import random
 
 import pytest
 
-import affine_reference as ar
-import band_reference as br
-import ends_reference as er
-import extend_reference as xr
+import gotoh_reference as gr
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SC = (2, -3, -1, -3)
@@ -21,6 +18,14 @@ MATRIX = ("ACGT", [[3, -2, 1, -4], [-1, 4, -3, 0], [2, -5, 5, -1], [-3, 1, -2, 2
 
 def _rand(rng, n, alphabet="ACGT"):
     return "".join(rng.choice(alphabet) for _ in range(n))
+
+
+def _scalar(ref, read, sc, w=0, tie=0, matrix=None, **more):
+    return gr.align_scalar(ref, read, sc, gr.GLOBAL, w, True, tie, matrix, **more)
+
+
+def _numpy(ref, read, sc, w=0, tie=0, matrix=None, **more):
+    return gr.align_numpy(ref, read, sc, gr.GLOBAL, w, True, tie, matrix, **more)
 
 
 def _kats():
@@ -40,12 +45,12 @@ def test_scalar_and_numpy_agree(matrix):
     n = 0
     for ref, read, sc in _pairs(9910 + (matrix is not None), 150, 0, 14):
         for tie in (0, 1):
-            a = xr.align_scalar(ref, read, sc, 0, tie, matrix, cells=True)
-            assert a == xr.align_numpy(ref, read, sc, 0, tie, matrix, cells=True), (ref, read, sc, tie)
-            assert a[:2] == xr.align_scalar(ref, read, sc, 0, tie, matrix)
+            a = _scalar(ref, read, sc, 0, tie, matrix, cells=True)
+            assert a == _numpy(ref, read, sc, 0, tie, matrix, cells=True), (ref, read, sc, tie)
+            assert a[:2] == _scalar(ref, read, sc, 0, tie, matrix)
             for (beg, (ra, qa)), (i, j) in zip(a[1], a[2]):       # every alignment spells the prefixes and the score it claims
-                assert beg == 1 and ra.replace(xr.GAP_CHAR, "") == ref[:j] and qa.replace(xr.GAP_CHAR, "") == read[:i]
-                assert er.rescore(ra, qa, sc, matrix) == a[0], (ref, read, sc, tie)
+                assert beg == 1 and ra.replace(gr.GAP_CHAR, "") == ref[:j] and qa.replace(gr.GAP_CHAR, "") == read[:i]
+                assert gr.rescore(ra, qa, sc, matrix) == a[0], (ref, read, sc, tie)
             if not ref or not read:
                 assert a == (0, [], [])
             n += 1
@@ -59,19 +64,19 @@ def test_scalar_and_numpy_agree_on_a_staircase(w):
     for _ in range(60):
         m = rng.randint(9, 40)
         n = max(1, m + rng.choice([-w, -1, 0, 1, w, 2 * w + 9]))       # (the last: a reference that runs on past the band)
-        if xr.refused(m, n, w, strip=8):
+        if gr.refused(m, n, w, gr.GLOBAL, True, strip=8):
             continue
         alphabet = rng.choice(["AC", "ACGT"])
         ref, read = _rand(rng, n, alphabet), _rand(rng, m, alphabet)
         sc = rng.choice(SCORES)
         matrix = rng.choice([None, MATRIX])
         for tie in (0, 1):
-            a = xr.align_scalar(ref, read, sc, w, tie, matrix, strip=8, cells=True)
-            assert a == xr.align_numpy(ref, read, sc, w, tie, matrix, strip=8, cells=True), (ref, read, sc, tie)
-            win = xr.windows(m, n, w, 8)
+            a = _scalar(ref, read, sc, w, tie, matrix, strip=8, cells=True)
+            assert a == _numpy(ref, read, sc, w, tie, matrix, strip=8, cells=True), (ref, read, sc, tie)
+            win = gr.windows(m, n, w, 8)
             for (beg, (ra, qa)), (i, j) in zip(a[1], a[2]):
                 assert win[(i - 1) // 8][0] <= j <= win[(i - 1) // 8][1]
-                assert beg == 1 and er.rescore(ra, qa, sc, matrix) == a[0]
+                assert beg == 1 and gr.rescore(ra, qa, sc, matrix) == a[0]
         done += 1
     assert done >= 30
 
@@ -80,8 +85,8 @@ def test_scalar_and_numpy_agree_on_a_staircase(w):
 def test_kats(kat):
     for tie, key in ((0, "serial"), (1, "strict")):
         want = (kat[key]["score"], [(b, tuple(s)) for b, s in kat[key]["alignments"]], [tuple(c) for c in kat[key]["cells"]])
-        for fn in (xr.align_scalar, xr.align_numpy):
-            assert fn(kat["ref"], kat["read"], kat["scores"], kat["w"], tie, None, kat["strip"], cells=True) == want, (key, fn.__name__)
+        for fn in (_scalar, _numpy):
+            assert fn(kat["ref"], kat["read"], kat["scores"], kat["w"], tie, strip=kat["strip"], cells=True) == want, (key, fn.__name__)
 
 
 def test_kats_cover_what_they_should():
@@ -105,14 +110,11 @@ def test_kats_cover_what_they_should():
 def _prefix_property(ref, read, sc, w, tie, matrix, strip):
     """(score, alignments, cells) put together from global alignments of prefixes alone"""
     m, n = len(read), len(ref)
-    win = xr.windows(m, n, w, strip)
+    win = gr.windows(m, n, w, strip)
     glob = {}
-    for i, j in ar._order(m, n, tie == 1):                        # the contract's order of tied cells
+    for i, j in gr.order(m, n, tie == 1):                        # the contract's order of tied cells
         if win[(i - 1) // strip][0] <= j <= win[(i - 1) // strip][1]:
-            if w > 0 and m > strip:
-                glob[(i, j)] = br.align_scalar(ref[:j], read[:i], sc, er.GLOBAL, w, tie, matrix, strip=strip)
-            else:
-                glob[(i, j)] = er.align_scalar(ref[:j], read[:i], sc, er.GLOBAL, tie, matrix)
+            glob[(i, j)] = gr.align_scalar(ref[:j], read[:i], sc, gr.GLOBAL, w, tie_mode=tie, matrix=matrix, strip=strip)     # (plain global)
     best = max(v[0] for v in glob.values())
     cells = [c for c, v in glob.items() if v[0] == best]
     alns = [glob[c][1][0] for c in cells]
@@ -127,8 +129,8 @@ def test_prefix_property(matrix):
     for ref, read, sc in _pairs(9930 + (matrix is not None), 60, 1, 12):
         for tie in (0, 1):
             want = _prefix_property(ref, read, sc, 0, tie, matrix, 1024)
-            assert xr.align_scalar(ref, read, sc, 0, tie, matrix, cells=True) == want, (ref, read, sc, tie)
-            assert xr.align_numpy(ref, read, sc, 0, tie, matrix, cells=True) == want, (ref, read, sc, tie)
+            assert _scalar(ref, read, sc, 0, tie, matrix, cells=True) == want, (ref, read, sc, tie)
+            assert _numpy(ref, read, sc, 0, tie, matrix, cells=True) == want, (ref, read, sc, tie)
 
 
 def test_prefix_property_banded():
@@ -138,15 +140,15 @@ def test_prefix_property_banded():
         w = rng.choice([1, 2, 3])
         m = rng.randint(9, 20)
         n = max(1, m + rng.choice([-w, 0, 1, w, 2 * w + 9]))
-        if xr.refused(m, n, w, strip=8):
+        if gr.refused(m, n, w, gr.GLOBAL, True, strip=8):
             continue
         ref, read = _rand(rng, n, "AC"), _rand(rng, m, "AC")
         sc = rng.choice(SCORES)
         matrix = rng.choice([None, MATRIX])
         for tie in (0, 1):
             want = _prefix_property(ref, read, sc, w, tie, matrix, 8)
-            assert xr.align_scalar(ref, read, sc, w, tie, matrix, strip=8, cells=True) == want, (ref, read, sc, w, tie)
-            assert xr.align_numpy(ref, read, sc, w, tie, matrix, strip=8, cells=True) == want, (ref, read, sc, w, tie)
+            assert _scalar(ref, read, sc, w, tie, matrix, strip=8, cells=True) == want, (ref, read, sc, w, tie)
+            assert _numpy(ref, read, sc, w, tie, matrix, strip=8, cells=True) == want, (ref, read, sc, w, tie)
         done += 1
     assert done >= 25
 
@@ -157,9 +159,9 @@ def test_a_band_over_everything_and_short_reads_are_unbanded():
         m, n = rng.randint(9, 30), rng.randint(1, 30)
         ref, read = _rand(rng, n, "AC"), _rand(rng, m, "AC")
         for tie in (0, 1):
-            assert xr.align_scalar(ref, read, SC, max(m, n), tie, strip=8) == xr.align_scalar(ref, read, SC, 0, tie)
+            assert _scalar(ref, read, SC, max(m, n), tie, strip=8) == _scalar(ref, read, SC, 0, tie)
     ref, read = _rand(rng, 30), _rand(rng, 8)
-    assert xr.align_numpy(ref, read, SC, 1, strip=8) == xr.align_numpy(ref, read, SC, 0)          # m = strip: not a long read
+    assert _numpy(ref, read, SC, 1, strip=8) == _numpy(ref, read, SC)          # m = strip: not a long read
 
 
 # ---- the mirror's extend= keyword on a fake context ----

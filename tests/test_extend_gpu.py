@@ -1,5 +1,5 @@
 """Seed extension on the GPU (option "extend" on a global run: the sw_affine_sweep_*extend* kernels of swmi_affine.hip and the
-global tracebacks) against tests/extend_reference.py: every score, every alignment with its begin, both
+global tracebacks) against tests/gotoh_reference.py: every score, every alignment with its begin, both
 strings and its maximum cell, the flags and the MapRef view.  set_option("extend", ...) is what fails without the feature.
 
 The eight extend sweeps and the tests that run them (the table of tests/test_affine_grid_gpu.py, continued):
@@ -19,17 +19,15 @@ The walks are those of sw_affine_traceback_global_kernel, _long_global_kernel an
 import json
 import os
 import random
-import subprocess
 
-import numpy as np
 import pytest
 
 import sparksmithwaterman_amd as sw
 from sparksmithwaterman_amd import _capi
 
+import affine_gpu_util as u
 import affine_grid_cases as gc
-import ends_reference as er
-import extend_reference as xr
+import gotoh_reference as gr
 
 pytestmark = pytest.mark.gpu
 
@@ -46,57 +44,22 @@ def ctx():
     c.close()
 
 
-def _rand(rng, n, alphabet="ACGT"):
-    return "".join(rng.choice(alphabet) for _ in range(n))
-
-
+# every run of this module is a global run with long reads on, and every expected value an extend result with its cells
 def _run(ctx, refs, reads, sc, tie=0, w=0, matrix=None, extend=1, **options):
-    ctx.set_option("gap_open", sc[3])
-    ctx.set_option("align_mode", GLOBAL)
-    ctx.set_option("long_reads", 1)
-    ctx.set_option("band", w)
-    ctx.set_option("extend", extend)
-    for name, value in options.items():
-        ctx.set_option(name, value)
-    if matrix:
-        ctx.set_score_matrix(*matrix)
-    else:
-        ctx.clear_score_matrix()
-    b = ctx.upload(refs, reads).run(sw.make_params(sc[:3], None, tie))
-    assert b.pipeline_mode() == 3
-    return b
+    return u.run(ctx, refs, reads, sc, tie, GLOBAL, w, extend, matrix, long_reads=1, **options)
+
+
+def _extend(ref, read, sc, w=0, tie=0, matrix=None, cells=True, align=gr.align_numpy):
+    return align(ref, read, sc, GLOBAL, w, True, tie, matrix, cells=cells)
 
 
 def _expect(refs, reads, sc, w=0, tie=0, matrix=None):
-    return {(r, q): xr.align_numpy(refs[r], reads[q], sc, w, tie, matrix, cells=True) for r in range(len(refs)) for q in range(len(reads))}
-
-
-def _check_pair(b, pair, want, what=None):
-    """one pair in full: want = (score, alignments, cells) as extend_reference returns them"""
-    es, ea, ec = want
-    assert b.score(pair) == es, (what, b.score(pair), es)
-    assert b.n_alignments(pair) == (len(ea), 0), (what, b.n_alignments(pair), len(ea))      # (flags 0: never degenerate)
-    assert b.alignments(pair) == ea, what
-    assert b.alignments(pair, with_cell=True) == [a + (c,) for a, c in zip(ea, ec)], what
-
-
-def _check(b, refs, reads, exp, map_ref=True):
-    for r in range(len(refs)):
-        for q in range(len(reads)):
-            _check_pair(b, r * len(reads) + q, exp[(r, q)], (r, q, len(refs[r]), len(reads[q])))
-    if map_ref:
-        packed = b.ref_sites_packed()
-        for r in range(len(refs)):
-            total = int(np.int32(sum(exp[(r, q)][0] for q in range(len(reads)))))
-            sites = sorted([a for q in range(len(reads)) for a in exp[(r, q)][1]], key=lambda t: t[0])
-            assert b.ref_total(r) == total
-            assert packed[r] == (total, 0, sites), r
-            assert b.ref_match_sites(r) == sites, r
+    return u.expect(refs, reads, sc, GLOBAL, w, True, tie, matrix, cells=True)
 
 
 def _planted(rng, m, n, i):
     """a pair whose one maximum cell is (i, i): a common head of i bases, then a read of A's against a reference of C's"""
-    head = _rand(rng, i)
+    head = u.rand(rng, i)
     return head + "C" * (n - i), head + "A" * (m - i)
 
 
@@ -110,12 +73,12 @@ def _kats():
 def test_extend_kats(ctx, tie):
     for k in _kats():
         sc = tuple(k["scores"])
-        want = xr.align_numpy(k["ref"], k["read"], sc, k["w"], tie, cells=True)       # (strip 1024: none of these reads is banded)
+        want = _extend(k["ref"], k["read"], sc, k["w"], tie)       # (strip 1024: none of these reads is banded)
         if k["strip"] == 1024:
             e = k["strict" if tie else "serial"]
             assert want == (e["score"], [(b, tuple(s)) for b, s in e["alignments"]], [tuple(c) for c in e["cells"]]), k["name"]
         b = _run(ctx, [k["ref"]], [k["read"]], sc, tie, k["w"])
-        _check_pair(b, 0, want, k["name"])
+        u.check_pair(b, 0, want, GLOBAL, k["name"])
         b.free()
 
 
@@ -129,9 +92,9 @@ def test_extend_grid_shapes(ctx, matrix, tie):
     mat = gc.score_matrix() if matrix else None
     b = _run(ctx, refs, reads, sc, tie, 0, mat)
     for q in range(len(reads)):
-        _check_pair(b, q, xr.align_numpy(refs[0], reads[q], sc, 0, tie, mat, cells=True), (0, q))
+        u.check_pair(b, q, _extend(refs[0], reads[q], sc, 0, tie, mat), GLOBAL, (0, q))
     for q in gc.FIRST_OF_CLASS:
-        _check_pair(b, len(reads) + q, xr.align_numpy(refs[1], reads[q], sc, 0, tie, mat, cells=True), (1, q))
+        u.check_pair(b, len(reads) + q, _extend(refs[1], reads[q], sc, 0, tie, mat), GLOBAL, (1, q))
     b.free()
 
 
@@ -145,18 +108,18 @@ def test_extend_maximum_in_hard_places(ctx):
     for n, m in ((37, 300), (61, 64), (203, 1000)):               # column n, no multiple of 8; fewer columns than lanes
         cases.append(("column n = %d" % n, _planted(rng, m, n, n), (n, n)))
     # the last step of the last block: lane lact - 1 at column n with (n + lact - 1) % 8 == 0; three columns are deleted on the way
-    head = _rand(rng, 100)
+    head = u.rand(rng, 100)
     ref = head[:50] + "TTT" + head[50:]
     cases.append(("last step", (ref, head), (100, 103)))
     assert gc.rows_per_lane(100) == 2 and (103 + 50 - 1) % 8 == 0
     sc = (5, -3, -1, -1)
     for tie in (0, 1):
-        want = [xr.align_numpy(ref, read, sc, 0, tie, cells=True) for _, (ref, read), _ in cases]
+        want = [_extend(ref, read, sc, 0, tie) for _, (ref, read), _ in cases]
         for (name, _, cell), e in zip(cases, want):
             assert e[2] == [cell], (name, e[2])
         b = _run(ctx, [c[1][0] for c in cases], [c[1][1] for c in cases], sc, tie)
         for x, (name, _, _) in enumerate(cases):
-            _check_pair(b, x * len(cases) + x, want[x], name)
+            u.check_pair(b, x * len(cases) + x, want[x], GLOBAL, name)
         b.free()
 
 
@@ -165,8 +128,8 @@ def test_extend_maximum_in_hard_places(ctx):
 def test_extend_pad_rows_do_not_compete(ctx, matrix):
     rng = random.Random(9961)
     draw = gc.MATRIX_DRAW if matrix else "ACGT"
-    refs = [_rand(rng, 150, draw), _rand(rng, 37, draw)]
-    reads = [_rand(rng, 65, draw), _rand(rng, 200, draw)]
+    refs = [u.rand(rng, 150, draw), u.rand(rng, 37, draw)]
+    reads = [u.rand(rng, 65, draw), u.rand(rng, 200, draw)]
     assert [gc.rows_per_lane(len(q)) * 64 - len(q) for q in reads] == [63, 56]
     sc = (2, 1, -1, -3)
     mat = gc.score_matrix() if matrix else None
@@ -176,7 +139,7 @@ def test_extend_pad_rows_do_not_compete(ctx, matrix):
             assert all(c[0] == 65 for c in exp[(0, 0)][2])         # every base adds to the score: the best cells are in row m,
                                                                   # where the reference is long enough, and a pad row would beat them
         b = _run(ctx, refs, reads, sc, tie, 0, mat)
-        _check(b, refs, reads, exp)
+        u.check(b, refs, reads, exp, GLOBAL)
         b.free()
 
 
@@ -187,17 +150,17 @@ def test_extend_grid_walks(ctx, matrix, tie):
     rng = random.Random(9962)
     draw = gc.MATRIX_DRAW if matrix else "ACGT"
     grid = gc.walk_grid(matrix)
-    refs = [ref + _rand(rng, 9, draw) for _, ref, _ in grid]         # a tail the extension leaves unaligned
+    refs = [ref + u.rand(rng, 9, draw) for _, ref, _ in grid]         # a tail the extension leaves unaligned
     reads = [read for _, _, read in grid]
     assert [gc.rows_per_lane(len(read)) for read in reads] == list(gc.RS)
     mat = gc.score_matrix() if matrix else None
-    exp = [xr.align_numpy(ref, read, gc.WALK_SCORES, 0, tie, mat, cells=True) for ref, read in zip(refs, reads)]
+    exp = [_extend(ref, read, gc.WALK_SCORES, 0, tie, mat) for ref, read in zip(refs, reads)]
     assert all((len(read), len(ref)) not in e[2] for e, ref, read in zip(exp, refs, reads))
     assert all(gc.longest_run(e[1][0][1][0]) >= 8 and gc.longest_run(e[1][0][1][1]) >= 8 for e in exp)
     for device_strings in (1, 0):
         b = _run(ctx, refs, reads, gc.WALK_SCORES, tie, 0, mat, device_strings=device_strings)
         for x, e in enumerate(exp):
-            _check_pair(b, x * len(reads) + x, e, x + 1)
+            u.check_pair(b, x * len(reads) + x, e, GLOBAL, x + 1)
         b.free()
 
 
@@ -212,7 +175,7 @@ def test_extend_more_ties_than_cell_cap(ctx, tie):
     assert exp[(0, 0)][0] == 0 and exp[(0, 0)][2] == [(k, k) for k in range(1, 41)]
     b = _run(ctx, refs, reads, sc, tie, cell_cap=8)
     assert b.timing().rerun_pairs > 0
-    _check(b, refs, reads, exp)                                   # the list is complete and in order
+    u.check(b, refs, reads, exp, GLOBAL)                                   # the list is complete and in order
     b.free()
 
 
@@ -222,13 +185,13 @@ def test_extend_random_pairs_with_many_ties(ctx, tie):
     rng = random.Random(9963 + tie)
     differ = 0
     for sc, alpha in (((1, -1, -1, 0), "AC"), ((3, 1, 0, -2), "A"), ((0, -2, -2, 0), "ACGTacgtN\xe9"), ((2, -1, -1, -1), "AC")):
-        refs = [_rand(rng, rng.randint(1, 90), alpha) for _ in range(6)] + ["", "AC" * 150, "CACC"]
-        reads = [_rand(rng, rng.randint(1, 70), alpha) for _ in range(6)] + ["", "CA", "ACA"]
+        refs = [u.rand(rng, rng.randint(1, 90), alpha) for _ in range(6)] + ["", "AC" * 150, "CACC"]
+        reads = [u.rand(rng, rng.randint(1, 70), alpha) for _ in range(6)] + ["", "CA", "ACA"]
         exp = _expect(refs, reads, sc, 0, tie)
         differ += sum(sorted(e[2]) != e[2] for e in exp.values()) if tie else 0      # (a strict order that is not the row-major one)
         assert exp[(6, 0)] == (0, [], []) and exp[(0, 6)] == (0, [], [])
         b = _run(ctx, refs, reads, sc, tie)
-        _check(b, refs, reads, exp)
+        u.check(b, refs, reads, exp, GLOBAL)
         b.free()
     assert differ >= 5 or not tie
 
@@ -241,7 +204,7 @@ def test_extend_negative_and_zero_scores(ctx):
         exp = _expect(refs, reads, sc)
         assert all(v[0] == best for v in exp.values())
         b = _run(ctx, refs, reads, sc)
-        _check(b, refs, reads, exp)
+        u.check(b, refs, reads, exp, GLOBAL)
         for pair in range(9):
             assert not b.n_alignments(pair)[1] & sw.PAIR_DEGENERATE
         b.free()
@@ -254,10 +217,10 @@ def test_extend_long_reads(ctx, m, n, i):
     rng = random.Random(9964 + m + i)
     ref, read = _planted(rng, m, n, i)
     for tie in (0, 1):
-        want = xr.align_numpy(ref, read, SC, 0, tie, cells=True)
+        want = _extend(ref, read, SC, 0, tie)
         assert want[2] == [(i, i)] and want[0] == 5 * i
         b = _run(ctx, [ref], [read], SC, tie)
-        _check_pair(b, 0, want, (m, n, i, tie))
+        u.check_pair(b, 0, want, GLOBAL, (m, n, i, tie))
         b.free()
 
 
@@ -269,13 +232,13 @@ def test_extend_mixed_launch(ctx, matrix):
     mat = gc.score_matrix() if matrix else None
     exp = _expect(refs, reads, sc, 0, 0, mat)
     b = _run(ctx, refs, reads, sc, 0, 0, mat)
-    _check(b, refs, reads, exp)
+    u.check(b, refs, reads, exp, GLOBAL)
     b.free()
     w = gc.MIXED_BAND
     expb = _expect(refs, reads, sc, w, 0, mat)
     assert expb != exp and all(expb[(r, q)] == exp[(r, q)] for r in range(2) for q in range(2))      # the band applies to the long read
     b = _run(ctx, refs, reads, sc, 0, w, mat)
-    _check(b, refs, reads, expb)
+    u.check(b, refs, reads, expb, GLOBAL)
     b.free()
 
 
@@ -284,22 +247,22 @@ def test_extend_mixed_launch(ctx, matrix):
 def test_extend_band_maximum_on_a_window_edge(ctx, w):
     rng = random.Random(9965 + w)
     m = 2049
-    win = xr.windows(m, 2049, w)
+    win = gr.windows(m, 2049, w)
     # first in-band column of strip 1: w read bases are inserted on the way, the maximum is cell (1025, 1025 - w)
-    head = _rand(rng, 1025)
+    head = u.rand(rng, 1025)
     first = (head[:500] + head[500 + w:] + "C" * (2049 - 1025 + w), head + "A" * 1024)
     assert win[1][0] == 1025 - w
     # last in-band column of strip 0: w reference columns are deleted on the way, the maximum is cell (1024, 1024 + w)
-    head = _rand(rng, 1024)
-    last = (head[:500] + _rand(rng, w, "T") + head[500:] + "C" * (2049 - 1024 - w), head + "A" * 1025)
+    head = u.rand(rng, 1024)
+    last = (head[:500] + u.rand(rng, w, "T") + head[500:] + "C" * (2049 - 1024 - w), head + "A" * 1025)
     assert win[0][1] == 1024 + w
     for (ref, read), cell in ((first, (1025, 1025 - w)), (last, (1024, 1024 + w))):
         assert (len(read), len(ref)) == (m, 2049)
         for tie in (0, 1):
-            want = xr.align_numpy(ref, read, SC, w, tie, cells=True)
+            want = _extend(ref, read, SC, w, tie)
             assert want[2] == [cell], (want[2], cell)
             b = _run(ctx, [ref], [read], SC, tie, w)
-            _check_pair(b, 0, want, (w, cell, tie))
+            u.check_pair(b, 0, want, GLOBAL, (w, cell, tie))
             b.free()
 
 
@@ -308,16 +271,16 @@ def test_extend_band_shapes_and_matrix(ctx):
     rng = random.Random(9966)
     for w, m, matrix, tie in ((7, 1025, False, 0), (9, 2049, True, 1), (300, 2048, False, 1)):
         draw = gc.MATRIX_DRAW if matrix else "ACGT"
-        base = _rand(rng, m + w + 40, draw)
+        base = u.rand(rng, m + w + 40, draw)
         read = gc.mutate(rng, base, draw, 0.04, 0.004)[:m]
-        read += _rand(rng, m - len(read), draw)
+        read += u.rand(rng, m - len(read), draw)
         refs = [base[:m - w], base]
         reads = [read, gc.mutate(rng, base[200:500], draw)]       # (the short read of the batch is swept in full)
         mat = gc.score_matrix() if matrix else None
         sc = gc.SHAPE_SCORES[matrix]
         exp = _expect(refs, reads, sc, w, tie, mat)
         b = _run(ctx, refs, reads, sc, tie, w, mat)
-        _check(b, refs, reads, exp)
+        u.check(b, refs, reads, exp, GLOBAL)
         b.free()
 
 
@@ -329,14 +292,14 @@ def _refused(b, params):
 
 def test_extend_band_geometry(ctx):
     rng = random.Random(9967)
-    base = _rand(rng, 2100)
+    base = u.rand(rng, 2100)
     p = sw.make_params(SC[:3])
     # a read of 1025 bases has two strips: global mode takes a reference of up to 2048 + 16 bases; the end cell of an extend run
     # is free, so it takes a longer one
     ref, read = base, gc.mutate(rng, base, "ACGT", 0.03, 0.003)[:1025]
     assert len(ref) > 2048 + 16 and len(read) == 1025
     b = _run(ctx, [ref], [read], SC, 0, 16)
-    _check_pair(b, 0, xr.align_numpy(ref, read, SC, 16, 0, cells=True))
+    u.check_pair(b, 0, _extend(ref, read, SC, 16, 0), GLOBAL)
     ctx.set_option("extend", 0)                                   # today's behaviour: (m, n) outside the band
     _refused(b, p)
     b.free()
@@ -344,7 +307,7 @@ def test_extend_band_geometry(ctx):
     ctx.set_option("extend", 1)
     ctx.set_option("band", 8)
     b = ctx.upload([base[:2041]], [base[:2049]]).run(p)
-    _check_pair(b, 0, xr.align_numpy(base[:2041], base[:2049], SC, 8, 0, cells=True))
+    u.check_pair(b, 0, _extend(base[:2041], base[:2049], SC, 8, 0), GLOBAL)
     b.free()
     b = ctx.upload([base[:2040]], [base[:2049]])
     _refused(b, p)
@@ -358,8 +321,8 @@ _VARIANTS = {}
 def _variants():
     if not _VARIANTS:
         rng = random.Random(9968)
-        refs = ["ACGTTGCA" * 40, _rand(rng, 900), "GATTACA" * 30 + _rand(rng, 200), _rand(rng, 64), _rand(rng, 2500)]
-        reads = ["ACGTTGCAAC", _rand(rng, 150), "GATTACAGATTACA", _rand(rng, 300), refs[4][1000:1400]]
+        refs = ["ACGTTGCA" * 40, u.rand(rng, 900), "GATTACA" * 30 + u.rand(rng, 200), u.rand(rng, 64), u.rand(rng, 2500)]
+        reads = ["ACGTTGCAAC", u.rand(rng, 150), "GATTACAGATTACA", u.rand(rng, 300), refs[4][1000:1400]]
         _VARIANTS.update(refs=refs, reads=reads, exp=_expect(refs, reads, (2, -3, -1, -2)))
     return _VARIANTS["refs"], _VARIANTS["reads"], _VARIANTS["exp"]
 
@@ -374,7 +337,7 @@ def test_extend_options(ctx, opt):
             assert b.score(r * len(reads) + q) == want[0]
         assert [b.ref_total(r) for r in range(len(refs))] == [sum(exp[(r, q)][0] for q in range(len(reads))) for r in range(len(refs))]
     else:
-        _check(b, refs, reads, exp)
+        u.check(b, refs, reads, exp, GLOBAL)
     if opt[0] == "max_workspace_bytes":
         assert b.timing().fill_launches >= 2
     b.free()
@@ -384,8 +347,8 @@ def test_extend_options(ctx, opt):
 def test_extend_invalid_values_leave_the_context(ctx):
     k = _kats()[0]
     sc = tuple(k["scores"])
-    want = xr.align_numpy(k["ref"], k["read"], sc, 0, 0, cells=True)
-    assert want[:2] != er.align_numpy(k["ref"], k["read"], sc, GLOBAL, 0)
+    want = _extend(k["ref"], k["read"], sc, 0, 0)
+    assert want[:2] != gr.align_numpy(k["ref"], k["read"], sc, GLOBAL)
     for start in (1, 0):
         b = _run(ctx, [k["ref"]], [k["read"]], sc, extend=start)
         for bad in (2, -1, 1 << 40):
@@ -394,16 +357,16 @@ def test_extend_invalid_values_leave_the_context(ctx):
             assert e.value.code == ERR_INVALID
         b.run(sw.make_params(sc[:3]))                             # the next run is still what it was
         if start:
-            _check_pair(b, 0, want)
+            u.check_pair(b, 0, want, GLOBAL)
         else:
-            assert (b.score(0), b.alignments(0)) == er.align_numpy(k["ref"], k["read"], sc, GLOBAL, 0)
+            assert (b.score(0), b.alignments(0)) == gr.align_numpy(k["ref"], k["read"], sc, GLOBAL)
         b.free()
 
 
 @pytest.mark.parametrize("mode", [sw.ALIGN_LOCAL, sw.ALIGN_FIT])
 def test_extend_needs_global(ctx, mode):
     rng = random.Random(9969)
-    ref, read = _rand(rng, 200), _rand(rng, 80)
+    ref, read = u.rand(rng, 200), u.rand(rng, 80)
     ctx.set_option("gap_open", SC[3])
     ctx.set_option("align_mode", mode)
     ctx.set_option("extend", 1)
@@ -412,7 +375,7 @@ def test_extend_needs_global(ctx, mode):
     _refused(b, p)
     ctx.set_option("extend", 0)                                   # the batch is still usable
     b.run(p)
-    assert (b.score(0), b.alignments(0)) == er.align_numpy(ref, read, SC, mode, 0)
+    assert (b.score(0), b.alignments(0)) == gr.align_numpy(ref, read, SC, mode)
     ctx.set_option("gap_open", 0)                                 # the linear pipeline refuses it too
     ctx.set_option("align_mode", sw.ALIGN_LOCAL)
     ctx.set_option("extend", 1)
@@ -422,11 +385,11 @@ def test_extend_needs_global(ctx, mode):
 
 def test_extend_travels_with_the_run(ctx):
     rng = random.Random(9970)
-    base = _rand(rng, 700)
-    refs = [base[:600] + _rand(rng, 60), gc.mutate(rng, base), _rand(rng, 300)] + [gc.mutate(rng, base) for _ in range(5)]
-    reads = [gc.mutate(rng, base[:400]), base[:90] + _rand(rng, 40)]
+    base = u.rand(rng, 700)
+    refs = [base[:600] + u.rand(rng, 60), gc.mutate(rng, base), u.rand(rng, 300)] + [gc.mutate(rng, base) for _ in range(5)]
+    reads = [gc.mutate(rng, base[:400]), base[:90] + u.rand(rng, 40)]
     exp = _expect(refs, reads, SC)
-    glob = {k: er.align_numpy(refs[k[0]], reads[k[1]], SC, GLOBAL, 0) for k in exp}
+    glob = {k: gr.align_numpy(refs[k[0]], reads[k[1]], SC, GLOBAL) for k in exp}
     assert all(exp[k][:2] != glob[k] for k in exp)
     p = sw.make_params(SC[:3])
     ctx.set_option("gap_open", SC[3])
@@ -453,23 +416,24 @@ def test_extend_travels_with_the_run(ctx):
         assert c.pipeline_mode() == 3
         for r in range(c.n_refs):
             for q in range(len(reads)):
-                _check_pair(c, r * len(reads) + q, exp[(first + r, q)], (first + r, q))
+                u.check_pair(c, r * len(reads) + q, exp[(first + r, q)], GLOBAL, (first + r, q))
     assert n_chunks >= 2
     st.close()
 
 
 def test_extend_0_is_global(ctx):
-    """nothing moved: with extend = 0 a global run equals ends_reference global, before and after an extend run of the batch"""
+    """nothing moved: with extend = 0 a global run equals the reference's plain global mode, before and after an extend run of the
+    batch"""
     refs, reads, exp = _variants()
     sc = (2, -3, -1, -2)
     b = _run(ctx, refs, reads, sc, extend=0)
     p = sw.make_params(sc[:3])
-    glob = {(r, q): er.align_numpy(refs[r], reads[q], sc, GLOBAL, 0) for r in range(len(refs)) for q in range(len(reads))}
+    glob = {(r, q): gr.align_numpy(refs[r], reads[q], sc, GLOBAL) for r in range(len(refs)) for q in range(len(reads))}
     for value in (0, 1, 0):
         ctx.set_option("extend", value)
         b.run(p)
         if value:
-            _check(b, refs, reads, exp)
+            u.check(b, refs, reads, exp, GLOBAL)
             continue
         for r in range(len(refs)):
             for q in range(len(reads)):
@@ -484,11 +448,11 @@ def test_extend_mirror(ctx):
     sc = k["scores"]
     for cls, tie in ((sw.SmithWaterman.OptAlignments, 0), (sw.DistributedSW.OptAlignments, 1)):
         got = cls(ctx, align_mode=GLOBAL, extend=True).call([k["ref"], k["read"]], sc)
-        assert got == xr.align_numpy(k["ref"], k["read"], sc, 0, tie)
+        assert got == _extend(k["ref"], k["read"], sc, 0, tie, cells=False)
         assert ctx.options["extend"] == 0 and ctx.options["align_mode"] == sw.ALIGN_LOCAL
     reads = [k["read"], "ACGT"]
     total, (ref, sites) = sw.Distribution.MapRef(ctx, align_mode=GLOBAL, extend=True).call(((">r", k["ref"]), reads, (sc, ["a", "i", "d", "-"])))
-    exp = [xr.align_numpy(k["ref"], q, sc) for q in reads]
+    exp = [_extend(k["ref"], q, sc, cells=False) for q in reads]
     assert total == sum(e[0] for e in exp) and sites == [a for e in exp for a in e[1]]
 
 
@@ -499,11 +463,11 @@ def test_extend_bound_int32(ctx):
     e, o, m = -(1 << 20), 0, 64
     n_ok = (1 << 31) // -e - 64
     assert (64 + n_ok) * -e <= 1 << 31 < (64 + n_ok + 1) * -e
-    read = _rand(rng, m, "AC")
-    ref = read[:40] + _rand(rng, n_ok + 1 - 40, "AC")
+    read = u.rand(rng, m, "AC")
+    ref = read[:40] + u.rand(rng, n_ok + 1 - 40, "AC")
     sc = (1 << 20, -3, e, o)
     b = _run(ctx, [ref[:n_ok]], [read], sc)
-    _check_pair(b, 0, xr.align_scalar(ref[:n_ok], read, sc, cells=True))
+    u.check_pair(b, 0, _extend(ref[:n_ok], read, sc, align=gr.align_scalar), GLOBAL)
     b.free()
     b = ctx.upload([ref], [read])
     _refused(b, sw.make_params(sc[:3]))
@@ -514,12 +478,12 @@ def test_extend_bounds_banded(ctx):
     """under a band: 3 * |gap_open| + (1024 * ceil(m / 1024) + n) * |gap| <= 2^30 and M * S <= 2^29, with M = 2048"""
     rng = random.Random(9972)
     S = 1 << 18
-    read = _rand(rng, 1025, "AC")
-    ref = read[:900] + _rand(rng, 1149, "AC")
+    read = u.rand(rng, 1025, "AC")
+    ref = read[:900] + u.rand(rng, 1149, "AC")
     assert len(ref) == 2049
     sc = (5, -3, -S, 0)                                           # (2048 + 2048) * 2^18 = 2^30, and M * S = 2^29
     b = _run(ctx, [ref[:2048]], [read], sc, 0, 8)
-    _check_pair(b, 0, xr.align_scalar(ref[:2048], read, sc, 8, cells=True))
+    u.check_pair(b, 0, _extend(ref[:2048], read, sc, 8, align=gr.align_scalar), GLOBAL)
     _refused(b, sw.make_params((S + 1, -3, -S)))                  # M * S one step past 2^29
     b.free()
     b = ctx.upload([ref], [read])                                 # one more column
@@ -527,22 +491,15 @@ def test_extend_bounds_banded(ctx):
     b.free()
     ctx.set_option("band", 0)                                     # unbanded the bounds are 2^31 and 2^30: the same pair runs
     b = ctx.upload([ref], [read]).run(sw.make_params(sc[:3]))
-    _check_pair(b, 0, xr.align_numpy(ref, read, sc, cells=True))
+    u.check_pair(b, 0, _extend(ref, read, sc), GLOBAL)
     b.free()
 
 
 # 13 -- the JNI shim's entry point from plain C99 (tests/c/shim_extend.c)
 def test_c99_shim_sets_extend(tmp_path):
-    exe = tmp_path / "shim_extend"
-    lib = os.path.join(ROOT, "sparksmithwaterman_amd", "lib")
-    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Wextra", "-Werror", "-pedantic",
-                           "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "bindings", "jni"),
-                           os.path.join(ROOT, "tests", "c", "shim_extend.c"), os.path.join(ROOT, "bindings", "jni", "swmi_shim.c"),
-                           "-L", lib, "-lswmi", "-Wl,-rpath," + lib, "-o", str(exe)])
-    out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0, out.stdout + out.stderr
+    out = u.run_shim(tmp_path, "shim_extend")
     k = _kats()[0]
     assert (k["ref"], k["read"], k["scores"]) == ("ACGTTGCA", "ACGTAC", [2, -3, -1, -3])
-    g = er.align_numpy(k["ref"], k["read"], k["scores"], GLOBAL, 0)
-    assert out.stdout.splitlines() == ["8 1 1:ACGT/ACGT mode 3", "%d 1 1:%s/%s mode 3" % (g[0], g[1][0][1][0], g[1][0][1][1]),
+    g = gr.align_numpy(k["ref"], k["read"], k["scores"], GLOBAL)
+    assert out.splitlines() == ["8 1 1:ACGT/ACGT mode 3", "%d 1 1:%s/%s mode 3" % (g[0], g[1][0][1][0], g[1][0][1][1]),
                                        "refused %d" % ERR_UNSUPPORTED]

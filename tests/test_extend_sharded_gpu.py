@@ -1,6 +1,6 @@
 """sharded_files --align-mode global --extend --long-reads --band on one MI355X, two ranks: three reads, one of two strips,
 against two dozen references of about 2.1 kbp -- longer than 1024 * 2 + band, which a plain banded global run refuses.  The
-result file must be what a driver loop over tests/extend_reference.py builds, and what the mirror classes' own file driver
+result file must be what a driver loop over tests/gotoh_reference.py builds, and what the mirror classes' own file driver
 writes with the same options."""
 import os
 import random
@@ -11,7 +11,7 @@ import pytest
 
 import sparksmithwaterman_amd as sw
 
-import extend_reference as xr
+import gotoh_reference as gr
 
 pytestmark = pytest.mark.gpu
 
@@ -53,7 +53,7 @@ def test_sharded_files_extend(tmp_path):
     # the driver loop (Distribution.java:573,600-613): the running maximum of the references' totals from 0, ties kept
     best, opt = 0, []
     for meta, seq in refs:
-        res = [xr.align_numpy(seq, q, SCORES, W, 0) for q in reads]
+        res = [gr.align_numpy(seq, q, SCORES, gr.GLOBAL, W, True) for q in reads]
         total = sum(r[0] for r in res)
         sites = sorted([a for r in res for a in r[1]], key=lambda t: t[0])
         if total > best:
@@ -61,7 +61,7 @@ def test_sharded_files_extend(tmp_path):
         elif total == best:
             opt.append(([meta, seq], sites))
     assert [o[0][0] for o in opt] == [">gi|near"] and best > 5 * 1000
-    assert xr.align_numpy(near, long_read, SCORES, W, 0, cells=True)[2][0][0] == 1100        # to the end of the read, not of the reference
+    assert gr.align_numpy(near, long_read, SCORES, gr.GLOBAL, W, True, cells=True)[2][0][0] == 1100        # to the end of the read, not of the reference
     env = dict(os.environ, SWMI_ONE_GPU="1", PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""))
     cmd = [sys.executable, "-m", "sparksmithwaterman_amd.sharded_files", "--ref-dir", str(ref_dir), "--in-dir", str(in_dir),
            "--out-dir", str(out_dir), "--world", "2", "--scores", ",".join(map(str, SCORES)),

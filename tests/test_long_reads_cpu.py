@@ -2,8 +2,7 @@
 tests/test_long_reads_gpu.py do not rest on one restatement, and the sharded driver's parser knows --long-reads."""
 import pytest
 
-import affine_reference as ar
-import ends_reference as er
+import gotoh_reference as gr
 import long_reads_cases as lc
 
 
@@ -12,19 +11,19 @@ def test_seam_cases_scalar_and_numpy_agree(case):
     name, ref, read, sc = case
     assert len(read) > lc.STRIP
     for tie in (0, 1):
-        want = ar.align_scalar(ref, read, sc, tie)
-        assert ar.align_numpy(ref, read, sc, tie) == want, (name, tie)
+        want = gr.align_scalar(ref, read, sc, tie_mode=tie)
+        assert gr.align_numpy(ref, read, sc, tie_mode=tie) == want, (name, tie)
         assert want[0] > 0 and want[1]
     # what each case is there for
-    s, al = ar.align_numpy(ref, read, sc, 0)
-    ends = [a[0] + len(a[1][0].replace(ar.GAP_CHAR, "")) - 1 for a in al]                 # last reference column
-    spelled = [len(a[1][1].replace(ar.GAP_CHAR, "")) for a in al]                         # read bases
+    s, al = gr.align_numpy(ref, read, sc)
+    ends = [a[0] + len(a[1][0].replace(gr.GAP_CHAR, "")) - 1 for a in al]                 # last reference column
+    spelled = [len(a[1][1].replace(gr.GAP_CHAR, "")) for a in al]                         # read bases
     if name == "diagonal":
         assert s >= 80 * sc[0] and ref[30:110] in al[0][1][0] and ref[30:110] in al[0][1][1]
     if name == "insertion":
-        assert s == 200 * 2 - 6 - 40 and al[0][1][0] == ref[20:120] + ar.GAP_CHAR * 40 + ref[120:220]
+        assert s == 200 * 2 - 6 - 40 and al[0][1][0] == ref[20:120] + gr.GAP_CHAR * 40 + ref[120:220]
     if name.startswith("deletion"):
-        assert s >= 128 * 5 - 6 - 24 and ref[20:80] + ar.GAP_CHAR * 12 + ref[92:160] in al[0][1][1]
+        assert s >= 128 * 5 - 6 - 24 and ref[20:80] + gr.GAP_CHAR * 12 + ref[92:160] in al[0][1][1]
     if name == "ties_both_strips":
         assert len(al) == 2 and ends == [64, 64]
     if name in ("later_strip_higher", "later_strip_lower"):
@@ -38,14 +37,14 @@ def test_ends_cases_scalar_and_numpy_agree(case):
     name, ref, read, sc, mode = case
     ties = {"global_1025_2500": (1,), "global_2049_2500": (0,)}.get(name, (0, 1))
     for tie in ties:
-        want = er.align_scalar(ref, read, sc, mode, tie)
-        assert er.align_numpy(ref, read, sc, mode, tie) == want, (name, tie)
+        want = gr.align_scalar(ref, read, sc, mode, tie_mode=tie)
+        assert gr.align_numpy(ref, read, sc, mode, tie_mode=tie) == want, (name, tie)
         for begin, (ra, qa) in want[1]:
-            assert qa.replace(ar.GAP_CHAR, "") == read
+            assert qa.replace(gr.GAP_CHAR, "") == read
             if mode == lc.GLOBAL:
-                assert ra.replace(ar.GAP_CHAR, "") == ref
+                assert ra.replace(gr.GAP_CHAR, "") == ref
         if name == "fit_head_overhang":
-            assert all(a[1][0].startswith(ar.GAP_CHAR * 1100) and not a[1][0].startswith(ar.GAP_CHAR * 1101) for a in want[1])
+            assert all(a[1][0].startswith(gr.GAP_CHAR * 1100) and not a[1][0].startswith(gr.GAP_CHAR * 1101) for a in want[1])
 
 
 def test_sharded_files_parser_accepts_long_reads():

@@ -1,18 +1,16 @@
 """Reads longer than 1024 bases on the affine kernels (option "long_reads": the strip sweeps and the long traceback of
-swmi_affine.hip), against the restatements of tests/affine_reference.py, tests/ends_reference.py and
-tests/matrix_reference.py.  Every test first sets long_reads = 1."""
+swmi_affine.hip), against the restatement of tests/gotoh_reference.py.  Every test first sets
+long_reads = 1."""
 import random
 
-import numpy as np
 import pytest
 
 import sparksmithwaterman_amd as sw
 from sparksmithwaterman_amd import _capi
 from sparksmithwaterman_amd import matrix as M
 
-import affine_reference as ar
-import ends_reference as er
-import matrix_reference as mr
+import affine_gpu_util as u
+import gotoh_reference as gr
 import long_reads_cases as lc
 
 pytestmark = pytest.mark.gpu
@@ -28,47 +26,6 @@ def ctx():
     c.close()
 
 
-def _rand(rng, n, alphabet="ACGT"):
-    return "".join(rng.choice(alphabet) for _ in range(n))
-
-
-def _run(ctx, refs, reads, scores, tie=0, mode=0):
-    ctx.set_option("gap_open", scores[3])
-    ctx.set_option("align_mode", mode)
-    b = ctx.upload(refs, reads).run(sw.make_params(scores[:3], None, tie))
-    assert b.pipeline_mode() == 3
-    return b
-
-
-def _check(b, refs, reads, exp, alignments=True):
-    """every pair's score, alignment list and strings; the MapRef view (totals, stably sorted match sites);
-    exp[(r, q)] = (score, alignments)"""
-    for r in range(len(refs)):
-        for q in range(len(reads)):
-            pair = r * len(reads) + q
-            es, ea = exp[(r, q)]
-            assert b.score(pair) == es, (r, q, len(refs[r]), len(reads[q]))
-            if not alignments:
-                continue
-            n, flags = b.n_alignments(pair)
-            assert n == len(ea), (r, q, n, len(ea))
-            if flags & sw.PAIR_DEGENERATE:
-                assert es == 0
-                continue
-            assert b.alignments(pair) == ea, (r, q, len(refs[r]), len(reads[q]))
-    if alignments:
-        packed = b.ref_sites_packed()
-        for r in range(len(refs)):
-            total = int(np.int32(sum(exp[(r, q)][0] for q in range(len(reads)))))
-            sites = sorted([a for q in range(len(reads)) for a in exp[(r, q)][1] if a != (0, ("", ""))], key=lambda t: t[0])
-            ndeg = sum(len(exp[(r, q)][1]) for q in range(len(reads)) if exp[(r, q)][0] == 0)
-            assert b.ref_total(r) == total
-            assert packed[r] == (total, ndeg, sites), r
-    else:
-        for r in range(len(refs)):
-            assert b.ref_total(r) == int(np.int32(sum(exp[(r, q)][0] for q in range(len(reads)))))
-
-
 # 1 -- strip counts and skew: all three kernel families in one batch
 _SHAPES = {}
 
@@ -76,8 +33,8 @@ _SHAPES = {}
 def _shapes():
     if not _SHAPES:
         rng = random.Random(8201)
-        refs = [_rand(rng, n) for n in (1, 40, 63, 300, 700)]
-        reads = [_rand(rng, m) for m in (1025, 1088, 2047, 2048, 2049, 3100, 1, 64, 150, 1024)]
+        refs = [u.rand(rng, n) for n in (1, 40, 63, 300, 700)]
+        reads = [u.rand(rng, m) for m in (1025, 1088, 2047, 2048, 2049, 3100, 1, 64, 150, 1024)]
         for k in (0, 2, 4, 5):                                   # (something to find: a stretch of the longest reference on either side of a seam)
             reads[k] = reads[k][:990] + refs[4][100:180] + reads[k][1070:]
         _SHAPES["refs"], _SHAPES["reads"] = refs, reads
@@ -91,9 +48,9 @@ def test_long_reads_strip_counts_and_skew(ctx, o, tie):
     sc = (5, -3, -2, o)
     key = ("exp", o, tie)
     if key not in _SHAPES:
-        _SHAPES[key] = {(r, q): ar.align_numpy(refs[r], reads[q], sc, tie) for r in range(len(refs)) for q in range(len(reads))}
-    b = _run(ctx, refs, reads, sc, tie)
-    _check(b, refs, reads, _SHAPES[key])
+        _SHAPES[key] = u.expect(refs, reads, sc, tie=tie)
+    b = u.run(ctx, refs, reads, sc, tie, 0)
+    u.check(b, refs, reads, _SHAPES[key])
     b.free()
 
 
@@ -101,12 +58,12 @@ def test_long_reads_strip_counts_and_skew(ctx, o, tie):
 @pytest.mark.parametrize("tie", [0, 1])
 def test_long_reads_across_the_seam(ctx, tie):
     for name, ref, read, sc in lc.seam_cases():
-        want = ar.align_numpy(ref, read, sc, tie)
-        b = _run(ctx, [ref], [read], sc, tie)
+        want = gr.align_numpy(ref, read, sc, tie_mode=tie)
+        b = u.run(ctx, [ref], [read], sc, tie, 0)
         assert (b.score(0), b.alignments(0)) == want, name
-        _check(b, [ref], [read], {(0, 0): want})
+        u.check(b, [ref], [read], {(0, 0): want})
         b.free()
-        rows = sorted(len(a[1][1].replace(ar.GAP_CHAR, "")) for a in want[1])      # (local: read bases each alignment spells)
+        rows = sorted(len(a[1][1].replace(gr.GAP_CHAR, "")) for a in want[1])      # (local: read bases each alignment spells)
         if name == "ties_both_strips":
             assert len(want[1]) == 2, name
         if name in ("later_strip_higher", "later_strip_lower"):
@@ -117,13 +74,13 @@ def test_long_reads_across_the_seam(ctx, tie):
 def test_long_reads_cell_list_overflow_rerun(ctx):
     rng = random.Random(8203)
     ref = "ACGTTGCA" * 60
-    read = _rand(rng, 500, "T") + "ACGTTGCAAC" + _rand(rng, 590, "T")
+    read = u.rand(rng, 500, "T") + "ACGTTGCAAC" + u.rand(rng, 590, "T")
     assert len(read) == 1100
     sc = (5, -3, -2, -6)
-    want = ar.align_numpy(ref, read, sc, 0)
+    want = gr.align_numpy(ref, read, sc)
     assert len(want[1]) > 4
     ctx.set_option("cell_cap", 4)
-    b = _run(ctx, [ref], [read], sc, 0)
+    b = u.run(ctx, [ref], [read], sc, 0, 0)
     assert b.timing().rerun_pairs == 1
     assert b.n_alignments(0)[0] == len(want[1])
     assert (b.score(0), b.alignments(0)) == want
@@ -134,12 +91,12 @@ def test_long_reads_cell_list_overflow_rerun(ctx):
 @pytest.mark.parametrize("tie", [0, 1])
 def test_long_reads_fit_and_global(ctx, tie):
     for name, ref, read, sc, mode in lc.ends_cases():
-        want = er.align_numpy(ref, read, sc, mode, tie)
-        b = _run(ctx, [ref], [read], sc, tie, mode)
+        want = gr.align_numpy(ref, read, sc, mode, tie_mode=tie)
+        b = u.run(ctx, [ref], [read], sc, tie, mode)
         assert (b.score(0), b.alignments(0)) == want, name
         b.free()
         if name == "fit_head_overhang":                          # the j == 0 tail starts at row 1100 and crosses the seam
-            assert all(a[1][0].startswith(ar.GAP_CHAR * 1100) for a in want[1]), name
+            assert all(a[1][0].startswith(gr.GAP_CHAR * 1100) for a in want[1]), name
 
 
 # 5 -- BLOSUM62
@@ -147,14 +104,14 @@ def test_long_reads_fit_and_global(ctx, tie):
 def test_long_reads_blosum62(ctx, mode):
     rng = random.Random(8205)
     amino = "ARNDCQEGHILKMFPSTWYV"
-    ref = _rand(rng, 400, amino)
-    read = list(_rand(rng, 1500, amino))
+    ref = u.rand(rng, 400, amino)
+    read = list(u.rand(rng, 1500, amino))
     read[950:1150] = ref[100:300]                                 # (a stretch of the reference across the seam)
     read = "".join(read)
     sc = (5, -4, -1, -11)
     ctx.set_score_matrix(M.BLOSUM62)
-    b = _run(ctx, [ref], [read], sc, 0, mode)
-    assert (b.score(0), b.alignments(0)) == er.align_numpy(ref, read, sc, mode, 0, (M.BLOSUM62.alphabet, M.BLOSUM62.scores))
+    b = u.run(ctx, [ref], [read], sc, 0, mode)
+    assert (b.score(0), b.alignments(0)) == gr.align_numpy(ref, read, sc, mode, matrix=(M.BLOSUM62.alphabet, M.BLOSUM62.scores))
     b.free()
 
 
@@ -163,9 +120,9 @@ def test_long_reads_bounds(ctx):
     S = 1 << 19
     sc = (S, -S, -S, -S)
     rng = random.Random(8206)
-    read = _rand(rng, 2049, "AC")
-    b = _run(ctx, [read[:2048]], [read[:2048]], sc, 0)             # M * S = 2^30: runs, and H reaches 2^30
-    want = ar.align_numpy(read[:2048], read[:2048], sc, 0)        # (int64 arithmetic)
+    read = u.rand(rng, 2049, "AC")
+    b = u.run(ctx, [read[:2048]], [read[:2048]], sc, 0, 0)             # M * S = 2^30: runs, and H reaches 2^30
+    want = gr.align_numpy(read[:2048], read[:2048], sc)        # (int64 arithmetic)
     assert want[0] == 1 << 30
     assert (b.score(0), b.alignments(0)) == want
     b.free()
@@ -178,11 +135,11 @@ def test_long_reads_bounds(ctx):
     ctx.set_option("align_mode", 2)
     e_, n = 463419, 2586
     assert (2048 + n) * e_ == (1 << 31) - 2
-    ref = _rand(rng, n, "AC")
+    ref = u.rand(rng, n, "AC")
     ctx.set_option("gap_open", 0)
     b = ctx.upload([ref], [read[:1025]])                          # 2^31 - 2: runs
     b.run(sw.make_params((5, -3, -e_)))
-    assert b.score(0) == er.align_numpy(ref, read[:1025], (5, -3, -e_, 0), 2, 0)[0]
+    assert b.score(0) == gr.align_numpy(ref, read[:1025], (5, -3, -e_, 0), 2)[0]
     ctx.set_option("gap_open", -1)                                # 3 more: 2^31 + 1, one past
     with pytest.raises(_capi.SwmiError) as e:
         b.run(sw.make_params((5, -3, -e_)))
@@ -217,7 +174,7 @@ def test_long_reads_workspace_cap_is_a_status(ctx):
     rng = random.Random(8207)
     ctx.set_option("max_workspace_bytes", 1 << 20)
     ctx.set_option("gap_open", -6)
-    b = ctx.upload([_rand(rng, 700)], [_rand(rng, 3100)])          # 4 strips x 97 blocks x 4 KiB
+    b = ctx.upload([u.rand(rng, 700)], [u.rand(rng, 3100)])          # 4 strips x 97 blocks x 4 KiB
     with pytest.raises(_capi.SwmiError) as e:
         b.run(sw.make_params((5, -3, -2)))
     assert e.value.code == ERR_UNSUPPORTED
@@ -231,13 +188,13 @@ _PLUMB = {}
 def _plumbing():
     if not _PLUMB:
         rng = random.Random(8208)
-        refs = [_rand(rng, 90), "ACGTTGCA" * 12, _rand(rng, 120)]
-        reads = [_rand(rng, 2049) for _ in range(4)] + [_rand(rng, 100)]
+        refs = [u.rand(rng, 90), "ACGTTGCA" * 12, u.rand(rng, 120)]
+        reads = [u.rand(rng, 2049) for _ in range(4)] + [u.rand(rng, 100)]
         reads[1] = reads[1][:1000] + refs[0][10:80] + reads[1][1070:]
         reads[2] = reads[2][:2040] + "ACGTTGCAA"
         sc = (5, -3, -2, -6)
         _PLUMB.update(refs=refs, reads=reads, sc=sc,
-                      exp={(r, q): ar.align_numpy(refs[r], reads[q], sc, 0) for r in range(len(refs)) for q in range(len(reads))})
+                      exp=u.expect(refs, reads, sc))
     return _PLUMB["refs"], _PLUMB["reads"], _PLUMB["sc"], _PLUMB["exp"]
 
 
@@ -245,8 +202,8 @@ def _plumbing():
 def test_long_reads_options(ctx, opt):
     refs, reads, sc, exp = _plumbing()
     ctx.set_option(*opt)
-    b = _run(ctx, refs, reads, sc, 0)
-    _check(b, refs, reads, exp, alignments=opt[0] != "scores_only")
+    b = u.run(ctx, refs, reads, sc, 0, 0)
+    u.check(b, refs, reads, exp, alignments=opt[0] != "scores_only")
     if opt[0] == "max_workspace_bytes":
         assert b.timing().fill_launches >= 2
     b.free()
@@ -260,14 +217,14 @@ def test_long_reads_async_takes_the_value_at_the_call(ctx):
     ctx.set_option("long_reads", 0)                               # does not reach the run in flight
     b.wait()
     assert b.pipeline_mode() == 3
-    _check(b, refs, reads, exp)
+    u.check(b, refs, reads, exp)
     b.free()
 
 
 def test_long_reads_stream_equals_the_batch(ctx):
     rng = random.Random(8209)
-    refs = [_rand(rng, rng.randint(60, 200)) for _ in range(12)]
-    read = _rand(rng, 1500)
+    refs = [u.rand(rng, rng.randint(60, 200)) for _ in range(12)]
+    read = u.rand(rng, 1500)
     read = read[:990] + refs[5][20:90] + read[1060:]
     sc = (5, -3, -2, -6)
     ctx.set_option("gap_open", sc[3])
@@ -275,12 +232,12 @@ def test_long_reads_stream_equals_the_batch(ctx):
     ctx.set_option("long_reads", 0)                               # (the slots copied it at the open)
     st.push(refs[:7]).push(refs[7:]).finish()
     ctx.set_option("long_reads", 1)
-    b = _run(ctx, refs, [read], sc, 0)
+    b = u.run(ctx, refs, [read], sc, 0, 0)
     assert [int(t) for t in st.totals()] == [b.ref_total(r) for r in range(len(refs))]
     for first, c in st.chunks():
         assert c.pipeline_mode() == 3
         for r in range(c.n_refs):
             assert c.ref_match_sites(r) == b.ref_match_sites(first + r), first + r
-    assert b.ref_match_sites(5) == sorted(ar.align_numpy(refs[5], read, sc, 0)[1], key=lambda t: t[0])
+    assert b.ref_match_sites(5) == sorted(gr.align_numpy(refs[5], read, sc)[1], key=lambda t: t[0])
     st.close()
     b.free()

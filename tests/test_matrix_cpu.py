@@ -1,4 +1,4 @@
-"""Score matrices without a GPU: the two restatements of the contract (tests/matrix_reference.py) against each other, against the
+"""Score matrices without a GPU: the two restatements of the contract (tests/gotoh_reference.py) against each other, against the
 linear oracle and the affine restatement where the matrix changes nothing, against hand-derived known answers, and the Python
 side of the API (NCBI parser, BLOSUM62, validation)."""
 import json
@@ -10,8 +10,7 @@ import pytest
 from oracle import sw_oracle as orc
 from sparksmithwaterman_amd import matrix as M
 
-import affine_reference as ar
-import matrix_reference as mr
+import gotoh_reference as gr
 import limit_cases as lc
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -46,7 +45,7 @@ def test_restatements_agree(tie):
         mat = _rand_matrix(rng, rng.choice(["ACGT", "ACGTN", "AC", "acgT"]))
         sc = (rng.randint(-2, 5), rng.randint(-5, 2), -rng.randint(0, 4), -rng.randint(0, 5))
         ref, read = _rand(rng, rng.randint(0, 14), "ACGTNacgtX"), _rand(rng, rng.randint(0, 10), "ACGTNacgtX")
-        assert mr.align_scalar(ref, read, sc, mat, tie) == mr.align_numpy(ref, read, sc, mat, tie), (ref, read, sc, mat)
+        assert gr.align_scalar(ref, read, sc, tie_mode=tie, matrix=mat) == gr.align_numpy(ref, read, sc, tie_mode=tie, matrix=mat), (ref, read, sc, mat)
 
 
 @pytest.mark.parametrize("tie", [0, 1])
@@ -63,7 +62,7 @@ def test_restatements_agree_at_the_entry_bound(tie):
         sc = (lc.L, -lc.L, -lc.L, o)
         for ref in refs:
             for read in reads:
-                assert mr.align_scalar(ref, read, sc, mat, tie) == mr.align_numpy(ref, read, sc, mat, tie), (ref, read, o)
+                assert gr.align_scalar(ref, read, sc, tie_mode=tie, matrix=mat) == gr.align_numpy(ref, read, sc, tie_mode=tie, matrix=mat), (ref, read, o)
 
 
 @pytest.mark.parametrize("tie", [0, 1])
@@ -75,8 +74,8 @@ def test_identity_matrix_is_the_linear_oracle(tie):
         ref, read = _rand(rng, rng.randint(1, 30), "ACGTNacgt"), _rand(rng, rng.randint(1, 12), "ACGTNacgt")
         s, al = orc.opt_alignments((ref, read), (match, mismatch, gap), b"aid-", tie)
         exp = (s, [(a[0], tuple(a[1])) for a in al])
-        for f in (mr.align_scalar, mr.align_numpy):
-            assert f(ref, read, (match, mismatch, gap, 0), mat, tie) == exp, (ref, read)
+        for f in (gr.align_scalar, gr.align_numpy):
+            assert f(ref, read, (match, mismatch, gap, 0), tie_mode=tie, matrix=mat) == exp, (ref, read)
 
 
 @pytest.mark.parametrize("tie", [0, 1])
@@ -86,9 +85,9 @@ def test_identity_matrix_is_the_affine_restatement(tie):
         sc = (rng.randint(1, 6), -rng.randint(0, 5), -rng.randint(0, 3), -rng.randint(1, 8))
         mat = M.uniform("acgt", sc[0], sc[1])
         ref, read = _rand(rng, rng.randint(1, 30), "ACGTNacgt"), _rand(rng, rng.randint(1, 12), "ACGTNacgt")
-        exp = ar.align_numpy(ref, read, sc, tie)
-        assert mr.align_scalar(ref, read, sc, mat, tie) == exp
-        assert mr.align_numpy(ref, read, sc, mat, tie) == exp
+        exp = gr.align_numpy(ref, read, sc, tie_mode=tie)
+        assert gr.align_scalar(ref, read, sc, tie_mode=tie, matrix=mat) == exp
+        assert gr.align_numpy(ref, read, sc, tie_mode=tie, matrix=mat) == exp
 
 
 @pytest.mark.parametrize("k", range(len(_kats())))
@@ -97,10 +96,10 @@ def test_known_answers(k):
     mat = _kat_matrix(kat)
     sc, tie = tuple(kat["scores"]), kat["tie_mode"]
     exp = (kat["score"], [(a[0], (a[1], a[2])) for a in kat["alignments"]])
-    got = mr.align_scalar(kat["ref"], kat["read"], sc, mat, tie, matrices=True)
+    got = gr.align_scalar(kat["ref"], kat["read"], sc, tie_mode=tie, matrix=mat, matrices=True)
     assert got[:2] == exp, kat["name"]
     assert got[2] == kat["H"], kat["name"]
-    assert mr.align_numpy(kat["ref"], kat["read"], sc, mat, tie) == exp, kat["name"]
+    assert gr.align_numpy(kat["ref"], kat["read"], sc, tie_mode=tie, matrix=mat) == exp, kat["name"]
 
 
 def test_kat_asymmetric_pins_row_as_read():
@@ -112,12 +111,12 @@ def test_kat_asymmetric_pins_row_as_read():
 def test_cell_score_rule():
     mat = ("Acé", [[1, 2, 3], [4, 5, 6], [7, 8, 9]])
     sc = (10, -10, -1, 0)
-    assert mr.cell_score("C", "a", sc, mat) == 2             # read a (row 0), reference C (column 1)
-    assert mr.cell_score("a", "C", sc, mat) == 4
-    assert mr.cell_score("\xc9", "\xe9", sc, mat) == 9       # É / é: one symbol
-    assert mr.cell_score("G", "g", sc, mat) == 10            # outside the alphabet: equal -> match
-    assert mr.cell_score("G", "A", sc, mat) == -10           # one side outside: mismatch
-    assert mr.cell_score("\xff", "\xff", sc, mat) == 10 and mr.cell_score("\xff", "\xdf", sc, mat) == -10
+    assert gr.cell_score("C", "a", sc, mat) == 2             # read a (row 0), reference C (column 1)
+    assert gr.cell_score("a", "C", sc, mat) == 4
+    assert gr.cell_score("\xc9", "\xe9", sc, mat) == 9       # É / é: one symbol
+    assert gr.cell_score("G", "g", sc, mat) == 10            # outside the alphabet: equal -> match
+    assert gr.cell_score("G", "A", sc, mat) == -10           # one side outside: mismatch
+    assert gr.cell_score("\xff", "\xff", sc, mat) == 10 and gr.cell_score("\xff", "\xdf", sc, mat) == -10
 
 
 def test_blosum62():

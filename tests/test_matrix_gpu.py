@@ -1,14 +1,13 @@
 """Substitution score matrices on the GPU (swmi_set_score_matrix, the matrix sweeps of swmi_affine.hip).
 
 Checked against the oracle where the matrix changes nothing (the identity matrix at gap_open = 0) and against the numpy
-restatement of the contract in tests/matrix_reference.py otherwise."""
+restatement of the contract in tests/gotoh_reference.py otherwise."""
 import os
 import random
 import subprocess
 import sys
 import time
 
-import numpy as np
 import pytest
 
 import sparksmithwaterman_amd as sw
@@ -17,7 +16,8 @@ from sparksmithwaterman_amd import matrix as M
 from oracle import io_oracle_py as ioo
 from oracle import sw_oracle as orc
 
-import matrix_reference as mr
+import affine_gpu_util as u
+import gotoh_reference as gr
 import limit_cases as lc
 
 pytestmark = pytest.mark.gpu
@@ -48,46 +48,13 @@ def _kat_matrix(kat):
     return m["alphabet"], m["rows"]
 
 
-def _rand(rng, n, alphabet="ACGT"):
-    return "".join(rng.choice(alphabet) for _ in range(n))
-
-
-def _expect_linear(ref, read, scores, tie):
-    s, al = orc.opt_alignments((ref, read), scores[:3], b"aid-", tie)
-    return s, [(a[0], tuple(a[1])) for a in al]
-
-
-def _check(b, refs, reads, expect, map_ref=True, alignments=True):
-    """every pair's score, alignment list and strings; the MapRef view (totals, stably sorted match sites)"""
+def _expect_linear(refs, reads, scores, tie):
     exp = {}
     for r, ref in enumerate(refs):
         for q, read in enumerate(reads):
-            pair = r * len(reads) + q
-            es, ea = exp[(r, q)] = expect(ref, read)
-            assert b.score(pair) == es, (r, q, len(ref), len(read))
-            if not alignments:
-                continue
-            n, flags = b.n_alignments(pair)
-            assert n == len(ea), (r, q, n, len(ea))
-            if flags & sw.PAIR_DEGENERATE:
-                assert es == 0 and (n == 0 or b.alignment(pair, n - 1) == (0, ("", "")))
-                continue
-            assert b.alignments(pair) == ea, (r, q, ref, read)
-    if map_ref and alignments:
-        packed = b.ref_sites_packed()
-        for r in range(len(refs)):
-            total = int(np.int32(sum(exp[(r, q)][0] for q in range(len(reads)))))
-            sites = sorted([a for q in range(len(reads)) for a in exp[(r, q)][1] if a != (0, ("", ""))], key=lambda t: t[0])
-            ndeg = sum(len(exp[(r, q)][1]) for q in range(len(reads)) if exp[(r, q)][0] == 0)
-            assert b.ref_total(r) == total
-            assert packed[r] == (total, ndeg, sites), r
+            s, al = orc.opt_alignments((ref, read), scores[:3], b"aid-", tie)
+            exp[(r, q)] = (s, [(a[0], tuple(a[1])) for a in al])
     return exp
-
-
-def _run(ctx, refs, reads, scores, matrix, tie=0):
-    ctx.set_option("gap_open", scores[3])
-    ctx.set_score_matrix(*matrix)
-    return ctx.upload(refs, reads).run(sw.make_params(scores[:3], None, tie))
 
 
 def _rand_matrix(rng, alphabet, lo=-6, hi=8):
@@ -98,13 +65,13 @@ def _rand_matrix(rng, alphabet, lo=-6, hi=8):
 @pytest.mark.parametrize("tie", [0, 1])
 def test_identity_matrix_matches_the_oracle(ctx, tie):
     rng = random.Random(101 + tie)
-    refs = [_rand(rng, rng.randint(1, 700), rng.choice(["ACGT", "ACGTN", "ACGTacgtN"])) for _ in range(16)]
+    refs = [u.rand(rng, rng.randint(1, 700), rng.choice(["ACGT", "ACGTN", "ACGTacgtN"])) for _ in range(16)]
     refs[3] = "ACGTTGCA" * 60                           # periodic: a tied maximum per period
-    reads = [_rand(rng, rng.randint(1, 220), rng.choice(["ACGT", "acgtN"])) for _ in range(30)]
+    reads = [u.rand(rng, rng.randint(1, 220), rng.choice(["ACGT", "acgtN"])) for _ in range(30)]
     reads[5] = "ACGTTGCAAC"
-    b = _run(ctx, refs, reads, (5, -3, -4, 0), tuple(M.uniform("ACGT", 5, -3)), tie)
+    b = u.run(ctx, refs, reads, (5, -3, -4, 0), tie, matrix=tuple(M.uniform("ACGT", 5, -3)), mode3=False)
     assert b.pipeline_mode() == 3
-    _check(b, refs, reads, lambda rf, rd: _expect_linear(rf, rd, (5, -3, -4), tie))
+    u.check(b, refs, reads, _expect_linear(refs, reads, (5, -3, -4), tie))
     b.free()
 
 
@@ -112,23 +79,23 @@ def test_identity_matrix_matches_the_oracle(ctx, tie):
 @pytest.mark.parametrize("tie", [0, 1])
 def test_random_matrices_every_read_length(ctx, tie):
     rng = random.Random(111 + tie)
-    reads = [_rand(rng, m, "ACGTNacgtX") for m in (1, 2, 63, 64, 65, 128, 129, 200, 256, 257, 320, 384, 448, 512, 513, 640,
+    reads = [u.rand(rng, m, "ACGTNacgtX") for m in (1, 2, 63, 64, 65, 128, 129, 200, 256, 257, 320, 384, 448, 512, 513, 640,
                                                    704, 768, 832, 896, 960, 1000, 1024)]
-    refs = [_rand(rng, 300, "ACGTNacgtX"), _rand(rng, 1100, "ACGTN")]
+    refs = [u.rand(rng, 300, "ACGTNacgtX"), u.rand(rng, 1100, "ACGTN")]
     for o, mat in ((-6, _rand_matrix(rng, "ACGTN")),                       # asymmetric, positive off-diagonal entries
                    (0, _rand_matrix(rng, "acgt", -3, 9)),
                    (-2, _rand_matrix(rng, "AC"))):
         sc = (4, -3, -2, o)
-        b = _run(ctx, refs, reads, sc, mat, tie)
+        b = u.run(ctx, refs, reads, sc, tie, matrix=mat, mode3=False)
         assert b.pipeline_mode() == 3
-        _check(b, refs, reads, lambda rf, rd: mr.align_numpy(rf, rd, sc, mat, tie))
+        u.check(b, refs, reads, u.expect(refs, reads, sc, tie=tie, matrix=mat))
         b.free()
 
 
 def test_kats(ctx):
     for k in _golden("matrix_kat.json")["kats"]:
         mat = _kat_matrix(k)
-        b = _run(ctx, [k["ref"]], [k["read"]], tuple(k["scores"]), mat, k["tie_mode"])
+        b = u.run(ctx, [k["ref"]], [k["read"]], tuple(k["scores"]), k["tie_mode"], matrix=mat, mode3=False)
         assert b.score(0) == k["score"], k["name"]
         assert [[x[0], x[1][0], x[1][1]] for x in b.alignments(0)] == k["alignments"], k["name"]
         b.free()
@@ -137,11 +104,11 @@ def test_kats(ctx):
 def test_blosum62_protein(ctx):
     rng = random.Random(121)
     aa = "ARNDCQEGHILKMFPSTWYV"
-    refs = [_rand(rng, rng.randint(50, 900), aa) for _ in range(6)]
-    reads = [_rand(rng, rng.randint(20, 400), aa) for _ in range(5)] + [refs[2][100:260]]
+    refs = [u.rand(rng, rng.randint(50, 900), aa) for _ in range(6)]
+    reads = [u.rand(rng, rng.randint(20, 400), aa) for _ in range(5)] + [refs[2][100:260]]
     sc = (1, -1, -1, -11)
-    b = _run(ctx, refs, reads, sc, M.BLOSUM62)
-    _check(b, refs, reads, lambda rf, rd: mr.align_numpy(rf, rd, sc, (M.BLOSUM62.alphabet, M.BLOSUM62.scores), 0))
+    b = u.run(ctx, refs, reads, sc, 0, matrix=M.BLOSUM62, mode3=False)
+    u.check(b, refs, reads, u.expect(refs, reads, sc, matrix=(M.BLOSUM62.alphabet, M.BLOSUM62.scores)))
     b.free()
 
 
@@ -153,9 +120,9 @@ def test_ties_and_cell_overflow(ctx, tie):
     reads = ["CCTGGGTCCTGC", "AG", "ACGTNNACG", "GA"]
     mat = ("AGC", [[3, -1, 0], [-1, 3, 0], [0, 0, 1]])
     sc = (3, -2, -3, -1)
-    b = _run(ctx, refs, reads, sc, mat, tie)
+    b = u.run(ctx, refs, reads, sc, tie, matrix=mat, mode3=False)
     assert b.timing().rerun_pairs >= 1
-    _check(b, refs, reads, lambda rf, rd: mr.align_numpy(rf, rd, sc, mat, tie))
+    u.check(b, refs, reads, u.expect(refs, reads, sc, tie=tie, matrix=mat))
     b.free()
 
 
@@ -167,8 +134,9 @@ def test_path_longer_than_the_match_bound(ctx):
     sc = (1, -1, -1, 0)
     for o in (0, -1):
         s = sc[:3] + (o,)
-        b = _run(ctx, refs, reads, s, mat)
-        exp = _check(b, refs, reads, lambda rf, rd: mr.align_numpy(rf, rd, s, mat, 0))
+        b = u.run(ctx, refs, reads, s, 0, matrix=mat, mode3=False)
+        exp = u.expect(refs, reads, s, matrix=mat)
+        u.check(b, refs, reads, exp)
         assert len(exp[(0, 0)][1][0][1][0]) == 42
         b.free()
 
@@ -177,14 +145,14 @@ def test_path_longer_than_the_match_bound(ctx):
 @pytest.mark.parametrize("opt", [("scores_only", 1), ("device_strings", 0), ("max_workspace_bytes", 1 << 20)])
 def test_options(ctx, opt):
     rng = random.Random(131)
-    refs = ["ACGTTGCA" * 40, _rand(rng, 900, "ACGTN"), _rand(rng, 2500)]
-    reads = ["ACGTTGCAAC", _rand(rng, 150), _rand(rng, 300), _rand(rng, 400)]
+    refs = ["ACGTTGCA" * 40, u.rand(rng, 900, "ACGTN"), u.rand(rng, 2500)]
+    reads = ["ACGTTGCAAC", u.rand(rng, 150), u.rand(rng, 300), u.rand(rng, 400)]
     mat = _rand_matrix(rng, "ACGT")
     sc = (5, -3, -2, -6)
     ctx.set_option(*opt)
-    b = _run(ctx, refs, reads, sc, mat)
+    b = u.run(ctx, refs, reads, sc, 0, matrix=mat, mode3=False)
     assert b.pipeline_mode() == 3
-    _check(b, refs, reads, lambda rf, rd: mr.align_numpy(rf, rd, sc, mat, 0), alignments=opt[0] != "scores_only")
+    u.check(b, refs, reads, u.expect(refs, reads, sc, matrix=mat), alignments=opt[0] != "scores_only")
     if opt[0] == "max_workspace_bytes":
         assert b.timing().fill_launches >= 2
     b.free()
@@ -192,8 +160,8 @@ def test_options(ctx, opt):
 
 def test_async_swap_and_rerun(ctx):
     rng = random.Random(141)
-    refs = [_rand(rng, 1500) for _ in range(40)]
-    reads = [_rand(rng, 150) for _ in range(20)]
+    refs = [u.rand(rng, 1500) for _ in range(40)]
+    reads = [u.rand(rng, 150) for _ in range(20)]
     m1, m2 = _rand_matrix(rng, "ACGT"), _rand_matrix(rng, "ACGT", -2, 12)
     sc = (5, -3, -2, -4)
     ctx.set_option("gap_open", sc[3])
@@ -210,14 +178,14 @@ def test_async_swap_and_rerun(ctx):
     assert t_swap < 0.25 and time.perf_counter() - t0 >= 0.3
     ctx.set_option("debug_async_delay_us", 0)
     sub = [0, 7, 39]
-    e1 = {(r, q): mr.align_numpy(refs[r], reads[q], sc, m1, 0) for r in sub for q in range(len(reads))}
+    e1 = {(r, q): gr.align_numpy(refs[r], reads[q], sc, matrix=m1) for r in sub for q in range(len(reads))}
     for (r, q), (s, al) in e1.items():
         assert b.score(r * len(reads) + q) == s
         assert b.alignments(r * len(reads) + q) == al
     b.run(sw.make_params(sc[:3]))                       # the same batch again: now m2 (no stale plan)
     for r in sub:
         for q in range(len(reads)):
-            s, al = mr.align_numpy(refs[r], reads[q], sc, m2, 0)
+            s, al = gr.align_numpy(refs[r], reads[q], sc, matrix=m2)
             assert b.score(r * len(reads) + q) == s
             assert b.alignments(r * len(reads) + q) == al
     b.free()
@@ -225,8 +193,8 @@ def test_async_swap_and_rerun(ctx):
 
 def test_stream_from_fasta(ctx, tmp_path):
     rng = random.Random(151)
-    refs = [_rand(rng, rng.randint(200, 800), "ACGTN") for _ in range(40)]
-    reads = [_rand(rng, 150), refs[17][100:250], _rand(rng, 64)]
+    refs = [u.rand(rng, rng.randint(200, 800), "ACGTN") for _ in range(40)]
+    reads = [u.rand(rng, 150), refs[17][100:250], u.rand(rng, 64)]
     path = tmp_path / "refs.fa"
     with open(path, "w") as f:
         for k, r in enumerate(refs):
@@ -240,7 +208,7 @@ def test_stream_from_fasta(ctx, tmp_path):
     st = ctx.stream(reads, sw.make_params(sc[:3]), slots=2, chunk_bytes=1 << 16)
     ctx.clear_score_matrix()                           # (the stream keeps the matrix set when it was opened)
     st.push_file(path).finish()
-    exp = [[mr.align_numpy(r, q, sc, mat, 0) for q in reads] for r in refs]
+    exp = [[gr.align_numpy(r, q, sc, matrix=mat) for q in reads] for r in refs]
     assert [int(t) for t in st.totals()] == [sum(e[0] for e in row) for row in exp]
     for first, c in st.chunks():
         assert c.pipeline_mode() == 3
@@ -253,15 +221,15 @@ def test_stream_from_fasta(ctx, tmp_path):
 
 def test_clearing_returns_to_mode_1(ctx):
     rng = random.Random(161)
-    refs = [_rand(rng, 400) for _ in range(3)]
-    reads = [_rand(rng, 100) for _ in range(3)]
+    refs = [u.rand(rng, 400) for _ in range(3)]
+    reads = [u.rand(rng, 100) for _ in range(3)]
     b = ctx.upload(refs, reads)
     ctx.set_score_matrix("ACGT", [[9, 0, 0, 0], [0, 9, 0, 0], [0, 0, 9, 0], [0, 0, 0, 9]])
     assert b.run(sw.make_params()).pipeline_mode() == 3
     ctx.clear_score_matrix()
     b.run(sw.make_params())
     assert b.pipeline_mode() == 1
-    _check(b, refs, reads, lambda rf, rd: _expect_linear(rf, rd, (5, -3, -4), 0))
+    u.check(b, refs, reads, _expect_linear(refs, reads, (5, -3, -4), 0))
     b.free()
 
 
@@ -319,9 +287,10 @@ def test_64_symbols_at_the_entry_bound(ctx, tie):
     L = lc.L
     for o in (0, -L):
         sc = (L, -L, -L, o)
-        b = _run(ctx, refs, reads, sc, mat, tie)
+        b = u.run(ctx, refs, reads, sc, tie, matrix=mat, mode3=False)
         assert b.pipeline_mode() == 3
-        _check(b, refs, reads, lambda rf, rd: (mr.align_scalar if len(rd) <= 65 else mr.align_numpy)(rf, rd, sc, mat, tie))
+        u.check(b, refs, reads, {(r, q): (gr.align_scalar if len(read) <= 65 else gr.align_numpy)(ref, read, sc, tie_mode=tie, matrix=mat)
+                                 for r, ref in enumerate(refs) for q, read in enumerate(reads)})
         b.free()
 
 
@@ -331,25 +300,19 @@ def test_all_entries_at_the_bound(ctx):
     mat = (alpha, [[1 << 20] * 64 for _ in range(64)])
     refs, reads = ["ACGTAC#!~xA", "Z9"], ["CGT!a~", "z"]          # (~ is outside: match / mismatch; x is the symbol X)
     for sc, tie in (((5, -3, -4, -6), 0), ((1 << 20, -(1 << 20), -(1 << 20), 0), 1)):
-        b = _run(ctx, refs, reads, sc, mat, tie)
-        exp = _check(b, refs, reads, lambda rf, rd: mr.align_scalar(rf, rd, sc, mat, tie))
+        b = u.run(ctx, refs, reads, sc, tie, matrix=mat, mode3=False)
+        exp = {(r, q): gr.align_scalar(ref, read, sc, tie_mode=tie, matrix=mat) for r, ref in enumerate(refs) for q, read in enumerate(reads)}
+        u.check(b, refs, reads, exp)
         assert exp[(1, 1)][0] == 1 << 20                          # read z / reference Z: one symbol
         b.free()
 
 
 # 6 -- the JNI shim's entry point from plain C99 (tests/c/shim_matrix.c)
 def test_c99_shim_sets_the_matrix(tmp_path):
-    exe = tmp_path / "shim_matrix"
-    lib = os.path.join(ROOT, "sparksmithwaterman_amd", "lib")
-    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Wextra", "-Werror", "-pedantic",
-                           "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "bindings", "jni"),
-                           os.path.join(ROOT, "tests", "c", "shim_matrix.c"), os.path.join(ROOT, "bindings", "jni", "swmi_shim.c"),
-                           "-L", lib, "-lswmi", "-Wl,-rpath," + lib, "-o", str(exe)])
-    out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0, out.stdout + out.stderr
+    out = u.run_shim(tmp_path, "shim_matrix")
     # ref CAGCA, read ACAG; read A vs reference C = 5 (tests/golden/matrix_kat.json "asymmetric, longer")
-    s, al = mr.align_numpy("CAGCA", "ACAG", (1, -1, -2, -1), ("AC", [[2, 5], [-3, 2]]), 0)
-    assert out.stdout.split() == [str(s), str(len(al))] + ["%d:%s/%s" % (a[0], a[1][0], a[1][1]) for a in al] + ["cleared", "1"]
+    s, al = gr.align_numpy("CAGCA", "ACAG", (1, -1, -2, -1), matrix=("AC", [[2, 5], [-3, 2]]))
+    assert out.split() == [str(s), str(len(al))] + ["%d:%s/%s" % (a[0], a[1][0], a[1][1]) for a in al] + ["cleared", "1"]
 
 
 # 7 -- the sharded file driver with --matrix at world 1
@@ -358,11 +321,11 @@ def test_sharded_files_matrix(tmp_path):
     ref_dir, in_dir = tmp_path / "reference", tmp_path / "input"
     ref_dir.mkdir()
     in_dir.mkdir()
-    refs = [_rand(rng, rng.randint(100, 300)) for _ in range(12)]
+    refs = [u.rand(rng, rng.randint(100, 300)) for _ in range(12)]
     with open(ref_dir / "a.fa", "w") as f:
         for k, r in enumerate(refs):
             f.write(">gi|r%d\n%s\n" % (k, r))
-    reads = [refs[4][20:70], _rand(rng, 40)]
+    reads = [refs[4][20:70], u.rand(rng, 40)]
     (in_dir / "input1.txt").write_text(">gi reads\n" + "\n".join(reads) + "\n")
     mfile = tmp_path / "m.txt"
     mfile.write_text("# ACGT, transitions score 1\n   A  C  G  T\nA  5 -3  1 -3\nC -3  5 -3  1\nG  1 -3  5 -3\nT -3  1 -3  5\n")
@@ -376,7 +339,7 @@ def test_sharded_files_matrix(tmp_path):
     mat = M.load(str(mfile))
     best, opt = 0, []
     for k, r in enumerate(refs):
-        per = [mr.align_numpy(r, q, (5, -3, -4, 0), (mat.alphabet, mat.scores), 0) for q in reads]
+        per = [gr.align_numpy(r, q, (5, -3, -4, 0), matrix=(mat.alphabet, mat.scores)) for q in reads]
         total = sum(e[0] for e in per)
         sites = sorted([a for e in per for a in e[1]], key=lambda t: t[0])
         if total > best:
