@@ -42,6 +42,8 @@ public class GpuSmithWaterman
 	static native void nativeSetBand( long ctx , int band ) ;
 	/** seed extension with ALIGN_GLOBAL: 1 on, 0 off (include/swmi.h: option "extend") */
 	static native void nativeSetExtend( long ctx , int extend ) ;
+	/** the drop-off threshold of seed extension for reads longer than 1024 bases, 0: off (include/swmi.h: option "xdrop") */
+	static native void nativeSetXdrop( long ctx , int xdrop ) ;
 	/** substitution scores on the context: alphabet = n ISO-8859-1 symbols, scores = n * n, row = read base; null clears */
 	static native void nativeSetScoreMatrix( long ctx , byte[] alphabet , int[] scores ) ;
 	static native void nativeFreeBatch( long ctx , long batch ) ;
@@ -114,6 +116,17 @@ public class GpuSmithWaterman
 	 * every executor thread.
 	 */
 	public static void setExtend( boolean extend ) { EXTEND = extend ; }
+
+	/** the drop-off threshold every context runs seed extension with, 0: none (applied next to extend, before every batch) */
+	private static volatile int XDROP = 0 ;
+
+	/**
+	 * With setExtend( true ) and setLongReads( true ): the sweep of a read longer than 1024 bases ends behind the first strip of 1024
+	 * rows whose last row lies more than xdrop below the best score so far, and the best cell so far is the answer; 0 (the
+	 * default): off.  With xdrop &gt; 0 and no seed extension the batch is refused.  For every batch aligned from now on, on every
+	 * executor thread.
+	 */
+	public static void setXdrop( int xdrop ) { XDROP = xdrop ; }
 
 	/** the score matrix every context applies before its next batch: { alphabet , scores } (null: none), and its version */
 	private static volatile Object[] MATRIX = null ;
@@ -251,6 +264,7 @@ public class GpuSmithWaterman
 			nativeSetLongReads( ctx , LONG_READS ? 1 : 0 ) ;
 			nativeSetBand( ctx , BAND ) ;
 			nativeSetExtend( ctx , EXTEND ? 1 : 0 ) ;
+			nativeSetXdrop( ctx , XDROP ) ;
 			applyScoreMatrix( nc ) ;
 			long batch = nativeAlignBatch( ctx , sc[0] , sc[1] , sc[2] , TIE_SERIAL , types , refBuf , refOff , n , readBuf , readOff , reads.size() ) ;
 			try

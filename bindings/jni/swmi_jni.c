@@ -77,6 +77,13 @@ JNIEXPORT void JNICALL Java_sw_GpuSmithWaterman_nativeSetExtend(JNIEnv *env, jcl
     if (swmi_shim_set_extend((swmi_ctx *)(intptr_t)ctx, extend, err, sizeof err) != SWMI_OK) throw_msg(env, err);
 }
 
+/* the drop-off threshold of seed extension on this context from now on, 0: off */
+JNIEXPORT void JNICALL Java_sw_GpuSmithWaterman_nativeSetXdrop(JNIEnv *env, jclass cls, jlong ctx, jint xdrop) {
+    char err[640];
+    (void)cls;
+    if (swmi_shim_set_xdrop((swmi_ctx *)(intptr_t)ctx, xdrop, err, sizeof err) != SWMI_OK) throw_msg(env, err);
+}
+
 /* a substitution score matrix on this context from now on: alphabet = n ISO-8859-1 symbols, scores = int[n * n], row = read base;
  * alphabet == null clears it */
 JNIEXPORT void JNICALL Java_sw_GpuSmithWaterman_nativeSetScoreMatrix(JNIEnv *env, jclass cls, jlong ctx, jbyteArray alphabet,

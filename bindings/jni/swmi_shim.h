@@ -43,6 +43,11 @@ int swmi_shim_set_band(swmi_ctx *ctx, int32_t band, char *err, size_t err_len);
  * instead of at (m, n); a run in another align_mode is then refused (SWMI_ERR_UNSUPPORTED).  0 (the default): off.  Any other
  * value is SWMI_ERR_INVALID and leaves the context as it was. */
 int swmi_shim_set_extend(swmi_ctx *ctx, int32_t extend, char *err, size_t err_len);
+/* nativeSetXdrop: the drop-off threshold of seed extension from then on (swmi_set_option "xdrop"): the sweep of a read longer than
+ * 1024 bases ends behind the first strip of 1024 rows whose last row lies more than `xdrop` below the best score so far; a run that
+ * is not an extend run is then refused (SWMI_ERR_UNSUPPORTED).  0 (the default): off.  A negative value is SWMI_ERR_INVALID and
+ * leaves the context as it was. */
+int swmi_shim_set_xdrop(swmi_ctx *ctx, int32_t xdrop, char *err, size_t err_len);
 
 /* nativeSetScoreMatrix: a substitution score matrix on this context (swmi_set_score_matrix): `alphabet` = n symbols narrowed to
  * bytes (ISO-8859-1), `scores` = n * n entries, row = read base, column = reference base (n_scores must be n * n).  n = 0 clears

@@ -191,6 +191,26 @@ void        swmi_default_params(swmi_params *p);
  *                reference longer than 1024 NS + w.  extend = 1 with any other align_mode is SWMI_ERR_UNSUPPORTED before anything is
  *                launched.  With 0 nothing changes.  A run (async runs and stream slots included) takes the value set when it was asked
  *                for.
+ * xdrop (default 0 = off and no change; 1 .. 2^31 - 1 = the threshold X; any other value is SWMI_ERR_INVALID and leaves the context
+ *                as it was): the DROP-OFF rule of an extend run (ksw2's zdrop, BWA-MEM's and BLAST's X-drop), at the granularity of the
+ *                sweep's strips.  It acts on pairs whose read has MORE than 1024 bases (so long_reads = 1 is needed for there to be
+ *                any), with or without band, with or without a score matrix, in both tie modes; a pair whose read has at most 1024
+ *                bases is computed in full by the kernels it takes today -- the same rule as for band.  For a read of m > 1024 bases,
+ *                NS = ceil(m / 1024) strips with the windows c_lo(s) .. c_hi(s) of option band ((1, n) without one), and
+ *                s = 0 .. NS - 2:  best(s) = the maximum of H(i, j) over the existing cells with 1 <= i <= 1024 (s + 1), j >= 1 (the
+ *                extend run's running maximum after strip s);  seam(s) = the maximum of H(1024 (s + 1), j) over c_lo(s) <= j <=
+ *                c_hi(s).  The sweep stops behind the first strip s* with  best(s*) - seam(s*) > X  (strict; the difference is taken
+ *                exactly, not in int32): strips s* + 1 .. are not swept, the pair's score is best(s*), its maximum cells are the
+ *                cells of rows i <= 1024 (s* + 1) that tie at it, in extend's order, each walked as extend walks it (begin = 1).
+ *                That is the extend result of (ref, read[:1024 (s* + 1)]) under the same band (for s* = 0 without a band: a read of
+ *                1024 bases is not banded).  Without such a strip the result is exactly the extend result.  No flag is set: flags
+ *                stays 0, and swmi_pair_rows_swept tells a stopped pair.  No gap-length term is added to X as ksw2 adds one to zdrop
+ *                (it needs one anchor cell; the maximum here is a list of tied cells).  cell_cap, the exact-size re-run (it stops at
+ *                the same strip), scores_only, device_strings and zero_copy apply as to any extend run; the bounds and refusals are
+ *                extend's, unchanged -- a strip with an empty window is refused even where a stop would never reach it.  xdrop > 0 on
+ *                a run that is not an extend run (align_mode global with extend = 1) is SWMI_ERR_UNSUPPORTED before anything is
+ *                launched.  A run (async runs and stream slots included) takes the value set when it was asked for (DESIGN.md
+ *                section 8h).
  * Further knobs: spin_us (how long a run polls its stream before it blocks, default 2000); col_chunks (0 automatic,
  * 1 never, N > 1 force up to N column chunks per pair: a launch of few pairs with long references is swept by several
  * wavefronts per pair -- a read of more than 256 rows by several strip pipelines); debug_strip_spins / debug_reverse_strips (tests of the strip pipeline's give-up path);
@@ -233,7 +253,7 @@ int  swmi_batch_wait(swmi_ctx *ctx);
 typedef struct swmi_timing {
     float    fill_ms, traceback_ms, d2h_ms, total_ms;
     uint32_t fill_launches, rerun_pairs;
-    uint64_t cells;             /* sum of m*n over the pairs of the run            */
+    uint64_t cells;             /* sum of m*n over the pairs of the run (nominal: a pair that option "xdrop" stopped counts in full) */
     uint64_t dir_bytes;         /* direction-field bytes written                   */
     uint32_t strip_fallbacks;   /* launches repeated with the one-wavefront sweep after the strip pipeline gave up */
     uint32_t col_chunks;        /* column chunks the sweep of the run was split into (0: one sweep per pair): one wavefront each, one strip pipeline each for reads of several strips */
@@ -251,6 +271,10 @@ int  swmi_batch_mode(const swmi_batch *b, int *mode);
 uint64_t swmi_batch_n_pairs(const swmi_batch *b);
 int      swmi_pair_score(const swmi_batch *b, uint64_t pair, int32_t *score);
 int      swmi_pair_n_alignments(const swmi_batch *b, uint64_t pair, uint64_t *n, uint32_t *flags);
+/* The read rows the pair's sweep covered: the read's length m for every pair that was not stopped (in every mode, with xdrop = 0
+ * too), 1024 (s* + 1) for a pair that option "xdrop" stopped behind strip s*: rows < m is the sign of a stop.  Works under
+ * scores_only. */
+int      swmi_pair_rows_swept(const swmi_batch *b, uint64_t pair, uint32_t *rows);
 /* all pairs at once: scores[n] and/or n_alignments[n] (either may be NULL), n = swmi_batch_n_pairs */
 int      swmi_batch_pair_results(const swmi_batch *b, int32_t *scores, uint64_t *n_alignments, uint64_t n);
 /* k-th alignment of the pair in OptAlignments order.  *ref_aln / *read_aln point to

@@ -16,6 +16,7 @@ ALIGN_LOCAL = 0      # option "align_mode": Smith-Waterman (the default)
 ALIGN_FIT = 1        # the whole read against any stretch of the reference
 ALIGN_GLOBAL = 2     # the whole read against the whole reference
 BAND_MAX = 1 << 20   # option "band": the largest half-width (0: no band)
+XDROP_MAX = (1 << 31) - 1   # option "xdrop": the largest threshold (0: off)
 PAIR_DEGENERATE = 0x1
 
 
@@ -70,6 +71,7 @@ SYMBOLS = [
     ("swmi_pair_alignment", C.c_int, [_P, C.c_uint64, C.c_uint64, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                       C.POINTER(C.c_int32), C.POINTER(C.c_char_p), C.POINTER(C.c_char_p),
                                       C.POINTER(C.c_uint32)]),
+    ("swmi_pair_rows_swept", C.c_int, [_P, C.c_uint64, C.POINTER(C.c_uint32)]),
     ("swmi_batch_pair_results", C.c_int, [_P, C.POINTER(C.c_int32), _u64p, C.c_uint64]),
     ("swmi_batch_materialise_all", C.c_int, [_P, _u64p, _u64p]),
     ("swmi_ref_total", C.c_int, [_P, C.c_uint32, C.POINTER(C.c_int32)]),

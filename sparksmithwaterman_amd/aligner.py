@@ -139,6 +139,12 @@ class Batch:
         check(self._lib.swmi_pair_n_alignments(self._h, pair, C.byref(n), C.byref(f)))
         return n.value, f.value
 
+    def rows_swept(self, pair):
+        """the read rows the pair's sweep covered: the read's length, or 1024 * (strips swept) when option "xdrop" stopped it"""
+        v = C.c_uint32()
+        check(self._lib.swmi_pair_rows_swept(self._h, pair, C.byref(v)))
+        return v.value
+
     def alignment(self, pair, k, with_cell=False):
         b, ei, ej = C.c_int32(), C.c_int32(), C.c_int32()
         r, q, ln = C.c_char_p(), C.c_char_p(), C.c_uint32()

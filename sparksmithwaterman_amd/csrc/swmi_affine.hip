@@ -63,7 +63,11 @@
 //   taken over every cell of rows 1 .. m as in local mode, from INT32_MIN up (the score may be <= 0; there is no degenerate
 //   case).  The walk from a maximum cell is global mode's: these runs are traced back by the three global traceback kernels.
 //
-// How the 41 kernels are made: the 32 sweeps are aff_sweep_entry<RLO, RHI, MATRIX, MODE, LONG, BAND> over one block function
+// sw_affine_sweep_{long,band}_xdrop[_matrix]_kernel: the strip sweeps of an extend run under option "xdrop" (DESIGN.md 8h), XDROP =
+//   1: between two strips the wave takes the maximum of H over the seam row and ends the pair when the running maximum lies more
+//   than the threshold above it; the PairOut carries the strips swept.  The threshold is one more scalar kernel argument.
+//
+// How the 45 kernels are made: the 36 sweeps are aff_sweep_entry<RLO, RHI, MATRIX, MODE, LONG, BAND, XDROP> over one block function
 //   (aff_block8); the 9 tracebacks are aff_traceback<MODE, LONG, BAND>, where !LONG is the walk with one strip and !BAND the
 //   walk whose windows are the whole reference.  One macro defines the sweeps, one the tracebacks; the launchers pick a kernel
 //   from typed tables.  The per-pair sweep is two thin bodies, aff_sweep_pair and aff_sweep_long_pair<.., BAND> (the one strip
@@ -293,10 +297,12 @@ __device__ __forceinline__ AffCells aff_cell_list(const FillArgs &A, const PairD
 #define AFF_STORE_BLOCK                                                                                       \
     uint32_t *__restrict__ dst = dir + (uint64_t)w * R * WAVE + lane;                                         \
     _Pragma("unroll") for (int k = 0; k < R; ++k) dst[k * WAVE] = S.acc[k];
-// AFF_PAIR_OUT(NCELLS) (lane, pd, ccap): the pair's PairOut.  NCELLS is what the degenerate case counts -- the pair's m * n cells
+// AFF_PAIR_OUT(NCELLS, XFLAGS) (lane, pd, ccap): the pair's PairOut.  NCELLS is what the degenerate case counts -- the pair's m * n cells
 //   or, under option "band", those inside the band -- and is evaluated in that branch only.  Text as well: as a function that
 //   takes the count as a value it changes the short local sweeps, as one that picks it inside the banded local ones
-#define AFF_PAIR_OUT(NCELLS)                                                                                  \
+//   XFLAGS: what the sweep reports above the flag bits -- the strips swept of a pair that option "xdrop" stopped
+//   (SWMI_F_STRIPS_SHIFT), the constant 0 everywhere else
+#define AFF_PAIR_OUT(NCELLS, XFLAGS)                                                                                \
     if (lane == 0) {                                                                                          \
         PairOut po;                                                                                           \
         if (MODE == AFF_LOCAL && S.cnt == 0u) {     /* maximum 0: every cell ties (SmithWaterman.java:154) */ \
@@ -305,7 +311,7 @@ __device__ __forceinline__ AffCells aff_cell_list(const FillArgs &A, const PairD
             po.n_cells = NCELLS;                                                                              \
         } else {                                                                                              \
             po.score = S.thr;                                                                                 \
-            po.flags = S.cnt > ccap ? SWMI_F_CELL_OVF : 0u;                                                   \
+            po.flags = (S.cnt > ccap ? SWMI_F_CELL_OVF : 0u) | (XFLAGS);                                      \
             po.n_cells = S.cnt;                                                                               \
         }                                                                                                     \
         A.out[pd.out_id] = po;                                                                                \
@@ -339,7 +345,7 @@ __device__ __forceinline__ void aff_sweep_pair(const FillArgs &A, const int o, c
         aff_block8<R, STRICT, MATRIX, MODE>(S, rw, t0, lane, n, row0, vrows, o, A.gap, A.match, A.mismatch, cells, ccap);
         AFF_STORE_BLOCK
     }
-    AFF_PAIR_OUT((uint64_t)m * n)
+    AFF_PAIR_OUT((uint64_t)m * n, 0u)
 }
 
 // A read of more than 1024 bases, strip after strip (R = 16 in every strip), over the same pieces as aff_sweep_pair.  Strip sx
@@ -362,9 +368,15 @@ __device__ __forceinline__ void aff_sweep_pair(const FillArgs &A, const int o, c
 // clo(sx) - 1 .. chi(sx - 1), lies inside clo(sx - 1) .. chi(sx - 1), all written by the strip above, whose stores all precede
 // the fence between the strips (clo = 1: columns 1 .. n, and column 0 is the mode's).  Vector loads and stores only: the row is
 // rewritten by vector stores of this kernel, which the scalar cache does not see.
-template <bool STRICT, bool MATRIX, int MODE, bool BAND>
+// XDROP (option "xdrop", threshold xd >= 1, extend runs only): at the top of strip sx >= 1, behind the same fence,
+//   the wave takes the maximum of H over the seam row inside the window of strip sx - 1 -- seam[j - 1].x, 64 columns per step,
+//   vector loads for the reason above; lane 63 of strip sx - 1 wrote every one of them before the fence -- and ends the pair
+//   when the running maximum S.thr lies more than xd above it: the strips from sx on are not swept, the cell list holds the
+//   cells of rows <= 1024 sx, and the PairOut carries sx, the strips swept, above its flag bits.  The comparison is made once per
+//   strip on wave-uniform values, in 64 bits.  Nothing enters the block loop.
+template <bool STRICT, bool MATRIX, int MODE, bool BAND, bool XDROP = false>
 __device__ __forceinline__ void aff_sweep_long_pair(const FillArgs &A, const int o, const PairDesc pd, const uint32_t lane, const uint32_t nn,
-                                                    const uint32_t wb) {
+                                                    const uint32_t wb, const uint32_t xd = 0u) {
     constexpr int R = SWMI_AFF_RMAX;
     constexpr int OUT = BAND && MODE != AFF_LOCAL ? SWMI_AFF_BAND_NEG : 0;
     const SeqDesc rd = A.refs[pd.ref_id];
@@ -382,6 +394,7 @@ __device__ __forceinline__ void aff_sweep_long_pair(const FillArgs &A, const int
     Z.row = seam;
     uint32_t *__restrict__ dir = A.dir + pd.dir_off;
     uint64_t inband = 0ull;                                      // BAND: in-band cells with i <= m (the degenerate count)
+    uint32_t stopped = 0u;                                       // XDROP: the strips swept of a pair that was stopped, else 0
 
     AffState<R> S;
     S.thr = MODE == AFF_LOCAL ? 1 : INT32_MIN; S.cnt = 0;       // (wave-uniform: they live on across the strips)
@@ -415,6 +428,22 @@ __device__ __forceinline__ void aff_sweep_long_pair(const FillArgs &A, const int
         if constexpr (!BAND) dir = A.dir + pd.dir_off + (uint64_t)sx * swmi_aff_strip_words(n);
         // the strip above has written its window of the seam row: its stores are in memory before this strip loads any of it
         if (sx) __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent");
+        if constexpr (XDROP) {
+            if (sx) {
+                // seam(sx - 1): the maximum of H(1024 sx, j) over the window of strip sx - 1 (the seam row is indexed by j - 1)
+                const uint32_t plo = BAND ? swmi_aff_band_lo(sx - 1u, wb) : 1u, phi = BAND ? swmi_aff_band_hi(sx - 1u, n, wb) : n;
+                // (four loads in flight per lane: one after the other, a 10 kbp row is 157 round trips to HBM per test)
+                int smax = INT32_MIN;
+                uint32_t c = plo - 1u + lane;
+                for (; c + 3u * WAVE < phi; c += 4u * WAVE) {
+                    const int s0 = seam[c].x, s1 = seam[c + WAVE].x, s2 = seam[c + 2u * WAVE].x, s3 = seam[c + 3u * WAVE].x;
+                    smax = max(max(smax, max(s0, s1)), max(s2, s3));
+                }
+                for (; c < phi; c += WAVE) smax = max(smax, seam[c].x);
+                smax = wave_max_i32(smax);
+                if ((int64_t)S.thr - (int64_t)smax > (int64_t)xd) { stopped = sx; break; }
+            }
+        }
         if constexpr (BAND) {
             if (clo > 1u) S.nh_prev = seam[clo - 2u].x;                            // (a vector load, behind the fence)
             else S.nh_prev = MODE != AFF_LOCAL && sx ? o + (int)(sx * SWMI_AFF_MAX_READ) * A.gap : 0;
@@ -448,7 +477,7 @@ __device__ __forceinline__ void aff_sweep_long_pair(const FillArgs &A, const int
         }
         if constexpr (BAND) dir += (uint64_t)W * R * WAVE;
     }
-    AFF_PAIR_OUT(BAND ? inband : (uint64_t)m * n)
+    AFF_PAIR_OUT(BAND ? inband : (uint64_t)m * n, XDROP ? stopped << SWMI_F_STRIPS_SHIFT : 0u)
 }
 
 #undef AFF_LOAD_ROWS
@@ -467,9 +496,11 @@ __device__ __forceinline__ void aff_sweep_dispatch(const FillArgs &A, const int 
 
 // mat / nn (MATRIX only): the score matrix image (swmi_aff_mat_words) and its side n + 1
 // LONG: the strip sweep of reads longer than 1024 bases (RLO, RHI unused); BAND (with LONG): inside a band of half-width wb
-template <int RLO, int RHI, bool MATRIX, int MODE = AFF_LOCAL, bool LONG = false, bool BAND = false>
+// XDROP (with LONG and AFF_EXTEND): the strip sweep under option "xdrop", threshold xd
+template <int RLO, int RHI, bool MATRIX, int MODE = AFF_LOCAL, bool LONG = false, bool BAND = false, bool XDROP = false>
 __device__ __forceinline__ void aff_sweep_entry(const FillArgs &A, const int o, const uint32_t *__restrict__ mat, const uint32_t nn,
-                                                const uint32_t wb = 0u) {
+                                                const uint32_t wb = 0u, const uint32_t xd = 0u) {
+    static_assert(!XDROP || (LONG && MODE == AFF_EXTEND), "xdrop is an option of the strip sweeps of an extend run");
     if (blockIdx.x == 0 && threadIdx.x == 0) A.hdr->reserved = 0ull;      // the traceback's bump allocator
     if (MATRIX) {                                                          // (before any wavefront leaves)
         for (uint32_t x = threadIdx.x; x < 256u; x += WAVE * AFF_WAVES) aff_mkey[x] = mat[x];
@@ -486,8 +517,8 @@ __device__ __forceinline__ void aff_sweep_entry(const FillArgs &A, const int o, 
     const PairDesc pd = A.pairs[pair];
     if constexpr (LONG) {
         if (uni(A.reads[pd.read_id].len) <= SWMI_AFF_MAX_READ) return;
-        if (A.strict) aff_sweep_long_pair<true, MATRIX, MODE, BAND>(A, o, pd, lane, nn, wb);
-        else          aff_sweep_long_pair<false, MATRIX, MODE, BAND>(A, o, pd, lane, nn, wb);
+        if (A.strict) aff_sweep_long_pair<true, MATRIX, MODE, BAND, XDROP>(A, o, pd, lane, nn, wb, xd);
+        else          aff_sweep_long_pair<false, MATRIX, MODE, BAND, XDROP>(A, o, pd, lane, nn, wb, xd);
         return;
     }
     const uint32_t R = uni(swmi_aff_rows_per_lane(A.reads[pd.read_id].len));
@@ -498,62 +529,83 @@ __device__ __forceinline__ void aff_sweep_entry(const FillArgs &A, const int o, 
 
 }  // namespace
 
-// The 32 sweep kernels: local, fit and global (option "align_mode") and extend (option "extend"), each plain and with a score matrix (MATRIX = 0 / 1), each
+// The 36 sweep kernels: local, fit and global (option "align_mode") and extend (option "extend"), each plain and with a score matrix (MATRIX = 0 / 1), each
 // narrow (R = 1..4), wide (R = 5..16), long (option "long_reads": RLO, RHI unused) and banded long (option "band", BAND = 1:
-// the half-width is one more scalar argument).  MATRIX and BAND make the four signatures.
-#define AFF_SWEEP_PARAMS_00 const FillArgs A, const int gap_open
-#define AFF_SWEEP_PARAMS_10 const FillArgs A, const int gap_open, const uint32_t *mat, const uint32_t nn
-#define AFF_SWEEP_PARAMS_01 const FillArgs A, const int gap_open, const uint32_t band
-#define AFF_SWEEP_PARAMS_11 const FillArgs A, const int gap_open, const uint32_t *mat, const uint32_t nn, const uint32_t band
-#define AFF_SWEEP_ARGS_00 A, gap_open, nullptr, 0u
-#define AFF_SWEEP_ARGS_10 A, gap_open, mat, nn
-#define AFF_SWEEP_ARGS_01 A, gap_open, nullptr, 0u, band
-#define AFF_SWEEP_ARGS_11 A, gap_open, mat, nn, band
-#define AFF_SWEEP_KERNEL(name, RLO, RHI, MATRIX, MODE, LONG, BAND)                                             \
-    extern "C" __global__ void __launch_bounds__(WAVE * AFF_WAVES) name(AFF_SWEEP_PARAMS_##MATRIX##BAND) {    \
-        aff_sweep_entry<RLO, RHI, MATRIX != 0, MODE, LONG, BAND != 0>(AFF_SWEEP_ARGS_##MATRIX##BAND);         \
+// the half-width is one more scalar argument).  The long and banded long extend sweeps come once more under option "xdrop" (XDROP = 1:
+// the threshold is one more scalar argument, the last).  MATRIX, BAND and XDROP make the signatures.
+#define AFF_SWEEP_PARAMS_000 const FillArgs A, const int gap_open
+#define AFF_SWEEP_PARAMS_100 const FillArgs A, const int gap_open, const uint32_t *mat, const uint32_t nn
+#define AFF_SWEEP_PARAMS_010 const FillArgs A, const int gap_open, const uint32_t band
+#define AFF_SWEEP_PARAMS_110 const FillArgs A, const int gap_open, const uint32_t *mat, const uint32_t nn, const uint32_t band
+#define AFF_SWEEP_PARAMS_001 AFF_SWEEP_PARAMS_000, const uint32_t xdrop
+#define AFF_SWEEP_PARAMS_101 AFF_SWEEP_PARAMS_100, const uint32_t xdrop
+#define AFF_SWEEP_PARAMS_011 AFF_SWEEP_PARAMS_010, const uint32_t xdrop
+#define AFF_SWEEP_PARAMS_111 AFF_SWEEP_PARAMS_110, const uint32_t xdrop
+#define AFF_SWEEP_ARGS_000 A, gap_open, nullptr, 0u
+#define AFF_SWEEP_ARGS_100 A, gap_open, mat, nn
+#define AFF_SWEEP_ARGS_010 A, gap_open, nullptr, 0u, band
+#define AFF_SWEEP_ARGS_110 A, gap_open, mat, nn, band
+#define AFF_SWEEP_ARGS_001 A, gap_open, nullptr, 0u, 0u, xdrop
+#define AFF_SWEEP_ARGS_101 A, gap_open, mat, nn, 0u, xdrop
+#define AFF_SWEEP_ARGS_011 A, gap_open, nullptr, 0u, band, xdrop
+#define AFF_SWEEP_ARGS_111 A, gap_open, mat, nn, band, xdrop
+#define AFF_SWEEP_KERNEL(name, RLO, RHI, MATRIX, MODE, LONG, BAND, XDROP)                                                 \
+    extern "C" __global__ void __launch_bounds__(WAVE * AFF_WAVES) name(AFF_SWEEP_PARAMS_##MATRIX##BAND##XDROP) {        \
+        aff_sweep_entry<RLO, RHI, MATRIX != 0, MODE, LONG, BAND != 0, XDROP != 0>(AFF_SWEEP_ARGS_##MATRIX##BAND##XDROP); \
     }
-AFF_SWEEP_KERNEL(sw_affine_sweep_kernel, 1, 4, 0, AFF_LOCAL, false, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_wide_kernel, 5, SWMI_AFF_RMAX, 0, AFF_LOCAL, false, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_long_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, AFF_LOCAL, true, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_matrix_kernel, 1, 4, 1, AFF_LOCAL, false, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_matrix_wide_kernel, 5, SWMI_AFF_RMAX, 1, AFF_LOCAL, false, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_long_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, AFF_LOCAL, true, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_fit_kernel, 1, 4, 0, AFF_FIT, false, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_fit_wide_kernel, 5, SWMI_AFF_RMAX, 0, AFF_FIT, false, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_long_fit_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, AFF_FIT, true, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_fit_matrix_kernel, 1, 4, 1, AFF_FIT, false, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_fit_matrix_wide_kernel, 5, SWMI_AFF_RMAX, 1, AFF_FIT, false, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_long_fit_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, AFF_FIT, true, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_global_kernel, 1, 4, 0, AFF_GLOBAL, false, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_global_wide_kernel, 5, SWMI_AFF_RMAX, 0, AFF_GLOBAL, false, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_long_global_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, AFF_GLOBAL, true, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_global_matrix_kernel, 1, 4, 1, AFF_GLOBAL, false, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_global_matrix_wide_kernel, 5, SWMI_AFF_RMAX, 1, AFF_GLOBAL, false, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_long_global_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, AFF_GLOBAL, true, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_band_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, AFF_LOCAL, true, 1)
-AFF_SWEEP_KERNEL(sw_affine_sweep_band_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, AFF_LOCAL, true, 1)
-AFF_SWEEP_KERNEL(sw_affine_sweep_band_fit_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, AFF_FIT, true, 1)
-AFF_SWEEP_KERNEL(sw_affine_sweep_band_fit_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, AFF_FIT, true, 1)
-AFF_SWEEP_KERNEL(sw_affine_sweep_band_global_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, AFF_GLOBAL, true, 1)
-AFF_SWEEP_KERNEL(sw_affine_sweep_band_global_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, AFF_GLOBAL, true, 1)
-AFF_SWEEP_KERNEL(sw_affine_sweep_extend_kernel, 1, 4, 0, AFF_EXTEND, false, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_extend_wide_kernel, 5, SWMI_AFF_RMAX, 0, AFF_EXTEND, false, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_long_extend_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, AFF_EXTEND, true, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_extend_matrix_kernel, 1, 4, 1, AFF_EXTEND, false, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_extend_matrix_wide_kernel, 5, SWMI_AFF_RMAX, 1, AFF_EXTEND, false, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_long_extend_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, AFF_EXTEND, true, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_band_extend_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, AFF_EXTEND, true, 1)
-AFF_SWEEP_KERNEL(sw_affine_sweep_band_extend_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, AFF_EXTEND, true, 1)
+AFF_SWEEP_KERNEL(sw_affine_sweep_kernel, 1, 4, 0, AFF_LOCAL, false, 0, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_wide_kernel, 5, SWMI_AFF_RMAX, 0, AFF_LOCAL, false, 0, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_long_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, AFF_LOCAL, true, 0, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_matrix_kernel, 1, 4, 1, AFF_LOCAL, false, 0, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_matrix_wide_kernel, 5, SWMI_AFF_RMAX, 1, AFF_LOCAL, false, 0, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_long_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, AFF_LOCAL, true, 0, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_fit_kernel, 1, 4, 0, AFF_FIT, false, 0, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_fit_wide_kernel, 5, SWMI_AFF_RMAX, 0, AFF_FIT, false, 0, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_long_fit_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, AFF_FIT, true, 0, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_fit_matrix_kernel, 1, 4, 1, AFF_FIT, false, 0, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_fit_matrix_wide_kernel, 5, SWMI_AFF_RMAX, 1, AFF_FIT, false, 0, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_long_fit_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, AFF_FIT, true, 0, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_global_kernel, 1, 4, 0, AFF_GLOBAL, false, 0, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_global_wide_kernel, 5, SWMI_AFF_RMAX, 0, AFF_GLOBAL, false, 0, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_long_global_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, AFF_GLOBAL, true, 0, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_global_matrix_kernel, 1, 4, 1, AFF_GLOBAL, false, 0, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_global_matrix_wide_kernel, 5, SWMI_AFF_RMAX, 1, AFF_GLOBAL, false, 0, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_long_global_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, AFF_GLOBAL, true, 0, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_band_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, AFF_LOCAL, true, 1, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_band_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, AFF_LOCAL, true, 1, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_band_fit_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, AFF_FIT, true, 1, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_band_fit_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, AFF_FIT, true, 1, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_band_global_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, AFF_GLOBAL, true, 1, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_band_global_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, AFF_GLOBAL, true, 1, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_extend_kernel, 1, 4, 0, AFF_EXTEND, false, 0, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_extend_wide_kernel, 5, SWMI_AFF_RMAX, 0, AFF_EXTEND, false, 0, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_long_extend_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, AFF_EXTEND, true, 0, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_extend_matrix_kernel, 1, 4, 1, AFF_EXTEND, false, 0, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_extend_matrix_wide_kernel, 5, SWMI_AFF_RMAX, 1, AFF_EXTEND, false, 0, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_long_extend_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, AFF_EXTEND, true, 0, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_band_extend_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, AFF_EXTEND, true, 1, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_band_extend_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, AFF_EXTEND, true, 1, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_long_xdrop_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, AFF_EXTEND, true, 0, 1)
+AFF_SWEEP_KERNEL(sw_affine_sweep_long_xdrop_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, AFF_EXTEND, true, 0, 1)
+AFF_SWEEP_KERNEL(sw_affine_sweep_band_xdrop_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, AFF_EXTEND, true, 1, 1)
+AFF_SWEEP_KERNEL(sw_affine_sweep_band_xdrop_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, AFF_EXTEND, true, 1, 1)
 #undef AFF_SWEEP_KERNEL
-#undef AFF_SWEEP_PARAMS_00
-#undef AFF_SWEEP_PARAMS_10
-#undef AFF_SWEEP_PARAMS_01
-#undef AFF_SWEEP_PARAMS_11
-#undef AFF_SWEEP_ARGS_00
-#undef AFF_SWEEP_ARGS_10
-#undef AFF_SWEEP_ARGS_01
-#undef AFF_SWEEP_ARGS_11
+#undef AFF_SWEEP_PARAMS_000
+#undef AFF_SWEEP_PARAMS_001
+#undef AFF_SWEEP_PARAMS_100
+#undef AFF_SWEEP_PARAMS_101
+#undef AFF_SWEEP_PARAMS_010
+#undef AFF_SWEEP_PARAMS_011
+#undef AFF_SWEEP_PARAMS_110
+#undef AFF_SWEEP_PARAMS_111
+#undef AFF_SWEEP_ARGS_000
+#undef AFF_SWEEP_ARGS_001
+#undef AFF_SWEEP_ARGS_100
+#undef AFF_SWEEP_ARGS_101
+#undef AFF_SWEEP_ARGS_010
+#undef AFF_SWEEP_ARGS_011
+#undef AFF_SWEEP_ARGS_110
+#undef AFF_SWEEP_ARGS_111
 
 // ------------------------------------------------------------------------------------------------
 // traceback
@@ -736,10 +788,12 @@ AFF_TRACEBACK_KERNEL(sw_affine_traceback_band_global_kernel, AFF_GLOBAL, true, 1
 // long_reads 0: the narrow and the wide sweep; r_min / r_max: the rows per lane of the launch's shortest and longest read (only
 //   the kernels that have pairs are launched).  long_reads 1: the strip sweep (every pair has a read longer than 1024 bases)
 // band: with long_reads, the half-width of option "band" (0: none): the banded strip sweep
+// xdrop: with long_reads and align_mode 3, the threshold of option "xdrop" (0: none): the strip sweep that may stop at a seam
 extern "C" hipError_t swmi_launch_affine_sweep(const FillArgs *a, int32_t gap_open, uint32_t align_mode, const uint32_t *mat, uint32_t nn,
-                                               uint32_t r_min, uint32_t r_max, uint32_t long_reads, uint32_t band, hipStream_t st) {
+                                               uint32_t r_min, uint32_t r_max, uint32_t long_reads, uint32_t band, uint32_t xdrop, hipStream_t st) {
     if (a->n_pairs == 0) return hipSuccess;
     if (align_mode > 3u || (mat && (nn < 2u || nn > SWMI_MAT_NN_MAX)) || band > SWMI_AFF_BAND_MAX) return hipErrorInvalidValue;
+    if (xdrop > 0x7FFFFFFFu || (xdrop && long_reads && align_mode != AFF_EXTEND)) return hipErrorInvalidValue;
     // [narrow / wide / long][align_mode], and [align_mode] of the banded long sweeps: one typed table per signature (plain /
     // matrix, without / with the half-width), so that a launch is checked against its kernel's parameter list
     static void (*const plain[3][4])(FillArgs, int) = {
@@ -757,11 +811,21 @@ extern "C" hipError_t swmi_launch_affine_sweep(const FillArgs *a, int32_t gap_op
     static void (*const bmatrix[4])(FillArgs, int, const uint32_t *, uint32_t, uint32_t) = {
         sw_affine_sweep_band_matrix_kernel, sw_affine_sweep_band_fit_matrix_kernel, sw_affine_sweep_band_global_matrix_kernel,
         sw_affine_sweep_band_extend_matrix_kernel};
+    // the strip sweeps of an extend run under option "xdrop": the threshold is the last argument
+    static void (*const xplain)(FillArgs, int, uint32_t) = sw_affine_sweep_long_xdrop_kernel;
+    static void (*const xmatrix)(FillArgs, int, const uint32_t *, uint32_t, uint32_t) = sw_affine_sweep_long_xdrop_matrix_kernel;
+    static void (*const xbplain)(FillArgs, int, uint32_t, uint32_t) = sw_affine_sweep_band_xdrop_kernel;
+    static void (*const xbmatrix)(FillArgs, int, const uint32_t *, uint32_t, uint32_t, uint32_t) = sw_affine_sweep_band_xdrop_matrix_kernel;
     const dim3 grid((a->n_pairs + AFF_WAVES - 1) / AFF_WAVES), block(WAVE * AFF_WAVES);
     const bool banded = long_reads && band;                       // (the long shape only)
     // (a launch's own error is what hipGetLastError returns below)
+    const bool stops = long_reads && xdrop;                       // (the long shape only)
     const auto launch = [&](int shape) {
-        if (banded && mat) hipLaunchKernelGGL(bmatrix[align_mode], grid, block, 0, st, *a, (int)gap_open, mat, nn, band);
+        if (stops && banded && mat) hipLaunchKernelGGL(xbmatrix, grid, block, 0, st, *a, (int)gap_open, mat, nn, band, xdrop);
+        else if (stops && banded)   hipLaunchKernelGGL(xbplain, grid, block, 0, st, *a, (int)gap_open, band, xdrop);
+        else if (stops && mat)      hipLaunchKernelGGL(xmatrix, grid, block, 0, st, *a, (int)gap_open, mat, nn, xdrop);
+        else if (stops)             hipLaunchKernelGGL(xplain, grid, block, 0, st, *a, (int)gap_open, xdrop);
+        else if (banded && mat) hipLaunchKernelGGL(bmatrix[align_mode], grid, block, 0, st, *a, (int)gap_open, mat, nn, band);
         else if (banded)   hipLaunchKernelGGL(bplain[align_mode], grid, block, 0, st, *a, (int)gap_open, band);
         else if (mat)      hipLaunchKernelGGL(matrix[shape][align_mode], grid, block, 0, st, *a, (int)gap_open, mat, nn);
         else               hipLaunchKernelGGL(plain[shape][align_mode], grid, block, 0, st, *a, (int)gap_open);

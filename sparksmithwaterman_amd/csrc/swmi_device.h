@@ -53,6 +53,11 @@
 #define SWMI_F_CELL_OVF     0x2u   // more tied max cells than cell_cap: host re-runs the pair
 #define SWMI_F_ARENA_OVF    0x4u   // a record of this pair did not fit the arena: host grows it, re-runs
 #define SWMI_F_DONE         0x8u   // the pair was handled whole by sw_resident_pairs_kernel: the traceback kernels leave it alone
+// bits 8-31: the strips swept of a pair whose strip sweep option "xdrop" stopped (>= 1; a read has at most 2^22 strips), 0 for every
+// other pair.  Not a flag: no kernel tests it, the traceback kernels copy it to the host with the word, and the host turns it
+// into swmi_pair_rows_swept
+#define SWMI_F_STRIPS_SHIFT 8u
+#define SWMI_F_STRIPS_MASK  0xFFFFFF00u
 
 struct SeqDesc {
     uint32_t len;     // bases

@@ -118,6 +118,7 @@ struct __attribute__((visibility("hidden"))) RunModes {
     int long_reads = 0;                     // 1: the affine kernels take reads longer than 1024 bases, swept in strips (swmi.h)
     int band = 0;                           // > 0: the half-width of the band the strip sweeps of such reads keep to (swmi.h); the affine kernels
     int extend = 0;                         // 1: seed extension -- a global run whose maximum is taken over every cell (swmi.h); refused in the other modes
+    int xdrop = 0;                          // > 0: the drop-off threshold X of an extend run -- the strip sweep of a long read ends at a seam (swmi.h); refused in other runs
     // the MODE of the affine kernels and their launchers: the align_mode, or 3 (extend) for a global run with option "extend"
     uint32_t kernel_mode() const { return extend && align_mode == SWMI_ALIGN_GLOBAL ? 3u : (uint32_t)align_mode; }
     bool operator==(const RunModes &o) const { return memcmp(this, &o, sizeof(RunModes)) == 0; }
@@ -167,7 +168,7 @@ struct swmi_ctx {
     bool cell_cap_set = false;              // cell_cap given by the caller (otherwise small launches get longer lists)
     int32_t gap_open = 0;                   // affine gaps: a gap of length k costs gap_open + k * gap (0: linear)
     int affine = -1;                        // -1: the affine kernels (mode 3) when gap_open != 0; 1: always
-    RunModes modes;                         // options "align_mode", "long_reads", "band" and "extend"
+    RunModes modes;                         // options "align_mode", "long_reads", "band", "extend" and "xdrop"
     std::mutex mat_mu;                      // guards `matrix` (not ctx->mu: setting a matrix does not wait for a run)
     std::shared_ptr<const ScoreMatrix> matrix;   // swmi_set_score_matrix; a run with one takes the affine kernels
     // swmi_batch_run_async: one run in flight on the context's own host thread
@@ -202,6 +203,7 @@ struct PairRes {
     int32_t score = 0;
     uint32_t flags = 0;
     uint64_t n_cells = 0;
+    uint32_t strips = 0;    // option "xdrop": the strips swept of a pair that was stopped, else 0 (swmi_pair_rows_swept)
     uint64_t first = 0;     // index of the pair's first HostAln (ordered)
     uint64_t count = 0;     // alignment records present (0 when degenerate)
 };

@@ -141,6 +141,15 @@ extern "C" int swmi_pair_n_alignments(const swmi_batch *b, uint64_t pair, uint64
     return SWMI_OK;
 }
 
+// the read rows a pair's sweep covered: the read's length, or 1024 * (strips swept) for a pair that option "xdrop" stopped
+extern "C" int swmi_pair_rows_swept(const swmi_batch *b, uint64_t pair, uint32_t *rows) {
+    int rc = check_pair(b, pair);
+    if (rc) return rc;
+    const PairRes &pr = b->pairs[pair];
+    if (rows) *rows = pr.strips ? pr.strips * SWMI_AFF_MAX_READ : b->read_desc[pair % b->n_reads].len;
+    return SWMI_OK;
+}
+
 // every pair's score and alignment count at once (bulk form of the two accessors above)
 extern "C" int swmi_batch_pair_results(const swmi_batch *b, int32_t *scores, uint64_t *n_alignments, uint64_t n) {
     if (!b) return fail(SWMI_ERR_INVALID, "batch is null");

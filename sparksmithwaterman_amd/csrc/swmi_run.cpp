@@ -265,9 +265,11 @@ static int enqueue_launches(RunState &rs, Launch &L, const ResidentArgs &xa, con
             fl.n_pairs = (uint32_t)plan.aff_n_long; fl.pairs = fa.pairs + fs.n_pairs;
             const uint32_t *mat = b->opt.mat ? b->d_mat.as<uint32_t>() : nullptr;
             const uint32_t nn = b->opt.mat ? b->opt.mat->n + 1u : 0u;
-            HIP_TRY(swmi_launch_affine_sweep(&fs, b->gap_open, b->opt.modes.kernel_mode(), mat, nn, plan.aff_r_min, plan.aff_r_max, 0u, 0u, ctx->stream));
-            // (option "band": the banded strip sweep; the other pairs are swept in full)
-            HIP_TRY(swmi_launch_affine_sweep(&fl, b->gap_open, b->opt.modes.kernel_mode(), mat, nn, 0u, 0u, 1u, (uint32_t)b->opt.modes.band, ctx->stream));
+            HIP_TRY(swmi_launch_affine_sweep(&fs, b->gap_open, b->opt.modes.kernel_mode(), mat, nn, plan.aff_r_min, plan.aff_r_max, 0u, 0u, 0u, ctx->stream));
+            // (option "band": the banded strip sweep; the other pairs are swept in full.  Option "xdrop": the strip sweep that may
+            // end at a seam; the other pairs take the kernels they take without it)
+            HIP_TRY(swmi_launch_affine_sweep(&fl, b->gap_open, b->opt.modes.kernel_mode(), mat, nn, 0u, 0u, 1u, (uint32_t)b->opt.modes.band,
+                                             (uint32_t)b->opt.modes.xdrop, ctx->stream));
         }
         else HIP_TRY(swmi_launch_fill(&fa, ctx->stream, ext ? ctx->ev[0] : nullptr, ext ? ctx->ev[1] : nullptr));
         rs.launches++;
@@ -340,7 +342,7 @@ static void collect_scores(const swmi_batch *b, const std::vector<Work> &work, c
             o.score = 0; o.flags = SWMI_F_DEGENERATE;
             o.n_cells = (uint64_t)b->read_desc[pair % b->n_reads].len * b->ref_desc[pair / b->n_reads].len;
         }
-        o.flags &= SWMI_F_DEGENERATE;
+        o.flags &= SWMI_F_DEGENERATE | SWMI_F_STRIPS_MASK;      // (the strips swept under option "xdrop" stay)
     }
 }
 
@@ -572,6 +574,10 @@ static int check_run_params(const swmi_ctx *ctx, const swmi_batch *b, const swmi
     // option "extend" is global mode's sweep with another choice of maximum cells: there is no such sweep for local and fit
     if (md.extend && md.align_mode != SWMI_ALIGN_GLOBAL)
         return fail(SWMI_ERR_UNSUPPORTED, "extend = 1 needs align_mode global (2), got align_mode %d", md.align_mode);
+    // option "xdrop" is the drop-off rule of an extend run: no other run has a running maximum over every cell to fall below
+    if (md.xdrop > 0 && !(md.extend && md.align_mode == SWMI_ALIGN_GLOBAL))
+        return fail(SWMI_ERR_UNSUPPORTED, "xdrop = %d needs an extend run (align_mode global (2) with extend = 1), got align_mode %d, extend %d",
+                    md.xdrop, md.align_mode, md.extend);
     uint64_t max_m, max_n;
     if (affine) {
         // the bounds within which every sum of the affine recurrence fits int32 (DESIGN.md "Affine gaps")
@@ -774,6 +780,10 @@ static int rerun_overflowed(RunState &rs, const std::vector<Work> &work, const s
         rc2.wpos.resize(hi - lo);
         for (size_t k = 0; k < hi - lo; k++) rc2.wpos[k] = (uint32_t)ovf[lo + k];      // chunk-local id -> position in `work`
         for (size_t k = 0; k < hi - lo; k++) b->pairs[w2[lo + k].pair].n_cells = outs[k].n_cells;
+        // (option "xdrop": the same kernel on the same inputs stops at the same strip)
+        for (size_t k = 0; k < hi - lo; k++)
+            if (b->pairs[w2[lo + k].pair].strips != outs[k].flags >> SWMI_F_STRIPS_SHIFT)
+                return fail(SWMI_ERR_HIP, "the exact-size re-run swept another number of strips");
         for (size_t k = 0; k < hi - lo; k++)
             if (outs[k].flags & SWMI_F_CELL_OVF)
                 return fail(SWMI_ERR_HIP, "cell list overflowed again on the exact-size re-run");
@@ -864,6 +874,7 @@ static int batch_run(swmi_ctx *ctx, swmi_batch *b, const swmi_params *p, RunOpti
             pr.score = outs[k].score;
             pr.flags = (outs[k].flags & SWMI_F_DEGENERATE) ? SWMI_PAIR_DEGENERATE : 0u;
             pr.n_cells = outs[k].n_cells;
+            pr.strips = outs[k].flags >> SWMI_F_STRIPS_SHIFT;
             if (outs[k].flags & SWMI_F_CELL_OVF) ovf.push_back(lo + k);
         }
     }

@@ -178,6 +178,8 @@ def _rank_main(args):
             ctx.set_option("band", args.band)
         if args.extend:                                     # seed extension: the global sweep, ended at the best cell
             ctx.set_option("extend", 1)
+        if args.xdrop:                                      # ... with the drop-off rule for reads longer than 1024 bases
+            ctx.set_option("xdrop", args.xdrop)
         if args.matrix:                                     # substitution scores on this rank's context (NCBI text format)
             from . import matrix as _matrix
             ctx.set_score_matrix(_matrix.load(args.matrix))
@@ -206,6 +208,10 @@ def _parser():
             ns = super().parse_args(args, namespace)
             if ns.extend and ns.align_mode != "global":
                 self.error("--extend requires --align-mode global")
+            if ns.xdrop < 0 or ns.xdrop > _capi.XDROP_MAX:
+                self.error("--xdrop takes a threshold of 0 .. 2^31 - 1")
+            if ns.xdrop and not ns.extend:
+                self.error("--xdrop requires --extend")
             return ns
     ap = Parser(description=__doc__.split("\n")[0])
     ap.add_argument("--ref-dir", required=True)
@@ -235,6 +241,10 @@ def _parser():
                     help="with --align-mode global: seed extension (option extend) -- the alignment is anchored at the start of the read "
                          "and of the reference and ends at the cell with the best score, the tails left unaligned; for left extension "
                          "reverse both sequences")
+    ap.add_argument("--xdrop", type=int, default=0, metavar="X",
+                    help="with --extend and --long-reads: the drop-off rule (option xdrop) -- the sweep of a read longer than 1024 bases "
+                         "ends behind the first strip of 1024 rows whose last row lies more than X below the best score so far, and "
+                         "the best cell so far is the answer.  0 (the default): off")
     ap.add_argument("--tie", choices=("serial", "strict"), default="serial",
                     help="serial: SmithWaterman's aligner (NoDistribution, DistributeReference); strict: DistributedSW's (DistributeAlgorithm)")
     ap.add_argument("--stream-chunk-bytes", type=int, default=512 << 10, help="sequence bytes per streamed chunk")
