@@ -44,6 +44,8 @@ public class GpuSmithWaterman
 	static native void nativeSetExtend( long ctx , int extend ) ;
 	/** the drop-off threshold of seed extension for reads longer than 1024 bases, 0: off (include/swmi.h: option "xdrop") */
 	static native void nativeSetXdrop( long ctx , int xdrop ) ;
+	/** the band of a banded seed extension follows the alignment: 1 on, 0 off (include/swmi.h: option "band_adapt") */
+	static native void nativeSetBandAdapt( long ctx , int bandAdapt ) ;
 	/** substitution scores on the context: alphabet = n ISO-8859-1 symbols, scores = n * n, row = read base; null clears */
 	static native void nativeSetScoreMatrix( long ctx , byte[] alphabet , int[] scores ) ;
 	static native void nativeFreeBatch( long ctx , long batch ) ;
@@ -127,6 +129,17 @@ public class GpuSmithWaterman
 	 * executor thread.
 	 */
 	public static void setXdrop( int xdrop ) { XDROP = xdrop ; }
+
+	/** whether every context lets the band of a banded seed extension follow the alignment (applied next to band, before every batch) */
+	private static volatile boolean BAND_ADAPT = false ;
+
+	/**
+	 * With setBand( w ), setExtend( true ) and setLongReads( true ): the window of every strip of 1024 rows of a read longer than 1024
+	 * bases is placed around the column where the row above it scores best, so that w only has to cover the drift inside one
+	 * strip; false (the default): the band stays around the main diagonal.  With true and no banded seed extension the batch is
+	 * refused.  For every batch aligned from now on, on every executor thread.
+	 */
+	public static void setBandAdapt( boolean bandAdapt ) { BAND_ADAPT = bandAdapt ; }
 
 	/** the score matrix every context applies before its next batch: { alphabet , scores } (null: none), and its version */
 	private static volatile Object[] MATRIX = null ;
@@ -265,6 +278,7 @@ public class GpuSmithWaterman
 			nativeSetBand( ctx , BAND ) ;
 			nativeSetExtend( ctx , EXTEND ? 1 : 0 ) ;
 			nativeSetXdrop( ctx , XDROP ) ;
+			nativeSetBandAdapt( ctx , BAND_ADAPT ? 1 : 0 ) ;
 			applyScoreMatrix( nc ) ;
 			long batch = nativeAlignBatch( ctx , sc[0] , sc[1] , sc[2] , TIE_SERIAL , types , refBuf , refOff , n , readBuf , readOff , reads.size() ) ;
 			try

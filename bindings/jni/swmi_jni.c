@@ -84,6 +84,13 @@ JNIEXPORT void JNICALL Java_sw_GpuSmithWaterman_nativeSetXdrop(JNIEnv *env, jcla
     if (swmi_shim_set_xdrop((swmi_ctx *)(intptr_t)ctx, xdrop, err, sizeof err) != SWMI_OK) throw_msg(env, err);
 }
 
+/* the band of a banded extend run follows the alignment on this context from now on: 1 on, 0 off */
+JNIEXPORT void JNICALL Java_sw_GpuSmithWaterman_nativeSetBandAdapt(JNIEnv *env, jclass cls, jlong ctx, jint band_adapt) {
+    char err[640];
+    (void)cls;
+    if (swmi_shim_set_band_adapt((swmi_ctx *)(intptr_t)ctx, band_adapt, err, sizeof err) != SWMI_OK) throw_msg(env, err);
+}
+
 /* a substitution score matrix on this context from now on: alphabet = n ISO-8859-1 symbols, scores = int[n * n], row = read base;
  * alphabet == null clears it */
 JNIEXPORT void JNICALL Java_sw_GpuSmithWaterman_nativeSetScoreMatrix(JNIEnv *env, jclass cls, jlong ctx, jbyteArray alphabet,

@@ -71,6 +71,14 @@ int swmi_shim_set_xdrop(swmi_ctx *ctx, int32_t xdrop, char *err, size_t err_len)
     return SWMI_OK;
 }
 
+int swmi_shim_set_band_adapt(swmi_ctx *ctx, int32_t band_adapt, char *err, size_t err_len) {
+    int rc;
+    if (!ctx) return shim_fail(SWMI_ERR_INVALID, err, err_len, "nativeSetBandAdapt", "context handle is 0");
+    if ((rc = swmi_set_option(ctx, "band_adapt", band_adapt)) != SWMI_OK)
+        return shim_fail(rc, err, err_len, "nativeSetBandAdapt", swmi_last_error());
+    return SWMI_OK;
+}
+
 int swmi_shim_set_score_matrix(swmi_ctx *ctx, const signed char *alphabet, size_t n, const int32_t *scores, size_t n_scores,
                                char *err, size_t err_len) {
     int rc;

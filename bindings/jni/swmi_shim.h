@@ -48,6 +48,11 @@ int swmi_shim_set_extend(swmi_ctx *ctx, int32_t extend, char *err, size_t err_le
  * is not an extend run is then refused (SWMI_ERR_UNSUPPORTED).  0 (the default): off.  A negative value is SWMI_ERR_INVALID and
  * leaves the context as it was. */
 int swmi_shim_set_xdrop(swmi_ctx *ctx, int32_t xdrop, char *err, size_t err_len);
+/* nativeSetBandAdapt: 1 = from then on the band of a banded extend run follows the alignment (swmi_set_option "band_adapt"): the
+ * window of a strip of 1024 rows is placed around the column where the row above it scores best; a run that is not a banded
+ * extend run is then refused (SWMI_ERR_UNSUPPORTED).  0 (the default): off.  Any other value is SWMI_ERR_INVALID and leaves the
+ * context as it was. */
+int swmi_shim_set_band_adapt(swmi_ctx *ctx, int32_t band_adapt, char *err, size_t err_len);
 
 /* nativeSetScoreMatrix: a substitution score matrix on this context (swmi_set_score_matrix): `alphabet` = n symbols narrowed to
  * bytes (ISO-8859-1), `scores` = n * n entries, row = read base, column = reference base (n_scores must be n * n).  n = 0 clears

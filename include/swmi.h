@@ -211,6 +211,33 @@ void        swmi_default_params(swmi_params *p);
  *                a run that is not an extend run (align_mode global with extend = 1) is SWMI_ERR_UNSUPPORTED before anything is
  *                launched.  A run (async runs and stream slots included) takes the value set when it was asked for (DESIGN.md
  *                section 8h).
+ * band_adapt (default 0 = off and no change; 1 = on; any other value is SWMI_ERR_INVALID and leaves the context as it was): the band
+ *                of a banded extend run FOLLOWS THE ALIGNMENT from strip to strip (libgaba's adaptive band, at the granularity of the
+ *                sweep's strips), so that the half-width w = band only has to cover the drift inside one strip of 1024 rows, not the
+ *                drift over the whole read.  It is an option of a banded extend run -- band > 0, align_mode global, extend = 1: on any
+ *                other run (the linear pipeline included) band_adapt = 1 is SWMI_ERR_UNSUPPORTED before anything is launched.  Like band
+ *                it acts on pairs whose read has MORE than 1024 bases (so long_reads = 1 is needed for there to be any); a shorter
+ *                read is computed in full by the kernels it takes today.  For a read of m > 1024 bases, NS = ceil(m / 1024) strips,
+ *                each with a centre, starting from c(-1) = 0:
+ *                  c_lo(s) = max(1, c(s - 1) + 1 - w),  c_hi(s) = min(n, c(s - 1) + 1024 + w)     (strip 0: the static window)
+ *                  p(s) = the smallest column j in c_lo(s) .. c_hi(s) at which H(1024 (s + 1), j) is largest,  s <= NS - 2
+ *                  c(s) = max(c(s - 1), p(s))                                         (the centre never moves left)
+ *                Both window ends are non-decreasing in s, a window has at most 1024 + 2 w columns, p(s) lies in the windows of
+ *                strips s and s + 1, and no window is empty (c(s) <= n): band's refusal of a strip with an empty window does not
+ *                apply, and a reference shorter than the read is taken, its last windows ending at n.  Everything else is band's
+ *                contract for an extend run with these windows: a cell outside its strip's window does not exist and reads as
+ *                -infinity (also column c_lo - 1 on the row above a strip whose window did not move, c_lo(s + 1) = c_lo(s) > 1); the
+ *                score is the maximum over the existing cells; tied cells come in extend's order; the walk is the global walk;
+ *                begin = 1.  cell_cap, the exact-size re-run (it places the same windows), scores_only, device_strings and zero_copy
+ *                apply as to any extend run.  With xdrop > 0 the drop-off test runs on these windows (seam(s) over c_lo(s) .. c_hi(s))
+ *                and comes first: behind a stop no further window is placed.  Bounds, for the batch's longest read (M = 1024 NS) and
+ *                longest reference, refused with SWMI_ERR_UNSUPPORTED before anything is launched:  M * S <= 2^29  as under band, and
+ *                (2 NS + 1) * |gap_open| + (M + n) * |gap| <= 2^30  in place of band's 3 * |gap_open| + (M + n) * |gap| <= 2^30 (an
+ *                existing cell is reached from the boundary by gap moves with two gap openings per strip, not by a diagonal); a
+ *                pair's workspace -- NS fields of ceil((min(n, 1024 + 2 w) + 63) / 8) blocks of 4 KiB, whatever the windows turn out to
+ *                be, and a table of NS window centres -- must fit max_workspace_bytes.  swmi_pair_band_window tells the windows a
+ *                pair's sweep used.  A run (async runs and stream slots included) takes the value set when it was asked for
+ *                (DESIGN.md section 8i).
  * Further knobs: spin_us (how long a run polls its stream before it blocks, default 2000); col_chunks (0 automatic,
  * 1 never, N > 1 force up to N column chunks per pair: a launch of few pairs with long references is swept by several
  * wavefronts per pair -- a read of more than 256 rows by several strip pipelines); debug_strip_spins / debug_reverse_strips (tests of the strip pipeline's give-up path);
@@ -275,6 +302,12 @@ int      swmi_pair_n_alignments(const swmi_batch *b, uint64_t pair, uint64_t *n,
  * too), 1024 (s* + 1) for a pair that option "xdrop" stopped behind strip s*: rows < m is the sign of a stop.  Works under
  * scores_only. */
 int      swmi_pair_rows_swept(const swmi_batch *b, uint64_t pair, uint32_t *rows);
+/* The window of reference columns *c_lo .. *c_hi (1-based, inclusive; either pointer may be NULL) that the pair's sweep used for
+ * strip `strip` of the read (rows 1024 strip + 1 .. 1024 (strip + 1)), after any run: (1, n) for a read of at most 1024 bases or a run
+ * without a band; max(1, 1024 strip + 1 - w) .. min(n, 1024 (strip + 1) + w) under option "band"; the window the sweep placed under
+ * option "band_adapt".  Works under scores_only.  A strip >= ceil(m / 1024) (>= 1 for m <= 1024), or one that option "xdrop" did not
+ * sweep (1024 strip >= swmi_pair_rows_swept), is SWMI_ERR_RANGE. */
+int      swmi_pair_band_window(const swmi_batch *b, uint64_t pair, uint32_t strip, uint32_t *c_lo, uint32_t *c_hi);
 /* all pairs at once: scores[n] and/or n_alignments[n] (either may be NULL), n = swmi_batch_n_pairs */
 int      swmi_batch_pair_results(const swmi_batch *b, int32_t *scores, uint64_t *n_alignments, uint64_t n);
 /* k-th alignment of the pair in OptAlignments order.  *ref_aln / *read_aln point to

@@ -72,6 +72,7 @@ SYMBOLS = [
                                       C.POINTER(C.c_int32), C.POINTER(C.c_char_p), C.POINTER(C.c_char_p),
                                       C.POINTER(C.c_uint32)]),
     ("swmi_pair_rows_swept", C.c_int, [_P, C.c_uint64, C.POINTER(C.c_uint32)]),
+    ("swmi_pair_band_window", C.c_int, [_P, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     ("swmi_batch_pair_results", C.c_int, [_P, C.POINTER(C.c_int32), _u64p, C.c_uint64]),
     ("swmi_batch_materialise_all", C.c_int, [_P, _u64p, _u64p]),
     ("swmi_ref_total", C.c_int, [_P, C.c_uint32, C.POINTER(C.c_int32)]),

@@ -145,6 +145,14 @@ class Batch:
         check(self._lib.swmi_pair_rows_swept(self._h, pair, C.byref(v)))
         return v.value
 
+    def band_window(self, pair, strip):
+        """(c_lo, c_hi): the reference columns the pair's sweep used for strip `strip` (rows 1024 * strip + 1 ..) of the read -- (1, n)
+        without a band or for a read of at most 1024 bases, the staircase's window under option "band", the window the sweep
+        placed under option "band_adapt"; SwmiError (SWMI_ERR_RANGE) for a strip the read does not have or "xdrop" did not sweep"""
+        lo, hi = C.c_uint32(), C.c_uint32()
+        check(self._lib.swmi_pair_band_window(self._h, pair, strip, C.byref(lo), C.byref(hi)))
+        return lo.value, hi.value
+
     def alignment(self, pair, k, with_cell=False):
         b, ei, ej = C.c_int32(), C.c_int32(), C.c_int32()
         r, q, ln = C.c_char_p(), C.c_char_p(), C.c_uint32()

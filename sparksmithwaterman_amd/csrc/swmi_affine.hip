@@ -67,8 +67,12 @@
 //   1: between two strips the wave takes the maximum of H over the seam row and ends the pair when the running maximum lies more
 //   than the threshold above it; the PairOut carries the strips swept.  The threshold is one more scalar kernel argument.
 //
-// How the 45 kernels are made: the 36 sweeps are aff_sweep_entry<RLO, RHI, MATRIX, MODE, LONG, BAND, XDROP> over one block function
-//   (aff_block8); the 9 tracebacks are aff_traceback<MODE, LONG, BAND>, where !LONG is the walk with one strip and !BAND the
+// sw_affine_sweep_band_adapt[_xdrop][_matrix]_kernel, sw_affine_traceback_band_adapt_global_kernel: the banded strip kernels of an
+//   extend run under option "band_adapt" (DESIGN.md 8i), ADAPT = 1: the window of a strip is placed around the column of the seam
+//   row's maximum instead of around j = i; the sweep leaves the centres in a table behind the pair's fields, the walk reads them.
+//
+// How the 50 kernels are made: the 40 sweeps are aff_sweep_entry<RLO, RHI, MATRIX, MODE, LONG, BAND, XDROP, ADAPT> over one block function
+//   (aff_block8); the 10 tracebacks are aff_traceback<MODE, LONG, BAND, ADAPT>, where !LONG is the walk with one strip and !BAND the
 //   walk whose windows are the whole reference.  One macro defines the sweeps, one the tracebacks; the launchers pick a kernel
 //   from typed tables.  The per-pair sweep is two thin bodies, aff_sweep_pair and aff_sweep_long_pair<.., BAND> (the one strip
 //   loop, banded or not), over shared pieces: vrows and the cell list as functions of values, the row load, the block store
@@ -374,9 +378,24 @@ __device__ __forceinline__ void aff_sweep_pair(const FillArgs &A, const int o, c
 //   when the running maximum S.thr lies more than xd above it: the strips from sx on are not swept, the cell list holds the
 //   cells of rows <= 1024 sx, and the PairOut carries sx, the strips swept, above its flag bits.  The comparison is made once per
 //   strip on wave-uniform values, in 64 bits.  Nothing enters the block loop.
-template <bool STRICT, bool MATRIX, int MODE, bool BAND, bool XDROP = false>
+// ADAPT (option "band_adapt", with BAND and AFF_EXTEND): the window follows a centre, cen = c(sx - 1), 0 for strip
+//   0: clo, chi = swmi_aff_adapt_lo / _hi (cen).  At the top of strip sx >= 1, behind the same fence, ONE pass over the seam row
+//   inside the window of strip sx - 1 finds the maximum of H there and p, the smallest column that holds it: a lane keeps its
+//   first strictly larger value (its columns ascend), the wave takes the maximum and then the smallest column among the lanes
+//   that hold it, both through wave_max_i32, so both are wave-uniform.  XDROP's test runs on the same maximum and comes first: a
+//   pair it stops places no further window.  Then cen = max(cen, p).  What differs from the static staircase:
+//   - the windows are monotone but clo may STAND STILL: clo(sx) = clo(sx - 1) > 1.  Column clo - 1 of the seam row was then not
+//     written by the strip above (it lies left of ITS window too), and nh_prev is OUT, not a seam load.  Otherwise clo(sx) - 1 >=
+//     clo(sx - 1) as before.  The strip's own column clo - 1 (S.h, S.e) is OUT whenever clo > 1, as under BAND
+//   - seam_end is chi(sx - 1) - (clo - 1): lane 0's loads stay inside clo(sx - 1) .. chi(sx - 1), since clo(sx) >= clo(sx - 1)
+//   - the in-place argument above is relative to the window's first column and holds as it stands; the pass reads the row
+//     before the strip stores anything
+//   - every strip's field has the fixed stride swmi_aff_adapt_strip_words: the window is not known before the strip above ends
+//   - lane 0 leaves cen in the pair's window table behind the fields (a vector store), for the traceback and the host
+template <bool STRICT, bool MATRIX, int MODE, bool BAND, bool XDROP = false, bool ADAPT = false>
 __device__ __forceinline__ void aff_sweep_long_pair(const FillArgs &A, const int o, const PairDesc pd, const uint32_t lane, const uint32_t nn,
                                                     const uint32_t wb, const uint32_t xd = 0u) {
+    static_assert(!ADAPT || (BAND && MODE == AFF_EXTEND), "band_adapt is an option of the banded strip sweeps of an extend run");
     constexpr int R = SWMI_AFF_RMAX;
     constexpr int OUT = BAND && MODE != AFF_LOCAL ? SWMI_AFF_BAND_NEG : 0;
     const SeqDesc rd = A.refs[pd.ref_id];
@@ -395,6 +414,9 @@ __device__ __forceinline__ void aff_sweep_long_pair(const FillArgs &A, const int
     uint32_t *__restrict__ dir = A.dir + pd.dir_off;
     uint64_t inband = 0ull;                                      // BAND: in-band cells with i <= m (the degenerate count)
     uint32_t stopped = 0u;                                       // XDROP: the strips swept of a pair that was stopped, else 0
+    uint32_t cen = 0u, plo = 1u, phi = 0u;                       // ADAPT: the centre c(sx - 1); the window of the strip above
+    const uint64_t astride = ADAPT ? swmi_aff_adapt_strip_words(n, wb) : 0ull;       // ADAPT: dwords of every strip's field
+    uint32_t *const wtab = ADAPT ? A.dir + pd.dir_off + (uint64_t)NS * astride : nullptr;   // ADAPT: the pair's window table
 
     AffState<R> S;
     S.thr = MODE == AFF_LOCAL ? 1 : INT32_MIN; S.cnt = 0;       // (wave-uniform: they live on across the strips)
@@ -402,7 +424,40 @@ __device__ __forceinline__ void aff_sweep_long_pair(const FillArgs &A, const int
         const uint32_t row0 = sx * SWMI_AFF_MAX_READ + lane * R;             // global index of the lane's first row, less 1
         const uint32_t vrows = aff_vrows<R, MODE>(m, row0);               // (row m is in the last strip)
         uint32_t clo = 1u, nw = n, seam_end = n;                 // the window's first column and length; the window columns the strip above wrote
-        if constexpr (BAND) {
+        if constexpr (ADAPT) {
+            if (sx) {
+                // the strip above has written its window of the seam row (the fence of the static sweeps, taken here: the window
+                // of this strip hangs on what the pass loads)
+                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent");
+                // (four loads in flight per lane, as in the XDROP pass; the seam row is indexed by j - 1)
+                int bv = INT32_MIN;
+                uint32_t bc = 0u;
+                uint32_t c = plo - 1u + lane;
+                for (; c + 3u * WAVE < phi; c += 4u * WAVE) {
+                    const int s0 = seam[c].x, s1 = seam[c + WAVE].x, s2 = seam[c + 2u * WAVE].x, s3 = seam[c + 3u * WAVE].x;
+                    if (s0 > bv) { bv = s0; bc = c; }
+                    if (s1 > bv) { bv = s1; bc = c + WAVE; }
+                    if (s2 > bv) { bv = s2; bc = c + 2u * WAVE; }
+                    if (s3 > bv) { bv = s3; bc = c + 3u * WAVE; }
+                }
+                for (; c < phi; c += WAVE) {
+                    const int s0 = seam[c].x;
+                    if (s0 > bv) { bv = s0; bc = c; }
+                }
+                const int smax = wave_max_i32(bv);               // seam(sx - 1): a real H, above INT32_MIN
+                if constexpr (XDROP) {
+                    if ((int64_t)S.thr - (int64_t)smax > (int64_t)xd) { stopped = sx; break; }
+                }
+                // p(sx - 1): the smallest column among the lanes that hold the maximum (bc < 2^31: its negative orders them)
+                const uint32_t p = (uint32_t)(-wave_max_i32(bv == smax ? -(int)bc : INT32_MIN)) + 1u;
+                if (p > cen) cen = p;
+            }
+            if (lane == 0) wtab[sx] = cen;
+            clo = swmi_aff_adapt_lo(cen, wb);
+            nw = swmi_aff_adapt_hi(cen, n, wb) - clo + 1u;
+            W = swmi_aff_strip_blocks(nw);
+            seam_end = sx ? phi - (clo - 1u) : 0u;
+        } else if constexpr (BAND) {
             clo = swmi_aff_band_lo(sx, wb);
             nw = swmi_aff_band_hi(sx, n, wb) - clo + 1u;
             W = swmi_aff_strip_blocks(nw);
@@ -426,9 +481,10 @@ __device__ __forceinline__ void aff_sweep_long_pair(const FillArgs &A, const int
         }
         Z.wlane = sx + 1u < NS ? 63u : 0xFFFFFFFFu;
         if constexpr (!BAND) dir = A.dir + pd.dir_off + (uint64_t)sx * swmi_aff_strip_words(n);
+        if constexpr (ADAPT) dir = A.dir + pd.dir_off + (uint64_t)sx * astride;
         // the strip above has written its window of the seam row: its stores are in memory before this strip loads any of it
-        if (sx) __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent");
-        if constexpr (XDROP) {
+        if constexpr (!ADAPT) { if (sx) __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent"); }
+        if constexpr (XDROP && !ADAPT) {
             if (sx) {
                 // seam(sx - 1): the maximum of H(1024 sx, j) over the window of strip sx - 1 (the seam row is indexed by j - 1)
                 const uint32_t plo = BAND ? swmi_aff_band_lo(sx - 1u, wb) : 1u, phi = BAND ? swmi_aff_band_hi(sx - 1u, n, wb) : n;
@@ -445,7 +501,7 @@ __device__ __forceinline__ void aff_sweep_long_pair(const FillArgs &A, const int
             }
         }
         if constexpr (BAND) {
-            if (clo > 1u) S.nh_prev = seam[clo - 2u].x;                            // (a vector load, behind the fence)
+            if (clo > 1u) S.nh_prev = !ADAPT || clo > plo ? seam[clo - 2u].x : OUT;   // (a vector load, behind the fence; ADAPT: a window that stood still)
             else S.nh_prev = MODE != AFF_LOCAL && sx ? o + (int)(sx * SWMI_AFF_MAX_READ) * A.gap : 0;
         }
         const uint32_t boff = clo - 1u, bsh = boff & 3u;         // (BAND) the window's first byte of the image
@@ -475,7 +531,8 @@ __device__ __forceinline__ void aff_sweep_long_pair(const FillArgs &A, const int
             aff_block8<R, STRICT, MATRIX, MODE, true, BAND>(S, rw, t0, lane, nw, row0, vrows, o, A.gap, A.match, A.mismatch, cells, ccap, Z);
             AFF_STORE_BLOCK
         }
-        if constexpr (BAND) dir += (uint64_t)W * R * WAVE;
+        if constexpr (BAND && !ADAPT) dir += (uint64_t)W * R * WAVE;
+        if constexpr (ADAPT) { plo = clo; phi = clo + nw - 1u; }
     }
     AFF_PAIR_OUT(BAND ? inband : (uint64_t)m * n, XDROP ? stopped << SWMI_F_STRIPS_SHIFT : 0u)
 }
@@ -497,10 +554,12 @@ __device__ __forceinline__ void aff_sweep_dispatch(const FillArgs &A, const int 
 // mat / nn (MATRIX only): the score matrix image (swmi_aff_mat_words) and its side n + 1
 // LONG: the strip sweep of reads longer than 1024 bases (RLO, RHI unused); BAND (with LONG): inside a band of half-width wb
 // XDROP (with LONG and AFF_EXTEND): the strip sweep under option "xdrop", threshold xd
-template <int RLO, int RHI, bool MATRIX, int MODE = AFF_LOCAL, bool LONG = false, bool BAND = false, bool XDROP = false>
+// ADAPT (with LONG, BAND and AFF_EXTEND): the banded strip sweep under option "band_adapt"
+template <int RLO, int RHI, bool MATRIX, int MODE = AFF_LOCAL, bool LONG = false, bool BAND = false, bool XDROP = false, bool ADAPT = false>
 __device__ __forceinline__ void aff_sweep_entry(const FillArgs &A, const int o, const uint32_t *__restrict__ mat, const uint32_t nn,
                                                 const uint32_t wb = 0u, const uint32_t xd = 0u) {
     static_assert(!XDROP || (LONG && MODE == AFF_EXTEND), "xdrop is an option of the strip sweeps of an extend run");
+    static_assert(!ADAPT || (LONG && BAND && MODE == AFF_EXTEND), "band_adapt is an option of the banded strip sweeps of an extend run");
     if (blockIdx.x == 0 && threadIdx.x == 0) A.hdr->reserved = 0ull;      // the traceback's bump allocator
     if (MATRIX) {                                                          // (before any wavefront leaves)
         for (uint32_t x = threadIdx.x; x < 256u; x += WAVE * AFF_WAVES) aff_mkey[x] = mat[x];
@@ -517,8 +576,8 @@ __device__ __forceinline__ void aff_sweep_entry(const FillArgs &A, const int o, 
     const PairDesc pd = A.pairs[pair];
     if constexpr (LONG) {
         if (uni(A.reads[pd.read_id].len) <= SWMI_AFF_MAX_READ) return;
-        if (A.strict) aff_sweep_long_pair<true, MATRIX, MODE, BAND, XDROP>(A, o, pd, lane, nn, wb, xd);
-        else          aff_sweep_long_pair<false, MATRIX, MODE, BAND, XDROP>(A, o, pd, lane, nn, wb, xd);
+        if (A.strict) aff_sweep_long_pair<true, MATRIX, MODE, BAND, XDROP, ADAPT>(A, o, pd, lane, nn, wb, xd);
+        else          aff_sweep_long_pair<false, MATRIX, MODE, BAND, XDROP, ADAPT>(A, o, pd, lane, nn, wb, xd);
         return;
     }
     const uint32_t R = uni(swmi_aff_rows_per_lane(A.reads[pd.read_id].len));
@@ -529,10 +588,11 @@ __device__ __forceinline__ void aff_sweep_entry(const FillArgs &A, const int o, 
 
 }  // namespace
 
-// The 36 sweep kernels: local, fit and global (option "align_mode") and extend (option "extend"), each plain and with a score matrix (MATRIX = 0 / 1), each
+// The 40 sweep kernels: local, fit and global (option "align_mode") and extend (option "extend"), each plain and with a score matrix (MATRIX = 0 / 1), each
 // narrow (R = 1..4), wide (R = 5..16), long (option "long_reads": RLO, RHI unused) and banded long (option "band", BAND = 1:
 // the half-width is one more scalar argument).  The long and banded long extend sweeps come once more under option "xdrop" (XDROP = 1:
-// the threshold is one more scalar argument, the last).  MATRIX, BAND and XDROP make the signatures.
+// the threshold is one more scalar argument, the last), and the banded ones of those once more under option "band_adapt" (ADAPT = 1: no
+// further argument).  MATRIX, BAND and XDROP make the signatures.
 #define AFF_SWEEP_PARAMS_000 const FillArgs A, const int gap_open
 #define AFF_SWEEP_PARAMS_100 const FillArgs A, const int gap_open, const uint32_t *mat, const uint32_t nn
 #define AFF_SWEEP_PARAMS_010 const FillArgs A, const int gap_open, const uint32_t band
@@ -549,46 +609,50 @@ __device__ __forceinline__ void aff_sweep_entry(const FillArgs &A, const int o, 
 #define AFF_SWEEP_ARGS_101 A, gap_open, mat, nn, 0u, xdrop
 #define AFF_SWEEP_ARGS_011 A, gap_open, nullptr, 0u, band, xdrop
 #define AFF_SWEEP_ARGS_111 A, gap_open, mat, nn, band, xdrop
-#define AFF_SWEEP_KERNEL(name, RLO, RHI, MATRIX, MODE, LONG, BAND, XDROP)                                                 \
+#define AFF_SWEEP_KERNEL(name, RLO, RHI, MATRIX, MODE, LONG, BAND, XDROP, ADAPT)                                          \
     extern "C" __global__ void __launch_bounds__(WAVE * AFF_WAVES) name(AFF_SWEEP_PARAMS_##MATRIX##BAND##XDROP) {        \
-        aff_sweep_entry<RLO, RHI, MATRIX != 0, MODE, LONG, BAND != 0, XDROP != 0>(AFF_SWEEP_ARGS_##MATRIX##BAND##XDROP); \
+        aff_sweep_entry<RLO, RHI, MATRIX != 0, MODE, LONG, BAND != 0, XDROP != 0, ADAPT != 0>(AFF_SWEEP_ARGS_##MATRIX##BAND##XDROP); \
     }
-AFF_SWEEP_KERNEL(sw_affine_sweep_kernel, 1, 4, 0, AFF_LOCAL, false, 0, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_wide_kernel, 5, SWMI_AFF_RMAX, 0, AFF_LOCAL, false, 0, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_long_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, AFF_LOCAL, true, 0, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_matrix_kernel, 1, 4, 1, AFF_LOCAL, false, 0, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_matrix_wide_kernel, 5, SWMI_AFF_RMAX, 1, AFF_LOCAL, false, 0, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_long_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, AFF_LOCAL, true, 0, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_fit_kernel, 1, 4, 0, AFF_FIT, false, 0, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_fit_wide_kernel, 5, SWMI_AFF_RMAX, 0, AFF_FIT, false, 0, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_long_fit_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, AFF_FIT, true, 0, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_fit_matrix_kernel, 1, 4, 1, AFF_FIT, false, 0, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_fit_matrix_wide_kernel, 5, SWMI_AFF_RMAX, 1, AFF_FIT, false, 0, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_long_fit_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, AFF_FIT, true, 0, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_global_kernel, 1, 4, 0, AFF_GLOBAL, false, 0, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_global_wide_kernel, 5, SWMI_AFF_RMAX, 0, AFF_GLOBAL, false, 0, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_long_global_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, AFF_GLOBAL, true, 0, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_global_matrix_kernel, 1, 4, 1, AFF_GLOBAL, false, 0, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_global_matrix_wide_kernel, 5, SWMI_AFF_RMAX, 1, AFF_GLOBAL, false, 0, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_long_global_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, AFF_GLOBAL, true, 0, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_band_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, AFF_LOCAL, true, 1, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_band_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, AFF_LOCAL, true, 1, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_band_fit_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, AFF_FIT, true, 1, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_band_fit_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, AFF_FIT, true, 1, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_band_global_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, AFF_GLOBAL, true, 1, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_band_global_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, AFF_GLOBAL, true, 1, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_extend_kernel, 1, 4, 0, AFF_EXTEND, false, 0, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_extend_wide_kernel, 5, SWMI_AFF_RMAX, 0, AFF_EXTEND, false, 0, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_long_extend_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, AFF_EXTEND, true, 0, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_extend_matrix_kernel, 1, 4, 1, AFF_EXTEND, false, 0, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_extend_matrix_wide_kernel, 5, SWMI_AFF_RMAX, 1, AFF_EXTEND, false, 0, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_long_extend_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, AFF_EXTEND, true, 0, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_band_extend_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, AFF_EXTEND, true, 1, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_band_extend_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, AFF_EXTEND, true, 1, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_long_xdrop_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, AFF_EXTEND, true, 0, 1)
-AFF_SWEEP_KERNEL(sw_affine_sweep_long_xdrop_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, AFF_EXTEND, true, 0, 1)
-AFF_SWEEP_KERNEL(sw_affine_sweep_band_xdrop_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, AFF_EXTEND, true, 1, 1)
-AFF_SWEEP_KERNEL(sw_affine_sweep_band_xdrop_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, AFF_EXTEND, true, 1, 1)
+AFF_SWEEP_KERNEL(sw_affine_sweep_kernel, 1, 4, 0, AFF_LOCAL, false, 0, 0, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_wide_kernel, 5, SWMI_AFF_RMAX, 0, AFF_LOCAL, false, 0, 0, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_long_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, AFF_LOCAL, true, 0, 0, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_matrix_kernel, 1, 4, 1, AFF_LOCAL, false, 0, 0, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_matrix_wide_kernel, 5, SWMI_AFF_RMAX, 1, AFF_LOCAL, false, 0, 0, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_long_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, AFF_LOCAL, true, 0, 0, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_fit_kernel, 1, 4, 0, AFF_FIT, false, 0, 0, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_fit_wide_kernel, 5, SWMI_AFF_RMAX, 0, AFF_FIT, false, 0, 0, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_long_fit_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, AFF_FIT, true, 0, 0, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_fit_matrix_kernel, 1, 4, 1, AFF_FIT, false, 0, 0, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_fit_matrix_wide_kernel, 5, SWMI_AFF_RMAX, 1, AFF_FIT, false, 0, 0, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_long_fit_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, AFF_FIT, true, 0, 0, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_global_kernel, 1, 4, 0, AFF_GLOBAL, false, 0, 0, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_global_wide_kernel, 5, SWMI_AFF_RMAX, 0, AFF_GLOBAL, false, 0, 0, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_long_global_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, AFF_GLOBAL, true, 0, 0, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_global_matrix_kernel, 1, 4, 1, AFF_GLOBAL, false, 0, 0, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_global_matrix_wide_kernel, 5, SWMI_AFF_RMAX, 1, AFF_GLOBAL, false, 0, 0, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_long_global_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, AFF_GLOBAL, true, 0, 0, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_band_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, AFF_LOCAL, true, 1, 0, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_band_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, AFF_LOCAL, true, 1, 0, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_band_fit_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, AFF_FIT, true, 1, 0, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_band_fit_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, AFF_FIT, true, 1, 0, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_band_global_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, AFF_GLOBAL, true, 1, 0, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_band_global_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, AFF_GLOBAL, true, 1, 0, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_extend_kernel, 1, 4, 0, AFF_EXTEND, false, 0, 0, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_extend_wide_kernel, 5, SWMI_AFF_RMAX, 0, AFF_EXTEND, false, 0, 0, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_long_extend_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, AFF_EXTEND, true, 0, 0, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_extend_matrix_kernel, 1, 4, 1, AFF_EXTEND, false, 0, 0, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_extend_matrix_wide_kernel, 5, SWMI_AFF_RMAX, 1, AFF_EXTEND, false, 0, 0, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_long_extend_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, AFF_EXTEND, true, 0, 0, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_band_extend_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, AFF_EXTEND, true, 1, 0, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_band_extend_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, AFF_EXTEND, true, 1, 0, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_long_xdrop_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, AFF_EXTEND, true, 0, 1, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_long_xdrop_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, AFF_EXTEND, true, 0, 1, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_band_xdrop_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, AFF_EXTEND, true, 1, 1, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_band_xdrop_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, AFF_EXTEND, true, 1, 1, 0)
+AFF_SWEEP_KERNEL(sw_affine_sweep_band_adapt_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, AFF_EXTEND, true, 1, 0, 1)
+AFF_SWEEP_KERNEL(sw_affine_sweep_band_adapt_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, AFF_EXTEND, true, 1, 0, 1)
+AFF_SWEEP_KERNEL(sw_affine_sweep_band_adapt_xdrop_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, AFF_EXTEND, true, 1, 1, 1)
+AFF_SWEEP_KERNEL(sw_affine_sweep_band_adapt_xdrop_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, AFF_EXTEND, true, 1, 1, 1)
 #undef AFF_SWEEP_KERNEL
 #undef AFF_SWEEP_PARAMS_000
 #undef AFF_SWEEP_PARAMS_001
@@ -620,9 +684,15 @@ AFF_SWEEP_KERNEL(sw_affine_sweep_band_xdrop_matrix_kernel, SWMI_AFF_RMAX, SWMI_A
 //   reached a cell with H = 0 and ends there, as at column 0, without touching the field -- that cell has no code.  (Left of the
 //   window the step index would wrap in lane 0 and name an inactive step of the row elsewhere; right of it it may lie past the
 //   strip's blocks.)  Fit and global never get there: an outside value loses every max strictly.
+// ADAPT (with BAND, the walk of an extend run under option "band_adapt"): clo, chi and W of strip sx come from the
+//   centre the sweep left in the pair's window table (an earlier launch on the same stream wrote it), read at the start cell and
+//   on every step up across a seam; the strip's field lies at the fixed stride swmi_aff_adapt_strip_words.  A centre is clamped to
+//   n, so that a table entry the sweep never wrote (a corrupted list that names a strip behind an xdrop stop) still gives a window
+//   of at most the stride's blocks and the guard w < W keeps the walk inside the pair's field.
 namespace {
-template <int MODE, bool LONG, bool BAND = false>
+template <int MODE, bool LONG, bool BAND = false, bool ADAPT = false>
 __device__ __forceinline__ void aff_traceback(const TraceArgs A, const uint32_t tile_words, const uint32_t ops_words, const uint32_t wb = 0u) {
+    static_assert(!ADAPT || (LONG && BAND && MODE == AFF_GLOBAL), "band_adapt: the banded walk of an extend run (global mode's)");
     extern __shared__ uint32_t lds[];
     const uint32_t lane = threadIdx.x;
     const uint32_t slot = blockIdx.y, nslots = gridDim.y;
@@ -652,6 +722,18 @@ __device__ __forceinline__ void aff_traceback(const TraceArgs A, const uint32_t 
     uint32_t wlo = 0xFFFFFFFFu, whi = 0u;                         // blocks [wlo, whi) are in the tile
     uint32_t tsx = LONG ? 0xFFFFFFFFu : 0u;                       // ... of this strip
     const uint32_t NS = LONG ? uni(swmi_aff_strips(m)) : 1u;
+    const uint64_t astride = ADAPT ? swmi_aff_adapt_strip_words(n, wb) : 0ull;     // ADAPT: dwords of every strip's field
+    const uint32_t *const wtab = ADAPT ? dir + (uint64_t)NS * astride : nullptr;    // ADAPT: the pair's window table
+// AFF_ADAPT_WINDOW: clo, chi and W of strip sx from the table (text, as the sweeps' shared pieces are: the static walks stay as they
+// were).  Only for sx < NS: the step up from row 1 leaves strip 0 for "strip" 0xFFFFFFFF -- the walk ends there, at row 0, and the
+// closed forms of the static band are harmless for it, but the table has no such entry to load
+#define AFF_ADAPT_WINDOW                                                                                                       \
+    {                                                                                                                          \
+        if (sx < NS) {                                                                                                         \
+            const uint32_t tc = uni(wtab[sx]), cen = tc < n ? tc : n;                                                          \
+            clo = swmi_aff_adapt_lo(cen, wb); chi = swmi_aff_adapt_hi(cen, n, wb); W = swmi_aff_strip_blocks(chi - clo + 1u);  \
+        }                                                                                                                      \
+    }
 
     for (uint32_t c = slot; c < ncell; c += nslots) {
         const uint32_t ci = uni(cells[c].x), cj = uni(cells[c].y);
@@ -661,6 +743,7 @@ __device__ __forceinline__ void aff_traceback(const TraceArgs A, const uint32_t 
         if constexpr (LONG) { sx = l / WAVE; l -= sx * WAVE; }
         if constexpr (BAND) {
             if (sx >= NS) sx = NS;                                // (a corrupted list: refused below, and no window is computed for it)
+            else if constexpr (ADAPT) AFF_ADAPT_WINDOW
             else { clo = swmi_aff_band_lo(sx, wb); chi = swmi_aff_band_hi(sx, n, wb); W = swmi_aff_band_blocks(sx, n, wb); }
         }
         uint32_t st = 0u;                                         // 0: H, else the state entered (AFF_DIAG / AFF_INS / AFF_DEL)
@@ -687,7 +770,7 @@ __device__ __forceinline__ void aff_traceback(const TraceArgs A, const uint32_t 
                 wlo = w + 1u >= NB ? w + 1u - NB : 0u;
                 whi = w + 1u;
                 if constexpr (LONG) tsx = sx;
-                const uint32_t *__restrict__ src = dir + (BAND ? swmi_aff_band_strip_off(sx, n, wb) : LONG ? (uint64_t)sx * swmi_aff_strip_words(n) : 0ull) +
+                const uint32_t *__restrict__ src = dir + (ADAPT ? (uint64_t)sx * astride : BAND ? swmi_aff_band_strip_off(sx, n, wb) : LONG ? (uint64_t)sx * swmi_aff_strip_words(n) : 0ull) +
                                                    (uint64_t)wlo * blk_words;
                 const uint32_t words = (whi - wlo) * blk_words;
                 for (uint32_t x = lane; x < words; x += WAVE) tile[x] = src[x];
@@ -720,7 +803,8 @@ __device__ __forceinline__ void aff_traceback(const TraceArgs A, const uint32_t 
                 else if (!LONG || l != 0u) { k = R - 1u; --l; }
                 else {                                            // up from a strip's first row: the last row of the strip above
                     k = R - 1u; l = WAVE - 1u; --sx;
-                    if constexpr (BAND) { clo = swmi_aff_band_lo(sx, wb); chi = swmi_aff_band_hi(sx, n, wb); W = swmi_aff_band_blocks(sx, n, wb); }
+                    if constexpr (ADAPT) AFF_ADAPT_WINDOW
+                    else if constexpr (BAND) { clo = swmi_aff_band_lo(sx, wb); chi = swmi_aff_band_hi(sx, n, wb); W = swmi_aff_band_blocks(sx, n, wb); }
                 }
             }
             cur |= op << (2u * (n_ops & 15u));
@@ -755,25 +839,27 @@ __device__ __forceinline__ void aff_traceback(const TraceArgs A, const uint32_t 
         WAVE_SYNC();
     }
 }
+#undef AFF_ADAPT_WINDOW
 }  // namespace
 
 #define AFF_TB_PARAMS_0 const TraceArgs A, const uint32_t tile_words, const uint32_t ops_words
 #define AFF_TB_PARAMS_1 const TraceArgs A, const uint32_t tile_words, const uint32_t ops_words, const uint32_t band
 #define AFF_TB_ARGS_0 A, tile_words, ops_words
 #define AFF_TB_ARGS_1 A, tile_words, ops_words, band
-#define AFF_TRACEBACK_KERNEL(name, MODE, LONG, BAND)                                                        \
+#define AFF_TRACEBACK_KERNEL(name, MODE, LONG, BAND, ADAPT)                                                 \
     extern "C" __global__ void __launch_bounds__(WAVE) name(AFF_TB_PARAMS_##BAND) {                        \
-        aff_traceback<MODE, LONG, BAND != 0>(AFF_TB_ARGS_##BAND);                                          \
+        aff_traceback<MODE, LONG, BAND != 0, ADAPT != 0>(AFF_TB_ARGS_##BAND);                              \
     }
-AFF_TRACEBACK_KERNEL(sw_affine_traceback_kernel, AFF_LOCAL, false, 0)
-AFF_TRACEBACK_KERNEL(sw_affine_traceback_fit_kernel, AFF_FIT, false, 0)
-AFF_TRACEBACK_KERNEL(sw_affine_traceback_global_kernel, AFF_GLOBAL, false, 0)
-AFF_TRACEBACK_KERNEL(sw_affine_traceback_long_kernel, AFF_LOCAL, true, 0)
-AFF_TRACEBACK_KERNEL(sw_affine_traceback_long_fit_kernel, AFF_FIT, true, 0)
-AFF_TRACEBACK_KERNEL(sw_affine_traceback_long_global_kernel, AFF_GLOBAL, true, 0)
-AFF_TRACEBACK_KERNEL(sw_affine_traceback_band_kernel, AFF_LOCAL, true, 1)
-AFF_TRACEBACK_KERNEL(sw_affine_traceback_band_fit_kernel, AFF_FIT, true, 1)
-AFF_TRACEBACK_KERNEL(sw_affine_traceback_band_global_kernel, AFF_GLOBAL, true, 1)
+AFF_TRACEBACK_KERNEL(sw_affine_traceback_kernel, AFF_LOCAL, false, 0, 0)
+AFF_TRACEBACK_KERNEL(sw_affine_traceback_fit_kernel, AFF_FIT, false, 0, 0)
+AFF_TRACEBACK_KERNEL(sw_affine_traceback_global_kernel, AFF_GLOBAL, false, 0, 0)
+AFF_TRACEBACK_KERNEL(sw_affine_traceback_long_kernel, AFF_LOCAL, true, 0, 0)
+AFF_TRACEBACK_KERNEL(sw_affine_traceback_long_fit_kernel, AFF_FIT, true, 0, 0)
+AFF_TRACEBACK_KERNEL(sw_affine_traceback_long_global_kernel, AFF_GLOBAL, true, 0, 0)
+AFF_TRACEBACK_KERNEL(sw_affine_traceback_band_kernel, AFF_LOCAL, true, 1, 0)
+AFF_TRACEBACK_KERNEL(sw_affine_traceback_band_fit_kernel, AFF_FIT, true, 1, 0)
+AFF_TRACEBACK_KERNEL(sw_affine_traceback_band_global_kernel, AFF_GLOBAL, true, 1, 0)
+AFF_TRACEBACK_KERNEL(sw_affine_traceback_band_adapt_global_kernel, AFF_GLOBAL, true, 1, 1)
 #undef AFF_TRACEBACK_KERNEL
 #undef AFF_TB_PARAMS_0
 #undef AFF_TB_PARAMS_1
@@ -789,11 +875,15 @@ AFF_TRACEBACK_KERNEL(sw_affine_traceback_band_global_kernel, AFF_GLOBAL, true, 1
 //   the kernels that have pairs are launched).  long_reads 1: the strip sweep (every pair has a read longer than 1024 bases)
 // band: with long_reads, the half-width of option "band" (0: none): the banded strip sweep
 // xdrop: with long_reads and align_mode 3, the threshold of option "xdrop" (0: none): the strip sweep that may stop at a seam
+// band_adapt: with long_reads, band and align_mode 3, option "band_adapt" (0 / 1): the banded strip sweep whose windows follow the
+//   alignment; every pair's workspace is then swmi_aff_adapt_work_words
 extern "C" hipError_t swmi_launch_affine_sweep(const FillArgs *a, int32_t gap_open, uint32_t align_mode, const uint32_t *mat, uint32_t nn,
-                                               uint32_t r_min, uint32_t r_max, uint32_t long_reads, uint32_t band, uint32_t xdrop, hipStream_t st) {
+                                               uint32_t r_min, uint32_t r_max, uint32_t long_reads, uint32_t band, uint32_t xdrop,
+                                               uint32_t band_adapt, hipStream_t st) {
     if (a->n_pairs == 0) return hipSuccess;
     if (align_mode > 3u || (mat && (nn < 2u || nn > SWMI_MAT_NN_MAX)) || band > SWMI_AFF_BAND_MAX) return hipErrorInvalidValue;
     if (xdrop > 0x7FFFFFFFu || (xdrop && long_reads && align_mode != AFF_EXTEND)) return hipErrorInvalidValue;
+    if (band_adapt > 1u || (band_adapt && long_reads && (!band || align_mode != AFF_EXTEND))) return hipErrorInvalidValue;
     // [narrow / wide / long][align_mode], and [align_mode] of the banded long sweeps: one typed table per signature (plain /
     // matrix, without / with the half-width), so that a launch is checked against its kernel's parameter list
     static void (*const plain[3][4])(FillArgs, int) = {
@@ -816,12 +906,22 @@ extern "C" hipError_t swmi_launch_affine_sweep(const FillArgs *a, int32_t gap_op
     static void (*const xmatrix)(FillArgs, int, const uint32_t *, uint32_t, uint32_t) = sw_affine_sweep_long_xdrop_matrix_kernel;
     static void (*const xbplain)(FillArgs, int, uint32_t, uint32_t) = sw_affine_sweep_band_xdrop_kernel;
     static void (*const xbmatrix)(FillArgs, int, const uint32_t *, uint32_t, uint32_t, uint32_t) = sw_affine_sweep_band_xdrop_matrix_kernel;
+    // the banded strip sweeps of an extend run under option "band_adapt", [xdrop]: the signatures of the banded sweeps
+    static void (*const aplain)(FillArgs, int, uint32_t) = sw_affine_sweep_band_adapt_kernel;
+    static void (*const amatrix)(FillArgs, int, const uint32_t *, uint32_t, uint32_t) = sw_affine_sweep_band_adapt_matrix_kernel;
+    static void (*const axplain)(FillArgs, int, uint32_t, uint32_t) = sw_affine_sweep_band_adapt_xdrop_kernel;
+    static void (*const axmatrix)(FillArgs, int, const uint32_t *, uint32_t, uint32_t, uint32_t) = sw_affine_sweep_band_adapt_xdrop_matrix_kernel;
     const dim3 grid((a->n_pairs + AFF_WAVES - 1) / AFF_WAVES), block(WAVE * AFF_WAVES);
     const bool banded = long_reads && band;                       // (the long shape only)
+    const bool adapts = banded && band_adapt;
     // (a launch's own error is what hipGetLastError returns below)
     const bool stops = long_reads && xdrop;                       // (the long shape only)
     const auto launch = [&](int shape) {
-        if (stops && banded && mat) hipLaunchKernelGGL(xbmatrix, grid, block, 0, st, *a, (int)gap_open, mat, nn, band, xdrop);
+        if (adapts && stops && mat) hipLaunchKernelGGL(axmatrix, grid, block, 0, st, *a, (int)gap_open, mat, nn, band, xdrop);
+        else if (adapts && stops)   hipLaunchKernelGGL(axplain, grid, block, 0, st, *a, (int)gap_open, band, xdrop);
+        else if (adapts && mat)     hipLaunchKernelGGL(amatrix, grid, block, 0, st, *a, (int)gap_open, mat, nn, band);
+        else if (adapts)            hipLaunchKernelGGL(aplain, grid, block, 0, st, *a, (int)gap_open, band);
+        else if (stops && banded && mat) hipLaunchKernelGGL(xbmatrix, grid, block, 0, st, *a, (int)gap_open, mat, nn, band, xdrop);
         else if (stops && banded)   hipLaunchKernelGGL(xbplain, grid, block, 0, st, *a, (int)gap_open, band, xdrop);
         else if (stops && mat)      hipLaunchKernelGGL(xmatrix, grid, block, 0, st, *a, (int)gap_open, mat, nn, xdrop);
         else if (stops)             hipLaunchKernelGGL(xplain, grid, block, 0, st, *a, (int)gap_open, xdrop);
@@ -839,11 +939,12 @@ extern "C" hipError_t swmi_launch_affine_sweep(const FillArgs *a, int32_t gap_op
 }
 
 // long_reads: the walk over the strips' fields (every pair of the launch has a read longer than 1024 bases)
-// band: as for the sweep
-extern "C" hipError_t swmi_launch_affine_traceback(const TraceArgs *a, uint32_t align_mode, uint32_t long_reads, uint32_t band, uint32_t tile_words,
-                                                   uint32_t ops_words, hipStream_t st) {
+// band, band_adapt: as for the sweep
+extern "C" hipError_t swmi_launch_affine_traceback(const TraceArgs *a, uint32_t align_mode, uint32_t long_reads, uint32_t band, uint32_t band_adapt,
+                                                   uint32_t tile_words, uint32_t ops_words, hipStream_t st) {
     if (a->n_pairs == 0) return hipSuccess;
     if (align_mode > 3u || band > SWMI_AFF_BAND_MAX) return hipErrorInvalidValue;
+    if (band_adapt > 1u || (band_adapt && long_reads && (!band || align_mode != AFF_EXTEND))) return hipErrorInvalidValue;
     // an extend run is walked by global mode's kernels: aff_traceback<AFF_GLOBAL, ..> starts at whatever cell the list names and
     // makes no use of its being (m, n)
     if (align_mode == AFF_EXTEND) align_mode = AFF_GLOBAL;
@@ -852,10 +953,12 @@ extern "C" hipError_t swmi_launch_affine_traceback(const TraceArgs *a, uint32_t 
         {sw_affine_traceback_long_kernel, sw_affine_traceback_long_fit_kernel, sw_affine_traceback_long_global_kernel}};
     static void (*const bkern[3])(TraceArgs, uint32_t, uint32_t, uint32_t) = {      // [align_mode]: the banded long walks
         sw_affine_traceback_band_kernel, sw_affine_traceback_band_fit_kernel, sw_affine_traceback_band_global_kernel};
+    static void (*const akern)(TraceArgs, uint32_t, uint32_t, uint32_t) = sw_affine_traceback_band_adapt_global_kernel;   // ... under option "band_adapt"
     static const bool attrs = [] {
         for (int mode = 0; mode < 3; ++mode) {
             swmi_allow_big_lds(kern[0][mode]); swmi_allow_big_lds(kern[1][mode]); swmi_allow_big_lds(bkern[mode]);
         }
+        swmi_allow_big_lds(akern);
         return true;
     }();
     (void)attrs;
@@ -864,7 +967,8 @@ extern "C" hipError_t swmi_launch_affine_traceback(const TraceArgs *a, uint32_t 
     const auto launch = [&](auto *k, auto... band) {
         hipLaunchKernelGGL(k, dim3(a->n_pairs, SWMI_AFF_TB_SLOTS), dim3(WAVE), lds, st, *a, tile_words, ops_words, band...);
     };
-    if (long_reads && band) launch(bkern[align_mode], band);
+    if (long_reads && band && band_adapt) launch(akern, band);
+    else if (long_reads && band) launch(bkern[align_mode], band);
     else                    launch(kern[long_reads ? 1 : 0][align_mode]);
     return hipGetLastError();
 }

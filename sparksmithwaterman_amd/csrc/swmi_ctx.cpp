@@ -183,6 +183,9 @@ extern "C" int swmi_set_option(swmi_ctx *ctx, const char *name, int64_t value) {
         if (value < 0 || value > 0x7FFFFFFFll)
             return fail(SWMI_ERR_INVALID, "xdrop must be 0 (off) or a threshold of 1 .. 2^31 - 1, got %lld", (long long)value);
         ctx->modes.xdrop = (int)value;
+    } else if (!strcmp(name, "band_adapt")) {
+        if (value != 0 && value != 1) return fail(SWMI_ERR_INVALID, "band_adapt must be 0 or 1, got %lld", (long long)value);
+        ctx->modes.band_adapt = (int)value;
     } else if (!strcmp(name, "arena_words_per_pair")) {
         if (value < 1) return fail(SWMI_ERR_INVALID, "arena_words_per_pair out of range");
         ctx->arena_words_per_pair = (uint64_t)value;

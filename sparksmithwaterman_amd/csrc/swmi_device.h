@@ -348,6 +348,27 @@ SWMI_HD static inline uint64_t swmi_aff_band_strip_off(uint32_t s, uint32_t n, u
 SWMI_HD static inline uint64_t swmi_aff_band_dir_words(uint32_t m, uint32_t n, uint32_t w) {
     return swmi_aff_band_strip_off(swmi_aff_strips(m), n, w);
 }
+// ---- option "band_adapt" (with band = w and option "extend"): the window of strip s follows a CENTRE c that the
+// sweep takes from the seam row above the strip -- c_lo = max(1, c + 1 - w), c_hi = min(n, c + 1024 + w), 0 <= c <= n; c = 0 is
+// strip 0's (static) window.  A window has at most min(n, 1024 + 2 w) columns, and every strip's field gets the blocks of that
+// many: a fixed stride, blocks beyond a strip's actual window neither written nor read.  Behind the NS fields the sweep leaves
+// the WINDOW TABLE, the centre it used for every strip it swept: what the traceback and swmi_pair_band_window read. ----
+SWMI_HD static inline uint32_t swmi_aff_adapt_lo(uint32_t c, uint32_t w) { return c + 1u > w ? c + 1u - w : 1u; }
+SWMI_HD static inline uint32_t swmi_aff_adapt_hi(uint32_t c, uint32_t n, uint32_t w) {       // (c <= n; w <= SWMI_AFF_BAND_MAX)
+    return n - c > SWMI_AFF_MAX_READ + w ? c + SWMI_AFF_MAX_READ + w : n;
+}
+// dwords of one strip's field, of the pair's NS fields, and of the pair's workspace: the fields and the table, which is rounded
+// to 64 dwords so that the next pair's field stays 256-byte aligned
+SWMI_HD static inline uint64_t swmi_aff_adapt_strip_words(uint32_t n, uint32_t w) {
+    const uint64_t cols = (uint64_t)SWMI_AFF_MAX_READ + 2ull * w;
+    return swmi_aff_strip_words(cols < n ? (uint32_t)cols : n);
+}
+SWMI_HD static inline uint64_t swmi_aff_adapt_dir_words(uint32_t m, uint32_t n, uint32_t w) {
+    return (uint64_t)swmi_aff_strips(m) * swmi_aff_adapt_strip_words(n, w);
+}
+SWMI_HD static inline uint64_t swmi_aff_adapt_work_words(uint32_t m, uint32_t n, uint32_t w) {
+    return swmi_aff_adapt_dir_words(m, n, w) + (((uint64_t)swmi_aff_strips(m) + 63u) & ~63ull);
+}
 // score matrices (swmi_set_score_matrix) on the affine sweeps: at most 64 symbols, plus class n = outside the alphabet.
 // Device image: 256 key dwords by base code (class * 4 | hi << 16, hi = the code outside the alphabet, else 0x1FF), then the
 // (n+1) x (n+1) int32 scores, row = read class, column = reference class (row and column n are not read: the kernel fills them).

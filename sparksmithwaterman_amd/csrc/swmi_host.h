@@ -119,11 +119,22 @@ struct __attribute__((visibility("hidden"))) RunModes {
     int band = 0;                           // > 0: the half-width of the band the strip sweeps of such reads keep to (swmi.h); the affine kernels
     int extend = 0;                         // 1: seed extension -- a global run whose maximum is taken over every cell (swmi.h); refused in the other modes
     int xdrop = 0;                          // > 0: the drop-off threshold X of an extend run -- the strip sweep of a long read ends at a seam (swmi.h); refused in other runs
+    int band_adapt = 0;                     // 1: the band of an extend run follows the alignment, strip by strip (swmi.h); refused in other runs
     // the MODE of the affine kernels and their launchers: the align_mode, or 3 (extend) for a global run with option "extend"
     uint32_t kernel_mode() const { return extend && align_mode == SWMI_ALIGN_GLOBAL ? 3u : (uint32_t)align_mode; }
     bool operator==(const RunModes &o) const { return memcmp(this, &o, sizeof(RunModes)) == 0; }
 };
 static_assert(std::has_unique_object_representations_v<RunModes>, "RunModes is compared bytewise: no padding, no floating point");
+// Option "band_adapt": the lower bound of every real H of a pair (m > 1024, NS = ceil(m / 1024) strips; gap_open, gap <= 0),
+// (2 NS + 1) gap_open + (1024 NS + n) gap, and the run's condition on it, >= -2^30 (swmi.h).  In the header, and
+// of plain integers: tests/test_adapt_cpu.py compiles it into a program of its own.
+static inline int64_t swmi_adapt_low(uint64_t m, uint64_t n, int64_t gap_open, int64_t gap) {
+    const int64_t ns = (int64_t)((m + SWMI_AFF_MAX_READ - 1) / SWMI_AFF_MAX_READ);
+    return (2 * ns + 1) * gap_open + (ns * (int64_t)SWMI_AFF_MAX_READ + (int64_t)n) * gap;
+}
+static inline bool swmi_adapt_bound_ok(uint64_t m, uint64_t n, int64_t gap_open, int64_t gap) {
+    return swmi_adapt_low(m, n, gap_open, gap) >= -((int64_t)1 << 30);
+}
 struct __attribute__((visibility("hidden"))) RunOptions {
     RunModes modes;
     std::shared_ptr<const ScoreMatrix> mat; // swmi_set_score_matrix (null: none); keeps the matrix's host image alive
@@ -168,7 +179,7 @@ struct swmi_ctx {
     bool cell_cap_set = false;              // cell_cap given by the caller (otherwise small launches get longer lists)
     int32_t gap_open = 0;                   // affine gaps: a gap of length k costs gap_open + k * gap (0: linear)
     int affine = -1;                        // -1: the affine kernels (mode 3) when gap_open != 0; 1: always
-    RunModes modes;                         // options "align_mode", "long_reads", "band", "extend" and "xdrop"
+    RunModes modes;                         // options "align_mode", "long_reads", "band", "extend", "xdrop" and "band_adapt"
     std::mutex mat_mu;                      // guards `matrix` (not ctx->mu: setting a matrix does not wait for a run)
     std::shared_ptr<const ScoreMatrix> matrix;   // swmi_set_score_matrix; a run with one takes the affine kernels
     // swmi_batch_run_async: one run in flight on the context's own host thread
@@ -293,6 +304,7 @@ struct swmi_batch {
     std::vector<Work> work;                 // schedule (pairs sorted by work), valid for work_mode
     int work_mode = -1;
     int work_band = 0;                      // the band the schedule's workspace sizes were made for (mode 3)
+    int work_adapt = 0;                     // ... and option "band_adapt" (its fields have a fixed stride and a window table behind them)
     bool work_tfused = false;               // the schedule's workspace sizes leave room for sw_tfused_kernel's column checkpoints
     uint32_t eff_mode = 1;                  // pipeline of the current run (3: the affine kernels, swmi_affine.hip)
     int32_t gap_open = 0;                   // the context's gap_open when the run started (mode 3)
@@ -305,6 +317,10 @@ struct swmi_batch {
     PlanKey plan_key;                       // the chunk the device-side item lists and `plan` were prepared for last
     ChunkPlan plan;
     std::vector<PairRes> pairs;             // by pair index
+    // option "band_adapt": the window tables the sweeps of the last run left (the centre of every strip, swmi_device.h), fetched
+    // after every launch; win_at[pair] = 1 + the index of the pair's first entry in win_tab, 0 for a pair without a table
+    std::vector<uint32_t> win_tab;
+    std::vector<uint64_t> win_at;
     // raw record streams of the last run (one per launch chunk), indexed lazily on the first alignment access
     // the record table entries (AlnRec, swmi_device.h) and the payload arenas of the launches, one RawChunk per launch
     struct RawChunk { size_t at, words; size_t tab_at, n_rec; size_t lo; std::vector<uint32_t> wpos; };   // wpos: re-run chunks only

@@ -150,6 +150,32 @@ extern "C" int swmi_pair_rows_swept(const swmi_batch *b, uint64_t pair, uint32_t
     return SWMI_OK;
 }
 
+// the window of reference columns the pair's sweep used for strip `strip` of the read (swmi.h)
+extern "C" int swmi_pair_band_window(const swmi_batch *b, uint64_t pair, uint32_t strip, uint32_t *c_lo, uint32_t *c_hi) {
+    int rc = check_pair(b, pair);
+    if (rc) return rc;
+    const PairRes &pr = b->pairs[pair];
+    const uint32_t m = b->read_desc[pair % b->n_reads].len, n = b->ref_desc[pair / b->n_reads].len;
+    const uint32_t ns = swmi_aff_strips(m), swept = pr.strips ? pr.strips : ns;
+    if (strip >= ns) return fail(SWMI_ERR_RANGE, "strip %u: the read of pair %llu has %u strip%s", strip, (unsigned long long)pair, ns, ns == 1 ? "" : "s");
+    if (strip >= swept) return fail(SWMI_ERR_RANGE, "strip %u of pair %llu was not swept: xdrop ended the sweep behind strip %u", strip,
+                                    (unsigned long long)pair, swept - 1u);
+    const RunModes &md = b->opt.modes;
+    uint32_t lo = 1u, hi = n;
+    if (b->eff_mode == 3 && md.band > 0 && m > SWMI_AFF_MAX_READ && n) {
+        if (md.band_adapt) {
+            if (pair >= b->win_at.size() || !b->win_at[pair]) return fail(SWMI_ERR_INVALID, "pair %llu has no window table", (unsigned long long)pair);
+            const uint32_t cen = std::min(b->win_tab[b->win_at[pair] - 1 + strip], n);
+            lo = swmi_aff_adapt_lo(cen, (uint32_t)md.band); hi = swmi_aff_adapt_hi(cen, n, (uint32_t)md.band);
+        } else {
+            lo = swmi_aff_band_lo(strip, (uint32_t)md.band); hi = swmi_aff_band_hi(strip, n, (uint32_t)md.band);
+        }
+    }
+    if (c_lo) *c_lo = lo;
+    if (c_hi) *c_hi = hi;
+    return SWMI_OK;
+}
+
 // every pair's score and alignment count at once (bulk form of the two accessors above)
 extern "C" int swmi_batch_pair_results(const swmi_batch *b, int32_t *scores, uint64_t *n_alignments, uint64_t n) {
     if (!b) return fail(SWMI_ERR_INVALID, "batch is null");

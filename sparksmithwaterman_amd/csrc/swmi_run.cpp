@@ -265,11 +265,11 @@ static int enqueue_launches(RunState &rs, Launch &L, const ResidentArgs &xa, con
             fl.n_pairs = (uint32_t)plan.aff_n_long; fl.pairs = fa.pairs + fs.n_pairs;
             const uint32_t *mat = b->opt.mat ? b->d_mat.as<uint32_t>() : nullptr;
             const uint32_t nn = b->opt.mat ? b->opt.mat->n + 1u : 0u;
-            HIP_TRY(swmi_launch_affine_sweep(&fs, b->gap_open, b->opt.modes.kernel_mode(), mat, nn, plan.aff_r_min, plan.aff_r_max, 0u, 0u, 0u, ctx->stream));
+            HIP_TRY(swmi_launch_affine_sweep(&fs, b->gap_open, b->opt.modes.kernel_mode(), mat, nn, plan.aff_r_min, plan.aff_r_max, 0u, 0u, 0u, 0u, ctx->stream));
             // (option "band": the banded strip sweep; the other pairs are swept in full.  Option "xdrop": the strip sweep that may
             // end at a seam; the other pairs take the kernels they take without it)
             HIP_TRY(swmi_launch_affine_sweep(&fl, b->gap_open, b->opt.modes.kernel_mode(), mat, nn, 0u, 0u, 1u, (uint32_t)b->opt.modes.band,
-                                             (uint32_t)b->opt.modes.xdrop, ctx->stream));
+                                             (uint32_t)b->opt.modes.xdrop, (uint32_t)b->opt.modes.band_adapt, ctx->stream));
         }
         else HIP_TRY(swmi_launch_fill(&fa, ctx->stream, ext ? ctx->ev[0] : nullptr, ext ? ctx->ev[1] : nullptr));
         rs.launches++;
@@ -298,8 +298,9 @@ static int enqueue_launches(RunState &rs, Launch &L, const ResidentArgs &xa, con
         ts.n_pairs = (uint32_t)(np - plan.aff_n_long);
         tl.n_pairs = (uint32_t)plan.aff_n_long; tl.pairs = ta.pairs + ts.n_pairs;
         const uint32_t ops_words = (uint32_t)(((uint64_t)plan.max_path + 15) / 16 + 1);
-        HIP_TRY(swmi_launch_affine_traceback(&ts, b->opt.modes.kernel_mode(), 0u, 0u, SWMI_AFF_TILE_WORDS, ops_words, ctx->stream));
-        HIP_TRY(swmi_launch_affine_traceback(&tl, b->opt.modes.kernel_mode(), 1u, (uint32_t)b->opt.modes.band, SWMI_AFF_TILE_WORDS, ops_words, ctx->stream));
+        HIP_TRY(swmi_launch_affine_traceback(&ts, b->opt.modes.kernel_mode(), 0u, 0u, 0u, SWMI_AFF_TILE_WORDS, ops_words, ctx->stream));
+        HIP_TRY(swmi_launch_affine_traceback(&tl, b->opt.modes.kernel_mode(), 1u, (uint32_t)b->opt.modes.band, (uint32_t)b->opt.modes.band_adapt,
+                                             SWMI_AFF_TILE_WORDS, ops_words, ctx->stream));
     } else if (n_res + n_tf < np) {
         HIP_TRY(swmi_launch_traceback(&ta, ctx->stream, ext ? ctx->ev[2] : nullptr, ext ? ctx->ev[3] : nullptr));
     }
@@ -424,6 +425,26 @@ static int collect_launch(RunState &rs, Launch &L, Clock::time_point t_done, std
     return SWMI_OK;
 }
 
+// Option "band_adapt": the window tables of the launch's long pairs, from the workspace (the next launch rewrites it) into the
+// batch, for swmi_pair_band_window.  One small copy per long pair: the tables lie behind the pairs' fields.  The exact-size re-run
+// of a pair leaves the same table (same kernel, same inputs) and overwrites the entry.
+static int fetch_windows(swmi_batch *b, const std::vector<Work> &work, size_t lo) {
+    const ChunkPlan &plan = b->plan;
+    if (b->eff_mode != 3 || !b->opt.modes.band_adapt || !plan.aff_n_long) return SWMI_OK;
+    const size_t np = b->pairs_on_device.size() / sizeof(PairDesc);
+    const PairDesc *pd = (const PairDesc *)b->pairs_on_device.data();
+    const uint32_t w = (uint32_t)b->opt.modes.band;
+    if (b->win_at.size() != b->pairs.size()) b->win_at.assign(b->pairs.size(), 0);
+    for (size_t k = np - plan.aff_n_long; k < np; k++) {
+        const uint32_t pair = work[lo + pd[k].out_id].pair;
+        const uint32_t m = b->read_desc[pd[k].read_id].len, n = b->ref_desc[pd[k].ref_id].len, ns = swmi_aff_strips(m);
+        if (!b->win_at[pair]) { b->win_at[pair] = b->win_tab.size() + 1; b->win_tab.resize(b->win_tab.size() + ns, 0u); }
+        HIP_TRY(hipMemcpy(b->win_tab.data() + (b->win_at[pair] - 1), b->d_dir.as<uint32_t>() + pd[k].dir_off + swmi_aff_adapt_dir_words(m, n, w),
+                          (size_t)ns * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    }
+    return SWMI_OK;
+}
+
 // Runs the kernels for work[lo, hi) -- one launch of each kernel the chunk needs -- waits, and keeps the records; a record arena
 // or table that proves too small is grown to the size the kernels asked for and the traceback repeated.
 // Cell-list geometry: uniform (cell_cap per pair) when cells_exact is null, else exact per pair (the re-run of overflowed pairs).
@@ -505,6 +526,7 @@ static int run_chunk(RunState &rs, const std::vector<Work> &work, size_t lo, siz
         }
         if (rs.ta.dbg && (rc = dump_traceback_diagnostics(b, rs.ta, np, plan.n_tf))) return rc;
         if (rs.fa.dbg && L.attempt == 0 && (rc = dump_fill_diagnostics(b, rs.fa, np))) return rc;
+        if (L.attempt == 0 && (rc = fetch_windows(b, work, lo))) return rc;      // (the workspace survives an arena-overflow retry)
         if (L.sweep_only) { collect_scores(b, work, L, outs); return SWMI_OK; }
         bool retry;
         if ((rc = collect_launch(rs, L, c2, saved_outs, outs, retry)) || !retry) return rc;
@@ -530,8 +552,9 @@ static int check_band(const swmi_ctx *ctx, const swmi_batch *b, const swmi_param
         max_m = std::max(max_m, m);
     }
     // a strip whose window is empty: the last strip's window starts at column 1024 (NS - 1) + 1 - w
+    // (option "band_adapt": no window is ever empty -- its centre is a column of the reference)
     const int64_t last_lo = (int64_t)rows - SWMI_AFF_MAX_READ + 1 - w;
-    if ((int64_t)min_n < last_lo)
+    if (!md.band_adapt && (int64_t)min_n < last_lo)
         return fail(SWMI_ERR_UNSUPPORTED, "band %d: the last strip of the longest read (%llu bases) starts at column %lld, past the end of the "
                     "shortest reference (%llu)", band, (unsigned long long)max_m, (long long)last_lo, (unsigned long long)min_n);
     // global mode: the one cell (m, n) must lie in the band, n <= 1024 NS + w (option "extend": the end cell is free -- the
@@ -544,14 +567,22 @@ static int check_band(const swmi_ctx *ctx, const swmi_batch *b, const swmi_param
     if (align_mode != SWMI_ALIGN_LOCAL && (int64_t)rows * S > ((int64_t)1 << 29))
         return fail(SWMI_ERR_UNSUPPORTED, "band %d, align_mode fit / global: the longest read (%llu bases) is swept as %llu rows, and %llu * %lld (the "
                     "largest |score|) is above 2^29", band, (unsigned long long)max_m, (unsigned long long)rows, (unsigned long long)rows, (long long)S);
-    if (align_mode == SWMI_ALIGN_GLOBAL) {
+    if (md.band_adapt) {
+        // moving windows: an existing cell is reached by a staircase of gap moves with two gap openings per strip and the
+        // boundary's, where the static band has a diagonal and three openings
+        const int64_t low = swmi_adapt_low(max_m, max_n, ctx->gap_open, p->gap);
+        if (!swmi_adapt_bound_ok(max_m, max_n, ctx->gap_open, p->gap))
+            return fail(SWMI_ERR_UNSUPPORTED, "band %d, band_adapt: (2 * ceil(m / 1024) + 1) * gap_open + (1024 * ceil(m / 1024) + n) * gap = %lld for the "
+                        "longest read (%llu) and reference (%llu) is below -2^30", band, (long long)low, (unsigned long long)max_m, (unsigned long long)max_n);
+    } else if (align_mode == SWMI_ALIGN_GLOBAL) {
         const int64_t low = 3 * (int64_t)ctx->gap_open + (int64_t)(rows + max_n) * (int64_t)p->gap;
         if (low < -((int64_t)1 << 30))
             return fail(SWMI_ERR_UNSUPPORTED, "band %d, align_mode global: 3 * gap_open + (1024 * ceil(m / 1024) + n) * gap = %lld for the longest "
                         "read (%llu) and reference (%llu) is below -2^30", band, (long long)low, (unsigned long long)max_m, (unsigned long long)max_n);
     }
     // the field of the largest pair alone against the workspace cap (it grows with m and with n)
-    const uint64_t bytes = swmi_aff_band_dir_words((uint32_t)max_m, (uint32_t)max_n, (uint32_t)band) * 4;
+    const uint64_t bytes = (md.band_adapt ? swmi_aff_adapt_work_words((uint32_t)max_m, (uint32_t)max_n, (uint32_t)band)
+                                          : swmi_aff_band_dir_words((uint32_t)max_m, (uint32_t)max_n, (uint32_t)band)) * 4;
     if (bytes > ctx->max_workspace_bytes)
         return fail(SWMI_ERR_UNSUPPORTED, "band %d: the direction field of the longest read (%llu) against the longest reference (%llu) takes %llu "
                     "bytes, more than max_workspace_bytes (%llu)", band, (unsigned long long)max_m, (unsigned long long)max_n,
@@ -578,6 +609,10 @@ static int check_run_params(const swmi_ctx *ctx, const swmi_batch *b, const swmi
     if (md.xdrop > 0 && !(md.extend && md.align_mode == SWMI_ALIGN_GLOBAL))
         return fail(SWMI_ERR_UNSUPPORTED, "xdrop = %d needs an extend run (align_mode global (2) with extend = 1), got align_mode %d, extend %d",
                     md.xdrop, md.align_mode, md.extend);
+    // option "band_adapt" moves the band of a banded extend run: there is nothing to move in any other run
+    if (md.band_adapt && !(md.band > 0 && md.extend && md.align_mode == SWMI_ALIGN_GLOBAL))
+        return fail(SWMI_ERR_UNSUPPORTED, "band_adapt = 1 needs a banded extend run (band > 0, align_mode global (2) with extend = 1), got band %d, "
+                    "align_mode %d, extend %d", md.band, md.align_mode, md.extend);
     uint64_t max_m, max_n;
     if (affine) {
         // the bounds within which every sum of the affine recurrence fits int32 (DESIGN.md "Affine gaps")
@@ -693,10 +728,12 @@ static int choose_traceback_grain(swmi_ctx *ctx, swmi_batch *b, const swmi_param
 // SmithWaterman.java:157-159: (0, [])).  It only depends on the sequence lengths and the pipeline mode: built once per batch.
 static void build_schedule(const swmi_ctx *ctx, swmi_batch *b) {
     const int band = b->eff_mode == 3 ? b->opt.modes.band : 0;
-    if (b->work_mode == (int)b->eff_mode && b->work_tfused == (ctx->tfused == 1) && b->work_band == band) return;
+    const int adapt = band > 0 ? b->opt.modes.band_adapt : 0;
+    if (b->work_mode == (int)b->eff_mode && b->work_tfused == (ctx->tfused == 1) && b->work_band == band && b->work_adapt == adapt) return;
     const uint32_t n_refs = b->n_refs, n_reads = b->n_reads;
     b->work_tfused = ctx->tfused == 1;
     b->work_band = band;
+    b->work_adapt = adapt;
     b->work.clear();
     b->work.reserve((uint64_t)n_refs * n_reads);
     b->work_cells = 0;
@@ -722,8 +759,10 @@ static void build_schedule(const swmi_ctx *ctx, swmi_batch *b) {
         b->work.push_back(w);
     };
     const bool tf = ctx->tfused == 1;
-    // (option "band": a read of several strips leaves the field of its windows only)
+    // (option "band": a read of several strips leaves the field of its windows only; option "band_adapt": fields of a fixed
+    // stride and the window table, which is charged to the launch's workspace with them)
     auto dir_words = [&](uint32_t m, uint32_t n) {
+        if (adapt && m > SWMI_AFF_MAX_READ) return swmi_aff_adapt_work_words(m, n, (uint32_t)band);
         return band > 0 && m > SWMI_AFF_MAX_READ ? swmi_aff_band_dir_words(m, n, (uint32_t)band) : swmi_dir_words(m, n, b->eff_mode, tf);
     };
     if (refs_uniform) {                              // (reads outermost: descending m x the one n)
@@ -813,6 +852,7 @@ static int batch_run(swmi_ctx *ctx, swmi_batch *b, const swmi_params *p, RunOpti
 
     const uint32_t n_refs = b->n_refs;
     b->pairs.assign((uint64_t)n_refs * b->n_reads, PairRes{});
+    b->win_tab.clear(); b->win_at.clear();
     b->alns.clear(); b->str_at.clear();
     b->raw.clear(); b->rtab.clear(); b->raw_chunks.clear(); b->indexed = false;
     b->raw_ext = nullptr; b->rtab_ext = nullptr;

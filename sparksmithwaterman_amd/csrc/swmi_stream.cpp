@@ -91,6 +91,11 @@ static int stream_process(swmi_stream *s, swmi_stream::Slot &sl, StreamChunk *c)
     r->work = std::move(b->work); b->work.clear(); b->work_mode = -1;
     r->work_mode = (int)r->eff_mode;
     r->pairs = std::move(b->pairs);
+    // (swmi_pair_band_window: the run's modes -- not its matrix, which a results-only batch has no use for -- and, under option
+    // "band_adapt", the window tables the sweeps left)
+    r->opt.modes = b->opt.modes;
+    r->win_tab = std::move(b->win_tab); r->win_at = std::move(b->win_at);
+    b->win_tab.clear(); b->win_at.clear();
     if (s->keep_records) {
         (void)settle_raw(b);
         r->raw = std::move(b->raw);

@@ -180,6 +180,8 @@ def _rank_main(args):
             ctx.set_option("extend", 1)
         if args.xdrop:                                      # ... with the drop-off rule for reads longer than 1024 bases
             ctx.set_option("xdrop", args.xdrop)
+        if args.band_adapt:                                 # ... and the band re-centred on the alignment from strip to strip
+            ctx.set_option("band_adapt", 1)
         if args.matrix:                                     # substitution scores on this rank's context (NCBI text format)
             from . import matrix as _matrix
             ctx.set_score_matrix(_matrix.load(args.matrix))
@@ -212,6 +214,8 @@ def _parser():
                 self.error("--xdrop takes a threshold of 0 .. 2^31 - 1")
             if ns.xdrop and not ns.extend:
                 self.error("--xdrop requires --extend")
+            if ns.band_adapt and not (ns.band and ns.extend):
+                self.error("--band-adapt requires --band and --extend")
             return ns
     ap = Parser(description=__doc__.split("\n")[0])
     ap.add_argument("--ref-dir", required=True)
@@ -245,6 +249,10 @@ def _parser():
                     help="with --extend and --long-reads: the drop-off rule (option xdrop) -- the sweep of a read longer than 1024 bases "
                          "ends behind the first strip of 1024 rows whose last row lies more than X below the best score so far, and "
                          "the best cell so far is the answer.  0 (the default): off")
+    ap.add_argument("--band-adapt", action="store_true",
+                    help="with --band and --extend: the band follows the alignment (option band_adapt) -- the window of a strip of "
+                         "1024 rows is placed around the column where the row above it scores best, so --band only has to cover the "
+                         "drift inside one strip")
     ap.add_argument("--tie", choices=("serial", "strict"), default="serial",
                     help="serial: SmithWaterman's aligner (NoDistribution, DistributeReference); strict: DistributedSW's (DistributeAlgorithm)")
     ap.add_argument("--stream-chunk-bytes", type=int, default=512 << 10, help="sequence bytes per streamed chunk")

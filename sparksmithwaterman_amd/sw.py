@@ -35,15 +35,16 @@ def _algo(align_scores, align_types):
 
 
 @_contextlib.contextmanager
-def _scores(ctx, align_scores, align_mode=None, long_reads=None, band=None, extend=None, xdrop=None):
+def _scores(ctx, align_scores, align_mode=None, long_reads=None, band=None, extend=None, xdrop=None, band_adapt=None):
     """alignScores {match, mismatch, gap} or {match, mismatch, gap, gapOpen}: yields the three entries make_params takes
     and, for four, sets the context's "gap_open" for the call (affine gaps: a gap of length k costs gapOpen + k * gap).
     align_mode (ALIGN_LOCAL / ALIGN_FIT / ALIGN_GLOBAL, or None: the context's own) is set for the call in the same way;
     long_reads (True / False, or None: the context's own) likewise sets option "long_reads": reads longer than 1024 bases on the
     affine kernels; band (a half-width, 0: none, or None: the context's own) sets option "band"; extend (True / False, or None:
     the context's own) sets option "extend": seed extension, with align_mode ALIGN_GLOBAL only; xdrop (a threshold 0 .. 2^31 - 1, 0:
-    off, or None: the context's own) sets option "xdrop": the drop-off rule of an extend run of a read longer than 1024 bases.
-    The options are put back afterwards."""
+    off, or None: the context's own) sets option "xdrop": the drop-off rule of an extend run of a read longer than 1024 bases;
+    band_adapt (True / False, or None: the context's own) sets option "band_adapt": the band of a banded extend run follows the
+    alignment.  The options are put back afterwards."""
     sc = tuple(int(x) for x in align_scores)
     if len(sc) == 4 and sc[3] > 0:
         raise ValueError("gapOpen (alignScores[3]) must be <= 0, got %d" % sc[3])
@@ -53,6 +54,8 @@ def _scores(ctx, align_scores, align_mode=None, long_reads=None, band=None, exte
         raise ValueError("extend must be None, True or False, got %r" % (extend,))
     if xdrop is not None and (isinstance(xdrop, bool) or not isinstance(xdrop, int) or not 0 <= xdrop <= _capi.XDROP_MAX):
         raise ValueError("xdrop must be None or an integer 0 .. 2^31 - 1, got %r" % (xdrop,))
+    if band_adapt is not None and band_adapt is not True and band_adapt is not False:
+        raise ValueError("band_adapt must be None, True or False, got %r" % (band_adapt,))
     restore = []
     try:
         if len(sc) == 4:
@@ -73,6 +76,9 @@ def _scores(ctx, align_scores, align_mode=None, long_reads=None, band=None, exte
         if xdrop is not None:
             restore.append(("xdrop", ctx.options.get("xdrop", 0)))
             ctx.set_option("xdrop", xdrop)
+        if band_adapt is not None:
+            restore.append(("band_adapt", ctx.options.get("band_adapt", 0)))
+            ctx.set_option("band_adapt", 1 if band_adapt else 0)
         yield sc[:3]
     finally:
         for name, prev in reversed(restore):
@@ -84,18 +90,19 @@ class SmithWaterman:
         """Function3<String[], int[], char[], Tuple2<Integer, ArrayList<Tuple2<Integer,String[]>>>>."""
         tie_mode = _capi.TIE_SERIAL
 
-        def __init__(self, context=None, align_mode=None, long_reads=None, band=None, extend=None, xdrop=None):
+        def __init__(self, context=None, align_mode=None, long_reads=None, band=None, extend=None, xdrop=None, band_adapt=None):
             self._ctx = context
             self._align_mode = align_mode       # ALIGN_FIT / ALIGN_GLOBAL: end-to-end alignment (option "align_mode")
             self._long_reads = long_reads       # True: reads longer than 1024 bases on the affine kernels (option "long_reads")
             self._band = band                   # a half-width: such reads inside the band |j - i| <= band only (option "band")
             self._extend = extend               # True: seed extension, with ALIGN_GLOBAL -- anchored at the start, ends at the best cell (option "extend")
             self._xdrop = xdrop                 # a threshold: an extend run of a long read stops at a strip seam that far below its best (option "xdrop")
+            self._band_adapt = band_adapt       # True: the band of an extend run follows the alignment from strip to strip (option "band_adapt")
 
         def call(self, seqs, alignScores=None, alignTypes=None):
             ctx = self._ctx or default_context()
             sc, ty = _algo(alignScores, alignTypes)
-            with _scores(ctx, sc, self._align_mode, self._long_reads, self._band, self._extend, self._xdrop) as sc3:
+            with _scores(ctx, sc, self._align_mode, self._long_reads, self._band, self._extend, self._xdrop, self._band_adapt) as sc3:
                 b = ctx.upload([seqs[0]], [seqs[1]])
                 try:
                     b.run(make_params(sc3, ty, self.tie_mode))
@@ -125,11 +132,12 @@ class Distribution:
         together; results come back in input order, each exactly what MapRef.call returns.
         """
 
-        def __init__(self, context=None, tie_mode=_capi.TIE_SERIAL, align_mode=None, long_reads=None, band=None, extend=None, xdrop=None):
+        def __init__(self, context=None, tie_mode=_capi.TIE_SERIAL, align_mode=None, long_reads=None, band=None, extend=None, xdrop=None, band_adapt=None):
             self._ctx = context
             self._band = band
             self._extend = extend
             self._xdrop = xdrop
+            self._band_adapt = band_adapt
             self._tie = tie_mode
             self._align_mode = align_mode
             self._long_reads = long_reads
@@ -145,7 +153,7 @@ class Distribution:
             for idxs in groups.values():
                 _, reads, algo = tuples[idxs[0]]
                 sc, ty = _algo(*(algo if algo is not None else (None, None)))
-                with _scores(ctx, sc, self._align_mode, self._long_reads, self._band, self._extend, self._xdrop) as sc3:
+                with _scores(ctx, sc, self._align_mode, self._long_reads, self._band, self._extend, self._xdrop, self._band_adapt) as sc3:
                     b = ctx.upload([tuples[i][0][1] for i in idxs], list(reads))
                     try:
                         b.run(make_params(sc3, ty, self._tie))
@@ -158,8 +166,8 @@ class Distribution:
     class MapRef:
         """PairFunction<Tuple3<String[], ArrayList<String>, Tuple2<int[],char[]>>, Integer, Tuple2<...>>."""
 
-        def __init__(self, context=None, tie_mode=_capi.TIE_SERIAL, align_mode=None, long_reads=None, band=None, extend=None, xdrop=None):
-            self._mp = Distribution.MapPartition(context, tie_mode, align_mode, long_reads, band, extend, xdrop)
+        def __init__(self, context=None, tie_mode=_capi.TIE_SERIAL, align_mode=None, long_reads=None, band=None, extend=None, xdrop=None, band_adapt=None):
+            self._mp = Distribution.MapPartition(context, tie_mode, align_mode, long_reads, band, extend, xdrop, band_adapt)
 
         def call(self, tuple3):
             return self._mp.call([tuple3])[0]
@@ -204,11 +212,12 @@ class _FileDriver:
     REF_DIR, IN_DIR = "/home/ubuntu/project/reference", "/home/ubuntu/project/input"   # :43-44
     OUT_DIR = "/home/ubuntu/project/output/reference"                 # :50
 
-    def __init__(self, context=None, tie_mode=_capi.TIE_SERIAL, align_mode=None, long_reads=None, band=None, extend=None, xdrop=None):
+    def __init__(self, context=None, tie_mode=_capi.TIE_SERIAL, align_mode=None, long_reads=None, band=None, extend=None, xdrop=None, band_adapt=None):
         self._ctx = context
         self._band = band
         self._extend = extend
         self._xdrop = xdrop
+        self._band_adapt = band_adapt
         self._tie = tie_mode
         self._align_mode = align_mode
         self._long_reads = long_reads
@@ -225,7 +234,7 @@ class _FileDriver:
             out_ext = ioArgs[5] if ioArgs[5] is not None else out_ext
         sc, ty = _algo(*(algoArgs if algoArgs is not None else (None, None)))
         ctx = self._ctx or default_context()
-        with _scores(ctx, sc, self._align_mode, self._long_reads, self._band, self._extend, self._xdrop) as sc3:
+        with _scores(ctx, sc, self._align_mode, self._long_reads, self._band, self._extend, self._xdrop, self._band_adapt) as sc3:
             return self._run(ctx, make_params(sc3, ty, self._tie), ref_dir, in_dir, delim, out_dir, out_name, out_ext)
 
     def _run(self, ctx, params, ref_dir, in_dir, delim, out_dir, out_name, out_ext):
