@@ -9,9 +9,9 @@ it vacuous; the results are kept, so the cases of a parametrised test share them
 
   kernel (sw_affine_...)                       run by
   sweep_band_adapt_kernel                      test_adapt_drift, test_adapt_tie_rule, test_adapt_centre_stands_still, ...
-  sweep_band_adapt_matrix_kernel               test_adapt_mixed_launch[True]
+  sweep_band_adapt_matrix_kernel               test_adapt_mixed_launch[True], test_adapt_matrix_strict_ties
   sweep_band_adapt_xdrop_kernel                test_adapt_xdrop_*, test_adapt_mixed_launch_xdrop[False]
-  sweep_band_adapt_xdrop_matrix_kernel         test_adapt_mixed_launch_xdrop[True]
+  sweep_band_adapt_xdrop_matrix_kernel         test_adapt_mixed_launch_xdrop[True], test_adapt_matrix_strict_ties
   traceback_band_adapt_global_kernel           every test but the scores_only case"""
 import functools
 import random
@@ -296,6 +296,21 @@ def test_adapt_mixed_launch_xdrop(ctx, matrix):
     for q, e in enumerate(want):
         _check_pair(b, q, e + (len(reads[q]),), len(reads[q]), (matrix, q))
     b.free()
+
+
+def test_adapt_matrix_strict_ties(ctx):
+    """sw_affine_sweep_band_adapt_matrix_kernel and _band_adapt_xdrop_matrix_kernel in the strict tie order (the mixed launches
+    run the serial one): a drifting read of two strips, without a threshold and under one nothing exceeds"""
+    rng = random.Random(9959)
+    w, mat = 64, gc.score_matrix()
+    ref, read = _drift_pair(rng, 1400, every=700, first=350, extra=30, tail=150)
+    want = ar.align(ref, read, SC, w, 0, 1, mat)
+    assert len(want[3]) == 2
+    drops = ar.trace(ref, read, SC, w, 0, 1, mat)[2]
+    for X in (0, max([b_ - s_ for b_, s_ in drops] + [0]) + 1):
+        b = _run(ctx, [ref], [read], w, 1, X, mat)
+        _check_pair(b, 0, want + (len(read),), len(read), X)
+        b.free()
 
 
 # 7 -- cell_cap = 1 on a pair with two tied maximum cells: the exact-size re-run places the same windows

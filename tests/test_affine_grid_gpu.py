@@ -1,6 +1,8 @@
 """Every rows-per-lane class of the affine kernels in every mode (swmi_affine.hip), against the restatements of the contract.
 
-The 24 sweep kernels and 9 traceback kernels, and the tests that run them (G: this module; a new kernel goes into this table):
+The 40 sweep kernels and 10 traceback kernels, and the tests that run them (G: this module; a new kernel goes into this table).
+Between them the tests named on a row of the extend, xdrop and band_adapt kernels run both tie orders; a test that runs the
+strict order is marked `strict:` where the others on the row run the serial one only:
 
   sweep kernel (sw_affine_sweep_...)    rows per lane     run by
   kernel                                1 .. 4            G test_grid_shapes[0-False-*], test_grid_walks[0-False-*]; test_affine_gpu.py
@@ -27,6 +29,25 @@ The 24 sweep kernels and 9 traceback kernels, and the tests that run them (G: th
   band_fit_matrix_kernel                strips of 16      G test_mixed_launch_fit_global[1-True]; test_band_gpu.py::test_band_64_symbol_matrix
   band_global_kernel                    strips of 16      G test_mixed_launch_fit_global[2-False]; test_band_gpu.py::test_band_shapes
   band_global_matrix_kernel             strips of 16      G test_mixed_launch_fit_global[2-True]; test_band_gpu.py::test_band_blosum62[2]
+  (option "extend" on a global run: test_extend_gpu.py, E)
+  extend_kernel                         1 .. 4            E test_extend_grid_shapes[False-*], test_extend_grid_walks[False-*], test_extend_kats
+  extend_wide_kernel                    5 .. 16           E test_extend_grid_shapes[False-*], test_extend_grid_walks[False-*]
+  long_extend_kernel                    strips of 16      E test_extend_mixed_launch[False]; strict: test_extend_long_reads
+  extend_matrix_kernel                  1 .. 4            E test_extend_grid_shapes[True-*], test_extend_grid_walks[True-*]
+  extend_matrix_wide_kernel             5 .. 16           E test_extend_grid_shapes[True-*], test_extend_grid_walks[True-*]
+  long_extend_matrix_kernel             strips of 16      E test_extend_mixed_launch[True]; strict: test_extend_long_read_with_a_matrix_strict_ties
+  band_extend_kernel                    strips of 16      E test_extend_band_geometry; strict: test_extend_band_maximum_on_a_window_edge, test_extend_band_shapes_and_matrix
+  band_extend_matrix_kernel             strips of 16      E test_extend_mixed_launch[True]; strict: test_extend_band_shapes_and_matrix
+  (option "xdrop" on an extend run: test_xdrop_gpu.py, X)
+  long_xdrop_kernel                     strips of 16      X test_xdrop_hand_derivable[0], test_xdrop_strip_edges; strict: test_xdrop_random_tails[1-0]
+  long_xdrop_matrix_kernel              strips of 16      X test_xdrop_mixed_launch[True-0]; strict: test_xdrop_matrix_strict_ties[0]
+  band_xdrop_kernel                     strips of 16      X test_xdrop_hand_derivable[64 / 16]; strict: test_xdrop_random_tails[1-64 / 16]
+  band_xdrop_matrix_kernel              strips of 16      X test_xdrop_mixed_launch[True-64]; strict: test_xdrop_matrix_strict_ties[64]
+  (option "band_adapt" on a banded extend run: test_adapt_gpu.py, A)
+  band_adapt_kernel                     strips of 16      A test_adapt_tie_rule; strict: test_adapt_drift[*-1], test_adapt_centre_stands_still[1], test_adapt_ties_and_the_rerun[1]
+  band_adapt_matrix_kernel              strips of 16      A test_adapt_mixed_launch[True]; strict: test_adapt_matrix_strict_ties
+  band_adapt_xdrop_kernel               strips of 16      A test_adapt_xdrop_planted_head; strict: test_adapt_xdrop_diverging_tail
+  band_adapt_xdrop_matrix_kernel        strips of 16      A test_adapt_mixed_launch_xdrop[True]; strict: test_adapt_matrix_strict_ties
 
   traceback kernel (sw_affine_traceback_...)              run by
   kernel                                                  G test_grid_walks[0-*] (walks of several tiles); test_affine_gpu.py
@@ -38,6 +59,9 @@ The 24 sweep kernels and 9 traceback kernels, and the tests that run them (G: th
   band_kernel                                             test_band_gpu.py::test_band_edges[0]; G test_c99_shim_sets_long_reads_and_band
   band_fit_kernel                                         G test_mixed_launch_fit_global[1-*]; test_band_gpu.py::test_band_edges[1]
   band_global_kernel                                      G test_mixed_launch_fit_global[2-*]; test_band_gpu.py::test_band_edges[2]
+  band_adapt_global_kernel                                A every test of test_adapt_gpu.py but the scores_only case
+  (an extend run is walked by global_kernel, long_global_kernel and band_global_kernel, started at cells other than (m, n):
+  E test_extend_grid_walks, test_extend_long_reads, test_extend_band_maximum_on_a_window_edge)
 
 Each narrow and wide sweep kernel holds one body per (R, tie order): 16 x 3 modes x 2 (plain / matrix) x 2 tie orders = 192
 bodies.  GRID_PARAMS below times the 16 classes of affine_grid_cases.RS is that grid; tests/test_affine_grid_cpu.py checks it.

@@ -10,7 +10,7 @@ The eight extend sweeps and the tests that run them (the table of tests/test_aff
   long_extend_kernel                    strips of 16      test_extend_long_reads, test_extend_mixed_launch[False]
   extend_matrix_kernel                  1 .. 4            test_extend_grid_shapes[True-*], test_extend_grid_walks[True-*]
   extend_matrix_wide_kernel             5 .. 16           test_extend_grid_shapes[True-*], test_extend_grid_walks[True-*]
-  long_extend_matrix_kernel             strips of 16      test_extend_mixed_launch[True]
+  long_extend_matrix_kernel             strips of 16      test_extend_mixed_launch[True], test_extend_long_read_with_a_matrix_strict_ties
   band_extend_kernel                    strips of 16      test_extend_band_maximum_on_a_window_edge, test_extend_band_geometry
   band_extend_matrix_kernel             strips of 16      test_extend_band_shapes_and_matrix, test_extend_mixed_launch[True]
 
@@ -239,6 +239,21 @@ def test_extend_mixed_launch(ctx, matrix):
     assert expb != exp and all(expb[(r, q)] == exp[(r, q)] for r in range(2) for q in range(2))      # the band applies to the long read
     b = _run(ctx, refs, reads, sc, 0, w, mat)
     u.check(b, refs, reads, expb, GLOBAL)
+    b.free()
+
+
+def test_extend_long_read_with_a_matrix_strict_ties(ctx):
+    """sw_affine_sweep_long_extend_matrix_kernel in the strict tie order (test_extend_mixed_launch[True] runs the serial one):
+    the smallest pair of two strips"""
+    rng = random.Random(9967)
+    mat, sc = gc.score_matrix(), gc.SHAPE_SCORES[True]
+    ref = u.rand(rng, 1060, gc.MATRIX_DRAW)
+    read = gc.mutate(rng, ref, gc.MATRIX_DRAW, 0.04, 0.004)[:1025]
+    read += u.rand(rng, 1025 - len(read), gc.MATRIX_DRAW)
+    want = _extend(ref, read, sc, 0, 1, mat)
+    assert want[0] > 0 and want[2][0][0] > 1024                   # (the maximum is in the second strip)
+    b = _run(ctx, [ref], [read], sc, 1, 0, mat)
+    u.check_pair(b, 0, want, GLOBAL, 1025)
     b.free()
 
 

@@ -10,9 +10,9 @@ has 3 strips or fewer.
 
   sweep kernel (sw_affine_sweep_...)    run by
   long_xdrop_kernel                     test_xdrop_hand_derivable[0], test_xdrop_random_tails[*-0], test_xdrop_strip_edges, ...
-  long_xdrop_matrix_kernel              test_xdrop_mixed_launch[True-0]
+  long_xdrop_matrix_kernel              test_xdrop_mixed_launch[True-0], test_xdrop_matrix_strict_ties[0]
   band_xdrop_kernel                     test_xdrop_hand_derivable[64 / 16], test_xdrop_random_tails[*-64 / 16], test_xdrop_mixed_launch[False-64]
-  band_xdrop_matrix_kernel              test_xdrop_mixed_launch[True-64]
+  band_xdrop_matrix_kernel              test_xdrop_mixed_launch[True-64], test_xdrop_matrix_strict_ties[64]
 
 The comparison's width has no test: best(s) - seam(s) <= |gap_open| + 1024 (s + 1) |gap| < 2^31 within the bounds a run is
 held to (DESIGN.md 8h has the proof), so no input reaches a difference that an int32 comparison would get wrong."""
@@ -183,6 +183,22 @@ def test_xdrop_mixed_launch(ctx, matrix, w):
     assert b.ref_sites_packed()[0] == (total, 0, sorted([a for e in want for a in e[1]], key=lambda t: t[0]))
     assert b.timing().cells == sum(len(q) * len(ref) for q in reads)              # nominal: a stopped pair counts in full
     b.free()
+
+
+@pytest.mark.parametrize("w", [0, 64])
+def test_xdrop_matrix_strict_ties(ctx, w):
+    """sw_affine_sweep_long_xdrop_matrix_kernel and _band_xdrop_matrix_kernel in the strict tie order (test_xdrop_mixed_launch
+    runs the serial one): the mixed launch's first read alone, on either side of its one difference"""
+    ref, reads = _mixed(True)
+    mat, read = gc.score_matrix(), reads[0]
+    d = _differences(ref, read, w, mat, 1)
+    assert len(d) == 1 and d[0] >= 1
+    for X, rows in ((d[0] - 1, 1024), (d[0], len(read))):
+        want = xr.align(ref, read, SC, X, w, 1, mat)
+        assert want[3] == rows
+        b = _run(ctx, [ref], [read], X, 1, w, mat)
+        _check_pair(b, 0, want, (w, X))
+        b.free()
 
 
 # 6 -- ties and the exact-size re-run (7: and the strict tie mode)
