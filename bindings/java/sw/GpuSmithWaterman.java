@@ -46,6 +46,9 @@ public class GpuSmithWaterman
 	static native void nativeSetXdrop( long ctx , int xdrop ) ;
 	/** the band of a banded seed extension follows the alignment: 1 on, 0 off (include/swmi.h: option "band_adapt") */
 	static native void nativeSetBandAdapt( long ctx , int bandAdapt ) ;
+	/** two-piece gaps: alignScores { match , mismatch , gap , gapOpen , gap2 , gapOpen2 } -- a gap of length k costs
+	 * max( gapOpen + k * gap , gapOpen2 + k * gap2 ) on a global or extend run; gapOpen2 0: off (include/swmi.h: option "gap_open2") */
+	static native void nativeSetGap2( long ctx , int gapOpen2 , int gap2 ) ;
 	/** substitution scores on the context: alphabet = n ISO-8859-1 symbols, scores = n * n, row = read base; null clears */
 	static native void nativeSetScoreMatrix( long ctx , byte[] alphabet , int[] scores ) ;
 	static native void nativeFreeBatch( long ctx , long batch ) ;
@@ -271,8 +274,10 @@ public class GpuSmithWaterman
 			NativeContext nc = context() ;
 			long ctx = nc.handle ;
 			// alignScores may carry a fourth entry, gapOpen (<= 0): affine gaps; three entries keep the linear scoring
-			if( sc.length != 3 && sc.length != 4 ) throw new IllegalArgumentException( "alignScores needs 3 or 4 entries: " + sc.length ) ;
-			nativeSetGapOpen( ctx , sc.length == 4 ? sc[3] : 0 ) ;
+			// ... and a fifth and sixth, gap2 and gapOpen2 (<= 0): two-piece gaps, with ALIGN_GLOBAL
+			if( sc.length != 3 && sc.length != 4 && sc.length != 6 ) throw new IllegalArgumentException( "alignScores needs 3, 4 or 6 entries: " + sc.length ) ;
+			nativeSetGapOpen( ctx , sc.length >= 4 ? sc[3] : 0 ) ;
+			nativeSetGap2( ctx , sc.length == 6 ? sc[5] : 0 , sc.length == 6 ? sc[4] : 0 ) ;
 			nativeSetAlignMode( ctx , ALIGN_MODE ) ;
 			nativeSetLongReads( ctx , LONG_READS ? 1 : 0 ) ;
 			nativeSetBand( ctx , BAND ) ;

@@ -91,6 +91,13 @@ JNIEXPORT void JNICALL Java_sw_GpuSmithWaterman_nativeSetBandAdapt(JNIEnv *env, 
     if (swmi_shim_set_band_adapt((swmi_ctx *)(intptr_t)ctx, band_adapt, err, sizeof err) != SWMI_OK) throw_msg(env, err);
 }
 
+/* two-piece gaps on this context from now on: gapOpen2 != 0 on, 0 off */
+JNIEXPORT void JNICALL Java_sw_GpuSmithWaterman_nativeSetGap2(JNIEnv *env, jclass cls, jlong ctx, jint gap_open2, jint gap2) {
+    char err[640];
+    (void)cls;
+    if (swmi_shim_set_gap2((swmi_ctx *)(intptr_t)ctx, gap_open2, gap2, err, sizeof err) != SWMI_OK) throw_msg(env, err);
+}
+
 /* a substitution score matrix on this context from now on: alphabet = n ISO-8859-1 symbols, scores = int[n * n], row = read base;
  * alphabet == null clears it */
 JNIEXPORT void JNICALL Java_sw_GpuSmithWaterman_nativeSetScoreMatrix(JNIEnv *env, jclass cls, jlong ctx, jbyteArray alphabet,

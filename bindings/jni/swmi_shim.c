@@ -71,6 +71,15 @@ int swmi_shim_set_xdrop(swmi_ctx *ctx, int32_t xdrop, char *err, size_t err_len)
     return SWMI_OK;
 }
 
+int swmi_shim_set_gap2(swmi_ctx *ctx, int32_t gap_open2, int32_t gap2, char *err, size_t err_len) {
+    int rc;
+    if (!ctx) return shim_fail(SWMI_ERR_INVALID, err, err_len, "nativeSetGap2", "context handle is 0");
+    if (gap_open2 > 0 || gap2 > 0) return shim_fail(SWMI_ERR_INVALID, err, err_len, "nativeSetGap2", "gap_open2 and gap2 must be <= 0");
+    if ((rc = swmi_set_option(ctx, "gap2", gap2)) != SWMI_OK || (rc = swmi_set_option(ctx, "gap_open2", gap_open2)) != SWMI_OK)
+        return shim_fail(rc, err, err_len, "nativeSetGap2", swmi_last_error());
+    return SWMI_OK;
+}
+
 int swmi_shim_set_band_adapt(swmi_ctx *ctx, int32_t band_adapt, char *err, size_t err_len) {
     int rc;
     if (!ctx) return shim_fail(SWMI_ERR_INVALID, err, err_len, "nativeSetBandAdapt", "context handle is 0");

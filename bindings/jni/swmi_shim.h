@@ -53,6 +53,11 @@ int swmi_shim_set_xdrop(swmi_ctx *ctx, int32_t xdrop, char *err, size_t err_len)
  * extend run is then refused (SWMI_ERR_UNSUPPORTED).  0 (the default): off.  Any other value is SWMI_ERR_INVALID and leaves the
  * context as it was. */
 int swmi_shim_set_band_adapt(swmi_ctx *ctx, int32_t band_adapt, char *err, size_t err_len);
+/* nativeSetGap2: two-piece gaps from then on (swmi_set_option "gap_open2" and "gap2"): with gap_open2 != 0 a gap of length k costs
+ * max(gapOpen + k * gap, gap_open2 + k * gap2) on a global or extend run; any other run is then refused (SWMI_ERR_UNSUPPORTED).
+ * gap_open2 = 0 (the default): one-piece gaps, gap2 is not read.  A value > 0 is SWMI_ERR_INVALID and leaves the context as it was
+ * (both values: gap2 is checked first, and set only with a valid gap_open2). */
+int swmi_shim_set_gap2(swmi_ctx *ctx, int32_t gap_open2, int32_t gap2, char *err, size_t err_len);
 
 /* nativeSetScoreMatrix: a substitution score matrix on this context (swmi_set_score_matrix): `alphabet` = n symbols narrowed to
  * bytes (ISO-8859-1), `scores` = n * n entries, row = read base, column = reference base (n_scores must be n * n).  n = 0 clears

@@ -238,6 +238,29 @@ void        swmi_default_params(swmi_params *p);
  *                be, and a table of NS window centres -- must fit max_workspace_bytes.  swmi_pair_band_window tells the windows a
  *                pair's sweep used.  A run (async runs and stream slots included) takes the value set when it was asked for
  *                (DESIGN.md section 8i).
+ * gap_open2 (default 0 = off and no change; a value > 0 or < INT32_MIN is SWMI_ERR_INVALID and leaves the context as it was) and
+ * gap2 (default 0; a value > 0 or < INT32_MIN is SWMI_ERR_INVALID likewise): TWO-PIECE AFFINE GAPS (minimap2's scoring, ksw2's extd2)
+ *                on global and extend runs.  A run is a two-piece run iff gap_open2 != 0; gap2 is then the second piece's per-base
+ *                extension, and with gap_open2 = 0 gap2 is not read.  With o1 = gap_open, e1 = gap, o2 = gap_open2, e2 = gap2 a gap
+ *                of length k costs  max(o1 + k * e1, o2 + k * e2)  -- piece 1 cheap to open and steep, piece 2 dear to open and flat,
+ *                though no order between the pieces is required and o1 = 0 is allowed.  The recurrence is global mode's (no floor at
+ *                0) with each gap state twice, p = 1, 2:
+ *                  Ep(i,j) = max(H(i,j-1) + op + ep, Ep(i,j-1) + ep),  xEp = 1 iff the extension is strictly better;  Fp, xFp with row i-1
+ *                  E = max(E1, E2), pE = 1 iff E2 > E1 (piece 1 wins a tie, in both tie modes);  F, pF likewise
+ *                  H from E, F and the diagonal by the two tie chains, unchanged (serial '>=' a > i > d, strict '>' d > i > a)
+ *                  H(0,0) = 0,  H(0,j) = max(o1 + j * e1, o2 + j * e2),  H(i,0) the same in i;  the gap states of row 0 and column 0
+ *                  are H + op, so that the first real cell opens (x = 0, value H + op + ep)
+ *                The walk is the global walk with five states: H reads the direction; a deletion enters E2 iff pE, else E1; an
+ *                insertion F2 iff pF, else F1; a gap state stays while its own x bit is set.  An extend run lists its tied maximum
+ *                cells in extend's order and walks each.  Scope: align_mode global with and without extend, reads of every length
+ *                (long_reads, with and without band), both tie modes; scores_only, device_strings, zero_copy, cell_cap, the exact-size
+ *                re-run and chunking under max_workspace_bytes apply as to any global run, and swmi_batch_mode reports 3.  With
+ *                gap_open2 != 0 these are SWMI_ERR_UNSUPPORTED before anything is launched: align_mode local or fit; a score matrix;
+ *                xdrop > 0; band_adapt = 1.  The bounds are global mode's, read with |gap_open| = max(|o1|, |o2|) and |gap| =
+ *                max(|e1|, |e2|); S also covers |o2| and |e2|; |o2|, |e2| <= 2^20 and gap2 <= 0.  A pair's direction field and seam row
+ *                are twice the one-piece size (the chunking and the refusal of a pair over max_workspace_bytes see the doubled field).
+ *                Unlike gap_open, both are run modes: a run (async runs and stream slots included) takes the values set when it was
+ *                asked for.
  * Further knobs: spin_us (how long a run polls its stream before it blocks, default 2000); col_chunks (0 automatic,
  * 1 never, N > 1 force up to N column chunks per pair: a launch of few pairs with long references is swept by several
  * wavefronts per pair -- a read of more than 256 rows by several strip pipelines); debug_strip_spins / debug_reverse_strips (tests of the strip pipeline's give-up path);

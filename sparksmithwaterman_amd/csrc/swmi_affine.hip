@@ -71,8 +71,13 @@
 //   extend run under option "band_adapt" (DESIGN.md 8i), ADAPT = 1: the window of a strip is placed around the column of the seam
 //   row's maximum instead of around j = i; the sweep leaves the centres in a table behind the pair's fields, the walk reads them.
 //
-// How the 50 kernels are made: the 40 sweeps are aff_sweep_entry<RLO, RHI, MATRIX, MODE, LONG, BAND, XDROP, ADAPT> over one block function
-//   (aff_block8); the 10 tracebacks are aff_traceback<MODE, LONG, BAND, ADAPT>, where !LONG is the walk with one strip and !BAND the
+// sw_affine_sweep2_{global,extend}[_wide]_kernel, sw_affine_sweep2_{long,band}_{global,extend}_kernel,
+// sw_affine_traceback2[_long|_band]_global_kernel: global and extend runs under option "gap_open2" (DESIGN.md 8j), TWO = 1: a gap of
+//   length k costs max(gap_open + k * gap, gap_open2 + k * gap2).  Two more gap states per cell, a second 4-bit plane in the field
+//   (blocks interleave the planes), 16-byte seam entries (H, F1, F2), a walk through five states.
+//
+// How the 61 kernels are made: the 48 sweeps are aff_sweep_entry<RLO, RHI, MATRIX, MODE, LONG, BAND, XDROP, ADAPT, TWO> over one block function
+//   (aff_block8); the 13 tracebacks are aff_traceback<MODE, LONG, BAND, ADAPT, TWO>, where !LONG is the walk with one strip and !BAND the
 //   walk whose windows are the whole reference.  One macro defines the sweeps, one the tracebacks; the launchers pick a kernel
 //   from typed tables.  The per-pair sweep is two thin bodies, aff_sweep_pair and aff_sweep_long_pair<.., BAND> (the one strip
 //   loop, banded or not), over shared pieces: vrows and the cell list as functions of values, the row load, the block store
@@ -112,6 +117,8 @@ __shared__ int aff_mtab[SWMI_MAT_NN_MAX * SWMI_MAT_NN_MAX];
 struct AffSeam {
     int h, f;              // lanes 0..7: (H, F) of the row above the strip at the 8 columns lane 0 takes in this block
     int2 *row;             // the pair's seam row: (H, F) per column
+    int f2;                // TWO: F2 of that row (f is F1)
+    int4 *row4;            // TWO: the pair's seam row, (H, F1, F2, -) per column: 16-byte entries, one load and one store each
     uint32_t wlane;        // the lane that writes it (63), none in the read's last strip
     uint32_t coff;         // BAND: the columns left of the strip's window (`row` starts at the window, cells are listed with global columns)
 };
@@ -126,6 +133,10 @@ struct AffState {
     int f_last;            // F of the lane's last row at its previous column (what lane l+1 reads as F(i-1, j))
     int thr;               // wave-uniform running maximum (starts at 1: a maximum of 0 is the degenerate case)
     uint32_t cnt;          // wave-uniform number of cells equal to thr
+    // TWO (two-piece gaps): e and f_last are piece 1's E and F; piece 2's, and the codes of plane 1
+    int e2[R];
+    uint32_t acc2[R];
+    int f2_last;
 };
 
 // 8 anti-diagonal steps t0 .. t0+7 (a lane outside its column range keeps its state).  The steps are a loop, not unrolled:
@@ -138,12 +149,20 @@ struct AffState {
 // LONG: one strip of a long read -- lane 0 is fed from Z (every strip, the first one too: its Z holds row 0 of the mode) and lane
 // Z.wlane leaves (H, F) of its last row in the seam row
 // BAND (with LONG): the strip sweeps a window of the reference -- n is the window's length, columns count from its first one
-template <int R, bool STRICT, bool MATRIX, int MODE, bool LONG = false, bool BAND = false>
+// TWO (option "gap_open2", global and extend runs): a gap of length k costs max(o + k*e, o2 + k*e2).  Each gap state
+//   exists once per piece -- (S.e, S.f_last) piece 1, (S.e2, S.f2_last) piece 2 -- E = max(E1, E2), F = max(F1, F2), piece 1 on a
+//   tie, and H is taken from E, F and the diagonal as before.  The cell leaves a second 4-bit code in S.acc2 (plane 1 of the
+//   field): bit 0 pE (E is E2), bit 1 pF, bit 2 xE2, bit 3 xF2; plane 0 is the one-piece code with xE1, xF1 in bits 2 and 3.
+//   Lane l+1 receives F2 of the last row by one more wave_shr1.  Row 0 is max(o + j*e, o2 + j*e2), F1(0,j) := H + o, F2 := H + o2.
+template <int R, bool STRICT, bool MATRIX, int MODE, bool LONG = false, bool BAND = false, bool TWO = false>
 __device__ __forceinline__ void aff_block8(AffState<R> &S, const uint2 rw, const uint32_t t0, const uint32_t lane,
                                            const uint32_t n, const uint32_t row0, const uint32_t vrows,
                                            const int o, const int e, const int vmat, const int vmis,
-                                           uint2 *__restrict__ cells, const uint32_t ccap, const AffSeam &Z = AffSeam{}) {
+                                           uint2 *__restrict__ cells, const uint32_t ccap, const AffSeam &Z = AffSeam{},
+                                           const int o2 = 0, const int e2 = 0) {
+    static_assert(!TWO || (AFF_ROW0_GAPS(MODE) && !MATRIX), "two-piece gaps: global and extend runs without a score matrix");
     const int oe = o + e;
+    const int oe2 = o2 + e2;                                     // (TWO)
 #pragma unroll 1
     for (uint32_t s = 0; s < 8; ++s) {
         const uint32_t wsel = s < 4 ? rw.x : rw.y;
@@ -151,9 +170,11 @@ __device__ __forceinline__ void aff_block8(AffState<R> &S, const uint2 rw, const
         const int feed = MATRIX ? (int)aff_mkey[fb] : (int)fb;  // (wave-uniform: lane 0's column)
         S.rb = wave_shr1(feed, S.rb);
         int nh, nf;
+        int nf2 = 0;                                             // (TWO)
         if constexpr (LONG) {
             nh = wave_shr1(__builtin_amdgcn_readlane(Z.h, (int)s), S.h[R - 1]);
             nf = wave_shr1(__builtin_amdgcn_readlane(Z.f, (int)s), S.f_last);
+            if constexpr (TWO) nf2 = wave_shr1(__builtin_amdgcn_readlane(Z.f2, (int)s), S.f2_last);
         } else if constexpr (MODE == AFF_LOCAL) {
             nh = wave_shr1_zero(S.h[R - 1]);
             nf = wave_shr1_zero(S.f_last);
@@ -162,14 +183,17 @@ __device__ __forceinline__ void aff_block8(AffState<R> &S, const uint2 rw, const
         if constexpr (MODE != AFF_LOCAL && !LONG) {
             // lane 0 reads row 0 of the mode: H(0,j) = 0 (fit) or o + j*e (global), F(0,j) := H(0,j) + o
             // (unsigned arithmetic: lane 0 runs up to 70 columns past n, where the value is not used)
-            const int h0 = AFF_ROW0_GAPS(MODE) ? (int)((uint32_t)o + (c0 + 1u) * (uint32_t)e) : 0;
+            int h0 = AFF_ROW0_GAPS(MODE) ? (int)((uint32_t)o + (c0 + 1u) * (uint32_t)e) : 0;
+            if constexpr (TWO) h0 = max(h0, (int)((uint32_t)o2 + (c0 + 1u) * (uint32_t)e2));
             nh = wave_shr1(h0, S.h[R - 1]);
             nf = wave_shr1((int)((uint32_t)h0 + (uint32_t)o), S.f_last);
+            if constexpr (TWO) nf2 = wave_shr1((int)((uint32_t)h0 + (uint32_t)o2), S.f2_last);
         }
         const bool inr = c0 < n;
         int mrow = MODE == AFF_LOCAL ? -1 : (MODE == AFF_EXTEND ? INT32_MIN : 0);
         if (inr) {
             int diag = S.nh_prev, up = nh, fup = nf;
+            int fup2 = nf2;                                      // (TWO)
             uint32_t sh = 4u * s;
             const uint32_t rkey = (uint32_t)S.rb, rlo = rkey & 0xFFFFu;
 #pragma unroll
@@ -197,6 +221,22 @@ __device__ __forceinline__ void aff_block8(AffState<R> &S, const uint2 rw, const
                     else        d = hv == 0 ? AFF_STOP : (dg == hv ? AFF_DIAG : (fn == hv ? AFF_INS : AFF_DEL));
                     // x bits from the sign of the difference (no compare mask): |values| < 2^30 + 2^21, the difference fits
                     code = d | (((uint32_t)(t1 - t2) >> 31) << 2) | (((uint32_t)(u1 - u2) >> 31) << 3);
+                } else if constexpr (TWO) {
+                    // en, fn: piece 1's states (what S.e and fup carry on); ev, fv: E and F
+                    const int t3 = left + oe2, t4 = S.e2[k] + e2;
+                    const int u3 = up + oe2, u4 = fup2 + e2;
+                    en = max(t1, t2);
+                    fn = max(u1, u2);
+                    const int en2 = max(t3, t4), fn2 = max(u3, u4);
+                    const int ev = max(en, en2), fv = max(fn, fn2);
+                    hv = max(max(ev, fv), dg);
+                    uint32_t d;
+                    if (STRICT) d = ev == hv ? AFF_DEL : (fv == hv ? AFF_INS : AFF_DIAG);
+                    else        d = dg == hv ? AFF_DIAG : (fv == hv ? AFF_INS : AFF_DEL);
+                    code = d | (t2 > t1 ? 4u : 0u) | (u2 > u1 ? 8u : 0u);
+                    S.acc2[k] |= ((en2 > en ? 1u : 0u) | (fn2 > fn ? 2u : 0u) | (t4 > t3 ? 4u : 0u) | (u4 > u3 ? 8u : 0u)) << sh;
+                    S.e2[k] = en2;
+                    fup2 = fn2;
                 } else {
                     en = max(t1, t2);
                     fn = max(u1, u2);
@@ -217,7 +257,9 @@ __device__ __forceinline__ void aff_block8(AffState<R> &S, const uint2 rw, const
                 else                                 { if ((uint32_t)k == vrows) mrow = hv; }
             }
             S.f_last = fup;
-            if constexpr (LONG) { if (lane == Z.wlane) Z.row[c0] = make_int2(S.h[R - 1], fup); }
+            if constexpr (TWO) S.f2_last = fup2;
+            if constexpr (LONG && TWO) { if (lane == Z.wlane) Z.row4[c0] = make_int4(S.h[R - 1], fup, fup2, 0); }
+            else if constexpr (LONG) { if (lane == Z.wlane) Z.row[c0] = make_int2(S.h[R - 1], fup); }
         }
         S.nh_prev = nh;
         if constexpr (AFF_ROW_M_ONLY(MODE)) {
@@ -276,10 +318,11 @@ __device__ __forceinline__ AffCells aff_cell_list(const FillArgs &A, const PairD
 
 // The two pieces that read or write the lane's state S are shared as TEXT, not as functions.  As an inlined function -- handed
 // S, its arrays, a pointer to them, or one row at a time by value -- either one changes the register allocation of the sweeps
-// (DESIGN.md 8e); the same statements expanded in place cannot.  Both expect R, MATRIX, MODE, S, A, o and the names below.
+// (DESIGN.md 8e); the same statements expanded in place cannot.  Both expect R, MATRIX, MODE, TWO, S, A, o, o2, e2 and the names below.
 // AFF_LOAD_ROWS (readw, m, row0, nn): the lane's rows row0 + 1 .. row0 + R (global row indices) -- their base codes, with MATRIX
 //   their row words class * (n+1) * 4 | hi << 16 (a read base inside the alphabet takes hi = 0x3FF, never a reference key's;
 //   pad rows: class n, hi 0xFFFF) -- and H and E at column 0: 0 (local), else H(i,0) = o + i*e, E(i,0) := H(i,0) + o
+//   TWO: H(i,0) = max(o + i*e, o2 + i*e2), E1(i,0) := H(i,0) + o, E2(i,0) := H(i,0) + o2
 #define AFF_LOAD_ROWS                                                                                         \
     _Pragma("unroll") for (int k = 0; k < R; ++k) {                                                           \
         const uint32_t row = row0 + (uint32_t)k;                                                              \
@@ -294,13 +337,17 @@ __device__ __forceinline__ AffCells aff_cell_list(const FillArgs &A, const PairD
             S.e[k] = 0;                                                                                       \
         } else {                                                                                              \
             S.h[k] = o + (int)(row + 1u) * A.gap;                                                             \
+            if constexpr (TWO) S.h[k] = max(S.h[k], o2 + (int)(row + 1u) * e2);                               \
             S.e[k] = S.h[k] + o;                                                                              \
+            if constexpr (TWO) S.e2[k] = S.h[k] + o2;                                                         \
         }                                                                                                     \
     }
 // AFF_STORE_BLOCK (dir, w, lane): block w of a field, the codes of the lane's R rows, 256 contiguous bytes per row slot
+//   TWO: the two planes of a block lie one behind the other -- dword ((w * 2 + plane) * R + k) * 64 + lane
 #define AFF_STORE_BLOCK                                                                                       \
-    uint32_t *__restrict__ dst = dir + (uint64_t)w * R * WAVE + lane;                                         \
-    _Pragma("unroll") for (int k = 0; k < R; ++k) dst[k * WAVE] = S.acc[k];
+    uint32_t *__restrict__ dst = dir + (uint64_t)w * (TWO ? 2 : 1) * R * WAVE + lane;                         \
+    _Pragma("unroll") for (int k = 0; k < R; ++k) dst[k * WAVE] = S.acc[k];                                   \
+    if constexpr (TWO) { _Pragma("unroll") for (int k = 0; k < R; ++k) dst[(R + k) * WAVE] = S.acc2[k]; }
 // AFF_PAIR_OUT(NCELLS, XFLAGS) (lane, pd, ccap): the pair's PairOut.  NCELLS is what the degenerate case counts -- the pair's m * n cells
 //   or, under option "band", those inside the band -- and is evaluated in that branch only.  Text as well: as a function that
 //   takes the count as a value it changes the short local sweeps, as one that picks it inside the banded local ones
@@ -321,8 +368,9 @@ __device__ __forceinline__ AffCells aff_cell_list(const FillArgs &A, const PairD
         A.out[pd.out_id] = po;                                                                                \
     }
 
-template <int R, bool STRICT, bool MATRIX, int MODE>
-__device__ __forceinline__ void aff_sweep_pair(const FillArgs &A, const int o, const PairDesc pd, const uint32_t lane, const uint32_t nn) {
+template <int R, bool STRICT, bool MATRIX, int MODE, bool TWO = false>
+__device__ __forceinline__ void aff_sweep_pair(const FillArgs &A, const int o, const PairDesc pd, const uint32_t lane, const uint32_t nn,
+                                               const int o2 = 0, const int e2 = 0) {
     const SeqDesc rd = A.refs[pd.ref_id];
     const SeqDesc qd = A.reads[pd.read_id];
     const uint32_t n = rd.len, m = qd.len;
@@ -339,6 +387,7 @@ __device__ __forceinline__ void aff_sweep_pair(const FillArgs &A, const int o, c
     AffState<R> S;
     AFF_LOAD_ROWS
     S.rb = 0; S.nh_prev = 0; S.f_last = 0;                       // (nh_prev of lane 0: H(0,0) = 0 in every mode)
+    if constexpr (TWO) S.f2_last = 0;
     S.thr = MODE == AFF_LOCAL ? 1 : INT32_MIN; S.cnt = 0;
     for (uint32_t w = 0; w < W; ++w) {
         const uint32_t t0 = 8u * w;
@@ -346,6 +395,12 @@ __device__ __forceinline__ void aff_sweep_pair(const FillArgs &A, const int o, c
         const uint2 rw = *reinterpret_cast<const uint2 *>(refw + (t0 >> 2));
 #pragma unroll
         for (int k = 0; k < R; ++k) S.acc[k] = 0u;
+        if constexpr (TWO) {
+#pragma unroll
+            for (int k = 0; k < R; ++k) S.acc2[k] = 0u;
+            aff_block8<R, STRICT, MATRIX, MODE, false, false, true>(S, rw, t0, lane, n, row0, vrows, o, A.gap, A.match, A.mismatch, cells, ccap,
+                                                                    AffSeam{}, o2, e2);
+        } else
         aff_block8<R, STRICT, MATRIX, MODE>(S, rw, t0, lane, n, row0, vrows, o, A.gap, A.match, A.mismatch, cells, ccap);
         AFF_STORE_BLOCK
     }
@@ -392,10 +447,18 @@ __device__ __forceinline__ void aff_sweep_pair(const FillArgs &A, const int o, c
 //     before the strip stores anything
 //   - every strip's field has the fixed stride swmi_aff_adapt_strip_words: the window is not known before the strip above ends
 //   - lane 0 leaves cen in the pair's window table behind the fields (a vector store), for the traceback and the host
-template <bool STRICT, bool MATRIX, int MODE, bool BAND, bool XDROP = false, bool ADAPT = false>
+// TWO (option "gap_open2"): the seam row carries (H, F1, F2) per column in 16-byte entries (int4, the fourth word
+//   unused), so that lane 0's load and lane 63's store stay one instruction each; the pair's seam row is 4 n dwords and starts on
+//   a 16-byte boundary (every pair of such a run has a row of that kind).  The in-place argument above counts COLUMNS, not bytes,
+//   and an entry is read and written whole: in strip sx lane 0 loads the entries of columns clo + t0 .. clo + t0 + 7 at step t0,
+//   lane 63 stores the entry of column clo + t - 63 at step t, so every entry is read at least 63 steps before this strip
+//   overwrites it, as it stands for 8-byte entries.  nh_prev reads word x of the entry of column clo - 1.  A strip's field is
+//   twice swmi_aff_strip_words of its window; under BAND a cell outside reads SWMI_AFF_BAND_NEG in all five values.
+template <bool STRICT, bool MATRIX, int MODE, bool BAND, bool XDROP = false, bool ADAPT = false, bool TWO = false>
 __device__ __forceinline__ void aff_sweep_long_pair(const FillArgs &A, const int o, const PairDesc pd, const uint32_t lane, const uint32_t nn,
-                                                    const uint32_t wb, const uint32_t xd = 0u) {
+                                                    const uint32_t wb, const uint32_t xd = 0u, const int o2 = 0, const int e2 = 0) {
     static_assert(!ADAPT || (BAND && MODE == AFF_EXTEND), "band_adapt is an option of the banded strip sweeps of an extend run");
+    static_assert(!TWO || (!XDROP && !ADAPT), "two-piece gaps: not under xdrop or band_adapt");
     constexpr int R = SWMI_AFF_RMAX;
     constexpr int OUT = BAND && MODE != AFF_LOCAL ? SWMI_AFF_BAND_NEG : 0;
     const SeqDesc rd = A.refs[pd.ref_id];
@@ -409,8 +472,10 @@ __device__ __forceinline__ void aff_sweep_long_pair(const FillArgs &A, const int
     const uint32_t ccap = cl.cap;
     uint2 *__restrict__ cells = cl.p;
     int2 *const seam = reinterpret_cast<int2 *>(A.seam + pd.seam_off);
+    int4 *const seam4 = reinterpret_cast<int4 *>(A.seam + pd.seam_off);     // (TWO)
     AffSeam Z;
     Z.row = seam;
+    Z.row4 = seam4;
     uint32_t *__restrict__ dir = A.dir + pd.dir_off;
     uint64_t inband = 0ull;                                      // BAND: in-band cells with i <= m (the degenerate count)
     uint32_t stopped = 0u;                                       // XDROP: the strips swept of a pair that was stopped, else 0
@@ -470,17 +535,24 @@ __device__ __forceinline__ void aff_sweep_long_pair(const FillArgs &A, const int
             if (clo > 1u) {
 #pragma unroll
                 for (int k = 0; k < R; ++k) { S.h[k] = OUT; S.e[k] = OUT; }
+                if constexpr (TWO) {
+#pragma unroll
+                    for (int k = 0; k < R; ++k) S.e2[k] = OUT;
+                }
             }
         }
         S.rb = 0; S.f_last = 0;
+        if constexpr (TWO) S.f2_last = 0;
         // nh_prev of lane 0: H(1024 * sx, clo - 1)
         if constexpr (!BAND) S.nh_prev = MODE != AFF_LOCAL && sx ? o + (int)(sx * SWMI_AFF_MAX_READ) * A.gap : 0;
+        if constexpr (!BAND && TWO) { if (sx) S.nh_prev = max(S.nh_prev, o2 + (int)(sx * SWMI_AFF_MAX_READ) * e2); }
         if constexpr (BAND) {
             Z.row = seam + (clo - 1u);
+            if constexpr (TWO) Z.row4 = seam4 + (clo - 1u);
             Z.coff = clo - 1u;
         }
         Z.wlane = sx + 1u < NS ? 63u : 0xFFFFFFFFu;
-        if constexpr (!BAND) dir = A.dir + pd.dir_off + (uint64_t)sx * swmi_aff_strip_words(n);
+        if constexpr (!BAND) dir = A.dir + pd.dir_off + (uint64_t)sx * (TWO ? 2u : 1u) * swmi_aff_strip_words(n);
         if constexpr (ADAPT) dir = A.dir + pd.dir_off + (uint64_t)sx * astride;
         // the strip above has written its window of the seam row: its stores are in memory before this strip loads any of it
         if constexpr (!ADAPT) { if (sx) __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent"); }
@@ -501,8 +573,9 @@ __device__ __forceinline__ void aff_sweep_long_pair(const FillArgs &A, const int
             }
         }
         if constexpr (BAND) {
-            if (clo > 1u) S.nh_prev = !ADAPT || clo > plo ? seam[clo - 2u].x : OUT;   // (a vector load, behind the fence; ADAPT: a window that stood still)
+            if (clo > 1u) S.nh_prev = !ADAPT || clo > plo ? (TWO ? seam4[clo - 2u].x : seam[clo - 2u].x) : OUT;   // (a vector load, behind the fence; ADAPT: a window that stood still)
             else S.nh_prev = MODE != AFF_LOCAL && sx ? o + (int)(sx * SWMI_AFF_MAX_READ) * A.gap : 0;
+            if constexpr (TWO) { if (clo <= 1u && sx) S.nh_prev = max(S.nh_prev, o2 + (int)(sx * SWMI_AFF_MAX_READ) * e2); }
         }
         const uint32_t boff = clo - 1u, bsh = boff & 3u;         // (BAND) the window's first byte of the image
         const uint32_t *__restrict__ refb = refw + (boff >> 2);
@@ -520,7 +593,16 @@ __device__ __forceinline__ void aff_sweep_long_pair(const FillArgs &A, const int
             // aff_block8; strip 0 has clo = 1), below it the seam -- the true F, not the H + o stand-in of row 0
             const uint32_t c = t0 + lane;
             Z.h = AFF_ROW0_GAPS(MODE) ? (int)((uint32_t)o + (c + 1u) * (uint32_t)A.gap) : 0;
+            if constexpr (TWO) Z.h = max(Z.h, (int)((uint32_t)o2 + (c + 1u) * (uint32_t)e2));
             Z.f = MODE == AFF_LOCAL ? 0 : (int)((uint32_t)Z.h + (uint32_t)o);
+            if constexpr (TWO) {
+                Z.f2 = (int)((uint32_t)Z.h + (uint32_t)o2);
+                if (sx) {
+                    int4 v = make_int4(OUT, OUT, OUT, 0);
+                    if (lane < 8u && c < seam_end) v = Z.row4[c];
+                    Z.h = v.x; Z.f = v.y; Z.f2 = v.z;
+                }
+            } else
             if (sx) {
                 int2 v = make_int2(OUT, OUT);
                 if (lane < 8u && c < seam_end) v = Z.row[c];
@@ -528,10 +610,14 @@ __device__ __forceinline__ void aff_sweep_long_pair(const FillArgs &A, const int
             }
 #pragma unroll
             for (int k = 0; k < R; ++k) S.acc[k] = 0u;
-            aff_block8<R, STRICT, MATRIX, MODE, true, BAND>(S, rw, t0, lane, nw, row0, vrows, o, A.gap, A.match, A.mismatch, cells, ccap, Z);
+            if constexpr (TWO) {
+#pragma unroll
+                for (int k = 0; k < R; ++k) S.acc2[k] = 0u;
+            }
+            aff_block8<R, STRICT, MATRIX, MODE, true, BAND, TWO>(S, rw, t0, lane, nw, row0, vrows, o, A.gap, A.match, A.mismatch, cells, ccap, Z, o2, e2);
             AFF_STORE_BLOCK
         }
-        if constexpr (BAND && !ADAPT) dir += (uint64_t)W * R * WAVE;
+        if constexpr (BAND && !ADAPT) dir += (uint64_t)W * (TWO ? 2 : 1) * R * WAVE;
         if constexpr (ADAPT) { plo = clo; phi = clo + nw - 1u; }
     }
     AFF_PAIR_OUT(BAND ? inband : (uint64_t)m * n, XDROP ? stopped << SWMI_F_STRIPS_SHIFT : 0u)
@@ -542,12 +628,12 @@ __device__ __forceinline__ void aff_sweep_long_pair(const FillArgs &A, const int
 #undef AFF_PAIR_OUT
 
 // RLO..RHI: the rows per lane this instantiation of the kernel takes (the others' registers would cap its occupancy)
-template <int RLO, int RHI, bool STRICT, bool MATRIX, int MODE>
+template <int RLO, int RHI, bool STRICT, bool MATRIX, int MODE, bool TWO = false>
 __device__ __forceinline__ void aff_sweep_dispatch(const FillArgs &A, const int o, const PairDesc pd, const uint32_t R, const uint32_t lane,
-                                                   const uint32_t nn) {
+                                                   const uint32_t nn, const int o2 = 0, const int e2 = 0) {
     if constexpr (RLO <= RHI) {
-        if (R == (uint32_t)RLO) aff_sweep_pair<RLO, STRICT, MATRIX, MODE>(A, o, pd, lane, nn);
-        else aff_sweep_dispatch<RLO + 1, RHI, STRICT, MATRIX, MODE>(A, o, pd, R, lane, nn);
+        if (R == (uint32_t)RLO) aff_sweep_pair<RLO, STRICT, MATRIX, MODE, TWO>(A, o, pd, lane, nn, o2, e2);
+        else aff_sweep_dispatch<RLO + 1, RHI, STRICT, MATRIX, MODE, TWO>(A, o, pd, R, lane, nn, o2, e2);
     }
 }
 
@@ -555,9 +641,12 @@ __device__ __forceinline__ void aff_sweep_dispatch(const FillArgs &A, const int 
 // LONG: the strip sweep of reads longer than 1024 bases (RLO, RHI unused); BAND (with LONG): inside a band of half-width wb
 // XDROP (with LONG and AFF_EXTEND): the strip sweep under option "xdrop", threshold xd
 // ADAPT (with LONG, BAND and AFF_EXTEND): the banded strip sweep under option "band_adapt"
-template <int RLO, int RHI, bool MATRIX, int MODE = AFF_LOCAL, bool LONG = false, bool BAND = false, bool XDROP = false, bool ADAPT = false>
+// TWO (AFF_GLOBAL and AFF_EXTEND, no MATRIX, XDROP or ADAPT): two-piece gaps, the second piece's open o2 and extension e2
+template <int RLO, int RHI, bool MATRIX, int MODE = AFF_LOCAL, bool LONG = false, bool BAND = false, bool XDROP = false, bool ADAPT = false,
+          bool TWO = false>
 __device__ __forceinline__ void aff_sweep_entry(const FillArgs &A, const int o, const uint32_t *__restrict__ mat, const uint32_t nn,
-                                                const uint32_t wb = 0u, const uint32_t xd = 0u) {
+                                                const uint32_t wb = 0u, const uint32_t xd = 0u, const int o2 = 0, const int e2 = 0) {
+    static_assert(!TWO || (AFF_ROW0_GAPS(MODE) && !MATRIX && !XDROP && !ADAPT), "two-piece gaps: plain global and extend runs");
     static_assert(!XDROP || (LONG && MODE == AFF_EXTEND), "xdrop is an option of the strip sweeps of an extend run");
     static_assert(!ADAPT || (LONG && BAND && MODE == AFF_EXTEND), "band_adapt is an option of the banded strip sweeps of an extend run");
     if (blockIdx.x == 0 && threadIdx.x == 0) A.hdr->reserved = 0ull;      // the traceback's bump allocator
@@ -576,14 +665,14 @@ __device__ __forceinline__ void aff_sweep_entry(const FillArgs &A, const int o, 
     const PairDesc pd = A.pairs[pair];
     if constexpr (LONG) {
         if (uni(A.reads[pd.read_id].len) <= SWMI_AFF_MAX_READ) return;
-        if (A.strict) aff_sweep_long_pair<true, MATRIX, MODE, BAND, XDROP, ADAPT>(A, o, pd, lane, nn, wb, xd);
-        else          aff_sweep_long_pair<false, MATRIX, MODE, BAND, XDROP, ADAPT>(A, o, pd, lane, nn, wb, xd);
+        if (A.strict) aff_sweep_long_pair<true, MATRIX, MODE, BAND, XDROP, ADAPT, TWO>(A, o, pd, lane, nn, wb, xd, o2, e2);
+        else          aff_sweep_long_pair<false, MATRIX, MODE, BAND, XDROP, ADAPT, TWO>(A, o, pd, lane, nn, wb, xd, o2, e2);
         return;
     }
     const uint32_t R = uni(swmi_aff_rows_per_lane(A.reads[pd.read_id].len));
     if (R < (uint32_t)RLO || R > (uint32_t)RHI) return;
-    if (A.strict) aff_sweep_dispatch<RLO, RHI, true, MATRIX, MODE>(A, o, pd, R, lane, nn);
-    else          aff_sweep_dispatch<RLO, RHI, false, MATRIX, MODE>(A, o, pd, R, lane, nn);
+    if (A.strict) aff_sweep_dispatch<RLO, RHI, true, MATRIX, MODE, TWO>(A, o, pd, R, lane, nn, o2, e2);
+    else          aff_sweep_dispatch<RLO, RHI, false, MATRIX, MODE, TWO>(A, o, pd, R, lane, nn, o2, e2);
 }
 
 }  // namespace
@@ -654,6 +743,29 @@ AFF_SWEEP_KERNEL(sw_affine_sweep_band_adapt_matrix_kernel, SWMI_AFF_RMAX, SWMI_A
 AFF_SWEEP_KERNEL(sw_affine_sweep_band_adapt_xdrop_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, AFF_EXTEND, true, 1, 1, 1)
 AFF_SWEEP_KERNEL(sw_affine_sweep_band_adapt_xdrop_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, AFF_EXTEND, true, 1, 1, 1)
 #undef AFF_SWEEP_KERNEL
+// The 8 two-piece sweeps (option "gap_open2"): global and extend, each narrow, wide, long and banded long, TWO = 1.
+// The second piece's open and extension follow gap_open; the banded ones take the half-width last.
+#define AFF_SWEEP2_PARAMS_0 const FillArgs A, const int gap_open, const int gap_open2, const int gap2
+#define AFF_SWEEP2_PARAMS_1 AFF_SWEEP2_PARAMS_0, const uint32_t band
+#define AFF_SWEEP2_ARGS_0 A, gap_open, nullptr, 0u, 0u, 0u, gap_open2, gap2
+#define AFF_SWEEP2_ARGS_1 A, gap_open, nullptr, 0u, band, 0u, gap_open2, gap2
+#define AFF_SWEEP2_KERNEL(name, RLO, RHI, MODE, LONG, BAND)                                                               \
+    extern "C" __global__ void __launch_bounds__(WAVE * AFF_WAVES) name(AFF_SWEEP2_PARAMS_##BAND) {                      \
+        aff_sweep_entry<RLO, RHI, false, MODE, LONG, BAND != 0, false, false, true>(AFF_SWEEP2_ARGS_##BAND);             \
+    }
+AFF_SWEEP2_KERNEL(sw_affine_sweep2_global_kernel, 1, 4, AFF_GLOBAL, false, 0)
+AFF_SWEEP2_KERNEL(sw_affine_sweep2_global_wide_kernel, 5, SWMI_AFF_RMAX, AFF_GLOBAL, false, 0)
+AFF_SWEEP2_KERNEL(sw_affine_sweep2_long_global_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, AFF_GLOBAL, true, 0)
+AFF_SWEEP2_KERNEL(sw_affine_sweep2_band_global_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, AFF_GLOBAL, true, 1)
+AFF_SWEEP2_KERNEL(sw_affine_sweep2_extend_kernel, 1, 4, AFF_EXTEND, false, 0)
+AFF_SWEEP2_KERNEL(sw_affine_sweep2_extend_wide_kernel, 5, SWMI_AFF_RMAX, AFF_EXTEND, false, 0)
+AFF_SWEEP2_KERNEL(sw_affine_sweep2_long_extend_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, AFF_EXTEND, true, 0)
+AFF_SWEEP2_KERNEL(sw_affine_sweep2_band_extend_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, AFF_EXTEND, true, 1)
+#undef AFF_SWEEP2_KERNEL
+#undef AFF_SWEEP2_PARAMS_0
+#undef AFF_SWEEP2_PARAMS_1
+#undef AFF_SWEEP2_ARGS_0
+#undef AFF_SWEEP2_ARGS_1
 #undef AFF_SWEEP_PARAMS_000
 #undef AFF_SWEEP_PARAMS_001
 #undef AFF_SWEEP_PARAMS_100
@@ -689,10 +801,20 @@ AFF_SWEEP_KERNEL(sw_affine_sweep_band_adapt_xdrop_matrix_kernel, SWMI_AFF_RMAX, 
 //   on every step up across a seam; the strip's field lies at the fixed stride swmi_aff_adapt_strip_words.  A centre is clamped to
 //   n, so that a table entry the sweep never wrote (a corrupted list that names a strip behind an xdrop stop) still gives a window
 //   of at most the stride's blocks and the guard w < W keeps the walk inside the pair's field.
+// TWO (the walk of a two-piece run, global mode's): a block is 2 R 64 dwords, plane 0 then plane 1, so a tile of
+//   consecutive blocks holds both; a strip's field is twice as long.  Five states: H, M, and per piece F and E (AFF_INS / AFF_DEL are
+//   piece 1's, AFF_INS2 / AFF_DEL2 piece 2's).  State H reads the direction from plane 0; an insertion enters F2 iff pF (plane 1,
+//   bit 1), a deletion E2 iff pE (bit 0); a gap state stays while its own x bit is set -- plane 0 bits 2, 3 for piece 1, plane 1
+//   bits 2, 3 for piece 2.  Plane 1 is read only on entering a gap state or in a piece-2 state.  A step up across a seam in
+//   state F2 continues in the strip above like any other.
+#define AFF_INS2 4u
+#define AFF_DEL2 5u
 namespace {
-template <int MODE, bool LONG, bool BAND = false, bool ADAPT = false>
+template <int MODE, bool LONG, bool BAND = false, bool ADAPT = false, bool TWO = false>
 __device__ __forceinline__ void aff_traceback(const TraceArgs A, const uint32_t tile_words, const uint32_t ops_words, const uint32_t wb = 0u) {
     static_assert(!ADAPT || (LONG && BAND && MODE == AFF_GLOBAL), "band_adapt: the banded walk of an extend run (global mode's)");
+    static_assert(!TWO || (MODE == AFF_GLOBAL && !ADAPT), "two-piece gaps: the global walk");
+    constexpr uint32_t PL = TWO ? 2u : 1u;                        // planes of the field
     extern __shared__ uint32_t lds[];
     const uint32_t lane = threadIdx.x;
     const uint32_t slot = blockIdx.y, nslots = gridDim.y;
@@ -710,7 +832,7 @@ __device__ __forceinline__ void aff_traceback(const TraceArgs A, const uint32_t 
     const uint32_t R = LONG ? SWMI_AFF_RMAX : uni(swmi_aff_rows_per_lane(m));
     uint32_t W = uni(LONG ? swmi_aff_strip_blocks(n) : swmi_aff_blocks(m, n));      // (BAND: of strip sx, set with it)
     uint32_t clo = 1u, chi = n;                                   // first and last column of strip sx's window
-    const uint32_t blk_words = R * WAVE;                          // dwords of one 8-step block
+    const uint32_t blk_words = PL * R * WAVE;                     // dwords of one 8-step block
     const uint32_t NB = tile_words / blk_words;                   // blocks per tile (>= 1: the host sizes the tile)
     const uint32_t max_ops = ops_words * 16u;
     const uint32_t *__restrict__ dir = A.dir + pd.dir_off;
@@ -770,20 +892,30 @@ __device__ __forceinline__ void aff_traceback(const TraceArgs A, const uint32_t 
                 wlo = w + 1u >= NB ? w + 1u - NB : 0u;
                 whi = w + 1u;
                 if constexpr (LONG) tsx = sx;
-                const uint32_t *__restrict__ src = dir + (ADAPT ? (uint64_t)sx * astride : BAND ? swmi_aff_band_strip_off(sx, n, wb) : LONG ? (uint64_t)sx * swmi_aff_strip_words(n) : 0ull) +
+                const uint32_t *__restrict__ src = dir + (ADAPT ? (uint64_t)sx * astride : BAND ? PL * swmi_aff_band_strip_off(sx, n, wb) : LONG ? (uint64_t)sx * PL * swmi_aff_strip_words(n) : 0ull) +
                                                    (uint64_t)wlo * blk_words;
                 const uint32_t words = (whi - wlo) * blk_words;
                 for (uint32_t x = lane; x < words; x += WAVE) tile[x] = src[x];
                 WAVE_SYNC();
             }
-            const uint32_t code = uni((tile[((w - wlo) * R + k) * WAVE + l] >> (4u * (t & 7u))) & 15u);
+            uint32_t code = uni((tile[((w - wlo) * PL * R + k) * WAVE + l] >> (4u * (t & 7u))) & 15u);
             if (st == 0u) {
                 st = code & 3u;
                 if (MODE == AFF_LOCAL) { if (st == AFF_STOP) break; }   // H(i, j) == 0: `while (score > 0)` (SmithWaterman.java:380)
                 else if (st == AFF_STOP) { ok = false; break; }         // (these sweeps write no code 0: a corrupted field)
+                if constexpr (TWO) {
+                    if (st != AFF_DIAG) {                               // entering a gap state: which piece (plane 1: pE bit 0, pF bit 1)
+                        const uint32_t c2 = uni((tile[(((w - wlo) * PL + 1u) * R + k) * WAVE + l] >> (4u * (t & 7u))) & 15u);
+                        if (st == AFF_INS && (c2 & 2u)) { st = AFF_INS2; code = c2; }
+                        else if (st == AFF_DEL && (c2 & 1u)) { st = AFF_DEL2; code = c2; }
+                    }
+                }
+            } else if constexpr (TWO) {
+                // in a piece-2 state: its x bits are plane 1's
+                if (st >= AFF_INS2) code = uni((tile[(((w - wlo) * PL + 1u) * R + k) * WAVE + l] >> (4u * (t & 7u))) & 15u);
             }
             if (n_ops >= max_ops) { ok = false; break; }
-            if (MODE == AFF_LOCAL || st != AFF_INS) begin = (int)j;     // (end-to-end: the moves that consume a reference base)
+            if (MODE == AFF_LOCAL || (st != AFF_INS && (!TWO || st != AFF_INS2))) begin = (int)j;     // (end-to-end: the moves that consume a reference base)
             uint32_t op;
             if (st == AFF_DIAG) {
                 op = SWMI_DIR_A;
@@ -793,6 +925,14 @@ __device__ __forceinline__ void aff_traceback(const TraceArgs A, const uint32_t 
                 op = SWMI_DIR_I;
                 st = (code & 8u) ? AFF_INS : 0u;
                 --i;
+            } else if (TWO && st == AFF_INS2) {
+                op = SWMI_DIR_I;
+                st = (code & 8u) ? AFF_INS2 : 0u;
+                --i;
+            } else if (TWO && st == AFF_DEL2) {
+                op = SWMI_DIR_D;
+                st = (code & 4u) ? AFF_DEL2 : 0u;
+                --j;
             } else {
                 op = SWMI_DIR_D;
                 st = (code & 4u) ? AFF_DEL : 0u;
@@ -841,25 +981,31 @@ __device__ __forceinline__ void aff_traceback(const TraceArgs A, const uint32_t 
 }
 #undef AFF_ADAPT_WINDOW
 }  // namespace
+#undef AFF_INS2
+#undef AFF_DEL2
 
 #define AFF_TB_PARAMS_0 const TraceArgs A, const uint32_t tile_words, const uint32_t ops_words
 #define AFF_TB_PARAMS_1 const TraceArgs A, const uint32_t tile_words, const uint32_t ops_words, const uint32_t band
 #define AFF_TB_ARGS_0 A, tile_words, ops_words
 #define AFF_TB_ARGS_1 A, tile_words, ops_words, band
-#define AFF_TRACEBACK_KERNEL(name, MODE, LONG, BAND, ADAPT)                                                 \
+#define AFF_TRACEBACK_KERNEL(name, MODE, LONG, BAND, ADAPT, TWO)                                            \
     extern "C" __global__ void __launch_bounds__(WAVE) name(AFF_TB_PARAMS_##BAND) {                        \
-        aff_traceback<MODE, LONG, BAND != 0, ADAPT != 0>(AFF_TB_ARGS_##BAND);                              \
+        aff_traceback<MODE, LONG, BAND != 0, ADAPT != 0, TWO != 0>(AFF_TB_ARGS_##BAND);                    \
     }
-AFF_TRACEBACK_KERNEL(sw_affine_traceback_kernel, AFF_LOCAL, false, 0, 0)
-AFF_TRACEBACK_KERNEL(sw_affine_traceback_fit_kernel, AFF_FIT, false, 0, 0)
-AFF_TRACEBACK_KERNEL(sw_affine_traceback_global_kernel, AFF_GLOBAL, false, 0, 0)
-AFF_TRACEBACK_KERNEL(sw_affine_traceback_long_kernel, AFF_LOCAL, true, 0, 0)
-AFF_TRACEBACK_KERNEL(sw_affine_traceback_long_fit_kernel, AFF_FIT, true, 0, 0)
-AFF_TRACEBACK_KERNEL(sw_affine_traceback_long_global_kernel, AFF_GLOBAL, true, 0, 0)
-AFF_TRACEBACK_KERNEL(sw_affine_traceback_band_kernel, AFF_LOCAL, true, 1, 0)
-AFF_TRACEBACK_KERNEL(sw_affine_traceback_band_fit_kernel, AFF_FIT, true, 1, 0)
-AFF_TRACEBACK_KERNEL(sw_affine_traceback_band_global_kernel, AFF_GLOBAL, true, 1, 0)
-AFF_TRACEBACK_KERNEL(sw_affine_traceback_band_adapt_global_kernel, AFF_GLOBAL, true, 1, 1)
+AFF_TRACEBACK_KERNEL(sw_affine_traceback_kernel, AFF_LOCAL, false, 0, 0, 0)
+AFF_TRACEBACK_KERNEL(sw_affine_traceback_fit_kernel, AFF_FIT, false, 0, 0, 0)
+AFF_TRACEBACK_KERNEL(sw_affine_traceback_global_kernel, AFF_GLOBAL, false, 0, 0, 0)
+AFF_TRACEBACK_KERNEL(sw_affine_traceback_long_kernel, AFF_LOCAL, true, 0, 0, 0)
+AFF_TRACEBACK_KERNEL(sw_affine_traceback_long_fit_kernel, AFF_FIT, true, 0, 0, 0)
+AFF_TRACEBACK_KERNEL(sw_affine_traceback_long_global_kernel, AFF_GLOBAL, true, 0, 0, 0)
+AFF_TRACEBACK_KERNEL(sw_affine_traceback_band_kernel, AFF_LOCAL, true, 1, 0, 0)
+AFF_TRACEBACK_KERNEL(sw_affine_traceback_band_fit_kernel, AFF_FIT, true, 1, 0, 0)
+AFF_TRACEBACK_KERNEL(sw_affine_traceback_band_global_kernel, AFF_GLOBAL, true, 1, 0, 0)
+AFF_TRACEBACK_KERNEL(sw_affine_traceback_band_adapt_global_kernel, AFF_GLOBAL, true, 1, 1, 0)
+// the 3 walks of a two-piece run (option "gap_open2"): global mode's, short, long and banded long
+AFF_TRACEBACK_KERNEL(sw_affine_traceback2_global_kernel, AFF_GLOBAL, false, 0, 0, 1)
+AFF_TRACEBACK_KERNEL(sw_affine_traceback2_long_global_kernel, AFF_GLOBAL, true, 0, 0, 1)
+AFF_TRACEBACK_KERNEL(sw_affine_traceback2_band_global_kernel, AFF_GLOBAL, true, 1, 0, 1)
 #undef AFF_TRACEBACK_KERNEL
 #undef AFF_TB_PARAMS_0
 #undef AFF_TB_PARAMS_1
@@ -877,10 +1023,13 @@ AFF_TRACEBACK_KERNEL(sw_affine_traceback_band_adapt_global_kernel, AFF_GLOBAL, t
 // xdrop: with long_reads and align_mode 3, the threshold of option "xdrop" (0: none): the strip sweep that may stop at a seam
 // band_adapt: with long_reads, band and align_mode 3, option "band_adapt" (0 / 1): the banded strip sweep whose windows follow the
 //   alignment; every pair's workspace is then swmi_aff_adapt_work_words
+// gap_open2, gap2: option "gap_open2" (0: none) and "gap2": the two-piece sweeps, align_mode 2 and 3 without mat, xdrop and band_adapt;
+//   every pair's field is then swmi_aff2_dir_words / swmi_aff2_band_dir_words and its seam row swmi_aff2_seam_words
 extern "C" hipError_t swmi_launch_affine_sweep(const FillArgs *a, int32_t gap_open, uint32_t align_mode, const uint32_t *mat, uint32_t nn,
                                                uint32_t r_min, uint32_t r_max, uint32_t long_reads, uint32_t band, uint32_t xdrop,
-                                               uint32_t band_adapt, hipStream_t st) {
+                                               uint32_t band_adapt, int32_t gap_open2, int32_t gap2, hipStream_t st) {
     if (a->n_pairs == 0) return hipSuccess;
+    if (gap_open2 && (align_mode < 2u || align_mode > 3u || mat || xdrop || band_adapt)) return hipErrorInvalidValue;
     if (align_mode > 3u || (mat && (nn < 2u || nn > SWMI_MAT_NN_MAX)) || band > SWMI_AFF_BAND_MAX) return hipErrorInvalidValue;
     if (xdrop > 0x7FFFFFFFu || (xdrop && long_reads && align_mode != AFF_EXTEND)) return hipErrorInvalidValue;
     if (band_adapt > 1u || (band_adapt && long_reads && (!band || align_mode != AFF_EXTEND))) return hipErrorInvalidValue;
@@ -911,13 +1060,21 @@ extern "C" hipError_t swmi_launch_affine_sweep(const FillArgs *a, int32_t gap_op
     static void (*const amatrix)(FillArgs, int, const uint32_t *, uint32_t, uint32_t) = sw_affine_sweep_band_adapt_matrix_kernel;
     static void (*const axplain)(FillArgs, int, uint32_t, uint32_t) = sw_affine_sweep_band_adapt_xdrop_kernel;
     static void (*const axmatrix)(FillArgs, int, const uint32_t *, uint32_t, uint32_t, uint32_t) = sw_affine_sweep_band_adapt_xdrop_matrix_kernel;
+    // the two-piece sweeps, [narrow / wide / long][extend], and [extend] of the banded long ones
+    static void (*const tplain[3][2])(FillArgs, int, int, int) = {
+        {sw_affine_sweep2_global_kernel, sw_affine_sweep2_extend_kernel},
+        {sw_affine_sweep2_global_wide_kernel, sw_affine_sweep2_extend_wide_kernel},
+        {sw_affine_sweep2_long_global_kernel, sw_affine_sweep2_long_extend_kernel}};
+    static void (*const tbplain[2])(FillArgs, int, int, int, uint32_t) = {sw_affine_sweep2_band_global_kernel, sw_affine_sweep2_band_extend_kernel};
     const dim3 grid((a->n_pairs + AFF_WAVES - 1) / AFF_WAVES), block(WAVE * AFF_WAVES);
     const bool banded = long_reads && band;                       // (the long shape only)
     const bool adapts = banded && band_adapt;
     // (a launch's own error is what hipGetLastError returns below)
     const bool stops = long_reads && xdrop;                       // (the long shape only)
     const auto launch = [&](int shape) {
-        if (adapts && stops && mat) hipLaunchKernelGGL(axmatrix, grid, block, 0, st, *a, (int)gap_open, mat, nn, band, xdrop);
+        if (gap_open2 && banded) hipLaunchKernelGGL(tbplain[align_mode - 2u], grid, block, 0, st, *a, (int)gap_open, (int)gap_open2, (int)gap2, band);
+        else if (gap_open2)      hipLaunchKernelGGL(tplain[shape][align_mode - 2u], grid, block, 0, st, *a, (int)gap_open, (int)gap_open2, (int)gap2);
+        else if (adapts && stops && mat) hipLaunchKernelGGL(axmatrix, grid, block, 0, st, *a, (int)gap_open, mat, nn, band, xdrop);
         else if (adapts && stops)   hipLaunchKernelGGL(axplain, grid, block, 0, st, *a, (int)gap_open, band, xdrop);
         else if (adapts && mat)     hipLaunchKernelGGL(amatrix, grid, block, 0, st, *a, (int)gap_open, mat, nn, band);
         else if (adapts)            hipLaunchKernelGGL(aplain, grid, block, 0, st, *a, (int)gap_open, band);
@@ -940,9 +1097,12 @@ extern "C" hipError_t swmi_launch_affine_sweep(const FillArgs *a, int32_t gap_op
 
 // long_reads: the walk over the strips' fields (every pair of the launch has a read longer than 1024 bases)
 // band, band_adapt: as for the sweep
+// two: the fields are those of the two-piece sweeps (option "gap_open2"): align_mode 2 and 3 without band_adapt; the tile holds at
+//   least one block of 2 * R * 64 dwords
 extern "C" hipError_t swmi_launch_affine_traceback(const TraceArgs *a, uint32_t align_mode, uint32_t long_reads, uint32_t band, uint32_t band_adapt,
-                                                   uint32_t tile_words, uint32_t ops_words, hipStream_t st) {
+                                                   uint32_t two, uint32_t tile_words, uint32_t ops_words, hipStream_t st) {
     if (a->n_pairs == 0) return hipSuccess;
+    if (two > 1u || (two && (align_mode < 2u || align_mode > 3u || band_adapt || tile_words < 2u * SWMI_AFF_RMAX * WAVE))) return hipErrorInvalidValue;
     if (align_mode > 3u || band > SWMI_AFF_BAND_MAX) return hipErrorInvalidValue;
     if (band_adapt > 1u || (band_adapt && long_reads && (!band || align_mode != AFF_EXTEND))) return hipErrorInvalidValue;
     // an extend run is walked by global mode's kernels: aff_traceback<AFF_GLOBAL, ..> starts at whatever cell the list names and
@@ -954,11 +1114,14 @@ extern "C" hipError_t swmi_launch_affine_traceback(const TraceArgs *a, uint32_t 
     static void (*const bkern[3])(TraceArgs, uint32_t, uint32_t, uint32_t) = {      // [align_mode]: the banded long walks
         sw_affine_traceback_band_kernel, sw_affine_traceback_band_fit_kernel, sw_affine_traceback_band_global_kernel};
     static void (*const akern)(TraceArgs, uint32_t, uint32_t, uint32_t) = sw_affine_traceback_band_adapt_global_kernel;   // ... under option "band_adapt"
+    static void (*const tkern[2])(TraceArgs, uint32_t, uint32_t) = {sw_affine_traceback2_global_kernel, sw_affine_traceback2_long_global_kernel};   // [long_reads]: two-piece
+    static void (*const tbkern)(TraceArgs, uint32_t, uint32_t, uint32_t) = sw_affine_traceback2_band_global_kernel;
     static const bool attrs = [] {
         for (int mode = 0; mode < 3; ++mode) {
             swmi_allow_big_lds(kern[0][mode]); swmi_allow_big_lds(kern[1][mode]); swmi_allow_big_lds(bkern[mode]);
         }
         swmi_allow_big_lds(akern);
+        swmi_allow_big_lds(tkern[0]); swmi_allow_big_lds(tkern[1]); swmi_allow_big_lds(tbkern);
         return true;
     }();
     (void)attrs;
@@ -967,7 +1130,9 @@ extern "C" hipError_t swmi_launch_affine_traceback(const TraceArgs *a, uint32_t 
     const auto launch = [&](auto *k, auto... band) {
         hipLaunchKernelGGL(k, dim3(a->n_pairs, SWMI_AFF_TB_SLOTS), dim3(WAVE), lds, st, *a, tile_words, ops_words, band...);
     };
-    if (long_reads && band && band_adapt) launch(akern, band);
+    if (two && long_reads && band) launch(tbkern, band);
+    else if (two) launch(tkern[long_reads ? 1 : 0]);
+    else if (long_reads && band && band_adapt) launch(akern, band);
     else if (long_reads && band) launch(bkern[align_mode], band);
     else                    launch(kern[long_reads ? 1 : 0][align_mode]);
     return hipGetLastError();

@@ -186,6 +186,14 @@ extern "C" int swmi_set_option(swmi_ctx *ctx, const char *name, int64_t value) {
     } else if (!strcmp(name, "band_adapt")) {
         if (value != 0 && value != 1) return fail(SWMI_ERR_INVALID, "band_adapt must be 0 or 1, got %lld", (long long)value);
         ctx->modes.band_adapt = (int)value;
+    } else if (!strcmp(name, "gap_open2")) {
+        if (value > 0) return fail(SWMI_ERR_INVALID, "gap_open2 must be <= 0 (a penalty; 0: one-piece gaps), got %lld", (long long)value);
+        if (value < INT32_MIN) return fail(SWMI_ERR_INVALID, "gap_open2 out of range");
+        ctx->modes.gap_open2 = (int)value;
+    } else if (!strcmp(name, "gap2")) {
+        if (value > 0) return fail(SWMI_ERR_INVALID, "gap2 must be <= 0 (the second piece's per-base extension), got %lld", (long long)value);
+        if (value < INT32_MIN) return fail(SWMI_ERR_INVALID, "gap2 out of range");
+        ctx->modes.gap2 = (int)value;
     } else if (!strcmp(name, "arena_words_per_pair")) {
         if (value < 1) return fail(SWMI_ERR_INVALID, "arena_words_per_pair out of range");
         ctx->arena_words_per_pair = (uint64_t)value;

@@ -348,6 +348,13 @@ SWMI_HD static inline uint64_t swmi_aff_band_strip_off(uint32_t s, uint32_t n, u
 SWMI_HD static inline uint64_t swmi_aff_band_dir_words(uint32_t m, uint32_t n, uint32_t w) {
     return swmi_aff_band_strip_off(swmi_aff_strips(m), n, w);
 }
+// ---- option "gap_open2" (two-piece gaps, global and extend runs): the field has two 4-bit planes, interleaved per
+// 8-step block -- dword ((w * 2 + plane) * R + k) * 64 + lane -- so every block, strip and field is twice the one-piece size, and
+// the seam row carries (H, F1, F2) per column in 16-byte entries.  A traceback tile must hold one block: 2 * 16 * 64 dwords. ----
+SWMI_HD static inline uint64_t swmi_aff2_dir_words(uint32_t m, uint32_t n) { return 2ull * swmi_aff_dir_words(m, n); }
+SWMI_HD static inline uint64_t swmi_aff2_band_dir_words(uint32_t m, uint32_t n, uint32_t w) { return 2ull * swmi_aff_band_dir_words(m, n, w); }
+SWMI_HD static inline uint64_t swmi_aff2_seam_words(uint32_t m, uint32_t n) { return m > SWMI_AFF_MAX_READ ? 4ull * n : 0ull; }
+static_assert(2u * SWMI_AFF_RMAX * 64u <= SWMI_AFF_TILE_WORDS, "a two-plane block fits the traceback tile");
 // ---- option "band_adapt" (with band = w and option "extend"): the window of strip s follows a CENTRE c that the
 // sweep takes from the seam row above the strip -- c_lo = max(1, c + 1 - w), c_hi = min(n, c + 1024 + w), 0 <= c <= n; c = 0 is
 // strip 0's (static) window.  A window has at most min(n, 1024 + 2 w) columns, and every strip's field gets the blocks of that

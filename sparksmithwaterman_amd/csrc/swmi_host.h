@@ -120,6 +120,9 @@ struct __attribute__((visibility("hidden"))) RunModes {
     int extend = 0;                         // 1: seed extension -- a global run whose maximum is taken over every cell (swmi.h); refused in the other modes
     int xdrop = 0;                          // > 0: the drop-off threshold X of an extend run -- the strip sweep of a long read ends at a seam (swmi.h); refused in other runs
     int band_adapt = 0;                     // 1: the band of an extend run follows the alignment, strip by strip (swmi.h); refused in other runs
+    int gap_open2 = 0;                      // != 0: two-piece gaps on a global or extend run -- the second piece's open (swmi.h); refused in other runs
+    int gap2 = 0;                           // ... and its per-base extension (not read while gap_open2 == 0)
+    bool two_piece() const { return gap_open2 != 0; }
     // the MODE of the affine kernels and their launchers: the align_mode, or 3 (extend) for a global run with option "extend"
     uint32_t kernel_mode() const { return extend && align_mode == SWMI_ALIGN_GLOBAL ? 3u : (uint32_t)align_mode; }
     bool operator==(const RunModes &o) const { return memcmp(this, &o, sizeof(RunModes)) == 0; }
@@ -179,7 +182,7 @@ struct swmi_ctx {
     bool cell_cap_set = false;              // cell_cap given by the caller (otherwise small launches get longer lists)
     int32_t gap_open = 0;                   // affine gaps: a gap of length k costs gap_open + k * gap (0: linear)
     int affine = -1;                        // -1: the affine kernels (mode 3) when gap_open != 0; 1: always
-    RunModes modes;                         // options "align_mode", "long_reads", "band", "extend", "xdrop" and "band_adapt"
+    RunModes modes;                         // options "align_mode", "long_reads", "band", "extend", "xdrop", "band_adapt", "gap_open2" and "gap2"
     std::mutex mat_mu;                      // guards `matrix` (not ctx->mu: setting a matrix does not wait for a run)
     std::shared_ptr<const ScoreMatrix> matrix;   // swmi_set_score_matrix; a run with one takes the affine kernels
     // swmi_batch_run_async: one run in flight on the context's own host thread
@@ -305,6 +308,7 @@ struct swmi_batch {
     int work_mode = -1;
     int work_band = 0;                      // the band the schedule's workspace sizes were made for (mode 3)
     int work_adapt = 0;                     // ... and option "band_adapt" (its fields have a fixed stride and a window table behind them)
+    bool work_two = false;                  // ... and option "gap_open2" (two planes, 16-byte seam entries)
     bool work_tfused = false;               // the schedule's workspace sizes leave room for sw_tfused_kernel's column checkpoints
     uint32_t eff_mode = 1;                  // pipeline of the current run (3: the affine kernels, swmi_affine.hip)
     int32_t gap_open = 0;                   // the context's gap_open when the run started (mode 3)

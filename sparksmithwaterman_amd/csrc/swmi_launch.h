@@ -20,8 +20,8 @@ extern "C" hipError_t swmi_launch_resident(const TraceArgs *a, const ResidentArg
 extern "C" hipError_t swmi_launch_tfused(const TraceArgs *a, const TFusedArgs *x, hipStream_t st);
 extern "C" hipError_t swmi_launch_affine_sweep(const FillArgs *a, int32_t gap_open, uint32_t align_mode, const uint32_t *mat, uint32_t nn,
                                                uint32_t r_min, uint32_t r_max, uint32_t long_reads, uint32_t band, uint32_t xdrop,
-                                               uint32_t band_adapt, hipStream_t st);
+                                               uint32_t band_adapt, int32_t gap_open2, int32_t gap2, hipStream_t st);
 extern "C" hipError_t swmi_launch_affine_traceback(const TraceArgs *a, uint32_t align_mode, uint32_t long_reads, uint32_t band, uint32_t band_adapt,
-                                                   uint32_t tile_words, uint32_t ops_words, hipStream_t st);
+                                                   uint32_t two, uint32_t tile_words, uint32_t ops_words, hipStream_t st);
 extern "C" hipError_t swmi_launch_encode(const uint8_t *raw, const uint64_t *raw_off, SeqDesc *desc, uint32_t *seqw,
                                          const uint8_t *lut, uint32_t n_seq, hipStream_t st);

@@ -265,11 +265,13 @@ static int enqueue_launches(RunState &rs, Launch &L, const ResidentArgs &xa, con
             fl.n_pairs = (uint32_t)plan.aff_n_long; fl.pairs = fa.pairs + fs.n_pairs;
             const uint32_t *mat = b->opt.mat ? b->d_mat.as<uint32_t>() : nullptr;
             const uint32_t nn = b->opt.mat ? b->opt.mat->n + 1u : 0u;
-            HIP_TRY(swmi_launch_affine_sweep(&fs, b->gap_open, b->opt.modes.kernel_mode(), mat, nn, plan.aff_r_min, plan.aff_r_max, 0u, 0u, 0u, 0u, ctx->stream));
+            // (option "gap_open2": the two-piece sweeps; gap2 is not read without it)
+            const int32_t o2 = b->opt.modes.gap_open2, e2 = o2 ? b->opt.modes.gap2 : 0;
+            HIP_TRY(swmi_launch_affine_sweep(&fs, b->gap_open, b->opt.modes.kernel_mode(), mat, nn, plan.aff_r_min, plan.aff_r_max, 0u, 0u, 0u, 0u, o2, e2, ctx->stream));
             // (option "band": the banded strip sweep; the other pairs are swept in full.  Option "xdrop": the strip sweep that may
             // end at a seam; the other pairs take the kernels they take without it)
             HIP_TRY(swmi_launch_affine_sweep(&fl, b->gap_open, b->opt.modes.kernel_mode(), mat, nn, 0u, 0u, 1u, (uint32_t)b->opt.modes.band,
-                                             (uint32_t)b->opt.modes.xdrop, (uint32_t)b->opt.modes.band_adapt, ctx->stream));
+                                             (uint32_t)b->opt.modes.xdrop, (uint32_t)b->opt.modes.band_adapt, o2, e2, ctx->stream));
         }
         else HIP_TRY(swmi_launch_fill(&fa, ctx->stream, ext ? ctx->ev[0] : nullptr, ext ? ctx->ev[1] : nullptr));
         rs.launches++;
@@ -298,9 +300,11 @@ static int enqueue_launches(RunState &rs, Launch &L, const ResidentArgs &xa, con
         ts.n_pairs = (uint32_t)(np - plan.aff_n_long);
         tl.n_pairs = (uint32_t)plan.aff_n_long; tl.pairs = ta.pairs + ts.n_pairs;
         const uint32_t ops_words = (uint32_t)(((uint64_t)plan.max_path + 15) / 16 + 1);
-        HIP_TRY(swmi_launch_affine_traceback(&ts, b->opt.modes.kernel_mode(), 0u, 0u, 0u, SWMI_AFF_TILE_WORDS, ops_words, ctx->stream));
+        // (option "gap_open2": a block of the field is 2 * R * 64 dwords, and SWMI_AFF_TILE_WORDS holds one -- swmi_device.h)
+        const uint32_t two = b->opt.modes.two_piece() ? 1u : 0u;
+        HIP_TRY(swmi_launch_affine_traceback(&ts, b->opt.modes.kernel_mode(), 0u, 0u, 0u, two, SWMI_AFF_TILE_WORDS, ops_words, ctx->stream));
         HIP_TRY(swmi_launch_affine_traceback(&tl, b->opt.modes.kernel_mode(), 1u, (uint32_t)b->opt.modes.band, (uint32_t)b->opt.modes.band_adapt,
-                                             SWMI_AFF_TILE_WORDS, ops_words, ctx->stream));
+                                             two, SWMI_AFF_TILE_WORDS, ops_words, ctx->stream));
     } else if (n_res + n_tf < np) {
         HIP_TRY(swmi_launch_traceback(&ta, ctx->stream, ext ? ctx->ev[2] : nullptr, ext ? ctx->ev[3] : nullptr));
     }
@@ -539,8 +543,9 @@ static int run_chunk(RunState &rs, const std::vector<Work> &work, size_t lo, siz
 // Option "band" (half-width w) with at least one read longer than 1024 bases: what a banded run refuses (swmi.h),
 // in 64-bit arithmetic.  rows = 1024 * strips of the longest read, S = the largest |score|, max_n = the longest reference.
 // Every condition is monotone in m and n, so the extreme lengths decide for every long pair of the batch.
+// go, ge: the gap open and extension the bounds are read with -- under option "gap_open2" the larger |.| of the two pieces
 static int check_band(const swmi_ctx *ctx, const swmi_batch *b, const swmi_params *p, const RunModes &md, uint64_t rows, int64_t S,
-                      uint64_t max_n) {
+                      uint64_t max_n, int64_t go, int64_t ge) {
     const int align_mode = md.align_mode, band = md.band;
     const int64_t w = band;
     uint64_t min_n = UINT64_MAX, min_long = UINT64_MAX, max_m = 0;
@@ -575,14 +580,19 @@ static int check_band(const swmi_ctx *ctx, const swmi_batch *b, const swmi_param
             return fail(SWMI_ERR_UNSUPPORTED, "band %d, band_adapt: (2 * ceil(m / 1024) + 1) * gap_open + (1024 * ceil(m / 1024) + n) * gap = %lld for the "
                         "longest read (%llu) and reference (%llu) is below -2^30", band, (long long)low, (unsigned long long)max_m, (unsigned long long)max_n);
     } else if (align_mode == SWMI_ALIGN_GLOBAL) {
-        const int64_t low = 3 * (int64_t)ctx->gap_open + (int64_t)(rows + max_n) * (int64_t)p->gap;
+        const int64_t low = 3 * go + (int64_t)(rows + max_n) * ge;
         if (low < -((int64_t)1 << 30))
             return fail(SWMI_ERR_UNSUPPORTED, "band %d, align_mode global: 3 * gap_open + (1024 * ceil(m / 1024) + n) * gap = %lld for the longest "
                         "read (%llu) and reference (%llu) is below -2^30", band, (long long)low, (unsigned long long)max_m, (unsigned long long)max_n);
     }
     // the field of the largest pair alone against the workspace cap (it grows with m and with n)
     const uint64_t bytes = (md.band_adapt ? swmi_aff_adapt_work_words((uint32_t)max_m, (uint32_t)max_n, (uint32_t)band)
-                                          : swmi_aff_band_dir_words((uint32_t)max_m, (uint32_t)max_n, (uint32_t)band)) * 4;
+                            : md.two_piece() ? swmi_aff2_band_dir_words((uint32_t)max_m, (uint32_t)max_n, (uint32_t)band)
+                                             : swmi_aff_band_dir_words((uint32_t)max_m, (uint32_t)max_n, (uint32_t)band)) * 4;
+    if (bytes > ctx->max_workspace_bytes && md.two_piece())
+        return fail(SWMI_ERR_UNSUPPORTED, "band %d, gap_open2: the two-plane direction field of the longest read (%llu) against the longest reference (%llu) "
+                    "takes %llu bytes (twice the one-piece field), more than max_workspace_bytes (%llu)", band, (unsigned long long)max_m,
+                    (unsigned long long)max_n, (unsigned long long)bytes, (unsigned long long)ctx->max_workspace_bytes);
     if (bytes > ctx->max_workspace_bytes)
         return fail(SWMI_ERR_UNSUPPORTED, "band %d: the direction field of the longest read (%llu) against the longest reference (%llu) takes %llu "
                     "bytes, more than max_workspace_bytes (%llu)", band, (unsigned long long)max_m, (unsigned long long)max_n,
@@ -613,6 +623,17 @@ static int check_run_params(const swmi_ctx *ctx, const swmi_batch *b, const swmi
     if (md.band_adapt && !(md.band > 0 && md.extend && md.align_mode == SWMI_ALIGN_GLOBAL))
         return fail(SWMI_ERR_UNSUPPORTED, "band_adapt = 1 needs a banded extend run (band > 0, align_mode global (2) with extend = 1), got band %d, "
                     "align_mode %d, extend %d", md.band, md.align_mode, md.extend);
+    // option "gap_open2": two-piece gaps are built for plain global and extend runs; gap2 is not read without it
+    if (md.two_piece()) {
+        if (md.align_mode != SWMI_ALIGN_GLOBAL)
+            return fail(SWMI_ERR_UNSUPPORTED, "gap_open2 = %d needs align_mode global (2), with or without extend; got align_mode %d", md.gap_open2, md.align_mode);
+        if (mat) return fail(SWMI_ERR_UNSUPPORTED, "gap_open2 = %d: two-piece gaps with a score matrix are not supported", md.gap_open2);
+        if (md.xdrop > 0) return fail(SWMI_ERR_UNSUPPORTED, "gap_open2 = %d: two-piece gaps under xdrop are not supported", md.gap_open2);
+        if (md.band_adapt) return fail(SWMI_ERR_UNSUPPORTED, "gap_open2 = %d: two-piece gaps under band_adapt are not supported", md.gap_open2);
+    }
+    // the gap open and extension the bounds are read with: the larger |.| of the two pieces (all four are <= 0)
+    const int64_t o2 = md.two_piece() ? md.gap_open2 : 0, e2 = md.two_piece() ? md.gap2 : 0;
+    const int64_t go = std::min<int64_t>(ctx->gap_open, o2), ge = std::min<int64_t>(p->gap, e2);
     uint64_t max_m, max_n;
     if (affine) {
         // the bounds within which every sum of the affine recurrence fits int32 (DESIGN.md "Affine gaps")
@@ -622,6 +643,8 @@ static int check_run_params(const swmi_ctx *ctx, const swmi_batch *b, const swmi
         if (std::llabs((int64_t)p->match) > lim || std::llabs((int64_t)p->mismatch) > lim || std::llabs((int64_t)p->gap) > lim ||
             std::llabs((int64_t)ctx->gap_open) > lim)
             return fail(SWMI_ERR_UNSUPPORTED, "affine gaps need |match|, |mismatch|, |gap|, |gap_open| <= 2^20");
+        if (std::llabs(o2) > lim || std::llabs(e2) > lim)
+            return fail(SWMI_ERR_UNSUPPORTED, "two-piece gaps need |gap_open2|, |gap2| <= 2^20");
         for (uint32_t q = 0; q < b->n_reads && !md.long_reads; q++)
             if (b->read_desc[q].len > SWMI_AFF_MAX_READ)
                 return fail(SWMI_ERR_UNSUPPORTED, "affine gaps: read %u has %u bases (at most %u; option long_reads lifts the limit)", q,
@@ -633,17 +656,24 @@ static int check_run_params(const swmi_ctx *ctx, const swmi_batch *b, const swmi
             // M * S <= 2^30 (swmi.h, DESIGN.md "Long reads"): H <= M * S, and no sum of the recurrence leaves int32
             int64_t S = std::max(std::max(std::llabs((int64_t)p->match), std::llabs((int64_t)p->mismatch)),
                                  std::max(std::llabs((int64_t)p->gap), std::llabs((int64_t)ctx->gap_open)));
+            S = std::max<int64_t>(S, std::max<int64_t>(std::llabs(o2), std::llabs(e2)));
             if (mat)
                 for (size_t x = 256; x < mat->image.size(); x++) S = std::max<int64_t>(S, std::llabs((int64_t)(int32_t)mat->image[x]));
             if ((int64_t)rows * S > ((int64_t)1 << 30))
                 return fail(SWMI_ERR_UNSUPPORTED, "long_reads: the longest read (%llu bases) is swept as %llu rows, and %llu * %lld (the largest "
                             "|score|) is above 2^30", (unsigned long long)max_m, (unsigned long long)rows, (unsigned long long)rows, (long long)S);
             if (md.band > 0 && max_m > SWMI_AFF_MAX_READ && max_n) {
-                int rc = check_band(ctx, b, p, md, rows, S, max_n);
+                int rc = check_band(ctx, b, p, md, rows, S, max_n, go, ge);
                 if (rc) return rc;
             }
             // a pair of several strips is one launch's work at the least: refused when its field alone is over the cap
             // (a banded run is checked with its own, smaller field in check_band)
+            if (md.band <= 0 && md.two_piece() && max_m > SWMI_AFF_MAX_READ && max_n &&
+                swmi_aff2_dir_words((uint32_t)max_m, (uint32_t)max_n) * 4 > ctx->max_workspace_bytes)
+                return fail(SWMI_ERR_UNSUPPORTED, "long_reads, gap_open2: the two-plane direction field of the longest read (%llu) against the longest "
+                            "reference (%llu) takes %llu bytes (twice the one-piece field), more than max_workspace_bytes (%llu)", (unsigned long long)max_m,
+                            (unsigned long long)max_n, (unsigned long long)(swmi_aff2_dir_words((uint32_t)max_m, (uint32_t)max_n) * 4),
+                            (unsigned long long)ctx->max_workspace_bytes);
             if (md.band <= 0 && max_m > SWMI_AFF_MAX_READ && max_n && swmi_aff_dir_words((uint32_t)max_m, (uint32_t)max_n) * 4 > ctx->max_workspace_bytes)
                 return fail(SWMI_ERR_UNSUPPORTED, "long_reads: the direction field of the longest read (%llu) against the longest reference (%llu) "
                             "takes %llu bytes, more than max_workspace_bytes (%llu)", (unsigned long long)max_m, (unsigned long long)max_n,
@@ -653,7 +683,7 @@ static int check_run_params(const swmi_ctx *ctx, const swmi_batch *b, const swmi
             // global mode: the smallest sum a sweep forms is 3 * gap_open + (64 * ceil(m / 64) + n) * gap (swmi.h, DESIGN.md
             // "End-to-end modes"); it must not leave int32.  Checked per pair in 64-bit arithmetic: it falls with m and n, so
             // the longest read against the longest reference decides.
-            const int64_t low = 3 * (int64_t)ctx->gap_open + (int64_t)(rows + max_n) * (int64_t)p->gap;
+            const int64_t low = 3 * go + (int64_t)(rows + max_n) * ge;
             if (max_m && max_n && low < (int64_t)INT32_MIN)
                 return fail(SWMI_ERR_UNSUPPORTED, "align_mode global: 3 * gap_open + (64 * ceil(m / 64) + n) * gap = %lld for the longest read "
                             "(%llu) and reference (%llu) is below -2^31", (long long)low, (unsigned long long)max_m, (unsigned long long)max_n);
@@ -729,11 +759,14 @@ static int choose_traceback_grain(swmi_ctx *ctx, swmi_batch *b, const swmi_param
 static void build_schedule(const swmi_ctx *ctx, swmi_batch *b) {
     const int band = b->eff_mode == 3 ? b->opt.modes.band : 0;
     const int adapt = band > 0 ? b->opt.modes.band_adapt : 0;
-    if (b->work_mode == (int)b->eff_mode && b->work_tfused == (ctx->tfused == 1) && b->work_band == band && b->work_adapt == adapt) return;
+    const bool two = b->eff_mode == 3 && b->opt.modes.two_piece();
+    if (b->work_mode == (int)b->eff_mode && b->work_tfused == (ctx->tfused == 1) && b->work_band == band && b->work_adapt == adapt &&
+        b->work_two == two) return;
     const uint32_t n_refs = b->n_refs, n_reads = b->n_reads;
     b->work_tfused = ctx->tfused == 1;
     b->work_band = band;
     b->work_adapt = adapt;
+    b->work_two = two;
     b->work.clear();
     b->work.reserve((uint64_t)n_refs * n_reads);
     b->work_cells = 0;
@@ -749,7 +782,8 @@ static void build_schedule(const swmi_ctx *ctx, swmi_batch *b) {
     const bool refs_uniform = n_refs && b->ref_desc[ro.front()].len == b->ref_desc[ro.back()].len;
     // (mode 3: the seam row of a read of several strips, none otherwise)
     const bool aff = b->eff_mode == 3;
-    auto seam_words = [aff](uint32_t m, uint32_t n) { return aff ? swmi_aff_seam_words(m, n) : swmi_seam_words(m, n); };
+    // (option "gap_open2": 16-byte seam entries and two planes of the field -- every pair of such a run)
+    auto seam_words = [aff, two](uint32_t m, uint32_t n) { return two ? swmi_aff2_seam_words(m, n) : aff ? swmi_aff_seam_words(m, n) : swmi_seam_words(m, n); };
     auto add = [&](uint32_t r, uint32_t q, uint32_t n, uint32_t m, uint64_t dw, uint64_t sw) {
         Work w;
         w.pair = r * n_reads + q;
@@ -763,6 +797,7 @@ static void build_schedule(const swmi_ctx *ctx, swmi_batch *b) {
     // stride and the window table, which is charged to the launch's workspace with them)
     auto dir_words = [&](uint32_t m, uint32_t n) {
         if (adapt && m > SWMI_AFF_MAX_READ) return swmi_aff_adapt_work_words(m, n, (uint32_t)band);
+        if (two) return band > 0 && m > SWMI_AFF_MAX_READ ? swmi_aff2_band_dir_words(m, n, (uint32_t)band) : swmi_aff2_dir_words(m, n);
         return band > 0 && m > SWMI_AFF_MAX_READ ? swmi_aff_band_dir_words(m, n, (uint32_t)band) : swmi_dir_words(m, n, b->eff_mode, tf);
     };
     if (refs_uniform) {                              // (reads outermost: descending m x the one n)

@@ -167,9 +167,14 @@ def _rank_main(args):
     scores = [int(x) for x in args.scores.split(",")]
     ctx = sw.Context(dev_id)
     try:
-        if len(scores) == 4:                                # match,mismatch,gap,gapOpen: affine gaps on this rank's context
+        if len(scores) not in (3, 4, 6):                    # (the parser refuses it; a caller that builds args itself)
+            raise ValueError("--scores takes 3, 4 or 6 entries, got %d" % len(scores))
+        if len(scores) >= 4:                                # match,mismatch,gap,gapOpen: affine gaps on this rank's context
             ctx.set_option("gap_open", scores[3])
-            scores = scores[:3]
+        if len(scores) == 6:                                # ...,gap2,gapOpen2: two-piece gaps (global and extend runs)
+            ctx.set_option("gap2", scores[4])
+            ctx.set_option("gap_open2", scores[5])
+        scores = scores[:3]
         if args.align_mode != "local":                      # end-to-end alignment: the streamed scores-only pass and the
             ctx.set_option("align_mode", _ALIGN_MODES[args.align_mode])    # realignment of the winners both run on this context
         if args.long_reads:                                 # reads longer than 1024 bases on the affine kernels
@@ -208,6 +213,8 @@ def _parser():
     class Parser(argparse.ArgumentParser):
         def parse_args(self, args=None, namespace=None):
             ns = super().parse_args(args, namespace)
+            if len(ns.scores.split(",")) not in (3, 4, 6):
+                self.error("--scores takes 3, 4 or 6 entries: match,mismatch,gap[,gapOpen[,gap2,gapOpen2]]")
             if ns.extend and ns.align_mode != "global":
                 self.error("--extend requires --align-mode global")
             if ns.xdrop < 0 or ns.xdrop > _capi.XDROP_MAX:
@@ -226,7 +233,9 @@ def _parser():
     ap.add_argument("--out-name", default="result")
     ap.add_argument("--out-ext", default=".txt")
     ap.add_argument("--scores", default="5,-3,-4",
-                    help="match,mismatch,gap (Distribution.java:36), or match,mismatch,gap,gapOpen for affine gaps (gapOpen <= 0)")
+                    help="match,mismatch,gap (Distribution.java:36), match,mismatch,gap,gapOpen for affine gaps (gapOpen <= 0), or "
+                         "match,mismatch,gap,gapOpen,gap2,gapOpen2 for two-piece gaps with --align-mode global: a gap of k bases costs "
+                         "max(gapOpen + k * gap, gapOpen2 + k * gap2)")
     ap.add_argument("--matrix", default=None,
                     help="a substitution score matrix file in the NCBI text format (row = read base, column = reference base); "
                          "bases outside its alphabet score match / mismatch from --scores")

@@ -36,8 +36,10 @@ def _algo(align_scores, align_types):
 
 @_contextlib.contextmanager
 def _scores(ctx, align_scores, align_mode=None, long_reads=None, band=None, extend=None, xdrop=None, band_adapt=None):
-    """alignScores {match, mismatch, gap} or {match, mismatch, gap, gapOpen}: yields the three entries make_params takes
-    and, for four, sets the context's "gap_open" for the call (affine gaps: a gap of length k costs gapOpen + k * gap).
+    """alignScores {match, mismatch, gap}, {match, mismatch, gap, gapOpen} or {match, mismatch, gap, gapOpen, gap2, gapOpen2}:
+    yields the three entries make_params takes and, for four, sets the context's "gap_open" for the call (affine gaps: a gap of
+    length k costs gapOpen + k * gap); for six also "gap2" and "gap_open2" (two-piece gaps on a global or extend run: a gap costs
+    max(gapOpen + k * gap, gapOpen2 + k * gap2); gapOpen2 = 0 is a one-piece run).
     align_mode (ALIGN_LOCAL / ALIGN_FIT / ALIGN_GLOBAL, or None: the context's own) is set for the call in the same way;
     long_reads (True / False, or None: the context's own) likewise sets option "long_reads": reads longer than 1024 bases on the
     affine kernels; band (a half-width, 0: none, or None: the context's own) sets option "band"; extend (True / False, or None:
@@ -46,8 +48,10 @@ def _scores(ctx, align_scores, align_mode=None, long_reads=None, band=None, exte
     band_adapt (True / False, or None: the context's own) sets option "band_adapt": the band of a banded extend run follows the
     alignment.  The options are put back afterwards."""
     sc = tuple(int(x) for x in align_scores)
-    if len(sc) == 4 and sc[3] > 0:
+    if len(sc) in (4, 6) and sc[3] > 0:
         raise ValueError("gapOpen (alignScores[3]) must be <= 0, got %d" % sc[3])
+    if len(sc) == 6 and (sc[4] > 0 or sc[5] > 0):
+        raise ValueError("gap2 and gapOpen2 (alignScores[4], [5]) must be <= 0, got %d, %d" % (sc[4], sc[5]))
     if align_mode is not None and align_mode not in (_capi.ALIGN_LOCAL, _capi.ALIGN_FIT, _capi.ALIGN_GLOBAL):
         raise ValueError("align_mode must be ALIGN_LOCAL, ALIGN_FIT or ALIGN_GLOBAL, got %r" % (align_mode,))
     if extend is not None and extend is not True and extend is not False:
@@ -58,9 +62,14 @@ def _scores(ctx, align_scores, align_mode=None, long_reads=None, band=None, exte
         raise ValueError("band_adapt must be None, True or False, got %r" % (band_adapt,))
     restore = []
     try:
-        if len(sc) == 4:
+        if len(sc) in (4, 6):
             restore.append(("gap_open", ctx.options.get("gap_open", 0)))
             ctx.set_option("gap_open", sc[3])
+        if len(sc) == 6:
+            restore.append(("gap2", ctx.options.get("gap2", 0)))
+            ctx.set_option("gap2", sc[4])
+            restore.append(("gap_open2", ctx.options.get("gap_open2", 0)))
+            ctx.set_option("gap_open2", sc[5])
         if align_mode is not None:
             restore.append(("align_mode", ctx.options.get("align_mode", _capi.ALIGN_LOCAL)))
             ctx.set_option("align_mode", int(align_mode))
