@@ -78,8 +78,8 @@
 //
 // How the 61 kernels are made: the 48 sweeps are aff_sweep_entry<RLO, RHI, MATRIX, MODE, LONG, BAND, XDROP, ADAPT, TWO> over one block function
 //   (aff_block8); the 13 tracebacks are aff_traceback<MODE, LONG, BAND, ADAPT, TWO>, where !LONG is the walk with one strip and !BAND the
-//   walk whose windows are the whole reference.  One macro defines the sweeps, one the tracebacks; the launchers pick a kernel
-//   from typed tables.  The per-pair sweep is two thin bodies, aff_sweep_pair and aff_sweep_long_pair<.., BAND> (the one strip
+//   walk whose windows are the whole reference.  One macro defines the sweeps, one the tracebacks; the launchers take the
+//   run's options as one AffRun (swmi_launch.h) and pick a kernel from tables typed by signature.  The per-pair sweep is two thin bodies, aff_sweep_pair and aff_sweep_long_pair<.., BAND> (the one strip
 //   loop, banded or not), over shared pieces: vrows and the cell list as functions of values, the row load, the block store
 //   and the epilogue as text (DESIGN.md 8e and 8f say why).
 #include <hip/hip_runtime.h>
@@ -1015,26 +1015,17 @@ AFF_TRACEBACK_KERNEL(sw_affine_traceback2_band_global_kernel, AFF_GLOBAL, true, 
 // ------------------------------------------------------------------------------------------------
 // host-callable launchers
 // ------------------------------------------------------------------------------------------------
-// align_mode: 0 local, 1 fit, 2 global (option "align_mode"), 3 extend (option "extend" on a global run: AFF_EXTEND)
-// mat / nn: the device image of the score matrix (swmi_aff_mat_words dwords) and its side n + 1 (2 .. 65), or null: the plain sweeps
-// long_reads 0: the narrow and the wide sweep; r_min / r_max: the rows per lane of the launch's shortest and longest read (only
-//   the kernels that have pairs are launched).  long_reads 1: the strip sweep (every pair has a read longer than 1024 bases)
-// band: with long_reads, the half-width of option "band" (0: none): the banded strip sweep
-// xdrop: with long_reads and align_mode 3, the threshold of option "xdrop" (0: none): the strip sweep that may stop at a seam
-// band_adapt: with long_reads, band and align_mode 3, option "band_adapt" (0 / 1): the banded strip sweep whose windows follow the
-//   alignment; every pair's workspace is then swmi_aff_adapt_work_words
-// gap_open2, gap2: option "gap_open2" (0: none) and "gap2": the two-piece sweeps, align_mode 2 and 3 without mat, xdrop and band_adapt;
-//   every pair's field is then swmi_aff2_dir_words / swmi_aff2_band_dir_words and its seam row swmi_aff2_seam_words
-extern "C" hipError_t swmi_launch_affine_sweep(const FillArgs *a, int32_t gap_open, uint32_t align_mode, const uint32_t *mat, uint32_t nn,
-                                               uint32_t r_min, uint32_t r_max, uint32_t long_reads, uint32_t band, uint32_t xdrop,
-                                               uint32_t band_adapt, int32_t gap_open2, int32_t gap2, hipStream_t st) {
+// Both take the run's options as one AffRun and refuse what aff_run_ok refuses (swmi_launch.h, which describes the arguments).
+// A kernel is picked from tables typed by signature -- ten for the sweeps: with / without the matrix, the half-width and the
+// threshold, and the two-piece sweeps with / without the half-width; two for the walks -- and launched through one generic
+// lambda, so that every launch is checked against its kernel's parameter list: one branch per signature.
+static_assert(AFF_EXTEND == 3, "AffRun.mode 3 is the extend run");
+
+extern "C" hipError_t swmi_launch_affine_sweep(const FillArgs *a, const AffRun *r, uint32_t long_reads, uint32_t r_min, uint32_t r_max,
+                                               hipStream_t st) {
     if (a->n_pairs == 0) return hipSuccess;
-    if (gap_open2 && (align_mode < 2u || align_mode > 3u || mat || xdrop || band_adapt)) return hipErrorInvalidValue;
-    if (align_mode > 3u || (mat && (nn < 2u || nn > SWMI_MAT_NN_MAX)) || band > SWMI_AFF_BAND_MAX) return hipErrorInvalidValue;
-    if (xdrop > 0x7FFFFFFFu || (xdrop && long_reads && align_mode != AFF_EXTEND)) return hipErrorInvalidValue;
-    if (band_adapt > 1u || (band_adapt && long_reads && (!band || align_mode != AFF_EXTEND))) return hipErrorInvalidValue;
-    // [narrow / wide / long][align_mode], and [align_mode] of the banded long sweeps: one typed table per signature (plain /
-    // matrix, without / with the half-width), so that a launch is checked against its kernel's parameter list
+    if (!aff_run_ok(*r, long_reads)) return hipErrorInvalidValue;
+    // [narrow / wide / long][mode]
     static void (*const plain[3][4])(FillArgs, int) = {
         {sw_affine_sweep_kernel, sw_affine_sweep_fit_kernel, sw_affine_sweep_global_kernel, sw_affine_sweep_extend_kernel},
         {sw_affine_sweep_wide_kernel, sw_affine_sweep_fit_wide_kernel, sw_affine_sweep_global_wide_kernel, sw_affine_sweep_extend_wide_kernel},
@@ -1045,21 +1036,19 @@ extern "C" hipError_t swmi_launch_affine_sweep(const FillArgs *a, int32_t gap_op
          sw_affine_sweep_extend_matrix_wide_kernel},
         {sw_affine_sweep_long_matrix_kernel, sw_affine_sweep_long_fit_matrix_kernel, sw_affine_sweep_long_global_matrix_kernel,
          sw_affine_sweep_long_extend_matrix_kernel}};
-    static void (*const bplain[4])(FillArgs, int, uint32_t) = {
-        sw_affine_sweep_band_kernel, sw_affine_sweep_band_fit_kernel, sw_affine_sweep_band_global_kernel, sw_affine_sweep_band_extend_kernel};
-    static void (*const bmatrix[4])(FillArgs, int, const uint32_t *, uint32_t, uint32_t) = {
+    // the banded strip sweeps, [mode] and, under option "band_adapt" (an extend run), [4]
+    static void (*const bplain[5])(FillArgs, int, uint32_t) = {
+        sw_affine_sweep_band_kernel, sw_affine_sweep_band_fit_kernel, sw_affine_sweep_band_global_kernel, sw_affine_sweep_band_extend_kernel,
+        sw_affine_sweep_band_adapt_kernel};
+    static void (*const bmatrix[5])(FillArgs, int, const uint32_t *, uint32_t, uint32_t) = {
         sw_affine_sweep_band_matrix_kernel, sw_affine_sweep_band_fit_matrix_kernel, sw_affine_sweep_band_global_matrix_kernel,
-        sw_affine_sweep_band_extend_matrix_kernel};
-    // the strip sweeps of an extend run under option "xdrop": the threshold is the last argument
+        sw_affine_sweep_band_extend_matrix_kernel, sw_affine_sweep_band_adapt_matrix_kernel};
+    // the strip sweeps of an extend run under option "xdrop" (the threshold is the last argument); the banded ones [band_adapt]
     static void (*const xplain)(FillArgs, int, uint32_t) = sw_affine_sweep_long_xdrop_kernel;
     static void (*const xmatrix)(FillArgs, int, const uint32_t *, uint32_t, uint32_t) = sw_affine_sweep_long_xdrop_matrix_kernel;
-    static void (*const xbplain)(FillArgs, int, uint32_t, uint32_t) = sw_affine_sweep_band_xdrop_kernel;
-    static void (*const xbmatrix)(FillArgs, int, const uint32_t *, uint32_t, uint32_t, uint32_t) = sw_affine_sweep_band_xdrop_matrix_kernel;
-    // the banded strip sweeps of an extend run under option "band_adapt", [xdrop]: the signatures of the banded sweeps
-    static void (*const aplain)(FillArgs, int, uint32_t) = sw_affine_sweep_band_adapt_kernel;
-    static void (*const amatrix)(FillArgs, int, const uint32_t *, uint32_t, uint32_t) = sw_affine_sweep_band_adapt_matrix_kernel;
-    static void (*const axplain)(FillArgs, int, uint32_t, uint32_t) = sw_affine_sweep_band_adapt_xdrop_kernel;
-    static void (*const axmatrix)(FillArgs, int, const uint32_t *, uint32_t, uint32_t, uint32_t) = sw_affine_sweep_band_adapt_xdrop_matrix_kernel;
+    static void (*const xbplain[2])(FillArgs, int, uint32_t, uint32_t) = {sw_affine_sweep_band_xdrop_kernel, sw_affine_sweep_band_adapt_xdrop_kernel};
+    static void (*const xbmatrix[2])(FillArgs, int, const uint32_t *, uint32_t, uint32_t, uint32_t) = {
+        sw_affine_sweep_band_xdrop_matrix_kernel, sw_affine_sweep_band_adapt_xdrop_matrix_kernel};
     // the two-piece sweeps, [narrow / wide / long][extend], and [extend] of the banded long ones
     static void (*const tplain[3][2])(FillArgs, int, int, int) = {
         {sw_affine_sweep2_global_kernel, sw_affine_sweep2_extend_kernel},
@@ -1067,61 +1056,53 @@ extern "C" hipError_t swmi_launch_affine_sweep(const FillArgs *a, int32_t gap_op
         {sw_affine_sweep2_long_global_kernel, sw_affine_sweep2_long_extend_kernel}};
     static void (*const tbplain[2])(FillArgs, int, int, int, uint32_t) = {sw_affine_sweep2_band_global_kernel, sw_affine_sweep2_band_extend_kernel};
     const dim3 grid((a->n_pairs + AFF_WAVES - 1) / AFF_WAVES), block(WAVE * AFF_WAVES);
-    const bool banded = long_reads && band;                       // (the long shape only)
-    const bool adapts = banded && band_adapt;
-    // (a launch's own error is what hipGetLastError returns below)
-    const bool stops = long_reads && xdrop;                       // (the long shape only)
-    const auto launch = [&](int shape) {
-        if (gap_open2 && banded) hipLaunchKernelGGL(tbplain[align_mode - 2u], grid, block, 0, st, *a, (int)gap_open, (int)gap_open2, (int)gap2, band);
-        else if (gap_open2)      hipLaunchKernelGGL(tplain[shape][align_mode - 2u], grid, block, 0, st, *a, (int)gap_open, (int)gap_open2, (int)gap2);
-        else if (adapts && stops && mat) hipLaunchKernelGGL(axmatrix, grid, block, 0, st, *a, (int)gap_open, mat, nn, band, xdrop);
-        else if (adapts && stops)   hipLaunchKernelGGL(axplain, grid, block, 0, st, *a, (int)gap_open, band, xdrop);
-        else if (adapts && mat)     hipLaunchKernelGGL(amatrix, grid, block, 0, st, *a, (int)gap_open, mat, nn, band);
-        else if (adapts)            hipLaunchKernelGGL(aplain, grid, block, 0, st, *a, (int)gap_open, band);
-        else if (stops && banded && mat) hipLaunchKernelGGL(xbmatrix, grid, block, 0, st, *a, (int)gap_open, mat, nn, band, xdrop);
-        else if (stops && banded)   hipLaunchKernelGGL(xbplain, grid, block, 0, st, *a, (int)gap_open, band, xdrop);
-        else if (stops && mat)      hipLaunchKernelGGL(xmatrix, grid, block, 0, st, *a, (int)gap_open, mat, nn, xdrop);
-        else if (stops)             hipLaunchKernelGGL(xplain, grid, block, 0, st, *a, (int)gap_open, xdrop);
-        else if (banded && mat) hipLaunchKernelGGL(bmatrix[align_mode], grid, block, 0, st, *a, (int)gap_open, mat, nn, band);
-        else if (banded)   hipLaunchKernelGGL(bplain[align_mode], grid, block, 0, st, *a, (int)gap_open, band);
-        else if (mat)      hipLaunchKernelGGL(matrix[shape][align_mode], grid, block, 0, st, *a, (int)gap_open, mat, nn);
-        else               hipLaunchKernelGGL(plain[shape][align_mode], grid, block, 0, st, *a, (int)gap_open);
+    // (extra...: what the kernel takes after the arguments every sweep takes.  A launch's own error is what hipGetLastError returns below)
+    const auto launch = [&](auto *k, auto... extra) { hipLaunchKernelGGL(k, grid, block, 0, st, *a, (int)r->gap_open, extra...); };
+    const uint32_t mode = r->mode, band = long_reads ? r->band : 0u, xdrop = long_reads ? r->xdrop : 0u;      // (options of the long shape only)
+    const uint32_t adapt = band ? r->adapt : 0u, nn = r->nn;
+    const uint32_t *const mat = r->mat;
+    const auto sweep = [&](int shape) {
+        if (r->gap_open2 && band)  launch(tbplain[mode - 2u], (int)r->gap_open2, (int)r->gap2, band);
+        else if (r->gap_open2)     launch(tplain[shape][mode - 2u], (int)r->gap_open2, (int)r->gap2);
+        else if (mat && band && xdrop) launch(xbmatrix[adapt], mat, nn, band, xdrop);
+        else if (mat && band)      launch(bmatrix[adapt ? 4u : mode], mat, nn, band);
+        else if (mat && xdrop)     launch(xmatrix, mat, nn, xdrop);
+        else if (mat)              launch(matrix[shape][mode], mat, nn);
+        else if (band && xdrop)    launch(xbplain[adapt], band, xdrop);
+        else if (band)             launch(bplain[adapt ? 4u : mode], band);
+        else if (xdrop)            launch(xplain, xdrop);
+        else                       launch(plain[shape][mode]);
     };
-    if (long_reads) launch(2);
+    if (long_reads) sweep(2);
     else {
-        if (r_min <= 4u) launch(0);
-        if (r_max >= 5u) launch(1);
+        if (r_min <= 4u) sweep(0);
+        if (r_max >= 5u) sweep(1);
     }
     return hipGetLastError();
 }
 
-// long_reads: the walk over the strips' fields (every pair of the launch has a read longer than 1024 bases)
-// band, band_adapt: as for the sweep
-// two: the fields are those of the two-piece sweeps (option "gap_open2"): align_mode 2 and 3 without band_adapt; the tile holds at
-//   least one block of 2 * R * 64 dwords
-extern "C" hipError_t swmi_launch_affine_traceback(const TraceArgs *a, uint32_t align_mode, uint32_t long_reads, uint32_t band, uint32_t band_adapt,
-                                                   uint32_t two, uint32_t tile_words, uint32_t ops_words, hipStream_t st) {
+extern "C" hipError_t swmi_launch_affine_traceback(const TraceArgs *a, const AffRun *r, uint32_t long_reads, uint32_t tile_words,
+                                                   uint32_t ops_words, hipStream_t st) {
     if (a->n_pairs == 0) return hipSuccess;
-    if (two > 1u || (two && (align_mode < 2u || align_mode > 3u || band_adapt || tile_words < 2u * SWMI_AFF_RMAX * WAVE))) return hipErrorInvalidValue;
-    if (align_mode > 3u || band > SWMI_AFF_BAND_MAX) return hipErrorInvalidValue;
-    if (band_adapt > 1u || (band_adapt && long_reads && (!band || align_mode != AFF_EXTEND))) return hipErrorInvalidValue;
+    if (!aff_run_ok(*r, long_reads)) return hipErrorInvalidValue;
+    const bool two = r->gap_open2 != 0;
+    // (the fields of the two-piece sweeps: the tile holds at least one block of 2 * R * 64 dwords)
+    if (two && tile_words < 2u * SWMI_AFF_RMAX * WAVE) return hipErrorInvalidValue;
     // an extend run is walked by global mode's kernels: aff_traceback<AFF_GLOBAL, ..> starts at whatever cell the list names and
     // makes no use of its being (m, n)
-    if (align_mode == AFF_EXTEND) align_mode = AFF_GLOBAL;
-    static void (*const kern[2][3])(TraceArgs, uint32_t, uint32_t) = {      // [long_reads][align_mode]
-        {sw_affine_traceback_kernel, sw_affine_traceback_fit_kernel, sw_affine_traceback_global_kernel},
-        {sw_affine_traceback_long_kernel, sw_affine_traceback_long_fit_kernel, sw_affine_traceback_long_global_kernel}};
-    static void (*const bkern[3])(TraceArgs, uint32_t, uint32_t, uint32_t) = {      // [align_mode]: the banded long walks
-        sw_affine_traceback_band_kernel, sw_affine_traceback_band_fit_kernel, sw_affine_traceback_band_global_kernel};
-    static void (*const akern)(TraceArgs, uint32_t, uint32_t, uint32_t) = sw_affine_traceback_band_adapt_global_kernel;   // ... under option "band_adapt"
-    static void (*const tkern[2])(TraceArgs, uint32_t, uint32_t) = {sw_affine_traceback2_global_kernel, sw_affine_traceback2_long_global_kernel};   // [long_reads]: two-piece
-    static void (*const tbkern)(TraceArgs, uint32_t, uint32_t, uint32_t) = sw_affine_traceback2_band_global_kernel;
+    const uint32_t mode = r->mode == AFF_EXTEND ? AFF_GLOBAL : r->mode;
+    // [long_reads][mode], then the two-piece walks [long_reads] (global mode's)
+    static void (*const kern[8])(TraceArgs, uint32_t, uint32_t) = {
+        sw_affine_traceback_kernel, sw_affine_traceback_fit_kernel, sw_affine_traceback_global_kernel,
+        sw_affine_traceback_long_kernel, sw_affine_traceback_long_fit_kernel, sw_affine_traceback_long_global_kernel,
+        sw_affine_traceback2_global_kernel, sw_affine_traceback2_long_global_kernel};
+    // the banded long walks, which take the half-width: [mode], then option "band_adapt"'s and the two-piece one (global mode's)
+    static void (*const bkern[5])(TraceArgs, uint32_t, uint32_t, uint32_t) = {
+        sw_affine_traceback_band_kernel, sw_affine_traceback_band_fit_kernel, sw_affine_traceback_band_global_kernel,
+        sw_affine_traceback_band_adapt_global_kernel, sw_affine_traceback2_band_global_kernel};
     static const bool attrs = [] {
-        for (int mode = 0; mode < 3; ++mode) {
-            swmi_allow_big_lds(kern[0][mode]); swmi_allow_big_lds(kern[1][mode]); swmi_allow_big_lds(bkern[mode]);
-        }
-        swmi_allow_big_lds(akern);
-        swmi_allow_big_lds(tkern[0]); swmi_allow_big_lds(tkern[1]); swmi_allow_big_lds(tbkern);
+        for (auto *k : kern) swmi_allow_big_lds(k);
+        for (auto *k : bkern) swmi_allow_big_lds(k);
         return true;
     }();
     (void)attrs;
@@ -1130,10 +1111,9 @@ extern "C" hipError_t swmi_launch_affine_traceback(const TraceArgs *a, uint32_t 
     const auto launch = [&](auto *k, auto... band) {
         hipLaunchKernelGGL(k, dim3(a->n_pairs, SWMI_AFF_TB_SLOTS), dim3(WAVE), lds, st, *a, tile_words, ops_words, band...);
     };
-    if (two && long_reads && band) launch(tbkern, band);
-    else if (two) launch(tkern[long_reads ? 1 : 0]);
-    else if (long_reads && band && band_adapt) launch(akern, band);
-    else if (long_reads && band) launch(bkern[align_mode], band);
-    else                    launch(kern[long_reads ? 1 : 0][align_mode]);
+    const uint32_t lng = long_reads ? 1u : 0u;
+    if (long_reads && r->band) launch(bkern[two ? 4u : r->adapt ? 3u : mode], r->band);
+    else                       launch(kern[two ? 6u + lng : 3u * lng + mode]);
     return hipGetLastError();
 }
+

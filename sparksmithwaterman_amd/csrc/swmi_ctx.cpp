@@ -347,7 +347,7 @@ int swmi_host::upload_device(swmi_ctx *ctx, swmi_batch *b, hipStream_t st, const
                                ctx->d_lut.as<uint8_t>(), n_reads, st));
     HIP_TRY(hipStreamSynchronize(st));
     // a new set of sequences invalidates everything derived from the old one
-    b->work_mode = -1; b->plan_key = PlanKey{}; b->pairs_dev_ptr = nullptr; b->pairs_on_device.clear();
+    b->work_key = SchedKey{}; b->plan_key = PlanKey{}; b->pairs_dev_ptr = nullptr; b->pairs_on_device.clear();
     b->has_run = false; b->acgt_known = false; b->auto_choice = -1;
     return SWMI_OK;
 }

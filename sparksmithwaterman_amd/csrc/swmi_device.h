@@ -259,12 +259,10 @@ SWMI_HD static inline uint32_t swmi_rows_per_lane(uint32_t m) {
     return r < 1u ? 1u : (r > SWMI_RMAX ? SWMI_RMAX : r);
 }
 // dwords of per-pair workspace.  mode 0: the direction field; mode 1: lane-state checkpoints + one maximum per
-// checkpoint window; mode 2: lane-state checkpoints; mode 3: the affine direction field (swmi_aff_dir_words).
+// checkpoint window; mode 2: lane-state checkpoints (mode 3, the affine kernels: swmi_aff_pair_dir_words below).
 // tfused: the context lets sw_tfused_kernel take pairs (option "tfused" = 1): such a pair keeps its column checkpoints in the
 // same region, which must then hold them.
-SWMI_HD static inline uint64_t swmi_aff_dir_words(uint32_t m, uint32_t n);
 SWMI_HD static inline uint64_t swmi_dir_words(uint32_t m, uint32_t n, uint32_t mode, bool tfused = false) {
-    if (mode == 3) return swmi_aff_dir_words(m, n);       // the affine pipeline: its 4-bit direction field
     uint32_t R = swmi_rows_per_lane(m);
     uint64_t strips = ((uint64_t)m + 64u * R - 1u) / (64u * R);
     uint64_t wblocks = ((uint64_t)n + 63u + 15u) / 16u;   // T = n + 63 steps at most
@@ -295,14 +293,6 @@ SWMI_HD static inline uint32_t swmi_aff_strips(uint32_t m) { return m ? (m + SWM
 SWMI_HD static inline uint32_t swmi_aff_strip_blocks(uint32_t n) { return (uint32_t)(((uint64_t)n + 63u + 7u) / 8u); }
 // dwords of one strip's field: [block][row slot][lane]
 SWMI_HD static inline uint64_t swmi_aff_strip_words(uint32_t n) { return (uint64_t)swmi_aff_strip_blocks(n) * SWMI_AFF_RMAX * 64u; }
-// dwords of a pair's affine direction field: one dword per (block, row slot, lane); m > 1024: the strips' fields, consecutive
-SWMI_HD static inline uint64_t swmi_aff_dir_words(uint32_t m, uint32_t n) {
-    if (m > SWMI_AFF_MAX_READ) return (uint64_t)swmi_aff_strips(m) * swmi_aff_strip_words(n);
-    return (uint64_t)swmi_aff_blocks(m, n) * swmi_aff_rows_per_lane(m) * 64u;
-}
-// dwords of a mode-3 pair's seam row: (H, F) of the strip's last row at every column, one row rewritten in place by every
-// strip but the last (reads of one strip have none)
-SWMI_HD static inline uint64_t swmi_aff_seam_words(uint32_t m, uint32_t n) { return m > SWMI_AFF_MAX_READ ? 2ull * n : 0ull; }
 // ---- option "band" (half-width w >= 1, reads longer than SWMI_AFF_MAX_READ only): strip s sweeps the WINDOW of columns
 // swmi_aff_band_lo(s, w) .. swmi_aff_band_hi(s, n, w) -- the band |j - i| <= w rounded outwards to the strip -- and leaves the
 // field of a (1024, window length) pair; the strips' fields are consecutive, now of unequal size.  The host refuses a pair with
@@ -341,19 +331,13 @@ SWMI_HD static inline uint64_t swmi_aff_band_blocks_before(uint32_t s, uint32_t 
          + k2 * mid
          + k3 * (((uint64_t)n + w + 70u) / 8u) - 64ull * k3 * (2u * q + k3 - 1u);
 }
-// dword offset of strip s's field in the pair's, and the whole field of a banded pair (m > 1024)
+// dword offset of strip s's field in the pair's (s = the pair's strips: the dwords of the whole field)
 SWMI_HD static inline uint64_t swmi_aff_band_strip_off(uint32_t s, uint32_t n, uint32_t w) {
     return swmi_aff_band_blocks_before(s, n, w) * SWMI_AFF_RMAX * 64u;
-}
-SWMI_HD static inline uint64_t swmi_aff_band_dir_words(uint32_t m, uint32_t n, uint32_t w) {
-    return swmi_aff_band_strip_off(swmi_aff_strips(m), n, w);
 }
 // ---- option "gap_open2" (two-piece gaps, global and extend runs): the field has two 4-bit planes, interleaved per
 // 8-step block -- dword ((w * 2 + plane) * R + k) * 64 + lane -- so every block, strip and field is twice the one-piece size, and
 // the seam row carries (H, F1, F2) per column in 16-byte entries.  A traceback tile must hold one block: 2 * 16 * 64 dwords. ----
-SWMI_HD static inline uint64_t swmi_aff2_dir_words(uint32_t m, uint32_t n) { return 2ull * swmi_aff_dir_words(m, n); }
-SWMI_HD static inline uint64_t swmi_aff2_band_dir_words(uint32_t m, uint32_t n, uint32_t w) { return 2ull * swmi_aff_band_dir_words(m, n, w); }
-SWMI_HD static inline uint64_t swmi_aff2_seam_words(uint32_t m, uint32_t n) { return m > SWMI_AFF_MAX_READ ? 4ull * n : 0ull; }
 static_assert(2u * SWMI_AFF_RMAX * 64u <= SWMI_AFF_TILE_WORDS, "a two-plane block fits the traceback tile");
 // ---- option "band_adapt" (with band = w and option "extend"): the window of strip s follows a CENTRE c that the
 // sweep takes from the seam row above the strip -- c_lo = max(1, c + 1 - w), c_hi = min(n, c + 1024 + w), 0 <= c <= n; c = 0 is
@@ -364,18 +348,33 @@ SWMI_HD static inline uint32_t swmi_aff_adapt_lo(uint32_t c, uint32_t w) { retur
 SWMI_HD static inline uint32_t swmi_aff_adapt_hi(uint32_t c, uint32_t n, uint32_t w) {       // (c <= n; w <= SWMI_AFF_BAND_MAX)
     return n - c > SWMI_AFF_MAX_READ + w ? c + SWMI_AFF_MAX_READ + w : n;
 }
-// dwords of one strip's field, of the pair's NS fields, and of the pair's workspace: the fields and the table, which is rounded
-// to 64 dwords so that the next pair's field stays 256-byte aligned
+// dwords of one strip's field
 SWMI_HD static inline uint64_t swmi_aff_adapt_strip_words(uint32_t n, uint32_t w) {
     const uint64_t cols = (uint64_t)SWMI_AFF_MAX_READ + 2ull * w;
     return swmi_aff_strip_words(cols < n ? (uint32_t)cols : n);
 }
-SWMI_HD static inline uint64_t swmi_aff_adapt_dir_words(uint32_t m, uint32_t n, uint32_t w) {
-    return (uint64_t)swmi_aff_strips(m) * swmi_aff_adapt_strip_words(n, w);
+// ---- a mode-3 pair's workspace under the run's options.  AffGeom holds the options that decide it, and these three functions alone
+// choose between the layouts above: an option that changes it is a member and a case here (SchedKey, swmi_host.h, keys on the struct) ----
+struct AffGeom {
+    uint32_t band;       // option "band": the half-width, 0: none (it shapes the fields of reads longer than SWMI_AFF_MAX_READ only)
+    bool adapt, two;     // options "band_adapt" (with band, never with two) and "gap_open2"
+    bool operator==(const AffGeom &o) const { return band == o.band && adapt == o.adapt && two == o.two; }
+};
+// dwords of the pair's direction fields (m > 1024: the strips', consecutive) = where the window table of "band_adapt" starts
+SWMI_HD static inline uint64_t swmi_aff_pair_table_off(uint32_t m, uint32_t n, AffGeom g) {
+    const uint64_t planes = g.two ? 2u : 1u, ns = swmi_aff_strips(m);
+    if (m <= SWMI_AFF_MAX_READ) return planes * swmi_aff_blocks(m, n) * swmi_aff_rows_per_lane(m) * 64u;
+    if (!g.band) return planes * ns * swmi_aff_strip_words(n);                      // every strip the whole reference
+    if (g.adapt) return ns * swmi_aff_adapt_strip_words(n, g.band);                 // a fixed stride per strip
+    return planes * swmi_aff_band_strip_off((uint32_t)ns, n, g.band);               // the strips' windows: the offset of strip NS
 }
-SWMI_HD static inline uint64_t swmi_aff_adapt_work_words(uint32_t m, uint32_t n, uint32_t w) {
-    return swmi_aff_adapt_dir_words(m, n, w) + (((uint64_t)swmi_aff_strips(m) + 63u) & ~63ull);
+// what the pair is charged in the launch's `dir` workspace: the fields and, under "band_adapt", the table -- one dword per strip,
+// rounded to 64 dwords so that the next pair's field stays 256-byte aligned
+SWMI_HD static inline uint64_t swmi_aff_pair_dir_words(uint32_t m, uint32_t n, AffGeom g) {
+    return swmi_aff_pair_table_off(m, n, g) + (g.band && g.adapt && m > SWMI_AFF_MAX_READ ? ((uint64_t)swmi_aff_strips(m) + 63u) & ~63ull : 0ull);
 }
+// dwords of the pair's seam row: (H, F) per column, two-piece 16 bytes; ONE row, rewritten in place by every strip but the last
+SWMI_HD static inline uint64_t swmi_aff_pair_seam_words(uint32_t m, uint32_t n, AffGeom g) { return m > SWMI_AFF_MAX_READ ? (g.two ? 4ull : 2ull) * n : 0ull; }
 // score matrices (swmi_set_score_matrix) on the affine sweeps: at most 64 symbols, plus class n = outside the alphabet.
 // Device image: 256 key dwords by base code (class * 4 | hi << 16, hi = the code outside the alphabet, else 0x1FF), then the
 // (n+1) x (n+1) int32 scores, row = read class, column = reference class (row and column n are not read: the kernel fills them).

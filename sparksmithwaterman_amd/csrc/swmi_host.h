@@ -138,6 +138,22 @@ static inline int64_t swmi_adapt_low(uint64_t m, uint64_t n, int64_t gap_open, i
 static inline bool swmi_adapt_bound_ok(uint64_t m, uint64_t n, int64_t gap_open, int64_t gap) {
     return swmi_adapt_low(m, n, gap_open, gap) >= -((int64_t)1 << 30);
 }
+// the options that decide the size of a mode-3 pair's workspace (swmi_device.h), as a run has them
+static inline AffGeom aff_geom(const RunModes &md) {
+    return AffGeom{md.band > 0 ? (uint32_t)md.band : 0u, md.band > 0 && md.band_adapt != 0, md.two_piece()};
+}
+// Everything a batch's schedule (swmi_batch::work: the pairs in launch order with their workspace sizes) depends on besides the
+// sequences.  A run whose key equals the key of the schedule the batch holds keeps it.  An input of the sizes that is missing
+// here hands a re-run under other options a schedule with the old sizes -- but an option that changes a mode-3 pair's workspace
+// is a member of AffGeom, which is part of the key as it is: add it there (and to aff_geom), not here.
+struct __attribute__((visibility("hidden"))) SchedKey {
+    int eff_mode = -1;                      // the pipeline the sizes were made for; -1: no schedule (a new upload, a schedule handed on)
+    bool tfused = false;                    // the sizes leave room for sw_tfused_kernel's column checkpoints
+    AffGeom geom{};                         // mode 3: the run's; all-zero under the other modes
+    SchedKey() = default;
+    SchedKey(uint32_t mode, bool tf, const RunModes &md) : eff_mode((int)mode), tfused(tf), geom(mode == 3 ? aff_geom(md) : AffGeom{}) {}
+    bool operator==(const SchedKey &o) const { return eff_mode == o.eff_mode && tfused == o.tfused && geom == o.geom; }
+};
 struct __attribute__((visibility("hidden"))) RunOptions {
     RunModes modes;
     std::shared_ptr<const ScoreMatrix> mat; // swmi_set_score_matrix (null: none); keeps the matrix's host image alive
@@ -304,12 +320,8 @@ struct swmi_batch {
     bool has_run = false;
     int auto_choice = -1;                   // sampled pre-pass of the automatic traceback grain: 0 tie-heavy, 1 not, -1 not decided yet
     swmi_params auto_params{};
-    std::vector<Work> work;                 // schedule (pairs sorted by work), valid for work_mode
-    int work_mode = -1;
-    int work_band = 0;                      // the band the schedule's workspace sizes were made for (mode 3)
-    int work_adapt = 0;                     // ... and option "band_adapt" (its fields have a fixed stride and a window table behind them)
-    bool work_two = false;                  // ... and option "gap_open2" (two planes, 16-byte seam entries)
-    bool work_tfused = false;               // the schedule's workspace sizes leave room for sw_tfused_kernel's column checkpoints
+    std::vector<Work> work;                 // schedule (pairs sorted by work), valid for work_key
+    SchedKey work_key;                      // reset or moved together with `work`
     uint32_t eff_mode = 1;                  // pipeline of the current run (3: the affine kernels, swmi_affine.hip)
     int32_t gap_open = 0;                   // the context's gap_open when the run started (mode 3)
     RunOptions opt;                         // the context's run options when the run was asked for (mode 3)

@@ -18,10 +18,35 @@ extern "C" hipError_t swmi_launch_traceback(const TraceArgs *a, hipStream_t st, 
 extern "C" hipError_t swmi_launch_traceback_split(const TraceArgs *a, uint32_t n_windows, hipStream_t st);
 extern "C" hipError_t swmi_launch_resident(const TraceArgs *a, const ResidentArgs *x, hipStream_t st);
 extern "C" hipError_t swmi_launch_tfused(const TraceArgs *a, const TFusedArgs *x, hipStream_t st);
-extern "C" hipError_t swmi_launch_affine_sweep(const FillArgs *a, int32_t gap_open, uint32_t align_mode, const uint32_t *mat, uint32_t nn,
-                                               uint32_t r_min, uint32_t r_max, uint32_t long_reads, uint32_t band, uint32_t xdrop,
-                                               uint32_t band_adapt, int32_t gap_open2, int32_t gap2, hipStream_t st);
-extern "C" hipError_t swmi_launch_affine_traceback(const TraceArgs *a, uint32_t align_mode, uint32_t long_reads, uint32_t band, uint32_t band_adapt,
-                                                   uint32_t two, uint32_t tile_words, uint32_t ops_words, hipStream_t st);
+// What the two launchers of the affine kernels (swmi_affine.hip) need from a run's options.  The host runtime builds one per run
+// (aff_run in swmi_run.cpp, the only place) and passes the same one to the launch of the short shape and of the long shape.
+struct AffRun {
+    int32_t gap_open;            // a gap of length k costs gap_open + k * gap
+    int32_t gap_open2, gap2;     // option "gap_open2" (0: none) and "gap2": the two-piece kernels
+    uint32_t mode;               // 0 local, 1 fit, 2 global (option "align_mode"), 3 extend (option "extend" on a global run)
+    uint32_t band;               // option "band": the half-width (0: none) -- the banded strip kernels
+    uint32_t xdrop;              // option "xdrop": the threshold (0: none) -- the strip sweep that may stop at a seam
+    uint32_t adapt;              // option "band_adapt" (0 / 1) -- the banded strip kernels whose windows follow the alignment
+    const uint32_t *mat;         // the device image of the score matrix (swmi_aff_mat_words dwords), or null: the plain sweeps
+    uint32_t nn;                 // ... and its side n + 1 (2 .. SWMI_MAT_NN_MAX)
+};
+// What the launchers refuse (hipErrorInvalidValue): the combinations no kernel exists for.  band, xdrop and adapt are options of
+// the long shape (long_reads: every pair of the launch has a read longer than SWMI_AFF_MAX_READ); the short shape ignores them.
+// Every run check_run_params (swmi_run.cpp) admits passes.
+static inline bool aff_run_ok(const AffRun &r, uint32_t long_reads) {
+    if (r.mode > 3u || r.band > SWMI_AFF_BAND_MAX || r.xdrop > 0x7FFFFFFFu || r.adapt > 1u) return false;
+    if (r.mat && (r.nn < 2u || r.nn > SWMI_MAT_NN_MAX)) return false;
+    if (r.gap_open2 && (r.mode < 2u || r.mat || r.xdrop || r.adapt)) return false;      // two-piece: plain global and extend runs
+    if (long_reads && r.xdrop && r.mode != 3u) return false;                            // xdrop: extend runs
+    if (long_reads && r.adapt && (!r.band || r.mode != 3u)) return false;               // band_adapt: banded extend runs
+    return true;
+}
+// long_reads 0: the pairs with reads of at most SWMI_AFF_MAX_READ bases; r_min / r_max: the rows per lane of the launch's shortest
+// and longest read (the narrow and the wide sweep: only the one that has pairs is launched).  long_reads 1: the strip kernels.
+extern "C" hipError_t swmi_launch_affine_sweep(const FillArgs *a, const AffRun *r, uint32_t long_reads, uint32_t r_min, uint32_t r_max,
+                                               hipStream_t st);
+// tile_words, ops_words: the LDS dwords of a wavefront's direction tile and of its packed ops
+extern "C" hipError_t swmi_launch_affine_traceback(const TraceArgs *a, const AffRun *r, uint32_t long_reads, uint32_t tile_words,
+                                                   uint32_t ops_words, hipStream_t st);
 extern "C" hipError_t swmi_launch_encode(const uint8_t *raw, const uint64_t *raw_off, SeqDesc *desc, uint32_t *seqw,
                                          const uint8_t *lut, uint32_t n_seq, hipStream_t st);

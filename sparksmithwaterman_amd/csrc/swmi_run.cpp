@@ -239,6 +239,19 @@ static TFusedArgs tfused_args(const swmi_batch *b) {
     return xt;
 }
 
+// The affine launch descriptor of the batch's run (swmi_launch.h) -- built here and nowhere else.
+static inline AffRun aff_run(const swmi_batch *b) {
+    const RunModes &md = b->opt.modes;
+    AffRun r{};
+    r.gap_open = b->gap_open;
+    r.gap_open2 = md.gap_open2; r.gap2 = md.gap_open2 ? md.gap2 : 0;      // (gap2 is not read without gap_open2)
+    r.mode = md.kernel_mode();
+    r.band = (uint32_t)md.band; r.xdrop = (uint32_t)md.xdrop; r.adapt = (uint32_t)md.band_adapt;
+    r.mat = b->opt.mat ? b->d_mat.as<uint32_t>() : nullptr;
+    r.nn = b->opt.mat ? b->opt.mat->n + 1u : 0u;
+    return r;
+}
+
 // every kernel of one attempt onto the stream, with the profiling events around them and, without zero-copy, the D2H copies
 static int enqueue_launches(RunState &rs, Launch &L, const ResidentArgs &xa, const TFusedArgs &xt) {
     swmi_ctx *ctx = rs.ctx;
@@ -248,6 +261,7 @@ static int enqueue_launches(RunState &rs, Launch &L, const ResidentArgs &xa, con
     TraceArgs &ta = rs.ta;
     const size_t np = L.np, n_res = plan.n_res, n_tf = plan.n_tf;
     const bool first = L.attempt == 0;
+    const AffRun ar = aff_run(b);       // (read by the mode-3 launches only)
     int rc;
     // diagnostics (SWMI_EXT_EVENTS=1): the plain case -- one sweep kernel, one traceback kernel -- timed by the kernels' own
     // dispatches instead of by events around them (the three events cost 3.5 us per run, tests/manual/prof_events_ab.py;
@@ -263,15 +277,9 @@ static int enqueue_launches(RunState &rs, Launch &L, const ResidentArgs &xa, con
             FillArgs fs = fa, fl = fa;
             fs.n_pairs = (uint32_t)(np - plan.aff_n_long);
             fl.n_pairs = (uint32_t)plan.aff_n_long; fl.pairs = fa.pairs + fs.n_pairs;
-            const uint32_t *mat = b->opt.mat ? b->d_mat.as<uint32_t>() : nullptr;
-            const uint32_t nn = b->opt.mat ? b->opt.mat->n + 1u : 0u;
-            // (option "gap_open2": the two-piece sweeps; gap2 is not read without it)
-            const int32_t o2 = b->opt.modes.gap_open2, e2 = o2 ? b->opt.modes.gap2 : 0;
-            HIP_TRY(swmi_launch_affine_sweep(&fs, b->gap_open, b->opt.modes.kernel_mode(), mat, nn, plan.aff_r_min, plan.aff_r_max, 0u, 0u, 0u, 0u, o2, e2, ctx->stream));
-            // (option "band": the banded strip sweep; the other pairs are swept in full.  Option "xdrop": the strip sweep that may
-            // end at a seam; the other pairs take the kernels they take without it)
-            HIP_TRY(swmi_launch_affine_sweep(&fl, b->gap_open, b->opt.modes.kernel_mode(), mat, nn, 0u, 0u, 1u, (uint32_t)b->opt.modes.band,
-                                             (uint32_t)b->opt.modes.xdrop, (uint32_t)b->opt.modes.band_adapt, o2, e2, ctx->stream));
+            // (options "band", "xdrop" and "band_adapt" are the strip kernels': the other pairs take the kernels they take without them)
+            HIP_TRY(swmi_launch_affine_sweep(&fs, &ar, 0u, plan.aff_r_min, plan.aff_r_max, ctx->stream));
+            HIP_TRY(swmi_launch_affine_sweep(&fl, &ar, 1u, 0u, 0u, ctx->stream));
         }
         else HIP_TRY(swmi_launch_fill(&fa, ctx->stream, ext ? ctx->ev[0] : nullptr, ext ? ctx->ev[1] : nullptr));
         rs.launches++;
@@ -301,10 +309,8 @@ static int enqueue_launches(RunState &rs, Launch &L, const ResidentArgs &xa, con
         tl.n_pairs = (uint32_t)plan.aff_n_long; tl.pairs = ta.pairs + ts.n_pairs;
         const uint32_t ops_words = (uint32_t)(((uint64_t)plan.max_path + 15) / 16 + 1);
         // (option "gap_open2": a block of the field is 2 * R * 64 dwords, and SWMI_AFF_TILE_WORDS holds one -- swmi_device.h)
-        const uint32_t two = b->opt.modes.two_piece() ? 1u : 0u;
-        HIP_TRY(swmi_launch_affine_traceback(&ts, b->opt.modes.kernel_mode(), 0u, 0u, 0u, two, SWMI_AFF_TILE_WORDS, ops_words, ctx->stream));
-        HIP_TRY(swmi_launch_affine_traceback(&tl, b->opt.modes.kernel_mode(), 1u, (uint32_t)b->opt.modes.band, (uint32_t)b->opt.modes.band_adapt,
-                                             two, SWMI_AFF_TILE_WORDS, ops_words, ctx->stream));
+        HIP_TRY(swmi_launch_affine_traceback(&ts, &ar, 0u, SWMI_AFF_TILE_WORDS, ops_words, ctx->stream));
+        HIP_TRY(swmi_launch_affine_traceback(&tl, &ar, 1u, SWMI_AFF_TILE_WORDS, ops_words, ctx->stream));
     } else if (n_res + n_tf < np) {
         HIP_TRY(swmi_launch_traceback(&ta, ctx->stream, ext ? ctx->ev[2] : nullptr, ext ? ctx->ev[3] : nullptr));
     }
@@ -437,13 +443,13 @@ static int fetch_windows(swmi_batch *b, const std::vector<Work> &work, size_t lo
     if (b->eff_mode != 3 || !b->opt.modes.band_adapt || !plan.aff_n_long) return SWMI_OK;
     const size_t np = b->pairs_on_device.size() / sizeof(PairDesc);
     const PairDesc *pd = (const PairDesc *)b->pairs_on_device.data();
-    const uint32_t w = (uint32_t)b->opt.modes.band;
+    const AffGeom g = aff_geom(b->opt.modes);
     if (b->win_at.size() != b->pairs.size()) b->win_at.assign(b->pairs.size(), 0);
     for (size_t k = np - plan.aff_n_long; k < np; k++) {
         const uint32_t pair = work[lo + pd[k].out_id].pair;
         const uint32_t m = b->read_desc[pd[k].read_id].len, n = b->ref_desc[pd[k].ref_id].len, ns = swmi_aff_strips(m);
         if (!b->win_at[pair]) { b->win_at[pair] = b->win_tab.size() + 1; b->win_tab.resize(b->win_tab.size() + ns, 0u); }
-        HIP_TRY(hipMemcpy(b->win_tab.data() + (b->win_at[pair] - 1), b->d_dir.as<uint32_t>() + pd[k].dir_off + swmi_aff_adapt_dir_words(m, n, w),
+        HIP_TRY(hipMemcpy(b->win_tab.data() + (b->win_at[pair] - 1), b->d_dir.as<uint32_t>() + pd[k].dir_off + swmi_aff_pair_table_off(m, n, g),
                           (size_t)ns * sizeof(uint32_t), hipMemcpyDeviceToHost));
     }
     return SWMI_OK;
@@ -586,9 +592,7 @@ static int check_band(const swmi_ctx *ctx, const swmi_batch *b, const swmi_param
                         "read (%llu) and reference (%llu) is below -2^30", band, (long long)low, (unsigned long long)max_m, (unsigned long long)max_n);
     }
     // the field of the largest pair alone against the workspace cap (it grows with m and with n)
-    const uint64_t bytes = (md.band_adapt ? swmi_aff_adapt_work_words((uint32_t)max_m, (uint32_t)max_n, (uint32_t)band)
-                            : md.two_piece() ? swmi_aff2_band_dir_words((uint32_t)max_m, (uint32_t)max_n, (uint32_t)band)
-                                             : swmi_aff_band_dir_words((uint32_t)max_m, (uint32_t)max_n, (uint32_t)band)) * 4;
+    const uint64_t bytes = swmi_aff_pair_dir_words((uint32_t)max_m, (uint32_t)max_n, aff_geom(md)) * 4;
     if (bytes > ctx->max_workspace_bytes && md.two_piece())
         return fail(SWMI_ERR_UNSUPPORTED, "band %d, gap_open2: the two-plane direction field of the longest read (%llu) against the longest reference (%llu) "
                     "takes %llu bytes (twice the one-piece field), more than max_workspace_bytes (%llu)", band, (unsigned long long)max_m,
@@ -668,16 +672,16 @@ static int check_run_params(const swmi_ctx *ctx, const swmi_batch *b, const swmi
             }
             // a pair of several strips is one launch's work at the least: refused when its field alone is over the cap
             // (a banded run is checked with its own, smaller field in check_band)
-            if (md.band <= 0 && md.two_piece() && max_m > SWMI_AFF_MAX_READ && max_n &&
-                swmi_aff2_dir_words((uint32_t)max_m, (uint32_t)max_n) * 4 > ctx->max_workspace_bytes)
+            const uint64_t bytes = md.band <= 0 && max_m > SWMI_AFF_MAX_READ && max_n
+                                       ? swmi_aff_pair_dir_words((uint32_t)max_m, (uint32_t)max_n, aff_geom(md)) * 4 : 0;
+            if (bytes > ctx->max_workspace_bytes && md.two_piece())
                 return fail(SWMI_ERR_UNSUPPORTED, "long_reads, gap_open2: the two-plane direction field of the longest read (%llu) against the longest "
                             "reference (%llu) takes %llu bytes (twice the one-piece field), more than max_workspace_bytes (%llu)", (unsigned long long)max_m,
-                            (unsigned long long)max_n, (unsigned long long)(swmi_aff2_dir_words((uint32_t)max_m, (uint32_t)max_n) * 4),
-                            (unsigned long long)ctx->max_workspace_bytes);
-            if (md.band <= 0 && max_m > SWMI_AFF_MAX_READ && max_n && swmi_aff_dir_words((uint32_t)max_m, (uint32_t)max_n) * 4 > ctx->max_workspace_bytes)
+                            (unsigned long long)max_n, (unsigned long long)bytes, (unsigned long long)ctx->max_workspace_bytes);
+            if (bytes > ctx->max_workspace_bytes)
                 return fail(SWMI_ERR_UNSUPPORTED, "long_reads: the direction field of the longest read (%llu) against the longest reference (%llu) "
                             "takes %llu bytes, more than max_workspace_bytes (%llu)", (unsigned long long)max_m, (unsigned long long)max_n,
-                            (unsigned long long)(swmi_aff_dir_words((uint32_t)max_m, (uint32_t)max_n) * 4), (unsigned long long)ctx->max_workspace_bytes);
+                            (unsigned long long)bytes, (unsigned long long)ctx->max_workspace_bytes);
         }
         if (md.align_mode == SWMI_ALIGN_GLOBAL) {
             // global mode: the smallest sum a sweep forms is 3 * gap_open + (64 * ceil(m / 64) + n) * gap (swmi.h, DESIGN.md
@@ -755,18 +759,11 @@ static int choose_traceback_grain(swmi_ctx *ctx, swmi_batch *b, const swmi_param
 }
 
 // The schedule: every pair with two non-empty sides (pairs with an empty side never enter ScoreMatrix's loops,
-// SmithWaterman.java:157-159: (0, [])).  It only depends on the sequence lengths and the pipeline mode: built once per batch.
+// SmithWaterman.java:157-159: (0, [])).  It depends on the sequence lengths and the run's SchedKey only: kept until one of them changes.
 static void build_schedule(const swmi_ctx *ctx, swmi_batch *b) {
-    const int band = b->eff_mode == 3 ? b->opt.modes.band : 0;
-    const int adapt = band > 0 ? b->opt.modes.band_adapt : 0;
-    const bool two = b->eff_mode == 3 && b->opt.modes.two_piece();
-    if (b->work_mode == (int)b->eff_mode && b->work_tfused == (ctx->tfused == 1) && b->work_band == band && b->work_adapt == adapt &&
-        b->work_two == two) return;
+    const SchedKey key(b->eff_mode, ctx->tfused == 1, b->opt.modes);
+    if (b->work_key == key) return;
     const uint32_t n_refs = b->n_refs, n_reads = b->n_reads;
-    b->work_tfused = ctx->tfused == 1;
-    b->work_band = band;
-    b->work_adapt = adapt;
-    b->work_two = two;
     b->work.clear();
     b->work.reserve((uint64_t)n_refs * n_reads);
     b->work_cells = 0;
@@ -780,10 +777,11 @@ static void build_schedule(const swmi_ctx *ctx, swmi_batch *b) {
     std::stable_sort(ro.begin(), ro.end(), [&](uint32_t a, uint32_t c) { return b->ref_desc[a].len > b->ref_desc[c].len; });
     std::stable_sort(qo.begin(), qo.end(), [&](uint32_t a, uint32_t c) { return b->read_desc[a].len > b->read_desc[c].len; });
     const bool refs_uniform = n_refs && b->ref_desc[ro.front()].len == b->ref_desc[ro.back()].len;
-    // (mode 3: the seam row of a read of several strips, none otherwise)
-    const bool aff = b->eff_mode == 3;
-    // (option "gap_open2": 16-byte seam entries and two planes of the field -- every pair of such a run)
-    auto seam_words = [aff, two](uint32_t m, uint32_t n) { return two ? swmi_aff2_seam_words(m, n) : aff ? swmi_aff_seam_words(m, n) : swmi_seam_words(m, n); };
+    // (mode 3: what the run's options make of a pair's field and seam row -- swmi_aff_pair_*, swmi_device.h)
+    const bool aff = b->eff_mode == 3, tf = key.tfused;
+    const AffGeom g = key.geom;
+    auto seam_words = [aff, g](uint32_t m, uint32_t n) { return aff ? swmi_aff_pair_seam_words(m, n, g) : swmi_seam_words(m, n); };
+    auto dir_words = [&](uint32_t m, uint32_t n) { return aff ? swmi_aff_pair_dir_words(m, n, g) : swmi_dir_words(m, n, b->eff_mode, tf); };
     auto add = [&](uint32_t r, uint32_t q, uint32_t n, uint32_t m, uint64_t dw, uint64_t sw) {
         Work w;
         w.pair = r * n_reads + q;
@@ -791,14 +789,6 @@ static void build_schedule(const swmi_ctx *ctx, swmi_batch *b) {
         w.dir_words = dw; w.seam_words = sw;
         b->work_cells += w.cells;
         b->work.push_back(w);
-    };
-    const bool tf = ctx->tfused == 1;
-    // (option "band": a read of several strips leaves the field of its windows only; option "band_adapt": fields of a fixed
-    // stride and the window table, which is charged to the launch's workspace with them)
-    auto dir_words = [&](uint32_t m, uint32_t n) {
-        if (adapt && m > SWMI_AFF_MAX_READ) return swmi_aff_adapt_work_words(m, n, (uint32_t)band);
-        if (two) return band > 0 && m > SWMI_AFF_MAX_READ ? swmi_aff2_band_dir_words(m, n, (uint32_t)band) : swmi_aff2_dir_words(m, n);
-        return band > 0 && m > SWMI_AFF_MAX_READ ? swmi_aff_band_dir_words(m, n, (uint32_t)band) : swmi_dir_words(m, n, b->eff_mode, tf);
     };
     if (refs_uniform) {                              // (reads outermost: descending m x the one n)
         for (uint32_t q : qo) {
@@ -824,7 +814,7 @@ static void build_schedule(const swmi_ctx *ctx, swmi_batch *b) {
             }
         }
     }
-    b->work_mode = (int)b->eff_mode;
+    b->work_key = key;
 }
 
 // the end of the launch that starts at work[lo]: as many pairs as fit the workspace cap (always at least one)

@@ -88,8 +88,8 @@ static int stream_process(swmi_stream *s, swmi_stream::Slot &sl, StreamChunk *c)
     r->read_bytes = s->read_bytes;
     r->ref_desc = b->ref_desc; r->read_desc = b->read_desc;
     r->params = b->params; r->has_run = true; r->eff_mode = b->eff_mode;
-    r->work = std::move(b->work); b->work.clear(); b->work_mode = -1;
-    r->work_mode = (int)r->eff_mode;
+    r->work = std::move(b->work); b->work.clear();
+    r->work_key = b->work_key; b->work_key = SchedKey{};      // (the key goes where the schedule goes)
     r->pairs = std::move(b->pairs);
     // (swmi_pair_band_window: the run's modes -- not its matrix, which a results-only batch has no use for -- and, under option
     // "band_adapt", the window tables the sweeps left)

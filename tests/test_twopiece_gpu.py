@@ -17,6 +17,7 @@ import pytest
 import sparksmithwaterman_amd as sw
 from sparksmithwaterman_amd import _capi
 
+import adapt_reference as ar
 import affine_gpu_util as u
 import affine_grid_cases as gc
 import gotoh_reference as gr
@@ -406,7 +407,38 @@ def test_doubled_field_and_the_workspace_cap(ctx):
     b.free()
 
 
-# 10 -- the JNI shim's entry point from plain C99 (tests/c/shim_twopiece.c)
+# 10 -- the schedule key: ONE batch on one context, re-run under options that each give the pair another workspace.  A schedule
+# kept from the run before would hand the run a workspace sized for the previous geometry
+def test_schedule_follows_the_run_options(ctx):
+    rng = random.Random(8816)
+    ref = u.rand(rng, 1300)
+    read = gc.mutate(rng, ref[:1080]) + u.rand(rng, 40)
+    read = read[:1100]
+    assert (len(read), len(ref)) == (1100, 1300)                  # two strips
+    w, sc = 64, SC[:4]
+    plain = u.expect([ref], [read], sc, GLOBAL, 0, False, cells=True)[(0, 0)]
+    banded = u.expect([ref], [read], sc, GLOBAL, w, True, cells=True)[(0, 0)]
+    assert plain[:2] != banded[:2]
+    steps = [({"long_reads": 1}, plain),
+             ({"band": w, "extend": 1}, banded),
+             ({"band_adapt": 1}, ar.align(ref, read, sc, w)[:3]),
+             ({"band_adapt": 0}, banded),
+             ({"gap_open2": SC[5], "gap2": SC[4]}, _want(ref, read, SC, w, 1)),
+             ({"gap_open2": 0, "band": 0, "extend": 0}, plain)]
+    ctx.set_option("gap_open", sc[3])
+    ctx.set_option("align_mode", GLOBAL)
+    b = ctx.upload([ref], [read])
+    p = sw.make_params(sc[:3])
+    for at, (options, want) in enumerate(steps):
+        for name, value in options.items():
+            ctx.set_option(name, value)
+        b.run(p)
+        assert b.pipeline_mode() == 3
+        u.check_pair(b, 0, want, GLOBAL, at)
+    b.free()
+
+
+# 11 -- the JNI shim's entry point from plain C99 (tests/c/shim_twopiece.c)
 def test_c99_shim_sets_gap2(tmp_path):
     out = u.run_shim(tmp_path, "shim_twopiece")
     ref, read = "GGCCCAGTCCAGCCCAACTAACGAATAAGTAGAATCCTCGGAAGT", "GGCCCAGTCCAGATCCTCGGAAGT"
