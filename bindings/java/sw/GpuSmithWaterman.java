@@ -51,6 +51,12 @@ public class GpuSmithWaterman
 	static native void nativeSetGap2( long ctx , int gapOpen2 , int gap2 ) ;
 	/** substitution scores on the context: alphabet = n ISO-8859-1 symbols, scores = n * n, row = read base; null clears */
 	static native void nativeSetScoreMatrix( long ctx , byte[] alphabet , int[] scores ) ;
+	/** a pair list over the sequences: specs = eight ints per pair ( alignPairs ) */
+	static native long nativeAlignPairs( long ctx , int match , int mismatch , int gap , int tieMode , byte[] types ,
+	                                     ByteBuffer refBytes , long[] refOff , int nRefs , ByteBuffer readBytes , long[] readOff , int nReads , int[] specs ) ;
+	static native void nativePairResults( long batch , int[] scores , long[] counts ) ;
+	/** fills info = { begin , last row , last column } and returns { refAligned , readAligned } as ISO-8859-1 bytes */
+	static native byte[][] nativePairAlignment( long batch , long pair , long k , int[] info ) ;
 	static native void nativeFreeBatch( long ctx , long batch ) ;
 	static native int nativeRefTotal( long batch , int ref ) ;
 	static native long nativeRefSiteCount( long batch , int ref ) ;
@@ -234,6 +240,78 @@ public class GpuSmithWaterman
 		return buf ;
 	}
 
+	/** the scores' optional entries and the class's run options onto a native context, before a native align call */
+	private static void applyRunOptions( NativeContext nc , int[] sc )
+	{
+		long ctx = nc.handle ;
+		// alignScores may carry a fourth entry, gapOpen (<= 0): affine gaps; three entries keep the linear scoring
+		// ... and a fifth and sixth, gap2 and gapOpen2 (<= 0): two-piece gaps, with ALIGN_GLOBAL
+		if( sc.length != 3 && sc.length != 4 && sc.length != 6 ) throw new IllegalArgumentException( "alignScores needs 3, 4 or 6 entries: " + sc.length ) ;
+		nativeSetGapOpen( ctx , sc.length >= 4 ? sc[3] : 0 ) ;
+		nativeSetGap2( ctx , sc.length == 6 ? sc[5] : 0 , sc.length == 6 ? sc[4] : 0 ) ;
+		nativeSetAlignMode( ctx , ALIGN_MODE ) ;
+		nativeSetLongReads( ctx , LONG_READS ? 1 : 0 ) ;
+		nativeSetBand( ctx , BAND ) ;
+		nativeSetExtend( ctx , EXTEND ? 1 : 0 ) ;
+		nativeSetXdrop( ctx , XDROP ) ;
+		nativeSetBandAdapt( ctx , BAND_ADAPT ? 1 : 0 ) ;
+		applyScoreMatrix( nc ) ;
+	}
+
+	/** swmi_pair_spec.flags: both segments of the pair are taken in reverse order ( a left extension ) */
+	public static final int SPEC_REVERSE = 1 ;
+
+	/**
+	 * A PAIR LIST in one native call: what a read mapper has after chaining.  refs / reads are uploaded once; specs holds eight
+	 * ints per pair -- { ref , read , refStart , refLen , readStart , readLen , flags , 0 } : indices into refs / reads, the 0-based
+	 * start and the length of the two segments ( -1 as a length: to the end of the sequence ) and SPEC_REVERSE in flags for a
+	 * left extension ( both segments are taken in reverse order ).  The GPU cuts the segments from the resident sequences.
+	 * Returns, per pair in list order, ( score , alignments as ( begin , { refAligned , readAligned } ) ) with coordinates in the
+	 * SEGMENTS: column j is reference character refStart + j - 1, or refStart + refLen - j when reversed.  alignScores and
+	 * alignTypes are OptAlignments' arrays ( null: the defaults ); the run options set on this class ( setAlignMode, setExtend,
+	 * setBand, ... ) apply.
+	 */
+	public static ArrayList<Tuple2<Integer,ArrayList<Tuple2<Integer,String[]>>>> alignPairs( String[] refs , String[] reads , int[] specs )
+	{
+		return alignPairs( refs , reads , specs , null , null ) ;
+	}
+	public static ArrayList<Tuple2<Integer,ArrayList<Tuple2<Integer,String[]>>>> alignPairs( String[] refs , String[] reads , int[] specs , int[] alignScores , char[] alignTypes )
+	{
+		int[] sc = alignScores != null ? alignScores : new int[]{ 5 , -3 , -4 } ;		// Distribution.java:36-37
+		char[] ty = alignTypes != null ? alignTypes : new char[]{ 'a' , 'i' , 'd' , '-' } ;
+		if( specs.length % 8 != 0 ) throw new IllegalArgumentException( "specs needs 8 ints per pair: " + specs.length ) ;
+		int nPairs = specs.length / 8 ;
+		long[] refOff = new long[refs.length+1] , readOff = new long[reads.length+1] ;
+		ByteBuffer refBuf = pack( java.util.Arrays.asList(refs) , refOff ) , readBuf = pack( java.util.Arrays.asList(reads) , readOff ) ;
+		byte[] types = { (byte)ty[0] , (byte)ty[1] , (byte)ty[2] , (byte)ty[3] } ;
+		NativeContext nc = context() ;
+		long ctx = nc.handle ;
+		applyRunOptions( nc , sc ) ;
+		long batch = nativeAlignPairs( ctx , sc[0] , sc[1] , sc[2] , TIE_SERIAL , types , refBuf , refOff , refs.length , readBuf , readOff , reads.length , specs ) ;
+		try
+		{
+			int[] scores = new int[nPairs] ;
+			long[] counts = new long[nPairs] ;
+			nativePairResults( batch , scores , counts ) ;
+			ArrayList<Tuple2<Integer,ArrayList<Tuple2<Integer,String[]>>>> out = new ArrayList<Tuple2<Integer,ArrayList<Tuple2<Integer,String[]>>>>( nPairs ) ;
+			int[] info = new int[3] ;
+			for( int p = 0 ; p < nPairs ; p++ )
+			{
+				if( counts[p] > Integer.MAX_VALUE ) throw new IllegalStateException( "pair " + p + " has " + counts[p] + " alignments" ) ;
+				ArrayList<Tuple2<Integer,String[]>> alns = new ArrayList<Tuple2<Integer,String[]>>( (int)counts[p] ) ;
+				for( long k = 0 ; k < counts[p] ; k++ )
+				{
+					byte[][] two = nativePairAlignment( batch , p , k , info ) ;
+					alns.add( two[0].length == 0 ? EMPTY_SITE : new Tuple2<Integer,String[]>( Integer.valueOf(info[0]) ,
+						new String[]{ new String( two[0] , StandardCharsets.ISO_8859_1 ) , new String( two[1] , StandardCharsets.ISO_8859_1 ) } ) ) ;
+				}
+				out.add( new Tuple2<Integer,ArrayList<Tuple2<Integer,String[]>>>( Integer.valueOf(scores[p]) , alns ) ) ;
+			}
+			return out ;
+		}
+		finally { nativeFreeBatch( ctx , batch ) ; }
+	}
+
 	/** mapPartitionsToPair variant: the elements of the partition in ONE native call per (at most) 1 GiB of references. */
 	public static class MapPartition implements PairFlatMapFunction< Iterator<Tuple3<String[],ArrayList<String>,Tuple2<int[],char[]>>> , Integer , Tuple2<String[],ArrayList<Tuple2<Integer,String[]>>> >
 	{
@@ -273,18 +351,7 @@ public class GpuSmithWaterman
 
 			NativeContext nc = context() ;
 			long ctx = nc.handle ;
-			// alignScores may carry a fourth entry, gapOpen (<= 0): affine gaps; three entries keep the linear scoring
-			// ... and a fifth and sixth, gap2 and gapOpen2 (<= 0): two-piece gaps, with ALIGN_GLOBAL
-			if( sc.length != 3 && sc.length != 4 && sc.length != 6 ) throw new IllegalArgumentException( "alignScores needs 3, 4 or 6 entries: " + sc.length ) ;
-			nativeSetGapOpen( ctx , sc.length >= 4 ? sc[3] : 0 ) ;
-			nativeSetGap2( ctx , sc.length == 6 ? sc[5] : 0 , sc.length == 6 ? sc[4] : 0 ) ;
-			nativeSetAlignMode( ctx , ALIGN_MODE ) ;
-			nativeSetLongReads( ctx , LONG_READS ? 1 : 0 ) ;
-			nativeSetBand( ctx , BAND ) ;
-			nativeSetExtend( ctx , EXTEND ? 1 : 0 ) ;
-			nativeSetXdrop( ctx , XDROP ) ;
-			nativeSetBandAdapt( ctx , BAND_ADAPT ? 1 : 0 ) ;
-			applyScoreMatrix( nc ) ;
+			applyRunOptions( nc , sc ) ;
 			long batch = nativeAlignBatch( ctx , sc[0] , sc[1] , sc[2] , TIE_SERIAL , types , refBuf , refOff , n , readBuf , readOff , reads.size() ) ;
 			try
 			{

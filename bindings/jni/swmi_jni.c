@@ -165,6 +165,96 @@ JNIEXPORT jlong JNICALL Java_sw_GpuSmithWaterman_nativeAlignBatch(
     return (jlong)(intptr_t)b;
 }
 
+/* a pair list over the sequences: specs = int[8 * nPairs], eight ints per pair as in swmi_pair_spec (swmi_shim.h) */
+JNIEXPORT jlong JNICALL Java_sw_GpuSmithWaterman_nativeAlignPairs(
+        JNIEnv *env, jclass cls, jlong ctx, jint match, jint mismatch, jint gap, jint tieMode, jbyteArray types,
+        jobject refBytes, jlongArray refOff, jint nRefs, jobject readBytes, jlongArray readOff, jint nReads, jintArray specs) {
+    char err[640];
+    jbyte ty[4] = {0, 0, 0, 0};
+    jsize ty_len;
+    jlong *ro, *qo;
+    jint *sp;
+    swmi_batch *b = NULL;
+    int rc;
+    (void)cls;
+    if (!types || !refOff || !readOff || !specs) { throw_msg(env, "nativeAlignPairs: null array argument"); return 0; }
+    ty_len = (*env)->GetArrayLength(env, types);
+    if (ty_len == 4) (*env)->GetByteArrayRegion(env, types, 0, 4, ty);
+    if ((*env)->GetArrayLength(env, refOff) != (jsize)nRefs + 1 || (*env)->GetArrayLength(env, readOff) != (jsize)nReads + 1) {
+        throw_msg(env, "nativeAlignPairs: an offset array does not have n + 1 entries");
+        return 0;
+    }
+    ro = (*env)->GetLongArrayElements(env, refOff, NULL);
+    qo = (*env)->GetLongArrayElements(env, readOff, NULL);
+    sp = (*env)->GetIntArrayElements(env, specs, NULL);
+    if (!ro || !qo || !sp) {
+        if (ro) (*env)->ReleaseLongArrayElements(env, refOff, ro, JNI_ABORT);
+        if (qo) (*env)->ReleaseLongArrayElements(env, readOff, qo, JNI_ABORT);
+        if (sp) (*env)->ReleaseIntArrayElements(env, specs, sp, JNI_ABORT);
+        throw_msg(env, "nativeAlignPairs: out of memory pinning the arrays");
+        return 0;
+    }
+    rc = swmi_shim_align_pairs((swmi_ctx *)(intptr_t)ctx, match, mismatch, gap, tieMode, (const signed char *)ty, (size_t)ty_len,
+                               refBytes ? (*env)->GetDirectBufferAddress(env, refBytes) : NULL,
+                               refBytes ? (int64_t)(*env)->GetDirectBufferCapacity(env, refBytes) : 0, (const int64_t *)ro, nRefs,
+                               readBytes ? (*env)->GetDirectBufferAddress(env, readBytes) : NULL,
+                               readBytes ? (int64_t)(*env)->GetDirectBufferCapacity(env, readBytes) : 0, (const int64_t *)qo, nReads,
+                               (const int32_t *)sp, (int64_t)(*env)->GetArrayLength(env, specs), &b, err, sizeof err);
+    (*env)->ReleaseLongArrayElements(env, refOff, ro, JNI_ABORT);
+    (*env)->ReleaseLongArrayElements(env, readOff, qo, JNI_ABORT);
+    (*env)->ReleaseIntArrayElements(env, specs, sp, JNI_ABORT);
+    if (rc != SWMI_OK) { throw_msg(env, err); return 0; }
+    return (jlong)(intptr_t)b;
+}
+
+/* every pair's score and number of alignments into the caller's arrays (both as long as the batch has pairs) */
+JNIEXPORT void JNICALL Java_sw_GpuSmithWaterman_nativePairResults(JNIEnv *env, jclass cls, jlong batch, jintArray scores, jlongArray counts) {
+    char err[640];
+    jint *sc;
+    jlong *ct;
+    int rc = SWMI_ERR_NOMEM;
+    (void)cls;
+    if (!scores || !counts) { throw_msg(env, "nativePairResults: null array argument"); return; }
+    if ((*env)->GetArrayLength(env, scores) != (*env)->GetArrayLength(env, counts)) { throw_msg(env, "nativePairResults: the arrays differ in length"); return; }
+    sc = (*env)->GetIntArrayElements(env, scores, NULL);
+    ct = (*env)->GetLongArrayElements(env, counts, NULL);
+    if (sc && ct)
+        rc = swmi_shim_pair_results((swmi_batch *)(intptr_t)batch, (int32_t *)sc, (int64_t *)ct, (int64_t)(*env)->GetArrayLength(env, scores), err, sizeof err);
+    else
+        snprintf(err, sizeof err, "nativePairResults: out of memory pinning the output arrays");
+    if (sc) (*env)->ReleaseIntArrayElements(env, scores, sc, 0);
+    if (ct) (*env)->ReleaseLongArrayElements(env, counts, ct, 0);
+    if (rc != SWMI_OK) throw_msg(env, err);
+}
+
+/* alignment k of a pair: fills info[0..2] = {begin, last row, last column} and returns {refAligned, readAligned} as ISO-8859-1 bytes */
+JNIEXPORT jobjectArray JNICALL Java_sw_GpuSmithWaterman_nativePairAlignment(JNIEnv *env, jclass cls, jlong batch, jlong pair, jlong k, jintArray info) {
+    char err[640];
+    int32_t b = 0, cell[2] = {0, 0}; const char *r = NULL, *q = NULL; uint32_t len = 0;
+    jint ji[3];
+    jobjectArray out;
+    jbyteArray ra, qa;
+    jclass bytes_cls;
+    (void)cls;
+    if (swmi_shim_pair_alignment((swmi_batch *)(intptr_t)batch, pair, k, &b, cell, &r, &q, &len, err, sizeof err) != SWMI_OK) {
+        throw_msg(env, err);
+        return NULL;
+    }
+    ji[0] = b; ji[1] = cell[0]; ji[2] = cell[1];
+    if (info && (*env)->GetArrayLength(env, info) >= 3) (*env)->SetIntArrayRegion(env, info, 0, 3, ji);
+    bytes_cls = (*env)->FindClass(env, "[B");
+    if (!bytes_cls) return NULL;
+    out = (*env)->NewObjectArray(env, 2, bytes_cls, NULL);
+    ra = (*env)->NewByteArray(env, (jsize)len);
+    qa = (*env)->NewByteArray(env, (jsize)len);
+    if (!out || !ra || !qa) return NULL;                     /* OutOfMemoryError is already pending */
+    (*env)->SetByteArrayRegion(env, ra, 0, (jsize)len, (const jbyte *)r);
+    (*env)->SetByteArrayRegion(env, qa, 0, (jsize)len, (const jbyte *)q);
+    (*env)->SetObjectArrayElement(env, out, 0, ra);
+    (*env)->SetObjectArrayElement(env, out, 1, qa);
+    return out;
+}
+
 JNIEXPORT void JNICALL Java_sw_GpuSmithWaterman_nativeFreeBatch(JNIEnv *env, jclass cls, jlong ctx, jlong batch) {
     (void)env; (void)cls;
     swmi_batch_free((swmi_ctx *)(intptr_t)ctx, (swmi_batch *)(intptr_t)batch);

@@ -125,6 +125,59 @@ int swmi_shim_align_batch(swmi_ctx *ctx, int32_t match, int32_t mismatch, int32_
     return SWMI_OK;
 }
 
+int swmi_shim_align_pairs(swmi_ctx *ctx, int32_t match, int32_t mismatch, int32_t gap, int32_t tie_mode,
+                          const signed char *types, size_t types_len,
+                          const void *ref_bytes, int64_t ref_cap, const int64_t *ref_off, int32_t n_refs,
+                          const void *read_bytes, int64_t read_cap, const int64_t *read_off, int32_t n_reads,
+                          const int32_t *specs, int64_t n_spec_ints, swmi_batch **out, char *err, size_t err_len) {
+    swmi_params p;
+    int rc;
+    if (!out) return shim_fail(SWMI_ERR_INVALID, err, err_len, "nativeAlignPairs", "out is null");
+    *out = NULL;
+    if (!ctx) return shim_fail(SWMI_ERR_INVALID, err, err_len, "nativeAlignPairs", "context handle is 0");
+    if (!types || types_len != 4)
+        return shim_fail(SWMI_ERR_INVALID, err, err_len, "nativeAlignPairs", "alignTypes must hold exactly 4 characters");
+    if ((rc = check_side("references", ref_bytes, ref_cap, ref_off, n_refs, err, err_len)) != SWMI_OK) return rc;
+    if ((rc = check_side("reads", read_bytes, read_cap, read_off, n_reads, err, err_len)) != SWMI_OK) return rc;
+    if (n_spec_ints < 0 || n_spec_ints % 8 != 0)
+        return shim_fail(SWMI_ERR_INVALID, err, err_len, "nativeAlignPairs", "specs must hold 8 ints per pair");
+    if (n_spec_ints > 0 && !specs) return shim_fail(SWMI_ERR_INVALID, err, err_len, "nativeAlignPairs", "specs is null");
+    swmi_default_params(&p);
+    p.match = match; p.mismatch = mismatch; p.gap = gap; p.tie_mode = tie_mode;
+    memcpy(p.types, types, 4);
+    /* eight jints are one swmi_pair_spec: the same size, its members the unsigned type of the same width */
+    rc = swmi_batch_upload_pairs(ctx, (const uint8_t *)ref_bytes, (const uint64_t *)(const void *)ref_off, (uint32_t)n_refs,
+                                 (const uint8_t *)read_bytes, (const uint64_t *)(const void *)read_off, (uint32_t)n_reads,
+                                 (const swmi_pair_spec *)(const void *)specs, (uint64_t)(n_spec_ints / 8), out);
+    if (rc != SWMI_OK) return shim_fail(rc, err, err_len, "swmi_batch_upload_pairs", swmi_last_error());
+    rc = swmi_batch_run(ctx, *out, &p);
+    if (rc != SWMI_OK) {
+        shim_fail(rc, err, err_len, "swmi_batch_run", swmi_last_error());
+        swmi_batch_free(ctx, *out);
+        *out = NULL;
+    }
+    return rc;
+}
+
+int swmi_shim_pair_results(const swmi_batch *b, int32_t *scores, int64_t *n_alignments, int64_t n, char *err, size_t err_len) {
+    int rc;
+    if (n < 0) return shim_fail(SWMI_ERR_RANGE, err, err_len, "nativePairResults", "negative array length");
+    /* (a count is below 2^63: jlong and uint64_t hold it alike) */
+    rc = swmi_batch_pair_results(b, scores, (uint64_t *)(void *)n_alignments, (uint64_t)n);
+    return rc == SWMI_OK ? rc : shim_fail(rc, err, err_len, "swmi_batch_pair_results", swmi_last_error());
+}
+
+int swmi_shim_pair_alignment(swmi_batch *b, int64_t pair, int64_t k, int32_t *begin, int32_t cell[2], const char **ref_aln,
+                             const char **read_aln, uint32_t *len, char *err, size_t err_len) {
+    int32_t ei = 0, ej = 0;
+    int rc;
+    if (pair < 0 || k < 0) return shim_fail(SWMI_ERR_RANGE, err, err_len, "nativePairAlignment", "negative index");
+    rc = swmi_pair_alignment(b, (uint64_t)pair, (uint64_t)k, begin, &ei, &ej, ref_aln, read_aln, len);
+    if (rc != SWMI_OK) return shim_fail(rc, err, err_len, "swmi_pair_alignment", swmi_last_error());
+    if (cell) { cell[0] = ei; cell[1] = ej; }
+    return SWMI_OK;
+}
+
 int swmi_shim_ref_total(const swmi_batch *b, int32_t ref, int32_t *total, char *err, size_t err_len) {
     int rc;
     if (ref < 0) return shim_fail(SWMI_ERR_RANGE, err, err_len, "nativeRefTotal", "negative reference index");

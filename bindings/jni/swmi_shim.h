@@ -26,6 +26,24 @@ int swmi_shim_align_batch(swmi_ctx *ctx, int32_t match, int32_t mismatch, int32_
                           const void *read_bytes, int64_t read_cap, const int64_t *read_off, int32_t n_reads,
                           swmi_batch **out, char *err, size_t err_len);
 
+/* nativeAlignPairs: a PAIR LIST over the sequences (swmi_batch_upload_pairs + swmi_batch_run): `specs` = int[8 * n_pairs], eight
+ * ints per pair in the order of swmi_pair_spec -- ref, read, refStart, refLen, readStart, readLen, flags (SWMI_SPEC_REVERSE: both
+ * segments reversed, a left extension), 0 -- taken as unsigned, so that -1 as a length is SWMI_SPEC_WHOLE; n_spec_ints = the
+ * array's length (a multiple of 8).  The other arguments are nativeAlignBatch's.  Pair k of the batch is spec k: its results are
+ * read with swmi_shim_pair_results and swmi_shim_pair_alignment (the swmi_shim_ref_* views need the cross product and fail with
+ * SWMI_ERR_UNSUPPORTED). */
+int swmi_shim_align_pairs(swmi_ctx *ctx, int32_t match, int32_t mismatch, int32_t gap, int32_t tie_mode,
+                          const signed char *types, size_t types_len,
+                          const void *ref_bytes, int64_t ref_cap, const int64_t *ref_off, int32_t n_refs,
+                          const void *read_bytes, int64_t read_cap, const int64_t *read_off, int32_t n_reads,
+                          const int32_t *specs, int64_t n_spec_ints, swmi_batch **out, char *err, size_t err_len);
+/* nativePairResults: every pair's score and number of alignments (either array may be NULL); n = the arrays' length, which must
+ * be the batch's number of pairs.  nativePairAlignment: alignment k of a pair, as swmi_pair_alignment hands it out; cell[0..1]
+ * receive the alignment's last cell (row, column), 1-based in the segments. */
+int swmi_shim_pair_results(const swmi_batch *b, int32_t *scores, int64_t *n_alignments, int64_t n, char *err, size_t err_len);
+int swmi_shim_pair_alignment(swmi_batch *b, int64_t pair, int64_t k, int32_t *begin, int32_t cell[2], const char **ref_aln,
+                             const char **read_aln, uint32_t *len, char *err, size_t err_len);
+
 /* nativeSetGapOpen: affine gaps on this context (swmi_set_option "gap_open"): a gap of length k then costs gap_open + k * gap.
  * gap_open <= 0; 0 (the default) is the linear scoring.  Applies to the batches the context aligns from then on. */
 int swmi_shim_set_gap_open(swmi_ctx *ctx, int32_t gap_open, char *err, size_t err_len);

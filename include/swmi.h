@@ -18,7 +18,8 @@
  *     tests (src/sw/SmithWaterman.java:309-318), reproduced exactly for Latin-1.  A JNI
  *     caller holding chars above U+00FF must canonicalise them first.
  *   - a batch is the cross product refs x reads, pair index = ref * n_reads + read:
- *     the order in which MapRef.call loops (Distribution.java:419-426).
+ *     the order in which MapRef.call loops (Distribution.java:419-426) -- or a pair list
+ *     (swmi_batch_upload_pairs), pair index = position in the list.
  *   - a context is bound to one GPU and owns one HIP stream; calls on one context
  *     are serialised internally, use one context per host thread for concurrency
  *     (Spark runs MapRef on every executor thread).
@@ -286,6 +287,43 @@ int  swmi_batch_upload(swmi_ctx *ctx,
                        const uint8_t *ref_bytes, const uint64_t *ref_off, uint32_t n_refs,
                        const uint8_t *read_bytes, const uint64_t *read_off, uint32_t n_reads,
                        swmi_batch **out);
+/* ---- pair lists: chosen segments of uploaded sequences, one batch ------------------ */
+/* A mapper's work list is not a cross product but a list of (reference window, read segment) pairs, windows overlapping,
+ * the left extension of a seed running over both sequences reversed.  swmi_batch_upload_pairs uploads the SOURCE sequences
+ * once (ref_off / read_off as for swmi_batch_upload) and a list of specs; a gfx950 kernel cuts, reverses and encodes the
+ * segments from the resident sources.  Pair k of such a batch is spec k, swmi_batch_n_pairs returns
+ * n_pairs, and the result of pair k is, bit for bit, what a one-pair batch of swmi_batch_upload returns for the two segments
+ * cut -- and under SWMI_SPEC_REVERSE reversed -- by the caller: score, flags, n_alignments, every alignment's begin / end_i /
+ * end_j and both strings with the caller's original case, swmi_pair_rows_swept and swmi_pair_band_window, under every option
+ * and pipeline the context selects.  The bounds a run checks on "the batch's longest read / reference" are read over the
+ * segments.  COORDINATES ARE THE SEGMENT'S: column j (1-based) of pair k is source byte  ref_start + j - 1  of the reference,
+ * or  ref_start + ref_len - j  when the pair is reversed; row i maps to the read's bytes in the same way.  A pair with an empty
+ * segment scores 0 with no alignments.
+ * Refused with SWMI_ERR_INVALID before anything is uploaded or launched, the message naming the pair: a source index out of
+ * range, start + len past the end of the source, a flag bit other than SWMI_SPEC_REVERSE, reserved != 0, specs == NULL with
+ * n_pairs > 0.  n_pairs >= 2^32 is SWMI_ERR_UNSUPPORTED; the segments' images together are subject to the 16 GiB image rule.
+ * n_pairs = 0 is a valid, empty batch.  The MapRef views (swmi_ref_total(s), swmi_ref_n_match_sites, swmi_ref_match_site,
+ * swmi_ref_sites_packed) have no meaning without the cross product and return SWMI_ERR_UNSUPPORTED on such a batch. */
+#define SWMI_SPEC_REVERSE 0x1u          /* both segments are taken in reverse byte order (left extension); no complement */
+#define SWMI_SPEC_WHOLE   0xFFFFFFFFu   /* as ref_len / read_len: from the start given to the end of the source */
+typedef struct swmi_pair_spec {         /* 32 bytes */
+    uint32_t ref, read;                 /* indices of the uploaded reference / read                      */
+    uint32_t ref_start, ref_len;        /* 0-based first byte and length of the reference segment        */
+    uint32_t read_start, read_len;
+    uint32_t flags;                     /* 0 or SWMI_SPEC_REVERSE                                        */
+    uint32_t reserved;                  /* 0                                                             */
+} swmi_pair_spec;
+int  swmi_batch_upload_pairs(swmi_ctx *ctx,
+                             const uint8_t *ref_bytes, const uint64_t *ref_off, uint32_t n_refs,
+                             const uint8_t *read_bytes, const uint64_t *read_off, uint32_t n_reads,
+                             const swmi_pair_spec *specs, uint64_t n_pairs, swmi_batch **out);
+/* Replaces the list on the same resident sources (left extensions, then right extensions; a second round under another
+ * band): the old results are dropped and the batch is to be run again.  A refused list leaves the batch as it was.  On a
+ * batch made by swmi_batch_upload: SWMI_ERR_INVALID. */
+int  swmi_batch_set_pairs(swmi_ctx *ctx, swmi_batch *b, const swmi_pair_spec *specs, uint64_t n_pairs);
+/* spec `pair` of the batch, SWMI_SPEC_WHOLE resolved to a length.  On a cross-product batch: SWMI_ERR_INVALID. */
+int  swmi_batch_pair_spec(const swmi_batch *b, uint64_t pair, swmi_pair_spec *spec);
+
 /* Fill + direction field + max-cell lists + device traceback for every pair, then
  * the compact result records device->host.  Synchronous on return. */
 int  swmi_batch_run(swmi_ctx *ctx, swmi_batch *b, const swmi_params *p);

@@ -18,6 +18,10 @@ ALIGN_GLOBAL = 2     # the whole read against the whole reference
 BAND_MAX = 1 << 20   # option "band": the largest half-width (0: no band)
 XDROP_MAX = (1 << 31) - 1   # option "xdrop": the largest threshold (0: off)
 PAIR_DEGENERATE = 0x1
+SPEC_REVERSE = 0x1          # swmi_pair_spec.flags: both segments in reverse byte order (left extension)
+SPEC_WHOLE = 0xFFFFFFFF     # as ref_len / read_len: from the start given to the end of the source
+ERR_INVALID = -1
+ERR_UNSUPPORTED = -5
 
 
 class SwmiError(RuntimeError):
@@ -37,6 +41,12 @@ class Timing(C.Structure):
                 ("cells", C.c_uint64), ("dir_bytes", C.c_uint64),
                 ("strip_fallbacks", C.c_uint32), ("col_chunks", C.c_uint32),
                 ("resident_pairs", C.c_uint32), ("tfused_pairs", C.c_uint32)]
+
+
+class PairSpec(C.Structure):
+    """swmi_pair_spec: one pair of a pair list (swmi_batch_upload_pairs), 32 bytes"""
+    _fields_ = [("ref", C.c_uint32), ("read", C.c_uint32), ("ref_start", C.c_uint32), ("ref_len", C.c_uint32),
+                ("read_start", C.c_uint32), ("read_len", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class StreamStats(C.Structure):
@@ -59,6 +69,10 @@ SYMBOLS = [
     ("swmi_set_option", C.c_int, [_P, C.c_char_p, C.c_int64]),
     ("swmi_set_score_matrix", C.c_int, [_P, C.c_char_p, C.c_uint32, C.POINTER(C.c_int32)]),
     ("swmi_batch_upload", C.c_int, [_P, C.c_char_p, _u64p, C.c_uint32, C.c_char_p, _u64p, C.c_uint32, C.POINTER(_P)]),
+    ("swmi_batch_upload_pairs", C.c_int, [_P, C.c_char_p, _u64p, C.c_uint32, C.c_char_p, _u64p, C.c_uint32, C.POINTER(PairSpec),
+                                          C.c_uint64, C.POINTER(_P)]),
+    ("swmi_batch_set_pairs", C.c_int, [_P, _P, C.POINTER(PairSpec), C.c_uint64]),
+    ("swmi_batch_pair_spec", C.c_int, [_P, C.c_uint64, C.POINTER(PairSpec)]),
     ("swmi_batch_run", C.c_int, [_P, _P, C.POINTER(Params)]),
     ("swmi_batch_run_async", C.c_int, [_P, _P, C.POINTER(Params)]),
     ("swmi_batch_wait", C.c_int, [_P]),

@@ -3,7 +3,7 @@ import ctypes as C
 import weakref
 
 from . import _capi
-from ._capi import Params, Timing, StreamStats, check
+from ._capi import Params, Timing, StreamStats, PairSpec, SwmiError, check
 
 DEFAULT_SCORES = (5, -3, -4)              # Distribution.java:36  {match, mismatch, gap}
 DEFAULT_TYPES = ("a", "i", "d", "-")      # Distribution.java:37
@@ -19,6 +19,66 @@ def make_params(align_scores=None, align_types=None, tie_mode=_capi.TIE_SERIAL):
     p.tie_mode = tie_mode
     p.types = b"".join(_capi.as_bytes(t)[:1] for t in ty)
     return p
+
+
+def normalise_pairs(pairs):
+    """The pairs of a pair list as 7-tuples (ref, read, ref_start, ref_len, read_start, read_len, reverse).  An entry is
+    (ref, read) -- both sources whole --, (ref, read, ref_start, ref_len, read_start, read_len), or the latter plus `reverse`
+    (true: both segments in reverse byte order, a left extension).  A length of None or _capi.SPEC_WHOLE runs to the end of
+    the source.  ValueError for anything else: another number of fields, a field that is no integer, a negative value or one
+    past 32 bits.  Ranges against the sources are the library's to check (it knows them)."""
+    out = []
+    for k, t in enumerate(pairs):
+        try:
+            t = tuple(t)
+        except TypeError:
+            raise ValueError("pair %d: not a tuple: %r" % (k, t))
+        if len(t) not in (2, 6, 7):
+            raise ValueError("pair %d: %d fields; (ref, read), (ref, read, ref_start, ref_len, read_start, read_len) or the latter "
+                             "plus reverse" % (k, len(t)))
+        rev = False
+        if len(t) == 7:
+            if not isinstance(t[6], (bool, int)) or t[6] not in (0, 1):
+                raise ValueError("pair %d: reverse must be a bool, got %r" % (k, t[6]))
+            rev = bool(t[6])
+        f = list(t[:6]) if len(t) >= 6 else [t[0], t[1], 0, None, 0, None]
+        for x in (3, 5):
+            if f[x] is None:
+                f[x] = _capi.SPEC_WHOLE
+        for x, v in enumerate(f):
+            if isinstance(v, bool) or not hasattr(v, "__index__"):
+                raise ValueError("pair %d: field %d is no integer: %r" % (k, x, v))
+            v = f[x] = int(v)
+            if v < 0 or v > 0xFFFFFFFF:
+                raise ValueError("pair %d: field %d = %d is outside 0 .. 2^32 - 1" % (k, x, v))
+        out.append(tuple(f) + (rev,))
+    return out
+
+
+def cut_segments(refs, reads, spec):
+    """the two segments of a normalised pair as the library aligns them: cut from the sources and, reversed, byte-reversed"""
+    r, q, rs, rl, qs, ql, rev = spec
+    ref, read = refs[r], reads[q]
+    a = ref[rs:] if rl == _capi.SPEC_WHOLE else ref[rs:rs + rl]
+    b = read[qs:] if ql == _capi.SPEC_WHOLE else read[qs:qs + ql]
+    return (a[::-1], b[::-1]) if rev else (a, b)
+
+
+def cell_to_source(spec, seg_lens, i, j):
+    """(read byte, reference byte), 0-based in the sources, of cell (i, j) (1-based row and column) of a normalised pair whose
+    segments have the lengths seg_lens = (reference, read): start + j - 1 forward, start + len - j reversed (swmi.h)"""
+    _, _, rs, _, qs, _, rev = spec
+    n, m = seg_lens
+    if rev:
+        return qs + m - i, rs + n - j
+    return qs + i - 1, rs + j - 1
+
+
+def _spec_array(specs):
+    arr = (PairSpec * max(len(specs), 1))()
+    for k, (r, q, rs, rl, qs, ql, rev) in enumerate(specs):
+        arr[k] = PairSpec(r, q, rs, rl, qs, ql, _capi.SPEC_REVERSE if rev else 0, 0)
+    return arr
 
 
 class Context:
@@ -58,6 +118,11 @@ class Context:
     def upload(self, refs, reads):
         """Sequences -> HBM.  refs/reads: lists of str or bytes."""
         return Batch(self, refs, reads)
+
+    def upload_pairs(self, refs, reads, pairs):
+        """Sources -> HBM once, and a pair list over them (swmi_batch_upload_pairs): pair k of the PairBatch is pairs[k], see
+        normalise_pairs for its forms.  The segments are cut, reversed and encoded on the GPU."""
+        return PairBatch(self, refs, reads, pairs)
 
     def stream(self, reads, params=None, slots=0, chunk_bytes=0):
         """A Stream aligning `reads` against references that arrive in chunks (swmi_stream_*)."""
@@ -99,6 +164,9 @@ class Batch:
         h = C.c_void_p()
         check(self._lib.swmi_batch_upload(ctx._h, rb, ro, self.n_refs, qb, qo, self.n_reads, C.byref(h)))
         self._h = h
+
+    def n_pairs(self):
+        return self.n_refs * self.n_reads
 
     def run(self, params=None):
         """Fill + traceback on the GPU for every pair, results to the host.  Synchronous."""
@@ -168,7 +236,7 @@ class Batch:
     def pair_results(self):
         """(scores int32[n_pairs], n_alignments uint64[n_pairs]) as numpy arrays, one native call."""
         import numpy as np
-        n = self.n_refs * self.n_reads
+        n = self.n_pairs()
         sc = np.empty(n, dtype=np.int32)
         na = np.empty(n, dtype=np.uint64)
         check(self._lib.swmi_batch_pair_results(self._h, sc.ctypes.data_as(C.POINTER(C.c_int32)),
@@ -178,7 +246,7 @@ class Batch:
     def scores(self):
         """every pair's score as a numpy int32 array (also after a scores_only run, which has no alignment counts)"""
         import numpy as np
-        n = self.n_refs * self.n_reads
+        n = self.n_pairs()
         sc = np.empty(n, dtype=np.int32)
         check(self._lib.swmi_batch_pair_results(self._h, sc.ctypes.data_as(C.POINTER(C.c_int32)), None, n))
         return sc
@@ -253,6 +321,52 @@ class Batch:
             self.free()
         except Exception:
             pass
+
+
+class PairBatch(Batch):
+    """A pair list over sources resident on the GPU (swmi_batch_upload_pairs): pair k is the k-th pair given, coordinates are
+    the segments' (to_source maps them back).  The MapRef views (ref_*) need the cross product and raise SwmiError."""
+
+    def __init__(self, ctx, refs, reads, pairs):
+        self._ctx = ctx
+        self._lib = ctx._lib
+        self._refs = [_capi.as_bytes(s) for s in refs]
+        self._reads = [_capi.as_bytes(s) for s in reads]
+        self.n_refs, self.n_reads = len(self._refs), len(self._reads)      # the SOURCES
+        self._specs = normalise_pairs(pairs)
+        rb, ro = _capi.pack(self._refs)
+        qb, qo = _capi.pack(self._reads)
+        h = C.c_void_p()
+        check(self._lib.swmi_batch_upload_pairs(ctx._h, rb, ro, self.n_refs, qb, qo, self.n_reads, _spec_array(self._specs),
+                                                len(self._specs), C.byref(h)))
+        self._h = h
+
+    def n_pairs(self):
+        return len(self._specs)
+
+    def set_pairs(self, pairs):
+        """another list on the same resident sources (swmi_batch_set_pairs); the results of the old one are dropped.  A list
+        the library refuses leaves the batch as it was."""
+        specs = normalise_pairs(pairs)
+        check(self._lib.swmi_batch_set_pairs(self._ctx._h, self._h, _spec_array(specs), len(specs)))
+        self._specs = specs
+        return self
+
+    def spec(self, pair):
+        """(ref, read, ref_start, ref_len, read_start, read_len, reverse) of the pair as the library holds it: lengths resolved"""
+        sp = PairSpec()
+        check(self._lib.swmi_batch_pair_spec(self._h, pair, C.byref(sp)))
+        return (sp.ref, sp.read, sp.ref_start, sp.ref_len, sp.read_start, sp.read_len, bool(sp.flags & _capi.SPEC_REVERSE))
+
+    def segments(self, pair):
+        """(reference segment, read segment) of the pair as str, cut -- and reversed -- on the host"""
+        a, b = cut_segments(self._refs, self._reads, self._specs[pair])
+        return a.decode("latin-1"), b.decode("latin-1")
+
+    def to_source(self, pair, i, j):
+        """(read byte, reference byte), 0-based in the sources, of cell (i, j) of the pair (1-based, as end_i / end_j)"""
+        a, b = cut_segments(self._refs, self._reads, self._specs[pair])
+        return cell_to_source(self._specs[pair], (len(a), len(b)), i, j)
 
 
 class Stream:

@@ -303,7 +303,7 @@ int swmi_host::check_offsets(const uint64_t *off, uint32_t n, const char *what) 
 extern "C" void swmi_batch_free(swmi_ctx *ctx, swmi_batch *b) {
     if (!b) return;
     if (ctx) (void)hipSetDevice(ctx->device);
-    b->d_raw.release(); b->d_raw_off.release();
+    b->d_raw.release(); b->d_raw_off.release(); b->d_src_off.release();
     b->d_seqw.release(); b->d_refs.release(); b->d_reads.release(); b->d_pairs.release();
     b->d_dir.release(); b->d_seam.release(); b->d_result.release(); b->d_cells.release();
     b->d_cells_off.release(); b->d_cells_cap.release(); b->d_dbg.release(); b->d_dbg2.release();
@@ -378,5 +378,152 @@ extern "C" int swmi_batch_upload(swmi_ctx *ctx,
     b->read_bytes.assign(read_bytes, read_bytes + read_off[n_reads]);
     if ((rc = upload_device(ctx, b.get(), ctx->stream, ref_bytes, read_bytes))) { swmi_batch_free(ctx, b.release()); return rc; }
     *out = b.release();
+    return SWMI_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// pair lists (swmi.h: swmi_batch_upload_pairs)
+// ------------------------------------------------------------------------------------------
+// The refusals of a list, on the host and before anything is uploaded or launched: `out` receives the list with
+// SWMI_SPEC_WHOLE resolved.  After it every segment lies inside its source, which is all sw_gather_kernel relies on.
+static int check_specs(const uint64_t *ref_off, uint32_t n_refs, const uint64_t *read_off, uint32_t n_reads, const swmi_pair_spec *specs,
+                       uint64_t n_pairs, std::vector<swmi_pair_spec> &out) {
+    if (n_pairs >= (1ull << 32)) return fail(SWMI_ERR_UNSUPPORTED, "more than 2^32-1 pairs in one batch (%llu)", (unsigned long long)n_pairs);
+    if (n_pairs && !specs) return fail(SWMI_ERR_INVALID, "specs is null with n_pairs = %llu (pair 0 is missing)", (unsigned long long)n_pairs);
+    out.resize(n_pairs);
+    for (uint64_t k = 0; k < n_pairs; k++) {
+        swmi_pair_spec sp = specs[k];
+        const unsigned long long kk = k;
+        if (sp.flags & ~SWMI_SPEC_REVERSE) return fail(SWMI_ERR_INVALID, "pair %llu: unknown flag bits 0x%x (only SWMI_SPEC_REVERSE is defined)", kk, sp.flags);
+        if (sp.reserved) return fail(SWMI_ERR_INVALID, "pair %llu: reserved must be 0, got %u", kk, sp.reserved);
+        if (sp.ref >= n_refs) return fail(SWMI_ERR_INVALID, "pair %llu: reference %u out of range (%u uploaded)", kk, sp.ref, n_refs);
+        if (sp.read >= n_reads) return fail(SWMI_ERR_INVALID, "pair %llu: read %u out of range (%u uploaded)", kk, sp.read, n_reads);
+        const uint64_t ref_len = ref_off[sp.ref + 1] - ref_off[sp.ref], read_len = read_off[sp.read + 1] - read_off[sp.read];
+        if (sp.ref_len == SWMI_SPEC_WHOLE && sp.ref_start <= ref_len) sp.ref_len = (uint32_t)(ref_len - sp.ref_start);
+        if (sp.read_len == SWMI_SPEC_WHOLE && sp.read_start <= read_len) sp.read_len = (uint32_t)(read_len - sp.read_start);
+        if ((uint64_t)sp.ref_start + sp.ref_len > ref_len)
+            return fail(SWMI_ERR_INVALID, "pair %llu: reference segment [%u, %u + %u) runs past the end of reference %u (%llu bytes)", kk,
+                        sp.ref_start, sp.ref_start, sp.ref_len, sp.ref, (unsigned long long)ref_len);
+        if ((uint64_t)sp.read_start + sp.read_len > read_len)
+            return fail(SWMI_ERR_INVALID, "pair %llu: read segment [%u, %u + %u) runs past the end of read %u (%llu bytes)", kk, sp.read_start,
+                        sp.read_start, sp.read_len, sp.read, (unsigned long long)read_len);
+        out[k] = sp;
+    }
+    return SWMI_OK;
+}
+
+// Device side of a pair list.  d_raw: the reference sources, the read sources from a 16-byte boundary (as upload_device lays
+// them out), then from a 4-byte boundary the raw bytes of every REVERSED segment, each a whole number of dwords (written by the
+// kernel).  d_raw_off / d_src_off: n_pairs + 1 entries for the reference segments, then n_pairs + 1 for the read segments (the
+// emitters' indexing, TraceArgs.raw_reads_at = n_pairs + 1; the last entry of a side is not read).  The sources get no image.
+// `specs` is checked (check_specs); the batch's host state changes only once nothing can be refused any more.
+static int pairs_to_device(swmi_ctx *ctx, swmi_batch *b, hipStream_t st, std::vector<swmi_pair_spec> &specs) {
+    const uint32_t np = (uint32_t)specs.size();
+    const uint64_t ref_total = b->ref_off[b->n_src_refs], read_total = b->read_off[b->n_src_reads];
+    const uint64_t read_base = (ref_total + 15) & ~(uint64_t)15;
+    std::vector<uint64_t> roff((size_t)np + 1, 0), qoff((size_t)np + 1, 0);          // the segments' lengths as offsets, for layout_sequences
+    for (uint32_t k = 0; k < np; k++) { roff[k + 1] = roff[k] + specs[k].ref_len; qoff[k + 1] = qoff[k] + specs[k].read_len; }
+    std::vector<SeqDesc> ref_desc, read_desc;
+    uint64_t words = layout_sequences(roff.data(), np, 0, ref_desc);
+    words = layout_sequences(qoff.data(), np, words, read_desc);
+    words = ((words + 3) & ~(uint64_t)3) + SWMI_SEQ_PAD_WORDS;
+    if (words >= (1ull << 32)) return fail(SWMI_ERR_UNSUPPORTED, "sequence image exceeds 16 GiB (the images of the %u pairs' segments together)", np);
+    const size_t side = (size_t)np + 1;
+    std::vector<uint64_t> raw_off(2 * side, 0), src_off(2 * side, 0);
+    uint64_t rev_at = (read_base + read_total + 3) & ~(uint64_t)3;
+    for (uint32_t k = 0; k < np; k++) {
+        const swmi_pair_spec &sp = specs[k];
+        const uint64_t rs = b->ref_off[sp.ref] + sp.ref_start, qs = read_base + b->read_off[sp.read] + sp.read_start;
+        if (sp.flags & SWMI_SPEC_REVERSE) {
+            src_off[k] = rs | (1ull << 63); src_off[side + k] = qs | (1ull << 63);
+            raw_off[k] = rev_at; rev_at += 4 * (((uint64_t)sp.ref_len + 3) / 4);
+            raw_off[side + k] = rev_at; rev_at += 4 * (((uint64_t)sp.read_len + 3) / 4);
+        } else {
+            src_off[k] = raw_off[k] = rs;
+            src_off[side + k] = raw_off[side + k] = qs;
+        }
+    }
+    int rc;
+    const size_t raw_need = rev_at + 16;
+    if (raw_need > b->d_raw.cap) b->sources_on_device = false;         // (growing the buffer drops what it held)
+    if ((rc = b->d_raw.reserve(raw_need))) return rc;
+    if ((rc = b->d_seqw.reserve(words * 4))) return rc;
+    if ((rc = b->d_raw_off.reserve(2 * side * 8))) return rc;
+    if ((rc = b->d_src_off.reserve(2 * side * 8))) return rc;
+    if ((rc = b->d_refs.reserve(std::max<size_t>(np, 1) * sizeof(SeqDesc)))) return rc;
+    if ((rc = b->d_reads.reserve(std::max<size_t>(np, 1) * sizeof(SeqDesc)))) return rc;
+    // from here on the batch is the new list
+    b->n_refs = b->n_reads = np;
+    b->specs.swap(specs);
+    b->ref_desc.swap(ref_desc); b->read_desc.swap(read_desc);
+    b->work.clear(); b->work_key = SchedKey{}; b->plan_key = PlanKey{}; b->pairs_dev_ptr = nullptr; b->pairs_on_device.clear();
+    b->has_run = false; b->acgt_known = false; b->auto_choice = -1;
+    b->pairs.clear(); b->alns.clear(); b->str_at.clear(); b->str_buf.clear(); b->raw.clear(); b->rtab.clear(); b->raw_chunks.clear();
+    b->raw_ext = nullptr; b->rtab_ext = nullptr; b->indexed = false; b->win_tab.clear(); b->win_at.clear();
+    uint8_t *raw = b->d_raw.as<uint8_t>();
+    if (!b->sources_on_device) {
+        if (ref_total) HIP_TRY(hipMemcpyAsync(raw, b->ref_bytes.data(), ref_total, hipMemcpyHostToDevice, st));
+        if (read_total) HIP_TRY(hipMemcpyAsync(raw + read_base, b->read_bytes.data(), read_total, hipMemcpyHostToDevice, st));
+    }
+    HIP_TRY(hipMemsetAsync(b->d_seqw.p, 0, words * 4, st));
+    uint64_t *d_raw_off = b->d_raw_off.as<uint64_t>(), *d_src_off = b->d_src_off.as<uint64_t>();
+    HIP_TRY(hipMemcpyAsync(d_raw_off, raw_off.data(), 2 * side * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_src_off, src_off.data(), 2 * side * 8, hipMemcpyHostToDevice, st));
+    if (np) {
+        HIP_TRY(hipMemcpyAsync(b->d_refs.p, b->ref_desc.data(), np * sizeof(SeqDesc), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(b->d_reads.p, b->read_desc.data(), np * sizeof(SeqDesc), hipMemcpyHostToDevice, st));
+    }
+    HIP_TRY(swmi_launch_gather(raw, d_src_off, d_raw_off, b->d_refs.as<SeqDesc>(), b->d_seqw.as<uint32_t>(), ctx->d_lut.as<uint8_t>(), np, st));
+    HIP_TRY(swmi_launch_gather(raw, d_src_off + side, d_raw_off + side, b->d_reads.as<SeqDesc>(), b->d_seqw.as<uint32_t>(),
+                               ctx->d_lut.as<uint8_t>(), np, st));
+    HIP_TRY(hipStreamSynchronize(st));               // (the host vectors above are pageable locals)
+    b->sources_on_device = true;
+    return SWMI_OK;
+}
+
+extern "C" int swmi_batch_upload_pairs(swmi_ctx *ctx,
+                                       const uint8_t *ref_bytes, const uint64_t *ref_off, uint32_t n_refs,
+                                       const uint8_t *read_bytes, const uint64_t *read_off, uint32_t n_reads,
+                                       const swmi_pair_spec *specs, uint64_t n_pairs, swmi_batch **out) {
+    if (!ctx || !out) return fail(SWMI_ERR_INVALID, "null argument");
+    *out = nullptr;
+    int rc;
+    if ((rc = check_offsets(ref_off, n_refs, "reference"))) return rc;
+    if ((rc = check_offsets(read_off, n_reads, "read"))) return rc;
+    if ((n_refs && ref_off[n_refs] && !ref_bytes) || (n_reads && read_off[n_reads] && !read_bytes))
+        return fail(SWMI_ERR_INVALID, "sequence bytes are null");
+    std::vector<swmi_pair_spec> resolved;
+    if ((rc = check_specs(ref_off, n_refs, read_off, n_reads, specs, n_pairs, resolved))) return rc;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    HIP_TRY(hipSetDevice(ctx->device));
+    std::unique_ptr<swmi_batch> b(new swmi_batch);
+    b->paired = true;
+    b->n_src_refs = n_refs; b->n_src_reads = n_reads;
+    b->ref_off.assign(ref_off, ref_off + n_refs + 1);
+    b->read_off.assign(read_off, read_off + n_reads + 1);
+    // (kept: host-built strings are cut from them, and a list with a larger reversed area uploads them again)
+    b->ref_bytes.assign(ref_bytes, ref_bytes + ref_off[n_refs]);
+    b->read_bytes.assign(read_bytes, read_bytes + read_off[n_reads]);
+    if ((rc = pairs_to_device(ctx, b.get(), ctx->stream, resolved))) { swmi_batch_free(ctx, b.release()); return rc; }
+    *out = b.release();
+    return SWMI_OK;
+}
+
+extern "C" int swmi_batch_set_pairs(swmi_ctx *ctx, swmi_batch *b, const swmi_pair_spec *specs, uint64_t n_pairs) {
+    if (!ctx || !b) return fail(SWMI_ERR_INVALID, "null argument");
+    if (!b->paired) return fail(SWMI_ERR_INVALID, "the batch is a cross product (swmi_batch_upload): only a batch of swmi_batch_upload_pairs takes a pair list");
+    std::lock_guard<std::mutex> g(ctx->mu);
+    int rc;
+    std::vector<swmi_pair_spec> resolved;
+    if ((rc = check_specs(b->ref_off.data(), b->n_src_refs, b->read_off.data(), b->n_src_reads, specs, n_pairs, resolved))) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    return pairs_to_device(ctx, b, ctx->stream, resolved);
+}
+
+extern "C" int swmi_batch_pair_spec(const swmi_batch *b, uint64_t pair, swmi_pair_spec *spec) {
+    if (!b || !spec) return fail(SWMI_ERR_INVALID, "null argument");
+    if (!b->paired) return fail(SWMI_ERR_INVALID, "the batch is a cross product (swmi_batch_upload): its pairs have no spec");
+    if (pair >= b->specs.size()) return fail(SWMI_ERR_RANGE, "pair %llu out of range", (unsigned long long)pair);
+    *spec = b->specs[pair];
     return SWMI_OK;
 }

@@ -241,7 +241,7 @@ struct PairRes {
 struct SiteRef { uint64_t pair; uint64_t k; int32_t begin; };
 
 struct Work {            // one pair scheduled for a launch
-    uint32_t pair;       // ref * n_reads + read
+    uint32_t pair;       // ref * n_reads + read (a pair list: the position in the list)
     uint64_t cells;      // m * n
     uint64_t dir_words;  // workspace dwords (direction field or checkpoints)
     uint64_t seam_words;
@@ -294,6 +294,15 @@ struct __attribute__((visibility("hidden"))) ChunkPlan {
 
 struct swmi_batch {
     uint32_t n_refs = 0, n_reads = 0;
+    // A PAIR LIST (swmi_batch_upload_pairs): the sequences of the batch -- n_refs, n_reads, ref_desc, read_desc, d_refs, d_reads,
+    // the images in d_seqw -- are the SEGMENTS, n_pairs on either side, pair k = (reference segment k, read segment k); everything
+    // from the schedule down sees Work, PairDesc and SeqDesc as for a cross product.  ref_bytes / read_bytes / ref_off / read_off
+    // are the SOURCES (n_src_refs, n_src_reads of them), resident in d_raw; specs[k] is pair k with SWMI_SPEC_WHOLE resolved.
+    bool paired = false;
+    uint32_t n_src_refs = 0, n_src_reads = 0;
+    std::vector<swmi_pair_spec> specs;
+    bool sources_on_device = false;         // d_raw holds the sources (it is grown, and filled again, when a list needs a larger reversed area)
+    DevBuf d_src_off;                       // per segment: where sw_gather_kernel reads it (bit 63: reversed), indexed as d_raw_off
     // original bytes (for string building: characters keep their case) and offsets
     std::vector<uint8_t> ref_bytes, read_bytes;
     // a streamed chunk keeps no copy of its references: their bytes are read again from the mapped file when an
@@ -361,6 +370,12 @@ struct swmi_batch {
     std::vector<uint64_t> ref_degenerate;   // leading (0,"","") sites per ref
     swmi_timing timing{};
 };
+
+// Which sequences a pair is made of: the cross product's division, or the identity of a pair list.  Every place that turns a
+// pair index into its two sequences goes through these two.
+static inline uint64_t batch_n_pairs(const swmi_batch *b) { return b->paired ? (uint64_t)b->n_refs : (uint64_t)b->n_refs * b->n_reads; }
+static inline uint32_t pair_ref(const swmi_batch *b, uint64_t pair) { return b->paired ? (uint32_t)pair : (uint32_t)(pair / b->n_reads); }
+static inline uint32_t pair_read(const swmi_batch *b, uint64_t pair) { return b->paired ? (uint32_t)pair : (uint32_t)(pair % b->n_reads); }
 
 struct RunState {
     swmi_ctx *ctx;

@@ -50,3 +50,6 @@ extern "C" hipError_t swmi_launch_affine_traceback(const TraceArgs *a, const Aff
                                                    uint32_t ops_words, hipStream_t st);
 extern "C" hipError_t swmi_launch_encode(const uint8_t *raw, const uint64_t *raw_off, SeqDesc *desc, uint32_t *seqw,
                                          const uint8_t *lut, uint32_t n_seq, hipStream_t st);
+// pair lists: the segments' images (and the raw bytes of reversed segments) from the resident sources (sw_gather_kernel)
+extern "C" hipError_t swmi_launch_gather(uint8_t *raw, const uint64_t *src_off, const uint64_t *raw_off, SeqDesc *desc, uint32_t *seqw,
+                                         const uint8_t *lut, uint32_t n_seg, hipStream_t st);

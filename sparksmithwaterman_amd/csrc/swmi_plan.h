@@ -261,12 +261,11 @@ struct Planner {
 // host arithmetic: fills `plan` in place and the arrays of `it`
 static int plan_chunk(swmi_ctx *ctx, swmi_batch *b, const std::vector<Work> &work, size_t lo, size_t np, bool exact, ChunkPlan &plan,
                       PlanItems &it) {
-    const uint32_t n_reads = b->n_reads;
     plan = ChunkPlan{};
     Planner pl(ctx, b, np, exact, plan, it);
     if (pl.res_possible)
         for (size_t k = 0; k < np && !pl.res_maybe; k++)
-            pl.res_maybe = pl.res_size_fits(b->read_desc[work[lo + k].pair % n_reads].len, b->ref_desc[work[lo + k].pair / n_reads].len);
+            pl.res_maybe = pl.res_size_fits(b->read_desc[pair_read(b, work[lo + k].pair)].len, b->ref_desc[pair_ref(b, work[lo + k].pair)].len);
     if ((pl.cols_possible || pl.res_maybe || pl.tf_possible) && !b->acgt_known) {
         // the fast-symbol flags are derived on the device by the encode kernel
         if (b->n_refs) HIP_TRY(hipMemcpy(b->ref_desc.data(), b->d_refs.p, b->n_refs * sizeof(SeqDesc), hipMemcpyDeviceToHost));
@@ -281,8 +280,8 @@ static int plan_chunk(swmi_ctx *ctx, swmi_batch *b, const std::vector<Work> &wor
     for (size_t k = 0; k < np; k++) {
         const Work &w = work[lo + k];
         PairDesc d{};
-        d.ref_id = w.pair / n_reads;
-        d.read_id = w.pair % n_reads;
+        d.ref_id = pair_ref(b, w.pair);
+        d.read_id = pair_read(b, w.pair);
         d.out_id = (uint32_t)k;
         const uint32_t m_ = b->read_desc[d.read_id].len, n_ = b->ref_desc[d.ref_id].len;
         if (b->eff_mode == 1) {

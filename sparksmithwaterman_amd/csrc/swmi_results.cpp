@@ -115,12 +115,12 @@ static int ensure_indexed(swmi_batch *b) {
 // ------------------------------------------------------------------------------------------
 // result accessors
 // ------------------------------------------------------------------------------------------
-extern "C" uint64_t swmi_batch_n_pairs(const swmi_batch *b) { return b ? (uint64_t)b->n_refs * b->n_reads : 0; }
+extern "C" uint64_t swmi_batch_n_pairs(const swmi_batch *b) { return b ? batch_n_pairs(b) : 0; }
 
 static int check_pair(const swmi_batch *b, uint64_t pair) {
     if (!b) return fail(SWMI_ERR_INVALID, "batch is null");
     if (!b->has_run) return fail(SWMI_ERR_INVALID, "batch has no results (run it first)");
-    if (pair >= (uint64_t)b->n_refs * b->n_reads) return fail(SWMI_ERR_RANGE, "pair %llu out of range", (unsigned long long)pair);
+    if (pair >= batch_n_pairs(b)) return fail(SWMI_ERR_RANGE, "pair %llu out of range", (unsigned long long)pair);
     return SWMI_OK;
 }
 
@@ -146,7 +146,7 @@ extern "C" int swmi_pair_rows_swept(const swmi_batch *b, uint64_t pair, uint32_t
     int rc = check_pair(b, pair);
     if (rc) return rc;
     const PairRes &pr = b->pairs[pair];
-    if (rows) *rows = pr.strips ? pr.strips * SWMI_AFF_MAX_READ : b->read_desc[pair % b->n_reads].len;
+    if (rows) *rows = pr.strips ? pr.strips * SWMI_AFF_MAX_READ : b->read_desc[pair_read(b, pair)].len;
     return SWMI_OK;
 }
 
@@ -155,7 +155,7 @@ extern "C" int swmi_pair_band_window(const swmi_batch *b, uint64_t pair, uint32_
     int rc = check_pair(b, pair);
     if (rc) return rc;
     const PairRes &pr = b->pairs[pair];
-    const uint32_t m = b->read_desc[pair % b->n_reads].len, n = b->ref_desc[pair / b->n_reads].len;
+    const uint32_t m = b->read_desc[pair_read(b, pair)].len, n = b->ref_desc[pair_ref(b, pair)].len;
     const uint32_t ns = swmi_aff_strips(m), swept = pr.strips ? pr.strips : ns;
     if (strip >= ns) return fail(SWMI_ERR_RANGE, "strip %u: the read of pair %llu has %u strip%s", strip, (unsigned long long)pair, ns, ns == 1 ? "" : "s");
     if (strip >= swept) return fail(SWMI_ERR_RANGE, "strip %u of pair %llu was not swept: xdrop ended the sweep behind strip %u", strip,
@@ -180,8 +180,8 @@ extern "C" int swmi_pair_band_window(const swmi_batch *b, uint64_t pair, uint32_
 extern "C" int swmi_batch_pair_results(const swmi_batch *b, int32_t *scores, uint64_t *n_alignments, uint64_t n) {
     if (!b) return fail(SWMI_ERR_INVALID, "batch is null");
     if (!b->has_run) return fail(SWMI_ERR_INVALID, "batch has no results (run it first)");
-    if (n != (uint64_t)b->n_refs * b->n_reads) return fail(SWMI_ERR_RANGE, "the batch has %llu pairs, not %llu",
-                                                           (unsigned long long)b->n_refs * b->n_reads, (unsigned long long)n);
+    if (n != batch_n_pairs(b)) return fail(SWMI_ERR_RANGE, "the batch has %llu pairs, not %llu",
+                                           (unsigned long long)batch_n_pairs(b), (unsigned long long)n);
     if (b->scores_only && n_alignments)
         return fail(SWMI_ERR_INVALID, "the batch was run with scores_only = 1: pass n_alignments = NULL");
     for (uint64_t k = 0; k < n; k++) {
@@ -194,9 +194,20 @@ extern "C" int swmi_batch_pair_results(const swmi_batch *b, int32_t *scores, uin
 // Pops the traceback "stack" into the two aligned strings (SmithWaterman.java:418-431): ops are stored
 // from the max cell backwards, so the strings are built by walking them in reverse.
 static void materialise(swmi_batch *b, uint64_t pair, HostAln &a, uint64_t slot) {
-    const uint32_t r = (uint32_t)(pair / b->n_reads), q = (uint32_t)(pair % b->n_reads);
-    const uint8_t *ref;
-    if (b->src_map) {
+    const uint32_t r = pair_ref(b, pair), q = pair_read(b, pair);
+    const uint8_t *ref, *read;
+    std::vector<uint8_t> rev_ref, rev_read;      // a reversed pair of a pair list: its two segments as the kernels saw them
+    if (b->paired) {
+        // a pair list: the segments are cut -- and reversed -- from the batch's copy of the source bytes
+        const swmi_pair_spec &sp = b->specs[pair];
+        ref = b->ref_bytes.data() + b->ref_off[sp.ref] + sp.ref_start;
+        read = b->read_bytes.data() + b->read_off[sp.read] + sp.read_start;
+        if (sp.flags & SWMI_SPEC_REVERSE) {
+            rev_ref.assign(std::make_reverse_iterator(ref + sp.ref_len), std::make_reverse_iterator(ref));
+            rev_read.assign(std::make_reverse_iterator(read + sp.read_len), std::make_reverse_iterator(read));
+            ref = rev_ref.data(); read = rev_read.data();
+        }
+    } else if (b->src_map) {
         auto it = b->src_cache.find(r);
         if (it == b->src_cache.end()) {
             it = b->src_cache.emplace(r, std::vector<uint8_t>()).first;
@@ -206,7 +217,7 @@ static void materialise(swmi_batch *b, uint64_t pair, HostAln &a, uint64_t slot)
     } else {
         ref = b->ref_bytes.data() + b->ref_off[r];
     }
-    const uint8_t *read = b->read_bytes.data() + b->read_off[q];
+    if (!b->paired) read = b->read_bytes.data() + b->read_off[q];
     char *sr = b->str_buf.data() + b->str_at[slot], *sq = sr + a.n_ops + 1;
     sr[a.n_ops] = 0; sq[a.n_ops] = 0;
     int64_t i = a.end_i, j = a.end_j;     // 1-based cell of the op being emitted (both >= 1 while ops remain)
@@ -266,7 +277,7 @@ extern "C" int swmi_pair_alignment(swmi_batch *b, uint64_t pair, uint64_t k,
     if (k >= pr.n_cells) return fail(SWMI_ERR_RANGE, "alignment %llu out of range", (unsigned long long)k);
     if (pr.flags & SWMI_PAIR_DEGENERATE) {
         // every cell, row-major, traces to (0, "", "")  (SmithWaterman.java:378-380)
-        const uint32_t n = b->ref_desc[pair / b->n_reads].len;
+        const uint32_t n = b->ref_desc[pair_ref(b, pair)].len;
         if (begin) *begin = 0;
         if (end_i) *end_i = (int32_t)(k / n) + 1;
         if (end_j) *end_j = (int32_t)(k % n) + 1;
@@ -301,7 +312,7 @@ extern "C" int swmi_batch_materialise_all(swmi_batch *b, uint64_t *n_alignments,
     int rc = ensure_indexed(b);
     if (rc) return rc;
     uint64_t na = 0, nc = 0;
-    const uint64_t np = (uint64_t)b->n_refs * b->n_reads;
+    const uint64_t np = batch_n_pairs(b);
     for (uint64_t pair = 0; pair < np; pair++) {
         const PairRes &pr = b->pairs[pair];
         if (pr.flags & SWMI_PAIR_DEGENERATE) { na += pr.n_cells; continue; }     // (0, "", "") each: nothing to build
@@ -345,8 +356,14 @@ extern "C" int swmi_batch_materialise_all(swmi_batch *b, uint64_t *n_alignments,
 // ------------------------------------------------------------------------------------------
 // MapRef view (Distribution.java:403-436)
 // ------------------------------------------------------------------------------------------
+// (a pair list has no "all reads of one reference": the views are refused there, swmi.h)
+static int unsupported_on_pair_list(const char *what) {
+    return fail(SWMI_ERR_UNSUPPORTED, "%s needs the cross product refs x reads: the batch is a pair list (swmi_batch_upload_pairs)", what);
+}
+
 static int check_ref(const swmi_batch *b, uint32_t ref) {
     if (!b) return fail(SWMI_ERR_INVALID, "batch is null");
+    if (b->paired) return unsupported_on_pair_list("a MapRef view");
     if (!b->has_run) return fail(SWMI_ERR_INVALID, "batch has no results (run it first)");
     if (ref >= b->n_refs) return fail(SWMI_ERR_RANGE, "reference %u out of range", ref);
     return SWMI_OK;
@@ -363,6 +380,7 @@ extern "C" int swmi_ref_total(const swmi_batch *b, uint32_t ref, int32_t *total)
 
 extern "C" int swmi_ref_totals(const swmi_batch *b, int32_t *totals, uint32_t n) {
     if (!b || !totals) return fail(SWMI_ERR_INVALID, "null argument");
+    if (b->paired) return unsupported_on_pair_list("swmi_ref_totals");
     if (!b->has_run) return fail(SWMI_ERR_INVALID, "batch has no results (run it first)");
     if (n != b->n_refs) return fail(SWMI_ERR_RANGE, "totals has %u entries, the batch has %u references", n, b->n_refs);
     for (uint32_t r = 0; r < b->n_refs; r++) {
@@ -425,6 +443,7 @@ extern "C" int swmi_ref_sites_packed(swmi_batch *b, uint32_t ref_lo, uint32_t re
                                      int32_t *begins, uint32_t *lens, uint64_t *str_off, uint64_t sites_cap,
                                      uint8_t *blob, uint64_t blob_cap, uint64_t *n_sites, uint64_t *blob_bytes) {
     if (!b) return fail(SWMI_ERR_INVALID, "batch is null");
+    if (b->paired) return unsupported_on_pair_list("swmi_ref_sites_packed");
     if (!b->has_run) return fail(SWMI_ERR_INVALID, "batch has no results (run it first)");
     if (ref_lo > ref_hi || ref_hi > b->n_refs) return fail(SWMI_ERR_RANGE, "reference range [%u, %u) out of range", ref_lo, ref_hi);
     int rc = ensure_indexed(b);

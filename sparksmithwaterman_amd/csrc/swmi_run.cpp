@@ -351,7 +351,7 @@ static void collect_scores(const swmi_batch *b, const std::vector<Work> &work, c
         if (o.score <= 0 && !(o.flags & SWMI_F_DEGENERATE) && b->opt.modes.align_mode == 0) {
             const uint32_t pair = work[L.lo + k].pair;
             o.score = 0; o.flags = SWMI_F_DEGENERATE;
-            o.n_cells = (uint64_t)b->read_desc[pair % b->n_reads].len * b->ref_desc[pair / b->n_reads].len;
+            o.n_cells = (uint64_t)b->read_desc[pair_read(b, pair)].len * b->ref_desc[pair_ref(b, pair)].len;
         }
         o.flags &= SWMI_F_DEGENERATE | SWMI_F_STRIPS_MASK;      // (the strips swept under option "xdrop" stay)
     }
@@ -722,15 +722,14 @@ static int check_run_params(const swmi_ctx *ctx, const swmi_batch *b, const swmi
 // (measured, profiles/r02/sweeps_*.md: with ~5 alignments per pair the split traceback wins up to ~200 pairs; from a
 // few hundred pairs on one workgroup per pair keeps every SIMD busy anyway and its teams share the window re-sweeps)
 static int choose_traceback_grain(swmi_ctx *ctx, swmi_batch *b, const swmi_params *p) {
-    const uint32_t n_reads = b->n_reads;
-    const uint64_t n_pairs = (uint64_t)b->n_refs * n_reads;
+    const uint64_t n_pairs = batch_n_pairs(b);
     if (!(ctx->tb_split < 0 && !ctx->scores_only && b->eff_mode == 1 && n_pairs >= 64 && n_pairs <= 256 &&
           (b->auto_choice < 0 || memcmp(&b->auto_params, p, sizeof(swmi_params)) != 0)))
         return SWMI_OK;
     std::vector<Work> sample;
     const uint64_t want = 48, stride = std::max<uint64_t>(1, n_pairs / want);
     for (uint64_t pi = stride / 2; pi < n_pairs && sample.size() < want; pi += stride) {
-        const uint32_t m = b->read_desc[pi % n_reads].len, n = b->ref_desc[pi / n_reads].len;
+        const uint32_t m = b->read_desc[pair_read(b, pi)].len, n = b->ref_desc[pair_ref(b, pi)].len;
         if (m == 0 || n == 0) continue;
         Work w;
         w.pair = (uint32_t)pi; w.cells = (uint64_t)m * n;
@@ -765,18 +764,18 @@ static void build_schedule(const swmi_ctx *ctx, swmi_batch *b) {
     if (b->work_key == key) return;
     const uint32_t n_refs = b->n_refs, n_reads = b->n_reads;
     b->work.clear();
-    b->work.reserve((uint64_t)n_refs * n_reads);
+    b->work.reserve(batch_n_pairs(b));
     b->work_cells = 0;
     // Longest first: the tail of a launch is made of short pairs.  The schedule depends on the LENGTHS only, so the two
     // sides are ordered by length once (n_refs log n_refs + n_reads log n_reads) and the pairs generated in that order --
     // by cells, exactly, whenever one side has a single length (one read, or a FASTA file of equal reads), else by
     // reference length first -- instead of sorting 10^6..10^8 pair records.
-    std::vector<uint32_t> ro(n_refs), qo(n_reads);
+    std::vector<uint32_t> ro(b->paired ? 0u : n_refs), qo(b->paired ? 0u : n_reads);     // (a pair list is sorted pair by pair, below)
     std::iota(ro.begin(), ro.end(), 0u);
     std::iota(qo.begin(), qo.end(), 0u);
     std::stable_sort(ro.begin(), ro.end(), [&](uint32_t a, uint32_t c) { return b->ref_desc[a].len > b->ref_desc[c].len; });
     std::stable_sort(qo.begin(), qo.end(), [&](uint32_t a, uint32_t c) { return b->read_desc[a].len > b->read_desc[c].len; });
-    const bool refs_uniform = n_refs && b->ref_desc[ro.front()].len == b->ref_desc[ro.back()].len;
+    const bool refs_uniform = !ro.empty() && b->ref_desc[ro.front()].len == b->ref_desc[ro.back()].len;
     // (mode 3: what the run's options make of a pair's field and seam row -- swmi_aff_pair_*, swmi_device.h)
     const bool aff = b->eff_mode == 3, tf = key.tfused;
     const AffGeom g = key.geom;
@@ -784,13 +783,27 @@ static void build_schedule(const swmi_ctx *ctx, swmi_batch *b) {
     auto dir_words = [&](uint32_t m, uint32_t n) { return aff ? swmi_aff_pair_dir_words(m, n, g) : swmi_dir_words(m, n, b->eff_mode, tf); };
     auto add = [&](uint32_t r, uint32_t q, uint32_t n, uint32_t m, uint64_t dw, uint64_t sw) {
         Work w;
-        w.pair = r * n_reads + q;
+        w.pair = b->paired ? r : r * n_reads + q;
         w.cells = (uint64_t)m * n;
         w.dir_words = dw; w.seam_words = sw;
         b->work_cells += w.cells;
         b->work.push_back(w);
     };
-    if (refs_uniform) {                              // (reads outermost: descending m x the one n)
+    if (b->paired) {
+        // a pair list: the pairs by cells, descending, in list order among equals; a pair with an empty side is left out
+        for (uint32_t k = 0; k < n_refs; k++) {
+            const uint32_t m = b->read_desc[k].len, n = b->ref_desc[k].len;
+            if (m && n) add(k, k, n, m, 0, 0);
+        }
+        std::stable_sort(b->work.begin(), b->work.end(), [](const Work &a, const Work &c) { return a.cells > c.cells; });
+        uint32_t last_m = 0xFFFFFFFFu, last_n = 0xFFFFFFFFu;
+        uint64_t dw = 0, sw = 0;
+        for (Work &w : b->work) {
+            const uint32_t m = b->read_desc[w.pair].len, n = b->ref_desc[w.pair].len;
+            if (m != last_m || n != last_n) { dw = dir_words(m, n); sw = seam_words(m, n); last_m = m; last_n = n; }
+            w.dir_words = dw; w.seam_words = sw;
+        }
+    } else if (refs_uniform) {                       // (reads outermost: descending m x the one n)
         for (uint32_t q : qo) {
             const uint32_t m = b->read_desc[q].len;
             if (m == 0) continue;
@@ -875,8 +888,8 @@ static int batch_run(swmi_ctx *ctx, swmi_batch *b, const swmi_params *p, RunOpti
     b->has_run = false;
     b->scores_only = ctx->scores_only != 0;
 
-    const uint32_t n_refs = b->n_refs;
-    b->pairs.assign((uint64_t)n_refs * b->n_reads, PairRes{});
+    const uint32_t n_refs = b->paired ? 0u : b->n_refs;     // (the references MapRef views exist for: none of a pair list)
+    b->pairs.assign(batch_n_pairs(b), PairRes{});
     b->win_tab.clear(); b->win_at.clear();
     b->alns.clear(); b->str_at.clear();
     b->raw.clear(); b->rtab.clear(); b->raw_chunks.clear(); b->indexed = false;

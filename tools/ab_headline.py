@@ -4,7 +4,10 @@
 Leading NAME=VALUE words of a variant go into the environment of its run, so two builds of the library can be compared
 (SWMI_LIB, sparksmithwaterman_amd/_capi.py); --repeat N runs the whole list N times, interleaved; --raw FILE appends
 every run's JSON line to FILE, prefixed with the variant.
-    python tools/ab_headline.py --repeat 5 --raw ab_raw.txt "SWMI_LIB=/path/to/parent/libswmi.so" "" """
+    python tools/ab_headline.py --repeat 5 --raw ab_raw.txt "SWMI_LIB=/path/to/parent/libswmi.so" ""
+SWMI_TREE=DIR as such a word runs DIR/bench.py instead -- another checkout with its own package and built library: the way to
+compare with a parent whose library lacks symbols this tree's binding declares (the binding refuses such a library).
+    python tools/ab_headline.py --repeat 5 "SWMI_TREE=/path/to/parent/checkout" "" """
 import json
 import os
 import subprocess
@@ -26,7 +29,7 @@ for rep in range(repeat):
         while words and "=" in words[0] and not words[0].startswith("-"):
             k, v = words.pop(0).split("=", 1)
             env[k] = v
-        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "50", "--warmup", "5", "--no-cpu-baseline"] + words,
+        p = subprocess.run([sys.executable, os.path.join(env.pop("SWMI_TREE", ROOT), "bench.py"), "--steps", "50", "--warmup", "5", "--no-cpu-baseline"] + words,
                            capture_output=True, text=True, env=env)
         try:
             line = p.stdout.strip().splitlines()[-1]
