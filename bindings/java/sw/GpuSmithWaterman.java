@@ -49,6 +49,12 @@ public class GpuSmithWaterman
 	/** two-piece gaps: alignScores { match , mismatch , gap , gapOpen , gap2 , gapOpen2 } -- a gap of length k costs
 	 * max( gapOpen + k * gap , gapOpen2 + k * gap2 ) on a global or extend run; gapOpen2 0: off (include/swmi.h: option "gap_open2") */
 	static native void nativeSetGap2( long ctx , int gapOpen2 , int gap2 ) ;
+	/** alignments as CIGARs: 1 M/I/D, 2 =/X/I/D, 0 off (include/swmi.h: option "cigar") */
+	static native void nativeSetCigar( long ctx , int cigar ) ;
+	/** fills info = { begin , last row , last column } and returns the CIGAR entries len &lt;&lt; 4 | op of alignment k, from its start */
+	static native int[] nativePairCigar( long batch , long pair , long k , int[] info ) ;
+	/** the edit distance (SAM's NM) of alignment k: X columns + inserted + deleted bases */
+	static native int nativePairNm( long batch , long pair , long k ) ;
 	/** substitution scores on the context: alphabet = n ISO-8859-1 symbols, scores = n * n, row = read base; null clears */
 	static native void nativeSetScoreMatrix( long ctx , byte[] alphabet , int[] scores ) ;
 	/** a pair list over the sequences: specs = eight ints per pair ( alignPairs ) */
@@ -149,6 +155,26 @@ public class GpuSmithWaterman
 	 * refused.  For every batch aligned from now on, on every executor thread.
 	 */
 	public static void setBandAdapt( boolean bandAdapt ) { BAND_ADAPT = bandAdapt ; }
+
+	/** the CIGAR payload every context asks its runs for, 0: none (applied next to bandAdapt, before every batch) */
+	private static volatile int CIGAR = 0 ;
+	public static final int CIGAR_M = 0 , CIGAR_I = 1 , CIGAR_D = 2 , CIGAR_EQ = 7 , CIGAR_X = 8 ;
+
+	/**
+	 * 1: the GPU writes every alignment as a run-length CIGAR of M / I / D with its edit distance; 2: of = / X / I / D; 0 (the
+	 * default): strings.  Such a run takes the affine kernels; the strings the other methods return stay the same.  For every
+	 * batch aligned from now on, on every executor thread.
+	 */
+	public static void setCigar( int cigar )
+	{
+		if( cigar < 0 || cigar > 2 ) throw new IllegalArgumentException( "cigar must be 0, 1 or 2: " + cigar ) ;
+		CIGAR = cigar ;
+	}
+
+	/** the CIGAR of alignment k of a pair of a native batch run under setCigar: entries len &lt;&lt; 4 | op ( CIGAR_M , ... ), from the alignment's start */
+	static int[] cigar( long batch , long pair , long k ) { return nativePairCigar( batch , pair , k , null ) ; }
+	/** ... and its edit distance */
+	static int nm( long batch , long pair , long k ) { return nativePairNm( batch , pair , k ) ; }
 
 	/** the score matrix every context applies before its next batch: { alphabet , scores } (null: none), and its version */
 	private static volatile Object[] MATRIX = null ;
@@ -255,6 +281,7 @@ public class GpuSmithWaterman
 		nativeSetExtend( ctx , EXTEND ? 1 : 0 ) ;
 		nativeSetXdrop( ctx , XDROP ) ;
 		nativeSetBandAdapt( ctx , BAND_ADAPT ? 1 : 0 ) ;
+		nativeSetCigar( ctx , CIGAR ) ;
 		applyScoreMatrix( nc ) ;
 	}
 

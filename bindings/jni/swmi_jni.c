@@ -91,6 +91,13 @@ JNIEXPORT void JNICALL Java_sw_GpuSmithWaterman_nativeSetBandAdapt(JNIEnv *env, 
     if (swmi_shim_set_band_adapt((swmi_ctx *)(intptr_t)ctx, band_adapt, err, sizeof err) != SWMI_OK) throw_msg(env, err);
 }
 
+/* alignments as CIGARs on this context from now on: 1 M/I/D, 2 =/X/I/D, 0 off */
+JNIEXPORT void JNICALL Java_sw_GpuSmithWaterman_nativeSetCigar(JNIEnv *env, jclass cls, jlong ctx, jint cigar) {
+    char err[640];
+    (void)cls;
+    if (swmi_shim_set_cigar((swmi_ctx *)(intptr_t)ctx, cigar, err, sizeof err) != SWMI_OK) throw_msg(env, err);
+}
+
 /* two-piece gaps on this context from now on: gapOpen2 != 0 on, 0 off */
 JNIEXPORT void JNICALL Java_sw_GpuSmithWaterman_nativeSetGap2(JNIEnv *env, jclass cls, jlong ctx, jint gap_open2, jint gap2) {
     char err[640];
@@ -253,6 +260,38 @@ JNIEXPORT jobjectArray JNICALL Java_sw_GpuSmithWaterman_nativePairAlignment(JNIE
     (*env)->SetObjectArrayElement(env, out, 0, ra);
     (*env)->SetObjectArrayElement(env, out, 1, qa);
     return out;
+}
+
+/* alignment k of a pair after a run under option "cigar": fills info[0..2] = {begin, last row, last column} and returns the entries
+ * len << 4 | op, first entry = start of the alignment */
+JNIEXPORT jintArray JNICALL Java_sw_GpuSmithWaterman_nativePairCigar(JNIEnv *env, jclass cls, jlong batch, jlong pair, jlong k, jintArray info) {
+    char err[640];
+    int32_t b = 0, cell[2] = {0, 0}; const uint32_t *cg = NULL; uint32_t n = 0, nm = 0;
+    jint ji[3];
+    jintArray out;
+    (void)cls;
+    if (swmi_shim_pair_cigar((swmi_batch *)(intptr_t)batch, pair, k, &b, cell, &cg, &n, &nm, err, sizeof err) != SWMI_OK) {
+        throw_msg(env, err);
+        return NULL;
+    }
+    ji[0] = b; ji[1] = cell[0]; ji[2] = cell[1];
+    if (info && (*env)->GetArrayLength(env, info) >= 3) (*env)->SetIntArrayRegion(env, info, 0, 3, ji);
+    out = (*env)->NewIntArray(env, (jsize)n);
+    if (!out) return NULL;                                   /* OutOfMemoryError is already pending */
+    if (n) (*env)->SetIntArrayRegion(env, out, 0, (jsize)n, (const jint *)(const void *)cg);
+    return out;
+}
+
+/* ... and its edit distance (SAM's NM) */
+JNIEXPORT jint JNICALL Java_sw_GpuSmithWaterman_nativePairNm(JNIEnv *env, jclass cls, jlong batch, jlong pair, jlong k) {
+    char err[640];
+    uint32_t nm = 0;
+    (void)cls;
+    if (swmi_shim_pair_cigar((swmi_batch *)(intptr_t)batch, pair, k, NULL, NULL, NULL, NULL, &nm, err, sizeof err) != SWMI_OK) {
+        throw_msg(env, err);
+        return 0;
+    }
+    return (jint)nm;
 }
 
 JNIEXPORT void JNICALL Java_sw_GpuSmithWaterman_nativeFreeBatch(JNIEnv *env, jclass cls, jlong ctx, jlong batch) {

@@ -88,6 +88,25 @@ int swmi_shim_set_band_adapt(swmi_ctx *ctx, int32_t band_adapt, char *err, size_
     return SWMI_OK;
 }
 
+int swmi_shim_set_cigar(swmi_ctx *ctx, int32_t cigar, char *err, size_t err_len) {
+    int rc;
+    if (!ctx) return shim_fail(SWMI_ERR_INVALID, err, err_len, "nativeSetCigar", "context handle is 0");
+    if ((rc = swmi_set_option(ctx, "cigar", cigar)) != SWMI_OK)
+        return shim_fail(rc, err, err_len, "nativeSetCigar", swmi_last_error());
+    return SWMI_OK;
+}
+
+int swmi_shim_pair_cigar(swmi_batch *b, int64_t pair, int64_t k, int32_t *begin, int32_t cell[2], const uint32_t **cigar,
+                         uint32_t *n_cigar, uint32_t *nm, char *err, size_t err_len) {
+    int32_t ei = 0, ej = 0;
+    int rc;
+    if (pair < 0 || k < 0) return shim_fail(SWMI_ERR_RANGE, err, err_len, "nativePairCigar", "negative index");
+    rc = swmi_pair_cigar(b, (uint64_t)pair, (uint64_t)k, begin, &ei, &ej, cigar, n_cigar, nm);
+    if (rc != SWMI_OK) return shim_fail(rc, err, err_len, "swmi_pair_cigar", swmi_last_error());
+    if (cell) { cell[0] = ei; cell[1] = ej; }
+    return SWMI_OK;
+}
+
 int swmi_shim_set_score_matrix(swmi_ctx *ctx, const signed char *alphabet, size_t n, const int32_t *scores, size_t n_scores,
                                char *err, size_t err_len) {
     int rc;

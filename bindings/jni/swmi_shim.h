@@ -76,6 +76,13 @@ int swmi_shim_set_band_adapt(swmi_ctx *ctx, int32_t band_adapt, char *err, size_
  * gap_open2 = 0 (the default): one-piece gaps, gap2 is not read.  A value > 0 is SWMI_ERR_INVALID and leaves the context as it was
  * (both values: gap2 is checked first, and set only with a valid gap_open2). */
 int swmi_shim_set_gap2(swmi_ctx *ctx, int32_t gap_open2, int32_t gap2, char *err, size_t err_len);
+/* nativeSetCigar: from then on the alignments are returned as CIGARs (swmi_set_option "cigar"): 1 = M / I / D, 2 = '=' / X / I / D,
+ * 0 (the default): off.  Any other value is SWMI_ERR_INVALID and leaves the context as it was.
+ * nativePairCigar: alignment k of a pair after a run under that option, as swmi_pair_cigar hands it out: *cigar points to *n_cigar
+ * entries  len << 4 | op  owned by the batch, *nm is the edit distance, cell[0..1] the alignment's last cell. */
+int swmi_shim_set_cigar(swmi_ctx *ctx, int32_t cigar, char *err, size_t err_len);
+int swmi_shim_pair_cigar(swmi_batch *b, int64_t pair, int64_t k, int32_t *begin, int32_t cell[2], const uint32_t **cigar,
+                         uint32_t *n_cigar, uint32_t *nm, char *err, size_t err_len);
 
 /* nativeSetScoreMatrix: a substitution score matrix on this context (swmi_set_score_matrix): `alphabet` = n symbols narrowed to
  * bytes (ISO-8859-1), `scores` = n * n entries, row = read base, column = reference base (n_scores must be n * n).  n = 0 clears

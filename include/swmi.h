@@ -262,6 +262,23 @@ void        swmi_default_params(swmi_params *p);
  *                are twice the one-piece size (the chunking and the refusal of a pair over max_workspace_bytes see the doubled field).
  *                Unlike gap_open, both are run modes: a run (async runs and stream slots included) takes the values set when it was
  *                asked for.
+ * cigar (default 0 = off and no change; 1 = M / I / D; 2 = '=' / X / I / D; any other value is SWMI_ERR_INVALID and leaves the context
+ *                as it was): the traceback kernels write every alignment as a run-length CIGAR with its edit distance instead of
+ *                strings or packed ops, read with swmi_pair_cigar.  An entry is BAM's,  len << 4 | op  (SWMI_CIGAR_M, _I, _D, _EQ, _X);
+ *                I consumes a read base (the column whose reference string has '_'), D a reference base.  Entries run from the START
+ *                of the alignment to its end cell: the order of the aligned strings, the reverse of the walk.  Adjacent entries
+ *                never have the same op; under cigar = 1 '=' and X merge into M.  Two bases are EQUAL by the library's own rule,
+ *                Character.toUpperCase equality on ISO-8859-1 (equal canonical codes), whatever they score: under a score matrix an
+ *                identical pair with a negative entry is still '=', a positively scored substitution still X.  nm = X columns +
+ *                inserted + deleted bases (SAM's NM), under cigar = 1 too.  len < 2^28 always: an alignment has at most 587,760
+ *                columns.  A run with cigar != 0 takes the affine kernels whatever gap_open / affine say (swmi_batch_mode = 3); with
+ *                gap_open = 0 it gives the linear pipeline's scores and alignments.  The record payload is then the CIGAR:
+ *                device_strings is not read.  scores_only = 1 wins (no records).  Every other accessor works as with device_strings
+ *                = 0 -- the host expands the CIGAR where it expanded the ops -- and returns what the same run with cigar = 0 returns,
+ *                strings with the caller's original case included.  zero_copy, cell_cap, max_workspace_bytes, arena_words_per_pair,
+ *                profiling, every affine option (align_mode, long_reads, band, extend, xdrop, band_adapt, gap_open2 / gap2, a score
+ *                matrix), pair lists and streams apply unchanged; the bounds and refusals are those of the affine run it becomes.
+ *                A run (async runs and stream slots included) takes the value set when it was asked for.
  * Further knobs: spin_us (how long a run polls its stream before it blocks, default 2000); col_chunks (0 automatic,
  * 1 never, N > 1 force up to N column chunks per pair: a launch of few pairs with long references is swept by several
  * wavefronts per pair -- a read of more than 256 rows by several strip pipelines); debug_strip_spins / debug_reverse_strips (tests of the strip pipeline's give-up path);
@@ -377,6 +394,19 @@ int      swmi_batch_pair_results(const swmi_batch *b, int32_t *scores, uint64_t 
 int      swmi_pair_alignment(swmi_batch *b, uint64_t pair, uint64_t k,
                              int32_t *begin, int32_t *end_i, int32_t *end_j,
                              const char **ref_aln, const char **read_aln, uint32_t *len);
+/* Option "cigar": the k-th alignment of the pair as a CIGAR.  *cigar points to *n_cigar entries  len << 4 | op  in the batch's
+ * result memory (valid until the next run / free), first entry = start of the alignment; *nm is the edit distance; begin / end_i /
+ * end_j as swmi_pair_alignment.  Any output pointer may be NULL.  An alignment of a degenerate local pair gives begin = 0,
+ * n_cigar = 0, nm = 0.  k out of range: SWMI_ERR_RANGE.  A batch whose last run had cigar = 0 or scores_only = 1:
+ * SWMI_ERR_UNSUPPORTED. */
+#define SWMI_CIGAR_M  0u
+#define SWMI_CIGAR_I  1u
+#define SWMI_CIGAR_D  2u
+#define SWMI_CIGAR_EQ 7u
+#define SWMI_CIGAR_X  8u
+int      swmi_pair_cigar(swmi_batch *b, uint64_t pair, uint64_t k,
+                         int32_t *begin, int32_t *end_i, int32_t *end_j,
+                         const uint32_t **cigar, uint32_t *n_cigar, uint32_t *nm);
 
 /* Builds the record index and both strings of EVERY alignment of the batch in one native call (what a caller that
  * consumes all of OptAlignments' output pays); returns the number of alignments (degenerate pairs count m*n) and

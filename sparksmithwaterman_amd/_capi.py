@@ -17,6 +17,8 @@ ALIGN_FIT = 1        # the whole read against any stretch of the reference
 ALIGN_GLOBAL = 2     # the whole read against the whole reference
 BAND_MAX = 1 << 20   # option "band": the largest half-width (0: no band)
 XDROP_MAX = (1 << 31) - 1   # option "xdrop": the largest threshold (0: off)
+CIGAR_M, CIGAR_I, CIGAR_D, CIGAR_EQ, CIGAR_X = 0, 1, 2, 7, 8     # option "cigar": the op of an entry  len << 4 | op  (BAM's)
+CIGAR_CHARS = {CIGAR_M: "M", CIGAR_I: "I", CIGAR_D: "D", CIGAR_EQ: "=", CIGAR_X: "X"}
 PAIR_DEGENERATE = 0x1
 SPEC_REVERSE = 0x1          # swmi_pair_spec.flags: both segments in reverse byte order (left extension)
 SPEC_WHOLE = 0xFFFFFFFF     # as ref_len / read_len: from the start given to the end of the source
@@ -85,6 +87,8 @@ SYMBOLS = [
     ("swmi_pair_alignment", C.c_int, [_P, C.c_uint64, C.c_uint64, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                       C.POINTER(C.c_int32), C.POINTER(C.c_char_p), C.POINTER(C.c_char_p),
                                       C.POINTER(C.c_uint32)]),
+    ("swmi_pair_cigar", C.c_int, [_P, C.c_uint64, C.c_uint64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                  C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     ("swmi_pair_rows_swept", C.c_int, [_P, C.c_uint64, C.POINTER(C.c_uint32)]),
     ("swmi_pair_band_window", C.c_int, [_P, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     ("swmi_batch_pair_results", C.c_int, [_P, C.POINTER(C.c_int32), _u64p, C.c_uint64]),

@@ -7,6 +7,12 @@ from ._capi import Params, Timing, StreamStats, PairSpec, SwmiError, check
 
 DEFAULT_SCORES = (5, -3, -4)              # Distribution.java:36  {match, mismatch, gap}
 DEFAULT_TYPES = ("a", "i", "d", "-")      # Distribution.java:37
+CIGAR_M, CIGAR_I, CIGAR_D, CIGAR_EQ, CIGAR_X = _capi.CIGAR_M, _capi.CIGAR_I, _capi.CIGAR_D, _capi.CIGAR_EQ, _capi.CIGAR_X
+
+
+def cigar_string(entries):
+    """[(len, op_char), ...] as Batch.cigar returns them -> SAM's text, e.g. "12=1X3I40=" ("" for no entries; SAM writes "*")"""
+    return "".join("%d%s" % (int(n), op) for n, op in entries)
 
 
 def make_params(align_scores=None, align_types=None, tie_mode=_capi.TIE_SERIAL):
@@ -232,6 +238,20 @@ class Batch:
     def alignments(self, pair, with_cell=False):
         n, _ = self.n_alignments(pair)
         return [self.alignment(pair, k, with_cell) for k in range(n)]
+
+    def cigar(self, pair, k):
+        """(begin, end_i, end_j, [(len, op_char), ...], nm) of the k-th alignment after a run under option "cigar" (1: M / I / D,
+        2: = / X / I / D): entries from the start of the alignment to its end cell, nm = X columns + inserted + deleted bases.
+        SwmiError (SWMI_ERR_UNSUPPORTED) after a run with cigar = 0 or scores_only = 1."""
+        b, ei, ej = C.c_int32(), C.c_int32(), C.c_int32()
+        p, n, nm = C.POINTER(C.c_uint32)(), C.c_uint32(), C.c_uint32()
+        check(self._lib.swmi_pair_cigar(self._h, pair, k, C.byref(b), C.byref(ei), C.byref(ej), C.byref(p), C.byref(n), C.byref(nm)))
+        ent = [(p[x] >> 4, _capi.CIGAR_CHARS.get(p[x] & 15, "?")) for x in range(n.value)]
+        return b.value, ei.value, ej.value, ent, nm.value
+
+    def cigars(self, pair):
+        n, _ = self.n_alignments(pair)
+        return [self.cigar(pair, k) for k in range(n)]
 
     def pair_results(self):
         """(scores int32[n_pairs], n_alignments uint64[n_pairs]) as numpy arrays, one native call."""

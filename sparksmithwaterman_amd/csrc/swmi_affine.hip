@@ -811,7 +811,8 @@ AFF_SWEEP2_KERNEL(sw_affine_sweep2_band_extend_kernel, SWMI_AFF_RMAX, SWMI_AFF_R
 #define AFF_DEL2 5u
 namespace {
 template <int MODE, bool LONG, bool BAND = false, bool ADAPT = false, bool TWO = false>
-__device__ __forceinline__ void aff_traceback(const TraceArgs A, const uint32_t tile_words, const uint32_t ops_words, const uint32_t wb = 0u) {
+__device__ __forceinline__ void aff_traceback(const TraceArgs A, const uint32_t tile_words, const uint32_t ops_words, const uint32_t cigar,
+                                              const uint32_t wb = 0u) {
     static_assert(!ADAPT || (LONG && BAND && MODE == AFF_GLOBAL), "band_adapt: the banded walk of an extend run (global mode's)");
     static_assert(!TWO || (MODE == AFF_GLOBAL && !ADAPT), "two-piece gaps: the global walk");
     constexpr uint32_t PL = TWO ? 2u : 1u;                        // planes of the field
@@ -963,14 +964,19 @@ __device__ __forceinline__ void aff_traceback(const TraceArgs A, const uint32_t 
         }
         if ((n_ops & 15u) != 0u && lane == 0) ops[n_ops >> 4] = cur;
         WAVE_SYNC();
+        // the payload: both strings, the packed ops or -- option "cigar", wave-uniform -- the CIGAR, sized by a pass of its own (swmi_emit.h)
         const bool strings = A.raw != nullptr;
-        const uint32_t words = swmi_payload_words(n_ops, strings);
+        SwmiCigar<SwmiOpsPacked> cg(SwmiOpsPacked{ops}, n_ops, ci, cj, reinterpret_cast<const uint8_t *>(A.seqw + rd.boff),
+                                    reinterpret_cast<const uint8_t *>(A.seqw + qd.boff), cigar, lane);
+        if (cigar && ok) cg.count();
+        const uint32_t words = cigar ? cg.words() : swmi_payload_words(n_ops, strings);
         unsigned long long off;
         uint32_t rslot;
         if (ok && swmi_reserve(A, lane, words, 1u, off, rslot)) {
             uint32_t *dst = A.arena + off;
             if (lane == 0) swmi_write_rec(A, rslot, pd.out_id, SWMI_RANK_BY_CELL, begin, ci, cj, n_ops, off);
-            if (strings) swmi_emit_strings(dst, SwmiOpsPacked{ops}, n_ops, ci, cj, raw_ref, raw_read, lane, scratch);
+            if (cigar) swmi_emit_cigar(dst, cg);
+            else if (strings) swmi_emit_strings(dst, SwmiOpsPacked{ops}, n_ops, ci, cj, raw_ref, raw_read, lane, scratch);
             else for (uint32_t x = lane; x < words; x += WAVE) dst[x] = ops[x];
         } else if (lane == 0) {
             atomicOr(&A.out[pd.out_id].flags, SWMI_F_ARENA_OVF);
@@ -984,10 +990,11 @@ __device__ __forceinline__ void aff_traceback(const TraceArgs A, const uint32_t 
 #undef AFF_INS2
 #undef AFF_DEL2
 
-#define AFF_TB_PARAMS_0 const TraceArgs A, const uint32_t tile_words, const uint32_t ops_words
-#define AFF_TB_PARAMS_1 const TraceArgs A, const uint32_t tile_words, const uint32_t ops_words, const uint32_t band
-#define AFF_TB_ARGS_0 A, tile_words, ops_words
-#define AFF_TB_ARGS_1 A, tile_words, ops_words, band
+// cigar: the payload kind (0: strings or packed ops, as TraceArgs.raw says; 1, 2: option "cigar") -- a runtime value, one kernel for all
+#define AFF_TB_PARAMS_0 const TraceArgs A, const uint32_t tile_words, const uint32_t ops_words, const uint32_t cigar
+#define AFF_TB_PARAMS_1 AFF_TB_PARAMS_0, const uint32_t band
+#define AFF_TB_ARGS_0 A, tile_words, ops_words, cigar
+#define AFF_TB_ARGS_1 A, tile_words, ops_words, cigar, band
 #define AFF_TRACEBACK_KERNEL(name, MODE, LONG, BAND, ADAPT, TWO)                                            \
     extern "C" __global__ void __launch_bounds__(WAVE) name(AFF_TB_PARAMS_##BAND) {                        \
         aff_traceback<MODE, LONG, BAND != 0, ADAPT != 0, TWO != 0>(AFF_TB_ARGS_##BAND);                    \
@@ -1092,12 +1099,12 @@ extern "C" hipError_t swmi_launch_affine_traceback(const TraceArgs *a, const Aff
     // makes no use of its being (m, n)
     const uint32_t mode = r->mode == AFF_EXTEND ? AFF_GLOBAL : r->mode;
     // [long_reads][mode], then the two-piece walks [long_reads] (global mode's)
-    static void (*const kern[8])(TraceArgs, uint32_t, uint32_t) = {
+    static void (*const kern[8])(TraceArgs, uint32_t, uint32_t, uint32_t) = {
         sw_affine_traceback_kernel, sw_affine_traceback_fit_kernel, sw_affine_traceback_global_kernel,
         sw_affine_traceback_long_kernel, sw_affine_traceback_long_fit_kernel, sw_affine_traceback_long_global_kernel,
         sw_affine_traceback2_global_kernel, sw_affine_traceback2_long_global_kernel};
     // the banded long walks, which take the half-width: [mode], then option "band_adapt"'s and the two-piece one (global mode's)
-    static void (*const bkern[5])(TraceArgs, uint32_t, uint32_t, uint32_t) = {
+    static void (*const bkern[5])(TraceArgs, uint32_t, uint32_t, uint32_t, uint32_t) = {
         sw_affine_traceback_band_kernel, sw_affine_traceback_band_fit_kernel, sw_affine_traceback_band_global_kernel,
         sw_affine_traceback_band_adapt_global_kernel, sw_affine_traceback2_band_global_kernel};
     static const bool attrs = [] {
@@ -1109,7 +1116,7 @@ extern "C" hipError_t swmi_launch_affine_traceback(const TraceArgs *a, const Aff
     const size_t lds = ((size_t)tile_words + ops_words + SWMI_EMIT_SCRATCH_WORDS) * sizeof(uint32_t);
     // (band...: the half-width, for the kernels that take it)
     const auto launch = [&](auto *k, auto... band) {
-        hipLaunchKernelGGL(k, dim3(a->n_pairs, SWMI_AFF_TB_SLOTS), dim3(WAVE), lds, st, *a, tile_words, ops_words, band...);
+        hipLaunchKernelGGL(k, dim3(a->n_pairs, SWMI_AFF_TB_SLOTS), dim3(WAVE), lds, st, *a, tile_words, ops_words, r->cigar, band...);
     };
     const uint32_t lng = long_reads ? 1u : 0u;
     if (long_reads && r->band) launch(bkern[two ? 4u : r->adapt ? 3u : mode], r->band);

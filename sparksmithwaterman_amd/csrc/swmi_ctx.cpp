@@ -194,6 +194,9 @@ extern "C" int swmi_set_option(swmi_ctx *ctx, const char *name, int64_t value) {
         if (value > 0) return fail(SWMI_ERR_INVALID, "gap2 must be <= 0 (the second piece's per-base extension), got %lld", (long long)value);
         if (value < INT32_MIN) return fail(SWMI_ERR_INVALID, "gap2 out of range");
         ctx->modes.gap2 = (int)value;
+    } else if (!strcmp(name, "cigar")) {
+        if (value < 0 || value > 2) return fail(SWMI_ERR_INVALID, "cigar must be 0 (off), 1 (M/I/D) or 2 (=/X/I/D), got %lld", (long long)value);
+        ctx->modes.cigar = (int)value;
     } else if (!strcmp(name, "arena_words_per_pair")) {
         if (value < 1) return fail(SWMI_ERR_INVALID, "arena_words_per_pair out of range");
         ctx->arena_words_per_pair = (uint64_t)value;

@@ -137,3 +137,99 @@ __device__ __forceinline__ void swmi_emit_strings(uint32_t *__restrict__ dst, co
     SwmiStrings<OPS> S(ops, n_ops, end_i, end_j, raw_ref, raw_read, lane, scratch);
     S.store_from(dst, S.n_chunks());
 }
+
+// ------------------------------------------------------------------------------------------------
+// CIGAR payload (option "cigar", include/swmi.h): dword 0 = n_cigar, dword 1 = nm, then n_cigar entries len << 4 | op (BAM's),
+// from the START of the alignment to its end cell -- the order of the strings, the reverse of the walk.  Ops: SWMI_CIGAR_*.
+// len < 2^28: an alignment has at most 587,760 columns (the path bound of the LDS staging area).
+//
+// The size depends on the data, so the wavefront goes over the ops twice: count() before the record is reserved, store() after.
+// Both take 64 ops per iteration, t ascending from the end cell (lane l: op 64 it + l), and classify them the same way: the cell
+// of op t from the ballot + mbcnt prefix counts (as SwmiStrings::chunk), an alignment op by comparing the two CANONICAL codes of
+// the byte images in seqw -- equal codes are equal upper-cased bytes, whatever the scores say.  A run starts where the class of
+// op t differs from that of op t - 1 (lane 0: from the last op of the iteration before).  store() keeps the open run as
+// wave-uniform values across iterations: the first boundary lane of an iteration closes it, every boundary lane with a later
+// boundary in the same ballot closes its own, the last one becomes the open run; lane 0 closes that at n_ops.  Run r of the walk
+// goes to entry n_cigar - 1 - r.  Nothing is read back from dst (it may be pinned host memory).
+#define SWMI_CIGAR_OP_M  0u
+#define SWMI_CIGAR_OP_I  1u
+#define SWMI_CIGAR_OP_D  2u
+#define SWMI_CIGAR_OP_EQ 7u
+#define SWMI_CIGAR_OP_X  8u
+SWMI_HD static inline uint32_t swmi_cigar_words(uint32_t n_cigar) { return 2u + n_cigar; }
+
+template <class OPS>
+struct SwmiCigar {
+    OPS ops;
+    uint32_t n_ops, end_i, end_j, lane, kind;                    // kind 1: M / I / D; 2: = / X / I / D
+    const uint8_t *__restrict__ code_ref, *__restrict__ code_read;
+    uint32_t n_cigar = 0u, nm = 0u;                              // after count()
+    uint32_t i, j, prev;                                          // the scan: cell of the iteration's first op, class of the op before it
+    __device__ __forceinline__ SwmiCigar(const OPS o, uint32_t n, uint32_t ei, uint32_t ej, const uint8_t *cr, const uint8_t *cq,
+                                         uint32_t k, uint32_t l)
+        : ops(o), n_ops(n), end_i(ei), end_j(ej), lane(l), kind(k), code_ref(cr), code_read(cq) {}
+    __device__ __forceinline__ void rewind() { i = end_i; j = end_j; prev = 0xFFFFFFFFu; }
+    // the class of op 64 it + lane (0xFFFFFFFF behind the end), the ballot of the lanes where a run starts, and the iteration's
+    // share of nm; must be called for it = 0, 1, ... after rewind()
+    __device__ __forceinline__ uint32_t scan(const uint32_t it, uint64_t &bm, uint32_t &mism) {
+        const uint32_t t = 64u * it + lane;
+        const bool valid = t < n_ops;
+        const uint32_t op = valid ? ops(t) : 3u;
+        const bool ur = valid && op != SWMI_DIR_I, uq = valid && op != SWMI_DIR_D;
+        const uint64_t mr = __builtin_amdgcn_ballot_w64(ur), mq = __builtin_amdgcn_ballot_w64(uq);
+        const uint32_t jj = j - __builtin_amdgcn_mbcnt_hi((uint32_t)(mr >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mr, 0u));
+        const uint32_t ii = i - __builtin_amdgcn_mbcnt_hi((uint32_t)(mq >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mq, 0u));
+        bool eq = false;
+        if (ur && uq) eq = code_ref[jj - 1u] == code_read[ii - 1u];      // (an alignment op sits on a cell with i, j >= 1)
+        uint32_t cls = 0xFFFFFFFFu;
+        if (valid) cls = op == SWMI_DIR_I ? SWMI_CIGAR_OP_I : op == SWMI_DIR_D ? SWMI_CIGAR_OP_D
+                       : kind == 1u ? SWMI_CIGAR_OP_M : eq ? SWMI_CIGAR_OP_EQ : SWMI_CIGAR_OP_X;
+        mism = (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(valid && !eq));
+        uint32_t before = (uint32_t)__shfl_up((int)cls, 1);
+        if (lane == 0u) before = prev;
+        bm = __builtin_amdgcn_ballot_w64(valid && cls != before);
+        prev = (uint32_t)__builtin_amdgcn_readlane((int)cls, 63);
+        j -= (uint32_t)__builtin_popcountll(mr);
+        i -= (uint32_t)__builtin_popcountll(mq);
+        return cls;
+    }
+    __device__ __forceinline__ void count() {
+        rewind();
+        n_cigar = 0u; nm = 0u;
+        for (uint32_t it = 0; 64u * it < n_ops; ++it) {
+            uint64_t bm; uint32_t mism;
+            (void)scan(it, bm, mism);
+            n_cigar += (uint32_t)__builtin_popcountll(bm);
+            nm += mism;
+        }
+    }
+    __device__ __forceinline__ uint32_t words() const { return swmi_cigar_words(n_cigar); }
+    __device__ __forceinline__ void store(uint32_t *__restrict__ dst) {
+        if (lane == 0u) { dst[0] = n_cigar; dst[1] = nm; }
+        uint32_t *__restrict__ ent = dst + 2u;
+        rewind();
+        uint32_t open_t = 0u, open_op = 0u, runs = 0u;           // the open run is run `runs - 1` of the walk (none while runs == 0)
+        for (uint32_t it = 0; 64u * it < n_ops; ++it) {
+            uint64_t bm; uint32_t mism;
+            const uint32_t cls = scan(it, bm, mism);
+            if (bm == 0ull) continue;
+            const uint32_t first = (uint32_t)__builtin_ctzll(bm), last = 63u - (uint32_t)__builtin_clzll(bm);
+            const uint32_t t = 64u * it + lane;
+            if (lane == first && runs != 0u && runs <= n_cigar) ent[n_cigar - runs] = ((t - open_t) << 4) | open_op;
+            const uint64_t later = lane < 63u ? bm >> (lane + 1u) : 0ull;
+            if (((bm >> lane) & 1ull) && later != 0ull) {
+                const uint32_t r = runs + (uint32_t)__builtin_popcountll(bm & ((1ull << lane) - 1ull));
+                const uint32_t len = 1u + (uint32_t)__builtin_ctzll(later);
+                if (r < n_cigar) ent[n_cigar - 1u - r] = (len << 4) | cls;
+            }
+            open_t = 64u * it + last;
+            open_op = (uint32_t)__builtin_amdgcn_readlane((int)cls, (int)last);
+            runs += (uint32_t)__builtin_popcountll(bm);
+        }
+        if (lane == 0u && runs != 0u && runs <= n_cigar) ent[n_cigar - runs] = ((n_ops - open_t) << 4) | open_op;
+    }
+};
+
+// the CIGAR payload of one alignment at dst, words() dwords, after C.count() sized it
+template <class OPS>
+__device__ __forceinline__ void swmi_emit_cigar(uint32_t *__restrict__ dst, SwmiCigar<OPS> &C) { C.store(dst); }

@@ -122,6 +122,7 @@ struct __attribute__((visibility("hidden"))) RunModes {
     int band_adapt = 0;                     // 1: the band of an extend run follows the alignment, strip by strip (swmi.h); refused in other runs
     int gap_open2 = 0;                      // != 0: two-piece gaps on a global or extend run -- the second piece's open (swmi.h); refused in other runs
     int gap2 = 0;                           // ... and its per-base extension (not read while gap_open2 == 0)
+    int cigar = 0;                          // 1 / 2: the records' payload is a CIGAR, M/I/D or =/X/I/D (swmi.h); the affine kernels
     bool two_piece() const { return gap_open2 != 0; }
     // the MODE of the affine kernels and their launchers: the align_mode, or 3 (extend) for a global run with option "extend"
     uint32_t kernel_mode() const { return extend && align_mode == SWMI_ALIGN_GLOBAL ? 3u : (uint32_t)align_mode; }
@@ -198,7 +199,7 @@ struct swmi_ctx {
     bool cell_cap_set = false;              // cell_cap given by the caller (otherwise small launches get longer lists)
     int32_t gap_open = 0;                   // affine gaps: a gap of length k costs gap_open + k * gap (0: linear)
     int affine = -1;                        // -1: the affine kernels (mode 3) when gap_open != 0; 1: always
-    RunModes modes;                         // options "align_mode", "long_reads", "band", "extend", "xdrop", "band_adapt", "gap_open2" and "gap2"
+    RunModes modes;                         // options "align_mode", "long_reads", "band", "extend", "xdrop", "band_adapt", "gap_open2", "gap2" and "cigar"
     std::mutex mat_mu;                      // guards `matrix` (not ctx->mu: setting a matrix does not wait for a run)
     std::shared_ptr<const ScoreMatrix> matrix;   // swmi_set_score_matrix; a run with one takes the affine kernels
     // swmi_batch_run_async: one run in flight on the context's own host thread
@@ -225,7 +226,7 @@ struct HostAln {
     uint32_t rank;
     int32_t begin, end_i, end_j;
     uint32_t n_ops;
-    const uint32_t *rec = nullptr;   // the alignment's payload in the arena: the two strings written by the kernels, or the packed ops
+    const uint32_t *rec = nullptr;   // the alignment's payload in the arena: the two strings written by the kernels, the packed ops, or the CIGAR
     int64_t str_id = -1;    // records without strings: >= 0 once the strings are built, offset of the reference-side string in swmi_batch::str_buf
 };
 
@@ -359,6 +360,7 @@ struct swmi_batch {
     std::vector<RawChunk> raw_chunks;
     bool indexed = false;
     bool rec_strings = false;               // the records of the last run carry both aligned strings (option device_strings)
+    int rec_cigar = 0;                      // != 0: they carry a CIGAR instead (option cigar, its value): {n_cigar, nm, entries} (swmi_emit.h)
     bool scores_only = false;               // the last run computed scores only (option scores_only): no counts, no alignments
     bool records_dropped = false;           // a streamed chunk whose records were not kept (option stream_keep_records = 0)
     std::vector<HostAln> alns;              // grouped by pair, ordered as OptAlignments returns them
@@ -398,4 +400,13 @@ static inline size_t result_arena_off(size_t np, uint64_t tab_cap) { return (res
 // dwords of one alignment's payload: the two strings, n_ops / 4 + 1 dwords each, or the ops packed 16 per dword (swmi_emit.h)
 static inline uint64_t rec_words(uint32_t n_ops, bool strings) {
     return strings ? 2 * ((uint64_t)n_ops / 4 + 1) : ((uint64_t)n_ops + 15) / 16;
+}
+// ... of a record of the batch's last run, at dword `off` of an arena of `words` dwords.  A CIGAR record is sized from its own first
+// dword, read only when it lies inside the arena; false: the payload does not fit the arena
+static inline bool payload_end(const swmi_batch *b, const AlnRec &e, const uint32_t *arena, uint64_t words, uint64_t &end) {
+    const uint64_t off = ((uint64_t)e.off_hi << 32) | e.off_lo;
+    if (!b->rec_cigar) { end = off + rec_words(e.n_ops, b->rec_strings); return end <= words; }
+    if (off + 2 > words || off + 2 < off) return false;
+    end = off + 2 + arena[off];
+    return end <= words;
 }

@@ -29,12 +29,13 @@ struct AffRun {
     uint32_t adapt;              // option "band_adapt" (0 / 1) -- the banded strip kernels whose windows follow the alignment
     const uint32_t *mat;         // the device image of the score matrix (swmi_aff_mat_words dwords), or null: the plain sweeps
     uint32_t nn;                 // ... and its side n + 1 (2 .. SWMI_MAT_NN_MAX)
+    uint32_t cigar;              // option "cigar" (0: off; 1: M/I/D, 2: =/X/I/D) -- the payload the walks write (swmi_emit.h); the sweeps do not read it
 };
 // What the launchers refuse (hipErrorInvalidValue): the combinations no kernel exists for.  band, xdrop and adapt are options of
 // the long shape (long_reads: every pair of the launch has a read longer than SWMI_AFF_MAX_READ); the short shape ignores them.
 // Every run check_run_params (swmi_run.cpp) admits passes.
 static inline bool aff_run_ok(const AffRun &r, uint32_t long_reads) {
-    if (r.mode > 3u || r.band > SWMI_AFF_BAND_MAX || r.xdrop > 0x7FFFFFFFu || r.adapt > 1u) return false;
+    if (r.mode > 3u || r.band > SWMI_AFF_BAND_MAX || r.xdrop > 0x7FFFFFFFu || r.adapt > 1u || r.cigar > 2u) return false;
     if (r.mat && (r.nn < 2u || r.nn > SWMI_MAT_NN_MAX)) return false;
     if (r.gap_open2 && (r.mode < 2u || r.mat || r.xdrop || r.adapt)) return false;      // two-piece: plain global and extend runs
     if (long_reads && r.xdrop && r.mode != 3u) return false;                            // xdrop: extend runs

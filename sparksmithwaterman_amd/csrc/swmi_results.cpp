@@ -12,9 +12,11 @@ int swmi_host::settle_raw(swmi_batch *b) {
     const AlnRec *tab = b->rtab_ext;
     b->raw_ext = nullptr; b->rtab_ext = nullptr;
     uint64_t used = 0;
-    for (uint64_t k = 0; k < b->raw_ext_records; k++)
-        used = std::max(used, (((uint64_t)tab[k].off_hi << 32) | tab[k].off_lo) + rec_words(tab[k].n_ops, b->rec_strings));
-    if (used > b->raw_ext_cap) return fail(SWMI_ERR_HIP, "record payloads overrun the arena");
+    for (uint64_t k = 0; k < b->raw_ext_records; k++) {
+        uint64_t end;
+        if (!payload_end(b, tab[k], aw, b->raw_ext_cap, end)) return fail(SWMI_ERR_HIP, "record payloads overrun the arena");
+        used = std::max(used, end);
+    }
     b->raw.assign(aw, aw + used);
     b->rtab.assign(tab, tab + b->raw_ext_records);
     if (b->raw_chunks.size() == 1) { b->raw_chunks[0].at = 0; b->raw_chunks[0].words = (size_t)used; b->raw_chunks[0].tab_at = 0; }
@@ -62,7 +64,8 @@ static int ensure_indexed(swmi_batch *b) {
             const uint64_t wp = wpos_of(sr, e.out_id);
             PairRes &pr = b->pairs[work[wp].pair];
             const uint64_t off = ((uint64_t)e.off_hi << 32) | e.off_lo;
-            if (off + rec_words(e.n_ops, b->rec_strings) > sr.words) return fail(SWMI_ERR_HIP, "record payload overruns the arena");
+            uint64_t end;
+            if (!payload_end(b, e, sr.arena, sr.words, end)) return fail(SWMI_ERR_HIP, "record payload overruns the arena");
             HostAln a;
             a.rank = e.rank; a.begin = e.begin; a.end_i = e.end_i; a.end_j = e.end_j; a.n_ops = e.n_ops;
             a.rec = sr.arena + off;
@@ -221,6 +224,27 @@ static void materialise(swmi_batch *b, uint64_t pair, HostAln &a, uint64_t slot)
     char *sr = b->str_buf.data() + b->str_at[slot], *sq = sr + a.n_ops + 1;
     sr[a.n_ops] = 0; sq[a.n_ops] = 0;
     int64_t i = a.end_i, j = a.end_j;     // 1-based cell of the op being emitted (both >= 1 while ops remain)
+    if (b->rec_cigar) {
+        // option "cigar": the payload is {n_cigar, nm, entries from the alignment's start}; the strings are filled from their end,
+        // entry by entry backwards -- the walk's order.  An entry that would leave the strings or a sequence ends the expansion
+        // (a corrupted record: the strings stay NUL-terminated)
+        const uint32_t nc = a.rec[0];
+        int64_t pos = (int64_t)a.n_ops - 1;
+        for (uint32_t e = nc; e-- > 0;) {
+            const uint32_t op = a.rec[2 + e] & 15u;
+            const int64_t len = a.rec[2 + e] >> 4;
+            const bool use_ref = op != SWMI_CIGAR_I, use_read = op != SWMI_CIGAR_D;
+            if (len > pos + 1 || (use_ref && len > j) || (use_read && len > i)) break;
+            for (int64_t x = 0; x < len; x++, pos--) {
+                sr[pos] = use_ref ? (char)ref[j - 1 - x] : '_';
+                sq[pos] = use_read ? (char)read[i - 1 - x] : '_';
+            }
+            if (use_ref) j -= len;
+            if (use_read) i -= len;
+        }
+        a.str_id = (int64_t)b->str_at[slot];
+        return;
+    }
     const uint32_t *ops = a.rec;
     // Four ops (one byte of the packed stream) at a time: a table gives, for each of the 256 byte values, how far behind the
     // current cell every op reads its reference / read base (or that it writes '_'), so the four characters of each string do
@@ -301,6 +325,39 @@ extern "C" int swmi_pair_alignment(swmi_batch *b, uint64_t pair, uint64_t k,
     if (a.str_id < 0) materialise(b, pair, a, pr.first + k);
     if (ref_aln) *ref_aln = b->str_buf.data() + a.str_id;
     if (read_aln) *read_aln = b->str_buf.data() + a.str_id + a.n_ops + 1;
+    return SWMI_OK;
+}
+
+// Option "cigar": the alignment as the traceback kernel wrote it -- a pointer into the record stream, nothing is built.
+extern "C" int swmi_pair_cigar(swmi_batch *b, uint64_t pair, uint64_t k,
+                               int32_t *begin, int32_t *end_i, int32_t *end_j,
+                               const uint32_t **cigar, uint32_t *n_cigar, uint32_t *nm) {
+    int rc = check_pair(b, pair);
+    if (rc) return rc;
+    if (b->scores_only)
+        return fail(SWMI_ERR_UNSUPPORTED, "the batch was run with scores_only = 1: scores and totals only, no CIGARs");
+    if (!b->rec_cigar)
+        return fail(SWMI_ERR_UNSUPPORTED, "the batch was run with cigar = 0: set option cigar to 1 or 2 before the run");
+    if ((rc = ensure_indexed(b))) return rc;
+    PairRes &pr = b->pairs[pair];
+    if (k >= pr.n_cells) return fail(SWMI_ERR_RANGE, "alignment %llu out of range", (unsigned long long)k);
+    if (pr.flags & SWMI_PAIR_DEGENERATE) {
+        const uint32_t n = b->ref_desc[pair_ref(b, pair)].len;
+        if (begin) *begin = 0;
+        if (end_i) *end_i = (int32_t)(k / n) + 1;
+        if (end_j) *end_j = (int32_t)(k % n) + 1;
+        if (cigar) *cigar = nullptr;
+        if (n_cigar) *n_cigar = 0;
+        if (nm) *nm = 0;
+        return SWMI_OK;
+    }
+    const HostAln &a = b->alns[pr.first + k];
+    if (begin) *begin = a.begin;
+    if (end_i) *end_i = a.end_i;
+    if (end_j) *end_j = a.end_j;
+    if (cigar) *cigar = a.rec + 2;
+    if (n_cigar) *n_cigar = a.rec[0];
+    if (nm) *nm = a.rec[1];
     return SWMI_OK;
 }
 

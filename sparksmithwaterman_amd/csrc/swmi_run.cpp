@@ -29,10 +29,10 @@ static int keep_chunk_records(RunState &rs, const AlnRec *tab, uint64_t n_rec, c
     }
     uint64_t used = 0;
     for (uint64_t k = 0; k < n_rec; k++) {
-        const uint64_t end = (((uint64_t)tab[k].off_hi << 32) | tab[k].off_lo) + rec_words(tab[k].n_ops, b->rec_strings);
+        uint64_t end;
+        if (!payload_end(b, tab[k], arena, arena_cap, end)) return fail(SWMI_ERR_HIP, "record payloads overrun the arena");
         used = std::max(used, end);
     }
-    if (used > arena_cap) return fail(SWMI_ERR_HIP, "record payloads overrun the arena");
     b->raw_chunks.push_back(swmi_batch::RawChunk{b->raw.size(), (size_t)used, b->rtab.size(), (size_t)n_rec, lo, {}});
     b->raw.insert(b->raw.end(), arena, arena + used);
     b->rtab.insert(b->rtab.end(), tab, tab + n_rec);
@@ -172,11 +172,14 @@ static int build_trace_args(RunState &rs, Launch &L) {
     ta.ovf_host = (uint32_t *)ctx->h_err.dp + 4;
     ((volatile uint32_t *)ctx->h_err.p)[4] = 0u; ((volatile uint32_t *)ctx->h_err.p)[5] = 0u;
     ta.win_off = nullptr; ta.q_count = nullptr; ta.q_items = nullptr; ta.q_cap = 0; ta.pad4 = 0;
-    const bool strings = ctx->device_strings != 0 && b->d_raw.p != nullptr;
+    // (option "cigar": the payload is the CIGAR -- device_strings is not read and the walks get no raw bytes)
+    const int cigar = b->eff_mode == 3 ? b->opt.modes.cigar : 0;
+    const bool strings = !cigar && ctx->device_strings != 0 && b->d_raw.p != nullptr;
     ta.raw = strings ? b->d_raw.as<uint8_t>() : nullptr;
     ta.raw_off = strings ? b->d_raw_off.as<uint64_t>() : nullptr;
     ta.raw_reads_at = b->n_refs + 1u;
     b->rec_strings = strings;
+    b->rec_cigar = cigar;
     if (L.zc) {
         // results land in pinned host memory while the kernel runs: [overflow word .. | PairOut x np | arena]
         if ((rc = b->h_result.reserve(L.a_off + L.arena_cap * 4))) return rc;
@@ -249,6 +252,7 @@ static inline AffRun aff_run(const swmi_batch *b) {
     r.band = (uint32_t)md.band; r.xdrop = (uint32_t)md.xdrop; r.adapt = (uint32_t)md.band_adapt;
     r.mat = b->opt.mat ? b->d_mat.as<uint32_t>() : nullptr;
     r.nn = b->opt.mat ? b->opt.mat->n + 1u : 0u;
+    r.cigar = (uint32_t)md.cigar;
     return r;
 }
 
@@ -874,8 +878,9 @@ static int batch_run(swmi_ctx *ctx, swmi_batch *b, const swmi_params *p, RunOpti
     if (!ctx || !b || !p) return fail(SWMI_ERR_INVALID, "null argument");
     std::lock_guard<std::mutex> g(ctx->mu);
     // (a score matrix and the end-to-end modes run on the affine kernels only)
-    // (... and so does a band)
-    const bool affine = ctx->affine == 1 || ctx->gap_open != 0 || opt.mat != nullptr || opt.modes.align_mode != SWMI_ALIGN_LOCAL || opt.modes.band > 0;
+    // (... and so do a band and a CIGAR payload)
+    const bool affine = ctx->affine == 1 || ctx->gap_open != 0 || opt.mat != nullptr || opt.modes.align_mode != SWMI_ALIGN_LOCAL || opt.modes.band > 0 ||
+                        opt.modes.cigar != 0;
     int rc;
     if ((rc = check_run_params(ctx, b, p, affine, opt))) return rc;
     static const bool host_dbg = getenv("SWMI_DEBUG_HOST") != nullptr;

@@ -106,6 +106,7 @@ static int stream_process(swmi_stream *s, swmi_stream::Slot &sl, StreamChunk *c)
         b->raw_ext = nullptr; b->rtab_ext = nullptr;
     }
     r->rec_strings = b->rec_strings;
+    r->rec_cigar = b->rec_cigar;              // (option "cigar" reaches the slots with the modes, below)
     r->scores_only = b->scores_only;
     r->indexed = false;
     r->ref_view_ready.assign(n_refs, 0);
