@@ -55,6 +55,10 @@ public class GpuSmithWaterman
 	static native int[] nativePairCigar( long batch , long pair , long k , int[] info ) ;
 	/** the edit distance (SAM's NM) of alignment k: X columns + inserted + deleted bases */
 	static native int nativePairNm( long batch , long pair , long k ) ;
+	/** the second-best score: the mask half-width in columns, -1 per pair, 0 off (include/swmi.h: option "subopt") */
+	static native void nativeSetSubopt( long ctx , int subopt ) ;
+	/** { second-best score , the reference column it ends in } of a pair after a run under that option */
+	static native int[] nativePairSubopt( long batch , long pair ) ;
 	/** substitution scores on the context: alphabet = n ISO-8859-1 symbols, scores = n * n, row = read base; null clears */
 	static native void nativeSetScoreMatrix( long ctx , byte[] alphabet , int[] scores ) ;
 	/** a pair list over the sequences: specs = eight ints per pair ( alignPairs ) */
@@ -176,6 +180,25 @@ public class GpuSmithWaterman
 	/** ... and its edit distance */
 	static int nm( long batch , long pair , long k ) { return nativePairNm( batch , pair , k ) ; }
 
+	/** the mask half-width of the second-best score every context asks its runs for, 0: none (applied next to cigar, before every batch) */
+	private static volatile int SUBOPT = 0 ;
+	public static final int SUBOPT_AUTO = -1 ;
+
+	/**
+	 * w in 1 .. 2^30: a local run also computes every pair's second-best score, the best score of an alignment that ends more than
+	 * w columns away from every column where the best one ends; SUBOPT_AUTO: w = max( m / 2 , 15 ) per pair, m the read's length;
+	 * 0 (the default): off.  Such a run takes the affine kernels and ALIGN_LOCAL.  For every batch aligned from now on, on every
+	 * executor thread.
+	 */
+	public static void setSubopt( int w )
+	{
+		if( w < -1 || w > ( 1 << 30 ) ) throw new IllegalArgumentException( "subopt must be 0, -1 or 1 .. 2^30: " + w ) ;
+		SUBOPT = w ;
+	}
+
+	/** { second-best score , the reference column it ends in } of a pair of a native batch run under setSubopt ( { 0 , 0 }: none ) */
+	static int[] subopt( long batch , long pair ) { return nativePairSubopt( batch , pair ) ; }
+
 	/** the score matrix every context applies before its next batch: { alphabet , scores } (null: none), and its version */
 	private static volatile Object[] MATRIX = null ;
 	private static final java.util.concurrent.atomic.AtomicLong MATRIX_VERSION = new java.util.concurrent.atomic.AtomicLong() ;
@@ -282,6 +305,7 @@ public class GpuSmithWaterman
 		nativeSetXdrop( ctx , XDROP ) ;
 		nativeSetBandAdapt( ctx , BAND_ADAPT ? 1 : 0 ) ;
 		nativeSetCigar( ctx , CIGAR ) ;
+		nativeSetSubopt( ctx , SUBOPT ) ;
 		applyScoreMatrix( nc ) ;
 	}
 

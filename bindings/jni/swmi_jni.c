@@ -98,6 +98,31 @@ JNIEXPORT void JNICALL Java_sw_GpuSmithWaterman_nativeSetCigar(JNIEnv *env, jcla
     if (swmi_shim_set_cigar((swmi_ctx *)(intptr_t)ctx, cigar, err, sizeof err) != SWMI_OK) throw_msg(env, err);
 }
 
+/* the second-best score on this context from now on: the mask half-width, -1 automatic, 0 off */
+JNIEXPORT void JNICALL Java_sw_GpuSmithWaterman_nativeSetSubopt(JNIEnv *env, jclass cls, jlong ctx, jint subopt) {
+    char err[640];
+    (void)cls;
+    if (swmi_shim_set_subopt((swmi_ctx *)(intptr_t)ctx, subopt, err, sizeof err) != SWMI_OK) throw_msg(env, err);
+}
+
+/* { second-best score, the reference column it ends in } of a pair after a run under option "subopt" */
+JNIEXPORT jintArray JNICALL Java_sw_GpuSmithWaterman_nativePairSubopt(JNIEnv *env, jclass cls, jlong batch, jlong pair) {
+    char err[640];
+    int32_t out[2] = {0, 0};
+    jint jo[2];
+    jintArray res;
+    (void)cls;
+    if (swmi_shim_pair_subopt((const swmi_batch *)(intptr_t)batch, pair, out, err, sizeof err) != SWMI_OK) {
+        throw_msg(env, err);
+        return NULL;
+    }
+    res = (*env)->NewIntArray(env, 2);
+    if (!res) return NULL;
+    jo[0] = out[0]; jo[1] = out[1];
+    (*env)->SetIntArrayRegion(env, res, 0, 2, jo);
+    return res;
+}
+
 /* two-piece gaps on this context from now on: gapOpen2 != 0 on, 0 off */
 JNIEXPORT void JNICALL Java_sw_GpuSmithWaterman_nativeSetGap2(JNIEnv *env, jclass cls, jlong ctx, jint gap_open2, jint gap2) {
     char err[640];

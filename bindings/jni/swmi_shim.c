@@ -96,6 +96,25 @@ int swmi_shim_set_cigar(swmi_ctx *ctx, int32_t cigar, char *err, size_t err_len)
     return SWMI_OK;
 }
 
+int swmi_shim_set_subopt(swmi_ctx *ctx, int32_t subopt, char *err, size_t err_len) {
+    int rc;
+    if (!ctx) return shim_fail(SWMI_ERR_INVALID, err, err_len, "nativeSetSubopt", "context handle is 0");
+    if ((rc = swmi_set_option(ctx, "subopt", subopt)) != SWMI_OK)
+        return shim_fail(rc, err, err_len, "nativeSetSubopt", swmi_last_error());
+    return SWMI_OK;
+}
+
+int swmi_shim_pair_subopt(const swmi_batch *b, int64_t pair, int32_t out[2], char *err, size_t err_len) {
+    int32_t s2 = 0;
+    uint32_t e2 = 0;
+    int rc;
+    if (pair < 0) return shim_fail(SWMI_ERR_RANGE, err, err_len, "nativePairSubopt", "negative index");
+    rc = swmi_pair_subopt(b, (uint64_t)pair, &s2, &e2);
+    if (rc != SWMI_OK) return shim_fail(rc, err, err_len, "swmi_pair_subopt", swmi_last_error());
+    if (out) { out[0] = s2; out[1] = (int32_t)e2; }      /* (a column is below 2^30) */
+    return SWMI_OK;
+}
+
 int swmi_shim_pair_cigar(swmi_batch *b, int64_t pair, int64_t k, int32_t *begin, int32_t cell[2], const uint32_t **cigar,
                          uint32_t *n_cigar, uint32_t *nm, char *err, size_t err_len) {
     int32_t ei = 0, ej = 0;

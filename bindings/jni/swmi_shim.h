@@ -84,6 +84,14 @@ int swmi_shim_set_cigar(swmi_ctx *ctx, int32_t cigar, char *err, size_t err_len)
 int swmi_shim_pair_cigar(swmi_batch *b, int64_t pair, int64_t k, int32_t *begin, int32_t cell[2], const uint32_t **cigar,
                          uint32_t *n_cigar, uint32_t *nm, char *err, size_t err_len);
 
+/* nativeSetSubopt: from then on a local run also returns every pair's second-best score (swmi_set_option "subopt"): 1 .. 2^30 = the
+ * mask half-width in columns, -1 = max(m / 2, 15) per pair, 0 (the default): off.  Any other value is SWMI_ERR_INVALID and leaves
+ * the context as it was.
+ * nativePairSubopt: out[0..1] = the pair's second-best score and the reference column it ends in after a run under that option, as
+ * swmi_pair_subopt hands them out ((0, 0): none). */
+int swmi_shim_set_subopt(swmi_ctx *ctx, int32_t subopt, char *err, size_t err_len);
+int swmi_shim_pair_subopt(const swmi_batch *b, int64_t pair, int32_t out[2], char *err, size_t err_len);
+
 /* nativeSetScoreMatrix: a substitution score matrix on this context (swmi_set_score_matrix): `alphabet` = n symbols narrowed to
  * bytes (ISO-8859-1), `scores` = n * n entries, row = read base, column = reference base (n_scores must be n * n).  n = 0 clears
  * it.  Applies to the batches the context aligns from then on (on the affine kernels). */

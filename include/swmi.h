@@ -279,6 +279,25 @@ void        swmi_default_params(swmi_params *p);
  *                profiling, every affine option (align_mode, long_reads, band, extend, xdrop, band_adapt, gap_open2 / gap2, a score
  *                matrix), pair lists and streams apply unchanged; the bounds and refusals are those of the affine run it becomes.
  *                A run (async runs and stream slots included) takes the value set when it was asked for.
+ * subopt (default 0 = off and no change; 1 .. 2^30 = the mask half-width w in columns; -1 = SWMI_SUBOPT_AUTO, per pair w =
+ *                max(floor(m / 2), 15), m the read's length -- SSW's maskLen; any other value is SWMI_ERR_INVALID and leaves the context
+ *                as it was): a local run also returns every pair's SECOND-BEST score, the best score of an alignment that ends
+ *                somewhere else in the same reference (BWA's score2 / te2 under KSW_XSUBO, SSW's score2 / ref_end2), read with
+ *                swmi_pair_subopt.  With s the pair's score: colmax(j) = the maximum of H(i, j) over the existing cells of column j,
+ *                1 <= i <= m (under band a cell outside its strip's window does not exist; a column with no existing cell has colmax
+ *                0); j* is a maximum column iff colmax(j*) = s -- exactly the columns of the pair's tied maximum cells, whatever
+ *                cell_cap is; column j is eligible iff |j - j*| > w for EVERY maximum column (strict, as in SSW); score2 = the largest
+ *                colmax over the eligible columns, 0 if there are none; end2 = the smallest eligible column with colmax = score2 if
+ *                score2 > 0, else 0.  So 0 <= score2 < s, or both are 0; a degenerate pair (s = 0) and a pair with an empty side give
+ *                (0, 0).  The values do not depend on the tie mode, on cell_cap, on chunking, or on whether the pair was re-run.
+ *                Scope: align_mode local, with and without a score matrix, both tie modes, reads of every length (long_reads, with
+ *                and without band).  A run with subopt != 0 takes the affine kernels whatever gap_open / affine say (swmi_batch_mode =
+ *                3); with gap_open = 0 it gives the linear pipeline's scores and alignments.  subopt != 0 with align_mode fit or
+ *                global (so also extend, xdrop, band_adapt, gap_open2) is SWMI_ERR_UNSUPPORTED before anything is launched.
+ *                scores_only, cigar, device_strings, zero_copy, cell_cap, max_workspace_bytes, profiling, pair lists and streams apply
+ *                unchanged, and every other accessor returns what the same run with subopt = 0 returns.  The sweep keeps one row of n
+ *                int32 column maxima per pair behind the pair's direction field (charged to max_workspace_bytes with it).  A run
+ *                (async runs and stream slots included) takes the value set when it was asked for.
  * Further knobs: spin_us (how long a run polls its stream before it blocks, default 2000); col_chunks (0 automatic,
  * 1 never, N > 1 force up to N column chunks per pair: a launch of few pairs with long references is swept by several
  * wavefronts per pair -- a read of more than 256 rows by several strip pipelines); debug_strip_spins / debug_reverse_strips (tests of the strip pipeline's give-up path);
@@ -407,6 +426,15 @@ int      swmi_pair_alignment(swmi_batch *b, uint64_t pair, uint64_t k,
 int      swmi_pair_cigar(swmi_batch *b, uint64_t pair, uint64_t k,
                          int32_t *begin, int32_t *end_i, int32_t *end_j,
                          const uint32_t **cigar, uint32_t *n_cigar, uint32_t *nm);
+
+/* Option "subopt": the pair's second-best local score and the (1-based) reference column it ends in, as option "subopt" defines
+ * them; (0, 0) when there is none.  Either pointer may be NULL.  Works under scores_only = 1 and on a stream's chunk batches; on a
+ * pair list end2 is in the segment's coordinates.  A batch whose last run had subopt = 0: SWMI_ERR_UNSUPPORTED; a pair out of
+ * range: SWMI_ERR_RANGE. */
+#define SWMI_SUBOPT_AUTO (-1)
+int      swmi_pair_subopt(const swmi_batch *b, uint64_t pair, int32_t *score2, uint32_t *end2);
+/* all pairs at once: score2[n] and/or end2[n] (either may be NULL), n = swmi_batch_n_pairs */
+int      swmi_batch_pair_subopt(const swmi_batch *b, int32_t *score2, uint32_t *end2, uint64_t n);
 
 /* Builds the record index and both strings of EVERY alignment of the batch in one native call (what a caller that
  * consumes all of OptAlignments' output pays); returns the number of alignments (degenerate pairs count m*n) and

@@ -271,6 +271,24 @@ class Batch:
         check(self._lib.swmi_batch_pair_results(self._h, sc.ctypes.data_as(C.POINTER(C.c_int32)), None, n))
         return sc
 
+    def subopt(self, pair):
+        """(score2, end2) after a run under option "subopt": the pair's second-best local score and the 1-based reference column it
+        ends in (on a pair list: of the segment; PairBatch.to_source maps it), (0, 0) when there is none.  Works after a scores_only
+        run.  SwmiError (SWMI_ERR_UNSUPPORTED) after a run with subopt = 0."""
+        s2, e2 = C.c_int32(), C.c_uint32()
+        check(self._lib.swmi_pair_subopt(self._h, pair, C.byref(s2), C.byref(e2)))
+        return s2.value, e2.value
+
+    def subopts(self):
+        """(scores2 int32[n_pairs], ends2 uint32[n_pairs]) as numpy arrays, one native call."""
+        import numpy as np
+        n = self.n_pairs()
+        s2 = np.empty(n, dtype=np.int32)
+        e2 = np.empty(n, dtype=np.uint32)
+        check(self._lib.swmi_batch_pair_subopt(self._h, s2.ctypes.data_as(C.POINTER(C.c_int32)),
+                                               e2.ctypes.data_as(C.POINTER(C.c_uint32)), n))
+        return s2, e2
+
     def materialise_all(self):
         """Index the records and build every alignment string natively; returns (n_alignments, n_chars)."""
         na, nc = C.c_uint64(), C.c_uint64()

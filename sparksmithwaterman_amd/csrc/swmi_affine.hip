@@ -76,7 +76,11 @@
 //   length k costs max(gap_open + k * gap, gap_open2 + k * gap2).  Two more gap states per cell, a second 4-bit plane in the field
 //   (blocks interleave the planes), 16-byte seam entries (H, F1, F2), a walk through five states.
 //
-// How the 61 kernels are made: the 48 sweeps are aff_sweep_entry<RLO, RHI, MATRIX, MODE, LONG, BAND, XDROP, ADAPT, TWO> over one block function
+// sw_affine_sweep_[long_|band_]subopt[_matrix][_wide]_kernel: the local sweeps under option "subopt" (DESIGN.md 8n), SUBOPT = 1: a running
+//   column maximum rides down the wave with its column, and the lane that finishes a column leaves colmax(j) in a row of n int32
+//   behind the pair's fields; sw_subopt_kernel (swmi_subopt.hip) turns the row into the pair's second-best score and its end column.
+//
+// How the 69 kernels are made: the 56 sweeps are aff_sweep_entry<RLO, RHI, MATRIX, MODE, LONG, BAND, XDROP, ADAPT, TWO, SUBOPT> over one block function
 //   (aff_block8); the 13 tracebacks are aff_traceback<MODE, LONG, BAND, ADAPT, TWO>, where !LONG is the walk with one strip and !BAND the
 //   walk whose windows are the whole reference.  One macro defines the sweeps, one the tracebacks; the launchers take the
 //   run's options as one AffRun (swmi_launch.h) and pick a kernel from tables typed by signature.  The per-pair sweep is two thin bodies, aff_sweep_pair and aff_sweep_long_pair<.., BAND> (the one strip
@@ -121,6 +125,10 @@ struct AffSeam {
     int4 *row4;            // TWO: the pair's seam row, (H, F1, F2, -) per column: 16-byte entries, one load and one store each
     uint32_t wlane;        // the lane that writes it (63), none in the read's last strip
     uint32_t coff;         // BAND: the columns left of the strip's window (`row` starts at the window, cells are listed with global columns)
+    // SUBOPT (option "subopt"; the short sweeps use these three too)
+    int cm;                // lanes 0..7: the column maxima the strips above left at the 8 columns lane 0 takes in this block (strip 0, short reads: not read)
+    int *cmrow;            // the pair's row of column maxima, from the window's first column on
+    uint32_t cmlane;       // the lane that holds a column's finished maximum and stores it: 63 in a strip, the owner of the read's last row in a short sweep
 };
 
 template <int R>
@@ -137,6 +145,7 @@ struct AffState {
     int e2[R];
     uint32_t acc2[R];
     int f2_last;
+    int cm;                // SUBOPT: the running maximum of H over the lane's current column, rows 1 .. the lane's last (it travels with the column)
 };
 
 // 8 anti-diagonal steps t0 .. t0+7 (a lane outside its column range keeps its state).  The steps are a loop, not unrolled:
@@ -154,13 +163,19 @@ struct AffState {
 //   tie, and H is taken from E, F and the diagonal as before.  The cell leaves a second 4-bit code in S.acc2 (plane 1 of the
 //   field): bit 0 pE (E is E2), bit 1 pF, bit 2 xE2, bit 3 xF2; plane 0 is the one-piece code with xE1, xF1 in bits 2 and 3.
 //   Lane l+1 receives F2 of the last row by one more wave_shr1.  Row 0 is max(o + j*e, o2 + j*e2), F1(0,j) := H + o, F2 := H + o2.
-template <int R, bool STRICT, bool MATRIX, int MODE, bool LONG = false, bool BAND = false, bool TWO = false>
+// SUBOPT (option "subopt", local runs): lane l is at column t - l at step t, so a column travels down the wave one lane per
+//   step and its running maximum rides along: S.cm = max(what lane l-1 held one step ago, mrow), mrow being the maximum of the
+//   lane's rows inside the read at this column (-1 when it has none, or no column).  The move runs every step in every lane.  Lane 0
+//   starts a column at 0 (H >= 0) or, in strips 1.., at what the strips above left (Z.cm, loaded as Z.h is).  Lane Z.cmlane holds the
+//   finished maximum and stores it into the pair's row, a plain vector store.
+template <int R, bool STRICT, bool MATRIX, int MODE, bool LONG = false, bool BAND = false, bool TWO = false, bool SUBOPT = false>
 __device__ __forceinline__ void aff_block8(AffState<R> &S, const uint2 rw, const uint32_t t0, const uint32_t lane,
                                            const uint32_t n, const uint32_t row0, const uint32_t vrows,
                                            const int o, const int e, const int vmat, const int vmis,
                                            uint2 *__restrict__ cells, const uint32_t ccap, const AffSeam &Z = AffSeam{},
                                            const int o2 = 0, const int e2 = 0) {
     static_assert(!TWO || (AFF_ROW0_GAPS(MODE) && !MATRIX), "two-piece gaps: global and extend runs without a score matrix");
+    static_assert(!SUBOPT || MODE == AFF_LOCAL, "subopt: local runs");
     const int oe = o + e;
     const int oe2 = o2 + e2;                                     // (TWO)
 #pragma unroll 1
@@ -262,6 +277,11 @@ __device__ __forceinline__ void aff_block8(AffState<R> &S, const uint2 rw, const
             else if constexpr (LONG) { if (lane == Z.wlane) Z.row[c0] = make_int2(S.h[R - 1], fup); }
         }
         S.nh_prev = nh;
+        if constexpr (SUBOPT) {
+            // (mrow is -1 in a lane without a column)
+            S.cm = max(wave_shr1(LONG ? __builtin_amdgcn_readlane(Z.cm, (int)s) : 0, S.cm), mrow);
+            if (inr && lane == Z.cmlane) Z.cmrow[c0] = S.cm;
+        }
         if constexpr (AFF_ROW_M_ONLY(MODE)) {
             // row m only: the one lane that owns it, at every column (fit) or at column n (global)
             const bool cand = inr && vrows != 0xFFFFFFFFu && (MODE == AFF_FIT || c0 + 1u == n);
@@ -368,7 +388,9 @@ __device__ __forceinline__ AffCells aff_cell_list(const FillArgs &A, const PairD
         A.out[pd.out_id] = po;                                                                                \
     }
 
-template <int R, bool STRICT, bool MATRIX, int MODE, bool TWO = false>
+// SUBOPT: the row of column maxima lies behind the field; the lane that owns the read's last row, lact - 1 of swmi_aff_blocks, stores
+// it -- W is sized for that lane to reach column n
+template <int R, bool STRICT, bool MATRIX, int MODE, bool TWO = false, bool SUBOPT = false>
 __device__ __forceinline__ void aff_sweep_pair(const FillArgs &A, const int o, const PairDesc pd, const uint32_t lane, const uint32_t nn,
                                                const int o2 = 0, const int e2 = 0) {
     const SeqDesc rd = A.refs[pd.ref_id];
@@ -389,6 +411,12 @@ __device__ __forceinline__ void aff_sweep_pair(const FillArgs &A, const int o, c
     S.rb = 0; S.nh_prev = 0; S.f_last = 0;                       // (nh_prev of lane 0: H(0,0) = 0 in every mode)
     if constexpr (TWO) S.f2_last = 0;
     S.thr = MODE == AFF_LOCAL ? 1 : INT32_MIN; S.cnt = 0;
+    AffSeam Zs{};                                                // (SUBOPT)
+    if constexpr (SUBOPT) {
+        S.cm = 0;
+        Zs.cmrow = reinterpret_cast<int *>(dir + (uint64_t)W * R * WAVE);
+        Zs.cmlane = (m + (uint32_t)R - 1u) / (uint32_t)R - 1u;
+    }
     for (uint32_t w = 0; w < W; ++w) {
         const uint32_t t0 = 8u * w;
         // lane 0's 8 reference bases (images are padded: the last block may read past the end)
@@ -400,7 +428,9 @@ __device__ __forceinline__ void aff_sweep_pair(const FillArgs &A, const int o, c
             for (int k = 0; k < R; ++k) S.acc2[k] = 0u;
             aff_block8<R, STRICT, MATRIX, MODE, false, false, true>(S, rw, t0, lane, n, row0, vrows, o, A.gap, A.match, A.mismatch, cells, ccap,
                                                                     AffSeam{}, o2, e2);
-        } else
+        } else if constexpr (SUBOPT)
+        aff_block8<R, STRICT, MATRIX, MODE, false, false, false, true>(S, rw, t0, lane, n, row0, vrows, o, A.gap, A.match, A.mismatch, cells, ccap, Zs);
+        else
         aff_block8<R, STRICT, MATRIX, MODE>(S, rw, t0, lane, n, row0, vrows, o, A.gap, A.match, A.mismatch, cells, ccap);
         AFF_STORE_BLOCK
     }
@@ -454,11 +484,18 @@ __device__ __forceinline__ void aff_sweep_pair(const FillArgs &A, const int o, c
 //   lane 63 stores the entry of column clo + t - 63 at step t, so every entry is read at least 63 steps before this strip
 //   overwrites it, as it stands for 8-byte entries.  nh_prev reads word x of the entry of column clo - 1.  A strip's field is
 //   twice swmi_aff_strip_words of its window; under BAND a cell outside reads SWMI_AFF_BAND_NEG in all five values.
-template <bool STRICT, bool MATRIX, int MODE, bool BAND, bool XDROP = false, bool ADAPT = false, bool TWO = false>
+// SUBOPT (option "subopt", local runs): the pair's row of column maxima, n int32 behind the strips' fields, is rewritten IN
+//   PLACE strip after strip like the seam row, and the argument above holds word for word: lane 0 loads the row's entries of columns
+//   clo + t0 .. clo + t0 + 7 at step t0, lane 63 stores the entry of column clo + t - 63 at step t, behind the same fence.  Lane 63
+//   stores in EVERY strip, the last one too.  The row is indexed by the global column: under BAND a column left of a later strip's
+//   window keeps what the earlier strips left, and lane 0 starts a column the strips above never reached (beyond seam_end) at 0 --
+//   the words there were never written.  Columns right of the last window stay unwritten: readers stop at swmi_aff_colmax_cols.
+template <bool STRICT, bool MATRIX, int MODE, bool BAND, bool XDROP = false, bool ADAPT = false, bool TWO = false, bool SUBOPT = false>
 __device__ __forceinline__ void aff_sweep_long_pair(const FillArgs &A, const int o, const PairDesc pd, const uint32_t lane, const uint32_t nn,
                                                     const uint32_t wb, const uint32_t xd = 0u, const int o2 = 0, const int e2 = 0) {
     static_assert(!ADAPT || (BAND && MODE == AFF_EXTEND), "band_adapt is an option of the banded strip sweeps of an extend run");
     static_assert(!TWO || (!XDROP && !ADAPT), "two-piece gaps: not under xdrop or band_adapt");
+    static_assert(!SUBOPT || (MODE == AFF_LOCAL && !XDROP && !ADAPT && !TWO), "subopt: local runs");
     constexpr int R = SWMI_AFF_RMAX;
     constexpr int OUT = BAND && MODE != AFF_LOCAL ? SWMI_AFF_BAND_NEG : 0;
     const SeqDesc rd = A.refs[pd.ref_id];
@@ -476,6 +513,10 @@ __device__ __forceinline__ void aff_sweep_long_pair(const FillArgs &A, const int
     AffSeam Z;
     Z.row = seam;
     Z.row4 = seam4;
+    // SUBOPT: the row of column maxima, behind the last strip's field
+    int *const cmbase = SUBOPT ? reinterpret_cast<int *>(A.dir + pd.dir_off + (BAND ? swmi_aff_band_strip_off(NS, n, wb) : (uint64_t)NS * swmi_aff_strip_words(n)))
+                               : nullptr;
+    if constexpr (SUBOPT) { Z.cmrow = cmbase; Z.cmlane = 63u; }
     uint32_t *__restrict__ dir = A.dir + pd.dir_off;
     uint64_t inband = 0ull;                                      // BAND: in-band cells with i <= m (the degenerate count)
     uint32_t stopped = 0u;                                       // XDROP: the strips swept of a pair that was stopped, else 0
@@ -543,6 +584,7 @@ __device__ __forceinline__ void aff_sweep_long_pair(const FillArgs &A, const int
         }
         S.rb = 0; S.f_last = 0;
         if constexpr (TWO) S.f2_last = 0;
+        if constexpr (SUBOPT) S.cm = 0;
         // nh_prev of lane 0: H(1024 * sx, clo - 1)
         if constexpr (!BAND) S.nh_prev = MODE != AFF_LOCAL && sx ? o + (int)(sx * SWMI_AFF_MAX_READ) * A.gap : 0;
         if constexpr (!BAND && TWO) { if (sx) S.nh_prev = max(S.nh_prev, o2 + (int)(sx * SWMI_AFF_MAX_READ) * e2); }
@@ -550,6 +592,7 @@ __device__ __forceinline__ void aff_sweep_long_pair(const FillArgs &A, const int
             Z.row = seam + (clo - 1u);
             if constexpr (TWO) Z.row4 = seam4 + (clo - 1u);
             Z.coff = clo - 1u;
+            if constexpr (SUBOPT) Z.cmrow = cmbase + (clo - 1u);
         }
         Z.wlane = sx + 1u < NS ? 63u : 0xFFFFFFFFu;
         if constexpr (!BAND) dir = A.dir + pd.dir_off + (uint64_t)sx * (TWO ? 2u : 1u) * swmi_aff_strip_words(n);
@@ -608,13 +651,18 @@ __device__ __forceinline__ void aff_sweep_long_pair(const FillArgs &A, const int
                 if (lane < 8u && c < seam_end) v = Z.row[c];
                 Z.h = v.x; Z.f = v.y;
             }
+            if constexpr (SUBOPT) {
+                // what the strips above left at lane 0's 8 columns (a vector load, behind the fence); 0 in strip 0 and beyond seam_end
+                Z.cm = 0;
+                if (sx && lane < 8u && c < seam_end) Z.cm = Z.cmrow[c];
+            }
 #pragma unroll
             for (int k = 0; k < R; ++k) S.acc[k] = 0u;
             if constexpr (TWO) {
 #pragma unroll
                 for (int k = 0; k < R; ++k) S.acc2[k] = 0u;
             }
-            aff_block8<R, STRICT, MATRIX, MODE, true, BAND, TWO>(S, rw, t0, lane, nw, row0, vrows, o, A.gap, A.match, A.mismatch, cells, ccap, Z, o2, e2);
+            aff_block8<R, STRICT, MATRIX, MODE, true, BAND, TWO, SUBOPT>(S, rw, t0, lane, nw, row0, vrows, o, A.gap, A.match, A.mismatch, cells, ccap, Z, o2, e2);
             AFF_STORE_BLOCK
         }
         if constexpr (BAND && !ADAPT) dir += (uint64_t)W * (TWO ? 2 : 1) * R * WAVE;
@@ -628,12 +676,12 @@ __device__ __forceinline__ void aff_sweep_long_pair(const FillArgs &A, const int
 #undef AFF_PAIR_OUT
 
 // RLO..RHI: the rows per lane this instantiation of the kernel takes (the others' registers would cap its occupancy)
-template <int RLO, int RHI, bool STRICT, bool MATRIX, int MODE, bool TWO = false>
+template <int RLO, int RHI, bool STRICT, bool MATRIX, int MODE, bool TWO = false, bool SUBOPT = false>
 __device__ __forceinline__ void aff_sweep_dispatch(const FillArgs &A, const int o, const PairDesc pd, const uint32_t R, const uint32_t lane,
                                                    const uint32_t nn, const int o2 = 0, const int e2 = 0) {
     if constexpr (RLO <= RHI) {
-        if (R == (uint32_t)RLO) aff_sweep_pair<RLO, STRICT, MATRIX, MODE, TWO>(A, o, pd, lane, nn, o2, e2);
-        else aff_sweep_dispatch<RLO + 1, RHI, STRICT, MATRIX, MODE, TWO>(A, o, pd, R, lane, nn, o2, e2);
+        if (R == (uint32_t)RLO) aff_sweep_pair<RLO, STRICT, MATRIX, MODE, TWO, SUBOPT>(A, o, pd, lane, nn, o2, e2);
+        else aff_sweep_dispatch<RLO + 1, RHI, STRICT, MATRIX, MODE, TWO, SUBOPT>(A, o, pd, R, lane, nn, o2, e2);
     }
 }
 
@@ -642,13 +690,15 @@ __device__ __forceinline__ void aff_sweep_dispatch(const FillArgs &A, const int 
 // XDROP (with LONG and AFF_EXTEND): the strip sweep under option "xdrop", threshold xd
 // ADAPT (with LONG, BAND and AFF_EXTEND): the banded strip sweep under option "band_adapt"
 // TWO (AFF_GLOBAL and AFF_EXTEND, no MATRIX, XDROP or ADAPT): two-piece gaps, the second piece's open o2 and extension e2
+// SUBOPT (AFF_LOCAL, no XDROP, ADAPT or TWO): the sweep also leaves the pair's row of column maxima (option "subopt")
 template <int RLO, int RHI, bool MATRIX, int MODE = AFF_LOCAL, bool LONG = false, bool BAND = false, bool XDROP = false, bool ADAPT = false,
-          bool TWO = false>
+          bool TWO = false, bool SUBOPT = false>
 __device__ __forceinline__ void aff_sweep_entry(const FillArgs &A, const int o, const uint32_t *__restrict__ mat, const uint32_t nn,
                                                 const uint32_t wb = 0u, const uint32_t xd = 0u, const int o2 = 0, const int e2 = 0) {
     static_assert(!TWO || (AFF_ROW0_GAPS(MODE) && !MATRIX && !XDROP && !ADAPT), "two-piece gaps: plain global and extend runs");
     static_assert(!XDROP || (LONG && MODE == AFF_EXTEND), "xdrop is an option of the strip sweeps of an extend run");
     static_assert(!ADAPT || (LONG && BAND && MODE == AFF_EXTEND), "band_adapt is an option of the banded strip sweeps of an extend run");
+    static_assert(!SUBOPT || (MODE == AFF_LOCAL && !XDROP && !ADAPT && !TWO), "subopt is an option of the local sweeps");
     if (blockIdx.x == 0 && threadIdx.x == 0) A.hdr->reserved = 0ull;      // the traceback's bump allocator
     if (MATRIX) {                                                          // (before any wavefront leaves)
         for (uint32_t x = threadIdx.x; x < 256u; x += WAVE * AFF_WAVES) aff_mkey[x] = mat[x];
@@ -665,14 +715,14 @@ __device__ __forceinline__ void aff_sweep_entry(const FillArgs &A, const int o, 
     const PairDesc pd = A.pairs[pair];
     if constexpr (LONG) {
         if (uni(A.reads[pd.read_id].len) <= SWMI_AFF_MAX_READ) return;
-        if (A.strict) aff_sweep_long_pair<true, MATRIX, MODE, BAND, XDROP, ADAPT, TWO>(A, o, pd, lane, nn, wb, xd, o2, e2);
-        else          aff_sweep_long_pair<false, MATRIX, MODE, BAND, XDROP, ADAPT, TWO>(A, o, pd, lane, nn, wb, xd, o2, e2);
+        if (A.strict) aff_sweep_long_pair<true, MATRIX, MODE, BAND, XDROP, ADAPT, TWO, SUBOPT>(A, o, pd, lane, nn, wb, xd, o2, e2);
+        else          aff_sweep_long_pair<false, MATRIX, MODE, BAND, XDROP, ADAPT, TWO, SUBOPT>(A, o, pd, lane, nn, wb, xd, o2, e2);
         return;
     }
     const uint32_t R = uni(swmi_aff_rows_per_lane(A.reads[pd.read_id].len));
     if (R < (uint32_t)RLO || R > (uint32_t)RHI) return;
-    if (A.strict) aff_sweep_dispatch<RLO, RHI, true, MATRIX, MODE, TWO>(A, o, pd, R, lane, nn, o2, e2);
-    else          aff_sweep_dispatch<RLO, RHI, false, MATRIX, MODE, TWO>(A, o, pd, R, lane, nn, o2, e2);
+    if (A.strict) aff_sweep_dispatch<RLO, RHI, true, MATRIX, MODE, TWO, SUBOPT>(A, o, pd, R, lane, nn, o2, e2);
+    else          aff_sweep_dispatch<RLO, RHI, false, MATRIX, MODE, TWO, SUBOPT>(A, o, pd, R, lane, nn, o2, e2);
 }
 
 }  // namespace
@@ -743,6 +793,21 @@ AFF_SWEEP_KERNEL(sw_affine_sweep_band_adapt_matrix_kernel, SWMI_AFF_RMAX, SWMI_A
 AFF_SWEEP_KERNEL(sw_affine_sweep_band_adapt_xdrop_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, AFF_EXTEND, true, 1, 1, 1)
 AFF_SWEEP_KERNEL(sw_affine_sweep_band_adapt_xdrop_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, AFF_EXTEND, true, 1, 1, 1)
 #undef AFF_SWEEP_KERNEL
+// The 8 local sweeps under option "subopt" (DESIGN.md 8n), SUBOPT = 1: narrow, wide, long and banded long, each plain and with a score
+// matrix, with the signatures of their SUBOPT = 0 twins -- the row of column maxima lies behind the pair's fields, which the sweep finds.
+#define AFF_SWEEPS_KERNEL(name, RLO, RHI, MATRIX, LONG, BAND)                                                             \
+    extern "C" __global__ void __launch_bounds__(WAVE * AFF_WAVES) name(AFF_SWEEP_PARAMS_##MATRIX##BAND##0) {            \
+        aff_sweep_entry<RLO, RHI, MATRIX != 0, AFF_LOCAL, LONG, BAND != 0, false, false, false, true>(AFF_SWEEP_ARGS_##MATRIX##BAND##0); \
+    }
+AFF_SWEEPS_KERNEL(sw_affine_sweep_subopt_kernel, 1, 4, 0, false, 0)
+AFF_SWEEPS_KERNEL(sw_affine_sweep_subopt_wide_kernel, 5, SWMI_AFF_RMAX, 0, false, 0)
+AFF_SWEEPS_KERNEL(sw_affine_sweep_long_subopt_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, true, 0)
+AFF_SWEEPS_KERNEL(sw_affine_sweep_subopt_matrix_kernel, 1, 4, 1, false, 0)
+AFF_SWEEPS_KERNEL(sw_affine_sweep_subopt_matrix_wide_kernel, 5, SWMI_AFF_RMAX, 1, false, 0)
+AFF_SWEEPS_KERNEL(sw_affine_sweep_long_subopt_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, true, 0)
+AFF_SWEEPS_KERNEL(sw_affine_sweep_band_subopt_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, true, 1)
+AFF_SWEEPS_KERNEL(sw_affine_sweep_band_subopt_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, true, 1)
+#undef AFF_SWEEPS_KERNEL
 // The 8 two-piece sweeps (option "gap_open2"): global and extend, each narrow, wide, long and banded long, TWO = 1.
 // The second piece's open and extension follow gap_open; the banded ones take the half-width last.
 #define AFF_SWEEP2_PARAMS_0 const FillArgs A, const int gap_open, const int gap_open2, const int gap2
@@ -1024,7 +1089,8 @@ AFF_TRACEBACK_KERNEL(sw_affine_traceback2_band_global_kernel, AFF_GLOBAL, true, 
 // ------------------------------------------------------------------------------------------------
 // Both take the run's options as one AffRun and refuse what aff_run_ok refuses (swmi_launch.h, which describes the arguments).
 // A kernel is picked from tables typed by signature -- ten for the sweeps: with / without the matrix, the half-width and the
-// threshold, and the two-piece sweeps with / without the half-width; two for the walks -- and launched through one generic
+// threshold, and the two-piece sweeps with / without the half-width (the sweeps of option "subopt" have their twins' signatures);
+// two for the walks -- and launched through one generic
 // lambda, so that every launch is checked against its kernel's parameter list: one branch per signature.
 static_assert(AFF_EXTEND == 3, "AffRun.mode 3 is the extend run");
 
@@ -1062,6 +1128,12 @@ extern "C" hipError_t swmi_launch_affine_sweep(const FillArgs *a, const AffRun *
         {sw_affine_sweep2_global_wide_kernel, sw_affine_sweep2_extend_wide_kernel},
         {sw_affine_sweep2_long_global_kernel, sw_affine_sweep2_long_extend_kernel}};
     static void (*const tbplain[2])(FillArgs, int, int, int, uint32_t) = {sw_affine_sweep2_band_global_kernel, sw_affine_sweep2_band_extend_kernel};
+    // the local sweeps under option "subopt", [narrow / wide / long], and the banded long ones
+    static void (*const splain[3])(FillArgs, int) = {sw_affine_sweep_subopt_kernel, sw_affine_sweep_subopt_wide_kernel, sw_affine_sweep_long_subopt_kernel};
+    static void (*const smatrix[3])(FillArgs, int, const uint32_t *, uint32_t) = {
+        sw_affine_sweep_subopt_matrix_kernel, sw_affine_sweep_subopt_matrix_wide_kernel, sw_affine_sweep_long_subopt_matrix_kernel};
+    static void (*const sbplain)(FillArgs, int, uint32_t) = sw_affine_sweep_band_subopt_kernel;
+    static void (*const sbmatrix)(FillArgs, int, const uint32_t *, uint32_t, uint32_t) = sw_affine_sweep_band_subopt_matrix_kernel;
     const dim3 grid((a->n_pairs + AFF_WAVES - 1) / AFF_WAVES), block(WAVE * AFF_WAVES);
     // (extra...: what the kernel takes after the arguments every sweep takes.  A launch's own error is what hipGetLastError returns below)
     const auto launch = [&](auto *k, auto... extra) { hipLaunchKernelGGL(k, grid, block, 0, st, *a, (int)r->gap_open, extra...); };
@@ -1071,6 +1143,10 @@ extern "C" hipError_t swmi_launch_affine_sweep(const FillArgs *a, const AffRun *
     const auto sweep = [&](int shape) {
         if (r->gap_open2 && band)  launch(tbplain[mode - 2u], (int)r->gap_open2, (int)r->gap2, band);
         else if (r->gap_open2)     launch(tplain[shape][mode - 2u], (int)r->gap_open2, (int)r->gap2);
+        else if (r->subopt && mat && band) launch(sbmatrix, mat, nn, band);
+        else if (r->subopt && mat) launch(smatrix[shape], mat, nn);
+        else if (r->subopt && band) launch(sbplain, band);
+        else if (r->subopt)        launch(splain[shape]);
         else if (mat && band && xdrop) launch(xbmatrix[adapt], mat, nn, band, xdrop);
         else if (mat && band)      launch(bmatrix[adapt ? 4u : mode], mat, nn, band);
         else if (mat && xdrop)     launch(xmatrix, mat, nn, xdrop);

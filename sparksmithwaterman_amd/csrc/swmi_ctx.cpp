@@ -197,6 +197,10 @@ extern "C" int swmi_set_option(swmi_ctx *ctx, const char *name, int64_t value) {
     } else if (!strcmp(name, "cigar")) {
         if (value < 0 || value > 2) return fail(SWMI_ERR_INVALID, "cigar must be 0 (off), 1 (M/I/D) or 2 (=/X/I/D), got %lld", (long long)value);
         ctx->modes.cigar = (int)value;
+    } else if (!strcmp(name, "subopt")) {
+        if (value < SWMI_SUBOPT_AUTO || value > (1ll << 30))
+            return fail(SWMI_ERR_INVALID, "subopt must be 0 (off), a mask half-width of 1 .. 2^30 columns or -1 (SWMI_SUBOPT_AUTO), got %lld", (long long)value);
+        ctx->modes.subopt = (int)value;
     } else if (!strcmp(name, "arena_words_per_pair")) {
         if (value < 1) return fail(SWMI_ERR_INVALID, "arena_words_per_pair out of range");
         ctx->arena_words_per_pair = (uint64_t)value;

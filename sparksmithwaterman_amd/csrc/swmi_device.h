@@ -358,9 +358,11 @@ SWMI_HD static inline uint64_t swmi_aff_adapt_strip_words(uint32_t n, uint32_t w
 struct AffGeom {
     uint32_t band;       // option "band": the half-width, 0: none (it shapes the fields of reads longer than SWMI_AFF_MAX_READ only)
     bool adapt, two;     // options "band_adapt" (with band, never with two) and "gap_open2"
-    bool operator==(const AffGeom &o) const { return band == o.band && adapt == o.adapt && two == o.two; }
+    bool subopt;         // option "subopt" (local runs: never with adapt or two): the pair's row of column maxima behind its fields
+    bool operator==(const AffGeom &o) const { return band == o.band && adapt == o.adapt && two == o.two && subopt == o.subopt; }
 };
-// dwords of the pair's direction fields (m > 1024: the strips', consecutive) = where the window table of "band_adapt" starts
+// dwords of the pair's direction fields (m > 1024: the strips', consecutive) = where the window table of "band_adapt" or the
+// row of column maxima of "subopt" starts
 SWMI_HD static inline uint64_t swmi_aff_pair_table_off(uint32_t m, uint32_t n, AffGeom g) {
     const uint64_t planes = g.two ? 2u : 1u, ns = swmi_aff_strips(m);
     if (m <= SWMI_AFF_MAX_READ) return planes * swmi_aff_blocks(m, n) * swmi_aff_rows_per_lane(m) * 64u;
@@ -368,10 +370,20 @@ SWMI_HD static inline uint64_t swmi_aff_pair_table_off(uint32_t m, uint32_t n, A
     if (g.adapt) return ns * swmi_aff_adapt_strip_words(n, g.band);                 // a fixed stride per strip
     return planes * swmi_aff_band_strip_off((uint32_t)ns, n, g.band);               // the strips' windows: the offset of strip NS
 }
-// what the pair is charged in the launch's `dir` workspace: the fields and, under "band_adapt", the table -- one dword per strip,
-// rounded to 64 dwords so that the next pair's field stays 256-byte aligned
+// ---- option "subopt" (local runs): behind the fields the sweep leaves colmax(j), the maximum of H over column j, one
+// int32 per column j = 1 .. n at dword j - 1, for sw_subopt_kernel.  Under "band" the columns right of the last strip's window are
+// never written: the row ends, for every reader, at swmi_aff_colmax_cols. ----
+SWMI_HD static inline uint32_t swmi_aff_colmax_cols(uint32_t m, uint32_t n, uint32_t band) {
+    return band && m > SWMI_AFF_MAX_READ ? swmi_aff_band_hi(swmi_aff_strips(m) - 1u, n, band) : n;
+}
+// what sw_subopt_kernel (swmi_subopt.hip) makes of the row, per pair: swmi.h's score2 and end2
+struct SuboptOut { int32_t score2; uint32_t end2; };
+// what the pair is charged in the launch's `dir` workspace: the fields and, under "band_adapt", the table -- one dword per strip --
+// or, under "subopt", the row of column maxima -- one per column; either rounded to 64 dwords so that the next pair's field stays
+// 256-byte aligned
 SWMI_HD static inline uint64_t swmi_aff_pair_dir_words(uint32_t m, uint32_t n, AffGeom g) {
-    return swmi_aff_pair_table_off(m, n, g) + (g.band && g.adapt && m > SWMI_AFF_MAX_READ ? ((uint64_t)swmi_aff_strips(m) + 63u) & ~63ull : 0ull);
+    return swmi_aff_pair_table_off(m, n, g) + (g.band && g.adapt && m > SWMI_AFF_MAX_READ ? ((uint64_t)swmi_aff_strips(m) + 63u) & ~63ull : 0ull) +
+           (g.subopt ? ((uint64_t)n + 63u) & ~63ull : 0ull);
 }
 // dwords of the pair's seam row: (H, F) per column, two-piece 16 bytes; ONE row, rewritten in place by every strip but the last
 SWMI_HD static inline uint64_t swmi_aff_pair_seam_words(uint32_t m, uint32_t n, AffGeom g) { return m > SWMI_AFF_MAX_READ ? (g.two ? 4ull : 2ull) * n : 0ull; }

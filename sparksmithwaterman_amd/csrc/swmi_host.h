@@ -123,6 +123,7 @@ struct __attribute__((visibility("hidden"))) RunModes {
     int gap_open2 = 0;                      // != 0: two-piece gaps on a global or extend run -- the second piece's open (swmi.h); refused in other runs
     int gap2 = 0;                           // ... and its per-base extension (not read while gap_open2 == 0)
     int cigar = 0;                          // 1 / 2: the records' payload is a CIGAR, M/I/D or =/X/I/D (swmi.h); the affine kernels
+    int subopt = 0;                         // != 0: a local run also returns every pair's second-best score -- the mask half-width, -1 automatic (swmi.h); refused in the other modes
     bool two_piece() const { return gap_open2 != 0; }
     // the MODE of the affine kernels and their launchers: the align_mode, or 3 (extend) for a global run with option "extend"
     uint32_t kernel_mode() const { return extend && align_mode == SWMI_ALIGN_GLOBAL ? 3u : (uint32_t)align_mode; }
@@ -141,7 +142,7 @@ static inline bool swmi_adapt_bound_ok(uint64_t m, uint64_t n, int64_t gap_open,
 }
 // the options that decide the size of a mode-3 pair's workspace (swmi_device.h), as a run has them
 static inline AffGeom aff_geom(const RunModes &md) {
-    return AffGeom{md.band > 0 ? (uint32_t)md.band : 0u, md.band > 0 && md.band_adapt != 0, md.two_piece()};
+    return AffGeom{md.band > 0 ? (uint32_t)md.band : 0u, md.band > 0 && md.band_adapt != 0, md.two_piece(), md.subopt != 0};
 }
 // Everything a batch's schedule (swmi_batch::work: the pairs in launch order with their workspace sizes) depends on besides the
 // sequences.  A run whose key equals the key of the schedule the batch holds keeps it.  An input of the sizes that is missing
@@ -199,7 +200,7 @@ struct swmi_ctx {
     bool cell_cap_set = false;              // cell_cap given by the caller (otherwise small launches get longer lists)
     int32_t gap_open = 0;                   // affine gaps: a gap of length k costs gap_open + k * gap (0: linear)
     int affine = -1;                        // -1: the affine kernels (mode 3) when gap_open != 0; 1: always
-    RunModes modes;                         // options "align_mode", "long_reads", "band", "extend", "xdrop", "band_adapt", "gap_open2", "gap2" and "cigar"
+    RunModes modes;                         // options "align_mode", "long_reads", "band", "extend", "xdrop", "band_adapt", "gap_open2", "gap2", "cigar" and "subopt"
     std::mutex mat_mu;                      // guards `matrix` (not ctx->mu: setting a matrix does not wait for a run)
     std::shared_ptr<const ScoreMatrix> matrix;   // swmi_set_score_matrix; a run with one takes the affine kernels
     // swmi_batch_run_async: one run in flight on the context's own host thread
@@ -343,6 +344,8 @@ struct swmi_batch {
     PlanKey plan_key;                       // the chunk the device-side item lists and `plan` were prepared for last
     ChunkPlan plan;
     std::vector<PairRes> pairs;             // by pair index
+    bool has_sub = false;                   // the last run had option "subopt": `sub` holds every pair's (score2, end2), (0, 0) for a pair that was not swept
+    std::vector<SuboptOut> sub;                // by pair index
     // option "band_adapt": the window tables the sweeps of the last run left (the centre of every strip, swmi_device.h), fetched
     // after every launch; win_at[pair] = 1 + the index of the pair's first entry in win_tab, 0 for a pair without a table
     std::vector<uint32_t> win_tab;
@@ -393,10 +396,11 @@ struct RunState {
     bool keep = true;                       // the launch's records belong to the batch's results (false: the sampled pre-pass)
 };
 
-// layout of the result block: [ArenaHdr | PairOut x np | record table, tab_cap entries | arena words ...]
+// layout of the result block: [ArenaHdr | PairOut x np | sub: SuboptOut x np (option "subopt" only) | record table, tab_cap entries | arena words ...]
 static inline size_t result_out_off() { return 64; }
-static inline size_t result_tab_off(size_t np) { return (64 + np * sizeof(PairOut) + 255) & ~(size_t)255; }
-static inline size_t result_arena_off(size_t np, uint64_t tab_cap) { return (result_tab_off(np) + tab_cap * sizeof(AlnRec) + 255) & ~(size_t)255; }
+static inline size_t result_sub_off(size_t np) { return 64 + np * sizeof(PairOut); }
+static inline size_t result_tab_off(size_t np, bool sub) { return (64 + np * (sizeof(PairOut) + (sub ? sizeof(SuboptOut) : 0)) + 255) & ~(size_t)255; }
+static inline size_t result_arena_off(size_t np, uint64_t tab_cap, bool sub) { return (result_tab_off(np, sub) + tab_cap * sizeof(AlnRec) + 255) & ~(size_t)255; }
 // dwords of one alignment's payload: the two strings, n_ops / 4 + 1 dwords each, or the ops packed 16 per dword (swmi_emit.h)
 static inline uint64_t rec_words(uint32_t n_ops, bool strings) {
     return strings ? 2 * ((uint64_t)n_ops / 4 + 1) : ((uint64_t)n_ops + 15) / 16;

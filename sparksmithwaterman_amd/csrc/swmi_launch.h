@@ -30,6 +30,7 @@ struct AffRun {
     const uint32_t *mat;         // the device image of the score matrix (swmi_aff_mat_words dwords), or null: the plain sweeps
     uint32_t nn;                 // ... and its side n + 1 (2 .. SWMI_MAT_NN_MAX)
     uint32_t cigar;              // option "cigar" (0: off; 1: M/I/D, 2: =/X/I/D) -- the payload the walks write (swmi_emit.h); the sweeps do not read it
+    int32_t subopt;              // option "subopt" (0: off; 1 .. 2^30: the mask half-width, -1: per pair) -- the local sweeps that leave the column maxima
 };
 // What the launchers refuse (hipErrorInvalidValue): the combinations no kernel exists for.  band, xdrop and adapt are options of
 // the long shape (long_reads: every pair of the launch has a read longer than SWMI_AFF_MAX_READ); the short shape ignores them.
@@ -38,6 +39,7 @@ static inline bool aff_run_ok(const AffRun &r, uint32_t long_reads) {
     if (r.mode > 3u || r.band > SWMI_AFF_BAND_MAX || r.xdrop > 0x7FFFFFFFu || r.adapt > 1u || r.cigar > 2u) return false;
     if (r.mat && (r.nn < 2u || r.nn > SWMI_MAT_NN_MAX)) return false;
     if (r.gap_open2 && (r.mode < 2u || r.mat || r.xdrop || r.adapt)) return false;      // two-piece: plain global and extend runs
+    if (r.subopt < -1 || r.subopt > (1 << 30) || (r.subopt && r.mode != 0u)) return false;   // subopt: local runs
     if (long_reads && r.xdrop && r.mode != 3u) return false;                            // xdrop: extend runs
     if (long_reads && r.adapt && (!r.band || r.mode != 3u)) return false;               // band_adapt: banded extend runs
     return true;
@@ -49,6 +51,21 @@ extern "C" hipError_t swmi_launch_affine_sweep(const FillArgs *a, const AffRun *
 // tile_words, ops_words: the LDS dwords of a wavefront's direction tile and of its packed ops
 extern "C" hipError_t swmi_launch_affine_traceback(const TraceArgs *a, const AffRun *r, uint32_t long_reads, uint32_t tile_words,
                                                    uint32_t ops_words, hipStream_t st);
+// Option "subopt" (swmi_subopt.hip): sw_subopt_kernel, one wavefront per pair of the launch -- the short and the long shape alike --
+// behind the sweeps on the same stream.  It reads the pair's score and its row of column maxima (behind the pair's fields in `dir`,
+// swmi_device.h) and writes (score2, end2) as swmi.h defines them.
+struct SuboptArgs {
+    const SeqDesc *refs, *reads;
+    const PairDesc *pairs;
+    const uint32_t *dir;         // the launch's workspace
+    const PairOut *out;          // the sweeps' pair outputs, by out_id
+    SuboptOut *sub;              // per out_id, device memory
+    SuboptOut *sub_host;         // zero-copy results: its host-mapped mirror, or null
+    uint32_t n_pairs;
+    uint32_t band;               // option "band" (0: none): it shapes the fields the row lies behind, and ends the row
+    int32_t subopt;              // the mask half-width, or -1: max(m / 2, 15) per pair
+};
+extern "C" hipError_t swmi_launch_subopt(const SuboptArgs *a, hipStream_t st);
 extern "C" hipError_t swmi_launch_encode(const uint8_t *raw, const uint64_t *raw_off, SeqDesc *desc, uint32_t *seqw,
                                          const uint8_t *lut, uint32_t n_seq, hipStream_t st);
 // pair lists: the segments' images (and the raw bytes of reversed segments) from the resident sources (sw_gather_kernel)

@@ -194,6 +194,29 @@ extern "C" int swmi_batch_pair_results(const swmi_batch *b, int32_t *scores, uin
     return SWMI_OK;
 }
 
+// option "subopt": the pair's second-best score and its end column (swmi.h)
+extern "C" int swmi_pair_subopt(const swmi_batch *b, uint64_t pair, int32_t *score2, uint32_t *end2) {
+    int rc = check_pair(b, pair);
+    if (rc) return rc;
+    if (!b->has_sub) return fail(SWMI_ERR_UNSUPPORTED, "the batch was run with subopt = 0: there is no second-best score");
+    if (score2) *score2 = b->sub[pair].score2;
+    if (end2) *end2 = b->sub[pair].end2;
+    return SWMI_OK;
+}
+
+extern "C" int swmi_batch_pair_subopt(const swmi_batch *b, int32_t *score2, uint32_t *end2, uint64_t n) {
+    if (!b) return fail(SWMI_ERR_INVALID, "batch is null");
+    if (!b->has_run) return fail(SWMI_ERR_INVALID, "batch has no results (run it first)");
+    if (!b->has_sub) return fail(SWMI_ERR_UNSUPPORTED, "the batch was run with subopt = 0: there is no second-best score");
+    if (n != batch_n_pairs(b)) return fail(SWMI_ERR_RANGE, "the batch has %llu pairs, not %llu",
+                                           (unsigned long long)batch_n_pairs(b), (unsigned long long)n);
+    for (uint64_t k = 0; k < n; k++) {
+        if (score2) score2[k] = b->sub[k].score2;
+        if (end2) end2[k] = b->sub[k].end2;
+    }
+    return SWMI_OK;
+}
+
 // Pops the traceback "stack" into the two aligned strings (SmithWaterman.java:418-431): ops are stored
 // from the max cell backwards, so the strings are built by walking them in reverse.
 static void materialise(swmi_batch *b, uint64_t pair, HostAln &a, uint64_t slot) {

@@ -51,6 +51,7 @@ struct Launch {
     bool split = false;                     // the split traceback takes the launch
     bool zc = false;                        // results land in pinned host memory while the kernels run
     bool sweep_only = false;                // option scores_only
+    bool sub = false;                       // option "subopt": the result block holds a SuboptOut per pair behind the pair outputs
     bool time_all = false;                  // (profiling = 2: only the sweep is bracketed -- two marker packets per run instead of three; each costs ~3.5 us of the step)
     uint64_t arena_cap = 0, tab_cap = 0;    // grown by an attempt that overflowed
     // per attempt
@@ -253,6 +254,7 @@ static inline AffRun aff_run(const swmi_batch *b) {
     r.mat = b->opt.mat ? b->d_mat.as<uint32_t>() : nullptr;
     r.nn = b->opt.mat ? b->opt.mat->n + 1u : 0u;
     r.cigar = (uint32_t)md.cigar;
+    r.subopt = md.subopt;
     return r;
 }
 
@@ -288,6 +290,17 @@ static int enqueue_launches(RunState &rs, Launch &L, const ResidentArgs &xa, con
         else HIP_TRY(swmi_launch_fill(&fa, ctx->stream, ext ? ctx->ev[0] : nullptr, ext ? ctx->ev[1] : nullptr));
         rs.launches++;
     }
+    if (L.sub) {
+        // option "subopt": the reduce over the rows of column maxima the sweeps left, behind them on the stream.  On EVERY attempt:
+        // it only reads the workspace, which survives a retry, and the pair outputs, which the retry has put back -- and the pinned
+        // block it mirrors into may have been re-allocated.  Timed with the sweep.
+        SuboptArgs sa{};
+        sa.refs = fa.refs; sa.reads = fa.reads; sa.pairs = fa.pairs; sa.dir = fa.dir; sa.out = fa.out;
+        sa.sub = (SuboptOut *)(L.res + result_sub_off(np));
+        sa.sub_host = L.zc && !L.sweep_only ? (SuboptOut *)((uint8_t *)b->h_result.dp + result_sub_off(np)) : nullptr;
+        sa.n_pairs = (uint32_t)np; sa.band = b->opt.modes.band > 0 ? (uint32_t)b->opt.modes.band : 0u; sa.subopt = ar.subopt;
+        HIP_TRY(swmi_launch_subopt(&sa, ctx->stream));
+    }
     if (n_tf) HIP_TRY(swmi_launch_tfused(&ta, &xt, ctx->stream));             // (sweep AND traceback of its pairs: timed with the sweep)
     if (L.whole_only && n_tf) rs.launches++;
     if (ctx->profiling && !ext) HIP_TRY(hipEventRecord(ctx->ev[1], ctx->stream));     // end of the sweep = start of the traceback
@@ -298,8 +311,9 @@ static int enqueue_launches(RunState &rs, Launch &L, const ResidentArgs &xa, con
         // option scores_only: the pair outputs as the sweep kernels left them (the traceback kernels, which otherwise mirror
         // them into the host block, do not run)
         if ((rc = b->h_result.reserve(L.a_off + L.arena_cap * 4))) return rc;
-        HIP_TRY(hipMemcpyAsync((uint8_t *)b->h_result.p + result_out_off(), L.res + result_out_off(), np * sizeof(PairOut),
-                               hipMemcpyDeviceToHost, ctx->stream));
+        // (option "subopt": and the SuboptOut array, which follows them)
+        HIP_TRY(hipMemcpyAsync((uint8_t *)b->h_result.p + result_out_off(), L.res + result_out_off(),
+                               np * (sizeof(PairOut) + (L.sub ? sizeof(SuboptOut) : 0)), hipMemcpyDeviceToHost, ctx->stream));
     } else if (L.split) {
         ta.win_off = b->d_win_off.as<uint32_t>();
         ta.q_count = b->d_queue.as<uint32_t>();
@@ -490,6 +504,7 @@ static int run_chunk(RunState &rs, const std::vector<Work> &work, size_t lo, siz
     L.zc = ctx->zero_copy != 0;
     L.sweep_only = ctx->scores_only != 0 && !cells_exact;
     L.time_all = ctx->profiling == 1;
+    L.sub = b->eff_mode == 3 && b->opt.modes.subopt != 0;
 
     const auto c0 = Clock::now();
     L.arena_cap = std::max<uint64_t>(np * ctx->arena_words_per_pair, 1024);
@@ -498,7 +513,7 @@ static int run_chunk(RunState &rs, const std::vector<Work> &work, size_t lo, siz
     for (L.attempt = 0;; L.attempt++) {
         // (an overflow that growing cannot cure -- a path longer than the staging area -- must not retry for ever)
         if (L.attempt > 4) return fail(SWMI_ERR_HIP, "the record arena overflowed %d times in a row; results discarded", L.attempt);
-        L.t_off = result_tab_off(np); L.a_off = result_arena_off(np, L.tab_cap);
+        L.t_off = result_tab_off(np, L.sub); L.a_off = result_arena_off(np, L.tab_cap, L.sub);
         if ((rc = b->d_result.reserve(L.a_off + L.arena_cap * 4))) return rc;
         L.res = b->d_result.as<uint8_t>();
         if (L.attempt > 0) {         // (on the first attempt the fill kernel zeroes the arena header itself)
@@ -541,6 +556,12 @@ static int run_chunk(RunState &rs, const std::vector<Work> &work, size_t lo, siz
         if (rs.ta.dbg && (rc = dump_traceback_diagnostics(b, rs.ta, np, plan.n_tf))) return rc;
         if (rs.fa.dbg && L.attempt == 0 && (rc = dump_fill_diagnostics(b, rs.fa, np))) return rc;
         if (L.attempt == 0 && (rc = fetch_windows(b, work, lo))) return rc;      // (the workspace survives an arena-overflow retry)
+        if (L.sub) {
+            // option "subopt": the launch's (score2, end2), in the host block by now -- written there by the kernel (zero-copy) or
+            // part of the D2H copy.  The exact-size re-run of a pair computes the same values and overwrites them.
+            const SuboptOut *hs = (const SuboptOut *)((const uint8_t *)b->h_result.p + result_sub_off(np));
+            for (size_t k = 0; k < np; k++) b->sub[work[lo + k].pair] = hs[k];
+        }
         if (L.sweep_only) { collect_scores(b, work, L, outs); return SWMI_OK; }
         bool retry;
         if ((rc = collect_launch(rs, L, c2, saved_outs, outs, retry)) || !retry) return rc;
@@ -613,6 +634,10 @@ static int check_band(const swmi_ctx *ctx, const swmi_batch *b, const swmi_param
 static int check_run_params(const swmi_ctx *ctx, const swmi_batch *b, const swmi_params *p, bool affine, const RunOptions &opt) {
     const RunModes &md = opt.modes;
     const ScoreMatrix *mat = opt.mat.get();
+    // option "subopt": the second-best score is defined, and built, for local runs -- which also rules out extend, xdrop, band_adapt
+    // and gap_open2, options of a global run
+    if (md.subopt != 0 && md.align_mode != SWMI_ALIGN_LOCAL)
+        return fail(SWMI_ERR_UNSUPPORTED, "subopt = %d needs align_mode local (0), got align_mode %d", md.subopt, md.align_mode);
     if (p->tie_mode != SWMI_TIE_SERIAL && p->tie_mode != SWMI_TIE_STRICT)
         return fail(SWMI_ERR_INVALID, "unknown tie_mode %d", p->tie_mode);
     // GetAlignment tests `align == alignTypes[0]`, then `== alignTypes[1]`, else deletion
@@ -878,9 +903,9 @@ static int batch_run(swmi_ctx *ctx, swmi_batch *b, const swmi_params *p, RunOpti
     if (!ctx || !b || !p) return fail(SWMI_ERR_INVALID, "null argument");
     std::lock_guard<std::mutex> g(ctx->mu);
     // (a score matrix and the end-to-end modes run on the affine kernels only)
-    // (... and so do a band and a CIGAR payload)
+    // (... and so do a band, a CIGAR payload and the second-best score)
     const bool affine = ctx->affine == 1 || ctx->gap_open != 0 || opt.mat != nullptr || opt.modes.align_mode != SWMI_ALIGN_LOCAL || opt.modes.band > 0 ||
-                        opt.modes.cigar != 0;
+                        opt.modes.cigar != 0 || opt.modes.subopt != 0;
     int rc;
     if ((rc = check_run_params(ctx, b, p, affine, opt))) return rc;
     static const bool host_dbg = getenv("SWMI_DEBUG_HOST") != nullptr;
@@ -896,6 +921,8 @@ static int batch_run(swmi_ctx *ctx, swmi_batch *b, const swmi_params *p, RunOpti
     const uint32_t n_refs = b->paired ? 0u : b->n_refs;     // (the references MapRef views exist for: none of a pair list)
     b->pairs.assign(batch_n_pairs(b), PairRes{});
     b->win_tab.clear(); b->win_at.clear();
+    b->has_sub = opt.modes.subopt != 0;
+    b->sub.assign(b->has_sub ? batch_n_pairs(b) : 0, SuboptOut{0, 0u});     // (a pair with an empty side is never swept: (0, 0))
     b->alns.clear(); b->str_at.clear();
     b->raw.clear(); b->rtab.clear(); b->raw_chunks.clear(); b->indexed = false;
     b->raw_ext = nullptr; b->rtab_ext = nullptr;

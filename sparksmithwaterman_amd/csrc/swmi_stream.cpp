@@ -96,6 +96,9 @@ static int stream_process(swmi_stream *s, swmi_stream::Slot &sl, StreamChunk *c)
     r->opt.modes = b->opt.modes;
     r->win_tab = std::move(b->win_tab); r->win_at = std::move(b->win_at);
     b->win_tab.clear(); b->win_at.clear();
+    // (option "subopt": every pair's second-best score, kept whether or not the records are)
+    r->has_sub = b->has_sub; r->sub = std::move(b->sub);
+    b->has_sub = false; b->sub.clear();
     if (s->keep_records) {
         (void)settle_raw(b);
         r->raw = std::move(b->raw);
