@@ -59,6 +59,10 @@ public class GpuSmithWaterman
 	static native void nativeSetSubopt( long ctx , int subopt ) ;
 	/** { second-best score , the reference column it ends in } of a pair after a run under that option */
 	static native int[] nativePairSubopt( long batch , long pair ) ;
+	/** the end bonus of extend runs: 1 .. 2^30 the bonus, 0 off (include/swmi.h: option "end_bonus") */
+	static native void nativeSetEndBonus( long ctx , int endBonus ) ;
+	/** { max score , to-end score , the reference column it ends in , taken to the end ? 1 : 0 } of a pair after a run under that option */
+	static native int[] nativePairEndScore( long batch , long pair ) ;
 	/** substitution scores on the context: alphabet = n ISO-8859-1 symbols, scores = n * n, row = read base; null clears */
 	static native void nativeSetScoreMatrix( long ctx , byte[] alphabet , int[] scores ) ;
 	/** a pair list over the sequences: specs = eight ints per pair ( alignPairs ) */
@@ -199,6 +203,23 @@ public class GpuSmithWaterman
 	/** { second-best score , the reference column it ends in } of a pair of a native batch run under setSubopt ( { 0 , 0 }: none ) */
 	static int[] subopt( long batch , long pair ) { return nativePairSubopt( batch , pair ) ; }
 
+	/** the end bonus every context asks its extend runs for, 0: none (applied next to subopt, before every batch) */
+	private static volatile int END_BONUS = 0 ;
+
+	/**
+	 * b in 1 .. 2^30: an extend run also computes every pair's best score in the read's last row and takes the pair to the end of
+	 * the read when that is less than b below the best score anywhere (strictly: toEnd + b > best); 0 (the default): off.  Needs an
+	 * extend run without xdrop, band_adapt or two-piece gaps.  For every batch aligned from now on, on every executor thread.
+	 */
+	public static void setEndBonus( int b )
+	{
+		if( b < 0 || b > ( 1 << 30 ) ) throw new IllegalArgumentException( "endBonus must be 0 or 1 .. 2^30: " + b ) ;
+		END_BONUS = b ;
+	}
+
+	/** { max score , to-end score , its reference column , taken to the end ? 1 : 0 } of a pair of a native batch run under setEndBonus */
+	static int[] endScore( long batch , long pair ) { return nativePairEndScore( batch , pair ) ; }
+
 	/** the score matrix every context applies before its next batch: { alphabet , scores } (null: none), and its version */
 	private static volatile Object[] MATRIX = null ;
 	private static final java.util.concurrent.atomic.AtomicLong MATRIX_VERSION = new java.util.concurrent.atomic.AtomicLong() ;
@@ -306,6 +327,7 @@ public class GpuSmithWaterman
 		nativeSetBandAdapt( ctx , BAND_ADAPT ? 1 : 0 ) ;
 		nativeSetCigar( ctx , CIGAR ) ;
 		nativeSetSubopt( ctx , SUBOPT ) ;
+		nativeSetEndBonus( ctx , END_BONUS ) ;
 		applyScoreMatrix( nc ) ;
 	}
 

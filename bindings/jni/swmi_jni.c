@@ -123,6 +123,31 @@ JNIEXPORT jintArray JNICALL Java_sw_GpuSmithWaterman_nativePairSubopt(JNIEnv *en
     return res;
 }
 
+/* the end bonus of extend runs on this context from now on: 1 .. 2^30 the bonus, 0 off */
+JNIEXPORT void JNICALL Java_sw_GpuSmithWaterman_nativeSetEndBonus(JNIEnv *env, jclass cls, jlong ctx, jint end_bonus) {
+    char err[640];
+    (void)cls;
+    if (swmi_shim_set_end_bonus((swmi_ctx *)(intptr_t)ctx, end_bonus, err, sizeof err) != SWMI_OK) throw_msg(env, err);
+}
+
+/* { max_score, end_score, end_col, taken to the end ? 1 : 0 } of a pair after a run under option "end_bonus" */
+JNIEXPORT jintArray JNICALL Java_sw_GpuSmithWaterman_nativePairEndScore(JNIEnv *env, jclass cls, jlong batch, jlong pair) {
+    char err[640];
+    int32_t out[4] = {0, 0, 0, 0};
+    jint jo[4];
+    jintArray res;
+    (void)cls;
+    if (swmi_shim_pair_end_score((const swmi_batch *)(intptr_t)batch, pair, out, err, sizeof err) != SWMI_OK) {
+        throw_msg(env, err);
+        return NULL;
+    }
+    res = (*env)->NewIntArray(env, 4);
+    if (!res) return NULL;
+    jo[0] = out[0]; jo[1] = out[1]; jo[2] = out[2]; jo[3] = out[3];
+    (*env)->SetIntArrayRegion(env, res, 0, 4, jo);
+    return res;
+}
+
 /* two-piece gaps on this context from now on: gapOpen2 != 0 on, 0 off */
 JNIEXPORT void JNICALL Java_sw_GpuSmithWaterman_nativeSetGap2(JNIEnv *env, jclass cls, jlong ctx, jint gap_open2, jint gap2) {
     char err[640];

@@ -115,6 +115,28 @@ int swmi_shim_pair_subopt(const swmi_batch *b, int64_t pair, int32_t out[2], cha
     return SWMI_OK;
 }
 
+int swmi_shim_set_end_bonus(swmi_ctx *ctx, int32_t end_bonus, char *err, size_t err_len) {
+    int rc;
+    if (!ctx) return shim_fail(SWMI_ERR_INVALID, err, err_len, "nativeSetEndBonus", "context handle is 0");
+    if ((rc = swmi_set_option(ctx, "end_bonus", end_bonus)) != SWMI_OK)
+        return shim_fail(rc, err, err_len, "nativeSetEndBonus", swmi_last_error());
+    return SWMI_OK;
+}
+
+int swmi_shim_pair_end_score(const swmi_batch *b, int64_t pair, int32_t out[4], char *err, size_t err_len) {
+    int32_t ms = 0, es = 0;
+    uint32_t ec = 0, flags = 0;
+    uint64_t na = 0;
+    int rc;
+    if (pair < 0) return shim_fail(SWMI_ERR_RANGE, err, err_len, "nativePairEndScore", "negative index");
+    rc = swmi_pair_end_score(b, (uint64_t)pair, &ms, &es, &ec);
+    if (rc != SWMI_OK) return shim_fail(rc, err, err_len, "swmi_pair_end_score", swmi_last_error());
+    rc = swmi_pair_n_alignments(b, (uint64_t)pair, &na, &flags);
+    if (rc != SWMI_OK) return shim_fail(rc, err, err_len, "swmi_pair_n_alignments", swmi_last_error());
+    if (out) { out[0] = ms; out[1] = es; out[2] = (int32_t)ec; out[3] = (flags & SWMI_PAIR_TO_END) ? 1 : 0; }      /* (a column is below 2^30) */
+    return SWMI_OK;
+}
+
 int swmi_shim_pair_cigar(swmi_batch *b, int64_t pair, int64_t k, int32_t *begin, int32_t cell[2], const uint32_t **cigar,
                          uint32_t *n_cigar, uint32_t *nm, char *err, size_t err_len) {
     int32_t ei = 0, ej = 0;

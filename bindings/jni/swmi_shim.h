@@ -92,6 +92,14 @@ int swmi_shim_pair_cigar(swmi_batch *b, int64_t pair, int64_t k, int32_t *begin,
 int swmi_shim_set_subopt(swmi_ctx *ctx, int32_t subopt, char *err, size_t err_len);
 int swmi_shim_pair_subopt(const swmi_batch *b, int64_t pair, int32_t out[2], char *err, size_t err_len);
 
+/* nativeSetEndBonus: from then on an extend run also returns every pair's best score in the read's last row and takes the pair to the
+ * read's end when that is less than the bonus below the best score (swmi_set_option "end_bonus"): 1 .. 2^30 = the bonus, 0 (the
+ * default): off.  Any other value is SWMI_ERR_INVALID and leaves the context as it was.
+ * nativePairEndScore: out[0..3] = the pair's max_score, end_score and end_col after a run under that option, as swmi_pair_end_score
+ * hands them out, and 1 if the pair was taken to the end (SWMI_PAIR_TO_END), else 0. */
+int swmi_shim_set_end_bonus(swmi_ctx *ctx, int32_t end_bonus, char *err, size_t err_len);
+int swmi_shim_pair_end_score(const swmi_batch *b, int64_t pair, int32_t out[4], char *err, size_t err_len);
+
 /* nativeSetScoreMatrix: a substitution score matrix on this context (swmi_set_score_matrix): `alphabet` = n symbols narrowed to
  * bytes (ISO-8859-1), `scores` = n * n entries, row = read base, column = reference base (n_scores must be n * n).  n = 0 clears
  * it.  Applies to the batches the context aligns from then on (on the affine kernels). */

@@ -298,6 +298,28 @@ void        swmi_default_params(swmi_params *p);
  *                unchanged, and every other accessor returns what the same run with subopt = 0 returns.  The sweep keeps one row of n
  *                int32 column maxima per pair behind the pair's direction field (charged to max_workspace_bytes with it).  A run
  *                (async runs and stream slots included) takes the value set when it was asked for.
+ * end_bonus (default 0 = off and no change; 1 .. 2^30 = the bonus b; any other value is SWMI_ERR_INVALID and leaves the context as
+ *                it was): an extend run (align_mode global, extend = 1) also returns, per pair, the best score of an extension that
+ *                reaches the END OF THE READ, and takes that extension when it is less than b worse than the best one anywhere
+ *                (BWA-MEM's gscore / pen_clip, ksw2's mqe / minimap2's end_bonus: no soft clip for one mismatch near the read's end).
+ *                For a pair with both sides non-empty: max_score = the maximum of H(i, j) over the existing cells, the score of the
+ *                run without the option; end_score = the maximum of H(m, j) over the existing cells of read row m (under band the
+ *                columns of the last strip's window of a long read, else 1 .. n; no window is empty, so the row has a cell;
+ *                end_score may be <= 0); end_col = the smallest (1-based) column that holds end_score.  The pair is taken TO THE END
+ *                iff (int64) end_score + b > (int64) max_score -- strict, minimap2's rule and BWA-MEM's gscore > max - pen_clip.  A
+ *                pair taken to the end has the score end_score, exactly one maximum cell (m, end_col) and one alignment, the global
+ *                walk from that cell: it spells the whole read and ref[:end_col], begin = 1, end_i = m, end_j = end_col; and
+ *                SWMI_PAIR_TO_END is set in the flags of swmi_pair_n_alignments.  One cell is listed, not every tied column, so the
+ *                exact-size re-run never applies to such a pair.  A pair not taken returns exactly what the run without the option
+ *                returns: score, tied cells in extend's order, flags 0, cell_cap and the re-run.  A pair with an empty side gives
+ *                score 0, no alignments and (0, 0, 0).  swmi_pair_end_score reads the three values, max_score whether or not the pair
+ *                was taken.  Scope: one-piece extend runs, reads of every length (long_reads, with and without band), with and
+ *                without a score matrix, both tie modes; scores_only, cigar, device_strings, zero_copy, cell_cap,
+ *                max_workspace_bytes, pair lists and streams apply unchanged.  end_bonus != 0 on a run that is not an extend run
+ *                (the linear pipeline included), or with xdrop > 0, band_adapt = 1 or gap_open2 != 0, is SWMI_ERR_UNSUPPORTED before
+ *                anything is launched.  The bounds are extend's, unchanged: the comparison is made in 64 bits and no new sum is formed
+ *                in int32.  A run (async runs and stream slots included) takes the value set when it was asked for (DESIGN.md
+ *                section 8o).
  * Further knobs: spin_us (how long a run polls its stream before it blocks, default 2000); col_chunks (0 automatic,
  * 1 never, N > 1 force up to N column chunks per pair: a launch of few pairs with long references is swept by several
  * wavefronts per pair -- a read of more than 256 rows by several strip pipelines); debug_strip_spins / debug_reverse_strips (tests of the strip pipeline's give-up path);
@@ -392,6 +414,8 @@ int  swmi_batch_mode(const swmi_batch *b, int *mode);
 /* ---- results of the last run (host memory owned by the batch) ------------------- */
 #define SWMI_PAIR_DEGENERATE 0x1u   /* max score 0: every one of the m*n cells is a "max cell" and
                                        yields (0,"","") -- SmithWaterman.java:154,182-185,378-380 */
+#define SWMI_PAIR_TO_END     0x2u   /* option "end_bonus": the pair was taken to the read's end -- its score is end_score and its one
+                                       alignment ends at (m, end_col) */
 uint64_t swmi_batch_n_pairs(const swmi_batch *b);
 int      swmi_pair_score(const swmi_batch *b, uint64_t pair, int32_t *score);
 int      swmi_pair_n_alignments(const swmi_batch *b, uint64_t pair, uint64_t *n, uint32_t *flags);
@@ -435,6 +459,15 @@ int      swmi_pair_cigar(swmi_batch *b, uint64_t pair, uint64_t k,
 int      swmi_pair_subopt(const swmi_batch *b, uint64_t pair, int32_t *score2, uint32_t *end2);
 /* all pairs at once: score2[n] and/or end2[n] (either may be NULL), n = swmi_batch_n_pairs */
 int      swmi_batch_pair_subopt(const swmi_batch *b, int32_t *score2, uint32_t *end2, uint64_t n);
+
+/* Option "end_bonus": the pair's max_score, end_score and end_col as that option defines them -- the best score anywhere (reported
+ * whether or not the pair was taken to the end: a caller needs it to undo the choice), the best score in read row m and the
+ * smallest (1-based) reference column that holds it; (0, 0, 0) for a pair with an empty side.  Every pointer may be NULL.  Works
+ * under scores_only = 1 and on a stream's chunk batches; on a pair list end_col is in the segment's coordinates.  A batch whose
+ * last run had end_bonus = 0: SWMI_ERR_UNSUPPORTED; a pair out of range: SWMI_ERR_RANGE. */
+int      swmi_pair_end_score(const swmi_batch *b, uint64_t pair, int32_t *max_score, int32_t *end_score, uint32_t *end_col);
+/* all pairs at once: max_score[n], end_score[n] and/or end_col[n] (each may be NULL), n = swmi_batch_n_pairs */
+int      swmi_batch_pair_end_scores(const swmi_batch *b, int32_t *max_score, int32_t *end_score, uint32_t *end_col, uint64_t n);
 
 /* Builds the record index and both strings of EVERY alignment of the batch in one native call (what a caller that
  * consumes all of OptAlignments' output pays); returns the number of alignments (degenerate pairs count m*n) and

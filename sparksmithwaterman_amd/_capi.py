@@ -20,7 +20,9 @@ XDROP_MAX = (1 << 31) - 1   # option "xdrop": the largest threshold (0: off)
 CIGAR_M, CIGAR_I, CIGAR_D, CIGAR_EQ, CIGAR_X = 0, 1, 2, 7, 8     # option "cigar": the op of an entry  len << 4 | op  (BAM's)
 CIGAR_CHARS = {CIGAR_M: "M", CIGAR_I: "I", CIGAR_D: "D", CIGAR_EQ: "=", CIGAR_X: "X"}
 SUBOPT_AUTO = -1     # option "subopt": the mask half-width per pair, max(m // 2, 15) (0: off; 1 .. 2^30: the half-width)
+END_BONUS_MAX = 1 << 30     # option "end_bonus": the largest bonus (0: off)
 PAIR_DEGENERATE = 0x1
+PAIR_TO_END = 0x2           # option "end_bonus": the pair was taken to the read's end (flags of swmi_pair_n_alignments)
 SPEC_REVERSE = 0x1          # swmi_pair_spec.flags: both segments in reverse byte order (left extension)
 SPEC_WHOLE = 0xFFFFFFFF     # as ref_len / read_len: from the start given to the end of the source
 ERR_INVALID = -1
@@ -95,6 +97,8 @@ SYMBOLS = [
     ("swmi_batch_pair_results", C.c_int, [_P, C.POINTER(C.c_int32), _u64p, C.c_uint64]),
     ("swmi_pair_subopt", C.c_int, [_P, C.c_uint64, C.POINTER(C.c_int32), C.POINTER(C.c_uint32)]),
     ("swmi_batch_pair_subopt", C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.c_uint64]),
+    ("swmi_pair_end_score", C.c_int, [_P, C.c_uint64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_uint32)]),
+    ("swmi_batch_pair_end_scores", C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.c_uint64]),
     ("swmi_batch_materialise_all", C.c_int, [_P, _u64p, _u64p]),
     ("swmi_ref_total", C.c_int, [_P, C.c_uint32, C.POINTER(C.c_int32)]),
     ("swmi_ref_totals", C.c_int, [_P, C.POINTER(C.c_int32), C.c_uint32]),

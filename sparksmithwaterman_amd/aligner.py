@@ -289,6 +289,27 @@ class Batch:
                                                e2.ctypes.data_as(C.POINTER(C.c_uint32)), n))
         return s2, e2
 
+    def end_score(self, pair):
+        """(max_score, end_score, end_col) after an extend run under option "end_bonus": the pair's best score anywhere (whether or
+        not the pair was taken to the end), its best score in the read's last row and the smallest 1-based reference column that holds
+        it (on a pair list: of the segment; PairBatch.to_source maps it); (0, 0, 0) for a pair with an empty side.  The flags of
+        n_alignments carry PAIR_TO_END for a pair that was taken.  Works after a scores_only run.  SwmiError (SWMI_ERR_UNSUPPORTED)
+        after a run with end_bonus = 0."""
+        ms, es, ec = C.c_int32(), C.c_int32(), C.c_uint32()
+        check(self._lib.swmi_pair_end_score(self._h, pair, C.byref(ms), C.byref(es), C.byref(ec)))
+        return ms.value, es.value, ec.value
+
+    def end_scores(self):
+        """(max_scores int32[n_pairs], end_scores int32[n_pairs], end_cols uint32[n_pairs]) as numpy arrays, one native call."""
+        import numpy as np
+        n = self.n_pairs()
+        ms = np.empty(n, dtype=np.int32)
+        es = np.empty(n, dtype=np.int32)
+        ec = np.empty(n, dtype=np.uint32)
+        check(self._lib.swmi_batch_pair_end_scores(self._h, ms.ctypes.data_as(C.POINTER(C.c_int32)), es.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                   ec.ctypes.data_as(C.POINTER(C.c_uint32)), n))
+        return ms, es, ec
+
     def materialise_all(self):
         """Index the records and build every alignment string natively; returns (n_alignments, n_chars)."""
         na, nc = C.c_uint64(), C.c_uint64()

@@ -80,7 +80,11 @@
 //   column maximum rides down the wave with its column, and the lane that finishes a column leaves colmax(j) in a row of n int32
 //   behind the pair's fields; sw_subopt_kernel (swmi_subopt.hip) turns the row into the pair's second-best score and its end column.
 //
-// How the 69 kernels are made: the 56 sweeps are aff_sweep_entry<RLO, RHI, MATRIX, MODE, LONG, BAND, XDROP, ADAPT, TWO, SUBOPT> over one block function
+// sw_affine_sweep_[long_|band_]endb[_matrix][_wide]_kernel: the extend sweeps under option "end_bonus" (DESIGN.md 8o), ENDB = 1: the lane
+//   that owns read row m keeps the maximum of H(m, j) and its smallest column, and the wave chooses between the best cell anywhere
+//   and the best extension that reaches the read's end where it writes the pair's PairOut.
+//
+// How the 77 kernels are made: the 64 sweeps are aff_sweep_entry<RLO, RHI, MATRIX, MODE, LONG, BAND, XDROP, ADAPT, TWO, SUBOPT, ENDB> over one block function
 //   (aff_block8); the 13 tracebacks are aff_traceback<MODE, LONG, BAND, ADAPT, TWO>, where !LONG is the walk with one strip and !BAND the
 //   walk whose windows are the whole reference.  One macro defines the sweeps, one the tracebacks; the launchers take the
 //   run's options as one AffRun (swmi_launch.h) and pick a kernel from tables typed by signature.  The per-pair sweep is two thin bodies, aff_sweep_pair and aff_sweep_long_pair<.., BAND> (the one strip
@@ -129,6 +133,8 @@ struct AffSeam {
     int cm;                // lanes 0..7: the column maxima the strips above left at the 8 columns lane 0 takes in this block (strip 0, short reads: not read)
     int *cmrow;            // the pair's row of column maxima, from the window's first column on
     uint32_t cmlane;       // the lane that holds a column's finished maximum and stores it: 63 in a strip, the owner of the read's last row in a short sweep
+    // ENDB (option "end_bonus"; the short sweeps use it too)
+    uint32_t elane;        // the lane that owns read row m: (m - 1) / R in a short sweep, the last strip's (m - 1 - 1024 sx) / 16; no lane (0xFFFFFFFF) in the strips above
 };
 
 template <int R>
@@ -146,6 +152,8 @@ struct AffState {
     uint32_t acc2[R];
     int f2_last;
     int cm;                // SUBOPT: the running maximum of H over the lane's current column, rows 1 .. the lane's last (it travels with the column)
+    int eg;                // ENDB: in the lane that owns read row m, the maximum of H(m, j) over the columns it has swept (INT32_MIN before the first)
+    uint32_t egc;          // ... and the smallest (global, 1-based) column that holds it
 };
 
 // 8 anti-diagonal steps t0 .. t0+7 (a lane outside its column range keeps its state).  The steps are a loop, not unrolled:
@@ -168,7 +176,12 @@ struct AffState {
 //   lane's rows inside the read at this column (-1 when it has none, or no column).  The move runs every step in every lane.  Lane 0
 //   starts a column at 0 (H >= 0) or, in strips 1.., at what the strips above left (Z.cm, loaded as Z.h is).  Lane Z.cmlane holds the
 //   finished maximum and stores it into the pair's row, a plain vector store.
-template <int R, bool STRICT, bool MATRIX, int MODE, bool LONG = false, bool BAND = false, bool TWO = false, bool SUBOPT = false>
+// ENDB (option "end_bonus", extend runs): read row m is slot vrows - 1 of lane Z.elane (vrows is local mode's, so a pad row
+//   never owns it).  At every step with a cell that lane takes H of that slot and the column when it is strictly greater than S.eg:
+//   its columns ascend, so S.egc ends as the smallest column that holds the maximum.  The slot is picked inside the unrolled row loop,
+//   as the k == vrows test of fit mode is -- by the test k < vrows that mrow already makes, the last slot that passes it, so that no
+//   further compare mask per row is kept in SGPRs: S.h is never indexed by a run-time value.
+template <int R, bool STRICT, bool MATRIX, int MODE, bool LONG = false, bool BAND = false, bool TWO = false, bool SUBOPT = false, bool ENDB = false>
 __device__ __forceinline__ void aff_block8(AffState<R> &S, const uint2 rw, const uint32_t t0, const uint32_t lane,
                                            const uint32_t n, const uint32_t row0, const uint32_t vrows,
                                            const int o, const int e, const int vmat, const int vmis,
@@ -176,6 +189,7 @@ __device__ __forceinline__ void aff_block8(AffState<R> &S, const uint2 rw, const
                                            const int o2 = 0, const int e2 = 0) {
     static_assert(!TWO || (AFF_ROW0_GAPS(MODE) && !MATRIX), "two-piece gaps: global and extend runs without a score matrix");
     static_assert(!SUBOPT || MODE == AFF_LOCAL, "subopt: local runs");
+    static_assert(!ENDB || (MODE == AFF_EXTEND && !TWO && !SUBOPT), "end_bonus: one-piece extend runs");
     const int oe = o + e;
     const int oe2 = o2 + e2;                                     // (TWO)
 #pragma unroll 1
@@ -209,6 +223,7 @@ __device__ __forceinline__ void aff_block8(AffState<R> &S, const uint2 rw, const
         if (inr) {
             int diag = S.nh_prev, up = nh, fup = nf;
             int fup2 = nf2;                                      // (TWO)
+            int hend = INT32_MIN;                                // (ENDB) H of the lane's last row inside the read
             uint32_t sh = 4u * s;
             const uint32_t rkey = (uint32_t)S.rb, rlo = rkey & 0xFFFFu;
 #pragma unroll
@@ -270,6 +285,10 @@ __device__ __forceinline__ void aff_block8(AffState<R> &S, const uint2 rw, const
                 S.e[k] = en;
                 if constexpr (!AFF_ROW_M_ONLY(MODE)) { if ((uint32_t)k < vrows) mrow = max(mrow, hv); }
                 else                                 { if ((uint32_t)k == vrows) mrow = hv; }
+                if constexpr (ENDB) { if ((uint32_t)k < vrows) hend = hv; }      // (the test of mrow: the last slot that passes it is vrows - 1)
+            }
+            if constexpr (ENDB) {
+                if (lane == Z.elane && hend > S.eg) { S.eg = hend; S.egc = c0 + 1u + (BAND ? Z.coff : 0u); }
             }
             S.f_last = fup;
             if constexpr (TWO) S.f2_last = fup2;
@@ -387,12 +406,42 @@ __device__ __forceinline__ AffCells aff_cell_list(const FillArgs &A, const PairD
         }                                                                                                     \
         A.out[pd.out_id] = po;                                                                                \
     }
+// AFF_PAIR_OUT_ENDB(ELANE) (lane, pd, m, cells, ccap, endb): the pair's PairOut under option "end_bonus" (DESIGN.md 8o), and its entry of
+//   the launch's EndOut array, which lies behind the A.n_out pair outputs.  ELANE (wave-uniform) owns read row m: its (S.eg, S.egc)
+//   are (end_score, end_col) -- it has swept at least one column of the row, no window being empty.  The pair is taken to the end iff
+//   end_score + endb > max_score, in 64 bits; lane 0 then names (m, end_col) as the pair's one cell.  Every store of the wave's cell
+//   list comes before that store in program order, and the wait puts them in memory first: another lane may have written entry 0.
+//   A pair that is not taken leaves what AFF_PAIR_OUT leaves (an extend run has no degenerate case).
+#define AFF_PAIR_OUT_ENDB(ELANE)                                                                              \
+    {                                                                                                         \
+        const int eg = __builtin_amdgcn_readlane(S.eg, (int)(ELANE));                                         \
+        const uint32_t egc = (uint32_t)__builtin_amdgcn_readlane((int)S.egc, (int)(ELANE));                   \
+        if (lane == 0) {                                                                                      \
+            PairOut po;                                                                                       \
+            EndOut eo;                                                                                        \
+            eo.max_score = S.thr; eo.end_score = eg; eo.end_col = egc;                                        \
+            if ((int64_t)eg + (int64_t)endb > (int64_t)S.thr) {                                               \
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");                                            \
+                cells[0] = make_uint2(m, egc);                                                                \
+                po.score = eg;                                                                                \
+                po.flags = SWMI_F_TO_END;                                                                     \
+                po.n_cells = 1ull;                                                                            \
+            } else {                                                                                          \
+                po.score = S.thr;                                                                             \
+                po.flags = S.cnt > ccap ? SWMI_F_CELL_OVF : 0u;                                               \
+                po.n_cells = S.cnt;                                                                           \
+            }                                                                                                 \
+            A.out[pd.out_id] = po;                                                                            \
+            reinterpret_cast<EndOut *>(A.out + A.n_out)[pd.out_id] = eo;                                      \
+        }                                                                                                     \
+    }
 
 // SUBOPT: the row of column maxima lies behind the field; the lane that owns the read's last row, lact - 1 of swmi_aff_blocks, stores
 // it -- W is sized for that lane to reach column n
-template <int R, bool STRICT, bool MATRIX, int MODE, bool TWO = false, bool SUBOPT = false>
+// ENDB: the bonus endb of option "end_bonus"; the lane that owns read row m tracks it, and the choice is made with the PairOut
+template <int R, bool STRICT, bool MATRIX, int MODE, bool TWO = false, bool SUBOPT = false, bool ENDB = false>
 __device__ __forceinline__ void aff_sweep_pair(const FillArgs &A, const int o, const PairDesc pd, const uint32_t lane, const uint32_t nn,
-                                               const int o2 = 0, const int e2 = 0) {
+                                               const int o2 = 0, const int e2 = 0, const uint32_t endb = 0u) {
     const SeqDesc rd = A.refs[pd.ref_id];
     const SeqDesc qd = A.reads[pd.read_id];
     const uint32_t n = rd.len, m = qd.len;
@@ -417,6 +466,10 @@ __device__ __forceinline__ void aff_sweep_pair(const FillArgs &A, const int o, c
         Zs.cmrow = reinterpret_cast<int *>(dir + (uint64_t)W * R * WAVE);
         Zs.cmlane = (m + (uint32_t)R - 1u) / (uint32_t)R - 1u;
     }
+    if constexpr (ENDB) {
+        S.eg = INT32_MIN; S.egc = 0u;
+        Zs.elane = uni((m - 1u) / (uint32_t)R);
+    }
     for (uint32_t w = 0; w < W; ++w) {
         const uint32_t t0 = 8u * w;
         // lane 0's 8 reference bases (images are padded: the last block may read past the end)
@@ -430,10 +483,14 @@ __device__ __forceinline__ void aff_sweep_pair(const FillArgs &A, const int o, c
                                                                     AffSeam{}, o2, e2);
         } else if constexpr (SUBOPT)
         aff_block8<R, STRICT, MATRIX, MODE, false, false, false, true>(S, rw, t0, lane, n, row0, vrows, o, A.gap, A.match, A.mismatch, cells, ccap, Zs);
+        else if constexpr (ENDB)
+        aff_block8<R, STRICT, MATRIX, MODE, false, false, false, false, true>(S, rw, t0, lane, n, row0, vrows, o, A.gap, A.match, A.mismatch, cells, ccap, Zs);
         else
         aff_block8<R, STRICT, MATRIX, MODE>(S, rw, t0, lane, n, row0, vrows, o, A.gap, A.match, A.mismatch, cells, ccap);
         AFF_STORE_BLOCK
     }
+    if constexpr (ENDB) AFF_PAIR_OUT_ENDB(Zs.elane)
+    else
     AFF_PAIR_OUT((uint64_t)m * n, 0u)
 }
 
@@ -490,12 +547,17 @@ __device__ __forceinline__ void aff_sweep_pair(const FillArgs &A, const int o, c
 //   stores in EVERY strip, the last one too.  The row is indexed by the global column: under BAND a column left of a later strip's
 //   window keeps what the earlier strips left, and lane 0 starts a column the strips above never reached (beyond seam_end) at 0 --
 //   the words there were never written.  Columns right of the last window stay unwritten: readers stop at swmi_aff_colmax_cols.
-template <bool STRICT, bool MATRIX, int MODE, bool BAND, bool XDROP = false, bool ADAPT = false, bool TWO = false, bool SUBOPT = false>
+// ENDB (option "end_bonus", extend runs): read row m lies in the last strip alone, in lane (m - 1 - 1024 (NS - 1)) / 16; the
+//   strips above name no owner (Z.elane = 0xFFFFFFFF) and leave (S.eg, S.egc) as they were set before the first.  Under BAND the row's
+//   existing cells are the columns of the last strip's window, and the column kept is global (Z.coff).  Nothing is loaded or stored.
+template <bool STRICT, bool MATRIX, int MODE, bool BAND, bool XDROP = false, bool ADAPT = false, bool TWO = false, bool SUBOPT = false, bool ENDB = false>
 __device__ __forceinline__ void aff_sweep_long_pair(const FillArgs &A, const int o, const PairDesc pd, const uint32_t lane, const uint32_t nn,
-                                                    const uint32_t wb, const uint32_t xd = 0u, const int o2 = 0, const int e2 = 0) {
+                                                    const uint32_t wb, const uint32_t xd = 0u, const int o2 = 0, const int e2 = 0,
+                                                    const uint32_t endb = 0u) {
     static_assert(!ADAPT || (BAND && MODE == AFF_EXTEND), "band_adapt is an option of the banded strip sweeps of an extend run");
     static_assert(!TWO || (!XDROP && !ADAPT), "two-piece gaps: not under xdrop or band_adapt");
     static_assert(!SUBOPT || (MODE == AFF_LOCAL && !XDROP && !ADAPT && !TWO), "subopt: local runs");
+    static_assert(!ENDB || (MODE == AFF_EXTEND && !XDROP && !ADAPT && !TWO && !SUBOPT), "end_bonus: one-piece extend runs without xdrop or band_adapt");
     constexpr int R = SWMI_AFF_RMAX;
     constexpr int OUT = BAND && MODE != AFF_LOCAL ? SWMI_AFF_BAND_NEG : 0;
     const SeqDesc rd = A.refs[pd.ref_id];
@@ -526,6 +588,8 @@ __device__ __forceinline__ void aff_sweep_long_pair(const FillArgs &A, const int
 
     AffState<R> S;
     S.thr = MODE == AFF_LOCAL ? 1 : INT32_MIN; S.cnt = 0;       // (wave-uniform: they live on across the strips)
+    const uint32_t elast = ENDB ? uni((m - 1u - (NS - 1u) * SWMI_AFF_MAX_READ) / (uint32_t)R) : 0u;      // ENDB: the lane of the last strip that owns read row m
+    if constexpr (ENDB) { S.eg = INT32_MIN; S.egc = 0u; }
     for (uint32_t sx = 0; sx < NS; ++sx) {
         const uint32_t row0 = sx * SWMI_AFF_MAX_READ + lane * R;             // global index of the lane's first row, less 1
         const uint32_t vrows = aff_vrows<R, MODE>(m, row0);               // (row m is in the last strip)
@@ -595,6 +659,7 @@ __device__ __forceinline__ void aff_sweep_long_pair(const FillArgs &A, const int
             if constexpr (SUBOPT) Z.cmrow = cmbase + (clo - 1u);
         }
         Z.wlane = sx + 1u < NS ? 63u : 0xFFFFFFFFu;
+        if constexpr (ENDB) Z.elane = sx + 1u < NS ? 0xFFFFFFFFu : elast;
         if constexpr (!BAND) dir = A.dir + pd.dir_off + (uint64_t)sx * (TWO ? 2u : 1u) * swmi_aff_strip_words(n);
         if constexpr (ADAPT) dir = A.dir + pd.dir_off + (uint64_t)sx * astride;
         // the strip above has written its window of the seam row: its stores are in memory before this strip loads any of it
@@ -662,26 +727,29 @@ __device__ __forceinline__ void aff_sweep_long_pair(const FillArgs &A, const int
 #pragma unroll
                 for (int k = 0; k < R; ++k) S.acc2[k] = 0u;
             }
-            aff_block8<R, STRICT, MATRIX, MODE, true, BAND, TWO, SUBOPT>(S, rw, t0, lane, nw, row0, vrows, o, A.gap, A.match, A.mismatch, cells, ccap, Z, o2, e2);
+            aff_block8<R, STRICT, MATRIX, MODE, true, BAND, TWO, SUBOPT, ENDB>(S, rw, t0, lane, nw, row0, vrows, o, A.gap, A.match, A.mismatch, cells, ccap, Z, o2, e2);
             AFF_STORE_BLOCK
         }
         if constexpr (BAND && !ADAPT) dir += (uint64_t)W * (TWO ? 2 : 1) * R * WAVE;
         if constexpr (ADAPT) { plo = clo; phi = clo + nw - 1u; }
     }
+    if constexpr (ENDB) AFF_PAIR_OUT_ENDB(elast)
+    else
     AFF_PAIR_OUT(BAND ? inband : (uint64_t)m * n, XDROP ? stopped << SWMI_F_STRIPS_SHIFT : 0u)
 }
 
 #undef AFF_LOAD_ROWS
 #undef AFF_STORE_BLOCK
 #undef AFF_PAIR_OUT
+#undef AFF_PAIR_OUT_ENDB
 
 // RLO..RHI: the rows per lane this instantiation of the kernel takes (the others' registers would cap its occupancy)
-template <int RLO, int RHI, bool STRICT, bool MATRIX, int MODE, bool TWO = false, bool SUBOPT = false>
+template <int RLO, int RHI, bool STRICT, bool MATRIX, int MODE, bool TWO = false, bool SUBOPT = false, bool ENDB = false>
 __device__ __forceinline__ void aff_sweep_dispatch(const FillArgs &A, const int o, const PairDesc pd, const uint32_t R, const uint32_t lane,
-                                                   const uint32_t nn, const int o2 = 0, const int e2 = 0) {
+                                                   const uint32_t nn, const int o2 = 0, const int e2 = 0, const uint32_t endb = 0u) {
     if constexpr (RLO <= RHI) {
-        if (R == (uint32_t)RLO) aff_sweep_pair<RLO, STRICT, MATRIX, MODE, TWO, SUBOPT>(A, o, pd, lane, nn, o2, e2);
-        else aff_sweep_dispatch<RLO + 1, RHI, STRICT, MATRIX, MODE, TWO, SUBOPT>(A, o, pd, R, lane, nn, o2, e2);
+        if (R == (uint32_t)RLO) aff_sweep_pair<RLO, STRICT, MATRIX, MODE, TWO, SUBOPT, ENDB>(A, o, pd, lane, nn, o2, e2, endb);
+        else aff_sweep_dispatch<RLO + 1, RHI, STRICT, MATRIX, MODE, TWO, SUBOPT, ENDB>(A, o, pd, R, lane, nn, o2, e2, endb);
     }
 }
 
@@ -691,14 +759,17 @@ __device__ __forceinline__ void aff_sweep_dispatch(const FillArgs &A, const int 
 // ADAPT (with LONG, BAND and AFF_EXTEND): the banded strip sweep under option "band_adapt"
 // TWO (AFF_GLOBAL and AFF_EXTEND, no MATRIX, XDROP or ADAPT): two-piece gaps, the second piece's open o2 and extension e2
 // SUBOPT (AFF_LOCAL, no XDROP, ADAPT or TWO): the sweep also leaves the pair's row of column maxima (option "subopt")
+// ENDB (AFF_EXTEND, no XDROP, ADAPT, TWO or SUBOPT): the sweep also finds the best score in read row m and chooses (option "end_bonus", bonus endb)
 template <int RLO, int RHI, bool MATRIX, int MODE = AFF_LOCAL, bool LONG = false, bool BAND = false, bool XDROP = false, bool ADAPT = false,
-          bool TWO = false, bool SUBOPT = false>
+          bool TWO = false, bool SUBOPT = false, bool ENDB = false>
 __device__ __forceinline__ void aff_sweep_entry(const FillArgs &A, const int o, const uint32_t *__restrict__ mat, const uint32_t nn,
-                                                const uint32_t wb = 0u, const uint32_t xd = 0u, const int o2 = 0, const int e2 = 0) {
+                                                const uint32_t wb = 0u, const uint32_t xd = 0u, const int o2 = 0, const int e2 = 0,
+                                                const uint32_t endb = 0u) {
     static_assert(!TWO || (AFF_ROW0_GAPS(MODE) && !MATRIX && !XDROP && !ADAPT), "two-piece gaps: plain global and extend runs");
     static_assert(!XDROP || (LONG && MODE == AFF_EXTEND), "xdrop is an option of the strip sweeps of an extend run");
     static_assert(!ADAPT || (LONG && BAND && MODE == AFF_EXTEND), "band_adapt is an option of the banded strip sweeps of an extend run");
     static_assert(!SUBOPT || (MODE == AFF_LOCAL && !XDROP && !ADAPT && !TWO), "subopt is an option of the local sweeps");
+    static_assert(!ENDB || (MODE == AFF_EXTEND && !XDROP && !ADAPT && !TWO && !SUBOPT), "end_bonus is an option of the one-piece extend sweeps without xdrop or band_adapt");
     if (blockIdx.x == 0 && threadIdx.x == 0) A.hdr->reserved = 0ull;      // the traceback's bump allocator
     if (MATRIX) {                                                          // (before any wavefront leaves)
         for (uint32_t x = threadIdx.x; x < 256u; x += WAVE * AFF_WAVES) aff_mkey[x] = mat[x];
@@ -715,14 +786,14 @@ __device__ __forceinline__ void aff_sweep_entry(const FillArgs &A, const int o, 
     const PairDesc pd = A.pairs[pair];
     if constexpr (LONG) {
         if (uni(A.reads[pd.read_id].len) <= SWMI_AFF_MAX_READ) return;
-        if (A.strict) aff_sweep_long_pair<true, MATRIX, MODE, BAND, XDROP, ADAPT, TWO, SUBOPT>(A, o, pd, lane, nn, wb, xd, o2, e2);
-        else          aff_sweep_long_pair<false, MATRIX, MODE, BAND, XDROP, ADAPT, TWO, SUBOPT>(A, o, pd, lane, nn, wb, xd, o2, e2);
+        if (A.strict) aff_sweep_long_pair<true, MATRIX, MODE, BAND, XDROP, ADAPT, TWO, SUBOPT, ENDB>(A, o, pd, lane, nn, wb, xd, o2, e2, endb);
+        else          aff_sweep_long_pair<false, MATRIX, MODE, BAND, XDROP, ADAPT, TWO, SUBOPT, ENDB>(A, o, pd, lane, nn, wb, xd, o2, e2, endb);
         return;
     }
     const uint32_t R = uni(swmi_aff_rows_per_lane(A.reads[pd.read_id].len));
     if (R < (uint32_t)RLO || R > (uint32_t)RHI) return;
-    if (A.strict) aff_sweep_dispatch<RLO, RHI, true, MATRIX, MODE, TWO, SUBOPT>(A, o, pd, R, lane, nn, o2, e2);
-    else          aff_sweep_dispatch<RLO, RHI, false, MATRIX, MODE, TWO, SUBOPT>(A, o, pd, R, lane, nn, o2, e2);
+    if (A.strict) aff_sweep_dispatch<RLO, RHI, true, MATRIX, MODE, TWO, SUBOPT, ENDB>(A, o, pd, R, lane, nn, o2, e2, endb);
+    else          aff_sweep_dispatch<RLO, RHI, false, MATRIX, MODE, TWO, SUBOPT, ENDB>(A, o, pd, R, lane, nn, o2, e2, endb);
 }
 
 }  // namespace
@@ -808,6 +879,29 @@ AFF_SWEEPS_KERNEL(sw_affine_sweep_long_subopt_matrix_kernel, SWMI_AFF_RMAX, SWMI
 AFF_SWEEPS_KERNEL(sw_affine_sweep_band_subopt_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, true, 1)
 AFF_SWEEPS_KERNEL(sw_affine_sweep_band_subopt_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, true, 1)
 #undef AFF_SWEEPS_KERNEL
+// The 8 extend sweeps under option "end_bonus" (DESIGN.md 8o), ENDB = 1: narrow, wide, long and banded long, each plain and with a score
+// matrix, with the signatures of their ENDB = 0 twins and the bonus as one more scalar, the last.
+#define AFF_SWEEPE_KERNEL(name, RLO, RHI, MATRIX, LONG, BAND)                                                             \
+    extern "C" __global__ void __launch_bounds__(WAVE * AFF_WAVES) name(AFF_SWEEP_PARAMS_##MATRIX##BAND##0, const uint32_t end_bonus) { \
+        aff_sweep_entry<RLO, RHI, MATRIX != 0, AFF_EXTEND, LONG, BAND != 0, false, false, false, false, true>(AFF_SWEEPE_ARGS_##MATRIX##BAND, end_bonus); \
+    }
+#define AFF_SWEEPE_ARGS_00 A, gap_open, nullptr, 0u, 0u, 0u, 0, 0
+#define AFF_SWEEPE_ARGS_10 A, gap_open, mat, nn, 0u, 0u, 0, 0
+#define AFF_SWEEPE_ARGS_01 A, gap_open, nullptr, 0u, band, 0u, 0, 0
+#define AFF_SWEEPE_ARGS_11 A, gap_open, mat, nn, band, 0u, 0, 0
+AFF_SWEEPE_KERNEL(sw_affine_sweep_endb_kernel, 1, 4, 0, false, 0)
+AFF_SWEEPE_KERNEL(sw_affine_sweep_endb_wide_kernel, 5, SWMI_AFF_RMAX, 0, false, 0)
+AFF_SWEEPE_KERNEL(sw_affine_sweep_long_endb_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, true, 0)
+AFF_SWEEPE_KERNEL(sw_affine_sweep_endb_matrix_kernel, 1, 4, 1, false, 0)
+AFF_SWEEPE_KERNEL(sw_affine_sweep_endb_matrix_wide_kernel, 5, SWMI_AFF_RMAX, 1, false, 0)
+AFF_SWEEPE_KERNEL(sw_affine_sweep_long_endb_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, true, 0)
+AFF_SWEEPE_KERNEL(sw_affine_sweep_band_endb_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, true, 1)
+AFF_SWEEPE_KERNEL(sw_affine_sweep_band_endb_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, true, 1)
+#undef AFF_SWEEPE_KERNEL
+#undef AFF_SWEEPE_ARGS_00
+#undef AFF_SWEEPE_ARGS_10
+#undef AFF_SWEEPE_ARGS_01
+#undef AFF_SWEEPE_ARGS_11
 // The 8 two-piece sweeps (option "gap_open2"): global and extend, each narrow, wide, long and banded long, TWO = 1.
 // The second piece's open and extension follow gap_open; the banded ones take the half-width last.
 #define AFF_SWEEP2_PARAMS_0 const FillArgs A, const int gap_open, const int gap_open2, const int gap2
@@ -1089,8 +1183,8 @@ AFF_TRACEBACK_KERNEL(sw_affine_traceback2_band_global_kernel, AFF_GLOBAL, true, 
 // ------------------------------------------------------------------------------------------------
 // Both take the run's options as one AffRun and refuse what aff_run_ok refuses (swmi_launch.h, which describes the arguments).
 // A kernel is picked from tables typed by signature -- ten for the sweeps: with / without the matrix, the half-width and the
-// threshold, and the two-piece sweeps with / without the half-width (the sweeps of option "subopt" have their twins' signatures);
-// two for the walks -- and launched through one generic
+// threshold, and the two-piece sweeps with / without the half-width (the sweeps of option "subopt" have their twins' signatures, those of
+// option "end_bonus" their twins' and the bonus); two for the walks -- and launched through one generic
 // lambda, so that every launch is checked against its kernel's parameter list: one branch per signature.
 static_assert(AFF_EXTEND == 3, "AffRun.mode 3 is the extend run");
 
@@ -1134,12 +1228,19 @@ extern "C" hipError_t swmi_launch_affine_sweep(const FillArgs *a, const AffRun *
         sw_affine_sweep_subopt_matrix_kernel, sw_affine_sweep_subopt_matrix_wide_kernel, sw_affine_sweep_long_subopt_matrix_kernel};
     static void (*const sbplain)(FillArgs, int, uint32_t) = sw_affine_sweep_band_subopt_kernel;
     static void (*const sbmatrix)(FillArgs, int, const uint32_t *, uint32_t, uint32_t) = sw_affine_sweep_band_subopt_matrix_kernel;
+    // the extend sweeps under option "end_bonus" (the bonus is the last argument), [narrow / wide / long], and the banded long ones
+    static void (*const eplain[3])(FillArgs, int, uint32_t) = {sw_affine_sweep_endb_kernel, sw_affine_sweep_endb_wide_kernel, sw_affine_sweep_long_endb_kernel};
+    static void (*const ematrix[3])(FillArgs, int, const uint32_t *, uint32_t, uint32_t) = {
+        sw_affine_sweep_endb_matrix_kernel, sw_affine_sweep_endb_matrix_wide_kernel, sw_affine_sweep_long_endb_matrix_kernel};
+    static void (*const ebplain)(FillArgs, int, uint32_t, uint32_t) = sw_affine_sweep_band_endb_kernel;
+    static void (*const ebmatrix)(FillArgs, int, const uint32_t *, uint32_t, uint32_t, uint32_t) = sw_affine_sweep_band_endb_matrix_kernel;
     const dim3 grid((a->n_pairs + AFF_WAVES - 1) / AFF_WAVES), block(WAVE * AFF_WAVES);
     // (extra...: what the kernel takes after the arguments every sweep takes.  A launch's own error is what hipGetLastError returns below)
     const auto launch = [&](auto *k, auto... extra) { hipLaunchKernelGGL(k, grid, block, 0, st, *a, (int)r->gap_open, extra...); };
     const uint32_t mode = r->mode, band = long_reads ? r->band : 0u, xdrop = long_reads ? r->xdrop : 0u;      // (options of the long shape only)
     const uint32_t adapt = band ? r->adapt : 0u, nn = r->nn;
     const uint32_t *const mat = r->mat;
+    const uint32_t endb = r->end_bonus;                           // (aff_run_ok: an extend run without xdrop, band_adapt or gap_open2)
     const auto sweep = [&](int shape) {
         if (r->gap_open2 && band)  launch(tbplain[mode - 2u], (int)r->gap_open2, (int)r->gap2, band);
         else if (r->gap_open2)     launch(tplain[shape][mode - 2u], (int)r->gap_open2, (int)r->gap2);
@@ -1147,6 +1248,10 @@ extern "C" hipError_t swmi_launch_affine_sweep(const FillArgs *a, const AffRun *
         else if (r->subopt && mat) launch(smatrix[shape], mat, nn);
         else if (r->subopt && band) launch(sbplain, band);
         else if (r->subopt)        launch(splain[shape]);
+        else if (endb && mat && band) launch(ebmatrix, mat, nn, band, endb);
+        else if (endb && mat)      launch(ematrix[shape], mat, nn, endb);
+        else if (endb && band)     launch(ebplain, band, endb);
+        else if (endb)             launch(eplain[shape], endb);
         else if (mat && band && xdrop) launch(xbmatrix[adapt], mat, nn, band, xdrop);
         else if (mat && band)      launch(bmatrix[adapt ? 4u : mode], mat, nn, band);
         else if (mat && xdrop)     launch(xmatrix, mat, nn, xdrop);

@@ -201,6 +201,10 @@ extern "C" int swmi_set_option(swmi_ctx *ctx, const char *name, int64_t value) {
         if (value < SWMI_SUBOPT_AUTO || value > (1ll << 30))
             return fail(SWMI_ERR_INVALID, "subopt must be 0 (off), a mask half-width of 1 .. 2^30 columns or -1 (SWMI_SUBOPT_AUTO), got %lld", (long long)value);
         ctx->modes.subopt = (int)value;
+    } else if (!strcmp(name, "end_bonus")) {
+        if (value < 0 || value > (1ll << 30))
+            return fail(SWMI_ERR_INVALID, "end_bonus must be 0 (off) or a bonus of 1 .. 2^30, got %lld", (long long)value);
+        ctx->modes.end_bonus = (int)value;
     } else if (!strcmp(name, "arena_words_per_pair")) {
         if (value < 1) return fail(SWMI_ERR_INVALID, "arena_words_per_pair out of range");
         ctx->arena_words_per_pair = (uint64_t)value;

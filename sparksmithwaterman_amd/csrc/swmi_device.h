@@ -53,6 +53,7 @@
 #define SWMI_F_CELL_OVF     0x2u   // more tied max cells than cell_cap: host re-runs the pair
 #define SWMI_F_ARENA_OVF    0x4u   // a record of this pair did not fit the arena: host grows it, re-runs
 #define SWMI_F_DONE         0x8u   // the pair was handled whole by sw_resident_pairs_kernel: the traceback kernels leave it alone
+#define SWMI_F_TO_END       0x10u  // option "end_bonus": the pair was taken to the read's end -- its score is end_score, its one cell (m, end_col)
 // bits 8-31: the strips swept of a pair whose strip sweep option "xdrop" stopped (>= 1; a read has at most 2^22 strips), 0 for every
 // other pair.  Not a flag: no kernel tests it, the traceback kernels copy it to the host with the word, and the host turns it
 // into swmi_pair_rows_swept
@@ -111,6 +112,14 @@ struct PairOut {
     uint64_t n_cells;     // number of tied maximum cells (m*n when degenerate)
 };
 
+// Option "end_bonus" (DESIGN.md 8o): what the extend sweeps of such a run leave per pair, by out_id, in the result block behind the
+// pair outputs -- swmi.h's max_score, end_score and end_col
+struct EndOut {
+    int32_t  max_score;   // the maximum of H over every existing cell: the score of the run without the option
+    int32_t  end_score;   // the maximum of H(m, j) over the existing cells of read row m
+    uint32_t end_col;     // the smallest (1-based) column that holds it
+};
+
 // One alignment = one entry of the RECORD TABLE (dense, 8 dwords each, in the order the records were reserved) + its payload
 // in the arena.  With TraceArgs.raw set: the two aligned strings GetAlignment returns (SmithWaterman.java:418-431), refAligned
 // then readAligned, n_ops/4 + 1 dwords each (NUL-terminated, NUL-padded).  Otherwise: ceil(n_ops/16) dwords of 2-bit ops (op t
@@ -163,7 +172,8 @@ struct FillArgs {
     const StripItem *strip_items; // the strips of a (pair, column chunk) consecutive and ascending
     uint32_t       *progress;    // per strip item: 16-step blocks finished (the item's index is PairDesc.pad + strip)
     uint32_t        n_strip_items;
-    uint32_t        pad3;
+    uint32_t        n_out;       // entries of out[]: the pairs of the whole launch (n_pairs is this kernel's share of them).  Read by the sweeps of
+                                 // option "end_bonus" alone: their EndOut array lies behind the pair outputs, at out + n_out
     uint32_t       *err_host;    // host-mapped word, set to 1 when a strip gave up waiting for its producer
     const ColItem  *col_items;   // mode 1: column chunks of single-strip pairs (few pairs, long references)
     uint32_t        n_col_items;

@@ -124,6 +124,7 @@ struct __attribute__((visibility("hidden"))) RunModes {
     int gap2 = 0;                           // ... and its per-base extension (not read while gap_open2 == 0)
     int cigar = 0;                          // 1 / 2: the records' payload is a CIGAR, M/I/D or =/X/I/D (swmi.h); the affine kernels
     int subopt = 0;                         // != 0: a local run also returns every pair's second-best score -- the mask half-width, -1 automatic (swmi.h); refused in the other modes
+    int end_bonus = 0;                      // > 0: an extend run also returns every pair's best score in read row m and takes the pair to the read's end when that is less than this bonus below the best score (swmi.h); refused in other runs
     bool two_piece() const { return gap_open2 != 0; }
     // the MODE of the affine kernels and their launchers: the align_mode, or 3 (extend) for a global run with option "extend"
     uint32_t kernel_mode() const { return extend && align_mode == SWMI_ALIGN_GLOBAL ? 3u : (uint32_t)align_mode; }
@@ -200,7 +201,7 @@ struct swmi_ctx {
     bool cell_cap_set = false;              // cell_cap given by the caller (otherwise small launches get longer lists)
     int32_t gap_open = 0;                   // affine gaps: a gap of length k costs gap_open + k * gap (0: linear)
     int affine = -1;                        // -1: the affine kernels (mode 3) when gap_open != 0; 1: always
-    RunModes modes;                         // options "align_mode", "long_reads", "band", "extend", "xdrop", "band_adapt", "gap_open2", "gap2", "cigar" and "subopt"
+    RunModes modes;                         // options "align_mode", "long_reads", "band", "extend", "xdrop", "band_adapt", "gap_open2", "gap2", "cigar", "subopt" and "end_bonus"
     std::mutex mat_mu;                      // guards `matrix` (not ctx->mu: setting a matrix does not wait for a run)
     std::shared_ptr<const ScoreMatrix> matrix;   // swmi_set_score_matrix; a run with one takes the affine kernels
     // swmi_batch_run_async: one run in flight on the context's own host thread
@@ -346,6 +347,8 @@ struct swmi_batch {
     std::vector<PairRes> pairs;             // by pair index
     bool has_sub = false;                   // the last run had option "subopt": `sub` holds every pair's (score2, end2), (0, 0) for a pair that was not swept
     std::vector<SuboptOut> sub;                // by pair index
+    bool has_endb = false;                  // the last run had option "end_bonus": `endv` holds every pair's (max_score, end_score, end_col), (0, 0, 0) for a pair that was not swept
+    std::vector<EndOut> endv;               // by pair index
     // option "band_adapt": the window tables the sweeps of the last run left (the centre of every strip, swmi_device.h), fetched
     // after every launch; win_at[pair] = 1 + the index of the pair's first entry in win_tab, 0 for a pair without a table
     std::vector<uint32_t> win_tab;
@@ -396,11 +399,13 @@ struct RunState {
     bool keep = true;                       // the launch's records belong to the batch's results (false: the sampled pre-pass)
 };
 
-// layout of the result block: [ArenaHdr | PairOut x np | sub: SuboptOut x np (option "subopt" only) | record table, tab_cap entries | arena words ...]
+// layout of the result block: [ArenaHdr | PairOut x np | sub: SuboptOut x np (option "subopt") or EndOut x np (option "end_bonus"), else nothing |
+//                              record table, tab_cap entries | arena words ...]
+// sub: the bytes per pair of that array -- the two options exclude each other, so they share the place
 static inline size_t result_out_off() { return 64; }
 static inline size_t result_sub_off(size_t np) { return 64 + np * sizeof(PairOut); }
-static inline size_t result_tab_off(size_t np, bool sub) { return (64 + np * (sizeof(PairOut) + (sub ? sizeof(SuboptOut) : 0)) + 255) & ~(size_t)255; }
-static inline size_t result_arena_off(size_t np, uint64_t tab_cap, bool sub) { return (result_tab_off(np, sub) + tab_cap * sizeof(AlnRec) + 255) & ~(size_t)255; }
+static inline size_t result_tab_off(size_t np, size_t sub) { return (64 + np * (sizeof(PairOut) + sub) + 255) & ~(size_t)255; }
+static inline size_t result_arena_off(size_t np, uint64_t tab_cap, size_t sub) { return (result_tab_off(np, sub) + tab_cap * sizeof(AlnRec) + 255) & ~(size_t)255; }
 // dwords of one alignment's payload: the two strings, n_ops / 4 + 1 dwords each, or the ops packed 16 per dword (swmi_emit.h)
 static inline uint64_t rec_words(uint32_t n_ops, bool strings) {
     return strings ? 2 * ((uint64_t)n_ops / 4 + 1) : ((uint64_t)n_ops + 15) / 16;

@@ -31,6 +31,7 @@ struct AffRun {
     uint32_t nn;                 // ... and its side n + 1 (2 .. SWMI_MAT_NN_MAX)
     uint32_t cigar;              // option "cigar" (0: off; 1: M/I/D, 2: =/X/I/D) -- the payload the walks write (swmi_emit.h); the sweeps do not read it
     int32_t subopt;              // option "subopt" (0: off; 1 .. 2^30: the mask half-width, -1: per pair) -- the local sweeps that leave the column maxima
+    uint32_t end_bonus;          // option "end_bonus" (0: off; 1 .. 2^30: the bonus) -- the extend sweeps that also choose the read's end
 };
 // What the launchers refuse (hipErrorInvalidValue): the combinations no kernel exists for.  band, xdrop and adapt are options of
 // the long shape (long_reads: every pair of the launch has a read longer than SWMI_AFF_MAX_READ); the short shape ignores them.
@@ -40,6 +41,8 @@ static inline bool aff_run_ok(const AffRun &r, uint32_t long_reads) {
     if (r.mat && (r.nn < 2u || r.nn > SWMI_MAT_NN_MAX)) return false;
     if (r.gap_open2 && (r.mode < 2u || r.mat || r.xdrop || r.adapt)) return false;      // two-piece: plain global and extend runs
     if (r.subopt < -1 || r.subopt > (1 << 30) || (r.subopt && r.mode != 0u)) return false;   // subopt: local runs
+    // end_bonus: one-piece extend runs without xdrop or band_adapt
+    if (r.end_bonus > (1u << 30) || (r.end_bonus && (r.mode != 3u || r.xdrop || r.adapt || r.gap_open2 || r.subopt))) return false;
     if (long_reads && r.xdrop && r.mode != 3u) return false;                            // xdrop: extend runs
     if (long_reads && r.adapt && (!r.band || r.mode != 3u)) return false;               // band_adapt: banded extend runs
     return true;

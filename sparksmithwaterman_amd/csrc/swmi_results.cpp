@@ -217,6 +217,31 @@ extern "C" int swmi_batch_pair_subopt(const swmi_batch *b, int32_t *score2, uint
     return SWMI_OK;
 }
 
+// option "end_bonus": the pair's best score anywhere, its best score in read row m and that score's first column (swmi.h)
+extern "C" int swmi_pair_end_score(const swmi_batch *b, uint64_t pair, int32_t *max_score, int32_t *end_score, uint32_t *end_col) {
+    int rc = check_pair(b, pair);
+    if (rc) return rc;
+    if (!b->has_endb) return fail(SWMI_ERR_UNSUPPORTED, "the batch was run with end_bonus = 0: there is no to-end score");
+    if (max_score) *max_score = b->endv[pair].max_score;
+    if (end_score) *end_score = b->endv[pair].end_score;
+    if (end_col) *end_col = b->endv[pair].end_col;
+    return SWMI_OK;
+}
+
+extern "C" int swmi_batch_pair_end_scores(const swmi_batch *b, int32_t *max_score, int32_t *end_score, uint32_t *end_col, uint64_t n) {
+    if (!b) return fail(SWMI_ERR_INVALID, "batch is null");
+    if (!b->has_run) return fail(SWMI_ERR_INVALID, "batch has no results (run it first)");
+    if (!b->has_endb) return fail(SWMI_ERR_UNSUPPORTED, "the batch was run with end_bonus = 0: there is no to-end score");
+    if (n != batch_n_pairs(b)) return fail(SWMI_ERR_RANGE, "the batch has %llu pairs, not %llu",
+                                           (unsigned long long)batch_n_pairs(b), (unsigned long long)n);
+    for (uint64_t k = 0; k < n; k++) {
+        if (max_score) max_score[k] = b->endv[k].max_score;
+        if (end_score) end_score[k] = b->endv[k].end_score;
+        if (end_col) end_col[k] = b->endv[k].end_col;
+    }
+    return SWMI_OK;
+}
+
 // Pops the traceback "stack" into the two aligned strings (SmithWaterman.java:418-431): ops are stored
 // from the max cell backwards, so the strings are built by walking them in reverse.
 static void materialise(swmi_batch *b, uint64_t pair, HostAln &a, uint64_t slot) {

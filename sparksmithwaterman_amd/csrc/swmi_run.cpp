@@ -52,6 +52,8 @@ struct Launch {
     bool zc = false;                        // results land in pinned host memory while the kernels run
     bool sweep_only = false;                // option scores_only
     bool sub = false;                       // option "subopt": the result block holds a SuboptOut per pair behind the pair outputs
+    bool endb = false;                      // option "end_bonus": ... an EndOut per pair, in the same place (the two options exclude each other)
+    size_t sub_bytes() const { return sub ? sizeof(SuboptOut) : endb ? sizeof(EndOut) : 0; }      // per pair, behind the pair outputs
     bool time_all = false;                  // (profiling = 2: only the sweep is bracketed -- two marker packets per run instead of three; each costs ~3.5 us of the step)
     uint64_t arena_cap = 0, tab_cap = 0;    // grown by an attempt that overflowed
     // per attempt
@@ -133,7 +135,7 @@ static int build_fill_args(RunState &rs, Launch &L) {
     fa.progress = pipe ? b->d_progress.as<uint32_t>() : nullptr;
     fa.n_strip_items = pipe ? (uint32_t)plan.n_strip_items : 0u;
     fa.err_host = (uint32_t *)ctx->h_err.dp;
-    fa.pad3 = 0;
+    fa.n_out = (uint32_t)L.np;
     if (L.attempt == 0) b->timing.col_chunks += (uint32_t)plan.n_col_items + (pipe ? (uint32_t)plan.n_strip_chunks : 0u);
     fa.col_items = plan.n_col_items ? b->d_col_items.as<ColItem>() : nullptr;
     fa.n_col_items = (uint32_t)plan.n_col_items;
@@ -255,6 +257,7 @@ static inline AffRun aff_run(const swmi_batch *b) {
     r.nn = b->opt.mat ? b->opt.mat->n + 1u : 0u;
     r.cigar = (uint32_t)md.cigar;
     r.subopt = md.subopt;
+    r.end_bonus = (uint32_t)md.end_bonus;
     return r;
 }
 
@@ -311,9 +314,9 @@ static int enqueue_launches(RunState &rs, Launch &L, const ResidentArgs &xa, con
         // option scores_only: the pair outputs as the sweep kernels left them (the traceback kernels, which otherwise mirror
         // them into the host block, do not run)
         if ((rc = b->h_result.reserve(L.a_off + L.arena_cap * 4))) return rc;
-        // (option "subopt": and the SuboptOut array, which follows them)
+        // (options "subopt" and "end_bonus": and the array that follows them)
         HIP_TRY(hipMemcpyAsync((uint8_t *)b->h_result.p + result_out_off(), L.res + result_out_off(),
-                               np * (sizeof(PairOut) + (L.sub ? sizeof(SuboptOut) : 0)), hipMemcpyDeviceToHost, ctx->stream));
+                               np * (sizeof(PairOut) + L.sub_bytes()), hipMemcpyDeviceToHost, ctx->stream));
     } else if (L.split) {
         ta.win_off = b->d_win_off.as<uint32_t>();
         ta.q_count = b->d_queue.as<uint32_t>();
@@ -329,6 +332,13 @@ static int enqueue_launches(RunState &rs, Launch &L, const ResidentArgs &xa, con
         // (option "gap_open2": a block of the field is 2 * R * 64 dwords, and SWMI_AFF_TILE_WORDS holds one -- swmi_device.h)
         HIP_TRY(swmi_launch_affine_traceback(&ts, &ar, 0u, SWMI_AFF_TILE_WORDS, ops_words, ctx->stream));
         HIP_TRY(swmi_launch_affine_traceback(&tl, &ar, 1u, SWMI_AFF_TILE_WORDS, ops_words, ctx->stream));
+        if (L.endb && L.zc) {
+            // option "end_bonus", zero-copy results: the walks mirror the pair outputs into the pinned block, and this copy puts the
+            // sweeps' EndOut array behind them.  On every attempt: the retry has put the array back with the pair outputs
+            // (saved_outs), and the pinned block may have been re-allocated.  (Without zero-copy it is part of the D2H copy below.)
+            HIP_TRY(hipMemcpyAsync((uint8_t *)b->h_result.p + result_sub_off(np), L.res + result_sub_off(np), np * sizeof(EndOut),
+                                   hipMemcpyDeviceToHost, ctx->stream));
+        }
     } else if (n_res + n_tf < np) {
         HIP_TRY(swmi_launch_traceback(&ta, ctx->stream, ext ? ctx->ev[2] : nullptr, ext ? ctx->ev[3] : nullptr));
     }
@@ -371,7 +381,7 @@ static void collect_scores(const swmi_batch *b, const std::vector<Work> &work, c
             o.score = 0; o.flags = SWMI_F_DEGENERATE;
             o.n_cells = (uint64_t)b->read_desc[pair_read(b, pair)].len * b->ref_desc[pair_ref(b, pair)].len;
         }
-        o.flags &= SWMI_F_DEGENERATE | SWMI_F_STRIPS_MASK;      // (the strips swept under option "xdrop" stay)
+        o.flags &= SWMI_F_DEGENERATE | SWMI_F_TO_END | SWMI_F_STRIPS_MASK;      // (the strips swept under option "xdrop" stay, and the choice of option "end_bonus")
     }
 }
 
@@ -400,11 +410,13 @@ static int collect_launch(RunState &rs, Launch &L, Clock::time_point t_done, std
     const uint64_t hdr_recs = zc && !overflow ? 0 : hdr->reserved >> SWMI_HDR_WORD_BITS;
     if (!zc) overflow = hdr_words > L.arena_cap || hdr_recs > L.tab_cap;
     if (overflow) {            // records were dropped: grow to the exact need and redo the traceback
+        // (option "end_bonus": the sweeps' EndOut array behind the pair outputs is carried along -- no kernel of the retry writes it)
+        const size_t keep = np * (sizeof(PairOut) + (L.endb ? sizeof(EndOut) : 0));
         if (zc) {
-            saved_outs.resize(np * sizeof(PairOut));
+            saved_outs.resize(keep);
             HIP_TRY(hipMemcpy(saved_outs.data(), L.res + result_out_off(), saved_outs.size(), hipMemcpyDeviceToHost));
         } else {
-            saved_outs.assign(h + result_out_off(), h + result_out_off() + np * sizeof(PairOut));
+            saved_outs.assign(h + result_out_off(), h + result_out_off() + keep);
         }
         for (size_t k = 0; k < np; k++) {
             PairOut &so = ((PairOut *)saved_outs.data())[k];
@@ -505,6 +517,7 @@ static int run_chunk(RunState &rs, const std::vector<Work> &work, size_t lo, siz
     L.sweep_only = ctx->scores_only != 0 && !cells_exact;
     L.time_all = ctx->profiling == 1;
     L.sub = b->eff_mode == 3 && b->opt.modes.subopt != 0;
+    L.endb = b->eff_mode == 3 && b->opt.modes.end_bonus != 0;
 
     const auto c0 = Clock::now();
     L.arena_cap = std::max<uint64_t>(np * ctx->arena_words_per_pair, 1024);
@@ -513,7 +526,7 @@ static int run_chunk(RunState &rs, const std::vector<Work> &work, size_t lo, siz
     for (L.attempt = 0;; L.attempt++) {
         // (an overflow that growing cannot cure -- a path longer than the staging area -- must not retry for ever)
         if (L.attempt > 4) return fail(SWMI_ERR_HIP, "the record arena overflowed %d times in a row; results discarded", L.attempt);
-        L.t_off = result_tab_off(np, L.sub); L.a_off = result_arena_off(np, L.tab_cap, L.sub);
+        L.t_off = result_tab_off(np, L.sub_bytes()); L.a_off = result_arena_off(np, L.tab_cap, L.sub_bytes());
         if ((rc = b->d_result.reserve(L.a_off + L.arena_cap * 4))) return rc;
         L.res = b->d_result.as<uint8_t>();
         if (L.attempt > 0) {         // (on the first attempt the fill kernel zeroes the arena header itself)
@@ -561,6 +574,12 @@ static int run_chunk(RunState &rs, const std::vector<Work> &work, size_t lo, siz
             // part of the D2H copy.  The exact-size re-run of a pair computes the same values and overwrites them.
             const SuboptOut *hs = (const SuboptOut *)((const uint8_t *)b->h_result.p + result_sub_off(np));
             for (size_t k = 0; k < np; k++) b->sub[work[lo + k].pair] = hs[k];
+        }
+        if (L.endb) {
+            // option "end_bonus": the launch's (max_score, end_score, end_col), in the host block by now -- part of a D2H copy on every
+            // path.  The exact-size re-run of a pair (one that was not taken to the end) computes the same values and overwrites them.
+            const EndOut *he = (const EndOut *)((const uint8_t *)b->h_result.p + result_sub_off(np));
+            for (size_t k = 0; k < np; k++) b->endv[work[lo + k].pair] = he[k];
         }
         if (L.sweep_only) { collect_scores(b, work, L, outs); return SWMI_OK; }
         bool retry;
@@ -638,6 +657,16 @@ static int check_run_params(const swmi_ctx *ctx, const swmi_batch *b, const swmi
     // and gap_open2, options of a global run
     if (md.subopt != 0 && md.align_mode != SWMI_ALIGN_LOCAL)
         return fail(SWMI_ERR_UNSUPPORTED, "subopt = %d needs align_mode local (0), got align_mode %d", md.subopt, md.align_mode);
+    // option "end_bonus": the to-end score is defined, and built, for one-piece extend runs whose sweep reaches read row m with the
+    // static windows -- the linear pipeline has no such run, and an extend run takes the affine kernels anyway
+    if (md.end_bonus != 0) {
+        if (!(md.extend && md.align_mode == SWMI_ALIGN_GLOBAL))
+            return fail(SWMI_ERR_UNSUPPORTED, "end_bonus = %d needs an extend run (align_mode global (2) with extend = 1), got align_mode %d, extend %d",
+                        md.end_bonus, md.align_mode, md.extend);
+        if (md.xdrop > 0) return fail(SWMI_ERR_UNSUPPORTED, "end_bonus = %d: the to-end score under xdrop is not supported (a stopped pair has no row m)", md.end_bonus);
+        if (md.band_adapt) return fail(SWMI_ERR_UNSUPPORTED, "end_bonus = %d: the to-end score under band_adapt is not supported", md.end_bonus);
+        if (md.two_piece()) return fail(SWMI_ERR_UNSUPPORTED, "end_bonus = %d: the to-end score with two-piece gaps (gap_open2) is not supported", md.end_bonus);
+    }
     if (p->tie_mode != SWMI_TIE_SERIAL && p->tie_mode != SWMI_TIE_STRICT)
         return fail(SWMI_ERR_INVALID, "unknown tie_mode %d", p->tie_mode);
     // GetAlignment tests `align == alignTypes[0]`, then `== alignTypes[1]`, else deletion
@@ -923,6 +952,8 @@ static int batch_run(swmi_ctx *ctx, swmi_batch *b, const swmi_params *p, RunOpti
     b->win_tab.clear(); b->win_at.clear();
     b->has_sub = opt.modes.subopt != 0;
     b->sub.assign(b->has_sub ? batch_n_pairs(b) : 0, SuboptOut{0, 0u});     // (a pair with an empty side is never swept: (0, 0))
+    b->has_endb = opt.modes.end_bonus != 0;
+    b->endv.assign(b->has_endb ? batch_n_pairs(b) : 0, EndOut{0, 0, 0u});   // (... (0, 0, 0))
     b->alns.clear(); b->str_at.clear();
     b->raw.clear(); b->rtab.clear(); b->raw_chunks.clear(); b->indexed = false;
     b->raw_ext = nullptr; b->rtab_ext = nullptr;
@@ -982,7 +1013,7 @@ static int batch_run(swmi_ctx *ctx, swmi_batch *b, const swmi_params *p, RunOpti
         for (size_t k = 0; k < hi - lo; k++) {
             PairRes &pr = b->pairs[work[lo + k].pair];
             pr.score = outs[k].score;
-            pr.flags = (outs[k].flags & SWMI_F_DEGENERATE) ? SWMI_PAIR_DEGENERATE : 0u;
+            pr.flags = ((outs[k].flags & SWMI_F_DEGENERATE) ? SWMI_PAIR_DEGENERATE : 0u) | ((outs[k].flags & SWMI_F_TO_END) ? SWMI_PAIR_TO_END : 0u);
             pr.n_cells = outs[k].n_cells;
             pr.strips = outs[k].flags >> SWMI_F_STRIPS_SHIFT;
             if (outs[k].flags & SWMI_F_CELL_OVF) ovf.push_back(lo + k);

@@ -187,6 +187,8 @@ def _rank_main(args):
             ctx.set_option("xdrop", args.xdrop)
         if args.band_adapt:                                 # ... and the band re-centred on the alignment from strip to strip
             ctx.set_option("band_adapt", 1)
+        if args.end_bonus:                                  # ... or a pair taken to the read's end when that is nearly as good
+            ctx.set_option("end_bonus", args.end_bonus)
         if args.matrix:                                     # substitution scores on this rank's context (NCBI text format)
             from . import matrix as _matrix
             ctx.set_score_matrix(_matrix.load(args.matrix))
@@ -223,6 +225,12 @@ def _parser():
                 self.error("--xdrop requires --extend")
             if ns.band_adapt and not (ns.band and ns.extend):
                 self.error("--band-adapt requires --band and --extend")
+            if ns.end_bonus < 0 or ns.end_bonus > _capi.END_BONUS_MAX:
+                self.error("--end-bonus takes a bonus of 0 .. 2^30")
+            if ns.end_bonus and not ns.extend:
+                self.error("--end-bonus requires --extend")
+            if ns.end_bonus and (ns.xdrop or ns.band_adapt or len(ns.scores.split(",")) == 6):
+                self.error("--end-bonus is not built for --xdrop, --band-adapt or two-piece gaps")
             return ns
     ap = Parser(description=__doc__.split("\n")[0])
     ap.add_argument("--ref-dir", required=True)
@@ -262,6 +270,10 @@ def _parser():
                     help="with --band and --extend: the band follows the alignment (option band_adapt) -- the window of a strip of "
                          "1024 rows is placed around the column where the row above it scores best, so --band only has to cover the "
                          "drift inside one strip")
+    ap.add_argument("--end-bonus", type=int, default=0, metavar="B",
+                    help="with --extend: take a pair to the end of the read (option end_bonus) when the best extension that reaches it "
+                         "scores less than B below the best one anywhere -- no soft clip for one mismatch near the read's end.  Not "
+                         "with --xdrop, --band-adapt or two-piece gaps.  0 (the default): off")
     ap.add_argument("--tie", choices=("serial", "strict"), default="serial",
                     help="serial: SmithWaterman's aligner (NoDistribution, DistributeReference); strict: DistributedSW's (DistributeAlgorithm)")
     ap.add_argument("--stream-chunk-bytes", type=int, default=512 << 10, help="sequence bytes per streamed chunk")
