@@ -63,6 +63,10 @@ public class GpuSmithWaterman
 	static native void nativeSetEndBonus( long ctx , int endBonus ) ;
 	/** { max score , to-end score , the reference column it ends in , taken to the end ? 1 : 0 } of a pair after a run under that option */
 	static native int[] nativePairEndScore( long batch , long pair ) ;
+	/** the best local hits: the most entries per pair, 0 off (include/swmi.h: option "hits"; needs nativeSetSubopt) */
+	static native void nativeSetHits( long ctx , int hits ) ;
+	/** { score , read row , reference column } of every hit of a pair after a run under that option, best first */
+	static native int[] nativePairHits( long batch , long pair ) ;
 	/** substitution scores on the context: alphabet = n ISO-8859-1 symbols, scores = n * n, row = read base; null clears */
 	static native void nativeSetScoreMatrix( long ctx , byte[] alphabet , int[] scores ) ;
 	/** a pair list over the sequences: specs = eight ints per pair ( alignPairs ) */
@@ -220,6 +224,24 @@ public class GpuSmithWaterman
 	/** { max score , to-end score , its reference column , taken to the end ? 1 : 0 } of a pair of a native batch run under setEndBonus */
 	static int[] endScore( long batch , long pair ) { return nativePairEndScore( batch , pair ) ; }
 
+	/** the most local hits per pair every context asks its runs for, 0: none (applied next to SUBOPT, before every batch) */
+	private static volatile int HITS = 0 ;
+
+	/**
+	 * k in 1 .. 16: a run under setSubopt also returns, per pair, up to k local hits -- the best alignment's score and end cell, then the
+	 * best scores that end more than the mask half-width away from it and from each other, each with the cell it ends in; 0 (the
+	 * default): off.  Needs setSubopt != 0: a batch aligned with hits and without it is refused.  For every batch aligned from now on,
+	 * on every executor thread.
+	 */
+	public static void setHits( int k )
+	{
+		if( k < 0 || k > 16 ) throw new IllegalArgumentException( "hits must be 0 .. 16: " + k ) ;
+		HITS = k ;
+	}
+
+	/** { score , read row , reference column } per hit of a pair of a native batch run under setHits, best first (1-based cells) */
+	static int[] hits( long batch , long pair ) { return nativePairHits( batch , pair ) ; }
+
 	/** the score matrix every context applies before its next batch: { alphabet , scores } (null: none), and its version */
 	private static volatile Object[] MATRIX = null ;
 	private static final java.util.concurrent.atomic.AtomicLong MATRIX_VERSION = new java.util.concurrent.atomic.AtomicLong() ;
@@ -327,6 +349,7 @@ public class GpuSmithWaterman
 		nativeSetBandAdapt( ctx , BAND_ADAPT ? 1 : 0 ) ;
 		nativeSetCigar( ctx , CIGAR ) ;
 		nativeSetSubopt( ctx , SUBOPT ) ;
+		nativeSetHits( ctx , HITS ) ;
 		nativeSetEndBonus( ctx , END_BONUS ) ;
 		applyScoreMatrix( nc ) ;
 	}

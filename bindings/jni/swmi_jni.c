@@ -148,6 +148,33 @@ JNIEXPORT jintArray JNICALL Java_sw_GpuSmithWaterman_nativePairEndScore(JNIEnv *
     return res;
 }
 
+/* the best local hits on this context from now on: the most entries per pair, 0 off */
+JNIEXPORT void JNICALL Java_sw_GpuSmithWaterman_nativeSetHits(JNIEnv *env, jclass cls, jlong ctx, jint hits) {
+    char err[640];
+    (void)cls;
+    if (swmi_shim_set_hits((swmi_ctx *)(intptr_t)ctx, hits, err, sizeof err) != SWMI_OK) throw_msg(env, err);
+}
+
+/* { score, read row, reference column } x the pair's hits after a run under option "hits" */
+JNIEXPORT jintArray JNICALL Java_sw_GpuSmithWaterman_nativePairHits(JNIEnv *env, jclass cls, jlong batch, jlong pair) {
+    char err[640];
+    int32_t out[3 * 16];
+    int32_t n = 0;
+    jint jo[3 * 16];
+    jintArray res;
+    int k;
+    (void)cls;
+    if (swmi_shim_pair_hits((const swmi_batch *)(intptr_t)batch, pair, out, 16, &n, err, sizeof err) != SWMI_OK) {
+        throw_msg(env, err);
+        return NULL;
+    }
+    res = (*env)->NewIntArray(env, 3 * n);
+    if (!res) return NULL;
+    for (k = 0; k < 3 * n; k++) jo[k] = out[k];
+    (*env)->SetIntArrayRegion(env, res, 0, 3 * n, jo);
+    return res;
+}
+
 /* two-piece gaps on this context from now on: gapOpen2 != 0 on, 0 off */
 JNIEXPORT void JNICALL Java_sw_GpuSmithWaterman_nativeSetGap2(JNIEnv *env, jclass cls, jlong ctx, jint gap_open2, jint gap2) {
     char err[640];

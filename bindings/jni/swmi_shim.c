@@ -137,6 +137,31 @@ int swmi_shim_pair_end_score(const swmi_batch *b, int64_t pair, int32_t out[4], 
     return SWMI_OK;
 }
 
+int swmi_shim_set_hits(swmi_ctx *ctx, int32_t hits, char *err, size_t err_len) {
+    int rc;
+    if (!ctx) return shim_fail(SWMI_ERR_INVALID, err, err_len, "nativeSetHits", "context handle is 0");
+    if ((rc = swmi_set_option(ctx, "hits", hits)) != SWMI_OK)
+        return shim_fail(rc, err, err_len, "nativeSetHits", swmi_last_error());
+    return SWMI_OK;
+}
+
+int swmi_shim_pair_hits(const swmi_batch *b, int64_t pair, int32_t *out, int32_t cap, int32_t *n, char *err, size_t err_len) {
+    swmi_hit h[16];                                       /* (option "hits": at most 16 entries) */
+    uint32_t cnt = 0, k;
+    int rc;
+    if (pair < 0) return shim_fail(SWMI_ERR_RANGE, err, err_len, "nativePairHits", "negative index");
+    if (out && cap < 0) return shim_fail(SWMI_ERR_RANGE, err, err_len, "nativePairHits", "negative capacity");
+    rc = swmi_pair_hits(b, (uint64_t)pair, h, 16u, &cnt);
+    if (rc != SWMI_OK) return shim_fail(rc, err, err_len, "swmi_pair_hits", swmi_last_error());
+    if (n) *n = (int32_t)cnt;
+    if (!out) return SWMI_OK;
+    if ((uint32_t)cap < cnt) return shim_fail(SWMI_ERR_RANGE, err, err_len, "nativePairHits", "the array holds fewer entries than the pair has");
+    for (k = 0; k < cnt; k++) {                           /* (a row and a column are below 2^31) */
+        out[3 * k] = h[k].score; out[3 * k + 1] = (int32_t)h[k].end_i; out[3 * k + 2] = (int32_t)h[k].end_j;
+    }
+    return SWMI_OK;
+}
+
 int swmi_shim_pair_cigar(swmi_batch *b, int64_t pair, int64_t k, int32_t *begin, int32_t cell[2], const uint32_t **cigar,
                          uint32_t *n_cigar, uint32_t *nm, char *err, size_t err_len) {
     int32_t ei = 0, ej = 0;

@@ -100,6 +100,15 @@ int swmi_shim_pair_subopt(const swmi_batch *b, int64_t pair, int32_t out[2], cha
 int swmi_shim_set_end_bonus(swmi_ctx *ctx, int32_t end_bonus, char *err, size_t err_len);
 int swmi_shim_pair_end_score(const swmi_batch *b, int64_t pair, int32_t out[4], char *err, size_t err_len);
 
+/* nativeSetHits: from then on a run under nativeSetSubopt also returns every pair's best local hits with their end cells
+ * (swmi_set_option "hits"): 1 .. 16 = the most entries per pair, 0 (the default): off.  Any other value is SWMI_ERR_INVALID and leaves
+ * the context as it was.
+ * nativePairHits: *n = the pair's count after a run under that option, and out[3 k .. 3 k + 2] = entry k's score, read row and reference
+ * column (1-based), as swmi_pair_hits hands them out.  out may be NULL (the count only); cap = the entries out holds, below the count:
+ * SWMI_ERR_RANGE. */
+int swmi_shim_set_hits(swmi_ctx *ctx, int32_t hits, char *err, size_t err_len);
+int swmi_shim_pair_hits(const swmi_batch *b, int64_t pair, int32_t *out, int32_t cap, int32_t *n, char *err, size_t err_len);
+
 /* nativeSetScoreMatrix: a substitution score matrix on this context (swmi_set_score_matrix): `alphabet` = n symbols narrowed to
  * bytes (ISO-8859-1), `scores` = n * n entries, row = read base, column = reference base (n_scores must be n * n).  n = 0 clears
  * it.  Applies to the batches the context aligns from then on (on the affine kernels). */

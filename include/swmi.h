@@ -298,6 +298,24 @@ void        swmi_default_params(swmi_params *p);
  *                unchanged, and every other accessor returns what the same run with subopt = 0 returns.  The sweep keeps one row of n
  *                int32 column maxima per pair behind the pair's direction field (charged to max_workspace_bytes with it).  A run
  *                (async runs and stream slots included) takes the value set when it was asked for.
+ * hits (default 0 = off and no change; 1 .. 16 = K, the most entries a pair returns; any other value is SWMI_ERR_INVALID and leaves
+ *                the context as it was): a run under subopt also returns every pair's K BEST LOCAL HITS WITH THEIR END CELLS, read
+ *                with swmi_pair_hits: what a mapper anchors the reverse pass on (SSW's ref_end1 / read_end1, BWA's te / qe), and the
+ *                next few peaks for repeats, secondary and supplementary alignments.  hits != 0 needs subopt != 0, which gives the
+ *                mask half-width w (fixed, or SWMI_SUBOPT_AUTO per pair); with subopt = 0 the run is SWMI_ERR_UNSUPPORTED before
+ *                anything is launched, and so are the runs subopt refuses (fit, global, extend, xdrop, band_adapt, gap_open2).  In
+ *                subopt's terms, for a pair with both sides non-empty and score s > 0: row(j) = the smallest row i, 1 <= i <= m,
+ *                whose existing cell has H(i, j) = colmax(j).  Entry 0, the primary: score = s, end_j = the smallest maximum column,
+ *                end_i = row(end_j).  Entry k, 1 <= k < K: column j is eligible iff |j - c| > w for EVERY maximum column c and for
+ *                c = end_j of every entry 1 .. k - 1 (strict, 64-bit arithmetic); score = the largest colmax over the eligible
+ *                columns -- if that is 0 the list ends at k entries; end_j = the smallest eligible column that holds it, end_i =
+ *                row(end_j).  So entry 1 is exactly (score2, end2) of swmi_pair_subopt, scores do not increase from entry 1 on, and
+ *                any two listed columns are more than w apart.  A degenerate pair (s = 0) and a pair with an empty side have 0
+ *                entries.  The values do not depend on the tie mode, on cell_cap, on chunking, or on whether the pair was re-run;
+ *                swmi_pair_subopt and every other accessor return what the same run with hits = 0 returns.  Everything subopt's
+ *                scope names applies unchanged.  The sweep keeps a second row of n int32 per pair behind the row of column maxima
+ *                (charged to max_workspace_bytes with it).  A run (async runs and stream slots included) takes the value set when
+ *                it was asked for.
  * end_bonus (default 0 = off and no change; 1 .. 2^30 = the bonus b; any other value is SWMI_ERR_INVALID and leaves the context as
  *                it was): an extend run (align_mode global, extend = 1) also returns, per pair, the best score of an extension that
  *                reaches the END OF THE READ, and takes that extension when it is less than b worse than the best one anywhere
@@ -459,6 +477,16 @@ int      swmi_pair_cigar(swmi_batch *b, uint64_t pair, uint64_t k,
 int      swmi_pair_subopt(const swmi_batch *b, uint64_t pair, int32_t *score2, uint32_t *end2);
 /* all pairs at once: score2[n] and/or end2[n] (either may be NULL), n = swmi_batch_n_pairs */
 int      swmi_batch_pair_subopt(const swmi_batch *b, int32_t *score2, uint32_t *end2, uint64_t n);
+
+/* Option "hits": the pair's entries as option "hits" defines them, best first; cells are 1-based (end_i the read row, end_j the
+ * reference column), reserved is 0.  *n_hits always receives the pair's count (n_hits may be NULL); hits may be NULL, which asks for the
+ * count only; cap below the count: SWMI_ERR_RANGE.  Works under scores_only = 1 and on a stream's chunk batches; on a pair list the cells
+ * are in the segments' coordinates.  A batch whose last run had hits = 0: SWMI_ERR_UNSUPPORTED; a pair out of range: SWMI_ERR_RANGE. */
+typedef struct swmi_hit { int32_t score; uint32_t end_i, end_j, reserved; } swmi_hit;
+int      swmi_pair_hits(const swmi_batch *b, uint64_t pair, swmi_hit *hits, uint32_t cap, uint32_t *n_hits);
+/* all pairs at once: n_hits[n] and/or hits[n * cap_per_pair], pair p's entry k at hits[p * cap_per_pair + k], the entries past its count
+ * zeroed (either may be NULL); n = swmi_batch_n_pairs.  cap_per_pair below the run's K with hits given: SWMI_ERR_RANGE. */
+int      swmi_batch_pair_hits(const swmi_batch *b, swmi_hit *hits, uint32_t cap_per_pair, uint32_t *n_hits, uint64_t n);
 
 /* Option "end_bonus": the pair's max_score, end_score and end_col as that option defines them -- the best score anywhere (reported
  * whether or not the pair was taken to the end: a caller needs it to undo the choice), the best score in read row m and the

@@ -21,6 +21,7 @@ CIGAR_M, CIGAR_I, CIGAR_D, CIGAR_EQ, CIGAR_X = 0, 1, 2, 7, 8     # option "cigar
 CIGAR_CHARS = {CIGAR_M: "M", CIGAR_I: "I", CIGAR_D: "D", CIGAR_EQ: "=", CIGAR_X: "X"}
 SUBOPT_AUTO = -1     # option "subopt": the mask half-width per pair, max(m // 2, 15) (0: off; 1 .. 2^30: the half-width)
 END_BONUS_MAX = 1 << 30     # option "end_bonus": the largest bonus (0: off)
+HITS_MAX = 16        # option "hits": the most entries per pair (0: off; needs option "subopt")
 PAIR_DEGENERATE = 0x1
 PAIR_TO_END = 0x2           # option "end_bonus": the pair was taken to the read's end (flags of swmi_pair_n_alignments)
 SPEC_REVERSE = 0x1          # swmi_pair_spec.flags: both segments in reverse byte order (left extension)
@@ -46,6 +47,11 @@ class Timing(C.Structure):
                 ("cells", C.c_uint64), ("dir_bytes", C.c_uint64),
                 ("strip_fallbacks", C.c_uint32), ("col_chunks", C.c_uint32),
                 ("resident_pairs", C.c_uint32), ("tfused_pairs", C.c_uint32)]
+
+
+class Hit(C.Structure):
+    """swmi_hit: one entry of option "hits" -- a local score and the 1-based cell it ends in, 16 bytes"""
+    _fields_ = [("score", C.c_int32), ("end_i", C.c_uint32), ("end_j", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class PairSpec(C.Structure):
@@ -97,6 +103,8 @@ SYMBOLS = [
     ("swmi_batch_pair_results", C.c_int, [_P, C.POINTER(C.c_int32), _u64p, C.c_uint64]),
     ("swmi_pair_subopt", C.c_int, [_P, C.c_uint64, C.POINTER(C.c_int32), C.POINTER(C.c_uint32)]),
     ("swmi_batch_pair_subopt", C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.c_uint64]),
+    ("swmi_pair_hits", C.c_int, [_P, C.c_uint64, C.POINTER(Hit), C.c_uint32, C.POINTER(C.c_uint32)]),
+    ("swmi_batch_pair_hits", C.c_int, [_P, C.POINTER(Hit), C.c_uint32, C.POINTER(C.c_uint32), C.c_uint64]),
     ("swmi_pair_end_score", C.c_int, [_P, C.c_uint64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_uint32)]),
     ("swmi_batch_pair_end_scores", C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.c_uint64]),
     ("swmi_batch_materialise_all", C.c_int, [_P, _u64p, _u64p]),

@@ -289,6 +289,39 @@ class Batch:
                                                e2.ctypes.data_as(C.POINTER(C.c_uint32)), n))
         return s2, e2
 
+    def hits(self, pair):
+        """[(score, end_i, end_j), ...] after a run under options "subopt" and "hits": the pair's best local hits, best first, each
+        with the 1-based cell it ends in (read row, reference column; on a pair list: of the segments).  Entry 0 is the primary,
+        entry 1 is subopt(pair); an empty list for a degenerate pair or one with an empty side.  Works after a scores_only run.
+        SwmiError (SWMI_ERR_UNSUPPORTED) after a run with hits = 0."""
+        n = C.c_uint32()
+        arr = (_capi.Hit * _capi.HITS_MAX)()
+        check(self._lib.swmi_pair_hits(self._h, pair, arr, _capi.HITS_MAX, C.byref(n)))
+        return [(arr[k].score, arr[k].end_i, arr[k].end_j) for k in range(n.value)]
+
+    def hits_all(self, k=_capi.HITS_MAX):
+        """(counts uint32[n_pairs], scores int32[n_pairs, k], end_i uint32[n_pairs, k], end_j uint32[n_pairs, k]) as numpy arrays, one
+        native call; the entries past a pair's count are 0.  k: the columns, at least the run's hits (default: the most there can be)."""
+        import numpy as np
+        n = self.n_pairs()
+        cnt = np.empty(n, dtype=np.uint32)
+        raw = np.zeros((n, int(k), 4), dtype=np.uint32)
+        check(self._lib.swmi_batch_pair_hits(self._h, raw.ctypes.data_as(C.POINTER(_capi.Hit)), int(k),
+                                             cnt.ctypes.data_as(C.POINTER(C.c_uint32)), n))
+        return cnt, raw[:, :, 0].astype(np.int32), raw[:, :, 1].copy(), raw[:, :, 2].copy()
+
+    def _hit_spec(self, pair, i, j):
+        """the reverse-extension spec of a hit (i, j) of the pair: both prefixes that end in the cell, reversed"""
+        return (pair // self.n_reads, pair % self.n_reads, 0, j, 0, i, _capi.SPEC_REVERSE)
+
+    def hit_specs(self, pair=None):
+        """The pair specs of the REVERSE EXTENSIONS of the hits -- of one pair, or of every pair in pair order: for a hit (i, j) of
+        the pair (ref r, read q) the spec (r, q, 0, j, 0, i, SPEC_REVERSE), ready for Context.upload_pairs on the same sources.  An
+        extend run over them finds, per hit, where its alignment starts: the extend score equals the hit's score, and the end cell
+        of that run, mapped with PairBatch.to_source, is the alignment's first cell."""
+        pairs = range(self.n_pairs()) if pair is None else [pair]
+        return [self._hit_spec(p, i, j) for p in pairs for _, i, j in self.hits(p)]
+
     def end_score(self, pair):
         """(max_score, end_score, end_col) after an extend run under option "end_bonus": the pair's best score anywhere (whether or
         not the pair was taken to the end), its best score in the read's last row and the smallest 1-based reference column that holds
@@ -410,6 +443,14 @@ class PairBatch(Batch):
         check(self._lib.swmi_batch_set_pairs(self._ctx._h, self._h, _spec_array(specs), len(specs)))
         self._specs = specs
         return self
+
+    def _hit_spec(self, pair, i, j):
+        """... on a pair list with an unreversed spec: offset by the spec's starts.  ValueError for a reversed spec (its cells count
+        from the segments' ends: the prefixes that end in the cell are no prefixes of the sources' segments)"""
+        r, q, rs, _, qs, _, rev = self._specs[pair]
+        if rev:
+            raise ValueError("pair %d has a reversed spec: hit_specs needs unreversed segments" % pair)
+        return (r, q, rs, j, qs, i, _capi.SPEC_REVERSE)
 
     def spec(self, pair):
         """(ref, read, ref_start, ref_len, read_start, read_len, reverse) of the pair as the library holds it: lengths resolved"""

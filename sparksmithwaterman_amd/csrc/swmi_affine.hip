@@ -80,11 +80,15 @@
 //   column maximum rides down the wave with its column, and the lane that finishes a column leaves colmax(j) in a row of n int32
 //   behind the pair's fields; sw_subopt_kernel (swmi_subopt.hip) turns the row into the pair's second-best score and its end column.
 //
+// sw_affine_sweep_[long_|band_]hits[_matrix][_wide]_kernel: the local sweeps under options "subopt" and "hits" (DESIGN.md 8p), SUBOPT = 1 and
+//   HITS = 1: the smallest row that holds the column maximum rides with it and is left in a second row behind the first;
+//   sw_hits_kernel (swmi_subopt.hip) picks the pair's K best separated end cells from the two rows.
+//
 // sw_affine_sweep_[long_|band_]endb[_matrix][_wide]_kernel: the extend sweeps under option "end_bonus" (DESIGN.md 8o), ENDB = 1: the lane
 //   that owns read row m keeps the maximum of H(m, j) and its smallest column, and the wave chooses between the best cell anywhere
 //   and the best extension that reaches the read's end where it writes the pair's PairOut.
 //
-// How the 77 kernels are made: the 64 sweeps are aff_sweep_entry<RLO, RHI, MATRIX, MODE, LONG, BAND, XDROP, ADAPT, TWO, SUBOPT, ENDB> over one block function
+// How the 85 kernels are made: the 72 sweeps are aff_sweep_entry<RLO, RHI, MATRIX, MODE, LONG, BAND, XDROP, ADAPT, TWO, SUBOPT, ENDB, HITS> over one block function
 //   (aff_block8); the 13 tracebacks are aff_traceback<MODE, LONG, BAND, ADAPT, TWO>, where !LONG is the walk with one strip and !BAND the
 //   walk whose windows are the whole reference.  One macro defines the sweeps, one the tracebacks; the launchers take the
 //   run's options as one AffRun (swmi_launch.h) and pick a kernel from tables typed by signature.  The per-pair sweep is two thin bodies, aff_sweep_pair and aff_sweep_long_pair<.., BAND> (the one strip
@@ -126,11 +130,14 @@ struct AffSeam {
     int h, f;              // lanes 0..7: (H, F) of the row above the strip at the 8 columns lane 0 takes in this block
     int2 *row;             // the pair's seam row: (H, F) per column
     int f2;                // TWO: F2 of that row (f is F1)
+    uint32_t cmrs;         // HITS: dwords from an entry of cmrow to the same column's entry of the row of rows (swmi_aff_colmax_stride).  It and
+                           //   cmr stand in the struct's two padding words: a struct of more than 64 bytes renames the narrow subopt sweeps' registers
     int4 *row4;            // TWO: the pair's seam row, (H, F1, F2, -) per column: 16-byte entries, one load and one store each
     uint32_t wlane;        // the lane that writes it (63), none in the read's last strip
     uint32_t coff;         // BAND: the columns left of the strip's window (`row` starts at the window, cells are listed with global columns)
     // SUBOPT (option "subopt"; the short sweeps use these three too)
     int cm;                // lanes 0..7: the column maxima the strips above left at the 8 columns lane 0 takes in this block (strip 0, short reads: not read)
+    int cmr;               // HITS (option "hits"): lanes 0..7: the rows that hold those maxima (strip 0, short reads: not read)
     int *cmrow;            // the pair's row of column maxima, from the window's first column on
     uint32_t cmlane;       // the lane that holds a column's finished maximum and stores it: 63 in a strip, the owner of the read's last row in a short sweep
     // ENDB (option "end_bonus"; the short sweeps use it too)
@@ -154,6 +161,7 @@ struct AffState {
     int cm;                // SUBOPT: the running maximum of H over the lane's current column, rows 1 .. the lane's last (it travels with the column)
     int eg;                // ENDB: in the lane that owns read row m, the maximum of H(m, j) over the columns it has swept (INT32_MIN before the first)
     uint32_t egc;          // ... and the smallest (global, 1-based) column that holds it
+    int cmr;               // HITS: the smallest (global, 1-based) row that holds S.cm, 0 while that is the seed's 0
 };
 
 // 8 anti-diagonal steps t0 .. t0+7 (a lane outside its column range keeps its state).  The steps are a loop, not unrolled:
@@ -176,12 +184,17 @@ struct AffState {
 //   lane's rows inside the read at this column (-1 when it has none, or no column).  The move runs every step in every lane.  Lane 0
 //   starts a column at 0 (H >= 0) or, in strips 1.., at what the strips above left (Z.cm, loaded as Z.h is).  Lane Z.cmlane holds the
 //   finished maximum and stores it into the pair's row, a plain vector store.
+// HITS (option "hits", with SUBOPT): the row that holds the column maximum rides with it in S.cmr.  Inside the row loop a
+//   strictly greater hv takes the row row0 + k + 1 along with mrow; at the move a lane keeps the shifted pair unless its own mrow is
+//   strictly greater.  Rows ascend with slot, lane and strip, so strict compares everywhere leave the SMALLEST row.  The storing lane
+//   writes the row Z.cmrs dwords behind the value.  A column whose maximum is 0 keeps the seed's row 0 (it is never reported).
 // ENDB (option "end_bonus", extend runs): read row m is slot vrows - 1 of lane Z.elane (vrows is local mode's, so a pad row
 //   never owns it).  At every step with a cell that lane takes H of that slot and the column when it is strictly greater than S.eg:
 //   its columns ascend, so S.egc ends as the smallest column that holds the maximum.  The slot is picked inside the unrolled row loop,
 //   as the k == vrows test of fit mode is -- by the test k < vrows that mrow already makes, the last slot that passes it, so that no
 //   further compare mask per row is kept in SGPRs: S.h is never indexed by a run-time value.
-template <int R, bool STRICT, bool MATRIX, int MODE, bool LONG = false, bool BAND = false, bool TWO = false, bool SUBOPT = false, bool ENDB = false>
+template <int R, bool STRICT, bool MATRIX, int MODE, bool LONG = false, bool BAND = false, bool TWO = false, bool SUBOPT = false, bool ENDB = false,
+          bool HITS = false>
 __device__ __forceinline__ void aff_block8(AffState<R> &S, const uint2 rw, const uint32_t t0, const uint32_t lane,
                                            const uint32_t n, const uint32_t row0, const uint32_t vrows,
                                            const int o, const int e, const int vmat, const int vmis,
@@ -190,6 +203,7 @@ __device__ __forceinline__ void aff_block8(AffState<R> &S, const uint2 rw, const
     static_assert(!TWO || (AFF_ROW0_GAPS(MODE) && !MATRIX), "two-piece gaps: global and extend runs without a score matrix");
     static_assert(!SUBOPT || MODE == AFF_LOCAL, "subopt: local runs");
     static_assert(!ENDB || (MODE == AFF_EXTEND && !TWO && !SUBOPT), "end_bonus: one-piece extend runs");
+    static_assert(!HITS || SUBOPT, "hits: the local sweeps of option subopt");
     const int oe = o + e;
     const int oe2 = o2 + e2;                                     // (TWO)
 #pragma unroll 1
@@ -220,6 +234,7 @@ __device__ __forceinline__ void aff_block8(AffState<R> &S, const uint2 rw, const
         }
         const bool inr = c0 < n;
         int mrow = MODE == AFF_LOCAL ? -1 : (MODE == AFF_EXTEND ? INT32_MIN : 0);
+        int mrr = 0;                                             // (HITS) the smallest row of the lane that holds mrow
         if (inr) {
             int diag = S.nh_prev, up = nh, fup = nf;
             int fup2 = nf2;                                      // (TWO)
@@ -283,6 +298,7 @@ __device__ __forceinline__ void aff_block8(AffState<R> &S, const uint2 rw, const
                 fup = fn;
                 S.h[k] = hv;
                 S.e[k] = en;
+                if constexpr (HITS) { if ((uint32_t)k < vrows && hv > mrow) mrr = (int)(row0 + (uint32_t)k + 1u); }
                 if constexpr (!AFF_ROW_M_ONLY(MODE)) { if ((uint32_t)k < vrows) mrow = max(mrow, hv); }
                 else                                 { if ((uint32_t)k == vrows) mrow = hv; }
                 if constexpr (ENDB) { if ((uint32_t)k < vrows) hend = hv; }      // (the test of mrow: the last slot that passes it is vrows - 1)
@@ -298,8 +314,16 @@ __device__ __forceinline__ void aff_block8(AffState<R> &S, const uint2 rw, const
         S.nh_prev = nh;
         if constexpr (SUBOPT) {
             // (mrow is -1 in a lane without a column)
+            if constexpr (HITS) {
+                const int pc = wave_shr1(LONG ? __builtin_amdgcn_readlane(Z.cm, (int)s) : 0, S.cm);
+                const int pr = wave_shr1(LONG ? __builtin_amdgcn_readlane(Z.cmr, (int)s) : 0, S.cmr);
+                S.cmr = mrow > pc ? mrr : pr;
+                S.cm = max(pc, mrow);
+                if (inr && lane == Z.cmlane) { Z.cmrow[c0] = S.cm; Z.cmrow[c0 + Z.cmrs] = S.cmr; }
+            } else {
             S.cm = max(wave_shr1(LONG ? __builtin_amdgcn_readlane(Z.cm, (int)s) : 0, S.cm), mrow);
             if (inr && lane == Z.cmlane) Z.cmrow[c0] = S.cm;
+            }
         }
         if constexpr (AFF_ROW_M_ONLY(MODE)) {
             // row m only: the one lane that owns it, at every column (fit) or at column n (global)
@@ -439,7 +463,7 @@ __device__ __forceinline__ AffCells aff_cell_list(const FillArgs &A, const PairD
 // SUBOPT: the row of column maxima lies behind the field; the lane that owns the read's last row, lact - 1 of swmi_aff_blocks, stores
 // it -- W is sized for that lane to reach column n
 // ENDB: the bonus endb of option "end_bonus"; the lane that owns read row m tracks it, and the choice is made with the PairOut
-template <int R, bool STRICT, bool MATRIX, int MODE, bool TWO = false, bool SUBOPT = false, bool ENDB = false>
+template <int R, bool STRICT, bool MATRIX, int MODE, bool TWO = false, bool SUBOPT = false, bool ENDB = false, bool HITS = false>
 __device__ __forceinline__ void aff_sweep_pair(const FillArgs &A, const int o, const PairDesc pd, const uint32_t lane, const uint32_t nn,
                                                const int o2 = 0, const int e2 = 0, const uint32_t endb = 0u) {
     const SeqDesc rd = A.refs[pd.ref_id];
@@ -465,6 +489,7 @@ __device__ __forceinline__ void aff_sweep_pair(const FillArgs &A, const int o, c
         S.cm = 0;
         Zs.cmrow = reinterpret_cast<int *>(dir + (uint64_t)W * R * WAVE);
         Zs.cmlane = (m + (uint32_t)R - 1u) / (uint32_t)R - 1u;
+        if constexpr (HITS) { S.cmr = 0; Zs.cmrs = (uint32_t)swmi_aff_colmax_stride(n); }
     }
     if constexpr (ENDB) {
         S.eg = INT32_MIN; S.egc = 0u;
@@ -482,7 +507,7 @@ __device__ __forceinline__ void aff_sweep_pair(const FillArgs &A, const int o, c
             aff_block8<R, STRICT, MATRIX, MODE, false, false, true>(S, rw, t0, lane, n, row0, vrows, o, A.gap, A.match, A.mismatch, cells, ccap,
                                                                     AffSeam{}, o2, e2);
         } else if constexpr (SUBOPT)
-        aff_block8<R, STRICT, MATRIX, MODE, false, false, false, true>(S, rw, t0, lane, n, row0, vrows, o, A.gap, A.match, A.mismatch, cells, ccap, Zs);
+        aff_block8<R, STRICT, MATRIX, MODE, false, false, false, true, false, HITS>(S, rw, t0, lane, n, row0, vrows, o, A.gap, A.match, A.mismatch, cells, ccap, Zs);
         else if constexpr (ENDB)
         aff_block8<R, STRICT, MATRIX, MODE, false, false, false, false, true>(S, rw, t0, lane, n, row0, vrows, o, A.gap, A.match, A.mismatch, cells, ccap, Zs);
         else
@@ -550,7 +575,12 @@ __device__ __forceinline__ void aff_sweep_pair(const FillArgs &A, const int o, c
 // ENDB (option "end_bonus", extend runs): read row m lies in the last strip alone, in lane (m - 1 - 1024 (NS - 1)) / 16; the
 //   strips above name no owner (Z.elane = 0xFFFFFFFF) and leave (S.eg, S.egc) as they were set before the first.  Under BAND the row's
 //   existing cells are the columns of the last strip's window, and the column kept is global (Z.coff).  Nothing is loaded or stored.
-template <bool STRICT, bool MATRIX, int MODE, bool BAND, bool XDROP = false, bool ADAPT = false, bool TWO = false, bool SUBOPT = false, bool ENDB = false>
+// HITS (with SUBOPT): the row of rows lies swmi_aff_colmax_stride(n) dwords behind the row of column maxima and is rewritten
+//   in place with it -- the same loads by lanes 0..7 at step t0, the same stores by lane 63 at step t, so an entry of either row is read at
+//   least 63 steps before this strip overwrites it.  A strip keeps the row the strips above left unless it holds a strictly greater
+//   value: the smallest row survives the seam.
+template <bool STRICT, bool MATRIX, int MODE, bool BAND, bool XDROP = false, bool ADAPT = false, bool TWO = false, bool SUBOPT = false, bool ENDB = false,
+          bool HITS = false>
 __device__ __forceinline__ void aff_sweep_long_pair(const FillArgs &A, const int o, const PairDesc pd, const uint32_t lane, const uint32_t nn,
                                                     const uint32_t wb, const uint32_t xd = 0u, const int o2 = 0, const int e2 = 0,
                                                     const uint32_t endb = 0u) {
@@ -558,6 +588,7 @@ __device__ __forceinline__ void aff_sweep_long_pair(const FillArgs &A, const int
     static_assert(!TWO || (!XDROP && !ADAPT), "two-piece gaps: not under xdrop or band_adapt");
     static_assert(!SUBOPT || (MODE == AFF_LOCAL && !XDROP && !ADAPT && !TWO), "subopt: local runs");
     static_assert(!ENDB || (MODE == AFF_EXTEND && !XDROP && !ADAPT && !TWO && !SUBOPT), "end_bonus: one-piece extend runs without xdrop or band_adapt");
+    static_assert(!HITS || SUBOPT, "hits: the local sweeps of option subopt");
     constexpr int R = SWMI_AFF_RMAX;
     constexpr int OUT = BAND && MODE != AFF_LOCAL ? SWMI_AFF_BAND_NEG : 0;
     const SeqDesc rd = A.refs[pd.ref_id];
@@ -579,6 +610,7 @@ __device__ __forceinline__ void aff_sweep_long_pair(const FillArgs &A, const int
     int *const cmbase = SUBOPT ? reinterpret_cast<int *>(A.dir + pd.dir_off + (BAND ? swmi_aff_band_strip_off(NS, n, wb) : (uint64_t)NS * swmi_aff_strip_words(n)))
                                : nullptr;
     if constexpr (SUBOPT) { Z.cmrow = cmbase; Z.cmlane = 63u; }
+    if constexpr (HITS) Z.cmrs = (uint32_t)swmi_aff_colmax_stride(n);
     uint32_t *__restrict__ dir = A.dir + pd.dir_off;
     uint64_t inband = 0ull;                                      // BAND: in-band cells with i <= m (the degenerate count)
     uint32_t stopped = 0u;                                       // XDROP: the strips swept of a pair that was stopped, else 0
@@ -649,6 +681,7 @@ __device__ __forceinline__ void aff_sweep_long_pair(const FillArgs &A, const int
         S.rb = 0; S.f_last = 0;
         if constexpr (TWO) S.f2_last = 0;
         if constexpr (SUBOPT) S.cm = 0;
+        if constexpr (HITS) S.cmr = 0;
         // nh_prev of lane 0: H(1024 * sx, clo - 1)
         if constexpr (!BAND) S.nh_prev = MODE != AFF_LOCAL && sx ? o + (int)(sx * SWMI_AFF_MAX_READ) * A.gap : 0;
         if constexpr (!BAND && TWO) { if (sx) S.nh_prev = max(S.nh_prev, o2 + (int)(sx * SWMI_AFF_MAX_READ) * e2); }
@@ -720,6 +753,10 @@ __device__ __forceinline__ void aff_sweep_long_pair(const FillArgs &A, const int
                 // what the strips above left at lane 0's 8 columns (a vector load, behind the fence); 0 in strip 0 and beyond seam_end
                 Z.cm = 0;
                 if (sx && lane < 8u && c < seam_end) Z.cm = Z.cmrow[c];
+                if constexpr (HITS) {
+                    Z.cmr = 0;
+                    if (sx && lane < 8u && c < seam_end) Z.cmr = Z.cmrow[c + Z.cmrs];
+                }
             }
 #pragma unroll
             for (int k = 0; k < R; ++k) S.acc[k] = 0u;
@@ -727,7 +764,7 @@ __device__ __forceinline__ void aff_sweep_long_pair(const FillArgs &A, const int
 #pragma unroll
                 for (int k = 0; k < R; ++k) S.acc2[k] = 0u;
             }
-            aff_block8<R, STRICT, MATRIX, MODE, true, BAND, TWO, SUBOPT, ENDB>(S, rw, t0, lane, nw, row0, vrows, o, A.gap, A.match, A.mismatch, cells, ccap, Z, o2, e2);
+            aff_block8<R, STRICT, MATRIX, MODE, true, BAND, TWO, SUBOPT, ENDB, HITS>(S, rw, t0, lane, nw, row0, vrows, o, A.gap, A.match, A.mismatch, cells, ccap, Z, o2, e2);
             AFF_STORE_BLOCK
         }
         if constexpr (BAND && !ADAPT) dir += (uint64_t)W * (TWO ? 2 : 1) * R * WAVE;
@@ -744,12 +781,12 @@ __device__ __forceinline__ void aff_sweep_long_pair(const FillArgs &A, const int
 #undef AFF_PAIR_OUT_ENDB
 
 // RLO..RHI: the rows per lane this instantiation of the kernel takes (the others' registers would cap its occupancy)
-template <int RLO, int RHI, bool STRICT, bool MATRIX, int MODE, bool TWO = false, bool SUBOPT = false, bool ENDB = false>
+template <int RLO, int RHI, bool STRICT, bool MATRIX, int MODE, bool TWO = false, bool SUBOPT = false, bool ENDB = false, bool HITS = false>
 __device__ __forceinline__ void aff_sweep_dispatch(const FillArgs &A, const int o, const PairDesc pd, const uint32_t R, const uint32_t lane,
                                                    const uint32_t nn, const int o2 = 0, const int e2 = 0, const uint32_t endb = 0u) {
     if constexpr (RLO <= RHI) {
-        if (R == (uint32_t)RLO) aff_sweep_pair<RLO, STRICT, MATRIX, MODE, TWO, SUBOPT, ENDB>(A, o, pd, lane, nn, o2, e2, endb);
-        else aff_sweep_dispatch<RLO + 1, RHI, STRICT, MATRIX, MODE, TWO, SUBOPT, ENDB>(A, o, pd, R, lane, nn, o2, e2, endb);
+        if (R == (uint32_t)RLO) aff_sweep_pair<RLO, STRICT, MATRIX, MODE, TWO, SUBOPT, ENDB, HITS>(A, o, pd, lane, nn, o2, e2, endb);
+        else aff_sweep_dispatch<RLO + 1, RHI, STRICT, MATRIX, MODE, TWO, SUBOPT, ENDB, HITS>(A, o, pd, R, lane, nn, o2, e2, endb);
     }
 }
 
@@ -759,9 +796,10 @@ __device__ __forceinline__ void aff_sweep_dispatch(const FillArgs &A, const int 
 // ADAPT (with LONG, BAND and AFF_EXTEND): the banded strip sweep under option "band_adapt"
 // TWO (AFF_GLOBAL and AFF_EXTEND, no MATRIX, XDROP or ADAPT): two-piece gaps, the second piece's open o2 and extension e2
 // SUBOPT (AFF_LOCAL, no XDROP, ADAPT or TWO): the sweep also leaves the pair's row of column maxima (option "subopt")
+// HITS (with SUBOPT): ... and, behind it, the row of the rows that hold them (option "hits")
 // ENDB (AFF_EXTEND, no XDROP, ADAPT, TWO or SUBOPT): the sweep also finds the best score in read row m and chooses (option "end_bonus", bonus endb)
 template <int RLO, int RHI, bool MATRIX, int MODE = AFF_LOCAL, bool LONG = false, bool BAND = false, bool XDROP = false, bool ADAPT = false,
-          bool TWO = false, bool SUBOPT = false, bool ENDB = false>
+          bool TWO = false, bool SUBOPT = false, bool ENDB = false, bool HITS = false>
 __device__ __forceinline__ void aff_sweep_entry(const FillArgs &A, const int o, const uint32_t *__restrict__ mat, const uint32_t nn,
                                                 const uint32_t wb = 0u, const uint32_t xd = 0u, const int o2 = 0, const int e2 = 0,
                                                 const uint32_t endb = 0u) {
@@ -770,6 +808,7 @@ __device__ __forceinline__ void aff_sweep_entry(const FillArgs &A, const int o, 
     static_assert(!ADAPT || (LONG && BAND && MODE == AFF_EXTEND), "band_adapt is an option of the banded strip sweeps of an extend run");
     static_assert(!SUBOPT || (MODE == AFF_LOCAL && !XDROP && !ADAPT && !TWO), "subopt is an option of the local sweeps");
     static_assert(!ENDB || (MODE == AFF_EXTEND && !XDROP && !ADAPT && !TWO && !SUBOPT), "end_bonus is an option of the one-piece extend sweeps without xdrop or band_adapt");
+    static_assert(!HITS || SUBOPT, "hits is an option of the local sweeps of option subopt");
     if (blockIdx.x == 0 && threadIdx.x == 0) A.hdr->reserved = 0ull;      // the traceback's bump allocator
     if (MATRIX) {                                                          // (before any wavefront leaves)
         for (uint32_t x = threadIdx.x; x < 256u; x += WAVE * AFF_WAVES) aff_mkey[x] = mat[x];
@@ -786,14 +825,14 @@ __device__ __forceinline__ void aff_sweep_entry(const FillArgs &A, const int o, 
     const PairDesc pd = A.pairs[pair];
     if constexpr (LONG) {
         if (uni(A.reads[pd.read_id].len) <= SWMI_AFF_MAX_READ) return;
-        if (A.strict) aff_sweep_long_pair<true, MATRIX, MODE, BAND, XDROP, ADAPT, TWO, SUBOPT, ENDB>(A, o, pd, lane, nn, wb, xd, o2, e2, endb);
-        else          aff_sweep_long_pair<false, MATRIX, MODE, BAND, XDROP, ADAPT, TWO, SUBOPT, ENDB>(A, o, pd, lane, nn, wb, xd, o2, e2, endb);
+        if (A.strict) aff_sweep_long_pair<true, MATRIX, MODE, BAND, XDROP, ADAPT, TWO, SUBOPT, ENDB, HITS>(A, o, pd, lane, nn, wb, xd, o2, e2, endb);
+        else          aff_sweep_long_pair<false, MATRIX, MODE, BAND, XDROP, ADAPT, TWO, SUBOPT, ENDB, HITS>(A, o, pd, lane, nn, wb, xd, o2, e2, endb);
         return;
     }
     const uint32_t R = uni(swmi_aff_rows_per_lane(A.reads[pd.read_id].len));
     if (R < (uint32_t)RLO || R > (uint32_t)RHI) return;
-    if (A.strict) aff_sweep_dispatch<RLO, RHI, true, MATRIX, MODE, TWO, SUBOPT, ENDB>(A, o, pd, R, lane, nn, o2, e2, endb);
-    else          aff_sweep_dispatch<RLO, RHI, false, MATRIX, MODE, TWO, SUBOPT, ENDB>(A, o, pd, R, lane, nn, o2, e2, endb);
+    if (A.strict) aff_sweep_dispatch<RLO, RHI, true, MATRIX, MODE, TWO, SUBOPT, ENDB, HITS>(A, o, pd, R, lane, nn, o2, e2, endb);
+    else          aff_sweep_dispatch<RLO, RHI, false, MATRIX, MODE, TWO, SUBOPT, ENDB, HITS>(A, o, pd, R, lane, nn, o2, e2, endb);
 }
 
 }  // namespace
@@ -879,6 +918,21 @@ AFF_SWEEPS_KERNEL(sw_affine_sweep_long_subopt_matrix_kernel, SWMI_AFF_RMAX, SWMI
 AFF_SWEEPS_KERNEL(sw_affine_sweep_band_subopt_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, true, 1)
 AFF_SWEEPS_KERNEL(sw_affine_sweep_band_subopt_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, true, 1)
 #undef AFF_SWEEPS_KERNEL
+// The 8 local sweeps under option "hits" (DESIGN.md 8p), SUBOPT = 1 and HITS = 1: the subopt sweeps' shapes and signatures -- the row of
+// rows lies behind the row of column maxima, which the sweep finds.
+#define AFF_SWEEPH_KERNEL(name, RLO, RHI, MATRIX, LONG, BAND)                                                             \
+    extern "C" __global__ void __launch_bounds__(WAVE * AFF_WAVES) name(AFF_SWEEP_PARAMS_##MATRIX##BAND##0) {            \
+        aff_sweep_entry<RLO, RHI, MATRIX != 0, AFF_LOCAL, LONG, BAND != 0, false, false, false, true, false, true>(AFF_SWEEP_ARGS_##MATRIX##BAND##0); \
+    }
+AFF_SWEEPH_KERNEL(sw_affine_sweep_hits_kernel, 1, 4, 0, false, 0)
+AFF_SWEEPH_KERNEL(sw_affine_sweep_hits_wide_kernel, 5, SWMI_AFF_RMAX, 0, false, 0)
+AFF_SWEEPH_KERNEL(sw_affine_sweep_long_hits_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, true, 0)
+AFF_SWEEPH_KERNEL(sw_affine_sweep_hits_matrix_kernel, 1, 4, 1, false, 0)
+AFF_SWEEPH_KERNEL(sw_affine_sweep_hits_matrix_wide_kernel, 5, SWMI_AFF_RMAX, 1, false, 0)
+AFF_SWEEPH_KERNEL(sw_affine_sweep_long_hits_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, true, 0)
+AFF_SWEEPH_KERNEL(sw_affine_sweep_band_hits_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, true, 1)
+AFF_SWEEPH_KERNEL(sw_affine_sweep_band_hits_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, true, 1)
+#undef AFF_SWEEPH_KERNEL
 // The 8 extend sweeps under option "end_bonus" (DESIGN.md 8o), ENDB = 1: narrow, wide, long and banded long, each plain and with a score
 // matrix, with the signatures of their ENDB = 0 twins and the bonus as one more scalar, the last.
 #define AFF_SWEEPE_KERNEL(name, RLO, RHI, MATRIX, LONG, BAND)                                                             \
@@ -1222,12 +1276,16 @@ extern "C" hipError_t swmi_launch_affine_sweep(const FillArgs *a, const AffRun *
         {sw_affine_sweep2_global_wide_kernel, sw_affine_sweep2_extend_wide_kernel},
         {sw_affine_sweep2_long_global_kernel, sw_affine_sweep2_long_extend_kernel}};
     static void (*const tbplain[2])(FillArgs, int, int, int, uint32_t) = {sw_affine_sweep2_band_global_kernel, sw_affine_sweep2_band_extend_kernel};
-    // the local sweeps under option "subopt", [narrow / wide / long], and the banded long ones
-    static void (*const splain[3])(FillArgs, int) = {sw_affine_sweep_subopt_kernel, sw_affine_sweep_subopt_wide_kernel, sw_affine_sweep_long_subopt_kernel};
-    static void (*const smatrix[3])(FillArgs, int, const uint32_t *, uint32_t) = {
-        sw_affine_sweep_subopt_matrix_kernel, sw_affine_sweep_subopt_matrix_wide_kernel, sw_affine_sweep_long_subopt_matrix_kernel};
-    static void (*const sbplain)(FillArgs, int, uint32_t) = sw_affine_sweep_band_subopt_kernel;
-    static void (*const sbmatrix)(FillArgs, int, const uint32_t *, uint32_t, uint32_t) = sw_affine_sweep_band_subopt_matrix_kernel;
+    // the local sweeps under option "subopt", [with option "hits"][narrow / wide / long], and [hits] of the banded long ones
+    static void (*const splain[2][3])(FillArgs, int) = {
+        {sw_affine_sweep_subopt_kernel, sw_affine_sweep_subopt_wide_kernel, sw_affine_sweep_long_subopt_kernel},
+        {sw_affine_sweep_hits_kernel, sw_affine_sweep_hits_wide_kernel, sw_affine_sweep_long_hits_kernel}};
+    static void (*const smatrix[2][3])(FillArgs, int, const uint32_t *, uint32_t) = {
+        {sw_affine_sweep_subopt_matrix_kernel, sw_affine_sweep_subopt_matrix_wide_kernel, sw_affine_sweep_long_subopt_matrix_kernel},
+        {sw_affine_sweep_hits_matrix_kernel, sw_affine_sweep_hits_matrix_wide_kernel, sw_affine_sweep_long_hits_matrix_kernel}};
+    static void (*const sbplain[2])(FillArgs, int, uint32_t) = {sw_affine_sweep_band_subopt_kernel, sw_affine_sweep_band_hits_kernel};
+    static void (*const sbmatrix[2])(FillArgs, int, const uint32_t *, uint32_t, uint32_t) = {
+        sw_affine_sweep_band_subopt_matrix_kernel, sw_affine_sweep_band_hits_matrix_kernel};
     // the extend sweeps under option "end_bonus" (the bonus is the last argument), [narrow / wide / long], and the banded long ones
     static void (*const eplain[3])(FillArgs, int, uint32_t) = {sw_affine_sweep_endb_kernel, sw_affine_sweep_endb_wide_kernel, sw_affine_sweep_long_endb_kernel};
     static void (*const ematrix[3])(FillArgs, int, const uint32_t *, uint32_t, uint32_t) = {
@@ -1240,14 +1298,15 @@ extern "C" hipError_t swmi_launch_affine_sweep(const FillArgs *a, const AffRun *
     const uint32_t mode = r->mode, band = long_reads ? r->band : 0u, xdrop = long_reads ? r->xdrop : 0u;      // (options of the long shape only)
     const uint32_t adapt = band ? r->adapt : 0u, nn = r->nn;
     const uint32_t *const mat = r->mat;
+    const uint32_t hits = r->hits ? 1u : 0u;                      // (aff_run_ok: with subopt only)
     const uint32_t endb = r->end_bonus;                           // (aff_run_ok: an extend run without xdrop, band_adapt or gap_open2)
     const auto sweep = [&](int shape) {
         if (r->gap_open2 && band)  launch(tbplain[mode - 2u], (int)r->gap_open2, (int)r->gap2, band);
         else if (r->gap_open2)     launch(tplain[shape][mode - 2u], (int)r->gap_open2, (int)r->gap2);
-        else if (r->subopt && mat && band) launch(sbmatrix, mat, nn, band);
-        else if (r->subopt && mat) launch(smatrix[shape], mat, nn);
-        else if (r->subopt && band) launch(sbplain, band);
-        else if (r->subopt)        launch(splain[shape]);
+        else if (r->subopt && mat && band) launch(sbmatrix[hits], mat, nn, band);
+        else if (r->subopt && mat) launch(smatrix[hits][shape], mat, nn);
+        else if (r->subopt && band) launch(sbplain[hits], band);
+        else if (r->subopt)        launch(splain[hits][shape]);
         else if (endb && mat && band) launch(ebmatrix, mat, nn, band, endb);
         else if (endb && mat)      launch(ematrix[shape], mat, nn, endb);
         else if (endb && band)     launch(ebplain, band, endb);

@@ -201,6 +201,10 @@ extern "C" int swmi_set_option(swmi_ctx *ctx, const char *name, int64_t value) {
         if (value < SWMI_SUBOPT_AUTO || value > (1ll << 30))
             return fail(SWMI_ERR_INVALID, "subopt must be 0 (off), a mask half-width of 1 .. 2^30 columns or -1 (SWMI_SUBOPT_AUTO), got %lld", (long long)value);
         ctx->modes.subopt = (int)value;
+    } else if (!strcmp(name, "hits")) {
+        if (value < 0 || value > (int64_t)SWMI_HITS_MAX)
+            return fail(SWMI_ERR_INVALID, "hits must be 0 (off) or 1 .. %u entries per pair, got %lld", SWMI_HITS_MAX, (long long)value);
+        ctx->modes.hits = (int)value;
     } else if (!strcmp(name, "end_bonus")) {
         if (value < 0 || value > (1ll << 30))
             return fail(SWMI_ERR_INVALID, "end_bonus must be 0 (off) or a bonus of 1 .. 2^30, got %lld", (long long)value);

@@ -369,7 +369,8 @@ struct AffGeom {
     uint32_t band;       // option "band": the half-width, 0: none (it shapes the fields of reads longer than SWMI_AFF_MAX_READ only)
     bool adapt, two;     // options "band_adapt" (with band, never with two) and "gap_open2"
     bool subopt;         // option "subopt" (local runs: never with adapt or two): the pair's row of column maxima behind its fields
-    bool operator==(const AffGeom &o) const { return band == o.band && adapt == o.adapt && two == o.two && subopt == o.subopt; }
+    bool hits;           // option "hits" (with subopt only): a second row behind that one, the smallest row that holds each column's maximum
+    bool operator==(const AffGeom &o) const { return band == o.band && adapt == o.adapt && two == o.two && subopt == o.subopt && hits == o.hits; }
 };
 // dwords of the pair's direction fields (m > 1024: the strips', consecutive) = where the window table of "band_adapt" or the
 // row of column maxima of "subopt" starts
@@ -388,12 +389,22 @@ SWMI_HD static inline uint32_t swmi_aff_colmax_cols(uint32_t m, uint32_t n, uint
 }
 // what sw_subopt_kernel (swmi_subopt.hip) makes of the row, per pair: swmi.h's score2 and end2
 struct SuboptOut { int32_t score2; uint32_t end2; };
+// ---- option "hits" (with "subopt"): TWO ROWS, not one row of pairs.  The row of column maxima stays where and what it
+// is under "subopt" alone; a second row of the same rounded length follows it and holds row(j), the smallest (1-based, global) read row
+// with H(i, j) = colmax(j), at dword j - 1.  sw_hits_kernel passes over the values up to 2 K times and reads a row index K times: the
+// passes stay dense 4-byte loads, and the sweeps' cmrow pointer and the in-place rewrite serve both rows with one stride.  row(j) is
+// meaningful where colmax(j) > 0 (a column of zeros keeps the seed's 0); no other column is ever reported. ----
+#define SWMI_HITS_MAX 16u
+SWMI_HD static inline uint64_t swmi_aff_colmax_stride(uint32_t n) { return ((uint64_t)n + 63u) & ~63ull; }
+// what sw_hits_kernel (swmi_subopt.hip) makes of the two rows, per pair: 1 + K entries of 16 bytes -- entry 0 is (n_hits, 0, 0, 0), entries
+// 1 .. n_hits are swmi.h's swmi_hit k - 1, the rest is zero
+struct HitEnt { int32_t score; uint32_t end_i, end_j, reserved; };
 // what the pair is charged in the launch's `dir` workspace: the fields and, under "band_adapt", the table -- one dword per strip --
-// or, under "subopt", the row of column maxima -- one per column; either rounded to 64 dwords so that the next pair's field stays
-// 256-byte aligned
+// or, under "subopt", the row of column maxima -- one per column, and under "hits" the row of their rows behind it; each rounded to 64
+// dwords so that the next pair's field stays 256-byte aligned
 SWMI_HD static inline uint64_t swmi_aff_pair_dir_words(uint32_t m, uint32_t n, AffGeom g) {
     return swmi_aff_pair_table_off(m, n, g) + (g.band && g.adapt && m > SWMI_AFF_MAX_READ ? ((uint64_t)swmi_aff_strips(m) + 63u) & ~63ull : 0ull) +
-           (g.subopt ? ((uint64_t)n + 63u) & ~63ull : 0ull);
+           (g.subopt ? (g.hits ? 2ull : 1ull) * (((uint64_t)n + 63u) & ~63ull) : 0ull);
 }
 // dwords of the pair's seam row: (H, F) per column, two-piece 16 bytes; ONE row, rewritten in place by every strip but the last
 SWMI_HD static inline uint64_t swmi_aff_pair_seam_words(uint32_t m, uint32_t n, AffGeom g) { return m > SWMI_AFF_MAX_READ ? (g.two ? 4ull : 2ull) * n : 0ull; }

@@ -124,6 +124,7 @@ struct __attribute__((visibility("hidden"))) RunModes {
     int gap2 = 0;                           // ... and its per-base extension (not read while gap_open2 == 0)
     int cigar = 0;                          // 1 / 2: the records' payload is a CIGAR, M/I/D or =/X/I/D (swmi.h); the affine kernels
     int subopt = 0;                         // != 0: a local run also returns every pair's second-best score -- the mask half-width, -1 automatic (swmi.h); refused in the other modes
+    int hits = 0;                           // 1 .. 16 = K: a run under subopt also returns every pair's K best separated end cells (swmi.h); refused without subopt
     int end_bonus = 0;                      // > 0: an extend run also returns every pair's best score in read row m and takes the pair to the read's end when that is less than this bonus below the best score (swmi.h); refused in other runs
     bool two_piece() const { return gap_open2 != 0; }
     // the MODE of the affine kernels and their launchers: the align_mode, or 3 (extend) for a global run with option "extend"
@@ -143,7 +144,7 @@ static inline bool swmi_adapt_bound_ok(uint64_t m, uint64_t n, int64_t gap_open,
 }
 // the options that decide the size of a mode-3 pair's workspace (swmi_device.h), as a run has them
 static inline AffGeom aff_geom(const RunModes &md) {
-    return AffGeom{md.band > 0 ? (uint32_t)md.band : 0u, md.band > 0 && md.band_adapt != 0, md.two_piece(), md.subopt != 0};
+    return AffGeom{md.band > 0 ? (uint32_t)md.band : 0u, md.band > 0 && md.band_adapt != 0, md.two_piece(), md.subopt != 0, md.subopt != 0 && md.hits != 0};
 }
 // Everything a batch's schedule (swmi_batch::work: the pairs in launch order with their workspace sizes) depends on besides the
 // sequences.  A run whose key equals the key of the schedule the batch holds keeps it.  An input of the sizes that is missing
@@ -201,7 +202,7 @@ struct swmi_ctx {
     bool cell_cap_set = false;              // cell_cap given by the caller (otherwise small launches get longer lists)
     int32_t gap_open = 0;                   // affine gaps: a gap of length k costs gap_open + k * gap (0: linear)
     int affine = -1;                        // -1: the affine kernels (mode 3) when gap_open != 0; 1: always
-    RunModes modes;                         // options "align_mode", "long_reads", "band", "extend", "xdrop", "band_adapt", "gap_open2", "gap2", "cigar", "subopt" and "end_bonus"
+    RunModes modes;                         // options "align_mode", "long_reads", "band", "extend", "xdrop", "band_adapt", "gap_open2", "gap2", "cigar", "subopt", "hits" and "end_bonus"
     std::mutex mat_mu;                      // guards `matrix` (not ctx->mu: setting a matrix does not wait for a run)
     std::shared_ptr<const ScoreMatrix> matrix;   // swmi_set_score_matrix; a run with one takes the affine kernels
     // swmi_batch_run_async: one run in flight on the context's own host thread
@@ -347,6 +348,8 @@ struct swmi_batch {
     std::vector<PairRes> pairs;             // by pair index
     bool has_sub = false;                   // the last run had option "subopt": `sub` holds every pair's (score2, end2), (0, 0) for a pair that was not swept
     std::vector<SuboptOut> sub;                // by pair index
+    int hits_k = 0;                         // the last run had option "hits" = hits_k (0: none): `hitv` holds 1 + hits_k entries per pair (swmi_device.h: HitEnt), zeros for a pair that was not swept
+    std::vector<HitEnt> hitv;               // by pair index
     bool has_endb = false;                  // the last run had option "end_bonus": `endv` holds every pair's (max_score, end_score, end_col), (0, 0, 0) for a pair that was not swept
     std::vector<EndOut> endv;               // by pair index
     // option "band_adapt": the window tables the sweeps of the last run left (the centre of every strip, swmi_device.h), fetched
@@ -401,9 +404,11 @@ struct RunState {
 
 // layout of the result block: [ArenaHdr | PairOut x np | sub: SuboptOut x np (option "subopt") or EndOut x np (option "end_bonus"), else nothing |
 //                              record table, tab_cap entries | arena words ...]
-// sub: the bytes per pair of that array -- the two options exclude each other, so they share the place
+// sub: the bytes per pair of that array -- the two options exclude each other, so they share the place.  Option "hits" (with "subopt"):
+// a second array, (1 + K) HitEnt per pair, follows the SuboptOut array at result_hits_off and counts in `sub`
 static inline size_t result_out_off() { return 64; }
 static inline size_t result_sub_off(size_t np) { return 64 + np * sizeof(PairOut); }
+static inline size_t result_hits_off(size_t np) { return result_sub_off(np) + np * sizeof(SuboptOut); }
 static inline size_t result_tab_off(size_t np, size_t sub) { return (64 + np * (sizeof(PairOut) + sub) + 255) & ~(size_t)255; }
 static inline size_t result_arena_off(size_t np, uint64_t tab_cap, size_t sub) { return (result_tab_off(np, sub) + tab_cap * sizeof(AlnRec) + 255) & ~(size_t)255; }
 // dwords of one alignment's payload: the two strings, n_ops / 4 + 1 dwords each, or the ops packed 16 per dword (swmi_emit.h)

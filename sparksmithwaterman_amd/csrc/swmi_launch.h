@@ -31,6 +31,7 @@ struct AffRun {
     uint32_t nn;                 // ... and its side n + 1 (2 .. SWMI_MAT_NN_MAX)
     uint32_t cigar;              // option "cigar" (0: off; 1: M/I/D, 2: =/X/I/D) -- the payload the walks write (swmi_emit.h); the sweeps do not read it
     int32_t subopt;              // option "subopt" (0: off; 1 .. 2^30: the mask half-width, -1: per pair) -- the local sweeps that leave the column maxima
+    uint32_t hits;               // option "hits" (0: off; 1 .. 16 = K, with subopt only) -- the local sweeps that leave the maxima's rows as well
     uint32_t end_bonus;          // option "end_bonus" (0: off; 1 .. 2^30: the bonus) -- the extend sweeps that also choose the read's end
 };
 // What the launchers refuse (hipErrorInvalidValue): the combinations no kernel exists for.  band, xdrop and adapt are options of
@@ -41,6 +42,7 @@ static inline bool aff_run_ok(const AffRun &r, uint32_t long_reads) {
     if (r.mat && (r.nn < 2u || r.nn > SWMI_MAT_NN_MAX)) return false;
     if (r.gap_open2 && (r.mode < 2u || r.mat || r.xdrop || r.adapt)) return false;      // two-piece: plain global and extend runs
     if (r.subopt < -1 || r.subopt > (1 << 30) || (r.subopt && r.mode != 0u)) return false;   // subopt: local runs
+    if (r.hits > SWMI_HITS_MAX || (r.hits && !r.subopt)) return false;                   // hits: runs under subopt
     // end_bonus: one-piece extend runs without xdrop or band_adapt
     if (r.end_bonus > (1u << 30) || (r.end_bonus && (r.mode != 3u || r.xdrop || r.adapt || r.gap_open2 || r.subopt))) return false;
     if (long_reads && r.xdrop && r.mode != 3u) return false;                            // xdrop: extend runs
@@ -69,6 +71,16 @@ struct SuboptArgs {
     int32_t subopt;              // the mask half-width, or -1: max(m / 2, 15) per pair
 };
 extern "C" hipError_t swmi_launch_subopt(const SuboptArgs *a, hipStream_t st);
+// Option "hits" (swmi_subopt.hip): sw_hits_kernel IN PLACE OF sw_subopt_kernel on such a run, one wavefront per pair.  It reads the
+// pair's score and its two rows -- the column maxima and, swmi_aff_colmax_stride(n) dwords behind, their rows -- and writes the pair's
+// SuboptOut as sw_subopt_kernel would and its 1 + K HitEnt (swmi_device.h).
+struct HitsArgs {
+    SuboptArgs s;                // as for sw_subopt_kernel
+    HitEnt *hits;                // (1 + k) entries per out_id, device memory
+    HitEnt *hits_host;           // zero-copy results: its host-mapped mirror, or null
+    uint32_t k;                  // option "hits": 1 .. SWMI_HITS_MAX
+};
+extern "C" hipError_t swmi_launch_hits(const HitsArgs *a, hipStream_t st);
 extern "C" hipError_t swmi_launch_encode(const uint8_t *raw, const uint64_t *raw_off, SeqDesc *desc, uint32_t *seqw,
                                          const uint8_t *lut, uint32_t n_seq, hipStream_t st);
 // pair lists: the segments' images (and the raw bytes of reversed segments) from the resident sources (sw_gather_kernel)

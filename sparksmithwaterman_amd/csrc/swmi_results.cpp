@@ -217,6 +217,40 @@ extern "C" int swmi_batch_pair_subopt(const swmi_batch *b, int32_t *score2, uint
     return SWMI_OK;
 }
 
+// option "hits": the pair's K best separated local end cells (swmi.h); `hitv` holds 1 + K entries per pair, the count first
+extern "C" int swmi_pair_hits(const swmi_batch *b, uint64_t pair, swmi_hit *hits, uint32_t cap, uint32_t *n_hits) {
+    int rc = check_pair(b, pair);
+    if (rc) return rc;
+    if (!b->hits_k) return fail(SWMI_ERR_UNSUPPORTED, "the batch was run with hits = 0: there is no list of hits");
+    const HitEnt *e = b->hitv.data() + pair * (size_t)(1 + b->hits_k);
+    const uint32_t cnt = (uint32_t)e[0].score;
+    if (n_hits) *n_hits = cnt;
+    if (!hits) return SWMI_OK;
+    if (cap < cnt) return fail(SWMI_ERR_RANGE, "pair %llu has %u hits, the array holds %u", (unsigned long long)pair, cnt, cap);
+    for (uint32_t k = 0; k < cnt; k++) hits[k] = swmi_hit{e[1 + k].score, e[1 + k].end_i, e[1 + k].end_j, 0u};
+    return SWMI_OK;
+}
+
+extern "C" int swmi_batch_pair_hits(const swmi_batch *b, swmi_hit *hits, uint32_t cap_per_pair, uint32_t *n_hits, uint64_t n) {
+    if (!b) return fail(SWMI_ERR_INVALID, "batch is null");
+    if (!b->has_run) return fail(SWMI_ERR_INVALID, "batch has no results (run it first)");
+    if (!b->hits_k) return fail(SWMI_ERR_UNSUPPORTED, "the batch was run with hits = 0: there is no list of hits");
+    if (n != batch_n_pairs(b)) return fail(SWMI_ERR_RANGE, "the batch has %llu pairs, not %llu",
+                                           (unsigned long long)batch_n_pairs(b), (unsigned long long)n);
+    if (hits && cap_per_pair < (uint32_t)b->hits_k)
+        return fail(SWMI_ERR_RANGE, "the run had hits = %d, the array holds %u entries per pair", b->hits_k, cap_per_pair);
+    const size_t per = 1 + (size_t)b->hits_k;
+    for (uint64_t p = 0; p < n; p++) {
+        const HitEnt *e = b->hitv.data() + p * per;
+        const uint32_t cnt = (uint32_t)e[0].score;
+        if (n_hits) n_hits[p] = cnt;
+        if (!hits) continue;
+        for (uint32_t k = 0; k < cap_per_pair; k++)
+            hits[p * cap_per_pair + k] = k < cnt ? swmi_hit{e[1 + k].score, e[1 + k].end_i, e[1 + k].end_j, 0u} : swmi_hit{0, 0u, 0u, 0u};
+    }
+    return SWMI_OK;
+}
+
 // option "end_bonus": the pair's best score anywhere, its best score in read row m and that score's first column (swmi.h)
 extern "C" int swmi_pair_end_score(const swmi_batch *b, uint64_t pair, int32_t *max_score, int32_t *end_score, uint32_t *end_col) {
     int rc = check_pair(b, pair);

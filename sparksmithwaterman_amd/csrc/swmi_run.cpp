@@ -53,7 +53,9 @@ struct Launch {
     bool sweep_only = false;                // option scores_only
     bool sub = false;                       // option "subopt": the result block holds a SuboptOut per pair behind the pair outputs
     bool endb = false;                      // option "end_bonus": ... an EndOut per pair, in the same place (the two options exclude each other)
-    size_t sub_bytes() const { return sub ? sizeof(SuboptOut) : endb ? sizeof(EndOut) : 0; }      // per pair, behind the pair outputs
+    uint32_t hits = 0;                      // option "hits" (with sub): K -- behind the SuboptOut array, 1 + K HitEnt per pair
+    size_t hit_bytes() const { return hits ? (1u + hits) * sizeof(HitEnt) : 0; }
+    size_t sub_bytes() const { return sub ? sizeof(SuboptOut) + hit_bytes() : endb ? sizeof(EndOut) : 0; }      // per pair, behind the pair outputs
     bool time_all = false;                  // (profiling = 2: only the sweep is bracketed -- two marker packets per run instead of three; each costs ~3.5 us of the step)
     uint64_t arena_cap = 0, tab_cap = 0;    // grown by an attempt that overflowed
     // per attempt
@@ -257,6 +259,7 @@ static inline AffRun aff_run(const swmi_batch *b) {
     r.nn = b->opt.mat ? b->opt.mat->n + 1u : 0u;
     r.cigar = (uint32_t)md.cigar;
     r.subopt = md.subopt;
+    r.hits = (uint32_t)md.hits;
     r.end_bonus = (uint32_t)md.end_bonus;
     return r;
 }
@@ -302,6 +305,15 @@ static int enqueue_launches(RunState &rs, Launch &L, const ResidentArgs &xa, con
         sa.sub = (SuboptOut *)(L.res + result_sub_off(np));
         sa.sub_host = L.zc && !L.sweep_only ? (SuboptOut *)((uint8_t *)b->h_result.dp + result_sub_off(np)) : nullptr;
         sa.n_pairs = (uint32_t)np; sa.band = b->opt.modes.band > 0 ? (uint32_t)b->opt.modes.band : 0u; sa.subopt = ar.subopt;
+        if (L.hits) {
+            // option "hits": sw_hits_kernel in its place -- it writes the SuboptOut array as well, and the HitEnt array behind it
+            HitsArgs ha{};
+            ha.s = sa;
+            ha.hits = (HitEnt *)(L.res + result_hits_off(np));
+            ha.hits_host = sa.sub_host ? (HitEnt *)((uint8_t *)b->h_result.dp + result_hits_off(np)) : nullptr;
+            ha.k = L.hits;
+            HIP_TRY(swmi_launch_hits(&ha, ctx->stream));
+        } else
         HIP_TRY(swmi_launch_subopt(&sa, ctx->stream));
     }
     if (n_tf) HIP_TRY(swmi_launch_tfused(&ta, &xt, ctx->stream));             // (sweep AND traceback of its pairs: timed with the sweep)
@@ -411,7 +423,8 @@ static int collect_launch(RunState &rs, Launch &L, Clock::time_point t_done, std
     if (!zc) overflow = hdr_words > L.arena_cap || hdr_recs > L.tab_cap;
     if (overflow) {            // records were dropped: grow to the exact need and redo the traceback
         // (option "end_bonus": the sweeps' EndOut array behind the pair outputs is carried along -- no kernel of the retry writes it)
-        const size_t keep = np * (sizeof(PairOut) + (L.endb ? sizeof(EndOut) : 0));
+        // (option "hits": the SuboptOut and HitEnt arrays are carried too -- sw_hits_kernel writes them again on the retry, the same values)
+        const size_t keep = np * (sizeof(PairOut) + (L.endb || L.hits ? L.sub_bytes() : 0));
         if (zc) {
             saved_outs.resize(keep);
             HIP_TRY(hipMemcpy(saved_outs.data(), L.res + result_out_off(), saved_outs.size(), hipMemcpyDeviceToHost));
@@ -517,6 +530,7 @@ static int run_chunk(RunState &rs, const std::vector<Work> &work, size_t lo, siz
     L.sweep_only = ctx->scores_only != 0 && !cells_exact;
     L.time_all = ctx->profiling == 1;
     L.sub = b->eff_mode == 3 && b->opt.modes.subopt != 0;
+    L.hits = L.sub ? (uint32_t)b->opt.modes.hits : 0u;
     L.endb = b->eff_mode == 3 && b->opt.modes.end_bonus != 0;
 
     const auto c0 = Clock::now();
@@ -574,6 +588,12 @@ static int run_chunk(RunState &rs, const std::vector<Work> &work, size_t lo, siz
             // part of the D2H copy.  The exact-size re-run of a pair computes the same values and overwrites them.
             const SuboptOut *hs = (const SuboptOut *)((const uint8_t *)b->h_result.p + result_sub_off(np));
             for (size_t k = 0; k < np; k++) b->sub[work[lo + k].pair] = hs[k];
+        }
+        if (L.hits) {
+            // option "hits": likewise the launch's 1 + K entries per pair
+            const HitEnt *hh = (const HitEnt *)((const uint8_t *)b->h_result.p + result_hits_off(np));
+            const size_t per = 1u + L.hits;
+            for (size_t k = 0; k < np; k++) std::copy(hh + k * per, hh + (k + 1) * per, b->hitv.begin() + (size_t)work[lo + k].pair * per);
         }
         if (L.endb) {
             // option "end_bonus": the launch's (max_score, end_score, end_col), in the host block by now -- part of a D2H copy on every
@@ -657,6 +677,9 @@ static int check_run_params(const swmi_ctx *ctx, const swmi_batch *b, const swmi
     // and gap_open2, options of a global run
     if (md.subopt != 0 && md.align_mode != SWMI_ALIGN_LOCAL)
         return fail(SWMI_ERR_UNSUPPORTED, "subopt = %d needs align_mode local (0), got align_mode %d", md.subopt, md.align_mode);
+    // option "hits": the K-round pick runs on the rows the sweeps of option "subopt" leave, which also gives the mask half-width
+    if (md.hits != 0 && md.subopt == 0)
+        return fail(SWMI_ERR_UNSUPPORTED, "hits = %d needs a run under subopt (the mask half-width, or -1), got subopt 0", md.hits);
     // option "end_bonus": the to-end score is defined, and built, for one-piece extend runs whose sweep reaches read row m with the
     // static windows -- the linear pipeline has no such run, and an extend run takes the affine kernels anyway
     if (md.end_bonus != 0) {
@@ -952,6 +975,8 @@ static int batch_run(swmi_ctx *ctx, swmi_batch *b, const swmi_params *p, RunOpti
     b->win_tab.clear(); b->win_at.clear();
     b->has_sub = opt.modes.subopt != 0;
     b->sub.assign(b->has_sub ? batch_n_pairs(b) : 0, SuboptOut{0, 0u});     // (a pair with an empty side is never swept: (0, 0))
+    b->hits_k = b->has_sub ? opt.modes.hits : 0;
+    b->hitv.assign(b->hits_k ? batch_n_pairs(b) * (size_t)(1 + b->hits_k) : 0, HitEnt{0, 0u, 0u, 0u});      // (... 0 entries)
     b->has_endb = opt.modes.end_bonus != 0;
     b->endv.assign(b->has_endb ? batch_n_pairs(b) : 0, EndOut{0, 0, 0u});   // (... (0, 0, 0))
     b->alns.clear(); b->str_at.clear();

@@ -99,6 +99,9 @@ static int stream_process(swmi_stream *s, swmi_stream::Slot &sl, StreamChunk *c)
     // (option "subopt": every pair's second-best score, kept whether or not the records are)
     r->has_sub = b->has_sub; r->sub = std::move(b->sub);
     b->has_sub = false; b->sub.clear();
+    // (option "hits": likewise every pair's entries)
+    r->hits_k = b->hits_k; r->hitv = std::move(b->hitv);
+    b->hits_k = 0; b->hitv.clear();
     // (option "end_bonus": likewise every pair's max_score, end_score and end_col)
     r->has_endb = b->has_endb; r->endv = std::move(b->endv);
     b->has_endb = false; b->endv.clear();
