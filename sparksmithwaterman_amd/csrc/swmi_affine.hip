@@ -88,10 +88,13 @@
 //   that owns read row m keeps the maximum of H(m, j) and its smallest column, and the wave chooses between the best cell anywhere
 //   and the best extension that reaches the read's end where it writes the pair's PairOut.
 //
-// How the 85 kernels are made: the 72 sweeps are aff_sweep_entry<RLO, RHI, MATRIX, MODE, LONG, BAND, XDROP, ADAPT, TWO, SUBOPT, ENDB, HITS> over one block function
-//   (aff_block8); the 13 tracebacks are aff_traceback<MODE, LONG, BAND, ADAPT, TWO>, where !LONG is the walk with one strip and !BAND the
-//   walk whose windows are the whole reference.  One macro defines the sweeps, one the tracebacks; the launchers take the
-//   run's options as one AffRun (swmi_launch.h) and pick a kernel from tables typed by signature.  The per-pair sweep is two thin bodies, aff_sweep_pair and aff_sweep_long_pair<.., BAND> (the one strip
+// How the 85 kernels are made: two lists, AFF_SWEEPS (72 rows) and AFF_TRACEBACKS (13), name every kernel with its
+//   MODE and its flags; the kernel definitions, their parameter lists and the launchers' tables are the lists under a macro each,
+//   and the file defines no kernel outside them.  A sweep is aff_sweep_entry<RLO, RHI, MODE, F> over one block function
+//   (aff_block8), a traceback aff_traceback<MODE, F>, F being the row's flags as one word (AFF_F_ of swmi_launch.h; !LONG is the
+//   walk with one strip and !BAND the walk whose windows are the whole reference).  Which combinations may exist is aff_flags_ok
+//   there, asserted for every row; the launchers take the run's options as one AffRun and search their table for the run's key.
+//   The per-pair sweep is two thin bodies, aff_sweep_pair and aff_sweep_long_pair (the one strip
 //   loop, banded or not), over shared pieces: vrows and the cell list as functions of values, the row load, the block store
 //   and the epilogue as text (DESIGN.md 8e and 8f say why).
 #include <hip/hip_runtime.h>
@@ -118,6 +121,12 @@
 // the modes that sweep global mode's cells (row 0 is o + j*e), and the ones whose maximum is taken over row m alone
 #define AFF_ROW0_GAPS(MODE) ((MODE) == AFF_GLOBAL || (MODE) == AFF_EXTEND)
 #define AFF_ROW_M_ONLY(MODE) ((MODE) == AFF_FIT || (MODE) == AFF_GLOBAL)
+// The device templates take MODE and one flags word F (the AFF_F_ bits of swmi_launch.h); each opens with the bits under the
+// names its body uses
+#define AFF_FLAG_NAMES(F)                                                                                                           \
+    [[maybe_unused]] constexpr bool MATRIX = ((F) & AFF_F_MATRIX) != 0, LONG = ((F) & AFF_F_LONG) != 0, BAND = ((F) & AFF_F_BAND) != 0, \
+                                    XDROP = ((F) & AFF_F_XDROP) != 0, ADAPT = ((F) & AFF_F_ADAPT) != 0, TWO = ((F) & AFF_F_TWO) != 0, \
+                                    SUBOPT = ((F) & AFF_F_SUBOPT) != 0, ENDB = ((F) & AFF_F_ENDB) != 0, HITS = ((F) & AFF_F_HITS) != 0;
 
 namespace {
 
@@ -193,17 +202,12 @@ struct AffState {
 //   its columns ascend, so S.egc ends as the smallest column that holds the maximum.  The slot is picked inside the unrolled row loop,
 //   as the k == vrows test of fit mode is -- by the test k < vrows that mrow already makes, the last slot that passes it, so that no
 //   further compare mask per row is kept in SGPRs: S.h is never indexed by a run-time value.
-template <int R, bool STRICT, bool MATRIX, int MODE, bool LONG = false, bool BAND = false, bool TWO = false, bool SUBOPT = false, bool ENDB = false,
-          bool HITS = false>
+template <int R, bool STRICT, int MODE, uint32_t F>
 __device__ __forceinline__ void aff_block8(AffState<R> &S, const uint2 rw, const uint32_t t0, const uint32_t lane,
                                            const uint32_t n, const uint32_t row0, const uint32_t vrows,
                                            const int o, const int e, const int vmat, const int vmis,
-                                           uint2 *__restrict__ cells, const uint32_t ccap, const AffSeam &Z = AffSeam{},
-                                           const int o2 = 0, const int e2 = 0) {
-    static_assert(!TWO || (AFF_ROW0_GAPS(MODE) && !MATRIX), "two-piece gaps: global and extend runs without a score matrix");
-    static_assert(!SUBOPT || MODE == AFF_LOCAL, "subopt: local runs");
-    static_assert(!ENDB || (MODE == AFF_EXTEND && !TWO && !SUBOPT), "end_bonus: one-piece extend runs");
-    static_assert(!HITS || SUBOPT, "hits: the local sweeps of option subopt");
+                                           uint2 *__restrict__ cells, const uint32_t ccap, const AffSeam &Z, const int o2, const int e2) {
+    AFF_FLAG_NAMES(F)
     const int oe = o + e;
     const int oe2 = o2 + e2;                                     // (TWO)
 #pragma unroll 1
@@ -463,9 +467,10 @@ __device__ __forceinline__ AffCells aff_cell_list(const FillArgs &A, const PairD
 // SUBOPT: the row of column maxima lies behind the field; the lane that owns the read's last row, lact - 1 of swmi_aff_blocks, stores
 // it -- W is sized for that lane to reach column n
 // ENDB: the bonus endb of option "end_bonus"; the lane that owns read row m tracks it, and the choice is made with the PairOut
-template <int R, bool STRICT, bool MATRIX, int MODE, bool TWO = false, bool SUBOPT = false, bool ENDB = false, bool HITS = false>
+template <int R, bool STRICT, int MODE, uint32_t F>
 __device__ __forceinline__ void aff_sweep_pair(const FillArgs &A, const int o, const PairDesc pd, const uint32_t lane, const uint32_t nn,
-                                               const int o2 = 0, const int e2 = 0, const uint32_t endb = 0u) {
+                                               const int o2, const int e2, const uint32_t endb) {
+    AFF_FLAG_NAMES(F)
     const SeqDesc rd = A.refs[pd.ref_id];
     const SeqDesc qd = A.reads[pd.read_id];
     const uint32_t n = rd.len, m = qd.len;
@@ -484,7 +489,7 @@ __device__ __forceinline__ void aff_sweep_pair(const FillArgs &A, const int o, c
     S.rb = 0; S.nh_prev = 0; S.f_last = 0;                       // (nh_prev of lane 0: H(0,0) = 0 in every mode)
     if constexpr (TWO) S.f2_last = 0;
     S.thr = MODE == AFF_LOCAL ? 1 : INT32_MIN; S.cnt = 0;
-    AffSeam Zs{};                                                // (SUBOPT)
+    AffSeam Zs{};                                                // (SUBOPT, ENDB; nothing else reads it in a short sweep)
     if constexpr (SUBOPT) {
         S.cm = 0;
         Zs.cmrow = reinterpret_cast<int *>(dir + (uint64_t)W * R * WAVE);
@@ -504,14 +509,8 @@ __device__ __forceinline__ void aff_sweep_pair(const FillArgs &A, const int o, c
         if constexpr (TWO) {
 #pragma unroll
             for (int k = 0; k < R; ++k) S.acc2[k] = 0u;
-            aff_block8<R, STRICT, MATRIX, MODE, false, false, true>(S, rw, t0, lane, n, row0, vrows, o, A.gap, A.match, A.mismatch, cells, ccap,
-                                                                    AffSeam{}, o2, e2);
-        } else if constexpr (SUBOPT)
-        aff_block8<R, STRICT, MATRIX, MODE, false, false, false, true, false, HITS>(S, rw, t0, lane, n, row0, vrows, o, A.gap, A.match, A.mismatch, cells, ccap, Zs);
-        else if constexpr (ENDB)
-        aff_block8<R, STRICT, MATRIX, MODE, false, false, false, false, true>(S, rw, t0, lane, n, row0, vrows, o, A.gap, A.match, A.mismatch, cells, ccap, Zs);
-        else
-        aff_block8<R, STRICT, MATRIX, MODE>(S, rw, t0, lane, n, row0, vrows, o, A.gap, A.match, A.mismatch, cells, ccap);
+        }
+        aff_block8<R, STRICT, MODE, F>(S, rw, t0, lane, n, row0, vrows, o, A.gap, A.match, A.mismatch, cells, ccap, Zs, o2, e2);
         AFF_STORE_BLOCK
     }
     if constexpr (ENDB) AFF_PAIR_OUT_ENDB(Zs.elane)
@@ -579,16 +578,10 @@ __device__ __forceinline__ void aff_sweep_pair(const FillArgs &A, const int o, c
 //   in place with it -- the same loads by lanes 0..7 at step t0, the same stores by lane 63 at step t, so an entry of either row is read at
 //   least 63 steps before this strip overwrites it.  A strip keeps the row the strips above left unless it holds a strictly greater
 //   value: the smallest row survives the seam.
-template <bool STRICT, bool MATRIX, int MODE, bool BAND, bool XDROP = false, bool ADAPT = false, bool TWO = false, bool SUBOPT = false, bool ENDB = false,
-          bool HITS = false>
+template <bool STRICT, int MODE, uint32_t F>
 __device__ __forceinline__ void aff_sweep_long_pair(const FillArgs &A, const int o, const PairDesc pd, const uint32_t lane, const uint32_t nn,
-                                                    const uint32_t wb, const uint32_t xd = 0u, const int o2 = 0, const int e2 = 0,
-                                                    const uint32_t endb = 0u) {
-    static_assert(!ADAPT || (BAND && MODE == AFF_EXTEND), "band_adapt is an option of the banded strip sweeps of an extend run");
-    static_assert(!TWO || (!XDROP && !ADAPT), "two-piece gaps: not under xdrop or band_adapt");
-    static_assert(!SUBOPT || (MODE == AFF_LOCAL && !XDROP && !ADAPT && !TWO), "subopt: local runs");
-    static_assert(!ENDB || (MODE == AFF_EXTEND && !XDROP && !ADAPT && !TWO && !SUBOPT), "end_bonus: one-piece extend runs without xdrop or band_adapt");
-    static_assert(!HITS || SUBOPT, "hits: the local sweeps of option subopt");
+                                                    const uint32_t wb, const uint32_t xd, const int o2, const int e2, const uint32_t endb) {
+    AFF_FLAG_NAMES(F)
     constexpr int R = SWMI_AFF_RMAX;
     constexpr int OUT = BAND && MODE != AFF_LOCAL ? SWMI_AFF_BAND_NEG : 0;
     const SeqDesc rd = A.refs[pd.ref_id];
@@ -764,7 +757,7 @@ __device__ __forceinline__ void aff_sweep_long_pair(const FillArgs &A, const int
 #pragma unroll
                 for (int k = 0; k < R; ++k) S.acc2[k] = 0u;
             }
-            aff_block8<R, STRICT, MATRIX, MODE, true, BAND, TWO, SUBOPT, ENDB, HITS>(S, rw, t0, lane, nw, row0, vrows, o, A.gap, A.match, A.mismatch, cells, ccap, Z, o2, e2);
+            aff_block8<R, STRICT, MODE, F>(S, rw, t0, lane, nw, row0, vrows, o, A.gap, A.match, A.mismatch, cells, ccap, Z, o2, e2);
             AFF_STORE_BLOCK
         }
         if constexpr (BAND && !ADAPT) dir += (uint64_t)W * (TWO ? 2 : 1) * R * WAVE;
@@ -781,34 +774,24 @@ __device__ __forceinline__ void aff_sweep_long_pair(const FillArgs &A, const int
 #undef AFF_PAIR_OUT_ENDB
 
 // RLO..RHI: the rows per lane this instantiation of the kernel takes (the others' registers would cap its occupancy)
-template <int RLO, int RHI, bool STRICT, bool MATRIX, int MODE, bool TWO = false, bool SUBOPT = false, bool ENDB = false, bool HITS = false>
+template <int RLO, int RHI, bool STRICT, int MODE, uint32_t F>
 __device__ __forceinline__ void aff_sweep_dispatch(const FillArgs &A, const int o, const PairDesc pd, const uint32_t R, const uint32_t lane,
-                                                   const uint32_t nn, const int o2 = 0, const int e2 = 0, const uint32_t endb = 0u) {
+                                                   const uint32_t nn, const int o2, const int e2, const uint32_t endb) {
     if constexpr (RLO <= RHI) {
-        if (R == (uint32_t)RLO) aff_sweep_pair<RLO, STRICT, MATRIX, MODE, TWO, SUBOPT, ENDB, HITS>(A, o, pd, lane, nn, o2, e2, endb);
-        else aff_sweep_dispatch<RLO + 1, RHI, STRICT, MATRIX, MODE, TWO, SUBOPT, ENDB, HITS>(A, o, pd, R, lane, nn, o2, e2, endb);
+        if (R == (uint32_t)RLO) aff_sweep_pair<RLO, STRICT, MODE, F>(A, o, pd, lane, nn, o2, e2, endb);
+        else aff_sweep_dispatch<RLO + 1, RHI, STRICT, MODE, F>(A, o, pd, R, lane, nn, o2, e2, endb);
     }
 }
 
-// mat / nn (MATRIX only): the score matrix image (swmi_aff_mat_words) and its side n + 1
-// LONG: the strip sweep of reads longer than 1024 bases (RLO, RHI unused); BAND (with LONG): inside a band of half-width wb
-// XDROP (with LONG and AFF_EXTEND): the strip sweep under option "xdrop", threshold xd
-// ADAPT (with LONG, BAND and AFF_EXTEND): the banded strip sweep under option "band_adapt"
-// TWO (AFF_GLOBAL and AFF_EXTEND, no MATRIX, XDROP or ADAPT): two-piece gaps, the second piece's open o2 and extension e2
-// SUBOPT (AFF_LOCAL, no XDROP, ADAPT or TWO): the sweep also leaves the pair's row of column maxima (option "subopt")
-// HITS (with SUBOPT): ... and, behind it, the row of the rows that hold them (option "hits")
-// ENDB (AFF_EXTEND, no XDROP, ADAPT, TWO or SUBOPT): the sweep also finds the best score in read row m and chooses (option "end_bonus", bonus endb)
-template <int RLO, int RHI, bool MATRIX, int MODE = AFF_LOCAL, bool LONG = false, bool BAND = false, bool XDROP = false, bool ADAPT = false,
-          bool TWO = false, bool SUBOPT = false, bool ENDB = false, bool HITS = false>
-__device__ __forceinline__ void aff_sweep_entry(const FillArgs &A, const int o, const uint32_t *__restrict__ mat, const uint32_t nn,
-                                                const uint32_t wb = 0u, const uint32_t xd = 0u, const int o2 = 0, const int e2 = 0,
-                                                const uint32_t endb = 0u) {
-    static_assert(!TWO || (AFF_ROW0_GAPS(MODE) && !MATRIX && !XDROP && !ADAPT), "two-piece gaps: plain global and extend runs");
-    static_assert(!XDROP || (LONG && MODE == AFF_EXTEND), "xdrop is an option of the strip sweeps of an extend run");
-    static_assert(!ADAPT || (LONG && BAND && MODE == AFF_EXTEND), "band_adapt is an option of the banded strip sweeps of an extend run");
-    static_assert(!SUBOPT || (MODE == AFF_LOCAL && !XDROP && !ADAPT && !TWO), "subopt is an option of the local sweeps");
-    static_assert(!ENDB || (MODE == AFF_EXTEND && !XDROP && !ADAPT && !TWO && !SUBOPT), "end_bonus is an option of the one-piece extend sweeps without xdrop or band_adapt");
-    static_assert(!HITS || SUBOPT, "hits is an option of the local sweeps of option subopt");
+// The body of every sweep kernel.  Its arguments are the kernels', in their order, a constant where a kernel has none: o2, e2
+// (TWO) the second piece's open and extension; mat, nn (MATRIX) the score matrix image (swmi_aff_mat_words) and its side n + 1;
+// wb (BAND) the half-width; xd (XDROP) the threshold; endb (ENDB) the bonus.  LONG: RLO and RHI are not used.  Which flags may
+// meet is aff_flags_ok (swmi_launch.h)
+template <int RLO, int RHI, int MODE, uint32_t F>
+__device__ __forceinline__ void aff_sweep_entry(const FillArgs &A, const int o, const int o2, const int e2, const uint32_t *__restrict__ mat,
+                                                const uint32_t nn, const uint32_t wb, const uint32_t xd, const uint32_t endb) {
+    static_assert(aff_flags_ok(MODE, F), "no such sweep");
+    AFF_FLAG_NAMES(F)
     if (blockIdx.x == 0 && threadIdx.x == 0) A.hdr->reserved = 0ull;      // the traceback's bump allocator
     if (MATRIX) {                                                          // (before any wavefront leaves)
         for (uint32_t x = threadIdx.x; x < 256u; x += WAVE * AFF_WAVES) aff_mkey[x] = mat[x];
@@ -825,176 +808,114 @@ __device__ __forceinline__ void aff_sweep_entry(const FillArgs &A, const int o, 
     const PairDesc pd = A.pairs[pair];
     if constexpr (LONG) {
         if (uni(A.reads[pd.read_id].len) <= SWMI_AFF_MAX_READ) return;
-        if (A.strict) aff_sweep_long_pair<true, MATRIX, MODE, BAND, XDROP, ADAPT, TWO, SUBOPT, ENDB, HITS>(A, o, pd, lane, nn, wb, xd, o2, e2, endb);
-        else          aff_sweep_long_pair<false, MATRIX, MODE, BAND, XDROP, ADAPT, TWO, SUBOPT, ENDB, HITS>(A, o, pd, lane, nn, wb, xd, o2, e2, endb);
+        if (A.strict) aff_sweep_long_pair<true, MODE, F>(A, o, pd, lane, nn, wb, xd, o2, e2, endb);
+        else          aff_sweep_long_pair<false, MODE, F>(A, o, pd, lane, nn, wb, xd, o2, e2, endb);
         return;
     }
     const uint32_t R = uni(swmi_aff_rows_per_lane(A.reads[pd.read_id].len));
     if (R < (uint32_t)RLO || R > (uint32_t)RHI) return;
-    if (A.strict) aff_sweep_dispatch<RLO, RHI, true, MATRIX, MODE, TWO, SUBOPT, ENDB, HITS>(A, o, pd, R, lane, nn, o2, e2, endb);
-    else          aff_sweep_dispatch<RLO, RHI, false, MATRIX, MODE, TWO, SUBOPT, ENDB, HITS>(A, o, pd, R, lane, nn, o2, e2, endb);
+    if (A.strict) aff_sweep_dispatch<RLO, RHI, true, MODE, F>(A, o, pd, R, lane, nn, o2, e2, endb);
+    else          aff_sweep_dispatch<RLO, RHI, false, MODE, F>(A, o, pd, R, lane, nn, o2, e2, endb);
 }
 
 }  // namespace
 
-// The 40 sweep kernels: local, fit and global (option "align_mode") and extend (option "extend"), each plain and with a score matrix (MATRIX = 0 / 1), each
-// narrow (R = 1..4), wide (R = 5..16), long (option "long_reads": RLO, RHI unused) and banded long (option "band", BAND = 1:
-// the half-width is one more scalar argument).  The long and banded long extend sweeps come once more under option "xdrop" (XDROP = 1:
-// the threshold is one more scalar argument, the last), and the banded ones of those once more under option "band_adapt" (ADAPT = 1: no
-// further argument).  MATRIX, BAND and XDROP make the signatures.
-#define AFF_SWEEP_PARAMS_000 const FillArgs A, const int gap_open
-#define AFF_SWEEP_PARAMS_100 const FillArgs A, const int gap_open, const uint32_t *mat, const uint32_t nn
-#define AFF_SWEEP_PARAMS_010 const FillArgs A, const int gap_open, const uint32_t band
-#define AFF_SWEEP_PARAMS_110 const FillArgs A, const int gap_open, const uint32_t *mat, const uint32_t nn, const uint32_t band
-#define AFF_SWEEP_PARAMS_001 AFF_SWEEP_PARAMS_000, const uint32_t xdrop
-#define AFF_SWEEP_PARAMS_101 AFF_SWEEP_PARAMS_100, const uint32_t xdrop
-#define AFF_SWEEP_PARAMS_011 AFF_SWEEP_PARAMS_010, const uint32_t xdrop
-#define AFF_SWEEP_PARAMS_111 AFF_SWEEP_PARAMS_110, const uint32_t xdrop
-#define AFF_SWEEP_ARGS_000 A, gap_open, nullptr, 0u
-#define AFF_SWEEP_ARGS_100 A, gap_open, mat, nn
-#define AFF_SWEEP_ARGS_010 A, gap_open, nullptr, 0u, band
-#define AFF_SWEEP_ARGS_110 A, gap_open, mat, nn, band
-#define AFF_SWEEP_ARGS_001 A, gap_open, nullptr, 0u, 0u, xdrop
-#define AFF_SWEEP_ARGS_101 A, gap_open, mat, nn, 0u, xdrop
-#define AFF_SWEEP_ARGS_011 A, gap_open, nullptr, 0u, band, xdrop
-#define AFF_SWEEP_ARGS_111 A, gap_open, mat, nn, band, xdrop
-#define AFF_SWEEP_KERNEL(name, RLO, RHI, MATRIX, MODE, LONG, BAND, XDROP, ADAPT)                                          \
-    extern "C" __global__ void __launch_bounds__(WAVE * AFF_WAVES) name(AFF_SWEEP_PARAMS_##MATRIX##BAND##XDROP) {        \
-        aff_sweep_entry<RLO, RHI, MATRIX != 0, MODE, LONG, BAND != 0, XDROP != 0, ADAPT != 0>(AFF_SWEEP_ARGS_##MATRIX##BAND##XDROP); \
+// THE LIST OF SWEEPS.  One row per kernel: its name, the rows per lane it takes (RLO .. RHI: 1 .. 4 narrow, 5 .. 16 wide; the strip
+// sweeps of option "long_reads" have 16 and do not use them), its MODE, and the flags of swmi_launch.h as 0 / 1.  The definitions
+// just below and the launcher's table at the end of the file are this list under two macros; DESIGN.md 8q says how to add an option.
+//                                                     RLO RHI  MODE     MATRIX LONG BAND XDROP ADAPT TWO SUBOPT ENDB HITS
+#define AFF_SWEEPS(X)                                                                                     \
+    X(sw_affine_sweep_kernel,                          1,  4, AFF_LOCAL,  0, 0, 0, 0, 0, 0, 0, 0, 0) \
+    X(sw_affine_sweep_wide_kernel,                     5, 16, AFF_LOCAL,  0, 0, 0, 0, 0, 0, 0, 0, 0) \
+    X(sw_affine_sweep_long_kernel,                    16, 16, AFF_LOCAL,  0, 1, 0, 0, 0, 0, 0, 0, 0) \
+    X(sw_affine_sweep_matrix_kernel,                   1,  4, AFF_LOCAL,  1, 0, 0, 0, 0, 0, 0, 0, 0) \
+    X(sw_affine_sweep_matrix_wide_kernel,              5, 16, AFF_LOCAL,  1, 0, 0, 0, 0, 0, 0, 0, 0) \
+    X(sw_affine_sweep_long_matrix_kernel,             16, 16, AFF_LOCAL,  1, 1, 0, 0, 0, 0, 0, 0, 0) \
+    X(sw_affine_sweep_fit_kernel,                      1,  4, AFF_FIT,    0, 0, 0, 0, 0, 0, 0, 0, 0) \
+    X(sw_affine_sweep_fit_wide_kernel,                 5, 16, AFF_FIT,    0, 0, 0, 0, 0, 0, 0, 0, 0) \
+    X(sw_affine_sweep_long_fit_kernel,                16, 16, AFF_FIT,    0, 1, 0, 0, 0, 0, 0, 0, 0) \
+    X(sw_affine_sweep_fit_matrix_kernel,               1,  4, AFF_FIT,    1, 0, 0, 0, 0, 0, 0, 0, 0) \
+    X(sw_affine_sweep_fit_matrix_wide_kernel,          5, 16, AFF_FIT,    1, 0, 0, 0, 0, 0, 0, 0, 0) \
+    X(sw_affine_sweep_long_fit_matrix_kernel,         16, 16, AFF_FIT,    1, 1, 0, 0, 0, 0, 0, 0, 0) \
+    X(sw_affine_sweep_global_kernel,                   1,  4, AFF_GLOBAL, 0, 0, 0, 0, 0, 0, 0, 0, 0) \
+    X(sw_affine_sweep_global_wide_kernel,              5, 16, AFF_GLOBAL, 0, 0, 0, 0, 0, 0, 0, 0, 0) \
+    X(sw_affine_sweep_long_global_kernel,             16, 16, AFF_GLOBAL, 0, 1, 0, 0, 0, 0, 0, 0, 0) \
+    X(sw_affine_sweep_global_matrix_kernel,            1,  4, AFF_GLOBAL, 1, 0, 0, 0, 0, 0, 0, 0, 0) \
+    X(sw_affine_sweep_global_matrix_wide_kernel,       5, 16, AFF_GLOBAL, 1, 0, 0, 0, 0, 0, 0, 0, 0) \
+    X(sw_affine_sweep_long_global_matrix_kernel,      16, 16, AFF_GLOBAL, 1, 1, 0, 0, 0, 0, 0, 0, 0) \
+    X(sw_affine_sweep_band_kernel,                    16, 16, AFF_LOCAL,  0, 1, 1, 0, 0, 0, 0, 0, 0) \
+    X(sw_affine_sweep_band_matrix_kernel,             16, 16, AFF_LOCAL,  1, 1, 1, 0, 0, 0, 0, 0, 0) \
+    X(sw_affine_sweep_band_fit_kernel,                16, 16, AFF_FIT,    0, 1, 1, 0, 0, 0, 0, 0, 0) \
+    X(sw_affine_sweep_band_fit_matrix_kernel,         16, 16, AFF_FIT,    1, 1, 1, 0, 0, 0, 0, 0, 0) \
+    X(sw_affine_sweep_band_global_kernel,             16, 16, AFF_GLOBAL, 0, 1, 1, 0, 0, 0, 0, 0, 0) \
+    X(sw_affine_sweep_band_global_matrix_kernel,      16, 16, AFF_GLOBAL, 1, 1, 1, 0, 0, 0, 0, 0, 0) \
+    X(sw_affine_sweep_extend_kernel,                   1,  4, AFF_EXTEND, 0, 0, 0, 0, 0, 0, 0, 0, 0) \
+    X(sw_affine_sweep_extend_wide_kernel,              5, 16, AFF_EXTEND, 0, 0, 0, 0, 0, 0, 0, 0, 0) \
+    X(sw_affine_sweep_long_extend_kernel,             16, 16, AFF_EXTEND, 0, 1, 0, 0, 0, 0, 0, 0, 0) \
+    X(sw_affine_sweep_extend_matrix_kernel,            1,  4, AFF_EXTEND, 1, 0, 0, 0, 0, 0, 0, 0, 0) \
+    X(sw_affine_sweep_extend_matrix_wide_kernel,       5, 16, AFF_EXTEND, 1, 0, 0, 0, 0, 0, 0, 0, 0) \
+    X(sw_affine_sweep_long_extend_matrix_kernel,      16, 16, AFF_EXTEND, 1, 1, 0, 0, 0, 0, 0, 0, 0) \
+    X(sw_affine_sweep_band_extend_kernel,             16, 16, AFF_EXTEND, 0, 1, 1, 0, 0, 0, 0, 0, 0) \
+    X(sw_affine_sweep_band_extend_matrix_kernel,      16, 16, AFF_EXTEND, 1, 1, 1, 0, 0, 0, 0, 0, 0) \
+    X(sw_affine_sweep_long_xdrop_kernel,              16, 16, AFF_EXTEND, 0, 1, 0, 1, 0, 0, 0, 0, 0) \
+    X(sw_affine_sweep_long_xdrop_matrix_kernel,       16, 16, AFF_EXTEND, 1, 1, 0, 1, 0, 0, 0, 0, 0) \
+    X(sw_affine_sweep_band_xdrop_kernel,              16, 16, AFF_EXTEND, 0, 1, 1, 1, 0, 0, 0, 0, 0) \
+    X(sw_affine_sweep_band_xdrop_matrix_kernel,       16, 16, AFF_EXTEND, 1, 1, 1, 1, 0, 0, 0, 0, 0) \
+    X(sw_affine_sweep_band_adapt_kernel,              16, 16, AFF_EXTEND, 0, 1, 1, 0, 1, 0, 0, 0, 0) \
+    X(sw_affine_sweep_band_adapt_matrix_kernel,       16, 16, AFF_EXTEND, 1, 1, 1, 0, 1, 0, 0, 0, 0) \
+    X(sw_affine_sweep_band_adapt_xdrop_kernel,        16, 16, AFF_EXTEND, 0, 1, 1, 1, 1, 0, 0, 0, 0) \
+    X(sw_affine_sweep_band_adapt_xdrop_matrix_kernel, 16, 16, AFF_EXTEND, 1, 1, 1, 1, 1, 0, 0, 0, 0) \
+    X(sw_affine_sweep_subopt_kernel,                   1,  4, AFF_LOCAL,  0, 0, 0, 0, 0, 0, 1, 0, 0) \
+    X(sw_affine_sweep_subopt_wide_kernel,              5, 16, AFF_LOCAL,  0, 0, 0, 0, 0, 0, 1, 0, 0) \
+    X(sw_affine_sweep_long_subopt_kernel,             16, 16, AFF_LOCAL,  0, 1, 0, 0, 0, 0, 1, 0, 0) \
+    X(sw_affine_sweep_subopt_matrix_kernel,            1,  4, AFF_LOCAL,  1, 0, 0, 0, 0, 0, 1, 0, 0) \
+    X(sw_affine_sweep_subopt_matrix_wide_kernel,       5, 16, AFF_LOCAL,  1, 0, 0, 0, 0, 0, 1, 0, 0) \
+    X(sw_affine_sweep_long_subopt_matrix_kernel,      16, 16, AFF_LOCAL,  1, 1, 0, 0, 0, 0, 1, 0, 0) \
+    X(sw_affine_sweep_band_subopt_kernel,             16, 16, AFF_LOCAL,  0, 1, 1, 0, 0, 0, 1, 0, 0) \
+    X(sw_affine_sweep_band_subopt_matrix_kernel,      16, 16, AFF_LOCAL,  1, 1, 1, 0, 0, 0, 1, 0, 0) \
+    X(sw_affine_sweep_hits_kernel,                     1,  4, AFF_LOCAL,  0, 0, 0, 0, 0, 0, 1, 0, 1) \
+    X(sw_affine_sweep_hits_wide_kernel,                5, 16, AFF_LOCAL,  0, 0, 0, 0, 0, 0, 1, 0, 1) \
+    X(sw_affine_sweep_long_hits_kernel,               16, 16, AFF_LOCAL,  0, 1, 0, 0, 0, 0, 1, 0, 1) \
+    X(sw_affine_sweep_hits_matrix_kernel,              1,  4, AFF_LOCAL,  1, 0, 0, 0, 0, 0, 1, 0, 1) \
+    X(sw_affine_sweep_hits_matrix_wide_kernel,         5, 16, AFF_LOCAL,  1, 0, 0, 0, 0, 0, 1, 0, 1) \
+    X(sw_affine_sweep_long_hits_matrix_kernel,        16, 16, AFF_LOCAL,  1, 1, 0, 0, 0, 0, 1, 0, 1) \
+    X(sw_affine_sweep_band_hits_kernel,               16, 16, AFF_LOCAL,  0, 1, 1, 0, 0, 0, 1, 0, 1) \
+    X(sw_affine_sweep_band_hits_matrix_kernel,        16, 16, AFF_LOCAL,  1, 1, 1, 0, 0, 0, 1, 0, 1) \
+    X(sw_affine_sweep_endb_kernel,                     1,  4, AFF_EXTEND, 0, 0, 0, 0, 0, 0, 0, 1, 0) \
+    X(sw_affine_sweep_endb_wide_kernel,                5, 16, AFF_EXTEND, 0, 0, 0, 0, 0, 0, 0, 1, 0) \
+    X(sw_affine_sweep_long_endb_kernel,               16, 16, AFF_EXTEND, 0, 1, 0, 0, 0, 0, 0, 1, 0) \
+    X(sw_affine_sweep_endb_matrix_kernel,              1,  4, AFF_EXTEND, 1, 0, 0, 0, 0, 0, 0, 1, 0) \
+    X(sw_affine_sweep_endb_matrix_wide_kernel,         5, 16, AFF_EXTEND, 1, 0, 0, 0, 0, 0, 0, 1, 0) \
+    X(sw_affine_sweep_long_endb_matrix_kernel,        16, 16, AFF_EXTEND, 1, 1, 0, 0, 0, 0, 0, 1, 0) \
+    X(sw_affine_sweep_band_endb_kernel,               16, 16, AFF_EXTEND, 0, 1, 1, 0, 0, 0, 0, 1, 0) \
+    X(sw_affine_sweep_band_endb_matrix_kernel,        16, 16, AFF_EXTEND, 1, 1, 1, 0, 0, 0, 0, 1, 0) \
+    X(sw_affine_sweep2_global_kernel,                  1,  4, AFF_GLOBAL, 0, 0, 0, 0, 0, 1, 0, 0, 0) \
+    X(sw_affine_sweep2_global_wide_kernel,             5, 16, AFF_GLOBAL, 0, 0, 0, 0, 0, 1, 0, 0, 0) \
+    X(sw_affine_sweep2_long_global_kernel,            16, 16, AFF_GLOBAL, 0, 1, 0, 0, 0, 1, 0, 0, 0) \
+    X(sw_affine_sweep2_band_global_kernel,            16, 16, AFF_GLOBAL, 0, 1, 1, 0, 0, 1, 0, 0, 0) \
+    X(sw_affine_sweep2_extend_kernel,                  1,  4, AFF_EXTEND, 0, 0, 0, 0, 0, 1, 0, 0, 0) \
+    X(sw_affine_sweep2_extend_wide_kernel,             5, 16, AFF_EXTEND, 0, 0, 0, 0, 0, 1, 0, 0, 0) \
+    X(sw_affine_sweep2_long_extend_kernel,            16, 16, AFF_EXTEND, 0, 1, 0, 0, 0, 1, 0, 0, 0) \
+    X(sw_affine_sweep2_band_extend_kernel,            16, 16, AFF_EXTEND, 0, 1, 1, 0, 0, 1, 0, 0, 0)
+static_assert(SWMI_AFF_RMAX == 16, "the RHI column of the list");
+// A kernel's parameters are pieces, one per flag that has any, in this order (TWO and MATRIX never meet): AFF_IF_<flag>(text) is
+// the text under a set flag, AFF_SEL_<flag>(a, b) is a under a set flag and b otherwise.
+//   const FillArgs A, const int gap_open [, gap_open2, gap2: TWO] [, mat, nn: MATRIX] [, band: BAND] [, xdrop: XDROP] [, end_bonus: ENDB]
+#define AFF_IF_0(...)
+#define AFF_IF_1(...) __VA_ARGS__
+#define AFF_SEL_0(a, b) b
+#define AFF_SEL_1(a, b) a
+#define AFF_SWEEP_KERNEL(name, RLO, RHI, MODE, MATRIX, LONG, BAND, XDROP, ADAPT, TWO, SUBOPT, ENDB, HITS)                                    \
+    static_assert(aff_flags_ok(MODE, aff_flags(MATRIX, LONG, BAND, XDROP, ADAPT, TWO, SUBOPT, ENDB, HITS)), #name);                          \
+    extern "C" __global__ void __launch_bounds__(WAVE * AFF_WAVES) name(const FillArgs A, const int gap_open                                  \
+            AFF_IF_##TWO(, const int gap_open2, const int gap2) AFF_IF_##MATRIX(, const uint32_t *mat, const uint32_t nn)                    \
+            AFF_IF_##BAND(, const uint32_t band) AFF_IF_##XDROP(, const uint32_t xdrop) AFF_IF_##ENDB(, const uint32_t end_bonus)) {         \
+        aff_sweep_entry<RLO, RHI, MODE, aff_flags(MATRIX, LONG, BAND, XDROP, ADAPT, TWO, SUBOPT, ENDB, HITS)>(                              \
+            A, gap_open, AFF_SEL_##TWO(gap_open2, 0), AFF_SEL_##TWO(gap2, 0), AFF_SEL_##MATRIX(mat, nullptr), AFF_SEL_##MATRIX(nn, 0u),      \
+            AFF_SEL_##BAND(band, 0u), AFF_SEL_##XDROP(xdrop, 0u), AFF_SEL_##ENDB(end_bonus, 0u));                                            \
     }
-AFF_SWEEP_KERNEL(sw_affine_sweep_kernel, 1, 4, 0, AFF_LOCAL, false, 0, 0, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_wide_kernel, 5, SWMI_AFF_RMAX, 0, AFF_LOCAL, false, 0, 0, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_long_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, AFF_LOCAL, true, 0, 0, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_matrix_kernel, 1, 4, 1, AFF_LOCAL, false, 0, 0, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_matrix_wide_kernel, 5, SWMI_AFF_RMAX, 1, AFF_LOCAL, false, 0, 0, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_long_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, AFF_LOCAL, true, 0, 0, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_fit_kernel, 1, 4, 0, AFF_FIT, false, 0, 0, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_fit_wide_kernel, 5, SWMI_AFF_RMAX, 0, AFF_FIT, false, 0, 0, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_long_fit_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, AFF_FIT, true, 0, 0, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_fit_matrix_kernel, 1, 4, 1, AFF_FIT, false, 0, 0, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_fit_matrix_wide_kernel, 5, SWMI_AFF_RMAX, 1, AFF_FIT, false, 0, 0, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_long_fit_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, AFF_FIT, true, 0, 0, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_global_kernel, 1, 4, 0, AFF_GLOBAL, false, 0, 0, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_global_wide_kernel, 5, SWMI_AFF_RMAX, 0, AFF_GLOBAL, false, 0, 0, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_long_global_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, AFF_GLOBAL, true, 0, 0, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_global_matrix_kernel, 1, 4, 1, AFF_GLOBAL, false, 0, 0, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_global_matrix_wide_kernel, 5, SWMI_AFF_RMAX, 1, AFF_GLOBAL, false, 0, 0, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_long_global_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, AFF_GLOBAL, true, 0, 0, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_band_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, AFF_LOCAL, true, 1, 0, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_band_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, AFF_LOCAL, true, 1, 0, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_band_fit_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, AFF_FIT, true, 1, 0, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_band_fit_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, AFF_FIT, true, 1, 0, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_band_global_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, AFF_GLOBAL, true, 1, 0, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_band_global_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, AFF_GLOBAL, true, 1, 0, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_extend_kernel, 1, 4, 0, AFF_EXTEND, false, 0, 0, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_extend_wide_kernel, 5, SWMI_AFF_RMAX, 0, AFF_EXTEND, false, 0, 0, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_long_extend_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, AFF_EXTEND, true, 0, 0, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_extend_matrix_kernel, 1, 4, 1, AFF_EXTEND, false, 0, 0, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_extend_matrix_wide_kernel, 5, SWMI_AFF_RMAX, 1, AFF_EXTEND, false, 0, 0, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_long_extend_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, AFF_EXTEND, true, 0, 0, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_band_extend_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, AFF_EXTEND, true, 1, 0, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_band_extend_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, AFF_EXTEND, true, 1, 0, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_long_xdrop_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, AFF_EXTEND, true, 0, 1, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_long_xdrop_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, AFF_EXTEND, true, 0, 1, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_band_xdrop_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, AFF_EXTEND, true, 1, 1, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_band_xdrop_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, AFF_EXTEND, true, 1, 1, 0)
-AFF_SWEEP_KERNEL(sw_affine_sweep_band_adapt_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, AFF_EXTEND, true, 1, 0, 1)
-AFF_SWEEP_KERNEL(sw_affine_sweep_band_adapt_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, AFF_EXTEND, true, 1, 0, 1)
-AFF_SWEEP_KERNEL(sw_affine_sweep_band_adapt_xdrop_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, AFF_EXTEND, true, 1, 1, 1)
-AFF_SWEEP_KERNEL(sw_affine_sweep_band_adapt_xdrop_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, AFF_EXTEND, true, 1, 1, 1)
+AFF_SWEEPS(AFF_SWEEP_KERNEL)
 #undef AFF_SWEEP_KERNEL
-// The 8 local sweeps under option "subopt" (DESIGN.md 8n), SUBOPT = 1: narrow, wide, long and banded long, each plain and with a score
-// matrix, with the signatures of their SUBOPT = 0 twins -- the row of column maxima lies behind the pair's fields, which the sweep finds.
-#define AFF_SWEEPS_KERNEL(name, RLO, RHI, MATRIX, LONG, BAND)                                                             \
-    extern "C" __global__ void __launch_bounds__(WAVE * AFF_WAVES) name(AFF_SWEEP_PARAMS_##MATRIX##BAND##0) {            \
-        aff_sweep_entry<RLO, RHI, MATRIX != 0, AFF_LOCAL, LONG, BAND != 0, false, false, false, true>(AFF_SWEEP_ARGS_##MATRIX##BAND##0); \
-    }
-AFF_SWEEPS_KERNEL(sw_affine_sweep_subopt_kernel, 1, 4, 0, false, 0)
-AFF_SWEEPS_KERNEL(sw_affine_sweep_subopt_wide_kernel, 5, SWMI_AFF_RMAX, 0, false, 0)
-AFF_SWEEPS_KERNEL(sw_affine_sweep_long_subopt_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, true, 0)
-AFF_SWEEPS_KERNEL(sw_affine_sweep_subopt_matrix_kernel, 1, 4, 1, false, 0)
-AFF_SWEEPS_KERNEL(sw_affine_sweep_subopt_matrix_wide_kernel, 5, SWMI_AFF_RMAX, 1, false, 0)
-AFF_SWEEPS_KERNEL(sw_affine_sweep_long_subopt_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, true, 0)
-AFF_SWEEPS_KERNEL(sw_affine_sweep_band_subopt_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, true, 1)
-AFF_SWEEPS_KERNEL(sw_affine_sweep_band_subopt_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, true, 1)
-#undef AFF_SWEEPS_KERNEL
-// The 8 local sweeps under option "hits" (DESIGN.md 8p), SUBOPT = 1 and HITS = 1: the subopt sweeps' shapes and signatures -- the row of
-// rows lies behind the row of column maxima, which the sweep finds.
-#define AFF_SWEEPH_KERNEL(name, RLO, RHI, MATRIX, LONG, BAND)                                                             \
-    extern "C" __global__ void __launch_bounds__(WAVE * AFF_WAVES) name(AFF_SWEEP_PARAMS_##MATRIX##BAND##0) {            \
-        aff_sweep_entry<RLO, RHI, MATRIX != 0, AFF_LOCAL, LONG, BAND != 0, false, false, false, true, false, true>(AFF_SWEEP_ARGS_##MATRIX##BAND##0); \
-    }
-AFF_SWEEPH_KERNEL(sw_affine_sweep_hits_kernel, 1, 4, 0, false, 0)
-AFF_SWEEPH_KERNEL(sw_affine_sweep_hits_wide_kernel, 5, SWMI_AFF_RMAX, 0, false, 0)
-AFF_SWEEPH_KERNEL(sw_affine_sweep_long_hits_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, true, 0)
-AFF_SWEEPH_KERNEL(sw_affine_sweep_hits_matrix_kernel, 1, 4, 1, false, 0)
-AFF_SWEEPH_KERNEL(sw_affine_sweep_hits_matrix_wide_kernel, 5, SWMI_AFF_RMAX, 1, false, 0)
-AFF_SWEEPH_KERNEL(sw_affine_sweep_long_hits_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, true, 0)
-AFF_SWEEPH_KERNEL(sw_affine_sweep_band_hits_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, true, 1)
-AFF_SWEEPH_KERNEL(sw_affine_sweep_band_hits_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, true, 1)
-#undef AFF_SWEEPH_KERNEL
-// The 8 extend sweeps under option "end_bonus" (DESIGN.md 8o), ENDB = 1: narrow, wide, long and banded long, each plain and with a score
-// matrix, with the signatures of their ENDB = 0 twins and the bonus as one more scalar, the last.
-#define AFF_SWEEPE_KERNEL(name, RLO, RHI, MATRIX, LONG, BAND)                                                             \
-    extern "C" __global__ void __launch_bounds__(WAVE * AFF_WAVES) name(AFF_SWEEP_PARAMS_##MATRIX##BAND##0, const uint32_t end_bonus) { \
-        aff_sweep_entry<RLO, RHI, MATRIX != 0, AFF_EXTEND, LONG, BAND != 0, false, false, false, false, true>(AFF_SWEEPE_ARGS_##MATRIX##BAND, end_bonus); \
-    }
-#define AFF_SWEEPE_ARGS_00 A, gap_open, nullptr, 0u, 0u, 0u, 0, 0
-#define AFF_SWEEPE_ARGS_10 A, gap_open, mat, nn, 0u, 0u, 0, 0
-#define AFF_SWEEPE_ARGS_01 A, gap_open, nullptr, 0u, band, 0u, 0, 0
-#define AFF_SWEEPE_ARGS_11 A, gap_open, mat, nn, band, 0u, 0, 0
-AFF_SWEEPE_KERNEL(sw_affine_sweep_endb_kernel, 1, 4, 0, false, 0)
-AFF_SWEEPE_KERNEL(sw_affine_sweep_endb_wide_kernel, 5, SWMI_AFF_RMAX, 0, false, 0)
-AFF_SWEEPE_KERNEL(sw_affine_sweep_long_endb_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, true, 0)
-AFF_SWEEPE_KERNEL(sw_affine_sweep_endb_matrix_kernel, 1, 4, 1, false, 0)
-AFF_SWEEPE_KERNEL(sw_affine_sweep_endb_matrix_wide_kernel, 5, SWMI_AFF_RMAX, 1, false, 0)
-AFF_SWEEPE_KERNEL(sw_affine_sweep_long_endb_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, true, 0)
-AFF_SWEEPE_KERNEL(sw_affine_sweep_band_endb_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 0, true, 1)
-AFF_SWEEPE_KERNEL(sw_affine_sweep_band_endb_matrix_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, 1, true, 1)
-#undef AFF_SWEEPE_KERNEL
-#undef AFF_SWEEPE_ARGS_00
-#undef AFF_SWEEPE_ARGS_10
-#undef AFF_SWEEPE_ARGS_01
-#undef AFF_SWEEPE_ARGS_11
-// The 8 two-piece sweeps (option "gap_open2"): global and extend, each narrow, wide, long and banded long, TWO = 1.
-// The second piece's open and extension follow gap_open; the banded ones take the half-width last.
-#define AFF_SWEEP2_PARAMS_0 const FillArgs A, const int gap_open, const int gap_open2, const int gap2
-#define AFF_SWEEP2_PARAMS_1 AFF_SWEEP2_PARAMS_0, const uint32_t band
-#define AFF_SWEEP2_ARGS_0 A, gap_open, nullptr, 0u, 0u, 0u, gap_open2, gap2
-#define AFF_SWEEP2_ARGS_1 A, gap_open, nullptr, 0u, band, 0u, gap_open2, gap2
-#define AFF_SWEEP2_KERNEL(name, RLO, RHI, MODE, LONG, BAND)                                                               \
-    extern "C" __global__ void __launch_bounds__(WAVE * AFF_WAVES) name(AFF_SWEEP2_PARAMS_##BAND) {                      \
-        aff_sweep_entry<RLO, RHI, false, MODE, LONG, BAND != 0, false, false, true>(AFF_SWEEP2_ARGS_##BAND);             \
-    }
-AFF_SWEEP2_KERNEL(sw_affine_sweep2_global_kernel, 1, 4, AFF_GLOBAL, false, 0)
-AFF_SWEEP2_KERNEL(sw_affine_sweep2_global_wide_kernel, 5, SWMI_AFF_RMAX, AFF_GLOBAL, false, 0)
-AFF_SWEEP2_KERNEL(sw_affine_sweep2_long_global_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, AFF_GLOBAL, true, 0)
-AFF_SWEEP2_KERNEL(sw_affine_sweep2_band_global_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, AFF_GLOBAL, true, 1)
-AFF_SWEEP2_KERNEL(sw_affine_sweep2_extend_kernel, 1, 4, AFF_EXTEND, false, 0)
-AFF_SWEEP2_KERNEL(sw_affine_sweep2_extend_wide_kernel, 5, SWMI_AFF_RMAX, AFF_EXTEND, false, 0)
-AFF_SWEEP2_KERNEL(sw_affine_sweep2_long_extend_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, AFF_EXTEND, true, 0)
-AFF_SWEEP2_KERNEL(sw_affine_sweep2_band_extend_kernel, SWMI_AFF_RMAX, SWMI_AFF_RMAX, AFF_EXTEND, true, 1)
-#undef AFF_SWEEP2_KERNEL
-#undef AFF_SWEEP2_PARAMS_0
-#undef AFF_SWEEP2_PARAMS_1
-#undef AFF_SWEEP2_ARGS_0
-#undef AFF_SWEEP2_ARGS_1
-#undef AFF_SWEEP_PARAMS_000
-#undef AFF_SWEEP_PARAMS_001
-#undef AFF_SWEEP_PARAMS_100
-#undef AFF_SWEEP_PARAMS_101
-#undef AFF_SWEEP_PARAMS_010
-#undef AFF_SWEEP_PARAMS_011
-#undef AFF_SWEEP_PARAMS_110
-#undef AFF_SWEEP_PARAMS_111
-#undef AFF_SWEEP_ARGS_000
-#undef AFF_SWEEP_ARGS_001
-#undef AFF_SWEEP_ARGS_100
-#undef AFF_SWEEP_ARGS_101
-#undef AFF_SWEEP_ARGS_010
-#undef AFF_SWEEP_ARGS_011
-#undef AFF_SWEEP_ARGS_110
-#undef AFF_SWEEP_ARGS_111
 
 // ------------------------------------------------------------------------------------------------
 // traceback
@@ -1023,11 +944,17 @@ AFF_SWEEP2_KERNEL(sw_affine_sweep2_band_extend_kernel, SWMI_AFF_RMAX, SWMI_AFF_R
 #define AFF_INS2 4u
 #define AFF_DEL2 5u
 namespace {
-template <int MODE, bool LONG, bool BAND = false, bool ADAPT = false, bool TWO = false>
+// The walks that may exist: modes 0 .. 2 (an extend run is walked by global mode's kernels, so the walk of option "band_adapt" is
+// held against the extend sweeps' rule) and the four flags that shape a field
+constexpr bool aff_traceback_ok(uint32_t mode, uint32_t f) {
+    return mode <= AFF_GLOBAL && !(f & ~(AFF_F_LONG | AFF_F_BAND | AFF_F_ADAPT | AFF_F_TWO)) &&
+           aff_flags_ok((f & AFF_F_ADAPT) && mode == AFF_GLOBAL ? AFF_EXTEND : mode, f);
+}
+template <int MODE, uint32_t F>
 __device__ __forceinline__ void aff_traceback(const TraceArgs A, const uint32_t tile_words, const uint32_t ops_words, const uint32_t cigar,
-                                              const uint32_t wb = 0u) {
-    static_assert(!ADAPT || (LONG && BAND && MODE == AFF_GLOBAL), "band_adapt: the banded walk of an extend run (global mode's)");
-    static_assert(!TWO || (MODE == AFF_GLOBAL && !ADAPT), "two-piece gaps: the global walk");
+                                              const uint32_t wb) {
+    static_assert(aff_traceback_ok(MODE, F), "no such walk");
+    AFF_FLAG_NAMES(F)
     constexpr uint32_t PL = TWO ? 2u : 1u;                        // planes of the field
     extern __shared__ uint32_t lds[];
     const uint32_t lane = threadIdx.x;
@@ -1203,164 +1130,128 @@ __device__ __forceinline__ void aff_traceback(const TraceArgs A, const uint32_t 
 #undef AFF_INS2
 #undef AFF_DEL2
 
-// cigar: the payload kind (0: strings or packed ops, as TraceArgs.raw says; 1, 2: option "cigar") -- a runtime value, one kernel for all
-#define AFF_TB_PARAMS_0 const TraceArgs A, const uint32_t tile_words, const uint32_t ops_words, const uint32_t cigar
-#define AFF_TB_PARAMS_1 AFF_TB_PARAMS_0, const uint32_t band
-#define AFF_TB_ARGS_0 A, tile_words, ops_words, cigar
-#define AFF_TB_ARGS_1 A, tile_words, ops_words, cigar, band
-#define AFF_TRACEBACK_KERNEL(name, MODE, LONG, BAND, ADAPT, TWO)                                            \
-    extern "C" __global__ void __launch_bounds__(WAVE) name(AFF_TB_PARAMS_##BAND) {                        \
-        aff_traceback<MODE, LONG, BAND != 0, ADAPT != 0, TWO != 0>(AFF_TB_ARGS_##BAND);                    \
+// THE LIST OF TRACEBACKS.  One row per kernel: its name, its MODE and the four flags a walk has.  The banded walks take the
+// half-width as one more argument, the last.  cigar: the payload kind (0: strings or packed ops, as TraceArgs.raw says; 1, 2: option
+// "cigar") -- a runtime value, one kernel for all
+//                                                   MODE      LONG BAND ADAPT TWO
+#define AFF_TRACEBACKS(X)                                                     \
+    X(sw_affine_traceback_kernel,                   AFF_LOCAL,  0, 0, 0, 0) \
+    X(sw_affine_traceback_fit_kernel,               AFF_FIT,    0, 0, 0, 0) \
+    X(sw_affine_traceback_global_kernel,            AFF_GLOBAL, 0, 0, 0, 0) \
+    X(sw_affine_traceback_long_kernel,              AFF_LOCAL,  1, 0, 0, 0) \
+    X(sw_affine_traceback_long_fit_kernel,          AFF_FIT,    1, 0, 0, 0) \
+    X(sw_affine_traceback_long_global_kernel,       AFF_GLOBAL, 1, 0, 0, 0) \
+    X(sw_affine_traceback_band_kernel,              AFF_LOCAL,  1, 1, 0, 0) \
+    X(sw_affine_traceback_band_fit_kernel,          AFF_FIT,    1, 1, 0, 0) \
+    X(sw_affine_traceback_band_global_kernel,       AFF_GLOBAL, 1, 1, 0, 0) \
+    X(sw_affine_traceback_band_adapt_global_kernel, AFF_GLOBAL, 1, 1, 1, 0) \
+    X(sw_affine_traceback2_global_kernel,           AFF_GLOBAL, 0, 0, 0, 1) \
+    X(sw_affine_traceback2_long_global_kernel,      AFF_GLOBAL, 1, 0, 0, 1) \
+    X(sw_affine_traceback2_band_global_kernel,      AFF_GLOBAL, 1, 1, 0, 1)
+#define AFF_TB_FLAGS(LONG, BAND, ADAPT, TWO) aff_flags(0, LONG, BAND, 0, ADAPT, TWO, 0, 0, 0)
+#define AFF_TRACEBACK_KERNEL(name, MODE, LONG, BAND, ADAPT, TWO)                                                                     \
+    static_assert(aff_traceback_ok(MODE, AFF_TB_FLAGS(LONG, BAND, ADAPT, TWO)), #name);                                             \
+    extern "C" __global__ void __launch_bounds__(WAVE) name(const TraceArgs A, const uint32_t tile_words, const uint32_t ops_words, \
+                                                            const uint32_t cigar AFF_IF_##BAND(, const uint32_t band)) {            \
+        aff_traceback<MODE, AFF_TB_FLAGS(LONG, BAND, ADAPT, TWO)>(A, tile_words, ops_words, cigar, AFF_SEL_##BAND(band, 0u));       \
     }
-AFF_TRACEBACK_KERNEL(sw_affine_traceback_kernel, AFF_LOCAL, false, 0, 0, 0)
-AFF_TRACEBACK_KERNEL(sw_affine_traceback_fit_kernel, AFF_FIT, false, 0, 0, 0)
-AFF_TRACEBACK_KERNEL(sw_affine_traceback_global_kernel, AFF_GLOBAL, false, 0, 0, 0)
-AFF_TRACEBACK_KERNEL(sw_affine_traceback_long_kernel, AFF_LOCAL, true, 0, 0, 0)
-AFF_TRACEBACK_KERNEL(sw_affine_traceback_long_fit_kernel, AFF_FIT, true, 0, 0, 0)
-AFF_TRACEBACK_KERNEL(sw_affine_traceback_long_global_kernel, AFF_GLOBAL, true, 0, 0, 0)
-AFF_TRACEBACK_KERNEL(sw_affine_traceback_band_kernel, AFF_LOCAL, true, 1, 0, 0)
-AFF_TRACEBACK_KERNEL(sw_affine_traceback_band_fit_kernel, AFF_FIT, true, 1, 0, 0)
-AFF_TRACEBACK_KERNEL(sw_affine_traceback_band_global_kernel, AFF_GLOBAL, true, 1, 0, 0)
-AFF_TRACEBACK_KERNEL(sw_affine_traceback_band_adapt_global_kernel, AFF_GLOBAL, true, 1, 1, 0)
-// the 3 walks of a two-piece run (option "gap_open2"): global mode's, short, long and banded long
-AFF_TRACEBACK_KERNEL(sw_affine_traceback2_global_kernel, AFF_GLOBAL, false, 0, 0, 1)
-AFF_TRACEBACK_KERNEL(sw_affine_traceback2_long_global_kernel, AFF_GLOBAL, true, 0, 0, 1)
-AFF_TRACEBACK_KERNEL(sw_affine_traceback2_band_global_kernel, AFF_GLOBAL, true, 1, 0, 1)
+AFF_TRACEBACKS(AFF_TRACEBACK_KERNEL)
 #undef AFF_TRACEBACK_KERNEL
-#undef AFF_TB_PARAMS_0
-#undef AFF_TB_PARAMS_1
-#undef AFF_TB_ARGS_0
-#undef AFF_TB_ARGS_1
 
 // ------------------------------------------------------------------------------------------------
 // host-callable launchers
 // ------------------------------------------------------------------------------------------------
 // Both take the run's options as one AffRun and refuse what aff_run_ok refuses (swmi_launch.h, which describes the arguments).
-// A kernel is picked from tables typed by signature -- ten for the sweeps: with / without the matrix, the half-width and the
-// threshold, and the two-piece sweeps with / without the half-width (the sweeps of option "subopt" have their twins' signatures, those of
-// option "end_bonus" their twins' and the bonus); two for the walks -- and launched through one generic
-// lambda, so that every launch is checked against its kernel's parameter list: one branch per signature.
+// Each has ONE table, the list above under a macro: a row is the kernel's key (aff_key of its shape, mode and flags), a launch
+// stub and the kernel's name.  The stub is a captureless lambda that launches its own kernel with the pieces of AffRun the
+// kernel's flags ask for, so every launch is checked against its kernel's parameter list, whatever the signature.  A run's key is
+// searched for; no row, no kernel: hipErrorInvalidValue.
 static_assert(AFF_EXTEND == 3, "AffRun.mode 3 is the extend run");
+namespace {
+struct AffSweepRow {
+    uint32_t key;
+    void (*launch)(const FillArgs &a, const AffRun &r, dim3 grid, hipStream_t st);
+    const char *name;
+};
+#define AFF_SWEEP_ROW(name, RLO, RHI, MODE, MATRIX, LONG, BAND, XDROP, ADAPT, TWO, SUBOPT, ENDB, HITS)                               \
+    {aff_key(LONG ? 2u : RLO == 1 ? 0u : 1u, MODE, aff_flags(MATRIX, LONG, BAND, XDROP, ADAPT, TWO, SUBOPT, ENDB, HITS)),            \
+     [](const FillArgs &a, const AffRun &r, dim3 grid, hipStream_t st) {                                                             \
+         hipLaunchKernelGGL(name, grid, dim3(WAVE * AFF_WAVES), 0, st, a, (int)r.gap_open AFF_IF_##TWO(, (int)r.gap_open2, (int)r.gap2) \
+                            AFF_IF_##MATRIX(, r.mat, r.nn) AFF_IF_##BAND(, r.band) AFF_IF_##XDROP(, r.xdrop) AFF_IF_##ENDB(, r.end_bonus)); \
+     }, #name},
+const AffSweepRow aff_sweeps[] = {AFF_SWEEPS(AFF_SWEEP_ROW)};
+#undef AFF_SWEEP_ROW
+
+struct AffTracebackRow {
+    uint32_t key;
+    void (*launch)(const TraceArgs &a, const AffRun &r, uint32_t tile_words, uint32_t ops_words, hipStream_t st);
+    const char *name;
+    const void *kernel;          // for swmi_allow_big_lds
+};
+#define AFF_TRACEBACK_ROW(name, MODE, LONG, BAND, ADAPT, TWO)                                                                        \
+    {aff_key(0u, MODE, AFF_TB_FLAGS(LONG, BAND, ADAPT, TWO)),                                                                        \
+     [](const TraceArgs &a, const AffRun &r, uint32_t tile_words, uint32_t ops_words, hipStream_t st) {                              \
+         const size_t lds = ((size_t)tile_words + ops_words + SWMI_EMIT_SCRATCH_WORDS) * sizeof(uint32_t);                           \
+         hipLaunchKernelGGL(name, dim3(a.n_pairs, SWMI_AFF_TB_SLOTS), dim3(WAVE), lds, st, a, tile_words, ops_words, r.cigar         \
+                            AFF_IF_##BAND(, r.band));                                                                                \
+     }, #name, reinterpret_cast<const void *>(name)},
+const AffTracebackRow aff_tracebacks[] = {AFF_TRACEBACKS(AFF_TRACEBACK_ROW)};
+#undef AFF_TRACEBACK_ROW
+
+// The rows of a run's kernels, null where the launchers refuse.  shape: 0 narrow, 1 wide, 2 long.
+const AffSweepRow *aff_sweep_row(const AffRun &r, uint32_t long_reads, uint32_t shape) {
+    if (!aff_run_ok(r, long_reads)) return nullptr;
+    const uint32_t key = aff_key(shape, r.mode, aff_run_flags(r, long_reads));
+    for (const AffSweepRow &row : aff_sweeps) if (row.key == key) return &row;
+    return nullptr;
+}
+const AffTracebackRow *aff_traceback_row(const AffRun &r, uint32_t long_reads) {
+    if (!aff_run_ok(r, long_reads)) return nullptr;
+    // an extend run is walked by global mode's kernels: aff_traceback<AFF_GLOBAL, ..> starts at whatever cell the list names and
+    // makes no use of its being (m, n) (DESIGN.md 8g)
+    const uint32_t mode = r.mode == AFF_EXTEND ? AFF_GLOBAL : r.mode;
+    const uint32_t key = aff_key(0u, mode, aff_run_flags(r, long_reads) & (AFF_F_LONG | AFF_F_BAND | AFF_F_ADAPT | AFF_F_TWO));
+    for (const AffTracebackRow &row : aff_tracebacks) if (row.key == key) return &row;
+    return nullptr;
+}
+}  // namespace
+
+extern "C" int swmi_affine_run_ok(const AffRun *r, uint32_t long_reads) { return aff_run_ok(*r, long_reads) ? 1 : 0; }
+extern "C" const char *swmi_affine_sweep_name(const AffRun *r, uint32_t long_reads, uint32_t shape) {
+    const AffSweepRow *row = aff_sweep_row(*r, long_reads, shape);
+    return row ? row->name : nullptr;
+}
+extern "C" const char *swmi_affine_traceback_name(const AffRun *r, uint32_t long_reads) {
+    const AffTracebackRow *row = aff_traceback_row(*r, long_reads);
+    return row ? row->name : nullptr;
+}
 
 extern "C" hipError_t swmi_launch_affine_sweep(const FillArgs *a, const AffRun *r, uint32_t long_reads, uint32_t r_min, uint32_t r_max,
                                                hipStream_t st) {
     if (a->n_pairs == 0) return hipSuccess;
-    if (!aff_run_ok(*r, long_reads)) return hipErrorInvalidValue;
-    // [narrow / wide / long][mode]
-    static void (*const plain[3][4])(FillArgs, int) = {
-        {sw_affine_sweep_kernel, sw_affine_sweep_fit_kernel, sw_affine_sweep_global_kernel, sw_affine_sweep_extend_kernel},
-        {sw_affine_sweep_wide_kernel, sw_affine_sweep_fit_wide_kernel, sw_affine_sweep_global_wide_kernel, sw_affine_sweep_extend_wide_kernel},
-        {sw_affine_sweep_long_kernel, sw_affine_sweep_long_fit_kernel, sw_affine_sweep_long_global_kernel, sw_affine_sweep_long_extend_kernel}};
-    static void (*const matrix[3][4])(FillArgs, int, const uint32_t *, uint32_t) = {
-        {sw_affine_sweep_matrix_kernel, sw_affine_sweep_fit_matrix_kernel, sw_affine_sweep_global_matrix_kernel, sw_affine_sweep_extend_matrix_kernel},
-        {sw_affine_sweep_matrix_wide_kernel, sw_affine_sweep_fit_matrix_wide_kernel, sw_affine_sweep_global_matrix_wide_kernel,
-         sw_affine_sweep_extend_matrix_wide_kernel},
-        {sw_affine_sweep_long_matrix_kernel, sw_affine_sweep_long_fit_matrix_kernel, sw_affine_sweep_long_global_matrix_kernel,
-         sw_affine_sweep_long_extend_matrix_kernel}};
-    // the banded strip sweeps, [mode] and, under option "band_adapt" (an extend run), [4]
-    static void (*const bplain[5])(FillArgs, int, uint32_t) = {
-        sw_affine_sweep_band_kernel, sw_affine_sweep_band_fit_kernel, sw_affine_sweep_band_global_kernel, sw_affine_sweep_band_extend_kernel,
-        sw_affine_sweep_band_adapt_kernel};
-    static void (*const bmatrix[5])(FillArgs, int, const uint32_t *, uint32_t, uint32_t) = {
-        sw_affine_sweep_band_matrix_kernel, sw_affine_sweep_band_fit_matrix_kernel, sw_affine_sweep_band_global_matrix_kernel,
-        sw_affine_sweep_band_extend_matrix_kernel, sw_affine_sweep_band_adapt_matrix_kernel};
-    // the strip sweeps of an extend run under option "xdrop" (the threshold is the last argument); the banded ones [band_adapt]
-    static void (*const xplain)(FillArgs, int, uint32_t) = sw_affine_sweep_long_xdrop_kernel;
-    static void (*const xmatrix)(FillArgs, int, const uint32_t *, uint32_t, uint32_t) = sw_affine_sweep_long_xdrop_matrix_kernel;
-    static void (*const xbplain[2])(FillArgs, int, uint32_t, uint32_t) = {sw_affine_sweep_band_xdrop_kernel, sw_affine_sweep_band_adapt_xdrop_kernel};
-    static void (*const xbmatrix[2])(FillArgs, int, const uint32_t *, uint32_t, uint32_t, uint32_t) = {
-        sw_affine_sweep_band_xdrop_matrix_kernel, sw_affine_sweep_band_adapt_xdrop_matrix_kernel};
-    // the two-piece sweeps, [narrow / wide / long][extend], and [extend] of the banded long ones
-    static void (*const tplain[3][2])(FillArgs, int, int, int) = {
-        {sw_affine_sweep2_global_kernel, sw_affine_sweep2_extend_kernel},
-        {sw_affine_sweep2_global_wide_kernel, sw_affine_sweep2_extend_wide_kernel},
-        {sw_affine_sweep2_long_global_kernel, sw_affine_sweep2_long_extend_kernel}};
-    static void (*const tbplain[2])(FillArgs, int, int, int, uint32_t) = {sw_affine_sweep2_band_global_kernel, sw_affine_sweep2_band_extend_kernel};
-    // the local sweeps under option "subopt", [with option "hits"][narrow / wide / long], and [hits] of the banded long ones
-    static void (*const splain[2][3])(FillArgs, int) = {
-        {sw_affine_sweep_subopt_kernel, sw_affine_sweep_subopt_wide_kernel, sw_affine_sweep_long_subopt_kernel},
-        {sw_affine_sweep_hits_kernel, sw_affine_sweep_hits_wide_kernel, sw_affine_sweep_long_hits_kernel}};
-    static void (*const smatrix[2][3])(FillArgs, int, const uint32_t *, uint32_t) = {
-        {sw_affine_sweep_subopt_matrix_kernel, sw_affine_sweep_subopt_matrix_wide_kernel, sw_affine_sweep_long_subopt_matrix_kernel},
-        {sw_affine_sweep_hits_matrix_kernel, sw_affine_sweep_hits_matrix_wide_kernel, sw_affine_sweep_long_hits_matrix_kernel}};
-    static void (*const sbplain[2])(FillArgs, int, uint32_t) = {sw_affine_sweep_band_subopt_kernel, sw_affine_sweep_band_hits_kernel};
-    static void (*const sbmatrix[2])(FillArgs, int, const uint32_t *, uint32_t, uint32_t) = {
-        sw_affine_sweep_band_subopt_matrix_kernel, sw_affine_sweep_band_hits_matrix_kernel};
-    // the extend sweeps under option "end_bonus" (the bonus is the last argument), [narrow / wide / long], and the banded long ones
-    static void (*const eplain[3])(FillArgs, int, uint32_t) = {sw_affine_sweep_endb_kernel, sw_affine_sweep_endb_wide_kernel, sw_affine_sweep_long_endb_kernel};
-    static void (*const ematrix[3])(FillArgs, int, const uint32_t *, uint32_t, uint32_t) = {
-        sw_affine_sweep_endb_matrix_kernel, sw_affine_sweep_endb_matrix_wide_kernel, sw_affine_sweep_long_endb_matrix_kernel};
-    static void (*const ebplain)(FillArgs, int, uint32_t, uint32_t) = sw_affine_sweep_band_endb_kernel;
-    static void (*const ebmatrix)(FillArgs, int, const uint32_t *, uint32_t, uint32_t, uint32_t) = sw_affine_sweep_band_endb_matrix_kernel;
-    const dim3 grid((a->n_pairs + AFF_WAVES - 1) / AFF_WAVES), block(WAVE * AFF_WAVES);
-    // (extra...: what the kernel takes after the arguments every sweep takes.  A launch's own error is what hipGetLastError returns below)
-    const auto launch = [&](auto *k, auto... extra) { hipLaunchKernelGGL(k, grid, block, 0, st, *a, (int)r->gap_open, extra...); };
-    const uint32_t mode = r->mode, band = long_reads ? r->band : 0u, xdrop = long_reads ? r->xdrop : 0u;      // (options of the long shape only)
-    const uint32_t adapt = band ? r->adapt : 0u, nn = r->nn;
-    const uint32_t *const mat = r->mat;
-    const uint32_t hits = r->hits ? 1u : 0u;                      // (aff_run_ok: with subopt only)
-    const uint32_t endb = r->end_bonus;                           // (aff_run_ok: an extend run without xdrop, band_adapt or gap_open2)
-    const auto sweep = [&](int shape) {
-        if (r->gap_open2 && band)  launch(tbplain[mode - 2u], (int)r->gap_open2, (int)r->gap2, band);
-        else if (r->gap_open2)     launch(tplain[shape][mode - 2u], (int)r->gap_open2, (int)r->gap2);
-        else if (r->subopt && mat && band) launch(sbmatrix[hits], mat, nn, band);
-        else if (r->subopt && mat) launch(smatrix[hits][shape], mat, nn);
-        else if (r->subopt && band) launch(sbplain[hits], band);
-        else if (r->subopt)        launch(splain[hits][shape]);
-        else if (endb && mat && band) launch(ebmatrix, mat, nn, band, endb);
-        else if (endb && mat)      launch(ematrix[shape], mat, nn, endb);
-        else if (endb && band)     launch(ebplain, band, endb);
-        else if (endb)             launch(eplain[shape], endb);
-        else if (mat && band && xdrop) launch(xbmatrix[adapt], mat, nn, band, xdrop);
-        else if (mat && band)      launch(bmatrix[adapt ? 4u : mode], mat, nn, band);
-        else if (mat && xdrop)     launch(xmatrix, mat, nn, xdrop);
-        else if (mat)              launch(matrix[shape][mode], mat, nn);
-        else if (band && xdrop)    launch(xbplain[adapt], band, xdrop);
-        else if (band)             launch(bplain[adapt ? 4u : mode], band);
-        else if (xdrop)            launch(xplain, xdrop);
-        else                       launch(plain[shape][mode]);
+    const dim3 grid((a->n_pairs + AFF_WAVES - 1) / AFF_WAVES);
+    const auto sweep = [&](uint32_t shape) {
+        const AffSweepRow *row = aff_sweep_row(*r, long_reads, shape);
+        if (row) row->launch(*a, *r, grid, st);
+        return row != nullptr;
     };
-    if (long_reads) sweep(2);
-    else {
-        if (r_min <= 4u) sweep(0);
-        if (r_max >= 5u) sweep(1);
-    }
-    return hipGetLastError();
+    // the short shape: the narrow and the wide sweep, each only if the launch has pairs for it
+    const bool ok = long_reads ? sweep(2u) : (r_min > 4u || sweep(0u)) && (r_max < 5u || sweep(1u));
+    return ok ? hipGetLastError() : hipErrorInvalidValue;      // (a launch's own error is what hipGetLastError returns)
 }
 
 extern "C" hipError_t swmi_launch_affine_traceback(const TraceArgs *a, const AffRun *r, uint32_t long_reads, uint32_t tile_words,
                                                    uint32_t ops_words, hipStream_t st) {
     if (a->n_pairs == 0) return hipSuccess;
-    if (!aff_run_ok(*r, long_reads)) return hipErrorInvalidValue;
-    const bool two = r->gap_open2 != 0;
+    const AffTracebackRow *row = aff_traceback_row(*r, long_reads);
+    if (!row) return hipErrorInvalidValue;
     // (the fields of the two-piece sweeps: the tile holds at least one block of 2 * R * 64 dwords)
-    if (two && tile_words < 2u * SWMI_AFF_RMAX * WAVE) return hipErrorInvalidValue;
-    // an extend run is walked by global mode's kernels: aff_traceback<AFF_GLOBAL, ..> starts at whatever cell the list names and
-    // makes no use of its being (m, n) (DESIGN.md 8g)
-    const uint32_t mode = r->mode == AFF_EXTEND ? AFF_GLOBAL : r->mode;
-    // [long_reads][mode], then the two-piece walks [long_reads] (global mode's)
-    static void (*const kern[8])(TraceArgs, uint32_t, uint32_t, uint32_t) = {
-        sw_affine_traceback_kernel, sw_affine_traceback_fit_kernel, sw_affine_traceback_global_kernel,
-        sw_affine_traceback_long_kernel, sw_affine_traceback_long_fit_kernel, sw_affine_traceback_long_global_kernel,
-        sw_affine_traceback2_global_kernel, sw_affine_traceback2_long_global_kernel};
-    // the banded long walks, which take the half-width: [mode], then option "band_adapt"'s and the two-piece one (global mode's)
-    static void (*const bkern[5])(TraceArgs, uint32_t, uint32_t, uint32_t, uint32_t) = {
-        sw_affine_traceback_band_kernel, sw_affine_traceback_band_fit_kernel, sw_affine_traceback_band_global_kernel,
-        sw_affine_traceback_band_adapt_global_kernel, sw_affine_traceback2_band_global_kernel};
+    if (r->gap_open2 && tile_words < 2u * SWMI_AFF_RMAX * WAVE) return hipErrorInvalidValue;
     static const bool attrs = [] {
-        for (auto *k : kern) swmi_allow_big_lds(k);
-        for (auto *k : bkern) swmi_allow_big_lds(k);
+        for (const AffTracebackRow &t : aff_tracebacks) swmi_allow_big_lds(t.kernel);
         return true;
     }();
     (void)attrs;
-    const size_t lds = ((size_t)tile_words + ops_words + SWMI_EMIT_SCRATCH_WORDS) * sizeof(uint32_t);
-    // (band...: the half-width, for the kernels that take it)
-    const auto launch = [&](auto *k, auto... band) {
-        hipLaunchKernelGGL(k, dim3(a->n_pairs, SWMI_AFF_TB_SLOTS), dim3(WAVE), lds, st, *a, tile_words, ops_words, r->cigar, band...);
-    };
-    const uint32_t lng = long_reads ? 1u : 0u;
-    if (long_reads && r->band) launch(bkern[two ? 4u : r->adapt ? 3u : mode], r->band);
-    else                       launch(kern[two ? 6u + lng : 3u * lng + mode]);
+    row->launch(*a, *r, tile_words, ops_words, st);
     return hipGetLastError();
 }
-

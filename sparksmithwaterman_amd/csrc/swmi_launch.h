@@ -34,21 +34,53 @@ struct AffRun {
     uint32_t hits;               // option "hits" (0: off; 1 .. 16 = K, with subopt only) -- the local sweeps that leave the maxima's rows as well
     uint32_t end_bonus;          // option "end_bonus" (0: off; 1 .. 2^30: the bonus) -- the extend sweeps that also choose the read's end
 };
-// What the launchers refuse (hipErrorInvalidValue): the combinations no kernel exists for.  band, xdrop and adapt are options of
-// the long shape (long_reads: every pair of the launch has a read longer than SWMI_AFF_MAX_READ); the short shape ignores them.
-// Every run check_run_params (swmi_run.cpp) admits passes.
-static inline bool aff_run_ok(const AffRun &r, uint32_t long_reads) {
-    if (r.mode > 3u || r.band > SWMI_AFF_BAND_MAX || r.xdrop > 0x7FFFFFFFu || r.adapt > 1u || r.cigar > 2u) return false;
-    if (r.mat && (r.nn < 2u || r.nn > SWMI_MAT_NN_MAX)) return false;
-    if (r.gap_open2 && (r.mode < 2u || r.mat || r.xdrop || r.adapt)) return false;      // two-piece: plain global and extend runs
-    if (r.subopt < -1 || r.subopt > (1 << 30) || (r.subopt && r.mode != 0u)) return false;   // subopt: local runs
-    if (r.hits > SWMI_HITS_MAX || (r.hits && !r.subopt)) return false;                   // hits: runs under subopt
-    // end_bonus: one-piece extend runs without xdrop or band_adapt
-    if (r.end_bonus > (1u << 30) || (r.end_bonus && (r.mode != 3u || r.xdrop || r.adapt || r.gap_open2 || r.subopt))) return false;
-    if (long_reads && r.xdrop && r.mode != 3u) return false;                            // xdrop: extend runs
-    if (long_reads && r.adapt && (!r.band || r.mode != 3u)) return false;               // band_adapt: banded extend runs
+// The flags word of an affine kernel: the 0/1 columns of the kernel lists of swmi_affine.hip (AFF_SWEEPS, AFF_TRACEBACKS), the
+// template argument of the device functions there and, with the mode and the shape, the key a launcher finds a kernel by.
+enum : uint32_t {
+    AFF_F_MATRIX = 1u << 0, AFF_F_LONG = 1u << 1, AFF_F_BAND = 1u << 2, AFF_F_XDROP = 1u << 3, AFF_F_ADAPT = 1u << 4,
+    AFF_F_TWO = 1u << 5, AFF_F_SUBOPT = 1u << 6, AFF_F_ENDB = 1u << 7, AFF_F_HITS = 1u << 8
+};
+constexpr uint32_t aff_flags(bool matrix, bool lng, bool band, bool xdrop, bool adapt, bool two, bool subopt, bool endb, bool hits) {
+    return (matrix ? AFF_F_MATRIX : 0u) | (lng ? AFF_F_LONG : 0u) | (band ? AFF_F_BAND : 0u) | (xdrop ? AFF_F_XDROP : 0u) |
+           (adapt ? AFF_F_ADAPT : 0u) | (two ? AFF_F_TWO : 0u) | (subopt ? AFF_F_SUBOPT : 0u) | (endb ? AFF_F_ENDB : 0u) | (hits ? AFF_F_HITS : 0u);
+}
+// shape: 0 narrow (1 .. 4 rows per lane), 1 wide (5 .. 16), 2 long (the strip sweeps); the walks have one shape, 0
+constexpr uint32_t aff_key(uint32_t shape, uint32_t mode, uint32_t flags) { return flags | mode << 9 | shape << 11; }
+// The combinations a kernel may exist for (mode: 0 local, 1 fit, 2 global, 3 extend).  Every row of the two lists and every
+// device entry static_asserts it; aff_run_ok refuses a run by it.
+constexpr bool aff_flags_ok(uint32_t mode, uint32_t f) {
+    const bool xdrop_or_adapt = f & (AFF_F_XDROP | AFF_F_ADAPT);
+    if (mode > 3u) return false;
+    if ((f & AFF_F_BAND) && !(f & AFF_F_LONG)) return false;                             // band: the strip sweeps
+    if ((f & AFF_F_XDROP) && !((f & AFF_F_LONG) && mode == 3u)) return false;            // xdrop: the strip sweeps of an extend run
+    if ((f & AFF_F_ADAPT) && !((f & AFF_F_BAND) && mode == 3u)) return false;            // band_adapt: the banded ones
+    if ((f & AFF_F_TWO) && (mode < 2u || (f & AFF_F_MATRIX) || xdrop_or_adapt)) return false;    // two-piece: plain global and extend runs
+    if ((f & AFF_F_SUBOPT) && mode != 0u) return false;                                  // subopt: local runs
+    if ((f & AFF_F_HITS) && !(f & AFF_F_SUBOPT)) return false;                           // hits: runs under subopt
+    if ((f & AFF_F_ENDB) && (mode != 3u || xdrop_or_adapt || (f & AFF_F_TWO))) return false;     // end_bonus: one-piece extend runs
     return true;
 }
+// The flags of a run's kernels.  band, xdrop and adapt are options of the long shape (long_reads: every pair of the launch has a
+// read longer than SWMI_AFF_MAX_READ); the short shape ignores them.  (band_adapt without a band: no kernel, aff_flags_ok.)
+static inline uint32_t aff_run_flags(const AffRun &r, uint32_t long_reads) {
+    return aff_flags(r.mat != nullptr, long_reads != 0u, long_reads && r.band, long_reads && r.xdrop, long_reads && r.adapt,
+                     r.gap_open2 != 0, r.subopt != 0, r.end_bonus != 0u, r.hits != 0u);
+}
+// What the launchers refuse (hipErrorInvalidValue): values out of range and the combinations no kernel exists for.
+// Every run check_run_params (swmi_run.cpp) admits passes.
+static inline bool aff_run_ok(const AffRun &r, uint32_t long_reads) {
+    if (r.band > SWMI_AFF_BAND_MAX || r.xdrop > 0x7FFFFFFFu || r.adapt > 1u || r.cigar > 2u) return false;
+    if (r.mat && (r.nn < 2u || r.nn > SWMI_MAT_NN_MAX)) return false;
+    if (r.subopt < -1 || r.subopt > (1 << 30) || r.hits > SWMI_HITS_MAX || r.end_bonus > (1u << 30)) return false;
+    // two-piece and end_bonus runs take neither xdrop nor band_adapt, whatever the shape
+    if ((r.gap_open2 || r.end_bonus) && (r.xdrop || r.adapt)) return false;
+    return aff_flags_ok(r.mode, aff_run_flags(r, long_reads));
+}
+// The kernel the launchers below pick for a run, by name -- null where they refuse the run; shape: 0 narrow, 1 wide, 2 long (what
+// a launch with long_reads set asks for).  They call no HIP function.  For the tests: not part of include/swmi.h.
+extern "C" int swmi_affine_run_ok(const AffRun *r, uint32_t long_reads);
+extern "C" const char *swmi_affine_sweep_name(const AffRun *r, uint32_t long_reads, uint32_t shape);
+extern "C" const char *swmi_affine_traceback_name(const AffRun *r, uint32_t long_reads);
 // long_reads 0: the pairs with reads of at most SWMI_AFF_MAX_READ bases; r_min / r_max: the rows per lane of the launch's shortest
 // and longest read (the narrow and the wide sweep: only the one that has pairs is launched).  long_reads 1: the strip kernels.
 extern "C" hipError_t swmi_launch_affine_sweep(const FillArgs *a, const AffRun *r, uint32_t long_reads, uint32_t r_min, uint32_t r_max,
