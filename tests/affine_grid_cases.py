@@ -129,6 +129,45 @@ def shape_grid(matrix=False):
     return _SHAPE[matrix]
 
 
+# ---- the option grids: subopt and hits run the shape grid; end_bonus has a grid of its own ----
+GRID_SUBOPT = 10                                                    # the mask half-width of test_grid_subopt and test_grid_hits
+GRID_HITS = 4
+ENDB_BONUSES = (1, 12)
+
+_ENDB = {}
+
+
+def endb_grid(R, matrix=False):
+    """(refs, reads) of class R for option end_bonus.  The shape grid's references end far before a long read does, so there only
+    the classes up to 7 ever take a pair to the end.  Here the reads are the three prefixes of one base sequence of 64 R bases with
+    the class's GRID_LENGTHS, and the references are cut from mutated copies of it: one ends a few bases before the shortest read
+    does, one between the ends of the two longer reads, one is a whole copy; each has a random tail, the last one 20 bases of it."""
+    if (R, matrix) not in _ENDB:
+        rng = random.Random(7500 + 16 * int(matrix) + R)
+        draw = MATRIX_DRAW if matrix else PLAIN_ALPHABET
+        base = rand_seq(rng, 64 * R, draw)
+        first, mid, last = GRID_LENGTHS[3 * (R - 1):3 * R]
+        reads = [base[:m] for m in (first, mid, last)]
+        refs = [mutate(rng, base, draw, 0.05, 0.01)[:cut] + rand_seq(rng, tail, draw)
+                for cut, tail in ((max(1, first - 4), 5), ((mid + last) // 2, 7), (last + 64, 20))]       # (the last: the whole copy)
+        _ENDB[(R, matrix)] = (refs, reads)
+    return _ENDB[(R, matrix)]
+
+
+# ---- the banded matrix run of subopt and hits: sw_affine_sweep_band_{subopt,hits}_matrix_kernel ----
+BAND_MATRIX_W, BAND_MATRIX_SUBOPT, BAND_MATRIX_HITS = 32, 60, 8
+_BAND_MATRIX = []
+
+
+def band_matrix_case():
+    """(ref, read): a read of 1100 bases -- two strips, 76 rows in the second -- and a mutated copy of it plus 40 random bases"""
+    if not _BAND_MATRIX:
+        rng = random.Random(7551)
+        read = rand_seq(rng, 1100, MATRIX_DRAW)
+        _BAND_MATRIX.append((mutate(rng, read, MATRIX_DRAW, 0.04, 0.004) + rand_seq(rng, 40, MATRIX_DRAW), read))
+    return _BAND_MATRIX[0]
+
+
 def walk_plan(R):
     """(m, inserted read bases, deleted reference columns) of the walk-grid pair of class R.  The reads of R = 1 and 2 (51 and
     115 bases) are too short for a run of 40 and one of 24 next to stretches that pay for them: 8 and 8, and 20 and 16."""

@@ -1,78 +1,28 @@
-"""Every rows-per-lane class of the affine kernels in every mode (swmi_affine.hip), against the restatements of the contract.
+"""The affine kernels (swmi_affine.hip) against the restatements of the contract: every rows-per-lane class of every narrow and wide
+sweep, and every kernel of the two lists AFF_SWEEPS and AFF_TRACEBACKS.
 
-The 40 sweep kernels and 10 traceback kernels, and the tests that run them (G: this module; a new kernel goes into this table).
-Between them the tests named on a row of the extend, xdrop and band_adapt kernels run both tie orders; a test that runs the
-strict order is marked `strict:` where the others on the row run the serial one only:
+What the module guarantees, and tests/test_affine_grid_cpu.py enforces without a GPU:
+  * every (R, mode, matrix, tie order) body of the local, fit and global sweeps is run by test_grid_shapes and test_grid_walks, and
+    every (R, matrix, tie order) body of the subopt, hits and end_bonus sweeps by test_grid_subopt, test_grid_hits and
+    test_grid_end_bonus -- 192 + 192 bodies (test_gpu_module_reaches_every_body); option "extend" has its grid in
+    tests/test_extend_gpu.py and the two-piece sweeps theirs in tests/test_twopiece_gpu.py::test_rows_per_lane_classes;
+  * every listed kernel is launched by test_census, in both tie orders, on inputs that make its own rule matter, and everything
+    the run returns is compared: tests/affine_census.py derives the list from the launchers' own selection, so a kernel added to
+    a list without an admitted run and an input recipe fails test_census_is_the_kernel_lists, which names it.
 
-  sweep kernel (sw_affine_sweep_...)    rows per lane     run by
-  kernel                                1 .. 4            G test_grid_shapes[0-False-*], test_grid_walks[0-False-*]; test_affine_gpu.py
-  wide_kernel                           5 .. 16           G test_grid_shapes[0-False-*], test_grid_walks[0-False-*]; test_affine_gpu.py
-  long_kernel                           strips of 16      test_long_reads_gpu.py::test_long_reads_strip_counts_and_skew
-  matrix_kernel                         1 .. 4            G test_grid_shapes[0-True-*], test_grid_walks[0-True-*]; test_matrix_gpu.py
-  matrix_wide_kernel                    5 .. 16           G test_grid_shapes[0-True-*], test_grid_walks[0-True-*]; test_matrix_gpu.py
-  long_matrix_kernel                    strips of 16      test_long_reads_gpu.py::test_long_reads_blosum62[0]
-  fit_kernel                            1 .. 4            G test_grid_shapes[1-False-*], test_grid_walks[1-False-*]; test_ends_gpu.py
-  fit_wide_kernel                       5 .. 16           G test_grid_shapes[1-False-*], test_grid_walks[1-False-*]; test_ends_gpu.py
-  long_fit_kernel                       strips of 16      G test_mixed_launch_fit_global[1-False]; test_long_reads_gpu.py::test_long_reads_fit_and_global
-  fit_matrix_kernel                     1 .. 4            G test_grid_shapes[1-True-*], test_grid_walks[1-True-*]
-  fit_matrix_wide_kernel                5 .. 16           G test_grid_shapes[1-True-*], test_grid_walks[1-True-*]
-  long_fit_matrix_kernel                strips of 16      G test_mixed_launch_fit_global[1-True] (no other test)
-  global_kernel                         1 .. 4            G test_grid_shapes[2-False-*], test_grid_walks[2-False-*]; test_ends_gpu.py
-  global_wide_kernel                    5 .. 16           G test_grid_shapes[2-False-*], test_grid_walks[2-False-*]; test_ends_gpu.py
-  long_global_kernel                    strips of 16      G test_mixed_launch_fit_global[2-False]; test_long_reads_gpu.py::test_long_reads_fit_and_global
-  global_matrix_kernel                  1 .. 4            G test_grid_shapes[2-True-*], test_grid_walks[2-True-*]
-  global_matrix_wide_kernel             5 .. 16           G test_grid_shapes[2-True-*], test_grid_walks[2-True-*]
-  long_global_matrix_kernel             strips of 16      G test_mixed_launch_fit_global[2-True]; test_long_reads_gpu.py::test_long_reads_blosum62[2]
-  band_kernel                           strips of 16      test_band_gpu.py::test_band_shapes; G test_c99_shim_sets_long_reads_and_band
-  band_matrix_kernel                    strips of 16      test_band_gpu.py::test_band_blosum62[0]
-  band_fit_kernel                       strips of 16      G test_mixed_launch_fit_global[1-False]; test_band_gpu.py::test_band_shapes
-  band_fit_matrix_kernel                strips of 16      G test_mixed_launch_fit_global[1-True]; test_band_gpu.py::test_band_64_symbol_matrix
-  band_global_kernel                    strips of 16      G test_mixed_launch_fit_global[2-False]; test_band_gpu.py::test_band_shapes
-  band_global_matrix_kernel             strips of 16      G test_mixed_launch_fit_global[2-True]; test_band_gpu.py::test_band_blosum62[2]
-  (option "extend" on a global run: test_extend_gpu.py, E)
-  extend_kernel                         1 .. 4            E test_extend_grid_shapes[False-*], test_extend_grid_walks[False-*], test_extend_kats
-  extend_wide_kernel                    5 .. 16           E test_extend_grid_shapes[False-*], test_extend_grid_walks[False-*]
-  long_extend_kernel                    strips of 16      E test_extend_mixed_launch[False]; strict: test_extend_long_reads
-  extend_matrix_kernel                  1 .. 4            E test_extend_grid_shapes[True-*], test_extend_grid_walks[True-*]
-  extend_matrix_wide_kernel             5 .. 16           E test_extend_grid_shapes[True-*], test_extend_grid_walks[True-*]
-  long_extend_matrix_kernel             strips of 16      E test_extend_mixed_launch[True]; strict: test_extend_long_read_with_a_matrix_strict_ties
-  band_extend_kernel                    strips of 16      E test_extend_band_geometry; strict: test_extend_band_maximum_on_a_window_edge, test_extend_band_shapes_and_matrix
-  band_extend_matrix_kernel             strips of 16      E test_extend_mixed_launch[True]; strict: test_extend_band_shapes_and_matrix
-  (option "xdrop" on an extend run: test_xdrop_gpu.py, X)
-  long_xdrop_kernel                     strips of 16      X test_xdrop_hand_derivable[0], test_xdrop_strip_edges; strict: test_xdrop_random_tails[1-0]
-  long_xdrop_matrix_kernel              strips of 16      X test_xdrop_mixed_launch[True-0]; strict: test_xdrop_matrix_strict_ties[0]
-  band_xdrop_kernel                     strips of 16      X test_xdrop_hand_derivable[64 / 16]; strict: test_xdrop_random_tails[1-64 / 16]
-  band_xdrop_matrix_kernel              strips of 16      X test_xdrop_mixed_launch[True-64]; strict: test_xdrop_matrix_strict_ties[64]
-  (option "band_adapt" on a banded extend run: test_adapt_gpu.py, A)
-  band_adapt_kernel                     strips of 16      A test_adapt_tie_rule; strict: test_adapt_drift[*-1], test_adapt_centre_stands_still[1], test_adapt_ties_and_the_rerun[1]
-  band_adapt_matrix_kernel              strips of 16      A test_adapt_mixed_launch[True]; strict: test_adapt_matrix_strict_ties
-  band_adapt_xdrop_kernel               strips of 16      A test_adapt_xdrop_planted_head; strict: test_adapt_xdrop_diverging_tail
-  band_adapt_xdrop_matrix_kernel        strips of 16      A test_adapt_mixed_launch_xdrop[True]; strict: test_adapt_matrix_strict_ties
-
-  traceback kernel (sw_affine_traceback_...)              run by
-  kernel                                                  G test_grid_walks[0-*] (walks of several tiles); test_affine_gpu.py
-  fit_kernel                                              G test_grid_walks[1-*], test_grid_shapes[1-*]; test_ends_gpu.py
-  global_kernel                                           G test_grid_walks[2-*], test_grid_shapes[2-*]; test_ends_gpu.py
-  long_kernel                                             test_long_reads_gpu.py::test_long_reads_across_the_seam
-  long_fit_kernel                                         G test_mixed_launch_fit_global[1-*]; test_long_reads_gpu.py::test_long_reads_fit_and_global
-  long_global_kernel                                      G test_mixed_launch_fit_global[2-*]; test_long_reads_gpu.py::test_long_reads_fit_and_global
-  band_kernel                                             test_band_gpu.py::test_band_edges[0]; G test_c99_shim_sets_long_reads_and_band
-  band_fit_kernel                                         G test_mixed_launch_fit_global[1-*]; test_band_gpu.py::test_band_edges[1]
-  band_global_kernel                                      G test_mixed_launch_fit_global[2-*]; test_band_gpu.py::test_band_edges[2]
-  band_adapt_global_kernel                                A every test of test_adapt_gpu.py but the scores_only case
-  (an extend run is walked by global_kernel, long_global_kernel and band_global_kernel, started at cells other than (m, n):
-  E test_extend_grid_walks, test_extend_long_reads, test_extend_band_maximum_on_a_window_edge)
-
-Each narrow and wide sweep kernel holds one body per (R, tie order): 16 x 3 modes x 2 (plain / matrix) x 2 tie orders = 192
-bodies.  GRID_PARAMS below times the 16 classes of affine_grid_cases.RS is that grid; tests/test_affine_grid_cpu.py checks it.
-All comparisons are exact: score, flags, number and order of the alignments, every begin and both strings, and the MapRef view."""
+Each narrow and wide sweep kernel holds one body per (R, tie order).  All comparisons are exact: score, flags, number and order of
+the alignments, every begin, both strings and the maximum cell, the MapRef view, and each option's own values."""
 import pytest
 
 import sparksmithwaterman_amd as sw
 
+import affine_census as ac
 import affine_gpu_util as u
 import affine_grid_cases as gc
+import end_bonus_reference as er
 import gotoh_reference as gr
+import hits_reference as hr
+import subopt_reference as sr
 
 pytestmark = pytest.mark.gpu
 
@@ -84,6 +34,9 @@ TIES = (0, 1)
 # (mode, matrix, tie) of test_grid_shapes and test_grid_walks; every case runs all 16 classes of gc.RS
 GRID_PARAMS = [(mode, matrix, tie) for mode in MODES for matrix in MATRIX for tie in TIES]
 MIXED_PARAMS = [(mode, matrix) for mode in (1, 2) for matrix in MATRIX]
+OPTION_PARAMS = [(matrix, tie) for matrix in MATRIX for tie in TIES]                   # test_grid_subopt, test_grid_hits
+ENDB_PARAMS = [(R, matrix, tie) for R in gc.RS for matrix in MATRIX for tie in TIES]   # test_grid_end_bonus
+CENSUS_PARAMS = [(e.sweep, tie) for e in ac.census() for tie in TIES]                  # test_census
 
 
 @pytest.fixture
@@ -178,7 +131,149 @@ def test_mixed_launch_fit_global(ctx, mode, matrix):
     b.free()
 
 
-# 4 -- the JNI shim's entry points from plain C99 (tests/c/shim_long.c)
+# 4 -- the option grids.  subopt and hits run the shape grid in one launch of 96 pairs: every class of the SUBOPT and HITS sweeps,
+# with the alignments checked as test_grid_shapes checks them -- each of those sweeps is an instantiation of its own that writes
+# its own direction field and cell list.  The expected values are kept: the alignments per (matrix, tie order), the option's
+# values per matrix (the tie order changes no H).
+_KEPT = {}
+
+
+def _kept(key, make):
+    if key not in _KEPT:
+        _KEPT[key] = make()
+    return _KEPT[key]
+
+
+def _grid_expected(matrix, tie):
+    refs, reads = gc.shape_grid(matrix)
+    sc, mat = gc.SHAPE_SCORES[matrix], _matrix(matrix)
+    pairs = [(r, q) for r in range(len(refs)) for q in range(len(reads))]
+    exp = _kept(("align", matrix, tie), lambda: u.expect(refs, reads, sc, 0, tie=tie, matrix=mat))
+    sub = _kept(("subopt", matrix), lambda: {(r, q): sr.subopt_numpy(refs[r], reads[q], sc, gc.GRID_SUBOPT, 0, mat) for r, q in pairs})
+    return refs, reads, sc, exp, sub
+
+
+def _check_subopts(b, n_reads, sub):
+    s2, e2 = b.subopts()
+    assert len(s2) == len(e2) == len(sub)
+    for (r, q), want in sub.items():
+        pair = r * n_reads + q
+        got = (b.score(pair),) + b.subopt(pair)
+        assert got == want, (r, q, got, want)
+        assert (int(s2[pair]), int(e2[pair])) == want[1:], (r, q)
+
+
+def _check_hits(b, n_reads, hits):
+    cnt, sc, ei, ej = b.hits_all()
+    assert len(cnt) == len(hits)
+    for (r, q), want in hits.items():
+        pair = r * n_reads + q
+        assert b.hits(pair) == want, (r, q, b.hits(pair), want)
+        assert int(cnt[pair]) == len(want), (r, q)
+        assert [(int(sc[pair, x]), int(ei[pair, x]), int(ej[pair, x])) for x in range(len(want))] == want, (r, q)
+
+
+@pytest.mark.parametrize("matrix,tie", OPTION_PARAMS)
+def test_grid_subopt(ctx, matrix, tie):
+    refs, reads, sc, exp, sub = _grid_expected(matrix, tie)
+    b = u.run(ctx, refs, reads, sc, tie, 0, matrix=_matrix(matrix), subopt=gc.GRID_SUBOPT)
+    u.check(b, refs, reads, exp, 0)
+    _check_subopts(b, len(reads), sub)
+    b.free()
+
+
+@pytest.mark.parametrize("matrix,tie", OPTION_PARAMS)
+def test_grid_hits(ctx, matrix, tie):
+    refs, reads, sc, exp, sub = _grid_expected(matrix, tie)
+    mat = _matrix(matrix)
+    hits = _kept(("hits", matrix), lambda: {(r, q): hr.hits_numpy(refs[r], reads[q], sc, gc.GRID_SUBOPT, gc.GRID_HITS, 0, mat)
+                                            for r in range(len(refs)) for q in range(len(reads))})
+    b = u.run(ctx, refs, reads, sc, tie, 0, matrix=mat, subopt=gc.GRID_SUBOPT, hits=gc.GRID_HITS)
+    u.check(b, refs, reads, exp, 0)
+    _check_subopts(b, len(reads), sub)
+    _check_hits(b, len(reads), hits)
+    b.free()
+
+
+def _check_end_bonus(b, refs, reads, exp, what):
+    """every pair against end_bonus_reference.align: score, the three values through both accessors, the count with PAIR_TO_END,
+    every alignment with its cell"""
+    ends = b.end_scores()
+    assert all(len(a) == len(refs) * len(reads) for a in ends)
+    for r in range(len(refs)):
+        for q in range(len(reads)):
+            pair = r * len(reads) + q
+            score, alns, cells, took, want_ends = exp[(r, q)]
+            where = (what, r, q, len(refs[r]), len(reads[q]))
+            assert b.score(pair) == score, (where, b.score(pair), score)
+            assert b.end_score(pair) == want_ends, (where, b.end_score(pair), want_ends)
+            assert tuple(int(a[pair]) for a in ends) == want_ends, where
+            assert b.n_alignments(pair) == (len(alns), sw.PAIR_TO_END if took else 0), (where, b.n_alignments(pair), len(alns), took)
+            assert b.alignments(pair, with_cell=True) == [a + (c,) for a, c in zip(alns, cells)], where
+
+
+# the end_bonus grid: the three reads of class R against references that end before, between and behind their ends, under two
+# bonuses (the restatement sweeps a pair once for both)
+@pytest.mark.parametrize("R,matrix,tie", ENDB_PARAMS)
+def test_grid_end_bonus(ctx, R, matrix, tie):
+    refs, reads = gc.endb_grid(R, matrix)
+    assert [gc.rows_per_lane(len(q)) for q in reads] == [R] * 3
+    sc, mat = gc.SHAPE_SCORES[matrix], _matrix(matrix)
+    for bonus in gc.ENDB_BONUSES:
+        exp = {(r, q): er.align(refs[r], reads[q], sc, bonus, 0, tie, mat) for r in range(len(refs)) for q in range(len(reads))}
+        b = u.run(ctx, refs, reads, sc, tie, sw.ALIGN_GLOBAL, 0, 1, matrix=mat, end_bonus=bonus)
+        _check_end_bonus(b, refs, reads, exp, (R, matrix, tie, bonus))
+        b.free()
+
+
+# the banded matrix runs of subopt and hits: sw_affine_sweep_band_subopt_matrix_kernel and sw_affine_sweep_band_hits_matrix_kernel,
+# which no other test of the per-feature modules launches
+@pytest.mark.parametrize("tie", TIES)
+def test_band_subopt_hits_matrix(ctx, tie):
+    ref, read = gc.band_matrix_case()
+    sc, mat = gc.SHAPE_SCORES[True], gc.score_matrix()
+    w, width, k = gc.BAND_MATRIX_W, gc.BAND_MATRIX_SUBOPT, gc.BAND_MATRIX_HITS
+    exp = {(0, 0): gr.align_numpy(ref, read, sc, 0, w, False, tie, mat, cells=True)}
+    sub = _kept("band subopt", lambda: {(0, 0): sr.subopt_numpy(ref, read, sc, width, w, mat)})
+    hits = _kept("band hits", lambda: {(0, 0): hr.hits_numpy(ref, read, sc, width, k, w, mat)})
+    for n_hits in (0, k):
+        b = u.run(ctx, [ref], [read], sc, tie, 0, w, matrix=mat, long_reads=1, subopt=width, hits=n_hits)
+        u.check(b, [ref], [read], exp, 0)
+        _check_subopts(b, 1, sub)
+        if n_hits:
+            _check_hits(b, 1, hits)
+        assert [b.band_window(0, s) for s in range(2)] == gr.windows(len(read), len(ref), w)
+        b.free()
+
+
+# 5 -- the census: every kernel of AFF_SWEEPS is launched on two pairs that make its own rule matter, and with it the traceback it
+# implies -- all of AFF_TRACEBACKS.  tests/test_affine_grid_cpu.py checks that the census is the two lists and that the options and
+# read lengths of ac.inputs() select the kernel the case is named after
+@pytest.mark.parametrize("kernel,tie", CENSUS_PARAMS, ids=["%s-%d" % p for p in CENSUS_PARAMS])
+def test_census(ctx, kernel, tie):
+    entry = next(e for e in ac.census() if e.sweep == kernel)
+    inp = ac.inputs(entry)
+    exp = ac.expected(entry, tie)
+    b = u.run(ctx, inp.refs, inp.reads, inp.scores, tie, inp.mode, inp.band, inp.extend, inp.matrix, **inp.options)
+    assert b.pipeline_mode() == 3
+    for pair, ((ref, read), e) in enumerate(zip(ac.pairs(inp), exp)):
+        what = (kernel, tie, pair)
+        score, alns, cells = e["align"]
+        assert b.score(pair) == score, (what, b.score(pair), score)
+        assert b.n_alignments(pair) == (len(alns), sw.PAIR_TO_END if e.get("taken") else 0), (what, b.n_alignments(pair), len(alns))
+        assert b.alignments(pair, with_cell=True) == [a + (c,) for a, c in zip(alns, cells)], what
+        assert b.rows_swept(pair) == e["rows_swept"], (what, b.rows_swept(pair), e["rows_swept"])
+        assert [b.band_window(pair, s) for s in range(len(e["windows"]))] == [tuple(x) for x in e["windows"]], what
+        if "subopt" in e:
+            assert (b.score(pair),) + b.subopt(pair) == e["subopt"], (what, b.subopt(pair), e["subopt"])
+        if "hits" in e:
+            assert b.hits(pair) == e["hits"], (what, b.hits(pair), e["hits"])
+        if "ends" in e:
+            assert b.end_score(pair) == e["ends"], (what, b.end_score(pair), e["ends"])
+    b.free()
+
+
+# 6 -- the JNI shim's entry points from plain C99 (tests/c/shim_long.c)
 def _lcg(n, x):
     out = []
     for _ in range(n):

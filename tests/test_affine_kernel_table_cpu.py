@@ -23,17 +23,10 @@ import re
 
 import pytest
 
-from sparksmithwaterman_amd import _capi
+from affine_census import AffRun, load          # the ctypes struct and the three prototypes, shared with the census
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MODES = ("", "_fit", "_global", "_extend")
-
-
-class AffRun(C.Structure):
-    """AffRun of swmi_launch.h"""
-    _fields_ = [("gap_open", C.c_int32), ("gap_open2", C.c_int32), ("gap2", C.c_int32), ("mode", C.c_uint32), ("band", C.c_uint32),
-                ("xdrop", C.c_uint32), ("adapt", C.c_uint32), ("mat", C.c_void_p), ("nn", C.c_uint32), ("cigar", C.c_uint32),
-                ("subopt", C.c_int32), ("hits", C.c_uint32), ("end_bonus", C.c_uint32)]
 
 
 def _parent_sweep(r, long_reads, shape):
@@ -68,14 +61,7 @@ def _parent_traceback(r, long_reads):
 
 @pytest.fixture(scope="module")
 def lib():
-    lib = _capi.load()
-    lib.swmi_affine_run_ok.restype = C.c_int
-    lib.swmi_affine_run_ok.argtypes = [C.POINTER(AffRun), C.c_uint32]
-    lib.swmi_affine_sweep_name.restype = C.c_char_p
-    lib.swmi_affine_sweep_name.argtypes = [C.POINTER(AffRun), C.c_uint32, C.c_uint32]
-    lib.swmi_affine_traceback_name.restype = C.c_char_p
-    lib.swmi_affine_traceback_name.argtypes = [C.POINTER(AffRun), C.c_uint32]
-    return lib
+    return load()
 
 
 def _listed(macro):
