@@ -358,6 +358,17 @@ public class GpuSmithWaterman
 	public static final int SPEC_REVERSE = 1 ;
 
 	/**
+	 * swmi_pair_spec.flags: the pair is on the minus strand -- the READ segment is taken reverse-complemented ( IUPAC codes, case
+	 * kept, U to A ) on the GPU and the reference segment is untouched; the read is uploaded once for both strands.  Combines with
+	 * SPEC_REVERSE : the reference is reversed iff SPEC_REVERSE is set, the read is reversed iff exactly one of the two is set
+	 * and complemented iff this one is.  Coordinates stay the segments': column j is reference character refStart + j - 1, or
+	 * refStart + refLen - j under SPEC_REVERSE ; row i is read character readStart + i - 1 when the read's order is forward
+	 * ( flags 0 or SPEC_REVERSE | SPEC_READ_REVCOMP ) and readStart + readLen - i when it is reversed ( flags SPEC_REVERSE or
+	 * SPEC_READ_REVCOMP ).  readAligned holds the complemented characters.
+	 */
+	public static final int SPEC_READ_REVCOMP = 4 ;
+
+	/**
 	 * A PAIR LIST in one native call: what a read mapper has after chaining.  refs / reads are uploaded once; specs holds eight
 	 * ints per pair -- { ref , read , refStart , refLen , readStart , readLen , flags , 0 } : indices into refs / reads, the 0-based
 	 * start and the length of the two segments ( -1 as a length: to the end of the sequence ) and SPEC_REVERSE in flags for a

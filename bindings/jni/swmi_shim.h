@@ -28,8 +28,12 @@ int swmi_shim_align_batch(swmi_ctx *ctx, int32_t match, int32_t mismatch, int32_
 
 /* nativeAlignPairs: a PAIR LIST over the sequences (swmi_batch_upload_pairs + swmi_batch_run): `specs` = int[8 * n_pairs], eight
  * ints per pair in the order of swmi_pair_spec -- ref, read, refStart, refLen, readStart, readLen, flags (SWMI_SPEC_REVERSE: both
- * segments reversed, a left extension), 0 -- taken as unsigned, so that -1 as a length is SWMI_SPEC_WHOLE; n_spec_ints = the
- * array's length (a multiple of 8).  The other arguments are nativeAlignBatch's.  Pair k of the batch is spec k: its results are
+ * segments reversed, a left extension; SWMI_SPEC_READ_REVCOMP = 4: the pair is on the minus strand, the read segment taken
+ * reverse-complemented and the reference untouched; the two combine), 0 -- taken as unsigned, so that -1 as a length is
+ * SWMI_SPEC_WHOLE; n_spec_ints = the array's length (a multiple of 8).  The flags are passed through as given.  Coordinates are
+ * the segments': column j is reference byte refStart + j - 1, or refStart + refLen - j under REVERSE; row i is read byte
+ * readStart + i - 1 when the read's order is forward (flags 0 or 5) and readStart + readLen - i when it is reversed (flags 1 or
+ * 4).  The other arguments are nativeAlignBatch's.  Pair k of the batch is spec k: its results are
  * read with swmi_shim_pair_results and swmi_shim_pair_alignment (the swmi_shim_ref_* views need the cross product and fail with
  * SWMI_ERR_UNSUPPORTED). */
 int swmi_shim_align_pairs(swmi_ctx *ctx, int32_t match, int32_t mismatch, int32_t gap, int32_t tie_mode,

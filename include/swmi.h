@@ -375,18 +375,32 @@ int  swmi_batch_upload(swmi_ctx *ctx,
  * segments.  COORDINATES ARE THE SEGMENT'S: column j (1-based) of pair k is source byte  ref_start + j - 1  of the reference,
  * or  ref_start + ref_len - j  when the pair is reversed; row i maps to the read's bytes in the same way.  A pair with an empty
  * segment scores 0 with no alignments.
+ * THE MINUS STRAND: under SWMI_SPEC_READ_REVCOMP the READ segment is taken reverse-complemented and the
+ * reference segment is untouched; the caller uploads each read once, for both strands.  The flag combines with
+ * SWMI_SPEC_REVERSE.  With R = the REVERSE bit and C = the READ_REVCOMP bit:
+ *      reference segment:  byte order reversed iff R,         never complemented
+ *      read segment:       byte order reversed iff R xor C,   complemented iff C
+ * so REVERSE | READ_REVCOMP is the left extension on the minus strand: the reference reversed, the read complemented in its own
+ * order.  Column j is source byte  ref_start + j - 1,  or  ref_start + ref_len - j  under R; row i is read source byte
+ * read_start + i - 1  when the read's order is forward (R == C) and  read_start + read_len - i  when it is reversed (R != C).
+ * The complement is a 256-entry byte table: A<->T, C<->G, R<->Y, K<->M, B<->V, D<->H; S, W and N map to themselves; U maps to A;
+ * the same for the lower-case letters, which stay lower-case; every other byte maps to itself.  It is applied BEFORE the
+ * canonical codes: the fast path, a score matrix's rows (row = read base), option "cigar" 2's = / X and the read string of an
+ * alignment (with its case) all see the complemented base.  The contract above holds with "and reverse-complemented under
+ * SWMI_SPEC_READ_REVCOMP" added: pair k gives what a one-pair swmi_batch_upload batch gives for the two transformed segments.
  * Refused with SWMI_ERR_INVALID before anything is uploaded or launched, the message naming the pair: a source index out of
- * range, start + len past the end of the source, a flag bit other than SWMI_SPEC_REVERSE, reserved != 0, specs == NULL with
+ * range, start + len past the end of the source, a flag bit other than SWMI_SPEC_REVERSE and SWMI_SPEC_READ_REVCOMP (0x2 is undefined), reserved != 0, specs == NULL with
  * n_pairs > 0.  n_pairs >= 2^32 is SWMI_ERR_UNSUPPORTED; the segments' images together are subject to the 16 GiB image rule.
  * n_pairs = 0 is a valid, empty batch.  The MapRef views (swmi_ref_total(s), swmi_ref_n_match_sites, swmi_ref_match_site,
  * swmi_ref_sites_packed) have no meaning without the cross product and return SWMI_ERR_UNSUPPORTED on such a batch. */
 #define SWMI_SPEC_REVERSE 0x1u          /* both segments are taken in reverse byte order (left extension); no complement */
+#define SWMI_SPEC_READ_REVCOMP 0x4u     /* the pair is on the minus strand: the read segment reverse-complemented, the reference untouched */
 #define SWMI_SPEC_WHOLE   0xFFFFFFFFu   /* as ref_len / read_len: from the start given to the end of the source */
 typedef struct swmi_pair_spec {         /* 32 bytes */
     uint32_t ref, read;                 /* indices of the uploaded reference / read                      */
     uint32_t ref_start, ref_len;        /* 0-based first byte and length of the reference segment        */
     uint32_t read_start, read_len;
-    uint32_t flags;                     /* 0 or SWMI_SPEC_REVERSE                                        */
+    uint32_t flags;                     /* SWMI_SPEC_REVERSE | SWMI_SPEC_READ_REVCOMP, or 0               */
     uint32_t reserved;                  /* 0                                                             */
 } swmi_pair_spec;
 int  swmi_batch_upload_pairs(swmi_ctx *ctx,

@@ -25,6 +25,7 @@ HITS_MAX = 16        # option "hits": the most entries per pair (0: off; needs o
 PAIR_DEGENERATE = 0x1
 PAIR_TO_END = 0x2           # option "end_bonus": the pair was taken to the read's end (flags of swmi_pair_n_alignments)
 SPEC_REVERSE = 0x1          # swmi_pair_spec.flags: both segments in reverse byte order (left extension)
+SPEC_READ_REVCOMP = 0x4     # ... the pair is on the minus strand: the read segment reverse-complemented, the reference untouched
 SPEC_WHOLE = 0xFFFFFFFF     # as ref_len / read_len: from the start given to the end of the source
 ERR_INVALID = -1
 ERR_UNSUPPORTED = -5

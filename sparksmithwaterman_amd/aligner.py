@@ -27,23 +27,48 @@ def make_params(align_scores=None, align_types=None, tie_mode=_capi.TIE_SERIAL):
     return p
 
 
+def _complement_table():
+    """swmi_host.h's complement_table, restated: the IUPAC pairs, S / W / N their own complements, U -> A, lower case alike"""
+    t = bytearray(range(256))
+    for x, y in zip(b"ATCGRYKMBVDHU", b"TAGCYRMKVBHDA"):
+        t[x], t[x | 0x20] = y, y | 0x20
+    return bytes(t)
+
+
+COMPLEMENT = _complement_table()          # 256 bytes: the complement of every byte value (SWMI_SPEC_READ_REVCOMP)
+
+
+def revcomp(seq):
+    """the reverse complement of a sequence (bytes, or str of Latin-1 characters; the same type comes back), by COMPLEMENT"""
+    if isinstance(seq, str):
+        return seq.encode("latin-1").translate(COMPLEMENT)[::-1].decode("latin-1")
+    return bytes(seq).translate(COMPLEMENT)[::-1]
+
+
 def normalise_pairs(pairs):
-    """The pairs of a pair list as 7-tuples (ref, read, ref_start, ref_len, read_start, read_len, reverse).  An entry is
-    (ref, read) -- both sources whole --, (ref, read, ref_start, ref_len, read_start, read_len), or the latter plus `reverse`
-    (true: both segments in reverse byte order, a left extension).  A length of None or _capi.SPEC_WHOLE runs to the end of
-    the source.  ValueError for anything else: another number of fields, a field that is no integer, a negative value or one
-    past 32 bits.  Ranges against the sources are the library's to check (it knows them)."""
+    """The pairs of a pair list as 7-tuples (ref, read, ref_start, ref_len, read_start, read_len, reverse), a pair on the minus
+    strand as that plus an eighth field "-".  An entry is (ref, read) -- both sources whole --, (ref, read, ref_start, ref_len,
+    read_start, read_len), the latter plus `reverse` (true: both segments in reverse byte order, a left extension), or that
+    plus the strand, "+" or "-" ("-": the read segment is taken reverse-complemented, SWMI_SPEC_READ_REVCOMP; "+" is dropped).
+    A length of None or _capi.SPEC_WHOLE runs to the end of the source.  ValueError for anything else: another number of
+    fields, a field that is no integer, a negative value or one past 32 bits, another strand.  Ranges against the sources are
+    the library's to check (it knows them)."""
     out = []
     for k, t in enumerate(pairs):
         try:
             t = tuple(t)
         except TypeError:
             raise ValueError("pair %d: not a tuple: %r" % (k, t))
-        if len(t) not in (2, 6, 7):
-            raise ValueError("pair %d: %d fields; (ref, read), (ref, read, ref_start, ref_len, read_start, read_len) or the latter "
-                             "plus reverse" % (k, len(t)))
+        strand = ()
+        if len(t) == 8:
+            if not isinstance(t[7], str) or t[7] not in ("+", "-"):
+                raise ValueError("pair %d: %d fields, and the eighth is no strand (\"+\" or \"-\"): %r" % (k, len(t), t[7]))
+            strand = ("-",) if t[7] == "-" else ()
+        elif len(t) not in (2, 6, 7):
+            raise ValueError("pair %d: %d fields; (ref, read), (ref, read, ref_start, ref_len, read_start, read_len), the latter "
+                             "plus reverse, or that plus the strand" % (k, len(t)))
         rev = False
-        if len(t) == 7:
+        if len(t) >= 7:
             if not isinstance(t[6], (bool, int)) or t[6] not in (0, 1):
                 raise ValueError("pair %d: reverse must be a bool, got %r" % (k, t[6]))
             rev = bool(t[6])
@@ -57,34 +82,55 @@ def normalise_pairs(pairs):
             v = f[x] = int(v)
             if v < 0 or v > 0xFFFFFFFF:
                 raise ValueError("pair %d: field %d = %d is outside 0 .. 2^32 - 1" % (k, x, v))
-        out.append(tuple(f) + (rev,))
+        out.append(tuple(f) + (rev,) + strand)
     return out
 
 
+def _is_minus(spec):
+    """whether a normalised pair is the 8-tuple of a minus-strand pair"""
+    return len(spec) == 8 and spec[7] == "-"
+
+
 def cut_segments(refs, reads, spec):
-    """the two segments of a normalised pair as the library aligns them: cut from the sources and, reversed, byte-reversed"""
-    r, q, rs, rl, qs, ql, rev = spec
+    """the two segments of a normalised pair as the library aligns them: cut from the sources, reversed byte-reversed, and on
+    the minus strand the read reverse-complemented (so a reversed minus pair has its read complemented in its own order);
+    bytes segments, for sources given as bytes"""
+    r, q, rs, rl, qs, ql, rev = spec[:7]
     ref, read = refs[r], reads[q]
     a = ref[rs:] if rl == _capi.SPEC_WHOLE else ref[rs:rs + rl]
     b = read[qs:] if ql == _capi.SPEC_WHOLE else read[qs:qs + ql]
+    if _is_minus(spec):
+        b = revcomp(b)
     return (a[::-1], b[::-1]) if rev else (a, b)
 
 
 def cell_to_source(spec, seg_lens, i, j):
     """(read byte, reference byte), 0-based in the sources, of cell (i, j) (1-based row and column) of a normalised pair whose
-    segments have the lengths seg_lens = (reference, read): start + j - 1 forward, start + len - j reversed (swmi.h)"""
-    _, _, rs, _, qs, _, rev = spec
+    segments have the lengths seg_lens = (reference, read): start + j - 1 forward, start + len - j reversed (swmi.h); the
+    read of a minus-strand pair is reversed when the pair is not, and the other way round"""
+    rs, qs, rev = spec[2], spec[4], spec[6]
     n, m = seg_lens
-    if rev:
-        return qs + m - i, rs + n - j
-    return qs + i - 1, rs + j - 1
+    return (qs + m - i if rev != _is_minus(spec) else qs + i - 1), (rs + n - j if rev else rs + j - 1)
 
 
 def _spec_array(specs):
     arr = (PairSpec * max(len(specs), 1))()
-    for k, (r, q, rs, rl, qs, ql, rev) in enumerate(specs):
-        arr[k] = PairSpec(r, q, rs, rl, qs, ql, _capi.SPEC_REVERSE if rev else 0, 0)
+    for k, sp in enumerate(specs):
+        r, q, rs, rl, qs, ql, rev = sp[:7]
+        arr[k] = PairSpec(r, q, rs, rl, qs, ql, (_capi.SPEC_REVERSE if rev else 0) | (_capi.SPEC_READ_REVCOMP if _is_minus(sp) else 0), 0)
     return arr
+
+
+def both_strands(pairs):
+    """every pair of a list followed by its minus-strand twin: [p0, p0 on "-", p1, p1 on "-", ...], normalised.  The list to
+    upload when the strand of a read is not known; PairBatch.best_strand picks the twin.  ValueError for a pair that is on the
+    minus strand already."""
+    out = []
+    for k, sp in enumerate(normalise_pairs(pairs)):
+        if _is_minus(sp):
+            raise ValueError("pair %d is on the minus strand already: both_strands takes plus-strand pairs" % k)
+        out += [sp, sp + ("-",)]
+    return out
 
 
 class Context:
@@ -127,7 +173,7 @@ class Context:
 
     def upload_pairs(self, refs, reads, pairs):
         """Sources -> HBM once, and a pair list over them (swmi_batch_upload_pairs): pair k of the PairBatch is pairs[k], see
-        normalise_pairs for its forms.  The segments are cut, reversed and encoded on the GPU."""
+        normalise_pairs for its forms.  The segments are cut, reversed, on the minus strand complemented, and encoded on the GPU."""
         return PairBatch(self, refs, reads, pairs)
 
     def stream(self, reads, params=None, slots=0, chunk_bytes=0):
@@ -446,20 +492,40 @@ class PairBatch(Batch):
 
     def _hit_spec(self, pair, i, j):
         """... on a pair list with an unreversed spec: offset by the spec's starts.  ValueError for a reversed spec (its cells count
-        from the segments' ends: the prefixes that end in the cell are no prefixes of the sources' segments)"""
-        r, q, rs, _, qs, _, rev = self._specs[pair]
+        from the segments' ends: the prefixes that end in the cell are no prefixes of the sources' segments).  On the minus
+        strand rows 1 .. i are the LAST i bytes of the read segment: (r, q, rs, j, qs + ql - i, i, True, "-")."""
+        r, q, rs, _, qs, ql, rev = self._specs[pair][:7]
         if rev:
             raise ValueError("pair %d has a reversed spec: hit_specs needs unreversed segments" % pair)
+        if _is_minus(self._specs[pair]):
+            if ql == _capi.SPEC_WHOLE:
+                ql = len(self._reads[q]) - qs
+            return (r, q, rs, j, qs + ql - i, i, True, "-")
         return (r, q, rs, j, qs, i, _capi.SPEC_REVERSE)
 
     def spec(self, pair):
-        """(ref, read, ref_start, ref_len, read_start, read_len, reverse) of the pair as the library holds it: lengths resolved"""
+        """(ref, read, ref_start, ref_len, read_start, read_len, reverse) of the pair as the library holds it: lengths resolved;
+        a minus-strand pair as that plus "-" """
         sp = PairSpec()
         check(self._lib.swmi_batch_pair_spec(self._h, pair, C.byref(sp)))
-        return (sp.ref, sp.read, sp.ref_start, sp.ref_len, sp.read_start, sp.read_len, bool(sp.flags & _capi.SPEC_REVERSE))
+        strand = ("-",) if sp.flags & _capi.SPEC_READ_REVCOMP else ()
+        return (sp.ref, sp.read, sp.ref_start, sp.ref_len, sp.read_start, sp.read_len, bool(sp.flags & _capi.SPEC_REVERSE)) + strand
+
+    def strand(self, pair):
+        """"+" or "-": the strand the pair was given"""
+        return "-" if _is_minus(self._specs[pair]) else "+"
+
+    def best_strand(self):
+        """On a list built by both_strands, after a run: per input pair the index (in this batch) of the twin with the higher
+        score; a tie goes to the plus strand.  ValueError on any other list."""
+        sp = self._specs
+        if len(sp) % 2 or any(_is_minus(sp[k]) or sp[k + 1] != sp[k] + ("-",) for k in range(0, len(sp), 2)):
+            raise ValueError("best_strand needs a list built by both_strands: every pair followed by its minus twin")
+        sc = self.scores()
+        return [k + 1 if sc[k + 1] > sc[k] else k for k in range(0, len(sp), 2)]
 
     def segments(self, pair):
-        """(reference segment, read segment) of the pair as str, cut -- and reversed -- on the host"""
+        """(reference segment, read segment) of the pair as str, cut -- reversed, and on the minus strand complemented -- on the host"""
         a, b = cut_segments(self._refs, self._reads, self._specs[pair])
         return a.decode("latin-1"), b.decode("latin-1")
 

@@ -23,8 +23,6 @@ int swmi_host::fail(int code, const char *fmt, ...) {
 
 int swmi_io_fail(int code, const std::string &msg) { return fail(code, "%s", msg.c_str()); }
 
-static const uint8_t *code_table();
-
 // ------------------------------------------------------------------------------------------
 // library / context
 // ------------------------------------------------------------------------------------------
@@ -53,6 +51,7 @@ static void ctx_release(swmi_ctx *c) {
     if (c->stream) (void)hipStreamDestroy(c->stream);
     c->h_err.release();
     c->d_lut.release();
+    c->d_comp.release();
     c->d_hdr_ring.release();
     delete c;
 }
@@ -89,6 +88,9 @@ extern "C" int swmi_create(int device, swmi_ctx **out) {
     { int r = c->d_lut.reserve(256); if (r) { ctx_release(c); return r; } }
     e = hipMemcpy(c->d_lut.p, code_table(), 256, hipMemcpyHostToDevice);
     if (e != hipSuccess) { ctx_release(c); return fail(SWMI_ERR_HIP, "code table upload: %s", hipGetErrorString(e)); }
+    { int r = c->d_comp.reserve(256); if (r) { ctx_release(c); return r; } }
+    e = hipMemcpy(c->d_comp.p, complement_table(), 256, hipMemcpyHostToDevice);
+    if (e != hipSuccess) { ctx_release(c); return fail(SWMI_ERR_HIP, "complement table upload: %s", hipGetErrorString(e)); }
     *out = c;
     return SWMI_OK;
 }
@@ -266,7 +268,7 @@ extern "C" int swmi_set_score_matrix(swmi_ctx *ctx, const uint8_t *alphabet, uin
 // code(x) == code(y)  <=>  toUpperCase(x) == toUpperCase(y).  Sequences made of those symbols only (and scores within
 // int4) run the v_dot8_i32_i4 cell stream -- a reference with N stretches stays on the fast path; any other byte alphabet
 // runs the compare-and-select variant.
-static const uint8_t *code_table() {
+const uint8_t *swmi_host::code_table() {
     static uint8_t T[256];
     static std::once_flag once;              // MapRef.call runs on every executor thread (Distribution.java:32,403)
     std::call_once(once, [] {
@@ -409,7 +411,8 @@ static int check_specs(const uint64_t *ref_off, uint32_t n_refs, const uint64_t 
     for (uint64_t k = 0; k < n_pairs; k++) {
         swmi_pair_spec sp = specs[k];
         const unsigned long long kk = k;
-        if (sp.flags & ~SWMI_SPEC_REVERSE) return fail(SWMI_ERR_INVALID, "pair %llu: unknown flag bits 0x%x (only SWMI_SPEC_REVERSE is defined)", kk, sp.flags);
+        if (sp.flags & ~(SWMI_SPEC_REVERSE | SWMI_SPEC_READ_REVCOMP))
+            return fail(SWMI_ERR_INVALID, "pair %llu: unknown flag bits 0x%x (SWMI_SPEC_REVERSE and SWMI_SPEC_READ_REVCOMP are defined)", kk, sp.flags);
         if (sp.reserved) return fail(SWMI_ERR_INVALID, "pair %llu: reserved must be 0, got %u", kk, sp.reserved);
         if (sp.ref >= n_refs) return fail(SWMI_ERR_INVALID, "pair %llu: reference %u out of range (%u uploaded)", kk, sp.ref, n_refs);
         if (sp.read >= n_reads) return fail(SWMI_ERR_INVALID, "pair %llu: read %u out of range (%u uploaded)", kk, sp.read, n_reads);
@@ -428,9 +431,10 @@ static int check_specs(const uint64_t *ref_off, uint32_t n_refs, const uint64_t 
 }
 
 // Device side of a pair list.  d_raw: the reference sources, the read sources from a 16-byte boundary (as upload_device lays
-// them out), then from a 4-byte boundary the raw bytes of every REVERSED segment, each a whole number of dwords (written by the
-// kernel).  d_raw_off / d_src_off: n_pairs + 1 entries for the reference segments, then n_pairs + 1 for the read segments (the
-// emitters' indexing, TraceArgs.raw_reads_at = n_pairs + 1; the last entry of a side is not read).  The sources get no image.
+// them out), then from a 4-byte boundary the raw bytes of every TRANSFORMED segment -- reversed, complemented or both --, each a
+// whole number of dwords (written by the kernel).  A reference segment is reversed under SWMI_SPEC_REVERSE; a read segment is
+// reversed under REVERSE xor READ_REVCOMP and complemented under READ_REVCOMP.  d_raw_off / d_src_off:
+// n_pairs + 1 entries for the reference segments, then n_pairs + 1 for the read segments (the emitters' indexing, TraceArgs.raw_reads_at = n_pairs + 1; the last entry of a side is not read).  The sources get no image.
 // `specs` is checked (check_specs); the batch's host state changes only once nothing can be refused any more.
 static int pairs_to_device(swmi_ctx *ctx, swmi_batch *b, hipStream_t st, std::vector<swmi_pair_spec> &specs) {
     const uint32_t np = (uint32_t)specs.size();
@@ -449,13 +453,16 @@ static int pairs_to_device(swmi_ctx *ctx, swmi_batch *b, hipStream_t st, std::ve
     for (uint32_t k = 0; k < np; k++) {
         const swmi_pair_spec &sp = specs[k];
         const uint64_t rs = b->ref_off[sp.ref] + sp.ref_start, qs = read_base + b->read_off[sp.read] + sp.read_start;
-        if (sp.flags & SWMI_SPEC_REVERSE) {
-            src_off[k] = rs | (1ull << 63); src_off[side + k] = qs | (1ull << 63);
+        const bool R = (sp.flags & SWMI_SPEC_REVERSE) != 0, Cc = (sp.flags & SWMI_SPEC_READ_REVCOMP) != 0;
+        src_off[k] = raw_off[k] = rs;
+        src_off[side + k] = raw_off[side + k] = qs;
+        if (R) {
+            src_off[k] |= 1ull << 63;
             raw_off[k] = rev_at; rev_at += 4 * (((uint64_t)sp.ref_len + 3) / 4);
+        }
+        if (R || Cc) {
+            src_off[side + k] |= (uint64_t)(R != Cc) << 63 | (uint64_t)Cc << 62;
             raw_off[side + k] = rev_at; rev_at += 4 * (((uint64_t)sp.read_len + 3) / 4);
-        } else {
-            src_off[k] = raw_off[k] = rs;
-            src_off[side + k] = raw_off[side + k] = qs;
         }
     }
     int rc;
@@ -488,9 +495,10 @@ static int pairs_to_device(swmi_ctx *ctx, swmi_batch *b, hipStream_t st, std::ve
         HIP_TRY(hipMemcpyAsync(b->d_refs.p, b->ref_desc.data(), np * sizeof(SeqDesc), hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(b->d_reads.p, b->read_desc.data(), np * sizeof(SeqDesc), hipMemcpyHostToDevice, st));
     }
-    HIP_TRY(swmi_launch_gather(raw, d_src_off, d_raw_off, b->d_refs.as<SeqDesc>(), b->d_seqw.as<uint32_t>(), ctx->d_lut.as<uint8_t>(), np, st));
+    HIP_TRY(swmi_launch_gather(raw, d_src_off, d_raw_off, b->d_refs.as<SeqDesc>(), b->d_seqw.as<uint32_t>(), ctx->d_lut.as<uint8_t>(),
+                               ctx->d_comp.as<uint8_t>(), np, st));
     HIP_TRY(swmi_launch_gather(raw, d_src_off + side, d_raw_off + side, b->d_reads.as<SeqDesc>(), b->d_seqw.as<uint32_t>(),
-                               ctx->d_lut.as<uint8_t>(), np, st));
+                               ctx->d_lut.as<uint8_t>(), ctx->d_comp.as<uint8_t>(), np, st));
     HIP_TRY(hipStreamSynchronize(st));               // (the host vectors above are pageable locals)
     b->sources_on_device = true;
     return SWMI_OK;
@@ -516,7 +524,7 @@ extern "C" int swmi_batch_upload_pairs(swmi_ctx *ctx,
     b->n_src_refs = n_refs; b->n_src_reads = n_reads;
     b->ref_off.assign(ref_off, ref_off + n_refs + 1);
     b->read_off.assign(read_off, read_off + n_reads + 1);
-    // (kept: host-built strings are cut from them, and a list with a larger reversed area uploads them again)
+    // (kept: host-built strings are cut from them, and a list with a larger transformed area uploads them again)
     b->ref_bytes.assign(ref_bytes, ref_bytes + ref_off[n_refs]);
     b->read_bytes.assign(read_bytes, read_bytes + read_off[n_reads]);
     if ((rc = pairs_to_device(ctx, b.get(), ctx->stream, resolved))) { swmi_batch_free(ctx, b.release()); return rc; }

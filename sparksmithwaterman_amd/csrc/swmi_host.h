@@ -41,6 +41,26 @@ int settle_raw(swmi_batch *b);
 int dump_traceback_diagnostics(swmi_batch *b, const TraceArgs &ta, size_t np, size_t n_tf);
 int dump_fill_diagnostics(swmi_batch *b, const FillArgs &fa, size_t np);
 void watchdog_wait(hipStream_t st, const swmi_batch *b, const char *limit_s);
+const uint8_t *code_table();                   // byte -> canonical code (swmi_ctx.cpp); applied AFTER the complement
+
+// The complement of a base, as a 256-entry byte table (SWMI_SPEC_READ_REVCOMP): the IUPAC pairs A<->T, C<->G,
+// R<->Y, K<->M, B<->V, D<->H; S, W and N are their own complements; U -> A (and so not an involution on U); lower case likewise
+// and stays lower case; every other byte maps to itself.  Stated here once: sw_gather_kernel reads a device copy of it
+// (swmi_ctx.d_comp), materialise reads it for host-built strings.
+inline const uint8_t *complement_table() {
+    static const struct Table {
+        uint8_t t[256];
+        Table() {
+            for (int i = 0; i < 256; i++) t[i] = (uint8_t)i;
+            const char *from = "ATCGRYKMBVDHU", *to = "TAGCYRMKVBHDA";
+            for (int k = 0; from[k]; k++) {
+                t[(uint8_t)from[k]] = (uint8_t)to[k];
+                t[(uint8_t)(from[k] | 0x20)] = (uint8_t)(to[k] | 0x20);
+            }
+        }
+    } T;
+    return T.t;
+}
 }  // namespace swmi_host
 using namespace swmi_host;
 
@@ -184,6 +204,7 @@ struct swmi_ctx {
     DevBuf d_hdr_ring;                      // arena headers of launches that run sw_tfused_kernel / sw_resident_pairs_kernel ONLY: a fresh zeroed
     uint32_t hdr_next = 0;                  // slot per launch, so that no kernel has to run first just to reset the bump pointer
     DevBuf d_lut;                           // 256-byte canonical-code table of the encode kernel
+    DevBuf d_comp;                          // 256-byte complement table of sw_gather_kernel (complement_table)
     int64_t spin_us = 2000;                 // how long a run polls its stream for completion before it blocks (a batch is sub-millisecond)
     uint32_t dbg_strip_spins = 0;           // test knob: spin budget of the strip pipeline (0 = default)
     uint32_t dbg_reverse_strips = 0;        // test knob: strip items dispatched consumer-first
@@ -305,8 +326,8 @@ struct swmi_batch {
     bool paired = false;
     uint32_t n_src_refs = 0, n_src_reads = 0;
     std::vector<swmi_pair_spec> specs;
-    bool sources_on_device = false;         // d_raw holds the sources (it is grown, and filled again, when a list needs a larger reversed area)
-    DevBuf d_src_off;                       // per segment: where sw_gather_kernel reads it (bit 63: reversed), indexed as d_raw_off
+    bool sources_on_device = false;         // d_raw holds the sources (it is grown, and filled again, when a list needs a larger transformed area)
+    DevBuf d_src_off;                       // per segment: where sw_gather_kernel reads it (bit 63: reversed, bit 62: complemented), indexed as d_raw_off
     // original bytes (for string building: characters keep their case) and offsets
     std::vector<uint8_t> ref_bytes, read_bytes;
     // a streamed chunk keeps no copy of its references: their bytes are read again from the mapped file when an

@@ -115,6 +115,7 @@ struct HitsArgs {
 extern "C" hipError_t swmi_launch_hits(const HitsArgs *a, hipStream_t st);
 extern "C" hipError_t swmi_launch_encode(const uint8_t *raw, const uint64_t *raw_off, SeqDesc *desc, uint32_t *seqw,
                                          const uint8_t *lut, uint32_t n_seq, hipStream_t st);
-// pair lists: the segments' images (and the raw bytes of reversed segments) from the resident sources (sw_gather_kernel)
+// pair lists: the segments' images (and the raw bytes of reversed or complemented segments) from the resident sources
+// (sw_gather_kernel); `comp`: the 256-byte complement table (swmi_host.h: complement_table)
 extern "C" hipError_t swmi_launch_gather(uint8_t *raw, const uint64_t *src_off, const uint64_t *raw_off, SeqDesc *desc, uint32_t *seqw,
-                                         const uint8_t *lut, uint32_t n_seg, hipStream_t st);
+                                         const uint8_t *lut, const uint8_t *comp, uint32_t n_seg, hipStream_t st);

@@ -281,16 +281,23 @@ extern "C" int swmi_batch_pair_end_scores(const swmi_batch *b, int32_t *max_scor
 static void materialise(swmi_batch *b, uint64_t pair, HostAln &a, uint64_t slot) {
     const uint32_t r = pair_ref(b, pair), q = pair_read(b, pair);
     const uint8_t *ref, *read;
-    std::vector<uint8_t> rev_ref, rev_read;      // a reversed pair of a pair list: its two segments as the kernels saw them
+    std::vector<uint8_t> rev_ref, rev_read;      // a transformed segment of a pair list: as the kernels saw it
     if (b->paired) {
-        // a pair list: the segments are cut -- and reversed -- from the batch's copy of the source bytes
+        // a pair list: the segments are cut -- and reversed, the read of a minus-strand pair complemented -- from
+        // the batch's copy of the source bytes
         const swmi_pair_spec &sp = b->specs[pair];
         ref = b->ref_bytes.data() + b->ref_off[sp.ref] + sp.ref_start;
         read = b->read_bytes.data() + b->read_off[sp.read] + sp.read_start;
-        if (sp.flags & SWMI_SPEC_REVERSE) {
+        const bool R = (sp.flags & SWMI_SPEC_REVERSE) != 0, Cc = (sp.flags & SWMI_SPEC_READ_REVCOMP) != 0;
+        if (R) {
             rev_ref.assign(std::make_reverse_iterator(ref + sp.ref_len), std::make_reverse_iterator(ref));
-            rev_read.assign(std::make_reverse_iterator(read + sp.read_len), std::make_reverse_iterator(read));
-            ref = rev_ref.data(); read = rev_read.data();
+            ref = rev_ref.data();
+        }
+        if (R || Cc) {
+            if (R != Cc) rev_read.assign(std::make_reverse_iterator(read + sp.read_len), std::make_reverse_iterator(read));
+            else rev_read.assign(read, read + sp.read_len);
+            if (Cc) { const uint8_t *K = complement_table(); for (auto &x : rev_read) x = K[x]; }
+            read = rev_read.data();
         }
     } else if (b->src_map) {
         auto it = b->src_cache.find(r);
