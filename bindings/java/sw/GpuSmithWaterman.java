@@ -63,6 +63,8 @@ public class GpuSmithWaterman
 	static native void nativeSetEndBonus( long ctx , int endBonus ) ;
 	/** { max score , to-end score , the reference column it ends in , taken to the end ? 1 : 0 } of a pair after a run under that option */
 	static native int[] nativePairEndScore( long batch , long pair ) ;
+	/** overlap (ends-free) alignment with ALIGN_FIT: 1 on, 0 off (include/swmi.h: option "overlap") */
+	static native void nativeSetOverlap( long ctx , int overlap ) ;
 	/** the best local hits: the most entries per pair, 0 off (include/swmi.h: option "hits"; needs nativeSetSubopt) */
 	static native void nativeSetHits( long ctx , int hits ) ;
 	/** { score , read row , reference column } of every hit of a pair after a run under that option, best first */
@@ -224,6 +226,17 @@ public class GpuSmithWaterman
 	/** { max score , to-end score , its reference column , taken to the end ? 1 : 0 } of a pair of a native batch run under setEndBonus */
 	static int[] endScore( long batch , long pair ) { return nativePairEndScore( batch , pair ) ; }
 
+	/** whether every context runs ALIGN_FIT as overlap alignment (applied next to END_BONUS, before every batch) */
+	private static volatile boolean OVERLAP = false ;
+
+	/**
+	 * true: a run with ALIGN_FIT is an overlap (ends-free, dovetail) alignment -- the read's ends are free as well as the
+	 * reference's, the alignment ends in the read's last row or the reference's last column and its score may be <= 0.  Needs
+	 * ALIGN_FIT without band, extend, two-piece gaps, subopt, hits and endBonus.  For every batch aligned from now on, on every
+	 * executor thread.
+	 */
+	public static void setOverlap( boolean overlap ) { OVERLAP = overlap ; }
+
 	/** the most local hits per pair every context asks its runs for, 0: none (applied next to SUBOPT, before every batch) */
 	private static volatile int HITS = 0 ;
 
@@ -351,6 +364,7 @@ public class GpuSmithWaterman
 		nativeSetSubopt( ctx , SUBOPT ) ;
 		nativeSetHits( ctx , HITS ) ;
 		nativeSetEndBonus( ctx , END_BONUS ) ;
+		nativeSetOverlap( ctx , OVERLAP ? 1 : 0 ) ;
 		applyScoreMatrix( nc ) ;
 	}
 

@@ -130,6 +130,13 @@ JNIEXPORT void JNICALL Java_sw_GpuSmithWaterman_nativeSetEndBonus(JNIEnv *env, j
     if (swmi_shim_set_end_bonus((swmi_ctx *)(intptr_t)ctx, end_bonus, err, sizeof err) != SWMI_OK) throw_msg(env, err);
 }
 
+/* overlap alignment on this context from now on (with align mode fit): 1 on, 0 off */
+JNIEXPORT void JNICALL Java_sw_GpuSmithWaterman_nativeSetOverlap(JNIEnv *env, jclass cls, jlong ctx, jint overlap) {
+    char err[640];
+    (void)cls;
+    if (swmi_shim_set_overlap((swmi_ctx *)(intptr_t)ctx, overlap, err, sizeof err) != SWMI_OK) throw_msg(env, err);
+}
+
 /* { max_score, end_score, end_col, taken to the end ? 1 : 0 } of a pair after a run under option "end_bonus" */
 JNIEXPORT jintArray JNICALL Java_sw_GpuSmithWaterman_nativePairEndScore(JNIEnv *env, jclass cls, jlong batch, jlong pair) {
     char err[640];

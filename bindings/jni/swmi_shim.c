@@ -123,6 +123,14 @@ int swmi_shim_set_end_bonus(swmi_ctx *ctx, int32_t end_bonus, char *err, size_t 
     return SWMI_OK;
 }
 
+int swmi_shim_set_overlap(swmi_ctx *ctx, int32_t overlap, char *err, size_t err_len) {
+    int rc;
+    if (!ctx) return shim_fail(SWMI_ERR_INVALID, err, err_len, "nativeSetOverlap", "context handle is 0");
+    if ((rc = swmi_set_option(ctx, "overlap", overlap)) != SWMI_OK)
+        return shim_fail(rc, err, err_len, "nativeSetOverlap", swmi_last_error());
+    return SWMI_OK;
+}
+
 int swmi_shim_pair_end_score(const swmi_batch *b, int64_t pair, int32_t out[4], char *err, size_t err_len) {
     int32_t ms = 0, es = 0;
     uint32_t ec = 0, flags = 0;

@@ -104,6 +104,11 @@ int swmi_shim_pair_subopt(const swmi_batch *b, int64_t pair, int32_t out[2], cha
 int swmi_shim_set_end_bonus(swmi_ctx *ctx, int32_t end_bonus, char *err, size_t err_len);
 int swmi_shim_pair_end_score(const swmi_batch *b, int64_t pair, int32_t out[4], char *err, size_t err_len);
 
+/* nativeSetOverlap: 1 = overlap (ends-free) alignment from then on (swmi_set_option "overlap"): a fit run whose read ends are free as
+ * well -- the alignment ends in the read's last row or the reference's last column and starts in row 0 or column 0.  Any other run is
+ * then refused (SWMI_ERR_UNSUPPORTED).  0 (the default): off.  Any other value is SWMI_ERR_INVALID and leaves the context as it was. */
+int swmi_shim_set_overlap(swmi_ctx *ctx, int32_t overlap, char *err, size_t err_len);
+
 /* nativeSetHits: from then on a run under nativeSetSubopt also returns every pair's best local hits with their end cells
  * (swmi_set_option "hits"): 1 .. 16 = the most entries per pair, 0 (the default): off.  Any other value is SWMI_ERR_INVALID and leaves
  * the context as it was.

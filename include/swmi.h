@@ -338,6 +338,27 @@ void        swmi_default_params(swmi_params *p);
  *                anything is launched.  The bounds are extend's, unchanged: the comparison is made in 64 bits and no new sum is formed
  *                in int32.  A run (async runs and stream slots included) takes the value set when it was asked for (DESIGN.md
  *                section 8o).
+ * overlap (default 0; any value but 0 and 1 is SWMI_ERR_INVALID and leaves the context as it was): 1 turns a run with align_mode =
+ *                SWMI_ALIGN_FIT into OVERLAP (ends-free, dovetail) alignment: fit frees the reference's ends, the option frees the
+ *                read's as well (parasail's sg; read overlaps, paired-end merging, adapter trimming).  E, F, the x bits and the tie
+ *                chains are fit mode's, with no floor at 0.  Boundaries: H(0,j) = 0 for j = 0 .. n and H(i,0) = 0 for i = 1 .. m;
+ *                E(i,0) = F(0,j) = -inf.  The score is the maximum of H over the COMPETING cells (m, j), 1 <= j <= n, and (i, n),
+ *                1 <= i <= m -- the read's last row and the reference's last column; row 0 and column 0 do not compete, so the score
+ *                is that of the best non-empty overlap, may be <= 0 (no overlap worth having) and SWMI_PAIR_DEGENERATE is never
+ *                set.  Every competing cell that holds the score is a maximum cell, (m, n) once, in local and extend mode's order
+ *                restricted to those cells: row-major in serial tie mode; per anti-diagonal with ascending j in strict mode, then
+ *                the stable sort by begin.  cell_cap and the exact-size re-run apply as to fit's list.  The walk starts at a
+ *                maximum cell and ends at the first cell of row 0 or column 0, where nothing is appended: the alignment spells
+ *                read[i0+1 .. end_i] against ref[j0+1 .. end_j] with i0 = 0 or j0 = 0 -- no inserted read head, no deleted reference
+ *                head.  begin is fit's: the column of the first reference base consumed, end_j if the alignment consumes none.  The
+ *                read's first base used is end_i - (read bases consumed) + 1, which the strings or the CIGAR give.  A pair with an
+ *                empty side scores 0 with no alignments.  Scope: reads of every length (long_reads), with and without a score
+ *                matrix, both tie modes; scores_only, cigar, device_strings, zero_copy, cell_cap, max_workspace_bytes, pair lists
+ *                (SWMI_SPEC_REVERSE and SWMI_SPEC_READ_REVCOMP included: overlaps between reads of opposite strands), set_pairs and
+ *                streams apply as to a fit run.  The run takes the affine kernels whatever gap_open says (swmi_batch_mode 3).
+ *                overlap = 1 with another align_mode, or with band != 0, extend, xdrop, band_adapt, gap_open2, subopt, hits or
+ *                end_bonus, is SWMI_ERR_UNSUPPORTED before anything is launched.  The bounds are fit's, unchanged.  A run (async
+ *                runs and stream slots included) takes the value set when it was asked for.
  * Further knobs: spin_us (how long a run polls its stream before it blocks, default 2000); col_chunks (0 automatic,
  * 1 never, N > 1 force up to N column chunks per pair: a launch of few pairs with long references is swept by several
  * wavefronts per pair -- a read of more than 256 rows by several strip pipelines); debug_strip_spins / debug_reverse_strips (tests of the strip pipeline's give-up path);

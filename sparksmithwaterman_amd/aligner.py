@@ -299,6 +299,21 @@ class Batch:
         n, _ = self.n_alignments(pair)
         return [self.cigar(pair, k) for k in range(n)]
 
+    def span(self, pair, k):
+        """(read_first, end_i, begin, end_j) of the k-th alignment, 1-based and inclusive: it spells read[read_first .. end_i] against
+        ref[begin .. end_j].  read_first = end_i - (read bases the alignment consumes) + 1, counted from the CIGAR after a run under
+        option "cigar" and else from the read's aligned string.  What the caller of an overlap run (option "overlap") needs to tell
+        a dovetail from a containment: the results themselves carry begin, end_i and end_j only."""
+        try:
+            begin, ei, ej, ent, _ = self.cigar(pair, k)
+            used = sum(ln for ln, op in ent if op != "D")
+        except SwmiError as e:
+            if e.code != _capi.ERR_UNSUPPORTED:
+                raise
+            begin, (_, read_al), (ei, ej) = self.alignment(pair, k, with_cell=True)
+            used = len(read_al) - read_al.count("_")              # (the gap character of the aligned strings)
+        return ei - used + 1, ei, begin, ej
+
     def pair_results(self):
         """(scores int32[n_pairs], n_alignments uint64[n_pairs]) as numpy arrays, one native call."""
         import numpy as np

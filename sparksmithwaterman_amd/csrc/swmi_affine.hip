@@ -88,9 +88,16 @@
 //   that owns read row m keeps the maximum of H(m, j) and its smallest column, and the wave chooses between the best cell anywhere
 //   and the best extension that reaches the read's end where it writes the pair's PairOut.
 //
-// How the 85 kernels are made: two lists, AFF_SWEEPS (72 rows) and AFF_TRACEBACKS (13), name every kernel with its
+// sw_affine_sweep_[long_]overlap[_matrix][_wide]_kernel, sw_affine_traceback_[long_]overlap_kernel: overlap (ends-free) alignment (option
+//   "overlap" on a fit run), MODE = 4: fit mode's cells with column 0 at 0 as well as row 0, the maximum taken over read row
+//   m and the last column from INT32_MIN + 1 up (the score may be <= 0; there is no degenerate case), and a walk that ends at the first
+//   cell of row 0 or column 0 without a tail.
+//
+// How the 93 kernels are made: two lists, AFF_SWEEPS (72 rows) and AFF_TRACEBACKS (13), name every kernel with its
 //   MODE and its flags; the kernel definitions, their parameter lists and the launchers' tables are the lists under a macro each,
-//   and the file defines no kernel outside them.  A sweep is aff_sweep_entry<RLO, RHI, MODE, F> over one block function
+//   and the file defines no kernel outside them and the second pair of lists, AFF_OVERLAP_SWEEPS (6) and AFF_OVERLAP_TRACEBACKS (2),
+//   which goes through the same macros (the first pair's row counts are pinned by the tests of the modes they hold).
+//   A sweep is aff_sweep_entry<RLO, RHI, MODE, F> over one block function
 //   (aff_block8), a traceback aff_traceback<MODE, F>, F being the row's flags as one word (AFF_F_ of swmi_launch.h; !LONG is the
 //   walk with one strip and !BAND the walk whose windows are the whole reference).  Which combinations may exist is aff_flags_ok
 //   there, asserted for every row; the launchers take the run's options as one AffRun and search their table for the run's key.
@@ -118,9 +125,14 @@
 // option "extend" (with align_mode global): global mode's cells, local mode's maximum over every cell.  Internal to this file
 // and the launchers' tables: the host passes it in place of the align_mode
 #define AFF_EXTEND 3
+// option "overlap" (with align_mode fit): fit mode's cells without a fixed end -- row 0 AND column 0 are 0, the maximum
+// is taken over read row m and the last column, the walk ends at row 0 or column 0.  Internal like AFF_EXTEND
+#define AFF_OVERLAP 4
 // the modes that sweep global mode's cells (row 0 is o + j*e), and the ones whose maximum is taken over row m alone
 #define AFF_ROW0_GAPS(MODE) ((MODE) == AFF_GLOBAL || (MODE) == AFF_EXTEND)
 #define AFF_ROW_M_ONLY(MODE) ((MODE) == AFF_FIT || (MODE) == AFF_GLOBAL)
+// the modes whose column 0 is o + i*e (local and overlap: 0)
+#define AFF_COL0_GAPS(MODE) ((MODE) == AFF_FIT || (MODE) == AFF_GLOBAL || (MODE) == AFF_EXTEND)
 // The device templates take MODE and one flags word F (the AFF_F_ bits of swmi_launch.h); each opens with the bits under the
 // names its body uses
 #define AFF_FLAG_NAMES(F)                                                                                                           \
@@ -180,6 +192,15 @@ struct AffState {
 //   compete.  A lane without a cell in this step idles at mrow = INT32_MIN: it passes `mrow >= thr` only while thr is still
 //   INT32_MIN, which is before step 0 alone (lane 0's cell (1, 1) -- of the first window under BAND -- raises it there), and it
 //   lists nothing even then: a listed cell is inr, inside the read and holds a real H
+// AFF_OVERLAP: fit mode's cell and row 0; a cell COMPETES iff it lies on read row m or in the last column.  vrows is
+//   local mode's.  Inside the row loop a lane takes, under the one test k < vrows, the maximum of its rows inside the read and H of the
+//   last of them (ENDB's hend: no array indexed by a run-time value, no further mask per row); behind the loop mrow is that maximum in
+//   the last column, H(m, j) in lane Z.elane, which owns read row m, and INT32_MIN everywhere else.  (Taking the last column's maximum
+//   from S.h behind the loop instead, once per lane, was tried: the wide sweep then spills 900 SGPRs and the strip sweep needs 234
+//   VGPRs.)  The threshold starts at INT32_MIN + 1, ONE ABOVE what an idle lane holds: a lane without a competing cell never reaches
+//   it, however late the first competing cell comes (row m, or column n of strip 0), and that cell -- a real H -- is strictly
+//   greater.  The list loop repeats the membership test: a row of the lane that happens to hold the maximum's value but does not
+//   compete is not listed
 // LONG: one strip of a long read -- lane 0 is fed from Z (every strip, the first one too: its Z holds row 0 of the mode) and lane
 // Z.wlane leaves (H, F) of its last row in the seam row
 // BAND (with LONG): the strip sweeps a window of the reference -- n is the window's length, columns count from its first one
@@ -237,12 +258,12 @@ __device__ __forceinline__ void aff_block8(AffState<R> &S, const uint2 rw, const
             if constexpr (TWO) nf2 = wave_shr1((int)((uint32_t)h0 + (uint32_t)o2), S.f2_last);
         }
         const bool inr = c0 < n;
-        int mrow = MODE == AFF_LOCAL ? -1 : (MODE == AFF_EXTEND ? INT32_MIN : 0);
+        int mrow = MODE == AFF_LOCAL ? -1 : (MODE == AFF_EXTEND || MODE == AFF_OVERLAP ? INT32_MIN : 0);
         int mrr = 0;                                             // (HITS) the smallest row of the lane that holds mrow
         if (inr) {
             int diag = S.nh_prev, up = nh, fup = nf;
             int fup2 = nf2;                                      // (TWO)
-            int hend = INT32_MIN;                                // (ENDB) H of the lane's last row inside the read
+            int hend = INT32_MIN;                                // (ENDB, AFF_OVERLAP) H of the lane's last row inside the read
             uint32_t sh = 4u * s;
             const uint32_t rkey = (uint32_t)S.rb, rlo = rkey & 0xFFFFu;
 #pragma unroll
@@ -303,12 +324,17 @@ __device__ __forceinline__ void aff_block8(AffState<R> &S, const uint2 rw, const
                 S.h[k] = hv;
                 S.e[k] = en;
                 if constexpr (HITS) { if ((uint32_t)k < vrows && hv > mrow) mrr = (int)(row0 + (uint32_t)k + 1u); }
-                if constexpr (!AFF_ROW_M_ONLY(MODE)) { if ((uint32_t)k < vrows) mrow = max(mrow, hv); }
-                else                                 { if ((uint32_t)k == vrows) mrow = hv; }
+                if constexpr (MODE == AFF_OVERLAP)        { if ((uint32_t)k < vrows) { mrow = max(mrow, hv); hend = hv; } }
+                else if constexpr (!AFF_ROW_M_ONLY(MODE)) { if ((uint32_t)k < vrows) mrow = max(mrow, hv); }
+                else                                      { if ((uint32_t)k == vrows) mrow = hv; }
                 if constexpr (ENDB) { if ((uint32_t)k < vrows) hend = hv; }      // (the test of mrow: the last slot that passes it is vrows - 1)
             }
             if constexpr (ENDB) {
                 if (lane == Z.elane && hend > S.eg) { S.eg = hend; S.egc = c0 + 1u + (BAND ? Z.coff : 0u); }
+            }
+            if constexpr (MODE == AFF_OVERLAP) {
+                // left of the last column only read row m competes: one cell, in the lane that owns the row
+                if (c0 + 1u != n) mrow = lane == Z.elane ? hend : INT32_MIN;
             }
             S.f_last = fup;
             if constexpr (TWO) S.f2_last = fup2;
@@ -351,9 +377,15 @@ __device__ __forceinline__ void aff_block8(AffState<R> &S, const uint2 rw, const
                 }
                 S.cnt = 0;
             }
+            // (AFF_OVERLAP) the lane's competing slots are clo .. vrows - 1: every row inside the read in the last column, row m alone in
+            // the lane that owns it, none elsewhere -- one unsigned compare per row, where the other modes have k < vrows
+            [[maybe_unused]] const uint32_t clo = MODE != AFF_OVERLAP || c0 + 1u == n ? 0u : (lane == Z.elane ? vrows - 1u : vrows);
+            [[maybe_unused]] const uint32_t cspan = vrows - clo;
 #pragma unroll
             for (int k = 0; k < R; ++k) {
-                const bool hit = inr && (uint32_t)k < vrows && S.h[k] == S.thr;
+                bool hit;
+                if constexpr (MODE == AFF_OVERLAP) hit = inr && (uint32_t)k - clo < cspan && S.h[k] == S.thr;
+                else                               hit = inr && (uint32_t)k < vrows && S.h[k] == S.thr;
                 const uint64_t hm = BALLOT(hit);
                 if (hm) {
                     const uint32_t pos = S.cnt + lanemask_lt_count(hm);
@@ -389,6 +421,7 @@ __device__ __forceinline__ AffCells aff_cell_list(const FillArgs &A, const PairD
 // AFF_LOAD_ROWS (readw, m, row0, nn): the lane's rows row0 + 1 .. row0 + R (global row indices) -- their base codes, with MATRIX
 //   their row words class * (n+1) * 4 | hi << 16 (a read base inside the alphabet takes hi = 0x3FF, never a reference key's;
 //   pad rows: class n, hi 0xFFFF) -- and H and E at column 0: 0 (local), else H(i,0) = o + i*e, E(i,0) := H(i,0) + o
+//   AFF_OVERLAP: H(i,0) = 0 and the same stand-in, E(i,0) := o
 //   TWO: H(i,0) = max(o + i*e, o2 + i*e2), E1(i,0) := H(i,0) + o, E2(i,0) := H(i,0) + o2
 #define AFF_LOAD_ROWS                                                                                         \
     _Pragma("unroll") for (int k = 0; k < R; ++k) {                                                           \
@@ -402,6 +435,9 @@ __device__ __forceinline__ AffCells aff_cell_list(const FillArgs &A, const PairD
         if constexpr (MODE == AFF_LOCAL) {                                                                    \
             S.h[k] = 0;                                                                                       \
             S.e[k] = 0;                                                                                       \
+        } else if constexpr (MODE == AFF_OVERLAP) {                                                           \
+            S.h[k] = 0;                                                                                       \
+            S.e[k] = o;                                                                                       \
         } else {                                                                                              \
             S.h[k] = o + (int)(row + 1u) * A.gap;                                                             \
             if constexpr (TWO) S.h[k] = max(S.h[k], o2 + (int)(row + 1u) * e2);                               \
@@ -488,8 +524,9 @@ __device__ __forceinline__ void aff_sweep_pair(const FillArgs &A, const int o, c
     AFF_LOAD_ROWS
     S.rb = 0; S.nh_prev = 0; S.f_last = 0;                       // (nh_prev of lane 0: H(0,0) = 0 in every mode)
     if constexpr (TWO) S.f2_last = 0;
-    S.thr = MODE == AFF_LOCAL ? 1 : INT32_MIN; S.cnt = 0;
-    AffSeam Zs{};                                                // (SUBOPT, ENDB; nothing else reads it in a short sweep)
+    S.thr = MODE == AFF_LOCAL ? 1 : MODE == AFF_OVERLAP ? INT32_MIN + 1 : INT32_MIN; S.cnt = 0;
+    AffSeam Zs{};                                                // (SUBOPT, ENDB, AFF_OVERLAP; nothing else reads it in a short sweep)
+    if constexpr (MODE == AFF_OVERLAP) Zs.elane = uni((m - 1u) / (uint32_t)R);      // the lane that owns read row m
     if constexpr (SUBOPT) {
         S.cm = 0;
         Zs.cmrow = reinterpret_cast<int *>(dir + (uint64_t)W * R * WAVE);
@@ -612,8 +649,8 @@ __device__ __forceinline__ void aff_sweep_long_pair(const FillArgs &A, const int
     uint32_t *const wtab = ADAPT ? A.dir + pd.dir_off + (uint64_t)NS * astride : nullptr;   // ADAPT: the pair's window table
 
     AffState<R> S;
-    S.thr = MODE == AFF_LOCAL ? 1 : INT32_MIN; S.cnt = 0;       // (wave-uniform: they live on across the strips)
-    const uint32_t elast = ENDB ? uni((m - 1u - (NS - 1u) * SWMI_AFF_MAX_READ) / (uint32_t)R) : 0u;      // ENDB: the lane of the last strip that owns read row m
+    S.thr = MODE == AFF_LOCAL ? 1 : MODE == AFF_OVERLAP ? INT32_MIN + 1 : INT32_MIN; S.cnt = 0;       // (wave-uniform: they live on across the strips)
+    const uint32_t elast = ENDB || MODE == AFF_OVERLAP ? uni((m - 1u - (NS - 1u) * SWMI_AFF_MAX_READ) / (uint32_t)R) : 0u;      // ENDB: the lane of the last strip that owns read row m
     if constexpr (ENDB) { S.eg = INT32_MIN; S.egc = 0u; }
     for (uint32_t sx = 0; sx < NS; ++sx) {
         const uint32_t row0 = sx * SWMI_AFF_MAX_READ + lane * R;             // global index of the lane's first row, less 1
@@ -676,7 +713,7 @@ __device__ __forceinline__ void aff_sweep_long_pair(const FillArgs &A, const int
         if constexpr (SUBOPT) S.cm = 0;
         if constexpr (HITS) S.cmr = 0;
         // nh_prev of lane 0: H(1024 * sx, clo - 1)
-        if constexpr (!BAND) S.nh_prev = MODE != AFF_LOCAL && sx ? o + (int)(sx * SWMI_AFF_MAX_READ) * A.gap : 0;
+        if constexpr (!BAND) S.nh_prev = AFF_COL0_GAPS(MODE) && sx ? o + (int)(sx * SWMI_AFF_MAX_READ) * A.gap : 0;
         if constexpr (!BAND && TWO) { if (sx) S.nh_prev = max(S.nh_prev, o2 + (int)(sx * SWMI_AFF_MAX_READ) * e2); }
         if constexpr (BAND) {
             Z.row = seam + (clo - 1u);
@@ -685,7 +722,7 @@ __device__ __forceinline__ void aff_sweep_long_pair(const FillArgs &A, const int
             if constexpr (SUBOPT) Z.cmrow = cmbase + (clo - 1u);
         }
         Z.wlane = sx + 1u < NS ? 63u : 0xFFFFFFFFu;
-        if constexpr (ENDB) Z.elane = sx + 1u < NS ? 0xFFFFFFFFu : elast;
+        if constexpr (ENDB || MODE == AFF_OVERLAP) Z.elane = sx + 1u < NS ? 0xFFFFFFFFu : elast;
         if constexpr (!BAND) dir = A.dir + pd.dir_off + (uint64_t)sx * (TWO ? 2u : 1u) * swmi_aff_strip_words(n);
         if constexpr (ADAPT) dir = A.dir + pd.dir_off + (uint64_t)sx * astride;
         // the strip above has written its window of the seam row: its stores are in memory before this strip loads any of it
@@ -915,6 +952,15 @@ static_assert(SWMI_AFF_RMAX == 16, "the RHI column of the list");
             AFF_SEL_##BAND(band, 0u), AFF_SEL_##XDROP(xdrop, 0u), AFF_SEL_##ENDB(end_bonus, 0u));                                            \
     }
 AFF_SWEEPS(AFF_SWEEP_KERNEL)
+// THE LIST OF OVERLAP SWEEPS (option "overlap", MODE 4): a list of its own behind the first, under the same two macros
+#define AFF_OVERLAP_SWEEPS(X)                                                                             \
+    X(sw_affine_sweep_overlap_kernel,                  1,  4, AFF_OVERLAP, 0, 0, 0, 0, 0, 0, 0, 0, 0) \
+    X(sw_affine_sweep_overlap_wide_kernel,             5, 16, AFF_OVERLAP, 0, 0, 0, 0, 0, 0, 0, 0, 0) \
+    X(sw_affine_sweep_overlap_matrix_kernel,           1,  4, AFF_OVERLAP, 1, 0, 0, 0, 0, 0, 0, 0, 0) \
+    X(sw_affine_sweep_overlap_matrix_wide_kernel,      5, 16, AFF_OVERLAP, 1, 0, 0, 0, 0, 0, 0, 0, 0) \
+    X(sw_affine_sweep_long_overlap_kernel,            16, 16, AFF_OVERLAP, 0, 1, 0, 0, 0, 0, 0, 0, 0) \
+    X(sw_affine_sweep_long_overlap_matrix_kernel,     16, 16, AFF_OVERLAP, 1, 1, 0, 0, 0, 0, 0, 0, 0)
+AFF_OVERLAP_SWEEPS(AFF_SWEEP_KERNEL)
 #undef AFF_SWEEP_KERNEL
 
 // ------------------------------------------------------------------------------------------------
@@ -945,9 +991,9 @@ AFF_SWEEPS(AFF_SWEEP_KERNEL)
 #define AFF_DEL2 5u
 namespace {
 // The walks that may exist: modes 0 .. 2 (an extend run is walked by global mode's kernels, so the walk of option "band_adapt" is
-// held against the extend sweeps' rule) and the four flags that shape a field
+// held against the extend sweeps' rule) and 4 (overlap), and the four flags that shape a field
 constexpr bool aff_traceback_ok(uint32_t mode, uint32_t f) {
-    return mode <= AFF_GLOBAL && !(f & ~(AFF_F_LONG | AFF_F_BAND | AFF_F_ADAPT | AFF_F_TWO)) &&
+    return (mode <= AFF_GLOBAL || mode == AFF_OVERLAP) && !(f & ~(AFF_F_LONG | AFF_F_BAND | AFF_F_ADAPT | AFF_F_TWO)) &&
            aff_flags_ok((f & AFF_F_ADAPT) && mode == AFF_GLOBAL ? AFF_EXTEND : mode, f);
 }
 template <int MODE, uint32_t F>
@@ -1013,8 +1059,9 @@ __device__ __forceinline__ void aff_traceback(const TraceArgs A, const uint32_t 
         uint32_t n_ops = 0, cur = 0;
         int begin = MODE == AFF_LOCAL ? 0 : (int)cj;
         bool ok = true;
-        while (MODE == AFF_LOCAL ? (i != 0u && j != 0u) : (i != 0u)) {
-            if (MODE != AFF_LOCAL && j == 0u) {                   // the read's head hangs over the reference start: inserted,
+        // (AFF_OVERLAP: the walk ends at the first cell of row 0 or column 0 -- local's condition -- with fit's codes and `begin`)
+        while (MODE == AFF_LOCAL || MODE == AFF_OVERLAP ? (i != 0u && j != 0u) : (i != 0u)) {
+            if (MODE != AFF_LOCAL && MODE != AFF_OVERLAP && j == 0u) {      // the read's head hangs over the reference start: inserted,
                 if (n_ops >= max_ops) { ok = false; break; }      // and the field is not touched
                 --i;
                 cur |= SWMI_DIR_I << (2u * (n_ops & 15u));
@@ -1156,6 +1203,11 @@ __device__ __forceinline__ void aff_traceback(const TraceArgs A, const uint32_t 
         aff_traceback<MODE, AFF_TB_FLAGS(LONG, BAND, ADAPT, TWO)>(A, tile_words, ops_words, cigar, AFF_SEL_##BAND(band, 0u));       \
     }
 AFF_TRACEBACKS(AFF_TRACEBACK_KERNEL)
+// THE LIST OF OVERLAP TRACEBACKS (option "overlap", MODE 4), behind the first as the sweeps' is
+#define AFF_OVERLAP_TRACEBACKS(X)                                              \
+    X(sw_affine_traceback_overlap_kernel,           AFF_OVERLAP, 0, 0, 0, 0) \
+    X(sw_affine_traceback_long_overlap_kernel,      AFF_OVERLAP, 1, 0, 0, 0)
+AFF_OVERLAP_TRACEBACKS(AFF_TRACEBACK_KERNEL)
 #undef AFF_TRACEBACK_KERNEL
 
 // ------------------------------------------------------------------------------------------------
@@ -1167,6 +1219,7 @@ AFF_TRACEBACKS(AFF_TRACEBACK_KERNEL)
 // kernel's flags ask for, so every launch is checked against its kernel's parameter list, whatever the signature.  A run's key is
 // searched for; no row, no kernel: hipErrorInvalidValue.
 static_assert(AFF_EXTEND == 3, "AffRun.mode 3 is the extend run");
+static_assert(AFF_OVERLAP == 4, "AffRun.mode 4 is the overlap run");
 namespace {
 struct AffSweepRow {
     uint32_t key;
@@ -1179,7 +1232,7 @@ struct AffSweepRow {
          hipLaunchKernelGGL(name, grid, dim3(WAVE * AFF_WAVES), 0, st, a, (int)r.gap_open AFF_IF_##TWO(, (int)r.gap_open2, (int)r.gap2) \
                             AFF_IF_##MATRIX(, r.mat, r.nn) AFF_IF_##BAND(, r.band) AFF_IF_##XDROP(, r.xdrop) AFF_IF_##ENDB(, r.end_bonus)); \
      }, #name},
-const AffSweepRow aff_sweeps[] = {AFF_SWEEPS(AFF_SWEEP_ROW)};
+const AffSweepRow aff_sweeps[] = {AFF_SWEEPS(AFF_SWEEP_ROW) AFF_OVERLAP_SWEEPS(AFF_SWEEP_ROW)};
 #undef AFF_SWEEP_ROW
 
 struct AffTracebackRow {
@@ -1195,7 +1248,7 @@ struct AffTracebackRow {
          hipLaunchKernelGGL(name, dim3(a.n_pairs, SWMI_AFF_TB_SLOTS), dim3(WAVE), lds, st, a, tile_words, ops_words, r.cigar         \
                             AFF_IF_##BAND(, r.band));                                                                                \
      }, #name, reinterpret_cast<const void *>(name)},
-const AffTracebackRow aff_tracebacks[] = {AFF_TRACEBACKS(AFF_TRACEBACK_ROW)};
+const AffTracebackRow aff_tracebacks[] = {AFF_TRACEBACKS(AFF_TRACEBACK_ROW) AFF_OVERLAP_TRACEBACKS(AFF_TRACEBACK_ROW)};
 #undef AFF_TRACEBACK_ROW
 
 // The rows of a run's kernels, null where the launchers refuse.  shape: 0 narrow, 1 wide, 2 long.

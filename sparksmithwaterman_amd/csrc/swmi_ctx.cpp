@@ -211,6 +211,9 @@ extern "C" int swmi_set_option(swmi_ctx *ctx, const char *name, int64_t value) {
         if (value < 0 || value > (1ll << 30))
             return fail(SWMI_ERR_INVALID, "end_bonus must be 0 (off) or a bonus of 1 .. 2^30, got %lld", (long long)value);
         ctx->modes.end_bonus = (int)value;
+    } else if (!strcmp(name, "overlap")) {
+        if (value != 0 && value != 1) return fail(SWMI_ERR_INVALID, "overlap must be 0 or 1, got %lld", (long long)value);
+        ctx->modes.overlap = (int)value;
     } else if (!strcmp(name, "arena_words_per_pair")) {
         if (value < 1) return fail(SWMI_ERR_INVALID, "arena_words_per_pair out of range");
         ctx->arena_words_per_pair = (uint64_t)value;

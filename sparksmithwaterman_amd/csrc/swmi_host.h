@@ -146,9 +146,13 @@ struct __attribute__((visibility("hidden"))) RunModes {
     int subopt = 0;                         // != 0: a local run also returns every pair's second-best score -- the mask half-width, -1 automatic (swmi.h); refused in the other modes
     int hits = 0;                           // 1 .. 16 = K: a run under subopt also returns every pair's K best separated end cells (swmi.h); refused without subopt
     int end_bonus = 0;                      // > 0: an extend run also returns every pair's best score in read row m and takes the pair to the read's end when that is less than this bonus below the best score (swmi.h); refused in other runs
+    int overlap = 0;                        // 1: overlap (ends-free) alignment -- a fit run whose read ends are free as well (swmi.h); refused in other runs
     bool two_piece() const { return gap_open2 != 0; }
-    // the MODE of the affine kernels and their launchers: the align_mode, or 3 (extend) for a global run with option "extend"
-    uint32_t kernel_mode() const { return extend && align_mode == SWMI_ALIGN_GLOBAL ? 3u : (uint32_t)align_mode; }
+    // the MODE of the affine kernels and their launchers: the align_mode, 3 (extend) for a global run with option "extend" or
+    // 4 (overlap) for a fit run with option "overlap"
+    uint32_t kernel_mode() const {
+        return extend && align_mode == SWMI_ALIGN_GLOBAL ? 3u : overlap && align_mode == SWMI_ALIGN_FIT ? 4u : (uint32_t)align_mode;
+    }
     bool operator==(const RunModes &o) const { return memcmp(this, &o, sizeof(RunModes)) == 0; }
 };
 static_assert(std::has_unique_object_representations_v<RunModes>, "RunModes is compared bytewise: no padding, no floating point");
@@ -223,7 +227,7 @@ struct swmi_ctx {
     bool cell_cap_set = false;              // cell_cap given by the caller (otherwise small launches get longer lists)
     int32_t gap_open = 0;                   // affine gaps: a gap of length k costs gap_open + k * gap (0: linear)
     int affine = -1;                        // -1: the affine kernels (mode 3) when gap_open != 0; 1: always
-    RunModes modes;                         // options "align_mode", "long_reads", "band", "extend", "xdrop", "band_adapt", "gap_open2", "gap2", "cigar", "subopt", "hits" and "end_bonus"
+    RunModes modes;                         // options "align_mode", "long_reads", "band", "extend", "xdrop", "band_adapt", "gap_open2", "gap2", "cigar", "subopt", "hits", "end_bonus" and "overlap"
     std::mutex mat_mu;                      // guards `matrix` (not ctx->mu: setting a matrix does not wait for a run)
     std::shared_ptr<const ScoreMatrix> matrix;   // swmi_set_score_matrix; a run with one takes the affine kernels
     // swmi_batch_run_async: one run in flight on the context's own host thread

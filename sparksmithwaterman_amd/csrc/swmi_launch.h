@@ -23,7 +23,7 @@ extern "C" hipError_t swmi_launch_tfused(const TraceArgs *a, const TFusedArgs *x
 struct AffRun {
     int32_t gap_open;            // a gap of length k costs gap_open + k * gap
     int32_t gap_open2, gap2;     // option "gap_open2" (0: none) and "gap2": the two-piece kernels
-    uint32_t mode;               // 0 local, 1 fit, 2 global (option "align_mode"), 3 extend (option "extend" on a global run)
+    uint32_t mode;               // 0 local, 1 fit, 2 global (option "align_mode"), 3 extend (option "extend" on a global run), 4 overlap (option "overlap" on a fit run)
     uint32_t band;               // option "band": the half-width (0: none) -- the banded strip kernels
     uint32_t xdrop;              // option "xdrop": the threshold (0: none) -- the strip sweep that may stop at a seam
     uint32_t adapt;              // option "band_adapt" (0 / 1) -- the banded strip kernels whose windows follow the alignment
@@ -45,12 +45,14 @@ constexpr uint32_t aff_flags(bool matrix, bool lng, bool band, bool xdrop, bool 
            (adapt ? AFF_F_ADAPT : 0u) | (two ? AFF_F_TWO : 0u) | (subopt ? AFF_F_SUBOPT : 0u) | (endb ? AFF_F_ENDB : 0u) | (hits ? AFF_F_HITS : 0u);
 }
 // shape: 0 narrow (1 .. 4 rows per lane), 1 wide (5 .. 16), 2 long (the strip sweeps); the walks have one shape, 0
-constexpr uint32_t aff_key(uint32_t shape, uint32_t mode, uint32_t flags) { return flags | mode << 9 | shape << 11; }
-// The combinations a kernel may exist for (mode: 0 local, 1 fit, 2 global, 3 extend).  Every row of the two lists and every
-// device entry static_asserts it; aff_run_ok refuses a run by it.
+// (nine flag bits, three bits of mode -- 0 .. 4 -- then the shape)
+constexpr uint32_t aff_key(uint32_t shape, uint32_t mode, uint32_t flags) { return flags | mode << 9 | shape << 12; }
+// The combinations a kernel may exist for (mode: 0 local, 1 fit, 2 global, 3 extend, 4 overlap).  Every row of the kernel lists and
+// every device entry static_asserts it; aff_run_ok refuses a run by it.
 constexpr bool aff_flags_ok(uint32_t mode, uint32_t f) {
     const bool xdrop_or_adapt = f & (AFF_F_XDROP | AFF_F_ADAPT);
-    if (mode > 3u) return false;
+    if (mode > 4u) return false;
+    if (mode == 4u) return !(f & ~(AFF_F_MATRIX | AFF_F_LONG));                          // overlap: a score matrix and long reads, nothing else
     if ((f & AFF_F_BAND) && !(f & AFF_F_LONG)) return false;                             // band: the strip sweeps
     if ((f & AFF_F_XDROP) && !((f & AFF_F_LONG) && mode == 3u)) return false;            // xdrop: the strip sweeps of an extend run
     if ((f & AFF_F_ADAPT) && !((f & AFF_F_BAND) && mode == 3u)) return false;            // band_adapt: the banded ones
@@ -74,6 +76,8 @@ static inline bool aff_run_ok(const AffRun &r, uint32_t long_reads) {
     if (r.subopt < -1 || r.subopt > (1 << 30) || r.hits > SWMI_HITS_MAX || r.end_bonus > (1u << 30)) return false;
     // two-piece and end_bonus runs take neither xdrop nor band_adapt, whatever the shape
     if ((r.gap_open2 || r.end_bonus) && (r.xdrop || r.adapt)) return false;
+    // an overlap run takes none of the options of the long shape either, whatever the shape
+    if (r.mode == 4u && (r.band || r.xdrop || r.adapt || r.gap_open2 || r.subopt || r.hits || r.end_bonus)) return false;
     return aff_flags_ok(r.mode, aff_run_flags(r, long_reads));
 }
 // The kernel the launchers below pick for a run, by name -- null where they refuse the run; shape: 0 narrow, 1 wide, 2 long (what

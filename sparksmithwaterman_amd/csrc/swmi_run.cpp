@@ -673,6 +673,16 @@ static int check_band(const swmi_ctx *ctx, const swmi_batch *b, const swmi_param
 static int check_run_params(const swmi_ctx *ctx, const swmi_batch *b, const swmi_params *p, bool affine, const RunOptions &opt) {
     const RunModes &md = opt.modes;
     const ScoreMatrix *mat = opt.mat.get();
+    // option "overlap" frees the read's ends of a fit run: defined, and built, for unbanded one-piece fit runs alone.
+    // Refused first, whatever pipeline the run would take: an overlap run takes the affine kernels (align_mode fit does)
+    if (md.overlap) {
+        if (md.align_mode != SWMI_ALIGN_FIT)
+            return fail(SWMI_ERR_UNSUPPORTED, "overlap = %d needs align_mode fit (1), got align_mode %d", md.overlap, md.align_mode);
+        const struct { const char *name; int value; } no[] = {{"band", md.band}, {"extend", md.extend}, {"xdrop", md.xdrop}, {"band_adapt", md.band_adapt},
+                                                               {"gap_open2", md.gap_open2}, {"subopt", md.subopt}, {"hits", md.hits}, {"end_bonus", md.end_bonus}};
+        for (const auto &x : no)
+            if (x.value != 0) return fail(SWMI_ERR_UNSUPPORTED, "overlap = %d with %s = %d is not supported", md.overlap, x.name, x.value);
+    }
     // option "subopt": the second-best score is defined, and built, for local runs -- which also rules out extend, xdrop, band_adapt
     // and gap_open2, options of a global run
     if (md.subopt != 0 && md.align_mode != SWMI_ALIGN_LOCAL)

@@ -189,6 +189,8 @@ def _rank_main(args):
             ctx.set_option("band_adapt", 1)
         if args.end_bonus:                                  # ... or a pair taken to the read's end when that is nearly as good
             ctx.set_option("end_bonus", args.end_bonus)
+        if args.overlap:                                    # overlap alignment: the fit sweep with the read's ends free as well
+            ctx.set_option("overlap", 1)
         if args.matrix:                                     # substitution scores on this rank's context (NCBI text format)
             from . import matrix as _matrix
             ctx.set_score_matrix(_matrix.load(args.matrix))
@@ -231,6 +233,10 @@ def _parser():
                 self.error("--end-bonus requires --extend")
             if ns.end_bonus and (ns.xdrop or ns.band_adapt or len(ns.scores.split(",")) == 6):
                 self.error("--end-bonus is not built for --xdrop, --band-adapt or two-piece gaps")
+            if ns.overlap and ns.align_mode != "fit":
+                self.error("--overlap requires --align-mode fit")
+            if ns.overlap and (ns.band or len(ns.scores.split(",")) == 6):
+                self.error("--overlap is not built for --band or two-piece gaps")
             return ns
     ap = Parser(description=__doc__.split("\n")[0])
     ap.add_argument("--ref-dir", required=True)
@@ -274,6 +280,10 @@ def _parser():
                     help="with --extend: take a pair to the end of the read (option end_bonus) when the best extension that reaches it "
                          "scores less than B below the best one anywhere -- no soft clip for one mismatch near the read's end.  Not "
                          "with --xdrop, --band-adapt or two-piece gaps.  0 (the default): off")
+    ap.add_argument("--overlap", action="store_true",
+                    help="with --align-mode fit: overlap (ends-free) alignment (option overlap) -- the read's ends are free as well as the "
+                         "reference's, and the alignment ends in the read's last row or the reference's last column.  Not with --band or "
+                         "two-piece gaps")
     ap.add_argument("--tie", choices=("serial", "strict"), default="serial",
                     help="serial: SmithWaterman's aligner (NoDistribution, DistributeReference); strict: DistributedSW's (DistributeAlgorithm)")
     ap.add_argument("--stream-chunk-bytes", type=int, default=512 << 10, help="sequence bytes per streamed chunk")

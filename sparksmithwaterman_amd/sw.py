@@ -35,7 +35,7 @@ def _algo(align_scores, align_types):
 
 
 @_contextlib.contextmanager
-def _scores(ctx, align_scores, align_mode=None, long_reads=None, band=None, extend=None, xdrop=None, band_adapt=None, end_bonus=None):
+def _scores(ctx, align_scores, align_mode=None, long_reads=None, band=None, extend=None, xdrop=None, band_adapt=None, end_bonus=None, overlap=None):
     """alignScores {match, mismatch, gap}, {match, mismatch, gap, gapOpen} or {match, mismatch, gap, gapOpen, gap2, gapOpen2}:
     yields the three entries make_params takes and, for four, sets the context's "gap_open" for the call (affine gaps: a gap of
     length k costs gapOpen + k * gap); for six also "gap2" and "gap_open2" (two-piece gaps on a global or extend run: a gap costs
@@ -47,7 +47,8 @@ def _scores(ctx, align_scores, align_mode=None, long_reads=None, band=None, exte
     off, or None: the context's own) sets option "xdrop": the drop-off rule of an extend run of a read longer than 1024 bases;
     band_adapt (True / False, or None: the context's own) sets option "band_adapt": the band of a banded extend run follows the
     alignment; end_bonus (a bonus 0 .. 2^30, 0: off, or None: the context's own) sets option "end_bonus": an extend run takes a pair to
-    the read's end when that scores less than the bonus below its best.  The options are put back afterwards."""
+    the read's end when that scores less than the bonus below its best; overlap (True / False, or None: the context's own) sets option
+    "overlap": overlap (ends-free) alignment, with align_mode ALIGN_FIT only.  The options are put back afterwards."""
     sc = tuple(int(x) for x in align_scores)
     if len(sc) in (4, 6) and sc[3] > 0:
         raise ValueError("gapOpen (alignScores[3]) must be <= 0, got %d" % sc[3])
@@ -63,6 +64,8 @@ def _scores(ctx, align_scores, align_mode=None, long_reads=None, band=None, exte
         raise ValueError("band_adapt must be None, True or False, got %r" % (band_adapt,))
     if end_bonus is not None and (isinstance(end_bonus, bool) or not isinstance(end_bonus, int) or not 0 <= end_bonus <= _capi.END_BONUS_MAX):
         raise ValueError("end_bonus must be None or an integer 0 .. 2^30, got %r" % (end_bonus,))
+    if overlap is not None and overlap is not True and overlap is not False:
+        raise ValueError("overlap must be None, True or False, got %r" % (overlap,))
     restore = []
     try:
         if len(sc) in (4, 6):
@@ -94,6 +97,9 @@ def _scores(ctx, align_scores, align_mode=None, long_reads=None, band=None, exte
         if end_bonus is not None:
             restore.append(("end_bonus", ctx.options.get("end_bonus", 0)))
             ctx.set_option("end_bonus", end_bonus)
+        if overlap is not None:
+            restore.append(("overlap", ctx.options.get("overlap", 0)))
+            ctx.set_option("overlap", 1 if overlap else 0)
         yield sc[:3]
     finally:
         for name, prev in reversed(restore):
@@ -105,7 +111,7 @@ class SmithWaterman:
         """Function3<String[], int[], char[], Tuple2<Integer, ArrayList<Tuple2<Integer,String[]>>>>."""
         tie_mode = _capi.TIE_SERIAL
 
-        def __init__(self, context=None, align_mode=None, long_reads=None, band=None, extend=None, xdrop=None, band_adapt=None, end_bonus=None):
+        def __init__(self, context=None, align_mode=None, long_reads=None, band=None, extend=None, xdrop=None, band_adapt=None, end_bonus=None, overlap=None):
             self._ctx = context
             self._align_mode = align_mode       # ALIGN_FIT / ALIGN_GLOBAL: end-to-end alignment (option "align_mode")
             self._long_reads = long_reads       # True: reads longer than 1024 bases on the affine kernels (option "long_reads")
@@ -114,11 +120,12 @@ class SmithWaterman:
             self._xdrop = xdrop                 # a threshold: an extend run of a long read stops at a strip seam that far below its best (option "xdrop")
             self._band_adapt = band_adapt       # True: the band of an extend run follows the alignment from strip to strip (option "band_adapt")
             self._end_bonus = end_bonus         # a bonus: an extend run takes a pair to the read's end when that scores less than this below its best (option "end_bonus")
+            self._overlap = overlap             # True: overlap alignment, with ALIGN_FIT -- all four sequence ends are free (option "overlap")
 
         def call(self, seqs, alignScores=None, alignTypes=None):
             ctx = self._ctx or default_context()
             sc, ty = _algo(alignScores, alignTypes)
-            with _scores(ctx, sc, self._align_mode, self._long_reads, self._band, self._extend, self._xdrop, self._band_adapt, self._end_bonus) as sc3:
+            with _scores(ctx, sc, self._align_mode, self._long_reads, self._band, self._extend, self._xdrop, self._band_adapt, self._end_bonus, self._overlap) as sc3:
                 b = ctx.upload([seqs[0]], [seqs[1]])
                 try:
                     b.run(make_params(sc3, ty, self.tie_mode))
@@ -148,13 +155,14 @@ class Distribution:
         together; results come back in input order, each exactly what MapRef.call returns.
         """
 
-        def __init__(self, context=None, tie_mode=_capi.TIE_SERIAL, align_mode=None, long_reads=None, band=None, extend=None, xdrop=None, band_adapt=None, end_bonus=None):
+        def __init__(self, context=None, tie_mode=_capi.TIE_SERIAL, align_mode=None, long_reads=None, band=None, extend=None, xdrop=None, band_adapt=None, end_bonus=None, overlap=None):
             self._ctx = context
             self._band = band
             self._extend = extend
             self._xdrop = xdrop
             self._band_adapt = band_adapt
             self._end_bonus = end_bonus
+            self._overlap = overlap
             self._tie = tie_mode
             self._align_mode = align_mode
             self._long_reads = long_reads
@@ -170,7 +178,7 @@ class Distribution:
             for idxs in groups.values():
                 _, reads, algo = tuples[idxs[0]]
                 sc, ty = _algo(*(algo if algo is not None else (None, None)))
-                with _scores(ctx, sc, self._align_mode, self._long_reads, self._band, self._extend, self._xdrop, self._band_adapt, self._end_bonus) as sc3:
+                with _scores(ctx, sc, self._align_mode, self._long_reads, self._band, self._extend, self._xdrop, self._band_adapt, self._end_bonus, self._overlap) as sc3:
                     b = ctx.upload([tuples[i][0][1] for i in idxs], list(reads))
                     try:
                         b.run(make_params(sc3, ty, self._tie))
@@ -183,8 +191,8 @@ class Distribution:
     class MapRef:
         """PairFunction<Tuple3<String[], ArrayList<String>, Tuple2<int[],char[]>>, Integer, Tuple2<...>>."""
 
-        def __init__(self, context=None, tie_mode=_capi.TIE_SERIAL, align_mode=None, long_reads=None, band=None, extend=None, xdrop=None, band_adapt=None, end_bonus=None):
-            self._mp = Distribution.MapPartition(context, tie_mode, align_mode, long_reads, band, extend, xdrop, band_adapt, end_bonus)
+        def __init__(self, context=None, tie_mode=_capi.TIE_SERIAL, align_mode=None, long_reads=None, band=None, extend=None, xdrop=None, band_adapt=None, end_bonus=None, overlap=None):
+            self._mp = Distribution.MapPartition(context, tie_mode, align_mode, long_reads, band, extend, xdrop, band_adapt, end_bonus, overlap)
 
         def call(self, tuple3):
             return self._mp.call([tuple3])[0]
@@ -229,13 +237,14 @@ class _FileDriver:
     REF_DIR, IN_DIR = "/home/ubuntu/project/reference", "/home/ubuntu/project/input"   # :43-44
     OUT_DIR = "/home/ubuntu/project/output/reference"                 # :50
 
-    def __init__(self, context=None, tie_mode=_capi.TIE_SERIAL, align_mode=None, long_reads=None, band=None, extend=None, xdrop=None, band_adapt=None, end_bonus=None):
+    def __init__(self, context=None, tie_mode=_capi.TIE_SERIAL, align_mode=None, long_reads=None, band=None, extend=None, xdrop=None, band_adapt=None, end_bonus=None, overlap=None):
         self._ctx = context
         self._band = band
         self._extend = extend
         self._xdrop = xdrop
         self._band_adapt = band_adapt
         self._end_bonus = end_bonus
+        self._overlap = overlap
         self._tie = tie_mode
         self._align_mode = align_mode
         self._long_reads = long_reads
@@ -252,7 +261,7 @@ class _FileDriver:
             out_ext = ioArgs[5] if ioArgs[5] is not None else out_ext
         sc, ty = _algo(*(algoArgs if algoArgs is not None else (None, None)))
         ctx = self._ctx or default_context()
-        with _scores(ctx, sc, self._align_mode, self._long_reads, self._band, self._extend, self._xdrop, self._band_adapt, self._end_bonus) as sc3:
+        with _scores(ctx, sc, self._align_mode, self._long_reads, self._band, self._extend, self._xdrop, self._band_adapt, self._end_bonus, self._overlap) as sc3:
             return self._run(ctx, make_params(sc3, ty, self._tie), ref_dir, in_dir, delim, out_dir, out_name, out_ext)
 
     def _run(self, ctx, params, ref_dir, in_dir, delim, out_dir, out_name, out_ext):
