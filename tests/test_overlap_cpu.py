@@ -1,6 +1,7 @@
 """Overlap (ends-free) alignment (option "overlap" on a fit run) without a GPU: the two restatements of the
 contract in tests/overlap_reference.py against each other, against a brute force over global alignments of spans and against
-properties that hold by construction; which kernels the launchers give a mode-4 run (the second pair of lists of swmi_affine.hip);
+properties that hold by construction; the recipes of tests/overlap_cases.py, each held to what it is built for, the two restatements
+against each other on them and every alignment re-scored; which kernels the launchers give a mode-4 run (the second pair of lists of swmi_affine.hip);
 the host mirror's overlap keyword on a fake context and the driver's --overlap argument."""
 import ctypes as C
 import itertools
@@ -10,7 +11,9 @@ import re
 
 import pytest
 
+import affine_grid_cases as gc
 import gotoh_reference as gr
+import overlap_cases as oc
 import overlap_reference as ov
 from affine_census import AffRun, dummy_matrix, load
 from test_ends_cpu import _FakeContext, _matrix
@@ -143,6 +146,63 @@ def test_corner_is_listed_once_and_order():
     assert (score, cells) == (2, [(2, 5)])
     H = ov.align_scalar("ACGAC", "ACT", (1, -3, -1, 0), matrices=True)[2]
     assert H[2][2] == 2
+
+
+# ---- the recipes of tests/overlap_cases.py: what each is built for, on the restatements alone ----
+def test_tie_sets_restatements_agree_and_hold_their_ties():
+    """6 sets x 64 pairs x 2 tie modes: the numpy form is the scalar one on all 768 runs; every set has pairs beyond cell_cap = 8,
+    sets 3 and 5 have alignments that start with a gap, set 3 never scores above 0"""
+    runs = 0
+    for sc, refs, reads in oc.tie_sets():
+        assert len(refs) == len(reads) == 8
+        for tie in (0, 1):
+            for ref in refs:
+                for read in reads:
+                    got = oc.want(ref, read, sc, tie)
+                    assert got == ov.align_scalar(ref, read, sc, tie_mode=tie, cells=True), (sc, ref, read, tie)
+                    _check_alignments(ref, read, sc, got)
+                    runs += 1
+    assert runs == 768
+    counts = oc.check_tie_sets()
+    assert all(c[0] >= 10 for c in counts) and counts[2][1] >= 20 and counts[4][1] >= 20 and counts[2][2] <= 0, counts
+
+
+@pytest.mark.parametrize("matrix", [False, True])
+def test_walk_pairs_keep_their_runs_with_all_four_ends_free(matrix):
+    """the cut walk grid: every pair's overlap alignment is not its fit alignment, keeps both planted runs, ends on row m left of
+    the corner and starts at column 0 below row 1; the uncut pair ends at the corner.  Classes R <= 4 against the scalar form."""
+    mat = oc.matrix_of(matrix)
+    for tie in (0, 1):
+        assert oc.check_walk_pairs(matrix, tie) == 16
+        for (R, ref, read), (_, whole_ref, whole_read) in zip(oc.walk_pairs(matrix), gc.walk_grid(matrix)):
+            for a, b in ((ref, read), (whole_ref, whole_read)):
+                got = oc.want(a, b, gc.WALK_SCORES, tie, mat)
+                _check_alignments(a, b, gc.WALK_SCORES, got, mat)
+                if R <= 4:
+                    assert got == ov.align_scalar(a, b, gc.WALK_SCORES, tie_mode=tie, matrix=mat, cells=True), (R, tie)
+
+
+@pytest.mark.parametrize("tie", [0, 1])
+def test_long_read_recipes(tie):
+    """the seam cases and the tied maxima over both strips and row m"""
+    oc.check_seam_cases(tie)
+    for name, ref, read, sc, span in oc.seam_cases():
+        _check_alignments(ref, read, sc, oc.want(ref, read, sc, tie))
+    oc.check_long_tie_case(tie)
+    ref, read = oc.long_tie_case()
+    _check_alignments(ref, read, oc.LONG_TIE_SCORES, oc.want(ref, read, oc.LONG_TIE_SCORES, tie))
+
+
+def test_bound_recipes():
+    """every score of the restatement (int64 sums) fits int32, one set ties in more than 64 cells, the two known answers"""
+    oc.check_bound_cases()
+    for name, ref, read, sc in oc.bound_cases():
+        for tie in (0, 1):
+            _check_alignments(ref, read, sc, oc.want(ref, read, sc, tie))
+    S = oc.LONG_S_OK
+    for name, ref, read in oc.long_bound_cases():
+        assert len(read) == 2049
+        _check_alignments(ref, read, (S, -S, -S, -S), oc.want(ref, read, (S, -S, -S, -S)))
 
 
 def _listed(macro):

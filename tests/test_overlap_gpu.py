@@ -4,13 +4,19 @@ its begin, both strings and its maximum cell, the flags and the MapRef view.  se
 feature.
 
   sweep kernel (sw_affine_sweep_...)    rows per lane     run by
-  overlap_kernel                        1 .. 4            test_rows_per_lane, test_planted_overlaps, test_census
-  overlap_wide_kernel                   5 .. 16           test_rows_per_lane, test_planted_overlaps, test_census
-  overlap_matrix_kernel                 1 .. 4            test_matrix, test_census
-  overlap_matrix_wide_kernel            5 .. 16           test_matrix, test_census
-  long_overlap_kernel                   strips of 16      test_long_reads, test_census
+  overlap_kernel                        1 .. 4            test_rows_per_lane, test_planted_overlaps, test_census, test_walk_grid,
+                                                          test_random_pairs_with_many_ties, test_options
+  overlap_wide_kernel                   5 .. 16           test_rows_per_lane, test_planted_overlaps, test_census, test_walk_grid,
+                                                          test_bounds, test_options
+  overlap_matrix_kernel                 1 .. 4            test_matrix, test_census, test_walk_grid
+  overlap_matrix_wide_kernel            5 .. 16           test_matrix, test_census, test_walk_grid
+  long_overlap_kernel                   strips of 16      test_long_reads, test_census, test_long_reads_seams,
+                                                          test_long_reads_more_ties_than_cell_cap, test_bounds
   long_overlap_matrix_kernel            strips of 16      test_matrix, test_census
-The walks: sw_affine_traceback_overlap_kernel with every short read, sw_affine_traceback_long_overlap_kernel with every long one."""
+The walks: sw_affine_traceback_overlap_kernel with every short read (gap runs: test_walk_grid; alignments that start with a gap:
+test_random_pairs_with_many_ties), sw_affine_traceback_long_overlap_kernel with every long one (a run across row 1024, two seams,
+column 0 at a seam: test_long_reads_seams; 709 walks of one pair: test_long_reads_more_ties_than_cell_cap).  The inputs of the tests
+named here for the first time come from tests/overlap_cases.py, which states what each is built for."""
 import ctypes as C
 import random
 
@@ -24,6 +30,7 @@ import affine_gpu_util as u
 import affine_grid_cases as gc
 import cigar_reference as cr
 import gotoh_reference as gr
+import overlap_cases as oc
 import overlap_reference as ov
 
 pytestmark = pytest.mark.gpu
@@ -194,6 +201,59 @@ def test_a_non_competing_cell_at_the_maximum_is_not_listed(ctx):
         b.free()
 
 
+# 3a -- direction ties, tied maximum cells and alignments that start with a gap: small alphabets, scores down to 0
+@pytest.mark.parametrize("tie", [0, 1])
+def test_random_pairs_with_many_ties(ctx, tie):
+    """the six sets of overlap_cases.tie_sets, 64 pairs each, with cell_cap = 8.  Sets 3 and 5 hold the alignments that start with a
+    gap: there the chains meet E(i,0) := o and F(0,j) := o.  Each set has at least 10 pairs with more than 8 tied cells over the two
+    tie modes together (tests/test_overlap_cpu.py); a run has one tie mode, so what it is held to is the restatement's count of such
+    pairs in that mode -- 17, 60, 6, 25, 6, 15 in either -- which sums to the 10 and more per set over this test's two cases."""
+    failed = []                                                   # every set is run: the message names all that differ
+    for k, (sc, refs, reads) in enumerate(oc.tie_sets(), 1):
+        exp = {(r, q): oc.want(refs[r], reads[q], sc, tie) for r in range(len(refs)) for q in range(len(reads))}
+        over = sum(len(e[2]) > oc.TIE_CELL_CAP for e in exp.values())
+        b = _run(ctx, refs, reads, sc, tie, cell_cap=oc.TIE_CELL_CAP)
+        print("set %d tie %d: rerun_pairs %d, pairs over cell_cap %d" % (k, tie, b.timing().rerun_pairs, over))
+        try:
+            u.check(b, refs, reads, exp, FIT)
+            assert b.timing().rerun_pairs >= over >= 5
+        except AssertionError as e:
+            failed.append(("set %d" % k, sc, str(e)[:200]))
+        b.free()
+    assert not failed, failed
+
+
+# 3b -- gap runs: the walk grid with all four ends free, and as it stands (the corner cell)
+@pytest.mark.parametrize("tie", [0, 1])
+@pytest.mark.parametrize("matrix", [False, True])
+def test_walk_grid(ctx, matrix, tie):
+    """an inserted run that crosses lanes and a deleted run longer than one traceback tile (R >= 6) in every rows-per-lane class, in
+    an alignment that ends on row m left of column n and reaches column 0 below row 1 (the cut pairs) or ends at (m, n) (the uncut
+    ones); Batch.span, then the same walks under cigar = 2"""
+    mat = oc.matrix_of(matrix)
+    for grid in (oc.walk_pairs(matrix), gc.walk_grid(matrix)):
+        refs, reads = [ref for _, ref, _ in grid], [read for _, _, read in grid]
+        assert [gc.rows_per_lane(len(read)) for read in reads] == list(gc.RS)
+        want = [oc.want(ref, read, gc.WALK_SCORES, tie, mat) for ref, read in zip(refs, reads)]
+        b = _run(ctx, refs, reads, gc.WALK_SCORES, tie, mat)
+        _check_diagonal(b, grid, want, len(reads))
+        for x, (_, alns, cells) in enumerate(want):
+            for k, (aln, cell) in enumerate(zip(alns, cells)):
+                assert b.span(x * len(reads) + x, k) == ov.span(cell, aln), (grid[x][0], k)
+        b.free()
+        b = _run(ctx, refs, reads, gc.WALK_SCORES, tie, mat, cigar=2)
+        for x, (score, alns, cells) in enumerate(want):
+            pair = x * len(reads) + x
+            got = b.cigars(pair)
+            assert b.score(pair) == score and len(got) == len(alns) >= 1, grid[x][0]
+            for k, ((begin, (ra, qa)), cell) in enumerate(zip(alns, cells)):
+                ent, nm = cr.cigar(ra, qa, 2)
+                assert got[k] == (begin, cell[0], cell[1], ent, nm), (grid[x][0], k)
+                assert b.span(pair, k) == ov.span(cell, alns[k]), (grid[x][0], k)
+        b.free()
+        ctx.set_option("cigar", 0)
+
+
 # 4 -- no overlap worth having
 def test_no_overlap(ctx):
     refs, reads = ["G" * 70, "G"], ["C" * 65, "C"]
@@ -295,6 +355,72 @@ def test_long_reads_mutated_dovetail(ctx, tie):
     b.free()
 
 
+# 6a -- the seams: column 0 at rows 1025 and 2049, a gap run across row 1024, a walk across two seams
+@pytest.mark.parametrize("tie", [0, 1])
+def test_long_reads_seams(ctx, tie):
+    """lane 0's diagonal for the first row of strip sx is H(1024 sx, 0) = 0 (fit has o + 1024 sx e there): only an alignment whose
+    first row is 1024 sx + 1, at column 1, reads it"""
+    failed = []                                                   # every case is run: the message names all that differ
+    for name, ref, read, sc, span in oc.seam_cases():
+        want = oc.want(ref, read, sc, tie)
+        assert len(read) > 1024 and len(want[2]) == 1, name
+        b = _run(ctx, [ref], [read], sc, tie)
+        try:
+            u.check_pair(b, 0, want, FIT, name)
+            assert b.span(0, 0) == ov.span(want[2][0], want[1][0]) and span in (None, b.span(0, 0)), name
+        except AssertionError as e:
+            failed.append(str(e)[:200])
+        b.free()
+    assert not failed, failed
+
+
+# 6b -- tied maxima on column n of both strips and on row m, more than cell_cap: the exact-size re-run of the strip sweep
+@pytest.mark.parametrize("tie", [0, 1])
+def test_long_reads_more_ties_than_cell_cap(ctx, tie):
+    ref, read = oc.long_tie_case()
+    want = oc.want(ref, read, oc.LONG_TIE_SCORES, tie)
+    assert len(want[2]) == 709
+    b = _run(ctx, [ref], [read], oc.LONG_TIE_SCORES, tie, cell_cap=8)
+    assert b.timing().rerun_pairs == 1 and b.n_alignments(0)[0] == 709
+    u.check(b, [ref], [read], {(0, 0): want}, FIT)
+    b.free()
+
+
+# 6c -- the arithmetic bounds: |score| = 2^20 with no floor, and M * S <= 2^30 under long_reads from both sides
+def test_bounds(ctx):
+    for name, ref, read, sc in oc.bound_cases():
+        for tie in (0, 1):
+            want = oc.want(ref, read, sc, tie)
+            if len(read) > 1024:                                  # 2048 rows * 2^20: the restatement's 2^30 is out of the library's reach
+                ctx.set_option("gap_open", sc[3])
+                b = ctx.upload([ref], [read])
+                _refused(b, sw.make_params(sc[:3], None, tie), "2^30")
+                assert b.timing().fill_launches == 0
+                b.free()
+                continue
+            b = _run(ctx, [ref], [read], sc, tie)
+            u.check_pair(b, 0, want, FIT, (name, tie))
+            b.free()
+    cases = oc.long_bound_cases()
+    refs, reads = [c[1] for c in cases], [c[2] for c in cases]
+    S = oc.LONG_S_OK
+    sc = (S, -S, -S, -S)
+    want = [oc.want(ref, read, sc) for ref, read in zip(refs, reads)]
+    assert want[0][0] == 2049 * S
+    b = _run(ctx, refs, reads, sc)
+    _check_diagonal(b, cases, want, len(reads))
+    b.free()
+    S = oc.LONG_S_REFUSED
+    ctx.set_option("gap_open", -S)
+    b = ctx.upload(refs, reads)
+    _refused(b, sw.make_params((S, -S, -S)), "2^30")
+    assert b.timing().fill_launches == 0                          # nothing was launched
+    ctx.set_option("gap_open", -oc.LONG_S_OK)
+    b.run(sw.make_params(sc[:3]))                                 # the batch is still usable
+    _check_diagonal(b, cases, want, len(reads))
+    b.free()
+
+
 # 8 -- the options that combine
 _VARIANTS = {}
 
@@ -309,10 +435,18 @@ def _variants():
     return _VARIANTS["refs"], _VARIANTS["reads"], _VARIANTS["exp"]
 
 
-@pytest.mark.parametrize("opt", [("scores_only", 1), ("device_strings", 0), ("zero_copy", 0), ("cigar", 1), ("cigar", 2)])
+@pytest.mark.parametrize("opt", [("scores_only", 1), ("device_strings", 0), ("zero_copy", 0), ("cigar", 1), ("cigar", 2),
+                                 ("arena_words_per_pair", 1), ("cell_cap", 1), ("max_workspace_bytes", 1 << 20)])
 def test_options(ctx, opt):
     refs, reads, exp = _variants()
+    if opt[0] == "max_workspace_bytes":                           # (the 1050 x 1200 field alone is over 1 MiB: that run is refused)
+        reads = reads[:3]
+        exp = {k: v for k, v in exp.items() if k[1] < 3}
     b = _run(ctx, refs, reads, (2, -3, -1, -2), **dict([opt]))
+    if opt[0] == "cell_cap":
+        assert any(len(want[2]) > 1 for want in exp.values()) and b.timing().rerun_pairs >= 1
+    if opt[0] == "max_workspace_bytes":
+        assert b.timing().fill_launches >= 2
     for (r, q), want in exp.items():
         pair = r * len(reads) + q
         assert b.score(pair) == want[0], (r, q)
