@@ -71,6 +71,10 @@ public class GpuSmithWaterman
 	static native int[] nativePairHits( long batch , long pair ) ;
 	/** substitution scores on the context: alphabet = n ISO-8859-1 symbols, scores = n * n, row = read base; null clears */
 	static native void nativeSetScoreMatrix( long ctx , byte[] alphabet , int[] scores ) ;
+	/** per-read score profiles on a batch of nativeAlignBatch, and the batch run again under them: alphabet = n ISO-8859-1 symbols,
+	 * scores = n entries per read byte in upload order, nRows = the reads' bytes; alphabet null clears ( setReadProfiles ) */
+	static native void nativeSetReadProfiles( long ctx , long batch , int match , int mismatch , int gap , int tieMode , byte[] types ,
+	                                          byte[] alphabet , int[] scores , long nRows ) ;
 	/** a pair list over the sequences: specs = eight ints per pair ( alignPairs ) */
 	static native long nativeAlignPairs( long ctx , int match , int mismatch , int gap , int tieMode , byte[] types ,
 	                                     ByteBuffer refBytes , long[] refOff , int nRefs , ByteBuffer readBytes , long[] readOff , int nReads , int[] specs ) ;
@@ -254,6 +258,40 @@ public class GpuSmithWaterman
 
 	/** { score , read row , reference column } per hit of a pair of a native batch run under setHits, best first (1-based cells) */
 	static int[] hits( long batch , long pair ) { return nativePairHits( batch , pair ) ; }
+
+	/**
+	 * Per-read score profiles (position-specific scoring matrices; include/swmi.h: swmi_batch_set_read_profiles) on a native batch of
+	 * this thread's context, and the batch run again under them: alphabet = the n symbols (ISO-8859-1, distinct ignoring case),
+	 * profiles[q][i][c] = the score of position i of read q against reference symbol alphabet[c]; a reference base outside the alphabet
+	 * scores mismatch.  alignScores = { match , mismatch , gap }, types and tieMode as the batch was aligned with.  alphabet null
+	 * clears the profiles.  The score matrix of setScoreMatrix must not be set at the same time.
+	 * PRECONDITION, which neither this method nor the library can check (the library has no query for a batch's reads): profiles has
+	 * one entry per read of the batch, in upload order, and profiles[q].length is the length of read q.  The library reads n entries
+	 * per read byte of the batch from the flattened array; with fewer rows than that it reads past the array's end.
+	 */
+	static void setReadProfiles( long ctx , long batch , int[] alignScores , int tieMode , byte[] types , String alphabet , int[][][] profiles )
+	{
+		if( alphabet == null ) { nativeSetReadProfiles( ctx , batch , alignScores[0] , alignScores[1] , alignScores[2] , tieMode , types , null , null , 0L ) ; return ; }
+		int n = alphabet.length() ;
+		for( int i = 0 ; i < n ; i++ )
+			if( alphabet.charAt(i) > 0xFF )
+				throw new IllegalArgumentException( "profile symbol " + i + " is not an ISO-8859-1 character" ) ;
+		if( profiles == null ) throw new IllegalArgumentException( "profiles is null" ) ;
+		long rows = 0 ;
+		for( int[][] p : profiles ) rows += p.length ;
+		if( rows * n > Integer.MAX_VALUE ) throw new IllegalArgumentException( "more than 2^31 - 1 profile entries in one batch" ) ;
+		int[] flat = new int[(int)( rows * n )] ;
+		int at = 0 ;
+		for( int q = 0 ; q < profiles.length ; q++ )
+			for( int i = 0 ; i < profiles[q].length ; i++ )
+			{
+				if( profiles[q][i] == null || profiles[q][i].length != n ) throw new IllegalArgumentException( "profile " + q + " row " + i + " needs " + n + " entries" ) ;
+				System.arraycopy( profiles[q][i] , 0 , flat , at , n ) ;
+				at += n ;
+			}
+		nativeSetReadProfiles( ctx , batch , alignScores[0] , alignScores[1] , alignScores[2] , tieMode , types ,
+		                       alphabet.getBytes( StandardCharsets.ISO_8859_1 ) , flat , rows ) ;
+	}
 
 	/** the score matrix every context applies before its next batch: { alphabet , scores } (null: none), and its version */
 	private static volatile Object[] MATRIX = null ;

@@ -218,6 +218,41 @@ JNIEXPORT void JNICALL Java_sw_GpuSmithWaterman_nativeSetScoreMatrix(JNIEnv *env
     if (rc != SWMI_OK) throw_msg(env, err);
 }
 
+/* per-read score profiles on a batch of nativeAlignBatch, and the batch run again under them: alphabet = n ISO-8859-1 symbols,
+ * scores = int[n * nRows], n entries per read byte in upload order; alphabet == null clears them */
+JNIEXPORT void JNICALL Java_sw_GpuSmithWaterman_nativeSetReadProfiles(JNIEnv *env, jclass cls, jlong ctx, jlong batch, jint match,
+                                                                      jint mismatch, jint gap, jint tieMode, jbyteArray types,
+                                                                      jbyteArray alphabet, jintArray scores, jlong nRows) {
+    char err[640];
+    jbyte ty[4] = {0, 0, 0, 0};
+    jbyte *a = NULL;
+    jint *sc = NULL;
+    jsize ty_len, n = 0, ns = 0;
+    int rc;
+    (void)cls;
+    if (!types) { throw_msg(env, "nativeSetReadProfiles: types is null"); return; }
+    ty_len = (*env)->GetArrayLength(env, types);
+    if (ty_len == 4) (*env)->GetByteArrayRegion(env, types, 0, 4, ty);
+    if (alphabet) {
+        if (!scores) { throw_msg(env, "nativeSetReadProfiles: scores is null"); return; }
+        n = (*env)->GetArrayLength(env, alphabet);
+        ns = (*env)->GetArrayLength(env, scores);
+        a = (*env)->GetByteArrayElements(env, alphabet, NULL);
+        sc = (*env)->GetIntArrayElements(env, scores, NULL);
+        if (!a || !sc) {
+            if (a) (*env)->ReleaseByteArrayElements(env, alphabet, a, JNI_ABORT);
+            if (sc) (*env)->ReleaseIntArrayElements(env, scores, sc, JNI_ABORT);
+            return;                                                   /* (OutOfMemoryError pending) */
+        }
+    }
+    rc = swmi_shim_set_read_profiles((swmi_ctx *)(intptr_t)ctx, (swmi_batch *)(intptr_t)batch, match, mismatch, gap, tieMode,
+                                     (const signed char *)ty, (size_t)ty_len, (const signed char *)a, (size_t)n, (const int32_t *)sc,
+                                     (size_t)ns, (int64_t)nRows, err, sizeof err);
+    if (a) (*env)->ReleaseByteArrayElements(env, alphabet, a, JNI_ABORT);
+    if (sc) (*env)->ReleaseIntArrayElements(env, scores, sc, JNI_ABORT);
+    if (rc != SWMI_OK) throw_msg(env, err);
+}
+
 /* refBytes/readBytes: direct ByteBuffers of ISO-8859-1 bytes; refOff/readOff: long[n+1] */
 JNIEXPORT jlong JNICALL Java_sw_GpuSmithWaterman_nativeAlignBatch(
         JNIEnv *env, jclass cls, jlong ctx, jint match, jint mismatch, jint gap, jint tieMode, jbyteArray types,

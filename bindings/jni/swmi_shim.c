@@ -194,6 +194,29 @@ int swmi_shim_set_score_matrix(swmi_ctx *ctx, const signed char *alphabet, size_
     return SWMI_OK;
 }
 
+int swmi_shim_set_read_profiles(swmi_ctx *ctx, swmi_batch *b, int32_t match, int32_t mismatch, int32_t gap, int32_t tie_mode,
+                                const signed char *types, size_t types_len, const signed char *alphabet, size_t n,
+                                const int32_t *scores, size_t n_scores, int64_t n_rows, char *err, size_t err_len) {
+    swmi_params p;
+    int rc;
+    if (!ctx) return shim_fail(SWMI_ERR_INVALID, err, err_len, "nativeSetReadProfiles", "context handle is 0");
+    if (!b) return shim_fail(SWMI_ERR_INVALID, err, err_len, "nativeSetReadProfiles", "batch handle is 0");
+    if (!types || types_len != 4)
+        return shim_fail(SWMI_ERR_INVALID, err, err_len, "nativeSetReadProfiles", "alignTypes must hold exactly 4 characters");
+    if (n > 64) return shim_fail(SWMI_ERR_INVALID, err, err_len, "nativeSetReadProfiles", "at most 64 symbols");
+    if (n > 0 && (!alphabet || !scores))
+        return shim_fail(SWMI_ERR_INVALID, err, err_len, "nativeSetReadProfiles", "alphabet or scores is null");
+    if (n_rows < 0 || n_scores != n * (size_t)n_rows)
+        return shim_fail(SWMI_ERR_INVALID, err, err_len, "nativeSetReadProfiles", "scores must hold n entries per read byte");
+    if ((rc = swmi_batch_set_read_profiles(ctx, b, n ? (const uint8_t *)alphabet : NULL, (uint32_t)n, n ? scores : NULL)) != SWMI_OK)
+        return shim_fail(rc, err, err_len, "swmi_batch_set_read_profiles", swmi_last_error());
+    swmi_default_params(&p);
+    p.match = match; p.mismatch = mismatch; p.gap = gap; p.tie_mode = tie_mode;
+    memcpy(p.types, types, 4);
+    if ((rc = swmi_batch_run(ctx, b, &p)) != SWMI_OK) return shim_fail(rc, err, err_len, "swmi_batch_run", swmi_last_error());
+    return SWMI_OK;
+}
+
 int swmi_shim_align_batch(swmi_ctx *ctx, int32_t match, int32_t mismatch, int32_t gap, int32_t tie_mode,
                           const signed char *types, size_t types_len,
                           const void *ref_bytes, int64_t ref_cap, const int64_t *ref_off, int32_t n_refs,

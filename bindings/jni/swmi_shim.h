@@ -124,6 +124,16 @@ int swmi_shim_pair_hits(const swmi_batch *b, int64_t pair, int32_t *out, int32_t
 int swmi_shim_set_score_matrix(swmi_ctx *ctx, const signed char *alphabet, size_t n, const int32_t *scores, size_t n_scores,
                                char *err, size_t err_len);
 
+/* nativeSetReadProfiles: per-read score profiles on a batch nativeAlignBatch returned (swmi_batch_set_read_profiles), and the batch
+ * run again under them with the same scores, tie mode and types: `alphabet` = n symbols narrowed to bytes, `scores` = n entries per
+ * read byte of the batch in upload order; n_rows = the reads' bytes as the caller uploaded them (readOff[nReads]), and n_scores
+ * must be n * n_rows.  n_rows is the CALLER's statement and a precondition: the library has no query for a batch's read bytes, reads
+ * n entries per read byte of the batch, and runs past `scores` when n_rows is less than that.  n = 0 clears the profiles and runs the batch without them.  A refused set leaves the batch as it was; a
+ * refused run leaves it with the new profiles and without results. */
+int swmi_shim_set_read_profiles(swmi_ctx *ctx, swmi_batch *b, int32_t match, int32_t mismatch, int32_t gap, int32_t tie_mode,
+                                const signed char *types, size_t types_len, const signed char *alphabet, size_t n,
+                                const int32_t *scores, size_t n_scores, int64_t n_rows, char *err, size_t err_len);
+
 /* nativeRefTotal / nativeRefSiteCount / nativeRefSite */
 int swmi_shim_ref_total(const swmi_batch *b, int32_t ref, int32_t *total, char *err, size_t err_len);
 int swmi_shim_ref_site_count(swmi_batch *b, int32_t ref, int64_t *n, char *err, size_t err_len);

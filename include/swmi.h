@@ -435,6 +435,32 @@ int  swmi_batch_set_pairs(swmi_ctx *ctx, swmi_batch *b, const swmi_pair_spec *sp
 /* spec `pair` of the batch, SWMI_SPEC_WHOLE resolved to a length.  On a cross-product batch: SWMI_ERR_INVALID. */
 int  swmi_batch_pair_spec(const swmi_batch *b, uint64_t pair, swmi_pair_spec *spec);
 
+/* ---- per-read score profiles (position-specific scoring matrices) ---------------------------------
+ * A profile makes the score of a cell depend on the POSITION in the read instead of on the read's letter: a PSSM of a protein
+ * search, or the quality-aware penalties of a mapper (a mismatch at a Q2 base costs less than one at a Q40 base).
+ * alphabet: n bytes as for swmi_set_score_matrix -- 1 <= n <= 64, pairwise distinct after canonicalisation.  scores: n entries per
+ * read byte of the batch, in upload order: the entry of read q, 0-based row i < m_q and symbol c is
+ * scores[(read_off[q] + i) * n + c], read_off being the array swmi_batch_upload was given.  The array is copied.  n = 0 (the
+ * pointers may be NULL) clears the profiles.  A run of a batch that has profiles scores cell (i, j) of (ref, read q) as
+ *      s(i,j) = scores[(read_off[q] + i - 1) * n + class(ref[j-1])]   if the reference byte's canonical code is in the alphabet
+ *             = params.mismatch                                       otherwise
+ * and everything else is the contract of the run's mode with this s: the recurrences, both tie chains, the order of tied maximum
+ * cells, local mode's degenerate maximum 0, the walks and `begin`.  The read's bytes are not read for scoring; they are what the
+ * aligned strings show (with case) and what cigar = 2 compares for = / X.  Such a run takes the affine kernels whatever gap_open /
+ * affine say (swmi_batch_mode = 3); S of the affine bounds covers the largest |entry|, and the path bound takes the largest entry
+ * as it does a matrix's.  Scope: align_mode local, fit and global, extend, overlap, both tie modes, any gap_open <= 0, scores_only,
+ * cigar, device_strings, zero_copy, profiling, cell_cap with its exact-size re-run, max_workspace_bytes, swmi_batch_run_async.
+ * Setting: duplicate symbols, n > 64, an entry with |entry| > 2^20 or a NULL pointer with n > 0 return SWMI_ERR_INVALID and leave
+ * the batch as it was; a batch of swmi_batch_upload_pairs returns SWMI_ERR_UNSUPPORTED (streams make their own chunk batches and
+ * take no profiles).  The call takes the context's lock as swmi_batch_set_pairs does; the batch's old results are dropped and the
+ * batch is to be run again.  A run takes the profiles set when it was asked for.
+ * Running: SWMI_ERR_UNSUPPORTED before anything is launched, the message naming the profile and the other value, for a context
+ * score matrix set at the same time, gap_open2, subopt, hits or end_bonus; for a batch whose longest read has more than 1024
+ * bases; and for a batch beyond the LDS bound: with m the longest read and M = 64 * ceil(m / 64), M * (n + 1) <= 32768 (every read
+ * of up to 1024 bases with n <= 31; n = 64 with reads of up to 448 bases).  band, xdrop and band_adapt act on reads longer than
+ * 1024 bases only and keep their rules.  A batch without profiles runs exactly as before. */
+int  swmi_batch_set_read_profiles(swmi_ctx *ctx, swmi_batch *b, const uint8_t *alphabet, uint32_t n, const int32_t *scores);
+
 /* Fill + direction field + max-cell lists + device traceback for every pair, then
  * the compact result records device->host.  Synchronous on return. */
 int  swmi_batch_run(swmi_ctx *ctx, swmi_batch *b, const swmi_params *p);

@@ -85,6 +85,7 @@ SYMBOLS = [
                                           C.c_uint64, C.POINTER(_P)]),
     ("swmi_batch_set_pairs", C.c_int, [_P, _P, C.POINTER(PairSpec), C.c_uint64]),
     ("swmi_batch_pair_spec", C.c_int, [_P, C.c_uint64, C.POINTER(PairSpec)]),
+    ("swmi_batch_set_read_profiles", C.c_int, [_P, _P, C.c_char_p, C.c_uint32, C.POINTER(C.c_int32)]),
     ("swmi_batch_run", C.c_int, [_P, _P, C.POINTER(Params)]),
     ("swmi_batch_run_async", C.c_int, [_P, _P, C.POINTER(Params)]),
     ("swmi_batch_wait", C.c_int, [_P]),

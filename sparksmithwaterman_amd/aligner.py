@@ -216,9 +216,49 @@ class Batch:
         h = C.c_void_p()
         check(self._lib.swmi_batch_upload(ctx._h, rb, ro, self.n_refs, qb, qo, self.n_reads, C.byref(h)))
         self._h = h
+        self._read_off = qo                 # (the reads' lengths, for set_read_profiles)
+        self.read_profiles = None           # what set_read_profiles() last set: (alphabet bytes, number of symbols), or None
 
     def n_pairs(self):
         return self.n_refs * self.n_reads
+
+    def set_read_profiles(self, alphabet, profiles=None):
+        """Per-read score profiles (swmi_batch_set_read_profiles): alphabet = n symbols as for
+        Context.set_score_matrix, profiles = one m_q x n integer array per read of the batch, in upload order -- row i scores
+        read position i against each symbol of the REFERENCE; a reference byte outside the alphabet scores `mismatch`.
+        set_read_profiles(None) clears them.  The old results are dropped: run the batch again."""
+        import numpy as np
+        from . import matrix as _matrix
+        if alphabet is None:
+            if profiles is not None:
+                raise ValueError("profiles without an alphabet")
+            check(self._lib.swmi_batch_set_read_profiles(self._ctx._h, self._h, None, 0, None))
+            self.read_profiles = None
+            return self
+        if profiles is None:
+            raise ValueError("an alphabet without profiles (set_read_profiles(None) clears them)")
+        sym = _matrix._symbols(alphabet)
+        n = len(sym)
+        off = getattr(self, "_read_off", None)        # (a pair list has none: the library refuses it)
+        lens = None if off is None else [off[q + 1] - off[q] for q in range(self.n_reads)]
+        if lens is not None and len(profiles) != len(lens):
+            raise ValueError("%d profiles for %d reads" % (len(profiles), len(lens)))
+        rows = []
+        for q, p in enumerate(profiles):
+            a = np.asarray(p)
+            if a.size and not np.all(a == np.floor(a)):
+                raise ValueError("profile %d has entries that are not integers" % q)
+            a = a.astype(np.int64).reshape(-1, n) if a.size else np.zeros((0, n), np.int64)
+            if lens is not None and a.shape[0] != lens[q]:
+                raise ValueError("profile %d has %d rows of %d entries for a read of %d bases" % (q, a.shape[0], n, lens[q]))
+            if a.size and int(np.abs(a).max()) > _matrix.MAX_ABS_SCORE:
+                raise ValueError("profile %d: |entries| must be <= 2^20" % q)
+            rows.append(a)
+        flat = np.ascontiguousarray(np.concatenate(rows) if rows else np.zeros((0, n)), dtype=np.int32)
+        ptr = flat.ctypes.data_as(C.POINTER(C.c_int32)) if flat.size else (C.c_int32 * 1)()
+        check(self._lib.swmi_batch_set_read_profiles(self._ctx._h, self._h, sym, n, ptr))
+        self.read_profiles = (sym, n)
+        return self
 
     def run(self, params=None):
         """Fill + traceback on the GPU for every pair, results to the host.  Synchronous."""

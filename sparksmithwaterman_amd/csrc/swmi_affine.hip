@@ -93,7 +93,14 @@
 //   m and the last column from INT32_MIN + 1 up (the score may be <= 0; there is no degenerate case), and a walk that ends at the first
 //   cell of row 0 or column 0 without a tail.
 //
-// How the 93 kernels are made: two lists, AFF_SWEEPS (72 rows) and AFF_TRACEBACKS (13), name every kernel with its
+// sw_affine_sweep_[fit_|global_|extend_|overlap_]profile[_wide]_kernel: the short sweeps of a batch with per-read score profiles
+//   (swmi_batch_set_read_profiles), PROFILE = 1: s(i,j) is entry [row i][class of the reference base] of the READ's own
+//   table -- one row per read position, not per read letter.  The workgroup stages the 256 keys (class * 4), every wavefront its
+//   read's table in dynamic LDS (prows rows of n + 1 dwords, column n = mismatch for a reference base outside the alphabet); a lane's
+//   row words are the byte offsets of its rows' table rows, and the cell is one LDS read at row word + key, with no select.  The
+//   read's bytes are not read.  A list of their own, AFF_PROFILE_SWEEPS (10), and a launcher of their own; the walks are unchanged.
+//
+// How the 93 kernels of the first four lists are made: two lists, AFF_SWEEPS (72 rows) and AFF_TRACEBACKS (13), name every kernel with its
 //   MODE and its flags; the kernel definitions, their parameter lists and the launchers' tables are the lists under a macro each,
 //   and the file defines no kernel outside them and the second pair of lists, AFF_OVERLAP_SWEEPS (6) and AFF_OVERLAP_TRACEBACKS (2),
 //   which goes through the same macros (the first pair's row counts are pinned by the tests of the modes they hold).
@@ -106,6 +113,7 @@
 //   and the epilogue as text (DESIGN.md 8e and 8f say why).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <algorithm>
 #include "swmi_device.h"
 #include "swmi_emit.h"
 #include "swmi_launch.h"
@@ -138,13 +146,18 @@
 #define AFF_FLAG_NAMES(F)                                                                                                           \
     [[maybe_unused]] constexpr bool MATRIX = ((F) & AFF_F_MATRIX) != 0, LONG = ((F) & AFF_F_LONG) != 0, BAND = ((F) & AFF_F_BAND) != 0, \
                                     XDROP = ((F) & AFF_F_XDROP) != 0, ADAPT = ((F) & AFF_F_ADAPT) != 0, TWO = ((F) & AFF_F_TWO) != 0, \
-                                    SUBOPT = ((F) & AFF_F_SUBOPT) != 0, ENDB = ((F) & AFF_F_ENDB) != 0, HITS = ((F) & AFF_F_HITS) != 0;
+                                    SUBOPT = ((F) & AFF_F_SUBOPT) != 0, ENDB = ((F) & AFF_F_ENDB) != 0, HITS = ((F) & AFF_F_HITS) != 0, \
+                                    PROFILE = ((F) & AFF_F_PROFILE) != 0;
 
 namespace {
 
 // the score matrix of the matrix sweeps (only their instantiations reference it: the other kernels allocate no LDS)
 __shared__ uint32_t aff_mkey[256];
 __shared__ int aff_mtab[SWMI_MAT_NN_MAX * SWMI_MAT_NN_MAX];
+// the reads' tables of the profile sweeps (PROFILE): dynamic LDS behind aff_mkey, which those sweeps stage too -- one
+// table per wavefront, prows rows of pnn dwords each (what the launcher sized the workgroup by); a lane's row words are byte offsets
+// from here
+extern __shared__ int aff_ptab[];
 
 // the strip sweeps (LONG): lane 0's feed from above and lane 63's hand-over to the next strip
 struct AffSeam {
@@ -235,7 +248,7 @@ __device__ __forceinline__ void aff_block8(AffState<R> &S, const uint2 rw, const
     for (uint32_t s = 0; s < 8; ++s) {
         const uint32_t wsel = s < 4 ? rw.x : rw.y;
         const uint32_t fb = (wsel >> (8u * (s & 3u))) & 0xFFu;
-        const int feed = MATRIX ? (int)aff_mkey[fb] : (int)fb;  // (wave-uniform: lane 0's column)
+        const int feed = MATRIX || PROFILE ? (int)aff_mkey[fb] : (int)fb;  // (wave-uniform: lane 0's column)
         S.rb = wave_shr1(feed, S.rb);
         int nh, nf;
         int nf2 = 0;                                             // (TWO)
@@ -274,6 +287,9 @@ __device__ __forceinline__ void aff_block8(AffState<R> &S, const uint2 rw, const
                     const uint32_t qk = (uint32_t)S.q[k];
                     const int tv = *reinterpret_cast<const int *>(reinterpret_cast<const char *>(aff_mtab) + ((qk & 0xFFFFu) + rlo));
                     sv = (qk ^ rkey) < 0x10000u ? vmat : tv;
+                } else if (PROFILE) {
+                    // the row's table row at the column of the reference base's class: one LDS read, no select
+                    sv = *reinterpret_cast<const int *>(reinterpret_cast<const char *>(aff_ptab) + ((uint32_t)S.q[k] + rkey));
                 } else {
                     sv = S.rb == S.q[k] ? vmat : vmis;
                 }
@@ -423,6 +439,8 @@ __device__ __forceinline__ AffCells aff_cell_list(const FillArgs &A, const PairD
 //   pad rows: class n, hi 0xFFFF) -- and H and E at column 0: 0 (local), else H(i,0) = o + i*e, E(i,0) := H(i,0) + o
 //   AFF_OVERLAP: H(i,0) = 0 and the same stand-in, E(i,0) := o
 //   TWO: H(i,0) = max(o + i*e, o2 + i*e2), E1(i,0) := H(i,0) + o, E2(i,0) := H(i,0) + o2
+//   PROFILE (expects pbase, pnn): the row words are the byte offsets of the rows' table rows in aff_ptab -- dword pbase + row * pnn;
+//   a pad row points at the read's row 0 (any valid row: it never competes).  The read's bytes are not read
 #define AFF_LOAD_ROWS                                                                                         \
     _Pragma("unroll") for (int k = 0; k < R; ++k) {                                                           \
         const uint32_t row = row0 + (uint32_t)k;                                                              \
@@ -432,6 +450,7 @@ __device__ __forceinline__ AffCells aff_cell_list(const FillArgs &A, const PairD
             const uint32_t hi = (key >> 16) == 0x1FFu ? 0x3FFu : key >> 16;                                   \
             S.q[k] = (int)(((key & 0xFFFFu) * nn) | (hi << 16));                                              \
         }                                                                                                     \
+        if (PROFILE) S.q[k] = (int)((pbase + (row < m ? row : 0u) * pnn) * 4u);                               \
         if constexpr (MODE == AFF_LOCAL) {                                                                    \
             S.h[k] = 0;                                                                                       \
             S.e[k] = 0;                                                                                       \
@@ -505,7 +524,7 @@ __device__ __forceinline__ AffCells aff_cell_list(const FillArgs &A, const PairD
 // ENDB: the bonus endb of option "end_bonus"; the lane that owns read row m tracks it, and the choice is made with the PairOut
 template <int R, bool STRICT, int MODE, uint32_t F>
 __device__ __forceinline__ void aff_sweep_pair(const FillArgs &A, const int o, const PairDesc pd, const uint32_t lane, const uint32_t nn,
-                                               const int o2, const int e2, const uint32_t endb) {
+                                               const int o2, const int e2, const uint32_t endb, const uint32_t *__restrict__ pimg) {
     AFF_FLAG_NAMES(F)
     const SeqDesc rd = A.refs[pd.ref_id];
     const SeqDesc qd = A.reads[pd.read_id];
@@ -519,6 +538,33 @@ __device__ __forceinline__ void aff_sweep_pair(const FillArgs &A, const int o, c
     const AffCells cl = aff_cell_list(A, pd);
     const uint32_t ccap = cl.cap;
     uint2 *__restrict__ cells = cl.p;
+    // PROFILE: nn carries the table's row stride n + 1 (low half) and the rows of a wavefront's table (high half); pimg is the
+    // profiles' image (AffProfile, swmi_launch.h).  The wavefront stages its read's table, m rows, column n filled with mismatch:
+    // entry x = row * pnn + c comes from scores[(row_off + row) * n + c], and x - row is row * n + c.  A read with more rows than
+    // the launcher sized the tables for is not swept (it admits none).  The wavefront reads what its own lanes wrote: LDS
+    // instructions of one wavefront complete in order, and the fence keeps the compiler from moving a read above the writes.
+    [[maybe_unused]] const uint32_t pnn = nn & 0xFFFFu, pbase = (threadIdx.x >> 6) * (nn >> 16) * pnn;
+    if constexpr (PROFILE) {
+        if (m > (nn >> 16)) {                                    // never seen: the run fails (run_chunk reads the word)
+            if (lane == 0 && A.err_host) *A.err_host = 1u;
+            return;
+        }
+        const uint32_t sy = pnn - 1u;
+        const uint64_t soff = *reinterpret_cast<const uint64_t *>(pimg + SWMI_PROF_KEY_WORDS);
+        const uint64_t roff = reinterpret_cast<const uint64_t *>(pimg + SWMI_PROF_HDR_WORDS)[pd.read_id];
+        const int *__restrict__ src = reinterpret_cast<const int *>(pimg) + soff + roff * sy;
+        // (row and column of entry x run along with it: one division per lane, and one for the wavefront's step of 64 entries)
+        const uint32_t rstep = uni(WAVE / pnn), cstep = uni(WAVE - rstep * pnn);
+        uint32_t row = lane / pnn, c = lane - row * pnn;
+        for (uint32_t x = lane; x < m * pnn; x += WAVE) {
+            aff_ptab[pbase + x] = c == sy ? A.mismatch : src[x - row];
+            row += rstep; c += cstep;
+            if (c >= pnn) { c -= pnn; row += 1u; }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    }
 
     AffState<R> S;
     AFF_LOAD_ROWS
@@ -621,6 +667,8 @@ __device__ __forceinline__ void aff_sweep_long_pair(const FillArgs &A, const int
     AFF_FLAG_NAMES(F)
     constexpr int R = SWMI_AFF_RMAX;
     constexpr int OUT = BAND && MODE != AFF_LOCAL ? SWMI_AFF_BAND_NEG : 0;
+    static_assert(!PROFILE, "a long read has no profile sweep: one table per strip is not built");
+    [[maybe_unused]] constexpr uint32_t pbase = 0u, pnn = 0u;    // (names of AFF_LOAD_ROWS under PROFILE)
     const SeqDesc rd = A.refs[pd.ref_id];
     const SeqDesc qd = A.reads[pd.read_id];
     const uint32_t n = rd.len, m = qd.len;
@@ -813,10 +861,11 @@ __device__ __forceinline__ void aff_sweep_long_pair(const FillArgs &A, const int
 // RLO..RHI: the rows per lane this instantiation of the kernel takes (the others' registers would cap its occupancy)
 template <int RLO, int RHI, bool STRICT, int MODE, uint32_t F>
 __device__ __forceinline__ void aff_sweep_dispatch(const FillArgs &A, const int o, const PairDesc pd, const uint32_t R, const uint32_t lane,
-                                                   const uint32_t nn, const int o2, const int e2, const uint32_t endb) {
+                                                   const uint32_t nn, const int o2, const int e2, const uint32_t endb,
+                                                   const uint32_t *__restrict__ pimg) {
     if constexpr (RLO <= RHI) {
-        if (R == (uint32_t)RLO) aff_sweep_pair<RLO, STRICT, MODE, F>(A, o, pd, lane, nn, o2, e2, endb);
-        else aff_sweep_dispatch<RLO + 1, RHI, STRICT, MODE, F>(A, o, pd, R, lane, nn, o2, e2, endb);
+        if (R == (uint32_t)RLO) aff_sweep_pair<RLO, STRICT, MODE, F>(A, o, pd, lane, nn, o2, e2, endb, pimg);
+        else aff_sweep_dispatch<RLO + 1, RHI, STRICT, MODE, F>(A, o, pd, R, lane, nn, o2, e2, endb, pimg);
     }
 }
 
@@ -824,6 +873,8 @@ __device__ __forceinline__ void aff_sweep_dispatch(const FillArgs &A, const int 
 // (TWO) the second piece's open and extension; mat, nn (MATRIX) the score matrix image (swmi_aff_mat_words) and its side n + 1;
 // wb (BAND) the half-width; xd (XDROP) the threshold; endb (ENDB) the bonus.  LONG: RLO and RHI are not used.  Which flags may
 // meet is aff_flags_ok (swmi_launch.h)
+// PROFILE (the rows of AFF_PROFILE_SWEEPS): mat is the profiles' image (AffProfile, swmi_launch.h) and nn is
+// (n + 1) | rows << 16, rows being the rows of one wavefront's LDS table -- what the launcher sized the workgroup by
 template <int RLO, int RHI, int MODE, uint32_t F>
 __device__ __forceinline__ void aff_sweep_entry(const FillArgs &A, const int o, const int o2, const int e2, const uint32_t *__restrict__ mat,
                                                 const uint32_t nn, const uint32_t wb, const uint32_t xd, const uint32_t endb) {
@@ -839,7 +890,13 @@ __device__ __forceinline__ void aff_sweep_entry(const FillArgs &A, const int o, 
         }
         __syncthreads();
     }
-    const uint32_t pair = blockIdx.x * AFF_WAVES + (threadIdx.x >> 6);
+    if constexpr (PROFILE) {
+        // the keys alone are the workgroup's (class * 4, class n outside the alphabet); every wavefront stages its own read's
+        // table (aff_sweep_pair).  The workgroup has as many wavefronts as the launcher gave it, 1 .. AFF_WAVES
+        for (uint32_t x = threadIdx.x; x < SWMI_PROF_KEY_WORDS; x += blockDim.x) aff_mkey[x] = mat[x];
+        __syncthreads();
+    }
+    const uint32_t pair = blockIdx.x * (PROFILE ? blockDim.x >> 6 : (uint32_t)AFF_WAVES) + (threadIdx.x >> 6);
     if (pair >= A.n_pairs) return;
     const uint32_t lane = threadIdx.x & 63u;
     const PairDesc pd = A.pairs[pair];
@@ -851,8 +908,8 @@ __device__ __forceinline__ void aff_sweep_entry(const FillArgs &A, const int o, 
     }
     const uint32_t R = uni(swmi_aff_rows_per_lane(A.reads[pd.read_id].len));
     if (R < (uint32_t)RLO || R > (uint32_t)RHI) return;
-    if (A.strict) aff_sweep_dispatch<RLO, RHI, true, MODE, F>(A, o, pd, R, lane, nn, o2, e2, endb);
-    else          aff_sweep_dispatch<RLO, RHI, false, MODE, F>(A, o, pd, R, lane, nn, o2, e2, endb);
+    if (A.strict) aff_sweep_dispatch<RLO, RHI, true, MODE, F>(A, o, pd, R, lane, nn, o2, e2, endb, mat);
+    else          aff_sweep_dispatch<RLO, RHI, false, MODE, F>(A, o, pd, R, lane, nn, o2, e2, endb, mat);
 }
 
 }  // namespace
@@ -942,12 +999,18 @@ static_assert(SWMI_AFF_RMAX == 16, "the RHI column of the list");
 #define AFF_IF_1(...) __VA_ARGS__
 #define AFF_SEL_0(a, b) b
 #define AFF_SEL_1(a, b) a
+// The MATRIX column of a row of AFF_PROFILE_SWEEPS is 2: the kernel has the matrix sweeps' piece (mat, nn) with the meaning
+// aff_sweep_entry gives it under PROFILE, and its flags word is AFF_F_PROFILE in place of AFF_F_MATRIX
+#define AFF_IF_2(...) __VA_ARGS__
+#define AFF_SEL_2(a, b) a
+#define AFF_ROW_FLAGS(MATRIX, LONG, BAND, XDROP, ADAPT, TWO, SUBOPT, ENDB, HITS)                                                              \
+    (aff_flags((MATRIX) == 1, LONG, BAND, XDROP, ADAPT, TWO, SUBOPT, ENDB, HITS) | ((MATRIX) == 2 ? AFF_F_PROFILE : 0u))
 #define AFF_SWEEP_KERNEL(name, RLO, RHI, MODE, MATRIX, LONG, BAND, XDROP, ADAPT, TWO, SUBOPT, ENDB, HITS)                                    \
-    static_assert(aff_flags_ok(MODE, aff_flags(MATRIX, LONG, BAND, XDROP, ADAPT, TWO, SUBOPT, ENDB, HITS)), #name);                          \
+    static_assert(aff_flags_ok(MODE, AFF_ROW_FLAGS(MATRIX, LONG, BAND, XDROP, ADAPT, TWO, SUBOPT, ENDB, HITS)), #name);                      \
     extern "C" __global__ void __launch_bounds__(WAVE * AFF_WAVES) name(const FillArgs A, const int gap_open                                  \
             AFF_IF_##TWO(, const int gap_open2, const int gap2) AFF_IF_##MATRIX(, const uint32_t *mat, const uint32_t nn)                    \
             AFF_IF_##BAND(, const uint32_t band) AFF_IF_##XDROP(, const uint32_t xdrop) AFF_IF_##ENDB(, const uint32_t end_bonus)) {         \
-        aff_sweep_entry<RLO, RHI, MODE, aff_flags(MATRIX, LONG, BAND, XDROP, ADAPT, TWO, SUBOPT, ENDB, HITS)>(                              \
+        aff_sweep_entry<RLO, RHI, MODE, AFF_ROW_FLAGS(MATRIX, LONG, BAND, XDROP, ADAPT, TWO, SUBOPT, ENDB, HITS)>(                          \
             A, gap_open, AFF_SEL_##TWO(gap_open2, 0), AFF_SEL_##TWO(gap2, 0), AFF_SEL_##MATRIX(mat, nullptr), AFF_SEL_##MATRIX(nn, 0u),      \
             AFF_SEL_##BAND(band, 0u), AFF_SEL_##XDROP(xdrop, 0u), AFF_SEL_##ENDB(end_bonus, 0u));                                            \
     }
@@ -961,6 +1024,21 @@ AFF_SWEEPS(AFF_SWEEP_KERNEL)
     X(sw_affine_sweep_long_overlap_kernel,            16, 16, AFF_OVERLAP, 0, 1, 0, 0, 0, 0, 0, 0, 0) \
     X(sw_affine_sweep_long_overlap_matrix_kernel,     16, 16, AFF_OVERLAP, 1, 1, 0, 0, 0, 0, 0, 0, 0)
 AFF_OVERLAP_SWEEPS(AFF_SWEEP_KERNEL)
+// THE LIST OF PROFILE SWEEPS (swmi_batch_set_read_profiles): the five modes, narrow and wide, with s(i,j) from the
+// read's own table.  A list of its own behind the overlap list, under the same two macros; its rows are in a table of their own
+// (aff_profile_sweeps), which swmi_launch_affine_profile_sweep searches by shape and mode
+#define AFF_PROFILE_SWEEPS(X)                                                                             \
+    X(sw_affine_sweep_profile_kernel,                  1,  4, AFF_LOCAL,   2, 0, 0, 0, 0, 0, 0, 0, 0) \
+    X(sw_affine_sweep_profile_wide_kernel,             5, 16, AFF_LOCAL,   2, 0, 0, 0, 0, 0, 0, 0, 0) \
+    X(sw_affine_sweep_fit_profile_kernel,              1,  4, AFF_FIT,     2, 0, 0, 0, 0, 0, 0, 0, 0) \
+    X(sw_affine_sweep_fit_profile_wide_kernel,         5, 16, AFF_FIT,     2, 0, 0, 0, 0, 0, 0, 0, 0) \
+    X(sw_affine_sweep_global_profile_kernel,           1,  4, AFF_GLOBAL,  2, 0, 0, 0, 0, 0, 0, 0, 0) \
+    X(sw_affine_sweep_global_profile_wide_kernel,      5, 16, AFF_GLOBAL,  2, 0, 0, 0, 0, 0, 0, 0, 0) \
+    X(sw_affine_sweep_extend_profile_kernel,           1,  4, AFF_EXTEND,  2, 0, 0, 0, 0, 0, 0, 0, 0) \
+    X(sw_affine_sweep_extend_profile_wide_kernel,      5, 16, AFF_EXTEND,  2, 0, 0, 0, 0, 0, 0, 0, 0) \
+    X(sw_affine_sweep_overlap_profile_kernel,          1,  4, AFF_OVERLAP, 2, 0, 0, 0, 0, 0, 0, 0, 0) \
+    X(sw_affine_sweep_overlap_profile_wide_kernel,     5, 16, AFF_OVERLAP, 2, 0, 0, 0, 0, 0, 0, 0, 0)
+AFF_PROFILE_SWEEPS(AFF_SWEEP_KERNEL)
 #undef AFF_SWEEP_KERNEL
 
 // ------------------------------------------------------------------------------------------------
@@ -1223,16 +1301,20 @@ static_assert(AFF_OVERLAP == 4, "AffRun.mode 4 is the overlap run");
 namespace {
 struct AffSweepRow {
     uint32_t key;
-    void (*launch)(const FillArgs &a, const AffRun &r, dim3 grid, hipStream_t st);
+    void (*launch)(const FillArgs &a, const AffRun &r, dim3 grid, uint32_t waves, size_t lds, hipStream_t st);
     const char *name;
+    const void *kernel;          // for swmi_allow_big_lds (the profile sweeps)
 };
+// (waves, lds: the wavefronts of a workgroup and its dynamic LDS -- AFF_WAVES and none but for the profile sweeps; the key of a
+// profile row is that of the plain sweep of its shape and mode: AFF_F_PROFILE is no part of a key, and the row is in its own table)
 #define AFF_SWEEP_ROW(name, RLO, RHI, MODE, MATRIX, LONG, BAND, XDROP, ADAPT, TWO, SUBOPT, ENDB, HITS)                               \
-    {aff_key(LONG ? 2u : RLO == 1 ? 0u : 1u, MODE, aff_flags(MATRIX, LONG, BAND, XDROP, ADAPT, TWO, SUBOPT, ENDB, HITS)),            \
-     [](const FillArgs &a, const AffRun &r, dim3 grid, hipStream_t st) {                                                             \
-         hipLaunchKernelGGL(name, grid, dim3(WAVE * AFF_WAVES), 0, st, a, (int)r.gap_open AFF_IF_##TWO(, (int)r.gap_open2, (int)r.gap2) \
+    {aff_key(LONG ? 2u : RLO == 1 ? 0u : 1u, MODE, aff_flags((MATRIX) == 1, LONG, BAND, XDROP, ADAPT, TWO, SUBOPT, ENDB, HITS)),     \
+     [](const FillArgs &a, const AffRun &r, dim3 grid, uint32_t waves, size_t lds, hipStream_t st) {                                 \
+         hipLaunchKernelGGL(name, grid, dim3(WAVE * waves), lds, st, a, (int)r.gap_open AFF_IF_##TWO(, (int)r.gap_open2, (int)r.gap2) \
                             AFF_IF_##MATRIX(, r.mat, r.nn) AFF_IF_##BAND(, r.band) AFF_IF_##XDROP(, r.xdrop) AFF_IF_##ENDB(, r.end_bonus)); \
-     }, #name},
+     }, #name, reinterpret_cast<const void *>(name)},
 const AffSweepRow aff_sweeps[] = {AFF_SWEEPS(AFF_SWEEP_ROW) AFF_OVERLAP_SWEEPS(AFF_SWEEP_ROW)};
+const AffSweepRow aff_profile_sweeps[] = {AFF_PROFILE_SWEEPS(AFF_SWEEP_ROW)};
 #undef AFF_SWEEP_ROW
 
 struct AffTracebackRow {
@@ -1256,6 +1338,16 @@ const AffSweepRow *aff_sweep_row(const AffRun &r, uint32_t long_reads, uint32_t 
     if (!aff_run_ok(r, long_reads)) return nullptr;
     const uint32_t key = aff_key(shape, r.mode, aff_run_flags(r, long_reads));
     for (const AffSweepRow &row : aff_sweeps) if (row.key == key) return &row;
+    return nullptr;
+}
+// The profile sweep of a run whose batch has profiles: the plain one-piece run of a short shape in any of the five
+// modes -- no score matrix, none of gap_open2, subopt, hits and end_bonus.  band, xdrop and band_adapt are the long shape's and do
+// not count here, as for every short sweep.
+const AffSweepRow *aff_profile_sweep_row(const AffRun &r, uint32_t shape) {
+    if (!aff_run_ok(r, 0u) || shape > 1u) return nullptr;
+    if (r.mat || r.gap_open2 || r.subopt || r.hits || r.end_bonus) return nullptr;
+    const uint32_t key = aff_key(shape, r.mode, 0u);
+    for (const AffSweepRow &row : aff_profile_sweeps) if (row.key == key) return &row;
     return nullptr;
 }
 const AffTracebackRow *aff_traceback_row(const AffRun &r, uint32_t long_reads) {
@@ -1285,12 +1377,52 @@ extern "C" hipError_t swmi_launch_affine_sweep(const FillArgs *a, const AffRun *
     const dim3 grid((a->n_pairs + AFF_WAVES - 1) / AFF_WAVES);
     const auto sweep = [&](uint32_t shape) {
         const AffSweepRow *row = aff_sweep_row(*r, long_reads, shape);
-        if (row) row->launch(*a, *r, grid, st);
+        if (row) row->launch(*a, *r, grid, AFF_WAVES, 0, st);
         return row != nullptr;
     };
     // the short shape: the narrow and the wide sweep, each only if the launch has pairs for it
     const bool ok = long_reads ? sweep(2u) : (r_min > 4u || sweep(0u)) && (r_max < 5u || sweep(1u));
     return ok ? hipGetLastError() : hipErrorInvalidValue;      // (a launch's own error is what hipGetLastError returns)
+}
+
+extern "C" const char *swmi_affine_profile_sweep_name(const AffRun *r, uint32_t shape) {
+    const AffSweepRow *row = aff_profile_sweep_row(*r, shape);
+    return row ? row->name : nullptr;
+}
+
+// A wavefront's table has `rows` rows of n + 1 dwords, rows = 64 * the rows per lane of the longest read the kernel takes in this
+// launch (the narrow sweep: at most 4); a workgroup gets as many wavefronts, at most AFF_WAVES, as tables fit the LDS beside the
+// 1 KiB of keys.  One table must fit: rows * (n + 1) <= SWMI_PROF_LDS_WORDS, which check_run_params (swmi_run.cpp) has made sure of.
+extern "C" hipError_t swmi_launch_affine_profile_sweep(const FillArgs *a, const AffRun *r, const AffProfile *p, uint32_t r_min, uint32_t r_max,
+                                                       hipStream_t st) {
+    if (a->n_pairs == 0) return hipSuccess;
+    if (!p || !p->image || p->n < 1u || p->n > SWMI_MAT_MAX_SYMBOLS || r_max < 1u || r_max > SWMI_AFF_RMAX) return hipErrorInvalidValue;
+    // (the dynamic LDS a profile sweep may ask for: the CU's less the kernel's own static 1 KiB of keys -- swmi_allow_big_lds asks
+    // for all of it, which a kernel with static LDS is refused)
+    static const hipError_t attrs = [] {
+        hipError_t e = hipSuccess;
+        for (const AffSweepRow &s : aff_profile_sweeps) {
+            const hipError_t x = hipFuncSetAttribute(s.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(SWMI_LDS_BYTES - 4u * SWMI_PROF_KEY_WORDS));
+            if (x != hipSuccess) e = x;
+        }
+        return e;
+    }();
+    if (attrs != hipSuccess) return attrs;
+    const uint32_t nn = p->n + 1u;
+    const auto sweep = [&](uint32_t shape) {
+        const AffSweepRow *row = aff_profile_sweep_row(*r, shape);
+        const uint32_t rows = WAVE * (shape == 0u ? std::min(r_max, 4u) : r_max);
+        const uint32_t tab_words = rows * nn;
+        if (!row || tab_words > SWMI_PROF_LDS_WORDS) return false;
+        const uint32_t waves = std::min<uint32_t>(AFF_WAVES, (SWMI_LDS_BYTES - 4u * SWMI_PROF_KEY_WORDS) / (4u * tab_words));
+        AffRun pr = *r;
+        pr.mat = p->image;
+        pr.nn = nn | rows << 16;
+        row->launch(*a, pr, dim3((a->n_pairs + waves - 1u) / waves), waves, (size_t)waves * tab_words * 4u, st);
+        return true;
+    };
+    const bool ok = (r_min > 4u || sweep(0u)) && (r_max < 5u || sweep(1u));
+    return ok ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 extern "C" hipError_t swmi_launch_affine_traceback(const TraceArgs *a, const AffRun *r, uint32_t long_reads, uint32_t tile_words,

@@ -223,6 +223,21 @@ extern "C" int swmi_set_option(swmi_ctx *ctx, const char *name, int64_t value) {
     return SWMI_OK;
 }
 
+// The classes of an alphabet of n symbols by canonical code (a score matrix's, a batch's profiles'): cls[code] = the symbol's index,
+// n for a code outside the alphabet.  Two symbols with one code are refused.
+static int alphabet_classes(const uint8_t *alphabet, uint32_t n, const char *what, uint32_t cls[256]) {
+    const uint8_t *T = code_table();
+    for (uint32_t c = 0; c < 256; c++) cls[c] = n;         // class n: outside the alphabet
+    for (uint32_t i = 0; i < n; i++) {
+        const uint8_t c = T[alphabet[i]];
+        if (cls[c] != n)
+            return fail(SWMI_ERR_INVALID, "%s symbols %u and %u are the same symbol (0x%02x, 0x%02x)", what, cls[c], i,
+                        alphabet[cls[c]], alphabet[i]);
+        cls[c] = i;
+    }
+    return SWMI_OK;
+}
+
 extern "C" int swmi_set_score_matrix(swmi_ctx *ctx, const uint8_t *alphabet, uint32_t n, const int32_t *scores) {
     if (!ctx) return fail(SWMI_ERR_INVALID, "null context");
     if (n == 0) {                                          // clears the matrix
@@ -232,16 +247,8 @@ extern "C" int swmi_set_score_matrix(swmi_ctx *ctx, const uint8_t *alphabet, uin
     }
     if (n > SWMI_MAT_MAX_SYMBOLS) return fail(SWMI_ERR_INVALID, "a score matrix has at most %u symbols, got %u", SWMI_MAT_MAX_SYMBOLS, n);
     if (!alphabet || !scores) return fail(SWMI_ERR_INVALID, "alphabet or scores is null");
-    const uint8_t *T = code_table();
     uint32_t cls[256];
-    for (uint32_t c = 0; c < 256; c++) cls[c] = n;         // class n: outside the alphabet
-    for (uint32_t i = 0; i < n; i++) {
-        const uint8_t c = T[alphabet[i]];
-        if (cls[c] != n)
-            return fail(SWMI_ERR_INVALID, "score matrix symbols %u and %u are the same symbol (0x%02x, 0x%02x)", cls[c], i,
-                        alphabet[cls[c]], alphabet[i]);
-        cls[c] = i;
-    }
+    if (int rc = alphabet_classes(alphabet, n, "score matrix", cls)) return rc;
     auto M = std::make_shared<ScoreMatrix>();
     M->n = n;
     M->max_entry = INT32_MIN;
@@ -328,7 +335,7 @@ extern "C" void swmi_batch_free(swmi_ctx *ctx, swmi_batch *b) {
     b->d_dir.release(); b->d_seam.release(); b->d_result.release(); b->d_cells.release();
     b->d_cells_off.release(); b->d_cells_cap.release(); b->d_dbg.release(); b->d_dbg2.release();
     b->d_strip_items.release(); b->d_progress.release(); b->d_col_items.release(); b->d_win_off.release(); b->d_queue.release(); b->d_res_items.release();
-    b->d_tf_items.release(); b->d_mat.release();
+    b->d_tf_items.release(); b->d_mat.release(); b->d_prof.release();
     b->h_result.release();
     delete b;
 }
@@ -551,5 +558,52 @@ extern "C" int swmi_batch_pair_spec(const swmi_batch *b, uint64_t pair, swmi_pai
     if (!b->paired) return fail(SWMI_ERR_INVALID, "the batch is a cross product (swmi_batch_upload): its pairs have no spec");
     if (pair >= b->specs.size()) return fail(SWMI_ERR_RANGE, "pair %llu out of range", (unsigned long long)pair);
     *spec = b->specs[pair];
+    return SWMI_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// per-read score profiles (swmi.h: swmi_batch_set_read_profiles)
+// ------------------------------------------------------------------------------------------
+// Builds the immutable ReadProfiles with its device image (AffProfile, swmi_launch.h) and hands it to the batch; the run uploads it.
+// Everything that can be refused is refused before the batch is touched.
+extern "C" int swmi_batch_set_read_profiles(swmi_ctx *ctx, swmi_batch *b, const uint8_t *alphabet, uint32_t n, const int32_t *scores) {
+    if (!ctx || !b) return fail(SWMI_ERR_INVALID, "null argument");
+    if (b->paired)
+        return fail(SWMI_ERR_UNSUPPORTED, "read profiles on a pair list (swmi_batch_upload_pairs) are not supported: a segment would need its rows cut, "
+                    "and the minus strand complemented columns");
+    std::shared_ptr<const ReadProfiles> next;
+    if (n != 0) {
+        if (n > SWMI_MAT_MAX_SYMBOLS) return fail(SWMI_ERR_INVALID, "read profiles have at most %u symbols, got %u", SWMI_MAT_MAX_SYMBOLS, n);
+        if (!alphabet || !scores) return fail(SWMI_ERR_INVALID, "alphabet or scores is null");
+        uint32_t cls[256];
+        if (int rc = alphabet_classes(alphabet, n, "read profile", cls)) return rc;
+        const uint64_t rows = b->read_off[b->n_reads], entries = rows * n;
+        auto P = std::make_shared<ReadProfiles>();
+        P->n = n;
+        P->max_entry = INT32_MIN;
+        for (uint64_t x = 0; x < entries; x++) {
+            if (std::llabs((int64_t)scores[x]) > (1 << 20))
+                return fail(SWMI_ERR_INVALID, "read profile entry [row %llu][%u] = %d: |entries| must be <= 2^20", (unsigned long long)(x / n),
+                            (uint32_t)(x % n), scores[x]);
+            P->max_entry = std::max(P->max_entry, scores[x]);
+            P->max_abs = std::max(P->max_abs, (int32_t)std::llabs((int64_t)scores[x]));
+        }
+        if (entries == 0) P->max_entry = 0;
+        const uint64_t soff = ((uint64_t)SWMI_PROF_HDR_WORDS + 2ull * b->n_reads + 1u) & ~1ull;
+        P->image.assign(soff + entries, 0u);
+        for (uint32_t c = 0; c < 256; c++) P->image[c] = cls[c] * 4u;
+        memcpy(&P->image[SWMI_PROF_KEY_WORDS], &soff, 8);
+        if (b->n_reads) memcpy(&P->image[SWMI_PROF_HDR_WORDS], b->read_off.data(), (size_t)b->n_reads * 8);
+        if (entries) memcpy(&P->image[soff], scores, entries * 4);
+        static std::atomic<uint64_t> gens{0};
+        P->gen = ++gens;
+        next = std::move(P);
+    }
+    std::lock_guard<std::mutex> g(ctx->mu);             // (serialised with the runs of the context, as swmi_batch_set_pairs is)
+    { std::lock_guard<std::mutex> gm(ctx->mat_mu); b->profiles = std::move(next); }
+    // the old results are dropped: the batch is to be run again
+    b->has_run = false;
+    b->pairs.clear(); b->alns.clear(); b->str_at.clear(); b->str_buf.clear(); b->raw.clear(); b->rtab.clear(); b->raw_chunks.clear();
+    b->raw_ext = nullptr; b->rtab_ext = nullptr; b->indexed = false; b->win_tab.clear(); b->win_at.clear();
     return SWMI_OK;
 }

@@ -129,6 +129,16 @@ struct ScoreMatrix {
     std::vector<uint32_t> image;            // the device image: swmi_aff_mat_words(n + 1) dwords (swmi_device.h)
 };
 
+// The per-read score profiles of a batch (swmi_batch_set_read_profiles), immutable once built and held by shared_ptr
+// as a ScoreMatrix is: the batch keeps the current ones, a run takes those set when it was asked for.
+struct ReadProfiles {
+    uint64_t gen = 0;                       // unique per set (the plan cache and the batch's device copy key on it)
+    uint32_t n = 0;                         // symbols
+    int32_t max_entry = 0;                  // the largest entry (path_bound)
+    int32_t max_abs = 0;                    // the largest |entry| (S of the affine bounds)
+    std::vector<uint32_t> image;            // the device image (AffProfile, swmi_launch.h): keys, the reads' first rows, the scores
+};
+
 // What a run takes as the context has it WHEN THE RUN IS ASKED FOR: swmi_batch_run_async records it at the call, a stream's
 // slots copy it at swmi_stream_open.  The context holds the plain part, RunModes, the plan key embeds it and every hand-over
 // copies it whole: a new option of this kind is a new member, its setter, its checks and its consumer.  (gap_open and affine
@@ -185,6 +195,7 @@ struct __attribute__((visibility("hidden"))) SchedKey {
 struct __attribute__((visibility("hidden"))) RunOptions {
     RunModes modes;
     std::shared_ptr<const ScoreMatrix> mat; // swmi_set_score_matrix (null: none); keeps the matrix's host image alive
+    std::shared_ptr<const ReadProfiles> prof;   // the BATCH's profiles (null: none), taken with the context's options (run_options)
 };
 
 // ------------------------------------------------------------------------------------------
@@ -243,12 +254,6 @@ struct swmi_ctx {
     std::string job_err;
 };
 
-// the context's run options as set now (in the header: every swmi_batch_run takes them, and no per-step call may cross a unit boundary)
-static inline RunOptions run_options(swmi_ctx *ctx) {
-    std::lock_guard<std::mutex> g(ctx->mat_mu);
-    return RunOptions{ctx->modes, ctx->matrix};
-}
-
 // one alignment as parsed from the arena
 struct HostAln {
     uint32_t rank;
@@ -293,13 +298,14 @@ struct __attribute__((visibility("hidden"))) PlanKey {
     bool exact = false;                     // the exact-size re-run: no resident, no tfused pairs
     bool scores_only = false;
     uint64_t mat_gen = 0;                   // the score matrix's generation (0: none): it bounds the paths (not the matrix: a key keeps none alive)
+    uint64_t prof_gen = 0;                  // the batch's profiles' generation (0: none), for the same reason
     RunModes modes;                         // the run's modes: the alignment mode bounds the paths too
     const void *d_pairs = nullptr;          // where the chunk's PairDesc image sits on the device, and its size
     size_t pairs_bytes = 0;
     bool operator==(const PlanKey &o) const {
         return valid == o.valid && lo == o.lo && hi == o.hi && work == o.work && memcmp(&params, &o.params, sizeof(swmi_params)) == 0 &&
                eff_mode == o.eff_mode && col_chunks == o.col_chunks && reverse_strips == o.reverse_strips && resident == o.resident &&
-               tfused == o.tfused && exact == o.exact && scores_only == o.scores_only && mat_gen == o.mat_gen &&
+               tfused == o.tfused && exact == o.exact && scores_only == o.scores_only && mat_gen == o.mat_gen && prof_gen == o.prof_gen &&
                modes == o.modes && d_pairs == o.d_pairs && pairs_bytes == o.pairs_bytes;
     }
 };
@@ -365,6 +371,9 @@ struct swmi_batch {
     RunOptions opt;                         // the context's run options when the run was asked for (mode 3)
     DevBuf d_mat;                           // the device image of opt.mat, copied on the run's stream
     uint64_t d_mat_gen = 0;                 // generation of the matrix in d_mat (0: none)
+    std::shared_ptr<const ReadProfiles> profiles;   // swmi_batch_set_read_profiles (null: none); guarded by the context's mat_mu
+    DevBuf d_prof;                          // the device image of opt.prof, copied on the run's stream
+    uint64_t d_prof_gen = 0;                // generation of the profiles in d_prof (0: none)
     uint64_t work_cells = 0;
     std::vector<uint8_t> pairs_on_device;   // image of the PairDesc array currently in d_pairs
     const void *pairs_dev_ptr = nullptr;
@@ -406,6 +415,13 @@ struct swmi_batch {
     std::vector<uint64_t> ref_degenerate;   // leading (0,"","") sites per ref
     swmi_timing timing{};
 };
+
+// the run options of a run of batch b: the context's as set now, and the batch's profiles as set now (b null: the context's alone)
+// (in the header: every swmi_batch_run takes them, and no per-step call may cross a unit boundary)
+static inline RunOptions run_options(swmi_ctx *ctx, const swmi_batch *b) {
+    std::lock_guard<std::mutex> g(ctx->mat_mu);
+    return RunOptions{ctx->modes, ctx->matrix, b ? b->profiles : nullptr};
+}
 
 // Which sequences a pair is made of: the cross product's division, or the identity of a pair list.  Every place that turns a
 // pair index into its two sequences goes through these two.

@@ -38,7 +38,11 @@ struct AffRun {
 // template argument of the device functions there and, with the mode and the shape, the key a launcher finds a kernel by.
 enum : uint32_t {
     AFF_F_MATRIX = 1u << 0, AFF_F_LONG = 1u << 1, AFF_F_BAND = 1u << 2, AFF_F_XDROP = 1u << 3, AFF_F_ADAPT = 1u << 4,
-    AFF_F_TWO = 1u << 5, AFF_F_SUBOPT = 1u << 6, AFF_F_ENDB = 1u << 7, AFF_F_HITS = 1u << 8
+    AFF_F_TWO = 1u << 5, AFF_F_SUBOPT = 1u << 6, AFF_F_ENDB = 1u << 7, AFF_F_HITS = 1u << 8,
+    // per-read score profiles (swmi_batch_set_read_profiles): a bit of the device templates' flags word alone.  It is
+    // no argument of aff_flags and no part of a key -- aff_key has no free bit below the mode -- so the profile sweeps have a table
+    // and a launcher of their own, keyed by shape and mode.
+    AFF_F_PROFILE = 1u << 16
 };
 constexpr uint32_t aff_flags(bool matrix, bool lng, bool band, bool xdrop, bool adapt, bool two, bool subopt, bool endb, bool hits) {
     return (matrix ? AFF_F_MATRIX : 0u) | (lng ? AFF_F_LONG : 0u) | (band ? AFF_F_BAND : 0u) | (xdrop ? AFF_F_XDROP : 0u) |
@@ -52,6 +56,7 @@ constexpr uint32_t aff_key(uint32_t shape, uint32_t mode, uint32_t flags) { retu
 constexpr bool aff_flags_ok(uint32_t mode, uint32_t f) {
     const bool xdrop_or_adapt = f & (AFF_F_XDROP | AFF_F_ADAPT);
     if (mode > 4u) return false;
+    if (f & AFF_F_PROFILE) return f == AFF_F_PROFILE;                                    // profiles: the five short one-piece sweeps, nothing else
     if (mode == 4u) return !(f & ~(AFF_F_MATRIX | AFF_F_LONG));                          // overlap: a score matrix and long reads, nothing else
     if ((f & AFF_F_BAND) && !(f & AFF_F_LONG)) return false;                             // band: the strip sweeps
     if ((f & AFF_F_XDROP) && !((f & AFF_F_LONG) && mode == 3u)) return false;            // xdrop: the strip sweeps of an extend run
@@ -85,6 +90,28 @@ static inline bool aff_run_ok(const AffRun &r, uint32_t long_reads) {
 extern "C" int swmi_affine_run_ok(const AffRun *r, uint32_t long_reads);
 extern "C" const char *swmi_affine_sweep_name(const AffRun *r, uint32_t long_reads, uint32_t shape);
 extern "C" const char *swmi_affine_traceback_name(const AffRun *r, uint32_t long_reads);
+// Per-read score profiles (swmi_batch_set_read_profiles): the device image of a batch's profiles.
+//   dwords 0 .. 255     key[code] = class(code) * 4, class n for a code outside the alphabet
+//   dwords 256, 257     where the scores start, in dwords from the image's start (64 bits)
+//   from dword 258      row_off[read], 64 bits each: the read's first row = its first byte in upload order
+//   then                the scores as the caller gave them, n int32 per row
+struct AffProfile {
+    const uint32_t *image;
+    uint32_t n;                  // symbols, 1 .. SWMI_MAT_MAX_SYMBOLS
+};
+#define SWMI_PROF_KEY_WORDS 256u
+#define SWMI_PROF_HDR_WORDS 258u
+// The LDS bound of a profile run (swmi.h): with m the longest read and M = 64 * ceil(m / 64), M * (n + 1) <= 32768 dwords -- one
+// wavefront's table, 128 KiB, beside the 1 KiB of keys.
+#define SWMI_PROF_LDS_WORDS 32768u
+// The profile sweep a run takes, by name -- null where the launcher below refuses: a run with gap_open2, subopt, hits, end_bonus or
+// a score matrix, and the long shape (shape: 0 narrow, 1 wide).  It calls no HIP function.  For the tests: not part of include/swmi.h.
+extern "C" const char *swmi_affine_profile_sweep_name(const AffRun *r, uint32_t shape);
+// The short shape of a run whose batch has profiles, in place of swmi_launch_affine_sweep (.., 0, ..); r->mat is null.  Every
+// wavefront stages its own read's table, so a workgroup has as many wavefronts (1 .. 4) as tables of the launch's longest read fit
+// the LDS.  The walks are the run's ordinary ones.
+extern "C" hipError_t swmi_launch_affine_profile_sweep(const FillArgs *a, const AffRun *r, const AffProfile *p, uint32_t r_min, uint32_t r_max,
+                                                       hipStream_t st);
 // long_reads 0: the pairs with reads of at most SWMI_AFF_MAX_READ bases; r_min / r_max: the rows per lane of the launch's shortest
 // and longest read (the narrow and the wide sweep: only the one that has pairs is launched).  long_reads 1: the strip kernels.
 extern "C" hipError_t swmi_launch_affine_sweep(const FillArgs *a, const AffRun *r, uint32_t long_reads, uint32_t r_min, uint32_t r_max,

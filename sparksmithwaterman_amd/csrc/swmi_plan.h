@@ -276,7 +276,9 @@ static int plan_chunk(swmi_ctx *ctx, swmi_batch *b, const std::vector<Work> &wor
     if (b->eff_mode == 1) it.win_off.resize(np + 1);
     uint32_t pb_m = 0xFFFFFFFFu, pb_n = 0xFFFFFFFFu, pb_val = 0;
     // (a score matrix entry above match lets a positive path run longer: the bound takes the largest score of one move)
-    const int32_t smax = b->opt.mat ? std::max(b->params.match, b->opt.mat->max_entry) : b->params.match;
+    // (the batch's profiles likewise: their largest entry)
+    const int32_t smax = b->opt.mat ? std::max(b->params.match, b->opt.mat->max_entry)
+                       : b->opt.prof ? std::max(b->params.match, b->opt.prof->max_entry) : b->params.match;
     for (size_t k = 0; k < np; k++) {
         const Work &w = work[lo + k];
         PairDesc d{};
@@ -359,6 +361,7 @@ static int prepare_chunk(RunState &rs, const std::vector<Work> &work, size_t lo,
     key.resident = ctx->resident; key.tfused = ctx->tfused;
     key.exact = cells_exact != nullptr; key.scores_only = ctx->scores_only != 0;
     key.mat_gen = b->opt.mat ? b->opt.mat->gen : 0u; key.modes = b->opt.modes;
+    key.prof_gen = b->opt.prof ? b->opt.prof->gen : 0u;
     key.d_pairs = b->d_pairs.p; key.pairs_bytes = np * sizeof(PairDesc);
     auto p1 = p0;
     if (key == b->plan_key) {

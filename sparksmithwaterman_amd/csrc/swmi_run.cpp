@@ -290,6 +290,11 @@ static int enqueue_launches(RunState &rs, Launch &L, const ResidentArgs &xa, con
             fs.n_pairs = (uint32_t)(np - plan.aff_n_long);
             fl.n_pairs = (uint32_t)plan.aff_n_long; fl.pairs = fa.pairs + fs.n_pairs;
             // (options "band", "xdrop" and "band_adapt" are the strip kernels': the other pairs take the kernels they take without them)
+            if (b->opt.prof) {
+                // the batch has profiles: the profile sweeps, through their own launcher; such a run has no long pairs
+                const AffProfile ap{b->d_prof.as<uint32_t>(), b->opt.prof->n};
+                HIP_TRY(swmi_launch_affine_profile_sweep(&fs, &ar, &ap, plan.aff_r_min, plan.aff_r_max, ctx->stream));
+            } else
             HIP_TRY(swmi_launch_affine_sweep(&fs, &ar, 0u, plan.aff_r_min, plan.aff_r_max, ctx->stream));
             HIP_TRY(swmi_launch_affine_sweep(&fl, &ar, 1u, 0u, 0u, ctx->stream));
         }
@@ -700,6 +705,26 @@ static int check_run_params(const swmi_ctx *ctx, const swmi_batch *b, const swmi
         if (md.band_adapt) return fail(SWMI_ERR_UNSUPPORTED, "end_bonus = %d: the to-end score under band_adapt is not supported", md.end_bonus);
         if (md.two_piece()) return fail(SWMI_ERR_UNSUPPORTED, "end_bonus = %d: the to-end score with two-piece gaps (gap_open2) is not supported", md.end_bonus);
     }
+    // The batch's per-read profiles (swmi_batch_set_read_profiles): built for the one-piece sweeps of reads of at
+    // most 1024 bases in the five modes, with one table per wavefront in LDS
+    const ReadProfiles *prof = opt.prof.get();
+    if (prof) {
+        if (mat) return fail(SWMI_ERR_UNSUPPORTED, "read profiles (%u symbols) with a score matrix (%u symbols) set on the context are not supported: "
+                             "clear one of them", prof->n, mat->n);
+        const struct { const char *name; int value; } no[] = {{"gap_open2", md.gap_open2}, {"subopt", md.subopt}, {"hits", md.hits}, {"end_bonus", md.end_bonus}};
+        for (const auto &x : no)
+            if (x.value != 0) return fail(SWMI_ERR_UNSUPPORTED, "read profiles (%u symbols) with %s = %d are not supported", prof->n, x.name, x.value);
+        uint64_t pm, pn;
+        longest_sequences(b, pm, pn);
+        if (pm > SWMI_AFF_MAX_READ)
+            return fail(SWMI_ERR_UNSUPPORTED, "read profiles (%u symbols): the longest read has %llu bases (at most %u: a longer read needs one table per strip)",
+                        prof->n, (unsigned long long)pm, SWMI_AFF_MAX_READ);
+        const uint64_t M = 64 * ((pm + 63) / 64);
+        if (M * (prof->n + 1u) > SWMI_PROF_LDS_WORDS)
+            return fail(SWMI_ERR_UNSUPPORTED, "read profiles (%u symbols): the longest read (%llu bases) needs a table of %llu * %u = %llu entries in LDS "
+                        "(at most %u)", prof->n, (unsigned long long)pm, (unsigned long long)M, prof->n + 1u, (unsigned long long)(M * (prof->n + 1u)),
+                        SWMI_PROF_LDS_WORDS);
+    }
     if (p->tie_mode != SWMI_TIE_SERIAL && p->tie_mode != SWMI_TIE_STRICT)
         return fail(SWMI_ERR_INVALID, "unknown tie_mode %d", p->tie_mode);
     // GetAlignment tests `align == alignTypes[0]`, then `== alignTypes[1]`, else deletion
@@ -754,6 +779,7 @@ static int check_run_params(const swmi_ctx *ctx, const swmi_batch *b, const swmi
             S = std::max<int64_t>(S, std::max<int64_t>(std::llabs(o2), std::llabs(e2)));
             if (mat)
                 for (size_t x = 256; x < mat->image.size(); x++) S = std::max<int64_t>(S, std::llabs((int64_t)(int32_t)mat->image[x]));
+            if (prof) S = std::max<int64_t>(S, prof->max_abs);
             if ((int64_t)rows * S > ((int64_t)1 << 30))
                 return fail(SWMI_ERR_UNSUPPORTED, "long_reads: the longest read (%llu bases) is swept as %llu rows, and %llu * %lld (the largest "
                             "|score|) is above 2^30", (unsigned long long)max_m, (unsigned long long)rows, (unsigned long long)rows, (long long)S);
@@ -967,7 +993,7 @@ static int batch_run(swmi_ctx *ctx, swmi_batch *b, const swmi_params *p, RunOpti
     // (a score matrix and the end-to-end modes run on the affine kernels only)
     // (... and so do a band, a CIGAR payload and the second-best score)
     const bool affine = ctx->affine == 1 || ctx->gap_open != 0 || opt.mat != nullptr || opt.modes.align_mode != SWMI_ALIGN_LOCAL || opt.modes.band > 0 ||
-                        opt.modes.cigar != 0 || opt.modes.subopt != 0;
+                        opt.modes.cigar != 0 || opt.modes.subopt != 0 || opt.prof != nullptr;      // (... and the batch's profiles)
     int rc;
     if ((rc = check_run_params(ctx, b, p, affine, opt))) return rc;
     static const bool host_dbg = getenv("SWMI_DEBUG_HOST") != nullptr;
@@ -1014,6 +1040,14 @@ static int batch_run(swmi_ctx *ctx, swmi_batch *b, const swmi_params *p, RunOpti
         HIP_TRY(hipMemcpyAsync(b->d_mat.p, b->opt.mat->image.data(), b->opt.mat->image.size() * 4, hipMemcpyHostToDevice, ctx->stream));
         HIP_TRY(hipStreamSynchronize(ctx->stream));
         b->d_mat_gen = b->opt.mat->gen;
+    }
+    if (b->opt.prof && b->d_prof_gen != b->opt.prof->gen) {
+        // the batch's profiles, likewise: the run's own device copy, complete before the run goes on, only when they changed
+        if ((rc = b->d_prof.reserve(b->opt.prof->image.size() * 4))) return rc;
+        b->d_prof_gen = 0;
+        HIP_TRY(hipMemcpyAsync(b->d_prof.p, b->opt.prof->image.data(), b->opt.prof->image.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        b->d_prof_gen = b->opt.prof->gen;
     }
     if ((rc = choose_traceback_grain(ctx, b, p))) return rc;
     if (b->eff_mode == 0) {
@@ -1071,7 +1105,7 @@ static int batch_run(swmi_ctx *ctx, swmi_batch *b, const swmi_params *p, RunOpti
 
 extern "C" int swmi_batch_run(swmi_ctx *ctx, swmi_batch *b, const swmi_params *p) {
     if (!ctx || !b || !p) return fail(SWMI_ERR_INVALID, "null argument");
-    return batch_run(ctx, b, p, run_options(ctx));
+    return batch_run(ctx, b, p, run_options(ctx, b));
 }
 
 // ---- asynchronous run: the same swmi_batch_run on the context's own host thread -------------------------------
@@ -1105,7 +1139,7 @@ extern "C" int swmi_batch_run_async(swmi_ctx *ctx, swmi_batch *b, const swmi_par
     if (!ctx->worker.joinable()) ctx->worker = std::thread(swmi_worker_loop, ctx);
     ctx->job_batch = b;
     ctx->job_params = *p;
-    ctx->job_opt = run_options(ctx);                   // (what is set now, whatever is set while the run is in flight)
+    ctx->job_opt = run_options(ctx, b);                 // (what is set now, whatever is set while the run is in flight)
     ctx->job_delay_us = ctx->dbg_async_delay_us;
     { std::lock_guard<std::mutex> lk(ctx->job_mu); ctx->job_state.store(1, std::memory_order_release); }
     ctx->job_cv.notify_all();

@@ -191,7 +191,7 @@ extern "C" int swmi_stream_open(swmi_ctx *ctx, const swmi_params *p, const uint8
         sl.ctx->auto_ties_x100 = ctx->auto_ties_x100; sl.ctx->arena_words_per_pair = ctx->arena_words_per_pair;
         sl.ctx->device_strings = ctx->device_strings; sl.ctx->scores_only = ctx->scores_only;
         sl.ctx->gap_open = ctx->gap_open; sl.ctx->affine = ctx->affine;
-        sl.ctx->modes = ctx->modes; sl.ctx->matrix = run_options(ctx).mat;
+        sl.ctx->modes = ctx->modes; sl.ctx->matrix = run_options(ctx, nullptr).mat;
         sl.ctx->spin_us = 50;                    // (a chunk takes milliseconds: the slot threads mostly block)
         sl.shell = new swmi_batch;
     }

@@ -91,6 +91,45 @@ def uniform(alphabet, match, mismatch):
     return ScoreMatrix(sym, tuple(tuple(match if i == j else mismatch for j in range(len(sym))) for i in range(len(sym))))
 
 
+def profile_from_matrix(read, alphabet, scores, default):
+    """The per-read profile (Batch.set_read_profiles) that scores as the matrix does: row i is the matrix row
+    of read[i]'s symbol, M[class(read[i])][.], and a row of `default` for a read base outside the alphabet (give `mismatch`: such
+    a base scores that against every symbol of the alphabet -- it can equal none).  alphabet, scores: as for validate, or a
+    ScoreMatrix as `alphabet` with scores None.  Returns a list of m rows of n ints."""
+    if isinstance(alphabet, ScoreMatrix) and scores is None:
+        alphabet, scores = alphabet.alphabet, alphabet.scores
+    sym, flat = validate(alphabet, scores)
+    n = len(sym)
+    cls = {canonical(c): k for k, c in enumerate(sym)}
+    rd = read if isinstance(read, (bytes, bytearray)) else read.encode("latin-1")
+    out = []
+    for b in rd:
+        k = cls.get(canonical(b))
+        out.append([int(default)] * n if k is None else flat[k * n:(k + 1) * n])
+    return out
+
+
+def quality_profile(read, quals, alphabet, match, mismatch_of_q):
+    """A quality-aware profile for a mapper: row i scores `match` in the column of read[i]'s symbol and mismatch_of_q(quals[i])
+    in every other column (a mismatch at a Q2 base costs less than one at a Q40 base).  A read base outside the alphabet
+    mismatches every symbol.  quals: one integer per base; mismatch_of_q: a function of it."""
+    sym = _symbols(alphabet)
+    n = len(sym)
+    cls = {canonical(c): k for k, c in enumerate(sym)}
+    rd = read if isinstance(read, (bytes, bytearray)) else read.encode("latin-1")
+    if len(quals) != len(rd):
+        raise ValueError("%d qualities for a read of %d bases" % (len(quals), len(rd)))
+    out = []
+    for b, q in zip(rd, quals):
+        mm = int(mismatch_of_q(q))
+        row = [mm] * n
+        k = cls.get(canonical(b))
+        if k is not None:
+            row[k] = int(match)
+        out.append(row)
+    return out
+
+
 # BLOSUM62 (Henikoff & Henikoff 1992) as NCBI distributes it
 BLOSUM62_TEXT = """\
 #  Matrix made by matblas from blosum62.iij
