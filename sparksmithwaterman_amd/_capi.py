@@ -134,6 +134,11 @@ SYMBOLS = [
     ("swmi_align_batch", C.c_int, [_P, C.POINTER(Params), C.c_char_p, _u64p, C.c_uint32, C.c_char_p, _u64p,
                                    C.c_uint32, C.POINTER(_P)]),
 ]
+# entry points of csrc/swmi_launch.h that answer for a launcher without a launch (no HIP call); include/swmi.h does not declare them.
+# Bound where the library has them: a tool that loads an earlier build (SWMI_LIB) goes without.
+LAUNCH_SYMBOLS = [
+    ("swmi_affine_profile_waves", C.c_uint32, [C.c_uint32, C.c_uint32, C.c_uint32]),
+]
 
 _lib = None
 
@@ -151,6 +156,10 @@ def load():
             f = getattr(lib, name)      # AttributeError if a declared symbol is not exported
             f.restype = res
             f.argtypes = args
+        for name, res, args in LAUNCH_SYMBOLS:
+            if hasattr(lib, name):
+                getattr(lib, name).restype = res
+                getattr(lib, name).argtypes = args
         _lib = lib
     return _lib
 

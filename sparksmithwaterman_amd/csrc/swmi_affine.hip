@@ -1393,6 +1393,19 @@ extern "C" const char *swmi_affine_profile_sweep_name(const AffRun *r, uint32_t 
 // A wavefront's table has `rows` rows of n + 1 dwords, rows = 64 * the rows per lane of the longest read the kernel takes in this
 // launch (the narrow sweep: at most 4); a workgroup gets as many wavefronts, at most AFF_WAVES, as tables fit the LDS beside the
 // 1 KiB of keys.  One table must fit: rows * (n + 1) <= SWMI_PROF_LDS_WORDS, which check_run_params (swmi_run.cpp) has made sure of.
+namespace {
+// the dwords of one wavefront's table in a launch of that shape whose longest read has r_max rows per lane
+inline uint32_t aff_profile_tab_words(uint32_t n, uint32_t r_max, uint32_t shape) {
+    return WAVE * (shape == 0u ? std::min(r_max, 4u) : r_max) * (n + 1u);
+}
+}  // namespace
+extern "C" uint32_t swmi_affine_profile_waves(uint32_t n, uint32_t r_max, uint32_t shape) {
+    if (n < 1u || n > SWMI_MAT_MAX_SYMBOLS || r_max < 1u || r_max > SWMI_AFF_RMAX || shape > 1u) return 0u;
+    const uint32_t tab_words = aff_profile_tab_words(n, r_max, shape);
+    if (tab_words > SWMI_PROF_LDS_WORDS) return 0u;
+    return std::min<uint32_t>(AFF_WAVES, (SWMI_LDS_BYTES - 4u * SWMI_PROF_KEY_WORDS) / (4u * tab_words));
+}
+
 extern "C" hipError_t swmi_launch_affine_profile_sweep(const FillArgs *a, const AffRun *r, const AffProfile *p, uint32_t r_min, uint32_t r_max,
                                                        hipStream_t st) {
     if (a->n_pairs == 0) return hipSuccess;
@@ -1411,10 +1424,9 @@ extern "C" hipError_t swmi_launch_affine_profile_sweep(const FillArgs *a, const 
     const uint32_t nn = p->n + 1u;
     const auto sweep = [&](uint32_t shape) {
         const AffSweepRow *row = aff_profile_sweep_row(*r, shape);
-        const uint32_t rows = WAVE * (shape == 0u ? std::min(r_max, 4u) : r_max);
-        const uint32_t tab_words = rows * nn;
-        if (!row || tab_words > SWMI_PROF_LDS_WORDS) return false;
-        const uint32_t waves = std::min<uint32_t>(AFF_WAVES, (SWMI_LDS_BYTES - 4u * SWMI_PROF_KEY_WORDS) / (4u * tab_words));
+        const uint32_t tab_words = aff_profile_tab_words(p->n, r_max, shape), rows = tab_words / nn;
+        const uint32_t waves = swmi_affine_profile_waves(p->n, r_max, shape);       // (0: the table does not fit)
+        if (!row || !waves) return false;
         AffRun pr = *r;
         pr.mat = p->image;
         pr.nn = nn | rows << 16;

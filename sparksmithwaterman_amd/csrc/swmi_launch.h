@@ -107,6 +107,11 @@ struct AffProfile {
 // The profile sweep a run takes, by name -- null where the launcher below refuses: a run with gap_open2, subopt, hits, end_bonus or
 // a score matrix, and the long shape (shape: 0 narrow, 1 wide).  It calls no HIP function.  For the tests: not part of include/swmi.h.
 extern "C" const char *swmi_affine_profile_sweep_name(const AffRun *r, uint32_t shape);
+// The wavefronts of a workgroup (1 .. 4) the launcher below gives the sweep of that shape in a launch over n symbols whose longest
+// read has r_max rows per lane: min(4, 159 KiB / table), table = 64 * r * (n + 1) int32 with r = r_max, for the narrow sweep
+// min(r_max, 4).  0 where one table exceeds SWMI_PROF_LDS_WORDS or an argument is out of range: no launch.  The launcher calls it, so
+// what a test reads is what a launch uses.  It calls no HIP function.  For the tests: not part of include/swmi.h.
+extern "C" uint32_t swmi_affine_profile_waves(uint32_t n, uint32_t r_max, uint32_t shape);
 // The short shape of a run whose batch has profiles, in place of swmi_launch_affine_sweep (.., 0, ..); r->mat is null.  Every
 // wavefront stages its own read's table, so a workgroup has as many wavefronts (1 .. 4) as tables of the launch's longest read fit
 // the LDS.  The walks are the run's ordinary ones.

@@ -1,7 +1,8 @@
 """Per-read score profiles (swmi_batch_set_read_profiles) without a GPU: the two restatements of
 tests/profile_reference.py against each other; the identity with a score matrix; which kernels the profile launcher gives a run (the
 list AFF_PROFILE_SWEEPS of swmi_affine.hip) -- the test that fails on a library without the feature; the Python helpers; and the
-condition on the grids of tests/profile_cases.py that a kernel which ignores the profile cannot meet."""
+condition on the grids of tests/profile_cases.py that a kernel which ignores the profile cannot meet; the wavefronts per workgroup
+the profile launcher computes (swmi_affine_profile_waves) and what the recipes built on them are built for."""
 import ctypes as C
 import os
 import random
@@ -194,6 +195,159 @@ def test_class_grid_differs_from_plain_scoring(R):
             total += 1
             differ += e[:2] != pc.plain(refs[r], reads[q], name, 0)[:2]
     assert total == 75 and 4 * differ >= 3 * total, (R, differ, total)
+
+
+# ---- the workgroup sizes of the profile launcher ----
+def _waves(n, r_max, shape):
+    from sparksmithwaterman_amd import _capi
+    return _capi.load().swmi_affine_profile_waves(n, r_max, shape)     # AttributeError on a library without the function
+
+
+def test_profile_waves_is_bound():
+    from sparksmithwaterman_amd import _capi
+    assert ("swmi_affine_profile_waves", C.c_uint32, [C.c_uint32] * 3) in _capi.LAUNCH_SYMBOLS
+    assert "swmi_affine_profile_waves" not in [s[0] for s in _capi.SYMBOLS]         # (include/swmi.h does not declare it)
+
+
+def test_profile_waves_table():
+    """the seven configurations of tests/profile_cases.py: 4, 3, 2, 1, 1, 2, 3 wavefronts per workgroup"""
+    assert [c[2] for c in pc.WAVE_CONFIGS.values()] == [4, 3, 2, 1, 1, 2, 3]
+    for name, (n, R, waves, shape) in pc.WAVE_CONFIGS.items():
+        assert _waves(n, R, shape) == waves, name
+        assert (shape == 0) == (R <= 4), name
+
+
+def test_profile_waves_bounds():
+    """0 where one table does not fit SWMI_PROF_LDS_WORDS = 32768 dwords (what check_run_params refuses), and for arguments the
+    launcher refuses; the narrow sweep's table has at most 256 rows whatever the launch's longest read"""
+    for n, R, fits in ((31, 16, True), (32, 16, False), (64, 7, True), (64, 8, False), (64, 16, False), (1, 16, True)):
+        assert (_waves(n, R, 1) > 0) == fits == (64 * R * (n + 1) <= 32768), (n, R)
+    for n in (1, 15, 64):
+        assert [_waves(n, R, 0) for R in range(4, 17)] == [_waves(n, 4, 0)] * 13
+    assert _waves(0, 4, 0) == _waves(65, 4, 0) == _waves(5, 0, 0) == _waves(5, 17, 1) == _waves(5, 4, 2) == 0
+    # every admitted size: as many tables as fit 159 KiB, at most four
+    for n in range(1, 65):
+        for R in range(1, 17):
+            table = 64 * R * (n + 1) * 4
+            assert _waves(n, R, 1) == (min(4, (159 << 10) // table) if table <= 32768 * 4 else 0), (n, R)
+
+
+@pytest.mark.parametrize("config", list(pc.WAVE_CONFIGS))
+def test_wave_grid_geometry(config):
+    """the five lengths of the class, references of 50 to 70 bases over the whole alphabet with bytes outside it and lower-case
+    letters, and a pair count that is no multiple of the wavefronts of a workgroup and at least twice them"""
+    n, R, waves, _ = pc.WAVE_CONFIGS[config]
+    alphabet, refs, reads, profiles = pc.wave_grid(config)
+    assert (alphabet, R) == pc.wave_config(config) and len(alphabet) == n == len({gr.upper(c) for c in alphabet})
+    assert [len(q) for q in reads] == pc.class_lengths(R) == [len(p) for p in profiles] and len(reads[0]) == 64 * R - 3
+    assert R != 16 or 1024 in [len(q) for q in reads]
+    assert all(len(row) == n for p in profiles for row in p)
+    pairs = len(refs) * len(reads)
+    assert pairs % waves != 0 or waves == 1
+    assert pairs >= 2 * waves and pairs >= 5
+    for ref in refs:
+        assert 50 <= len(ref) <= 70
+        assert any(pc.is_outside(c, alphabet) for c in ref) and any(c.islower() for c in ref)
+    used = {gr.upper(c) for ref in refs for c in ref if not pc.is_outside(c, alphabet)}
+    assert len(used) >= min(n, 8) and not used <= set(pc.ALPHABET)           # columns beyond ACGTN's five are read
+
+
+def test_wave_grid_differs_from_plain_scoring():
+    """the profile decides: every pair of the one-wavefront configuration scores differently under match / mismatch"""
+    alphabet, refs, reads, profiles = pc.wave_grid("n64_R7")
+    exp = pc.wave_expected("n64_R7", "local", 0)
+    assert all(exp[(0, q)][:2] != pc.plain(refs[0], reads[q], "local", 0)[:2] for q in range(5))
+
+
+@pytest.mark.parametrize("variant", list(pc.MIXED))
+def test_mixed_classes_need_both_kernels(variant):
+    n, lengths, ref_lengths, (narrow, wide) = pc.MIXED[variant]
+    alphabet, refs, reads, profiles = pc.mixed_classes(variant)
+    assert len(alphabet) == n and len(refs) == 3 and [len(r) for r in refs] == list(ref_lengths)
+    assert [len(q) for q in reads] == list(lengths) + [pc.MIXED_TWIN] * 2 == [len(p) for p in profiles]
+    assert lengths[:8] == (1, 64, 65, 0, 256, 257, 300, 130) and sorted(lengths) != list(lengths)
+    rs = [pc.rows_per_lane(m) for m in lengths if m]
+    r_min, r_max = min(rs), max(rs)
+    assert r_min <= 4 < r_max
+    assert (_waves(n, r_max, 0), _waves(n, r_max, 1)) == (narrow, wide) == {"n15": (4, 2), "n64": (2, 1)}[variant]
+    # the two equal reads carry different profiles, and the difference shows
+    assert reads[10] == reads[11] and profiles[10] != profiles[11]
+    exp = pc.mixed_expected(variant, "local")
+    assert all(exp[(r, 10)][:2] != exp[(r, 11)][:2] for r in range(3))
+    # the empty read: no alignments in any mode
+    for name in pc.MODES:
+        assert all(pc.mixed_expected(variant, name)[(r, 3)] == (0, [], []) for r in range(3)), name
+    assert set(pc.MIXED_TIE) == set(pc.MODES) and set(pc.MIXED_TIE.values()) == {0, 1}
+    for ref in refs:
+        assert any(pc.is_outside(c, alphabet) for c in ref) and any(c.islower() for c in ref)
+
+
+def test_mixed_classes_chunk_with_another_r_max():
+    """under MIXED_CAP the n = 15 batch takes two launches, and the second has reads of classes 1 to 5 only: its wide sweep gets
+    320-row tables and 4 wavefronts where the whole batch's gets 1024 rows and 2"""
+    alphabet, refs, reads, _ = pc.mixed_classes("n15")
+    plan = pc.launches(refs, reads, pc.MIXED_CAP)
+    assert [len(ch) for ch in plan] == [24, 9] and sum(len(ch) for ch in plan) == 3 * 11
+    r_max = [max(pc.rows_per_lane(len(reads[q])) for _, q in ch) for ch in plan]
+    r_min = [min(pc.rows_per_lane(len(reads[q])) for _, q in ch) for ch in plan]
+    assert r_max == [16, 5] and r_min == [1, 1]
+    assert [_waves(15, r, 1) for r in r_max] == [2, 4]
+    assert pc.launches(refs, reads, 1 << 40) == [[p for ch in plan for p in ch]]
+    # dir_words is swmi_aff_pair_dir_words: 1024 x 60 is 16 blocks of 16 x 64 dwords, 1 x 1 one block of 64
+    assert pc.dir_words(1024, 60) == 16 * 1024 and pc.dir_words(1, 1) == 64 and pc.dir_words(65, 10) == (10 + 33 - 1 + 7) // 8 * 128
+
+
+def test_periodic_wide_case():
+    """score 192 in 239 tied maximum cells, in both tie modes; the four other pairs stay within cell_cap = 2"""
+    alphabet, ref, reads, profiles = pc.periodic_wide_case()
+    assert alphabet == pc.alphabet_of(15) and ref == "ACGT" * 12 and reads[2] == "ACGT" * 250
+    assert [pc.rows_per_lane(len(q)) for q in reads] == [1, 2, 16, 3, 3]
+    for tie in (0, 1):
+        score, alns, cells = pc.want(ref, reads[2], profiles[2], "local", tie, pc.SC, alphabet)
+        assert score == 192 and len(cells) == len(alns) == 239
+        for q in (0, 1, 3, 4):
+            other = pc.want(ref, reads[q], profiles[q], "local", tie, pc.SC, alphabet)
+            assert other[0] > 0 and 1 <= len(other[2]) <= 2, q
+    assert (_waves(15, 16, 1), _waves(15, 3, 0)) == (2, 4)
+
+
+def test_alphabet_edges():
+    """the two restatements agree on every pair; the row strides are 2, 3, 64, 65 and 7; both cases of e-acute reach its column"""
+    cases = pc.alphabet_edges()
+    assert [len(c[0]) + 1 for c in cases] == [2, 3, 64, 65, 7]
+    for alphabet, refs, reads, profiles in cases:
+        assert tuple(len(q) for q in reads) == pc.EDGE_READS == (1, 63, 64, 65)
+        assert len({gr.upper(c) for c in alphabet}) == len(alphabet)
+        for name in ("local", "global"):
+            mode, extend, overlap = pc.MODES[name]
+            for r, ref in enumerate(refs):
+                for q, read in enumerate(reads):
+                    a = pr.align_scalar(ref, read, alphabet, profiles[q], pc.SC, mode, extend, overlap, 0, cells=True)
+                    assert a == pc.want(ref, read, profiles[q], name, 0, pc.SC, alphabet), (alphabet, name, r, q)
+    alphabet, refs, reads, profiles = cases[-1]
+    assert alphabet == "AC\xe9\xff\xf7\xd7"
+    for ref in refs:
+        assert all(c in ref for c in "\xc9\xe9\xff\xdf\xb5\xf7\xd7")
+    assert [pc.is_outside(c, alphabet) for c in "\xc9\xe9\xff\xdf\xb5\xf7\xd7"] == [False, False, False, True, True, False, False]
+    cls = pr._classes(alphabet)
+    assert cls[0xC9] == cls[0xE9] == 2 and cls[0xFF] == 3 and cls[0xF7] == 4 and cls[0xD7] == 5 and cls[0xDF] == cls[0xB5] == -1
+    # e-acute's column changed: a score changes; and with the upper-case bytes taken out of the reference it changes in another way
+    q = 3
+    bumped = [row[:2] + [row[2] + 40] + row[3:] for row in profiles[q]]
+    base = [pc.want(ref, reads[q], profiles[q], "local", 0, pc.SC, alphabet)[0] for ref in refs]
+    moved = [pc.want(ref, reads[q], bumped, "local", 0, pc.SC, alphabet)[0] for ref in refs]
+    lower_only = [pc.want(ref.replace("\xc9", "\xdf"), reads[q], bumped, "local", 0, pc.SC, alphabet)[0] for ref in refs]
+    assert moved != base and lower_only != moved
+
+
+def test_mismatch_case_depends_on_mismatch():
+    refs, reads, profiles = pc.mismatch_case()
+    assert all(any(pc.is_outside(c, pc.ALPHABET) for c in ref) for ref in refs)
+    assert pc.SC_MISMATCH[0][1] != pc.SC_MISMATCH[1][1] and pc.SC_MISMATCH[0][::2] == pc.SC_MISMATCH[1][::2]
+    for name in ("local", "global"):
+        a, b = ({(r, q): pc.want(refs[r], reads[q], profiles[q], name, 0, sc) for r in range(2) for q in range(3)} for sc in pc.SC_MISMATCH)
+        assert sum(a[k][0] != b[k][0] for k in a) >= 3, name     # half the scores or more differ
+    assert {pc.rows_per_lane(len(q)) for q in reads} == {1, 2, 5}       # the narrow and the wide sweep
 
 
 def test_protein_pairs_and_the_periodic_case():

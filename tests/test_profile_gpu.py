@@ -6,6 +6,17 @@ both strings and its maximum cell.  Batch.set_read_profiles is what fails withou
   [fit_|global_|extend_|overlap_]profile_kernel        1 .. 4     test_rows_per_lane (R 1 .. 4), test_matrix_parity, test_ties_beyond_cell_cap,
                                                                   test_lifecycle*, test_payloads, test_path_bound
   [..]profile_wide_kernel                              5 .. 16    test_rows_per_lane (R 5 .. 16), test_matrix_parity, test_bounds*, test_chunking
+
+  wavefronts per workgroup (swmi_affine_profile_waves)            run by
+  4                                                               every test above but test_bounds*; test_wavefronts_per_workgroup[n8_R16]
+  3                                 wide                          test_wavefronts_per_workgroup[n9_R16]
+                                    narrow                        test_wavefronts_per_workgroup[n64_R3]
+  2                                 wide                          test_wavefronts_per_workgroup[n15_R16], test_rerun_in_a_wide_class (the re-run)
+                                    narrow                        test_wavefronts_per_workgroup[n64_R4]
+  1                                 wide                          test_wavefronts_per_workgroup[n31_R16, n64_R7], test_bounds*
+  narrow 4 + wide 2, one pair array                               test_mixed_classes_in_one_batch (n = 15), test_rerun_in_a_wide_class (first launch)
+  narrow 2 + wide 1, one pair array                               test_mixed_classes_in_one_batch (n = 64)
+  narrow 4 + wide 2, then narrow 4 + wide 4 (another r_max)       test_mixed_classes_chunked
 The inputs come from tests/profile_cases.py, which states what each is built for; tests/test_profile_cpu.py holds them to it."""
 import ctypes as C
 import random
@@ -13,6 +24,7 @@ import random
 import pytest
 
 import sparksmithwaterman_amd as sw
+from sparksmithwaterman_amd import _capi
 from sparksmithwaterman_amd import matrix as mx
 
 import affine_gpu_util as u
@@ -299,7 +311,114 @@ def test_payloads(ctx, name):
         b.free()
 
 
-# 7 -- the path bound takes the largest entry
+# 7 -- the workgroup sizes the launcher computes: min(4, 159 KiB / table) wavefronts, table = 64 r (n + 1) int32
+#   configuration   table                      wavefronts   pairs   workgroups (the last one partial)
+#   n8_R16          1024 x  9:  36 KiB         4            15      4
+#   n9_R16          1024 x 10:  40 KiB         3            10      4
+#   n15_R16         1024 x 16:  64 KiB         2            15      8
+#   n31_R16         1024 x 32: 128 KiB         1             5      5
+#   n64_R7           448 x 65: 114 KiB         1             5      5
+#   n64_R4           256 x 65:  65 KiB         2 (narrow)   15      8
+#   n64_R3           192 x 65:  49 KiB         3 (narrow)   10      4
+def _waves(n, r_max, shape):
+    return _capi.load().swmi_affine_profile_waves(n, r_max, shape)
+
+
+@pytest.mark.parametrize("name", list(pc.MODES))
+@pytest.mark.parametrize("config", list(pc.WAVE_CONFIGS))
+def test_wavefronts_per_workgroup(ctx, config, name):
+    """a launcher whose grid counts four wavefronts to a workgroup, or a kernel that finds its pair so, skips pairs wherever there
+    are fewer: every pair of the launch is checked in full"""
+    n, R, waves, shape = pc.WAVE_CONFIGS[config]
+    assert _waves(n, R, shape) == waves
+    alphabet, refs, reads, profiles = pc.wave_grid(config)
+    for tie in (0, 1):
+        b = _run(ctx, refs, reads, profiles, name, tie, alphabet=alphabet)
+        _check(b, refs, reads, pc.wave_expected(config, name, tie), name)
+        b.free()
+
+
+def _mixed_waves(variant, reads):
+    rs = [pc.rows_per_lane(len(q)) for q in reads if q]
+    assert min(rs) <= 4 < max(rs)
+    return _waves(pc.MIXED[variant][0], max(rs), 0), _waves(pc.MIXED[variant][0], max(rs), 1)
+
+
+@pytest.mark.parametrize("name", list(pc.MODES))
+def test_mixed_classes_in_one_batch(ctx, name):
+    """the narrow and the wide kernel over one pair array, each with its own workgroup size and table size: 4 and 2 wavefronts
+    (n = 15), 2 and 1 (n = 64).  The empty read's pairs have no alignments; the two equal reads get the results of their own
+    profiles"""
+    for variant in pc.MIXED:
+        alphabet, refs, reads, profiles = pc.mixed_classes(variant)
+        assert _mixed_waves(variant, reads) == pc.MIXED[variant][3]
+        exp = pc.mixed_expected(variant, name)
+        b = _run(ctx, refs, reads, profiles, name, pc.MIXED_TIE[name], alphabet=alphabet)
+        assert b.timing().fill_launches == 1
+        _check(b, refs, reads, exp, name)
+        for r in range(len(refs)):
+            empty, twin = r * len(reads) + 3, r * len(reads) + 10
+            assert (b.score(empty), b.n_alignments(empty)) == (exp[(r, 3)][0], (0, 0)) and exp[(r, 3)][1] == []
+            assert reads[10] == reads[11] and exp[(r, 10)][:2] != exp[(r, 11)][:2]
+            assert (b.score(twin), b.score(twin + 1)) == (exp[(r, 10)][0], exp[(r, 11)][0])
+        b.free()
+
+
+def test_mixed_classes_chunked(ctx):
+    """the n = 15 batch under max_workspace_bytes = 1 MiB: two launches, the second with reads of classes 1 to 5 only -- its wide
+    sweep has 320-row tables and 4 wavefronts where the first launch's has 1024 rows and 2 (tests/test_profile_cpu.py holds the
+    restated plan to that)"""
+    alphabet, refs, reads, profiles = pc.mixed_classes("n15")
+    tie = pc.MIXED_TIE["fit"]
+    plan = pc.launches(refs, reads, pc.MIXED_CAP)
+    need = 4 * sum(pc.dir_words(len(reads[q]), len(refs[r])) for ch in plan for r, q in ch)
+    b = _run(ctx, refs, reads, profiles, "fit", tie, alphabet=alphabet)
+    assert b.timing().fill_launches == 1 and b.timing().dir_bytes == need > pc.MIXED_CAP
+    b.free()
+    b = _run(ctx, refs, reads, profiles, "fit", tie, alphabet=alphabet, max_workspace_bytes=pc.MIXED_CAP)
+    assert b.timing().fill_launches == len(plan) == 2 and b.timing().dir_bytes == need
+    _check(b, refs, reads, pc.mixed_expected("n15", "fit"), "fit")
+    b.free()
+
+
+@pytest.mark.parametrize("tie", [0, 1])
+def test_rerun_in_a_wide_class(ctx, tie):
+    """the exact-size re-run has its own r_max, and so its own workgroup size: one pair of class 16 in a launch of its own (the wide
+    sweep alone, 2 wavefronts), after a first launch over classes 1 to 16"""
+    alphabet, ref, reads, profiles = pc.periodic_wide_case()
+    assert (_waves(15, 16, 1), _waves(15, 16, 0)) == (2, 4)
+    b = _run(ctx, [ref], reads, profiles, "local", tie, alphabet=alphabet, cell_cap=2)
+    assert b.timing().rerun_pairs == 1
+    for q, want in enumerate(pc.periodic_wide_expected(tie)):
+        u.check_pair(b, q, want, 0, q)
+    assert b.score(2) == 192 and b.n_alignments(2) == (239, 0)
+    b.free()
+
+
+def test_alphabet_edges(ctx):
+    """row strides 2, 3, 64 and 65 of the staging loop against reads of 1, 63, 64 and 65 rows, and an alphabet above 0x7F"""
+    for k, (alphabet, refs, reads, profiles) in enumerate(pc.alphabet_edges()):
+        for name in ("local", "global"):
+            b = _run(ctx, refs, reads, profiles, name, 0, alphabet=alphabet)
+            _check(b, refs, reads, pc.edges_expected(k, name), name)
+            b.free()
+
+
+def test_mismatch_is_staged_per_run(ctx):
+    """one batch, one set of profiles, two runs that differ in mismatch: column n of every table is the run's"""
+    refs, reads, profiles = pc.mismatch_case()
+    for name in ("local", "global"):
+        _set(ctx, name, pc.SC)
+        b = ctx.upload(refs, reads).set_read_profiles(pc.ALPHABET, profiles)
+        for k in (0, 1, 0):
+            assert pc.SC_MISMATCH[k][3] == pc.SC[3]
+            b.run(sw.make_params(pc.SC_MISMATCH[k][:3]))
+            assert b.pipeline_mode() == 3
+            _check(b, refs, reads, pc.mismatch_expected(name, k), name)
+        b.free()
+
+
+# 8 -- the path bound takes the largest entry
 def test_path_bound(ctx):
     """all entries <= 0: a local pair is degenerate.  Entries of 50 under match 1, gap -1: a 42-move path of score 60 where the bound
     read with match alone allows 2 + 2 moves (the analogue of test_matrix_gpu.py::test_path_longer_than_the_match_bound)"""
