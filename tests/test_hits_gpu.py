@@ -6,10 +6,11 @@ On every pair of every test: entry 1 is Batch.subopt(pair), and entry 0's cell i
 the run has alignments.  The cases are chosen where the row carry can go wrong -- every rows-per-lane class with the storing lane
 below and at 63, the strip seam, the band's windows, a maximum held by several rows of one lane, of two lanes, of two strips -- and
 where the rounds can: equal secondaries, the strict mask around an earlier hit, a list shorter than K, K = 1; then the host
-machinery around the per-pair array."""
+machinery around the per-pair array.  Where the rounds of sw_hits_kernel over a row can go wrong -- step edges, the lookahead, row
+ends, sixteen entries, an earlier entry across a step edge -- is tests/test_pick_gpu.py's; the check helpers are shared with it
+(tests/pick_gpu_util.py)."""
 import random
 
-import numpy as np
 import pytest
 
 import sparksmithwaterman_amd as sw
@@ -18,6 +19,7 @@ from sparksmithwaterman_amd import matrix as M
 
 import affine_gpu_util as u
 import hits_reference as hr
+from pick_gpu_util import weaken, planted, hits_expect as expect, hits_check_pair as check_pair, hits_check as check, hits_run_and_check as run_and_check
 
 pytestmark = pytest.mark.gpu
 
@@ -34,68 +36,6 @@ def ctx():
     c = sw.Context(0)
     yield c
     c.close()
-
-
-def weaken(read, k, alphabet="ACGT"):
-    """the read with k substitutions at evenly spaced places (each base replaced by the next one of the alphabet)"""
-    out = list(read)
-    for x in range(k):
-        p = (2 * x + 1) * len(read) // (2 * k)
-        out[p] = alphabet[(alphabet.index(out[p]) + 1) % len(alphabet)]
-    return "".join(out)
-
-
-def planted(rng, read, gaps, loads):
-    """random stretches (lengths `gaps`, one more than copies) around copies of the read with `loads` substitutions each; the
-    reference and the 1-based end column of every copy"""
-    ref, ends = u.rand(rng, gaps[0]), []
-    for g, load in zip(gaps[1:], loads):
-        ref += weaken(read, load)
-        ends.append(len(ref))
-        ref += u.rand(rng, g)
-    return ref, ends
-
-
-def expect(refs, reads, sc, w, k, band=0, matrix=None):
-    return {(r, q): hr.hits_numpy(refs[r], reads[q], sc, w, k, band, matrix) for r in range(len(refs)) for q in range(len(reads))}
-
-
-def check_pair(b, pair, want, k, what=None, cells=True):
-    got = b.hits(pair)
-    assert got == want, (what, pair, got, want)
-    s2, e2 = b.subopt(pair)
-    if len(got) >= 2:
-        assert (got[1][0], got[1][2]) == (s2, e2), (what, pair)
-    elif k >= 2:
-        assert (s2, e2) == (0, 0), (what, pair)
-    if got:
-        assert b.score(pair) == got[0][0], (what, pair)
-        if cells:
-            assert got[0][1:] in [a[-1] for a in b.alignments(pair, with_cell=True)], (what, pair)
-    else:
-        assert b.score(pair) == 0
-
-
-def check(b, refs, reads, exp, k, what=None, cells=True):
-    """every pair through the per-pair accessor, then the whole batch through the other one"""
-    n = len(refs) * len(reads)
-    for r in range(len(refs)):
-        for q in range(len(reads)):
-            check_pair(b, r * len(reads) + q, exp[(r, q)], k, (what, r, q, len(refs[r]), len(reads[q])), cells)
-    cnt, sc, ei, ej = b.hits_all()
-    assert cnt.shape == (n,) and sc.shape == ei.shape == ej.shape == (n, 16) and sc.dtype == np.int32
-    for r in range(len(refs)):
-        for q in range(len(reads)):
-            pair, want = r * len(reads) + q, exp[(r, q)]
-            assert int(cnt[pair]) == len(want)
-            assert [(int(sc[pair, x]), int(ei[pair, x]), int(ej[pair, x])) for x in range(16)] == want + [(0, 0, 0)] * (16 - len(want))
-
-
-def run_and_check(ctx, refs, reads, sc, w, k, band=None, matrix=None, tie=0, exp=None, cells=True, **options):
-    exp = exp or expect(refs, reads, sc, w, k, band or 0, matrix and (matrix.alphabet, matrix.scores))
-    b = u.run(ctx, refs, reads, sc, tie, LOCAL, band, matrix=matrix, subopt=w, hits=k, **options)
-    check(b, refs, reads, exp, k, (w, k, band, tie), cells and not options.get("scores_only"))
-    return b, exp
 
 
 # ---- the row carry in every sweep ----------------------------------------------------------------------------------------------

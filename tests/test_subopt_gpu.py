@@ -6,7 +6,8 @@ The cases are chosen where the column maxima can go wrong: every rows-per-lane c
 8-column blocks' edges, the mask's strict '>' on either side, tied maxima, the seam between two strips with the runner-up on either
 side of it, the band's windows (a column left of a later window, a copy outside the band, the columns right of the last window),
 and the host machinery around the per-pair array: zero-copy or not, several launches, the exact-size re-run, async, streams, pair
-lists."""
+lists.  Where the pass of sw_subopt_kernel over a row can go wrong -- step edges, the lookahead, row ends, dense maxima, partly filled
+workgroups -- is tests/test_pick_gpu.py's; the check helpers are shared with it (tests/pick_gpu_util.py)."""
 import random
 
 import pytest
@@ -17,6 +18,7 @@ from sparksmithwaterman_amd import matrix as M
 
 import affine_gpu_util as u
 import subopt_reference as sr
+from pick_gpu_util import weaken, planted, subopt_expect as expect, subopt_check as check, subopt_run_and_check as run_and_check
 
 pytestmark = pytest.mark.gpu
 
@@ -32,49 +34,6 @@ def ctx():
     c = sw.Context(0)
     yield c
     c.close()
-
-
-def weaken(read, k, alphabet="ACGT"):
-    """the read with k substitutions at evenly spaced places (each base replaced by the next one of the alphabet)"""
-    out = list(read)
-    for x in range(k):
-        p = (2 * x + 1) * len(read) // (2 * k)
-        out[p] = alphabet[(alphabet.index(out[p]) + 1) % len(alphabet)]
-    return "".join(out)
-
-
-def planted(rng, read, gaps, loads):
-    """random stretches (lengths `gaps`, one more than copies) around copies of the read with `loads` substitutions each; the
-    reference and the 1-based end column of every copy"""
-    ref, ends = u.rand(rng, gaps[0]), []
-    for g, load in zip(gaps[1:], loads):
-        ref += weaken(read, load)
-        ends.append(len(ref))
-        ref += u.rand(rng, g)
-    return ref, ends
-
-
-def expect(refs, reads, sc, w, band=0, matrix=None):
-    return {(r, q): sr.subopt_numpy(refs[r], reads[q], sc, w, band, matrix) for r in range(len(refs)) for q in range(len(reads))}
-
-
-def check(b, refs, reads, exp, what=None):
-    """every pair: score, score2 and end2, through the per-pair and the whole-batch accessor"""
-    s2, e2 = b.subopts()
-    assert len(s2) == len(e2) == len(refs) * len(reads)
-    for r in range(len(refs)):
-        for q in range(len(reads)):
-            pair = r * len(reads) + q
-            got = (b.score(pair),) + b.subopt(pair)
-            assert got == exp[(r, q)], (what, r, q, len(refs[r]), len(reads[q]), got, exp[(r, q)])
-            assert (int(s2[pair]), int(e2[pair])) == got[1:], (what, pair)
-
-
-def run_and_check(ctx, refs, reads, sc, w, band=None, matrix=None, tie=0, exp=None, **options):
-    exp = exp or expect(refs, reads, sc, w, band or 0, matrix and (matrix.alphabet, matrix.scores))
-    b = u.run(ctx, refs, reads, sc, tie, LOCAL, band, matrix=matrix, subopt=w, **options)
-    check(b, refs, reads, exp, (w, band, tie))
-    return b, exp
 
 
 # ---- the sweep: rows per lane, the storing lane, block edges -----------------------------------------------------------------
